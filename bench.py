@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — 6 kbp windows classified/sec on N MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU.  Under a launcher (torch.distributed.run is only that: RANK / LOCAL_RANK / WORLD_SIZE /
@@ -31,11 +31,15 @@ table of all 14-mers, head A from 9-mer tables: genomad_amd/csrc/gnn_fused_tk.hi
 timed, `kmer_tables` in the line says how long that took - else the default "f16x3tc"; --no-kmer-tables measures the latter.
 `roofline.table_reads` lists what f16x3tk reads instead of computing (half of the algorithmic FLOPs) and the bytes that costs.
 
+A plain run does only what `value` needs: it sets up (weights, engine, communicator, k-mer tables, HBM-resident input), warms
+up, times the K steps, writes --dump-outputs DIR (the scores of the job's last step, DIR/scores.npy) and prints the line.
+Everything below is measured and checked with --full only.
+
 After the timed region (untimed) every window of the job is classified once more with the exact-f32 device path and,
 bit for bit, through the synchronous entry point: `parity` reports max |dscore| over ALL timed windows, how many exceed
 1e-4 and 5e-5, and the process exits non-zero if any window exceeds the 1e-4 tolerance or any bit differs.
 
-At N = 1 the default line also carries two untimed blocks (<= 25 s together, never part of `value`):
+At N = 1 the --full line also carries two untimed blocks (<= 25 s together, never part of `value`):
   main_e2e      the drop-in entry point genomad_amd.nn_classification.main() with the reference's signature
                 (nn_classification.py:21-30) on a config-1-shaped FASTA (8 records, ~5.4 Mbp, 906 windows; TSV rows of the seven
                 plasmids against the oracle chain formatted like :344-348) and on a ~600 MB synthetic FASTA written to the temp
@@ -45,7 +49,7 @@ At N = 1 the default line also carries two untimed blocks (<
 A failure of any rank (exception, signal from the launcher, a stage that runs into its time-out) prints ONE JSON line with "error",
 the rank, the stage it was in and the last library error, and exits non-zero.
 
-Extra objects in the JSON line:
+Extra objects in the --full JSON line (besides `parity`, `steps_verified`, the golden comparison and the per-rank timings):
   roofline      dominant kernel (fused front end): algorithmic FLOP per launch / HIP-event duration measured
                 live on the library's stream, against the dense bf16/f16 MFMA peak (2.5 PFLOP/s)
   cpu_baseline  the numpy restatement of the reference (oracle/, reference-faithful mode: explicit one-hot,
@@ -87,6 +91,25 @@ DTYPE_TEXT = {"f16c6": "f16 MFMA + MX-fp6 (e2m3, both operands block scaled) cor
                          "with split-f16 MFMA, 3 products per operand pair, f32 accumulate; head B's y @ w_v direct; logits GEMM split-f16 x 3, "
                          "dense head exact f32)",
               "bf16x3": "bf16x3 (split-bf16 MFMA, 3 passes, f32 accumulate)", "f32": "f32"}
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6                       # --dump-outputs: all files together
+
+
+def dump_outputs(directory: str, **arrays):
+    """--dump-outputs: every array as DIR/<name>.npy, float64 as it is and anything else as float32.  An array that would take the
+    files past DUMP_LIMIT_BYTES keeps a fixed, seeded sample of its rows (in row order), so that two builds run with the same
+    arguments write the same rows."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(len(arrays), 1) - 4096       # room for the .npy header
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > budget:
+            keep = budget // max(a[:1].nbytes, 1)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def cpu_baseline(weights, sample: int, batch: int = 128, budget_s: float = 40.0):
@@ -637,10 +660,11 @@ def main():
                          "instead of the synchronous gnn_classify_dev that main() uses.  Measured equal for the default arithmetic "
                          "(141.4 vs 141.1 k windows/s at 2048 windows per step: the kernel is power-bound, the overlapped back end "
                          "costs the front end what it saves), +8-10 %% for the opt-in f16c6 at that step size")
-    ap.add_argument("--check", default="all", choices=["all", "golden", "none"],
+    ap.add_argument("--check", default=None, choices=["all", "golden", "none"],
                     help="untimed parity pass: 'all' = every timed window against the exact-f32 device path (+ the golden "
-                         "file), 'golden' = only the committed reference-graph scores of the first 10 000 windows")
-    ap.add_argument("--cpu-sample", type=int, default=1024, help="windows for the CPU baseline (0 = skip)")
+                         "file), 'golden' = only the committed reference-graph scores of the first 10 000 windows "
+                         "(default: 'all' with --full, else 'none')")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="windows for the CPU baseline (0 = skip; default: 1024 with --full, else 0)")
     ap.add_argument("--kernel", default="classify", choices=["classify", "encoder"],
                     help="'encoder' benches the stand-alone byte->one-hot HBM kernel instead")
     ap.add_argument("--onehot-dtype", default="u8", choices=["u8", "bf16", "f32"])
@@ -667,10 +691,26 @@ def main():
                          "with a 1-rank run of the same job bit for bit)")
     ap.add_argument("--no-encoder", action="store_true", help="skip the encoder block of the classification line (untimed, < 0.2 s)")
     ap.add_argument("--no-extras", action="store_true", help="skip the untimed main_e2e and metagenome blocks of the N = 1 line (~25 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline figure as well: the CPU baseline, the untimed parity pass and "
+                         "the bit-for-bit re-run of every step, the golden comparison, the roofline with its MFMA probes, per-rank "
+                         "timings and the isolated gather, the encoder block and, at N = 1, the main_e2e and metagenome blocks.  Without "
+                         "it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy (float32): "
+                         "scores.npy = the (windows of the job's last step, 3) class scores in job order (the windows workload; "
+                         "contig_scores.npy = the per-contig scores for --workload metagenome); a larger output than "
+                         f"{DUMP_LIMIT_BYTES // 10**6} MB is cut to a fixed, seeded sample of its rows")
     ap.add_argument("--share-devices", action="store_true",
                     help="testing aid for boxes with fewer GPUs than ranks: rank r uses device r mod (visible devices), so the "
                          "spawn and the RCCL bootstrap run as far as RCCL's own duplicate-device check")
     args = ap.parse_args()
+    if args.cpu_sample is None:
+        args.cpu_sample = 1024 if args.full else 0
+    if args.check is None:
+        args.check = "all" if args.full else "none"
+    if args.dump_outputs and args.kernel == "encoder":
+        sys.exit("--dump-outputs: the stand-alone encoder's one-hot output is not dumped; use it with --kernel classify")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # a plain process asked for N GPUs: become the launcher of N ranks of this same command line
@@ -712,9 +752,11 @@ def main():
     STATE["rccl_ranks"] = int(rccl_ranks.value)
     assert rccl_ranks.value == world and rccl_rank.value == rank
     # which physical GPU every rank is bound to (PCI bus id): two ranks on one device are visible in the line
-    my_dev = (eng.pci_bus_id() if hasattr(eng, "pci_bus_id") else f"fake:{local_rank}").encode()
-    gathered_dev_ids = sharding.gather_bytes(comm, my_dev)                 # a collective: every rank calls it, rank 0 gets the list
-    per_rank_device = [b.decode() for b in gathered_dev_ids] if gathered_dev_ids is not None else None
+    per_rank_device = None
+    if args.full:
+        my_dev = (eng.pci_bus_id() if hasattr(eng, "pci_bus_id") else f"fake:{local_rank}").encode()
+        gathered_dev_ids = sharding.gather_bytes(comm, my_dev)             # a collective: every rank calls it, rank 0 gets the list
+        per_rank_device = [b.decode() for b in gathered_dev_ids] if gathered_dev_ids is not None else None
 
     def barrier():
         eng.sync()
@@ -756,28 +798,31 @@ def main():
         eng.synth_windows_dev(rank * wps_enc, wps_enc, bases.ptr)
         for _ in range(max(args.warmup, 1)):
             _lib.check(eng.lib.gnn_onehot_dev(eng.ctx, bases.ptr, wps_enc, code, out.ptr))
-        eng.profile_enable(True)
-        eng.profile_reset()
+        if args.full:
+            eng.profile_enable(True)
+            eng.profile_reset()
         barrier()
         t0 = time.perf_counter()
         for _ in range(K):
             _lib.check(eng.lib.gnn_onehot_dev(eng.ctx, bases.ptr, wps_enc, code, out.ptr))
         barrier()
         dt = max_over_ranks(time.perf_counter() - t0)
-        ms, launches = eng.profile_get(_lib.K_ENCODER)
         if rank == 0:
-            per = ENCODER_BYTES[args.onehot_dtype] * wps_enc
-            gbs = per * launches / (ms * 1e-3) / 1e9
-            print(json.dumps({
+            line = {
                 "metric": "6 kbp windows one-hot encoded/sec (stand-alone encoder kernel)",
                 "value": round(world * wps_enc * K / dt, 1), "unit": "windows/s", "n_gpus": world, "steps": K,
                 "warmup": args.warmup, "ms_per_step": round(dt / K * 1e3, 4), "higher_is_better": True,
                 "scaling": "weak", "vs_baseline": None, "dtype": args.onehot_dtype, "data": "synthetic",
-                "config": {"workload": f"{wps_enc} synthetic 6 kbp windows per step -> one-hot depth 257 ({args.onehot_dtype})"},
-                "roofline": {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                             "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": None,
-                             "kernel": "onehot_kernel", "bytes_per_launch": per,
-                             "avg_launch_ms": round(ms / max(launches, 1), 5)}}))
+                "config": {"workload": f"{wps_enc} synthetic 6 kbp windows per step -> one-hot depth 257 ({args.onehot_dtype})"}}
+            if args.full:
+                ms, launches = eng.profile_get(_lib.K_ENCODER)
+                per = ENCODER_BYTES[args.onehot_dtype] * wps_enc
+                gbs = per * launches / (ms * 1e-3) / 1e9
+                line["roofline"] = {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                    "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": None,
+                                    "kernel": "onehot_kernel", "bytes_per_launch": per,
+                                    "avg_launch_ms": round(ms / max(launches, 1), 5)}
+            print(json.dumps(line))
         return
 
     if args.workload == "metagenome":
@@ -804,8 +849,9 @@ def main():
 
         for _ in range(min(args.warmup, 1)):
             run_chunk(my_chunks[0] if my_chunks else 0)
-        eng.profile_enable(True)
-        eng.profile_reset()
+        if args.full:
+            eng.profile_enable(True)
+            eng.profile_reset()
         barrier()
         t0 = time.perf_counter()
         parts, n_windows, n_bp = [], 0, 0
@@ -818,10 +864,14 @@ def main():
         barrier()
         dt = max_over_ranks(time.perf_counter() - t0)
         tot = comm.allgather_i64([n_bp]).sum()
-        front_ms, front_launches = eng.profile_get(_lib.K_F32_FRONT if args.precision == "f32" else _lib.K_FUSED)
-        back_ms, _ = eng.profile_get(_lib.K_BACKEND)
-        eng.profile_enable(False)
+        front_launches = 0
+        if args.full:
+            front_ms, front_launches = eng.profile_get(_lib.K_F32_FRONT if args.precision == "f32" else _lib.K_FUSED)
+            back_ms, _ = eng.profile_get(_lib.K_BACKEND)
+            eng.profile_enable(False)
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, contig_scores=preds)
             extra = {}
             if front_launches and args.precision != "f32":
                 extra["roofline"] = front_roofline(args.precision, n_windows / front_launches, front_ms / front_launches, front_launches,
@@ -885,8 +935,9 @@ def main():
     set_stage("warmup")
     for i in range(0, args.warmup, group):
         step((i % K) if (i % K) + group <= K else 0, min(group, K))
-    eng.profile_enable(True)
-    eng.profile_reset()
+    if args.full:
+        eng.profile_enable(True)
+        eng.profile_reset()
     sampler = PowerSampler(local_rank) if args.power else None
     barrier()
     set_stage("timed")
@@ -908,24 +959,30 @@ def main():
     gather_ms = (time.perf_counter() - t_g) * 1e3     # on rank 0: includes waiting for the slowest rank's last step
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
-    own_us = comm.allgather_i64([int(t_own * 1e6)])[:, 0]
-    # the same gather once more, untimed and between barriers (no rank is still computing): what the collective itself costs,
-    # so that a slow first RCCL call cannot be mistaken for poor scaling
-    barrier()
-    t_g2 = time.perf_counter()
-    comm.gather_dev(scores.ptr, gathered_dev.ptr if gathered_dev is not None else None, n_local * 12, 0)
-    eng.sync()
-    gather_ms_isolated = max_over_ranks((time.perf_counter() - t_g2) * 1e3)
+    if rank == 0 and args.dump_outputs:
+        # the job's last step: step K-1 of every rank, i.e. the last wps_local windows of each rank's contiguous shard
+        last = np.concatenate([np.arange(r * n_local + (K - 1) * wps_local, (r + 1) * n_local) for r in range(world)])
+        dump_outputs(args.dump_outputs, scores=host_scores[last])
+    if args.full:
+        own_us = comm.allgather_i64([int(t_own * 1e6)])[:, 0]
+        # the same gather once more, untimed and between barriers (no rank is still computing): what the collective itself costs,
+        # so that a slow first RCCL call cannot be mistaken for poor scaling
+        barrier()
+        t_g2 = time.perf_counter()
+        comm.gather_dev(scores.ptr, gathered_dev.ptr if gathered_dev is not None else None, n_local * 12, 0)
+        eng.sync()
+        gather_ms_isolated = max_over_ranks((time.perf_counter() - t_g2) * 1e3)
 
-    kid = _lib.K_F32_FRONT if args.precision == "f32" else _lib.K_FUSED
-    front_ms, front_launches = eng.profile_get(kid)
-    back_ms, _ = eng.profile_get(_lib.K_BACKEND)
-    eng.profile_enable(False)
-    front_us_ranks = comm.allgather_i64([int(front_ms * 1e3), int(front_launches)])
+        kid = _lib.K_F32_FRONT if args.precision == "f32" else _lib.K_FUSED
+        front_ms, front_launches = eng.profile_get(kid)
+        back_ms, _ = eng.profile_get(_lib.K_BACKEND)
+        eng.profile_enable(False)
+        front_us_ranks = comm.allgather_i64([int(front_ms * 1e3), int(front_launches)])
 
     # ---- untimed: the opt-in fast arithmetic on the same steps, for the record (f16c6: 1.5 MFMA pass equivalents; it does NOT hold
     # the 1e-4 tolerance on 10^6 windows, which is why it is not the default and never enters `value`)
-    mine = scores.download((n_local, 3), np.float32)
+    verify = args.full or args.check != "none"          # the untimed checks of what was just timed
+    mine = scores.download((n_local, 3), np.float32) if verify or args.fast_mode_steps > 0 else None
     fast = None
     if args.fast_mode_steps > 0 and args.precision != "f16c6":
         kf = min(args.fast_mode_steps, K)
@@ -953,11 +1010,13 @@ def main():
     set_stage("parity")
     # ---- untimed checks of what was just timed, on every rank over ITS windows
     # (1) bit for bit against a second run through the synchronous entry point
-    for k in range(K):
-        eng.classify_dev(bases.ptr + k * wps_local * 6000, wps_local, scores.ptr + k * wps_local * 12, args.precision)
-    eng.sync()
-    again = scores.download((n_local, 3), np.float32)
-    mismatching = int(comm.allgather_i64([int(np.count_nonzero((mine != again).any(axis=1)))])[:, 0].sum())
+    mismatching = 0
+    if verify:
+        for k in range(K):
+            eng.classify_dev(bases.ptr + k * wps_local * 6000, wps_local, scores.ptr + k * wps_local * 12, args.precision)
+        eng.sync()
+        again = scores.download((n_local, 3), np.float32)
+        mismatching = int(comm.allgather_i64([int(np.count_nonzero((mine != again).any(axis=1)))])[:, 0].sum())
     # (2) every timed window against the exact-f32 device path (itself 4e-6 from the fp64 oracle and 1.1e-5 from the
     #     reference-graph golden on config 2: tests/test_gpu_parity.py): max |dscore|, and how many windows pass 1e-4 / 5e-5
     parity = None
@@ -989,12 +1048,7 @@ def main():
             "n_gpus": world, "steps": K, "warmup": args.warmup, "ms_per_step": round(dt / K * 1e3, 3),
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": DTYPE_TEXT[args.precision], "data": "synthetic",
-            "rccl_ranks": int(rccl_ranks.value),
-            "per_rank_windows_per_s": [round(n_local / (u * 1e-6), 1) for u in own_us.tolist()],
-            "per_rank_steps_ms": [round(u * 1e-3, 2) for u in own_us.tolist()],
-            "per_rank_front_ms_total": [round(u * 1e-3, 2) for u in front_us_ranks[:, 0].tolist()],
-            "gather_ms": round(gather_ms, 3), "gather_ms_isolated": round(gather_ms_isolated, 3),
-            "comm_init_s": round(comm_init_s, 3), "per_rank_device": per_rank_device,
+            "rccl_ranks": int(rccl_ranks.value), "gather_ms": round(gather_ms, 3), "comm_init_s": round(comm_init_s, 3),
             "config": {"workload": f"{total} synthetic 6 kbp windows ({K} steps x {wps}{' per GPU' if args.scaling == 'weak' else ''}), "
                                    f"{'sharded contiguously over' if args.scaling == 'strong' else 'on each of'} {world} GPU(s) "
                                    f"= {n_local} per GPU, synthetic weights of the reference shapes, HBM-resident input, "
@@ -1006,39 +1060,44 @@ def main():
                        "entry_point": "gnn_classify_dev_async" if args.async_steps else "gnn_classify_dev",
                        "device": info["name"].strip(), "cus": info["cus"]},
         }
-        win_per_launch = n_local / max(front_launches, 1)
-        avg_ms = front_ms / max(front_launches, 1)
-        tflops = FLOP_PER_WINDOW * win_per_launch / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
-        passes = MFMA_PASSES.get(args.precision)
-        out["roofline"] = front_roofline(args.precision, win_per_launch, avg_ms, front_launches, front_ms, back_ms)
-        if args.precision != "f32":
-            # context for `frac`: what this power-managed chip sustains on the bf16 MFMA with nothing else running
-            # (outside the timed region, ~200 ms)
-            probe = ctypes.c_double()
-            _lib.check(eng.lib.gnn_mfma_probe(eng.ctx, 200, ctypes.byref(probe)))
-            out["roofline"]["issued_mfma_tflops_bf16_equivalent"] = round(tflops * passes, 1)
-            out["roofline"]["mfma_probe_sustained_tflops"] = round(probe.value, 1)
-            out["roofline"]["issued_vs_probe"] = round(tflops * passes / probe.value, 4)
-            if args.precision == "f16c6":
-                # the power floor of the opt-in fast arithmetic: its own MFMA mix (8 f16 + 4 MX-fp6 per k32 step) on register operands,
-                # in algorithmic TFLOP/s
-                same = ctypes.c_double()
-                _lib.check(eng.lib.gnn_mfma_probe_kind(eng.ctx, 2, 200, ctypes.byref(same)))
-                out["roofline"]["mfma_probe_same_mix_algorithmic_tflops"] = round(same.value, 1)
-                out["roofline"]["frac_of_power_floor"] = round(tflops / same.value, 4)
-                out["roofline"]["frac_ceiling_at_power_floor"] = round(same.value / MFMA_PEAK_TFLOPS, 4)
-            if args.precision in ("f16x3", "f16x3tc", "f16x3tk", "bf16x3"):
-                # the power floor of THIS arithmetic: register-operand MFMAs of the kernel's own instruction (f16 draws more than
-                # bf16 per MFMA on this chip), nothing else running; the kernel issues `passes` of them per algorithmic product
-                same = ctypes.c_double()
-                _lib.check(eng.lib.gnn_mfma_probe_kind(eng.ctx, 0 if args.precision == "bf16x3" else 1, 200, ctypes.byref(same)))
-                out["roofline"]["mfma_probe_same_instruction_tflops"] = round(same.value, 1)
-                out["roofline"]["frac_of_power_floor"] = round(tflops * passes / same.value, 4)
-                out["roofline"]["frac_ceiling_at_power_floor"] = round(same.value / passes / MFMA_PEAK_TFLOPS, 4)
+        if args.full:
+            out.update({"per_rank_windows_per_s": [round(n_local / (u * 1e-6), 1) for u in own_us.tolist()],
+                        "per_rank_steps_ms": [round(u * 1e-3, 2) for u in own_us.tolist()],
+                        "per_rank_front_ms_total": [round(u * 1e-3, 2) for u in front_us_ranks[:, 0].tolist()],
+                        "gather_ms_isolated": round(gather_ms_isolated, 3), "per_rank_device": per_rank_device})
+            win_per_launch = n_local / max(front_launches, 1)
+            avg_ms = front_ms / max(front_launches, 1)
+            tflops = FLOP_PER_WINDOW * win_per_launch / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
+            passes = MFMA_PASSES.get(args.precision)
+            out["roofline"] = front_roofline(args.precision, win_per_launch, avg_ms, front_launches, front_ms, back_ms)
+            if args.precision != "f32":
+                # context for `frac`: what this power-managed chip sustains on the bf16 MFMA with nothing else running
+                # (outside the timed region, ~200 ms)
+                probe = ctypes.c_double()
+                _lib.check(eng.lib.gnn_mfma_probe(eng.ctx, 200, ctypes.byref(probe)))
+                out["roofline"]["issued_mfma_tflops_bf16_equivalent"] = round(tflops * passes, 1)
+                out["roofline"]["mfma_probe_sustained_tflops"] = round(probe.value, 1)
+                out["roofline"]["issued_vs_probe"] = round(tflops * passes / probe.value, 4)
+                if args.precision == "f16c6":
+                    # the power floor of the opt-in fast arithmetic: its own MFMA mix (8 f16 + 4 MX-fp6 per k32 step) on register operands,
+                    # in algorithmic TFLOP/s
+                    same = ctypes.c_double()
+                    _lib.check(eng.lib.gnn_mfma_probe_kind(eng.ctx, 2, 200, ctypes.byref(same)))
+                    out["roofline"]["mfma_probe_same_mix_algorithmic_tflops"] = round(same.value, 1)
+                    out["roofline"]["frac_of_power_floor"] = round(tflops / same.value, 4)
+                    out["roofline"]["frac_ceiling_at_power_floor"] = round(same.value / MFMA_PEAK_TFLOPS, 4)
+                if args.precision in ("f16x3", "f16x3tc", "f16x3tk", "bf16x3"):
+                    # the power floor of THIS arithmetic: register-operand MFMAs of the kernel's own instruction (f16 draws more than
+                    # bf16 per MFMA on this chip), nothing else running; the kernel issues `passes` of them per algorithmic product
+                    same = ctypes.c_double()
+                    _lib.check(eng.lib.gnn_mfma_probe_kind(eng.ctx, 0 if args.precision == "bf16x3" else 1, 200, ctypes.byref(same)))
+                    out["roofline"]["mfma_probe_same_instruction_tflops"] = round(same.value, 1)
+                    out["roofline"]["frac_of_power_floor"] = round(tflops * passes / same.value, 4)
+                    out["roofline"]["frac_ceiling_at_power_floor"] = round(same.value / passes / MFMA_PEAK_TFLOPS, 4)
         # parity of what was just timed: every window against the exact-f32 device path (above), and the first windows of
         # the job against the committed outputs of the reference's own graph (tests/golden/config2_golden.npz, windows 0..9999)
         real = os.environ.get("GENOMAD_AMD_BENCH_FAKE_ENGINE") != "1"
-        if not args.no_encoder and real:
+        if args.full and not args.no_encoder and real:
             set_stage("encoder")
             try:
                 out["encoder"] = encoder_block(eng, rank)
@@ -1048,7 +1107,7 @@ def main():
         # that enters `value`; a failure is reported inside its block and in `failed`
         if kmer is not None:
             out["kmer_tables"] = kmer
-        if world == 1 and real and not args.no_extras and args.precision in (DEFAULT_PRECISION, "f16x3tk"):
+        if args.full and world == 1 and real and not args.no_extras and args.precision in (DEFAULT_PRECISION, "f16x3tk"):
             for name, fn in (("main_e2e", lambda: main_e2e_block(eng, weights)), ("metagenome", lambda: metagenome_block(eng, args.precision))):
                 set_stage(name)
                 t_x = time.perf_counter()
@@ -1081,8 +1140,9 @@ def main():
             out["dscore_tolerance"] = 1e-4
             if not out["max_abs_dscore"] <= 1e-4:
                 failed.append(f"max |dscore| {out['max_abs_dscore']:.3e} against the reference-graph golden exceeds 1e-4")
-        out["steps_verified"] = {"windows_all_ranks": int(total), "mismatching_windows_all_ranks": mismatching,
-                                 "against": "untimed re-run of every step through the synchronous gnn_classify_dev, bit for bit"}
+        if verify:
+            out["steps_verified"] = {"windows_all_ranks": int(total), "mismatching_windows_all_ranks": mismatching,
+                                     "against": "untimed re-run of every step through the synchronous gnn_classify_dev, bit for bit"}
         if cpu_base is not None:
             out["cpu_baseline"] = cpu_base
             if args.scaling == "strong" or world == 1:      # host_scores[:sample] are the job's first windows = the CPU sample

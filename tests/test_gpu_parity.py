@@ -1099,19 +1099,28 @@ def test_default_launch_size_follows_the_free_device_memory(synth_weights):
 
 
 def test_bench_command_line_prints_one_complete_json_line(tmp_path):
-    """The driver's command, at a size that takes seconds: `python bench.py --gpus 1 --steps K --warmup W` prints exactly one
+    """The driver's command, at a size that takes seconds: `python bench.py --gpus 1 --steps K --warmup W --full` prints exactly one
     JSON line on stdout with the contract's fields, goes through RCCL at N = 1 (rccl_ranks), checks EVERY timed window against
     the exact-f32 path (parity.ok) and every step bit for bit against the synchronous entry point, and exits 0; the fast opt-in
-    arithmetic is allowed to fail that check but must then say so and exit non-zero, never print a clean line."""
+    arithmetic is allowed to fail that check but must then say so and exit non-zero, never print a clean line.  The plain command
+    prints the headline fields and writes, with --dump-outputs, the scores of the last step: the same bits as the --full run's."""
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
            "--windows-per-step", "2048", "--cpu-sample", "0"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    lines = [x for x in r.stdout.splitlines() if x.strip()]
-    assert len(lines) == 1, r.stdout
-    d = json.loads(lines[0])
+    dumps = {}
+    for name, extra in (("plain", []), ("full", ["--full"])):
+        dumps[name] = tmp_path / name
+        r = subprocess.run(cmd + extra + ["--dump-outputs", str(dumps[name])], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [x for x in r.stdout.splitlines() if x.strip()]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+            assert key in d, key
+        assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0
+    plain, full = (np.load(dumps[n] / "scores.npy") for n in ("plain", "full"))
+    assert plain.shape == (2048, 3) and plain.dtype == np.float32 and np.array_equal(plain, full)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "rccl_ranks", "parity", "steps_verified"):
         assert key in d, key

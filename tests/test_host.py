@@ -337,12 +337,12 @@ def test_packed_reader_and_candidate_spans_match_reference_rules(golden_dir, tmp
         assert list(ln) == [b - a for a, b in sequence.window_spans(L)]
 
 
-def test_native_fasta_packer_equals_the_python_rules_and_the_reference(tmp_path):
+def test_native_fasta_packer_equals_the_python_rules_and_the_reference(tmp_path, golden_dir):
     """gnn_fasta_scan / gnn_fasta_pack (host code in the library, in place) against the pure-Python
-    statement of the rules and, when the checkout is present, against the REFERENCE's own read_fasta
-    and check_fasta executed in place — on adversarial layouts and on random FASTA-like text."""
-    from oracle import reference_harness
-    ref_seq = reference_harness.load_reference_sequence() if reference_harness.available() else None
+    statement of the rules and against what the REFERENCE's own read_fasta and check_fasta returned when
+    executed in place (tests/golden/reference_calls.json, oracle/make_golden_reference_calls.py) — on
+    adversarial layouts and on random FASTA-like text."""
+    ref_fasta = json.load(open(os.path.join(golden_dir, "reference_calls.json")))["fasta"]
     cases = [
         b"", b"\n", b">", b">\n", b">a", b">a\n", b">a\nACGT", b">a\nACGT\n", b"ACGT\n>a\nAC\n\nGT\n",
         b">a\n\n\n>b\nNNNN\n>c\nnNACGTNn\n>d\nN\nA\nN\n", b">a desc here\n AC GT \n>b\tq\nAC>GT\n>>c\n>\nAC\n",
@@ -358,6 +358,7 @@ def test_native_fasta_packer_equals_the_python_rules_and_the_reference(tmp_path)
     for i, text in enumerate(cases):
         p = tmp_path / f"case{i}.fna"
         p.write_bytes(text)
+        ref_rec = ref_fasta[hashlib.sha256(text).hexdigest()]          # recorded for exactly this text
         def attempt(f, *a):
             try:
                 return f(*a)
@@ -375,14 +376,13 @@ def test_native_fasta_packer_equals_the_python_rules_and_the_reference(tmp_path)
             assert bytes(got_s) == bytes(want_s) and list(got_o) == list(want_o), (i, text)
             rec = list(sequence.read_fasta(p, strip_n=strip))
             assert [len(s) for _, s in rec] == list(np.diff(got_o)), (i, text)
-            if ref_seq is not None:
-                ref = [(r.accession, r.seq) for r in ref_seq.read_fasta(p, strip_n=strip)]
-                assert [a for a, _ in ref] == list(got_n), (i, text)
-                assert "".join(s for _, s in ref).encode() == bytes(got_s), (i, text)
+            ref = ref_rec[f"strip_{str(strip).lower()}"]
+            assert ref["accessions"] == list(got_n), (i, text)
+            assert ref["seq"].encode() == bytes(got_s), (i, text)
         ok = attempt(sequence.check_fasta, p)
         assert ok == attempt(sequence.check_fasta_py, p), (i, text)
-        if ref_seq is not None and not isinstance(ok, str):
-            assert ok == ref_seq.check_fasta(p), (i, text)
+        if not isinstance(ok, str):
+            assert ok == ref_rec["check_fasta"], (i, text)
 
 
 def test_keras_h5_weight_ingestion_roundtrip(synth_weights, tmp_path):
@@ -541,20 +541,15 @@ def test_h5weights_cli_dry_run_prints_the_assignment_and_names_the_failing_rule(
     assert "does not look like the nn_classifier.h5" in err and "disagrees with the order" in err
 
 
-def test_gen_patches_follows_the_reference_initializer():
+def test_gen_patches_follows_the_reference_initializer(golden_dir):
     """synthetic.gen_patches restates gen_filters_igloo(4, 2100, 5997, return_sequences=False,
     build_backbone=False) (igloo.py:220-302, the initializer of `random_patches`, :106-115).  The reference
-    function is pure numpy, so it is RUN IN PLACE here: same shape and dtype kind, every patch = 4 distinct
-    positions in [0, 5997) sorted ascending, and — both being uniform draws — matching position statistics."""
-    from oracle import reference_harness as rh
-    if not rh.available():
-        pytest.skip("needs the reference checkout")
+    function is pure numpy; what it returned when RUN IN PLACE after np.random.seed(5) is recorded in
+    tests/golden/reference_calls.npz (oracle/make_golden_reference_calls.py): same shape and dtype kind, every
+    patch = 4 distinct positions in [0, 5997) sorted ascending, and — both being uniform draws — matching
+    position statistics."""
     from genomad_amd import synthetic
-    nn = rh.load_reference_network()
-    import importlib
-    igloo = importlib.import_module("genomad.neural_network.igloo")
-    np.random.seed(5)
-    ref = np.asarray(igloo.gen_filters_igloo(4, 2100, 5997, return_sequences=False, build_backbone=False))
+    ref = np.load(os.path.join(golden_dir, "reference_calls.npz"))["patches_seed5"]
     mine = synthetic.gen_patches(np.random.default_rng(5))
     assert ref.shape == mine.shape == (2100, 4, 1)
     for p in (ref.astype(np.int64), mine.astype(np.int64)):
@@ -567,7 +562,6 @@ def test_gen_patches_follows_the_reference_initializer():
         expect = 5997 * (k + 1) / 5
         assert abs(r[:, k].mean() - expect) < 120 and abs(m[:, k].mean() - expect) < 120
     assert abs(r.std() - m.std()) < 60
-    assert nn is not None
 
 
 def test_tfrecord_wire_format(tmp_path):
@@ -642,19 +636,21 @@ def test_install_rebinds_the_reference_entry_point_and_undoes_cuda_visible_devic
     restart, threads, verbose, cleanup)`` positionally (cli.py:772-774; end-to-end goes through the same
     command, :1367-1376).  Importing the reference module exports CUDA_VISIBLE_DEVICES=-1
     (modules/nn_classification.py:8), which HIP honours: install() and main() must remove it before any HIP
-    call.  Runs the REAL reference package namespace in place (numba stubbed, genomad/__init__.py bypassed)."""
-    from oracle import reference_harness as rh
-    if not rh.available():
-        pytest.skip("needs the reference checkout")
-    import importlib
-    rh.load_reference_sequence()
+    call.  The reference package namespace is stood in for by bare ``genomad`` / ``genomad.modules`` modules and a
+    ``genomad.modules.nn_classification`` whose import does what the reference module's does at :8 (nothing else of
+    it is reached: install() replaces it)."""
+    import types
     monkeypatch.delenv("CUDA_VISIBLE_DEVICES", raising=False)
-    ref_mod = importlib.import_module("genomad.modules.nn_classification")
-    importlib.reload(ref_mod)                                   # (re)runs its module-level os.environ writes
-    assert os.environ.get("CUDA_VISIBLE_DEVICES") == "-1"
-    import genomad
-    monkeypatch.setattr(genomad, "nn_classification", ref_mod, raising=False)   # what genomad/__init__.py:5-14 binds
-    monkeypatch.setitem(sys.modules, "genomad.modules.nn_classification", ref_mod)
+    genomad = types.ModuleType("genomad")
+    genomad.__path__ = []
+    genomad.modules = types.ModuleType("genomad.modules")
+    genomad.modules.__path__ = []
+    ref_mod = types.ModuleType("genomad.modules.nn_classification")
+    os.environ["CUDA_VISIBLE_DEVICES"] = "-1"                  # what importing it does
+    genomad.modules.nn_classification = ref_mod
+    genomad.nn_classification = ref_mod                        # what genomad/__init__.py:5-14 binds
+    for m in (genomad, genomad.modules, ref_mod):
+        monkeypatch.setitem(sys.modules, m.__name__, m)
     try:
         this = nnc.install()
         assert this is nnc and genomad.nn_classification is nnc
@@ -681,9 +677,6 @@ def test_install_rebinds_the_reference_entry_point_and_undoes_cuda_visible_devic
         assert (tmp_path / "out2" / "sample_nn_classification" / "sample_nn_classification.tsv").exists()
     finally:
         os.environ.pop("CUDA_VISIBLE_DEVICES", None)
-        sys.modules["genomad.modules.nn_classification"] = ref_mod
-        import genomad.modules
-        genomad.modules.nn_classification = ref_mod
 
 
 def _gloo_main_worker(rank, world, port, fasta, out_dir, q):
@@ -921,7 +914,7 @@ def test_unknown_precision_name_is_refused_up_front(tmp_path, monkeypatch):
 
 
 def test_bench_n8_line_is_complete_over_the_fake_engine(tmp_path):
-    """The driver's own command, `python bench.py --gpus 8 --steps 20 --warmup 5`, end to end on the CPU over tests/fake_engine.py
+    """The driver's own command with --full, `python bench.py --gpus 8 --steps 20 --warmup 5 --full`, end to end on the CPU over tests/fake_engine.py
     (GENOMAD_AMD_BENCH_FAKE_ENGINE=1): bench.py spawns its 8 ranks, shards the job contiguously, gathers the scores on rank 0
     and prints ONE line that carries what an 8-GPU measurement has to be read with - `roofline`, `cpu_baseline` (rank 0, before
     the communicator exists), `rccl_ranks` 8, one `per_rank_*` entry per rank, the gather's own duration and the communicator's
@@ -931,7 +924,7 @@ def test_bench_n8_line_is_complete_over_the_fake_engine(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["GENOMAD_AMD_BENCH_FAKE_ENGINE"] = "1"
     env["OPENBLAS_NUM_THREADS"] = "2"
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5",
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--full",
                         "--windows-per-step", "1024", "--cpu-sample", "2"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
@@ -1308,7 +1301,7 @@ def test_bench_strong_scaling_keeps_the_tuned_launch_shape_at_every_n():
     got = {}
     for name, extra in (("n8", ["--gpus", "8"]), ("n8_single", ["--gpus", "8", "--no-coalesce"]), ("n1", ["--gpus", "1"])):
         r = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "8", "--warmup", "3", "--windows-per-step", "4096", "--chunk", "1024",
-                            "--cpu-sample", "0"] + extra, env=env, capture_output=True, text=True, timeout=600)
+                            "--cpu-sample", "0", "--full"] + extra, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         got[name] = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")][0]
     n8, single, n1 = got["n8"], got["n8_single"], got["n1"]
@@ -1319,6 +1312,36 @@ def test_bench_strong_scaling_keeps_the_tuned_launch_shape_at_every_n():
     for o in (n8, single, n1):
         assert o["steps"] == 8 and o["parity"]["windows"] == 8 * 4096 and o["steps_verified"]["mismatching_windows_all_ranks"] == 0
         assert o["max_abs_dscore"] == 0.0 and "failed" not in o
+
+
+def test_bench_plain_run_times_only_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py --gpus N --steps K --warmup W` does only what `value` needs (no CPU baseline, no parity pass, no roofline, no
+    golden comparison, no per-rank timings), and --dump-outputs DIR writes the scores of the job's last step - step K-1 of every rank,
+    in job order - as DIR/scores.npy (float32): the same rows as in the --full run's gathered scores.  Over the fake engine, N = 1 and 2."""
+    import subprocess
+    root = Path(__file__).resolve().parents[1]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    env["GENOMAD_AMD_BENCH_FAKE_ENGINE"] = "1"
+    env["OPENBLAS_NUM_THREADS"] = "2"
+    base = [sys.executable, str(root / "bench.py"), "--steps", "3", "--warmup", "1", "--windows-per-step", "1024"]
+    r = subprocess.run(base + ["--gpus", "1", "--full", "--cpu-sample", "0", "--dump-scores", str(tmp_path / "all.npy")],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    every = np.load(tmp_path / "all.npy")                                    # (3 x 1024, 3) in job order
+    for n, rows in ((1, np.arange(2048, 3072)), (2, np.r_[1024:1536, 2560:3072])):
+        out = tmp_path / f"dump{n}"
+        r = subprocess.run(base + ["--gpus", str(n), "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        o = lines[0]
+        assert o["n_gpus"] == n and o["steps"] == 3 and o["warmup"] == 1 and o["ms_per_step"] > 0 and o["higher_is_better"] is True
+        assert o["metric"] == "6 kbp windows classified/sec" and o["unit"] == "windows/s" and o["value"] > 0 and o["dtype"]
+        for key in ("cpu_baseline", "parity", "steps_verified", "roofline", "max_abs_dscore", "per_rank_windows_per_s", "gather_ms_isolated"):
+            assert key not in o, key
+        assert [p.name for p in out.iterdir()] == ["scores.npy"]
+        got = np.load(out / "scores.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, every[rows])
 
 
 def test_hbm_traffic_json_is_a_function_of_the_committed_pmc_passes():
@@ -1363,6 +1386,18 @@ def test_native_accession_digests_equal_the_python_mirror():
     assert not sharding.fasta_verdict(None, got[:0], lambda: True)
 
 
+def _blas_thread_ceiling(visible: int) -> int:
+    """The threads this machine's BLAS grants when asked for `visible` of them (OpenBLAS' compile-time NUM_THREADS can cap it below the
+    visible cores), measured in a fresh process that no launcher's OMP_NUM_THREADS reaches."""
+    import subprocess
+    code = ("import sys\nimport numpy\nfrom threadpoolctl import threadpool_info, threadpool_limits\n"
+            "with threadpool_limits(limits=int(sys.argv[1])):\n"
+            "    print(max([p['num_threads'] for p in threadpool_info() if p.get('user_api') == 'blas'] or [0]))")
+    env = {k: v for k, v in os.environ.items() if k not in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS")}
+    r = subprocess.run([sys.executable, "-c", code, str(visible)], env=env, capture_output=True, text=True, timeout=120)
+    return int(r.stdout.strip()) if r.returncode == 0 and r.stdout.strip() and int(r.stdout.strip()) > 0 else visible
+
+
 def test_cpu_baseline_is_not_throttled_by_the_launcher_and_keeps_its_budget():
     """`python -m torch.distributed.run --nproc-per-node N` (N > 1) exports OMP_NUM_THREADS=1, which OpenBLAS honours: rank 0's
     1 024-window CPU baseline would run on ONE thread (~25 minutes) while the other ranks wait for its RCCL id - the driver's
@@ -1378,7 +1413,8 @@ def test_cpu_baseline_is_not_throttled_by_the_launcher_and_keeps_its_budget():
     assert r.returncode == 0, r.stderr[-2000:]
     o = json.loads(r.stdout.strip().splitlines()[-1])
     assert o["env"] == "1" and o["n"] == 8
-    assert o["cores"] == o["visible"] or o["visible"] == 1, o           # not the launcher's single thread
+    # not the launcher's single thread: every visible core, or as many as the BLAS library grants at most
+    assert o["cores"] == min(o["visible"], _blas_thread_ceiling(o["visible"])) or o["visible"] == 1, o
     r = subprocess.run([sys.executable, "-c", code % (str(root), "0.001")], env=env, capture_output=True, text=True, timeout=600)
     o = json.loads(r.stdout.strip().splitlines()[-1])
     assert o["n"] == 2 and "cut from 8" in o["sample"]                   # one batch, then the budget is gone: said in the line
@@ -1386,7 +1422,7 @@ def test_cpu_baseline_is_not_throttled_by_the_launcher_and_keeps_its_budget():
 
 def test_bench_under_the_drivers_launcher_with_two_ranks_over_the_fake_engine():
     """The driver's N > 1 command verbatim - `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
-    --master-port P bench.py --gpus N --steps K --warmup W` - on the CPU over tests/fake_engine.py: the launcher's environment
+    --master-port P bench.py --gpus N --steps K --warmup W`, with --full - on the CPU over tests/fake_engine.py: the launcher's environment
     (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_PORT, and its OMP_NUM_THREADS=1) reaches bench.py, the ranks find each other through
     the rendezvous file keyed on the launcher's identity, rank 0 prints ONE JSON line with a CPU baseline that was not throttled to
     one thread, and every rank exits 0."""
@@ -1400,7 +1436,7 @@ def test_bench_under_the_drivers_launcher_with_two_ranks_over_the_fake_engine():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "OMP_NUM_THREADS")}
     env["GENOMAD_AMD_BENCH_FAKE_ENGINE"] = "1"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), str(root / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
+                        "--master-port", str(port), str(root / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--full",
                         "--windows-per-step", "512", "--cpu-sample", "4"], env=env, capture_output=True, text=True, timeout=900, cwd=str(root))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
@@ -1408,7 +1444,8 @@ def test_bench_under_the_drivers_launcher_with_two_ranks_over_the_fake_engine():
     o = lines[0]
     assert o["n_gpus"] == 2 and o["rccl_ranks"] == 2 and o["steps"] == 4 and o["fake_engine"] is True
     assert o["cpu_baseline"]["omp_num_threads_env"] == "1"                      # the launcher did export it ...
-    assert o["cpu_baseline"]["cores"] == o["cpu_baseline"]["host_cpus_visible"] or o["cpu_baseline"]["host_cpus_visible"] == 1   # ... and it did not bind
+    visible = o["cpu_baseline"]["host_cpus_visible"]
+    assert o["cpu_baseline"]["cores"] == min(visible, _blas_thread_ceiling(visible)) or visible == 1   # ... and it did not bind
     assert o["steps_verified"]["mismatching_windows_all_ranks"] == 0 and o["parity"]["ok"] and "failed" not in o
 
 

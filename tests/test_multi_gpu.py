@@ -4,7 +4,7 @@ are visible and otherwise run D = min(devices, 8) ranks, one process per GPU, st
 (bench.spawn_ranks: RANK / LOCAL_RANK / WORLD_SIZE + a private rendezvous directory):
 
   (i)   every collective of genomad_amd/rccl.py (ncclAllGather, ncclGather host and device, all-reduce max, barrier) across D devices;
-  (ii)  `bench.py --gpus D --steps 2 --windows-per-step 4096 D`: exit 0, rccl_ranks == D, no mismatching window, and the gathered
+  (ii)  `bench.py --gpus D --full --steps 2 --windows-per-step 4096 D`: exit 0, rccl_ranks == D, no mismatching window, and the gathered
         scores bit-equal to a 1-rank run of the same job (sharding the reference's predict loop, nn_classification.py:316-320,
         must not change a bit);
   (iii) main() under D ranks on a small FASTA == single process, bit for bit (contigs sharded, ONE gather, rank 0 writes).
@@ -67,7 +67,7 @@ def _check_bench(world, tmp_path, fake):
     for n in (world, 1):
         dump = tmp_path / f"scores_{n}.npy"
         r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--windows-per-step",
-                            str(4096 * world), "--cpu-sample", "0", "--dump-scores", str(dump)], env=env, capture_output=True, text=True, timeout=1800)
+                            str(4096 * world), "--cpu-sample", "0", "--full", "--dump-scores", str(dump)], env=env, capture_output=True, text=True, timeout=1800)
         assert r.returncode == 0, r.stderr[-3000:]
         lines[n] = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")][0]
     o = lines[world]
