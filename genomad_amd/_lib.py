@@ -13,6 +13,9 @@ LIB_PATH = Path(os.environ.get("GENOMAD_AMD_LIB", _HERE / "csrc" / "libgenomad_n
 
 WINDOW, TOKENS, DEPTH, CH = 6000, 5997, 257, 128
 PATCHES, PATCH_SIZE, POOLED, FEAT, HIDDEN, CLASSES = 2100, 4, 749, 256, 512, 3
+EMBED_DIM = 512                                  # GNN_EMBED_DIM: create_encoder()'s output (model.py:14-31)
+EMB_F32, EMB_BF16 = 0, 1                         # gnn_emb_dtype
+EMB_DTYPES = {"f32": EMB_F32, "bf16": EMB_BF16}
 
 PREC_F32, PREC_BF16X3, PREC_BF16, PREC_F16C8, PREC_F16X3, PREC_F16C6, PREC_F16X3TC, PREC_F16X3TK = 0, 1, 2, 3, 4, 5, 6, 7
 # PREC_BF16 (single bf16 pass) and PREC_F16C8 (f16 + fp8 corrections) were removed in round 6: both fail the 1e-4 tolerance; the
@@ -95,6 +98,9 @@ SIGNATURES = {
     "gnn_span_byte_count": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _vp]),
     "gnn_classify_spans": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _vp]),
     "gnn_classify_contigs": (_int, [_vp, _vp, _int, _i64, _vp, _i64, _int, _int, _vp, _vp, _i64, C.POINTER(_i64)]),
+    "gnn_classify_contigs_embed": (_int, [_vp, _vp, _int, _i64, _vp, _i64, _int, _int, _vp, _vp, _i64, C.POINTER(_i64), _vp]),
+    "gnn_embed": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
+    "gnn_embed_dev": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_debug_forward": (_int, [_vp, _vp, _i64, _int, _vp, C.POINTER(Taps)]),
     "gnn_synth_windows_dev": (_int, [_vp, _u64, _i64, _i64, _vp]),
     "gnn_profile_enable": (_int, [_vp, _int]),

@@ -241,6 +241,12 @@ void free_stage(gnn_ctx* ctx) {
     ctx->stage_scores = nullptr;
     ctx->stage_scores_host = nullptr;
     ctx->stage_windows = 0;
+    if (ctx->stage_emb) (void)hipFree(ctx->stage_emb);
+    if (ctx->emb_scores) (void)hipFree(ctx->emb_scores);
+    ctx->stage_emb = nullptr;
+    ctx->stage_emb_bytes = 0;
+    ctx->emb_scores = nullptr;
+    ctx->emb_scores_windows = 0;
     for (int i = 0; i < 2; ++i) {
         if (ctx->pin[i]) (void)hipHostFree(ctx->pin[i]);
         if (ctx->pin_ev[i]) (void)hipEventDestroy(ctx->pin_ev[i]);
@@ -300,8 +306,13 @@ static int stage_upload(gnn_ctx* ctx, const uint8_t* src, size_t bytes) {
     return GNN_OK;
 }
 
+size_t emb_elem_bytes(int emb_dtype) {
+    return emb_dtype == GNN_EMB_F32 ? sizeof(float) : emb_dtype == GNN_EMB_BF16 ? sizeof(uint16_t) : 0;
+}
+
 // One pass of the hot path over n windows whose bases are on the device.
-int classify_chunks(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int precision, float* scores_dev, bool defer_last) {
+int classify_chunks(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int precision, float* scores_dev, bool defer_last,
+                    void* emb_dev, int emb_dtype) {
     if (!ctx->has_weights) {
         set_error("gnn_load_weights has not been called");
         return GNN_ERR_STATE;
@@ -434,6 +445,10 @@ int classify_chunks(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int preci
             if ((rc = fill(ws.mp, 2 * NPAIR)) || (rc = fill(ws.m, 2 * NP)) || (rc = fill(ws.yp, (size_t)2 * POOLED * C)) ||
                 (rc = fill(ws.logits, 2 * POOLED)) || (rc = fill(ws.alpha, 2 * POOLED)) || (rc = fill(ws.feat, FEAT)))
                 return rc;
+            // the chunk's embedding rows too (all-ones bytes: a NaN in f32 and in bf16), so a row the back end misses reads as NaN
+            if (emb_dev)
+                GNN_HIP(hipMemsetAsync(static_cast<uint8_t*>(emb_dev) + (size_t)a * HID * emb_elem_bytes(emb_dtype), 0xFF,
+                                       (size_t)m * HID * emb_elem_bytes(emb_dtype), guard.main));
         }
         if (f32) {
             ProfScope ps(ctx, GNN_K_F32_FRONT);
@@ -454,7 +469,11 @@ int classify_chunks(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int preci
         {
             ProfScope ps(ctx, GNN_K_BACKEND);
             // the Toom-Cook front end feeds the back end of the default arithmetic
-            rc = launch_backend(ctx, m, (precision == GNN_PREC_F16X3TC || precision == GNN_PREC_F16X3TK) ? GNN_PREC_F16X3 : precision, scores_dev + a * GNN_CLASSES);
+            // embeddings: window a + i's row is row a + i of the caller's buffer, so an overlapped back end (second stream, other
+            // workspace) writes rows of its own chunk only
+            void* emb = emb_dev ? static_cast<uint8_t*>(emb_dev) + (size_t)a * HID * emb_elem_bytes(emb_dtype) : nullptr;
+            rc = launch_backend(ctx, m, (precision == GNN_PREC_F16X3TC || precision == GNN_PREC_F16X3TK) ? GNN_PREC_F16X3 : precision,
+                                scores_dev + a * GNN_CLASSES, emb, emb_dtype);
         }
         if (overlap) {
             if (!rc) {
@@ -958,6 +977,88 @@ int gnn_classify_dev_async(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, in
 }
 
 int gnn_classify_flush(gnn_ctx* ctx) { return check_ctx(ctx); }
+
+// argument checks shared by the embedding entry points
+static int embed_args(int precision, int emb_dtype, const char* what) {
+    if (precision == GNN_PREC_F16C6) {
+        set_error(std::string(what) + ": GNN_PREC_F16C6 has no embedding path (the frozen mode's dense head runs on the matrix pipe "
+                  "and is outside the tolerance); use f16x3tc, f16x3tk, f16x3, bf16x3 or f32");
+        return GNN_ERR_ARG;
+    }
+    if (!emb_elem_bytes(emb_dtype)) {
+        set_error(std::string(what) + ": unknown gnn_emb_dtype " + std::to_string(emb_dtype));
+        return GNN_ERR_ARG;
+    }
+    return GNN_OK;
+}
+
+int gnn_embed_dev(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int precision, int emb_dtype, void* emb_dev,
+                  float* scores_dev) {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!bases_dev || !emb_dev))) {
+        set_error("bad argument to gnn_embed_dev");
+        return GNN_ERR_ARG;
+    }
+    if ((rc = embed_args(precision, emb_dtype, "gnn_embed_dev"))) return rc;
+    if (n == 0) return GNN_OK;
+    if (!scores_dev) {              // the scores of the same pass still have to land somewhere: a grow-only scratch of the ctx
+        if (ctx->emb_scores_windows < n) {
+            GNN_HIP(hipStreamSynchronize(ctx->stream));
+            if (ctx->emb_scores) (void)hipFree(ctx->emb_scores);
+            ctx->emb_scores = nullptr;
+            ctx->emb_scores_windows = 0;
+            void* q = nullptr;
+            if ((rc = dev_buffer(ctx, (size_t)n * GNN_CLASSES * sizeof(float), &q))) return rc;
+            ctx->emb_scores = static_cast<float*>(q);
+            ctx->emb_scores_windows = n;
+        }
+        scores_dev = ctx->emb_scores;
+    }
+    return classify_chunks(ctx, bases_dev, n, precision, scores_dev, false, emb_dev, emb_dtype);
+}
+
+int gnn_embed(gnn_ctx* ctx, const uint8_t* bases_host, int64_t n, int precision, int emb_dtype, void* emb_host,
+              float* scores_host) {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!bases_host || !emb_host))) {
+        set_error("bad argument to gnn_embed");
+        return GNN_ERR_ARG;
+    }
+    if ((rc = embed_args(precision, emb_dtype, "gnn_embed"))) return rc;
+    if (n == 0) return GNN_OK;
+    // the staging of gnn_classify plus a device slab for the embeddings (2 KB per window in f32: 64 MB at the slab's maximum)
+    const int64_t slab = std::min<int64_t>(n, STAGE_MAX_WINDOWS);
+    const size_t row = (size_t)HID * emb_elem_bytes(emb_dtype);
+    if ((rc = ensure_stage(ctx, slab))) return rc;
+    if (ctx->stage_emb_bytes < (size_t)slab * row) {
+        GNN_HIP(hipStreamSynchronize(ctx->stream));
+        if (ctx->stage_emb) (void)hipFree(ctx->stage_emb);
+        ctx->stage_emb = nullptr;
+        ctx->stage_emb_bytes = 0;
+        void* q = nullptr;
+        if ((rc = dev_buffer(ctx, (size_t)slab * HID * sizeof(float), &q))) return rc;      // sized for f32: serves both dtypes
+        ctx->stage_emb = q;
+        ctx->stage_emb_bytes = (size_t)slab * HID * sizeof(float);
+    }
+    for (int64_t a0 = 0; a0 < n && !rc; a0 += slab) {
+        const int64_t m = std::min(slab, n - a0);
+        rc = stage_upload(ctx, bases_host + a0 * W, (size_t)m * W);
+        if (!rc) rc = classify_chunks(ctx, ctx->stage_bases, m, precision, ctx->stage_scores, false, ctx->stage_emb, emb_dtype);
+        if (!rc) {
+            if (scores_host)
+                GNN_HIP(hipMemcpyAsync(ctx->stage_scores_host, ctx->stage_scores, (size_t)m * GNN_CLASSES * sizeof(float),
+                                       hipMemcpyDeviceToHost, ctx->stream));
+            GNN_HIP(hipMemcpyAsync(static_cast<uint8_t*>(emb_host) + (size_t)a0 * row, ctx->stage_emb, (size_t)m * row,
+                                   hipMemcpyDeviceToHost, ctx->stream));
+            GNN_HIP(hipStreamSynchronize(ctx->stream));
+            if (scores_host)
+                std::memcpy(scores_host + a0 * GNN_CLASSES, ctx->stage_scores_host, (size_t)m * GNN_CLASSES * sizeof(float));
+        }
+    }
+    return rc;
+}
 
 int gnn_classify(gnn_ctx* ctx, const uint8_t* bases_host, int64_t n, int precision, float* scores_host) {
     return gnn_debug_forward(ctx, bases_host, n, precision, scores_host, nullptr);

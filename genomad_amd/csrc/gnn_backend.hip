@@ -307,11 +307,22 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ log
 // Dense stack for DW windows per block, 512 threads = one per hidden unit.
 constexpr int DW = 8;
 
+// h1 -> bf16 with round-to-nearest-even; a NaN stays a (quiet) NaN, so the range fallback still sees it
+__device__ __forceinline__ uint16_t f32_to_bf16_rne(float v) {
+    const uint32_t u = __float_as_uint(v);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x0040u);
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+// EMB (GNN_EMB_* + 1, 0 = none): also store h1 - the encoder embedding of create_encoder(), model.py:14-31 - as emb[n][512] of
+// that dtype.  Thread j owns hidden unit j of the block's DW windows, so every row store is one coalesced 2 KB (1 KB) line.
+// EMB = 0 is the kernel the scores have always used; the stores change no arithmetic, so the scores are bit-identical either way.
+template <int EMB>
 __global__ __launch_bounds__(512) void dense_kernel(const float* __restrict__ feat,
                                                     const float* __restrict__ d1k, const float* __restrict__ d1b,
                                                     const float* __restrict__ d2k, const float* __restrict__ d2b,
                                                     const float* __restrict__ d3k, const float* __restrict__ d3b,
-                                                    int n, float* __restrict__ scores) {
+                                                    int n, float* __restrict__ scores, void* __restrict__ emb) {
     __shared__ float f[DW][FEAT];
     __shared__ float h1[DW][HID];
     __shared__ float h2[DW][HID];
@@ -335,6 +346,15 @@ __global__ __launch_bounds__(512) void dense_kernel(const float* __restrict__ fe
     // ReLU written so that NaN stays NaN (fmaxf would turn it into 0 and hide an overflow of the f16-operand
     // front ends behind plausible finite scores; main() relies on non-finite scores to fall back to bf16x3)
     for (int w = 0; w < DW; ++w) h1[w][j] = acc[w] < 0.f ? 0.f : acc[w];
+    if constexpr (EMB == GNN_EMB_F32 + 1) {
+#pragma unroll
+        for (int w = 0; w < DW; ++w)
+            if (w0 + w < n) static_cast<float*>(emb)[(size_t)(w0 + w) * HID + j] = acc[w] < 0.f ? 0.f : acc[w];
+    } else if constexpr (EMB == GNN_EMB_BF16 + 1) {
+#pragma unroll
+        for (int w = 0; w < DW; ++w)
+            if (w0 + w < n) static_cast<uint16_t*>(emb)[(size_t)(w0 + w) * HID + j] = f32_to_bf16_rne(acc[w] < 0.f ? 0.f : acc[w]);
+    }
     __syncthreads();
 #pragma unroll
     for (int w = 0; w < DW; ++w) acc[w] = d2b[j];
@@ -476,7 +496,11 @@ __global__ __launch_bounds__(256) void dense_mfma_kernel(const float* __restrict
     }
 }
 
-int launch_backend(gnn_ctx* ctx, int64_t n, int precision, float* scores_dev) {
+int launch_backend(gnn_ctx* ctx, int64_t n, int precision, float* scores_dev, void* emb_dev, int emb_dtype) {
+    if (emb_dev && (precision == GNN_PREC_F16C6 || precision == GNN_PREC_F16C8 || (emb_dtype != GNN_EMB_F32 && emb_dtype != GNN_EMB_BF16))) {
+        set_error("embeddings: the dense head of this arithmetic does not produce them (f16c6 is frozen), or a bad gnn_emb_dtype");
+        return GNN_ERR_ARG;
+    }
     const DeviceWeights& d = ctx->w;
     Workspace& ws = ctx->ws;
     hipLaunchKernelGGL(m_kernel, dim3((unsigned)n, 2), dim3(256), 0, ctx->stream, ws.mp, d.w_bias[0], d.w_bias[1],
@@ -500,13 +524,22 @@ int launch_backend(gnn_ctx* ctx, int64_t n, int precision, float* scores_dev) {
                            ctx->stream, ws.m, d.w_qk[0], d.w_qk[1], (int)n, ws.logits);
     hipLaunchKernelGGL(attn_kernel, dim3((unsigned)n, 2), dim3(256), 0, ctx->stream, ws.logits, ws.yp, ws.alpha,
                        ws.feat);
-    if (precision != GNN_PREC_F16C6 && precision != GNN_PREC_F16C8)    // exact f32 FMAs (f32 range and accuracy)
-        hipLaunchKernelGGL(dense_kernel, dim3((unsigned)((n + DW - 1) / DW)), dim3(512), 0, ctx->stream, ws.feat,
-                           d.d1_k, d.d1_b, d.d2_k, d.d2_b, d.d3_k, d.d3_b, (int)n, scores_dev);
-    else                                                                // split-f16 x 3 on the matrix pipe
+    if (precision != GNN_PREC_F16C6 && precision != GNN_PREC_F16C8) {    // exact f32 FMAs (f32 range and accuracy)
+        const dim3 grid((unsigned)((n + DW - 1) / DW));
+        if (!emb_dev)
+            hipLaunchKernelGGL(dense_kernel<0>, grid, dim3(512), 0, ctx->stream, ws.feat, d.d1_k, d.d1_b, d.d2_k, d.d2_b, d.d3_k,
+                               d.d3_b, (int)n, scores_dev, nullptr);
+        else if (emb_dtype == GNN_EMB_F32)
+            hipLaunchKernelGGL(dense_kernel<GNN_EMB_F32 + 1>, grid, dim3(512), 0, ctx->stream, ws.feat, d.d1_k, d.d1_b, d.d2_k, d.d2_b,
+                               d.d3_k, d.d3_b, (int)n, scores_dev, emb_dev);
+        else
+            hipLaunchKernelGGL(dense_kernel<GNN_EMB_BF16 + 1>, grid, dim3(512), 0, ctx->stream, ws.feat, d.d1_k, d.d1_b, d.d2_k, d.d2_b,
+                               d.d3_k, d.d3_b, (int)n, scores_dev, emb_dev);
+    } else {                                                            // split-f16 x 3 on the matrix pipe
         hipLaunchKernelGGL(dense_mfma_kernel, dim3((unsigned)((n + DM_ROWS - 1) / DM_ROWS)), dim3(256), 0, ctx->stream, ws.feat,
                            reinterpret_cast<const uint4*>(d.d1_frag), d.d1_b, reinterpret_cast<const uint4*>(d.d2_frag), d.d2_b,
                            d.d3_k, d.d3_b, (int)n, scores_dev);
+    }
     GNN_HIP(hipGetLastError());
     return GNN_OK;
 }

@@ -164,6 +164,10 @@ struct gnn_ctx {
     // the windows and their scores, two pinned bounce buffers the windows go through in pieces (the copy of piece i+1 into
     // its bounce buffer overlaps the DMA of piece i) and a pinned landing buffer for the scores.  No allocation per call.
     uint8_t* stage_bases = nullptr;
+    void* stage_emb = nullptr;                    // gnn_embed: the slab's embeddings (grow-only, stage_emb_bytes)
+    size_t stage_emb_bytes = 0;
+    float* emb_scores = nullptr;                  // gnn_embed_dev without a scores pointer: the scores land here (grow-only, windows)
+    int64_t emb_scores_windows = 0;
     float* stage_scores = nullptr;
     float* stage_scores_host = nullptr;
     int64_t stage_windows = 0;
@@ -191,12 +195,16 @@ int launch_span_count(gnn_ctx* ctx, const uint8_t* seq, const int64_t* starts, c
 int launch_materialize(gnn_ctx* ctx, const uint8_t* seq, const int64_t* starts, const int32_t* lens, int64_t n,
                        uint8_t* bases);
 int launch_front_f32(gnn_ctx* ctx, const uint8_t* bases, int64_t n);         // -> ws.mp, ws.yp (+ ws.x)
-int launch_backend(gnn_ctx* ctx, int64_t n, int precision, float* scores_dev);   // ws.mp, ws.yp -> scores
+// ws.mp, ws.yp -> scores; emb_dev != NULL: also h1 (the encoder embedding) as emb_dev[n][GNN_EMBED_DIM] of emb_dtype (gnn_emb_dtype)
+int launch_backend(gnn_ctx* ctx, int64_t n, int precision, float* scores_dev, void* emb_dev = nullptr, int emb_dtype = GNN_EMB_F32);
 // one pass of the hot path over n windows whose padded bases are on the device (gnn_api.hip)
 // defer_last: leave the last chunk's back end pending on the second stream (gnn_classify_dev_async).  flush_backend()
 // makes ctx->stream wait for whatever is pending (the end of a synchronous classify_chunks); finish_pending() waits for it on
 // the host - every other entry point that enqueues on ctx->stream, reads scores or touches the workspaces calls it first
-int classify_chunks(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int precision, float* scores_dev, bool defer_last = false);
+// emb_dev != NULL: window i's embedding goes to row i of emb_dev (the rows of a chunk are its own, whichever workspace it ran in)
+int classify_chunks(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int precision, float* scores_dev, bool defer_last = false,
+                    void* emb_dev = nullptr, int emb_dtype = GNN_EMB_F32);
+size_t emb_elem_bytes(int emb_dtype);   // bytes of one embedding value (gnn_api.hip); 0 for a bad gnn_emb_dtype
 int flush_backend(gnn_ctx* ctx);
 int finish_pending(gnn_ctx* ctx);
 void free_contig_ws(gnn_ctx* ctx);     // gnn_contigs.hip

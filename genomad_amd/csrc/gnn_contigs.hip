@@ -41,6 +41,13 @@ struct ContigWorkspace {
     size_t bases_cap = 0;
     float* d_out = nullptr;
     size_t out_cap = 0;
+    // gnn_classify_contigs_embed: one slab's window embeddings (f32) and the per-contig running sums / kept-window counts
+    float* d_emb = nullptr;
+    size_t emb_cap = 0;
+    float* d_emb_sum = nullptr;
+    size_t emb_sum_cap = 0;
+    int32_t* d_emb_kept = nullptr;
+    size_t emb_kept_cap = 0;
 };
 
 template <typename Tp>
@@ -67,7 +74,8 @@ void free_contig_ws(gnn_ctx* ctx) {
     for (hipEvent_t e : w->piece_done) (void)hipEventDestroy(e);
     if (w->copy_stream) (void)hipStreamDestroy(w->copy_stream);
     for (void* p : {(void*)w->seq, (void*)w->d_starts, (void*)w->d_ids, (void*)w->d_lens, (void*)w->d_window_n,
-                    (void*)w->d_counts, (void*)w->d_scores, (void*)w->d_bases, (void*)w->d_out})
+                    (void*)w->d_counts, (void*)w->d_scores, (void*)w->d_bases, (void*)w->d_out, (void*)w->d_emb,
+                    (void*)w->d_emb_sum, (void*)w->d_emb_kept})
         if (p) (void)hipFree(p);
     delete w;
     ctx->contig_ws = nullptr;
@@ -98,14 +106,52 @@ __global__ void masked_segment_mean_kernel(const float* __restrict__ scores, con
     out[i] = kept ? s / (float)kept : 0.f;
 }
 
+// Per-contig embedding fold of one slab [a, a + m) of the window table: one block per contig the slab touches (ids are sorted, so
+// contigs ids[a] .. ids[a+m-1]), 128 lanes x 4 columns = one 2 KB row per step, read as float4s (coalesced: a row is contiguous).
+// The contig's kept windows of this slab are added to its running sum in window order, starting from what the slabs before left
+// there, so the sum is ((0 + e_0) + e_1) + ... whatever the slab and launch sizes.  Kept = the rule of masked_segment_mean_kernel.
+constexpr int FOLD_THREADS = HID / 4;
+
+__global__ __launch_bounds__(FOLD_THREADS) void emb_fold_kernel(const float* __restrict__ emb, const int64_t* __restrict__ ids,
+                                                                const int32_t* __restrict__ window_n, const int32_t* __restrict__ counts,
+                                                                int64_t a, int64_t m, float* __restrict__ sums, int32_t* __restrict__ kept) {
+    const int64_t seg = ids[a] + blockIdx.x;
+    int64_t lo = a, hi = a + m;                 // first window of the slab with ids >= seg
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (ids[mid] < seg) lo = mid + 1; else hi = mid;
+    }
+    float4* row = reinterpret_cast<float4*>(sums + (size_t)seg * HID) + threadIdx.x;
+    float4 s = *row;
+    int k = 0;
+    for (int64_t i = lo; i < a + m && ids[i] == seg; ++i)
+        if (window_n[i] == 0 || counts[i] <= MAX_N) {
+            const float4 v = reinterpret_cast<const float4*>(emb + (size_t)(i - a) * HID)[threadIdx.x];
+            s.x += v.x;
+            s.y += v.y;
+            s.z += v.z;
+            s.w += v.w;
+            ++k;
+        }
+    *row = s;
+    if (threadIdx.x == 0) kept[seg] += k;
+}
+
+// sums -> means in place (a contig without a kept window keeps its zero row, as the scores do)
+__global__ void emb_mean_kernel(float* __restrict__ sums, const int32_t* __restrict__ kept, int64_t n_contigs) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_contigs * HID) return;
+    const int k = kept[i / HID];
+    sums[i] = k ? sums[i] / (float)k : 0.f;
+}
+
 }  // namespace gnn
 
 using namespace gnn;
 
-extern "C" int gnn_classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes,
-                                    const int64_t* offsets_host, int64_t n_contigs, int single_window, int precision,
-                                    float* contig_scores_host, int64_t* window_ids_host, int64_t ids_capacity,
-                                    int64_t* n_windows_out) {
+static int classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes, const int64_t* offsets_host,
+                            int64_t n_contigs, int single_window, int precision, float* contig_scores_host, int64_t* window_ids_host,
+                            int64_t ids_capacity, int64_t* n_windows_out, float* contig_emb_host) {
     if (!ctx) {
         set_error("ctx is NULL");
         return GNN_ERR_ARG;
@@ -149,6 +195,7 @@ extern "C" int gnn_classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on
     const int64_t n = (int64_t)w.starts.size();
     *n_windows_out = 0;
     if (n_contigs) std::memset(contig_scores_host, 0, (size_t)n_contigs * GNN_CLASSES * sizeof(float));
+    if (n_contigs && contig_emb_host) std::memset(contig_emb_host, 0, (size_t)n_contigs * HID * sizeof(float));
     if (n == 0) return GNN_OK;
     if (!window_ids_host || ids_capacity < n) {
         set_error("window_ids_host holds " + std::to_string(ids_capacity) + " entries, " + std::to_string(n) + " candidate windows");
@@ -173,6 +220,16 @@ extern "C" int gnn_classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on
     const int64_t slab = std::min<int64_t>(n, 4 * std::max<int64_t>(ctx->chunk_fused, 1));
     if ((rc = grow(w.d_bases, w.bases_cap, (size_t)slab * W))) return rc;
     if ((rc = grow(w.d_out, w.out_cap, (size_t)n_contigs * GNN_CLASSES))) return rc;
+    if (contig_emb_host) {
+        // a slab's window embeddings (2 KB each) and the per-contig sums: never every window's row (10 M windows would be 20 GB)
+        if (w.emb_cap < (size_t)slab * HID || w.emb_sum_cap < (size_t)n_contigs * HID || w.emb_kept_cap < (size_t)n_contigs)
+            GNN_HIP(hipStreamSynchronize(ctx->stream));
+        if ((rc = grow(w.d_emb, w.emb_cap, (size_t)slab * HID))) return rc;
+        if ((rc = grow(w.d_emb_sum, w.emb_sum_cap, (size_t)n_contigs * HID))) return rc;
+        if ((rc = grow(w.d_emb_kept, w.emb_kept_cap, (size_t)n_contigs))) return rc;
+        GNN_HIP(hipMemsetAsync(w.d_emb_sum, 0, (size_t)n_contigs * HID * sizeof(float), ctx->stream));
+        GNN_HIP(hipMemsetAsync(w.d_emb_kept, 0, (size_t)n_contigs * sizeof(int32_t), ctx->stream));
+    }
     const uint8_t* seq_dev = seq;
     int64_t n_pieces = 0;
     if (seq_on_host) {
@@ -211,7 +268,22 @@ extern "C" int gnn_classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on
         }
         if ((rc = launch_span_count(ctx, seq_dev, w.d_starts + a, w.d_lens + a, m, 'N', w.d_counts + a))) return rc;
         if ((rc = launch_materialize(ctx, seq_dev, w.d_starts + a, w.d_lens + a, m, w.d_bases))) return rc;
-        if ((rc = classify_chunks(ctx, w.d_bases, m, precision, w.d_scores + a * GNN_CLASSES))) return rc;
+        if ((rc = classify_chunks(ctx, w.d_bases, m, precision, w.d_scores + a * GNN_CLASSES, false, contig_emb_host ? w.d_emb : nullptr,
+                                  GNN_EMB_F32)))
+            return rc;
+        if (contig_emb_host) {     // classify_chunks has ordered its back ends before ctx->stream: the slab's rows are complete
+            const int64_t touched = w.ids[a + m - 1] - w.ids[a] + 1;
+            hipLaunchKernelGGL(emb_fold_kernel, dim3((unsigned)touched), dim3(FOLD_THREADS), 0, ctx->stream, w.d_emb, w.d_ids,
+                               w.d_window_n, w.d_counts, a, m, w.d_emb_sum, w.d_emb_kept);
+            GNN_HIP(hipGetLastError());
+        }
+    }
+    if (contig_emb_host) {
+        const int64_t cells = n_contigs * HID;
+        hipLaunchKernelGGL(emb_mean_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, w.d_emb_sum, w.d_emb_kept,
+                           n_contigs);
+        GNN_HIP(hipGetLastError());
+        GNN_HIP(hipMemcpyAsync(contig_emb_host, w.d_emb_sum, (size_t)cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     }
     const int64_t threads = n_contigs * GNN_CLASSES;
     hipLaunchKernelGGL(masked_segment_mean_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream,
@@ -226,4 +298,29 @@ extern "C" int gnn_classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on
         if (w.window_n[i] == 0 || w.counts[i] <= MAX_N) window_ids_host[kept++] = w.ids[i];
     *n_windows_out = kept;
     return GNN_OK;
+}
+
+extern "C" int gnn_classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes,
+                                    const int64_t* offsets_host, int64_t n_contigs, int single_window, int precision,
+                                    float* contig_scores_host, int64_t* window_ids_host, int64_t ids_capacity,
+                                    int64_t* n_windows_out) {
+    return classify_contigs(ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision, contig_scores_host,
+                            window_ids_host, ids_capacity, n_windows_out, nullptr);
+}
+
+extern "C" int gnn_classify_contigs_embed(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes,
+                                          const int64_t* offsets_host, int64_t n_contigs, int single_window, int precision,
+                                          float* contig_scores_host, int64_t* window_ids_host, int64_t ids_capacity,
+                                          int64_t* n_windows_out, float* contig_emb_host) {
+    if (n_contigs > 0 && !contig_emb_host) {
+        set_error("bad argument to gnn_classify_contigs_embed: contig_emb_host is NULL");
+        return GNN_ERR_ARG;
+    }
+    if (precision == GNN_PREC_F16C6) {
+        set_error("gnn_classify_contigs_embed: GNN_PREC_F16C6 has no embedding path (the frozen mode's dense head runs on the matrix "
+                  "pipe and is outside the tolerance); use f16x3tc, f16x3tk, f16x3, bf16x3 or f32");
+        return GNN_ERR_ARG;
+    }
+    return classify_contigs(ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision, contig_scores_host,
+                            window_ids_host, ids_capacity, n_windows_out, n_contigs > 0 ? contig_emb_host : nullptr);
 }

@@ -167,6 +167,25 @@ class NNEngine:
     def flush(self):
         check(self.lib.gnn_classify_flush(self.ctx))
 
+    # -- encoder embeddings ---------------------------------------------------------------
+    def embed(self, bases, precision=_lib.DEFAULT_PRECISION, dtype="f32", with_scores=False):
+        """(n,6000) uint8 windows -> (n,512) encoder embeddings: create_encoder()'s output (model.py:14-31), the h1 the
+        classifier reads.  dtype "f32" -> float32; "bf16" -> uint16 bit patterns (the f32 values rounded to nearest even).
+        with_scores: also the (n,3) class scores of the same pass (bit-identical to :meth:`classify`), as (emb, scores)."""
+        b = self._check_bases(bases)
+        npdt = np.float32 if _lib.EMB_DTYPES[dtype] == _lib.EMB_F32 else np.uint16
+        emb = np.empty((len(b), _lib.EMBED_DIM), dtype=npdt)
+        scores = np.empty((len(b), _lib.CLASSES), dtype=np.float32) if with_scores else None
+        check(self.lib.gnn_embed(self.ctx, b.ctypes.data, len(b), _lib.PRECISIONS[precision], _lib.EMB_DTYPES[dtype],
+                                 emb.ctypes.data, scores.ctypes.data if with_scores else None))
+        return (emb, scores) if with_scores else emb
+
+    def embed_dev(self, bases_ptr: int, n: int, emb_ptr: int, precision=_lib.DEFAULT_PRECISION, dtype="f32", scores_ptr=None):
+        """Asynchronous: device pointers in and out (emb: n x 512 of ``dtype``; scores: n x 3 f32 or None), enqueued on the
+        engine's stream."""
+        check(self.lib.gnn_embed_dev(self.ctx, bases_ptr, int(n), _lib.PRECISIONS[precision], _lib.EMB_DTYPES[dtype], emb_ptr,
+                                     scores_ptr))
+
     def debug_forward(self, bases, precision="f32", taps=("m_a", "m_b", "yp_a", "yp_b",
                                                          "alpha_a", "alpha_b", "feat")):
         """Scores plus the requested intermediates as a dict of numpy arrays."""
@@ -204,7 +223,7 @@ class NNEngine:
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         return self._classify_contigs(seq_ptr, 0, int(offsets[-1]) if len(offsets) else 0, offsets, single_window, precision)
 
-    def _classify_contigs(self, seq_ptr, on_host, seq_bytes, offsets, single_window, precision):
+    def _classify_contigs(self, seq_ptr, on_host, seq_bytes, offsets, single_window, precision, embed=False):
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         if offsets.ndim != 1 or len(offsets) < 1:
             raise ValueError("offsets must hold n_contigs + 1 byte offsets")
@@ -213,10 +232,29 @@ class NNEngine:
         cap = int(((np.diff(offsets) + _lib.WINDOW - 1) // _lib.WINDOW).sum()) if n_contigs else 0
         ids = np.empty(max(cap, 1), dtype=np.int64)
         n = C.c_int64()
-        check(self.lib.gnn_classify_contigs(self.ctx, seq_ptr, int(on_host), int(seq_bytes), offsets.ctypes.data, n_contigs,
-                                            int(bool(single_window)), _lib.PRECISIONS[precision], scores.ctypes.data,
-                                            ids.ctypes.data, cap, C.byref(n)))
-        return scores, ids[:n.value].copy()
+        args = (self.ctx, seq_ptr, int(on_host), int(seq_bytes), offsets.ctypes.data, n_contigs, int(bool(single_window)),
+                _lib.PRECISIONS[precision], scores.ctypes.data, ids.ctypes.data, cap, C.byref(n))
+        if not embed:
+            check(self.lib.gnn_classify_contigs(*args))
+            return scores, ids[:n.value].copy()
+        emb = np.zeros((n_contigs, _lib.EMBED_DIM), dtype=np.float32)
+        check(self.lib.gnn_classify_contigs_embed(*args, emb.ctypes.data))
+        return scores, emb, ids[:n.value].copy()
+
+    def embed_contigs(self, seq: np.ndarray, offsets: np.ndarray, single_window: bool = False,
+                      precision=_lib.DEFAULT_PRECISION):
+        """:meth:`classify_contigs` plus the per-contig embedding (``gnn_classify_contigs_embed``): the f32 mean of the encoder
+        embeddings of the contig's kept windows, a zero row for a contig without one.  Returns (contig_scores (n_contigs, 3),
+        contig_embeddings (n_contigs, 512), contig ids of the kept windows); scores and ids are those of classify_contigs."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        return self._classify_contigs(seq.ctypes.data, 1, seq.nbytes, offsets, single_window, precision, embed=True)
+
+    def embed_contigs_dev(self, seq_ptr: int, offsets: np.ndarray, single_window: bool = False,
+                          precision=_lib.DEFAULT_PRECISION):
+        """Same as :meth:`embed_contigs` for a packed contig buffer that is already resident in HBM."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        return self._classify_contigs(seq_ptr, 0, int(offsets[-1]) if len(offsets) else 0, offsets, single_window, precision,
+                                      embed=True)
 
     def classify_contigs_spans(self, seq_ptr: int, offsets: np.ndarray, single_window: bool = False,
                                precision=_lib.DEFAULT_PRECISION):

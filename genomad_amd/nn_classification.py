@@ -62,6 +62,9 @@ class Outputs:
         self.provirus_window_id_output = self.encoded_proviruses_dir / f"{p}_provirus_window_id.npz"
         self.provirus_nn_classification_output = d / f"{p}_provirus_nn_classification.tsv"
         self.provirus_nn_classification_npz_output = d / f"{p}_provirus_nn_classification.npz"
+        # written only when GENOMAD_AMD_EMBEDDINGS=1 (encoder embeddings per contig; no counterpart in the reference)
+        self.nn_embeddings_output = d / f"{p}_nn_embeddings.npz"
+        self.provirus_nn_embeddings_output = d / f"{p}_provirus_nn_embeddings.npz"
         f = o / f"{p}_find_proviruses"
         self.find_proviruses_execution_info = f / f"{p}_find_proviruses.json"
         self.find_proviruses_output = f / f"{p}_provirus.tsv"
@@ -335,6 +338,25 @@ def classify_contigs_safely(eng, seq, offsets, single_window, precision, console
     return pr, wid
 
 
+def embed_contigs_safely(eng, seq, offsets, single_window, precision, console=None):
+    """NNEngine.embed_contigs with the range fallback of :func:`_range_fallback`: a piece whose scores come back non-finite is
+    recomputed with the next arithmetic, and its embeddings are those of that same recomputation.  (scores, embeddings, ids)."""
+    def run(a):
+        pr, emb, wid = eng.embed_contigs(seq, offsets, single_window, a)
+        return pr, (emb, wid)
+    pr, (emb, wid), _ = _with_range_fallback(run, precision, console)
+    return pr, emb, wid
+
+
+def embeddings_requested() -> bool:
+    """GENOMAD_AMD_EMBEDDINGS=1: main() also writes the per-contig encoder embeddings (<prefix>_nn_embeddings.npz); unset or 0:
+    nothing changes.  Any other value is an error."""
+    v = os.environ.get("GENOMAD_AMD_EMBEDDINGS", "0").strip()
+    if v not in ("", "0", "1"):
+        raise ValueError(f"GENOMAD_AMD_EMBEDDINGS={v!r}: expected 1 (write the embeddings) or 0")
+    return v == "1"
+
+
 # ---- runtime parity sentinel (VERDICT r04 item 4) ---------------------------------------------------------------------
 # The 1e-4 claim of the production arithmetic has only ever met synthetic weights (the trained nn_classifier.h5 is not in the
 # checkout).  So every run of main() classifies its first windows a second time with the exact-f32 device path (GNN_PREC_F32:
@@ -453,6 +475,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     from . import rccl, sharding
     rccl.prepare_env()        # before ANY HIP call: drops the reference's CUDA_VISIBLE_DEVICES=-1 (:8)
     configured_precision()    # a mistyped GENOMAD_AMD_PRECISION stops here
+    embeddings = embeddings_requested()
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -470,6 +493,11 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     parameter_dict = {"single_window": single_window}
     md5_async(input_path)            # starts hashing now; check_fasta and the stages overlap with it
     device_front_end = _backend is None and os.environ.get("GENOMAD_AMD_FRONT_END", "device") == "device"
+    if embeddings and not device_front_end:
+        # the per-window host path (GpuBackend) has no embedding output: stop rather than leave the requested file out
+        console.error("GENOMAD_AMD_EMBEDDINGS=1 needs the device front end: the host front end (GENOMAD_AMD_FRONT_END=host) does "
+                      "not compute encoder embeddings. Unset GENOMAD_AMD_FRONT_END or GENOMAD_AMD_EMBEDDINGS.")
+        sys.exit(1)
 
     def everywhere(*flags):
         """Decisions read from files that rank 0 is about to rewrite are taken on rank 0 and made known to
@@ -592,15 +620,16 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         if rank0:
             write_tsv(tsv_path, names, predictions)                                  # :340-352 (always rewritten)
 
-    def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what):
+    def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, emb_path=None):
         """Product path: the contig front end (NNEngine.classify_contigs) does windowing, the N rule,
         tokenising, classification and the per-contig mean on the GPU, so encoding and classification
         are one step; ``<prefix>_seq_window_id.npz`` is still written.  With several ranks the CONTIGS are
         sharded: every rank reads and packs only its own record-aligned byte range of the file (for
         compressed inputs: every world-th record-aligned chunk of the decompressed stream), classifies it
         on its GPU, and rank 0 collects the per-contig scores with one gather and writes the files —
-        results are bit-identical for any number of ranks."""
-        (have_npz,) = everywhere(rank0 and skip and npz_path.exists())                   # :284-292
+        results are bit-identical for any number of ranks.  ``emb_path`` (GENOMAD_AMD_EMBEDDINGS=1): the per-contig encoder
+        embeddings are computed in the same pass and written there; a run that finds the scores but not that file classifies again."""
+        (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and (emb_path is None or emb_path.exists()))   # :284-292
         names = predictions = None
         if have_npz:
             gate()
@@ -614,7 +643,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             eng = _engine()
             size = Path(fasta).stat().st_size * (1 if sequence.compression_of(fasta) == "uncompressed" else 4)
             precision = select_arithmetic(eng, precision, size, comm, console)
-            parts = []
+            parts, emb_parts = [], []
             sentinel = {"d": None, "done": False}
 
             def classify(sq, off):
@@ -623,7 +652,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     sentinel["d"] = parity_sentinel(eng, sentinel_windows(sq, off, single_window), precision, console)
                     if comm is None:                                # one rank: a failed check stops the run here, not after the whole
                         sentinel_verdict(None, sentinel["d"], console, precision)       # file (several ranks leave together below)
-                return classify_contigs_safely(eng, sq, off, single_window, precision, console)
+                if emb_path is not None:
+                    return embed_contigs_safely(eng, sq, off, single_window, precision, console)
+                pr, wid = classify_contigs_safely(eng, sq, off, single_window, precision, console)
+                return pr, None, wid
 
             validate = sharded_check and fasta is input_path        # the provirus FASTA is geNomad's own output: never validated
             seen = []                                               # digests of the accessions of ALL records of this rank's share (validate)
@@ -646,8 +678,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                         nm, sq, off = nxt.result()
                         if k + 1 < pieces:
                             nxt = pool.submit(read, k + 1)
-                        pr, wid = classify(sq, off)
+                        pr, emb, wid = classify(sq, off)
                         parts.append((rank * 64 + k, nm, pr, wid))
+                        emb_parts.append((rank * 64 + k, emb))
             else:
                 # compressed streams cannot be read by byte range: every rank decompresses the stream
                 # chunk by chunk (bounded memory) and packs + classifies every world-th chunk
@@ -655,13 +688,15 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     if i % world != rank:
                         continue
                     nm, sq, off = pack(chunk)
-                    pr, wid = classify(sq, off)
+                    pr, emb, wid = classify(sq, off)
                     parts.append((i, nm, pr, wid))
+                    emb_parts.append((i, emb))
             if validate:
                 digests = np.concatenate(seen) if seen else np.zeros(0, dtype="<u8")
                 state["verdict"] = sharding.fasta_verdict(comm, digests, lambda: sequence.check_fasta(input_path))
             sentinel_verdict(comm, sentinel["d"], console, precision)      # before anything is written
             names, predictions, ids, n_windows = sharding.gather_contig_parts(comm, parts)
+            embeddings_all = sharding.gather_contig_embeddings(comm, emb_parts) if emb_path is not None else None
             gate()
             if not n_windows:                                                        # :297-299
                 console.error("No sequences were found. Please check your input FASTA.")
@@ -673,6 +708,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                 np.savez_compressed(wid_path, **{names_key: names, ids_key: ids})
                 console.log(f"{what.capitalize()}s classified ({len(ids)} windows).")
                 np.savez_compressed(npz_path, **{names_key: names, "predictions": predictions})
+                if emb_path is not None:
+                    np.savez_compressed(emb_path, **{names_key: names, "embeddings": embeddings_all})
+                    console.log(f"Encoder embeddings of the {what}s written to {emb_path.name}.")
         if cleanup and rank0 and enc_dir.is_dir():
             console.log(f"Deleting encoded {what} data.")
             shutil.rmtree(enc_dir)
@@ -680,14 +718,16 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             write_tsv(tsv_path, names, predictions)
 
     run = stage_device if device_front_end else stage
+    emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
     try:
         run(input_path, outputs.encoded_sequences_dir, outputs.seq_window_id_output,
             outputs.nn_classification_npz_output, outputs.nn_classification_output,
-            "contig_names", "contig_ids", "sequence")
+            "contig_names", "contig_ids", "sequence", **emb_kw(outputs.nn_embeddings_output))
         if classify_proviruses:                                                      # :248-281, :355-425
             run(outputs.find_proviruses_nucleotide_output, outputs.encoded_proviruses_dir,
                 outputs.provirus_window_id_output, outputs.provirus_nn_classification_npz_output,
-                outputs.provirus_nn_classification_output, "provirus_names", "provirus_ids", "provirus")
+                outputs.provirus_nn_classification_output, "provirus_names", "provirus_ids", "provirus",
+                **emb_kw(outputs.provirus_nn_embeddings_output))
     finally:
         if check_pool is not None:
             check_pool.shutdown(wait=True)

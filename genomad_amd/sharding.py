@@ -157,6 +157,37 @@ def gather_contig_parts(comm, parts, root: int = 0):
             np.concatenate(out_ids) if out_ids else np.zeros(0, np.int64), total_windows)
 
 
+def gather_contig_embeddings(comm, parts, width: int = 512, root: int = 0):
+    """Per-contig rows of contig-sharded pieces -> ``root``, in the piece order of :func:`gather_contig_parts`.  ``parts`` = this
+    rank's list of (order_key, rows (k, width) float32), the same keys and contig counts as the pieces handed to
+    gather_contig_parts (the encoder embeddings of main()).  The rows travel in ONE padded gather, the piece table as bytes; the
+    rows are only moved, so the table is bit-identical for any number of ranks.  Returns (n_contigs, width) float32 on ``root``,
+    None elsewhere."""
+    comm = comm or LocalComm()
+    parts = list(parts)
+    table = np.array([[int(key), len(rows)] for key, rows in parts], dtype="<i8").reshape(-1, 2)
+    k = int(table[:, 1].sum()) if len(table) else 0
+    per = max(int(comm.allgather_i64([k])[:, 0].max()), 1)
+    send = np.zeros((per, width), np.float32)
+    if k:
+        send[:k] = np.concatenate([np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, width) for _, rows in parts])
+    got = comm.gather_array(send, root)
+    table_blobs = gather_bytes(comm, table.tobytes(), root)
+    if comm.rank != root:
+        return None
+    pieces = []                      # (order_key, rank, contig slice)
+    for r in range(comm.world):
+        c0 = 0
+        for key, nc in np.frombuffer(table_blobs[r], dtype="<i8").reshape(-1, 2):
+            pieces.append((int(key), r, c0, c0 + int(nc)))
+            c0 += int(nc)
+    pieces.sort()
+    if len({p[0] for p in pieces}) != len(pieces):
+        raise ValueError("duplicate piece keys in gather_contig_embeddings")
+    out = [got[r][c0:c1] for _, r, c0, c1 in pieces]
+    return np.concatenate(out, axis=0) if out else np.zeros((0, width), np.float32)
+
+
 def gather_contig_results(comm, names, predictions, window_ids, root: int = 0):
     """One piece per rank, in rank order (see :func:`gather_contig_parts`)."""
     comm = comm or LocalComm()

@@ -37,6 +37,7 @@ extern "C" {
 #define GNN_FEAT 256         /* igloo.py:83                 concat of the two IGLOO heads  */
 #define GNN_HIDDEN 512       /* model.py:28,40                                             */
 #define GNN_CLASSES 3        /* model.py:44                 chromosome, plasmid, virus     */
+#define GNN_EMBED_DIM 512    /* model.py:28                 create_encoder()'s output width (= GNN_HIDDEN) */
 
 typedef enum gnn_status {
     GNN_OK = 0,
@@ -91,6 +92,9 @@ typedef enum gnn_precision {
 int gnn_has_experimental(void);
 
 typedef enum gnn_onehot_dtype { GNN_OH_U8 = 0, GNN_OH_BF16 = 1, GNN_OH_F32 = 2 } gnn_onehot_dtype;
+
+/* dtype of an embedding row: f32, or bf16 (the f32 value rounded to nearest even; a NaN stays a NaN) */
+typedef enum gnn_emb_dtype { GNN_EMB_F32 = 0, GNN_EMB_BF16 = 1 } gnn_emb_dtype;
 
 /*
  * Weights in the reference's own layouts (what Keras load_weights would put into the
@@ -216,6 +220,18 @@ int gnn_classify_flush(gnn_ctx* ctx);
 int gnn_classify_dev(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n_windows, int precision,
                      float* scores_dev);   /* asynchronous on the ctx stream */
 
+/* ---- encoder embeddings: create_encoder()'s output (model.py:14-31: one-hot -> IGLOO block -> Dense512 -> BatchNorm -> ReLU),
+ * the h1 of the dense head, which the classifier (model.py:34-45) reads and then drops.  The same forward pass as gnn_classify:
+ * emb[n][GNN_EMBED_DIM] of emb_dtype (gnn_emb_dtype) per window, and - when the scores pointer is not NULL - the class scores,
+ * bit-identical to gnn_classify / gnn_classify_dev.  A NaN of an f16 arithmetic's overflow stays a NaN in both (the range fallback
+ * of main() recomputes the batch).  GNN_PREC_F16C6 (frozen, outside the tolerance) has no embedding path: GNN_ERR_ARG.
+ * gnn_embed: host pointers, synchronous, chunked like gnn_classify.  gnn_embed_dev: device pointers, asynchronous on the ctx
+ * stream like gnn_classify_dev. */
+int gnn_embed(gnn_ctx* ctx, const uint8_t* bases_host, int64_t n_windows, int precision, int emb_dtype, void* emb_host,
+              float* scores_host_or_null);
+int gnn_embed_dev(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n_windows, int precision, int emb_dtype, void* emb_dev,
+                  float* scores_dev_or_null);
+
 /* replaces tf.math.segment_mean(pred, contig_ids) nn_classification.py:320.
  * ids sorted ascending, out has n_segments rows (zero row for an id with no window). */
 int gnn_segment_mean(gnn_ctx* ctx, const float* scores_host, const int64_t* ids_host, int64_t n,
@@ -247,6 +263,15 @@ int gnn_classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int6
                          const int64_t* offsets_host, int64_t n_contigs, int single_window, int precision,
                          float* contig_scores_host, int64_t* window_ids_host, int64_t ids_capacity,
                          int64_t* n_windows_out);
+/* gnn_classify_contigs plus the per-contig embedding: contig_emb_host[n_contigs][GNN_EMBED_DIM] f32 = mean of the encoder
+ * embeddings (see gnn_embed) of the contig's KEPT windows - the windows and the N rule of the scores' mean - and a zero row for a
+ * contig without one.  Window embeddings are folded into per-contig f32 sums on the device after every slab of windows, added in
+ * window order (a contig may straddle slabs), so the result does not depend on gnn_set_chunk; they never leave the device.
+ * Scores and window ids are bit-identical to gnn_classify_contigs.  GNN_PREC_F16C6: GNN_ERR_ARG. */
+int gnn_classify_contigs_embed(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes,
+                               const int64_t* offsets_host, int64_t n_contigs, int single_window, int precision,
+                               float* contig_scores_host, int64_t* window_ids_host, int64_t ids_capacity,
+                               int64_t* n_windows_out, float* contig_emb_host);
 
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
