@@ -10,6 +10,10 @@
 // classified, windows the rule drops (window_n > 0 and more than 4000 literal 'N') just do not enter their
 // contig's mean, so no host round trip sits between the rule and the classification.  (Dropped windows are
 // rare: they cost one window's work each.)  All buffers are persistent and grow-only (gnn_destroy frees them).
+//
+// gnn_scan_contigs is the same function at a stride: windows start every `stride` bases instead of every 6000, their scores DO
+// leave the device, and a fold kernel turns them into a track of one score triple per stride-wide bin ("Score tracks").
+// At stride 6000 the span table, and with it every bit of the contig scores, is the one of gnn_classify_contigs.
 #include <algorithm>
 #include <cstring>
 
@@ -48,7 +52,38 @@ struct ContigWorkspace {
     size_t emb_sum_cap = 0;
     int32_t* d_emb_kept = nullptr;
     size_t emb_kept_cap = 0;
+    // gnn_scan_contigs: CSR offsets of every contig's windows and bins, the track (3 f32 per bin) and its cover counts
+    std::vector<int64_t> win_off, bin_off;
+    int64_t* d_win_off = nullptr;
+    int64_t* d_bin_off = nullptr;
+    size_t off_cap = 0;
+    float* d_track = nullptr;
+    int32_t* d_cover = nullptr;
+    size_t bin_cap = 0;
 };
+
+// What gnn_scan_contigs adds to a call of classify_contigs: host buffers for the per-window and per-bin results.
+struct ScanOut {
+    float* window_scores;
+    uint8_t* window_kept;       // may be NULL
+    int64_t windows_capacity;
+    float* track;               // may be NULL
+    int32_t* cover;             // may be NULL
+    int64_t bins_capacity;
+};
+
+// The window rule, once: seq_windows(seq, 6000, 2500, max_windows) of the reference (sequence.py:150-167) with the window start
+// advancing by `stride` instead of 6000.  Window 0 always exists; window k > 0 exists while no earlier window reached the contig's
+// end and its own length is at least MIN_TAIL.  f(k, length).  At stride == W this is the loop gnn_classify_contigs always ran.
+template <typename F>
+static inline void for_each_window(int64_t len, int64_t stride, int single_window, F&& f) {
+    for (int64_t k = 0; k * stride < len; ++k) {
+        const int64_t l = std::min<int64_t>(W, len - k * stride);
+        if (l < MIN_TAIL && k > 0) break;             // a short tail is dropped, a short first window kept
+        f(k, l);
+        if (l < MIN_TAIL || (single_window && k == 0) || k * stride + W >= len) break;
+    }
+}
 
 template <typename Tp>
 static int grow(Tp*& p, size_t& cap, size_t need, size_t elem = sizeof(Tp)) {
@@ -75,7 +110,8 @@ void free_contig_ws(gnn_ctx* ctx) {
     if (w->copy_stream) (void)hipStreamDestroy(w->copy_stream);
     for (void* p : {(void*)w->seq, (void*)w->d_starts, (void*)w->d_ids, (void*)w->d_lens, (void*)w->d_window_n,
                     (void*)w->d_counts, (void*)w->d_scores, (void*)w->d_bases, (void*)w->d_out, (void*)w->d_emb,
-                    (void*)w->d_emb_sum, (void*)w->d_emb_kept})
+                    (void*)w->d_emb_sum, (void*)w->d_emb_kept, (void*)w->d_win_off, (void*)w->d_bin_off, (void*)w->d_track,
+                    (void*)w->d_cover})
         if (p) (void)hipFree(p);
     delete w;
     ctx->contig_ws = nullptr;
@@ -145,13 +181,49 @@ __global__ void emb_mean_kernel(float* __restrict__ sums, const int32_t* __restr
     sums[i] = k ? sums[i] / (float)k : 0.f;
 }
 
+// The track fold of gnn_scan_contigs: one thread per (bin, class), the output index is the thread index (coalesced stores).  Bin b
+// of a contig is [b * stride, (b + 1) * stride); window k covers it iff k <= b and b * stride < k * stride + len_k, which bounds
+// k from below by b - (W - 1) / stride: at most ceil(W / stride) windows, read in increasing k and added in that order in f32 (the
+// order is part of the contract: no atomics), divided once.  Kept = the rule of masked_segment_mean_kernel.  A bin without a kept
+// covering window (a dropped tail, or every covering window masked by the N rule) is NaN in all three classes, cover 0.
+__global__ void scan_track_kernel(const float* __restrict__ scores, const int32_t* __restrict__ lens, const int32_t* __restrict__ counts,
+                                  const int64_t* __restrict__ win_off, const int64_t* __restrict__ bin_off, int64_t n_contigs,
+                                  int64_t n_bins, int stride, float* __restrict__ track, int32_t* __restrict__ cover) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_bins * GNN_CLASSES) return;
+    const int64_t bin = i / GNN_CLASSES;
+    const int cl = (int)(i % GNN_CLASSES);
+    int64_t lo = 0, hi = n_contigs - 1;            // the contig with bin_off[c] <= bin < bin_off[c + 1] (empty contigs own no bin)
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (bin_off[mid + 1] <= bin) lo = mid + 1; else hi = mid;
+    }
+    const int64_t b = bin - bin_off[lo];
+    const int64_t w0 = win_off[lo], nw = win_off[lo + 1] - w0;
+    const int64_t reach = (W - 1) / stride;
+    const int64_t k_lo = b > reach ? b - reach : 0, k_hi = b < nw - 1 ? b : nw - 1;
+    float s = 0.f;
+    int kept = 0;
+    for (int64_t k = k_lo; k <= k_hi; ++k) {
+        const int64_t j = w0 + k;
+        if (b * stride < k * stride + lens[j] && (k == 0 || counts[j] <= MAX_N)) {
+            s += scores[j * GNN_CLASSES + cl];
+            ++kept;
+        }
+    }
+    track[i] = kept ? s / (float)kept : __builtin_nanf("");
+    if (cl == 0) cover[bin] = kept;
+}
+
 }  // namespace gnn
 
 using namespace gnn;
 
 static int classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes, const int64_t* offsets_host,
                             int64_t n_contigs, int single_window, int precision, float* contig_scores_host, int64_t* window_ids_host,
-                            int64_t ids_capacity, int64_t* n_windows_out, float* contig_emb_host) {
+                            int64_t ids_capacity, int64_t* n_windows_out, float* contig_emb_host, int64_t stride = W,
+                            const ScanOut* scan = nullptr) {
+    const char* const fn = scan ? "gnn_scan_contigs" : "gnn_classify_contigs";
     if (!ctx) {
         set_error("ctx is NULL");
         return GNN_ERR_ARG;
@@ -161,9 +233,9 @@ static int classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, i
         const int frc = finish_pending(ctx);
         if (frc) return frc;
     }
-    if (n_contigs < 0 || seq_bytes < 0 || !offsets_host || !n_windows_out || (n_contigs > 0 && !contig_scores_host) ||
+    if (n_contigs < 0 || seq_bytes < 0 || !offsets_host || !n_windows_out || (n_contigs > 0 && !contig_scores_host && !scan) ||
         (seq_bytes > 0 && !seq)) {
-        set_error("bad argument to gnn_classify_contigs");
+        set_error(std::string("bad argument to ") + fn);
         return GNN_ERR_ARG;
     }
     if (offsets_host[0] < 0 || offsets_host[n_contigs] > seq_bytes) {
@@ -173,31 +245,43 @@ static int classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, i
     if (!ctx->contig_ws) ctx->contig_ws = new ContigWorkspace();
     ContigWorkspace& w = *ctx->contig_ws;
 
-    // ---- candidate windows: seq_windows(seq, 6000, 2500, max_windows) for every contig (sequence.py:150-167)
+    // ---- candidate windows: seq_windows(seq, 6000, 2500, max_windows) for every contig (sequence.py:150-167), at `stride`
     w.starts.clear(), w.lens.clear(), w.ids.clear(), w.window_n.clear();
+    w.win_off.assign(1, 0), w.bin_off.assign(1, 0);
     for (int64_t c = 0; c < n_contigs; ++c) {
         const int64_t a = offsets_host[c], b = offsets_host[c + 1];
         if (b < a) {
             set_error("contig offsets are not non-decreasing");
             return GNN_ERR_ARG;
         }
-        const int64_t len = b - a;
-        for (int64_t k = 0; k * W < len; ++k) {
-            const int64_t l = std::min<int64_t>(W, len - k * W);
-            if (l < MIN_TAIL && k > 0) break;             // a short tail is dropped, a short first window kept
-            w.starts.push_back(a + k * W);
+        for_each_window(b - a, stride, single_window, [&](int64_t k, int64_t l) {
+            w.starts.push_back(a + k * stride);
             w.lens.push_back((int32_t)l);
             w.ids.push_back(c);
             w.window_n.push_back((int32_t)k);
-            if (l < MIN_TAIL || (single_window && k == 0)) break;
+        });
+        if (scan) {
+            w.win_off.push_back((int64_t)w.starts.size());
+            w.bin_off.push_back(w.bin_off.back() + (b - a + stride - 1) / stride);
         }
     }
     const int64_t n = (int64_t)w.starts.size();
+    const int64_t n_bins = w.bin_off.back();
+    const bool fold = scan && (scan->track || scan->cover);
     *n_windows_out = 0;
-    if (n_contigs) std::memset(contig_scores_host, 0, (size_t)n_contigs * GNN_CLASSES * sizeof(float));
+    if (n_contigs && contig_scores_host) std::memset(contig_scores_host, 0, (size_t)n_contigs * GNN_CLASSES * sizeof(float));
     if (n_contigs && contig_emb_host) std::memset(contig_emb_host, 0, (size_t)n_contigs * HID * sizeof(float));
     if (n == 0) return GNN_OK;
-    if (!window_ids_host || ids_capacity < n) {
+    if (scan) {
+        if (!scan->window_scores || scan->windows_capacity < n) {
+            set_error("window_scores_host holds " + std::to_string(scan->windows_capacity) + " windows, the scan has " + std::to_string(n));
+            return GNN_ERR_ARG;
+        }
+        if (fold && scan->bins_capacity < n_bins) {
+            set_error("track_host / cover_host hold " + std::to_string(scan->bins_capacity) + " bins, the scan has " + std::to_string(n_bins));
+            return GNN_ERR_ARG;
+        }
+    } else if (!window_ids_host || ids_capacity < n) {
         set_error("window_ids_host holds " + std::to_string(ids_capacity) + " entries, " + std::to_string(n) + " candidate windows");
         return GNN_ERR_ARG;
     }
@@ -214,12 +298,28 @@ static int classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, i
         if (!rc) rc = grow(w.d_window_n, c4, (size_t)n);
         if (!rc) rc = grow(w.d_counts, c5, (size_t)n);
         if (!rc) rc = grow(w.d_scores, c6, (size_t)n * GNN_CLASSES);
-        w.span_cap = rc ? 0 : c1;
+        // in windows: grow()'s head-room is counted in elements, so the scores buffer (3 per window) holds fewer windows than c1
+        w.span_cap = rc ? 0 : std::min(c1, c6 / GNN_CLASSES);
         if (rc) return rc;
     }
     const int64_t slab = std::min<int64_t>(n, 4 * std::max<int64_t>(ctx->chunk_fused, 1));
     if ((rc = grow(w.d_bases, w.bases_cap, (size_t)slab * W))) return rc;
     if ((rc = grow(w.d_out, w.out_cap, (size_t)n_contigs * GNN_CLASSES))) return rc;
+    if (fold) {        // 16 B per contig and 16 B per bin (hipFree of a buffer that grows waits for the kernels that read it)
+        if (w.off_cap < (size_t)n_contigs + 1) {
+            size_t c1 = 0, c2 = 0;
+            if (!rc) rc = grow(w.d_win_off, c1, (size_t)n_contigs + 1);
+            if (!rc) rc = grow(w.d_bin_off, c2, (size_t)n_contigs + 1);
+            w.off_cap = rc ? 0 : c1;
+        }
+        if (!rc && w.bin_cap < (size_t)n_bins) {
+            size_t c1 = 0, c2 = 0;
+            if (!rc) rc = grow(w.d_track, c1, (size_t)n_bins * GNN_CLASSES);
+            if (!rc) rc = grow(w.d_cover, c2, (size_t)n_bins);
+            w.bin_cap = rc ? 0 : std::min(c1 / GNN_CLASSES, c2);       // in bins (see span_cap)
+        }
+        if (rc) return rc;
+    }
     if (contig_emb_host) {
         // a slab's window embeddings (2 KB each) and the per-contig sums: never every window's row (10 M windows would be 20 GB)
         if (w.emb_cap < (size_t)slab * HID || w.emb_sum_cap < (size_t)n_contigs * HID || w.emb_kept_cap < (size_t)n_contigs)
@@ -290,12 +390,36 @@ static int classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, i
                        w.d_scores, w.d_ids, w.d_window_n, w.d_counts, n, n_contigs, w.d_out);
     GNN_HIP(hipGetLastError());
     w.counts.resize((size_t)n);
-    GNN_HIP(hipMemcpyAsync(contig_scores_host, w.d_out, (size_t)threads * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (contig_scores_host)
+        GNN_HIP(hipMemcpyAsync(contig_scores_host, w.d_out, (size_t)threads * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     GNN_HIP(hipMemcpyAsync(w.counts.data(), w.d_counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (scan) {
+        GNN_HIP(hipMemcpyAsync(scan->window_scores, w.d_scores, (size_t)n * GNN_CLASSES * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        if (fold) {
+            const size_t off_bytes = (size_t)(n_contigs + 1) * sizeof(int64_t);
+            GNN_HIP(hipMemcpyAsync(w.d_win_off, w.win_off.data(), off_bytes, hipMemcpyHostToDevice, ctx->stream));
+            GNN_HIP(hipMemcpyAsync(w.d_bin_off, w.bin_off.data(), off_bytes, hipMemcpyHostToDevice, ctx->stream));
+            const int64_t cells = n_bins * GNN_CLASSES;
+            hipLaunchKernelGGL(scan_track_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, w.d_scores, w.d_lens,
+                               w.d_counts, w.d_win_off, w.d_bin_off, n_contigs, n_bins, (int)stride, w.d_track, w.d_cover);
+            GNN_HIP(hipGetLastError());
+            if (scan->track)
+                GNN_HIP(hipMemcpyAsync(scan->track, w.d_track, (size_t)cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+            if (scan->cover)
+                GNN_HIP(hipMemcpyAsync(scan->cover, w.d_cover, (size_t)n_bins * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
     GNN_HIP(hipStreamSynchronize(ctx->stream));
     int64_t kept = 0;
-    for (int64_t i = 0; i < n; ++i)
-        if (w.window_n[i] == 0 || w.counts[i] <= MAX_N) window_ids_host[kept++] = w.ids[i];
+    for (int64_t i = 0; i < n; ++i) {
+        const bool keep = w.window_n[i] == 0 || w.counts[i] <= MAX_N;
+        if (scan) {
+            if (scan->window_kept) scan->window_kept[i] = keep ? 1 : 0;
+            kept += keep;
+        } else if (keep) {
+            window_ids_host[kept++] = w.ids[i];
+        }
+    }
     *n_windows_out = kept;
     return GNN_OK;
 }
@@ -323,4 +447,54 @@ extern "C" int gnn_classify_contigs_embed(gnn_ctx* ctx, const uint8_t* seq, int 
     }
     return classify_contigs(ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision, contig_scores_host,
                             window_ids_host, ids_capacity, n_windows_out, n_contigs > 0 ? contig_emb_host : nullptr);
+}
+
+static int check_stride(int stride, const char* fn) {
+    if (stride >= 1 && stride <= W) return GNN_OK;
+    set_error(std::string(fn) + ": stride " + std::to_string(stride) + " is outside [1, " + std::to_string(W) + "]");
+    return GNN_ERR_ARG;
+}
+
+extern "C" int gnn_scan_plan(const int64_t* offsets_host, int64_t n_contigs, int stride, int single_window, int64_t* n_windows_out,
+                             int64_t* n_bins_out, int64_t* win_offsets_or_null, int64_t* bin_offsets_or_null, int64_t* starts_or_null,
+                             int32_t* lens_or_null) {
+    if (!offsets_host || n_contigs < 0 || !n_windows_out || !n_bins_out) {
+        set_error("bad argument to gnn_scan_plan");
+        return GNN_ERR_ARG;
+    }
+    if (int rc = check_stride(stride, "gnn_scan_plan")) return rc;
+    for (int64_t c = 0; c < n_contigs; ++c)
+        if (offsets_host[c + 1] < offsets_host[c]) {
+            set_error("contig offsets are not non-decreasing");
+            return GNN_ERR_ARG;
+        }
+    int64_t n = 0, bins = 0;
+    if (win_offsets_or_null) win_offsets_or_null[0] = 0;
+    if (bin_offsets_or_null) bin_offsets_or_null[0] = 0;
+    for (int64_t c = 0; c < n_contigs; ++c) {
+        const int64_t len = offsets_host[c + 1] - offsets_host[c];
+        for_each_window(len, stride, single_window, [&](int64_t k, int64_t l) {
+            if (starts_or_null) starts_or_null[n] = k * stride;
+            if (lens_or_null) lens_or_null[n] = (int32_t)l;
+            ++n;
+        });
+        bins += (len + stride - 1) / stride;
+        if (win_offsets_or_null) win_offsets_or_null[c + 1] = n;
+        if (bin_offsets_or_null) bin_offsets_or_null[c + 1] = bins;
+    }
+    *n_windows_out = n;
+    *n_bins_out = bins;
+    return GNN_OK;
+}
+
+extern "C" int gnn_scan_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes, const int64_t* offsets_host,
+                                int64_t n_contigs, int stride, int single_window, int precision, float* window_scores_host,
+                                uint8_t* window_kept_host_or_null, int64_t windows_capacity, float* track_host_or_null,
+                                int32_t* cover_host_or_null, int64_t bins_capacity, float* contig_scores_host_or_null) {
+    if (int rc = check_stride(stride, "gnn_scan_contigs")) return rc;
+    const ScanOut scan{window_scores_host, window_kept_host_or_null, windows_capacity, track_host_or_null, cover_host_or_null,
+                       bins_capacity};
+    int64_t kept = 0;
+    return classify_contigs(ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision,
+                            contig_scores_host_or_null, nullptr, 0, &kept, nullptr, stride, &scan);
 }

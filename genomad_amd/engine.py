@@ -38,6 +38,21 @@ class DeviceBuffer:
             self.ptr = None
 
 
+class ScanResult:
+    """What :meth:`NNEngine.scan_contigs` returns.  Windows (CSR over contigs by ``win_offsets``): ``starts`` (contig-relative),
+    ``lens``, ``kept`` (bool: the N rule's mask), ``scores`` (n_windows, 3).  Bins (CSR by ``bin_offsets``, ``stride`` bases each):
+    ``track`` (n_bins, 3; NaN where ``cover`` == 0), ``cover`` (kept windows averaged into the bin).  ``contig_scores``
+    (n_contigs, 3): the mean of each contig's kept windows."""
+    FIELDS = ("stride", "win_offsets", "starts", "lens", "kept", "scores", "bin_offsets", "track", "cover", "contig_scores")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw[k])
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+
 class NNEngine:
     def __init__(self, device: int = 0, weights: dict = None, chunk: int = None):
         self.lib = _lib.load()
@@ -255,6 +270,52 @@ class NNEngine:
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         return self._classify_contigs(seq_ptr, 0, int(offsets[-1]) if len(offsets) else 0, offsets, single_window, precision,
                                       embed=True)
+
+    # -- score tracks --------------------------------------------------------------------
+    def scan_plan(self, offsets: np.ndarray, stride: int, single_window: bool = False):
+        """``gnn_scan_plan`` (host only): (win_offsets, bin_offsets, contig-relative starts, lens) of a scan at ``stride``."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError("offsets must hold n_contigs + 1 byte offsets")
+        n_contigs = len(offsets) - 1
+        nw, nb = C.c_int64(), C.c_int64()
+        head = (offsets.ctypes.data, n_contigs, int(stride), int(bool(single_window)), C.byref(nw), C.byref(nb))
+        check(self.lib.gnn_scan_plan(*head, None, None, None, None))
+        win_off, bin_off = np.zeros(n_contigs + 1, np.int64), np.zeros(n_contigs + 1, np.int64)
+        starts, lens = np.zeros(nw.value, np.int64), np.zeros(nw.value, np.int32)
+        check(self.lib.gnn_scan_plan(*head, win_off.ctypes.data, bin_off.ctypes.data, starts.ctypes.data, lens.ctypes.data))
+        return win_off, bin_off, starts, lens
+
+    def scan_contigs(self, seq: np.ndarray, offsets: np.ndarray, stride: int, single_window: bool = False,
+                     precision=_lib.DEFAULT_PRECISION) -> ScanResult:
+        """Score track along every contig (``gnn_scan_contigs``): overlapping 6000-base windows every ``stride`` bases
+        (1 <= stride <= 6000), each scored by the forward pass of :meth:`classify`, and their mean per stride-wide bin - where in
+        a contig the signal is, which :meth:`classify_contigs` averages away.  The window and bin rules are those of
+        ``sequence.scan_spans`` / ``sequence.scan_track``; at stride 6000 windows and ``contig_scores`` are those of
+        classify_contigs.  Overlapping windows are classified independently: 6000 / stride times the work."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        return self._scan_contigs(seq.ctypes.data, 1, seq.nbytes, offsets, stride, single_window, precision)
+
+    def scan_contigs_dev(self, seq_ptr: int, offsets: np.ndarray, stride: int, single_window: bool = False,
+                         precision=_lib.DEFAULT_PRECISION) -> ScanResult:
+        """Same as :meth:`scan_contigs` for a packed contig buffer that is already resident in HBM."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        return self._scan_contigs(seq_ptr, 0, int(offsets[-1]) if len(offsets) else 0, offsets, stride, single_window, precision)
+
+    def _scan_contigs(self, seq_ptr, on_host, seq_bytes, offsets, stride, single_window, precision):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        win_off, bin_off, starts, lens = self.scan_plan(offsets, stride, single_window)
+        n_contigs, n, n_bins = len(offsets) - 1, len(starts), int(bin_off[-1])
+        scores = np.zeros((n, _lib.CLASSES), dtype=np.float32)
+        kept = np.zeros(n, dtype=np.uint8)
+        track = np.zeros((n_bins, _lib.CLASSES), dtype=np.float32)
+        cover = np.zeros(n_bins, dtype=np.int32)
+        contig_scores = np.zeros((n_contigs, _lib.CLASSES), dtype=np.float32)
+        check(self.lib.gnn_scan_contigs(self.ctx, seq_ptr, int(on_host), int(seq_bytes), offsets.ctypes.data, n_contigs, int(stride),
+                                        int(bool(single_window)), _lib.PRECISIONS[precision], scores.ctypes.data, kept.ctypes.data, n,
+                                        track.ctypes.data, cover.ctypes.data, n_bins, contig_scores.ctypes.data))
+        return ScanResult(stride=int(stride), win_offsets=win_off, starts=starts, lens=lens, kept=kept.astype(bool), scores=scores,
+                          bin_offsets=bin_off, track=track, cover=cover, contig_scores=contig_scores)
 
     def classify_contigs_spans(self, seq_ptr: int, offsets: np.ndarray, single_window: bool = False,
                                precision=_lib.DEFAULT_PRECISION):

@@ -65,6 +65,9 @@ class Outputs:
         # written only when GENOMAD_AMD_EMBEDDINGS=1 (encoder embeddings per contig; no counterpart in the reference)
         self.nn_embeddings_output = d / f"{p}_nn_embeddings.npz"
         self.provirus_nn_embeddings_output = d / f"{p}_provirus_nn_embeddings.npz"
+        # written only when GENOMAD_AMD_SCAN_STRIDE is set (score tracks along the contigs; no counterpart in the reference)
+        self.nn_scan_output = d / f"{p}_nn_scan.npz"
+        self.provirus_nn_scan_output = d / f"{p}_provirus_nn_scan.npz"
         f = o / f"{p}_find_proviruses"
         self.find_proviruses_execution_info = f / f"{p}_find_proviruses.json"
         self.find_proviruses_output = f / f"{p}_provirus.tsv"
@@ -357,6 +360,38 @@ def embeddings_requested() -> bool:
     return v == "1"
 
 
+def scan_contigs_safely(eng, seq, offsets, stride, single_window, precision, console=None):
+    """NNEngine.scan_contigs with the range fallback of :func:`_range_fallback`: a piece with a non-finite window score is scanned
+    again with the next arithmetic, and everything returned is that scan's."""
+    def run(a):
+        res = eng.scan_contigs(seq, offsets, stride, single_window, a)
+        return res.scores, res
+    _, res, _ = _with_range_fallback(run, precision, console)
+    return res
+
+
+def scan_stride_requested():
+    """GENOMAD_AMD_SCAN_STRIDE=<int in [1, 6000]>: main() also writes the score tracks along the contigs (<prefix>_nn_scan.npz),
+    windows every that many bases; unset or empty: nothing changes (None).  Any other value is an error."""
+    v = os.environ.get("GENOMAD_AMD_SCAN_STRIDE", "").strip()
+    if not v:
+        return None
+    try:
+        stride = int(v)
+    except ValueError:
+        stride = 0
+    if not 1 <= stride <= sequence.WINDOW:
+        raise ValueError(f"GENOMAD_AMD_SCAN_STRIDE={v!r}: expected an integer in [1, {sequence.WINDOW}] (bases between window starts)")
+    return stride
+
+
+def _scan_file_has_stride(path, stride) -> bool:
+    try:
+        return int(np.load(path)["stride"]) == stride
+    except Exception:  # noqa: BLE001  (missing or unreadable: scan again)
+        return False
+
+
 # ---- runtime parity sentinel (VERDICT r04 item 4) ---------------------------------------------------------------------
 # The 1e-4 claim of the production arithmetic has only ever met synthetic weights (the trained nn_classifier.h5 is not in the
 # checkout).  So every run of main() classifies its first windows a second time with the exact-f32 device path (GNN_PREC_F32:
@@ -476,6 +511,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     rccl.prepare_env()        # before ANY HIP call: drops the reference's CUDA_VISIBLE_DEVICES=-1 (:8)
     configured_precision()    # a mistyped GENOMAD_AMD_PRECISION stops here
     embeddings = embeddings_requested()
+    scan_stride = scan_stride_requested()
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -497,6 +533,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         # the per-window host path (GpuBackend) has no embedding output: stop rather than leave the requested file out
         console.error("GENOMAD_AMD_EMBEDDINGS=1 needs the device front end: the host front end (GENOMAD_AMD_FRONT_END=host) does "
                       "not compute encoder embeddings. Unset GENOMAD_AMD_FRONT_END or GENOMAD_AMD_EMBEDDINGS.")
+        sys.exit(1)
+    if scan_stride is not None and not device_front_end:
+        console.error("GENOMAD_AMD_SCAN_STRIDE needs the device front end: the host front end (GENOMAD_AMD_FRONT_END=host) does "
+                      "not scan contigs. Unset GENOMAD_AMD_FRONT_END or GENOMAD_AMD_SCAN_STRIDE.")
         sys.exit(1)
 
     def everywhere(*flags):
@@ -620,7 +660,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         if rank0:
             write_tsv(tsv_path, names, predictions)                                  # :340-352 (always rewritten)
 
-    def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, emb_path=None):
+    def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, emb_path=None, scan_path=None):
         """Product path: the contig front end (NNEngine.classify_contigs) does windowing, the N rule,
         tokenising, classification and the per-contig mean on the GPU, so encoding and classification
         are one step; ``<prefix>_seq_window_id.npz`` is still written.  With several ranks the CONTIGS are
@@ -628,8 +668,11 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         compressed inputs: every world-th record-aligned chunk of the decompressed stream), classifies it
         on its GPU, and rank 0 collects the per-contig scores with one gather and writes the files —
         results are bit-identical for any number of ranks.  ``emb_path`` (GENOMAD_AMD_EMBEDDINGS=1): the per-contig encoder
-        embeddings are computed in the same pass and written there; a run that finds the scores but not that file classifies again."""
-        (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and (emb_path is None or emb_path.exists()))   # :284-292
+        embeddings are computed in the same pass and written there; a run that finds the scores but not that file classifies again.
+        ``scan_path`` (GENOMAD_AMD_SCAN_STRIDE): every piece is also scanned at that stride (NNEngine.scan_contigs) and the score
+        tracks are written there; a run that finds the scores but no scan file of that stride runs the stage again."""
+        (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and (emb_path is None or emb_path.exists())
+                                 and (scan_path is None or _scan_file_has_stride(scan_path, scan_stride)))   # :284-292
         names = predictions = None
         if have_npz:
             gate()
@@ -643,10 +686,17 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             eng = _engine()
             size = Path(fasta).stat().st_size * (1 if sequence.compression_of(fasta) == "uncompressed" else 4)
             precision = select_arithmetic(eng, precision, size, comm, console)
-            parts, emb_parts = [], []
+            parts, emb_parts, scan_parts = [], [], []
             sentinel = {"d": None, "done": False}
 
-            def classify(sq, off):
+            def classify(key, nm, sq, off):
+                pr, emb, wid = classify_piece(sq, off)
+                parts.append((key, nm, pr, wid))
+                emb_parts.append((key, emb))
+                if scan_path is not None:       # after the normal classification, with the arithmetic the run selected
+                    scan_parts.append((key, scan_contigs_safely(eng, sq, off, scan_stride, single_window, precision, console)))
+
+            def classify_piece(sq, off):
                 if not sentinel["done"] and len(off) > 1:           # this rank's first piece with a contig: the run's parity sample
                     sentinel["done"] = True
                     sentinel["d"] = parity_sentinel(eng, sentinel_windows(sq, off, single_window), precision, console)
@@ -678,9 +728,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                         nm, sq, off = nxt.result()
                         if k + 1 < pieces:
                             nxt = pool.submit(read, k + 1)
-                        pr, emb, wid = classify(sq, off)
-                        parts.append((rank * 64 + k, nm, pr, wid))
-                        emb_parts.append((rank * 64 + k, emb))
+                        classify(rank * 64 + k, nm, sq, off)
             else:
                 # compressed streams cannot be read by byte range: every rank decompresses the stream
                 # chunk by chunk (bounded memory) and packs + classifies every world-th chunk
@@ -688,15 +736,14 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     if i % world != rank:
                         continue
                     nm, sq, off = pack(chunk)
-                    pr, emb, wid = classify(sq, off)
-                    parts.append((i, nm, pr, wid))
-                    emb_parts.append((i, emb))
+                    classify(i, nm, sq, off)
             if validate:
                 digests = np.concatenate(seen) if seen else np.zeros(0, dtype="<u8")
                 state["verdict"] = sharding.fasta_verdict(comm, digests, lambda: sequence.check_fasta(input_path))
             sentinel_verdict(comm, sentinel["d"], console, precision)      # before anything is written
             names, predictions, ids, n_windows = sharding.gather_contig_parts(comm, parts)
             embeddings_all = sharding.gather_contig_embeddings(comm, emb_parts) if emb_path is not None else None
+            scans_all = sharding.gather_contig_scans(comm, scan_parts) if scan_path is not None else None
             gate()
             if not n_windows:                                                        # :297-299
                 console.error("No sequences were found. Please check your input FASTA.")
@@ -711,6 +758,13 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                 if emb_path is not None:
                     np.savez_compressed(emb_path, **{names_key: names, "embeddings": embeddings_all})
                     console.log(f"Encoder embeddings of the {what}s written to {emb_path.name}.")
+                if scan_path is not None:
+                    sc = scans_all
+                    np.savez_compressed(scan_path, **{names_key: names, "stride": np.int64(scan_stride), "win_offsets": sc["win_offsets"],
+                                                      "window_start": sc["starts"], "window_len": sc["lens"], "window_kept": sc["kept"],
+                                                      "window_scores": sc["scores"], "bin_offsets": sc["bin_offsets"],
+                                                      "track": sc["track"], "cover": sc["cover"]})
+                    console.log(f"Score tracks of the {what}s (stride {scan_stride}, {len(sc['starts'])} windows) written to {scan_path.name}.")
         if cleanup and rank0 and enc_dir.is_dir():
             console.log(f"Deleting encoded {what} data.")
             shutil.rmtree(enc_dir)
@@ -719,15 +773,16 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
 
     run = stage_device if device_front_end else stage
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
+    scan_kw = (lambda path: {"scan_path": path}) if scan_stride is not None else (lambda path: {})
     try:
         run(input_path, outputs.encoded_sequences_dir, outputs.seq_window_id_output,
             outputs.nn_classification_npz_output, outputs.nn_classification_output,
-            "contig_names", "contig_ids", "sequence", **emb_kw(outputs.nn_embeddings_output))
+            "contig_names", "contig_ids", "sequence", **emb_kw(outputs.nn_embeddings_output), **scan_kw(outputs.nn_scan_output))
         if classify_proviruses:                                                      # :248-281, :355-425
             run(outputs.find_proviruses_nucleotide_output, outputs.encoded_proviruses_dir,
                 outputs.provirus_window_id_output, outputs.provirus_nn_classification_npz_output,
                 outputs.provirus_nn_classification_output, "provirus_names", "provirus_ids", "provirus",
-                **emb_kw(outputs.provirus_nn_embeddings_output))
+                **emb_kw(outputs.provirus_nn_embeddings_output), **scan_kw(outputs.provirus_nn_scan_output))
     finally:
         if check_pool is not None:
             check_pool.shutdown(wait=True)

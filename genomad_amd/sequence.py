@@ -391,6 +391,69 @@ def candidate_spans(offsets: np.ndarray, single_window: bool = False):
     return starts, lens, ids, window_n
 
 
+def scan_spans(offsets: np.ndarray, stride: int, single_window: bool = False):
+    """The window rule of a scan (``gnn_scan_plan`` / ``gnn_scan_contigs``), vectorised over all contigs: windows of 6000 bases
+    starting every ``stride`` bases (1 <= stride <= 6000).  Window 0 of a non-empty contig always exists; window k > 0 exists
+    while no earlier window reached the contig's end and it is at least 2500 long - so with k* = max(0, ceil((L - 6000) / stride))
+    a contig of length L has k* + (k* == 0 or L - k* * stride >= 2500) windows, and only the last can be shorter than 6000.  Bins
+    are stride wide: ceil(L / stride) per contig.  Returns (starts int64 - positions in the packed buffer, as
+    :func:`candidate_spans`; the contig-relative start is window_n * stride -, lens int32, contig_ids int64, window_n int32,
+    win_offsets int64 (n_contigs + 1), bin_offsets int64 (n_contigs + 1)).  At stride 6000 the first four are candidate_spans."""
+    stride = int(stride)
+    if not 1 <= stride <= WINDOW:
+        raise ValueError(f"stride {stride} is outside [1, {WINDOW}]")
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lengths = np.diff(offsets)
+    if len(lengths) and int(lengths.min()) < 0:
+        raise ValueError("contig offsets are not non-decreasing")
+    kstar = np.maximum(0, -(-(lengths - WINDOW) // stride))
+    nwin = kstar + ((kstar == 0) | (lengths - kstar * stride >= MIN_TAIL))
+    nwin = np.where(lengths > 0, nwin, 0)
+    if single_window:
+        nwin = np.minimum(nwin, 1)
+    win_offsets = np.concatenate([[0], np.cumsum(nwin)]).astype(np.int64)
+    bin_offsets = np.concatenate([[0], np.cumsum(-(-lengths // stride))]).astype(np.int64)
+    ids = np.repeat(np.arange(len(lengths), dtype=np.int64), nwin)
+    window_n = (np.arange(int(win_offsets[-1]), dtype=np.int64) - win_offsets[:-1][ids]).astype(np.int32)
+    starts = offsets[:-1][ids] + window_n.astype(np.int64) * stride
+    lens = np.minimum(WINDOW, offsets[1:][ids] - starts).astype(np.int32)
+    return starts, lens, ids, window_n, win_offsets, bin_offsets
+
+
+def materialize_spans(seq: np.ndarray, starts, lens) -> np.ndarray:
+    """(n, 6000) uint8: the spans seq[start : start + len] upper-cased and right-padded with 'N' - what the device front end
+    materialises for every window (nn_classification.py:72: seq_window.seq_ascii.ljust(6000, b"N")), in numpy."""
+    out = np.full((len(starts), WINDOW), ord("N"), dtype=np.uint8)
+    for i, (a, l) in enumerate(zip(starts, lens)):
+        w = np.asarray(seq[int(a):int(a) + int(l)], dtype=np.uint8)
+        out[i, :len(w)] = np.where((w >= 97) & (w <= 122), w - 32, w)
+    return out
+
+
+def scan_track(scores, kept, lens, win_offsets, bin_offsets, stride: int):
+    """The track of a scan, spelled out (the definition ``gnn_scan_contigs`` folds on the device; readable, not fast): bin b of a
+    contig is [b * stride, (b + 1) * stride); window k covers it iff k <= b and b * stride < k * stride + lens[k].  track[b] = the
+    float32 sum, in increasing k, of the scores of the KEPT windows covering b, divided once by their number cover[b]; NaN where
+    cover[b] == 0.  Returns (track (n_bins, 3) float32, cover (n_bins,) int32)."""
+    scores = np.asarray(scores, dtype=np.float32).reshape(-1, 3)
+    stride = int(stride)
+    n_bins = int(bin_offsets[-1])
+    track = np.full((n_bins, 3), np.nan, dtype=np.float32)
+    cover = np.zeros(n_bins, dtype=np.int32)
+    for c in range(len(win_offsets) - 1):
+        w0, nw = int(win_offsets[c]), int(win_offsets[c + 1] - win_offsets[c])
+        for b in range(int(bin_offsets[c + 1] - bin_offsets[c])):
+            s, n = np.zeros(3, dtype=np.float32), 0
+            for k in range(max(0, b - (WINDOW - 1) // stride), min(b, nw - 1) + 1):
+                if b * stride < k * stride + int(lens[w0 + k]) and kept[w0 + k]:
+                    s = s + scores[w0 + k]                       # float32 + float32: the device's sequential sum
+                    n += 1
+            if n:
+                track[int(bin_offsets[c]) + b] = s / np.float32(n)
+                cover[int(bin_offsets[c]) + b] = n
+    return track, cover
+
+
 def prefix_of(input_path: Path) -> str:
     """nn_classification.py:106-108: stem, minus one more extension if the file is compressed."""
     prefix = Path(input_path).stem

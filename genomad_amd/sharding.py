@@ -20,6 +20,7 @@ The product transport is :class:`genomad_amd.rccl.RcclComm` (RCCL over xGMI thro
 ``gnn_comm_*``); ``LocalComm`` below is the one-process case; the CPU test-suite drives the same functions
 with a gloo transport (tests/gloo_comm.py, world size 2 and 3).
 """
+import io
 import json
 from typing import List, Optional, Tuple
 
@@ -186,6 +187,50 @@ def gather_contig_embeddings(comm, parts, width: int = 512, root: int = 0):
         raise ValueError("duplicate piece keys in gather_contig_embeddings")
     out = [got[r][c0:c1] for _, r, c0, c1 in pieces]
     return np.concatenate(out, axis=0) if out else np.zeros((0, width), np.float32)
+
+
+SCAN_WINDOW_FIELDS = ("starts", "lens", "kept", "scores")      # per window; CSR over contigs by win_offsets
+SCAN_BIN_FIELDS = ("track", "cover")                           # per bin; CSR over contigs by bin_offsets
+
+
+def gather_contig_scans(comm, parts, root: int = 0):
+    """Score tracks of contig-sharded pieces -> ``root``, in the piece order of :func:`gather_contig_parts`.  ``parts`` = this rank's
+    list of (order_key, scan) with the same keys and contig counts as the pieces handed to gather_contig_parts; ``scan`` = the
+    arrays of one ``NNEngine.scan_contigs`` call (win_offsets, starts, lens, kept, scores, bin_offsets, track, cover; an object with
+    ``asdict()`` or a dict).  Window and bin counts differ from rank to rank, so each rank's pieces travel as one byte string
+    (:func:`gather_bytes`).  ``root`` concatenates the pieces and rebases the two CSR offset arrays; the values are only moved, so
+    the result is bit-identical for any number of ranks.  Returns a dict of those eight arrays on ``root``, None elsewhere."""
+    comm = comm or LocalComm()
+    arrays = {"keys": np.array([int(key) for key, _ in parts], dtype="<i8")}
+    for i, (_, scan) in enumerate(parts):
+        scan = scan.asdict() if hasattr(scan, "asdict") else scan
+        for f in ("win_offsets", "bin_offsets") + SCAN_WINDOW_FIELDS + SCAN_BIN_FIELDS:
+            arrays[f"{i}_{f}"] = np.ascontiguousarray(scan[f])
+    buf = io.BytesIO()
+    np.savez(buf, **arrays)
+    blobs = gather_bytes(comm, buf.getvalue(), root)
+    if comm.rank != root:
+        return None
+    pieces = []                      # (order_key, {field: array})
+    for blob in blobs:
+        z = np.load(io.BytesIO(blob))
+        for i, key in enumerate(z["keys"]):
+            pieces.append((int(key), {f[len(str(i)) + 1:]: z[f] for f in z.files if f.startswith(f"{i}_")}))
+    if len({p[0] for p in pieces}) != len(pieces):
+        raise ValueError("duplicate piece keys in gather_contig_scans")
+    pieces.sort(key=lambda p: p[0])
+    out = {"win_offsets": [np.zeros(1, np.int64)], "bin_offsets": [np.zeros(1, np.int64)]}
+    out.update({f: [] for f in SCAN_WINDOW_FIELDS + SCAN_BIN_FIELDS})
+    w0 = b0 = 0
+    for _, d in pieces:
+        out["win_offsets"].append(d["win_offsets"][1:].astype(np.int64) + w0)
+        out["bin_offsets"].append(d["bin_offsets"][1:].astype(np.int64) + b0)
+        w0, b0 = w0 + int(d["win_offsets"][-1]), b0 + int(d["bin_offsets"][-1])
+        for f in SCAN_WINDOW_FIELDS + SCAN_BIN_FIELDS:
+            out[f].append(d[f])
+    empty = {"starts": np.zeros(0, np.int64), "lens": np.zeros(0, np.int32), "kept": np.zeros(0, bool),
+             "scores": np.zeros((0, 3), np.float32), "track": np.zeros((0, 3), np.float32), "cover": np.zeros(0, np.int32)}
+    return {f: np.concatenate(v) if v else empty[f] for f, v in out.items()}
 
 
 def gather_contig_results(comm, names, predictions, window_ids, root: int = 0):

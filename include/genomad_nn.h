@@ -273,6 +273,40 @@ int gnn_classify_contigs_embed(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host
                                float* contig_scores_host, int64_t* window_ids_host, int64_t ids_capacity,
                                int64_t* n_windows_out, float* contig_emb_host);
 
+/* ---- score tracks: the contig front end at a stride ("Score tracks along contigs") -----------------------------------
+ * Overlapping 6000-base windows every `stride` bases (1 <= stride <= 6000) along every contig, each scored by the same forward
+ * pass as gnn_classify, folded into one score triple per stride-wide bin.  For a contig of length L > 0:
+ *   windows  window k starts at k * stride and is min(6000, L - k * stride) long.  Window 0 always exists; window k > 0 exists
+ *            while no earlier window reached the contig's end ((k - 1) * stride + 6000 < L) and it is at least 2500 long;
+ *            single_window keeps window 0 only.  At stride 6000: seq_windows(seq, 6000, 2500, max_windows), the table of
+ *            gnn_classify_contigs.  Content: the span upper-cased and right-padded with 'N', as gnn_classify_spans.
+ *   kept     window k is kept unless k > 0 and it holds more than 4000 literal 'N' bytes (the rule of gnn_classify_contigs).  Every
+ *            window is scored; kept is a mask.
+ *   bins     bin b = [b * stride, min((b + 1) * stride, L)), ceil(L / stride) of them.  Window k covers bin b iff k <= b and
+ *            b * stride < k * stride + its length.  track[b][c] = f32 sum, in increasing k, of class c over the kept windows that
+ *            cover b, divided once by their number cover[b]; NaN in all three classes where cover[b] == 0 (a dropped tail, or every
+ *            covering window masked).
+ *   contig   mean over the contig's kept scan windows, in the arithmetic and order of gnn_classify_contigs (bit-identical to it at
+ *            stride 6000); a zero row for a contig without a window.
+ * gnn_scan_plan - host only, no ctx, no GPU - answers the sizes: the number of windows and bins of all contigs, and, where the
+ * pointers are not NULL, the CSR offsets per contig (n_contigs + 1 entries each) and the contig-relative start and the length of
+ * every window (*n_windows_out entries: call once for the sizes, then again with the arrays).  GNN_ERR_ARG for a stride outside
+ * [1, 6000] or decreasing offsets. */
+int gnn_scan_plan(const int64_t* offsets_host, int64_t n_contigs, int stride, int single_window, int64_t* n_windows_out,
+                  int64_t* n_bins_out, int64_t* win_offsets_or_null, int64_t* bin_offsets_or_null, int64_t* starts_or_null,
+                  int32_t* lens_or_null);
+/* The scan of a packed contig buffer (seq, seq_on_host, seq_bytes, offsets_host as gnn_classify_contigs; every arithmetic it
+ * accepts).  window_scores_host[n_windows][3] and window_kept_host[n_windows] (1 = kept) in the order of gnn_scan_plan, capacity
+ * windows_capacity windows; track_host[n_bins][3] and cover_host[n_bins], capacity bins_capacity bins; contig_scores_host
+ * [n_contigs][3].  Every output except window_scores_host may be NULL; a capacity that is too small is GNN_ERR_ARG and the message
+ * names the size needed.  Synchronous.  Device memory, persistent in the ctx and grow-only: the 40 B per window of
+ * gnn_classify_contigs' own table (spans, N counts, 12 B of scores - the scan adds nothing per window) and 16 B per bin.  Overlapping windows are
+ * classified independently: a scan at stride S costs 6000 / S times the windows of gnn_classify_contigs. */
+int gnn_scan_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes, const int64_t* offsets_host,
+                     int64_t n_contigs, int stride, int single_window, int precision, float* window_scores_host,
+                     uint8_t* window_kept_host_or_null, int64_t windows_capacity, float* track_host_or_null,
+                     int32_t* cover_host_or_null, int64_t bins_capacity, float* contig_scores_host_or_null);
+
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
  * in-memory text buffer (already decompressed, newlines normalised to '\n').
