@@ -57,47 +57,7 @@ struct ProfScope {
     }
 };
 
-template <typename Tp>
-static int upload(gnn_ctx* ctx, const Tp* host, size_t count, Tp** dev) {
-    void* p = nullptr;
-    GNN_HIP(hipMalloc(&p, count * sizeof(Tp)));
-    ctx->owned.push_back(p);
-    GNN_HIP(hipMemcpy(p, host, count * sizeof(Tp), hipMemcpyHostToDevice));
-    *dev = static_cast<Tp*>(p);
-    return GNN_OK;
-}
-
-static int dev_buffer(gnn_ctx* ctx, size_t bytes, void** out) {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();      // the runtime keeps the failure as its "last error": a caller that retries with a smaller size would
-                                      // otherwise read THIS out-of-memory behind its next, successful kernel launch
-        set_error("hipMalloc of " + std::to_string(bytes) + " bytes failed: " + hipGetErrorString(e));
-        return GNN_ERR_NOMEM;
-    }
-    *out = p;
-    return GNN_OK;
-}
-
-static void free_ws(Workspace& ws) {
-    auto f = [](auto*& p) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    };
-    f(ws.tokens);
-    f(ws.x[0]);
-    f(ws.x[1]);
-    f(ws.x[2]);
-    f(ws.mp);
-    f(ws.m);
-    f(ws.yp);
-    f(ws.logits);
-    f(ws.alpha);
-    f(ws.feat);
-    ws.chunk = 0;
-    ws.x_chunk = 0;
-}
+static void free_ws(Workspace& ws) { ws = Workspace(); }
 
 // bytes of workspace per window of a fused launch (mp, m, yp, logits, alpha, feat): 0.86 MB
 constexpr size_t WS_BYTES_PER_WINDOW = ((size_t)2 * NPAIR + 2 * NP + (size_t)2 * POOLED * C + 4 * POOLED + FEAT) * sizeof(float);
@@ -111,23 +71,14 @@ static int ensure_ws(gnn_ctx* ctx, Workspace& ws, int64_t chunk, int64_t x_chunk
     }
     if (ws.chunk < chunk) {
         GNN_HIP(hipStreamSynchronize(ctx->stream));
-        auto re = [&](auto*& p, size_t bytes) -> int {
-            if (p) (void)hipFree(p);
-            p = nullptr;
-            void* q = nullptr;
-            int rc = dev_buffer(ctx, bytes, &q);
-            p = static_cast<std::remove_reference_t<decltype(p)>>(q);
-            return rc;
-        };
         // a failed allocation leaves NO workspace behind (chunk = x_chunk = 0), never a half-grown one whose
         // stale size would let a later, smaller call launch kernels on null pointers
-        int rc = GNN_OK;
-        if (!rc) rc = re(ws.mp, (size_t)chunk * 2 * NPAIR * sizeof(float));
-        if (!rc) rc = re(ws.m, (size_t)chunk * 2 * NP * sizeof(float));
-        if (!rc) rc = re(ws.yp, (size_t)chunk * 2 * POOLED * C * sizeof(float));
-        if (!rc) rc = re(ws.logits, (size_t)chunk * 2 * POOLED * sizeof(float));
-        if (!rc) rc = re(ws.alpha, (size_t)chunk * 2 * POOLED * sizeof(float));
-        if (!rc) rc = re(ws.feat, (size_t)chunk * FEAT * sizeof(float));
+        int rc = ws.mp.reserve((size_t)chunk * 2 * NPAIR);
+        if (!rc) rc = ws.m.reserve((size_t)chunk * 2 * NP);
+        if (!rc) rc = ws.yp.reserve((size_t)chunk * 2 * POOLED * C);
+        if (!rc) rc = ws.logits.reserve((size_t)chunk * 2 * POOLED);
+        if (!rc) rc = ws.alpha.reserve((size_t)chunk * 2 * POOLED);
+        if (!rc) rc = ws.feat.reserve((size_t)chunk * FEAT);
         if (rc) {
             free_ws(ws);
             return rc;
@@ -137,28 +88,16 @@ static int ensure_ws(gnn_ctx* ctx, Workspace& ws, int64_t chunk, int64_t x_chunk
     if (ws.x_chunk < x_chunk) {
         GNN_HIP(hipStreamSynchronize(ctx->stream));
         ws.x_chunk = 0;
-        for (int i = 0; i < 3; ++i) {
-            if (ws.x[i]) (void)hipFree(ws.x[i]);
-            ws.x[i] = nullptr;
-        }
-        if (ws.tokens) (void)hipFree(ws.tokens);
-        ws.tokens = nullptr;
-        for (int i = 0; i < 3; ++i) {
-            void* q = nullptr;
-            int rc = dev_buffer(ctx, (size_t)x_chunk * T * C * sizeof(float), &q);
-            if (rc) {
-                free_ws(ws);
-                return rc;
-            }
-            ws.x[i] = static_cast<float*>(q);
-        }
-        void* q = nullptr;
-        int rc = dev_buffer(ctx, (size_t)x_chunk * T * sizeof(uint16_t), &q);
+        for (DevBuf<float>& x : ws.x) x.reset();
+        ws.tokens.reset();
+        int rc = GNN_OK;
+        for (DevBuf<float>& x : ws.x)
+            if (!rc) rc = x.reserve((size_t)x_chunk * T * C);
+        if (!rc) rc = ws.tokens.reserve((size_t)x_chunk * T);
         if (rc) {
             free_ws(ws);
             return rc;
         }
-        ws.tokens = static_cast<uint16_t*>(q);
         ws.x_chunk = x_chunk;
     }
     return GNN_OK;
@@ -233,62 +172,48 @@ void build_conv1_pair_tables(const float* k1, std::vector<float>& pt) {
 constexpr int64_t STAGE_MAX_WINDOWS = 32768;          // windows per slab: 197 MB of bases on the device at most
 constexpr size_t PIN_BYTES = (size_t)8 << 20;         // one bounce buffer
 
+// windows the slab holds: its three buffers are allocated together, with the same count
+static int64_t stage_windows(const gnn_ctx* ctx) {
+    return (int64_t)std::min({ctx->stage_bases.capacity() / W, ctx->stage_scores.capacity() / GNN_CLASSES,
+                              ctx->stage_scores_host.capacity() / GNN_CLASSES});
+}
+
 void free_stage(gnn_ctx* ctx) {
-    if (ctx->stage_bases) (void)hipFree(ctx->stage_bases);
-    if (ctx->stage_scores) (void)hipFree(ctx->stage_scores);
-    if (ctx->stage_scores_host) (void)hipHostFree(ctx->stage_scores_host);
-    ctx->stage_bases = nullptr;
-    ctx->stage_scores = nullptr;
-    ctx->stage_scores_host = nullptr;
-    ctx->stage_windows = 0;
-    if (ctx->stage_emb) (void)hipFree(ctx->stage_emb);
-    if (ctx->emb_scores) (void)hipFree(ctx->emb_scores);
-    ctx->stage_emb = nullptr;
-    ctx->stage_emb_bytes = 0;
-    ctx->emb_scores = nullptr;
-    ctx->emb_scores_windows = 0;
+    ctx->stage_bases.reset();
+    ctx->stage_scores.reset();
+    ctx->stage_scores_host.reset();
+    ctx->stage_emb.reset();
+    ctx->emb_scores.reset();
     for (int i = 0; i < 2; ++i) {
-        if (ctx->pin[i]) (void)hipHostFree(ctx->pin[i]);
+        ctx->pin[i].reset();
         if (ctx->pin_ev[i]) (void)hipEventDestroy(ctx->pin_ev[i]);
-        ctx->pin[i] = nullptr;
         ctx->pin_ev[i] = nullptr;
         ctx->pin_busy[i] = false;
     }
 }
 
 static int ensure_stage(gnn_ctx* ctx, int64_t windows) {
+    int rc;
     for (int i = 0; i < 2; ++i)
         if (!ctx->pin[i]) {
-            GNN_HIP(hipHostMalloc(&ctx->pin[i], PIN_BYTES, hipHostMallocDefault));
+            if ((rc = ctx->pin[i].reserve(PIN_BYTES))) return rc;
             GNN_HIP(hipEventCreateWithFlags(&ctx->pin_ev[i], hipEventDisableTiming));
         }
-    if (ctx->stage_windows >= windows) return GNN_OK;
+    const int64_t have = stage_windows(ctx);
+    if (have >= windows) return GNN_OK;
     GNN_HIP(hipStreamSynchronize(ctx->stream));
-    const int64_t want = std::max<int64_t>(windows, std::min<int64_t>(2 * ctx->stage_windows, STAGE_MAX_WINDOWS));
-    if (ctx->stage_bases) (void)hipFree(ctx->stage_bases);
-    if (ctx->stage_scores) (void)hipFree(ctx->stage_scores);
-    if (ctx->stage_scores_host) (void)hipHostFree(ctx->stage_scores_host);
-    ctx->stage_bases = nullptr;
-    ctx->stage_scores = nullptr;
-    ctx->stage_scores_host = nullptr;
-    ctx->stage_windows = 0;
-    void *b = nullptr, *sc = nullptr, *sh = nullptr;
-    int rc = dev_buffer(ctx, (size_t)want * W, &b);
-    if (!rc) rc = dev_buffer(ctx, (size_t)want * GNN_CLASSES * sizeof(float), &sc);
-    if (!rc && hipHostMalloc(&sh, (size_t)want * GNN_CLASSES * sizeof(float), hipHostMallocDefault) != hipSuccess) {
-        set_error("hipHostMalloc of the score landing buffer failed");
-        rc = GNN_ERR_NOMEM;
+    const size_t want = (size_t)std::max<int64_t>(windows, std::min<int64_t>(2 * have, STAGE_MAX_WINDOWS));
+    ctx->stage_bases.reset();
+    ctx->stage_scores.reset();
+    ctx->stage_scores_host.reset();
+    rc = ctx->stage_bases.reserve(want * W);
+    if (!rc) rc = ctx->stage_scores.reserve(want * GNN_CLASSES);
+    if (!rc && (rc = ctx->stage_scores_host.reserve(want * GNN_CLASSES))) set_error("hipHostMalloc of the score landing buffer failed");
+    if (rc) {            // all three or none
+        ctx->stage_bases.reset();
+        ctx->stage_scores.reset();
     }
-    if (rc) {
-        if (b) (void)hipFree(b);
-        if (sc) (void)hipFree(sc);
-        return rc;
-    }
-    ctx->stage_bases = static_cast<uint8_t*>(b);
-    ctx->stage_scores = static_cast<float*>(sc);
-    ctx->stage_scores_host = static_cast<float*>(sh);
-    ctx->stage_windows = want;
-    return GNN_OK;
+    return rc;
 }
 
 // host windows -> the device slab, through the two bounce buffers (pageable source: the runtime would otherwise pin or
@@ -411,15 +336,9 @@ int classify_chunks(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int preci
         // one aligned staging copy (6 KB per window, on the stream the front end runs on) and then through the SAME kernel - the
         // scores do not depend on where the caller's buffer starts (nn_classification.py:316-317: any batch, any offset).
         if (!f32 && (reinterpret_cast<uintptr_t>(b) & 3u)) {
-            if (ctx->align_windows < m) {
+            if (ctx->align_buf.capacity() < (size_t)m * W) {
                 GNN_HIP(hipStreamSynchronize(guard.main));
-                if (ctx->align_buf) (void)hipFree(ctx->align_buf);
-                ctx->align_buf = nullptr;
-                ctx->align_windows = 0;
-                void* q = nullptr;
-                if ((rc = dev_buffer(ctx, (size_t)chunk * W, &q))) return rc;
-                ctx->align_buf = static_cast<uint8_t*>(q);
-                ctx->align_windows = chunk;
+                if ((rc = ctx->align_buf.reserve((size_t)chunk * W))) return rc;
             }
             GNN_HIP(hipMemcpyAsync(ctx->align_buf, b, (size_t)m * W, hipMemcpyDeviceToDevice, guard.main));
             b = ctx->align_buf;
@@ -633,12 +552,11 @@ int gnn_destroy(gnn_ctx* ctx) {
     if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);     // back ends an asynchronous call left pending
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->comm || ctx->comm_scratch) (void)gnn_comm_destroy(ctx);
+    // every buffer (workspaces, staging, weight packs, k-mer tables, phase_cycles) is released by its owner at `delete ctx`
+    // below, behind the streams' destruction: both streams were synchronised above and nothing was enqueued since, so no
+    // stream can still read what is freed, and ctx->device stays current until then
     free_contig_ws(ctx);
     free_stage(ctx);
-    if (ctx->align_buf) (void)hipFree(ctx->align_buf);
-    free_kmer_tables(ctx);
-    free_ws(ctx->ws);
-    free_ws(ctx->ws_alt);
     if (ctx->stream2) {
         for (int i = 0; i < 2; ++i) {
             if (ctx->ev_front[i]) (void)hipEventDestroy(ctx->ev_front[i]);
@@ -646,7 +564,6 @@ int gnn_destroy(gnn_ctx* ctx) {
         }
         (void)hipStreamDestroy(ctx->stream2);
     }
-    for (void* p : ctx->owned) (void)hipFree(p);
     for (auto& s : ctx->prof)
         for (auto& pr : s.pending) {
             (void)hipEventDestroy(pr.first);
@@ -797,12 +714,7 @@ int gnn_load_weights(gnn_ctx* ctx, const gnn_weights* w) {
         if (r) return r;
         if ((r = upload(ctx, b.data(), b.size(), db))) return r;
         const std::vector<uint16_t> fr = pack_frags(k.data(), in, HID, true);   // the same folded kernel, f16 hi / lo limbs, for dense_mfma_kernel
-        void* p = nullptr;
-        GNN_HIP(hipMalloc(&p, fr.size() * sizeof(uint16_t)));
-        ctx->owned.push_back(p);
-        GNN_HIP(hipMemcpy(p, fr.data(), fr.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        *dfrag = static_cast<uint16_t*>(p);
-        return GNN_OK;
+        return upload(ctx, fr, dfrag);
     };
     if ((rc = fold(w->enc, FEAT, &d.d1_k, &d.d1_b, &d.d1_frag))) return rc;
     if ((rc = fold(w->head, HID, &d.d2_k, &d.d2_b, &d.d2_frag))) return rc;
@@ -871,14 +783,17 @@ int gnn_dev_alloc(gnn_ctx* ctx, size_t bytes, void** dev_ptr) {
         set_error("dev_ptr is NULL");
         return GNN_ERR_ARG;
     }
-    return dev_buffer(ctx, bytes ? bytes : 1, dev_ptr);
+    DevBuf<unsigned char> b;
+    if ((rc = b.reserve(bytes ? bytes : 1))) return rc;
+    *dev_ptr = b.release();           // the caller owns it from here (gnn_dev_free)
+    return GNN_OK;
 }
 
 int gnn_dev_free(gnn_ctx* ctx, void* dev_ptr) {
     int rc = check_ctx(ctx);
     if (rc) return rc;
     GNN_HIP(hipStreamSynchronize(ctx->stream));
-    if (dev_ptr) GNN_HIP(hipFree(dev_ptr));
+    if (dev_ptr) GNN_HIP(hipFree(dev_ptr));        // the caller's memory (gnn_dev_alloc released it): no buffer object owns it
     return GNN_OK;
 }
 
@@ -917,17 +832,12 @@ int gnn_tokenize(gnn_ctx* ctx, const uint8_t* bases_host, int64_t n, uint16_t* t
         return GNN_ERR_ARG;
     }
     if (n == 0) return GNN_OK;
-    void *b = nullptr, *t = nullptr;
-    if ((rc = dev_buffer(ctx, (size_t)n * W, &b))) return rc;
-    if ((rc = dev_buffer(ctx, (size_t)n * T * sizeof(uint16_t), &t))) {
-        (void)hipFree(b);
-        return rc;
-    }
+    DevBuf<uint8_t> b;
+    DevBuf<uint16_t> t;
+    if ((rc = b.reserve((size_t)n * W)) || (rc = t.reserve((size_t)n * T))) return rc;
     rc = gnn_memcpy_h2d(ctx, b, bases_host, (size_t)n * W);
-    if (!rc) rc = launch_tokenize(ctx, (const uint8_t*)b, n, (uint16_t*)t);
+    if (!rc) rc = launch_tokenize(ctx, b, n, t);
     if (!rc) rc = gnn_memcpy_d2h(ctx, tokens_host, t, (size_t)n * T * sizeof(uint16_t));
-    (void)hipFree(b);
-    (void)hipFree(t);
     return rc;
 }
 
@@ -1003,15 +913,9 @@ int gnn_embed_dev(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int precisi
     if ((rc = embed_args(precision, emb_dtype, "gnn_embed_dev"))) return rc;
     if (n == 0) return GNN_OK;
     if (!scores_dev) {              // the scores of the same pass still have to land somewhere: a grow-only scratch of the ctx
-        if (ctx->emb_scores_windows < n) {
+        if (ctx->emb_scores.capacity() < (size_t)n * GNN_CLASSES) {
             GNN_HIP(hipStreamSynchronize(ctx->stream));
-            if (ctx->emb_scores) (void)hipFree(ctx->emb_scores);
-            ctx->emb_scores = nullptr;
-            ctx->emb_scores_windows = 0;
-            void* q = nullptr;
-            if ((rc = dev_buffer(ctx, (size_t)n * GNN_CLASSES * sizeof(float), &q))) return rc;
-            ctx->emb_scores = static_cast<float*>(q);
-            ctx->emb_scores_windows = n;
+            if ((rc = ctx->emb_scores.reserve((size_t)n * GNN_CLASSES))) return rc;
         }
         scores_dev = ctx->emb_scores;
     }
@@ -1032,15 +936,9 @@ int gnn_embed(gnn_ctx* ctx, const uint8_t* bases_host, int64_t n, int precision,
     const int64_t slab = std::min<int64_t>(n, STAGE_MAX_WINDOWS);
     const size_t row = (size_t)HID * emb_elem_bytes(emb_dtype);
     if ((rc = ensure_stage(ctx, slab))) return rc;
-    if (ctx->stage_emb_bytes < (size_t)slab * row) {
+    if (ctx->stage_emb.capacity() * sizeof(float) < (size_t)slab * row) {
         GNN_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->stage_emb) (void)hipFree(ctx->stage_emb);
-        ctx->stage_emb = nullptr;
-        ctx->stage_emb_bytes = 0;
-        void* q = nullptr;
-        if ((rc = dev_buffer(ctx, (size_t)slab * HID * sizeof(float), &q))) return rc;      // sized for f32: serves both dtypes
-        ctx->stage_emb = q;
-        ctx->stage_emb_bytes = (size_t)slab * HID * sizeof(float);
+        if ((rc = ctx->stage_emb.reserve((size_t)slab * HID))) return rc;      // sized for f32: serves both dtypes
     }
     for (int64_t a0 = 0; a0 < n && !rc; a0 += slab) {
         const int64_t m = std::min(slab, n - a0);
@@ -1135,29 +1033,17 @@ int gnn_debug_forward(gnn_ctx* ctx, const uint8_t* bases_host, int64_t n, int pr
 
 // Copy the span table to the device; checks every span against the rules of the caller's contract.
 static int upload_spans(gnn_ctx* ctx, const int64_t* starts_host, const int32_t* lens_host, int64_t n,
-                        int64_t** starts_dev, int32_t** lens_dev) {
+                        DevBuf<int64_t>& starts_dev, DevBuf<int32_t>& lens_dev) {
     for (int64_t i = 0; i < n; ++i)
         if (starts_host[i] < 0 || lens_host[i] < 0 || lens_host[i] > W) {
             set_error("span " + std::to_string(i) + " has a negative start or a length outside [0, 6000]");
             return GNN_ERR_ARG;
         }
-    void *ps = nullptr, *pl = nullptr;
-    int rc = dev_buffer(ctx, (size_t)n * sizeof(int64_t), &ps);
-    if (rc) return rc;
-    if ((rc = dev_buffer(ctx, (size_t)n * sizeof(int32_t), &pl))) {
-        (void)hipFree(ps);
-        return rc;
-    }
-    rc = gnn_memcpy_h2d(ctx, ps, starts_host, (size_t)n * sizeof(int64_t));
-    if (!rc) rc = gnn_memcpy_h2d(ctx, pl, lens_host, (size_t)n * sizeof(int32_t));
-    if (rc) {
-        (void)hipFree(ps);
-        (void)hipFree(pl);
-        return rc;
-    }
-    *starts_dev = static_cast<int64_t*>(ps);
-    *lens_dev = static_cast<int32_t*>(pl);
-    return GNN_OK;
+    int rc = starts_dev.reserve((size_t)n);
+    if (!rc) rc = lens_dev.reserve((size_t)n);
+    if (!rc) rc = gnn_memcpy_h2d(ctx, starts_dev, starts_host, (size_t)n * sizeof(int64_t));
+    if (!rc) rc = gnn_memcpy_h2d(ctx, lens_dev, lens_host, (size_t)n * sizeof(int32_t));
+    return rc;
 }
 
 int gnn_span_byte_count(gnn_ctx* ctx, const uint8_t* seq_dev, const int64_t* starts_host, const int32_t* lens_host,
@@ -1169,16 +1055,12 @@ int gnn_span_byte_count(gnn_ctx* ctx, const uint8_t* seq_dev, const int64_t* sta
         return GNN_ERR_ARG;
     }
     if (n == 0) return GNN_OK;
-    int64_t* ds = nullptr;
-    int32_t* dl = nullptr;
-    if ((rc = upload_spans(ctx, starts_host, lens_host, n, &ds, &dl))) return rc;
-    void* dc = nullptr;
-    rc = dev_buffer(ctx, (size_t)n * sizeof(int32_t), &dc);
-    if (!rc) rc = launch_span_count(ctx, seq_dev, ds, dl, n, byte, (int32_t*)dc);
+    DevBuf<int64_t> ds;
+    DevBuf<int32_t> dl, dc;
+    if ((rc = upload_spans(ctx, starts_host, lens_host, n, ds, dl))) return rc;
+    rc = dc.reserve((size_t)n);
+    if (!rc) rc = launch_span_count(ctx, seq_dev, ds, dl, n, byte, dc);
     if (!rc) rc = gnn_memcpy_d2h(ctx, counts_host, dc, (size_t)n * sizeof(int32_t));
-    (void)hipFree(ds);
-    (void)hipFree(dl);
-    if (dc) (void)hipFree(dc);
     return rc;
 }
 
@@ -1191,24 +1073,21 @@ int gnn_classify_spans(gnn_ctx* ctx, const uint8_t* seq_dev, const int64_t* star
         return GNN_ERR_ARG;
     }
     if (n == 0) return GNN_OK;
-    int64_t* ds = nullptr;
-    int32_t* dl = nullptr;
-    if ((rc = upload_spans(ctx, starts_host, lens_host, n, &ds, &dl))) return rc;
+    DevBuf<int64_t> ds;
+    DevBuf<int32_t> dl;
+    if ((rc = upload_spans(ctx, starts_host, lens_host, n, ds, dl))) return rc;
     // windows are materialised one slab at a time (6 KB each), never the whole table
     const int64_t slab = std::min<int64_t>(n, 4 * std::max<int64_t>(ctx->chunk_fused, 1));
-    void *db = nullptr, *dsc = nullptr;
-    rc = dev_buffer(ctx, (size_t)slab * W, &db);
-    if (!rc) rc = dev_buffer(ctx, (size_t)n * GNN_CLASSES * sizeof(float), &dsc);
+    DevBuf<uint8_t> db;
+    DevBuf<float> dsc;
+    rc = db.reserve((size_t)slab * W);
+    if (!rc) rc = dsc.reserve((size_t)n * GNN_CLASSES);
     for (int64_t a = 0; a < n && !rc; a += slab) {
         const int64_t m = std::min(slab, n - a);
-        rc = launch_materialize(ctx, seq_dev, ds + a, dl + a, m, (uint8_t*)db);
-        if (!rc) rc = classify_chunks(ctx, (const uint8_t*)db, m, precision, (float*)dsc + a * GNN_CLASSES);
+        rc = launch_materialize(ctx, seq_dev, ds + a, dl + a, m, db);
+        if (!rc) rc = classify_chunks(ctx, db, m, precision, dsc + a * GNN_CLASSES);
     }
     if (!rc) rc = gnn_memcpy_d2h(ctx, scores_host, dsc, (size_t)n * GNN_CLASSES * sizeof(float));
-    (void)hipFree(ds);
-    (void)hipFree(dl);
-    if (db) (void)hipFree(db);
-    if (dsc) (void)hipFree(dsc);
     return rc;
 }
 
@@ -1246,11 +1125,10 @@ int gnn_phase_cycles(gnn_ctx* ctx, int on, unsigned long long* out16) {
     if (out16 && ctx->phase_cycles)
         GNN_HIP(hipMemcpy(out16, ctx->phase_cycles, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (on) {
-        if (!ctx->phase_cycles) GNN_HIP(hipMalloc((void**)&ctx->phase_cycles, 16 * sizeof(unsigned long long)));
+        if ((rc = ctx->phase_cycles.reserve(16))) return rc;
         GNN_HIP(hipMemset(ctx->phase_cycles, 0, 16 * sizeof(unsigned long long)));
-    } else if (ctx->phase_cycles) {
-        (void)hipFree(ctx->phase_cycles);
-        ctx->phase_cycles = nullptr;
+    } else {
+        ctx->phase_cycles.reset();
     }
     return GNN_OK;
 }

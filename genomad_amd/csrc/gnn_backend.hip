@@ -590,18 +590,17 @@ extern "C" int gnn_segment_mean(gnn_ctx* ctx, const float* scores_host, const in
         return GNN_ERR_ARG;
     }
     GNN_HIP(hipSetDevice(ctx->device));
-    float *ds = nullptr, *dout = nullptr;
-    int64_t* di = nullptr;
-    int rc = GNN_OK;
+    DevBuf<float> ds, dout;
+    DevBuf<int64_t> di;
+    int rc = ds.reserve(std::max<size_t>(1, (size_t)n * GNN_CLASSES));
+    if (!rc) rc = di.reserve(std::max<size_t>(1, (size_t)n));
+    if (!rc) rc = dout.reserve((size_t)n_segments * GNN_CLASSES);
     auto step = [&](hipError_t e, const char* what) {
         if (rc == GNN_OK && e != hipSuccess) {
             set_error(std::string(what) + " failed: " + hipGetErrorString(e));
             rc = GNN_ERR_HIP;
         }
     };
-    step(hipMalloc((void**)&ds, std::max<size_t>(1, (size_t)n * GNN_CLASSES * sizeof(float))), "hipMalloc scores");
-    step(hipMalloc((void**)&di, std::max<size_t>(1, (size_t)n * sizeof(int64_t))), "hipMalloc ids");
-    step(hipMalloc((void**)&dout, (size_t)n_segments * GNN_CLASSES * sizeof(float)), "hipMalloc out");
     if (n > 0 && rc == GNN_OK) {
         step(hipMemcpyAsync(ds, scores_host, (size_t)n * GNN_CLASSES * sizeof(float), hipMemcpyHostToDevice, ctx->stream), "copy scores");
         step(hipMemcpyAsync(di, ids_host, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream), "copy ids");
@@ -609,13 +608,10 @@ extern "C" int gnn_segment_mean(gnn_ctx* ctx, const float* scores_host, const in
     if (rc == GNN_OK) {
         const int64_t threads = n_segments * GNN_CLASSES;
         hipLaunchKernelGGL(segment_mean_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream,
-                           ds, di, n, n_segments, dout);
+                           ds.get(), di.get(), n, n_segments, dout.get());
         step(hipGetLastError(), "segment_mean launch");
         step(hipMemcpyAsync(out_host, dout, (size_t)n_segments * GNN_CLASSES * sizeof(float), hipMemcpyDeviceToHost, ctx->stream), "copy out");
         step(hipStreamSynchronize(ctx->stream), "sync");
     }
-    (void)hipFree(ds);
-    (void)hipFree(di);
-    (void)hipFree(dout);
     return rc;
 }

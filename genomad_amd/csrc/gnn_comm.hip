@@ -82,15 +82,11 @@ static int need_comm(gnn_ctx* ctx) {
 
 // grow-only device staging buffer of the communicator
 static int comm_scratch(gnn_ctx* ctx, size_t bytes, void** out) {
-    if (ctx->comm_scratch_bytes < bytes) {
+    if (ctx->comm_scratch.capacity() < bytes) {
         GNN_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->comm_scratch) (void)hipFree(ctx->comm_scratch);
-        ctx->comm_scratch = nullptr;
-        ctx->comm_scratch_bytes = 0;
-        GNN_HIP(hipMalloc(&ctx->comm_scratch, bytes));
-        ctx->comm_scratch_bytes = bytes;
+        if (int rc = ctx->comm_scratch.reserve(bytes)) return rc;
     }
-    *out = ctx->comm_scratch;
+    *out = ctx->comm_scratch.get();
     return GNN_OK;
 }
 
@@ -147,9 +143,7 @@ int gnn_comm_destroy(gnn_ctx* ctx) {
         (void)g_rccl.CommDestroy(static_cast<ncclComm_t>(ctx->comm));
         ctx->comm = nullptr;
     }
-    if (ctx->comm_scratch) (void)hipFree(ctx->comm_scratch);
-    ctx->comm_scratch = nullptr;
-    ctx->comm_scratch_bytes = 0;
+    ctx->comm_scratch.reset();
     ctx->comm_ranks = 1;
     ctx->comm_rank = 0;
     return GNN_OK;

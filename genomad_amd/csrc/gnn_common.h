@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/genomad_nn.h"
+#include "gnn_devmem.h"
 
 namespace gnn {
 
@@ -45,7 +46,8 @@ bool debug_switch(const char* name);   // gnn_api.hip: environment switch read o
         }                                                                                      \
     } while (0)
 
-// Device-resident, re-packed weights.
+// Device-resident, re-packed weights.  The raw pointers are views of allocations ctx->owned keeps (upload() below); what is
+// allocated without a host image (the all-N constants, WvaTable, the k-mer tables) is a buffer of its own.
 struct DeviceWeights {
     // f32 reference layouts
     float* conv1_k = nullptr;   // (6,257,128)
@@ -85,39 +87,39 @@ struct DeviceWeights {
     float* conv1_pairs6 = nullptr;
     float* weff6[2] = {nullptr, nullptr};      // folded IGLOO weights, entry pairs x [i 8][entry parity][block 4][4 ch]
     int32_t* bucket_ptr6[2] = {nullptr, nullptr};
-    float* c6_yp_const = nullptr;   // (2, 749, 128) / (2, 8400): the f16c6 kernel's yp and mp of an all-N window (padding skip)
-    float* c6_mp_const = nullptr;
+    DevBuf<float> c6_yp_const;   // (2, 749, 128) / (2, 8400): the f16c6 kernel's yp and mp of an all-N window (padding skip)
+    DevBuf<float> c6_mp_const;
     // Toom-Cook F(3,6) front end (gnn_fused_tc.hip): transformed conv weights [k16 unit 8][xi 8][nblk 4][hi | lo][lane 64][8] f16,
     // the power of two the inverse transform multiplies by, IGLOO entry ranges per 96-row step, all-N window outputs
     uint16_t* tc_frag[2] = {nullptr, nullptr};
     float tc_inv_s[2] = {1.f, 1.f};
     int32_t* bucket_ptr96[2] = {nullptr, nullptr};
-    float* tc_yp_const = nullptr;
-    float* tc_mp_const = nullptr;
-    float* tc_wva_tbl = nullptr;    // head A's y @ w_v per 9-mer: gnn_fused_tc.hip, WvaTable (1.38 GB)
+    DevBuf<float> tc_yp_const;
+    DevBuf<float> tc_mp_const;
+    DevBuf<float> tc_wva_tbl;     // head A's y @ w_v per 9-mer: gnn_fused_tc.hip, WvaTable (1.38 GB)
     // k-mer tables of GNN_PREC_F16X3TK (gnn_fused_tk.hip, gnn_build_kmer_tables): x2 per 14-mer (137.4 GB), head A's pair products per
-    // (entry, 9-mer) (8.8 GB), that kernel's outputs of an all-N window.  Not in ctx->owned: gnn_drop_kmer_tables frees them
-    float* tk_x2_tbl = nullptr;
-    float* tk_mpa_tbl = nullptr;
-    float* tk_x1t_tbl = nullptr;    // x1 over WvaTable's index space (1.38 GB): head A's entries at 9-mers MpaTable has no column for
-    float* tk_pt_tbl = nullptr;     // conv2's six tap tables over WvaTable's index space (8.3 GB): the rows the 14-mer table cannot index
-    float* tk_yp_const = nullptr;
-    float* tk_mp_const = nullptr;
-    float* x3_yp_const[2] = {nullptr, nullptr};   // the same of gnn_fused_x3.hip: [0] bf16 limbs, [1] f16 limbs
-    float* x3_mp_const[2] = {nullptr, nullptr};
+    // (entry, 9-mer) (8.8 GB), that kernel's outputs of an all-N window.  gnn_drop_kmer_tables frees them on their own
+    DevBuf<float> tk_x2_tbl;
+    DevBuf<float> tk_mpa_tbl;
+    DevBuf<float> tk_x1t_tbl;     // x1 over WvaTable's index space (1.38 GB): head A's entries at 9-mers MpaTable has no column for
+    DevBuf<float> tk_pt_tbl;      // conv2's six tap tables over WvaTable's index space (8.3 GB): the rows the 14-mer table cannot index
+    DevBuf<float> tk_yp_const;
+    DevBuf<float> tk_mp_const;
+    DevBuf<float> x3_yp_const[2];  // the same of gnn_fused_x3.hip: [0] bf16 limbs, [1] f16 limbs
+    DevBuf<float> x3_mp_const[2];
 };
 
 struct Workspace {
     int64_t chunk = 0;          // windows per launch
-    uint16_t* tokens = nullptr; // (chunk, 5997)           f32 path only
-    float* x[3] = {nullptr, nullptr, nullptr};  // (chunk,5997,128) each, f32 path only
+    DevBuf<uint16_t> tokens;    // (chunk, 5997)           f32 path only
+    DevBuf<float> x[3];         // (chunk,5997,128) each, f32 path only
     int64_t x_chunk = 0;        // windows the x buffers hold
-    float* mp = nullptr;        // (chunk, 2, 8400) pair dot products in bucket order
-    float* m = nullptr;         // (chunk, 2, 2100)  bias + the four pair products of every patch
-    float* yp = nullptr;        // (chunk, 2, 749, 128)
-    float* logits = nullptr;    // (chunk, 2, 749)
-    float* alpha = nullptr;     // (chunk, 2, 749)   (tap)
-    float* feat = nullptr;      // (chunk, 256)
+    DevBuf<float> mp;           // (chunk, 2, 8400) pair dot products in bucket order
+    DevBuf<float> m;            // (chunk, 2, 2100)  bias + the four pair products of every patch
+    DevBuf<float> yp;           // (chunk, 2, 749, 128)
+    DevBuf<float> logits;       // (chunk, 2, 749)
+    DevBuf<float> alpha;        // (chunk, 2, 749)   (tap)
+    DevBuf<float> feat;         // (chunk, 256)
 };
 
 struct ContigWorkspace;
@@ -153,38 +155,70 @@ struct gnn_ctx {
     bool profile = false;
     gnn::ProfileSlot prof[GNN_K_COUNT];
     std::vector<hipEvent_t> event_pool;
-    std::vector<void*> owned;   // device allocations to free at destroy
+    std::vector<gnn::DevBuf<unsigned char>> owned;   // the weight packs (gnn::upload)
     int cu_count = 0;
     int last_split = 1;                           // workgroups per window of the last streaming-kernel launch (gnn_debug_last_split)
     bool time_split = true;                       // x3 kernel: several workgroups per window when a launch is smaller than the chip (gnn_debug_set_time_split)
     bool c6_pad_skip = true;                      // f16c6: copy the all-N tail of a window instead of computing it (gnn_debug_set_pad_skip)
-    unsigned long long* phase_cycles = nullptr;   // non-null: fused kernel runs its instrumented build
+    gnn::DevBuf<unsigned long long> phase_cycles;  // non-null: fused kernel runs its instrumented build
     gnn::ContigWorkspace* contig_ws = nullptr;    // gnn_contigs.hip: persistent buffers of gnn_classify_contigs
     // gnn_classify / gnn_debug_forward (host windows in, host scores out): persistent, grow-only staging - a device slab for
     // the windows and their scores, two pinned bounce buffers the windows go through in pieces (the copy of piece i+1 into
     // its bounce buffer overlaps the DMA of piece i) and a pinned landing buffer for the scores.  No allocation per call.
-    uint8_t* stage_bases = nullptr;
-    void* stage_emb = nullptr;                    // gnn_embed: the slab's embeddings (grow-only, stage_emb_bytes)
-    size_t stage_emb_bytes = 0;
-    float* emb_scores = nullptr;                  // gnn_embed_dev without a scores pointer: the scores land here (grow-only, windows)
-    int64_t emb_scores_windows = 0;
-    float* stage_scores = nullptr;
-    float* stage_scores_host = nullptr;
-    int64_t stage_windows = 0;
-    void* pin[2] = {nullptr, nullptr};
+    gnn::DevBuf<uint8_t> stage_bases;             // W bytes per window
+    gnn::DevBuf<float> stage_emb;                 // gnn_embed: the slab's embeddings (grow-only; f32 elements, serves bf16 too)
+    gnn::DevBuf<float> emb_scores;                // gnn_embed_dev without a scores pointer: the scores land here (grow-only)
+    gnn::DevBuf<float> stage_scores;              // GNN_CLASSES per window, as stage_scores_host
+    gnn::PinnedBuf<float> stage_scores_host;
+    gnn::PinnedBuf<uint8_t> pin[2];
     hipEvent_t pin_ev[2] = {nullptr, nullptr};
     bool pin_busy[2] = {false, false};
     // classify_chunks: staging of a window buffer that is not 4-byte aligned (the streaming kernels fetch bases as aligned dwords)
-    uint8_t* align_buf = nullptr;
-    int64_t align_windows = 0;
+    gnn::DevBuf<uint8_t> align_buf;
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;
-    void* comm_scratch = nullptr;
-    size_t comm_scratch_bytes = 0;
+    gnn::DevBuf<unsigned char> comm_scratch;
 };
 
 namespace gnn {
+
+// The one way a weight pack reaches the device: an allocation ctx->owned keeps until gnn_destroy, filled from the host.
+template <typename Tp>
+int upload(gnn_ctx* ctx, const Tp* host, size_t count, Tp** dev) {
+    DevBuf<unsigned char> b;
+    if (int rc = b.upload(reinterpret_cast<const unsigned char*>(host), count * sizeof(Tp))) return rc;
+    *dev = reinterpret_cast<Tp*>(b.get());
+    ctx->owned.emplace_back(std::move(b));
+    return GNN_OK;
+}
+template <typename Tp>
+int upload(gnn_ctx* ctx, const std::vector<Tp>& v, Tp** dev) {
+    return upload(ctx, v.data(), v.size(), dev);
+}
+
+// The padding skip's constants: a fused front end runs ONCE on an all-N window and its yp (2, 749, 128) and mp (2, 8400) are
+// kept; the kernels copy them for a window's all-N tail instead of computing it.  run(bases, yp, mp) fills the kernel's Args
+// and enqueues one window on ctx->stream.
+template <typename Run>
+int all_n_consts(gnn_ctx* ctx, DevBuf<float>& yp, DevBuf<float>& mp, Run&& run) {
+    DevBuf<uint8_t> bn;
+    int rc = bn.reserve(W);
+    if (!rc) rc = yp.reserve((size_t)2 * POOLED * C);
+    if (!rc) rc = mp.reserve((size_t)2 * NPAIR);
+    if (rc) return rc;
+    hipError_t e = hipMemsetAsync(bn, 'N', W, ctx->stream);
+    if (e == hipSuccess) {
+        run(bn.get(), yp.get(), mp.get());
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // before bn goes
+    if (e == hipSuccess) return GNN_OK;
+    yp.reset();           // no constants rather than unwritten ones
+    mp.reset();
+    set_error(std::string("the all-N window's launch failed: ") + hipGetErrorString(e));
+    return GNN_ERR_HIP;
+}
 
 // ---- kernel launchers (each enqueues on ctx->stream, returns gnn_status) ----
 int launch_tokenize(gnn_ctx* ctx, const uint8_t* bases, int64_t n, uint16_t* tokens);

@@ -80,7 +80,9 @@ static int run_f64(gnn_ctx* ctx, std::initializer_list<std::pair<const double*, 
                    double* out_host, Launch launch) {
     GNN_HIP(hipSetDevice(ctx->device));
     if (int frc = finish_pending(ctx)) return frc;
+    std::vector<DevBuf<double>> bufs(ins.size());
     std::vector<double*> dev;
+    DevBuf<double> dout;
     int rc = GNN_OK;
     auto fail = [&](hipError_t e, const char* what) {
         if (rc == GNN_OK && e != hipSuccess) {
@@ -89,23 +91,19 @@ static int run_f64(gnn_ctx* ctx, std::initializer_list<std::pair<const double*, 
         }
     };
     for (auto& in : ins) {
-        double* p = nullptr;
-        fail(hipMalloc((void**)&p, std::max<size_t>(in.second, 1) * sizeof(double)), "hipMalloc");
-        dev.push_back(p);
+        DevBuf<double>& b = bufs[dev.size()];
+        if (rc == GNN_OK) rc = b.reserve(std::max<size_t>(in.second, 1));
+        dev.push_back(b);
         if (rc == GNN_OK && in.second)
-            fail(hipMemcpyAsync(p, in.first, in.second * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "copy in");
+            fail(hipMemcpyAsync(b, in.first, in.second * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "copy in");
     }
-    double* dout = nullptr;
-    fail(hipMalloc((void**)&dout, (size_t)n * 3 * sizeof(double)), "hipMalloc");
+    if (rc == GNN_OK) rc = dout.reserve((size_t)n * 3);
     if (rc == GNN_OK) {
         launch(dev, dout);
         fail(hipGetLastError(), "launch");
         fail(hipMemcpyAsync(out_host, dout, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "copy out");
         fail(hipStreamSynchronize(ctx->stream), "sync");
     }
-    for (double* p : dev)
-        if (p) (void)hipFree(p);
-    if (dout) (void)hipFree(dout);
     return rc;
 }
 

@@ -31,35 +31,30 @@ struct ContigWorkspace {
     // host side of the span table
     std::vector<int64_t> starts, ids;
     std::vector<int32_t> lens, window_n, counts;
-    // device side (capacities in elements / bytes)
-    uint8_t* seq = nullptr;
-    size_t seq_cap = 0;
-    int64_t* d_starts = nullptr;
-    int64_t* d_ids = nullptr;
-    int32_t* d_lens = nullptr;
-    int32_t* d_window_n = nullptr;
-    int32_t* d_counts = nullptr;
-    float* d_scores = nullptr;
-    size_t span_cap = 0;
-    uint8_t* d_bases = nullptr;
-    size_t bases_cap = 0;
-    float* d_out = nullptr;
-    size_t out_cap = 0;
+    // device side
+    DevBuf<uint8_t> seq;
+    DevBuf<int64_t> d_starts, d_ids;             // the span table: one element per candidate window ...
+    DevBuf<int32_t> d_lens, d_window_n, d_counts;
+    DevBuf<float> d_scores;                      // ... and GNN_CLASSES per window
+    DevBuf<uint8_t> d_bases;
+    DevBuf<float> d_out;
     // gnn_classify_contigs_embed: one slab's window embeddings (f32) and the per-contig running sums / kept-window counts
-    float* d_emb = nullptr;
-    size_t emb_cap = 0;
-    float* d_emb_sum = nullptr;
-    size_t emb_sum_cap = 0;
-    int32_t* d_emb_kept = nullptr;
-    size_t emb_kept_cap = 0;
+    DevBuf<float> d_emb, d_emb_sum;
+    DevBuf<int32_t> d_emb_kept;
     // gnn_scan_contigs: CSR offsets of every contig's windows and bins, the track (3 f32 per bin) and its cover counts
     std::vector<int64_t> win_off, bin_off;
-    int64_t* d_win_off = nullptr;
-    int64_t* d_bin_off = nullptr;
-    size_t off_cap = 0;
-    float* d_track = nullptr;
-    int32_t* d_cover = nullptr;
-    size_t bin_cap = 0;
+    DevBuf<int64_t> d_win_off, d_bin_off;
+    DevBuf<float> d_track;
+    DevBuf<int32_t> d_cover;
+
+    // What the buffer groups hold, in windows / contigs + 1 / bins.  The head-room is counted in elements, so a buffer with
+    // several elements per window or bin holds fewer of them than its neighbours: the smallest member decides.
+    size_t span_cap() const {
+        return std::min({d_starts.capacity(), d_ids.capacity(), d_lens.capacity(), d_window_n.capacity(), d_counts.capacity(),
+                         d_scores.capacity() / GNN_CLASSES});
+    }
+    size_t off_cap() const { return std::min(d_win_off.capacity(), d_bin_off.capacity()); }
+    size_t bin_cap() const { return std::min(d_track.capacity() / GNN_CLASSES, d_cover.capacity()); }
 };
 
 // What gnn_scan_contigs adds to a call of classify_contigs: host buffers for the per-window and per-bin results.
@@ -85,22 +80,16 @@ static inline void for_each_window(int64_t len, int64_t stride, int single_windo
     }
 }
 
+// Grow-only with some head-room (amortised).
 template <typename Tp>
-static int grow(Tp*& p, size_t& cap, size_t need, size_t elem = sizeof(Tp)) {
-    if (cap >= need && p) return GNN_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    void* q = nullptr;
-    const size_t want = need + need / 4 + 64;          // some head-room: grow-only, amortised
-    hipError_t e = hipMalloc(&q, want * elem);
-    if (e != hipSuccess) {
-        set_error("hipMalloc of " + std::to_string(want * elem) + " bytes failed: " + hipGetErrorString(e));
-        return GNN_ERR_NOMEM;
-    }
-    p = static_cast<Tp*>(q);
-    cap = want;
-    return GNN_OK;
+static int reserve_roomy(DevBuf<Tp>& b, size_t need) {
+    return b.reserve(need, need / 4 + 64);
+}
+
+// A group that is sized together is re-allocated as a whole: every member is emptied before the first one grows.
+template <typename... Bufs>
+static void reset_all(Bufs&... bufs) {
+    (bufs.reset(), ...);
 }
 
 void free_contig_ws(gnn_ctx* ctx) {
@@ -108,11 +97,6 @@ void free_contig_ws(gnn_ctx* ctx) {
     if (!w) return;
     for (hipEvent_t e : w->piece_done) (void)hipEventDestroy(e);
     if (w->copy_stream) (void)hipStreamDestroy(w->copy_stream);
-    for (void* p : {(void*)w->seq, (void*)w->d_starts, (void*)w->d_ids, (void*)w->d_lens, (void*)w->d_window_n,
-                    (void*)w->d_counts, (void*)w->d_scores, (void*)w->d_bases, (void*)w->d_out, (void*)w->d_emb,
-                    (void*)w->d_emb_sum, (void*)w->d_emb_kept, (void*)w->d_win_off, (void*)w->d_bin_off, (void*)w->d_track,
-                    (void*)w->d_cover})
-        if (p) (void)hipFree(p);
     delete w;
     ctx->contig_ws = nullptr;
 }
@@ -288,52 +272,48 @@ static int classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, i
 
     // ---- device buffers
     int rc = GNN_OK;
-    size_t cap = w.span_cap;
-    if (cap < (size_t)n) {
+    if (w.span_cap() < (size_t)n) {
         GNN_HIP(hipStreamSynchronize(ctx->stream));
-        size_t c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0;
-        if (!rc) rc = grow(w.d_starts, c1, (size_t)n);
-        if (!rc) rc = grow(w.d_ids, c2, (size_t)n);
-        if (!rc) rc = grow(w.d_lens, c3, (size_t)n);
-        if (!rc) rc = grow(w.d_window_n, c4, (size_t)n);
-        if (!rc) rc = grow(w.d_counts, c5, (size_t)n);
-        if (!rc) rc = grow(w.d_scores, c6, (size_t)n * GNN_CLASSES);
-        // in windows: grow()'s head-room is counted in elements, so the scores buffer (3 per window) holds fewer windows than c1
-        w.span_cap = rc ? 0 : std::min(c1, c6 / GNN_CLASSES);
+        reset_all(w.d_starts, w.d_ids, w.d_lens, w.d_window_n, w.d_counts, w.d_scores);
+        if (!rc) rc = reserve_roomy(w.d_starts, (size_t)n);
+        if (!rc) rc = reserve_roomy(w.d_ids, (size_t)n);
+        if (!rc) rc = reserve_roomy(w.d_lens, (size_t)n);
+        if (!rc) rc = reserve_roomy(w.d_window_n, (size_t)n);
+        if (!rc) rc = reserve_roomy(w.d_counts, (size_t)n);
+        if (!rc) rc = reserve_roomy(w.d_scores, (size_t)n * GNN_CLASSES);
         if (rc) return rc;
     }
     const int64_t slab = std::min<int64_t>(n, 4 * std::max<int64_t>(ctx->chunk_fused, 1));
-    if ((rc = grow(w.d_bases, w.bases_cap, (size_t)slab * W))) return rc;
-    if ((rc = grow(w.d_out, w.out_cap, (size_t)n_contigs * GNN_CLASSES))) return rc;
+    if ((rc = reserve_roomy(w.d_bases, (size_t)slab * W))) return rc;
+    if ((rc = reserve_roomy(w.d_out, (size_t)n_contigs * GNN_CLASSES))) return rc;
     if (fold) {        // 16 B per contig and 16 B per bin (hipFree of a buffer that grows waits for the kernels that read it)
-        if (w.off_cap < (size_t)n_contigs + 1) {
-            size_t c1 = 0, c2 = 0;
-            if (!rc) rc = grow(w.d_win_off, c1, (size_t)n_contigs + 1);
-            if (!rc) rc = grow(w.d_bin_off, c2, (size_t)n_contigs + 1);
-            w.off_cap = rc ? 0 : c1;
+        if (w.off_cap() < (size_t)n_contigs + 1) {
+            reset_all(w.d_win_off, w.d_bin_off);
+            if (!rc) rc = reserve_roomy(w.d_win_off, (size_t)n_contigs + 1);
+            if (!rc) rc = reserve_roomy(w.d_bin_off, (size_t)n_contigs + 1);
         }
-        if (!rc && w.bin_cap < (size_t)n_bins) {
-            size_t c1 = 0, c2 = 0;
-            if (!rc) rc = grow(w.d_track, c1, (size_t)n_bins * GNN_CLASSES);
-            if (!rc) rc = grow(w.d_cover, c2, (size_t)n_bins);
-            w.bin_cap = rc ? 0 : std::min(c1 / GNN_CLASSES, c2);       // in bins (see span_cap)
+        if (!rc && w.bin_cap() < (size_t)n_bins) {
+            reset_all(w.d_track, w.d_cover);
+            if (!rc) rc = reserve_roomy(w.d_track, (size_t)n_bins * GNN_CLASSES);
+            if (!rc) rc = reserve_roomy(w.d_cover, (size_t)n_bins);
         }
         if (rc) return rc;
     }
     if (contig_emb_host) {
         // a slab's window embeddings (2 KB each) and the per-contig sums: never every window's row (10 M windows would be 20 GB)
-        if (w.emb_cap < (size_t)slab * HID || w.emb_sum_cap < (size_t)n_contigs * HID || w.emb_kept_cap < (size_t)n_contigs)
+        if (w.d_emb.capacity() < (size_t)slab * HID || w.d_emb_sum.capacity() < (size_t)n_contigs * HID ||
+            w.d_emb_kept.capacity() < (size_t)n_contigs)
             GNN_HIP(hipStreamSynchronize(ctx->stream));
-        if ((rc = grow(w.d_emb, w.emb_cap, (size_t)slab * HID))) return rc;
-        if ((rc = grow(w.d_emb_sum, w.emb_sum_cap, (size_t)n_contigs * HID))) return rc;
-        if ((rc = grow(w.d_emb_kept, w.emb_kept_cap, (size_t)n_contigs))) return rc;
+        if ((rc = reserve_roomy(w.d_emb, (size_t)slab * HID))) return rc;
+        if ((rc = reserve_roomy(w.d_emb_sum, (size_t)n_contigs * HID))) return rc;
+        if ((rc = reserve_roomy(w.d_emb_kept, (size_t)n_contigs))) return rc;
         GNN_HIP(hipMemsetAsync(w.d_emb_sum, 0, (size_t)n_contigs * HID * sizeof(float), ctx->stream));
         GNN_HIP(hipMemsetAsync(w.d_emb_kept, 0, (size_t)n_contigs * sizeof(int32_t), ctx->stream));
     }
     const uint8_t* seq_dev = seq;
     int64_t n_pieces = 0;
     if (seq_on_host) {
-        if ((rc = grow(w.seq, w.seq_cap, (size_t)seq_bytes))) return rc;
+        if ((rc = reserve_roomy(w.seq, (size_t)seq_bytes))) return rc;
         seq_dev = w.seq;
         if (!w.copy_stream) GNN_HIP(hipStreamCreateWithFlags(&w.copy_stream, hipStreamNonBlocking));
         n_pieces = (seq_bytes + PIECE - 1) / PIECE;
@@ -368,7 +348,7 @@ static int classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, i
         }
         if ((rc = launch_span_count(ctx, seq_dev, w.d_starts + a, w.d_lens + a, m, 'N', w.d_counts + a))) return rc;
         if ((rc = launch_materialize(ctx, seq_dev, w.d_starts + a, w.d_lens + a, m, w.d_bases))) return rc;
-        if ((rc = classify_chunks(ctx, w.d_bases, m, precision, w.d_scores + a * GNN_CLASSES, false, contig_emb_host ? w.d_emb : nullptr,
+        if ((rc = classify_chunks(ctx, w.d_bases, m, precision, w.d_scores + a * GNN_CLASSES, false, contig_emb_host ? w.d_emb.get() : nullptr,
                                   GNN_EMB_F32)))
             return rc;
         if (contig_emb_host) {     // classify_chunks has ordered its back ends before ctx->stream: the slab's rows are complete

@@ -803,16 +803,6 @@ static void pack_c6(const float* wmat, int K, int N, std::vector<uint32_t>& frag
         }
 }
 
-template <typename Tp>
-static int upload_vec(gnn_ctx* ctx, const std::vector<Tp>& v, Tp** dev) {
-    void* p = nullptr;
-    GNN_HIP(hipMalloc(&p, v.size() * sizeof(Tp)));
-    ctx->owned.push_back(p);
-    GNN_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(Tp), hipMemcpyHostToDevice));
-    *dev = static_cast<Tp*>(p);
-    return GNN_OK;
-}
-
 }  // namespace c6
 
 namespace c6 {
@@ -841,15 +831,15 @@ int pack_fused_c6_weights(gnn_ctx* ctx, const gnn_weights* w) {
     for (int i = 0; i < 2; ++i) {
         pack_c6(ck[i], KS * C, C, f, s);          // one allocation: fragments, then the scale words (one buffer resource in the kernel)
         f.insert(f.end(), s.begin(), s.end());
-        if ((rc = upload_vec(ctx, f, &d.conv_c6[i]))) return rc;
+        if ((rc = upload(ctx, f, &d.conv_c6[i]))) return rc;
         pack_c6(ig[i]->w_v, C, C, f, s);
         f.insert(f.end(), s.begin(), s.end());
-        if ((rc = upload_vec(ctx, f, &d.wv_c6[i]))) return rc;
+        if ((rc = upload(ctx, f, &d.wv_c6[i]))) return rc;
         // entry ranges of the position-sorted IGLOO pairs per step of FT6 rows
         std::vector<int32_t> ptr(STEPS6 + 1, 0);
         for (int e = 0; e < NPAIR; ++e) ptr[ig[i]->patches[e] / FT6 + 1] += 1;
         for (int st = 0; st < STEPS6; ++st) ptr[st + 1] += ptr[st];
-        if ((rc = upload_vec(ctx, ptr, &d.bucket_ptr6[i]))) return rc;
+        if ((rc = upload(ctx, ptr, &d.bucket_ptr6[i]))) return rc;
         // folded IGLOO weights in entry (position-sorted) order, re-laid for 4 lanes per entry: see PairW
         std::vector<int32_t> order(NPAIR);
         for (int e = 0; e < NPAIR; ++e) order[e] = e;
@@ -861,7 +851,7 @@ int pack_fused_c6_weights(gnn_ctx* ctx, const gnn_weights* w) {
             for (int c = 0; c < C; ++c)     // channel 32 p + 4 i + k  ->  i * 32 + p * 4 + k  (+ 16 for the odd entry)
                 dst[((c >> 2) & 7) * 32 + (c >> 5) * 4 + (c & 3)] = ig[i]->w_mult[(size_t)pair * C + c] * ig[i]->w_summer[j * C + c];
         }
-        if ((rc = upload_vec(ctx, w6, &d.weff6[i]))) return rc;
+        if ((rc = upload(ctx, w6, &d.weff6[i]))) return rc;
     }
     // conv1 pair tables in the lane order of this kernel's gather, conv1 bias folded into table 0 (every position adds
     // exactly one row of each table)
@@ -877,31 +867,18 @@ int pack_fused_c6_weights(gnn_ctx* ctx, const gnn_weights* w) {
                 dst[i * 32 + pq * 4 + e] = src[c] + (j == 0 ? w->conv1_bias[c] : 0.f);
             }
         }
-    if ((rc = upload_vec(ctx, pq, &d.conv1_pairs6))) return rc;
+    if ((rc = upload(ctx, pq, &d.conv1_pairs6))) return rc;
     // the all-N window's outputs, computed once by the kernel itself (padding skip: see the kernel's prologue)
-    {
-        void *bn = nullptr, *yc = nullptr, *mc = nullptr;
-        GNN_HIP(hipMalloc(&bn, W));
-        GNN_HIP(hipMalloc(&yc, (size_t)2 * POOLED * C * sizeof(float)));
-        GNN_HIP(hipMalloc(&mc, (size_t)2 * NPAIR * sizeof(float)));
-        ctx->owned.push_back(bn);
-        ctx->owned.push_back(yc);
-        ctx->owned.push_back(mc);
-        GNN_HIP(hipMemsetAsync(bn, 'N', W, ctx->stream));
+    return all_n_consts(ctx, d.c6_yp_const, d.c6_mp_const, [&](const uint8_t* bn, float* yp, float* mp) {
         Args a;
-        fill_args(ctx, a, static_cast<const uint8_t*>(bn));
-        a.mp = static_cast<float*>(mc);
-        a.yp = static_cast<float*>(yc);
+        fill_args(ctx, a, bn);
+        a.mp = mp;
+        a.yp = yp;
         a.yp_c = nullptr;
         a.mp_c = nullptr;
         a.cycles = nullptr;
         hipLaunchKernelGGL((fused_front_c6_kernel<false>), dim3(1), dim3(512), 0, ctx->stream, a);
-        GNN_HIP(hipGetLastError());
-        GNN_HIP(hipStreamSynchronize(ctx->stream));
-        d.c6_yp_const = static_cast<float*>(yc);
-        d.c6_mp_const = static_cast<float*>(mc);
-    }
-    return GNN_OK;
+    });
 }
 
 int c6_rows_per_step() { return c6::FT6; }
@@ -926,8 +903,8 @@ int launch_front_c6(gnn_ctx* ctx, const uint8_t* bases, int64_t n) {
     fill_args(ctx, a, bases);
     a.mp = ctx->ws.mp;
     a.yp = ctx->ws.yp;
-    a.yp_c = pad_skip ? ctx->w.c6_yp_const : nullptr;
-    a.mp_c = pad_skip ? ctx->w.c6_mp_const : nullptr;
+    a.yp_c = pad_skip ? ctx->w.c6_yp_const.get() : nullptr;
+    a.mp_c = pad_skip ? ctx->w.c6_mp_const.get() : nullptr;
     a.cycles = ctx->phase_cycles;
     if (ctx->phase_cycles) hipLaunchKernelGGL((fused_front_c6_kernel<true>), dim3((unsigned)n), dim3(512), 0, ctx->stream, a);
     else hipLaunchKernelGGL((fused_front_c6_kernel<false>), dim3((unsigned)n), dim3(512), 0, ctx->stream, a);

@@ -451,7 +451,7 @@ static void fill_args(const gnn_ctx* ctx, Args& a, const uint8_t* bases) {
         a.pos_sorted[i] = d.pos_sorted[i];
         a.bucket_ptr[i] = d.bucket_ptr96[i];
     }
-    a.wva_tbl = reinterpret_cast<const unsigned char*>(d.tc_wva_tbl);
+    a.wva_tbl = reinterpret_cast<const unsigned char*>(d.tc_wva_tbl.get());
     a.cycles = nullptr;
     a.split = 1;
 }
@@ -524,11 +524,7 @@ int pack_fused_tc_weights(gnn_ctx* ctx, const gnn_weights* w) {
             for (size_t b0 = 0; b0 < frag.size(); b0 += 2 * 64 * 8)
                 for (size_t i = 0; i < 64 * 8; ++i) frag[b0 + 64 * 8 + i] &= mask;
         }
-        void* p = nullptr;
-        GNN_HIP(hipMalloc(&p, frag.size() * 2));
-        ctx->owned.push_back(p);
-        GNN_HIP(hipMemcpy(p, frag.data(), frag.size() * 2, hipMemcpyHostToDevice));
-        d.tc_frag[cv] = static_cast<uint16_t*>(p);
+        if (int rc = upload(ctx, frag, &d.tc_frag[cv])) return rc;
         d.tc_inv_s[cv] = (float)(1.0 / scale);
     }
     const gnn_igloo_weights* ig[2] = {&w->igloo_a, &w->igloo_b};
@@ -536,49 +532,26 @@ int pack_fused_tc_weights(gnn_ctx* ctx, const gnn_weights* w) {
         std::vector<int32_t> ptr(STEPST + 1, 0);
         for (int i = 0; i < NPAIR; ++i) ptr[ig[h]->patches[i] / FTT + 1] += 1;      // range-checked by gnn_load_weights before
         for (int s = 0; s < STEPST; ++s) ptr[s + 1] += ptr[s];
-        void* p = nullptr;
-        GNN_HIP(hipMalloc(&p, ptr.size() * 4));
-        ctx->owned.push_back(p);
-        GNN_HIP(hipMemcpy(p, ptr.data(), ptr.size() * 4, hipMemcpyHostToDevice));
-        d.bucket_ptr96[h] = static_cast<int32_t*>(p);
+        if (int rc = upload(ctx, ptr, &d.bucket_ptr96[h])) return rc;
     }
     // head A's y @ w_v table (WvaTable): 1.38 GB, built on the device from the pair tables and w_v A
     {
-        void* p = nullptr;
         const size_t bytes = (size_t)WvaTable::ROWS * WvaTable::ROW_BYTES;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("hipMalloc of the " + std::to_string(bytes >> 20) + " MiB table of head A's y @ w_v rows failed: " + hipGetErrorString(e));
-            return GNN_ERR_NOMEM;
-        }
-        ctx->owned.push_back(p);
-        d.tc_wva_tbl = static_cast<float*>(p);
-        const int rc = build_wva_rows_table(ctx, d.w_v[0], d.tc_wva_tbl);
+        const std::string what = "hipMalloc of the " + std::to_string(bytes >> 20) + " MiB table of head A's y @ w_v rows";
+        int rc = d.tc_wva_tbl.reserve(bytes / sizeof(float), 0, what.c_str());
+        if (!rc) rc = build_wva_rows_table(ctx, d.w_v[0], d.tc_wva_tbl);
         if (rc) return rc;
     }
     // the all-N window's outputs, computed once by the kernel itself (padding skip)
-    void* bn = nullptr;
-    GNN_HIP(hipMalloc(&bn, W));
-    ctx->owned.push_back(bn);
-    GNN_HIP(hipMemsetAsync(bn, 'N', W, ctx->stream));
-    void *yc = nullptr, *mc = nullptr;
-    GNN_HIP(hipMalloc(&yc, (size_t)2 * POOLED * C * sizeof(float)));
-    ctx->owned.push_back(yc);
-    GNN_HIP(hipMalloc(&mc, (size_t)2 * NPAIR * sizeof(float)));
-    ctx->owned.push_back(mc);
-    Args a;
-    fill_args(ctx, a, static_cast<const uint8_t*>(bn));
-    a.mp = static_cast<float*>(mc);
-    a.yp = static_cast<float*>(yc);
-    a.yp_c = nullptr;
-    a.mp_c = nullptr;
-    launch(a, false, 1, ctx->stream);
-    GNN_HIP(hipGetLastError());
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
-    d.tc_yp_const = static_cast<float*>(yc);
-    d.tc_mp_const = static_cast<float*>(mc);
-    return GNN_OK;
+    return all_n_consts(ctx, d.tc_yp_const, d.tc_mp_const, [&](const uint8_t* bn, float* yp, float* mp) {
+        Args a;
+        fill_args(ctx, a, bn);
+        a.mp = mp;
+        a.yp = yp;
+        a.yp_c = nullptr;
+        a.mp_c = nullptr;
+        launch(a, false, 1, ctx->stream);
+    });
 }
 
 int launch_front_tc(gnn_ctx* ctx, const uint8_t* bases, int64_t n) {
@@ -591,8 +564,8 @@ int launch_front_tc(gnn_ctx* ctx, const uint8_t* bases, int64_t n) {
     fill_args(ctx, a, bases);
     a.mp = ctx->ws.mp;
     a.yp = ctx->ws.yp;
-    a.yp_c = ctx->c6_pad_skip ? ctx->w.tc_yp_const : nullptr;
-    a.mp_c = ctx->c6_pad_skip ? ctx->w.tc_mp_const : nullptr;
+    a.yp_c = ctx->c6_pad_skip ? ctx->w.tc_yp_const.get() : nullptr;
+    a.mp_c = ctx->c6_pad_skip ? ctx->w.tc_mp_const.get() : nullptr;
     a.cycles = ctx->phase_cycles;
     if (ctx->time_split && n > 0 && ctx->cu_count > 0) a.split = (int)std::max<int64_t>(1, std::min<int64_t>(4, ctx->cu_count / n));
     ctx->last_split = a.split;

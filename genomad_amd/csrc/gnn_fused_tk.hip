@@ -756,7 +756,7 @@ static void fill_args(const gnn_ctx* ctx, ArgsK& a, const uint8_t* bases) {
         a.pos_sorted[i] = d.pos_sorted[i];
         a.bucket_ptr[i] = d.bucket_ptr96[i];
     }
-    a.wva_tbl = reinterpret_cast<const unsigned char*>(d.tc_wva_tbl);
+    a.wva_tbl = reinterpret_cast<const unsigned char*>(d.tc_wva_tbl.get());
     a.x2_tbl = d.tk_x2_tbl;
     a.mpa_tbl = d.tk_mpa_tbl;
     a.x1t_tbl = d.tk_x1t_tbl;
@@ -781,10 +781,7 @@ size_t kmer_tables_bytes() {
 
 void free_kmer_tables(gnn_ctx* ctx) {
     DeviceWeights& d = ctx->w;
-    for (float** p : {&d.tk_x2_tbl, &d.tk_mpa_tbl, &d.tk_pt_tbl, &d.tk_x1t_tbl, &d.tk_yp_const, &d.tk_mp_const}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
+    for (DevBuf<float>* b : {&d.tk_x2_tbl, &d.tk_mpa_tbl, &d.tk_pt_tbl, &d.tk_x1t_tbl, &d.tk_yp_const, &d.tk_mp_const}) b->reset();
 }
 
 // X2Table and MpaTable on the device.  `reserve` bytes must stay free behind them (workspaces of the launches to come).
@@ -804,11 +801,11 @@ int build_kmer_tables(gnn_ctx* ctx, size_t reserve) {
                   std::to_string(free_b >> 30) + " GiB free on the device: GNN_PREC_F16X3TC keeps serving");
         return GNN_ERR_NOMEM;
     }
-    void *x1 = nullptr, *P = nullptr, *x2 = nullptr, *mpa = nullptr, *pt = nullptr, *x1t = nullptr, *eye = nullptr;
+    // the tables are built in locals and move into ctx->w once complete; whatever is still local when a step fails frees itself
+    DevBuf<float> x2, mpa, x1, pt, x1t, eye;
+    DevBuf<double> P;
     auto fail = [&](hipError_t e, const char* what) {
         (void)hipGetLastError();
-        for (void* p : {x1, P, x2, mpa, pt, x1t, eye})
-            if (p) (void)hipFree(p);
         set_error(std::string("k-mer tables: ") + what + " failed: " + hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? GNN_ERR_NOMEM : GNN_ERR_HIP;
     };
@@ -823,76 +820,62 @@ int build_kmer_tables(gnn_ctx* ctx, size_t reserve) {
         std::fprintf(stderr, "genomad_nn k-mer tables: %-40s %.3f s\n", what, std::chrono::duration<double>(now - t_last).count());
         t_last = now;
     };
-    if ((e = hipMalloc(&x2, x2_b)) != hipSuccess) return fail(e, "hipMalloc of the 14-mer table");
+    int rc;
+    if ((rc = x2.reserve(x2_b / 4, 0, "k-mer tables: hipMalloc of the 14-mer table"))) return rc;
     lap("hipMalloc 137 GB");
-    if ((e = hipMalloc(&mpa, mpa_b)) != hipSuccess) return fail(e, "hipMalloc of head A's pair-product table");
-    if ((e = hipMalloc(&x1, x1_b)) != hipSuccess) return fail(e, "hipMalloc of the 9-mer x1 table");
-    if ((e = hipMalloc(&pt, pt_b)) != hipSuccess) return fail(e, "hipMalloc of conv2's tap tables");
-    if ((e = hipMalloc(&x1t, x1t_b)) != hipSuccess) return fail(e, "hipMalloc of the x1 table");
-    if ((e = hipMalloc(&eye, (size_t)C * C * 4)) != hipSuccess) return fail(e, "hipMalloc of the identity");
-    if ((e = hipMalloc(&P, p_b)) != hipSuccess) return fail(e, "hipMalloc of the f64 tap tables");
+    if ((rc = mpa.reserve(mpa_b / 4, 0, "k-mer tables: hipMalloc of head A's pair-product table"))) return rc;
+    if ((rc = x1.reserve(x1_b / 4, 0, "k-mer tables: hipMalloc of the 9-mer x1 table"))) return rc;
+    if ((rc = pt.reserve(pt_b / 4, 0, "k-mer tables: hipMalloc of conv2's tap tables"))) return rc;
+    if ((rc = x1t.reserve(x1t_b / 4, 0, "k-mer tables: hipMalloc of the x1 table"))) return rc;
+    if ((rc = eye.reserve((size_t)C * C, 0, "k-mer tables: hipMalloc of the identity"))) return rc;
+    if ((rc = P.reserve(p_b / 8, 0, "k-mer tables: hipMalloc of the f64 tap tables"))) return rc;
     {   // x1 over WvaTable's index space = the same builder with the identity as the matrix (products with 0 and 1, summed in f64: exact)
         std::vector<float> id((size_t)C * C, 0.f);
         for (int k = 0; k < C; ++k) id[(size_t)k * C + k] = 1.f;
         if ((e = hipMemcpy(eye, id.data(), id.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload of the identity");
-        if (build_wva_rows_table(ctx, static_cast<const float*>(eye), static_cast<float*>(x1t))) return fail(hipGetLastError(), "launch of the x1 table build");
+        if (build_wva_rows_table(ctx, eye, x1t)) return fail(hipGetLastError(), "launch of the x1 table build");
     }
     lap("hipMalloc of the other four");
     for (int j = 0; j < KS; ++j)
-        if (build_wva_rows_table(ctx, d.conv_k[0] + (size_t)j * C * C, static_cast<float*>(pt) + (size_t)j * WvaTable::ROWS * C)) return fail(hipGetLastError(), "launch of a tap-table build");
+        if (build_wva_rows_table(ctx, d.conv_k[0] + (size_t)j * C * C, pt + (size_t)j * WvaTable::ROWS * C)) return fail(hipGetLastError(), "launch of a tap-table build");
     lap("tap tables over WvaTable's rows (6 x 2.7 M)");
     hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(x1tab_kernel, dim3(K9_ROWS), dim3(128), 0, st, d.conv1_pairs6, static_cast<float*>(x1));
+    hipLaunchKernelGGL(x1tab_kernel, dim3(K9_ROWS), dim3(128), 0, st, d.conv1_pairs6, x1.get());
     if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch of x1tab_kernel");
     lap("x1 per 9-mer");
-    hipLaunchKernelGGL(pj_kernel, dim3((K9_ROWS + PJ_ROWS - 1) / PJ_ROWS, KS), dim3(128), 0, st, static_cast<const float*>(x1), d.conv_k[0], static_cast<double*>(P));
+    hipLaunchKernelGGL(pj_kernel, dim3((K9_ROWS + PJ_ROWS - 1) / PJ_ROWS, KS), dim3(128), 0, st, x1.get(), d.conv_k[0], P.get());
     if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch of pj_kernel");
     lap("f64 tap tables per 9-mer");
-    hipLaunchKernelGGL(x2tab_kernel, dim3((X2_ROWS + X2TAB_ROWS - 1) / X2TAB_ROWS), dim3(256), 0, st, static_cast<const double*>(P), d.conv_b[0], static_cast<float*>(x2));
+    hipLaunchKernelGGL(x2tab_kernel, dim3((X2_ROWS + X2TAB_ROWS - 1) / X2TAB_ROWS), dim3(256), 0, st, P.get(), d.conv_b[0], x2.get());
     if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch of x2tab_kernel");
     lap("x2 per 14-mer (137 GB)");
-    hipLaunchKernelGGL(mpa_kernel, dim3((K9_ROWS + MPA_T - 1) / MPA_T, (NPAIR + MPA_T - 1) / MPA_T), dim3(256), 0, st, static_cast<const float*>(x1),
-                       d.weff_sorted[0], static_cast<float*>(mpa));
+    hipLaunchKernelGGL(mpa_kernel, dim3((K9_ROWS + MPA_T - 1) / MPA_T, (NPAIR + MPA_T - 1) / MPA_T), dim3(256), 0, st, x1.get(),
+                       d.weff_sorted[0], mpa.get());
     if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch of mpa_kernel");
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "building the tables");
     lap("head A's pair products (8.8 GB)");
-    (void)hipFree(x1);
-    (void)hipFree(P);
-    (void)hipFree(eye);
-    x1 = P = eye = nullptr;
-    d.tk_x2_tbl = static_cast<float*>(x2);
-    d.tk_mpa_tbl = static_cast<float*>(mpa);
-    d.tk_pt_tbl = static_cast<float*>(pt);
-    d.tk_x1t_tbl = static_cast<float*>(x1t);
-    // the all-N window's outputs, computed once by the kernel itself (padding skip)
-    void *bn = nullptr, *yc = nullptr, *mc = nullptr;
-    if ((e = hipMalloc(&bn, W)) != hipSuccess || (e = hipMalloc(&yc, (size_t)2 * POOLED * C * sizeof(float))) != hipSuccess ||
-        (e = hipMalloc(&mc, (size_t)2 * NPAIR * sizeof(float))) != hipSuccess) {
-        for (void* p : {bn, yc, mc})
-            if (p) (void)hipFree(p);
+    x1.reset();
+    P.reset();
+    eye.reset();
+    d.tk_x2_tbl = std::move(x2);
+    d.tk_mpa_tbl = std::move(mpa);
+    d.tk_pt_tbl = std::move(pt);
+    d.tk_x1t_tbl = std::move(x1t);
+    // the all-N window's outputs, computed once by the kernel itself (padding skip); it reads the tables from ctx->w (fill_args)
+    rc = all_n_consts(ctx, d.tk_yp_const, d.tk_mp_const, [&](const uint8_t* bn, float* yp, float* mp) {
+        ArgsK a;
+        fill_args(ctx, a, bn);
+        a.mp = mp;
+        a.yp = yp;
+        a.yp_c = nullptr;
+        a.mp_c = nullptr;
+        launch(a, false, 1, st);
+    });
+    if (rc) {
         free_kmer_tables(ctx);
-        x2 = mpa = pt = x1t = nullptr;
-        return fail(e, "hipMalloc of the all-N window's outputs");
+        set_error(std::string("k-mer tables: ") + gnn_last_error());
     }
-    (void)hipMemsetAsync(bn, 'N', W, st);
-    ArgsK a;
-    fill_args(ctx, a, static_cast<const uint8_t*>(bn));
-    a.mp = static_cast<float*>(mc);
-    a.yp = static_cast<float*>(yc);
-    a.yp_c = nullptr;
-    a.mp_c = nullptr;
-    launch(a, false, 1, st);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(bn);
-    d.tk_yp_const = static_cast<float*>(yc);
-    d.tk_mp_const = static_cast<float*>(mc);
-    if (e != hipSuccess) {
-        free_kmer_tables(ctx);
-        x2 = mpa = pt = x1t = nullptr;
-        return fail(e, "the all-N window's launch");
-    }
-    return GNN_OK;
+    return rc;
 }
 
 int launch_front_tk(gnn_ctx* ctx, const uint8_t* bases, int64_t n) {
@@ -909,8 +892,8 @@ int launch_front_tk(gnn_ctx* ctx, const uint8_t* bases, int64_t n) {
     fill_args(ctx, a, bases);
     a.mp = ctx->ws.mp;
     a.yp = ctx->ws.yp;
-    a.yp_c = ctx->c6_pad_skip ? ctx->w.tk_yp_const : nullptr;
-    a.mp_c = ctx->c6_pad_skip ? ctx->w.tk_mp_const : nullptr;
+    a.yp_c = ctx->c6_pad_skip ? ctx->w.tk_yp_const.get() : nullptr;
+    a.mp_c = ctx->c6_pad_skip ? ctx->w.tk_mp_const.get() : nullptr;
     a.cycles = ctx->phase_cycles;
     if (ctx->time_split && n > 0 && ctx->cu_count > 0) a.split = (int)std::max<int64_t>(1, std::min<int64_t>(4, ctx->cu_count / n));
     ctx->last_split = a.split;

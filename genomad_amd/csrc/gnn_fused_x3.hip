@@ -629,27 +629,17 @@ static void launch(const Args& a, bool f16, bool prof, unsigned nwin, hipStream_
 int pack_fused_x3_consts(gnn_ctx* ctx) {
     using namespace x3;
     DeviceWeights& d = ctx->w;
-    void* bn = nullptr;
-    GNN_HIP(hipMalloc(&bn, W));
-    ctx->owned.push_back(bn);
-    GNN_HIP(hipMemsetAsync(bn, 'N', W, ctx->stream));
     for (int m = 0; m < 2; ++m) {              // 0: bf16 limbs, 1: f16 limbs
-        void *yc = nullptr, *mc = nullptr;
-        GNN_HIP(hipMalloc(&yc, (size_t)2 * POOLED * C * sizeof(float)));
-        ctx->owned.push_back(yc);
-        GNN_HIP(hipMalloc(&mc, (size_t)2 * NPAIR * sizeof(float)));
-        ctx->owned.push_back(mc);
-        Args a;
-        fill_args(ctx, a, static_cast<const uint8_t*>(bn), m == 1);
-        a.mp = static_cast<float*>(mc);
-        a.yp = static_cast<float*>(yc);
-        a.yp_c = nullptr;
-        a.mp_c = nullptr;
-        launch(a, m == 1, false, 1, ctx->stream);
-        GNN_HIP(hipGetLastError());
-        GNN_HIP(hipStreamSynchronize(ctx->stream));
-        d.x3_yp_const[m] = static_cast<float*>(yc);
-        d.x3_mp_const[m] = static_cast<float*>(mc);
+        const int rc = all_n_consts(ctx, d.x3_yp_const[m], d.x3_mp_const[m], [&](const uint8_t* bn, float* yp, float* mp) {
+            Args a;
+            fill_args(ctx, a, bn, m == 1);
+            a.mp = mp;
+            a.yp = yp;
+            a.yp_c = nullptr;
+            a.mp_c = nullptr;
+            launch(a, m == 1, false, 1, ctx->stream);
+        });
+        if (rc) return rc;
     }
     return GNN_OK;
 }
@@ -665,8 +655,8 @@ int launch_front_x3(gnn_ctx* ctx, const uint8_t* bases, int64_t n, int precision
     fill_args(ctx, a, bases, f16);
     a.mp = ctx->ws.mp;
     a.yp = ctx->ws.yp;
-    a.yp_c = ctx->c6_pad_skip ? ctx->w.x3_yp_const[f16] : nullptr;
-    a.mp_c = ctx->c6_pad_skip ? ctx->w.x3_mp_const[f16] : nullptr;
+    a.yp_c = ctx->c6_pad_skip ? ctx->w.x3_yp_const[f16].get() : nullptr;
+    a.mp_c = ctx->c6_pad_skip ? ctx->w.x3_mp_const[f16].get() : nullptr;
     a.cycles = ctx->phase_cycles;
     // fewer windows than CUs (one workgroup owns a CU): deal every window's steps to several workgroups.  Capped at 4: each
     // additional workgroup recomputes one step of 47, and below 12 steps per run the prologue starts to show

@@ -56,28 +56,18 @@ std::vector<uint16_t> pack_frags(const float* wmat, int K, int N, bool f16) {
     return out;
 }
 
-template <typename Tp>
-static int upload_vec(gnn_ctx* ctx, const std::vector<Tp>& v, Tp** dev) {
-    void* p = nullptr;
-    GNN_HIP(hipMalloc(&p, v.size() * sizeof(Tp)));
-    ctx->owned.push_back(p);
-    GNN_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(Tp), hipMemcpyHostToDevice));
-    *dev = static_cast<Tp*>(p);
-    return GNN_OK;
-}
-
 int pack_fused_weights(gnn_ctx* ctx, const gnn_weights* w) {
     DeviceWeights& d = ctx->w;
     int rc;
     const float* ck[2] = {w->conv2_kernel, w->conv3_kernel};
     const gnn_igloo_weights* ig[2] = {&w->igloo_a, &w->igloo_b};
     for (int i = 0; i < 2; ++i) {
-        if ((rc = upload_vec(ctx, pack_frags(ck[i], KS * C, C), &d.conv_frag[i]))) return rc;
-        if ((rc = upload_vec(ctx, pack_frags(ig[i]->w_v, C, C), &d.wv_frag[i]))) return rc;
-        if ((rc = upload_vec(ctx, pack_frags(ig[i]->w_qk, NP, POOLED), &d.wqk_frag[i]))) return rc;
-        if ((rc = upload_vec(ctx, pack_frags(ig[i]->w_qk, NP, POOLED, true), &d.wqk_frag_h[i]))) return rc;
-        if ((rc = upload_vec(ctx, pack_frags(ck[i], KS * C, C, true), &d.conv_frag_h[i]))) return rc;
-        if ((rc = upload_vec(ctx, pack_frags(ig[i]->w_v, C, C, true), &d.wv_frag_h[i]))) return rc;
+        if ((rc = upload(ctx, pack_frags(ck[i], KS * C, C), &d.conv_frag[i]))) return rc;
+        if ((rc = upload(ctx, pack_frags(ig[i]->w_v, C, C), &d.wv_frag[i]))) return rc;
+        if ((rc = upload(ctx, pack_frags(ig[i]->w_qk, NP, POOLED), &d.wqk_frag[i]))) return rc;
+        if ((rc = upload(ctx, pack_frags(ig[i]->w_qk, NP, POOLED, true), &d.wqk_frag_h[i]))) return rc;
+        if ((rc = upload(ctx, pack_frags(ck[i], KS * C, C, true), &d.conv_frag_h[i]))) return rc;
+        if ((rc = upload(ctx, pack_frags(ig[i]->w_v, C, C, true), &d.wv_frag_h[i]))) return rc;
     }
     return GNN_OK;
 }

@@ -122,21 +122,21 @@ extern "C" int gnn_mfma_probe_kind(gnn_ctx* ctx, int kind, int ms_target, double
             v = (uint16_t)(sign | (exp << 7) | man);
         }
     }
-    void *dop = nullptr, *dsink = nullptr;
-    GNN_HIP(hipMalloc(&dop, host.size() * 2));
-    GNN_HIP(hipMalloc(&dsink, 16));
-    GNN_HIP(hipMemcpy(dop, host.data(), host.size() * 2, hipMemcpyHostToDevice));
+    DevBuf<uint16_t> dop;
+    DevBuf<float> dsink;
+    if (int arc = dop.upload(host.data(), host.size())) return arc;
+    if (int arc = dsink.reserve(4)) return arc;
     hipEvent_t e0, e1;
     GNN_HIP(hipEventCreate(&e0));
     GNN_HIP(hipEventCreate(&e1));
     auto run = [&](int iters, float* ms) -> int {
         GNN_HIP(hipEventRecord(e0, ctx->stream));
         if (kind == 2)
-            hipLaunchKernelGGL(mfma_probe_c6_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const uint4*)dop, iters, (float*)dsink);
+            hipLaunchKernelGGL(mfma_probe_c6_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const uint4*)dop.get(), iters, dsink.get());
         else if (kind == 1)
-            hipLaunchKernelGGL(mfma_probe_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, (const uint4*)dop, iters, (float*)dsink);
+            hipLaunchKernelGGL(mfma_probe_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, (const uint4*)dop.get(), iters, dsink.get());
         else
-            hipLaunchKernelGGL(mfma_probe_kernel<0>, dim3(blocks), dim3(256), 0, ctx->stream, (const uint4*)dop, iters, (float*)dsink);
+            hipLaunchKernelGGL(mfma_probe_kernel<0>, dim3(blocks), dim3(256), 0, ctx->stream, (const uint4*)dop.get(), iters, dsink.get());
         GNN_HIP(hipEventRecord(e1, ctx->stream));
         GNN_HIP(hipEventSynchronize(e1));
         GNN_HIP(hipEventElapsedTime(ms, e0, e1));
@@ -153,7 +153,5 @@ extern "C" int gnn_mfma_probe_kind(gnn_ctx* ctx, int kind, int ms_target, double
     if (!rc) *tflops_out = (double)blocks * 4 /*waves*/ * iters * (kind == 2 ? 8.0 : 12.0) * 32768.0 / (ms * 1e-3) / 1e12;
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    (void)hipFree(dop);
-    (void)hipFree(dsink);
     return rc;
 }
