@@ -36,6 +36,8 @@ OUT_OF_TOLERANCE = {"f16c6": 1.2e-4}
 DEFAULT_PRECISION = "f16x3tc"
 ERR_ARG, ERR_HIP, ERR_STATE, ERR_WEIGHTS, ERR_NOMEM = -1, -2, -3, -4, -5      # gnn_status
 OH_U8, OH_BF16, OH_F32 = 0, 1, 2
+STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2       # gnn_strand
+STRANDS = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
 K_FUSED, K_BACKEND, K_ENCODER, K_F32_FRONT = 0, 1, 2, 3
 
 _f32p = C.POINTER(C.c_float)
@@ -101,6 +103,11 @@ SIGNATURES = {
     "gnn_classify_contigs_embed": (_int, [_vp, _vp, _int, _i64, _vp, _i64, _int, _int, _vp, _vp, _i64, C.POINTER(_i64), _vp]),
     "gnn_scan_plan": (_int, [_vp, _i64, _int, _int, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _vp, _vp]),
     "gnn_scan_contigs": (_int, [_vp, _vp, _int, _i64, _vp, _i64, _int, _int, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "gnn_revcomp_spans_dev": (_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
+    "gnn_classify_contigs_strand": (_int, [_vp, _vp, _int, _i64, _vp, _i64, _int, _int, _vp, _vp, _i64, C.POINTER(_i64), _vp, _int, _vp,
+                                           _vp]),
+    "gnn_scan_contigs_strand": (_int, [_vp, _vp, _int, _i64, _vp, _i64, _int, _int, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _int, _vp,
+                                       _vp]),
     "gnn_embed": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_embed_dev": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_debug_forward": (_int, [_vp, _vp, _i64, _int, _vp, C.POINTER(Taps)]),

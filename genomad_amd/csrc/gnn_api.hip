@@ -1091,6 +1091,27 @@ int gnn_classify_spans(gnn_ctx* ctx, const uint8_t* seq_dev, const int64_t* star
     return rc;
 }
 
+int gnn_revcomp_spans_dev(gnn_ctx* ctx, const uint8_t* seq_dev, const int64_t* starts_host, const int32_t* lens_host,
+                          int64_t n, uint8_t* bases_dev_out) {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!seq_dev || !starts_host || !lens_host || !bases_dev_out))) {
+        set_error("bad argument to gnn_revcomp_spans_dev");
+        return GNN_ERR_ARG;
+    }
+    if ((uintptr_t)bases_dev_out & 3) {
+        set_error("gnn_revcomp_spans_dev: bases_dev_out is not 4-byte aligned");
+        return GNN_ERR_ARG;
+    }
+    if (n == 0) return GNN_OK;
+    DevBuf<int64_t> ds;
+    DevBuf<int32_t> dl;
+    if ((rc = upload_spans(ctx, starts_host, lens_host, n, ds, dl))) return rc;
+    if ((rc = launch_revcomp(ctx, seq_dev, ds, dl, n, bases_dev_out))) return rc;
+    GNN_HIP(hipStreamSynchronize(ctx->stream));      // the span table goes with this call
+    return GNN_OK;
+}
+
 int gnn_profile_enable(gnn_ctx* ctx, int on) {
     if (!ctx) {
         set_error("ctx is NULL");

@@ -228,6 +228,9 @@ int launch_span_count(gnn_ctx* ctx, const uint8_t* seq, const int64_t* starts, c
                       int byte, int32_t* counts);
 int launch_materialize(gnn_ctx* ctx, const uint8_t* seq, const int64_t* starts, const int32_t* lens, int64_t n,
                        uint8_t* bases);
+// the same spans as reverse-complement windows (gnn_encode.hip, revcomp_kernel); bases must be 4-byte aligned, as above
+int launch_revcomp(gnn_ctx* ctx, const uint8_t* seq, const int64_t* starts, const int32_t* lens, int64_t n,
+                   uint8_t* bases);
 int launch_front_f32(gnn_ctx* ctx, const uint8_t* bases, int64_t n);         // -> ws.mp, ws.yp (+ ws.x)
 // ws.mp, ws.yp -> scores; emb_dev != NULL: also h1 (the encoder embedding) as emb_dev[n][GNN_EMBED_DIM] of emb_dtype (gnn_emb_dtype)
 int launch_backend(gnn_ctx* ctx, int64_t n, int precision, float* scores_dev, void* emb_dev = nullptr, int emb_dtype = GNN_EMB_F32);

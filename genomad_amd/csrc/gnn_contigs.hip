@@ -14,6 +14,11 @@
 // gnn_scan_contigs is the same function at a stride: windows start every `stride` bases instead of every 6000, their scores DO
 // leave the device, and a fold kernel turns them into a track of one score triple per stride-wide bin ("Score tracks").
 // At stride 6000 the span table, and with it every bit of the contig scores, is the one of gnn_classify_contigs.
+//
+// The *_strand entry points are the same function with one more parameter ("Both strands"): every span is also - or only -
+// materialised as its reverse complement (revcomp_kernel), a slab's forward and reverse windows go through the front end as ONE
+// batch, and a split kernel files the batch's scores per strand and forms the `both` score (f + r) * 0.5f.  Spans, the N rule, ids,
+// bins and the folds are the forward ones.
 #include <algorithm>
 #include <cstring>
 
@@ -46,6 +51,12 @@ struct ContigWorkspace {
     DevBuf<int64_t> d_win_off, d_bin_off;
     DevBuf<float> d_track;
     DevBuf<int32_t> d_cover;
+    // the *_strand entry points: the reverse windows' and the combined (`both`) scores, GNN_CLASSES per window each; the scores of
+    // one slab's batch [forward | reverse] before the split; the per-contig means of each strand ([forward | reverse] rows); the
+    // reverse strand's own embedding sums and kept-window counts
+    DevBuf<float> d_scores_rev, d_scores_mix, d_slab_scores, d_out_strand;
+    DevBuf<float> d_emb_sum_rev;
+    DevBuf<int32_t> d_emb_kept_rev;
 
     // What the buffer groups hold, in windows / contigs + 1 / bins.  The head-room is counted in elements, so a buffer with
     // several elements per window or bin holds fewer of them than its neighbours: the smallest member decides.
@@ -53,6 +64,7 @@ struct ContigWorkspace {
         return std::min({d_starts.capacity(), d_ids.capacity(), d_lens.capacity(), d_window_n.capacity(), d_counts.capacity(),
                          d_scores.capacity() / GNN_CLASSES});
     }
+    size_t strand_cap() const { return std::min(d_scores_rev.capacity(), d_scores_mix.capacity()) / GNN_CLASSES; }
     size_t off_cap() const { return std::min(d_win_off.capacity(), d_bin_off.capacity()); }
     size_t bin_cap() const { return std::min(d_track.capacity() / GNN_CLASSES, d_cover.capacity()); }
 };
@@ -65,6 +77,16 @@ struct ScanOut {
     float* track;               // may be NULL
     int32_t* cover;             // may be NULL
     int64_t bins_capacity;
+};
+
+// What the *_strand entry points add: the mode (gnn_strand) and host buffers for each strand's own results (any may be NULL).  A
+// strand is computed when the mode needs it or one of its buffers is given.
+struct StrandOut {
+    int strand;
+    float* contig_fwd;          // [n_contigs][3]: each strand's own masked mean
+    float* contig_rev;
+    float* window_fwd;          // scans only: [n_windows][3]
+    float* window_rev;
 };
 
 // The window rule, once: seq_windows(seq, 6000, 2500, max_windows) of the reference (sequence.py:150-167) with the window start
@@ -199,6 +221,27 @@ __global__ void scan_track_kernel(const float* __restrict__ scores, const int32_
     if (cl == 0) cover[bin] = kept;
 }
 
+// The scores of one slab's batch [m forward windows | m reverse windows] -> each strand's rows of the window table, and the
+// `both` score (f + r) * 0.5f: one f32 addition, one exact halving - a single rounding.  One thread per (window, class).
+__global__ void strand_split_kernel(const float* __restrict__ batch, int64_t cells, float* __restrict__ fwd, float* __restrict__ rev,
+                                    float* __restrict__ mix) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cells) return;
+    const float f = batch[i], r = batch[cells + i];
+    fwd[i] = f;
+    rev[i] = r;
+    mix[i] = (f + r) * 0.5f;
+}
+
+// `both`: the two strands' embedding sums -> (sum_f + sum_r) / (2 kept), in place in sum_f (zero row without a kept window)
+__global__ void emb_both_mean_kernel(float* __restrict__ sums, const float* __restrict__ sums_rev, const int32_t* __restrict__ kept,
+                                     int64_t n_contigs) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_contigs * HID) return;
+    const int k = kept[i / HID];
+    sums[i] = k ? (sums[i] + sums_rev[i]) / (float)(2 * k) : 0.f;
+}
+
 }  // namespace gnn
 
 using namespace gnn;
@@ -206,8 +249,13 @@ using namespace gnn;
 static int classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes, const int64_t* offsets_host,
                             int64_t n_contigs, int single_window, int precision, float* contig_scores_host, int64_t* window_ids_host,
                             int64_t ids_capacity, int64_t* n_windows_out, float* contig_emb_host, int64_t stride = W,
-                            const ScanOut* scan = nullptr) {
+                            const ScanOut* scan = nullptr, const StrandOut* so = nullptr) {
     const char* const fn = scan ? "gnn_scan_contigs" : "gnn_classify_contigs";
+    const int strand = so ? so->strand : GNN_STRAND_FORWARD;
+    // which strands run: what the mode averages, and what the caller asked to see on its own
+    const bool need_f = strand != GNN_STRAND_REVERSE || (so && (so->contig_fwd || so->window_fwd));
+    const bool need_r = strand != GNN_STRAND_FORWARD || (so && (so->contig_rev || so->window_rev));
+    const int64_t ns = (need_f ? 1 : 0) + (need_r ? 1 : 0);
     if (!ctx) {
         set_error("ctx is NULL");
         return GNN_ERR_ARG;
@@ -255,6 +303,9 @@ static int classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, i
     *n_windows_out = 0;
     if (n_contigs && contig_scores_host) std::memset(contig_scores_host, 0, (size_t)n_contigs * GNN_CLASSES * sizeof(float));
     if (n_contigs && contig_emb_host) std::memset(contig_emb_host, 0, (size_t)n_contigs * HID * sizeof(float));
+    if (so)
+        for (float* p : {so->contig_fwd, so->contig_rev})
+            if (n_contigs && p) std::memset(p, 0, (size_t)n_contigs * GNN_CLASSES * sizeof(float));
     if (n == 0) return GNN_OK;
     if (scan) {
         if (!scan->window_scores || scan->windows_capacity < n) {
@@ -283,9 +334,19 @@ static int classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, i
         if (!rc) rc = reserve_roomy(w.d_scores, (size_t)n * GNN_CLASSES);
         if (rc) return rc;
     }
-    const int64_t slab = std::min<int64_t>(n, 4 * std::max<int64_t>(ctx->chunk_fused, 1));
-    if ((rc = reserve_roomy(w.d_bases, (size_t)slab * W))) return rc;
+    if (need_r && w.strand_cap() < (size_t)n) {      // 24 B per window more, and only for a caller of the *_strand entry points
+        GNN_HIP(hipStreamSynchronize(ctx->stream));
+        reset_all(w.d_scores_rev, w.d_scores_mix);
+        if (!rc) rc = reserve_roomy(w.d_scores_rev, (size_t)n * GNN_CLASSES);
+        if (!rc) rc = reserve_roomy(w.d_scores_mix, (size_t)n * GNN_CLASSES);
+        if (rc) return rc;
+    }
+    // a slab is what d_bases holds: 4 launches of windows, of one strand or - forward windows, then reverse windows - of both
+    const int64_t slab = std::min<int64_t>(n, std::max<int64_t>(4 * std::max<int64_t>(ctx->chunk_fused, 1) / ns, 1));
+    if ((rc = reserve_roomy(w.d_bases, (size_t)(slab * ns) * W))) return rc;
     if ((rc = reserve_roomy(w.d_out, (size_t)n_contigs * GNN_CLASSES))) return rc;
+    if (ns == 2 && (rc = reserve_roomy(w.d_slab_scores, (size_t)(slab * 2) * GNN_CLASSES))) return rc;
+    if (so && (so->contig_fwd || so->contig_rev) && (rc = reserve_roomy(w.d_out_strand, (size_t)n_contigs * 2 * GNN_CLASSES))) return rc;
     if (fold) {        // 16 B per contig and 16 B per bin (hipFree of a buffer that grows waits for the kernels that read it)
         if (w.off_cap() < (size_t)n_contigs + 1) {
             reset_all(w.d_win_off, w.d_bin_off);
@@ -301,10 +362,18 @@ static int classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, i
     }
     if (contig_emb_host) {
         // a slab's window embeddings (2 KB each) and the per-contig sums: never every window's row (10 M windows would be 20 GB)
-        if (w.d_emb.capacity() < (size_t)slab * HID || w.d_emb_sum.capacity() < (size_t)n_contigs * HID ||
-            w.d_emb_kept.capacity() < (size_t)n_contigs)
+        const bool rev_sum = strand != GNN_STRAND_FORWARD;
+        if (w.d_emb.capacity() < (size_t)(slab * ns) * HID || w.d_emb_sum.capacity() < (size_t)n_contigs * HID ||
+            w.d_emb_kept.capacity() < (size_t)n_contigs ||
+            (rev_sum && (w.d_emb_sum_rev.capacity() < (size_t)n_contigs * HID || w.d_emb_kept_rev.capacity() < (size_t)n_contigs)))
             GNN_HIP(hipStreamSynchronize(ctx->stream));
-        if ((rc = reserve_roomy(w.d_emb, (size_t)slab * HID))) return rc;
+        if ((rc = reserve_roomy(w.d_emb, (size_t)(slab * ns) * HID))) return rc;
+        if (rev_sum) {       // the reverse strand folds into a sum of its own: two independent sums, whatever the slab size
+            if ((rc = reserve_roomy(w.d_emb_sum_rev, (size_t)n_contigs * HID))) return rc;
+            if ((rc = reserve_roomy(w.d_emb_kept_rev, (size_t)n_contigs))) return rc;
+            GNN_HIP(hipMemsetAsync(w.d_emb_sum_rev, 0, (size_t)n_contigs * HID * sizeof(float), ctx->stream));
+            GNN_HIP(hipMemsetAsync(w.d_emb_kept_rev, 0, (size_t)n_contigs * sizeof(int32_t), ctx->stream));
+        }
         if ((rc = reserve_roomy(w.d_emb_sum, (size_t)n_contigs * HID))) return rc;
         if ((rc = reserve_roomy(w.d_emb_kept, (size_t)n_contigs))) return rc;
         GNN_HIP(hipMemsetAsync(w.d_emb_sum, 0, (size_t)n_contigs * HID * sizeof(float), ctx->stream));
@@ -347,40 +416,75 @@ static int classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, i
             if (upto > 0) GNN_HIP(hipStreamWaitEvent(ctx->stream, w.piece_done[upto - 1], 0));
         }
         if ((rc = launch_span_count(ctx, seq_dev, w.d_starts + a, w.d_lens + a, m, 'N', w.d_counts + a))) return rc;
-        if ((rc = launch_materialize(ctx, seq_dev, w.d_starts + a, w.d_lens + a, m, w.d_bases))) return rc;
-        if ((rc = classify_chunks(ctx, w.d_bases, m, precision, w.d_scores + a * GNN_CLASSES, false, contig_emb_host ? w.d_emb.get() : nullptr,
+        const int64_t r0 = need_f ? m : 0;      // the batch's first reverse window (the N count above served both strands)
+        if (need_f && (rc = launch_materialize(ctx, seq_dev, w.d_starts + a, w.d_lens + a, m, w.d_bases))) return rc;
+        if (need_r && (rc = launch_revcomp(ctx, seq_dev, w.d_starts + a, w.d_lens + a, m, w.d_bases + r0 * W))) return rc;
+        float* const batch_scores = ns == 2 ? w.d_slab_scores.get() : (need_f ? w.d_scores : w.d_scores_rev) + a * GNN_CLASSES;
+        if ((rc = classify_chunks(ctx, w.d_bases, m * ns, precision, batch_scores, false, contig_emb_host ? w.d_emb.get() : nullptr,
                                   GNN_EMB_F32)))
             return rc;
+        if (ns == 2) {
+            const int64_t cells = m * GNN_CLASSES;
+            hipLaunchKernelGGL(strand_split_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, w.d_slab_scores,
+                               cells, w.d_scores + a * GNN_CLASSES, w.d_scores_rev + a * GNN_CLASSES, w.d_scores_mix + a * GNN_CLASSES);
+            GNN_HIP(hipGetLastError());
+        }
         if (contig_emb_host) {     // classify_chunks has ordered its back ends before ctx->stream: the slab's rows are complete
             const int64_t touched = w.ids[a + m - 1] - w.ids[a] + 1;
-            hipLaunchKernelGGL(emb_fold_kernel, dim3((unsigned)touched), dim3(FOLD_THREADS), 0, ctx->stream, w.d_emb, w.d_ids,
-                               w.d_window_n, w.d_counts, a, m, w.d_emb_sum, w.d_emb_kept);
+            if (strand != GNN_STRAND_REVERSE)
+                hipLaunchKernelGGL(emb_fold_kernel, dim3((unsigned)touched), dim3(FOLD_THREADS), 0, ctx->stream, w.d_emb, w.d_ids,
+                                   w.d_window_n, w.d_counts, a, m, w.d_emb_sum, w.d_emb_kept);
+            if (strand != GNN_STRAND_FORWARD)
+                hipLaunchKernelGGL(emb_fold_kernel, dim3((unsigned)touched), dim3(FOLD_THREADS), 0, ctx->stream, w.d_emb + r0 * HID, w.d_ids,
+                                   w.d_window_n, w.d_counts, a, m, w.d_emb_sum_rev, w.d_emb_kept_rev);
             GNN_HIP(hipGetLastError());
         }
     }
+    // the window scores of the mode: what the contig mean, the track and window_scores_host carry
+    const float* const d_mode = strand == GNN_STRAND_BOTH ? w.d_scores_mix : (strand == GNN_STRAND_REVERSE ? w.d_scores_rev : w.d_scores);
     if (contig_emb_host) {
         const int64_t cells = n_contigs * HID;
-        hipLaunchKernelGGL(emb_mean_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, w.d_emb_sum, w.d_emb_kept,
-                           n_contigs);
+        float* const d_mean = strand == GNN_STRAND_REVERSE ? w.d_emb_sum_rev : w.d_emb_sum;
+        if (strand == GNN_STRAND_BOTH)
+            hipLaunchKernelGGL(emb_both_mean_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, w.d_emb_sum,
+                               w.d_emb_sum_rev, w.d_emb_kept, n_contigs);
+        else
+            hipLaunchKernelGGL(emb_mean_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, d_mean,
+                               strand == GNN_STRAND_REVERSE ? w.d_emb_kept_rev : w.d_emb_kept, n_contigs);
         GNN_HIP(hipGetLastError());
-        GNN_HIP(hipMemcpyAsync(contig_emb_host, w.d_emb_sum, (size_t)cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        GNN_HIP(hipMemcpyAsync(contig_emb_host, d_mean, (size_t)cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     }
     const int64_t threads = n_contigs * GNN_CLASSES;
     hipLaunchKernelGGL(masked_segment_mean_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream,
-                       w.d_scores, w.d_ids, w.d_window_n, w.d_counts, n, n_contigs, w.d_out);
+                       d_mode, w.d_ids, w.d_window_n, w.d_counts, n, n_contigs, w.d_out);
     GNN_HIP(hipGetLastError());
+    if (so) {
+        const struct { float* host; const float* d_win; float* d_mean; float* win_host; } each[2] = {
+            {so->contig_fwd, w.d_scores, w.d_out_strand, so->window_fwd},
+            {so->contig_rev, w.d_scores_rev, w.d_out_strand + threads, so->window_rev}};
+        for (const auto& e : each) {
+            if (e.host) {
+                hipLaunchKernelGGL(masked_segment_mean_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream,
+                                   e.d_win, w.d_ids, w.d_window_n, w.d_counts, n, n_contigs, e.d_mean);
+                GNN_HIP(hipGetLastError());
+                GNN_HIP(hipMemcpyAsync(e.host, e.d_mean, (size_t)threads * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+            }
+            if (e.win_host)
+                GNN_HIP(hipMemcpyAsync(e.win_host, e.d_win, (size_t)n * GNN_CLASSES * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
     w.counts.resize((size_t)n);
     if (contig_scores_host)
         GNN_HIP(hipMemcpyAsync(contig_scores_host, w.d_out, (size_t)threads * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     GNN_HIP(hipMemcpyAsync(w.counts.data(), w.d_counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (scan) {
-        GNN_HIP(hipMemcpyAsync(scan->window_scores, w.d_scores, (size_t)n * GNN_CLASSES * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        GNN_HIP(hipMemcpyAsync(scan->window_scores, d_mode, (size_t)n * GNN_CLASSES * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
         if (fold) {
             const size_t off_bytes = (size_t)(n_contigs + 1) * sizeof(int64_t);
             GNN_HIP(hipMemcpyAsync(w.d_win_off, w.win_off.data(), off_bytes, hipMemcpyHostToDevice, ctx->stream));
             GNN_HIP(hipMemcpyAsync(w.d_bin_off, w.bin_off.data(), off_bytes, hipMemcpyHostToDevice, ctx->stream));
             const int64_t cells = n_bins * GNN_CLASSES;
-            hipLaunchKernelGGL(scan_track_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, w.d_scores, w.d_lens,
+            hipLaunchKernelGGL(scan_track_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, d_mode, w.d_lens,
                                w.d_counts, w.d_win_off, w.d_bin_off, n_contigs, n_bins, (int)stride, w.d_track, w.d_cover);
             GNN_HIP(hipGetLastError());
             if (scan->track)
@@ -477,4 +581,42 @@ extern "C" int gnn_scan_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_hos
     int64_t kept = 0;
     return classify_contigs(ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision,
                             contig_scores_host_or_null, nullptr, 0, &kept, nullptr, stride, &scan);
+}
+
+static int check_strand(int strand, const char* fn) {
+    if (strand == GNN_STRAND_FORWARD || strand == GNN_STRAND_REVERSE || strand == GNN_STRAND_BOTH) return GNN_OK;
+    set_error(std::string(fn) + ": strand " + std::to_string(strand) + " is not a gnn_strand (0 forward, 1 reverse, 2 both)");
+    return GNN_ERR_ARG;
+}
+
+extern "C" int gnn_classify_contigs_strand(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes,
+                                           const int64_t* offsets_host, int64_t n_contigs, int single_window, int precision,
+                                           float* contig_scores_host, int64_t* window_ids_host, int64_t ids_capacity,
+                                           int64_t* n_windows_out, float* contig_emb_host_or_null, int strand,
+                                           float* contig_scores_fwd_host_or_null, float* contig_scores_rev_host_or_null) {
+    if (int rc = check_strand(strand, "gnn_classify_contigs_strand")) return rc;
+    if (contig_emb_host_or_null && precision == GNN_PREC_F16C6) {
+        set_error("gnn_classify_contigs_strand: GNN_PREC_F16C6 has no embedding path (the frozen mode's dense head runs on the matrix "
+                  "pipe and is outside the tolerance); use f16x3tc, f16x3tk, f16x3, bf16x3 or f32");
+        return GNN_ERR_ARG;
+    }
+    const StrandOut so{strand, contig_scores_fwd_host_or_null, contig_scores_rev_host_or_null, nullptr, nullptr};
+    return classify_contigs(ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision, contig_scores_host,
+                            window_ids_host, ids_capacity, n_windows_out, n_contigs > 0 ? contig_emb_host_or_null : nullptr, W, nullptr,
+                            &so);
+}
+
+extern "C" int gnn_scan_contigs_strand(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes, const int64_t* offsets_host,
+                                       int64_t n_contigs, int stride, int single_window, int precision, float* window_scores_host,
+                                       uint8_t* window_kept_host_or_null, int64_t windows_capacity, float* track_host_or_null,
+                                       int32_t* cover_host_or_null, int64_t bins_capacity, float* contig_scores_host_or_null, int strand,
+                                       float* window_scores_fwd_host_or_null, float* window_scores_rev_host_or_null) {
+    if (int rc = check_stride(stride, "gnn_scan_contigs_strand")) return rc;
+    if (int rc = check_strand(strand, "gnn_scan_contigs_strand")) return rc;
+    const ScanOut scan{window_scores_host, window_kept_host_or_null, windows_capacity, track_host_or_null, cover_host_or_null,
+                       bins_capacity};
+    const StrandOut so{strand, nullptr, nullptr, window_scores_fwd_host_or_null, window_scores_rev_host_or_null};
+    int64_t kept = 0;
+    return classify_contigs(ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision,
+                            contig_scores_host_or_null, nullptr, 0, &kept, nullptr, stride, &scan, &so);
 }

@@ -189,6 +189,44 @@ __global__ __launch_bounds__(256) void materialize_kernel(const uint8_t* __restr
     out[g] = word;
 }
 
+// Span -> padded REVERSE-COMPLEMENT window: out[i] = comp(upper(seq[start + len - 1 - i])) for i < len, 'N' for len <= i < 6000
+// (right-padded like the forward window: the pad is not reversed to the front).  comp: A<->T, C<->G, every other byte unchanged -
+// the tokenizer maps any non-ACGT byte to token 0 on either strand, so an IUPAC-exact table would change no score.  One thread
+// per 4 output bytes, as materialize_kernel: the reads of a wave run backwards over 256 contiguous span bytes, the stores are
+// coalesced dwords.
+__global__ __launch_bounds__(256) void revcomp_kernel(const uint8_t* __restrict__ seq,
+                                                      const int64_t* __restrict__ starts,
+                                                      const int32_t* __restrict__ lens, int64_t n,
+                                                      uint32_t* __restrict__ out) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n * (W / 4)) return;
+    const int64_t wi = g / (W / 4);
+    const int p0 = (int)(g - wi * (W / 4)) * 4;
+    const int len = lens[wi];
+    const uint8_t* last = seq + starts[wi] + len - 1;      // read only where p0 + k < len: never before the span's first byte
+    uint32_t word = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint32_t ch = 'N';
+        if (p0 + k < len) {
+            ch = last[-(p0 + k)];
+            if (ch >= 'a' && ch <= 'z') ch -= 32;      // str.upper() on ASCII
+            ch = ch == 'A' ? 'T' : (ch == 'T' ? 'A' : (ch == 'C' ? 'G' : (ch == 'G' ? 'C' : ch)));
+        }
+        word |= ch << (8 * k);
+    }
+    out[g] = word;
+}
+
+int launch_revcomp(gnn_ctx* ctx, const uint8_t* seq, const int64_t* starts, const int32_t* lens, int64_t n,
+                   uint8_t* bases) {
+    const int64_t groups = n * (W / 4);
+    hipLaunchKernelGGL(revcomp_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, ctx->stream, seq,
+                       starts, lens, n, reinterpret_cast<uint32_t*>(bases));
+    GNN_HIP(hipGetLastError());
+    return GNN_OK;
+}
+
 int launch_span_count(gnn_ctx* ctx, const uint8_t* seq, const int64_t* starts, const int32_t* lens, int64_t n,
                       int byte, int32_t* counts) {
     hipLaunchKernelGGL(span_count_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, seq, starts, lens,

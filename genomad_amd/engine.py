@@ -53,6 +53,13 @@ class ScanResult:
         return {k: getattr(self, k) for k in self.FIELDS}
 
 
+class StrandScanResult(ScanResult):
+    """What :meth:`NNEngine.scan_contigs_strand` returns: the fields of :class:`ScanResult` for the strand mode ``strand``
+    ("forward", "reverse" or "both": ``scores``, ``track`` and ``contig_scores`` carry it; the window tables, ``kept`` and ``cover``
+    do not depend on it) plus ``scores_fwd`` and ``scores_rev`` (n_windows, 3): each strand's own window scores."""
+    FIELDS = ScanResult.FIELDS + ("strand", "scores_fwd", "scores_rev")
+
+
 class NNEngine:
     def __init__(self, device: int = 0, weights: dict = None, chunk: int = None):
         self.lib = _lib.load()
@@ -316,6 +323,88 @@ class NNEngine:
                                         track.ctypes.data, cover.ctypes.data, n_bins, contig_scores.ctypes.data))
         return ScanResult(stride=int(stride), win_offsets=win_off, starts=starts, lens=lens, kept=kept.astype(bool), scores=scores,
                           bin_offsets=bin_off, track=track, cover=cover, contig_scores=contig_scores)
+
+    # -- both strands --------------------------------------------------------------------
+    def revcomp_spans_dev(self, seq_ptr: int, starts, lens, bases_ptr: int):
+        """``gnn_revcomp_spans_dev``: the reverse windows (``sequence.revcomp_spans``) of the spans (start, len <= 6000) of a packed
+        buffer in HBM, written to ``bases_ptr`` (n x 6000 bytes on the device, 4-byte aligned) - ready for :meth:`classify_dev` /
+        :meth:`embed_dev`.  Returns when they are written."""
+        starts = np.ascontiguousarray(starts, dtype=np.int64)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        if starts.shape != lens.shape or starts.ndim != 1:
+            raise ValueError("starts and lens must be 1-d arrays of one length")
+        check(self.lib.gnn_revcomp_spans_dev(self.ctx, seq_ptr, starts.ctypes.data, lens.ctypes.data, len(starts), bases_ptr))
+
+    def classify_contigs_strand(self, seq: np.ndarray, offsets: np.ndarray, strand="both", single_window: bool = False,
+                                precision=_lib.DEFAULT_PRECISION, embed: bool = False):
+        """:meth:`classify_contigs` on the forward windows, their reverse complements, or both (``gnn_classify_contigs_strand``;
+        the definitions are ``sequence.revcomp_spans`` and ``sequence.strand_mean``).  The windows, the N rule and the window ids
+        are the forward ones; under "both" a window's score is the f32 mean of its two strands and the contig score the mean of
+        those.  Returns (contig_scores (n_contigs, 3) of the mode, contig ids of the kept windows, contig embeddings
+        (n_contigs, 512) of the mode or None without ``embed``, forward contig scores, reverse contig scores); a strand the
+        mode does not need is computed for its own scores.  "forward" is bit-identical to classify_contigs / embed_contigs."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        return self._classify_contigs_strand(seq.ctypes.data, 1, seq.nbytes, offsets, strand, single_window, precision, embed)
+
+    def classify_contigs_strand_dev(self, seq_ptr: int, offsets: np.ndarray, strand="both", single_window: bool = False,
+                                    precision=_lib.DEFAULT_PRECISION, embed: bool = False):
+        """Same as :meth:`classify_contigs_strand` for a packed contig buffer that is already resident in HBM."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        return self._classify_contigs_strand(seq_ptr, 0, int(offsets[-1]) if len(offsets) else 0, offsets, strand, single_window,
+                                             precision, embed)
+
+    @staticmethod
+    def _strand_code(strand) -> int:
+        return _lib.STRANDS[strand] if isinstance(strand, str) else int(strand)       # an int goes to the library as it is
+
+    def _classify_contigs_strand(self, seq_ptr, on_host, seq_bytes, offsets, strand, single_window, precision, embed):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError("offsets must hold n_contigs + 1 byte offsets")
+        n_contigs = len(offsets) - 1
+        scores, fwd, rev = (np.zeros((n_contigs, _lib.CLASSES), dtype=np.float32) for _ in range(3))
+        emb = np.zeros((n_contigs, _lib.EMBED_DIM), dtype=np.float32) if embed else None
+        cap = int(((np.diff(offsets) + _lib.WINDOW - 1) // _lib.WINDOW).sum()) if n_contigs else 0
+        ids = np.empty(max(cap, 1), dtype=np.int64)
+        n = C.c_int64()
+        check(self.lib.gnn_classify_contigs_strand(
+            self.ctx, seq_ptr, int(on_host), int(seq_bytes), offsets.ctypes.data, n_contigs, int(bool(single_window)),
+            _lib.PRECISIONS[precision], scores.ctypes.data, ids.ctypes.data, cap, C.byref(n), emb.ctypes.data if embed else None,
+            self._strand_code(strand), fwd.ctypes.data, rev.ctypes.data))
+        return scores, ids[:n.value].copy(), emb, fwd, rev
+
+    def scan_contigs_strand(self, seq: np.ndarray, offsets: np.ndarray, stride: int, strand="both", single_window: bool = False,
+                            precision=_lib.DEFAULT_PRECISION) -> StrandScanResult:
+        """:meth:`scan_contigs` with a strand mode (``gnn_scan_contigs_strand``): ``scores``, ``track`` and ``contig_scores`` carry
+        the mode, ``scores_fwd`` / ``scores_rev`` each strand's own window scores; everything else is the forward scan's."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        return self._scan_contigs_strand(seq.ctypes.data, 1, seq.nbytes, offsets, stride, strand, single_window, precision)
+
+    def scan_contigs_strand_dev(self, seq_ptr: int, offsets: np.ndarray, stride: int, strand="both", single_window: bool = False,
+                                precision=_lib.DEFAULT_PRECISION) -> StrandScanResult:
+        """Same as :meth:`scan_contigs_strand` for a packed contig buffer that is already resident in HBM."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        return self._scan_contigs_strand(seq_ptr, 0, int(offsets[-1]) if len(offsets) else 0, offsets, stride, strand, single_window,
+                                         precision)
+
+    def _scan_contigs_strand(self, seq_ptr, on_host, seq_bytes, offsets, stride, strand, single_window, precision):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        win_off, bin_off, starts, lens = self.scan_plan(offsets, stride, single_window)
+        n_contigs, n, n_bins = len(offsets) - 1, len(starts), int(bin_off[-1])
+        scores, fwd, rev = (np.zeros((n, _lib.CLASSES), dtype=np.float32) for _ in range(3))
+        kept = np.zeros(n, dtype=np.uint8)
+        track = np.zeros((n_bins, _lib.CLASSES), dtype=np.float32)
+        cover = np.zeros(n_bins, dtype=np.int32)
+        contig_scores = np.zeros((n_contigs, _lib.CLASSES), dtype=np.float32)
+        code = self._strand_code(strand)
+        check(self.lib.gnn_scan_contigs_strand(self.ctx, seq_ptr, int(on_host), int(seq_bytes), offsets.ctypes.data, n_contigs,
+                                               int(stride), int(bool(single_window)), _lib.PRECISIONS[precision], scores.ctypes.data,
+                                               kept.ctypes.data, n, track.ctypes.data, cover.ctypes.data, n_bins,
+                                               contig_scores.ctypes.data, code, fwd.ctypes.data, rev.ctypes.data))
+        name = {v: k for k, v in _lib.STRANDS.items()}[code]
+        return StrandScanResult(stride=int(stride), win_offsets=win_off, starts=starts, lens=lens, kept=kept.astype(bool),
+                                scores=scores, bin_offsets=bin_off, track=track, cover=cover, contig_scores=contig_scores,
+                                strand=name, scores_fwd=fwd, scores_rev=rev)
 
     def classify_contigs_spans(self, seq_ptr: int, offsets: np.ndarray, single_window: bool = False,
                                precision=_lib.DEFAULT_PRECISION):

@@ -68,6 +68,9 @@ class Outputs:
         # written only when GENOMAD_AMD_SCAN_STRIDE is set (score tracks along the contigs; no counterpart in the reference)
         self.nn_scan_output = d / f"{p}_nn_scan.npz"
         self.provirus_nn_scan_output = d / f"{p}_provirus_nn_scan.npz"
+        # written only when GENOMAD_AMD_STRAND is reverse or both (each strand's contig scores; no counterpart in the reference)
+        self.nn_strand_output = d / f"{p}_nn_strand.npz"
+        self.provirus_nn_strand_output = d / f"{p}_provirus_nn_strand.npz"
         f = o / f"{p}_find_proviruses"
         self.find_proviruses_execution_info = f / f"{p}_find_proviruses.json"
         self.find_proviruses_output = f / f"{p}_provirus.tsv"
@@ -392,6 +395,55 @@ def _scan_file_has_stride(path, stride) -> bool:
         return False
 
 
+def strand_contigs_safely(eng, seq, offsets, strand, single_window, precision, embed=False, console=None):
+    """NNEngine.classify_contigs_strand, asking for each strand's own scores, with the range fallback of :func:`_range_fallback`:
+    a non-finite score on EITHER strand sends the piece to the next arithmetic.  (scores, embeddings or None, ids, forward, reverse)."""
+    def run(a):
+        pr, wid, emb, fwd, rev = eng.classify_contigs_strand(seq, offsets, strand, single_window, a, embed)
+        return np.stack([pr, fwd, rev]), (pr, emb, wid, fwd, rev)
+    _, out, _ = _with_range_fallback(run, precision, console)
+    return out
+
+
+def scan_contigs_strand_safely(eng, seq, offsets, stride, strand, single_window, precision, console=None):
+    """NNEngine.scan_contigs_strand with the range fallback: a non-finite window score on either strand scans the piece again."""
+    def run(a):
+        res = eng.scan_contigs_strand(seq, offsets, stride, strand, single_window, a)
+        return np.stack([res.scores, res.scores_fwd, res.scores_rev]), res
+    _, res, _ = _with_range_fallback(run, precision, console)
+    return res
+
+
+def strand_requested() -> str:
+    """GENOMAD_AMD_STRAND=forward|reverse|both: which strand of every window main() scores (``both``: the f32 mean of the two);
+    unset, empty or ``forward``: nothing changes.  Any other value is an error."""
+    v = os.environ.get("GENOMAD_AMD_STRAND", "").strip()
+    if not v:
+        return "forward"
+    if v not in sequence.STRANDS:
+        raise ValueError(f"GENOMAD_AMD_STRAND={v!r}: expected one of forward, reverse, both (the strand of every window that is scored)")
+    return v
+
+
+def _strand_of_file(path) -> str:
+    """The mode a stage's outputs were computed under: what its strand file says; no file = forward."""
+    if not Path(path).exists():
+        return "forward"
+    try:
+        return str(np.load(path)["strand"])
+    except Exception:  # noqa: BLE001  (unreadable: no mode matches, the stage runs again)
+        return "?"
+
+
+def _npz_strand(path) -> str:
+    """The mode an embeddings or scan file was computed under: its ``strand`` entry, which only reverse / both write."""
+    try:
+        z = np.load(path)
+        return str(z["strand"]) if "strand" in z.files else "forward"
+    except Exception:  # noqa: BLE001  (missing or unreadable: no mode matches)
+        return "?"
+
+
 # ---- runtime parity sentinel (VERDICT r04 item 4) ---------------------------------------------------------------------
 # The 1e-4 claim of the production arithmetic has only ever met synthetic weights (the trained nn_classifier.h5 is not in the
 # checkout).  So every run of main() classifies its first windows a second time with the exact-f32 device path (GNN_PREC_F32:
@@ -512,6 +564,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     configured_precision()    # a mistyped GENOMAD_AMD_PRECISION stops here
     embeddings = embeddings_requested()
     scan_stride = scan_stride_requested()
+    strand = strand_requested()
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -537,6 +590,11 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     if scan_stride is not None and not device_front_end:
         console.error("GENOMAD_AMD_SCAN_STRIDE needs the device front end: the host front end (GENOMAD_AMD_FRONT_END=host) does "
                       "not scan contigs. Unset GENOMAD_AMD_FRONT_END or GENOMAD_AMD_SCAN_STRIDE.")
+        sys.exit(1)
+
+    if strand != "forward" and not device_front_end:
+        console.error("GENOMAD_AMD_STRAND needs the device front end: the host front end (GENOMAD_AMD_FRONT_END=host) does "
+                      "not cut reverse-complement windows. Unset GENOMAD_AMD_FRONT_END or GENOMAD_AMD_STRAND.")
         sys.exit(1)
 
     def everywhere(*flags):
@@ -660,7 +718,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         if rank0:
             write_tsv(tsv_path, names, predictions)                                  # :340-352 (always rewritten)
 
-    def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, emb_path=None, scan_path=None):
+    def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, strand_path, emb_path=None, scan_path=None):
         """Product path: the contig front end (NNEngine.classify_contigs) does windowing, the N rule,
         tokenising, classification and the per-contig mean on the GPU, so encoding and classification
         are one step; ``<prefix>_seq_window_id.npz`` is still written.  With several ranks the CONTIGS are
@@ -670,9 +728,15 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         results are bit-identical for any number of ranks.  ``emb_path`` (GENOMAD_AMD_EMBEDDINGS=1): the per-contig encoder
         embeddings are computed in the same pass and written there; a run that finds the scores but not that file classifies again.
         ``scan_path`` (GENOMAD_AMD_SCAN_STRIDE): every piece is also scanned at that stride (NNEngine.scan_contigs) and the score
-        tracks are written there; a run that finds the scores but no scan file of that stride runs the stage again."""
-        (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and (emb_path is None or emb_path.exists())
-                                 and (scan_path is None or _scan_file_has_stride(scan_path, scan_stride)))   # :284-292
+        tracks are written there; a run that finds the scores but no scan file of that stride runs the stage again.
+        ``strand_path`` (GENOMAD_AMD_STRAND): under ``reverse`` or ``both`` every score, embedding and track carries that mode and each
+        strand's contig scores are written there; the file also says which mode the stage's outputs were computed under (absent:
+        forward), and a run that asks for another mode runs the stage again.  Embeddings and scan files of reverse / both carry the
+        mode as well, so one left behind by an earlier run is not taken for another mode's."""
+        (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and _strand_of_file(strand_path) == strand
+                                 and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
+                                 and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
+                                                            and _npz_strand(scan_path) == strand)))   # :284-292
         names = predictions = None
         if have_npz:
             gate()
@@ -686,22 +750,28 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             eng = _engine()
             size = Path(fasta).stat().st_size * (1 if sequence.compression_of(fasta) == "uncompressed" else 4)
             precision = select_arithmetic(eng, precision, size, comm, console)
-            parts, emb_parts, scan_parts = [], [], []
+            parts, emb_parts, scan_parts, strand_parts = [], [], [], []
             sentinel = {"d": None, "done": False}
 
             def classify(key, nm, sq, off):
-                pr, emb, wid = classify_piece(sq, off)
+                pr, emb, wid = classify_piece(key, sq, off)
                 parts.append((key, nm, pr, wid))
                 emb_parts.append((key, emb))
-                if scan_path is not None:       # after the normal classification, with the arithmetic the run selected
+                if scan_path is not None and strand == "forward":       # after the normal classification, with the arithmetic the run selected
                     scan_parts.append((key, scan_contigs_safely(eng, sq, off, scan_stride, single_window, precision, console)))
+                elif scan_path is not None:
+                    scan_parts.append((key, scan_contigs_strand_safely(eng, sq, off, scan_stride, strand, single_window, precision, console)))
 
-            def classify_piece(sq, off):
+            def classify_piece(key, sq, off):
                 if not sentinel["done"] and len(off) > 1:           # this rank's first piece with a contig: the run's parity sample
                     sentinel["done"] = True
                     sentinel["d"] = parity_sentinel(eng, sentinel_windows(sq, off, single_window), precision, console)
                     if comm is None:                                # one rank: a failed check stops the run here, not after the whole
                         sentinel_verdict(None, sentinel["d"], console, precision)       # file (several ranks leave together below)
+                if strand != "forward":
+                    pr, emb, wid, fwd, rev = strand_contigs_safely(eng, sq, off, strand, single_window, precision, emb_path is not None, console)
+                    strand_parts.append((key, fwd, rev))
+                    return pr, emb, wid
                 if emb_path is not None:
                     return embed_contigs_safely(eng, sq, off, single_window, precision, console)
                 pr, wid = classify_contigs_safely(eng, sq, off, single_window, precision, console)
@@ -743,7 +813,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             sentinel_verdict(comm, sentinel["d"], console, precision)      # before anything is written
             names, predictions, ids, n_windows = sharding.gather_contig_parts(comm, parts)
             embeddings_all = sharding.gather_contig_embeddings(comm, emb_parts) if emb_path is not None else None
-            scans_all = sharding.gather_contig_scans(comm, scan_parts) if scan_path is not None else None
+            strand_fields = sharding.SCAN_STRAND_FIELDS if strand != "forward" else ()
+            scans_all = sharding.gather_contig_scans(comm, scan_parts, extra_window_fields=strand_fields) if scan_path is not None else None
+            strands_all = sharding.gather_contig_strand_scores(comm, strand_parts) if strand != "forward" else None
             gate()
             if not n_windows:                                                        # :297-299
                 console.error("No sequences were found. Please check your input FASTA.")
@@ -756,15 +828,26 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                 console.log(f"{what.capitalize()}s classified ({len(ids)} windows).")
                 np.savez_compressed(npz_path, **{names_key: names, "predictions": predictions})
                 if emb_path is not None:
-                    np.savez_compressed(emb_path, **{names_key: names, "embeddings": embeddings_all})
+                    np.savez_compressed(emb_path, **{names_key: names, "embeddings": embeddings_all,
+                                                     **({"strand": np.array(strand)} if strand != "forward" else {})})
                     console.log(f"Encoder embeddings of the {what}s written to {emb_path.name}.")
                 if scan_path is not None:
                     sc = scans_all
                     np.savez_compressed(scan_path, **{names_key: names, "stride": np.int64(scan_stride), "win_offsets": sc["win_offsets"],
                                                       "window_start": sc["starts"], "window_len": sc["lens"], "window_kept": sc["kept"],
                                                       "window_scores": sc["scores"], "bin_offsets": sc["bin_offsets"],
-                                                      "track": sc["track"], "cover": sc["cover"]})
+                                                      "track": sc["track"], "cover": sc["cover"],
+                                                      **({"strand": np.array(strand), "window_scores_fwd": sc["scores_fwd"],
+                                                          "window_scores_rev": sc["scores_rev"]} if strand != "forward" else {})})
                     console.log(f"Score tracks of the {what}s (stride {scan_stride}, {len(sc['starts'])} windows) written to {scan_path.name}.")
+                if strand != "forward":
+                    fwd, rev = strands_all
+                    np.savez_compressed(strand_path, **{names_key: names, "strand": np.array(strand), "scores_fwd": fwd, "scores_rev": rev,
+                                                        "max_abs_diff": np.abs(fwd - rev).max(axis=1) if len(fwd) else np.zeros(0, np.float32)})
+                    console.log(f"Strand mode {strand}: forward and reverse scores of the {what}s written to {strand_path.name} "
+                                f"(largest per-{what} |forward - reverse| {float(np.abs(fwd - rev).max()) if len(fwd) else 0.0:.4f}).")
+                elif strand_path.exists():          # these outputs are forward ones again: the file that said otherwise goes
+                    strand_path.unlink()
         if cleanup and rank0 and enc_dir.is_dir():
             console.log(f"Deleting encoded {what} data.")
             shutil.rmtree(enc_dir)
@@ -774,14 +857,16 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     run = stage_device if device_front_end else stage
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
     scan_kw = (lambda path: {"scan_path": path}) if scan_stride is not None else (lambda path: {})
+    strand_kw = (lambda path: {"strand_path": path}) if device_front_end else (lambda path: {})
     try:
         run(input_path, outputs.encoded_sequences_dir, outputs.seq_window_id_output,
             outputs.nn_classification_npz_output, outputs.nn_classification_output,
-            "contig_names", "contig_ids", "sequence", **emb_kw(outputs.nn_embeddings_output), **scan_kw(outputs.nn_scan_output))
+            "contig_names", "contig_ids", "sequence", **strand_kw(outputs.nn_strand_output), **emb_kw(outputs.nn_embeddings_output),
+            **scan_kw(outputs.nn_scan_output))
         if classify_proviruses:                                                      # :248-281, :355-425
             run(outputs.find_proviruses_nucleotide_output, outputs.encoded_proviruses_dir,
                 outputs.provirus_window_id_output, outputs.provirus_nn_classification_npz_output,
-                outputs.provirus_nn_classification_output, "provirus_names", "provirus_ids", "provirus",
+                outputs.provirus_nn_classification_output, "provirus_names", "provirus_ids", "provirus", **strand_kw(outputs.provirus_nn_strand_output),
                 **emb_kw(outputs.provirus_nn_embeddings_output), **scan_kw(outputs.provirus_nn_scan_output))
     finally:
         if check_pool is not None:

@@ -430,6 +430,30 @@ def materialize_spans(seq: np.ndarray, starts, lens) -> np.ndarray:
     return out
 
 
+STRANDS = ("forward", "reverse", "both")              # gnn_strand: GNN_STRAND_FORWARD = 0, _REVERSE = 1, _BOTH = 2
+_COMPLEMENT = np.arange(256, dtype=np.uint8)
+_COMPLEMENT[[ord(c) for c in "ACGT"]] = [ord(c) for c in "TGCA"]
+
+
+def revcomp_spans(seq: np.ndarray, starts, lens) -> np.ndarray:
+    """(n, 6000) uint8: the REVERSE windows of the spans seq[start : start + len] (``gnn_revcomp_spans_dev``, in numpy):
+    out[i] = comp(upper(seq[start + len - 1 - i])) for i < len and 'N' for len <= i < 6000 - right-padded like the forward window
+    of :func:`materialize_spans`; the pad is not reversed to the front.  comp: A <-> T, C <-> G, every other byte unchanged.  The
+    tokenizer maps any non-ACGT byte to token 0 on either strand, so an IUPAC-exact complement table would change no score."""
+    fwd = materialize_spans(seq, starts, lens)
+    out = np.full_like(fwd, ord("N"))
+    for i, l in enumerate(lens):
+        out[i, :int(l)] = _COMPLEMENT[fwd[i, :int(l)][::-1]]
+    return out
+
+
+def strand_mean(f, r) -> np.ndarray:
+    """The window score under strand mode ``both``: (f + r) * 0.5 per class in float32 - one float32 addition (the only rounding)
+    and an exact halving, what the device's split kernel computes."""
+    f, r = np.asarray(f, dtype=np.float32), np.asarray(r, dtype=np.float32)
+    return (f + r) * np.float32(0.5)
+
+
 def scan_track(scores, kept, lens, win_offsets, bin_offsets, stride: int):
     """The track of a scan, spelled out (the definition ``gnn_scan_contigs`` folds on the device; readable, not fast): bin b of a
     contig is [b * stride, (b + 1) * stride); window k covers it iff k <= b and b * stride < k * stride + lens[k].  track[b] = the

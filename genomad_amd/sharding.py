@@ -193,18 +193,38 @@ SCAN_WINDOW_FIELDS = ("starts", "lens", "kept", "scores")      # per window; CSR
 SCAN_BIN_FIELDS = ("track", "cover")                           # per bin; CSR over contigs by bin_offsets
 
 
-def gather_contig_scans(comm, parts, root: int = 0):
+def gather_contig_strand_scores(comm, parts, root: int = 0):
+    """Each strand's own per-contig scores of contig-sharded pieces -> ``root``, in the piece order of :func:`gather_contig_parts`.
+    ``parts`` = this rank's list of (order_key, forward (k, 3) float32, reverse (k, 3) float32), the arrays
+    ``NNEngine.classify_contigs_strand`` returns beside the mode's scores.  They travel as one (k, 6) row table through
+    :func:`gather_contig_embeddings` - moved, never recomputed, so the same bits for any number of ranks.  Returns (forward, reverse),
+    each (n_contigs, 3) float32, on ``root``; None elsewhere."""
+    rows = [(key, np.concatenate([np.asarray(f, np.float32).reshape(-1, 3), np.asarray(r, np.float32).reshape(-1, 3)], axis=1))
+            for key, f, r in parts]
+    got = gather_contig_embeddings(comm, rows, width=6, root=root)
+    if got is None:
+        return None
+    return np.ascontiguousarray(got[:, :3]), np.ascontiguousarray(got[:, 3:])
+
+
+SCAN_STRAND_FIELDS = ("scores_fwd", "scores_rev")              # per window, of a scan with a strand mode (StrandScanResult)
+
+
+def gather_contig_scans(comm, parts, root: int = 0, extra_window_fields=()):
     """Score tracks of contig-sharded pieces -> ``root``, in the piece order of :func:`gather_contig_parts`.  ``parts`` = this rank's
     list of (order_key, scan) with the same keys and contig counts as the pieces handed to gather_contig_parts; ``scan`` = the
     arrays of one ``NNEngine.scan_contigs`` call (win_offsets, starts, lens, kept, scores, bin_offsets, track, cover; an object with
     ``asdict()`` or a dict).  Window and bin counts differ from rank to rank, so each rank's pieces travel as one byte string
     (:func:`gather_bytes`).  ``root`` concatenates the pieces and rebases the two CSR offset arrays; the values are only moved, so
-    the result is bit-identical for any number of ranks.  Returns a dict of those eight arrays on ``root``, None elsewhere."""
+    the result is bit-identical for any number of ranks.  Returns a dict of those eight arrays on ``root``, None elsewhere.
+    ``extra_window_fields`` (SCAN_STRAND_FIELDS for the scans of ``NNEngine.scan_contigs_strand``): further (n_windows, 3) float32
+    arrays of every scan, gathered and returned the same way."""
     comm = comm or LocalComm()
+    window_fields = SCAN_WINDOW_FIELDS + tuple(extra_window_fields)
     arrays = {"keys": np.array([int(key) for key, _ in parts], dtype="<i8")}
     for i, (_, scan) in enumerate(parts):
         scan = scan.asdict() if hasattr(scan, "asdict") else scan
-        for f in ("win_offsets", "bin_offsets") + SCAN_WINDOW_FIELDS + SCAN_BIN_FIELDS:
+        for f in ("win_offsets", "bin_offsets") + window_fields + SCAN_BIN_FIELDS:
             arrays[f"{i}_{f}"] = np.ascontiguousarray(scan[f])
     buf = io.BytesIO()
     np.savez(buf, **arrays)
@@ -220,16 +240,17 @@ def gather_contig_scans(comm, parts, root: int = 0):
         raise ValueError("duplicate piece keys in gather_contig_scans")
     pieces.sort(key=lambda p: p[0])
     out = {"win_offsets": [np.zeros(1, np.int64)], "bin_offsets": [np.zeros(1, np.int64)]}
-    out.update({f: [] for f in SCAN_WINDOW_FIELDS + SCAN_BIN_FIELDS})
+    out.update({f: [] for f in window_fields + SCAN_BIN_FIELDS})
     w0 = b0 = 0
     for _, d in pieces:
         out["win_offsets"].append(d["win_offsets"][1:].astype(np.int64) + w0)
         out["bin_offsets"].append(d["bin_offsets"][1:].astype(np.int64) + b0)
         w0, b0 = w0 + int(d["win_offsets"][-1]), b0 + int(d["bin_offsets"][-1])
-        for f in SCAN_WINDOW_FIELDS + SCAN_BIN_FIELDS:
+        for f in window_fields + SCAN_BIN_FIELDS:
             out[f].append(d[f])
     empty = {"starts": np.zeros(0, np.int64), "lens": np.zeros(0, np.int32), "kept": np.zeros(0, bool),
              "scores": np.zeros((0, 3), np.float32), "track": np.zeros((0, 3), np.float32), "cover": np.zeros(0, np.int32)}
+    empty.update({f: np.zeros((0, 3), np.float32) for f in extra_window_fields})
     return {f: np.concatenate(v) if v else empty[f] for f, v in out.items()}
 
 

@@ -307,6 +307,51 @@ int gnn_scan_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t 
                      uint8_t* window_kept_host_or_null, int64_t windows_capacity, float* track_host_or_null,
                      int32_t* cover_host_or_null, int64_t bins_capacity, float* contig_scores_host_or_null);
 
+/* ---- both strands: reverse-complement windows on the device ("Both strands") ------------------------------------------
+ * The classifier is not strand-symmetric (causal convolutions, window-relative patch positions): a window and its reverse
+ * complement are two inputs, and which strand a contig was written on is arbitrary.  These entry points score either strand, or
+ * both and their mean, with the forward pass of gnn_classify.
+ *   complement   of an upper-cased byte: A <-> T, C <-> G, every other byte unchanged.  The tokenizer maps any non-ACGT byte to
+ *                token 0 on either strand, so an IUPAC-exact table would change no score.
+ *   reverse      window of a span (start, len <= 6000) of the packed buffer: out[i] = comp(upper(seq[start + len - 1 - i])) for
+ *                i < len and 'N' for len <= i < 6000 - right-padded like the forward window; the pad is NOT reversed to the front.
+ *   windows      spans, window ids, bins and the kept mask are the FORWARD ones: the reverse complement is taken per window, not per
+ *                contig (a reverse-complemented contig would be cut into other windows).  The N rule counts literal 'N' once on the
+ *                raw forward span - N maps to N, so the count is that of the reverse window too.  window ids, kept, the CSR offsets
+ *                and cover therefore do not depend on the strand, and every output aligns element by element.
+ *   modes        gnn_strand.  Window score under GNN_STRAND_BOTH: (f + r) * 0.5f per class in f32 - one rounding.
+ *   contig       the masked mean of gnn_classify_contigs over the kept windows' scores OF THE MODE: under BOTH the mean of the
+ *                combined window scores, not the half-sum of the two contig means.  Track: the fold of gnn_scan_contigs over them.
+ *   embedding    per strand the slab fold of gnn_classify_contigs_embed into its own f32 sum: REVERSE = sum_r / kept, BOTH =
+ *                (sum_f + sum_r) / (2 kept) - two independent sums, so independent of gnn_set_chunk; zero row without a kept window.
+ * GNN_STRAND_FORWARD is bit-identical to the entry points without a strand.  A strand is computed when the mode needs it or one of
+ * its own output buffers is given (REVERSE with contig_scores_fwd_host: both strands run, the mode's outputs are the reverse ones).
+ * When both run, a slab's forward and reverse windows go through the front end as one batch, forward windows first; the front
+ * ends are batch-invariant, so no score depends on it.  A strand outside the enum: GNN_ERR_ARG, the message names the value.
+ * Device memory, persistent in the ctx and grow-only: 24 B per window (reverse and combined scores), 12 B per window of one slab,
+ * 24 B per contig, and a second embedding sum (2 KB per contig) when an embedding is asked for under REVERSE or BOTH. */
+typedef enum gnn_strand { GNN_STRAND_FORWARD = 0, GNN_STRAND_REVERSE = 1, GNN_STRAND_BOTH = 2 } gnn_strand;
+/* The building block and the window-level route: bases_dev_out[n_spans][6000] = the reverse windows of the spans (start, len) of
+ * seq_dev, ready for gnn_classify_dev / gnn_embed_dev.  bases_dev_out: device pointer, 4-byte aligned.  Spans as
+ * gnn_classify_spans (host arrays, lengths in [0, 6000]).  Returns when the windows are written. */
+int gnn_revcomp_spans_dev(gnn_ctx* ctx, const uint8_t* seq_dev, const int64_t* starts_host, const int32_t* lens_host, int64_t n_spans,
+                          uint8_t* bases_dev_out);
+/* gnn_classify_contigs_embed with a strand: contig_scores_host, and contig_emb_host_or_null (may be NULL: no embedding is computed;
+ * with it GNN_PREC_F16C6 is GNN_ERR_ARG) carry the mode; window ids as gnn_classify_contigs.  contig_scores_fwd_host_or_null /
+ * contig_scores_rev_host_or_null [n_contigs][3]: each strand's own masked mean. */
+int gnn_classify_contigs_strand(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes, const int64_t* offsets_host,
+                                int64_t n_contigs, int single_window, int precision, float* contig_scores_host,
+                                int64_t* window_ids_host, int64_t ids_capacity, int64_t* n_windows_out, float* contig_emb_host_or_null,
+                                int strand, float* contig_scores_fwd_host_or_null, float* contig_scores_rev_host_or_null);
+/* gnn_scan_contigs with a strand: window_scores_host, track_host, contig_scores_host carry the mode; kept and cover are those of
+ * gnn_scan_contigs.  window_scores_fwd_host_or_null / window_scores_rev_host_or_null [n_windows][3] (capacity windows_capacity):
+ * each strand's own window scores. */
+int gnn_scan_contigs_strand(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes, const int64_t* offsets_host,
+                            int64_t n_contigs, int stride, int single_window, int precision, float* window_scores_host,
+                            uint8_t* window_kept_host_or_null, int64_t windows_capacity, float* track_host_or_null,
+                            int32_t* cover_host_or_null, int64_t bins_capacity, float* contig_scores_host_or_null, int strand,
+                            float* window_scores_fwd_host_or_null, float* window_scores_rev_host_or_null);
+
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
  * in-memory text buffer (already decompressed, newlines normalised to '\n').
