@@ -108,19 +108,23 @@ def oracle16(synth_weights):
     return bases, scores, taps
 
 
+# per-stage tolerances of the unfused f32 kernels against the fp64 oracle (absolute; also used by tests/test_window_lengths_gpu.py)
+F32_CHECKS = [("x1", "x1", 2e-6), ("x2", "x2", 2e-5), ("x3", "x3", 5e-5), ("m_a", "mA", 2e-5),
+              ("m_b", "mB", 1e-4), ("yp_a", "ypA", 2e-5), ("yp_b", "ypB", 1e-4),
+              ("alpha_a", "alphaA", 1e-6), ("alpha_b", "alphaB", 2e-5), ("feat", "f", 1e-4)]
+F32_SCORE_TOL = 2e-5
+
+
 def test_f32_path_intermediates(engine, oracle16):
     """Per-stage parity of the unfused f32 kernels against the fp64 oracle."""
     bases, scores64, t64 = oracle16
     n = 4
     scores, taps = engine.debug_forward(bases[:n], "f32", taps=("x1", "x2", "x3", "m_a", "m_b", "yp_a",
                                                                "yp_b", "alpha_a", "alpha_b", "feat"))
-    checks = [("x1", "x1", 2e-6), ("x2", "x2", 2e-5), ("x3", "x3", 5e-5), ("m_a", "mA", 2e-5),
-              ("m_b", "mB", 1e-4), ("yp_a", "ypA", 2e-5), ("yp_b", "ypB", 1e-4),
-              ("alpha_a", "alphaA", 1e-6), ("alpha_b", "alphaB", 2e-5), ("feat", "f", 1e-4)]
-    for mine, ref, tol in checks:
+    for mine, ref, tol in F32_CHECKS:
         err = np.abs(taps[mine] - t64[ref][:n]).max()
         assert err <= tol, f"{mine}: max abs err {err:.3e} > {tol}"
-    assert np.abs(scores - scores64[:n]).max() <= 2e-5
+    assert np.abs(scores - scores64[:n]).max() <= F32_SCORE_TOL
 
 
 def test_f32_path_scores_vs_golden(engine, golden_dir):
@@ -178,16 +182,21 @@ from genomad_amd._lib import DEFAULT_PRECISION  # noqa: E402
 CONTIG_PRECS = [DEFAULT_PRECISION, "f16x3tk", "bf16x3"]
 
 
+# per-stage tolerances of the fused kernels against the fp64 oracle (bf16x3's; also used by tests/test_window_lengths_gpu.py) and the
+# factor per arithmetic: 4-bit correction terms / 11+11-bit limbs vs bf16's 8+8
+FUSED_CHECKS = [("m_a", "mA", 1e-4), ("m_b", "mB", 1e-3), ("yp_a", "ypA", 1e-4), ("yp_b", "ypB", 1e-3),
+                ("alpha_a", "alphaA", 1e-5), ("alpha_b", "alphaB", 2e-4), ("feat", "f", 5e-4)]
+FUSED_LOOSE = {"f16c6": 2.5, "f16x3": 0.25, "f16x3tc": 0.25, "f16x3tk": 0.25}
+
+
 @pytest.mark.parametrize("prec", FUSED)
 def test_fused_intermediates(engine, oracle16, prec, request):
     """Fused kernels (activations in LDS, low-precision MFMA operands) against the fp64 oracle, per stage."""
     need_tables(request, prec)
     bases, scores64, t64 = oracle16
     scores, taps = engine.debug_forward(bases, prec)
-    loose = {"f16c6": 2.5, "f16x3": 0.25, "f16x3tc": 0.25, "f16x3tk": 0.25}.get(prec, 1.0)   # 4-bit correction terms / 11+11-bit limbs vs bf16's 8+8
-    checks = [("m_a", "mA", 1e-4), ("m_b", "mB", 1e-3), ("yp_a", "ypA", 1e-4), ("yp_b", "ypB", 1e-3),
-              ("alpha_a", "alphaA", 1e-5), ("alpha_b", "alphaB", 2e-4), ("feat", "f", 5e-4)]
-    for mine, ref, tol in checks:
+    loose = FUSED_LOOSE.get(prec, 1.0)
+    for mine, ref, tol in FUSED_CHECKS:
         err = np.abs(taps[mine] - t64[ref]).max()
         assert err <= tol * loose, f"{prec} {mine}: max abs err {err:.3e} > {tol * loose}"
     assert np.abs(scores - scores64).max() <= SCORE_TOL
@@ -911,17 +920,20 @@ def test_second_weight_set_and_engine(synth_weights):
 
 @pytest.mark.parametrize("prec", ["f16c6", "f16x3", "f16x3tc", "f16x3tk", "bf16x3"])
 def test_padding_skip_is_bit_identical(engine, prec, request):
-    """The streaming kernels (f16c6; f16x3 / bf16x3 of gnn_fused_x3.hip) copy the yp rows and pair products of a window's all-N tail from an all-N window instead of
+    """All four streaming kernels (f16c6 of gnn_fused_c6.hip; f16x3 / bf16x3 of gnn_fused_x3.hip; f16x3tc of gnn_fused_tc.hip; f16x3tk of
+    gnn_fused_tk.hip) copy the yp rows and pair products of a window's all-N tail from an all-N window instead of
     computing them (the padding of a contig's last window, nn_classification.py:72).  With the skip switched off the
     scores AND the intermediates must be the same bits: windows of every length class (empty, shorter than a step,
-    ending exactly on / one base around a step boundary, N runs inside, IUPAC codes and lower case in the tail, full)."""
+    ending exactly on / one base around a step boundary, on both sides of a change of the step count - L = k FT - 15 | L + 1, for the
+    96-row steps of tc / tk and the 128-row steps of x3 / c6, up to where the copy disappears -, N runs inside, IUPAC codes and lower
+    case in the tail, full).  Every length: tests/test_window_lengths_gpu.py."""
     need_tables(request, prec)
     from genomad_amd import _lib
     rng = np.random.default_rng(11)
     def win(n, tail=b"N"):
         body = bytes(rng.choice(list(b"ACGT"), n).tolist())
         return (body + tail * 6000)[:6000]
-    lens = [0, 1, 3, 100, 112, 113, 114, 127, 128, 129, 2500, 2559, 2560, 2561, 4000, 5984, 5996, 5997, 6000]
+    lens = [0, 1, 3, 81, 82, 100, 112, 113, 114, 127, 128, 129, 177, 178, 2500, 2559, 2560, 2561, 4000, 5873, 5874, 5937, 5938, 5984, 5996, 5997, 6000]
     wins = [win(n) for n in lens]
     wins.append(win(3000, b"n"))                      # lower-case n: not ACGT either
     wins.append(win(3000, b"R"))                      # IUPAC code
