@@ -108,6 +108,9 @@ SIGNATURES = {
                                            _vp]),
     "gnn_scan_contigs_strand": (_int, [_vp, _vp, _int, _i64, _vp, _i64, _int, _int, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _int, _vp,
                                        _vp]),
+    "gnn_occlusion_plan": (_int, [_vp, _i64, _int, _int, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _vp, _vp]),
+    "gnn_occlude_spans_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gnn_occlude_contigs": (_int, [_vp, _vp, _int, _i64, _vp, _i64, _int, _int, _int, _vp, _vp, _i64, _vp, _i64, _vp]),
     "gnn_embed": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_embed_dev": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_debug_forward": (_int, [_vp, _vp, _i64, _int, _vp, C.POINTER(Taps)]),

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -122,7 +123,79 @@ struct Workspace {
     DevBuf<float> feat;         // (chunk, 256)
 };
 
-struct ContigWorkspace;
+// ---- the contig front end's window rule and persistent buffers (gnn_contigs.hip, gnn_occlude.hip) ----
+constexpr int MIN_TAIL = 2500;        // nn_classification.py:68  seq_windows(seq, 6000, 2500, ...)
+constexpr int MAX_N = 4000;           // nn_classification.py:70  window_n > 0 and count("N") > 4000 -> skip
+constexpr int64_t PIECE = 64ll << 20; // bytes per host->device piece of the sequence buffer
+
+struct ContigWorkspace {
+    hipStream_t copy_stream = nullptr;
+    std::vector<hipEvent_t> piece_done;
+    // host side of the span table
+    std::vector<int64_t> starts, ids;
+    std::vector<int32_t> lens, window_n, counts;
+    // device side
+    DevBuf<uint8_t> seq;
+    DevBuf<int64_t> d_starts, d_ids;             // the span table: one element per candidate window ...
+    DevBuf<int32_t> d_lens, d_window_n, d_counts;
+    DevBuf<float> d_scores;                      // ... and GNN_CLASSES per window
+    DevBuf<uint8_t> d_bases;
+    DevBuf<float> d_out;
+    // gnn_classify_contigs_embed: one slab's window embeddings (f32) and the per-contig running sums / kept-window counts
+    DevBuf<float> d_emb, d_emb_sum;
+    DevBuf<int32_t> d_emb_kept;
+    // gnn_scan_contigs: CSR offsets of every contig's windows and bins, the track (3 f32 per bin) and its cover counts
+    std::vector<int64_t> win_off, bin_off;
+    DevBuf<int64_t> d_win_off, d_bin_off;
+    DevBuf<float> d_track;
+    DevBuf<int32_t> d_cover;
+    // the *_strand entry points: the reverse windows' and the combined (`both`) scores, GNN_CLASSES per window each; the scores of
+    // one slab's batch [forward | reverse] before the split; the per-contig means of each strand ([forward | reverse] rows); the
+    // reverse strand's own embedding sums and kept-window counts
+    DevBuf<float> d_scores_rev, d_scores_mix, d_slab_scores, d_out_strand;
+    DevBuf<float> d_emb_sum_rev;
+    DevBuf<int32_t> d_emb_kept_rev;
+    // gnn_occlude_contigs (gnn_occlude.hip): CSR offsets of every window's blocks, and ONE slab's occluded scores (12 B per pair; the
+    // deltas replace them in place) - nothing here grows with the number of pairs of a call
+    std::vector<int64_t> blk_off;
+    DevBuf<int64_t> d_blk_off;
+    DevBuf<float> d_occ;
+
+    // What the buffer groups hold, in windows / contigs + 1 / bins.  The head-room is counted in elements, so a buffer with
+    // several elements per window or bin holds fewer of them than its neighbours: the smallest member decides.
+    size_t span_cap() const {
+        return std::min({d_starts.capacity(), d_ids.capacity(), d_lens.capacity(), d_window_n.capacity(), d_counts.capacity(),
+                         d_scores.capacity() / GNN_CLASSES});
+    }
+    size_t strand_cap() const { return std::min(d_scores_rev.capacity(), d_scores_mix.capacity()) / GNN_CLASSES; }
+    size_t off_cap() const { return std::min(d_win_off.capacity(), d_bin_off.capacity()); }
+    size_t bin_cap() const { return std::min(d_track.capacity() / GNN_CLASSES, d_cover.capacity()); }
+};
+
+// The window rule, once: seq_windows(seq, 6000, 2500, max_windows) of the reference (sequence.py:150-167) with the window start
+// advancing by `stride` instead of 6000.  Window 0 always exists; window k > 0 exists while no earlier window reached the contig's
+// end and its own length is at least MIN_TAIL.  f(k, length).  At stride == W this is the loop gnn_classify_contigs always ran.
+template <typename F>
+static inline void for_each_window(int64_t len, int64_t stride, int single_window, F&& f) {
+    for (int64_t k = 0; k * stride < len; ++k) {
+        const int64_t l = std::min<int64_t>(W, len - k * stride);
+        if (l < MIN_TAIL && k > 0) break;             // a short tail is dropped, a short first window kept
+        f(k, l);
+        if (l < MIN_TAIL || (single_window && k == 0) || k * stride + W >= len) break;
+    }
+}
+
+// Grow-only with some head-room (amortised).
+template <typename Tp>
+static int reserve_roomy(DevBuf<Tp>& b, size_t need) {
+    return b.reserve(need, need / 4 + 64);
+}
+
+// A group that is sized together is re-allocated as a whole: every member is emptied before the first one grows.
+template <typename... Bufs>
+static void reset_all(Bufs&... bufs) {
+    (bufs.reset(), ...);
+}
 
 struct ProfileSlot {
     double total_ms = 0.0;
@@ -231,6 +304,14 @@ int launch_materialize(gnn_ctx* ctx, const uint8_t* seq, const int64_t* starts, 
 // the same spans as reverse-complement windows (gnn_encode.hip, revcomp_kernel); bases must be 4-byte aligned, as above
 int launch_revcomp(gnn_ctx* ctx, const uint8_t* seq, const int64_t* starts, const int32_t* lens, int64_t n,
                    uint8_t* bases);
+// occluded windows (gnn_encode.hip, occlude_kernel): window i of the span table materialised with [lo, hi) set to 'N'.  By pairs
+// (blk_off != NULL): out row r is pair pair0 + r of the CSR blk_off[n_windows + 1], its window found on the device, its block
+// [j * block, (j + 1) * block).  By spans (blk_off == NULL): out row r is span r with [lo[r], hi[r]).  bases 4-byte aligned
+int launch_occlude(gnn_ctx* ctx, const uint8_t* seq, const int64_t* starts, const int32_t* lens, const int64_t* blk_off,
+                   int64_t n_windows, int64_t pair0, int block, const int32_t* lo, const int32_t* hi, int64_t n_rows, uint8_t* bases);
+// the N rule's masked mean per contig (gnn_contigs.hip, masked_segment_mean_kernel)
+int launch_masked_segment_mean(gnn_ctx* ctx, const float* scores, const int64_t* ids, const int32_t* window_n, const int32_t* counts,
+                               int64_t n, int64_t n_seg, float* out);
 int launch_front_f32(gnn_ctx* ctx, const uint8_t* bases, int64_t n);         // -> ws.mp, ws.yp (+ ws.x)
 // ws.mp, ws.yp -> scores; emb_dev != NULL: also h1 (the encoder embedding) as emb_dev[n][GNN_EMBED_DIM] of emb_dtype (gnn_emb_dtype)
 int launch_backend(gnn_ctx* ctx, int64_t n, int precision, float* scores_dev, void* emb_dev = nullptr, int emb_dtype = GNN_EMB_F32);

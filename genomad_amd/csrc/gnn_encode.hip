@@ -218,6 +218,68 @@ __global__ __launch_bounds__(256) void revcomp_kernel(const uint8_t* __restrict_
     out[g] = word;
 }
 
+// Span -> padded OCCLUDED window: the forward window of materialize_kernel with the window-relative interval [lo, hi) set to 'N'
+// ("Occlusion maps").  The scheme of materialize_kernel - 4 output bytes per thread, one dword store, a span start at any
+// alignment, no byte read where p0 + k >= len - with one workgroup row per window piece: OCC_PIECES blocks of 256 threads cover the
+// 1500 dwords of an output row, so the row, and with it everything the search below reads, is uniform over the block.
+//   by pairs  (blk_off != NULL): output row r is pair p = pair0 + r of the CSR blk_off[n_windows + 1] (blk_off[i + 1] - blk_off[i]
+//             = ceil(len_i / block) >= 1: every window has a base).  Its window i is found HERE, by bisection of blk_off - a table
+//             with one entry per window; nothing with one entry per pair is read - and its block is j = p - blk_off[i]:
+//             [j * block, (j + 1) * block).  The last block may reach past len: the pad is 'N' already.
+//   by spans  (blk_off == NULL): output row r is span r with [lo[r], hi[r]).
+// Bytes inside [lo, hi) are not read at all.
+constexpr int OCC_PIECES = (W / 4 + 255) / 256;      // 6
+
+__global__ __launch_bounds__(256) void occlude_kernel(const uint8_t* __restrict__ seq, const int64_t* __restrict__ starts,
+                                                      const int32_t* __restrict__ lens, const int64_t* __restrict__ blk_off,
+                                                      int64_t n_windows, int64_t pair0, int block, const int32_t* __restrict__ lo_of,
+                                                      const int32_t* __restrict__ hi_of, int64_t n_rows,
+                                                      uint32_t* __restrict__ out) {
+    const int64_t r = blockIdx.x / OCC_PIECES;
+    const int g = (int)(blockIdx.x % OCC_PIECES) * 256 + threadIdx.x;      // dword of the row
+    if (r >= n_rows || g >= W / 4) return;
+    int64_t wi = r;
+    int lo, hi;
+    if (blk_off) {
+        const int64_t p = pair0 + r;
+        int64_t a = 0, b = n_windows - 1;              // the window with blk_off[a] <= p < blk_off[a + 1]
+        while (a < b) {
+            const int64_t mid = (a + b) >> 1;
+            if (blk_off[mid + 1] <= p) a = mid + 1; else b = mid;
+        }
+        wi = a;
+        lo = (int)(p - blk_off[a]) * block;
+        hi = lo + block;
+    } else {
+        lo = lo_of[r];
+        hi = hi_of[r];
+    }
+    const int p0 = g * 4;
+    const uint8_t* p = seq + starts[wi];
+    const int len = lens[wi];
+    uint32_t word = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint32_t ch = 'N';
+        const int q = p0 + k;
+        if (q < len && (q < lo || q >= hi)) {
+            ch = p[q];
+            if (ch >= 'a' && ch <= 'z') ch -= 32;      // str.upper() on ASCII
+        }
+        word |= ch << (8 * k);
+    }
+    out[r * (W / 4) + g] = word;
+}
+
+int launch_occlude(gnn_ctx* ctx, const uint8_t* seq, const int64_t* starts, const int32_t* lens, const int64_t* blk_off,
+                   int64_t n_windows, int64_t pair0, int block, const int32_t* lo, const int32_t* hi, int64_t n_rows, uint8_t* bases) {
+    if (n_rows <= 0) return GNN_OK;
+    hipLaunchKernelGGL(occlude_kernel, dim3((unsigned)(n_rows * OCC_PIECES)), dim3(256), 0, ctx->stream, seq, starts, lens, blk_off,
+                       n_windows, pair0, block, lo, hi, n_rows, reinterpret_cast<uint32_t*>(bases));
+    GNN_HIP(hipGetLastError());
+    return GNN_OK;
+}
+
 int launch_revcomp(gnn_ctx* ctx, const uint8_t* seq, const int64_t* starts, const int32_t* lens, int64_t n,
                    uint8_t* bases) {
     const int64_t groups = n * (W / 4);

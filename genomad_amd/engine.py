@@ -60,6 +60,22 @@ class StrandScanResult(ScanResult):
     FIELDS = ScanResult.FIELDS + ("strand", "scores_fwd", "scores_rev")
 
 
+class OcclusionResult:
+    """What :meth:`NNEngine.occlude_contigs` returns.  Windows (CSR over contigs by ``win_offsets``): ``starts`` (contig-relative),
+    ``lens``, ``kept`` (bool: the N rule's mask), ``scores`` (n_windows, 3: the windows' ordinary scores).  Pairs (CSR over windows
+    by ``blk_offsets``, ``block`` bases each - ``sequence.occlusion_blocks``): ``delta`` (n_pairs, 3) = scores[window] - the score
+    of the window with that block set to N; positive where the block supports the class.  ``contig_scores`` (n_contigs, 3): the
+    mean of each contig's kept windows."""
+    FIELDS = ("block", "win_offsets", "starts", "lens", "kept", "scores", "blk_offsets", "delta", "contig_scores")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw[k])
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+
 class NNEngine:
     def __init__(self, device: int = 0, weights: dict = None, chunk: int = None):
         self.lib = _lib.load()
@@ -323,6 +339,63 @@ class NNEngine:
                                         track.ctypes.data, cover.ctypes.data, n_bins, contig_scores.ctypes.data))
         return ScanResult(stride=int(stride), win_offsets=win_off, starts=starts, lens=lens, kept=kept.astype(bool), scores=scores,
                           bin_offsets=bin_off, track=track, cover=cover, contig_scores=contig_scores)
+
+    # -- occlusion maps ------------------------------------------------------------------
+    def occlusion_plan(self, offsets: np.ndarray, block: int, single_window: bool = False):
+        """``gnn_occlusion_plan`` (host only): (win_offsets, contig-relative starts, lens, blk_offsets) of an occlusion map with
+        blocks of ``block`` bases - the windows of :meth:`classify_contigs` and the CSR of their (window, block) pairs."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError("offsets must hold n_contigs + 1 byte offsets")
+        n_contigs = len(offsets) - 1
+        nw, npairs = C.c_int64(), C.c_int64()
+        head = (offsets.ctypes.data, n_contigs, int(block), int(bool(single_window)), C.byref(nw), C.byref(npairs))
+        check(self.lib.gnn_occlusion_plan(*head, None, None, None, None))
+        win_off, blk_off = np.zeros(n_contigs + 1, np.int64), np.zeros(nw.value + 1, np.int64)
+        starts, lens = np.zeros(nw.value, np.int64), np.zeros(nw.value, np.int32)
+        check(self.lib.gnn_occlusion_plan(*head, win_off.ctypes.data, starts.ctypes.data, lens.ctypes.data, blk_off.ctypes.data))
+        return win_off, starts, lens, blk_off
+
+    def occlude_spans_dev(self, seq_ptr: int, starts, lens, lo, hi, bases_ptr: int):
+        """``gnn_occlude_spans_dev``: the occluded windows (``sequence.occlude_spans``) of the spans (start, len <= 6000) of a packed
+        buffer in HBM - each materialised with its window-relative interval [lo, hi) set to N - written to ``bases_ptr`` (n x 6000
+        bytes on the device, 4-byte aligned), ready for :meth:`classify_dev` / :meth:`embed_dev`.  Returns when they are written."""
+        starts = np.ascontiguousarray(starts, dtype=np.int64)
+        lens, lo, hi = (np.ascontiguousarray(a, dtype=np.int32) for a in (lens, lo, hi))
+        if starts.ndim != 1 or not (starts.shape == lens.shape == lo.shape == hi.shape):
+            raise ValueError("starts, lens, lo and hi must be 1-d arrays of one length")
+        check(self.lib.gnn_occlude_spans_dev(self.ctx, seq_ptr, starts.ctypes.data, lens.ctypes.data, lo.ctypes.data, hi.ctypes.data,
+                                             len(starts), bases_ptr))
+
+    def occlude_contigs(self, seq: np.ndarray, offsets: np.ndarray, block: int, single_window: bool = False,
+                        precision=_lib.DEFAULT_PRECISION) -> OcclusionResult:
+        """Occlusion map of every contig (``gnn_occlude_contigs``): each window of :meth:`classify_contigs` is scored as it is and
+        once per block of ``block`` bases (1 <= block <= 6000) with that block set to N, the model's own "unknown"; ``delta`` is how
+        far each class moved - which bases the score rests on.  Windows, ``kept`` and ``contig_scores`` are those of
+        classify_contigs, ``scores`` those of ``scan_contigs(stride=6000)``, every occluded score that of :meth:`classify` on the
+        same bytes (``sequence.occlude_spans``).  1 + ceil(6000 / block) forward passes per window."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        return self._occlude_contigs(seq.ctypes.data, 1, seq.nbytes, offsets, block, single_window, precision)
+
+    def occlude_contigs_dev(self, seq_ptr: int, offsets: np.ndarray, block: int, single_window: bool = False,
+                            precision=_lib.DEFAULT_PRECISION) -> OcclusionResult:
+        """Same as :meth:`occlude_contigs` for a packed contig buffer that is already resident in HBM."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        return self._occlude_contigs(seq_ptr, 0, int(offsets[-1]) if len(offsets) else 0, offsets, block, single_window, precision)
+
+    def _occlude_contigs(self, seq_ptr, on_host, seq_bytes, offsets, block, single_window, precision):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        win_off, starts, lens, blk_off = self.occlusion_plan(offsets, block, single_window)
+        n_contigs, n, n_pairs = len(offsets) - 1, len(starts), int(blk_off[-1])
+        scores = np.zeros((n, _lib.CLASSES), dtype=np.float32)
+        kept = np.zeros(n, dtype=np.uint8)
+        delta = np.zeros((n_pairs, _lib.CLASSES), dtype=np.float32)
+        contig_scores = np.zeros((n_contigs, _lib.CLASSES), dtype=np.float32)
+        check(self.lib.gnn_occlude_contigs(self.ctx, seq_ptr, int(on_host), int(seq_bytes), offsets.ctypes.data, n_contigs, int(block),
+                                           int(bool(single_window)), _lib.PRECISIONS[precision], scores.ctypes.data, kept.ctypes.data, n,
+                                           delta.ctypes.data, n_pairs, contig_scores.ctypes.data))
+        return OcclusionResult(block=int(block), win_offsets=win_off, starts=starts, lens=lens, kept=kept.astype(bool), scores=scores,
+                               blk_offsets=blk_off, delta=delta, contig_scores=contig_scores)
 
     # -- both strands --------------------------------------------------------------------
     def revcomp_spans_dev(self, seq_ptr: int, starts, lens, bases_ptr: int):

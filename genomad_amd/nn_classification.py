@@ -71,6 +71,9 @@ class Outputs:
         # written only when GENOMAD_AMD_STRAND is reverse or both (each strand's contig scores; no counterpart in the reference)
         self.nn_strand_output = d / f"{p}_nn_strand.npz"
         self.provirus_nn_strand_output = d / f"{p}_provirus_nn_strand.npz"
+        # written only when GENOMAD_AMD_OCCLUSION_BLOCK is set (occlusion maps of the contigs; no counterpart in the reference)
+        self.nn_occlusion_output = d / f"{p}_nn_occlusion.npz"
+        self.provirus_nn_occlusion_output = d / f"{p}_provirus_nn_occlusion.npz"
         f = o / f"{p}_find_proviruses"
         self.find_proviruses_execution_info = f / f"{p}_find_proviruses.json"
         self.find_proviruses_output = f / f"{p}_provirus.tsv"
@@ -395,6 +398,42 @@ def _scan_file_has_stride(path, stride) -> bool:
         return False
 
 
+def occlude_contigs_safely(eng, seq, offsets, block, single_window, precision, console=None):
+    """NNEngine.occlude_contigs with the range fallback of :func:`_range_fallback`: a piece with a non-finite window score or delta is
+    occluded again with the next arithmetic, and everything returned is that run's."""
+    def run(a):
+        res = eng.occlude_contigs(seq, offsets, block, single_window, a)
+        return np.concatenate([res.scores.reshape(-1), res.delta.reshape(-1)]), res
+    _, res, _ = _with_range_fallback(run, precision, console)
+    return res
+
+
+def occlusion_block_requested():
+    """GENOMAD_AMD_OCCLUSION_BLOCK=<int in [1, 6000]>: main() also writes the occlusion maps of the contigs (<prefix>_nn_occlusion.npz):
+    every window scored again with each block of that many bases set to N; unset or empty: nothing changes (None).  Any other value
+    is an error."""
+    v = os.environ.get("GENOMAD_AMD_OCCLUSION_BLOCK", "").strip()
+    if not v:
+        return None
+    try:
+        block = int(v)
+    except ValueError:
+        block = 0
+    if not 1 <= block <= sequence.WINDOW:
+        raise ValueError(f"GENOMAD_AMD_OCCLUSION_BLOCK={v!r}: expected an integer in [1, {sequence.WINDOW}] (bases per occluded block)")
+    return block
+
+
+def _occlusion_block_of_file(path):
+    """The block size a stage's occlusion file was computed with; no file = None (no occlusion was asked for)."""
+    if not Path(path).exists():
+        return None
+    try:
+        return int(np.load(path)["block"])
+    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
+        return -1
+
+
 def strand_contigs_safely(eng, seq, offsets, strand, single_window, precision, embed=False, console=None):
     """NNEngine.classify_contigs_strand, asking for each strand's own scores, with the range fallback of :func:`_range_fallback`:
     a non-finite score on EITHER strand sends the piece to the next arithmetic.  (scores, embeddings or None, ids, forward, reverse)."""
@@ -565,6 +604,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     embeddings = embeddings_requested()
     scan_stride = scan_stride_requested()
     strand = strand_requested()
+    occlusion_block = occlusion_block_requested()
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -595,6 +635,15 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     if strand != "forward" and not device_front_end:
         console.error("GENOMAD_AMD_STRAND needs the device front end: the host front end (GENOMAD_AMD_FRONT_END=host) does "
                       "not cut reverse-complement windows. Unset GENOMAD_AMD_FRONT_END or GENOMAD_AMD_STRAND.")
+        sys.exit(1)
+
+    if occlusion_block is not None and not device_front_end:
+        console.error("GENOMAD_AMD_OCCLUSION_BLOCK needs the device front end: the host front end (GENOMAD_AMD_FRONT_END=host) does "
+                      "not occlude windows. Unset GENOMAD_AMD_FRONT_END or GENOMAD_AMD_OCCLUSION_BLOCK.")
+        sys.exit(1)
+    if occlusion_block is not None and strand != "forward":
+        console.error(f"GENOMAD_AMD_OCCLUSION_BLOCK is forward-strand only: it cannot be combined with GENOMAD_AMD_STRAND={strand}. "
+                      "Unset GENOMAD_AMD_STRAND or GENOMAD_AMD_OCCLUSION_BLOCK.")
         sys.exit(1)
 
     def everywhere(*flags):
@@ -718,7 +767,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         if rank0:
             write_tsv(tsv_path, names, predictions)                                  # :340-352 (always rewritten)
 
-    def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, strand_path, emb_path=None, scan_path=None):
+    def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, strand_path, occ_path, emb_path=None, scan_path=None):
         """Product path: the contig front end (NNEngine.classify_contigs) does windowing, the N rule,
         tokenising, classification and the per-contig mean on the GPU, so encoding and classification
         are one step; ``<prefix>_seq_window_id.npz`` is still written.  With several ranks the CONTIGS are
@@ -732,8 +781,13 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         ``strand_path`` (GENOMAD_AMD_STRAND): under ``reverse`` or ``both`` every score, embedding and track carries that mode and each
         strand's contig scores are written there; the file also says which mode the stage's outputs were computed under (absent:
         forward), and a run that asks for another mode runs the stage again.  Embeddings and scan files of reverse / both carry the
-        mode as well, so one left behind by an earlier run is not taken for another mode's."""
+        mode as well, so one left behind by an earlier run is not taken for another mode's.
+        ``occ_path`` (GENOMAD_AMD_OCCLUSION_BLOCK): after its normal classification every piece is also occluded with blocks of that
+        size (NNEngine.occlude_contigs) and the maps are written there.  The file follows the strand file's rule: it says which block
+        size the stage was run with (absent: none), a run that asks for another runs the stage again, and one that asks for none
+        removes it."""
         (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and _strand_of_file(strand_path) == strand
+                                 and _occlusion_block_of_file(occ_path) == occlusion_block
                                  and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
                                  and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
                                                             and _npz_strand(scan_path) == strand)))   # :284-292
@@ -750,7 +804,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             eng = _engine()
             size = Path(fasta).stat().st_size * (1 if sequence.compression_of(fasta) == "uncompressed" else 4)
             precision = select_arithmetic(eng, precision, size, comm, console)
-            parts, emb_parts, scan_parts, strand_parts = [], [], [], []
+            parts, emb_parts, scan_parts, strand_parts, occ_parts = [], [], [], [], []
             sentinel = {"d": None, "done": False}
 
             def classify(key, nm, sq, off):
@@ -761,6 +815,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     scan_parts.append((key, scan_contigs_safely(eng, sq, off, scan_stride, single_window, precision, console)))
                 elif scan_path is not None:
                     scan_parts.append((key, scan_contigs_strand_safely(eng, sq, off, scan_stride, strand, single_window, precision, console)))
+                if occlusion_block is not None:                         # likewise after, and beside, the normal classification
+                    occ_parts.append((key, occlude_contigs_safely(eng, sq, off, occlusion_block, single_window, precision, console)))
 
             def classify_piece(key, sq, off):
                 if not sentinel["done"] and len(off) > 1:           # this rank's first piece with a contig: the run's parity sample
@@ -816,6 +872,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             strand_fields = sharding.SCAN_STRAND_FIELDS if strand != "forward" else ()
             scans_all = sharding.gather_contig_scans(comm, scan_parts, extra_window_fields=strand_fields) if scan_path is not None else None
             strands_all = sharding.gather_contig_strand_scores(comm, strand_parts) if strand != "forward" else None
+            occ_all = sharding.gather_contig_occlusions(comm, occ_parts) if occlusion_block is not None else None
             gate()
             if not n_windows:                                                        # :297-299
                 console.error("No sequences were found. Please check your input FASTA.")
@@ -848,6 +905,12 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                 f"(largest per-{what} |forward - reverse| {float(np.abs(fwd - rev).max()) if len(fwd) else 0.0:.4f}).")
                 elif strand_path.exists():          # these outputs are forward ones again: the file that said otherwise goes
                     strand_path.unlink()
+                if occlusion_block is not None:
+                    np.savez_compressed(occ_path, **{names_key: names, "block": np.int64(occlusion_block), **occ_all})
+                    console.log(f"Occlusion maps of the {what}s (blocks of {occlusion_block}, {len(occ_all['delta'])} (window, block) pairs) "
+                                f"written to {occ_path.name}.")
+                elif occ_path.exists():             # no occlusion was asked for: the file that said otherwise goes
+                    occ_path.unlink()
         if cleanup and rank0 and enc_dir.is_dir():
             console.log(f"Deleting encoded {what} data.")
             shutil.rmtree(enc_dir)
@@ -857,16 +920,16 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     run = stage_device if device_front_end else stage
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
     scan_kw = (lambda path: {"scan_path": path}) if scan_stride is not None else (lambda path: {})
-    strand_kw = (lambda path: {"strand_path": path}) if device_front_end else (lambda path: {})
+    strand_kw = (lambda path, occ: {"strand_path": path, "occ_path": occ}) if device_front_end else (lambda path, occ: {})
     try:
         run(input_path, outputs.encoded_sequences_dir, outputs.seq_window_id_output,
             outputs.nn_classification_npz_output, outputs.nn_classification_output,
-            "contig_names", "contig_ids", "sequence", **strand_kw(outputs.nn_strand_output), **emb_kw(outputs.nn_embeddings_output),
+            "contig_names", "contig_ids", "sequence", **strand_kw(outputs.nn_strand_output, outputs.nn_occlusion_output), **emb_kw(outputs.nn_embeddings_output),
             **scan_kw(outputs.nn_scan_output))
         if classify_proviruses:                                                      # :248-281, :355-425
             run(outputs.find_proviruses_nucleotide_output, outputs.encoded_proviruses_dir,
                 outputs.provirus_window_id_output, outputs.provirus_nn_classification_npz_output,
-                outputs.provirus_nn_classification_output, "provirus_names", "provirus_ids", "provirus", **strand_kw(outputs.provirus_nn_strand_output),
+                outputs.provirus_nn_classification_output, "provirus_names", "provirus_ids", "provirus", **strand_kw(outputs.provirus_nn_strand_output, outputs.provirus_nn_occlusion_output),
                 **emb_kw(outputs.provirus_nn_embeddings_output), **scan_kw(outputs.provirus_nn_scan_output))
     finally:
         if check_pool is not None:

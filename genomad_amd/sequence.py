@@ -454,6 +454,37 @@ def strand_mean(f, r) -> np.ndarray:
     return (f + r) * np.float32(0.5)
 
 
+def occlude_spans(seq: np.ndarray, starts, lens, lo, hi) -> np.ndarray:
+    """(n, 6000) uint8: the OCCLUDED windows of the spans seq[start : start + len] (``gnn_occlude_spans_dev``, in numpy): the forward
+    window of :func:`materialize_spans` with the window-relative interval [lo, hi) set to 'N'.  0 <= lo <= hi <= 6000; an empty
+    interval gives the forward window, an interval that reaches into the pad changes nothing there."""
+    out = materialize_spans(seq, starts, lens)
+    for i, (a, b) in enumerate(zip(lo, hi)):
+        a, b = int(a), int(b)
+        if not 0 <= a <= b <= WINDOW:
+            raise ValueError(f"span {i} has the interval [{a}, {b}): 0 <= lo <= hi <= {WINDOW} is required")
+        out[i, a:b] = ord("N")
+    return out
+
+
+def occlusion_blocks(lens, block: int):
+    """The (window, block) pairs of an occlusion map (``gnn_occlusion_plan`` / ``gnn_occlude_contigs``): window i of length lens[i]
+    has ceil(lens[i] / block) blocks, block j is the window-relative interval [j * block, min((j + 1) * block, lens[i])); the pad is
+    never a block.  Pairs run in window order, then block order.  Returns (blk_offsets int64 (n_windows + 1) - the CSR of the pairs
+    over the windows -, owner int64 (n_pairs: the pair's window), lo int32, hi int32 (n_pairs))."""
+    block = int(block)
+    if not 1 <= block <= WINDOW:
+        raise ValueError(f"block {block} is outside [1, {WINDOW}]")
+    lens = np.asarray(lens, dtype=np.int64)
+    nb = -(-lens // block)
+    blk_offsets = np.concatenate([[0], np.cumsum(nb)]).astype(np.int64)
+    owner = np.repeat(np.arange(len(lens), dtype=np.int64), nb)
+    j = np.arange(int(blk_offsets[-1]), dtype=np.int64) - blk_offsets[:-1][owner]
+    lo = j * block
+    hi = np.minimum(lo + block, lens[owner])
+    return blk_offsets, owner, lo.astype(np.int32), hi.astype(np.int32)
+
+
 def scan_track(scores, kept, lens, win_offsets, bin_offsets, stride: int):
     """The track of a scan, spelled out (the definition ``gnn_scan_contigs`` folds on the device; readable, not fast): bin b of a
     contig is [b * stride, (b + 1) * stride); window k covers it iff k <= b and b * stride < k * stride + lens[k].  track[b] = the

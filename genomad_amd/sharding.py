@@ -254,6 +254,52 @@ def gather_contig_scans(comm, parts, root: int = 0, extra_window_fields=()):
     return {f: np.concatenate(v) if v else empty[f] for f, v in out.items()}
 
 
+OCCLUSION_WINDOW_FIELDS = ("starts", "lens", "kept", "scores")      # per window; CSR over contigs by win_offsets
+OCCLUSION_EMPTY = {"starts": np.zeros(0, np.int64), "lens": np.zeros(0, np.int32), "kept": np.zeros(0, bool),
+                   "scores": np.zeros((0, 3), np.float32), "delta": np.zeros((0, 3), np.float32),
+                   "contig_scores": np.zeros((0, 3), np.float32)}
+
+
+def gather_contig_occlusions(comm, parts, root: int = 0):
+    """Occlusion maps of contig-sharded pieces -> ``root``, in the piece order of :func:`gather_contig_parts`: the sibling of
+    :func:`gather_contig_scans`, by the same mechanism.  ``parts`` = this rank's list of (order_key, result) with the keys and contig
+    counts of the pieces handed to gather_contig_parts; ``result`` = the arrays of one ``NNEngine.occlude_contigs`` call (win_offsets,
+    starts, lens, kept, scores, blk_offsets, delta, contig_scores; an object with ``asdict()`` or a dict).  Each rank's pieces travel
+    as one byte string; ``root`` concatenates them and rebases the two CSR arrays - win_offsets over contigs, blk_offsets over
+    windows; the values are only moved, so the result is bit-identical for any number of ranks.  Returns a dict of those eight
+    arrays on ``root``, None elsewhere."""
+    comm = comm or LocalComm()
+    fields = ("win_offsets", "blk_offsets") + OCCLUSION_WINDOW_FIELDS + ("delta", "contig_scores")
+    arrays = {"keys": np.array([int(key) for key, _ in parts], dtype="<i8")}
+    for i, (_, res) in enumerate(parts):
+        res = res.asdict() if hasattr(res, "asdict") else res
+        for f in fields:
+            arrays[f"{i}_{f}"] = np.ascontiguousarray(res[f])
+    buf = io.BytesIO()
+    np.savez(buf, **arrays)
+    blobs = gather_bytes(comm, buf.getvalue(), root)
+    if comm.rank != root:
+        return None
+    pieces = []                      # (order_key, {field: array})
+    for blob in blobs:
+        z = np.load(io.BytesIO(blob))
+        for i, key in enumerate(z["keys"]):
+            pieces.append((int(key), {f: z[f"{i}_{f}"] for f in fields}))
+    if len({p[0] for p in pieces}) != len(pieces):
+        raise ValueError("duplicate piece keys in gather_contig_occlusions")
+    pieces.sort(key=lambda p: p[0])
+    out = {"win_offsets": [np.zeros(1, np.int64)], "blk_offsets": [np.zeros(1, np.int64)]}
+    out.update({f: [] for f in fields[2:]})
+    w0 = p0 = 0
+    for _, d in pieces:
+        out["win_offsets"].append(d["win_offsets"][1:].astype(np.int64) + w0)
+        out["blk_offsets"].append(d["blk_offsets"][1:].astype(np.int64) + p0)
+        w0, p0 = w0 + int(d["win_offsets"][-1]), p0 + int(d["blk_offsets"][-1])
+        for f in fields[2:]:
+            out[f].append(d[f])
+    return {f: np.concatenate(v) if v else OCCLUSION_EMPTY[f] for f, v in out.items()}
+
+
 def gather_contig_results(comm, names, predictions, window_ids, root: int = 0):
     """One piece per rank, in rank order (see :func:`gather_contig_parts`)."""
     comm = comm or LocalComm()

@@ -352,6 +352,51 @@ int gnn_scan_contigs_strand(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, i
                             int32_t* cover_host_or_null, int64_t bins_capacity, float* contig_scores_host_or_null, int strand,
                             float* window_scores_fwd_host_or_null, float* window_scores_rev_host_or_null);
 
+/* ---- occlusion maps: per-block score change along contigs ("Occlusion maps") -------------------------------------------
+ * Which bases a score rests on, answered with the forward pass of gnn_classify alone: mask a block of a window with 'N' - the
+ * model's own "unknown": every 4-mer that touches a non-ACGT byte is token 0, and 'N' is the byte short windows are padded with -
+ * score the window again and report how far each class moved.
+ *   block     B, 1 <= B <= 6000.
+ *   windows   the table of gnn_classify_contigs: seq_windows(seq, 6000, 2500, max_windows) per contig, honouring single_window.
+ *             Window ids, the N rule and the kept mask are unchanged.  Every window is occluded; kept is a mask, as in the scan.
+ *   blocks    window i of length len_i has nb_i = ceil(len_i / B) blocks; block j is the window-relative interval
+ *             [j B, min((j + 1) B, len_i)).  The pad is never a block.
+ *   pairs     all (window, block) pairs in window order, then block order: P = sum nb_i, indexed through the CSR
+ *             blk_offsets[n_windows + 1].
+ *   occluded  window: the forward window as gnn_classify_spans materialises it (upper-cased, right-padded with 'N') with the
+ *             block's bytes set to 'N'.
+ *   delta     delta[p][c] = base[i][c] - occ[p][c], one f32 subtraction; base is the window's ordinary score.  Positive: the block
+ *             supports class c.  A block that holds no ACGT byte yields exactly +0.0: its tokens are the window's own, and every
+ *             arithmetic is batch-invariant.
+ *   identity  base is bit-identical to gnn_scan_contigs at stride 6000, the contig scores and kept to gnn_classify_contigs, occ to
+ *             gnn_classify on the same bytes - whatever gnn_set_chunk, where seq lives, or what ran on the ctx before.
+ * Cost: 1 + ceil(6000 / B) forward passes per full window.  Forward strand only.
+ * gnn_occlusion_plan - host only, no ctx, no GPU, like gnn_scan_plan - answers the sizes: the number of windows and of pairs, and,
+ * where the pointers are not NULL, win_offsets (n_contigs + 1), the contig-relative start and the length of every window
+ * (*n_windows_out entries) and blk_offsets (*n_windows_out + 1): call once for the sizes, then again with the arrays.  GNN_ERR_ARG
+ * (the message says [1, 6000]) for a block outside that range, and for decreasing offsets. */
+int gnn_occlusion_plan(const int64_t* offsets_host, int64_t n_contigs, int block, int single_window,
+                       int64_t* n_windows_out, int64_t* n_pairs_out, int64_t* win_offsets_or_null,
+                       int64_t* starts_or_null, int32_t* lens_or_null, int64_t* blk_offsets_or_null);
+/* The building block, the counterpart of gnn_revcomp_spans_dev: bases_dev_out[n_spans][6000] = each span (start, len) of seq_dev
+ * materialised with the window-relative interval [lo, hi) set to 'N', ready for gnn_classify_dev / gnn_embed_dev.  0 <= lo <= hi <=
+ * 6000; an empty interval gives the plain forward window, an interval that reaches into the pad changes nothing there.
+ * bases_dev_out: device pointer, 4-byte aligned.  Spans as gnn_classify_spans (host arrays, lengths in [0, 6000]); a violation is
+ * GNN_ERR_ARG and the message names the offending value.  Returns when the windows are written. */
+int gnn_occlude_spans_dev(gnn_ctx* ctx, const uint8_t* seq_dev, const int64_t* starts_host, const int32_t* lens_host,
+                          const int32_t* lo_host, const int32_t* hi_host, int64_t n_spans, uint8_t* bases_dev_out);
+/* The occlusion map of a packed contig buffer (seq, seq_on_host, seq_bytes, offsets_host as gnn_scan_contigs; every arithmetic
+ * gnn_classify_contigs accepts).  window_scores_host[n_windows][3] (base) and window_kept_host[n_windows] (1 = kept) in the order of
+ * gnn_occlusion_plan, capacity windows_capacity windows; delta_host[n_pairs][3], capacity pairs_capacity pairs; contig_scores_host
+ * [n_contigs][3].  A capacity that is too small is GNN_ERR_ARG and the message names the size needed; n_contigs == 0, or no window
+ * at all, is GNN_OK.  Synchronous.  The base windows go first; then the pairs in slabs of at most 4 launches, each materialised,
+ * scored, differenced and copied out.  Device memory, persistent in the ctx and grow-only, does not grow with the number of pairs:
+ * 6000 B + 12 B per pair of ONE slab, the 40 B per window of gnn_classify_contigs' table and 8 B per window of blk_offsets. */
+int gnn_occlude_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes, const int64_t* offsets_host,
+                        int64_t n_contigs, int block, int single_window, int precision, float* window_scores_host,
+                        uint8_t* window_kept_host_or_null, int64_t windows_capacity, float* delta_host,
+                        int64_t pairs_capacity, float* contig_scores_host_or_null);
+
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
  * in-memory text buffer (already decompressed, newlines normalised to '\n').
