@@ -125,7 +125,7 @@ int finish_pending(gnn_ctx* ctx) {
 // between host and device, allocate and free, and read the workspaces - none of them is on a path where the few hundred
 // microseconds matter, and nothing they do can then depend on how a cross-stream dependency is resolved
 // (profiles/history/r02c6_async_flake.md).  Callers that never use the asynchronous entry point never have anything pending here.
-static int check_ctx(gnn_ctx* ctx, bool flush = true) {
+int check_ctx(gnn_ctx* ctx, bool flush) {
     if (!ctx) {
         set_error("ctx is NULL");
         return GNN_ERR_ARG;
@@ -406,6 +406,13 @@ int classify_chunks(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int preci
         if (rc) return rc;
     }
     return defer_last ? GNN_OK : flush_backend(ctx);     // the caller synchronises ctx->stream only
+}
+
+int check_embed_precision(int precision, const char* fn) {
+    if (precision != GNN_PREC_F16C6) return GNN_OK;
+    set_error(std::string(fn) + ": GNN_PREC_F16C6 has no embedding path (the frozen mode's dense head runs on the matrix pipe "
+              "and is outside the tolerance); use f16x3tc, f16x3tk, f16x3, bf16x3 or f32");
+    return GNN_ERR_ARG;
 }
 
 }  // namespace gnn
@@ -890,11 +897,7 @@ int gnn_classify_flush(gnn_ctx* ctx) { return check_ctx(ctx); }
 
 // argument checks shared by the embedding entry points
 static int embed_args(int precision, int emb_dtype, const char* what) {
-    if (precision == GNN_PREC_F16C6) {
-        set_error(std::string(what) + ": GNN_PREC_F16C6 has no embedding path (the frozen mode's dense head runs on the matrix pipe "
-                  "and is outside the tolerance); use f16x3tc, f16x3tk, f16x3, bf16x3 or f32");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = check_embed_precision(precision, what)) return rc;
     if (!emb_elem_bytes(emb_dtype)) {
         set_error(std::string(what) + ": unknown gnn_emb_dtype " + std::to_string(emb_dtype));
         return GNN_ERR_ARG;

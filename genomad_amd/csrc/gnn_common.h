@@ -185,6 +185,43 @@ static inline void for_each_window(int64_t len, int64_t stride, int single_windo
     }
 }
 
+// The window table, once: the rule above over every contig of `offsets`, f(contig, k, length) per window in table order.  Counts
+// the windows and the stride-wide bins (ceil(length / stride) per contig) and, where a CSR array [n_contigs + 1] is given, files
+// the running counts per contig.  The offsets are validated before anything is written.
+struct WindowWalk {
+    int64_t* win_off = nullptr;
+    int64_t* bin_off = nullptr;
+    int64_t windows = 0, bins = 0;
+};
+template <typename F>
+static int walk_windows(const int64_t* offsets, int64_t n_contigs, int64_t stride, int single_window, WindowWalk& out, F&& f) {
+    for (int64_t c = 0; c < n_contigs; ++c)
+        if (offsets[c + 1] < offsets[c]) {
+            set_error("contig offsets are not non-decreasing");
+            return GNN_ERR_ARG;
+        }
+    out.windows = out.bins = 0;
+    if (out.win_off) out.win_off[0] = 0;
+    if (out.bin_off) out.bin_off[0] = 0;
+    for (int64_t c = 0; c < n_contigs; ++c) {
+        const int64_t len = offsets[c + 1] - offsets[c];
+        for_each_window(len, stride, single_window, [&](int64_t k, int64_t l) {
+            f(c, k, l);
+            ++out.windows;
+        });
+        out.bins += (len + stride - 1) / stride;
+        if (out.win_off) out.win_off[c + 1] = out.windows;
+        if (out.bin_off) out.bin_off[c + 1] = out.bins;
+    }
+    return GNN_OK;
+}
+
+// The N rule, once (nn_classification.py:70): a contig's first window is always kept, a later one unless it holds more than
+// MAX_N literal 'N'.  Decides which windows enter a contig's score, embedding and track - on the device and on the host.
+__host__ __device__ inline bool window_kept(int32_t window_n, int32_t n_count) {
+    return window_n == 0 || n_count <= MAX_N;
+}
+
 // Grow-only with some head-room (amortised).
 template <typename Tp>
 static int reserve_roomy(DevBuf<Tp>& b, size_t need) {
@@ -195,6 +232,15 @@ static int reserve_roomy(DevBuf<Tp>& b, size_t need) {
 template <typename... Bufs>
 static void reset_all(Bufs&... bufs) {
     (bufs.reset(), ...);
+}
+
+// One thread per cell, 256 per block: kernel(args...) on `stream`.  The arguments convert to the kernel's parameter types here, so
+// a DevBuf goes in as the pointer it owns.
+template <typename... P, typename... A>
+static int launch_1d(void (*kernel)(P...), int64_t cells, hipStream_t stream, A&&... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, static_cast<P>(args)...);
+    GNN_HIP(hipGetLastError());
+    return GNN_OK;
 }
 
 struct ProfileSlot {
@@ -325,8 +371,61 @@ int classify_chunks(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int preci
 size_t emb_elem_bytes(int emb_dtype);   // bytes of one embedding value (gnn_api.hip); 0 for a bad gnn_emb_dtype
 int flush_backend(gnn_ctx* ctx);
 int finish_pending(gnn_ctx* ctx);
-void free_contig_ws(gnn_ctx* ctx);     // gnn_contigs.hip
+// The entry preamble (gnn_api.hip): a NULL ctx is an error, the ctx's device becomes current, and - unless flush is false - what an
+// asynchronous classification left pending is finished.
+int check_ctx(gnn_ctx* ctx, bool flush = true);
+// GNN_OK, or the error of an embedding asked of GNN_PREC_F16C6 under the entry point's name (gnn_api.hip)
+int check_embed_precision(int precision, const char* fn);
 void free_stage(gnn_ctx* ctx);         // gnn_api.hip: staging of the host-buffer entry points
+
+// ---- the contig front end's steps (gnn_contigs.hip); gnn_occlude.hip runs the same ones ----
+// What every contig entry point is given.
+struct ContigIn {
+    gnn_ctx* ctx;
+    const uint8_t* seq;          // the packed contigs, on the host (seq_on_host) or on the device
+    int seq_on_host;
+    int64_t seq_bytes;
+    const int64_t* offsets;      // host, [n_contigs + 1]
+    int64_t n_contigs;
+    int single_window, precision;
+    int64_t stride;              // W, or a scan's stride
+};
+
+// Where a call's kernels read the packed sequence.  Already on the device: the caller's pointer, and upto() has nothing to do.  On
+// the host: w.seq, which begin() reserves and upto() fills in PIECEs on the copy stream while earlier pieces are classified on
+// the ctx stream.  This is the only code that writes w.seq or touches the copy stream.
+class SeqFeed {
+  public:
+    int begin(const ContigIn& in, ContigWorkspace& w);
+    // every piece that holds a byte below `end` is on its way, and the ctx stream waits for the last of them
+    int upto(int64_t end);
+    const uint8_t* dev() const { return dev_; }
+
+  private:
+    gnn_ctx* ctx_ = nullptr;
+    ContigWorkspace* w_ = nullptr;
+    const uint8_t* host_ = nullptr;      // NULL: nothing to upload
+    const uint8_t* dev_ = nullptr;
+    int64_t bytes_ = 0, n_pieces_ = 0, uploaded_ = 0;
+};
+
+// Entry: check_ctx, the arguments every contig call shares (`outputs_ok`: the caller's verdict on its own pointers; the message
+// names `fn`), the offsets against the buffer, and the ctx's workspace, created on first use.
+int contig_begin(const ContigIn& in, const char* fn, bool outputs_ok, ContigWorkspace** w);
+// Plan: the host side of the span table (w.starts / lens / ids / window_n) by walk_windows at in.stride; csr: also w.win_off and
+// w.bin_off; block > 0: also w.blk_off, the CSR of every window's blocks of `block` bases.
+int plan_windows(const ContigIn& in, ContigWorkspace& w, bool csr, int block);
+// The per-window device tables hold the planned windows (grown as a group) and the four uploads are enqueued on the ctx stream.
+int upload_span_table(gnn_ctx* ctx, ContigWorkspace& w);
+// One slab [a, a + m) of the span table: what its windows read is uploaded, their N are counted into w.d_counts, they are
+// materialised into w.d_bases - the forward windows, then the reverse ones, whichever are asked for - and the batch is classified:
+// scores[(fwd + rev) * m][GNN_CLASSES], and emb[(fwd + rev) * m][HID] unless NULL.
+int slab_pass(const ContigIn& in, ContigWorkspace& w, SeqFeed& feed, int64_t a, int64_t m, bool fwd, bool rev, float* scores,
+              float* emb);
+// After the counts came back (w.counts): the N rule per window on the host.  mask[i] = 1 / 0 and the contig ids of the kept
+// windows, compacted, where asked for; returns how many are kept.
+int64_t kept_windows(const ContigWorkspace& w, uint8_t* mask_or_null, int64_t* ids_or_null);
+void free_contig_ws(gnn_ctx* ctx);
 
 int launch_front_c6(gnn_ctx* ctx, const uint8_t* bases, int64_t n);             // GNN_PREC_F16C6 -> ws.mp, ws.yp
 int launch_front_x3(gnn_ctx* ctx, const uint8_t* bases, int64_t n, int precision);   // GNN_PREC_F16X3 / BF16X3 (gnn_fused_x3.hip) -> ws.mp, ws.yp

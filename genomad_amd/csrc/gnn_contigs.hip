@@ -39,11 +39,21 @@ struct ScanOut {
 // What the *_strand entry points add: the mode (gnn_strand) and host buffers for each strand's own results (any may be NULL).  A
 // strand is computed when the mode needs it or one of its buffers is given.
 struct StrandOut {
-    int strand;
-    float* contig_fwd;          // [n_contigs][3]: each strand's own masked mean
-    float* contig_rev;
-    float* window_fwd;          // scans only: [n_windows][3]
-    float* window_rev;
+    int strand = GNN_STRAND_FORWARD;
+    float* contig_fwd = nullptr;          // [n_contigs][3]: each strand's own masked mean
+    float* contig_rev = nullptr;
+    float* window_fwd = nullptr;          // scans only: [n_windows][3]
+    float* window_rev = nullptr;
+};
+
+// What a contig call hands back per contig (any may be NULL where the entry point allows it): the mode's scores, the contig ids
+// of the kept windows with their count (gnn_classify_contigs*; a scan reports kept per window instead) and the embeddings.
+struct ContigOut {
+    float* scores = nullptr;            // [n_contigs][3]
+    int64_t* window_ids = nullptr;
+    int64_t ids_capacity = 0;
+    int64_t* n_windows = nullptr;
+    float* emb = nullptr;               // [n_contigs][HID]
 };
 
 void free_contig_ws(gnn_ctx* ctx) {
@@ -73,7 +83,7 @@ __global__ void masked_segment_mean_kernel(const float* __restrict__ scores, con
     float s = 0.f;
     int kept = 0;
     for (int64_t k = lo; k < n && ids[k] == seg; ++k)
-        if (window_n[k] == 0 || counts[k] <= MAX_N) {
+        if (window_kept(window_n[k], counts[k])) {
             s += scores[k * GNN_CLASSES + cl];
             ++kept;
         }
@@ -82,17 +92,13 @@ __global__ void masked_segment_mean_kernel(const float* __restrict__ scores, con
 
 int launch_masked_segment_mean(gnn_ctx* ctx, const float* scores, const int64_t* ids, const int32_t* window_n, const int32_t* counts,
                                int64_t n, int64_t n_seg, float* out) {
-    const int64_t threads = n_seg * GNN_CLASSES;
-    hipLaunchKernelGGL(masked_segment_mean_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, scores, ids,
-                       window_n, counts, n, n_seg, out);
-    GNN_HIP(hipGetLastError());
-    return GNN_OK;
+    return launch_1d(masked_segment_mean_kernel, n_seg * GNN_CLASSES, ctx->stream, scores, ids, window_n, counts, n, n_seg, out);
 }
 
 // Per-contig embedding fold of one slab [a, a + m) of the window table: one block per contig the slab touches (ids are sorted, so
 // contigs ids[a] .. ids[a+m-1]), 128 lanes x 4 columns = one 2 KB row per step, read as float4s (coalesced: a row is contiguous).
 // The contig's kept windows of this slab are added to its running sum in window order, starting from what the slabs before left
-// there, so the sum is ((0 + e_0) + e_1) + ... whatever the slab and launch sizes.  Kept = the rule of masked_segment_mean_kernel.
+// there, so the sum is ((0 + e_0) + e_1) + ... whatever the slab and launch sizes.
 constexpr int FOLD_THREADS = HID / 4;
 
 __global__ __launch_bounds__(FOLD_THREADS) void emb_fold_kernel(const float* __restrict__ emb, const int64_t* __restrict__ ids,
@@ -108,7 +114,7 @@ __global__ __launch_bounds__(FOLD_THREADS) void emb_fold_kernel(const float* __r
     float4 s = *row;
     int k = 0;
     for (int64_t i = lo; i < a + m && ids[i] == seg; ++i)
-        if (window_n[i] == 0 || counts[i] <= MAX_N) {
+        if (window_kept(window_n[i], counts[i])) {
             const float4 v = reinterpret_cast<const float4*>(emb + (size_t)(i - a) * HID)[threadIdx.x];
             s.x += v.x;
             s.y += v.y;
@@ -131,7 +137,7 @@ __global__ void emb_mean_kernel(float* __restrict__ sums, const int32_t* __restr
 // The track fold of gnn_scan_contigs: one thread per (bin, class), the output index is the thread index (coalesced stores).  Bin b
 // of a contig is [b * stride, (b + 1) * stride); window k covers it iff k <= b and b * stride < k * stride + len_k, which bounds
 // k from below by b - (W - 1) / stride: at most ceil(W / stride) windows, read in increasing k and added in that order in f32 (the
-// order is part of the contract: no atomics), divided once.  Kept = the rule of masked_segment_mean_kernel.  A bin without a kept
+// order is part of the contract: no atomics), divided once.  Kept = window_kept.  A bin without a kept
 // covering window (a dropped tail, or every covering window masked by the N rule) is NaN in all three classes, cover 0.
 __global__ void scan_track_kernel(const float* __restrict__ scores, const int32_t* __restrict__ lens, const int32_t* __restrict__ counts,
                                   const int64_t* __restrict__ win_off, const int64_t* __restrict__ bin_off, int64_t n_contigs,
@@ -153,7 +159,7 @@ __global__ void scan_track_kernel(const float* __restrict__ scores, const int32_
     int kept = 0;
     for (int64_t k = k_lo; k <= k_hi; ++k) {
         const int64_t j = w0 + k;
-        if (b * stride < k * stride + lens[j] && (k == 0 || counts[j] <= MAX_N)) {
+        if (b * stride < k * stride + lens[j] && window_kept((int32_t)k, counts[j])) {      // k, the index within the contig, IS window_n[j]
             s += scores[j * GNN_CLASSES + cl];
             ++kept;
         }
@@ -183,269 +189,311 @@ __global__ void emb_both_mean_kernel(float* __restrict__ sums, const float* __re
     sums[i] = k ? (sums[i] + sums_rev[i]) / (float)(2 * k) : 0.f;
 }
 
+// ---- the steps every contig call is made of (declared in gnn_common.h) ----
+
+int contig_begin(const ContigIn& in, const char* fn, bool outputs_ok, ContigWorkspace** w) {
+    if (int rc = check_ctx(in.ctx)) return rc;
+    if (in.n_contigs < 0 || in.seq_bytes < 0 || !in.offsets || !outputs_ok || (in.seq_bytes > 0 && !in.seq)) {
+        set_error(std::string("bad argument to ") + fn);
+        return GNN_ERR_ARG;
+    }
+    if (in.offsets[0] < 0 || in.offsets[in.n_contigs] > in.seq_bytes) {
+        set_error("contig offsets outside the sequence buffer");
+        return GNN_ERR_ARG;
+    }
+    if (!in.ctx->contig_ws) in.ctx->contig_ws = new ContigWorkspace();
+    *w = in.ctx->contig_ws;
+    return GNN_OK;
+}
+
+// candidate windows: seq_windows(seq, 6000, 2500, max_windows) for every contig (sequence.py:150-167), at in.stride
+int plan_windows(const ContigIn& in, ContigWorkspace& w, bool csr, int block) {
+    w.starts.clear(), w.lens.clear(), w.ids.clear(), w.window_n.clear();
+    w.blk_off.assign(1, 0);
+    WindowWalk walk;
+    if (csr) {
+        w.win_off.resize((size_t)in.n_contigs + 1), w.bin_off.resize((size_t)in.n_contigs + 1);
+        walk.win_off = w.win_off.data(), walk.bin_off = w.bin_off.data();
+    }
+    return walk_windows(in.offsets, in.n_contigs, in.stride, in.single_window, walk, [&](int64_t c, int64_t k, int64_t l) {
+        w.starts.push_back(in.offsets[c] + k * in.stride);
+        w.lens.push_back((int32_t)l);
+        w.ids.push_back(c);
+        w.window_n.push_back((int32_t)k);
+        if (block) w.blk_off.push_back(w.blk_off.back() + (l + block - 1) / block);
+    });
+}
+
+int upload_span_table(gnn_ctx* ctx, ContigWorkspace& w) {
+    const size_t n = w.starts.size();
+    if (w.span_cap() < n) {
+        GNN_HIP(hipStreamSynchronize(ctx->stream));      // a buffer that grows is freed first: nothing may still read it
+        reset_all(w.d_starts, w.d_ids, w.d_lens, w.d_window_n, w.d_counts, w.d_scores);      // empty, not half-grown, on failure
+        int rc = reserve_roomy(w.d_starts, n);
+        if (!rc) rc = reserve_roomy(w.d_ids, n);
+        if (!rc) rc = reserve_roomy(w.d_lens, n);
+        if (!rc) rc = reserve_roomy(w.d_window_n, n);
+        if (!rc) rc = reserve_roomy(w.d_counts, n);
+        if (!rc) rc = reserve_roomy(w.d_scores, n * GNN_CLASSES);
+        if (rc) return rc;
+    }
+    GNN_HIP(hipMemcpyAsync(w.d_starts, w.starts.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    GNN_HIP(hipMemcpyAsync(w.d_lens, w.lens.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    GNN_HIP(hipMemcpyAsync(w.d_ids, w.ids.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    GNN_HIP(hipMemcpyAsync(w.d_window_n, w.window_n.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    return GNN_OK;
+}
+
+int SeqFeed::begin(const ContigIn& in, ContigWorkspace& w) {
+    ctx_ = in.ctx, w_ = &w, dev_ = in.seq;
+    if (!in.seq_on_host) return GNN_OK;
+    if (w.seq.capacity() < (size_t)in.seq_bytes) {      // freed before it grows: neither stream may still touch it
+        GNN_HIP(hipStreamSynchronize(ctx_->stream));
+        if (w.copy_stream) GNN_HIP(hipStreamSynchronize(w.copy_stream));
+    }
+    if (int rc = reserve_roomy(w.seq, (size_t)in.seq_bytes)) return rc;
+    host_ = in.seq, dev_ = w.seq, bytes_ = in.seq_bytes;
+    if (!w.copy_stream) GNN_HIP(hipStreamCreateWithFlags(&w.copy_stream, hipStreamNonBlocking));
+    n_pieces_ = (bytes_ + PIECE - 1) / PIECE;
+    while ((int64_t)w.piece_done.size() < n_pieces_) {
+        hipEvent_t e = nullptr;
+        GNN_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        w.piece_done.push_back(e);
+    }
+    // the previous call's kernels may still read w.seq: order the copies behind them
+    hipEvent_t& first = w.piece_done[0];
+    GNN_HIP(hipEventRecord(first, ctx_->stream));
+    GNN_HIP(hipStreamWaitEvent(w.copy_stream, first, 0));
+    return GNN_OK;
+}
+
+int SeqFeed::upto(int64_t end) {
+    if (!host_) return GNN_OK;
+    const int64_t upto = std::min<int64_t>(n_pieces_, (end + PIECE - 1) / PIECE);
+    for (; uploaded_ < upto; ++uploaded_) {
+        const int64_t off = uploaded_ * PIECE, len = std::min(PIECE, bytes_ - off);
+        GNN_HIP(hipMemcpyAsync(w_->seq + off, host_ + off, (size_t)len, hipMemcpyHostToDevice, w_->copy_stream));
+        GNN_HIP(hipEventRecord(w_->piece_done[uploaded_], w_->copy_stream));
+    }
+    if (upto > 0) GNN_HIP(hipStreamWaitEvent(ctx_->stream, w_->piece_done[upto - 1], 0));
+    return GNN_OK;
+}
+
+int slab_pass(const ContigIn& in, ContigWorkspace& w, SeqFeed& feed, int64_t a, int64_t m, bool fwd, bool rev, float* scores,
+              float* emb) {
+    int rc = feed.upto(w.starts[a + m - 1] + w.lens[a + m - 1]);       // spans are in buffer order: the slab's last byte
+    if (rc) return rc;
+    const int64_t* const starts = w.d_starts + a;
+    const int32_t* const lens = w.d_lens + a;
+    if ((rc = launch_span_count(in.ctx, feed.dev(), starts, lens, m, 'N', w.d_counts + a))) return rc;      // serves both strands
+    if (fwd && (rc = launch_materialize(in.ctx, feed.dev(), starts, lens, m, w.d_bases))) return rc;
+    if (rev && (rc = launch_revcomp(in.ctx, feed.dev(), starts, lens, m, w.d_bases + (fwd ? m : 0) * W))) return rc;
+    return classify_chunks(in.ctx, w.d_bases, m * (fwd + rev), in.precision, scores, false, emb, GNN_EMB_F32);
+}
+
+int64_t kept_windows(const ContigWorkspace& w, uint8_t* mask_or_null, int64_t* ids_or_null) {
+    int64_t kept = 0;
+    for (size_t i = 0; i < w.starts.size(); ++i) {
+        const bool keep = window_kept(w.window_n[i], w.counts[i]);
+        if (mask_or_null) mask_or_null[i] = keep ? 1 : 0;
+        if (keep && ids_or_null) ids_or_null[kept] = w.ids[i];
+        kept += keep;
+    }
+    return kept;
+}
+
 }  // namespace gnn
 
 using namespace gnn;
 
-static int classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes, const int64_t* offsets_host,
-                            int64_t n_contigs, int single_window, int precision, float* contig_scores_host, int64_t* window_ids_host,
-                            int64_t ids_capacity, int64_t* n_windows_out, float* contig_emb_host, int64_t stride = W,
-                            const ScanOut* scan = nullptr, const StrandOut* so = nullptr) {
-    const char* const fn = scan ? "gnn_scan_contigs" : "gnn_classify_contigs";
-    const int strand = so ? so->strand : GNN_STRAND_FORWARD;
-    // which strands run: what the mode averages, and what the caller asked to see on its own
-    const bool need_f = strand != GNN_STRAND_REVERSE || (so && (so->contig_fwd || so->window_fwd));
-    const bool need_r = strand != GNN_STRAND_FORWARD || (so && (so->contig_rev || so->window_rev));
-    const int64_t ns = (need_f ? 1 : 0) + (need_r ? 1 : 0);
-    if (!ctx) {
-        set_error("ctx is NULL");
-        return GNN_ERR_ARG;
-    }
-    GNN_HIP(hipSetDevice(ctx->device));
-    {
-        const int frc = finish_pending(ctx);
-        if (frc) return frc;
-    }
-    if (n_contigs < 0 || seq_bytes < 0 || !offsets_host || !n_windows_out || (n_contigs > 0 && !contig_scores_host && !scan) ||
-        (seq_bytes > 0 && !seq)) {
-        set_error(std::string("bad argument to ") + fn);
-        return GNN_ERR_ARG;
-    }
-    if (offsets_host[0] < 0 || offsets_host[n_contigs] > seq_bytes) {
-        set_error("contig offsets outside the sequence buffer");
-        return GNN_ERR_ARG;
-    }
-    if (!ctx->contig_ws) ctx->contig_ws = new ContigWorkspace();
-    ContigWorkspace& w = *ctx->contig_ws;
+// ---- gnn_classify_contigs, gnn_scan_contigs and their *_embed / *_strand forms: one call, in five steps ----
 
-    // ---- candidate windows: seq_windows(seq, 6000, 2500, max_windows) for every contig (sequence.py:150-167), at `stride`
-    w.starts.clear(), w.lens.clear(), w.ids.clear(), w.window_n.clear();
-    w.win_off.assign(1, 0), w.bin_off.assign(1, 0);
-    for (int64_t c = 0; c < n_contigs; ++c) {
-        const int64_t a = offsets_host[c], b = offsets_host[c + 1];
-        if (b < a) {
-            set_error("contig offsets are not non-decreasing");
-            return GNN_ERR_ARG;
+// What the steps of one call share: the table's size, which strands run, the slab, what is folded.
+struct ContigCall {
+    const ContigIn& in;
+    ContigWorkspace& w;
+    const StrandOut& so;
+    const ScanOut* scan;
+    float* contig_scores_host;
+    float* emb_host;            // NULL: no embeddings
+    int64_t n, n_bins;          // candidate windows, bins (scans)
+    bool need_f, need_r;        // which strands run: what the mode averages, and what the caller asked to see on its own
+    int64_t ns, slab;           // strands that run; windows per slab
+    bool fold;                  // a scan with a track
+    // the window scores of the mode: what the contig mean, the track and window_scores_host carry
+    const float* d_mode() const {
+        return so.strand == GNN_STRAND_BOTH ? w.d_scores_mix : (so.strand == GNN_STRAND_REVERSE ? w.d_scores_rev : w.d_scores);
+    }
+};
+
+// ---- reserve: everything but the span table and the sequence
+static int reserve_buffers(const ContigCall& c) {
+    gnn_ctx* const ctx = c.in.ctx;
+    ContigWorkspace& w = c.w;
+    const size_t n = (size_t)c.n, n_contigs = (size_t)c.in.n_contigs, batch = (size_t)(c.slab * c.ns);
+    int rc = GNN_OK;
+    if (c.need_r && w.strand_cap() < n) {      // 24 B per window more, and only for a caller of the *_strand entry points
+        GNN_HIP(hipStreamSynchronize(ctx->stream));
+        reset_all(w.d_scores_rev, w.d_scores_mix);
+        if (!rc) rc = reserve_roomy(w.d_scores_rev, n * GNN_CLASSES);
+        if (!rc) rc = reserve_roomy(w.d_scores_mix, n * GNN_CLASSES);
+        if (rc) return rc;
+    }
+    if ((rc = reserve_roomy(w.d_bases, batch * W))) return rc;
+    if ((rc = reserve_roomy(w.d_out, n_contigs * GNN_CLASSES))) return rc;
+    if (c.ns == 2 && (rc = reserve_roomy(w.d_slab_scores, batch * GNN_CLASSES))) return rc;
+    if ((c.so.contig_fwd || c.so.contig_rev) && (rc = reserve_roomy(w.d_out_strand, n_contigs * 2 * GNN_CLASSES))) return rc;
+    if (c.fold) {        // 16 B per contig and 16 B per bin (hipFree of a buffer that grows waits for the kernels that read it)
+        if (w.off_cap() < n_contigs + 1) {
+            reset_all(w.d_win_off, w.d_bin_off);
+            if (!rc) rc = reserve_roomy(w.d_win_off, n_contigs + 1);
+            if (!rc) rc = reserve_roomy(w.d_bin_off, n_contigs + 1);
         }
-        for_each_window(b - a, stride, single_window, [&](int64_t k, int64_t l) {
-            w.starts.push_back(a + k * stride);
-            w.lens.push_back((int32_t)l);
-            w.ids.push_back(c);
-            w.window_n.push_back((int32_t)k);
-        });
-        if (scan) {
-            w.win_off.push_back((int64_t)w.starts.size());
-            w.bin_off.push_back(w.bin_off.back() + (b - a + stride - 1) / stride);
+        if (!rc && w.bin_cap() < (size_t)c.n_bins) {
+            reset_all(w.d_track, w.d_cover);
+            if (!rc) rc = reserve_roomy(w.d_track, (size_t)c.n_bins * GNN_CLASSES);
+            if (!rc) rc = reserve_roomy(w.d_cover, (size_t)c.n_bins);
+        }
+        if (rc) return rc;
+    }
+    if (!c.emb_host) return GNN_OK;
+    // a slab's window embeddings (2 KB each) and the per-contig sums: never every window's row (10 M windows would be 20 GB)
+    const bool rev_sum = c.so.strand != GNN_STRAND_FORWARD;
+    if (w.d_emb.capacity() < batch * HID || w.d_emb_sum.capacity() < n_contigs * HID || w.d_emb_kept.capacity() < n_contigs ||
+        (rev_sum && (w.d_emb_sum_rev.capacity() < n_contigs * HID || w.d_emb_kept_rev.capacity() < n_contigs)))
+        GNN_HIP(hipStreamSynchronize(ctx->stream));
+    if ((rc = reserve_roomy(w.d_emb, batch * HID))) return rc;
+    if (rev_sum) {       // the reverse strand folds into a sum of its own: two independent sums, whatever the slab size
+        if ((rc = reserve_roomy(w.d_emb_sum_rev, n_contigs * HID))) return rc;
+        if ((rc = reserve_roomy(w.d_emb_kept_rev, n_contigs))) return rc;
+        GNN_HIP(hipMemsetAsync(w.d_emb_sum_rev, 0, n_contigs * HID * sizeof(float), ctx->stream));
+        GNN_HIP(hipMemsetAsync(w.d_emb_kept_rev, 0, n_contigs * sizeof(int32_t), ctx->stream));
+    }
+    if ((rc = reserve_roomy(w.d_emb_sum, n_contigs * HID))) return rc;
+    if ((rc = reserve_roomy(w.d_emb_kept, n_contigs))) return rc;
+    GNN_HIP(hipMemsetAsync(w.d_emb_sum, 0, n_contigs * HID * sizeof(float), ctx->stream));
+    GNN_HIP(hipMemsetAsync(w.d_emb_kept, 0, n_contigs * sizeof(int32_t), ctx->stream));
+    return GNN_OK;
+}
+
+// ---- pass: slabs of windows through the front end; both strands' scores are split, the embeddings folded, slab by slab
+static int run_slabs(const ContigCall& c, SeqFeed& feed) {
+    hipStream_t const stream = c.in.ctx->stream;
+    ContigWorkspace& w = c.w;
+    const int strand = c.so.strand;
+    int rc = GNN_OK;
+    for (int64_t a = 0; a < c.n; a += c.slab) {
+        const int64_t m = std::min(c.slab, c.n - a), row = a * GNN_CLASSES;
+        float* const batch_scores = c.ns == 2 ? w.d_slab_scores.get() : (c.need_f ? w.d_scores : w.d_scores_rev) + row;
+        if ((rc = slab_pass(c.in, w, feed, a, m, c.need_f, c.need_r, batch_scores, c.emb_host ? w.d_emb.get() : nullptr))) return rc;
+        if (c.ns == 2 && (rc = launch_1d(strand_split_kernel, m * GNN_CLASSES, stream, w.d_slab_scores, m * GNN_CLASSES, w.d_scores + row,
+                                         w.d_scores_rev + row, w.d_scores_mix + row)))
+            return rc;
+        if (c.emb_host) {     // classify_chunks has ordered its back ends before ctx->stream: the slab's rows are complete
+            const int64_t touched = w.ids[a + m - 1] - w.ids[a] + 1;
+            const int64_t r0 = c.need_f ? m : 0;      // the batch's first reverse window
+            if (strand != GNN_STRAND_REVERSE)
+                hipLaunchKernelGGL(emb_fold_kernel, dim3((unsigned)touched), dim3(FOLD_THREADS), 0, stream, w.d_emb, w.d_ids,
+                                   w.d_window_n, w.d_counts, a, m, w.d_emb_sum, w.d_emb_kept);
+            if (strand != GNN_STRAND_FORWARD)
+                hipLaunchKernelGGL(emb_fold_kernel, dim3((unsigned)touched), dim3(FOLD_THREADS), 0, stream, w.d_emb + r0 * HID, w.d_ids,
+                                   w.d_window_n, w.d_counts, a, m, w.d_emb_sum_rev, w.d_emb_kept_rev);
+            GNN_HIP(hipGetLastError());
         }
     }
-    const int64_t n = (int64_t)w.starts.size();
-    const int64_t n_bins = w.bin_off.back();
-    const bool fold = scan && (scan->track || scan->cover);
-    *n_windows_out = 0;
-    if (n_contigs && contig_scores_host) std::memset(contig_scores_host, 0, (size_t)n_contigs * GNN_CLASSES * sizeof(float));
-    if (n_contigs && contig_emb_host) std::memset(contig_emb_host, 0, (size_t)n_contigs * HID * sizeof(float));
-    if (so)
-        for (float* p : {so->contig_fwd, so->contig_rev})
-            if (n_contigs && p) std::memset(p, 0, (size_t)n_contigs * GNN_CLASSES * sizeof(float));
+    return GNN_OK;
+}
+
+// ---- folds and copies back: embedding means, the masked means per contig, the track; everything the host asked for
+static int fold_and_copy_back(const ContigCall& c) {
+    hipStream_t const stream = c.in.ctx->stream;
+    ContigWorkspace& w = c.w;
+    const int strand = c.so.strand;
+    const int64_t n = c.n, n_contigs = c.in.n_contigs, threads = n_contigs * GNN_CLASSES;
+    const size_t window_bytes = (size_t)n * GNN_CLASSES * sizeof(float), contig_bytes = (size_t)threads * sizeof(float);
+    int rc = GNN_OK;
+    if (c.emb_host) {
+        const int64_t cells = n_contigs * HID;
+        float* const d_mean = strand == GNN_STRAND_REVERSE ? w.d_emb_sum_rev : w.d_emb_sum;
+        rc = strand == GNN_STRAND_BOTH
+                 ? launch_1d(emb_both_mean_kernel, cells, stream, w.d_emb_sum, w.d_emb_sum_rev, w.d_emb_kept, n_contigs)
+                 : launch_1d(emb_mean_kernel, cells, stream, d_mean, strand == GNN_STRAND_REVERSE ? w.d_emb_kept_rev : w.d_emb_kept,
+                             n_contigs);
+        if (rc) return rc;
+        GNN_HIP(hipMemcpyAsync(c.emb_host, d_mean, (size_t)cells * sizeof(float), hipMemcpyDeviceToHost, stream));
+    }
+    if ((rc = launch_masked_segment_mean(c.in.ctx, c.d_mode(), w.d_ids, w.d_window_n, w.d_counts, n, n_contigs, w.d_out))) return rc;
+    const struct { float* host; const float* d_win; float* d_mean; float* win_host; } each[2] = {
+        {c.so.contig_fwd, w.d_scores, w.d_out_strand, c.so.window_fwd},
+        {c.so.contig_rev, w.d_scores_rev, w.d_out_strand + threads, c.so.window_rev}};
+    for (const auto& e : each) {
+        if (e.host) {
+            if ((rc = launch_masked_segment_mean(c.in.ctx, e.d_win, w.d_ids, w.d_window_n, w.d_counts, n, n_contigs, e.d_mean))) return rc;
+            GNN_HIP(hipMemcpyAsync(e.host, e.d_mean, contig_bytes, hipMemcpyDeviceToHost, stream));
+        }
+        if (e.win_host) GNN_HIP(hipMemcpyAsync(e.win_host, e.d_win, window_bytes, hipMemcpyDeviceToHost, stream));
+    }
+    w.counts.resize((size_t)n);
+    if (c.contig_scores_host) GNN_HIP(hipMemcpyAsync(c.contig_scores_host, w.d_out, contig_bytes, hipMemcpyDeviceToHost, stream));
+    GNN_HIP(hipMemcpyAsync(w.counts.data(), w.d_counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    if (!c.scan) return GNN_OK;
+    GNN_HIP(hipMemcpyAsync(c.scan->window_scores, c.d_mode(), window_bytes, hipMemcpyDeviceToHost, stream));
+    if (!c.fold) return GNN_OK;
+    const size_t off_bytes = (size_t)(n_contigs + 1) * sizeof(int64_t);
+    GNN_HIP(hipMemcpyAsync(w.d_win_off, w.win_off.data(), off_bytes, hipMemcpyHostToDevice, stream));
+    GNN_HIP(hipMemcpyAsync(w.d_bin_off, w.bin_off.data(), off_bytes, hipMemcpyHostToDevice, stream));
+    const int64_t cells = c.n_bins * GNN_CLASSES;
+    if ((rc = launch_1d(scan_track_kernel, cells, stream, c.d_mode(), w.d_lens, w.d_counts, w.d_win_off, w.d_bin_off, n_contigs, c.n_bins,
+                        (int)c.in.stride, w.d_track, w.d_cover)))
+        return rc;
+    if (c.scan->track) GNN_HIP(hipMemcpyAsync(c.scan->track, w.d_track, (size_t)cells * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (c.scan->cover)
+        GNN_HIP(hipMemcpyAsync(c.scan->cover, w.d_cover, (size_t)c.n_bins * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    return GNN_OK;
+}
+
+static int classify_contigs(const ContigIn& in, const ContigOut& out, const StrandOut& so = {}, const ScanOut* scan = nullptr) {
+    const char* const fn = scan ? "gnn_scan_contigs" : "gnn_classify_contigs";
+    ContigWorkspace* wp = nullptr;
+    int rc = contig_begin(in, fn, scan || (out.n_windows && (in.n_contigs == 0 || out.scores)), &wp);
+    if (rc) return rc;
+    // ---- plan: the window table, the outputs zeroed, the caller's capacities
+    if ((rc = plan_windows(in, *wp, scan != nullptr, 0))) return rc;
+    const bool need_f = so.strand != GNN_STRAND_REVERSE || so.contig_fwd || so.window_fwd;
+    const bool need_r = so.strand != GNN_STRAND_FORWARD || so.contig_rev || so.window_rev;
+    const int64_t n = (int64_t)wp->starts.size(), ns = (need_f ? 1 : 0) + (need_r ? 1 : 0);
+    // a slab is what d_bases holds: 4 launches of windows, of one strand or - forward windows, then reverse windows - of both
+    const int64_t slab = std::min<int64_t>(n, std::max<int64_t>(4 * std::max<int64_t>(in.ctx->chunk_fused, 1) / ns, 1));
+    const ContigCall c{in, *wp, so, scan, out.scores, in.n_contigs > 0 ? out.emb : nullptr, n, scan ? wp->bin_off.back() : 0,
+                       need_f, need_r, ns, slab, scan && (scan->track || scan->cover)};
+    if (out.n_windows) *out.n_windows = 0;
+    for (float* p : {out.scores, so.contig_fwd, so.contig_rev})
+        if (in.n_contigs && p) std::memset(p, 0, (size_t)in.n_contigs * GNN_CLASSES * sizeof(float));
+    if (c.emb_host) std::memset(c.emb_host, 0, (size_t)in.n_contigs * HID * sizeof(float));
     if (n == 0) return GNN_OK;
     if (scan) {
         if (!scan->window_scores || scan->windows_capacity < n) {
             set_error("window_scores_host holds " + std::to_string(scan->windows_capacity) + " windows, the scan has " + std::to_string(n));
             return GNN_ERR_ARG;
         }
-        if (fold && scan->bins_capacity < n_bins) {
-            set_error("track_host / cover_host hold " + std::to_string(scan->bins_capacity) + " bins, the scan has " + std::to_string(n_bins));
+        if (c.fold && scan->bins_capacity < c.n_bins) {
+            set_error("track_host / cover_host hold " + std::to_string(scan->bins_capacity) + " bins, the scan has " + std::to_string(c.n_bins));
             return GNN_ERR_ARG;
         }
-    } else if (!window_ids_host || ids_capacity < n) {
-        set_error("window_ids_host holds " + std::to_string(ids_capacity) + " entries, " + std::to_string(n) + " candidate windows");
+    } else if (!out.window_ids || out.ids_capacity < n) {
+        set_error("window_ids_host holds " + std::to_string(out.ids_capacity) + " entries, " + std::to_string(n) + " candidate windows");
         return GNN_ERR_ARG;
     }
-
-    // ---- device buffers
-    int rc = GNN_OK;
-    if (w.span_cap() < (size_t)n) {
-        GNN_HIP(hipStreamSynchronize(ctx->stream));
-        reset_all(w.d_starts, w.d_ids, w.d_lens, w.d_window_n, w.d_counts, w.d_scores);
-        if (!rc) rc = reserve_roomy(w.d_starts, (size_t)n);
-        if (!rc) rc = reserve_roomy(w.d_ids, (size_t)n);
-        if (!rc) rc = reserve_roomy(w.d_lens, (size_t)n);
-        if (!rc) rc = reserve_roomy(w.d_window_n, (size_t)n);
-        if (!rc) rc = reserve_roomy(w.d_counts, (size_t)n);
-        if (!rc) rc = reserve_roomy(w.d_scores, (size_t)n * GNN_CLASSES);
-        if (rc) return rc;
-    }
-    if (need_r && w.strand_cap() < (size_t)n) {      // 24 B per window more, and only for a caller of the *_strand entry points
-        GNN_HIP(hipStreamSynchronize(ctx->stream));
-        reset_all(w.d_scores_rev, w.d_scores_mix);
-        if (!rc) rc = reserve_roomy(w.d_scores_rev, (size_t)n * GNN_CLASSES);
-        if (!rc) rc = reserve_roomy(w.d_scores_mix, (size_t)n * GNN_CLASSES);
-        if (rc) return rc;
-    }
-    // a slab is what d_bases holds: 4 launches of windows, of one strand or - forward windows, then reverse windows - of both
-    const int64_t slab = std::min<int64_t>(n, std::max<int64_t>(4 * std::max<int64_t>(ctx->chunk_fused, 1) / ns, 1));
-    if ((rc = reserve_roomy(w.d_bases, (size_t)(slab * ns) * W))) return rc;
-    if ((rc = reserve_roomy(w.d_out, (size_t)n_contigs * GNN_CLASSES))) return rc;
-    if (ns == 2 && (rc = reserve_roomy(w.d_slab_scores, (size_t)(slab * 2) * GNN_CLASSES))) return rc;
-    if (so && (so->contig_fwd || so->contig_rev) && (rc = reserve_roomy(w.d_out_strand, (size_t)n_contigs * 2 * GNN_CLASSES))) return rc;
-    if (fold) {        // 16 B per contig and 16 B per bin (hipFree of a buffer that grows waits for the kernels that read it)
-        if (w.off_cap() < (size_t)n_contigs + 1) {
-            reset_all(w.d_win_off, w.d_bin_off);
-            if (!rc) rc = reserve_roomy(w.d_win_off, (size_t)n_contigs + 1);
-            if (!rc) rc = reserve_roomy(w.d_bin_off, (size_t)n_contigs + 1);
-        }
-        if (!rc && w.bin_cap() < (size_t)n_bins) {
-            reset_all(w.d_track, w.d_cover);
-            if (!rc) rc = reserve_roomy(w.d_track, (size_t)n_bins * GNN_CLASSES);
-            if (!rc) rc = reserve_roomy(w.d_cover, (size_t)n_bins);
-        }
-        if (rc) return rc;
-    }
-    if (contig_emb_host) {
-        // a slab's window embeddings (2 KB each) and the per-contig sums: never every window's row (10 M windows would be 20 GB)
-        const bool rev_sum = strand != GNN_STRAND_FORWARD;
-        if (w.d_emb.capacity() < (size_t)(slab * ns) * HID || w.d_emb_sum.capacity() < (size_t)n_contigs * HID ||
-            w.d_emb_kept.capacity() < (size_t)n_contigs ||
-            (rev_sum && (w.d_emb_sum_rev.capacity() < (size_t)n_contigs * HID || w.d_emb_kept_rev.capacity() < (size_t)n_contigs)))
-            GNN_HIP(hipStreamSynchronize(ctx->stream));
-        if ((rc = reserve_roomy(w.d_emb, (size_t)(slab * ns) * HID))) return rc;
-        if (rev_sum) {       // the reverse strand folds into a sum of its own: two independent sums, whatever the slab size
-            if ((rc = reserve_roomy(w.d_emb_sum_rev, (size_t)n_contigs * HID))) return rc;
-            if ((rc = reserve_roomy(w.d_emb_kept_rev, (size_t)n_contigs))) return rc;
-            GNN_HIP(hipMemsetAsync(w.d_emb_sum_rev, 0, (size_t)n_contigs * HID * sizeof(float), ctx->stream));
-            GNN_HIP(hipMemsetAsync(w.d_emb_kept_rev, 0, (size_t)n_contigs * sizeof(int32_t), ctx->stream));
-        }
-        if ((rc = reserve_roomy(w.d_emb_sum, (size_t)n_contigs * HID))) return rc;
-        if ((rc = reserve_roomy(w.d_emb_kept, (size_t)n_contigs))) return rc;
-        GNN_HIP(hipMemsetAsync(w.d_emb_sum, 0, (size_t)n_contigs * HID * sizeof(float), ctx->stream));
-        GNN_HIP(hipMemsetAsync(w.d_emb_kept, 0, (size_t)n_contigs * sizeof(int32_t), ctx->stream));
-    }
-    const uint8_t* seq_dev = seq;
-    int64_t n_pieces = 0;
-    if (seq_on_host) {
-        if ((rc = reserve_roomy(w.seq, (size_t)seq_bytes))) return rc;
-        seq_dev = w.seq;
-        if (!w.copy_stream) GNN_HIP(hipStreamCreateWithFlags(&w.copy_stream, hipStreamNonBlocking));
-        n_pieces = (seq_bytes + PIECE - 1) / PIECE;
-        while ((int64_t)w.piece_done.size() < n_pieces) {
-            hipEvent_t e = nullptr;
-            GNN_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            w.piece_done.push_back(e);
-        }
-        // the previous call's kernels may still read w.seq: order the copies behind them
-        hipEvent_t& first = w.piece_done[0];
-        GNN_HIP(hipEventRecord(first, ctx->stream));
-        GNN_HIP(hipStreamWaitEvent(w.copy_stream, first, 0));
-    }
-    GNN_HIP(hipMemcpyAsync(w.d_starts, w.starts.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(w.d_lens, w.lens.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(w.d_ids, w.ids.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(w.d_window_n, w.window_n.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-
-    // ---- slabs of windows: upload what they read (copy stream), count N, materialise, classify (ctx stream)
-    int64_t uploaded = 0;       // pieces issued so far
-    for (int64_t a = 0; a < n; a += slab) {
-        const int64_t m = std::min(slab, n - a);
-        if (seq_on_host) {
-            const int64_t need = w.starts[a + m - 1] + w.lens[a + m - 1];       // spans are in buffer order
-            const int64_t upto = std::min<int64_t>(n_pieces, (need + PIECE - 1) / PIECE);
-            for (; uploaded < upto; ++uploaded) {
-                const int64_t off = uploaded * PIECE, len = std::min(PIECE, seq_bytes - off);
-                GNN_HIP(hipMemcpyAsync(w.seq + off, seq + off, (size_t)len, hipMemcpyHostToDevice, w.copy_stream));
-                GNN_HIP(hipEventRecord(w.piece_done[uploaded], w.copy_stream));
-            }
-            if (upto > 0) GNN_HIP(hipStreamWaitEvent(ctx->stream, w.piece_done[upto - 1], 0));
-        }
-        if ((rc = launch_span_count(ctx, seq_dev, w.d_starts + a, w.d_lens + a, m, 'N', w.d_counts + a))) return rc;
-        const int64_t r0 = need_f ? m : 0;      // the batch's first reverse window (the N count above served both strands)
-        if (need_f && (rc = launch_materialize(ctx, seq_dev, w.d_starts + a, w.d_lens + a, m, w.d_bases))) return rc;
-        if (need_r && (rc = launch_revcomp(ctx, seq_dev, w.d_starts + a, w.d_lens + a, m, w.d_bases + r0 * W))) return rc;
-        float* const batch_scores = ns == 2 ? w.d_slab_scores.get() : (need_f ? w.d_scores : w.d_scores_rev) + a * GNN_CLASSES;
-        if ((rc = classify_chunks(ctx, w.d_bases, m * ns, precision, batch_scores, false, contig_emb_host ? w.d_emb.get() : nullptr,
-                                  GNN_EMB_F32)))
-            return rc;
-        if (ns == 2) {
-            const int64_t cells = m * GNN_CLASSES;
-            hipLaunchKernelGGL(strand_split_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, w.d_slab_scores,
-                               cells, w.d_scores + a * GNN_CLASSES, w.d_scores_rev + a * GNN_CLASSES, w.d_scores_mix + a * GNN_CLASSES);
-            GNN_HIP(hipGetLastError());
-        }
-        if (contig_emb_host) {     // classify_chunks has ordered its back ends before ctx->stream: the slab's rows are complete
-            const int64_t touched = w.ids[a + m - 1] - w.ids[a] + 1;
-            if (strand != GNN_STRAND_REVERSE)
-                hipLaunchKernelGGL(emb_fold_kernel, dim3((unsigned)touched), dim3(FOLD_THREADS), 0, ctx->stream, w.d_emb, w.d_ids,
-                                   w.d_window_n, w.d_counts, a, m, w.d_emb_sum, w.d_emb_kept);
-            if (strand != GNN_STRAND_FORWARD)
-                hipLaunchKernelGGL(emb_fold_kernel, dim3((unsigned)touched), dim3(FOLD_THREADS), 0, ctx->stream, w.d_emb + r0 * HID, w.d_ids,
-                                   w.d_window_n, w.d_counts, a, m, w.d_emb_sum_rev, w.d_emb_kept_rev);
-            GNN_HIP(hipGetLastError());
-        }
-    }
-    // the window scores of the mode: what the contig mean, the track and window_scores_host carry
-    const float* const d_mode = strand == GNN_STRAND_BOTH ? w.d_scores_mix : (strand == GNN_STRAND_REVERSE ? w.d_scores_rev : w.d_scores);
-    if (contig_emb_host) {
-        const int64_t cells = n_contigs * HID;
-        float* const d_mean = strand == GNN_STRAND_REVERSE ? w.d_emb_sum_rev : w.d_emb_sum;
-        if (strand == GNN_STRAND_BOTH)
-            hipLaunchKernelGGL(emb_both_mean_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, w.d_emb_sum,
-                               w.d_emb_sum_rev, w.d_emb_kept, n_contigs);
-        else
-            hipLaunchKernelGGL(emb_mean_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, d_mean,
-                               strand == GNN_STRAND_REVERSE ? w.d_emb_kept_rev : w.d_emb_kept, n_contigs);
-        GNN_HIP(hipGetLastError());
-        GNN_HIP(hipMemcpyAsync(contig_emb_host, d_mean, (size_t)cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    const int64_t threads = n_contigs * GNN_CLASSES;
-    hipLaunchKernelGGL(masked_segment_mean_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream,
-                       d_mode, w.d_ids, w.d_window_n, w.d_counts, n, n_contigs, w.d_out);
-    GNN_HIP(hipGetLastError());
-    if (so) {
-        const struct { float* host; const float* d_win; float* d_mean; float* win_host; } each[2] = {
-            {so->contig_fwd, w.d_scores, w.d_out_strand, so->window_fwd},
-            {so->contig_rev, w.d_scores_rev, w.d_out_strand + threads, so->window_rev}};
-        for (const auto& e : each) {
-            if (e.host) {
-                hipLaunchKernelGGL(masked_segment_mean_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream,
-                                   e.d_win, w.d_ids, w.d_window_n, w.d_counts, n, n_contigs, e.d_mean);
-                GNN_HIP(hipGetLastError());
-                GNN_HIP(hipMemcpyAsync(e.host, e.d_mean, (size_t)threads * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-            }
-            if (e.win_host)
-                GNN_HIP(hipMemcpyAsync(e.win_host, e.d_win, (size_t)n * GNN_CLASSES * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        }
-    }
-    w.counts.resize((size_t)n);
-    if (contig_scores_host)
-        GNN_HIP(hipMemcpyAsync(contig_scores_host, w.d_out, (size_t)threads * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(w.counts.data(), w.d_counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (scan) {
-        GNN_HIP(hipMemcpyAsync(scan->window_scores, d_mode, (size_t)n * GNN_CLASSES * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        if (fold) {
-            const size_t off_bytes = (size_t)(n_contigs + 1) * sizeof(int64_t);
-            GNN_HIP(hipMemcpyAsync(w.d_win_off, w.win_off.data(), off_bytes, hipMemcpyHostToDevice, ctx->stream));
-            GNN_HIP(hipMemcpyAsync(w.d_bin_off, w.bin_off.data(), off_bytes, hipMemcpyHostToDevice, ctx->stream));
-            const int64_t cells = n_bins * GNN_CLASSES;
-            hipLaunchKernelGGL(scan_track_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, d_mode, w.d_lens,
-                               w.d_counts, w.d_win_off, w.d_bin_off, n_contigs, n_bins, (int)stride, w.d_track, w.d_cover);
-            GNN_HIP(hipGetLastError());
-            if (scan->track)
-                GNN_HIP(hipMemcpyAsync(scan->track, w.d_track, (size_t)cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-            if (scan->cover)
-                GNN_HIP(hipMemcpyAsync(scan->cover, w.d_cover, (size_t)n_bins * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        }
-    }
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
-    int64_t kept = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        const bool keep = w.window_n[i] == 0 || w.counts[i] <= MAX_N;
-        if (scan) {
-            if (scan->window_kept) scan->window_kept[i] = keep ? 1 : 0;
-            kept += keep;
-        } else if (keep) {
-            window_ids_host[kept++] = w.ids[i];
-        }
-    }
-    *n_windows_out = kept;
+    // ---- reserve, pass, folds, copies back
+    SeqFeed feed;
+    if ((rc = upload_span_table(in.ctx, c.w))) return rc;
+    if ((rc = reserve_buffers(c))) return rc;
+    if ((rc = feed.begin(in, c.w))) return rc;
+    if ((rc = run_slabs(c, feed))) return rc;
+    if ((rc = fold_and_copy_back(c))) return rc;
+    GNN_HIP(hipStreamSynchronize(in.ctx->stream));
+    const int64_t kept = kept_windows(c.w, scan ? scan->window_kept : nullptr, scan ? nullptr : out.window_ids);
+    if (out.n_windows) *out.n_windows = kept;
     return GNN_OK;
 }
 
@@ -453,8 +501,8 @@ extern "C" int gnn_classify_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on
                                     const int64_t* offsets_host, int64_t n_contigs, int single_window, int precision,
                                     float* contig_scores_host, int64_t* window_ids_host, int64_t ids_capacity,
                                     int64_t* n_windows_out) {
-    return classify_contigs(ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision, contig_scores_host,
-                            window_ids_host, ids_capacity, n_windows_out, nullptr);
+    return classify_contigs({ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision, W},
+                            {contig_scores_host, window_ids_host, ids_capacity, n_windows_out});
 }
 
 extern "C" int gnn_classify_contigs_embed(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes,
@@ -465,13 +513,9 @@ extern "C" int gnn_classify_contigs_embed(gnn_ctx* ctx, const uint8_t* seq, int 
         set_error("bad argument to gnn_classify_contigs_embed: contig_emb_host is NULL");
         return GNN_ERR_ARG;
     }
-    if (precision == GNN_PREC_F16C6) {
-        set_error("gnn_classify_contigs_embed: GNN_PREC_F16C6 has no embedding path (the frozen mode's dense head runs on the matrix "
-                  "pipe and is outside the tolerance); use f16x3tc, f16x3tk, f16x3, bf16x3 or f32");
-        return GNN_ERR_ARG;
-    }
-    return classify_contigs(ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision, contig_scores_host,
-                            window_ids_host, ids_capacity, n_windows_out, n_contigs > 0 ? contig_emb_host : nullptr);
+    if (int rc = check_embed_precision(precision, "gnn_classify_contigs_embed")) return rc;
+    return classify_contigs({ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision, W},
+                            {contig_scores_host, window_ids_host, ids_capacity, n_windows_out, contig_emb_host});
 }
 
 static int check_stride(int stride, const char* fn) {
@@ -488,27 +532,14 @@ extern "C" int gnn_scan_plan(const int64_t* offsets_host, int64_t n_contigs, int
         return GNN_ERR_ARG;
     }
     if (int rc = check_stride(stride, "gnn_scan_plan")) return rc;
-    for (int64_t c = 0; c < n_contigs; ++c)
-        if (offsets_host[c + 1] < offsets_host[c]) {
-            set_error("contig offsets are not non-decreasing");
-            return GNN_ERR_ARG;
-        }
-    int64_t n = 0, bins = 0;
-    if (win_offsets_or_null) win_offsets_or_null[0] = 0;
-    if (bin_offsets_or_null) bin_offsets_or_null[0] = 0;
-    for (int64_t c = 0; c < n_contigs; ++c) {
-        const int64_t len = offsets_host[c + 1] - offsets_host[c];
-        for_each_window(len, stride, single_window, [&](int64_t k, int64_t l) {
-            if (starts_or_null) starts_or_null[n] = k * stride;
-            if (lens_or_null) lens_or_null[n] = (int32_t)l;
-            ++n;
-        });
-        bins += (len + stride - 1) / stride;
-        if (win_offsets_or_null) win_offsets_or_null[c + 1] = n;
-        if (bin_offsets_or_null) bin_offsets_or_null[c + 1] = bins;
-    }
-    *n_windows_out = n;
-    *n_bins_out = bins;
+    WindowWalk walk{win_offsets_or_null, bin_offsets_or_null};
+    const int rc = walk_windows(offsets_host, n_contigs, stride, single_window, walk, [&](int64_t, int64_t k, int64_t l) {
+        if (starts_or_null) starts_or_null[walk.windows] = k * stride;
+        if (lens_or_null) lens_or_null[walk.windows] = (int32_t)l;
+    });
+    if (rc) return rc;
+    *n_windows_out = walk.windows;
+    *n_bins_out = walk.bins;
     return GNN_OK;
 }
 
@@ -519,9 +550,8 @@ extern "C" int gnn_scan_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_hos
     if (int rc = check_stride(stride, "gnn_scan_contigs")) return rc;
     const ScanOut scan{window_scores_host, window_kept_host_or_null, windows_capacity, track_host_or_null, cover_host_or_null,
                        bins_capacity};
-    int64_t kept = 0;
-    return classify_contigs(ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision,
-                            contig_scores_host_or_null, nullptr, 0, &kept, nullptr, stride, &scan);
+    return classify_contigs({ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision, stride},
+                            {contig_scores_host_or_null}, StrandOut{GNN_STRAND_FORWARD}, &scan);
 }
 
 static int check_strand(int strand, const char* fn) {
@@ -536,15 +566,11 @@ extern "C" int gnn_classify_contigs_strand(gnn_ctx* ctx, const uint8_t* seq, int
                                            int64_t* n_windows_out, float* contig_emb_host_or_null, int strand,
                                            float* contig_scores_fwd_host_or_null, float* contig_scores_rev_host_or_null) {
     if (int rc = check_strand(strand, "gnn_classify_contigs_strand")) return rc;
-    if (contig_emb_host_or_null && precision == GNN_PREC_F16C6) {
-        set_error("gnn_classify_contigs_strand: GNN_PREC_F16C6 has no embedding path (the frozen mode's dense head runs on the matrix "
-                  "pipe and is outside the tolerance); use f16x3tc, f16x3tk, f16x3, bf16x3 or f32");
-        return GNN_ERR_ARG;
-    }
-    const StrandOut so{strand, contig_scores_fwd_host_or_null, contig_scores_rev_host_or_null, nullptr, nullptr};
-    return classify_contigs(ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision, contig_scores_host,
-                            window_ids_host, ids_capacity, n_windows_out, n_contigs > 0 ? contig_emb_host_or_null : nullptr, W, nullptr,
-                            &so);
+    if (contig_emb_host_or_null)
+        if (int rc = check_embed_precision(precision, "gnn_classify_contigs_strand")) return rc;
+    return classify_contigs({ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision, W},
+                            {contig_scores_host, window_ids_host, ids_capacity, n_windows_out, contig_emb_host_or_null},
+                            StrandOut{strand, contig_scores_fwd_host_or_null, contig_scores_rev_host_or_null});
 }
 
 extern "C" int gnn_scan_contigs_strand(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes, const int64_t* offsets_host,
@@ -556,8 +582,8 @@ extern "C" int gnn_scan_contigs_strand(gnn_ctx* ctx, const uint8_t* seq, int seq
     if (int rc = check_strand(strand, "gnn_scan_contigs_strand")) return rc;
     const ScanOut scan{window_scores_host, window_kept_host_or_null, windows_capacity, track_host_or_null, cover_host_or_null,
                        bins_capacity};
-    const StrandOut so{strand, nullptr, nullptr, window_scores_fwd_host_or_null, window_scores_rev_host_or_null};
-    int64_t kept = 0;
-    return classify_contigs(ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision,
-                            contig_scores_host_or_null, nullptr, 0, &kept, nullptr, stride, &scan, &so);
+    StrandOut so{strand};
+    so.window_fwd = window_scores_fwd_host_or_null, so.window_rev = window_scores_rev_host_or_null;
+    return classify_contigs({ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision, stride},
+                            {contig_scores_host_or_null}, so, &scan);
 }

@@ -17,8 +17,8 @@
 // The base windows go first, in the slabs of gnn_classify_contigs; the contig scores are their masked mean.  Then the pairs, in
 // slabs of at most what d_bases holds (4 launches): a slab is materialised by occlude_kernel, scored by classify_chunks, differenced
 // in place by occlusion_delta_kernel and copied to delta_host.  Device memory does not grow with P: 6000 B + 12 B per pair of ONE
-// slab, the per-window tables of gnn_classify_contigs and 8 B per window of blk_offsets.  The sequence goes up in one ordered copy on
-// the ctx stream (an occlusion call is at least two passes over it: there is nothing worth hiding the upload behind).
+// slab, the per-window tables of gnn_classify_contigs and 8 B per window of blk_offsets.  Entry, plan, span table, sequence feed and
+// the base windows' slabs are the steps of gnn_classify_contigs (gnn_common.h), run forward-only.
 #include <cstring>
 
 #include "gnn_common.h"
@@ -59,37 +59,24 @@ extern "C" int gnn_occlusion_plan(const int64_t* offsets_host, int64_t n_contigs
         return GNN_ERR_ARG;
     }
     if (int rc = check_block(block, "gnn_occlusion_plan")) return rc;
-    for (int64_t c = 0; c < n_contigs; ++c)
-        if (offsets_host[c + 1] < offsets_host[c]) {
-            set_error("contig offsets are not non-decreasing");
-            return GNN_ERR_ARG;
-        }
-    int64_t n = 0, pairs = 0;
-    if (win_offsets_or_null) win_offsets_or_null[0] = 0;
+    int64_t pairs = 0;
+    WindowWalk walk{win_offsets_or_null};
+    const int rc = walk_windows(offsets_host, n_contigs, W, single_window, walk, [&](int64_t, int64_t k, int64_t l) {
+        if (starts_or_null) starts_or_null[walk.windows] = k * W;
+        if (lens_or_null) lens_or_null[walk.windows] = (int32_t)l;
+        pairs += (l + block - 1) / block;
+        if (blk_offsets_or_null) blk_offsets_or_null[walk.windows + 1] = pairs;
+    });
+    if (rc) return rc;
     if (blk_offsets_or_null) blk_offsets_or_null[0] = 0;
-    for (int64_t c = 0; c < n_contigs; ++c) {
-        for_each_window(offsets_host[c + 1] - offsets_host[c], W, single_window, [&](int64_t k, int64_t l) {
-            if (starts_or_null) starts_or_null[n] = k * W;
-            if (lens_or_null) lens_or_null[n] = (int32_t)l;
-            pairs += (l + block - 1) / block;
-            ++n;
-            if (blk_offsets_or_null) blk_offsets_or_null[n] = pairs;
-        });
-        if (win_offsets_or_null) win_offsets_or_null[c + 1] = n;
-    }
-    *n_windows_out = n;
+    *n_windows_out = walk.windows;
     *n_pairs_out = pairs;
     return GNN_OK;
 }
 
 extern "C" int gnn_occlude_spans_dev(gnn_ctx* ctx, const uint8_t* seq_dev, const int64_t* starts_host, const int32_t* lens_host,
                                      const int32_t* lo_host, const int32_t* hi_host, int64_t n, uint8_t* bases_dev_out) {
-    if (!ctx) {
-        set_error("ctx is NULL");
-        return GNN_ERR_ARG;
-    }
-    GNN_HIP(hipSetDevice(ctx->device));
-    if (int rc = finish_pending(ctx)) return rc;
+    if (int rc = check_ctx(ctx)) return rc;
     if (n < 0 || (n > 0 && (!seq_dev || !starts_host || !lens_host || !lo_host || !hi_host || !bases_dev_out))) {
         set_error("bad argument to gnn_occlude_spans_dev");
         return GNN_ERR_ARG;
@@ -135,40 +122,14 @@ extern "C" int gnn_occlude_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_
                                    int64_t pairs_capacity, float* contig_scores_host_or_null) {
     const char* const fn = "gnn_occlude_contigs";
     if (int rc = check_block(block, fn)) return rc;
-    if (!ctx) {
-        set_error("ctx is NULL");
-        return GNN_ERR_ARG;
-    }
-    GNN_HIP(hipSetDevice(ctx->device));
-    if (int rc = finish_pending(ctx)) return rc;
-    if (n_contigs < 0 || seq_bytes < 0 || !offsets_host || (seq_bytes > 0 && !seq)) {
-        set_error(std::string("bad argument to ") + fn);
-        return GNN_ERR_ARG;
-    }
-    if (offsets_host[0] < 0 || offsets_host[n_contigs] > seq_bytes) {
-        set_error("contig offsets outside the sequence buffer");
-        return GNN_ERR_ARG;
-    }
-    if (!ctx->contig_ws) ctx->contig_ws = new ContigWorkspace();
-    ContigWorkspace& w = *ctx->contig_ws;
+    const ContigIn in{ctx, seq, seq_on_host, seq_bytes, offsets_host, n_contigs, single_window, precision, W};
+    ContigWorkspace* wp = nullptr;
+    int rc = contig_begin(in, fn, true, &wp);
+    if (rc) return rc;
+    ContigWorkspace& w = *wp;
 
-    // ---- windows (the table of gnn_classify_contigs) and the CSR of their blocks
-    w.starts.clear(), w.lens.clear(), w.ids.clear(), w.window_n.clear();
-    w.blk_off.assign(1, 0);
-    for (int64_t c = 0; c < n_contigs; ++c) {
-        const int64_t a = offsets_host[c], b = offsets_host[c + 1];
-        if (b < a) {
-            set_error("contig offsets are not non-decreasing");
-            return GNN_ERR_ARG;
-        }
-        for_each_window(b - a, W, single_window, [&](int64_t k, int64_t l) {
-            w.starts.push_back(a + k * W);
-            w.lens.push_back((int32_t)l);
-            w.ids.push_back(c);
-            w.window_n.push_back((int32_t)k);
-            w.blk_off.push_back(w.blk_off.back() + (l + block - 1) / block);
-        });
-    }
+    // ---- plan: the windows (the table of gnn_classify_contigs) and the CSR of their blocks
+    if ((rc = plan_windows(in, w, false, block))) return rc;
     const int64_t n = (int64_t)w.starts.size();
     const int64_t n_pairs = w.blk_off.back();
     if (n_contigs && contig_scores_host_or_null) std::memset(contig_scores_host_or_null, 0, (size_t)n_contigs * GNN_CLASSES * sizeof(float));
@@ -182,49 +143,24 @@ extern "C" int gnn_occlude_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_
         return GNN_ERR_ARG;
     }
 
-    // ---- device buffers: the span table of gnn_classify_contigs, blk_offsets, and one slab of windows / of pairs
-    int rc = GNN_OK;
-    if (w.span_cap() < (size_t)n) {
-        GNN_HIP(hipStreamSynchronize(ctx->stream));
-        reset_all(w.d_starts, w.d_ids, w.d_lens, w.d_window_n, w.d_counts, w.d_scores);
-        if (!rc) rc = reserve_roomy(w.d_starts, (size_t)n);
-        if (!rc) rc = reserve_roomy(w.d_ids, (size_t)n);
-        if (!rc) rc = reserve_roomy(w.d_lens, (size_t)n);
-        if (!rc) rc = reserve_roomy(w.d_window_n, (size_t)n);
-        if (!rc) rc = reserve_roomy(w.d_counts, (size_t)n);
-        if (!rc) rc = reserve_roomy(w.d_scores, (size_t)n * GNN_CLASSES);
-        if (rc) return rc;
-    }
+    // ---- reserve: the span table, blk_offsets, one slab of windows / of pairs, the sequence
+    if ((rc = upload_span_table(ctx, w))) return rc;
     const int64_t launches4 = std::max<int64_t>(4 * std::max<int64_t>(ctx->chunk_fused, 1), 1);     // what d_bases holds today
     const int64_t slab_w = std::min(n, launches4), slab_p = std::min(n_pairs, launches4);
     if (w.d_blk_off.capacity() < (size_t)n + 1 || w.d_bases.capacity() < (size_t)std::max(slab_w, slab_p) * W ||
-        w.d_occ.capacity() < (size_t)slab_p * GNN_CLASSES || w.d_out.capacity() < (size_t)n_contigs * GNN_CLASSES ||
-        (seq_on_host && w.seq.capacity() < (size_t)seq_bytes))
+        w.d_occ.capacity() < (size_t)slab_p * GNN_CLASSES || w.d_out.capacity() < (size_t)n_contigs * GNN_CLASSES)
         GNN_HIP(hipStreamSynchronize(ctx->stream));      // a buffer that grows is freed first: nothing may still read it
     if ((rc = reserve_roomy(w.d_blk_off, (size_t)n + 1))) return rc;
     if ((rc = reserve_roomy(w.d_bases, (size_t)std::max(slab_w, slab_p) * W))) return rc;
     if ((rc = reserve_roomy(w.d_occ, (size_t)slab_p * GNN_CLASSES))) return rc;
     if ((rc = reserve_roomy(w.d_out, (size_t)n_contigs * GNN_CLASSES))) return rc;
-    const uint8_t* seq_dev = seq;
-    if (seq_on_host) {
-        if ((rc = reserve_roomy(w.seq, (size_t)seq_bytes))) return rc;
-        seq_dev = w.seq;
-        if (w.copy_stream) GNN_HIP(hipStreamSynchronize(w.copy_stream));      // an earlier call's piece uploads into w.seq are over
-        GNN_HIP(hipMemcpyAsync(w.seq, seq, (size_t)seq_bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    GNN_HIP(hipMemcpyAsync(w.d_starts, w.starts.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(w.d_lens, w.lens.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(w.d_ids, w.ids.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(w.d_window_n, w.window_n.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    SeqFeed feed;
+    if ((rc = feed.begin(in, w))) return rc;
     GNN_HIP(hipMemcpyAsync(w.d_blk_off, w.blk_off.data(), (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
 
-    // ---- the base windows: N counts, forward windows, scores; the contig scores are their masked mean
-    for (int64_t a = 0; a < n; a += slab_w) {
-        const int64_t m = std::min(slab_w, n - a);
-        if ((rc = launch_span_count(ctx, seq_dev, w.d_starts + a, w.d_lens + a, m, 'N', w.d_counts + a))) return rc;
-        if ((rc = launch_materialize(ctx, seq_dev, w.d_starts + a, w.d_lens + a, m, w.d_bases))) return rc;
-        if ((rc = classify_chunks(ctx, w.d_bases, m, precision, w.d_scores + a * GNN_CLASSES))) return rc;
-    }
+    // ---- the base windows, forward only: N counts, windows, scores; the contig scores are their masked mean
+    for (int64_t a = 0; a < n; a += slab_w)
+        if ((rc = slab_pass(in, w, feed, a, std::min(slab_w, n - a), true, false, w.d_scores + a * GNN_CLASSES, nullptr))) return rc;
     if ((rc = launch_masked_segment_mean(ctx, w.d_scores, w.d_ids, w.d_window_n, w.d_counts, n, n_contigs, w.d_out))) return rc;
     w.counts.resize((size_t)n);
     if (contig_scores_host_or_null)
@@ -233,19 +169,18 @@ extern "C" int gnn_occlude_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_
     GNN_HIP(hipMemcpyAsync(w.counts.data(), w.d_counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     GNN_HIP(hipMemcpyAsync(window_scores_host, w.d_scores, (size_t)n * GNN_CLASSES * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
 
-    // ---- the pairs, a slab at a time: occluded windows, their scores, base - occ in place, out
+    // ---- the pairs, a slab at a time: occluded windows, their scores, base - occ in place, out.  A pair reads the bytes of its
+    // window and nothing else, and the base pass's last slab named the last byte any window reads (spans are in buffer order): the
+    // feed has nothing left to upload, and the ctx stream already waits for all of it.
     for (int64_t p0 = 0; p0 < n_pairs; p0 += slab_p) {
         const int64_t m = std::min(slab_p, n_pairs - p0);
-        if ((rc = launch_occlude(ctx, seq_dev, w.d_starts, w.d_lens, w.d_blk_off, n, p0, block, nullptr, nullptr, m, w.d_bases))) return rc;
+        if ((rc = launch_occlude(ctx, feed.dev(), w.d_starts, w.d_lens, w.d_blk_off, n, p0, block, nullptr, nullptr, m, w.d_bases))) return rc;
         if ((rc = classify_chunks(ctx, w.d_bases, m, precision, w.d_occ))) return rc;
-        const int64_t cells = m * GNN_CLASSES;
-        hipLaunchKernelGGL(occlusion_delta_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, w.d_scores,
-                           w.d_blk_off, n, p0, m, w.d_occ);
-        GNN_HIP(hipGetLastError());
-        GNN_HIP(hipMemcpyAsync(delta_host + p0 * GNN_CLASSES, w.d_occ, (size_t)cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = launch_1d(occlusion_delta_kernel, m * GNN_CLASSES, ctx->stream, w.d_scores, w.d_blk_off, n, p0, m, w.d_occ))) return rc;
+        GNN_HIP(hipMemcpyAsync(delta_host + p0 * GNN_CLASSES, w.d_occ, (size_t)m * GNN_CLASSES * sizeof(float), hipMemcpyDeviceToHost,
+                               ctx->stream));
     }
     GNN_HIP(hipStreamSynchronize(ctx->stream));
-    if (window_kept_host_or_null)
-        for (int64_t i = 0; i < n; ++i) window_kept_host_or_null[i] = (w.window_n[i] == 0 || w.counts[i] <= MAX_N) ? 1 : 0;
+    kept_windows(w, window_kept_host_or_null, nullptr);
     return GNN_OK;
 }

@@ -240,6 +240,92 @@ class NNEngine:
                                          scores.ctypes.data, C.byref(t)))
         return scores, arrays
 
+    # -- packed contigs: what every contig method is given ---------------------------------
+    @staticmethod
+    def _offsets(offsets) -> np.ndarray:
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError("offsets must hold n_contigs + 1 byte offsets")
+        return offsets
+
+    @classmethod
+    def _packed(cls, seq, offsets):
+        """(packed bytes, offsets) as the contig entry points take them: (ptr, on_host, bytes, offsets, n_contigs).  ``seq`` is a
+        host array (any dtype / layout numpy converts to contiguous uint8) or the device address of byte 0; the returned ``keep``
+        owns the bytes ``ptr`` points at."""
+        offsets = cls._offsets(offsets)
+        if isinstance(seq, np.ndarray):
+            keep = np.ascontiguousarray(seq, dtype=np.uint8)
+            return (keep.ctypes.data, 1, keep.nbytes, offsets, len(offsets) - 1), keep
+        return (seq, 0, int(offsets[-1]), offsets, len(offsets) - 1), None
+
+    @staticmethod
+    def _strand_code(strand) -> int:
+        return _lib.STRANDS[strand] if isinstance(strand, str) else int(strand)       # an int goes to the library as it is
+
+    def _classify_contigs(self, seq, offsets, single_window, precision, embed=False, strand=None):
+        """gnn_classify_contigs / _embed / _strand -> (scores, ids, emb or None, fwd or None, rev or None)"""
+        (ptr, on_host, nbytes, offsets, n_contigs), _keep = self._packed(seq, offsets)
+        scores = np.zeros((n_contigs, _lib.CLASSES), dtype=np.float32)
+        emb = np.zeros((n_contigs, _lib.EMBED_DIM), dtype=np.float32) if embed else None
+        cap = int(((np.diff(offsets) + _lib.WINDOW - 1) // _lib.WINDOW).sum()) if n_contigs else 0
+        ids = np.empty(max(cap, 1), dtype=np.int64)
+        n = C.c_int64()
+        args = (self.ctx, ptr, on_host, nbytes, offsets.ctypes.data, n_contigs, int(bool(single_window)),
+                _lib.PRECISIONS[precision], scores.ctypes.data, ids.ctypes.data, cap, C.byref(n))
+        fwd = rev = None
+        if strand is not None:
+            fwd, rev = (np.zeros((n_contigs, _lib.CLASSES), dtype=np.float32) for _ in range(2))
+            check(self.lib.gnn_classify_contigs_strand(*args, emb.ctypes.data if embed else None, self._strand_code(strand),
+                                                       fwd.ctypes.data, rev.ctypes.data))
+        elif embed:
+            check(self.lib.gnn_classify_contigs_embed(*args, emb.ctypes.data))
+        else:
+            check(self.lib.gnn_classify_contigs(*args))
+        return scores, ids[:n.value].copy(), emb, fwd, rev
+
+    def _scan_contigs(self, seq, offsets, stride, single_window, precision, strand=None):
+        """gnn_scan_contigs / _strand -> ScanResult / StrandScanResult"""
+        (ptr, on_host, nbytes, offsets, n_contigs), _keep = self._packed(seq, offsets)
+        win_off, bin_off, starts, lens = self.scan_plan(offsets, stride, single_window)
+        n, n_bins = len(starts), int(bin_off[-1])
+        scores = np.zeros((n, _lib.CLASSES), dtype=np.float32)
+        kept = np.zeros(n, dtype=np.uint8)
+        track = np.zeros((n_bins, _lib.CLASSES), dtype=np.float32)
+        cover = np.zeros(n_bins, dtype=np.int32)
+        contig_scores = np.zeros((n_contigs, _lib.CLASSES), dtype=np.float32)
+        args = (self.ctx, ptr, on_host, nbytes, offsets.ctypes.data, n_contigs, int(stride), int(bool(single_window)),
+                _lib.PRECISIONS[precision], scores.ctypes.data, kept.ctypes.data, n, track.ctypes.data, cover.ctypes.data, n_bins,
+                contig_scores.ctypes.data)
+        if strand is None:
+            check(self.lib.gnn_scan_contigs(*args))
+        else:
+            code = self._strand_code(strand)
+            fwd, rev = (np.zeros((n, _lib.CLASSES), dtype=np.float32) for _ in range(2))
+            check(self.lib.gnn_scan_contigs_strand(*args, code, fwd.ctypes.data, rev.ctypes.data))
+        fields = dict(stride=int(stride), win_offsets=win_off, starts=starts, lens=lens, kept=kept.astype(bool), scores=scores,
+                      bin_offsets=bin_off, track=track, cover=cover, contig_scores=contig_scores)
+        if strand is None:
+            return ScanResult(**fields)
+        name = {v: k for k, v in _lib.STRANDS.items()}[code]
+        return StrandScanResult(**fields, strand=name, scores_fwd=fwd, scores_rev=rev)
+
+    def _occlude_contigs(self, seq, offsets, block, single_window, precision):
+        """gnn_occlude_contigs -> OcclusionResult"""
+        (ptr, on_host, nbytes, offsets, n_contigs), _keep = self._packed(seq, offsets)
+        win_off, starts, lens, blk_off = self.occlusion_plan(offsets, block, single_window)
+        n, n_pairs = len(starts), int(blk_off[-1])
+        scores = np.zeros((n, _lib.CLASSES), dtype=np.float32)
+        kept = np.zeros(n, dtype=np.uint8)
+        delta = np.zeros((n_pairs, _lib.CLASSES), dtype=np.float32)
+        contig_scores = np.zeros((n_contigs, _lib.CLASSES), dtype=np.float32)
+        check(self.lib.gnn_occlude_contigs(self.ctx, ptr, on_host, nbytes, offsets.ctypes.data, n_contigs, int(block),
+                                           int(bool(single_window)), _lib.PRECISIONS[precision], scores.ctypes.data, kept.ctypes.data, n,
+                                           delta.ctypes.data, n_pairs, contig_scores.ctypes.data))
+        return OcclusionResult(block=int(block), win_offsets=win_off, starts=starts, lens=lens, kept=kept.astype(bool), scores=scores,
+                               blk_offsets=blk_off, delta=delta, contig_scores=contig_scores)
+
+    # -- contig scores and embeddings ------------------------------------------------------
     def classify_contigs(self, seq: np.ndarray, offsets: np.ndarray, single_window: bool = False,
                          precision=_lib.DEFAULT_PRECISION):
         """Contig front end: packed raw contig bytes -> per-contig scores.
@@ -251,55 +337,32 @@ class NNEngine:
         device and the window scores never leave it.  Returns (contig_scores (n_contigs, 3), contig ids of
         the kept windows).
         """
-        seq = np.ascontiguousarray(seq, dtype=np.uint8)
-        return self._classify_contigs(seq.ctypes.data, 1, seq.nbytes, offsets, single_window, precision)
+        return self._classify_contigs(np.asarray(seq), offsets, single_window, precision)[:2]
 
     def classify_contigs_dev(self, seq_ptr: int, offsets: np.ndarray, single_window: bool = False,
                              precision=_lib.DEFAULT_PRECISION):
         """Same as :meth:`classify_contigs` for a packed contig buffer that is already resident in
         HBM (``seq_ptr`` = device address of byte 0, ``offsets`` = (n_contigs+1,) byte offsets)."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        return self._classify_contigs(seq_ptr, 0, int(offsets[-1]) if len(offsets) else 0, offsets, single_window, precision)
-
-    def _classify_contigs(self, seq_ptr, on_host, seq_bytes, offsets, single_window, precision, embed=False):
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        if offsets.ndim != 1 or len(offsets) < 1:
-            raise ValueError("offsets must hold n_contigs + 1 byte offsets")
-        n_contigs = len(offsets) - 1
-        scores = np.zeros((n_contigs, _lib.CLASSES), dtype=np.float32)
-        cap = int(((np.diff(offsets) + _lib.WINDOW - 1) // _lib.WINDOW).sum()) if n_contigs else 0
-        ids = np.empty(max(cap, 1), dtype=np.int64)
-        n = C.c_int64()
-        args = (self.ctx, seq_ptr, int(on_host), int(seq_bytes), offsets.ctypes.data, n_contigs, int(bool(single_window)),
-                _lib.PRECISIONS[precision], scores.ctypes.data, ids.ctypes.data, cap, C.byref(n))
-        if not embed:
-            check(self.lib.gnn_classify_contigs(*args))
-            return scores, ids[:n.value].copy()
-        emb = np.zeros((n_contigs, _lib.EMBED_DIM), dtype=np.float32)
-        check(self.lib.gnn_classify_contigs_embed(*args, emb.ctypes.data))
-        return scores, emb, ids[:n.value].copy()
+        return self._classify_contigs(seq_ptr, offsets, single_window, precision)[:2]
 
     def embed_contigs(self, seq: np.ndarray, offsets: np.ndarray, single_window: bool = False,
                       precision=_lib.DEFAULT_PRECISION):
         """:meth:`classify_contigs` plus the per-contig embedding (``gnn_classify_contigs_embed``): the f32 mean of the encoder
         embeddings of the contig's kept windows, a zero row for a contig without one.  Returns (contig_scores (n_contigs, 3),
         contig_embeddings (n_contigs, 512), contig ids of the kept windows); scores and ids are those of classify_contigs."""
-        seq = np.ascontiguousarray(seq, dtype=np.uint8)
-        return self._classify_contigs(seq.ctypes.data, 1, seq.nbytes, offsets, single_window, precision, embed=True)
+        scores, ids, emb = self._classify_contigs(np.asarray(seq), offsets, single_window, precision, embed=True)[:3]
+        return scores, emb, ids
 
     def embed_contigs_dev(self, seq_ptr: int, offsets: np.ndarray, single_window: bool = False,
                           precision=_lib.DEFAULT_PRECISION):
         """Same as :meth:`embed_contigs` for a packed contig buffer that is already resident in HBM."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        return self._classify_contigs(seq_ptr, 0, int(offsets[-1]) if len(offsets) else 0, offsets, single_window, precision,
-                                      embed=True)
+        scores, ids, emb = self._classify_contigs(seq_ptr, offsets, single_window, precision, embed=True)[:3]
+        return scores, emb, ids
 
     # -- score tracks --------------------------------------------------------------------
     def scan_plan(self, offsets: np.ndarray, stride: int, single_window: bool = False):
         """``gnn_scan_plan`` (host only): (win_offsets, bin_offsets, contig-relative starts, lens) of a scan at ``stride``."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        if offsets.ndim != 1 or len(offsets) < 1:
-            raise ValueError("offsets must hold n_contigs + 1 byte offsets")
+        offsets = self._offsets(offsets)
         n_contigs = len(offsets) - 1
         nw, nb = C.c_int64(), C.c_int64()
         head = (offsets.ctypes.data, n_contigs, int(stride), int(bool(single_window)), C.byref(nw), C.byref(nb))
@@ -316,37 +379,18 @@ class NNEngine:
         a contig the signal is, which :meth:`classify_contigs` averages away.  The window and bin rules are those of
         ``sequence.scan_spans`` / ``sequence.scan_track``; at stride 6000 windows and ``contig_scores`` are those of
         classify_contigs.  Overlapping windows are classified independently: 6000 / stride times the work."""
-        seq = np.ascontiguousarray(seq, dtype=np.uint8)
-        return self._scan_contigs(seq.ctypes.data, 1, seq.nbytes, offsets, stride, single_window, precision)
+        return self._scan_contigs(np.asarray(seq), offsets, stride, single_window, precision)
 
     def scan_contigs_dev(self, seq_ptr: int, offsets: np.ndarray, stride: int, single_window: bool = False,
                          precision=_lib.DEFAULT_PRECISION) -> ScanResult:
         """Same as :meth:`scan_contigs` for a packed contig buffer that is already resident in HBM."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        return self._scan_contigs(seq_ptr, 0, int(offsets[-1]) if len(offsets) else 0, offsets, stride, single_window, precision)
-
-    def _scan_contigs(self, seq_ptr, on_host, seq_bytes, offsets, stride, single_window, precision):
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        win_off, bin_off, starts, lens = self.scan_plan(offsets, stride, single_window)
-        n_contigs, n, n_bins = len(offsets) - 1, len(starts), int(bin_off[-1])
-        scores = np.zeros((n, _lib.CLASSES), dtype=np.float32)
-        kept = np.zeros(n, dtype=np.uint8)
-        track = np.zeros((n_bins, _lib.CLASSES), dtype=np.float32)
-        cover = np.zeros(n_bins, dtype=np.int32)
-        contig_scores = np.zeros((n_contigs, _lib.CLASSES), dtype=np.float32)
-        check(self.lib.gnn_scan_contigs(self.ctx, seq_ptr, int(on_host), int(seq_bytes), offsets.ctypes.data, n_contigs, int(stride),
-                                        int(bool(single_window)), _lib.PRECISIONS[precision], scores.ctypes.data, kept.ctypes.data, n,
-                                        track.ctypes.data, cover.ctypes.data, n_bins, contig_scores.ctypes.data))
-        return ScanResult(stride=int(stride), win_offsets=win_off, starts=starts, lens=lens, kept=kept.astype(bool), scores=scores,
-                          bin_offsets=bin_off, track=track, cover=cover, contig_scores=contig_scores)
+        return self._scan_contigs(seq_ptr, offsets, stride, single_window, precision)
 
     # -- occlusion maps ------------------------------------------------------------------
     def occlusion_plan(self, offsets: np.ndarray, block: int, single_window: bool = False):
         """``gnn_occlusion_plan`` (host only): (win_offsets, contig-relative starts, lens, blk_offsets) of an occlusion map with
         blocks of ``block`` bases - the windows of :meth:`classify_contigs` and the CSR of their (window, block) pairs."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        if offsets.ndim != 1 or len(offsets) < 1:
-            raise ValueError("offsets must hold n_contigs + 1 byte offsets")
+        offsets = self._offsets(offsets)
         n_contigs = len(offsets) - 1
         nw, npairs = C.c_int64(), C.c_int64()
         head = (offsets.ctypes.data, n_contigs, int(block), int(bool(single_window)), C.byref(nw), C.byref(npairs))
@@ -374,28 +418,12 @@ class NNEngine:
         far each class moved - which bases the score rests on.  Windows, ``kept`` and ``contig_scores`` are those of
         classify_contigs, ``scores`` those of ``scan_contigs(stride=6000)``, every occluded score that of :meth:`classify` on the
         same bytes (``sequence.occlude_spans``).  1 + ceil(6000 / block) forward passes per window."""
-        seq = np.ascontiguousarray(seq, dtype=np.uint8)
-        return self._occlude_contigs(seq.ctypes.data, 1, seq.nbytes, offsets, block, single_window, precision)
+        return self._occlude_contigs(np.asarray(seq), offsets, block, single_window, precision)
 
     def occlude_contigs_dev(self, seq_ptr: int, offsets: np.ndarray, block: int, single_window: bool = False,
                             precision=_lib.DEFAULT_PRECISION) -> OcclusionResult:
         """Same as :meth:`occlude_contigs` for a packed contig buffer that is already resident in HBM."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        return self._occlude_contigs(seq_ptr, 0, int(offsets[-1]) if len(offsets) else 0, offsets, block, single_window, precision)
-
-    def _occlude_contigs(self, seq_ptr, on_host, seq_bytes, offsets, block, single_window, precision):
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        win_off, starts, lens, blk_off = self.occlusion_plan(offsets, block, single_window)
-        n_contigs, n, n_pairs = len(offsets) - 1, len(starts), int(blk_off[-1])
-        scores = np.zeros((n, _lib.CLASSES), dtype=np.float32)
-        kept = np.zeros(n, dtype=np.uint8)
-        delta = np.zeros((n_pairs, _lib.CLASSES), dtype=np.float32)
-        contig_scores = np.zeros((n_contigs, _lib.CLASSES), dtype=np.float32)
-        check(self.lib.gnn_occlude_contigs(self.ctx, seq_ptr, int(on_host), int(seq_bytes), offsets.ctypes.data, n_contigs, int(block),
-                                           int(bool(single_window)), _lib.PRECISIONS[precision], scores.ctypes.data, kept.ctypes.data, n,
-                                           delta.ctypes.data, n_pairs, contig_scores.ctypes.data))
-        return OcclusionResult(block=int(block), win_offsets=win_off, starts=starts, lens=lens, kept=kept.astype(bool), scores=scores,
-                               blk_offsets=blk_off, delta=delta, contig_scores=contig_scores)
+        return self._occlude_contigs(seq_ptr, offsets, block, single_window, precision)
 
     # -- both strands --------------------------------------------------------------------
     def revcomp_spans_dev(self, seq_ptr: int, starts, lens, bases_ptr: int):
@@ -416,68 +444,23 @@ class NNEngine:
         those.  Returns (contig_scores (n_contigs, 3) of the mode, contig ids of the kept windows, contig embeddings
         (n_contigs, 512) of the mode or None without ``embed``, forward contig scores, reverse contig scores); a strand the
         mode does not need is computed for its own scores.  "forward" is bit-identical to classify_contigs / embed_contigs."""
-        seq = np.ascontiguousarray(seq, dtype=np.uint8)
-        return self._classify_contigs_strand(seq.ctypes.data, 1, seq.nbytes, offsets, strand, single_window, precision, embed)
+        return self._classify_contigs(np.asarray(seq), offsets, single_window, precision, embed, strand)
 
     def classify_contigs_strand_dev(self, seq_ptr: int, offsets: np.ndarray, strand="both", single_window: bool = False,
                                     precision=_lib.DEFAULT_PRECISION, embed: bool = False):
         """Same as :meth:`classify_contigs_strand` for a packed contig buffer that is already resident in HBM."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        return self._classify_contigs_strand(seq_ptr, 0, int(offsets[-1]) if len(offsets) else 0, offsets, strand, single_window,
-                                             precision, embed)
-
-    @staticmethod
-    def _strand_code(strand) -> int:
-        return _lib.STRANDS[strand] if isinstance(strand, str) else int(strand)       # an int goes to the library as it is
-
-    def _classify_contigs_strand(self, seq_ptr, on_host, seq_bytes, offsets, strand, single_window, precision, embed):
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        if offsets.ndim != 1 or len(offsets) < 1:
-            raise ValueError("offsets must hold n_contigs + 1 byte offsets")
-        n_contigs = len(offsets) - 1
-        scores, fwd, rev = (np.zeros((n_contigs, _lib.CLASSES), dtype=np.float32) for _ in range(3))
-        emb = np.zeros((n_contigs, _lib.EMBED_DIM), dtype=np.float32) if embed else None
-        cap = int(((np.diff(offsets) + _lib.WINDOW - 1) // _lib.WINDOW).sum()) if n_contigs else 0
-        ids = np.empty(max(cap, 1), dtype=np.int64)
-        n = C.c_int64()
-        check(self.lib.gnn_classify_contigs_strand(
-            self.ctx, seq_ptr, int(on_host), int(seq_bytes), offsets.ctypes.data, n_contigs, int(bool(single_window)),
-            _lib.PRECISIONS[precision], scores.ctypes.data, ids.ctypes.data, cap, C.byref(n), emb.ctypes.data if embed else None,
-            self._strand_code(strand), fwd.ctypes.data, rev.ctypes.data))
-        return scores, ids[:n.value].copy(), emb, fwd, rev
+        return self._classify_contigs(seq_ptr, offsets, single_window, precision, embed, strand)
 
     def scan_contigs_strand(self, seq: np.ndarray, offsets: np.ndarray, stride: int, strand="both", single_window: bool = False,
                             precision=_lib.DEFAULT_PRECISION) -> StrandScanResult:
         """:meth:`scan_contigs` with a strand mode (``gnn_scan_contigs_strand``): ``scores``, ``track`` and ``contig_scores`` carry
         the mode, ``scores_fwd`` / ``scores_rev`` each strand's own window scores; everything else is the forward scan's."""
-        seq = np.ascontiguousarray(seq, dtype=np.uint8)
-        return self._scan_contigs_strand(seq.ctypes.data, 1, seq.nbytes, offsets, stride, strand, single_window, precision)
+        return self._scan_contigs(np.asarray(seq), offsets, stride, single_window, precision, strand)
 
     def scan_contigs_strand_dev(self, seq_ptr: int, offsets: np.ndarray, stride: int, strand="both", single_window: bool = False,
                                 precision=_lib.DEFAULT_PRECISION) -> StrandScanResult:
         """Same as :meth:`scan_contigs_strand` for a packed contig buffer that is already resident in HBM."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        return self._scan_contigs_strand(seq_ptr, 0, int(offsets[-1]) if len(offsets) else 0, offsets, stride, strand, single_window,
-                                         precision)
-
-    def _scan_contigs_strand(self, seq_ptr, on_host, seq_bytes, offsets, stride, strand, single_window, precision):
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        win_off, bin_off, starts, lens = self.scan_plan(offsets, stride, single_window)
-        n_contigs, n, n_bins = len(offsets) - 1, len(starts), int(bin_off[-1])
-        scores, fwd, rev = (np.zeros((n, _lib.CLASSES), dtype=np.float32) for _ in range(3))
-        kept = np.zeros(n, dtype=np.uint8)
-        track = np.zeros((n_bins, _lib.CLASSES), dtype=np.float32)
-        cover = np.zeros(n_bins, dtype=np.int32)
-        contig_scores = np.zeros((n_contigs, _lib.CLASSES), dtype=np.float32)
-        code = self._strand_code(strand)
-        check(self.lib.gnn_scan_contigs_strand(self.ctx, seq_ptr, int(on_host), int(seq_bytes), offsets.ctypes.data, n_contigs,
-                                               int(stride), int(bool(single_window)), _lib.PRECISIONS[precision], scores.ctypes.data,
-                                               kept.ctypes.data, n, track.ctypes.data, cover.ctypes.data, n_bins,
-                                               contig_scores.ctypes.data, code, fwd.ctypes.data, rev.ctypes.data))
-        name = {v: k for k, v in _lib.STRANDS.items()}[code]
-        return StrandScanResult(stride=int(stride), win_offsets=win_off, starts=starts, lens=lens, kept=kept.astype(bool),
-                                scores=scores, bin_offsets=bin_off, track=track, cover=cover, contig_scores=contig_scores,
-                                strand=name, scores_fwd=fwd, scores_rev=rev)
+        return self._scan_contigs(seq_ptr, offsets, stride, single_window, precision, strand)
 
     def classify_contigs_spans(self, seq_ptr: int, offsets: np.ndarray, single_window: bool = False,
                                precision=_lib.DEFAULT_PRECISION):

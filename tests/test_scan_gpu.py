@@ -174,6 +174,74 @@ def test_scan_errors_leave_the_ctx_usable(engine):
     assert np.array_equal(c6.scores, engine.classify(_numpy_scan(seq, offsets, 2000)["wins"], "f16c6"))
 
 
+# ---- every family on one ctx ---------------------------------------------------------------------------------------------------
+EDGE_LENS = [0, 1, 2499, 2500, 20600, 6000, 8499, 8500, 12001, 3000]       # the window rule's edges, and one contig for the N rule
+
+
+def _edge_contigs():
+    """ten contigs in lower and upper case; the fifth has a later window the N rule drops (4001 N) and one it keeps (exactly 4000)"""
+    rng = np.random.default_rng(20261018)
+    alphabet = np.frombuffer(b"ACGTacgt", np.uint8)
+    parts = [alphabet[rng.integers(0, 8, n)] for n in EDGE_LENS]
+    parts[4][6000:6000 + sequence.MAX_N + 1] = ord("N")
+    parts[4][12000 + 17:12000 + 17 + sequence.MAX_N] = ord("N")
+    return np.concatenate(parts), np.concatenate([[0], np.cumsum(EDGE_LENS)]).astype(np.int64)
+
+
+def _bits(res):
+    """a call's result as (dtype, shape, bytes) per array: equality of these is equality bit for bit, NaN payloads included"""
+    vals = [getattr(res, k) for k in res.FIELDS] if hasattr(res, "FIELDS") else list(res)
+    return [(a.dtype, a.shape, a.tobytes()) for a in map(np.asarray, vals)]
+
+
+# the calls of the interleaved sequence: (name, host-array variant?, call on (engine, packed bytes or device address, offsets, prec))
+FAMILY_CALLS = [
+    ("classify", True, lambda e, s, o, p: e.classify_contigs(s, o, False, p)),
+    ("occlude", False, lambda e, s, o, p: e.occlude_contigs_dev(s, o, 1500, False, p)),
+    ("scan", True, lambda e, s, o, p: e.scan_contigs(s, o, 2000, False, p)),
+    ("strand both + embeddings", False, lambda e, s, o, p: e.classify_contigs_strand_dev(s, o, "both", False, p, True)),
+    ("scan strand", True, lambda e, s, o, p: e.scan_contigs_strand(s, o, 3501, "both", False, p)),
+    ("embed", False, lambda e, s, o, p: e.embed_contigs_dev(s, o, False, p)),
+    ("classify again", True, lambda e, s, o, p: e.classify_contigs(s, o, False, p)),
+]
+
+
+def _run_calls(synth_weights, seq, offsets, prec, calls):
+    """the calls in order on ONE fresh ctx of 2 windows per launch (slabs of 8 windows, 4 under both strands: every call needs
+    several), the *_dev ones on a device copy of the packed bytes"""
+    from genomad_amd.engine import NNEngine
+    with NNEngine(0, synth_weights, chunk=2) as eng:
+        dev = eng.alloc(seq.nbytes)
+        try:
+            dev.upload(seq)
+            return [_bits(call(eng, seq if on_host else dev.ptr, offsets, prec)) for _, on_host, call in calls]
+        finally:
+            dev.free()
+
+
+def test_the_edge_contigs_sit_on_the_window_and_n_rules():
+    seq, offsets = _edge_contigs()
+    starts, lens, ids, window_n = sequence.candidate_spans(offsets, False)
+    assert np.bincount(ids, minlength=10).tolist() == [0, 1, 1, 1, 4, 1, 1, 2, 2, 1]       # 8499: tail dropped; 8500: tail kept
+    assert lens[ids == 7].tolist() == [6000, 2500] and lens[ids == 8].tolist() == [6000, 6000]
+    nn = np.array([np.count_nonzero(seq[a:a + n] == ord("N")) for a, n in zip(starts, lens)])
+    assert nn[ids == 4].tolist() == [0, sequence.MAX_N + 1, sequence.MAX_N, 0] and window_n[ids == 4].tolist() == [0, 1, 2, 3]
+    assert np.isin(seq, np.frombuffer(b"acgt", np.uint8)).any() and np.isin(seq, np.frombuffer(b"ACGT", np.uint8)).any()
+
+
+@pytest.mark.parametrize("prec", ["f16x3tc", "bf16x3"])
+def test_all_families_interleaved_on_one_ctx_equal_each_call_made_first_on_a_fresh_ctx(synth_weights, engine, prec):
+    """classify, occlude, scan, strand-both with embeddings, scan-strand, embed, classify - host arrays and resident buffers in
+    turn, so the sequence feed and the already-resident path interleave on one workspace - against each call made alone"""
+    seq, offsets = _edge_contigs()
+    got = _run_calls(synth_weights, seq, offsets, prec, FAMILY_CALLS)
+    for i, call in enumerate(FAMILY_CALLS[:-1]):
+        assert got[i] == _run_calls(synth_weights, seq, offsets, prec, [call])[0], call[0]
+    assert got[6] == got[0]
+    kept = np.frombuffer(got[2][4][2], bool)                  # the scan's mask: the N rule dropped a window, on this input too
+    assert not kept.all() and kept.any()
+
+
 # ---- main() -------------------------------------------------------------------------------------------------------------------
 SCAN_KEYS = ["bin_offsets", "contig_names", "cover", "stride", "track", "win_offsets", "window_kept", "window_len", "window_scores",
              "window_start"]
