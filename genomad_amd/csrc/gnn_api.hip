@@ -184,6 +184,7 @@ void free_stage(gnn_ctx* ctx) {
     ctx->stage_scores_host.reset();
     ctx->stage_emb.reset();
     ctx->emb_scores.reset();
+    ctx->stage_attr.reset();
     for (int i = 0; i < 2; ++i) {
         ctx->pin[i].reset();
         if (ctx->pin_ev[i]) (void)hipEventDestroy(ctx->pin_ev[i]);
@@ -237,7 +238,7 @@ size_t emb_elem_bytes(int emb_dtype) {
 
 // One pass of the hot path over n windows whose bases are on the device.
 int classify_chunks(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int precision, float* scores_dev, bool defer_last,
-                    void* emb_dev, int emb_dtype) {
+                    void* emb_dev, int emb_dtype, const AttribOut* attr) {
     if (!ctx->has_weights) {
         set_error("gnn_load_weights has not been called");
         return GNN_ERR_STATE;
@@ -284,6 +285,11 @@ int classify_chunks(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int preci
     }
     if (rc) return rc;
     if (!f32 && chunk < std::min<int64_t>(ctx->chunk_fused, std::max<int64_t>(n, 1))) ctx->chunk_fused = chunk;
+    if (attr && ctx->attr_g.capacity() < (size_t)chunk * FEAT * GNN_CLASSES) {      // grows: no attribution kernel may still read it
+        if (ctx->stream2) GNN_HIP(hipStreamSynchronize(ctx->stream2));
+        GNN_HIP(hipStreamSynchronize(ctx->stream));
+        if ((rc = ctx->attr_g.reserve((size_t)chunk * FEAT * GNN_CLASSES))) return rc;
+    }
     // An asynchronous call (gnn_classify_dev_async, or whatever one left pending): the back end of chunk i (five small, mostly
     // HBM-bound kernels, 4 % of the time) is enqueued on a second stream and runs beside the front end of chunk i+1 (of this call
     // or of the next one); two workspaces alternate.  A synchronous multi-chunk call no longer does that (rounds 2-4 did): beside
@@ -392,7 +398,17 @@ int classify_chunks(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int preci
             // workspace) writes rows of its own chunk only
             void* emb = emb_dev ? static_cast<uint8_t*>(emb_dev) + (size_t)a * HID * emb_elem_bytes(emb_dtype) : nullptr;
             rc = launch_backend(ctx, m, (precision == GNN_PREC_F16X3TC || precision == GNN_PREC_F16X3TK) ? GNN_PREC_F16X3 : precision,
-                                scores_dev + a * GNN_CLASSES, emb, emb_dtype);
+                                scores_dev ? scores_dev + a * GNN_CLASSES : nullptr, emb, emb_dtype, !attr);
+        }
+        // attribution: the head's gradient and the contribution maps of THIS chunk, on the stream and the workspace its back end
+        // ran on - before the swap below hands the workspace to the next chunk
+        if (attr && !rc) {
+            ProfScope ps(ctx, GNN_K_ATTR_HEAD);
+            rc = launch_attrib_head(ctx, m, scores_dev ? scores_dev + a * GNN_CLASSES : nullptr, *attr, a);
+        }
+        if (attr && !rc) {
+            ProfScope ps(ctx, GNN_K_ATTR_CONTRIB);
+            rc = launch_attrib_contrib(ctx, m, *attr, a);
         }
         if (overlap) {
             if (!rc) {
@@ -956,6 +972,61 @@ int gnn_embed(gnn_ctx* ctx, const uint8_t* bases_host, int64_t n, int precision,
             GNN_HIP(hipStreamSynchronize(ctx->stream));
             if (scores_host)
                 std::memcpy(scores_host + a0 * GNN_CLASSES, ctx->stage_scores_host, (size_t)m * GNN_CLASSES * sizeof(float));
+        }
+    }
+    return rc;
+}
+
+int gnn_attribute_dev(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int precision, int bin, float* contrib_dev, float* bias_dev,
+                      float* logits_dev, float* scores_dev) {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!bases_dev || !contrib_dev))) {
+        set_error("bad argument to gnn_attribute_dev");
+        return GNN_ERR_ARG;
+    }
+    if ((rc = check_attrib_args(precision, bin, "gnn_attribute_dev"))) return rc;
+    if (n == 0) return GNN_OK;
+    const AttribOut at{bin, contrib_dev, bias_dev, logits_dev};
+    return classify_chunks(ctx, bases_dev, n, precision, scores_dev, false, nullptr, GNN_EMB_F32, &at);
+}
+
+int gnn_attribute(gnn_ctx* ctx, const uint8_t* bases_host, int64_t n, int precision, int bin, float* contrib_host, float* bias_host,
+                  float* logits_host, float* scores_host) {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!bases_host || !contrib_host))) {
+        set_error("bad argument to gnn_attribute");
+        return GNN_ERR_ARG;
+    }
+    if ((rc = check_attrib_args(precision, bin, "gnn_attribute"))) return rc;
+    if (n == 0) return GNN_OK;
+    // the staging of gnn_classify plus a device slab for the maps, bias and logits: at most ATTR_SLAB windows at a time (18 KB of
+    // map per window at bin = 1: 74 MB)
+    constexpr int64_t ATTR_SLAB = 4096;
+    const int64_t slab = std::min<int64_t>(n, ATTR_SLAB);
+    const size_t map = (size_t)2 * attrib_bins(bin) * GNN_CLASSES;
+    if ((rc = ensure_stage(ctx, slab))) return rc;
+    if (ctx->stage_attr.capacity() < (size_t)slab * (map + 2 * GNN_CLASSES)) {
+        GNN_HIP(hipStreamSynchronize(ctx->stream));
+        if ((rc = ctx->stage_attr.reserve((size_t)slab * (map + 2 * GNN_CLASSES)))) return rc;
+    }
+    float* const d_contrib = ctx->stage_attr;
+    float* const d_bias = d_contrib + (size_t)slab * map;
+    float* const d_logits = d_bias + (size_t)slab * GNN_CLASSES;
+    const AttribOut at{bin, d_contrib, d_bias, d_logits};
+    for (int64_t a0 = 0; a0 < n && !rc; a0 += slab) {
+        const int64_t m = std::min(slab, n - a0);
+        rc = stage_upload(ctx, bases_host + a0 * W, (size_t)m * W);
+        if (!rc) rc = classify_chunks(ctx, ctx->stage_bases, m, precision, ctx->stage_scores, false, nullptr, GNN_EMB_F32, &at);
+        if (!rc) {
+            const size_t row = (size_t)GNN_CLASSES * sizeof(float);
+            if (scores_host) GNN_HIP(hipMemcpyAsync(ctx->stage_scores_host, ctx->stage_scores, (size_t)m * row, hipMemcpyDeviceToHost, ctx->stream));
+            GNN_HIP(hipMemcpyAsync(contrib_host + (size_t)a0 * map, d_contrib, (size_t)m * map * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+            if (bias_host) GNN_HIP(hipMemcpyAsync(bias_host + a0 * GNN_CLASSES, d_bias, (size_t)m * row, hipMemcpyDeviceToHost, ctx->stream));
+            if (logits_host) GNN_HIP(hipMemcpyAsync(logits_host + a0 * GNN_CLASSES, d_logits, (size_t)m * row, hipMemcpyDeviceToHost, ctx->stream));
+            GNN_HIP(hipStreamSynchronize(ctx->stream));
+            if (scores_host) std::memcpy(scores_host + a0 * GNN_CLASSES, ctx->stage_scores_host, (size_t)m * row);
         }
     }
     return rc;

@@ -317,6 +317,8 @@ __device__ __forceinline__ uint16_t f32_to_bf16_rne(float v) {
 // EMB (GNN_EMB_* + 1, 0 = none): also store h1 - the encoder embedding of create_encoder(), model.py:14-31 - as emb[n][512] of
 // that dtype.  Thread j owns hidden unit j of the block's DW windows, so every row store is one coalesced 2 KB (1 KB) line.
 // EMB = 0 is the kernel the scores have always used; the stores change no arithmetic, so the scores are bit-identical either way.
+// attrib_head_kernel (gnn_attrib.hip) repeats this forward pass term for term and promises the same bits: a change of the arithmetic
+// here is a change there (tests/test_attribution_gpu.py compares the scores of the two bit for bit).
 template <int EMB>
 __global__ __launch_bounds__(512) void dense_kernel(const float* __restrict__ feat,
                                                     const float* __restrict__ d1k, const float* __restrict__ d1b,
@@ -496,7 +498,7 @@ __global__ __launch_bounds__(256) void dense_mfma_kernel(const float* __restrict
     }
 }
 
-int launch_backend(gnn_ctx* ctx, int64_t n, int precision, float* scores_dev, void* emb_dev, int emb_dtype) {
+int launch_backend(gnn_ctx* ctx, int64_t n, int precision, float* scores_dev, void* emb_dev, int emb_dtype, bool dense) {
     if (emb_dev && (precision == GNN_PREC_F16C6 || precision == GNN_PREC_F16C8 || (emb_dtype != GNN_EMB_F32 && emb_dtype != GNN_EMB_BF16))) {
         set_error("embeddings: the dense head of this arithmetic does not produce them (f16c6 is frozen), or a bad gnn_emb_dtype");
         return GNN_ERR_ARG;
@@ -524,6 +526,10 @@ int launch_backend(gnn_ctx* ctx, int64_t n, int precision, float* scores_dev, vo
                            ctx->stream, ws.m, d.w_qk[0], d.w_qk[1], (int)n, ws.logits);
     hipLaunchKernelGGL(attn_kernel, dim3((unsigned)n, 2), dim3(256), 0, ctx->stream, ws.logits, ws.yp, ws.alpha,
                        ws.feat);
+    if (!dense) {                                                        // the attribution's head kernel follows (classify_chunks)
+        GNN_HIP(hipGetLastError());
+        return GNN_OK;
+    }
     if (precision != GNN_PREC_F16C6 && precision != GNN_PREC_F16C8) {    // exact f32 FMAs (f32 range and accuracy)
         const dim3 grid((unsigned)((n + DW - 1) / DW));
         if (!emb_dev)

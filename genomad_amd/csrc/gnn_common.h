@@ -160,6 +160,8 @@ struct ContigWorkspace {
     std::vector<int64_t> blk_off;
     DevBuf<int64_t> d_blk_off;
     DevBuf<float> d_occ;
+    // gnn_attribute_contigs (gnn_attrib.hip): ONE slab's maps, bias and logits (24 nb + 24 B per window of the slab)
+    DevBuf<float> d_attr;
 
     // What the buffer groups hold, in windows / contigs + 1 / bins.  The head-room is counted in elements, so a buffer with
     // several elements per window or bin holds fewer of them than its neighbours: the smallest member decides.
@@ -243,6 +245,16 @@ static int launch_1d(void (*kernel)(P...), int64_t cells, hipStream_t stream, A&
     return GNN_OK;
 }
 
+// What an attribution call adds to a pass of classify_chunks (gnn_attrib.hip): device buffers, row i = window i of the pass.
+// contrib[n][2][attrib_bins(bin)][3]; bias[n][3] and logits[n][3] may be NULL.
+struct AttribOut {
+    int bin;
+    float* contrib;
+    float* bias;
+    float* logits;
+};
+static inline int attrib_bins(int bin) { return (POOLED + bin - 1) / bin; }      // the last bin may be short
+
 struct ProfileSlot {
     double total_ms = 0.0;
     int64_t launches = 0;
@@ -287,6 +299,8 @@ struct gnn_ctx {
     gnn::DevBuf<uint8_t> stage_bases;             // W bytes per window
     gnn::DevBuf<float> stage_emb;                 // gnn_embed: the slab's embeddings (grow-only; f32 elements, serves bf16 too)
     gnn::DevBuf<float> emb_scores;                // gnn_embed_dev without a scores pointer: the scores land here (grow-only)
+    gnn::DevBuf<float> stage_attr;                // gnn_attribute: the slab's maps, bias and logits (grow-only)
+    gnn::DevBuf<float> attr_g;                    // attribution: d logit / d feat of one launch's windows, [chunk][256][3] (gnn_attrib.hip)
     gnn::DevBuf<float> stage_scores;              // GNN_CLASSES per window, as stage_scores_host
     gnn::PinnedBuf<float> stage_scores_host;
     gnn::PinnedBuf<uint8_t> pin[2];
@@ -360,14 +374,23 @@ int launch_masked_segment_mean(gnn_ctx* ctx, const float* scores, const int64_t*
                                int64_t n, int64_t n_seg, float* out);
 int launch_front_f32(gnn_ctx* ctx, const uint8_t* bases, int64_t n);         // -> ws.mp, ws.yp (+ ws.x)
 // ws.mp, ws.yp -> scores; emb_dev != NULL: also h1 (the encoder embedding) as emb_dev[n][GNN_EMBED_DIM] of emb_dtype (gnn_emb_dtype)
-int launch_backend(gnn_ctx* ctx, int64_t n, int precision, float* scores_dev, void* emb_dev = nullptr, int emb_dtype = GNN_EMB_F32);
+// dense = false: everything up to ws.feat; the dense head is then the attribution's (launch_attrib_head, which writes the scores)
+int launch_backend(gnn_ctx* ctx, int64_t n, int precision, float* scores_dev, void* emb_dev = nullptr, int emb_dtype = GNN_EMB_F32,
+                   bool dense = true);
+// attribution (gnn_attrib.hip): precision and bin checked under the entry point's name; the head kernel (ws.feat -> scores, ctx->attr_g,
+// bias, logits) and the contribution kernel (ws.alpha, ws.yp, ctx->attr_g -> contrib) of the n windows in ctx->ws, whose outputs
+// are rows row0 .. row0 + n - 1 of `at`
+int check_attrib_args(int precision, int bin, const char* fn);
+int launch_attrib_head(gnn_ctx* ctx, int64_t n, float* scores_dev, const AttribOut& at, int64_t row0);
+int launch_attrib_contrib(gnn_ctx* ctx, int64_t n, const AttribOut& at, int64_t row0);
 // one pass of the hot path over n windows whose padded bases are on the device (gnn_api.hip)
 // defer_last: leave the last chunk's back end pending on the second stream (gnn_classify_dev_async).  flush_backend()
 // makes ctx->stream wait for whatever is pending (the end of a synchronous classify_chunks); finish_pending() waits for it on
 // the host - every other entry point that enqueues on ctx->stream, reads scores or touches the workspaces calls it first
 // emb_dev != NULL: window i's embedding goes to row i of emb_dev (the rows of a chunk are its own, whichever workspace it ran in)
+// attr != NULL: window i's contribution map, bias and logits go to row i of attr's buffers; scores_dev may then be NULL
 int classify_chunks(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n, int precision, float* scores_dev, bool defer_last = false,
-                    void* emb_dev = nullptr, int emb_dtype = GNN_EMB_F32);
+                    void* emb_dev = nullptr, int emb_dtype = GNN_EMB_F32, const AttribOut* attr = nullptr);
 size_t emb_elem_bytes(int emb_dtype);   // bytes of one embedding value (gnn_api.hip); 0 for a bad gnn_emb_dtype
 int flush_backend(gnn_ctx* ctx);
 int finish_pending(gnn_ctx* ctx);
@@ -419,9 +442,9 @@ int plan_windows(const ContigIn& in, ContigWorkspace& w, bool csr, int block);
 int upload_span_table(gnn_ctx* ctx, ContigWorkspace& w);
 // One slab [a, a + m) of the span table: what its windows read is uploaded, their N are counted into w.d_counts, they are
 // materialised into w.d_bases - the forward windows, then the reverse ones, whichever are asked for - and the batch is classified:
-// scores[(fwd + rev) * m][GNN_CLASSES], and emb[(fwd + rev) * m][HID] unless NULL.
+// scores[(fwd + rev) * m][GNN_CLASSES], emb[(fwd + rev) * m][HID] unless NULL, and the maps of `attr` unless NULL.
 int slab_pass(const ContigIn& in, ContigWorkspace& w, SeqFeed& feed, int64_t a, int64_t m, bool fwd, bool rev, float* scores,
-              float* emb);
+              float* emb, const AttribOut* attr = nullptr);
 // After the counts came back (w.counts): the N rule per window on the host.  mask[i] = 1 / 0 and the contig ids of the kept
 // windows, compacted, where asked for; returns how many are kept.
 int64_t kept_windows(const ContigWorkspace& w, uint8_t* mask_or_null, int64_t* ids_or_null);

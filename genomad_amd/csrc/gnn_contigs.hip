@@ -280,7 +280,7 @@ int SeqFeed::upto(int64_t end) {
 }
 
 int slab_pass(const ContigIn& in, ContigWorkspace& w, SeqFeed& feed, int64_t a, int64_t m, bool fwd, bool rev, float* scores,
-              float* emb) {
+              float* emb, const AttribOut* attr) {
     int rc = feed.upto(w.starts[a + m - 1] + w.lens[a + m - 1]);       // spans are in buffer order: the slab's last byte
     if (rc) return rc;
     const int64_t* const starts = w.d_starts + a;
@@ -288,7 +288,7 @@ int slab_pass(const ContigIn& in, ContigWorkspace& w, SeqFeed& feed, int64_t a, 
     if ((rc = launch_span_count(in.ctx, feed.dev(), starts, lens, m, 'N', w.d_counts + a))) return rc;      // serves both strands
     if (fwd && (rc = launch_materialize(in.ctx, feed.dev(), starts, lens, m, w.d_bases))) return rc;
     if (rev && (rc = launch_revcomp(in.ctx, feed.dev(), starts, lens, m, w.d_bases + (fwd ? m : 0) * W))) return rc;
-    return classify_chunks(in.ctx, w.d_bases, m * (fwd + rev), in.precision, scores, false, emb, GNN_EMB_F32);
+    return classify_chunks(in.ctx, w.d_bases, m * (fwd + rev), in.precision, scores, false, emb, GNN_EMB_F32, attr);
 }
 
 int64_t kept_windows(const ContigWorkspace& w, uint8_t* mask_or_null, int64_t* ids_or_null) {

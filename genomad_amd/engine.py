@@ -76,6 +76,22 @@ class OcclusionResult:
         return {k: getattr(self, k) for k in self.FIELDS}
 
 
+class AttributionResult:
+    """What :meth:`NNEngine.attribute_contigs` returns.  Windows (CSR over contigs by ``win_offsets``): ``starts`` (contig-relative),
+    ``lens``, ``kept`` (bool: the N rule's mask), ``window_scores`` (n_windows, 3).  Maps: ``contrib`` (n_windows, 2, nb, 3) - head A,
+    B; bins of ``bin`` pooled positions (a position = 8 tokens; nb = ceil(749 / bin)); class - each bin's signed share of the
+    window's pre-softmax ``logits`` (n_windows, 3), and ``bias`` (n_windows, 3), the remainder: contrib.sum((1, 2)) + bias = logits.
+    ``contig_scores`` (n_contigs, 3): the mean of each contig's kept windows."""
+    FIELDS = ("bin", "win_offsets", "starts", "lens", "kept", "window_scores", "contrib", "bias", "logits", "contig_scores")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw[k])
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+
 class NNEngine:
     def __init__(self, device: int = 0, weights: dict = None, chunk: int = None):
         self.lib = _lib.load()
@@ -424,6 +440,62 @@ class NNEngine:
                             precision=_lib.DEFAULT_PRECISION) -> OcclusionResult:
         """Same as :meth:`occlude_contigs` for a packed contig buffer that is already resident in HBM."""
         return self._occlude_contigs(seq_ptr, offsets, block, single_window, precision)
+
+    # -- attention contribution maps ------------------------------------------------------
+    @staticmethod
+    def attribution_bins(bin: int) -> int:
+        """nb = ceil(749 / bin): the bins of a contribution map with ``bin`` pooled positions each (the last one may be short)."""
+        return -(-_lib.POOLED // int(bin))
+
+    def attribute(self, bases, bin: int = 1, precision=_lib.DEFAULT_PRECISION):
+        """(n,6000) uint8 windows -> (contrib (n, 2, nb, 3), bias (n, 3), logits (n, 3), scores (n, 3)), all float32
+        (``gnn_attribute``): each pooled position's share of each pre-softmax logit, per attention head - gradient x input at the
+        attention layer with the attention weights held fixed.  contrib.sum((1, 2)) + bias = logits; the scores are those of
+        :meth:`classify`, bit for bit.  ``bin`` pooled positions (8 tokens each) per output bin, 1 <= bin <= 749.  The map decomposes
+        the logit exactly; it does not predict what an edit of the window would do (:meth:`occlude_contigs` does)."""
+        b = self._check_bases(bases)
+        nb = self.attribution_bins(bin) if 1 <= int(bin) <= _lib.POOLED else 1      # a bad bin is the library's to refuse
+        contrib = np.zeros((len(b), 2, nb, _lib.CLASSES), dtype=np.float32)
+        bias, logits, scores = (np.zeros((len(b), _lib.CLASSES), dtype=np.float32) for _ in range(3))
+        check(self.lib.gnn_attribute(self.ctx, b.ctypes.data, len(b), _lib.PRECISIONS[precision], int(bin), contrib.ctypes.data,
+                                     bias.ctypes.data, logits.ctypes.data, scores.ctypes.data))
+        return contrib, bias, logits, scores
+
+    def attribute_dev(self, bases_ptr: int, n: int, bin: int, contrib_ptr: int, precision=_lib.DEFAULT_PRECISION, bias_ptr=None,
+                      logits_ptr=None, scores_ptr=None):
+        """Asynchronous: device pointers in and out (contrib: n x 2 x nb x 3 f32; bias, logits, scores: n x 3 f32 or None),
+        enqueued on the engine's stream (``gnn_attribute_dev``)."""
+        check(self.lib.gnn_attribute_dev(self.ctx, bases_ptr, int(n), _lib.PRECISIONS[precision], int(bin), contrib_ptr, bias_ptr,
+                                         logits_ptr, scores_ptr))
+
+    def _attribute_contigs(self, seq, offsets, bin, single_window, precision):
+        """gnn_attribute_contigs -> AttributionResult"""
+        (ptr, on_host, nbytes, offsets, n_contigs), _keep = self._packed(seq, offsets)
+        win_off, _, starts, lens = self.scan_plan(offsets, _lib.WINDOW, single_window)
+        n = len(starts)
+        nb = self.attribution_bins(bin) if 1 <= int(bin) <= _lib.POOLED else 1
+        contrib = np.zeros((n, 2, nb, _lib.CLASSES), dtype=np.float32)
+        bias, logits, scores = (np.zeros((n, _lib.CLASSES), dtype=np.float32) for _ in range(3))
+        kept = np.zeros(n, dtype=np.uint8)
+        contig_scores = np.zeros((n_contigs, _lib.CLASSES), dtype=np.float32)
+        check(self.lib.gnn_attribute_contigs(self.ctx, ptr, on_host, nbytes, offsets.ctypes.data, n_contigs, int(bin),
+                                             int(bool(single_window)), _lib.PRECISIONS[precision], contrib.ctypes.data, n,
+                                             bias.ctypes.data, logits.ctypes.data, scores.ctypes.data, kept.ctypes.data,
+                                             contig_scores.ctypes.data))
+        return AttributionResult(bin=int(bin), win_offsets=win_off, starts=starts, lens=lens, kept=kept.astype(bool),
+                                 window_scores=scores, contrib=contrib, bias=bias, logits=logits, contig_scores=contig_scores)
+
+    def attribute_contigs(self, seq: np.ndarray, offsets: np.ndarray, bin: int = 1, single_window: bool = False,
+                          precision=_lib.DEFAULT_PRECISION) -> AttributionResult:
+        """Contribution maps of every window of every contig (``gnn_attribute_contigs``): the windows, ``kept`` and
+        ``contig_scores`` of :meth:`classify_contigs`, the window scores of ``scan_contigs(stride=6000)``, and per window the maps
+        of :meth:`attribute` - in the same forward pass, with no extra one."""
+        return self._attribute_contigs(np.asarray(seq), offsets, bin, single_window, precision)
+
+    def attribute_contigs_dev(self, seq_ptr: int, offsets: np.ndarray, bin: int = 1, single_window: bool = False,
+                              precision=_lib.DEFAULT_PRECISION) -> AttributionResult:
+        """Same as :meth:`attribute_contigs` for a packed contig buffer that is already resident in HBM."""
+        return self._attribute_contigs(seq_ptr, offsets, bin, single_window, precision)
 
     # -- both strands --------------------------------------------------------------------
     def revcomp_spans_dev(self, seq_ptr: int, starts, lens, bases_ptr: int):

@@ -74,6 +74,9 @@ class Outputs:
         # written only when GENOMAD_AMD_OCCLUSION_BLOCK is set (occlusion maps of the contigs; no counterpart in the reference)
         self.nn_occlusion_output = d / f"{p}_nn_occlusion.npz"
         self.provirus_nn_occlusion_output = d / f"{p}_provirus_nn_occlusion.npz"
+        # written only when GENOMAD_AMD_ATTRIBUTION_BIN is set (attention contribution maps of the windows; no counterpart in the reference)
+        self.nn_attribution_output = d / f"{p}_nn_attribution.npz"
+        self.provirus_nn_attribution_output = d / f"{p}_provirus_nn_attribution.npz"
         f = o / f"{p}_find_proviruses"
         self.find_proviruses_execution_info = f / f"{p}_find_proviruses.json"
         self.find_proviruses_output = f / f"{p}_provirus.tsv"
@@ -434,6 +437,45 @@ def _occlusion_block_of_file(path):
         return -1
 
 
+def attribute_contigs_safely(eng, seq, offsets, bin, single_window, precision, console=None):
+    """NNEngine.attribute_contigs with the range fallback of :func:`_range_fallback`: a piece with a non-finite window score is
+    attributed again with the next arithmetic, and everything returned is that run's."""
+    def run(a):
+        res = eng.attribute_contigs(seq, offsets, bin, single_window, a)
+        return res.window_scores, res
+    _, res, _ = _with_range_fallback(run, precision, console)
+    return res
+
+
+ATTRIBUTION_POSITIONS = 749          # pooled positions per attention head (GNN_POOLED)
+
+
+def attribution_bin_requested():
+    """GENOMAD_AMD_ATTRIBUTION_BIN=<int in [1, 749]>: main() also writes the attention contribution maps of the windows
+    (<prefix>_nn_attribution.npz): each bin of that many pooled positions' share of every window's logits, computed in the pass that
+    scores the window; unset or empty: nothing changes (None).  Any other value is an error."""
+    v = os.environ.get("GENOMAD_AMD_ATTRIBUTION_BIN", "").strip()
+    if not v:
+        return None
+    try:
+        bin_ = int(v)
+    except ValueError:
+        bin_ = 0
+    if not 1 <= bin_ <= ATTRIBUTION_POSITIONS:
+        raise ValueError(f"GENOMAD_AMD_ATTRIBUTION_BIN={v!r}: expected an integer in [1, {ATTRIBUTION_POSITIONS}] (pooled positions per bin of the map)")
+    return bin_
+
+
+def _attribution_bin_of_file(path):
+    """The bin a stage's attribution file was computed with; no file = None (no attribution was asked for)."""
+    if not Path(path).exists():
+        return None
+    try:
+        return int(np.load(path)["bin"])
+    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
+        return -1
+
+
 def strand_contigs_safely(eng, seq, offsets, strand, single_window, precision, embed=False, console=None):
     """NNEngine.classify_contigs_strand, asking for each strand's own scores, with the range fallback of :func:`_range_fallback`:
     a non-finite score on EITHER strand sends the piece to the next arithmetic.  (scores, embeddings or None, ids, forward, reverse)."""
@@ -605,6 +647,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     scan_stride = scan_stride_requested()
     strand = strand_requested()
     occlusion_block = occlusion_block_requested()
+    attribution_bin = attribution_bin_requested()
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -644,6 +687,19 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     if occlusion_block is not None and strand != "forward":
         console.error(f"GENOMAD_AMD_OCCLUSION_BLOCK is forward-strand only: it cannot be combined with GENOMAD_AMD_STRAND={strand}. "
                       "Unset GENOMAD_AMD_STRAND or GENOMAD_AMD_OCCLUSION_BLOCK.")
+        sys.exit(1)
+
+    if attribution_bin is not None and not device_front_end:
+        console.error("GENOMAD_AMD_ATTRIBUTION_BIN needs the device front end: the host front end (GENOMAD_AMD_FRONT_END=host) does "
+                      "not compute contribution maps. Unset GENOMAD_AMD_FRONT_END or GENOMAD_AMD_ATTRIBUTION_BIN.")
+        sys.exit(1)
+    if attribution_bin is not None and configured_precision() == "f16c6":
+        console.error("GENOMAD_AMD_ATTRIBUTION_BIN cannot be combined with GENOMAD_AMD_PRECISION=f16c6: the maps are the gradient of the "
+                      "exact f32 dense head, which that arithmetic does not run. Unset GENOMAD_AMD_PRECISION or GENOMAD_AMD_ATTRIBUTION_BIN.")
+        sys.exit(1)
+    if attribution_bin is not None and strand != "forward":
+        console.error(f"GENOMAD_AMD_ATTRIBUTION_BIN is forward-strand only: it cannot be combined with GENOMAD_AMD_STRAND={strand}. "
+                      "Unset GENOMAD_AMD_STRAND or GENOMAD_AMD_ATTRIBUTION_BIN.")
         sys.exit(1)
 
     def everywhere(*flags):
@@ -767,7 +823,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         if rank0:
             write_tsv(tsv_path, names, predictions)                                  # :340-352 (always rewritten)
 
-    def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, strand_path, occ_path, emb_path=None, scan_path=None):
+    def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, strand_path, occ_path, attr_path, emb_path=None,
+                     scan_path=None):
         """Product path: the contig front end (NNEngine.classify_contigs) does windowing, the N rule,
         tokenising, classification and the per-contig mean on the GPU, so encoding and classification
         are one step; ``<prefix>_seq_window_id.npz`` is still written.  With several ranks the CONTIGS are
@@ -785,9 +842,13 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         ``occ_path`` (GENOMAD_AMD_OCCLUSION_BLOCK): after its normal classification every piece is also occluded with blocks of that
         size (NNEngine.occlude_contigs) and the maps are written there.  The file follows the strand file's rule: it says which block
         size the stage was run with (absent: none), a run that asks for another runs the stage again, and one that asks for none
-        removes it."""
+        removes it.
+        ``attr_path`` (GENOMAD_AMD_ATTRIBUTION_BIN): after its normal classification every piece also goes through
+        NNEngine.attribute_contigs with bins of that many pooled positions, and the maps are written there.  The file follows the
+        occlusion file's rule, with the bin in place of the block."""
         (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and _strand_of_file(strand_path) == strand
                                  and _occlusion_block_of_file(occ_path) == occlusion_block
+                                 and _attribution_bin_of_file(attr_path) == attribution_bin
                                  and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
                                  and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
                                                             and _npz_strand(scan_path) == strand)))   # :284-292
@@ -804,7 +865,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             eng = _engine()
             size = Path(fasta).stat().st_size * (1 if sequence.compression_of(fasta) == "uncompressed" else 4)
             precision = select_arithmetic(eng, precision, size, comm, console)
-            parts, emb_parts, scan_parts, strand_parts, occ_parts = [], [], [], [], []
+            parts, emb_parts, scan_parts, strand_parts, occ_parts, attr_parts = [], [], [], [], [], []
             sentinel = {"d": None, "done": False}
 
             def classify(key, nm, sq, off):
@@ -817,6 +878,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     scan_parts.append((key, scan_contigs_strand_safely(eng, sq, off, scan_stride, strand, single_window, precision, console)))
                 if occlusion_block is not None:                         # likewise after, and beside, the normal classification
                     occ_parts.append((key, occlude_contigs_safely(eng, sq, off, occlusion_block, single_window, precision, console)))
+                if attribution_bin is not None:
+                    attr_parts.append((key, attribute_contigs_safely(eng, sq, off, attribution_bin, single_window, precision, console)))
 
             def classify_piece(key, sq, off):
                 if not sentinel["done"] and len(off) > 1:           # this rank's first piece with a contig: the run's parity sample
@@ -873,6 +936,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             scans_all = sharding.gather_contig_scans(comm, scan_parts, extra_window_fields=strand_fields) if scan_path is not None else None
             strands_all = sharding.gather_contig_strand_scores(comm, strand_parts) if strand != "forward" else None
             occ_all = sharding.gather_contig_occlusions(comm, occ_parts) if occlusion_block is not None else None
+            attr_all = (sharding.gather_contig_attributions(comm, attr_parts, -(-ATTRIBUTION_POSITIONS // attribution_bin))
+                        if attribution_bin is not None else None)
             gate()
             if not n_windows:                                                        # :297-299
                 console.error("No sequences were found. Please check your input FASTA.")
@@ -911,6 +976,12 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                 f"written to {occ_path.name}.")
                 elif occ_path.exists():             # no occlusion was asked for: the file that said otherwise goes
                     occ_path.unlink()
+                if attribution_bin is not None:
+                    np.savez_compressed(attr_path, **{names_key: names, "bin": np.int64(attribution_bin), **attr_all})
+                    console.log(f"Attention contribution maps of the {what}s (bins of {attribution_bin} pooled positions, "
+                                f"{len(attr_all['contrib'])} windows) written to {attr_path.name}.")
+                elif attr_path.exists():            # likewise
+                    attr_path.unlink()
         if cleanup and rank0 and enc_dir.is_dir():
             console.log(f"Deleting encoded {what} data.")
             shutil.rmtree(enc_dir)
@@ -920,16 +991,17 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     run = stage_device if device_front_end else stage
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
     scan_kw = (lambda path: {"scan_path": path}) if scan_stride is not None else (lambda path: {})
-    strand_kw = (lambda path, occ: {"strand_path": path, "occ_path": occ}) if device_front_end else (lambda path, occ: {})
+    strand_kw = ((lambda path, occ, attr: {"strand_path": path, "occ_path": occ, "attr_path": attr}) if device_front_end
+                 else (lambda path, occ, attr: {}))
     try:
         run(input_path, outputs.encoded_sequences_dir, outputs.seq_window_id_output,
             outputs.nn_classification_npz_output, outputs.nn_classification_output,
-            "contig_names", "contig_ids", "sequence", **strand_kw(outputs.nn_strand_output, outputs.nn_occlusion_output), **emb_kw(outputs.nn_embeddings_output),
+            "contig_names", "contig_ids", "sequence", **strand_kw(outputs.nn_strand_output, outputs.nn_occlusion_output, outputs.nn_attribution_output), **emb_kw(outputs.nn_embeddings_output),
             **scan_kw(outputs.nn_scan_output))
         if classify_proviruses:                                                      # :248-281, :355-425
             run(outputs.find_proviruses_nucleotide_output, outputs.encoded_proviruses_dir,
                 outputs.provirus_window_id_output, outputs.provirus_nn_classification_npz_output,
-                outputs.provirus_nn_classification_output, "provirus_names", "provirus_ids", "provirus", **strand_kw(outputs.provirus_nn_strand_output, outputs.provirus_nn_occlusion_output),
+                outputs.provirus_nn_classification_output, "provirus_names", "provirus_ids", "provirus", **strand_kw(outputs.provirus_nn_strand_output, outputs.provirus_nn_occlusion_output, outputs.provirus_nn_attribution_output),
                 **emb_kw(outputs.provirus_nn_embeddings_output), **scan_kw(outputs.provirus_nn_scan_output))
     finally:
         if check_pool is not None:

@@ -260,20 +260,17 @@ OCCLUSION_EMPTY = {"starts": np.zeros(0, np.int64), "lens": np.zeros(0, np.int32
                    "contig_scores": np.zeros((0, 3), np.float32)}
 
 
-def gather_contig_occlusions(comm, parts, root: int = 0):
-    """Occlusion maps of contig-sharded pieces -> ``root``, in the piece order of :func:`gather_contig_parts`: the sibling of
-    :func:`gather_contig_scans`, by the same mechanism.  ``parts`` = this rank's list of (order_key, result) with the keys and contig
-    counts of the pieces handed to gather_contig_parts; ``result`` = the arrays of one ``NNEngine.occlude_contigs`` call (win_offsets,
-    starts, lens, kept, scores, blk_offsets, delta, contig_scores; an object with ``asdict()`` or a dict).  Each rank's pieces travel
-    as one byte string; ``root`` concatenates them and rebases the two CSR arrays - win_offsets over contigs, blk_offsets over
-    windows; the values are only moved, so the result is bit-identical for any number of ranks.  Returns a dict of those eight
-    arrays on ``root``, None elsewhere."""
+def _gather_csr_pieces(comm, parts, csr, fields, empty, what, root):
+    """The mechanism of the occlusion and attribution gathers.  ``parts`` = this rank's list of (order_key, result), a result being
+    an object with ``asdict()`` or a dict of arrays.  Each rank's pieces travel as one byte string (:func:`gather_bytes`); ``root``
+    sorts them by key, concatenates every array of ``fields`` and rebases the CSR arrays: ``csr`` = (name, ...), each continued by
+    its own last entry.  The values are only moved.  ``empty``: what a field is when there is no piece at all.  Returns the dict
+    on ``root``, None elsewhere."""
     comm = comm or LocalComm()
-    fields = ("win_offsets", "blk_offsets") + OCCLUSION_WINDOW_FIELDS + ("delta", "contig_scores")
     arrays = {"keys": np.array([int(key) for key, _ in parts], dtype="<i8")}
     for i, (_, res) in enumerate(parts):
         res = res.asdict() if hasattr(res, "asdict") else res
-        for f in fields:
+        for f in csr + fields:
             arrays[f"{i}_{f}"] = np.ascontiguousarray(res[f])
     buf = io.BytesIO()
     np.savez(buf, **arrays)
@@ -284,20 +281,45 @@ def gather_contig_occlusions(comm, parts, root: int = 0):
     for blob in blobs:
         z = np.load(io.BytesIO(blob))
         for i, key in enumerate(z["keys"]):
-            pieces.append((int(key), {f: z[f"{i}_{f}"] for f in fields}))
+            pieces.append((int(key), {f: z[f"{i}_{f}"] for f in csr + fields}))
     if len({p[0] for p in pieces}) != len(pieces):
-        raise ValueError("duplicate piece keys in gather_contig_occlusions")
+        raise ValueError(f"duplicate piece keys in {what}")
     pieces.sort(key=lambda p: p[0])
-    out = {"win_offsets": [np.zeros(1, np.int64)], "blk_offsets": [np.zeros(1, np.int64)]}
-    out.update({f: [] for f in fields[2:]})
-    w0 = p0 = 0
+    out = {f: [np.zeros(1, np.int64)] for f in csr}
+    out.update({f: [] for f in fields})
+    base = {f: 0 for f in csr}
     for _, d in pieces:
-        out["win_offsets"].append(d["win_offsets"][1:].astype(np.int64) + w0)
-        out["blk_offsets"].append(d["blk_offsets"][1:].astype(np.int64) + p0)
-        w0, p0 = w0 + int(d["win_offsets"][-1]), p0 + int(d["blk_offsets"][-1])
-        for f in fields[2:]:
+        for f in csr:
+            out[f].append(d[f][1:].astype(np.int64) + base[f])
+            base[f] += int(d[f][-1])
+        for f in fields:
             out[f].append(d[f])
-    return {f: np.concatenate(v) if v else OCCLUSION_EMPTY[f] for f, v in out.items()}
+    return {f: np.concatenate(v) if v else empty[f] for f, v in out.items()}
+
+
+def gather_contig_occlusions(comm, parts, root: int = 0):
+    """Occlusion maps of contig-sharded pieces -> ``root``, in the piece order of :func:`gather_contig_parts`: the sibling of
+    :func:`gather_contig_scans`.  ``parts`` = this rank's list of (order_key, result) with the keys and contig counts of the pieces
+    handed to gather_contig_parts; ``result`` = the arrays of one ``NNEngine.occlude_contigs`` call (win_offsets, starts, lens, kept,
+    scores, blk_offsets, delta, contig_scores; an object with ``asdict()`` or a dict).  ``root`` rebases the two CSR arrays -
+    win_offsets over contigs, blk_offsets over windows; the values are only moved, so the result is bit-identical for any number of
+    ranks.  Returns a dict of those eight arrays on ``root``, None elsewhere."""
+    return _gather_csr_pieces(comm, parts, ("win_offsets", "blk_offsets"), OCCLUSION_WINDOW_FIELDS + ("delta", "contig_scores"),
+                              OCCLUSION_EMPTY, "gather_contig_occlusions", root)
+
+
+ATTRIBUTION_WINDOW_FIELDS = ("starts", "lens", "kept", "window_scores", "contrib", "bias", "logits")      # per window
+
+
+def gather_contig_attributions(comm, parts, nb: int, root: int = 0):
+    """Contribution maps of contig-sharded pieces -> ``root``, by the mechanism of :func:`gather_contig_occlusions`.  ``result`` =
+    the arrays of one ``NNEngine.attribute_contigs`` call, every map with ``nb`` bins; win_offsets is the one CSR array.  Returns a
+    dict of win_offsets, the per-window arrays and contig_scores on ``root``, None elsewhere."""
+    row = np.zeros((0, 3), np.float32)
+    empty = {"starts": np.zeros(0, np.int64), "lens": np.zeros(0, np.int32), "kept": np.zeros(0, bool), "window_scores": row,
+             "contrib": np.zeros((0, 2, int(nb), 3), np.float32), "bias": row, "logits": row, "contig_scores": row}
+    return _gather_csr_pieces(comm, parts, ("win_offsets",), ATTRIBUTION_WINDOW_FIELDS + ("contig_scores",), empty,
+                              "gather_contig_attributions", root)
 
 
 def gather_contig_results(comm, names, predictions, window_ids, root: int = 0):

@@ -397,6 +397,42 @@ int gnn_occlude_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64
                         uint8_t* window_kept_host_or_null, int64_t windows_capacity, float* delta_host,
                         int64_t pairs_capacity, float* contig_scores_host_or_null);
 
+/* ---- attention contribution maps: each pooled position's share of a logit ("Attention contribution maps") -------------
+ * The encoder ends in two attention sums over 749 pooled positions, feat[h*128 + ch] = sum_q alpha[h][q] yp[h][q][ch] (h = head A, B;
+ * igloo.py:208-214), and the dense head behind them is piecewise linear.  For the window's own ReLU pattern logit_c = g_c . feat +
+ * bias_c with g_c = d logit_c / d feat, so every logit decomposes exactly, signed and per class, over (head, pooled position):
+ *   contrib   contrib[h][q][c] = alpha[h][q] * sum_ch yp[h][q][ch] g_c[h*128 + ch]; sum_h sum_q contrib + bias_c = logit_c.
+ *             Gradient x input at the attention layer with alpha held fixed, in logit units; bias is the same-sign-pattern remainder.
+ *   masks     the device's own: a hidden unit is active iff the value the dense head stores for it is > 0.
+ *   bins      `bin` pooled positions per output bin, 1 <= bin <= 749: nb = ceil(749 / bin), bin b = [b bin, min((b + 1) bin, 749)),
+ *             the last one may be short.  A position's value does not depend on bin: the map at bin = k is, bit for bit, the f32
+ *             sums in increasing q of the bin = 1 map.
+ *   position  q of either head is the max-pool of tokens 8q .. 8q + 7, whose 4-mers span bases 8q .. 8q + 10; each token's features
+ *             see further back through the causal convolutions (5 tokens for head A, 15 for head B).  Tokens 5992 .. 5996 belong to
+ *             no position.  The pad positions of a short window carry contributions like any other.
+ *   not       a prediction of what an edit would do: alpha depends on the whole window (gnn_occlude_contigs answers that).
+ * Costs no extra forward pass: the maps are computed from the back end's workspace of the launch that scores the window; the scores
+ * of this path are bit-identical to gnn_classify.  Every arithmetic with the f32 dense head; GNN_PREC_F16C6: GNN_ERR_ARG, the
+ * message names it.  A bin outside [1, 749]: GNN_ERR_ARG, the message gives the range.  Forward strand only.
+ * contrib[n][2][nb][3] f32; bias[n][3], logits[n][3] (pre-softmax) and scores[n][3] may be NULL.
+ * gnn_attribute: host pointers, synchronous, chunked like gnn_embed.  gnn_attribute_dev: device pointers, asynchronous on the ctx
+ * stream like gnn_embed_dev. */
+int gnn_attribute(gnn_ctx* ctx, const uint8_t* bases_host, int64_t n_windows, int precision, int bin, float* contrib_host,
+                  float* bias_host_or_null, float* logits_host_or_null, float* scores_host_or_null);
+int gnn_attribute_dev(gnn_ctx* ctx, const uint8_t* bases_dev, int64_t n_windows, int precision, int bin, float* contrib_dev,
+                      float* bias_dev_or_null, float* logits_dev_or_null, float* scores_dev_or_null);
+/* The maps of a packed contig buffer (seq, seq_on_host, seq_bytes, offsets_host as gnn_classify_contigs).  The window table is that
+ * of gnn_classify_contigs: its sizes, starts and lengths are gnn_scan_plan's at stride 6000.  Every window is attributed; kept is a
+ * mask, as in the scan.  contrib_host[n_windows][2][nb][3], capacity windows_capacity windows - too small is GNN_ERR_ARG and the
+ * message names the size needed; bias, logits, window_scores [n_windows][3], window_kept [n_windows], contig_scores [n_contigs][3] may
+ * be NULL.  Window scores are bit-identical to gnn_scan_contigs at stride 6000, contig scores and kept to gnn_classify_contigs, maps,
+ * bias and logits to gnn_attribute on the same bytes.  Synchronous.  The maps are copied out slab by slab (4 launches): device
+ * memory, persistent in the ctx and grow-only, is 24 nb + 24 B per window of ONE slab beside gnn_classify_contigs' own tables. */
+int gnn_attribute_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes, const int64_t* offsets_host,
+                          int64_t n_contigs, int bin, int single_window, int precision, float* contrib_host, int64_t windows_capacity,
+                          float* bias_host_or_null, float* logits_host_or_null, float* window_scores_host_or_null,
+                          uint8_t* window_kept_host_or_null, float* contig_scores_host_or_null);
+
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
  * in-memory text buffer (already decompressed, newlines normalised to '\n').
@@ -476,7 +512,9 @@ int gnn_synth_windows_dev(gnn_ctx* ctx, uint64_t seed, int64_t first, int64_t n_
 #define GNN_K_BACKEND 1      /* logits GEMM + softmax + attention + dense stack           */
 #define GNN_K_ENCODER 2      /* stand-alone byte -> one-hot encoder                       */
 #define GNN_K_F32_FRONT 3    /* unfused f32 front end (all its kernels)                   */
-#define GNN_K_COUNT 4
+#define GNN_K_ATTR_HEAD 4    /* attribution: dense head forward + backward (gnn_attribute*)  */
+#define GNN_K_ATTR_CONTRIB 5 /* attribution: the contribution kernel (second read of yp)     */
+#define GNN_K_COUNT 6
 int gnn_profile_enable(gnn_ctx* ctx, int on);
 int gnn_profile_reset(gnn_ctx* ctx);
 /* synchronises the stream, then total milliseconds and number of launches of kernel_id */
