@@ -30,33 +30,6 @@ bool debug_switch(const char* name) {
     return on;
 }
 
-struct ProfScope {
-    gnn_ctx* ctx;
-    int id;
-    hipEvent_t a = nullptr, b = nullptr;
-    ProfScope(gnn_ctx* c, int kid) : ctx(c), id(kid) {
-        if (!ctx->profile) return;
-        auto take = [&]() {
-            hipEvent_t e = nullptr;
-            if (!ctx->event_pool.empty()) {
-                e = ctx->event_pool.back();
-                ctx->event_pool.pop_back();
-            } else if (hipEventCreate(&e) != hipSuccess) {
-                e = nullptr;
-            }
-            return e;
-        };
-        a = take();
-        b = take();
-        if (a) (void)hipEventRecord(a, ctx->stream);
-    }
-    ~ProfScope() {
-        if (!ctx->profile || !a || !b) return;
-        (void)hipEventRecord(b, ctx->stream);
-        ctx->prof[id].pending.emplace_back(a, b);
-    }
-};
-
 static void free_ws(Workspace& ws) { ws = Workspace(); }
 
 // bytes of workspace per window of a fused launch (mp, m, yp, logits, alpha, feat): 0.86 MB

@@ -128,6 +128,30 @@ constexpr int MIN_TAIL = 2500;        // nn_classification.py:68  seq_windows(se
 constexpr int MAX_N = 4000;           // nn_classification.py:70  window_n > 0 and count("N") > 4000 -> skip
 constexpr int64_t PIECE = 64ll << 20; // bytes per host->device piece of the sequence buffer
 
+// ---- region calls (gnn_regions.hip): persistent, grow-only; a sibling of the other groups of ContigWorkspace ----
+// Per contig 16 B (bin and tile CSR), per tile of `tile` bins 98 B (transfer matrix 72, entry vector 24, composed back pointers 1,
+// exit state 1), per bin 1 B (back pointers) - what gnn_region_states_dev needs - and, for gnn_call_regions alone, 14 B per bin (the
+// track 12, the states 1, the flags 1), 12 B per 256 bins (the block tables) and 65 B per region.
+struct RegionWorkspace {
+    int tile = 256;                              // bins per tile (gnn_debug_set_region_tile); no result depends on it
+    PinnedBuf<int64_t> h_off;                    // host image of d_off; rewritten only after `tables_read`
+    hipEvent_t tables_read = nullptr;            // recorded behind the upload of h_off
+    DevBuf<int64_t> d_off;                       // [bin_off (n_contigs + 1) | tile_off (n_contigs + 1)]
+    DevBuf<int64_t> d_transfer, d_entry;         // 9 and 3 per tile
+    DevBuf<uint8_t> d_comp, d_exit;              // 1 per tile each
+    DevBuf<uint8_t> d_psi;                       // 1 per bin
+    // gnn_call_regions
+    DevBuf<float> d_track;                       // 3 per bin
+    DevBuf<uint8_t> d_state, d_flag;             // 1 per bin each
+    DevBuf<int32_t> d_blk_count;                 // flags per block of 256 bins
+    DevBuf<int64_t> d_blk_off;                   // their exclusive prefix sums, then the total
+    DevBuf<int64_t> d_r_contig, d_r_lo, d_r_hi, d_r_evidence, d_r_qsum;      // 1, 1, 1, 1 and 3 per region
+    DevBuf<uint8_t> d_r_state;
+    ~RegionWorkspace() {
+        if (tables_read) (void)hipEventDestroy(tables_read);
+    }
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -162,6 +186,8 @@ struct ContigWorkspace {
     DevBuf<float> d_occ;
     // gnn_attribute_contigs (gnn_attrib.hip): ONE slab's maps, bias and logits (24 nb + 24 B per window of the slab)
     DevBuf<float> d_attr;
+    // gnn_call_regions / gnn_region_states_dev (gnn_regions.hip)
+    RegionWorkspace regions;
 
     // What the buffer groups hold, in windows / contigs + 1 / bins.  The head-room is counted in elements, so a buffer with
     // several elements per window or bin holds fewer of them than its neighbours: the smallest member decides.
@@ -315,6 +341,34 @@ struct gnn_ctx {
 };
 
 namespace gnn {
+
+// HIP-event timing of what is enqueued on ctx->stream while the scope lives, filed under kernel id `id` (gnn_profile_get)
+struct ProfScope {
+    gnn_ctx* ctx;
+    int id;
+    hipEvent_t a = nullptr, b = nullptr;
+    ProfScope(gnn_ctx* c, int kid) : ctx(c), id(kid) {
+        if (!ctx->profile) return;
+        auto take = [&]() {
+            hipEvent_t e = nullptr;
+            if (!ctx->event_pool.empty()) {
+                e = ctx->event_pool.back();
+                ctx->event_pool.pop_back();
+            } else if (hipEventCreate(&e) != hipSuccess) {
+                e = nullptr;
+            }
+            return e;
+        };
+        a = take();
+        b = take();
+        if (a) (void)hipEventRecord(a, ctx->stream);
+    }
+    ~ProfScope() {
+        if (!ctx->profile || !a || !b) return;
+        (void)hipEventRecord(b, ctx->stream);
+        ctx->prof[id].pending.emplace_back(a, b);
+    }
+};
 
 // The one way a weight pack reaches the device: an allocation ctx->owned keeps until gnn_destroy, filled from the host.
 template <typename Tp>

@@ -92,6 +92,36 @@ class AttributionResult:
         return {k: getattr(self, k) for k in self.FIELDS}
 
 
+class RegionResult:
+    """What :meth:`NNEngine.call_regions` returns (the definition is ``sequence.call_regions``).  ``penalty``; bins (CSR over contigs
+    by ``bin_offsets``): ``state`` (n_bins,) uint8, the path's class per bin.  Regions, ordered by contig, then position:
+    ``region_contig``, ``region_lo``, ``region_hi`` (int64; contig-relative bins, half-open), ``region_state`` (uint8),
+    ``region_evidence`` (int64) and ``region_qsum`` (n_regions, 3) int64.  With ``offsets`` and ``stride`` given also the derived
+    table of ``sequence.region_table``: ``stride``, ``start``, ``end`` (bases), ``mean`` (n_regions, 3), ``margin``; None otherwise."""
+    FIELDS = ("penalty", "bin_offsets", "state", "region_contig", "region_lo", "region_hi", "region_state", "region_evidence",
+              "region_qsum", "stride", "start", "end", "mean", "margin")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw.get(k))
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    @property
+    def regions(self) -> dict:
+        """the six region arrays under the names of ``sequence.call_regions``"""
+        return {k: getattr(self, "region_" + k) for k in ("contig", "lo", "hi", "state", "evidence", "qsum")}
+
+    @classmethod
+    def build(cls, penalty, bin_offsets, state, regions, offsets=None, stride=None):
+        """from the output of ``sequence.call_regions`` or the library; the table where ``offsets`` and ``stride`` are given"""
+        from . import sequence as S
+        table = S.region_table(regions, offsets, stride) if offsets is not None and stride is not None else {}
+        return cls(penalty=float(penalty), bin_offsets=bin_offsets, state=state, **{"region_" + k: v for k, v in regions.items()},
+                   stride=None if stride is None else int(stride), **table)
+
+
 class NNEngine:
     def __init__(self, device: int = 0, weights: dict = None, chunk: int = None):
         self.lib = _lib.load()
@@ -401,6 +431,51 @@ class NNEngine:
                          precision=_lib.DEFAULT_PRECISION) -> ScanResult:
         """Same as :meth:`scan_contigs` for a packed contig buffer that is already resident in HBM."""
         return self._scan_contigs(seq_ptr, offsets, stride, single_window, precision)
+
+    # -- region calls --------------------------------------------------------------------
+    def set_region_tile(self, bins: int):
+        """test aid (``gnn_debug_set_region_tile``): bins per tile of the region kernels' scan, 1..4096; no result depends on it."""
+        check(self.lib.gnn_debug_set_region_tile(self.ctx, int(bins)))
+
+    def call_regions(self, track, bin_offsets, penalty, offsets=None, stride=None) -> RegionResult:
+        """Region calls along contigs (``gnn_call_regions``; the definition is ``sequence.call_regions``): one 3-state Viterbi path
+        per contig over the track of a scan (``track`` (n_bins, 3), ``bin_offsets``: any strand mode's), a switch between classes
+        costing ``penalty`` (0..4096, in score x bins: a run of n bins is split off when its summed advantage exceeds 2 x penalty).
+        Integer arithmetic on the device: bit-identical to the numpy definition.  ``offsets`` (the contigs' byte offsets) and
+        ``stride`` add base coordinates, means and margins (``sequence.region_table``)."""
+        track = np.ascontiguousarray(track, dtype=np.float32).reshape(-1, _lib.CLASSES)
+        bin_off = self._offsets(bin_offsets)
+        n_contigs, n_bins = len(bin_off) - 1, int(bin_off[-1])
+        if len(track) != n_bins:
+            raise ValueError(f"the track has {len(track)} bins, bin_offsets end at {n_bins}")
+        state = np.zeros(n_bins, dtype=np.uint8)
+        n = C.c_int64(0)
+        cap = n_contigs + n_bins // 16 + 1024           # a guess: the call says what it needs when this is too small
+        while True:
+            arrs = {"contig": np.zeros(cap, np.int64), "lo": np.zeros(cap, np.int64), "hi": np.zeros(cap, np.int64),
+                    "state": np.zeros(cap, np.uint8), "evidence": np.zeros(cap, np.int64), "qsum": np.zeros((cap, _lib.CLASSES), np.int64)}
+            rc = self.lib.gnn_call_regions(self.ctx, track.ctypes.data, bin_off.ctypes.data, n_contigs, float(penalty), state.ctypes.data,
+                                           *(a.ctypes.data for a in arrs.values()), cap, C.byref(n))
+            if rc == _lib.ERR_ARG and n.value > cap:
+                cap = n.value
+                continue
+            check(rc)
+            break
+        regions = {k: a[:n.value].copy() for k, a in arrs.items()}
+        return RegionResult.build(penalty, bin_off, state, regions, offsets, stride)
+
+    def region_states_dev(self, track_ptr: int, bin_offsets, penalty, state_ptr: int):
+        """Asynchronous building block (``gnn_region_states_dev``): track (n_bins x 3 f32) and states (n_bins uint8) are device
+        pointers; the path's state per bin is enqueued on the engine's stream."""
+        bin_off = self._offsets(bin_offsets)
+        check(self.lib.gnn_region_states_dev(self.ctx, track_ptr, bin_off.ctypes.data, len(bin_off) - 1, float(penalty), state_ptr))
+
+    def scan_regions(self, seq: np.ndarray, offsets: np.ndarray, stride: int, penalty, single_window: bool = False,
+                     precision=_lib.DEFAULT_PRECISION, strand=None):
+        """:meth:`scan_contigs` (``strand`` given: :meth:`scan_contigs_strand`) followed by :meth:`call_regions` on its track.
+        Returns (the scan's result, RegionResult with the derived table)."""
+        scan = self._scan_contigs(np.asarray(seq), offsets, stride, single_window, precision, strand)
+        return scan, self.call_regions(scan.track, scan.bin_offsets, penalty, self._offsets(offsets), stride)
 
     # -- occlusion maps ------------------------------------------------------------------
     def occlusion_plan(self, offsets: np.ndarray, block: int, single_window: bool = False):

@@ -77,6 +77,11 @@ class Outputs:
         # written only when GENOMAD_AMD_ATTRIBUTION_BIN is set (attention contribution maps of the windows; no counterpart in the reference)
         self.nn_attribution_output = d / f"{p}_nn_attribution.npz"
         self.provirus_nn_attribution_output = d / f"{p}_provirus_nn_attribution.npz"
+        # written only when GENOMAD_AMD_REGION_PENALTY is set (region calls along the score tracks; no counterpart in the reference)
+        self.nn_regions_output = d / f"{p}_nn_regions.npz"
+        self.nn_regions_tsv_output = d / f"{p}_nn_regions.tsv"
+        self.provirus_nn_regions_output = d / f"{p}_provirus_nn_regions.npz"
+        self.provirus_nn_regions_tsv_output = d / f"{p}_provirus_nn_regions.tsv"
         f = o / f"{p}_find_proviruses"
         self.find_proviruses_execution_info = f / f"{p}_find_proviruses.json"
         self.find_proviruses_output = f / f"{p}_provirus.tsv"
@@ -476,6 +481,50 @@ def _attribution_bin_of_file(path):
         return -1
 
 
+def region_penalty_requested():
+    """GENOMAD_AMD_REGION_PENALTY=<float in [0, 4096]>: main() also calls regions along the score tracks of GENOMAD_AMD_SCAN_STRIDE
+    (<prefix>_nn_regions.npz and .tsv): a Viterbi segmentation in which a switch between classes costs that many score x bins;
+    unset or empty: nothing changes (None).  Any other value is an error."""
+    v = os.environ.get("GENOMAD_AMD_REGION_PENALTY", "").strip()
+    if not v:
+        return None
+    try:
+        penalty = float(v)
+    except ValueError:
+        penalty = -1.0
+    if not 0.0 <= penalty <= sequence.REGION_PENALTY_MAX:
+        raise ValueError(f"GENOMAD_AMD_REGION_PENALTY={v!r}: expected a number in [0, {sequence.REGION_PENALTY_MAX:g}] (the cost of a switch "
+                         "between classes, in score x bins)")
+    return penalty
+
+
+def _regions_of_file(path):
+    """(stride, penalty) a stage's region file was computed with; no file = None (no regions were asked for)."""
+    if not Path(path).exists():
+        return None
+    try:
+        z = np.load(path)
+        return int(z["stride"]), float(z["penalty"])
+    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
+        return -1, -1.0
+
+
+REGION_TSV_HEADER = ("seq_name\tstart\tend\tclass\tn_bins\tevidence_bins\t"
+                     + "\t".join("mean_" + c[:-len("_score")] for c in TSV_HEADER.split()[1:]) + "\tmargin\n")
+
+
+def write_regions_tsv(path, names, res):
+    """One line per region of a RegionResult with its table: coordinates 0-based half-open, floats '%.4f', the class names those of
+    the classification TSV's header."""
+    classes = [c[:-len("_score")] for c in TSV_HEADER.split()[1:]]
+    with open(path, "w") as fout:
+        fout.write(REGION_TSV_HEADER)
+        for i in range(len(res.region_contig)):
+            mean = "\t".join(f"{x:.4f}" for x in res.mean[i])
+            fout.write(f"{names[res.region_contig[i]]}\t{res.start[i]}\t{res.end[i]}\t{classes[res.region_state[i]]}\t"
+                       f"{res.region_hi[i] - res.region_lo[i]}\t{res.region_evidence[i]}\t{mean}\t{res.margin[i]:.4f}\n")
+
+
 def strand_contigs_safely(eng, seq, offsets, strand, single_window, precision, embed=False, console=None):
     """NNEngine.classify_contigs_strand, asking for each strand's own scores, with the range fallback of :func:`_range_fallback`:
     a non-finite score on EITHER strand sends the piece to the next arithmetic.  (scores, embeddings or None, ids, forward, reverse)."""
@@ -648,6 +697,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     strand = strand_requested()
     occlusion_block = occlusion_block_requested()
     attribution_bin = attribution_bin_requested()
+    region_penalty = region_penalty_requested()
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -673,6 +723,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     if scan_stride is not None and not device_front_end:
         console.error("GENOMAD_AMD_SCAN_STRIDE needs the device front end: the host front end (GENOMAD_AMD_FRONT_END=host) does "
                       "not scan contigs. Unset GENOMAD_AMD_FRONT_END or GENOMAD_AMD_SCAN_STRIDE.")
+        sys.exit(1)
+    if region_penalty is not None and scan_stride is None:
+        console.error("GENOMAD_AMD_REGION_PENALTY needs GENOMAD_AMD_SCAN_STRIDE: regions are called along the score tracks of a scan. "
+                      "Set GENOMAD_AMD_SCAN_STRIDE or unset GENOMAD_AMD_REGION_PENALTY.")
         sys.exit(1)
 
     if strand != "forward" and not device_front_end:
@@ -823,8 +877,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         if rank0:
             write_tsv(tsv_path, names, predictions)                                  # :340-352 (always rewritten)
 
-    def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, strand_path, occ_path, attr_path, emb_path=None,
-                     scan_path=None):
+    def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, strand_path, occ_path, attr_path, regions_paths,
+                     emb_path=None, scan_path=None):
         """Product path: the contig front end (NNEngine.classify_contigs) does windowing, the N rule,
         tokenising, classification and the per-contig mean on the GPU, so encoding and classification
         are one step; ``<prefix>_seq_window_id.npz`` is still written.  With several ranks the CONTIGS are
@@ -845,10 +899,17 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         removes it.
         ``attr_path`` (GENOMAD_AMD_ATTRIBUTION_BIN): after its normal classification every piece also goes through
         NNEngine.attribute_contigs with bins of that many pooled positions, and the maps are written there.  The file follows the
-        occlusion file's rule, with the bin in place of the block."""
+        occlusion file's rule, with the bin in place of the block.
+        ``regions_paths`` (npz, tsv; GENOMAD_AMD_REGION_PENALTY): rank 0 calls regions (NNEngine.call_regions) on the gathered track -
+        regions are per contig, so the result does not depend on the number of ranks - and writes both files.  They follow the
+        occlusion file's rule, with (stride, penalty) in place of the block."""
+        regions_path, regions_tsv_path = regions_paths
+        regions_request = None if region_penalty is None else (scan_stride, region_penalty)
         (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and _strand_of_file(strand_path) == strand
                                  and _occlusion_block_of_file(occ_path) == occlusion_block
                                  and _attribution_bin_of_file(attr_path) == attribution_bin
+                                 and _regions_of_file(regions_path) == regions_request
+                                 and (regions_request is None) == (not regions_tsv_path.exists())
                                  and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
                                  and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
                                                             and _npz_strand(scan_path) == strand)))   # :284-292
@@ -872,10 +933,12 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                 pr, emb, wid = classify_piece(key, sq, off)
                 parts.append((key, nm, pr, wid))
                 emb_parts.append((key, emb))
-                if scan_path is not None and strand == "forward":       # after the normal classification, with the arithmetic the run selected
-                    scan_parts.append((key, scan_contigs_safely(eng, sq, off, scan_stride, single_window, precision, console)))
-                elif scan_path is not None:
-                    scan_parts.append((key, scan_contigs_strand_safely(eng, sq, off, scan_stride, strand, single_window, precision, console)))
+                if scan_path is not None:       # after the normal classification, with the arithmetic the run selected
+                    sc = (scan_contigs_safely(eng, sq, off, scan_stride, single_window, precision, console) if strand == "forward" else
+                          scan_contigs_strand_safely(eng, sq, off, scan_stride, strand, single_window, precision, console))
+                    if region_penalty is not None:                      # the region table needs every contig's length on rank 0
+                        sc = dict(sc.asdict(), contig_len=np.diff(np.asarray(off, np.int64)))
+                    scan_parts.append((key, sc))
                 if occlusion_block is not None:                         # likewise after, and beside, the normal classification
                     occ_parts.append((key, occlude_contigs_safely(eng, sq, off, occlusion_block, single_window, precision, console)))
                 if attribution_bin is not None:
@@ -933,7 +996,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             names, predictions, ids, n_windows = sharding.gather_contig_parts(comm, parts)
             embeddings_all = sharding.gather_contig_embeddings(comm, emb_parts) if emb_path is not None else None
             strand_fields = sharding.SCAN_STRAND_FIELDS if strand != "forward" else ()
-            scans_all = sharding.gather_contig_scans(comm, scan_parts, extra_window_fields=strand_fields) if scan_path is not None else None
+            length_fields = sharding.SCAN_LENGTH_FIELDS if region_penalty is not None else ()
+            scans_all = (sharding.gather_contig_scans(comm, scan_parts, extra_window_fields=strand_fields, extra_contig_fields=length_fields)
+                         if scan_path is not None else None)
             strands_all = sharding.gather_contig_strand_scores(comm, strand_parts) if strand != "forward" else None
             occ_all = sharding.gather_contig_occlusions(comm, occ_parts) if occlusion_block is not None else None
             attr_all = (sharding.gather_contig_attributions(comm, attr_parts, -(-ATTRIBUTION_POSITIONS // attribution_bin))
@@ -982,6 +1047,18 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                 f"{len(attr_all['contrib'])} windows) written to {attr_path.name}.")
                 elif attr_path.exists():            # likewise
                     attr_path.unlink()
+                if region_penalty is not None:
+                    contig_offsets = np.concatenate([[0], np.cumsum(scans_all["contig_len"])]).astype(np.int64)
+                    res = eng.call_regions(scans_all["track"], scans_all["bin_offsets"], region_penalty, contig_offsets, scan_stride)
+                    np.savez_compressed(regions_path, **{names_key: names, "stride": np.int64(scan_stride), "penalty": np.float64(region_penalty),
+                                                         **{k: v for k, v in res.asdict().items() if k not in ("stride", "penalty")}})
+                    write_regions_tsv(regions_tsv_path, names, res)
+                    console.log(f"Regions of the {what}s (stride {scan_stride}, switch penalty {region_penalty:g}, {len(res.region_contig)} regions) "
+                                f"written to {regions_path.name} and {regions_tsv_path.name}.")
+                else:                               # likewise, both files
+                    for p in (regions_path, regions_tsv_path):
+                        if p.exists():
+                            p.unlink()
         if cleanup and rank0 and enc_dir.is_dir():
             console.log(f"Deleting encoded {what} data.")
             shutil.rmtree(enc_dir)
@@ -991,17 +1068,19 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     run = stage_device if device_front_end else stage
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
     scan_kw = (lambda path: {"scan_path": path}) if scan_stride is not None else (lambda path: {})
-    strand_kw = ((lambda path, occ, attr: {"strand_path": path, "occ_path": occ, "attr_path": attr}) if device_front_end
-                 else (lambda path, occ, attr: {}))
+    strand_kw = ((lambda path, occ, attr, reg: {"strand_path": path, "occ_path": occ, "attr_path": attr, "regions_paths": reg})
+                 if device_front_end else (lambda path, occ, attr, reg: {}))
     try:
         run(input_path, outputs.encoded_sequences_dir, outputs.seq_window_id_output,
             outputs.nn_classification_npz_output, outputs.nn_classification_output,
-            "contig_names", "contig_ids", "sequence", **strand_kw(outputs.nn_strand_output, outputs.nn_occlusion_output, outputs.nn_attribution_output), **emb_kw(outputs.nn_embeddings_output),
+            "contig_names", "contig_ids", "sequence", **strand_kw(outputs.nn_strand_output, outputs.nn_occlusion_output, outputs.nn_attribution_output,
+                                                           (outputs.nn_regions_output, outputs.nn_regions_tsv_output)), **emb_kw(outputs.nn_embeddings_output),
             **scan_kw(outputs.nn_scan_output))
         if classify_proviruses:                                                      # :248-281, :355-425
             run(outputs.find_proviruses_nucleotide_output, outputs.encoded_proviruses_dir,
                 outputs.provirus_window_id_output, outputs.provirus_nn_classification_npz_output,
-                outputs.provirus_nn_classification_output, "provirus_names", "provirus_ids", "provirus", **strand_kw(outputs.provirus_nn_strand_output, outputs.provirus_nn_occlusion_output, outputs.provirus_nn_attribution_output),
+                outputs.provirus_nn_classification_output, "provirus_names", "provirus_ids", "provirus", **strand_kw(outputs.provirus_nn_strand_output, outputs.provirus_nn_occlusion_output, outputs.provirus_nn_attribution_output,
+                                                                           (outputs.provirus_nn_regions_output, outputs.provirus_nn_regions_tsv_output)),
                 **emb_kw(outputs.provirus_nn_embeddings_output), **scan_kw(outputs.provirus_nn_scan_output))
     finally:
         if check_pool is not None:

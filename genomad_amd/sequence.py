@@ -509,6 +509,107 @@ def scan_track(scores, kept, lens, win_offsets, bin_offsets, stride: int):
     return track, cover
 
 
+REGION_Q_ONE = 1 << 20                    # the integer a score of 1.0 becomes (gnn_regions.hip)
+REGION_PENALTY_MAX = 4096.0
+REGION_FIELDS = ("contig", "lo", "hi", "state", "evidence", "qsum")
+
+
+def region_penalty(penalty) -> int:
+    """P = rint(penalty * 2^20) (ties to even), the switch penalty in the integer units of the emissions; 0 <= penalty <= 4096."""
+    p = float(penalty)
+    if not 0.0 <= p <= REGION_PENALTY_MAX:             # a NaN fails both comparisons
+        raise ValueError(f"penalty {penalty!r} is outside [0, {REGION_PENALTY_MAX:g}]")
+    return int(np.rint(np.float64(p) * REGION_Q_ONE))
+
+
+def region_emissions(track):
+    """(q int64 (n_bins, 3), evidence bool (n_bins,)) of a track: a bin is an evidence bin iff its three values are finite; its
+    q = rint(min(max(v, 0), 1) * 2^20) - the float32 product with a power of two is exact, the rounding is to nearest, ties to
+    even; every other bin has q = 0."""
+    t = np.asarray(track, dtype=np.float32).reshape(-1, 3)
+    evidence = np.isfinite(t).all(axis=1)
+    with np.errstate(invalid="ignore"):
+        q = np.rint(np.minimum(np.maximum(t, np.float32(0)), np.float32(1)) * np.float32(REGION_Q_ONE))
+    return np.where(evidence[:, None], q, 0).astype(np.int64), evidence
+
+
+def call_regions(track, bin_offsets, penalty):
+    """Region calls along contigs, spelled out (the definition ``gnn_call_regions`` computes on the device; readable, not fast):
+    one 3-state Viterbi path per contig over the integer emissions of :func:`region_emissions`, with a switch costing
+    P = :func:`region_penalty`.  d[0][s] = q[0][s]; d[b][s] = q[b][s] + max(d[b-1][s], max_{s' != s} d[b-1][s'] - P); the back
+    pointer stays on a tie and otherwise names the lowest s' attaining the maximum; the last bin takes the lowest s with maximal
+    d, and the path follows the back pointers.  Python integers throughout: exact.  A region is a maximal run of equal states
+    within one contig.  ``track`` (n_bins, 3) and ``bin_offsets`` (n_contigs + 1) are those of a scan; bins below bin_offsets[0]
+    belong to no contig and keep state 0.  Returns (state uint8 (n_bins,), regions): ``regions`` is a dict of ``contig``, ``lo``,
+    ``hi`` (int64; contig-relative bins, half-open), ``state`` (uint8), ``evidence`` (int64: evidence bins in the region) and
+    ``qsum`` (int64 (n_regions, 3): the sum of q over the region), ordered by contig, then position."""
+    P = region_penalty(penalty)
+    off = np.asarray(bin_offsets, dtype=np.int64)
+    if off.ndim != 1 or len(off) < 1:
+        raise ValueError("bin_offsets must hold n_contigs + 1 offsets")
+    if int(off[0]) < 0:
+        raise ValueError(f"the first bin offset {int(off[0])} is negative")
+    if len(off) > 1 and int(np.diff(off).min()) < 0:
+        raise ValueError("bin offsets are not non-decreasing")
+    q, evidence = region_emissions(track)
+    if len(q) != int(off[-1]):
+        raise ValueError(f"the track has {len(q)} bins, bin_offsets end at {int(off[-1])}")
+    state = np.zeros(len(q), dtype=np.uint8)
+    out = {k: [] for k in REGION_FIELDS}
+    for c in range(len(off) - 1):
+        a, n = int(off[c]), int(off[c + 1] - off[c])
+        if n == 0:
+            continue
+        d = [int(v) for v in q[a]]
+        psi = np.zeros((n, 3), dtype=np.uint8)
+        for b in range(1, n):
+            nxt = []
+            for s in range(3):
+                o1, o2 = (t for t in range(3) if t != s)
+                best = o1 if d[o1] >= d[o2] else o2                  # the lowest s' attaining the maximum
+                if d[s] >= d[best] - P:                               # a tie stays
+                    psi[b, s] = s
+                    nxt.append(int(q[a + b, s]) + d[s])
+                else:
+                    psi[b, s] = best
+                    nxt.append(int(q[a + b, s]) + d[best] - P)
+            d = nxt
+        s = d.index(max(d))                                           # the lowest s with maximal d
+        for b in range(n - 1, -1, -1):
+            state[a + b] = s
+            s = int(psi[b, s])
+        st = state[a:a + n]
+        lo = np.concatenate([[0], np.flatnonzero(st[1:] != st[:-1]) + 1])
+        hi = np.concatenate([lo[1:], [n]])
+        for l, h in zip(lo, hi):
+            out["contig"].append(c), out["lo"].append(l), out["hi"].append(h), out["state"].append(st[l])
+            out["evidence"].append(int(evidence[a + l:a + h].sum()))
+            out["qsum"].append(q[a + l:a + h].sum(axis=0))
+    regions = {k: np.asarray(out[k], dtype=np.uint8 if k == "state" else np.int64) for k in REGION_FIELDS}
+    regions["qsum"] = regions["qsum"].reshape(-1, 3)
+    return state, regions
+
+
+def region_table(regions, offsets, stride: int):
+    """What a reader of regions wants, derived from the exact fields of :func:`call_regions`: ``start`` = lo * stride and ``end`` =
+    min(hi * stride, L) (int64: 0-based half-open bases within the contig of length L = diff(offsets)), ``mean`` (n_regions, 3)
+    float64 = qsum / (evidence * 2^20), NaN where evidence == 0, and ``margin`` float64 = (qsum[state] - the larger of the other
+    two) / 2^20: by how many bins' worth of score the called class leads.  Returns a dict of the four."""
+    lengths = np.diff(np.asarray(offsets, dtype=np.int64))
+    stride = int(stride)
+    contig, qsum = np.asarray(regions["contig"], np.int64), np.asarray(regions["qsum"], np.int64).reshape(-1, 3)
+    state, ev = np.asarray(regions["state"], np.int64), np.asarray(regions["evidence"], np.int64)
+    start = np.asarray(regions["lo"], np.int64) * stride
+    end = np.minimum(np.asarray(regions["hi"], np.int64) * stride, lengths[contig])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(ev[:, None] > 0, qsum / (ev[:, None] * float(REGION_Q_ONE)), np.nan)
+    rows = np.arange(len(state))
+    others = qsum.copy()
+    others[rows, state] = np.iinfo(np.int64).min
+    margin = (qsum[rows, state] - others.max(axis=1)) / float(REGION_Q_ONE) if len(state) else np.zeros(0)
+    return {"start": start, "end": end, "mean": mean.reshape(-1, 3), "margin": np.asarray(margin, dtype=np.float64)}
+
+
 def prefix_of(input_path: Path) -> str:
     """nn_classification.py:106-108: stem, minus one more extension if the file is compressed."""
     prefix = Path(input_path).stem

@@ -207,10 +207,11 @@ def gather_contig_strand_scores(comm, parts, root: int = 0):
     return np.ascontiguousarray(got[:, :3]), np.ascontiguousarray(got[:, 3:])
 
 
+SCAN_LENGTH_FIELDS = ("contig_len",)                           # per contig: its length in bases (main() adds it for the region table)
 SCAN_STRAND_FIELDS = ("scores_fwd", "scores_rev")              # per window, of a scan with a strand mode (StrandScanResult)
 
 
-def gather_contig_scans(comm, parts, root: int = 0, extra_window_fields=()):
+def gather_contig_scans(comm, parts, root: int = 0, extra_window_fields=(), extra_contig_fields=()):
     """Score tracks of contig-sharded pieces -> ``root``, in the piece order of :func:`gather_contig_parts`.  ``parts`` = this rank's
     list of (order_key, scan) with the same keys and contig counts as the pieces handed to gather_contig_parts; ``scan`` = the
     arrays of one ``NNEngine.scan_contigs`` call (win_offsets, starts, lens, kept, scores, bin_offsets, track, cover; an object with
@@ -218,9 +219,10 @@ def gather_contig_scans(comm, parts, root: int = 0, extra_window_fields=()):
     (:func:`gather_bytes`).  ``root`` concatenates the pieces and rebases the two CSR offset arrays; the values are only moved, so
     the result is bit-identical for any number of ranks.  Returns a dict of those eight arrays on ``root``, None elsewhere.
     ``extra_window_fields`` (SCAN_STRAND_FIELDS for the scans of ``NNEngine.scan_contigs_strand``): further (n_windows, 3) float32
-    arrays of every scan, gathered and returned the same way."""
+    arrays of every scan, gathered and returned the same way.  ``extra_contig_fields`` (SCAN_LENGTH_FIELDS: the contig lengths the
+    region table needs): further (n_contigs,) int64 arrays of every scan, likewise - they ride in the same byte string."""
     comm = comm or LocalComm()
-    window_fields = SCAN_WINDOW_FIELDS + tuple(extra_window_fields)
+    window_fields = SCAN_WINDOW_FIELDS + tuple(extra_window_fields) + tuple(extra_contig_fields)
     arrays = {"keys": np.array([int(key) for key, _ in parts], dtype="<i8")}
     for i, (_, scan) in enumerate(parts):
         scan = scan.asdict() if hasattr(scan, "asdict") else scan
@@ -251,6 +253,7 @@ def gather_contig_scans(comm, parts, root: int = 0, extra_window_fields=()):
     empty = {"starts": np.zeros(0, np.int64), "lens": np.zeros(0, np.int32), "kept": np.zeros(0, bool),
              "scores": np.zeros((0, 3), np.float32), "track": np.zeros((0, 3), np.float32), "cover": np.zeros(0, np.int32)}
     empty.update({f: np.zeros((0, 3), np.float32) for f in extra_window_fields})
+    empty.update({f: np.zeros(0, np.int64) for f in extra_contig_fields})
     return {f: np.concatenate(v) if v else empty[f] for f, v in out.items()}
 
 

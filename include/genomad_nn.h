@@ -433,6 +433,63 @@ int gnn_attribute_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int
                           float* bias_host_or_null, float* logits_host_or_null, float* window_scores_host_or_null,
                           uint8_t* window_kept_host_or_null, float* contig_scores_host_or_null);
 
+/* ---- region calls along contigs: Viterbi over score tracks ----------------------------------------------------------
+ * From a track to "bins 41-78 of this contig look viral": a segmentation with a switch cost, one 3-state Viterbi path per contig,
+ * bit-exact.  The input is any track (gnn_scan_contigs, gnn_scan_contigs_strand under any mode).
+ * Inputs.
+ *   - track[n_bins][3] f32 and bin_offsets[n_contigs + 1], the CSR of gnn_scan_plan / gnn_scan_contigs.
+ *   - A switch penalty `penalty`, a double, 0 <= penalty <= 4096, in units of score x bins.
+ * Emissions (exact, no transcendental on either side).
+ *   - Bin b is an *evidence* bin iff all three values of track[b] are finite.
+ *   - For an evidence bin, q[b][s] = rint(min(max(track[b][s], 0), 1) * 2^20) as an integer.  The f32 product with a power of two
+ *     is exact, and the rounding is to nearest, ties to even.
+ *   - For any other bin q[b][.] = 0.  This covers an uncovered bin (NaN by construction) and a NaN from an f16 overflow.
+ *   - P = rint(penalty * 2^20) as int64, computed once on the host in double.
+ *   - Linear scores rather than log scores make the objective the expected number of correctly labelled bins minus `penalty` per
+ *     switch.  They also make every quantity an integer: max and + on int64 are associative, so a parallel scan and the
+ *     sequential definition give identical results.
+ * Path, per contig with n > 0 bins, K = 3 states in class order.
+ *   - d[0][s] = q[0][s].
+ *   - d[b][s] = q[b][s] + max(d[b-1][s], max_{s' != s} d[b-1][s'] - P).
+ *   - Back pointer psi[b][s] = s if d[b-1][s] >= max_{s' != s}(d[b-1][s'] - P).  A tie stays.  Otherwise it is the lowest s'
+ *     attaining the maximum.
+ *   - The last bin's state is the lowest s with maximal d[n-1][s], and the path follows psi backwards.
+ *   - All DP values are int64.
+ *   - Consequences, which are also tests:
+ *       - At P = 0, every evidence bin gets its lowest-index argmax.
+ *       - At penalty = 4096, on contigs of fewer than 4096 bins, every contig is one region.
+ *       - A contig without any evidence bin is one region of state 0 with evidence = 0.
+ *       - An interior uncovered run takes a state from its neighbours and never forces a switch.
+ * Regions.
+ *   - A region is a maximal run of equal states within one contig.
+ *   - Regions are ordered by contig, then by position.
+ *   - An empty contig has no region.
+ *   - Each region has these fields: contig (int64); lo, hi (int64, contig-relative bins, half-open); state (uint8); evidence
+ *     (int64, the number of evidence bins in the region); qsum[3] (int64, the sum of q over the region).
+ *   - The sums are integer, so they are exact and independent of order.
+ *   - The Python layer derives these from the fields above: base coordinates lo * stride, min(hi * stride, L);
+ *     mean = qsum / (evidence * 2^20), NaN where evidence == 0; margin = (qsum[state] - max other) / 2^20.
+ * The kernels (gnn_regions.hip) are a chunked max-plus scan over tiles of 256 bins; no result depends on the tile size.  Device
+ * memory, persistent in the ctx and grow-only: 16 B per contig, 98 B per tile and 1 B per bin for gnn_region_states_dev;
+ * gnn_call_regions adds 14 B per bin (the track, the states, the flags), 12 B per 256 bins and 65 B per region.
+ * bin_offsets_host[0] may be positive: the bins below it belong to no contig, are not read and their states are not written.
+ *
+ * gnn_call_regions: host pointers, synchronous.  state_host_or_null[n_bins]: the path's state per bin.  The six region arrays
+ * (region_qsum[regions_capacity][3], the others [regions_capacity]) may all be NULL together: only *n_regions_out is then written -
+ * this is how a caller sizes them.  A capacity that is too small is GNN_ERR_ARG and the message names the size needed; nothing is
+ * written to the arrays then.  n_contigs == 0 or n_bins == 0 is GNN_OK with 0 regions.  GNN_ERR_ARG, with the range in the message,
+ * for a penalty outside [0, 4096] or not finite, for decreasing offsets and for a negative first offset - checked before the ctx. */
+int gnn_call_regions(gnn_ctx* ctx, const float* track_host, const int64_t* bin_offsets_host, int64_t n_contigs, double penalty,
+                     uint8_t* state_host_or_null, int64_t* region_contig, int64_t* region_lo, int64_t* region_hi,
+                     uint8_t* region_state, int64_t* region_evidence, int64_t* region_qsum, int64_t regions_capacity,
+                     int64_t* n_regions_out);
+/* The building block on device pointers: track_dev[n_bins][3] -> state_dev[n_bins], asynchronous on the ctx stream like
+ * gnn_classify_dev (the offsets are read before the call returns).  Arguments are checked as above. */
+int gnn_region_states_dev(gnn_ctx* ctx, const float* track_dev, const int64_t* bin_offsets_host, int64_t n_contigs, double penalty,
+                          uint8_t* state_dev);
+/* test aid: bins per tile of the scan, 1 <= bins <= 4096, default 256.  Results do not depend on it. */
+int gnn_debug_set_region_tile(gnn_ctx* ctx, int bins);
+
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
  * in-memory text buffer (already decompressed, newlines normalised to '\n').
@@ -514,7 +571,8 @@ int gnn_synth_windows_dev(gnn_ctx* ctx, uint64_t seed, int64_t first, int64_t n_
 #define GNN_K_F32_FRONT 3    /* unfused f32 front end (all its kernels)                   */
 #define GNN_K_ATTR_HEAD 4    /* attribution: dense head forward + backward (gnn_attribute*)  */
 #define GNN_K_ATTR_CONTRIB 5 /* attribution: the contribution kernel (second read of yp)     */
-#define GNN_K_COUNT 6
+#define GNN_K_REGIONS 6      /* region calls: every kernel of gnn_region_states_dev / gnn_call_regions */
+#define GNN_K_COUNT 7
 int gnn_profile_enable(gnn_ctx* ctx, int on);
 int gnn_profile_reset(gnn_ctx* ctx);
 /* synchronises the stream, then total milliseconds and number of launches of kernel_id */
