@@ -38,7 +38,10 @@ ERR_ARG, ERR_HIP, ERR_STATE, ERR_WEIGHTS, ERR_NOMEM = -1, -2, -3, -4, -5      # 
 OH_U8, OH_BF16, OH_F32 = 0, 1, 2
 STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2       # gnn_strand
 STRANDS = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
-K_FUSED, K_BACKEND, K_ENCODER, K_F32_FRONT, K_ATTR_HEAD, K_ATTR_CONTRIB, K_REGIONS = 0, 1, 2, 3, 4, 5, 6
+K_FUSED, K_BACKEND, K_ENCODER, K_F32_FRONT, K_ATTR_HEAD, K_ATTR_CONTRIB, K_REGIONS, K_NEIGHBOURS = 0, 1, 2, 3, 4, 5, 6, 7
+KNN_COSINE, KNN_DOT = 0, 1                                  # gnn_knn_metric
+KNN_METRICS = {"cosine": KNN_COSINE, "dot": KNN_DOT}
+KNN_K_MAX = 64
 
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
@@ -117,6 +120,9 @@ SIGNATURES = {
     "gnn_call_regions": (_int, [_vp, _vp, _vp, _i64, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
     "gnn_region_states_dev": (_int, [_vp, _vp, _vp, _i64, C.c_double, _vp]),
     "gnn_debug_set_region_tile": (_int, [_vp, _int]),
+    "gnn_neighbours": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _int, _vp, _vp]),
+    "gnn_neighbours_dev": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _int, _vp, _vp]),
+    "gnn_debug_set_neighbour_split": (_int, [_vp, _i64]),
     "gnn_embed": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_embed_dev": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_debug_forward": (_int, [_vp, _vp, _i64, _int, _vp, C.POINTER(Taps)]),

@@ -152,6 +152,20 @@ struct RegionWorkspace {
     }
 };
 
+// ---- nearest neighbours (gnn_neighbours.hip): persistent, grow-only.  Per base row 2 KB of f16 fragments + 1 B flag (and, for the
+// host entry point, its 2 KB of f32); per query row of ONE slab of 16384 the same, 8 k B per base range of partial lists and 12 k B
+// of results.  Nothing grows with the number of queries.
+struct NeighbourWorkspace {
+    int64_t split = 0;                           // base rows per workgroup (gnn_debug_set_neighbour_split); 0: the library's choice
+    DevBuf<uint4> bfrag, qfrag;                  // [32-row block][k-step 32][hi | lo][lane 64] x 16 B
+    DevBuf<uint8_t> bvalid, qvalid;
+    DevBuf<float> psim;                          // partial lists [query of the slab][range][k]
+    DevBuf<int32_t> pidx;
+    DevBuf<float> d_base, d_query;               // gnn_neighbours: the base's rows and one slab's query rows
+    DevBuf<int64_t> d_idx;                       // gnn_neighbours: one slab's results
+    DevBuf<float> d_sim;
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -334,6 +348,7 @@ struct gnn_ctx {
     bool pin_busy[2] = {false, false};
     // classify_chunks: staging of a window buffer that is not 4-byte aligned (the streaming kernels fetch bases as aligned dwords)
     gnn::DevBuf<uint8_t> align_buf;
+    gnn::NeighbourWorkspace nn;                   // gnn_neighbours.hip
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;

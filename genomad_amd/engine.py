@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, weights as _weights
+from . import _lib, sequence as _sequence, weights as _weights
 from ._lib import GnnError, check  # noqa: F401  (re-export)
 
 
@@ -476,6 +476,36 @@ class NNEngine:
         Returns (the scan's result, RegionResult with the derived table)."""
         scan = self._scan_contigs(np.asarray(seq), offsets, stride, single_window, precision, strand)
         return scan, self.call_regions(scan.track, scan.bin_offsets, penalty, self._offsets(offsets), stride)
+
+    # -- nearest neighbours ---------------------------------------------------------------
+    def set_neighbour_split(self, rows: int):
+        """test aid (``gnn_debug_set_neighbour_split``): base rows per workgroup of the neighbour search (0: the library's choice); no
+        result depends on it."""
+        check(self.lib.gnn_debug_set_neighbour_split(self.ctx, int(rows)))
+
+    @staticmethod
+    def _knn_metric(metric) -> int:
+        return _lib.KNN_METRICS[metric] if isinstance(metric, str) else int(metric)
+
+    def neighbours(self, query, base=None, k=10, metric="cosine"):
+        """Nearest neighbours among encoder embeddings (``gnn_neighbours``; the definition is ``sequence.nearest_neighbours``): for
+        every row of ``query`` (nq, 512) its ``k`` (1..64) most similar rows of ``base`` (nb, 512) under ``metric`` ("cosine" or
+        "dot"), exact search on the matrix pipe.  ``base=None``: the self-search, pair (i, i) excluded.  Returns (idx int64 (nq, k),
+        sim float32 (nq, k)), each row ordered by (similarity descending, base index ascending), padded with -1 / NaN; rows that
+        are not finite (under cosine: or zero) neither match nor are matched."""
+        q = _sequence.neighbour_rows(query)
+        b = None if base is None else _sequence.neighbour_rows(base, "base")
+        idx = np.empty((len(q), max(int(k), 0)), dtype=np.int64)         # a k outside [1, 64] is the library's error
+        sim = np.empty((len(q), max(int(k), 0)), dtype=np.float32)
+        check(self.lib.gnn_neighbours(self.ctx, q.ctypes.data, len(q), None if b is None else b.ctypes.data, 0 if b is None else len(b),
+                                      int(k), self._knn_metric(metric), idx.ctypes.data, sim.ctypes.data))
+        return idx, sim
+
+    def neighbours_dev(self, query_ptr: int, n_query: int, base_ptr, n_base: int, idx_ptr: int, sim_ptr: int, k=10, metric="cosine"):
+        """Asynchronous (``gnn_neighbours_dev``): device pointers in (query n_query x 512 f32; base n_base x 512 f32, or None for
+        the self-search) and out (idx n_query x k int64, sim n_query x k f32), enqueued on the engine's stream."""
+        check(self.lib.gnn_neighbours_dev(self.ctx, query_ptr, int(n_query), base_ptr, int(n_base), int(k), self._knn_metric(metric),
+                                          idx_ptr, sim_ptr))
 
     # -- occlusion maps ------------------------------------------------------------------
     def occlusion_plan(self, offsets: np.ndarray, block: int, single_window: bool = False):

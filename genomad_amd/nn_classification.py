@@ -82,6 +82,9 @@ class Outputs:
         self.nn_regions_tsv_output = d / f"{p}_nn_regions.tsv"
         self.provirus_nn_regions_output = d / f"{p}_provirus_nn_regions.npz"
         self.provirus_nn_regions_tsv_output = d / f"{p}_provirus_nn_regions.tsv"
+        # written only when GENOMAD_AMD_NEIGHBOURS is set (nearest neighbours among the per-contig embeddings; no counterpart in the reference)
+        self.nn_neighbours_output = d / f"{p}_nn_neighbours.npz"
+        self.provirus_nn_neighbours_output = d / f"{p}_provirus_nn_neighbours.npz"
         f = o / f"{p}_find_proviruses"
         self.find_proviruses_execution_info = f / f"{p}_find_proviruses.json"
         self.find_proviruses_output = f / f"{p}_provirus.tsv"
@@ -509,6 +512,35 @@ def _regions_of_file(path):
         return -1, -1.0
 
 
+NEIGHBOUR_METRIC = "cosine"          # what main() searches with
+
+
+def neighbours_requested():
+    """GENOMAD_AMD_NEIGHBOURS=<int in [1, 64]>: main() also writes every contig's that many nearest neighbours among the per-contig
+    encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1 (<prefix>_nn_neighbours.npz: cosine similarity, the contig itself excluded);
+    unset or empty: nothing changes (None).  Any other value is an error."""
+    v = os.environ.get("GENOMAD_AMD_NEIGHBOURS", "").strip()
+    if not v:
+        return None
+    try:
+        k = int(v)
+    except ValueError:
+        k = 0
+    if not 1 <= k <= sequence.NEIGHBOUR_K_MAX:
+        raise ValueError(f"GENOMAD_AMD_NEIGHBOURS={v!r}: expected an integer in [1, {sequence.NEIGHBOUR_K_MAX}] (neighbours per contig)")
+    return k
+
+
+def _neighbours_of_file(path):
+    """The k a stage's neighbour file was computed with; no file = None (no neighbours were asked for)."""
+    if not Path(path).exists():
+        return None
+    try:
+        return int(np.load(path)["k"])
+    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
+        return -1
+
+
 REGION_TSV_HEADER = ("seq_name\tstart\tend\tclass\tn_bins\tevidence_bins\t"
                      + "\t".join("mean_" + c[:-len("_score")] for c in TSV_HEADER.split()[1:]) + "\tmargin\n")
 
@@ -698,6 +730,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     occlusion_block = occlusion_block_requested()
     attribution_bin = attribution_bin_requested()
     region_penalty = region_penalty_requested()
+    neighbours_k = neighbours_requested()
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -727,6 +760,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     if region_penalty is not None and scan_stride is None:
         console.error("GENOMAD_AMD_REGION_PENALTY needs GENOMAD_AMD_SCAN_STRIDE: regions are called along the score tracks of a scan. "
                       "Set GENOMAD_AMD_SCAN_STRIDE or unset GENOMAD_AMD_REGION_PENALTY.")
+        sys.exit(1)
+    if neighbours_k is not None and not embeddings:
+        console.error("GENOMAD_AMD_NEIGHBOURS needs GENOMAD_AMD_EMBEDDINGS=1: neighbours are searched among the per-contig encoder "
+                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_NEIGHBOURS.")
         sys.exit(1)
 
     if strand != "forward" and not device_front_end:
@@ -878,7 +915,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             write_tsv(tsv_path, names, predictions)                                  # :340-352 (always rewritten)
 
     def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, strand_path, occ_path, attr_path, regions_paths,
-                     emb_path=None, scan_path=None):
+                     nn_path, emb_path=None, scan_path=None):
         """Product path: the contig front end (NNEngine.classify_contigs) does windowing, the N rule,
         tokenising, classification and the per-contig mean on the GPU, so encoding and classification
         are one step; ``<prefix>_seq_window_id.npz`` is still written.  With several ranks the CONTIGS are
@@ -902,7 +939,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         occlusion file's rule, with the bin in place of the block.
         ``regions_paths`` (npz, tsv; GENOMAD_AMD_REGION_PENALTY): rank 0 calls regions (NNEngine.call_regions) on the gathered track -
         regions are per contig, so the result does not depend on the number of ranks - and writes both files.  They follow the
-        occlusion file's rule, with (stride, penalty) in place of the block."""
+        occlusion file's rule, with (stride, penalty) in place of the block.
+        ``nn_path`` (GENOMAD_AMD_NEIGHBOURS, which needs the embeddings): rank 0 runs the self-search (NNEngine.neighbours) on the
+        gathered per-contig embeddings - of the strand mode the stage ran under - and writes every contig's k nearest there.  The
+        file follows the occlusion file's rule, with k in place of the block."""
         regions_path, regions_tsv_path = regions_paths
         regions_request = None if region_penalty is None else (scan_stride, region_penalty)
         (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and _strand_of_file(strand_path) == strand
@@ -910,6 +950,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                  and _attribution_bin_of_file(attr_path) == attribution_bin
                                  and _regions_of_file(regions_path) == regions_request
                                  and (regions_request is None) == (not regions_tsv_path.exists())
+                                 and _neighbours_of_file(nn_path) == neighbours_k
+                                 and (neighbours_k is None or _npz_strand(nn_path) == strand)
                                  and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
                                  and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
                                                             and _npz_strand(scan_path) == strand)))   # :284-292
@@ -1059,6 +1101,15 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     for p in (regions_path, regions_tsv_path):
                         if p.exists():
                             p.unlink()
+                if neighbours_k is not None:
+                    nn_idx, nn_sim = eng.neighbours(embeddings_all, None, neighbours_k, NEIGHBOUR_METRIC)
+                    np.savez_compressed(nn_path, **{names_key: names, "k": np.int64(neighbours_k), "metric": np.array(NEIGHBOUR_METRIC),
+                                                    "idx": nn_idx, "sim": nn_sim,
+                                                    **({"strand": np.array(strand)} if strand != "forward" else {})})
+                    console.log(f"Nearest neighbours of the {what}s ({neighbours_k} per {what}, {NEIGHBOUR_METRIC} similarity of the encoder "
+                                f"embeddings) written to {nn_path.name}.")
+                elif nn_path.exists():              # likewise
+                    nn_path.unlink()
         if cleanup and rank0 and enc_dir.is_dir():
             console.log(f"Deleting encoded {what} data.")
             shutil.rmtree(enc_dir)
@@ -1068,19 +1119,22 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     run = stage_device if device_front_end else stage
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
     scan_kw = (lambda path: {"scan_path": path}) if scan_stride is not None else (lambda path: {})
-    strand_kw = ((lambda path, occ, attr, reg: {"strand_path": path, "occ_path": occ, "attr_path": attr, "regions_paths": reg})
-                 if device_front_end else (lambda path, occ, attr, reg: {}))
+    strand_kw = ((lambda path, occ, attr, reg, nn: {"strand_path": path, "occ_path": occ, "attr_path": attr, "regions_paths": reg,
+                                                    "nn_path": nn})
+                 if device_front_end else (lambda path, occ, attr, reg, nn: {}))
     try:
         run(input_path, outputs.encoded_sequences_dir, outputs.seq_window_id_output,
             outputs.nn_classification_npz_output, outputs.nn_classification_output,
             "contig_names", "contig_ids", "sequence", **strand_kw(outputs.nn_strand_output, outputs.nn_occlusion_output, outputs.nn_attribution_output,
-                                                           (outputs.nn_regions_output, outputs.nn_regions_tsv_output)), **emb_kw(outputs.nn_embeddings_output),
+                                                           (outputs.nn_regions_output, outputs.nn_regions_tsv_output),
+                                                           outputs.nn_neighbours_output), **emb_kw(outputs.nn_embeddings_output),
             **scan_kw(outputs.nn_scan_output))
         if classify_proviruses:                                                      # :248-281, :355-425
             run(outputs.find_proviruses_nucleotide_output, outputs.encoded_proviruses_dir,
                 outputs.provirus_window_id_output, outputs.provirus_nn_classification_npz_output,
                 outputs.provirus_nn_classification_output, "provirus_names", "provirus_ids", "provirus", **strand_kw(outputs.provirus_nn_strand_output, outputs.provirus_nn_occlusion_output, outputs.provirus_nn_attribution_output,
-                                                                           (outputs.provirus_nn_regions_output, outputs.provirus_nn_regions_tsv_output)),
+                                                                           (outputs.provirus_nn_regions_output, outputs.provirus_nn_regions_tsv_output),
+                                                                           outputs.provirus_nn_neighbours_output),
                 **emb_kw(outputs.provirus_nn_embeddings_output), **scan_kw(outputs.provirus_nn_scan_output))
     finally:
         if check_pool is not None:

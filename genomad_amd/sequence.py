@@ -610,6 +610,64 @@ def region_table(regions, offsets, stride: int):
     return {"start": start, "end": end, "mean": mean.reshape(-1, 3), "margin": np.asarray(margin, dtype=np.float64)}
 
 
+NEIGHBOUR_DIM = 512                       # GNN_EMBED_DIM: the rows are encoder embeddings
+NEIGHBOUR_K_MAX = 64
+NEIGHBOUR_METRICS = ("cosine", "dot")
+
+
+def neighbour_rows(rows, what="query") -> np.ndarray:
+    """(n, 512) float32, C-contiguous: the rows of a neighbour search as the device takes them."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] != NEIGHBOUR_DIM:
+        raise ValueError(f"{what} has the shape {rows.shape}: (n, {NEIGHBOUR_DIM}) rows are required")
+    return rows
+
+
+def neighbour_k(k) -> int:
+    k = int(k)
+    if not 1 <= k <= NEIGHBOUR_K_MAX:
+        raise ValueError(f"k {k} is outside [1, {NEIGHBOUR_K_MAX}]")
+    return k
+
+
+def nearest_neighbours(query, base=None, k=10, metric="cosine"):
+    """Nearest neighbours among encoder embeddings, spelled out (the definition ``gnn_neighbours`` computes on the device; float64
+    throughout, readable, not fast).  ``query`` (nq, 512) and ``base`` (nb, 512) are float32 rows; ``base=None`` is the self-search:
+    base = query and the pair (i, i) is excluded.  A row is valid iff every element is finite and, under ``cosine``, its norm is
+    > 0 (a contig without a kept window has a zero row); an invalid query gets no neighbours, an invalid base row is nobody's.
+    ``cosine``: x.y / (|x| |y|); ``dot``: x.y, under which a zero row is valid.  Returns (idx int64 (nq, k), sim float32 (nq, k)),
+    each row ordered by (similarity descending, base index ascending) and padded with idx = -1, sim = NaN where fewer than k
+    candidates exist.  1 <= k <= 64."""
+    k = neighbour_k(k)
+    if metric not in NEIGHBOUR_METRICS:
+        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    q32 = neighbour_rows(query)
+    self_search = base is None
+    b32 = q32 if self_search else neighbour_rows(base, "base")
+
+    def unit(r32):
+        ok = np.isfinite(r32).all(axis=1)
+        r = np.where(ok[:, None], r32, 0).astype(np.float64)
+        if metric == "cosine":
+            norm = np.sqrt((r * r).sum(axis=1))
+            ok &= norm > 0
+            r = r / np.where(ok, norm, 1.0)[:, None]
+        return r, ok
+
+    q, q_ok = unit(q32)
+    b, b_ok = (q, q_ok) if self_search else unit(b32)
+    idx = np.full((len(q), k), -1, dtype=np.int64)
+    sim = np.full((len(q), k), np.nan, dtype=np.float32)
+    cand = np.flatnonzero(b_ok)
+    for i in np.flatnonzero(q_ok):
+        c = cand[cand != i] if self_search else cand
+        s = b[c] @ q[i]
+        order = np.lexsort((c, -s))[:k]                  # similarity descending, then base index ascending
+        idx[i, :len(order)] = c[order]
+        sim[i, :len(order)] = s[order]
+    return idx, sim
+
+
 def prefix_of(input_path: Path) -> str:
     """nn_classification.py:106-108: stem, minus one more extension if the file is compressed."""
     prefix = Path(input_path).stem

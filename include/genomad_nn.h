@@ -490,6 +490,39 @@ int gnn_region_states_dev(gnn_ctx* ctx, const float* track_dev, const int64_t* b
 /* test aid: bins per tile of the scan, 1 <= bins <= 4096, default 256.  Results do not depend on it. */
 int gnn_debug_set_region_tile(gnn_ctx* ctx, int bins);
 
+/* ---- nearest neighbours among encoder embeddings: cosine top-k on the device ---------------------------------
+ * "What is this contig like": for every query row the k most similar base rows, exact search (every pair is computed).  The rows are
+ * what gnn_embed / gnn_classify_contigs_embed write; no forward pass runs and no other entry point's result changes.
+ *   rows      query[n_query][GNN_EMBED_DIM] and base[n_base][GNN_EMBED_DIM], f32, C-contiguous (device pointers: 16-byte aligned).
+ *             base == NULL is the self-search: base = query (n_base is ignored) and the pair (i, i) is excluded.
+ *   valid     a row is valid iff every element is finite and, under GNN_KNN_COSINE, its norm is > 0 (a contig without a kept window
+ *             has a zero row: it neither matches nor is matched).  An invalid query gets no neighbours; an invalid base row is nobody's.
+ *   metric    GNN_KNN_COSINE: x.y / (|x| |y|).  GNN_KNN_DOT: x.y; a zero row is valid under it.
+ *   outputs   idx[n_query][k] int64 (base row) and sim[n_query][k] f32, each row ordered by (similarity descending, base index
+ *             ascending) on the device's own f32 similarities - a total order, so the result depends neither on how the base is split
+ *             over workgroups nor on the slabs the queries are walked in.  Fewer than k candidates: padded with idx = -1, sim = NaN.
+ *   ranges    1 <= k <= 64, n_query >= 0, 0 <= base rows < 2^31.  n_query == 0 is GNN_OK; no base row gives all -1 / NaN.
+ *             GNN_ERR_ARG, with the range in the message, for k, the metric and the sizes - checked before the ctx is looked at.
+ *   values    split-f16 limbs (hi + lo), three v_mfma_f32_32x32x16_f16 products per k-step, f32 accumulation in a fixed order: a
+ *             pair's similarity depends on its two rows only.  Cosine: the f32 norm is taken in a fixed order, the normalised row is
+ *             scaled by 2^8 before the split and the f32 result by 2^-16 (both exact: the low limbs stay f16 normals) - within 1e-5 of
+ *             the fp64 cosine, 1e-6 typical.  Dot: the rows are split unscaled: exact for small integers; needs |element| < 65504
+ *             (f16 range) - beyond it a pair's similarity is not finite, and a NaN similarity is never returned.
+ * Device memory, persistent in the ctx and grow-only: per base row 2 KB of f16 fragments + 1 B (gnn_neighbours: + the row's 2 KB of
+ * f32); the queries are walked in slabs of 16384 rows, and per query row of ONE slab: 2 KB of fragments (+ 2 KB of f32 for
+ * gnn_neighbours; nothing in the self-search, which reads the base's), 8 k B per base range of partial lists (a range is at most
+ * 65280 base rows) and, for gnn_neighbours, 12 k B of results.  Nothing grows with n_query.
+ * gnn_neighbours: host pointers, synchronous; the base goes up once, the queries slab by slab.  gnn_neighbours_dev: device pointers,
+ * asynchronous on the ctx stream like gnn_classify_dev. */
+typedef enum gnn_knn_metric { GNN_KNN_COSINE = 0, GNN_KNN_DOT = 1 } gnn_knn_metric;
+int gnn_neighbours(gnn_ctx* ctx, const float* query_host, int64_t n_query, const float* base_host_or_null, int64_t n_base, int k,
+                   int metric, int64_t* idx_host, float* sim_host);
+int gnn_neighbours_dev(gnn_ctx* ctx, const float* query_dev, int64_t n_query, const float* base_dev_or_null, int64_t n_base, int k,
+                       int metric, int64_t* idx_dev, float* sim_dev);
+/* test aid: base rows per workgroup of the search (rounded up to a multiple of 32, at most 65280); 0, the default: the library's
+ * choice, two workgroups per CU.  Results do not depend on it. */
+int gnn_debug_set_neighbour_split(gnn_ctx* ctx, int64_t base_rows_per_workgroup);
+
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
  * in-memory text buffer (already decompressed, newlines normalised to '\n').
@@ -572,7 +605,8 @@ int gnn_synth_windows_dev(gnn_ctx* ctx, uint64_t seed, int64_t first, int64_t n_
 #define GNN_K_ATTR_HEAD 4    /* attribution: dense head forward + backward (gnn_attribute*)  */
 #define GNN_K_ATTR_CONTRIB 5 /* attribution: the contribution kernel (second read of yp)     */
 #define GNN_K_REGIONS 6      /* region calls: every kernel of gnn_region_states_dev / gnn_call_regions */
-#define GNN_K_COUNT 7
+#define GNN_K_NEIGHBOURS 7   /* nearest neighbours: the prepare, tile and merge kernels of gnn_neighbours / gnn_neighbours_dev */
+#define GNN_K_COUNT 8
 int gnn_profile_enable(gnn_ctx* ctx, int on);
 int gnn_profile_reset(gnn_ctx* ctx);
 /* synchronises the stream, then total milliseconds and number of launches of kernel_id */
