@@ -1,0 +1,314 @@
+// Clusters among encoder embeddings (include/genomad_nn.h, "clusters"): the connected components of the graph
+// with an edge {i, j} iff both rows are valid and sim(i, j) >= threshold - single linkage at the threshold, exact, five kernels.
+//   prepare    nn_prepare of gnn_nn_frag.h, as it is: the neighbour search's fragments and flags, in its buffers.
+//   init       parent[i] = i, degree = size = key = 0.
+//   tile       nn_tile_kernel's skeleton - 64 rows' fragments in LDS, the base streamed in steps of 256 columns, the same three
+//              products per k-step in the same order, the same scale - over the UPPER TRIANGLE only.  The value of the pair {i, j},
+//              i < j, is the f32 that gnn_neighbours returns for query i and base row j; (j, i) is never computed: hi.lo then lo.hi is
+//              not symmetric in the last bit.  Behind every step, for every value with row < col, both rows valid and s >= threshold
+//              (false for a NaN): the edge is counted at both ends and the two rows are joined.  No lists, no barrier per step.
+//   flatten    label = the root of the row's tree; the root gathers the tree's size and the key of its representative.
+//   summarise  every valid row takes its root's size and representative; an invalid row is -1 / 0 / 0 / -1.
+// Union-find: parent[] is int32 in global memory and a link always points to the SMALLER index, so a tree's root is its smallest
+// member and the label needs no tie rule.  parent[x] is x until one compare-and-swap replaces it by something smaller, and never
+// changes again.  Degrees and sizes are integer adds, the key an integer max: nothing depends on the order the workgroups run in or
+// on the split of the base.  No loop here waits for another workgroup: every loop's termination argument stands next to it.
+#include <cmath>
+
+#include "gnn_nn_frag.h"
+
+namespace gnn {
+namespace {
+
+constexpr int64_t N_MAX = (int64_t)1 << 31;      // rows are int32 in parent[]
+
+__global__ __launch_bounds__(256) void cl_init_kernel(int64_t n, int32_t* __restrict__ parent, int32_t* __restrict__ degree,
+                                                      int32_t* __restrict__ size, unsigned long long* __restrict__ key) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    parent[i] = (int32_t)i;
+    degree[i] = 0;
+    size[i] = 0;
+    key[i] = 0;
+}
+
+struct ClusterArgs {
+    const uint4* frag;         // round_up(n, 64) / 32 blocks: rows and columns alike
+    const uint8_t* valid;      // [round_up(n, 64)]
+    int64_t n;
+    int64_t split_rows;        // base rows per workgroup: a multiple of 32
+    float scale;               // 2^-16 for cosine, 1 for dot
+    float threshold;
+    int32_t* parent;
+    int32_t* degree;
+};
+
+// a load that the compiler neither caches nor hoists; what it returns may still be older than another workgroup's compare-and-swap
+__device__ __forceinline__ int cl_peek(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Join the trees of rows a and b; returns a member of the joined tree at or above both (the next edge of the same column starts
+// there).  Every value parent[x] ever holds is x or smaller than x, whatever copy of it a load returns.
+__device__ __forceinline__ int cl_join(int32_t* parent, int a, int b) {
+    // The pre-check: climb both trees with loads.  A stale load returns x itself (the climb stops early) or the one link x ever got:
+    // u and v stay members of a's and b's trees, and equal ones prove one tree.  Ends: a step goes to p < u, and u >= 0.
+    int u = a, v = b;
+    for (;;) {
+        const int p = cl_peek(parent + u);
+        if (p == u) break;
+        u = p;
+    }
+    for (;;) {
+        const int p = cl_peek(parent + v);
+        if (p == v) break;
+        v = p;
+    }
+    // The monotone loop.  It acts on the compare-and-swap's own return only.  old == u: u was a root and now points to the smaller
+    // v - done.  Otherwise u had the link old < u already, and joining old with v joins the same trees.  Ends: max(u, v) falls with
+    // every pass (the larger of the two is replaced by something smaller than itself) and is >= 0; no pass waits for anybody.
+    while (u != v) {
+        if (u < v) {
+            const int t = u;
+            u = v;
+            v = t;
+        }
+        const int old = atomicCAS(parent + u, u, v);
+        if (old == u) return v;
+        u = old;
+    }
+    return u;
+}
+
+// grid = (row tiles, base ranges), 256 threads.  LDS: the tile's fragments 128 KB, its rows' edge counts and flags.
+__global__ __launch_bounds__(256) void cl_tile_kernel(ClusterArgs a) {
+    __shared__ uint4 qs[2 * BLK_U4];
+    __shared__ int ldeg[QT];               // edges of this workgroup's columns at the tile's rows: flushed once
+    __shared__ uint8_t lok[QT];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * QT;
+    const int64_t b0 = (int64_t)blockIdx.y * a.split_rows, b1 = min(a.n, b0 + a.split_rows);
+    if (b1 <= r0 + 1) return;              // no column of the range lies right of the tile's first row (the whole workgroup leaves)
+    {
+        const uint4* src = a.frag + (int64_t)blockIdx.x * 2 * BLK_U4;
+        for (int i = tid; i < 2 * BLK_U4; i += 256) qs[i] = src[i];
+        if (tid < QT) {
+            ldeg[tid] = 0;
+            lok[tid] = r0 + tid < a.n && a.valid[r0 + tid];
+        }
+    }
+    __syncthreads();
+    const int64_t last_blk = (b1 - 1) / 32;
+    // the first step begins at the 32-column block that holds the tile's first row (r0 and b0 are multiples of 32); a pair's value
+    // depends on its two rows only, so where a step begins changes nothing.  Ends: c0 grows by STEP towards b1.
+    for (int64_t c0 = max(b0, r0); c0 < b1; c0 += STEP) {
+        const uint4* bp[2];
+        int cg[2];                         // the lane's column, -1: no edge can end there
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            const int64_t blk = c0 / 32 + wave * 2 + nb;
+            bp[nb] = a.frag + min(blk, last_blk) * BLK_U4 + lane;
+            const int64_t col = blk * 32 + (lane & 31);
+            cg[nb] = col < b1 && a.valid[col] ? (int)col : -1;
+        }
+        f32x16 acc[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        BFrag f0, f1;
+        nn_load_b(f0, bp, 0);
+#pragma unroll 1
+        for (int ks = 0; ks < NKS; ks += 2) {              // k-step ks + 1 is fetched under the MFMAs of ks
+            nn_load_b(f1, bp, ks + 1);
+            nn_mfma(qs, ks, lane, f0, acc);
+            nn_load_b(f0, bp, min(ks + 2, NKS - 1));
+            nn_mfma(qs, ks + 1, lane, f1, acc);
+        }
+        // ---- edges: C/D layout column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5); bit (mb * 2 + nb) * 16 + reg
+        unsigned long long edge = 0;
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int rg = (int)r0 + row;
+                const bool rok = lok[row];
+#pragma unroll
+                for (int nb = 0; nb < 2; ++nb) {
+                    const float s = acc[mb][nb][r] * a.scale;
+                    const bool e = rok && rg < cg[nb] && s >= a.threshold;          // cg = -1 fails rg < cg; a NaN fails >=
+                    edge |= (unsigned long long)e << ((mb * 2 + nb) * 16 + r);
+                }
+            }
+        if (__ballot(edge != 0) == 0) continue;            // wave-uniform, and no barrier follows in the loop
+        // ---- degrees.  A row's edges of this step lie in one register of 32 lanes per column block: a ballot counts them, one lane
+        // per half adds them in LDS.  A column is one lane's in all its registers and the other half's: one add per column and step
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const unsigned long long e0 = __ballot((edge >> (mb * 32 + r)) & 1), e1 = __ballot((edge >> (mb * 32 + 16 + r)) & 1);
+                const int half = lane >> 5;
+                const int c = __popc((unsigned)(e0 >> (32 * half))) + __popc((unsigned)(e1 >> (32 * half)));
+                if ((lane & 31) == 0 && c) atomicAdd(&ldeg[mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half], c);
+            }
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            int c = __popc((unsigned)(edge >> (nb * 16)) & 0xffffu) + __popc((unsigned)(edge >> (32 + nb * 16)) & 0xffffu);
+            c += __shfl_xor(c, 32);
+            if (lane < 32 && c) atomicAdd(a.degree + cg[nb], c);               // c > 0 only where cg >= 0
+        }
+        // ---- joins, edge by edge.  Ends: every pass clears the lowest set bit of `edge`; cl_join ends by its own argument
+        int top[2] = {cg[0], cg[1]};       // a member of the column's tree, as low as this lane has seen
+        while (edge) {
+            const int b = __ffsll((long long)edge) - 1;
+            edge &= edge - 1;
+            const int r = b & 15, nb = (b >> 4) & 1, mb = b >> 5;
+            const int rg = (int)r0 + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int t = cl_join(a.parent, rg, nb ? top[1] : top[0]);
+            if (nb) top[1] = t; else top[0] = t;
+        }
+    }
+    __syncthreads();
+    if (tid < QT && ldeg[tid]) atomicAdd(a.degree + r0 + tid, ldeg[tid]);       // ldeg > 0 only at a valid row < n
+}
+
+// A launch of its own behind the tile kernel: plain loads see every link.  Ends: a step of the climb goes to p < r, and r >= 0.
+__global__ __launch_bounds__(256) void cl_flatten_kernel(int64_t n, const uint8_t* __restrict__ valid, const int32_t* __restrict__ parent,
+                                                         const int32_t* __restrict__ degree, int32_t* __restrict__ size,
+                                                         unsigned long long* __restrict__ key, int64_t* __restrict__ label) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (!valid[i]) {
+        label[i] = -1;
+        return;
+    }
+    int r = (int)i;
+    for (;;) {
+        const int p = parent[r];
+        if (p == r) break;
+        r = p;
+    }
+    label[i] = r;
+    atomicAdd(size + r, 1);
+    // the largest degree wins, among equals the smallest row
+    atomicMax(key + r, ((unsigned long long)(unsigned)degree[i] << 32) | (0xffffffffull - (unsigned long long)i));
+}
+
+__global__ __launch_bounds__(256) void cl_summarise_kernel(int64_t n, const uint8_t* __restrict__ valid, const int32_t* __restrict__ degree,
+                                                           const int32_t* __restrict__ size, const unsigned long long* __restrict__ key,
+                                                           const int64_t* __restrict__ label, int64_t* __restrict__ degree_out,
+                                                           int64_t* __restrict__ size_out, int64_t* __restrict__ rep_out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (!valid[i]) {
+        degree_out[i] = 0;
+        size_out[i] = 0;
+        rep_out[i] = -1;
+        return;
+    }
+    const int64_t r = label[i];
+    degree_out[i] = degree[i];
+    size_out[i] = size[r];
+    rep_out[i] = (int64_t)(0xffffffffull - (key[r] & 0xffffffffull));
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+
+int check_cluster_args(const char* fn, const void* rows, int64_t n, float threshold, int metric, const void* label, const void* degree,
+                       const void* size, const void* rep) {
+    const std::string f(fn);
+    if (n < 0 || n >= N_MAX) {
+        set_error(f + ": " + std::to_string(n) + " rows is outside [0, 2^31)");
+        return GNN_ERR_ARG;
+    }
+    if (!std::isfinite(threshold)) {
+        set_error(f + ": threshold " + std::to_string(threshold) + " is outside (-inf, inf): a finite f32 is required");
+        return GNN_ERR_ARG;
+    }
+    if (metric != GNN_KNN_COSINE && metric != GNN_KNN_DOT) {
+        set_error(f + ": metric " + std::to_string(metric) + " is outside [0, 1] (GNN_KNN_COSINE, GNN_KNN_DOT)");
+        return GNN_ERR_ARG;
+    }
+    if (n > 0 && (!rows || !label || !degree || !size || !rep)) {
+        set_error("bad argument to " + f + ": the rows and the four outputs are required");
+        return GNN_ERR_ARG;
+    }
+    return GNN_OK;
+}
+
+// n > 0 rows on the device -> the four arrays on the device, enqueued on the ctx's stream
+int cl_run(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int metric, int64_t* label, int64_t* degree, int64_t* size,
+           int64_t* rep) {
+    NeighbourWorkspace& w = ctx->nn;
+    ClusterWorkspace& c = ctx->cl;
+    int rc = nn_prepare(ctx, rows_dev, n, metric, w.bfrag, w.bvalid);
+    if (!rc) rc = nn_reserve(ctx, c.parent, (size_t)n);
+    if (!rc) rc = nn_reserve(ctx, c.degree, (size_t)n);
+    if (!rc) rc = nn_reserve(ctx, c.size, (size_t)n);
+    if (!rc) rc = nn_reserve(ctx, c.key, (size_t)n);
+    if (rc) return rc;
+    const int64_t tiles = (n + QT - 1) / QT;
+    const int64_t split_rows = nn_split_rows(ctx, tiles, n);
+    const int64_t splits = (n + split_rows - 1) / split_rows;
+    if (splits > 65535) {
+        set_error("gnn_cluster: " + std::to_string(n) + " rows in ranges of " + std::to_string(split_rows) + " are more than 65535 ranges");
+        return GNN_ERR_ARG;
+    }
+    ProfScope prof(ctx, GNN_K_NEIGHBOURS);
+    const dim3 per_row((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(cl_init_kernel, per_row, dim3(256), 0, ctx->stream, n, c.parent.get(), c.degree.get(), c.size.get(), c.key.get());
+    GNN_HIP(hipGetLastError());
+    ClusterArgs a;
+    a.frag = w.bfrag.get();
+    a.valid = w.bvalid.get();
+    a.n = n;
+    a.split_rows = split_rows;
+    a.scale = metric == GNN_KNN_COSINE ? 1.f / 65536.f : 1.f;
+    a.threshold = threshold;
+    a.parent = c.parent.get();
+    a.degree = c.degree.get();
+    hipLaunchKernelGGL(cl_tile_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, ctx->stream, a);
+    GNN_HIP(hipGetLastError());
+    hipLaunchKernelGGL(cl_flatten_kernel, per_row, dim3(256), 0, ctx->stream, n, w.bvalid.get(), c.parent.get(), c.degree.get(), c.size.get(),
+                       c.key.get(), label);
+    GNN_HIP(hipGetLastError());
+    hipLaunchKernelGGL(cl_summarise_kernel, per_row, dim3(256), 0, ctx->stream, n, w.bvalid.get(), c.degree.get(), c.size.get(), c.key.get(),
+                       label, degree, size, rep);
+    GNN_HIP(hipGetLastError());
+    return GNN_OK;
+}
+
+}  // namespace
+}  // namespace gnn
+
+using namespace gnn;
+
+extern "C" int gnn_cluster_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int metric, int64_t* label_dev,
+                               int64_t* degree_dev, int64_t* size_dev, int64_t* rep_dev) {
+    if (int rc = check_cluster_args("gnn_cluster_dev", rows_dev, n, threshold, metric, label_dev, degree_dev, size_dev, rep_dev)) return rc;
+    if (int rc = check_ctx(ctx)) return rc;
+    if (n == 0) return GNN_OK;
+    return cl_run(ctx, rows_dev, n, threshold, metric, label_dev, degree_dev, size_dev, rep_dev);
+}
+
+extern "C" int gnn_cluster(gnn_ctx* ctx, const float* rows_host, int64_t n, float threshold, int metric, int64_t* label_host,
+                           int64_t* degree_host, int64_t* size_host, int64_t* rep_host) {
+    if (int rc = check_cluster_args("gnn_cluster", rows_host, n, threshold, metric, label_host, degree_host, size_host, rep_host)) return rc;
+    if (int rc = check_ctx(ctx)) return rc;
+    if (n == 0) return GNN_OK;
+    NeighbourWorkspace& w = ctx->nn;
+    ClusterWorkspace& c = ctx->cl;
+    int rc = nn_reserve(ctx, w.d_base, (size_t)n * D);
+    if (!rc) rc = nn_reserve(ctx, c.d_out, (size_t)4 * n);
+    if (rc) return rc;
+    GNN_HIP(hipMemcpyAsync(w.d_base, rows_host, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    int64_t* out = c.d_out;
+    if ((rc = cl_run(ctx, w.d_base, n, threshold, metric, out, out + n, out + 2 * n, out + 3 * n))) return rc;
+    int64_t* const host[4] = {label_host, degree_host, size_host, rep_host};
+    for (int i = 0; i < 4; ++i)
+        GNN_HIP(hipMemcpyAsync(host[i], out + (int64_t)i * n, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    GNN_HIP(hipStreamSynchronize(ctx->stream));
+    return GNN_OK;
+}

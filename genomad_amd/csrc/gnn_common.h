@@ -166,6 +166,15 @@ struct NeighbourWorkspace {
     DevBuf<float> d_sim;
 };
 
+// ---- clusters (gnn_clusters.hip): persistent, grow-only.  The fragments and flags are NeighbourWorkspace's bfrag / bvalid (and d_base
+// for the host entry point); here 20 B per row and, for gnn_cluster alone, its 32 B of results.  Nothing is n x n.
+struct ClusterWorkspace {
+    DevBuf<int32_t> parent;                      // union-find: a link points to a smaller index, a root to itself
+    DevBuf<int32_t> degree, size;                // edges at the row; rows of the tree, at its root
+    DevBuf<unsigned long long> key;              // at the root: max of (degree << 32) | (2^32 - 1 - row) over the tree
+    DevBuf<int64_t> d_out;                       // gnn_cluster: [label | degree | size | rep]
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -349,6 +358,7 @@ struct gnn_ctx {
     // classify_chunks: staging of a window buffer that is not 4-byte aligned (the streaming kernels fetch bases as aligned dwords)
     gnn::DevBuf<uint8_t> align_buf;
     gnn::NeighbourWorkspace nn;                   // gnn_neighbours.hip
+    gnn::ClusterWorkspace cl;                     // gnn_clusters.hip
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;

@@ -122,6 +122,40 @@ class RegionResult:
                    stride=None if stride is None else int(stride), **table)
 
 
+class ClusterResult:
+    """What :meth:`NNEngine.cluster` returns (the definition is ``sequence.threshold_clusters``): ``label``, ``degree``, ``size``,
+    ``rep`` (int64 (n,); -1 / 0 / 0 / -1 for an invalid row), the ``threshold`` as the float32 it was compared as, and ``metric``."""
+    FIELDS = ("label", "degree", "size", "rep", "threshold", "metric")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw.get(k))
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    @property
+    def n_clusters(self) -> int:
+        """clusters, singletons included: the rows that are their own label"""
+        return int((self.label == np.arange(len(self.label))).sum())
+
+    @property
+    def n_edges(self) -> int:
+        return int(self.degree.sum()) // 2
+
+    def table(self, names=None):
+        """``sequence.cluster_table``: one record per cluster, ordered by label"""
+        from . import sequence as S
+        return S.cluster_table(self, names)
+
+    @classmethod
+    def build(cls, arrays, threshold, metric):
+        """from the four arrays of ``sequence.threshold_clusters`` or the library"""
+        from . import sequence as S
+        label, degree, size, rep = arrays
+        return cls(label=label, degree=degree, size=size, rep=rep, threshold=float(S.cluster_threshold(threshold)), metric=str(metric))
+
+
 class NNEngine:
     def __init__(self, device: int = 0, weights: dict = None, chunk: int = None):
         self.lib = _lib.load()
@@ -506,6 +540,29 @@ class NNEngine:
         the self-search) and out (idx n_query x k int64, sim n_query x k f32), enqueued on the engine's stream."""
         check(self.lib.gnn_neighbours_dev(self.ctx, query_ptr, int(n_query), base_ptr, int(n_base), int(k), self._knn_metric(metric),
                                           idx_ptr, sim_ptr))
+
+    # -- clusters ------------------------------------------------------------------------
+    def cluster(self, rows, threshold, metric="cosine") -> ClusterResult:
+        """Clusters among encoder embeddings (``gnn_cluster``; the definition is ``sequence.threshold_clusters``): the connected
+        components of the graph with an edge between two valid rows of ``rows`` (n, 512) whose similarity under ``metric`` is >=
+        ``threshold`` - single linkage, exact search over the upper triangle on the matrix pipe.  The similarity of the pair i < j
+        is the float32 :meth:`neighbours` returns for query i and base row j.  Clusters chain: ``degree`` and ``rep`` tell a chain
+        (a representative with few edges for its cluster's size) from a clique.  :meth:`set_neighbour_split` sets the range of
+        this search too; no result depends on it."""
+        r = _sequence.neighbour_rows(rows, "rows")
+        if isinstance(metric, str) and metric not in _lib.KNN_METRICS:
+            raise ValueError(f"metric {metric!r}: expected one of {tuple(_lib.KNN_METRICS)}")
+        out = [np.empty(len(r), dtype=np.int64) for _ in range(4)]
+        check(self.lib.gnn_cluster(self.ctx, r.ctypes.data, len(r), float(threshold), self._knn_metric(metric),
+                                   *(a.ctypes.data for a in out)))
+        return ClusterResult.build(out, np.float32(threshold), metric)
+
+    def cluster_dev(self, rows_ptr: int, n: int, threshold, label_ptr: int, degree_ptr: int, size_ptr: int, rep_ptr: int,
+                    metric="cosine"):
+        """Asynchronous (``gnn_cluster_dev``): device pointers in (rows n x 512 f32) and out (label, degree, size, rep: n int64
+        each), enqueued on the engine's stream."""
+        check(self.lib.gnn_cluster_dev(self.ctx, rows_ptr, int(n), float(threshold), self._knn_metric(metric), label_ptr, degree_ptr,
+                                       size_ptr, rep_ptr))
 
     # -- occlusion maps ------------------------------------------------------------------
     def occlusion_plan(self, offsets: np.ndarray, block: int, single_window: bool = False):

@@ -85,6 +85,11 @@ class Outputs:
         # written only when GENOMAD_AMD_NEIGHBOURS is set (nearest neighbours among the per-contig embeddings; no counterpart in the reference)
         self.nn_neighbours_output = d / f"{p}_nn_neighbours.npz"
         self.provirus_nn_neighbours_output = d / f"{p}_provirus_nn_neighbours.npz"
+        # written only when GENOMAD_AMD_CLUSTERS is set (threshold clusters among the per-contig embeddings; no counterpart in the reference)
+        self.nn_clusters_output = d / f"{p}_nn_clusters.npz"
+        self.nn_clusters_tsv_output = d / f"{p}_nn_clusters.tsv"
+        self.provirus_nn_clusters_output = d / f"{p}_provirus_nn_clusters.npz"
+        self.provirus_nn_clusters_tsv_output = d / f"{p}_provirus_nn_clusters.tsv"
         f = o / f"{p}_find_proviruses"
         self.find_proviruses_execution_info = f / f"{p}_find_proviruses.json"
         self.find_proviruses_output = f / f"{p}_provirus.tsv"
@@ -541,6 +546,47 @@ def _neighbours_of_file(path):
         return -1
 
 
+def clusters_requested():
+    """GENOMAD_AMD_CLUSTERS=<float in [-1, 1]>: main() also writes the single-linkage clusters of the contigs at that cosine similarity
+    of the per-contig encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1 (<prefix>_nn_clusters.npz and .tsv); unset or empty: nothing
+    changes (None).  Any other value is an error.  Returns the threshold as it is compared: the float32 it rounds to."""
+    v = os.environ.get("GENOMAD_AMD_CLUSTERS", "").strip()
+    if not v:
+        return None
+    try:
+        t = float(v)
+    except ValueError:
+        t = float("nan")
+    if not -1.0 <= t <= 1.0:                             # a NaN fails both comparisons
+        raise ValueError(f"GENOMAD_AMD_CLUSTERS={v!r}: expected a float in [-1, 1] (the cosine similarity at which two contigs are joined)")
+    return float(np.float32(t))
+
+
+def _clusters_of_file(path):
+    """The threshold a stage's cluster file was computed with; no file = None (no clusters were asked for)."""
+    if not Path(path).exists():
+        return None
+    try:
+        return float(np.load(path)["threshold"])
+    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
+        return float("nan")
+
+
+CLUSTER_TSV_HEADER = "seq_name\tcluster\tcluster_size\trepresentative\tdegree\n"
+
+
+def write_clusters_tsv(path, names, res):
+    """One line per contig of a ClusterResult: the name of its cluster's label contig, the cluster's size, the name of its
+    representative and the contig's own degree; a contig without a valid embedding has NA, 0, NA, 0."""
+    with open(path, "w") as fout:
+        fout.write(CLUSTER_TSV_HEADER)
+        for i, name in enumerate(names):
+            if res.label[i] < 0:
+                fout.write(f"{name}\tNA\t0\tNA\t0\n")
+            else:
+                fout.write(f"{name}\t{names[res.label[i]]}\t{res.size[i]}\t{names[res.rep[i]]}\t{res.degree[i]}\n")
+
+
 REGION_TSV_HEADER = ("seq_name\tstart\tend\tclass\tn_bins\tevidence_bins\t"
                      + "\t".join("mean_" + c[:-len("_score")] for c in TSV_HEADER.split()[1:]) + "\tmargin\n")
 
@@ -731,6 +777,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     attribution_bin = attribution_bin_requested()
     region_penalty = region_penalty_requested()
     neighbours_k = neighbours_requested()
+    clusters_threshold = clusters_requested()
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -764,6 +811,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     if neighbours_k is not None and not embeddings:
         console.error("GENOMAD_AMD_NEIGHBOURS needs GENOMAD_AMD_EMBEDDINGS=1: neighbours are searched among the per-contig encoder "
                       "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_NEIGHBOURS.")
+        sys.exit(1)
+    if clusters_threshold is not None and not embeddings:
+        console.error("GENOMAD_AMD_CLUSTERS needs GENOMAD_AMD_EMBEDDINGS=1: clusters are formed among the per-contig encoder "
+                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_CLUSTERS.")
         sys.exit(1)
 
     if strand != "forward" and not device_front_end:
@@ -915,7 +966,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             write_tsv(tsv_path, names, predictions)                                  # :340-352 (always rewritten)
 
     def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, strand_path, occ_path, attr_path, regions_paths,
-                     nn_path, emb_path=None, scan_path=None):
+                     nn_path, clusters_paths, emb_path=None, scan_path=None):
         """Product path: the contig front end (NNEngine.classify_contigs) does windowing, the N rule,
         tokenising, classification and the per-contig mean on the GPU, so encoding and classification
         are one step; ``<prefix>_seq_window_id.npz`` is still written.  With several ranks the CONTIGS are
@@ -942,7 +993,11 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         occlusion file's rule, with (stride, penalty) in place of the block.
         ``nn_path`` (GENOMAD_AMD_NEIGHBOURS, which needs the embeddings): rank 0 runs the self-search (NNEngine.neighbours) on the
         gathered per-contig embeddings - of the strand mode the stage ran under - and writes every contig's k nearest there.  The
-        file follows the occlusion file's rule, with k in place of the block."""
+        file follows the occlusion file's rule, with k in place of the block.
+        ``clusters_paths`` (npz, tsv; GENOMAD_AMD_CLUSTERS, which needs the embeddings): rank 0 clusters the same gathered embeddings
+        (NNEngine.cluster, cosine) where it runs the neighbour search, and writes both files.  They follow the neighbour file's
+        rule, with the threshold in place of k."""
+        clusters_path, clusters_tsv_path = clusters_paths
         regions_path, regions_tsv_path = regions_paths
         regions_request = None if region_penalty is None else (scan_stride, region_penalty)
         (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and _strand_of_file(strand_path) == strand
@@ -952,6 +1007,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                  and (regions_request is None) == (not regions_tsv_path.exists())
                                  and _neighbours_of_file(nn_path) == neighbours_k
                                  and (neighbours_k is None or _npz_strand(nn_path) == strand)
+                                 and _clusters_of_file(clusters_path) == clusters_threshold
+                                 and (clusters_threshold is None) == (not clusters_tsv_path.exists())
+                                 and (clusters_threshold is None or _npz_strand(clusters_path) == strand)
                                  and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
                                  and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
                                                             and _npz_strand(scan_path) == strand)))   # :284-292
@@ -1110,6 +1168,20 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                 f"embeddings) written to {nn_path.name}.")
                 elif nn_path.exists():              # likewise
                     nn_path.unlink()
+                if clusters_threshold is not None:
+                    res = eng.cluster(embeddings_all, clusters_threshold, NEIGHBOUR_METRIC)
+                    np.savez_compressed(clusters_path, **{names_key: names, "threshold": np.float64(clusters_threshold),
+                                                          "metric": np.array(NEIGHBOUR_METRIC), "label": res.label, "degree": res.degree,
+                                                          "size": res.size, "rep": res.rep,
+                                                          **({"strand": np.array(strand)} if strand != "forward" else {})})
+                    write_clusters_tsv(clusters_tsv_path, names, res)
+                    console.log(f"Clusters of the {what}s ({NEIGHBOUR_METRIC} similarity of the encoder embeddings >= {clusters_threshold:g}, "
+                                f"single linkage: {res.n_clusters} clusters, {res.n_edges} edges) written to {clusters_path.name} and "
+                                f"{clusters_tsv_path.name}.")
+                else:                               # likewise, both files
+                    for p in (clusters_path, clusters_tsv_path):
+                        if p.exists():
+                            p.unlink()
         if cleanup and rank0 and enc_dir.is_dir():
             console.log(f"Deleting encoded {what} data.")
             shutil.rmtree(enc_dir)
@@ -1119,22 +1191,26 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     run = stage_device if device_front_end else stage
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
     scan_kw = (lambda path: {"scan_path": path}) if scan_stride is not None else (lambda path: {})
-    strand_kw = ((lambda path, occ, attr, reg, nn: {"strand_path": path, "occ_path": occ, "attr_path": attr, "regions_paths": reg,
-                                                    "nn_path": nn})
-                 if device_front_end else (lambda path, occ, attr, reg, nn: {}))
+    strand_kw = ((lambda path, occ, attr, reg, nn, cl: {"strand_path": path, "occ_path": occ, "attr_path": attr, "regions_paths": reg,
+                                                        "nn_path": nn, "clusters_paths": cl})
+                 if device_front_end else (lambda path, occ, attr, reg, nn, cl: {}))
     try:
         run(input_path, outputs.encoded_sequences_dir, outputs.seq_window_id_output,
             outputs.nn_classification_npz_output, outputs.nn_classification_output,
             "contig_names", "contig_ids", "sequence", **strand_kw(outputs.nn_strand_output, outputs.nn_occlusion_output, outputs.nn_attribution_output,
                                                            (outputs.nn_regions_output, outputs.nn_regions_tsv_output),
-                                                           outputs.nn_neighbours_output), **emb_kw(outputs.nn_embeddings_output),
+                                                           outputs.nn_neighbours_output,
+                                                           (outputs.nn_clusters_output, outputs.nn_clusters_tsv_output)),
+            **emb_kw(outputs.nn_embeddings_output),
             **scan_kw(outputs.nn_scan_output))
         if classify_proviruses:                                                      # :248-281, :355-425
             run(outputs.find_proviruses_nucleotide_output, outputs.encoded_proviruses_dir,
                 outputs.provirus_window_id_output, outputs.provirus_nn_classification_npz_output,
                 outputs.provirus_nn_classification_output, "provirus_names", "provirus_ids", "provirus", **strand_kw(outputs.provirus_nn_strand_output, outputs.provirus_nn_occlusion_output, outputs.provirus_nn_attribution_output,
                                                                            (outputs.provirus_nn_regions_output, outputs.provirus_nn_regions_tsv_output),
-                                                                           outputs.provirus_nn_neighbours_output),
+                                                                           outputs.provirus_nn_neighbours_output,
+                                                                           (outputs.provirus_nn_clusters_output,
+                                                                            outputs.provirus_nn_clusters_tsv_output)),
                 **emb_kw(outputs.provirus_nn_embeddings_output), **scan_kw(outputs.provirus_nn_scan_output))
     finally:
         if check_pool is not None:

@@ -668,6 +668,87 @@ def nearest_neighbours(query, base=None, k=10, metric="cosine"):
     return idx, sim
 
 
+CLUSTER_FIELDS = ("label", "degree", "size", "rep")
+
+
+def cluster_threshold(threshold) -> np.float32:
+    """The threshold as the device compares it: the float32 it rounds to; it must be finite (before and after the rounding)."""
+    try:
+        with np.errstate(over="ignore"):
+            t = np.float32(threshold)
+    except (TypeError, ValueError):
+        raise ValueError(f"threshold {threshold!r}: a finite float is required") from None
+    if not np.isfinite(t):
+        raise ValueError(f"threshold {threshold!r}: a finite float is required")
+    return t
+
+
+def threshold_clusters(rows, threshold, metric="cosine"):
+    """Clusters among encoder embeddings, spelled out (the definition ``gnn_cluster`` computes on the device; float64 throughout,
+    readable, not fast, n x n).  ``rows`` (n, 512) float32; validity and ``metric`` as in :func:`nearest_neighbours`.  There is an
+    edge {i, j}, i != j, iff both rows are valid and sim(i, j) >= the float32 ``threshold`` rounds to; clusters are the connected
+    components (single linkage at the threshold), a valid row without an edge a cluster of one.  Returns four int64 arrays of n:
+    ``label`` (the smallest index of the row's cluster), ``degree`` (edges at the row), ``size`` (rows of its cluster) and ``rep``
+    (the member of its cluster with the largest degree, ties to the smallest index); an invalid row has -1, 0, 0, -1."""
+    if metric not in NEIGHBOUR_METRICS:
+        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    r32 = neighbour_rows(rows, "rows")
+    thr = float(cluster_threshold(threshold))
+    n = len(r32)
+    ok = np.isfinite(r32).all(axis=1)
+    r = np.where(ok[:, None], r32, 0).astype(np.float64)
+    if metric == "cosine":
+        norm = np.sqrt((r * r).sum(axis=1))
+        ok &= norm > 0
+        r = r / np.where(ok, norm, 1.0)[:, None]
+    adj = (r @ r.T >= thr) & ok[:, None] & ok[None, :]
+    adj |= adj.T                        # x.y and y.x may differ in the last bit of a float64 sum: an edge either way is an edge
+    adj[np.arange(n), np.arange(n)] = False
+    label = np.full(n, -1, dtype=np.int64)
+    degree = adj.sum(axis=1).astype(np.int64)
+    size = np.zeros(n, dtype=np.int64)
+    rep = np.full(n, -1, dtype=np.int64)
+    for i in np.flatnonzero(ok):        # ascending: the first unlabelled row of a component is its smallest
+        if label[i] >= 0:
+            continue
+        members, stack = [i], [i]
+        label[i] = i
+        while stack:
+            for j in np.flatnonzero(adj[stack.pop()] & (label < 0)):
+                label[j] = i
+                members.append(j)
+                stack.append(j)
+        members = np.sort(np.asarray(members, dtype=np.int64))
+        size[members] = len(members)
+        rep[members] = members[np.argmax(degree[members])]        # argmax: the first = the smallest index among equals
+    return label, degree, size, rep
+
+
+def cluster_table(result, names=None):
+    """One record per cluster of a :func:`threshold_clusters` result (the four arrays, a dict of them, or anything with them as
+    attributes), ordered by label: ``label``, ``size``, ``rep``, ``members`` (their indices in ascending order; the names where
+    ``names`` is given, as are then ``label`` and ``rep``) and ``edges``, the number of edges inside the cluster (half the sum of
+    its degrees: size * (size - 1) / 2 for a clique, size - 1 at the least - a chain)."""
+    if isinstance(result, dict):
+        label, degree, size, rep = (result[k] for k in CLUSTER_FIELDS)
+    elif isinstance(result, (tuple, list)):
+        label, degree, size, rep = result
+    else:
+        label, degree, size, rep = (getattr(result, k) for k in CLUSTER_FIELDS)
+    label, degree, size, rep = (np.asarray(a, dtype=np.int64) for a in (label, degree, size, rep))
+    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    order = np.argsort(label, kind="stable")
+    order = order[label[order] >= 0]
+    out = []
+    bounds = np.flatnonzero(np.diff(label[order], prepend=-1)) if len(order) else []
+    for a, b in zip(bounds, list(bounds[1:]) + [len(order)]):
+        members = order[a:b]
+        root = int(label[members[0]])
+        out.append({"label": name(root), "size": int(size[root]), "rep": name(rep[root]), "members": [name(i) for i in members],
+                    "edges": int(degree[members].sum()) // 2})
+    return out
+
+
 def prefix_of(input_path: Path) -> str:
     """nn_classification.py:106-108: stem, minus one more extension if the file is compressed."""
     prefix = Path(input_path).stem

@@ -523,6 +523,33 @@ int gnn_neighbours_dev(gnn_ctx* ctx, const float* query_dev, int64_t n_query, co
  * choice, two workgroups per CU.  Results do not depend on it. */
 int gnn_debug_set_neighbour_split(gnn_ctx* ctx, int64_t base_rows_per_workgroup);
 
+/* ---- clusters among encoder embeddings: threshold components on the device ----------------------------------
+ * "Which rows belong together, and which one stands for the group": the connected components of the graph that has an edge {i, j},
+ * i != j, iff both rows are valid and sim(i, j) >= threshold - single linkage at the threshold, exact (every pair i < j is computed,
+ * no pair twice).  Rows, validity and metric are those of the nearest neighbours above; no forward pass runs and no other entry
+ * point's result changes.
+ *   value     the similarity of the pair {i, j}, i < j, is the f32 that gnn_neighbours returns for query i and base row j (the same
+ *             fragments, k-steps and order); (j, i) is never computed - the limb products are not symmetric in the last bit.  A
+ *             similarity that is not a number is no edge.  The threshold is compared as the f32 given; a tie is an edge.
+ *   outputs   four int64 arrays of n: label = the smallest index of the row's cluster; degree = the number of edges at the row; size
+ *             = the rows of its cluster; rep = the member of its cluster with the largest degree, ties to the smallest index.  A
+ *             valid row without an edge is a cluster of one (label = rep = itself, size 1).  An invalid row: -1, 0, 0, -1.
+ *   ranges    0 <= n < 2^31, a finite threshold, a metric in [0, 1]; GNN_ERR_ARG with the value and the range in the message - checked
+ *             before the ctx is looked at, nothing is written.  n == 0 is GNN_OK and writes nothing.
+ *   exact     degrees, sizes and representatives are integer sums and maxima, the label is the root of a union-find whose links point
+ *             to the smaller index: nothing depends on the order workgroups run in or on how the base is split over them
+ *             (gnn_debug_set_neighbour_split sets the range for this search too).
+ * Single linkage chains: two rows far below the threshold share a cluster when a path of edges joins them.  degree and rep are there
+ * so that a caller sees it - a chain's representative has few edges for its cluster's size.
+ * Device memory, persistent in the ctx and grow-only: the 2 KB of fragments + 1 B per row of the neighbour search (shared with it;
+ * gnn_cluster: + the row's 2 KB of f32) and 20 B per row of parent, degree, size and key (gnn_cluster: + 32 B of results).  Nothing is
+ * n x n and no edge list is stored.
+ * gnn_cluster: host pointers, synchronous.  gnn_cluster_dev: device pointers, asynchronous on the ctx stream like gnn_classify_dev. */
+int gnn_cluster(gnn_ctx* ctx, const float* rows_host, int64_t n, float threshold, int metric, int64_t* label_host, int64_t* degree_host,
+                int64_t* size_host, int64_t* rep_host);
+int gnn_cluster_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int metric, int64_t* label_dev, int64_t* degree_dev,
+                    int64_t* size_dev, int64_t* rep_dev);
+
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
  * in-memory text buffer (already decompressed, newlines normalised to '\n').
@@ -605,7 +632,8 @@ int gnn_synth_windows_dev(gnn_ctx* ctx, uint64_t seed, int64_t first, int64_t n_
 #define GNN_K_ATTR_HEAD 4    /* attribution: dense head forward + backward (gnn_attribute*)  */
 #define GNN_K_ATTR_CONTRIB 5 /* attribution: the contribution kernel (second read of yp)     */
 #define GNN_K_REGIONS 6      /* region calls: every kernel of gnn_region_states_dev / gnn_call_regions */
-#define GNN_K_NEIGHBOURS 7   /* nearest neighbours: the prepare, tile and merge kernels of gnn_neighbours / gnn_neighbours_dev */
+#define GNN_K_NEIGHBOURS 7   /* nearest neighbours: the prepare, tile and merge kernels of gnn_neighbours / gnn_neighbours_dev; clusters:
+                              * every kernel of gnn_cluster / gnn_cluster_dev */
 #define GNN_K_COUNT 8
 int gnn_profile_enable(gnn_ctx* ctx, int on);
 int gnn_profile_reset(gnn_ctx* ctx);
