@@ -175,6 +175,21 @@ struct ClusterWorkspace {
     DevBuf<int64_t> d_out;                       // gnn_cluster: [label | degree | size | rep]
 };
 
+// ---- representatives (gnn_representatives.hip): persistent, grow-only.  The fragments and flags are NeighbourWorkspace's bfrag /
+// bvalid (and d_base for the host entry point); here 21 B per row (padded to 64), one live byte per 64 and per 32 rows, two counters
+// and, for gnn_representatives alone, its 20 B of results.  Nothing is n x n.
+struct RepresentativeWorkspace {
+    DevBuf<uint8_t> state;                       // INVALID, UNDECIDED, FRESH, REP or MEMBER
+    DevBuf<unsigned> flag;                       // HIT | WAIT of the round, cleared by its decide
+    DevBuf<unsigned long long> key;              // at a member: max of (image of the similarity << 32) | (2^32 - 1 - representative)
+    DevBuf<unsigned long long> size;             // at a representative: the rows of its cluster
+    DevBuf<uint8_t> row_live, col_live;          // per 64 rows: a FRESH or UNDECIDED row; per 32 rows: an UNDECIDED row
+    DevBuf<unsigned long long> count;            // [undecided rows, members]
+    PinnedBuf<unsigned long long> h_count;       // where the host reads one of them, once per round
+    DevBuf<int64_t> d_out;                       // gnn_representatives: [rep | size | sim (f32)]
+    std::vector<float> round_ms;                 // profiling on: HIP-event time of every round of the last call
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -359,6 +374,7 @@ struct gnn_ctx {
     gnn::DevBuf<uint8_t> align_buf;
     gnn::NeighbourWorkspace nn;                   // gnn_neighbours.hip
     gnn::ClusterWorkspace cl;                     // gnn_clusters.hip
+    gnn::RepresentativeWorkspace rp;              // gnn_representatives.hip
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;

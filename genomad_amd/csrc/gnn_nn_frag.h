@@ -1,6 +1,6 @@
-// What the searches over encoder embeddings share (gnn_neighbours.hip, gnn_clusters.hip): the fragment layout and its constants,
-// the prepare kernel and its launcher, the fragment loads and the three-product MFMA step, the split of the base over workgroups.
-// Both searches run the same k-steps in the same order on the same fragments: a pair's f32 value is the same in both.
+// What the searches over encoder embeddings share (gnn_neighbours.hip, gnn_clusters.hip, gnn_representatives.hip): the fragment layout
+// and its constants, the prepare kernel and its launcher, the fragment loads and the three-product MFMA step, the split of the base
+// over workgroups.  All of them run the same k-steps in the same order on the same fragments: a pair's f32 value is the same in each.
 #pragma once
 #include <cmath>
 

@@ -156,6 +156,43 @@ class ClusterResult:
         return cls(label=label, degree=degree, size=size, rep=rep, threshold=float(S.cluster_threshold(threshold)), metric=str(metric))
 
 
+class RepresentativeResult:
+    """What :meth:`NNEngine.representatives` returns (the definition is ``sequence.greedy_representatives``), in the caller's index
+    space: ``rep`` (int64; a representative names itself, -1 for an invalid row), ``sim`` (float32; a member's similarity to its
+    representative, NaN otherwise), ``size`` (int64; 0 for an invalid row), ``rank`` (int64; the row's place in the priority order),
+    ``rounds`` (the synchronous rounds the device ran: a property of the graph and the order), the ``threshold`` as the float32 it
+    was compared as, and ``metric``."""
+    FIELDS = ("rep", "sim", "size", "rank", "rounds", "threshold", "metric")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw.get(k))
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    @property
+    def is_rep(self) -> np.ndarray:
+        return self.rep == np.arange(len(self.rep))
+
+    @property
+    def n_clusters(self) -> int:
+        return int(self.is_rep.sum())
+
+    def table(self, names=None):
+        """``sequence.representative_table``: one record per cluster, ordered by the representative's rank"""
+        from . import sequence as S
+        return S.representative_table(self, names)
+
+    @classmethod
+    def build(cls, arrays, threshold, metric):
+        """from the (rep, sim, size, rank, rounds) of ``sequence.greedy_representatives`` or the library"""
+        from . import sequence as S
+        rep, sim, size, rank, rounds = arrays
+        return cls(rep=rep, sim=sim, size=size, rank=rank, rounds=int(rounds), threshold=float(S.cluster_threshold(threshold)),
+                   metric=str(metric))
+
+
 class NNEngine:
     def __init__(self, device: int = 0, weights: dict = None, chunk: int = None):
         self.lib = _lib.load()
@@ -563,6 +600,53 @@ class NNEngine:
         each), enqueued on the engine's stream."""
         check(self.lib.gnn_cluster_dev(self.ctx, rows_ptr, int(n), float(threshold), self._knn_metric(metric), label_ptr, degree_ptr,
                                        size_ptr, rep_ptr))
+
+    # -- representatives -----------------------------------------------------------------
+    def representatives(self, rows, threshold, weight=None, metric="cosine") -> RepresentativeResult:
+        """Representatives among encoder embeddings (``gnn_representatives``; the definition is
+        ``sequence.greedy_representatives``): greedy incremental clusters of ``rows`` (n, 512).  The rows are walked by (``weight``
+        descending, index ascending) - ``None``: index order -; a row founds a cluster unless an earlier representative has a
+        similarity >= ``threshold`` to it, otherwise it joins the most similar such representative.  Stars, not chains: every
+        member is within the threshold of its representative, no two representatives are within it of each other.  The rows are
+        permuted by rank before the call and ``rep`` is mapped back: the similarity of a pair is the float32 :meth:`neighbours`
+        returns for query = the row of smaller rank and base row = the other, in the permuted order.  The device runs synchronous
+        rounds (``rounds``; a path walked end to end takes as many as it has rows), one stream synchronise each.
+        :meth:`set_neighbour_split` sets the range of this search too; no result depends on it."""
+        r = _sequence.neighbour_rows(rows, "rows")
+        if isinstance(metric, str) and metric not in _lib.KNN_METRICS:
+            raise ValueError(f"metric {metric!r}: expected one of {tuple(_lib.KNN_METRICS)}")
+        n = len(r)
+        order = _sequence.priority_order(weight, n)
+        rank = np.empty(n, dtype=np.int64)
+        rank[order] = np.arange(n)
+        p = r if weight is None else np.ascontiguousarray(r[order])
+        rep_p, sim_p, size_p = np.empty(n, np.int64), np.empty(n, np.float32), np.empty(n, np.int64)
+        rounds = C.c_int64(0)
+        check(self.lib.gnn_representatives(self.ctx, p.ctypes.data, n, float(threshold), self._knn_metric(metric), rep_p.ctypes.data,
+                                           sim_p.ctypes.data, size_p.ctypes.data, C.addressof(rounds)))
+        rep, sim, size = np.empty(n, np.int64), np.empty(n, np.float32), np.empty(n, np.int64)
+        rep[order] = np.where(rep_p >= 0, order[np.maximum(rep_p, 0)], -1)
+        sim[order], size[order] = sim_p, size_p
+        return RepresentativeResult.build((rep, sim, size, rank, rounds.value), np.float32(threshold), metric)
+
+    def representatives_dev(self, rows_ptr: int, n: int, threshold, rep_ptr: int, sim_ptr: int, size_ptr: int, metric="cosine") -> int:
+        """``gnn_representatives_dev``: device pointers in (rows n x 512 f32 IN PRIORITY ORDER: index = rank) and out (rep int64,
+        sim f32, size int64, n each, in that order's index space), enqueued on the engine's stream - which is synchronised once per
+        round; the arrays are ready when the stream is.  Returns ``rounds``."""
+        rounds = C.c_int64(0)
+        check(self.lib.gnn_representatives_dev(self.ctx, rows_ptr, int(n), float(threshold), self._knn_metric(metric), rep_ptr, sim_ptr,
+                                               size_ptr, C.addressof(rounds)))
+        return int(rounds.value)
+
+    def representative_round_ms(self):
+        """measurement only (``gnn_debug_representative_round_ms``): with profiling enabled, the HIP-event milliseconds of every
+        round of the last ``representatives`` / ``representatives_dev`` call"""
+        n = C.c_int64(0)
+        check(self.lib.gnn_debug_representative_round_ms(self.ctx, None, 0, C.addressof(n)))
+        ms = np.zeros(n.value, np.float64)
+        if n.value:
+            check(self.lib.gnn_debug_representative_round_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
+        return ms
 
     # -- occlusion maps ------------------------------------------------------------------
     def occlusion_plan(self, offsets: np.ndarray, block: int, single_window: bool = False):

@@ -90,6 +90,11 @@ class Outputs:
         self.nn_clusters_tsv_output = d / f"{p}_nn_clusters.tsv"
         self.provirus_nn_clusters_output = d / f"{p}_provirus_nn_clusters.npz"
         self.provirus_nn_clusters_tsv_output = d / f"{p}_provirus_nn_clusters.tsv"
+        # written only when GENOMAD_AMD_REPRESENTATIVES is set (greedy clusters among the per-contig embeddings; no counterpart in the reference)
+        self.nn_representatives_output = d / f"{p}_nn_representatives.npz"
+        self.nn_representatives_tsv_output = d / f"{p}_nn_representatives.tsv"
+        self.provirus_nn_representatives_output = d / f"{p}_provirus_nn_representatives.npz"
+        self.provirus_nn_representatives_tsv_output = d / f"{p}_provirus_nn_representatives.tsv"
         f = o / f"{p}_find_proviruses"
         self.find_proviruses_execution_info = f / f"{p}_find_proviruses.json"
         self.find_proviruses_output = f / f"{p}_provirus.tsv"
@@ -587,6 +592,41 @@ def write_clusters_tsv(path, names, res):
                 fout.write(f"{name}\t{names[res.label[i]]}\t{res.size[i]}\t{names[res.rep[i]]}\t{res.degree[i]}\n")
 
 
+def representatives_requested():
+    """GENOMAD_AMD_REPRESENTATIVES=<float in [-1, 1]>: main() also writes the greedy clusters of the contigs at that cosine similarity of
+    the per-contig encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1 - contigs walked by their number of kept windows, the larger first,
+    every contig within the threshold of its representative (<prefix>_nn_representatives.npz and .tsv); unset or empty: nothing changes
+    (None).  Any other value is an error.  Returns the threshold as it is compared: the float32 it rounds to."""
+    v = os.environ.get("GENOMAD_AMD_REPRESENTATIVES", "").strip()
+    if not v:
+        return None
+    try:
+        t = float(v)
+    except ValueError:
+        t = float("nan")
+    if not -1.0 <= t <= 1.0:                             # a NaN fails both comparisons
+        raise ValueError(f"GENOMAD_AMD_REPRESENTATIVES={v!r}: expected a float in [-1, 1] (the cosine similarity at which a contig joins "
+                         "a representative)")
+    return float(np.float32(t))
+
+
+REPRESENTATIVE_TSV_HEADER = "seq_name\trepresentative\tsimilarity\tcluster_size\tis_representative\n"
+
+
+def write_representatives_tsv(path, names, res):
+    """One line per contig of a RepresentativeResult: the name of its representative, its similarity to it (NA for a representative),
+    the cluster's size and whether the contig is the representative; a contig without a valid embedding has NA, NA, 0, False."""
+    with open(path, "w") as fout:
+        fout.write(REPRESENTATIVE_TSV_HEADER)
+        for i, name in enumerate(names):
+            if res.rep[i] < 0:
+                fout.write(f"{name}\tNA\tNA\t0\tFalse\n")
+            elif res.rep[i] == i:
+                fout.write(f"{name}\t{name}\tNA\t{res.size[i]}\tTrue\n")
+            else:
+                fout.write(f"{name}\t{names[res.rep[i]]}\t{res.sim[i]:.6f}\t{res.size[i]}\tFalse\n")
+
+
 REGION_TSV_HEADER = ("seq_name\tstart\tend\tclass\tn_bins\tevidence_bins\t"
                      + "\t".join("mean_" + c[:-len("_score")] for c in TSV_HEADER.split()[1:]) + "\tmargin\n")
 
@@ -778,6 +818,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     region_penalty = region_penalty_requested()
     neighbours_k = neighbours_requested()
     clusters_threshold = clusters_requested()
+    representatives_threshold = representatives_requested()
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -815,6 +856,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     if clusters_threshold is not None and not embeddings:
         console.error("GENOMAD_AMD_CLUSTERS needs GENOMAD_AMD_EMBEDDINGS=1: clusters are formed among the per-contig encoder "
                       "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_CLUSTERS.")
+        sys.exit(1)
+    if representatives_threshold is not None and not embeddings:
+        console.error("GENOMAD_AMD_REPRESENTATIVES needs GENOMAD_AMD_EMBEDDINGS=1: representatives are chosen among the per-contig encoder "
+                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_REPRESENTATIVES.")
         sys.exit(1)
 
     if strand != "forward" and not device_front_end:
@@ -966,7 +1011,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             write_tsv(tsv_path, names, predictions)                                  # :340-352 (always rewritten)
 
     def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, strand_path, occ_path, attr_path, regions_paths,
-                     nn_path, clusters_paths, emb_path=None, scan_path=None):
+                     nn_path, clusters_paths, representatives_paths, emb_path=None, scan_path=None):
         """Product path: the contig front end (NNEngine.classify_contigs) does windowing, the N rule,
         tokenising, classification and the per-contig mean on the GPU, so encoding and classification
         are one step; ``<prefix>_seq_window_id.npz`` is still written.  With several ranks the CONTIGS are
@@ -996,8 +1041,13 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         file follows the occlusion file's rule, with k in place of the block.
         ``clusters_paths`` (npz, tsv; GENOMAD_AMD_CLUSTERS, which needs the embeddings): rank 0 clusters the same gathered embeddings
         (NNEngine.cluster, cosine) where it runs the neighbour search, and writes both files.  They follow the neighbour file's
-        rule, with the threshold in place of k."""
+        rule, with the threshold in place of k.
+        ``representatives_paths`` (npz, tsv; GENOMAD_AMD_REPRESENTATIVES, which needs the embeddings): rank 0 runs the greedy clustering
+        (NNEngine.representatives, cosine) on the same gathered embeddings, the contig's number of kept windows (the count of its
+        entries in the gathered window ids: no further collective) as its weight, ties in FASTA order.  The files follow the
+        clusters files' rule."""
         clusters_path, clusters_tsv_path = clusters_paths
+        representatives_path, representatives_tsv_path = representatives_paths
         regions_path, regions_tsv_path = regions_paths
         regions_request = None if region_penalty is None else (scan_stride, region_penalty)
         (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and _strand_of_file(strand_path) == strand
@@ -1010,6 +1060,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                  and _clusters_of_file(clusters_path) == clusters_threshold
                                  and (clusters_threshold is None) == (not clusters_tsv_path.exists())
                                  and (clusters_threshold is None or _npz_strand(clusters_path) == strand)
+                                 and _clusters_of_file(representatives_path) == representatives_threshold
+                                 and (representatives_threshold is None) == (not representatives_tsv_path.exists())
+                                 and (representatives_threshold is None or _npz_strand(representatives_path) == strand)
                                  and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
                                  and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
                                                             and _npz_strand(scan_path) == strand)))   # :284-292
@@ -1182,6 +1235,22 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     for p in (clusters_path, clusters_tsv_path):
                         if p.exists():
                             p.unlink()
+                if representatives_threshold is not None:
+                    weight = np.bincount(np.asarray(ids, dtype=np.int64), minlength=len(names)).astype(np.int64)     # kept windows
+                    res = eng.representatives(embeddings_all, representatives_threshold, weight, NEIGHBOUR_METRIC)
+                    np.savez_compressed(representatives_path, **{names_key: names, "threshold": np.float64(representatives_threshold),
+                                                                 "metric": np.array(NEIGHBOUR_METRIC), "weight": weight, "rep": res.rep,
+                                                                 "sim": res.sim, "size": res.size, "rank": res.rank,
+                                                                 "rounds": np.int64(res.rounds),
+                                                                 **({"strand": np.array(strand)} if strand != "forward" else {})})
+                    write_representatives_tsv(representatives_tsv_path, names, res)
+                    console.log(f"Representatives of the {what}s ({NEIGHBOUR_METRIC} similarity of the encoder embeddings >= "
+                                f"{representatives_threshold:g}, greedy by kept windows: {res.n_clusters} clusters in {res.rounds} rounds) "
+                                f"written to {representatives_path.name} and {representatives_tsv_path.name}.")
+                else:                               # likewise, both files
+                    for p in (representatives_path, representatives_tsv_path):
+                        if p.exists():
+                            p.unlink()
         if cleanup and rank0 and enc_dir.is_dir():
             console.log(f"Deleting encoded {what} data.")
             shutil.rmtree(enc_dir)
@@ -1191,16 +1260,17 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     run = stage_device if device_front_end else stage
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
     scan_kw = (lambda path: {"scan_path": path}) if scan_stride is not None else (lambda path: {})
-    strand_kw = ((lambda path, occ, attr, reg, nn, cl: {"strand_path": path, "occ_path": occ, "attr_path": attr, "regions_paths": reg,
-                                                        "nn_path": nn, "clusters_paths": cl})
-                 if device_front_end else (lambda path, occ, attr, reg, nn, cl: {}))
+    strand_kw = ((lambda path, occ, attr, reg, nn, cl, rp: {"strand_path": path, "occ_path": occ, "attr_path": attr, "regions_paths": reg,
+                                                            "nn_path": nn, "clusters_paths": cl, "representatives_paths": rp})
+                 if device_front_end else (lambda path, occ, attr, reg, nn, cl, rp: {}))
     try:
         run(input_path, outputs.encoded_sequences_dir, outputs.seq_window_id_output,
             outputs.nn_classification_npz_output, outputs.nn_classification_output,
             "contig_names", "contig_ids", "sequence", **strand_kw(outputs.nn_strand_output, outputs.nn_occlusion_output, outputs.nn_attribution_output,
                                                            (outputs.nn_regions_output, outputs.nn_regions_tsv_output),
                                                            outputs.nn_neighbours_output,
-                                                           (outputs.nn_clusters_output, outputs.nn_clusters_tsv_output)),
+                                                           (outputs.nn_clusters_output, outputs.nn_clusters_tsv_output),
+                                                           (outputs.nn_representatives_output, outputs.nn_representatives_tsv_output)),
             **emb_kw(outputs.nn_embeddings_output),
             **scan_kw(outputs.nn_scan_output))
         if classify_proviruses:                                                      # :248-281, :355-425
@@ -1210,7 +1280,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                                                            (outputs.provirus_nn_regions_output, outputs.provirus_nn_regions_tsv_output),
                                                                            outputs.provirus_nn_neighbours_output,
                                                                            (outputs.provirus_nn_clusters_output,
-                                                                            outputs.provirus_nn_clusters_tsv_output)),
+                                                                            outputs.provirus_nn_clusters_tsv_output),
+                                                                           (outputs.provirus_nn_representatives_output,
+                                                                            outputs.provirus_nn_representatives_tsv_output)),
                 **emb_kw(outputs.provirus_nn_embeddings_output), **scan_kw(outputs.provirus_nn_scan_output))
     finally:
         if check_pool is not None:

@@ -749,6 +749,127 @@ def cluster_table(result, names=None):
     return out
 
 
+REPRESENTATIVE_FIELDS = ("rep", "sim", "size", "rank")
+
+
+def priority_order(weight, n) -> np.ndarray:
+    """The order in which :func:`greedy_representatives` walks n rows: their indices by (``weight`` descending, index ascending);
+    ``weight=None`` is the index order.  ``order[k]`` is the row of rank k.  A weight array of another length than n, or one that
+    holds a value that is not finite, is a ValueError."""
+    n = int(n)
+    if weight is None:
+        return np.arange(n, dtype=np.int64)
+    try:
+        w = np.asarray(weight, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"weight {weight!r}: {n} finite numbers are required") from None
+    if w.shape != (n,):
+        raise ValueError(f"weight has the shape {w.shape}: one value for each of the {n} rows is required")
+    if not np.isfinite(w).all():
+        raise ValueError(f"weight holds {int((~np.isfinite(w)).sum())} values that are not finite: finite weights are required")
+    return np.argsort(-w, kind="stable").astype(np.int64)         # stable: equal weights keep the index order
+
+
+def representative_rounds(edge, valid):
+    """The synchronous rounds ``gnn_representatives`` runs in place of the walk, on rows in priority order: ``edge`` (n, n) bool, read
+    for i < j only; ``valid`` (n,) bool.  A round looks at the states of its start: an undecided row with an edge to a smaller-rank
+    row that became a representative in the previous round turns member; otherwise an undecided row with no edge to a smaller-rank
+    undecided row turns representative; otherwise it stays undecided.  Returns (is_rep bool (n,), rounds): the rounds until no row is
+    undecided.  The undecided row of smallest rank is decided in every round, so at most n rounds run."""
+    valid = np.asarray(valid, dtype=bool)
+    n = len(valid)
+    up = np.triu(np.asarray(edge, dtype=bool).reshape(n, n), 1) & valid[:, None] & valid[None, :]
+    undecided, fresh, is_rep = valid.copy(), np.zeros(n, bool), np.zeros(n, bool)
+    rounds = 0
+    while undecided.any():
+        hit = up[fresh].any(axis=0)                      # an edge from a representative of the previous round
+        wait = up[undecided].any(axis=0)                 # an edge from a smaller-rank undecided row
+        member = undecided & hit
+        fresh = undecided & ~hit & ~wait
+        is_rep |= fresh
+        undecided = undecided & ~member & ~fresh
+        rounds += 1
+    return is_rep, rounds
+
+
+def greedy_representatives(rows, threshold, weight=None, metric="cosine"):
+    """Representatives among encoder embeddings, spelled out (the definition ``gnn_representatives`` computes on the device; float64
+    throughout, readable, not fast, n x n): greedy incremental clustering.  ``rows`` (n, 512) float32; validity, ``metric`` and
+    ``threshold`` as in :func:`threshold_clusters`.  The valid rows are walked by rank (:func:`priority_order`: ``weight`` descending,
+    index ascending).  A row becomes a representative iff no representative of smaller rank has sim >= threshold to it; otherwise
+    it is a member of the representative of smaller rank with the largest similarity, ties to the smaller rank.  The similarity of a
+    pair is taken once, as (smaller rank) . (larger rank).  Returns (rep, sim, size, rank, rounds): ``rep`` int64 - the row's
+    representative in the caller's index space, a representative names itself, an invalid row has -1; ``sim`` float32 - a member's
+    similarity to ``rep``, NaN for representatives and invalid rows; ``size`` int64 - the rows of its cluster, 0 for an invalid
+    row; ``rank`` int64 - the row's place in the order; ``rounds`` - what :func:`representative_rounds` counts on this graph."""
+    if metric not in NEIGHBOUR_METRICS:
+        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    r32 = neighbour_rows(rows, "rows")
+    thr = float(cluster_threshold(threshold))
+    n = len(r32)
+    order = priority_order(weight, n)
+    rank = np.empty(n, dtype=np.int64)
+    rank[order] = np.arange(n)
+    r32 = r32[order]                                     # from here on index = rank
+    ok = np.isfinite(r32).all(axis=1)
+    r = np.where(ok[:, None], r32, 0).astype(np.float64)
+    if metric == "cosine":
+        norm = np.sqrt((r * r).sum(axis=1))
+        ok &= norm > 0
+        r = r / np.where(ok, norm, 1.0)[:, None]
+    # one pair at a time and the same sum either way round: identical rows get identical values, so a tie is a tie (a matrix
+    # product may round two equal pairs differently); read for i < j only
+    s = np.stack([(r * r[i]).sum(axis=1) for i in range(n)]) if n else np.zeros((0, 0))
+    edge = np.triu(s >= thr, 1) & ok[:, None] & ok[None, :]
+    rep_p = np.full(n, -1, dtype=np.int64)
+    sim_p = np.full(n, np.nan, dtype=np.float32)
+    reps = []
+    for j in np.flatnonzero(ok):                         # the walk
+        near = [i for i in reps if edge[i, j]]
+        if not near:
+            reps.append(int(j))
+            rep_p[j] = j
+        else:
+            best = max(near, key=lambda i: (s[i, j], -i))
+            rep_p[j], sim_p[j] = best, s[best, j]
+    count = np.bincount(rep_p[rep_p >= 0], minlength=n)
+    size_p = np.where(rep_p >= 0, count[np.maximum(rep_p, 0)], 0).astype(np.int64)
+    _, rounds = representative_rounds(edge, ok)
+    rep, sim, size = np.empty(n, np.int64), np.empty(n, np.float32), np.empty(n, np.int64)
+    rep[order] = np.where(rep_p >= 0, order[np.maximum(rep_p, 0)], -1)
+    sim[order], size[order] = sim_p, size_p
+    return rep, sim, size, rank, int(rounds)
+
+
+def representative_table(result, names=None):
+    """One record per cluster of a :func:`greedy_representatives` result (the tuple, a dict of its arrays, or anything with them as
+    attributes), ordered by the representative's rank: ``rep``, ``size``, ``members`` (every row of the cluster by rank, so the
+    representative comes first; the names where ``names`` is given, as is then ``rep``) and ``min_sim``, the smallest similarity of
+    a member to the representative (None for a cluster of one)."""
+    if isinstance(result, dict):
+        rep, sim, size, rank = (result[k] for k in REPRESENTATIVE_FIELDS)
+    elif isinstance(result, (tuple, list)):
+        rep, sim, size, rank = result[:4]
+    else:
+        rep, sim, size, rank = (getattr(result, k) for k in REPRESENTATIVE_FIELDS)
+    rep, size, rank = (np.asarray(a, dtype=np.int64) for a in (rep, size, rank))
+    sim = np.asarray(sim, dtype=np.float32)
+    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    by_rank = np.argsort(rank, kind="stable")
+    members = {}
+    for i in by_rank:
+        if rep[i] >= 0:
+            members.setdefault(int(rep[i]), []).append(int(i))
+    out = []
+    for r in by_rank:
+        if rep[r] != r:
+            continue
+        rows_of = members[int(r)]
+        sims = [float(sim[i]) for i in rows_of if i != r]
+        out.append({"rep": name(r), "size": int(size[r]), "members": [name(i) for i in rows_of], "min_sim": min(sims) if sims else None})
+    return out
+
+
 def prefix_of(input_path: Path) -> str:
     """nn_classification.py:106-108: stem, minus one more extension if the file is compressed."""
     prefix = Path(input_path).stem

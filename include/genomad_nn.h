@@ -550,6 +550,42 @@ int gnn_cluster(gnn_ctx* ctx, const float* rows_host, int64_t n, float threshold
 int gnn_cluster_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int metric, int64_t* label_dev, int64_t* degree_dev,
                     int64_t* size_dev, int64_t* rep_dev);
 
+/* ---- representatives among encoder embeddings: greedy clusters on the device --------------------------------
+ * "Which rows stand for the others": greedy incremental clustering, as dereplication tools do it.  THE ROWS ARRIVE IN PRIORITY ORDER
+ * (index = rank; NNEngine.representatives sorts by weight and maps the answer back).  Walked in that order, a valid row is a
+ * representative iff no representative of smaller rank has sim >= threshold to it; otherwise it is a member of the representative of
+ * smaller rank with the largest similarity, ties to the smaller rank.  Every member is within the threshold of its representative, no
+ * two representatives are within the threshold of each other, no cluster chains (gnn_cluster above is single linkage and does).  Rows,
+ * validity, metric and threshold are those of gnn_cluster; no forward pass runs and no other entry point's result changes.
+ *   value     the similarity of the pair i < j is the f32 that gnn_neighbours returns for query i and base row j (the same fragments,
+ *             k-steps, order and scale as gnn_cluster); (j, i) is never computed.  A tie with the threshold is an edge.
+ *   outputs   rep (int64): the row's representative, a representative names itself; sim (f32): a member's similarity to rep, NaN for a
+ *             representative; size (int64): the rows of its cluster.  An invalid row: -1, NaN, 0.
+ *   rounds    the device replaces the walk by synchronous rounds over the states of their start: an undecided row with an edge to a
+ *             smaller-rank row that became a representative in the previous round turns member; otherwise an undecided row with no
+ *             edge to a smaller-rank undecided row turns representative; otherwise it waits.  The representatives are the walk's.
+ *             *rounds_host = the rounds until no row is undecided: a property of the graph and the order, not of the device.  WORST
+ *             CASE: a path walked end to end takes as many rounds as it has rows, each a launch over the rows still live and one
+ *             synchronise.  The undecided row of smallest rank is decided in every round, so at most n rounds run; a round that does
+ *             not lower the count of undecided rows returns GNN_ERR_STATE with a message instead of going on.
+ *   ranges    0 <= n < 2^31, a finite threshold, a metric in [0, 1]; GNN_ERR_ARG with the value and the range in the message - checked
+ *             before the ctx is looked at, nothing is written.  n == 0 is GNN_OK, *rounds_host = 0 where the pointer is given.
+ *   exact     flags are ORs, keys 64-bit maxima, sizes integer adds: bit-identical for every split of the base
+ *             (gnn_debug_set_neighbour_split sets the range for this search too).
+ * Device memory, persistent in the ctx and grow-only: the 2 KB of fragments + 1 B per row of the neighbour search (shared with it;
+ * gnn_representatives: + the row's 2 KB of f32), 21 B per row of state, flag, key and size, one live byte per 64 and per 32 rows, 16 B
+ * of counters (gnn_representatives: + 20 B of results per row).  Nothing is n x n and no edge list is stored.
+ * gnn_representatives: host pointers, synchronous.  gnn_representatives_dev: device pointers (rounds_host stays a host pointer); it
+ * enqueues on the ctx stream but SYNCHRONISES IT ONCE PER ROUND - the host reads 8 bytes, the undecided count - and is asynchronous
+ * only in its last launches: the three arrays are ready when the stream is. */
+int gnn_representatives(gnn_ctx* ctx, const float* rows_host, int64_t n, float threshold, int metric, int64_t* rep_host, float* sim_host,
+                        int64_t* size_host, int64_t* rounds_host);
+int gnn_representatives_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int metric, int64_t* rep_dev, float* sim_dev,
+                            int64_t* size_dev, int64_t* rounds_host);
+/* measurement only: with gnn_profile_enable on, the HIP-event milliseconds of every round (its tile and decide launches) of the ctx's
+ * last gnn_representatives* call; *n_out = the rounds recorded, at most `capacity` of them are written. */
+int gnn_debug_representative_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
+
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
  * in-memory text buffer (already decompressed, newlines normalised to '\n').
@@ -633,7 +669,7 @@ int gnn_synth_windows_dev(gnn_ctx* ctx, uint64_t seed, int64_t first, int64_t n_
 #define GNN_K_ATTR_CONTRIB 5 /* attribution: the contribution kernel (second read of yp)     */
 #define GNN_K_REGIONS 6      /* region calls: every kernel of gnn_region_states_dev / gnn_call_regions */
 #define GNN_K_NEIGHBOURS 7   /* nearest neighbours: the prepare, tile and merge kernels of gnn_neighbours / gnn_neighbours_dev; clusters:
-                              * every kernel of gnn_cluster / gnn_cluster_dev */
+                              * every kernel of gnn_cluster / gnn_cluster_dev; representatives: every kernel of gnn_representatives* */
 #define GNN_K_COUNT 8
 int gnn_profile_enable(gnn_ctx* ctx, int on);
 int gnn_profile_reset(gnn_ctx* ctx);
