@@ -506,8 +506,13 @@ int gnn_debug_set_region_tile(gnn_ctx* ctx, int bins);
  *   values    split-f16 limbs (hi + lo), three v_mfma_f32_32x32x16_f16 products per k-step, f32 accumulation in a fixed order: a
  *             pair's similarity depends on its two rows only.  Cosine: the f32 norm is taken in a fixed order, the normalised row is
  *             scaled by 2^8 before the split and the f32 result by 2^-16 (both exact: the low limbs stay f16 normals) - within 1e-5 of
- *             the fp64 cosine, 1e-6 typical.  Dot: the rows are split unscaled: exact for small integers; needs |element| < 65504
- *             (f16 range) - beyond it a pair's similarity is not finite, and a NaN similarity is never returned.
+ *             the fp64 cosine, 1e-6 typical; a power of two per row changes no bit, from rows whose elements are all subnormal to
+ *             rows at FLT_MAX.  Dot: the rows are split unscaled: exact for small integers; within 1e-5 sum_i |x_i y_i| of the fp64
+ *             dot where every non-zero element has 2^-7 <= |element| < 65504 (the limbs carry an element to
+ *             max(2^-22 |element|, 2^-25): below 2^-3 the low limb is an f16 subnormal and the error is absolute - measured 0.09 of
+ *             that bound on heavy-tailed rows up to 6e4, 10 times the bound for elements below 2^-9: scale such rows first);
+ *             needs |element| < 65504 (f16 range) - beyond it a pair's similarity is not finite, and a NaN similarity is never
+ *             returned: such a row is nobody's neighbour, has none, and is a cluster of its own.
  * Device memory, persistent in the ctx and grow-only: per base row 2 KB of f16 fragments + 1 B (gnn_neighbours: + the row's 2 KB of
  * f32); the queries are walked in slabs of 16384 rows, and per query row of ONE slab: 2 KB of fragments (+ 2 KB of f32 for
  * gnn_neighbours; nothing in the self-search, which reads the base's), 8 k B per base range of partial lists (a range is at most
