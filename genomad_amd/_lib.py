@@ -120,6 +120,10 @@ SIGNATURES = {
     "gnn_call_regions": (_int, [_vp, _vp, _vp, _i64, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
     "gnn_region_states_dev": (_int, [_vp, _vp, _vp, _i64, C.c_double, _vp]),
     "gnn_debug_set_region_tile": (_int, [_vp, _int]),
+    "gnn_interval_plan": (_int, [_vp, _i64, _int, _int, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "gnn_embed_intervals": (_int, [_vp, _vp, _int, _i64, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "gnn_interval_fold_dev": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "gnn_interval_finish_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "gnn_neighbours": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_neighbours_dev": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_debug_set_neighbour_split": (_int, [_vp, _i64]),

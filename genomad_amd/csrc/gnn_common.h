@@ -152,6 +152,27 @@ struct RegionWorkspace {
     }
 };
 
+// ---- interval embeddings (gnn_intervals.hip): persistent, grow-only; a sibling of the other groups of ContigWorkspace ----
+// Per interval 16 B (its member range) for gnn_interval_fold_dev, and 1 B per row of ONE slice (the kept flags); gnn_embed_intervals
+// adds, per interval, 4 KB for the sums S and U (8 KB under GNN_STRAND_BOTH) and 20 B of score sums, count and coherence, and 12 B
+// per window of one slab (the combined scores of BOTH).
+struct IntervalWorkspace {
+    PinnedBuf<int64_t> h_range;                  // host image of d_range; rewritten only after `tables_read`
+    PinnedBuf<uint8_t> h_kept;                   // ... and of d_kept
+    hipEvent_t tables_read = nullptr;            // recorded behind their uploads
+    DevBuf<int64_t> d_range;                     // [w_lo (n_intervals) | w_hi (n_intervals)]
+    DevBuf<uint8_t> d_kept;                      // gnn_interval_fold_dev: the slice's kept flags
+    // gnn_embed_intervals
+    std::vector<int64_t> w_lo, w_hi;
+    DevBuf<float> d_sum, d_unit, d_sum_rev, d_unit_rev;      // HID per interval each
+    DevBuf<float> d_score_sum, d_coherence;      // 3 and 1 per interval
+    DevBuf<int32_t> d_count;
+    DevBuf<float> d_mix;                         // one slab's combined window scores
+    ~IntervalWorkspace() {
+        if (tables_read) (void)hipEventDestroy(tables_read);
+    }
+};
+
 // ---- nearest neighbours (gnn_neighbours.hip): persistent, grow-only.  Per base row 2 KB of f16 fragments + 1 B flag (and, for the
 // host entry point, its 2 KB of f32); per query row of ONE slab of 16384 the same, 8 k B per base range of partial lists and 12 k B
 // of results.  Nothing grows with the number of queries.
@@ -226,6 +247,8 @@ struct ContigWorkspace {
     DevBuf<float> d_attr;
     // gnn_call_regions / gnn_region_states_dev (gnn_regions.hip)
     RegionWorkspace regions;
+    // gnn_embed_intervals / gnn_interval_fold_dev (gnn_intervals.hip)
+    IntervalWorkspace intervals;
 
     // What the buffer groups hold, in windows / contigs + 1 / bins.  The head-room is counted in elements, so a buffer with
     // several elements per window or bin holds fewer of them than its neighbours: the smallest member decides.
@@ -544,6 +567,11 @@ int slab_pass(const ContigIn& in, ContigWorkspace& w, SeqFeed& feed, int64_t a, 
 // windows, compacted, where asked for; returns how many are kept.
 int64_t kept_windows(const ContigWorkspace& w, uint8_t* mask_or_null, int64_t* ids_or_null);
 void free_contig_ws(gnn_ctx* ctx);
+// GNN_OK, or GNN_ERR_ARG under the entry point's name for a stride outside [1, 6000] / a strand outside gnn_strand
+int check_stride(int stride, const char* fn);
+int check_strand(int strand, const char* fn);
+// lanes of the embedding folds (gnn_contigs.hip, gnn_intervals.hip): x 4 columns = one 2 KB row per step, read as float4s
+constexpr int FOLD_THREADS = HID / 4;
 
 int launch_front_c6(gnn_ctx* ctx, const uint8_t* bases, int64_t n);             // GNN_PREC_F16C6 -> ws.mp, ws.yp
 int launch_front_x3(gnn_ctx* ctx, const uint8_t* bases, int64_t n, int precision);   // GNN_PREC_F16X3 / BF16X3 (gnn_fused_x3.hip) -> ws.mp, ws.yp

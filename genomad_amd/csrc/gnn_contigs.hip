@@ -98,9 +98,7 @@ int launch_masked_segment_mean(gnn_ctx* ctx, const float* scores, const int64_t*
 // Per-contig embedding fold of one slab [a, a + m) of the window table: one block per contig the slab touches (ids are sorted, so
 // contigs ids[a] .. ids[a+m-1]), 128 lanes x 4 columns = one 2 KB row per step, read as float4s (coalesced: a row is contiguous).
 // The contig's kept windows of this slab are added to its running sum in window order, starting from what the slabs before left
-// there, so the sum is ((0 + e_0) + e_1) + ... whatever the slab and launch sizes.
-constexpr int FOLD_THREADS = HID / 4;
-
+// there, so the sum is ((0 + e_0) + e_1) + ... whatever the slab and launch sizes.  FOLD_THREADS: gnn_common.h.
 __global__ __launch_bounds__(FOLD_THREADS) void emb_fold_kernel(const float* __restrict__ emb, const int64_t* __restrict__ ids,
                                                                 const int32_t* __restrict__ window_n, const int32_t* __restrict__ counts,
                                                                 int64_t a, int64_t m, float* __restrict__ sums, int32_t* __restrict__ kept) {
@@ -518,7 +516,7 @@ extern "C" int gnn_classify_contigs_embed(gnn_ctx* ctx, const uint8_t* seq, int 
                             {contig_scores_host, window_ids_host, ids_capacity, n_windows_out, contig_emb_host});
 }
 
-static int check_stride(int stride, const char* fn) {
+int gnn::check_stride(int stride, const char* fn) {
     if (stride >= 1 && stride <= W) return GNN_OK;
     set_error(std::string(fn) + ": stride " + std::to_string(stride) + " is outside [1, " + std::to_string(W) + "]");
     return GNN_ERR_ARG;
@@ -554,7 +552,7 @@ extern "C" int gnn_scan_contigs(gnn_ctx* ctx, const uint8_t* seq, int seq_on_hos
                             {contig_scores_host_or_null}, StrandOut{GNN_STRAND_FORWARD}, &scan);
 }
 
-static int check_strand(int strand, const char* fn) {
+int gnn::check_strand(int strand, const char* fn) {
     if (strand == GNN_STRAND_FORWARD || strand == GNN_STRAND_REVERSE || strand == GNN_STRAND_BOTH) return GNN_OK;
     set_error(std::string(fn) + ": strand " + std::to_string(strand) + " is not a gnn_strand (0 forward, 1 reverse, 2 both)");
     return GNN_ERR_ARG;

@@ -122,6 +122,24 @@ class RegionResult:
                    stride=None if stride is None else int(stride), **table)
 
 
+class IntervalResult:
+    """What :meth:`NNEngine.embed_intervals` returns (the definition is ``sequence.interval_embeddings``).  ``stride`` and ``strand``
+    of the pass; per interval ``contig``, ``start``, ``end`` (int64; 0-based half-open bases within the contig), its member windows
+    [``w_lo``, ``w_hi``) in the window order of a scan at ``stride``, ``count`` (int32: the kept members), ``embedding``
+    (n_intervals, 512) float32 - their mean encoder embedding, a zero row where count == 0: ordinary rows for
+    :meth:`NNEngine.neighbours`, :meth:`NNEngine.cluster` and :meth:`NNEngine.representatives` -, ``coherence`` (float32 in [0, 1]:
+    the mean resultant length of the members' unit rows; low where the mean averages unlike windows) and ``scores``
+    (n_intervals, 3): the mean of the members' window scores."""
+    FIELDS = ("stride", "strand", "contig", "start", "end", "w_lo", "w_hi", "count", "embedding", "coherence", "scores")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw[k])
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+
 class ClusterResult:
     """What :meth:`NNEngine.cluster` returns (the definition is ``sequence.threshold_clusters``): ``label``, ``degree``, ``size``,
     ``rep`` (int64 (n,); -1 / 0 / 0 / -1 for an invalid row), the ``threshold`` as the float32 it was compared as, and ``metric``."""
@@ -547,6 +565,117 @@ class NNEngine:
         Returns (the scan's result, RegionResult with the derived table)."""
         scan = self._scan_contigs(np.asarray(seq), offsets, stride, single_window, precision, strand)
         return scan, self.call_regions(scan.track, scan.bin_offsets, penalty, self._offsets(offsets), stride)
+
+    # -- interval embeddings ---------------------------------------------------------------
+    def interval_plan(self, offsets: np.ndarray, stride: int, contig, start, end, single_window: bool = False):
+        """``gnn_interval_plan`` (host only): the member windows (w_lo, w_hi) of the intervals, validated
+        (``sequence.interval_windows`` is the numpy mirror)."""
+        offsets = self._offsets(offsets)
+        contig, start, end = self._intervals(contig, start, end)
+        w_lo, w_hi = np.zeros(len(contig), np.int64), np.zeros(len(contig), np.int64)
+        check(self.lib.gnn_interval_plan(offsets.ctypes.data, len(offsets) - 1, int(stride), int(bool(single_window)), contig.ctypes.data,
+                                         start.ctypes.data, end.ctypes.data, len(contig), w_lo.ctypes.data, w_hi.ctypes.data))
+        return w_lo, w_hi
+
+    @staticmethod
+    def _intervals(contig, start, end):
+        arrs = tuple(np.ascontiguousarray(a, dtype=np.int64).reshape(-1) for a in (contig, start, end))
+        if not len(arrs[0]) == len(arrs[1]) == len(arrs[2]):
+            raise ValueError("contig, start and end differ in length")
+        return arrs
+
+    def _embed_intervals(self, seq, offsets, stride, contig, start, end, strand, single_window, precision) -> IntervalResult:
+        (ptr, on_host, nbytes, offsets, n_contigs), _keep = self._packed(seq, offsets)
+        contig, start, end = self._intervals(contig, start, end)
+        n = len(contig)
+        code = self._strand_code(strand)
+        emb = np.zeros((n, _lib.EMBED_DIM), dtype=np.float32)
+        count = np.zeros(n, dtype=np.int32)
+        coherence = np.zeros(n, dtype=np.float32)
+        scores = np.zeros((n, _lib.CLASSES), dtype=np.float32)
+        check(self.lib.gnn_embed_intervals(self.ctx, ptr, on_host, nbytes, offsets.ctypes.data, n_contigs, int(stride),
+                                           int(bool(single_window)), _lib.PRECISIONS[precision], code, contig.ctypes.data, start.ctypes.data,
+                                           end.ctypes.data, n, emb.ctypes.data, count.ctypes.data, coherence.ctypes.data, scores.ctypes.data))
+        w_lo, w_hi = self.interval_plan(offsets, stride, contig, start, end, single_window) if n and n_contigs else (
+            np.zeros(n, np.int64), np.zeros(n, np.int64))
+        name = {v: k for k, v in _lib.STRANDS.items()}[code]
+        return IntervalResult(stride=int(stride), strand=name, contig=contig, start=start, end=end, w_lo=w_lo, w_hi=w_hi, count=count,
+                              embedding=emb, coherence=coherence, scores=scores)
+
+    def embed_intervals(self, seq: np.ndarray, offsets: np.ndarray, stride: int, contig, start, end, strand="forward",
+                        single_window: bool = False, precision=_lib.DEFAULT_PRECISION) -> IntervalResult:
+        """Encoder embeddings for parts of contigs (``gnn_embed_intervals``; the definition is ``sequence.interval_windows`` +
+        ``sequence.interval_embeddings``): the windows of a scan at ``stride`` go through the forward pass once more, and the rows of
+        the kept windows whose centre base lies in an interval (``contig``, ``start``, ``end``: sorted, disjoint, 0-based half-open
+        bases) are folded on the device into that interval's mean embedding, mean scores and coherence.  What
+        :meth:`embed_contigs` answers per contig, for the regions :meth:`call_regions` names.  Costs one scan of the same windows;
+        no window row leaves the device."""
+        return self._embed_intervals(np.asarray(seq), offsets, stride, contig, start, end, strand, single_window, precision)
+
+    def embed_intervals_dev(self, seq_ptr: int, offsets: np.ndarray, stride: int, contig, start, end, strand="forward",
+                            single_window: bool = False, precision=_lib.DEFAULT_PRECISION) -> IntervalResult:
+        """Same as :meth:`embed_intervals` for a packed contig buffer that is already resident in HBM."""
+        return self._embed_intervals(seq_ptr, offsets, stride, contig, start, end, strand, single_window, precision)
+
+    def embed_regions(self, seq: np.ndarray, offsets: np.ndarray, regions: RegionResult, strand="forward", single_window: bool = False,
+                      precision=_lib.DEFAULT_PRECISION) -> IntervalResult:
+        """:meth:`embed_intervals` on the regions of a :class:`RegionResult` built with ``offsets`` and ``stride`` (its
+        ``region_contig``, ``start``, ``end``): one embedding per called region.  Regions of a contig are sorted and disjoint by
+        construction.  A result without the derived table is refused."""
+        if regions.stride is None or regions.start is None or regions.end is None:
+            raise ValueError("the RegionResult has no base coordinates: call_regions(..., offsets=, stride=) builds them")
+        return self.embed_intervals(seq, offsets, regions.stride, regions.region_contig, regions.start, regions.end, strand, single_window,
+                                    precision)
+
+    def fold_intervals(self, rows, kept, w_lo, w_hi, scores=None, rows_per_call=None):
+        """The building blocks (``gnn_interval_fold_dev`` + ``gnn_interval_finish_dev``) on rows of the caller's choosing: ``rows``
+        (n, 512) float32, ``kept`` (n,) the mask, [w_lo[i], w_hi[i]) the member rows of interval i, ``scores`` (n, 3) or None.  The
+        rows are fed in slices of ``rows_per_call`` (None: all at once); no result depends on it.  Returns a dict of ``count``,
+        ``embedding``, ``coherence`` (float32) and ``scores`` as ``sequence.interval_embeddings``."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, _lib.EMBED_DIM)
+        n = len(rows)
+        kept = np.ascontiguousarray(np.asarray(kept).astype(bool), dtype=np.uint8)
+        w_lo, w_hi = (np.ascontiguousarray(a, dtype=np.int64).reshape(-1) for a in (w_lo, w_hi))
+        if len(kept) != n or len(w_lo) != len(w_hi):
+            raise ValueError("kept has one flag per row, and w_lo and w_hi one entry per interval")
+        if len(w_hi) and int(w_hi.max()) > n:
+            raise ValueError(f"a member range ends at {int(w_hi.max())}, beyond the {n} rows")
+        if scores is not None:
+            scores = np.ascontiguousarray(scores, dtype=np.float32).reshape(n, _lib.CLASSES)
+        ni = len(w_lo)
+        out = {"count": np.zeros(ni, np.int32), "embedding": np.zeros((ni, _lib.EMBED_DIM), np.float32),
+               "coherence": np.zeros(ni, np.float32), "scores": np.zeros((ni, _lib.CLASSES), np.float32)}
+        if ni == 0 or n == 0:
+            return out
+        step = n if rows_per_call is None else max(1, int(rows_per_call))
+        sizes = {"rows": rows.nbytes, "scores": n * 12, "sum": ni * 2048, "unit": ni * 2048, "score_sum": ni * 12, "count": ni * 4,
+                 "coherence": ni * 4}
+        bufs = {}
+        try:
+            for k, v in sizes.items():
+                bufs[k] = self.alloc(v)
+            bufs["rows"].upload(rows)
+            if scores is not None:
+                bufs["scores"].upload(scores)
+            for k in ("sum", "unit", "score_sum", "count"):
+                bufs[k].upload(np.zeros(sizes[k], np.uint8))
+            sc = bufs["scores"].ptr if scores is not None else None
+            ssum = bufs["score_sum"].ptr if scores is not None else None
+            for a in range(0, n, step):
+                check(self.lib.gnn_interval_fold_dev(self.ctx, bufs["rows"].ptr, sc, a, min(step, n - a), kept.ctypes.data, w_lo.ctypes.data,
+                                                     w_hi.ctypes.data, ni, bufs["sum"].ptr, bufs["unit"].ptr, ssum, bufs["count"].ptr))
+            check(self.lib.gnn_interval_finish_dev(self.ctx, bufs["sum"].ptr, bufs["unit"].ptr, None, None, ssum, bufs["count"].ptr, ni,
+                                                   bufs["sum"].ptr, bufs["coherence"].ptr, ssum))
+            self.sync()
+            out["embedding"] = bufs["sum"].download((ni, _lib.EMBED_DIM), np.float32)
+            out["count"] = bufs["count"].download((ni,), np.int32)
+            out["coherence"] = bufs["coherence"].download((ni,), np.float32)
+            if scores is not None:
+                out["scores"] = bufs["score_sum"].download((ni, _lib.CLASSES), np.float32)
+        finally:
+            for b in bufs.values():
+                b.free()
+        return out
 
     # -- nearest neighbours ---------------------------------------------------------------
     def set_neighbour_split(self, rows: int):

@@ -82,6 +82,9 @@ class Outputs:
         self.nn_regions_tsv_output = d / f"{p}_nn_regions.tsv"
         self.provirus_nn_regions_output = d / f"{p}_provirus_nn_regions.npz"
         self.provirus_nn_regions_tsv_output = d / f"{p}_provirus_nn_regions.tsv"
+        # written only when GENOMAD_AMD_REGION_EMBEDDINGS=1 (encoder embeddings per called region; no counterpart in the reference)
+        self.nn_region_embeddings_output = d / f"{p}_nn_region_embeddings.npz"
+        self.provirus_nn_region_embeddings_output = d / f"{p}_provirus_nn_region_embeddings.npz"
         # written only when GENOMAD_AMD_NEIGHBOURS is set (nearest neighbours among the per-contig embeddings; no counterpart in the reference)
         self.nn_neighbours_output = d / f"{p}_nn_neighbours.npz"
         self.provirus_nn_neighbours_output = d / f"{p}_provirus_nn_neighbours.npz"
@@ -522,6 +525,37 @@ def _regions_of_file(path):
         return -1, -1.0
 
 
+def embed_intervals_safely(eng, seq, offsets, stride, contig, start, end, strand, single_window, precision, console=None):
+    """NNEngine.embed_intervals with the range fallback of :func:`_range_fallback`: a piece with a non-finite interval score or
+    embedding is folded again with the next arithmetic, and everything returned is that pass's."""
+    def run(a):
+        res = eng.embed_intervals(seq, offsets, stride, contig, start, end, strand, single_window, a)
+        return np.concatenate([res.scores.ravel(), res.embedding.ravel()]), res
+    _, res, _ = _with_range_fallback(run, precision, console)
+    return res
+
+
+def region_embeddings_requested() -> bool:
+    """GENOMAD_AMD_REGION_EMBEDDINGS=1: main() also writes one encoder embedding per region called under GENOMAD_AMD_REGION_PENALTY
+    (<prefix>_nn_region_embeddings.npz: the mean over the scan windows centred in the region, their mean scores, their number and
+    the coherence of their rows); unset or 0: nothing changes.  Any other value is an error."""
+    v = os.environ.get("GENOMAD_AMD_REGION_EMBEDDINGS", "0").strip()
+    if v not in ("", "0", "1"):
+        raise ValueError(f"GENOMAD_AMD_REGION_EMBEDDINGS={v!r}: expected 1 (write the region embeddings) or 0")
+    return v == "1"
+
+
+def _region_embeddings_of_file(path):
+    """(stride, penalty, strand) a stage's region embeddings were computed with; no file = None (none were asked for)."""
+    if not Path(path).exists():
+        return None
+    try:
+        z = np.load(path)
+        return int(z["stride"]), float(z["penalty"]), str(z["strand"])
+    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
+        return -1, -1.0, ""
+
+
 NEIGHBOUR_METRIC = "cosine"          # what main() searches with
 
 
@@ -816,6 +850,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     occlusion_block = occlusion_block_requested()
     attribution_bin = attribution_bin_requested()
     region_penalty = region_penalty_requested()
+    region_embeddings = region_embeddings_requested()
     neighbours_k = neighbours_requested()
     clusters_threshold = clusters_requested()
     representatives_threshold = representatives_requested()
@@ -848,6 +883,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     if region_penalty is not None and scan_stride is None:
         console.error("GENOMAD_AMD_REGION_PENALTY needs GENOMAD_AMD_SCAN_STRIDE: regions are called along the score tracks of a scan. "
                       "Set GENOMAD_AMD_SCAN_STRIDE or unset GENOMAD_AMD_REGION_PENALTY.")
+        sys.exit(1)
+    if region_embeddings and region_penalty is None:
+        console.error("GENOMAD_AMD_REGION_EMBEDDINGS=1 needs GENOMAD_AMD_REGION_PENALTY: the embeddings are those of the regions called "
+                      "along the score tracks. Set GENOMAD_AMD_REGION_PENALTY or unset GENOMAD_AMD_REGION_EMBEDDINGS.")
         sys.exit(1)
     if neighbours_k is not None and not embeddings:
         console.error("GENOMAD_AMD_NEIGHBOURS needs GENOMAD_AMD_EMBEDDINGS=1: neighbours are searched among the per-contig encoder "
@@ -1011,7 +1050,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             write_tsv(tsv_path, names, predictions)                                  # :340-352 (always rewritten)
 
     def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, strand_path, occ_path, attr_path, regions_paths,
-                     nn_path, clusters_paths, representatives_paths, emb_path=None, scan_path=None):
+                     nn_path, clusters_paths, representatives_paths, emb_path=None, scan_path=None, region_emb_path=None):
         """Product path: the contig front end (NNEngine.classify_contigs) does windowing, the N rule,
         tokenising, classification and the per-contig mean on the GPU, so encoding and classification
         are one step; ``<prefix>_seq_window_id.npz`` is still written.  With several ranks the CONTIGS are
@@ -1045,7 +1084,14 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         ``representatives_paths`` (npz, tsv; GENOMAD_AMD_REPRESENTATIVES, which needs the embeddings): rank 0 runs the greedy clustering
         (NNEngine.representatives, cosine) on the same gathered embeddings, the contig's number of kept windows (the count of its
         entries in the gathered window ids: no further collective) as its weight, ties in FASTA order.  The files follow the
-        clusters files' rule."""
+        clusters files' rule.
+        ``region_emb_path`` (GENOMAD_AMD_REGION_EMBEDDINGS=1, which needs the regions): right after a piece's scan, while its
+        sequence is in memory, the piece's own track is segmented (regions are per contig and exact integers: they are the ones
+        rank 0 calls on the gathered track, which rank 0 checks) and NNEngine.embed_intervals folds the scan windows' encoder
+        embeddings into the regions, in the run's arithmetic and strand mode.  The file follows the occlusion file's rule, with
+        (stride, penalty, strand) in place of the block."""
+        region_emb_request = None if region_emb_path is None else (scan_stride, region_penalty, strand)
+        region_emb_file = region_emb_path if region_emb_path is not None else region_emb_default[what]
         clusters_path, clusters_tsv_path = clusters_paths
         representatives_path, representatives_tsv_path = representatives_paths
         regions_path, regions_tsv_path = regions_paths
@@ -1055,6 +1101,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                  and _attribution_bin_of_file(attr_path) == attribution_bin
                                  and _regions_of_file(regions_path) == regions_request
                                  and (regions_request is None) == (not regions_tsv_path.exists())
+                                 and _region_embeddings_of_file(region_emb_file) == region_emb_request
                                  and _neighbours_of_file(nn_path) == neighbours_k
                                  and (neighbours_k is None or _npz_strand(nn_path) == strand)
                                  and _clusters_of_file(clusters_path) == clusters_threshold
@@ -1079,7 +1126,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             eng = _engine()
             size = Path(fasta).stat().st_size * (1 if sequence.compression_of(fasta) == "uncompressed" else 4)
             precision = select_arithmetic(eng, precision, size, comm, console)
-            parts, emb_parts, scan_parts, strand_parts, occ_parts, attr_parts = [], [], [], [], [], []
+            parts, emb_parts, scan_parts, strand_parts, occ_parts, attr_parts, region_emb_parts = [], [], [], [], [], [], []
             sentinel = {"d": None, "done": False}
 
             def classify(key, nm, sq, off):
@@ -1089,6 +1136,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                 if scan_path is not None:       # after the normal classification, with the arithmetic the run selected
                     sc = (scan_contigs_safely(eng, sq, off, scan_stride, single_window, precision, console) if strand == "forward" else
                           scan_contigs_strand_safely(eng, sq, off, scan_stride, strand, single_window, precision, console))
+                    if region_emb_path is not None:                     # while the piece's sequence is in memory
+                        region_emb_parts.append((key, region_embeddings_of_piece(sc, sq, off)))
                     if region_penalty is not None:                      # the region table needs every contig's length on rank 0
                         sc = dict(sc.asdict(), contig_len=np.diff(np.asarray(off, np.int64)))
                     scan_parts.append((key, sc))
@@ -1096,6 +1145,18 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     occ_parts.append((key, occlude_contigs_safely(eng, sq, off, occlusion_block, single_window, precision, console)))
                 if attribution_bin is not None:
                     attr_parts.append((key, attribute_contigs_safely(eng, sq, off, attribution_bin, single_window, precision, console)))
+
+            def region_embeddings_of_piece(sc, sq, off):
+                """the piece's regions, called on its own track, and their interval embeddings: the fields of
+                sharding.gather_contig_region_embeddings"""
+                off = np.asarray(off, np.int64)
+                reg = eng.call_regions(sc.track, sc.bin_offsets, region_penalty, off, scan_stride)
+                iv = embed_intervals_safely(eng, sq, off, scan_stride, reg.region_contig, reg.start, reg.end, strand, single_window,
+                                            precision, console)
+                per_contig = np.bincount(reg.region_contig, minlength=len(off) - 1)
+                return {"region_offsets": np.concatenate([[0], np.cumsum(per_contig)]).astype(np.int64), "start": reg.start,
+                        "end": reg.end, "state": reg.region_state, "count": iv.count, "embedding": iv.embedding,
+                        "coherence": iv.coherence, "scores": iv.scores}
 
             def classify_piece(key, sq, off):
                 if not sentinel["done"] and len(off) > 1:           # this rank's first piece with a contig: the run's parity sample
@@ -1156,6 +1217,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             occ_all = sharding.gather_contig_occlusions(comm, occ_parts) if occlusion_block is not None else None
             attr_all = (sharding.gather_contig_attributions(comm, attr_parts, -(-ATTRIBUTION_POSITIONS // attribution_bin))
                         if attribution_bin is not None else None)
+            region_emb_all = sharding.gather_contig_region_embeddings(comm, region_emb_parts) if region_emb_path is not None else None
             gate()
             if not n_windows:                                                        # :297-299
                 console.error("No sequences were found. Please check your input FASTA.")
@@ -1212,6 +1274,21 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     for p in (regions_path, regions_tsv_path):
                         if p.exists():
                             p.unlink()
+                if region_emb_path is not None:
+                    re_ = region_emb_all
+                    mine = (re_["contig"], re_["start"], re_["end"], re_["state"])
+                    called = (res.region_contig, res.start, res.end, res.region_state)
+                    if not all(np.array_equal(a, b) for a, b in zip(mine, called)):
+                        raise RuntimeError(f"the regions the pieces embedded ({len(mine[0])}) are not the regions called on the gathered "
+                                           f"track ({len(called[0])}, {regions_path.name})")
+                    np.savez_compressed(region_emb_path, **{names_key: names, "contig": re_["contig"], "start": re_["start"],
+                                                            "end": re_["end"], "state": re_["state"], "embedding": re_["embedding"],
+                                                            "count": re_["count"], "coherence": re_["coherence"], "scores": re_["scores"],
+                                                            "stride": np.int64(scan_stride), "penalty": np.float64(region_penalty),
+                                                            "strand": np.array(strand)})
+                    console.log(f"Encoder embeddings of the {len(mine[0])} regions of the {what}s written to {region_emb_path.name}.")
+                elif region_emb_file.exists():      # likewise
+                    region_emb_file.unlink()
                 if neighbours_k is not None:
                     nn_idx, nn_sim = eng.neighbours(embeddings_all, None, neighbours_k, NEIGHBOUR_METRIC)
                     np.savez_compressed(nn_path, **{names_key: names, "k": np.int64(neighbours_k), "metric": np.array(NEIGHBOUR_METRIC),
@@ -1258,8 +1335,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             write_tsv(tsv_path, names, predictions)
 
     run = stage_device if device_front_end else stage
+    region_emb_default = {"sequence": outputs.nn_region_embeddings_output, "provirus": outputs.provirus_nn_region_embeddings_output}
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
     scan_kw = (lambda path: {"scan_path": path}) if scan_stride is not None else (lambda path: {})
+    region_emb_kw = (lambda path: {"region_emb_path": path}) if region_embeddings else (lambda path: {})
     strand_kw = ((lambda path, occ, attr, reg, nn, cl, rp: {"strand_path": path, "occ_path": occ, "attr_path": attr, "regions_paths": reg,
                                                             "nn_path": nn, "clusters_paths": cl, "representatives_paths": rp})
                  if device_front_end else (lambda path, occ, attr, reg, nn, cl, rp: {}))
@@ -1272,7 +1351,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                                            (outputs.nn_clusters_output, outputs.nn_clusters_tsv_output),
                                                            (outputs.nn_representatives_output, outputs.nn_representatives_tsv_output)),
             **emb_kw(outputs.nn_embeddings_output),
-            **scan_kw(outputs.nn_scan_output))
+            **scan_kw(outputs.nn_scan_output), **region_emb_kw(outputs.nn_region_embeddings_output))
         if classify_proviruses:                                                      # :248-281, :355-425
             run(outputs.find_proviruses_nucleotide_output, outputs.encoded_proviruses_dir,
                 outputs.provirus_window_id_output, outputs.provirus_nn_classification_npz_output,
@@ -1283,7 +1362,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                                                             outputs.provirus_nn_clusters_tsv_output),
                                                                            (outputs.provirus_nn_representatives_output,
                                                                             outputs.provirus_nn_representatives_tsv_output)),
-                **emb_kw(outputs.provirus_nn_embeddings_output), **scan_kw(outputs.provirus_nn_scan_output))
+                **emb_kw(outputs.provirus_nn_embeddings_output), **scan_kw(outputs.provirus_nn_scan_output),
+                **region_emb_kw(outputs.provirus_nn_region_embeddings_output))
     finally:
         if check_pool is not None:
             check_pool.shutdown(wait=True)

@@ -610,6 +610,94 @@ def region_table(regions, offsets, stride: int):
     return {"start": start, "end": end, "mean": mean.reshape(-1, 3), "margin": np.asarray(margin, dtype=np.float64)}
 
 
+def interval_windows(offsets, stride: int, iv_contig, iv_start, iv_end, single_window: bool = False):
+    """The member windows of intervals of contigs (``gnn_interval_plan``, in numpy).  Intervals are triples (contig, start, end),
+    0-based half-open bases within the contig, 0 <= start <= end <= L, sorted by (contig, start) and pairwise disjoint within a
+    contig; gaps and empty intervals are allowed, anything else is a ValueError naming the first offending interval.  Window k of
+    a contig (:func:`scan_spans` at ``stride``) has the centre base m_k = k * stride + len_k // 2 and belongs to the interval of
+    its contig with start <= m_k < end, or to none.  m_k is strictly increasing in k, so the members are one range of the global
+    window order.  Membership does not depend on the N rule.  Returns (w_lo, w_hi) int64 (n_intervals,): members [w_lo, w_hi)."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    _, lens, _, window_n, win_offsets, _ = scan_spans(offsets, stride, single_window)
+    centre = window_n.astype(np.int64) * int(stride) + lens.astype(np.int64) // 2
+    contig, start, end = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (iv_contig, iv_start, iv_end))
+    if not len(contig) == len(start) == len(end):
+        raise ValueError("iv_contig, iv_start and iv_end differ in length")
+    n_contigs = len(offsets) - 1
+    w_lo, w_hi = np.zeros(len(contig), np.int64), np.zeros(len(contig), np.int64)
+    for i, (c, s, e) in enumerate(zip(contig.tolist(), start.tolist(), end.tolist())):
+        def bad(why):
+            return ValueError(f"interval {i} (contig {c}, [{s}, {e})) {why}")
+        if not 0 <= c < n_contigs:
+            raise bad(f"names a contig outside [0, {n_contigs})")
+        length = int(offsets[c + 1] - offsets[c])
+        if s < 0:
+            raise bad("starts below 0")
+        if e < s:
+            raise bad("ends before it starts")
+        if e > length:
+            raise bad(f"ends beyond its contig of {length} bases")
+        if i > 0 and (contig[i - 1] > c or (contig[i - 1] == c and start[i - 1] > s)):
+            raise bad(f"is not sorted by (contig, start): it follows contig {int(contig[i - 1])}, start {int(start[i - 1])}")
+        if i > 0 and contig[i - 1] == c and end[i - 1] > s:
+            raise bad(f"overlaps interval {i - 1}, which ends at {int(end[i - 1])}")
+        a, b = int(win_offsets[c]), int(win_offsets[c + 1])
+        w_lo[i] = a + np.searchsorted(centre[a:b], s, side="left")
+        w_hi[i] = a + np.searchsorted(centre[a:b], e, side="left")
+    return w_lo, w_hi
+
+
+def interval_embeddings(rows, scores, kept, w_lo, w_hi, rows_rev=None):
+    """Interval embeddings, spelled out (the definition ``gnn_embed_intervals`` folds on the device; readable, not fast).  ``rows``
+    (n_windows, 512) float32 are the windows' encoder embeddings, ``scores`` (n_windows, 3) their scores of the strand mode (or
+    None), ``kept`` the N rule's mask, [w_lo[i], w_hi[i]) the members of interval i (:func:`interval_windows`).  With e_0, e_1, ...
+    the rows of an interval's KEPT members in window order:
+
+    - ``count`` int32: their number;
+    - ``embedding``: ((0 + e_0) + e_1) + ... in float32, divided once by float32(count); a zero row when count == 0;
+    - ``scores``: the same sequential float32 sum and single divide over the members' scores (zeros when ``scores`` is None);
+    - ``coherence`` float64 in [0, 1], the mean resultant length of the unit rows: u_i = e_i / sqrt(sum_j e_i[j]^2), a zero row
+      when that sum is 0 or not finite; coherence = |u_0 + u_1 + ...| / count, 0 when count == 0 - evaluated in float64.
+
+    ``rows_rev`` (the reverse windows' rows) selects strand mode ``both``: two independent sums, embedding = (S_f + S_r) /
+    float32(2 count) and coherence = |U_f + U_r| / (2 count); ``scores`` are then the combined window scores
+    (:func:`strand_mean`).  Returns a dict of ``count``, ``embedding``, ``scores`` and ``coherence``."""
+    rows = np.asarray(rows, dtype=np.float32).reshape(-1, NEIGHBOUR_DIM)
+    strands = [rows] if rows_rev is None else [rows, np.asarray(rows_rev, dtype=np.float32).reshape(-1, NEIGHBOUR_DIM)]
+    if scores is not None:
+        scores = np.asarray(scores, dtype=np.float32).reshape(-1, 3)
+    kept = np.asarray(kept).astype(bool)
+    n = len(w_lo)
+    out = {"count": np.zeros(n, np.int32), "embedding": np.zeros((n, NEIGHBOUR_DIM), np.float32),
+           "scores": np.zeros((n, 3), np.float32), "coherence": np.zeros(n, np.float64)}
+    for i in range(n):
+        members = [k for k in range(int(w_lo[i]), int(w_hi[i])) if kept[k]]
+        if not members:
+            continue
+        S = np.zeros(NEIGHBOUR_DIM, np.float32)
+        U = np.zeros(NEIGHBOUR_DIM, np.float64)
+        sc = np.zeros(3, np.float32)
+        for strand, r in enumerate(strands):
+            s = np.zeros(NEIGHBOUR_DIM, np.float32)
+            for k in members:
+                with np.errstate(over="ignore", invalid="ignore"):
+                    s = s + r[k]                                  # float32 + float32: the device's sequential sum
+                    n2 = np.square(r[k].astype(np.float64)).sum()
+                if n2 > 0 and np.isfinite(n2):
+                    U += r[k].astype(np.float64) / np.sqrt(n2)
+            S = s if strand == 0 else S + s
+        for k in members:
+            if scores is not None:
+                sc = sc + scores[k]
+        count = len(members)
+        out["count"][i] = count
+        with np.errstate(over="ignore", invalid="ignore"):
+            out["embedding"][i] = S / np.float32(len(strands) * count)
+        out["scores"][i] = sc / np.float32(count)
+        out["coherence"][i] = np.sqrt(np.square(U).sum()) / (len(strands) * count)
+    return out
+
+
 NEIGHBOUR_DIM = 512                       # GNN_EMBED_DIM: the rows are encoder embeddings
 NEIGHBOUR_K_MAX = 64
 NEIGHBOUR_METRICS = ("cosine", "dot")

@@ -311,6 +311,27 @@ def gather_contig_occlusions(comm, parts, root: int = 0):
                               OCCLUSION_EMPTY, "gather_contig_occlusions", root)
 
 
+REGION_EMBEDDING_FIELDS = ("start", "end", "state", "count", "embedding", "coherence", "scores")      # per region
+
+
+def gather_contig_region_embeddings(comm, parts, width: int = 512, root: int = 0):
+    """Interval embeddings of the regions of contig-sharded pieces -> ``root``, by the mechanism of
+    :func:`gather_contig_occlusions`: a third CSR family per contig.  ``result`` = a dict of ``region_offsets`` (the CSR of a piece's
+    regions over its contigs, n_contigs + 1 entries) and, per region, ``start``, ``end`` (int64 bases), ``state`` (uint8), ``count``
+    (int32), ``embedding`` (n, ``width``) float32, ``coherence`` (float32) and ``scores`` (n, 3) float32.  ``root`` rebases the CSR
+    and derives every region's contig index from it; the values are only moved, so the result is bit-identical for any number of
+    ranks.  Returns a dict of region_offsets, ``contig`` and the per-region arrays on ``root``, None elsewhere."""
+    empty = {"start": np.zeros(0, np.int64), "end": np.zeros(0, np.int64), "state": np.zeros(0, np.uint8), "count": np.zeros(0, np.int32),
+             "embedding": np.zeros((0, int(width)), np.float32), "coherence": np.zeros(0, np.float32),
+             "scores": np.zeros((0, 3), np.float32)}
+    out = _gather_csr_pieces(comm, parts, ("region_offsets",), REGION_EMBEDDING_FIELDS, empty, "gather_contig_region_embeddings", root)
+    if out is None:
+        return None
+    per_contig = np.diff(out["region_offsets"])
+    out["contig"] = np.repeat(np.arange(len(per_contig), dtype=np.int64), per_contig)
+    return out
+
+
 ATTRIBUTION_WINDOW_FIELDS = ("starts", "lens", "kept", "window_scores", "contrib", "bias", "logits")      # per window
 
 

@@ -490,6 +490,69 @@ int gnn_region_states_dev(gnn_ctx* ctx, const float* track_dev, const int64_t* b
 /* test aid: bins per tile of the scan, 1 <= bins <= 4096, default 256.  Results do not depend on it. */
 int gnn_debug_set_region_tile(gnn_ctx* ctx, int bins);
 
+/* ---- interval embeddings: encoder rows for parts of contigs ---------------------------------------------------
+ * gnn_classify_contigs_embed answers one embedding per contig; a region call (gnn_call_regions) names a PART of a contig.  These
+ * entry points fold the window embeddings of a scan into caller-given intervals, on the device; their rows are ordinary
+ * [n][GNN_EMBED_DIM] f32 input for gnn_neighbours / gnn_cluster / gnn_representatives.
+ *   windows     those of gnn_scan_plan at `stride` (1 .. 6000), honouring single_window; kept is the N rule's mask of gnn_scan_contigs.
+ *   intervals   n_intervals triples (iv_contig, iv_start, iv_end), int64, 0-based half-open bases within the contig:
+ *               0 <= start <= end <= L_contig, sorted by (contig, start), pairwise disjoint within a contig.  Gaps and empty intervals
+ *               (start == end) are allowed.  Anything else is GNN_ERR_ARG; the message names the first offending interval and why.
+ *   membership  window k of a contig (start k * stride, length len_k) has the centre base m_k = k * stride + len_k / 2 (integer
+ *               division) and belongs to the interval of its contig with start <= m_k < end, or to none.  m_k is strictly increasing
+ *               in k, so an interval's members are one range [w_lo, w_hi) of the global window order, possibly empty, and a window has
+ *               at most one interval.  Membership does not depend on kept; kept decides what is summed.  No overlap weights.
+ *   outputs     per interval, with e_0, e_1, ... the f32 rows gnn_embed returns for its KEPT members, in window order:
+ *               count      int32, the number of kept members.
+ *               embedding  [GNN_EMBED_DIM] f32: ((0 + e_0) + e_1) + ... in f32, divided once by (float)count - the arithmetic of
+ *                          gnn_classify_contigs_embed; a zero row when count == 0.
+ *               scores     [3] f32: the same sequential sum and single divide over the members' window scores of the strand mode.
+ *               coherence  f32 in [0, 1], the mean resultant length of the members' unit rows: u_i = e_i / sqrt(sum_j e_i[j]^2), or a
+ *                          zero row when that sum is 0 or not finite; U = ((0 + u_0) + u_1) + ...; coherence = |U| / count, 0 when
+ *                          count == 0.  1: the members point one way; low: the mean averages unlike rows.  The device computes it in
+ *                          f32 (a fixed reduction order per row, rsqrt); it agrees with a float64 evaluation of the definition to 1e-5
+ *                          for intervals of up to 64 kept members, and grows by about 3e-8 per further member.
+ *   strand      gnn_strand, as gnn_classify_contigs_strand.  REVERSE folds the reverse windows' rows and scores.  BOTH keeps two
+ *               independent sums per interval: embedding = (S_f + S_r) / (2 count), coherence = |U_f + U_r| / (2 count), scores fold
+ *               the combined window scores (f + r) * 0.5f.  Windows, membership, kept and count are the forward ones in every mode.
+ * No result depends on gnn_set_chunk, on where seq lives, or on what ran on the ctx before: every sum is sequential in window order
+ * and continues, slab by slab, from what the slabs before left in device memory.
+ *
+ * gnn_interval_plan - host only, no ctx, no GPU, like gnn_scan_plan - validates the intervals and answers w_lo_out / w_hi_out
+ * [n_intervals]: the member range of every interval in the window order of gnn_scan_plan.  GNN_ERR_ARG also for a stride outside
+ * [1, 6000] and decreasing offsets. */
+int gnn_interval_plan(const int64_t* offsets_host, int64_t n_contigs, int stride, int single_window, const int64_t* iv_contig,
+                      const int64_t* iv_start, const int64_t* iv_end, int64_t n_intervals, int64_t* w_lo_out, int64_t* w_hi_out);
+/* The pass over a packed contig buffer (seq, seq_on_host, seq_bytes, offsets_host as gnn_scan_contigs): the windows of the scan go
+ * through the forward pass slab by slab - under REVERSE / BOTH a slab's forward and reverse windows as one batch - and every slab's
+ * rows are folded into the intervals it touches before the next slab overwrites them.  emb_host[n_intervals][GNN_EMBED_DIM],
+ * count_host[n_intervals]; coherence_host_or_null[n_intervals] and scores_host_or_null[n_intervals][3] may be NULL.  Synchronous.
+ * n_intervals == 0 or n_contigs == 0 is GNN_OK and writes nothing.  GNN_PREC_F16C6: GNN_ERR_ARG, as for every embedding entry
+ * point.  Device memory, persistent in the ctx and grow-only: gnn_scan_contigs' window table, one slab of rows (2 KB per window of
+ * the slab) and, per interval, 4 KB for the two sums (8 KB under BOTH), 16 B for the member range and 20 B of scores, count and
+ * coherence.  Nothing grows with the number of windows beyond the table. */
+int gnn_embed_intervals(gnn_ctx* ctx, const uint8_t* seq, int seq_on_host, int64_t seq_bytes, const int64_t* offsets_host,
+                        int64_t n_contigs, int stride, int single_window, int precision, int strand, const int64_t* iv_contig,
+                        const int64_t* iv_start, const int64_t* iv_end, int64_t n_intervals, float* emb_host, int32_t* count_host,
+                        float* coherence_host_or_null, float* scores_host_or_null);
+/* The building block on device pointers, asynchronous on the ctx stream (the host arrays are read before the call returns).  Rows
+ * [first_window, first_window + n_rows) of ANY f32 matrix rows_dev[n][GNN_EMBED_DIM] (16-byte aligned) - and of scores_dev_or_null
+ * [n][3] - are folded into the running sums sum_dev / unit_dev [n_intervals][GNN_EMBED_DIM], score_sum_dev_or_null[n_intervals][3]
+ * and count_dev[n_intervals], which the caller zeroed before the first slice; slices are fed in increasing window order.
+ * kept_host[n] (1 = kept) is read at those rows; w_lo_host / w_hi_host[n_intervals] are member ranges as gnn_interval_plan answers
+ * them: 0 <= w_lo[i] <= w_hi[i] <= w_lo[i + 1], anything else is GNN_ERR_ARG naming the interval.  A range may reach beyond the
+ * slice: only its rows inside the slice are read.  n_rows == 0 or n_intervals == 0 is GNN_OK. */
+int gnn_interval_fold_dev(gnn_ctx* ctx, const float* rows_dev, const float* scores_dev_or_null, int64_t first_window, int64_t n_rows,
+                          const uint8_t* kept_host, const int64_t* w_lo_host, const int64_t* w_hi_host, int64_t n_intervals,
+                          float* sum_dev, float* unit_dev, float* score_sum_dev_or_null, int32_t* count_dev);
+/* The sums of gnn_interval_fold_dev -> the outputs, asynchronous on the ctx stream: emb_dev[n_intervals][GNN_EMBED_DIM],
+ * coherence_dev_or_null[n_intervals], scores_dev_or_null[n_intervals][3] (needs score_sum_dev).  sum_rev_dev_or_null and
+ * unit_rev_dev_or_null, given together, are a second strand's sums: the combination of GNN_STRAND_BOTH.  An output may be the sum
+ * it is made from (emb_dev == sum_dev, scores_dev == score_sum_dev): every element is read before it is written. */
+int gnn_interval_finish_dev(gnn_ctx* ctx, const float* sum_dev, const float* unit_dev, const float* sum_rev_dev_or_null,
+                            const float* unit_rev_dev_or_null, const float* score_sum_dev_or_null, const int32_t* count_dev,
+                            int64_t n_intervals, float* emb_dev, float* coherence_dev_or_null, float* scores_dev_or_null);
+
 /* ---- nearest neighbours among encoder embeddings: cosine top-k on the device ---------------------------------
  * "What is this contig like": for every query row the k most similar base rows, exact search (every pair is computed).  The rows are
  * what gnn_embed / gnn_classify_contigs_embed write; no forward pass runs and no other entry point's result changes.
@@ -672,7 +735,8 @@ int gnn_synth_windows_dev(gnn_ctx* ctx, uint64_t seed, int64_t first, int64_t n_
 #define GNN_K_F32_FRONT 3    /* unfused f32 front end (all its kernels)                   */
 #define GNN_K_ATTR_HEAD 4    /* attribution: dense head forward + backward (gnn_attribute*)  */
 #define GNN_K_ATTR_CONTRIB 5 /* attribution: the contribution kernel (second read of yp)     */
-#define GNN_K_REGIONS 6      /* region calls: every kernel of gnn_region_states_dev / gnn_call_regions */
+#define GNN_K_REGIONS 6      /* region calls: every kernel of gnn_region_states_dev / gnn_call_regions; interval embeddings: the fold and
+                              * finish kernels of gnn_embed_intervals / gnn_interval_fold_dev / gnn_interval_finish_dev */
 #define GNN_K_NEIGHBOURS 7   /* nearest neighbours: the prepare, tile and merge kernels of gnn_neighbours / gnn_neighbours_dev; clusters:
                               * every kernel of gnn_cluster / gnn_cluster_dev; representatives: every kernel of gnn_representatives* */
 #define GNN_K_COUNT 8
