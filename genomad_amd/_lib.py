@@ -132,6 +132,9 @@ SIGNATURES = {
     "gnn_representatives": (_int, [_vp, _vp, _i64, C.c_float, _int, _vp, _vp, _vp, _vp]),
     "gnn_representatives_dev": (_int, [_vp, _vp, _i64, C.c_float, _int, _vp, _vp, _vp, _vp]),
     "gnn_debug_representative_round_ms": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_linkage": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_linkage_dev": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_debug_linkage_round_ms": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_embed": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_embed_dev": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_debug_forward": (_int, [_vp, _vp, _i64, _int, _vp, C.POINTER(Taps)]),

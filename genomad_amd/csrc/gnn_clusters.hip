@@ -9,10 +9,11 @@
 //              (false for a NaN): the edge is counted at both ends and the two rows are joined.  No lists, no barrier per step.
 //   flatten    label = the root of the row's tree; the root gathers the tree's size and the key of its representative.
 //   summarise  every valid row takes its root's size and representative; an invalid row is -1 / 0 / 0 / -1.
-// Union-find: parent[] is int32 in global memory and a link always points to the SMALLER index, so a tree's root is its smallest
-// member and the label needs no tie rule.  parent[x] is x until one compare-and-swap replaces it by something smaller, and never
-// changes again.  Degrees and sizes are integer adds, the key an integer max: nothing depends on the order the workgroups run in or
-// on the split of the base.  No loop here waits for another workgroup: every loop's termination argument stands next to it.
+// Union-find (cl_peek and cl_join of gnn_nn_frag.h, shared with gnn_linkage.hip): parent[] is int32 in global memory and a link
+// always points to the SMALLER index, so a tree's root is its smallest member and the label needs no tie rule.  parent[x] is x until
+// one compare-and-swap replaces it by something smaller, and never changes again.  Degrees and sizes are integer adds, the key an
+// integer max: nothing depends on the order the workgroups run in or on the split of the base.  No loop here waits for another
+// workgroup: every loop's termination argument stands next to it.
 #include <cmath>
 
 #include "gnn_nn_frag.h"
@@ -42,41 +43,6 @@ struct ClusterArgs {
     int32_t* parent;
     int32_t* degree;
 };
-
-// a load that the compiler neither caches nor hoists; what it returns may still be older than another workgroup's compare-and-swap
-__device__ __forceinline__ int cl_peek(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// Join the trees of rows a and b; returns a member of the joined tree at or above both (the next edge of the same column starts
-// there).  Every value parent[x] ever holds is x or smaller than x, whatever copy of it a load returns.
-__device__ __forceinline__ int cl_join(int32_t* parent, int a, int b) {
-    // The pre-check: climb both trees with loads.  A stale load returns x itself (the climb stops early) or the one link x ever got:
-    // u and v stay members of a's and b's trees, and equal ones prove one tree.  Ends: a step goes to p < u, and u >= 0.
-    int u = a, v = b;
-    for (;;) {
-        const int p = cl_peek(parent + u);
-        if (p == u) break;
-        u = p;
-    }
-    for (;;) {
-        const int p = cl_peek(parent + v);
-        if (p == v) break;
-        v = p;
-    }
-    // The monotone loop.  It acts on the compare-and-swap's own return only.  old == u: u was a root and now points to the smaller
-    // v - done.  Otherwise u had the link old < u already, and joining old with v joins the same trees.  Ends: max(u, v) falls with
-    // every pass (the larger of the two is replaced by something smaller than itself) and is >= 0; no pass waits for anybody.
-    while (u != v) {
-        if (u < v) {
-            const int t = u;
-            u = v;
-            v = t;
-        }
-        const int old = atomicCAS(parent + u, u, v);
-        if (old == u) return v;
-        u = old;
-    }
-    return u;
-}
 
 // grid = (row tiles, base ranges), 256 threads.  LDS: the tile's fragments 128 KB, its rows' edge counts and flags.
 __global__ __launch_bounds__(256) void cl_tile_kernel(ClusterArgs a) {

@@ -211,6 +211,21 @@ struct RepresentativeWorkspace {
     std::vector<float> round_ms;                 // profiling on: HIP-event time of every round of the last call
 };
 
+// ---- single-linkage tree (gnn_linkage.hip): persistent, grow-only.  The fragments and flags are NeighbourWorkspace's bfrag / bvalid
+// (and d_base for the host entry point); here 40 B per row and one counter.  Nothing is n x n.
+struct LinkageWorkspace {
+    DevBuf<int32_t> parent;                      // union-find: a link points to a smaller index, a root to itself
+    DevBuf<int32_t> comp;                        // the root of the row's tree at the start of the round
+    DevBuf<unsigned long long> best;             // at a row: max of (image of the similarity << 32) | (2^32 - 1 - partner), 0: none
+    DevBuf<unsigned long long> cbest;            // at a root: max of (image << 32) | (2^32 - 1 - lo) over its rows' best pairs
+    DevBuf<int32_t> chi;                         // at a root: min of hi among the rows that match cbest
+    DevBuf<int32_t> ea, eb;                      // the edges recorded so far, in no order: lo, hi
+    DevBuf<unsigned> es;                         // and the image of their similarity
+    DevBuf<unsigned long long> count;            // edges recorded so far
+    PinnedBuf<unsigned long long> h_count;       // where the host reads it, once per round
+    std::vector<float> round_ms;                 // profiling on: HIP-event time of every round of the last call
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -398,6 +413,7 @@ struct gnn_ctx {
     gnn::NeighbourWorkspace nn;                   // gnn_neighbours.hip
     gnn::ClusterWorkspace cl;                     // gnn_clusters.hip
     gnn::RepresentativeWorkspace rp;              // gnn_representatives.hip
+    gnn::LinkageWorkspace lk;                     // gnn_linkage.hip
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;

@@ -1,0 +1,465 @@
+// Single-linkage tree among encoder embeddings (include/genomad_nn.h, "single-linkage tree"): the
+// maximum-similarity spanning tree (a forest where NaN pairs split it) of the complete graph over the valid rows, under the strict
+// order (value descending, lo ascending, hi ascending) - what Kruskal takes.  Boruvka rounds; a round is six launches:
+//   reset      best = cbest = 0, chi = INT_MAX, parent = comp (the trees of the last round, compressed to depth one; comp[i] is -1
+//              for an invalid row, which stays a tree of its own that nothing joins).
+//   tile       cl_tile_kernel's skeleton - 64 rows' fragments in LDS, the base streamed in steps of 256 columns, the same three
+//              products per k-step in the same order, the same scale - over the UPPER TRIANGLE only.  Every value with row < col, both
+//              rows valid, comp[row] != comp[col] and not NaN is a candidate AT BOTH ENDS: best[x] = max of
+//              (image(s) << 32) | (2^32 - 1 - partner) over the candidates at x, 0: none.  A lane keeps a running best per accumulator
+//              register over the workgroup's steps (the row side: one LDS max per row and wave at the end, one global max per row and
+//              workgroup) and takes one max per column and step (the column side).  A wave whose rows and columns share one component
+//              skips its k-loop.
+//   pick       cbest[root] = max of (image << 32) | (2^32 - 1 - lo) over the best keys of the component's rows; then chi[root] = min
+//              of hi among the rows that match: the component's best outgoing edge in the strict order.
+//   link       per root with a chosen edge: the edge is recorded - not when the other component chose the same edge and has the
+//              smaller root - in a slot taken by an integer add, and the two trees are joined (cl_join of gnn_nn_frag.h).
+//   flatten    comp[i] = the root of i's tree.
+// The host reads 8 bytes per round - the edges recorded so far - and stops after a round that adds none; it then sorts the records.
+// Every best, cbest and chi is an integer max or min of values that depend on the pair alone, the slots' order is sorted away: nothing
+// depends on the order the workgroups run in or on the split of the base.  No loop here waits for another workgroup: every loop's
+// termination argument stands next to it.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+#include "gnn_nn_frag.h"
+
+namespace gnn {
+namespace {
+
+constexpr int64_t N_MAX = (int64_t)1 << 31;      // rows are int32 in parent[] and 32 bits of a key
+constexpr int ROUNDS_MAX = 32;                   // components at least halve per round: n < 2^31 needs at most 31
+constexpr unsigned long long LOW32 = 0xffffffffull;
+
+// the order-preserving map of an f32 that is not NaN to a u32 > 0; -0 counts as +0
+__device__ __forceinline__ unsigned lk_image(float s) {
+    unsigned u = __float_as_uint(s);
+    u = u == 0x80000000u ? 0u : u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+inline float lk_value(unsigned image) {
+    const unsigned u = (image & 0x80000000u) ? (image ^ 0x80000000u) : ~image;
+    float s;
+    memcpy(&s, &u, sizeof s);
+    return s;
+}
+
+__device__ __forceinline__ unsigned long long lk_peek(const unsigned long long* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ unsigned long long lk_shfl_xor(unsigned long long v, int mask) {
+    const unsigned lo = __shfl_xor((unsigned)v, mask), hi = __shfl_xor((unsigned)(v >> 32), mask);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+__global__ __launch_bounds__(256) void lk_init_kernel(int64_t n, const uint8_t* __restrict__ valid, int32_t* __restrict__ comp) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) comp[i] = valid[i] ? (int32_t)i : -1;
+}
+
+__global__ __launch_bounds__(256) void lk_reset_kernel(int64_t n, const int32_t* __restrict__ comp, int32_t* __restrict__ parent,
+                                                       unsigned long long* __restrict__ best, unsigned long long* __restrict__ cbest,
+                                                       int32_t* __restrict__ chi) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    parent[i] = comp[i] < 0 ? (int32_t)i : comp[i];
+    best[i] = 0;
+    cbest[i] = 0;
+    chi[i] = INT_MAX;
+}
+
+struct LinkageArgs {
+    const uint4* frag;         // round_up(n, 64) / 32 blocks: rows and columns alike
+    const int32_t* comp;       // [n] the root of the row's component, flat; -1: the row is invalid
+    int64_t n;
+    int64_t split_rows;        // base rows per workgroup: a multiple of 32
+    float scale;               // 2^-16 for cosine, 1 for dot
+    unsigned long long* best;  // [n]
+};
+
+// The candidates of one step: C/D layout column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  The registers are walked
+// by ascending row and a lane's columns ascend with nb and with the steps, and `!(s <= best so far)` is false for an equal value (-0
+// equals +0) and true while the best is still NaN (none): the smallest partner among equals is kept.  An invalid column has scale =
+// NaN, so its values fail s == s like a NaN pair.  DIAG: the step overlaps the tile's own rows, and only then is row < col a test.
+template <bool DIAG>
+__device__ __forceinline__ void lk_candidates(const f32x16 (&acc)[2][2], const int* lcomp, int r0, int lane, const float (&scale)[2],
+                                              const int (&col)[2], const int (&cc)[2], float (&bval)[2][16], int (&bcol)[2][16],
+                                              float (&cval)[2], int (&crow)[2]) {
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int rg = r0 + row;
+            const int rc = lcomp[row];
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+                const float s = acc[mb][nb][r] * scale[nb];
+                const bool e = rc >= 0 && rc != cc[nb] && s == s && (!DIAG || rg < col[nb]);
+                if (e && !(s <= bval[mb][r])) {
+                    bval[mb][r] = s;
+                    bcol[mb][r] = col[nb];
+                }
+                if (e && !(s <= cval[nb])) {
+                    cval[nb] = s;
+                    crow[nb] = rg;
+                }
+            }
+        }
+}
+
+// grid = (row tiles, base ranges), 256 threads.  LDS: the tile's fragments 128 KB - one workgroup per CU, a wave has its SIMD's whole
+// register file: 64 VGPRs of running bests beside the 64 of acc -, its rows' components and bests.
+__global__ __launch_bounds__(256) void lk_tile_kernel(LinkageArgs a) {
+    __shared__ uint4 qs[2 * BLK_U4];
+    __shared__ unsigned long long lbest[QT];   // the rows' best partners among this workgroup's columns: flushed once
+    __shared__ int lcomp[QT];                  // the row's component, -1: the row is invalid or beyond n
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * QT;
+    const int64_t b0 = (int64_t)blockIdx.y * a.split_rows, b1 = min(a.n, b0 + a.split_rows);
+    if (b1 <= r0 + 1) return;              // no column of the range lies right of the tile's first row (the whole workgroup leaves)
+    {
+        const uint4* src = a.frag + (int64_t)blockIdx.x * 2 * BLK_U4;
+        for (int i = tid; i < 2 * BLK_U4; i += 256) qs[i] = src[i];
+        if (tid < QT) {
+            lbest[tid] = 0;
+            lcomp[tid] = r0 + tid < a.n ? a.comp[r0 + tid] : -1;
+        }
+    }
+    __syncthreads();
+    // the component all valid rows of the tile share; -1: they do not.  The same in every wave: a tile without a valid row leaves whole
+    int tc;
+    {
+        const int c = lcomp[lane];
+        const unsigned long long okm = __ballot(c >= 0);
+        if (okm == 0) return;
+        const int first = __shfl(c, __ffsll((long long)okm) - 1);
+        tc = __all(c < 0 || c == first) ? first : -1;
+    }
+    float bval[2][16];                     // per accumulator register: the best value at its row in this lane's columns, NaN: none
+    int bcol[2][16];                       // and its column, -1: none
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            bval[mb][r] = NAN;
+            bcol[mb][r] = -1;
+        }
+    const int64_t last_blk = (b1 - 1) / 32;
+    // what a step needs of its columns, fetched one step ahead - with one wave per SIMD nothing else hides a load in front of the
+    // fragment loads: the column's component (-1: no column, or an invalid one) and what best[] holds for it now.  The latter may be
+    // older than another workgroup's maximum by the time it is used: then a maximum is merely not skipped.
+    int ncc[2];
+    unsigned long long npk[2];
+    auto fetch = [&](int64_t c0) {
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            const int64_t col = (c0 / 32 + wave * 2 + nb) * 32 + (lane & 31);
+            ncc[nb] = col < b1 ? a.comp[col] : -1;
+            npk[nb] = col < b1 ? lk_peek(a.best + col) : ~0ull;
+        }
+    };
+    fetch(max(b0, r0));
+    // as in cl_tile_kernel.  Ends: c0 grows by STEP towards b1.
+    for (int64_t c0 = max(b0, r0); c0 < b1; c0 += STEP) {
+        const uint4* bp[2];
+        int col[2], cc[2];                 // the lane's column and its component, -1: no edge can end there
+        unsigned long long pk[2];
+        float scale[2];
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            const int64_t blk = c0 / 32 + wave * 2 + nb;
+            bp[nb] = a.frag + min(blk, last_blk) * BLK_U4 + lane;
+            col[nb] = (int)(blk * 32 + (lane & 31));       // read only where cc >= 0: there it is < b1 < 2^31
+            cc[nb] = ncc[nb];
+            pk[nb] = npk[nb];
+            scale[nb] = cc[nb] >= 0 ? a.scale : NAN;
+        }
+        fetch(c0 + STEP);
+        // the skip rule: every column of the wave is no column or in the tile's one component (tc = -1 equals no column's).
+        // Wave-uniform, and no barrier follows in the loop
+        if (__all((cc[0] < 0 || cc[0] == tc) && (cc[1] < 0 || cc[1] == tc))) continue;
+        f32x16 acc[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        BFrag f0, f1;
+        nn_load_b(f0, bp, 0);
+#pragma unroll 1
+        for (int ks = 0; ks < NKS; ks += 2) {              // k-step ks + 1 is fetched under the MFMAs of ks
+            nn_load_b(f1, bp, ks + 1);
+            nn_mfma(qs, ks, lane, f0, acc);
+            nn_load_b(f0, bp, min(ks + 2, NKS - 1));
+            nn_mfma(qs, ks + 1, lane, f1, acc);
+        }
+        float cval[2] = {NAN, NAN};        // per column of the lane: the best value in this step's rows, and its row
+        int crow[2] = {-1, -1};
+        if (c0 < r0 + QT)                  // wave-uniform
+            lk_candidates<true>(acc, lcomp, (int)r0, lane, scale, col, cc, bval, bcol, cval, crow);
+        else
+            lk_candidates<false>(acc, lcomp, (int)r0, lane, scale, col, cc, bval, bcol, cval, crow);
+        // ---- the column side: a column is one lane's in all its registers and the other half's - one max per column and step, and
+        // only where it can raise what the load of a step ago saw
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            unsigned long long key = crow[nb] >= 0 ? ((unsigned long long)lk_image(cval[nb]) << 32) | (LOW32 - (unsigned)crow[nb]) : 0ull;
+            const unsigned long long other = lk_shfl_xor(key, 32);
+            key = other > key ? other : key;
+            if (lane < 32 && key > pk[nb]) atomicMax(a.best + col[nb], key);     // key > 0 only where cc >= 0: col < b1
+        }
+    }
+    // ---- the row side, once: a row's candidates lie in one register of the 32 lanes of a half
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            unsigned long long key = bcol[mb][r] >= 0 ? ((unsigned long long)lk_image(bval[mb][r]) << 32) | (LOW32 - (unsigned)bcol[mb][r]) : 0ull;
+#pragma unroll
+            for (int s = 16; s > 0; s >>= 1) {
+                const unsigned long long other = lk_shfl_xor(key, s);
+                key = other > key ? other : key;
+            }
+            if ((lane & 31) == 0 && key) atomicMax(&lbest[mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)], key);
+        }
+    __syncthreads();
+    if (tid < QT && lbest[tid]) atomicMax(a.best + r0 + tid, lbest[tid]);       // lbest > 0 only at a valid row < n
+}
+
+// best[i] names i's best partner; the component's key names the smaller end of the pair
+__global__ __launch_bounds__(256) void lk_pick_lo_kernel(int64_t n, const int32_t* __restrict__ comp, const unsigned long long* __restrict__ best,
+                                                         unsigned long long* __restrict__ cbest) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || best[i] == 0) return;
+    const unsigned partner = (unsigned)(LOW32 - (best[i] & LOW32));
+    const unsigned lo = min((unsigned)i, partner);
+    atomicMax(cbest + comp[i], (best[i] & ~LOW32) | (LOW32 - lo));
+}
+
+__global__ __launch_bounds__(256) void lk_pick_hi_kernel(int64_t n, const int32_t* __restrict__ comp, const unsigned long long* __restrict__ best,
+                                                         const unsigned long long* __restrict__ cbest, int32_t* __restrict__ chi) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || best[i] == 0) return;
+    const unsigned partner = (unsigned)(LOW32 - (best[i] & LOW32));
+    const unsigned lo = min((unsigned)i, partner), hi = max((unsigned)i, partner);
+    if (((best[i] & ~LOW32) | (LOW32 - lo)) == cbest[comp[i]]) atomicMin(chi + comp[i], (int32_t)hi);
+}
+
+// One thread per root with a chosen edge.  comp, cbest and chi are the round's and constant here; only parent[] changes.
+__global__ __launch_bounds__(256) void lk_link_kernel(int64_t n, int64_t capacity, const int32_t* __restrict__ comp,
+                                                      const unsigned long long* __restrict__ cbest, const int32_t* __restrict__ chi,
+                                                      int32_t* parent, int32_t* __restrict__ ea, int32_t* __restrict__ eb,
+                                                      unsigned* __restrict__ es, unsigned long long* __restrict__ count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || comp[i] != (int32_t)i || cbest[i] == 0) return;
+    const int lo = (int)(LOW32 - (cbest[i] & LOW32)), hi = chi[i];
+    if ((int64_t)hi >= n) return;          // never: the row that set cbest[i] matches it and has set chi[i]
+    const int other = comp[lo] == (int32_t)i ? comp[hi] : comp[lo];
+    // a mutual pick is recorded once, by the smaller root; any other pair of components chose two different edges
+    const bool mutual = cbest[other] == cbest[i] && chi[other] == hi;
+    if (!(mutual && other < (int)i)) {
+        const unsigned long long slot = atomicAdd(count, 1ull);
+        if ((int64_t)slot < capacity) {    // a forest has at most n - 1 edges: always
+            ea[slot] = lo;
+            eb[slot] = hi;
+            es[slot] = (unsigned)(cbest[i] >> 32);
+        }
+    }
+    (void)cl_join(parent, (int)i, other);
+}
+
+// A launch of its own behind the links: plain loads see every link.  Ends: a step of the climb goes to p < r, and r >= 0.
+__global__ __launch_bounds__(256) void lk_flatten_kernel(int64_t n, const int32_t* __restrict__ parent, int32_t* comp) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || comp[i] < 0) return;     // an invalid row stays -1
+    int r = (int)i;
+    for (;;) {
+        const int p = parent[r];
+        if (p == r) break;
+        r = p;
+    }
+    comp[i] = r;
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+
+int check_linkage_args(const char* fn, const void* rows, int64_t n, int metric, const void* a, const void* b, const void* sim, const void* valid,
+                       const void* n_edges, const void* rounds) {
+    const std::string f(fn);
+    if (n < 0 || n >= N_MAX) {
+        set_error(f + ": " + std::to_string(n) + " rows is outside [0, 2^31)");
+        return GNN_ERR_ARG;
+    }
+    if (metric != GNN_KNN_COSINE && metric != GNN_KNN_DOT) {
+        set_error(f + ": metric " + std::to_string(metric) + " is outside [0, 1] (GNN_KNN_COSINE, GNN_KNN_DOT)");
+        return GNN_ERR_ARG;
+    }
+    if (!n_edges || !rounds || (n > 0 && (!rows || !valid)) || (n > 1 && (!a || !b || !sim))) {
+        set_error("bad argument to " + f + ": the rows, the four arrays, n_edges and rounds are required");
+        return GNN_ERR_ARG;
+    }
+    return GNN_OK;
+}
+
+// n > 0 rows on the device -> the sorted tree, the flags and the two counts on the host.  The ctx's stream is synchronised once per
+// round (the host reads the number of edges) and once for the records.
+int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int metric, int64_t* a_host, int64_t* b_host, float* sim_host,
+           uint8_t* valid_host, int64_t* n_edges_host, int64_t* rounds_host) {
+    NeighbourWorkspace& w = ctx->nn;
+    LinkageWorkspace& k = ctx->lk;
+    const int64_t capacity = n - 1;
+    int rc = nn_prepare(ctx, rows_dev, n, metric, w.bfrag, w.bvalid);
+    if (!rc) rc = nn_reserve(ctx, k.parent, (size_t)n);
+    if (!rc) rc = nn_reserve(ctx, k.comp, (size_t)n);
+    if (!rc) rc = nn_reserve(ctx, k.chi, (size_t)n);
+    if (!rc) rc = nn_reserve(ctx, k.best, (size_t)n);
+    if (!rc) rc = nn_reserve(ctx, k.cbest, (size_t)n);
+    if (!rc) rc = nn_reserve(ctx, k.ea, (size_t)n);
+    if (!rc) rc = nn_reserve(ctx, k.eb, (size_t)n);
+    if (!rc) rc = nn_reserve(ctx, k.es, (size_t)n);
+    if (!rc) rc = nn_reserve(ctx, k.count, 1);
+    if (!rc) rc = k.h_count.reserve(1);
+    if (rc) return rc;
+    const int64_t tiles = (n + QT - 1) / QT;
+    const int64_t split_rows = nn_split_rows(ctx, tiles, n);
+    const int64_t splits = (n + split_rows - 1) / split_rows;
+    if (splits > 65535) {
+        set_error(std::string(fn) + ": " + std::to_string(n) + " rows in ranges of " + std::to_string(split_rows) + " are more than 65535 ranges");
+        return GNN_ERR_ARG;
+    }
+    const dim3 per_row((unsigned)((n + 255) / 256)), tile_grid((unsigned)tiles, (unsigned)splits);
+    LinkageArgs a;
+    a.frag = w.bfrag.get();
+    a.comp = k.comp.get();
+    a.n = n;
+    a.split_rows = split_rows;
+    a.scale = metric == GNN_KNN_COSINE ? 1.f / 65536.f : 1.f;
+    a.best = k.best.get();
+    k.round_ms.clear();
+    {
+        ProfScope prof(ctx, GNN_K_NEIGHBOURS);
+        GNN_HIP(hipMemsetAsync(k.count.get(), 0, sizeof(unsigned long long), ctx->stream));
+        hipLaunchKernelGGL(lk_init_kernel, per_row, dim3(256), 0, ctx->stream, n, w.bvalid.get(), k.comp.get());
+        GNN_HIP(hipGetLastError());
+    }
+    // One Boruvka round per pass.  Every component with an outgoing edge is joined to another one, so the components that are not
+    // yet final at least halve: at most 31 rounds add an edge for n < 2^31, and one more adds none.  Ends: the loop is bounded by
+    // ROUNDS_MAX whatever the device answers; it leaves early after a round that adds no edge or completes a spanning tree.
+    unsigned long long edges = 0;
+    int64_t rounds = 0;
+    for (int pass = 0;; ++pass) {
+        if (pass == ROUNDS_MAX) {
+            set_error(std::string(fn) + ": round " + std::to_string(pass + 1) + " would be needed for " + std::to_string(n) + " rows (" +
+                      std::to_string(edges) + " edges so far): at most " + std::to_string(ROUNDS_MAX) + " rounds can be");
+            return GNN_ERR_STATE;
+        }
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        {
+            ProfScope prof(ctx, GNN_K_NEIGHBOURS);
+            e0 = prof.a;
+            e1 = prof.b;
+            hipLaunchKernelGGL(lk_reset_kernel, per_row, dim3(256), 0, ctx->stream, n, k.comp.get(), k.parent.get(), k.best.get(), k.cbest.get(),
+                               k.chi.get());
+            GNN_HIP(hipGetLastError());
+            hipLaunchKernelGGL(lk_tile_kernel, tile_grid, dim3(256), 0, ctx->stream, a);
+            GNN_HIP(hipGetLastError());
+            hipLaunchKernelGGL(lk_pick_lo_kernel, per_row, dim3(256), 0, ctx->stream, n, k.comp.get(), k.best.get(), k.cbest.get());
+            GNN_HIP(hipGetLastError());
+            hipLaunchKernelGGL(lk_pick_hi_kernel, per_row, dim3(256), 0, ctx->stream, n, k.comp.get(), k.best.get(), k.cbest.get(), k.chi.get());
+            GNN_HIP(hipGetLastError());
+            hipLaunchKernelGGL(lk_link_kernel, per_row, dim3(256), 0, ctx->stream, n, capacity, k.comp.get(), k.cbest.get(), k.chi.get(),
+                               k.parent.get(), k.ea.get(), k.eb.get(), k.es.get(), k.count.get());
+            GNN_HIP(hipGetLastError());
+            hipLaunchKernelGGL(lk_flatten_kernel, per_row, dim3(256), 0, ctx->stream, n, k.parent.get(), k.comp.get());
+            GNN_HIP(hipGetLastError());
+        }
+        GNN_HIP(hipMemcpyAsync(k.h_count.get(), k.count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        GNN_HIP(hipStreamSynchronize(ctx->stream));
+        const unsigned long long now = k.h_count.get()[0];
+        float ms = 0.f;                    // profiling only: the round's two events have completed with the synchronise above
+        if (e0 && e1 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) k.round_ms.push_back(ms);
+        if (now > (unsigned long long)capacity) {
+            set_error(std::string(fn) + ": round " + std::to_string(pass + 1) + " recorded " + std::to_string(now) + " edges among " +
+                      std::to_string(n) + " rows: a forest has at most n - 1");
+            return GNN_ERR_STATE;
+        }
+        if (now == edges) break;
+        edges = now;
+        ++rounds;
+        if (edges == (unsigned long long)capacity) break;
+    }
+    const size_t m = (size_t)edges;
+    std::vector<int32_t> ea(m), eb(m);
+    std::vector<unsigned> es(m);
+    if (m) {
+        GNN_HIP(hipMemcpyAsync(ea.data(), k.ea.get(), m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        GNN_HIP(hipMemcpyAsync(eb.data(), k.eb.get(), m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        GNN_HIP(hipMemcpyAsync(es.data(), k.es.get(), m * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    GNN_HIP(hipMemcpyAsync(valid_host, w.bvalid.get(), (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    GNN_HIP(hipStreamSynchronize(ctx->stream));
+    std::vector<int64_t> order(m);
+    std::iota(order.begin(), order.end(), (int64_t)0);
+    std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) {
+        if (es[x] != es[y]) return es[x] > es[y];
+        if (ea[x] != ea[y]) return ea[x] < ea[y];
+        return eb[x] < eb[y];
+    });
+    for (int64_t i = 0; i < capacity; ++i) {
+        const bool edge = i < (int64_t)m;
+        a_host[i] = edge ? ea[order[i]] : -1;
+        b_host[i] = edge ? eb[order[i]] : -1;
+        sim_host[i] = edge ? lk_value(es[order[i]]) : NAN;
+    }
+    *n_edges_host = (int64_t)m;
+    *rounds_host = rounds;
+    return GNN_OK;
+}
+
+}  // namespace
+}  // namespace gnn
+
+using namespace gnn;
+
+extern "C" int gnn_linkage_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, int metric, int64_t* a_host, int64_t* b_host, float* sim_host,
+                               uint8_t* valid_host, int64_t* n_edges_host, int64_t* rounds_host) {
+    const char* const fn = "gnn_linkage_dev";
+    if (int rc = check_linkage_args(fn, rows_dev, n, metric, a_host, b_host, sim_host, valid_host, n_edges_host, rounds_host)) return rc;
+    if (int rc = check_ctx(ctx)) return rc;
+    *n_edges_host = 0;
+    *rounds_host = 0;
+    if (n == 0) return GNN_OK;
+    return lk_run(ctx, fn, rows_dev, n, metric, a_host, b_host, sim_host, valid_host, n_edges_host, rounds_host);
+}
+
+extern "C" int gnn_linkage(gnn_ctx* ctx, const float* rows_host, int64_t n, int metric, int64_t* a_host, int64_t* b_host, float* sim_host,
+                           uint8_t* valid_host, int64_t* n_edges_host, int64_t* rounds_host) {
+    const char* const fn = "gnn_linkage";
+    if (int rc = check_linkage_args(fn, rows_host, n, metric, a_host, b_host, sim_host, valid_host, n_edges_host, rounds_host)) return rc;
+    if (int rc = check_ctx(ctx)) return rc;
+    *n_edges_host = 0;
+    *rounds_host = 0;
+    if (n == 0) return GNN_OK;
+    NeighbourWorkspace& w = ctx->nn;
+    if (int rc = nn_reserve(ctx, w.d_base, (size_t)n * D)) return rc;
+    GNN_HIP(hipMemcpyAsync(w.d_base, rows_host, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    return lk_run(ctx, fn, w.d_base, n, metric, a_host, b_host, sim_host, valid_host, n_edges_host, rounds_host);
+}
+
+extern "C" int gnn_debug_linkage_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (capacity < 0 || (capacity > 0 && !ms_out) || !n_out) {
+        set_error("bad argument to gnn_debug_linkage_round_ms: a capacity >= 0, its array and n_out are required");
+        return GNN_ERR_ARG;
+    }
+    const std::vector<float>& ms = ctx->lk.round_ms;
+    *n_out = (int64_t)ms.size();
+    for (int64_t i = 0; i < std::min<int64_t>(capacity, (int64_t)ms.size()); ++i) ms_out[i] = ms[i];
+    return GNN_OK;
+}

@@ -1,6 +1,7 @@
-// What the searches over encoder embeddings share (gnn_neighbours.hip, gnn_clusters.hip, gnn_representatives.hip): the fragment layout
-// and its constants, the prepare kernel and its launcher, the fragment loads and the three-product MFMA step, the split of the base
-// over workgroups.  All of them run the same k-steps in the same order on the same fragments: a pair's f32 value is the same in each.
+// What the searches over encoder embeddings share (gnn_neighbours.hip, gnn_clusters.hip, gnn_representatives.hip, gnn_linkage.hip): the
+// fragment layout and its constants, the prepare kernel and its launcher, the fragment loads and the three-product MFMA step, the
+// split of the base over workgroups, the union-find.  All of them run the same k-steps in the same order on the same fragments: a
+// pair's f32 value is the same in each.
 #pragma once
 #include <cmath>
 
@@ -111,6 +112,43 @@ __device__ __forceinline__ void nn_mfma(const uint4* qs, int ks, int lane, const
             acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[mb][nb], 0, 0, 0);
         }
     }
+}
+
+// ---- the union-find of the clusters and of the single-linkage tree (gnn_clusters.hip, gnn_linkage.hip): parent[] is int32 in global
+// memory, a link always points to the SMALLER index, a root to itself.
+// a load that the compiler neither caches nor hoists; what it returns may still be older than another workgroup's compare-and-swap
+__device__ __forceinline__ int cl_peek(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Join the trees of rows a and b; returns a member of the joined tree at or above both (the next edge of the same column starts
+// there).  Every value parent[x] ever holds is x or smaller than x, whatever copy of it a load returns.
+__device__ __forceinline__ int cl_join(int32_t* parent, int a, int b) {
+    // The pre-check: climb both trees with loads.  A stale load returns x itself (the climb stops early) or the one link x ever got:
+    // u and v stay members of a's and b's trees, and equal ones prove one tree.  Ends: a step goes to p < u, and u >= 0.
+    int u = a, v = b;
+    for (;;) {
+        const int p = cl_peek(parent + u);
+        if (p == u) break;
+        u = p;
+    }
+    for (;;) {
+        const int p = cl_peek(parent + v);
+        if (p == v) break;
+        v = p;
+    }
+    // The monotone loop.  It acts on the compare-and-swap's own return only.  old == u: u was a root and now points to the smaller
+    // v - done.  Otherwise u had the link old < u already, and joining old with v joins the same trees.  Ends: max(u, v) falls with
+    // every pass (the larger of the two is replaced by something smaller than itself) and is >= 0; no pass waits for anybody.
+    while (u != v) {
+        if (u < v) {
+            const int t = u;
+            u = v;
+            v = t;
+        }
+        const int old = atomicCAS(parent + u, u, v);
+        if (old == u) return v;
+        u = old;
+    }
+    return u;
 }
 
 // a buffer that grows is freed first: nothing enqueued may still read it

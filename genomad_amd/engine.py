@@ -211,6 +211,54 @@ class RepresentativeResult:
                    metric=str(metric))
 
 
+class LinkageResult:
+    """What :meth:`NNEngine.linkage` returns (the definition is ``sequence.single_linkage_tree``): the single-linkage tree's edges,
+    best first - ``a`` (int64, the smaller row), ``b`` (int64, the larger), ``sim`` (float32), trimmed to ``n_edges`` -, ``valid``
+    (uint8 (n,)), ``n``, ``n_valid``, ``rounds`` (the Boruvka rounds of the device that added an edge) and ``metric``."""
+    FIELDS = ("a", "b", "sim", "valid", "n", "n_valid", "rounds", "metric")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw.get(k))
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    @property
+    def n_edges(self) -> int:
+        return len(self.a)
+
+    def cut(self, threshold) -> np.ndarray:
+        """``sequence.linkage_cut``: the ``label`` of :meth:`NNEngine.cluster` at ``threshold``"""
+        from . import sequence as S
+        return S.linkage_cut(self.a, self.b, self.sim, self.valid, threshold)
+
+    def cluster_counts(self, thresholds) -> np.ndarray:
+        """``sequence.linkage_cluster_counts``: the clusters a cut leaves at each threshold"""
+        from . import sequence as S
+        return S.linkage_cluster_counts(self.sim, self.n_valid, thresholds)
+
+    def matrix(self) -> np.ndarray:
+        """``sequence.linkage_matrix``: SciPy's convention, distance = 1 - sim; cosine, all rows valid and a spanning tree only"""
+        from . import sequence as S
+        if self.metric != "cosine":
+            raise ValueError(f"metric {self.metric!r}: 1 - sim is a distance under cosine only")
+        if self.n_valid != self.n:
+            raise ValueError(f"{self.n - self.n_valid} of {self.n} rows are invalid: a linkage matrix needs every row")
+        return S.linkage_matrix(self.a, self.b, self.sim, self.n)
+
+    def table(self, names=None):
+        """``sequence.linkage_table``: one record per merge - rank, a, b, sim, clusters left"""
+        from . import sequence as S
+        return S.linkage_table(self.a, self.b, self.sim, self.n_valid, names)
+
+    @classmethod
+    def build(cls, arrays, metric, rounds=0):
+        """from the (a, b, sim, valid) of ``sequence.single_linkage_tree`` or the library, already trimmed"""
+        a, b, sim, valid = arrays
+        return cls(a=a, b=b, sim=sim, valid=valid, n=len(valid), n_valid=int(np.count_nonzero(valid)), rounds=int(rounds), metric=str(metric))
+
+
 class NNEngine:
     def __init__(self, device: int = 0, weights: dict = None, chunk: int = None):
         self.lib = _lib.load()
@@ -775,6 +823,45 @@ class NNEngine:
         ms = np.zeros(n.value, np.float64)
         if n.value:
             check(self.lib.gnn_debug_representative_round_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
+        return ms
+
+    # -- single-linkage tree -------------------------------------------------------------
+    def _linkage(self, fn, rows_ptr, n, metric) -> LinkageResult:
+        if isinstance(metric, str) and metric not in _lib.KNN_METRICS:
+            raise ValueError(f"metric {metric!r}: expected one of {tuple(_lib.KNN_METRICS)}")
+        cap = max(int(n) - 1, 0)
+        a, b, sim = np.empty(cap, np.int64), np.empty(cap, np.int64), np.empty(cap, np.float32)
+        valid = np.zeros(max(int(n), 0), np.uint8)
+        n_edges, rounds = C.c_int64(0), C.c_int64(0)
+        check(fn(self.ctx, rows_ptr, int(n), self._knn_metric(metric), a.ctypes.data, b.ctypes.data, sim.ctypes.data, valid.ctypes.data,
+                 C.addressof(n_edges), C.addressof(rounds)))
+        m = n_edges.value
+        name = metric if isinstance(metric, str) else {v: k for k, v in _lib.KNN_METRICS.items()}[int(metric)]
+        return LinkageResult.build((a[:m].copy(), b[:m].copy(), sim[:m].copy(), valid), name, rounds.value)
+
+    def linkage(self, rows, metric="cosine") -> LinkageResult:
+        """The single-linkage tree among encoder embeddings (``gnn_linkage``; the definition is ``sequence.single_linkage_tree``):
+        the maximum-similarity spanning tree over the valid rows of ``rows`` (n, 512), edges ordered by (similarity descending, smaller
+        row, larger row) - Boruvka rounds over the upper triangle on the matrix pipe, exact.  It answers :meth:`cluster` at every
+        threshold: ``result.cut(t)`` is ``cluster(rows, t).label`` and ``result.cluster_counts`` the number of clusters, without
+        another pass.  The similarity of the pair i < j is the float32 :meth:`neighbours` returns for query i and base row j.
+        :meth:`set_neighbour_split` sets the range of this search too; no result depends on it."""
+        r = _sequence.neighbour_rows(rows, "rows")
+        return self._linkage(self.lib.gnn_linkage, r.ctypes.data, len(r), metric)
+
+    def linkage_dev(self, rows_ptr: int, n: int, metric="cosine") -> LinkageResult:
+        """``gnn_linkage_dev``: the rows (n x 512 f32) on the device, the result on the host; the engine's stream is synchronised once
+        per round and the call returns with the result."""
+        return self._linkage(self.lib.gnn_linkage_dev, rows_ptr, n, metric)
+
+    def linkage_round_ms(self):
+        """measurement only (``gnn_debug_linkage_round_ms``): with profiling enabled, the HIP-event milliseconds of every round of the
+        last ``linkage`` / ``linkage_dev`` call, a last round that added no edge included"""
+        n = C.c_int64(0)
+        check(self.lib.gnn_debug_linkage_round_ms(self.ctx, None, 0, C.addressof(n)))
+        ms = np.zeros(n.value, np.float64)
+        if n.value:
+            check(self.lib.gnn_debug_linkage_round_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
         return ms
 
     # -- occlusion maps ------------------------------------------------------------------

@@ -98,6 +98,11 @@ class Outputs:
         self.nn_representatives_tsv_output = d / f"{p}_nn_representatives.tsv"
         self.provirus_nn_representatives_output = d / f"{p}_provirus_nn_representatives.npz"
         self.provirus_nn_representatives_tsv_output = d / f"{p}_provirus_nn_representatives.tsv"
+        # written only when GENOMAD_AMD_LINKAGE=1 (the single-linkage tree among the per-contig embeddings; no counterpart in the reference)
+        self.nn_linkage_output = d / f"{p}_nn_linkage.npz"
+        self.nn_linkage_tsv_output = d / f"{p}_nn_linkage.tsv"
+        self.provirus_nn_linkage_output = d / f"{p}_provirus_nn_linkage.npz"
+        self.provirus_nn_linkage_tsv_output = d / f"{p}_provirus_nn_linkage.tsv"
         f = o / f"{p}_find_proviruses"
         self.find_proviruses_execution_info = f / f"{p}_find_proviruses.json"
         self.find_proviruses_output = f / f"{p}_provirus.tsv"
@@ -661,6 +666,38 @@ def write_representatives_tsv(path, names, res):
                 fout.write(f"{name}\t{names[res.rep[i]]}\t{res.sim[i]:.6f}\t{res.size[i]}\tFalse\n")
 
 
+def linkage_requested() -> bool:
+    """GENOMAD_AMD_LINKAGE=1: main() also writes the single-linkage tree of the contigs under the cosine similarity of the per-contig
+    encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1 - the merges that answer GENOMAD_AMD_CLUSTERS at every threshold at once
+    (<prefix>_nn_linkage.npz and .tsv); unset, empty or 0: nothing changes.  Any other value is an error."""
+    v = os.environ.get("GENOMAD_AMD_LINKAGE", "").strip()
+    if v in ("", "0"):
+        return False
+    if v != "1":
+        raise ValueError(f"GENOMAD_AMD_LINKAGE={v!r}: expected 1 (write the single-linkage tree of the contigs), 0 or nothing")
+    return True
+
+
+LINKAGE_TSV_HEADER = "rank\tcontig_a\tcontig_b\tsimilarity\tclusters_left\n"
+
+
+def write_linkage_tsv(path, names, res):
+    """One line per merge of a LinkageResult, best first: its rank (from 1), the names of the two contigs whose edge joins two
+    clusters, the edge's similarity and the clusters left among the contigs with a valid embedding once it is made."""
+    with open(path, "w") as fout:
+        fout.write(LINKAGE_TSV_HEADER)
+        for m in res.table(names):
+            fout.write(f"{m['rank']}\t{m['a']}\t{m['b']}\t{m['sim']:.6f}\t{m['clusters_left']}\n")
+
+
+def write_linkage(npz_path, tsv_path, names_key, names, res, strand="forward"):
+    """Both linkage files of a stage: the arrays of a LinkageResult with the contig names, and the table of its merges."""
+    np.savez_compressed(npz_path, **{names_key: names, "metric": np.array(res.metric), "a": res.a, "b": res.b, "sim": res.sim,
+                                     "valid": res.valid, "rounds": np.int64(res.rounds),
+                                     **({"strand": np.array(strand)} if strand != "forward" else {})})
+    write_linkage_tsv(tsv_path, names, res)
+
+
 REGION_TSV_HEADER = ("seq_name\tstart\tend\tclass\tn_bins\tevidence_bins\t"
                      + "\t".join("mean_" + c[:-len("_score")] for c in TSV_HEADER.split()[1:]) + "\tmargin\n")
 
@@ -854,6 +891,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     neighbours_k = neighbours_requested()
     clusters_threshold = clusters_requested()
     representatives_threshold = representatives_requested()
+    linkage = linkage_requested()
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -899,6 +937,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     if representatives_threshold is not None and not embeddings:
         console.error("GENOMAD_AMD_REPRESENTATIVES needs GENOMAD_AMD_EMBEDDINGS=1: representatives are chosen among the per-contig encoder "
                       "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_REPRESENTATIVES.")
+        sys.exit(1)
+    if linkage and not embeddings:
+        console.error("GENOMAD_AMD_LINKAGE needs GENOMAD_AMD_EMBEDDINGS=1: the tree is built among the per-contig encoder "
+                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_LINKAGE.")
         sys.exit(1)
 
     if strand != "forward" and not device_front_end:
@@ -1050,7 +1092,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             write_tsv(tsv_path, names, predictions)                                  # :340-352 (always rewritten)
 
     def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, strand_path, occ_path, attr_path, regions_paths,
-                     nn_path, clusters_paths, representatives_paths, emb_path=None, scan_path=None, region_emb_path=None):
+                     nn_path, clusters_paths, representatives_paths, linkage_paths, emb_path=None, scan_path=None, region_emb_path=None):
         """Product path: the contig front end (NNEngine.classify_contigs) does windowing, the N rule,
         tokenising, classification and the per-contig mean on the GPU, so encoding and classification
         are one step; ``<prefix>_seq_window_id.npz`` is still written.  With several ranks the CONTIGS are
@@ -1085,6 +1127,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         (NNEngine.representatives, cosine) on the same gathered embeddings, the contig's number of kept windows (the count of its
         entries in the gathered window ids: no further collective) as its weight, ties in FASTA order.  The files follow the
         clusters files' rule.
+        ``linkage_paths`` (npz, tsv; GENOMAD_AMD_LINKAGE=1, which needs the embeddings): rank 0 builds the single-linkage tree
+        (NNEngine.linkage, cosine) of the same gathered embeddings and writes both files.  They are there iff they were asked for,
+        in the strand mode asked for; otherwise the stage runs again.
         ``region_emb_path`` (GENOMAD_AMD_REGION_EMBEDDINGS=1, which needs the regions): right after a piece's scan, while its
         sequence is in memory, the piece's own track is segmented (regions are per contig and exact integers: they are the ones
         rank 0 calls on the gathered track, which rank 0 checks) and NNEngine.embed_intervals folds the scan windows' encoder
@@ -1094,6 +1139,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         region_emb_file = region_emb_path if region_emb_path is not None else region_emb_default[what]
         clusters_path, clusters_tsv_path = clusters_paths
         representatives_path, representatives_tsv_path = representatives_paths
+        linkage_path, linkage_tsv_path = linkage_paths
         regions_path, regions_tsv_path = regions_paths
         regions_request = None if region_penalty is None else (scan_stride, region_penalty)
         (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and _strand_of_file(strand_path) == strand
@@ -1110,6 +1156,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                  and _clusters_of_file(representatives_path) == representatives_threshold
                                  and (representatives_threshold is None) == (not representatives_tsv_path.exists())
                                  and (representatives_threshold is None or _npz_strand(representatives_path) == strand)
+                                 and linkage == linkage_path.exists() == linkage_tsv_path.exists()
+                                 and (not linkage or _npz_strand(linkage_path) == strand)
                                  and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
                                  and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
                                                             and _npz_strand(scan_path) == strand)))   # :284-292
@@ -1328,6 +1376,16 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     for p in (representatives_path, representatives_tsv_path):
                         if p.exists():
                             p.unlink()
+                if linkage:
+                    res = eng.linkage(embeddings_all, NEIGHBOUR_METRIC)
+                    write_linkage(linkage_path, linkage_tsv_path, names_key, names, res, strand)
+                    console.log(f"Single-linkage tree of the {what}s ({NEIGHBOUR_METRIC} similarity of the encoder embeddings: {res.n_edges} "
+                                f"merges among {res.n_valid} {what}s in {res.rounds} rounds) written to {linkage_path.name} and "
+                                f"{linkage_tsv_path.name}.")
+                else:                               # likewise, both files
+                    for p in (linkage_path, linkage_tsv_path):
+                        if p.exists():
+                            p.unlink()
         if cleanup and rank0 and enc_dir.is_dir():
             console.log(f"Deleting encoded {what} data.")
             shutil.rmtree(enc_dir)
@@ -1339,9 +1397,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
     scan_kw = (lambda path: {"scan_path": path}) if scan_stride is not None else (lambda path: {})
     region_emb_kw = (lambda path: {"region_emb_path": path}) if region_embeddings else (lambda path: {})
-    strand_kw = ((lambda path, occ, attr, reg, nn, cl, rp: {"strand_path": path, "occ_path": occ, "attr_path": attr, "regions_paths": reg,
-                                                            "nn_path": nn, "clusters_paths": cl, "representatives_paths": rp})
-                 if device_front_end else (lambda path, occ, attr, reg, nn, cl, rp: {}))
+    strand_kw = ((lambda path, occ, attr, reg, nn, cl, rp, lk: {"strand_path": path, "occ_path": occ, "attr_path": attr, "regions_paths": reg,
+                                                                "nn_path": nn, "clusters_paths": cl, "representatives_paths": rp,
+                                                                "linkage_paths": lk})
+                 if device_front_end else (lambda path, occ, attr, reg, nn, cl, rp, lk: {}))
     try:
         run(input_path, outputs.encoded_sequences_dir, outputs.seq_window_id_output,
             outputs.nn_classification_npz_output, outputs.nn_classification_output,
@@ -1349,7 +1408,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                                            (outputs.nn_regions_output, outputs.nn_regions_tsv_output),
                                                            outputs.nn_neighbours_output,
                                                            (outputs.nn_clusters_output, outputs.nn_clusters_tsv_output),
-                                                           (outputs.nn_representatives_output, outputs.nn_representatives_tsv_output)),
+                                                           (outputs.nn_representatives_output, outputs.nn_representatives_tsv_output),
+                                                           (outputs.nn_linkage_output, outputs.nn_linkage_tsv_output)),
             **emb_kw(outputs.nn_embeddings_output),
             **scan_kw(outputs.nn_scan_output), **region_emb_kw(outputs.nn_region_embeddings_output))
         if classify_proviruses:                                                      # :248-281, :355-425
@@ -1361,7 +1421,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                                                            (outputs.provirus_nn_clusters_output,
                                                                             outputs.provirus_nn_clusters_tsv_output),
                                                                            (outputs.provirus_nn_representatives_output,
-                                                                            outputs.provirus_nn_representatives_tsv_output)),
+                                                                            outputs.provirus_nn_representatives_tsv_output),
+                                                                           (outputs.provirus_nn_linkage_output,
+                                                                            outputs.provirus_nn_linkage_tsv_output)),
                 **emb_kw(outputs.provirus_nn_embeddings_output), **scan_kw(outputs.provirus_nn_scan_output),
                 **region_emb_kw(outputs.provirus_nn_region_embeddings_output))
     finally:

@@ -958,6 +958,134 @@ def representative_table(result, names=None):
     return out
 
 
+def single_linkage_tree(rows, metric="cosine"):
+    """The single-linkage tree among encoder embeddings, spelled out (the definition ``gnn_linkage`` computes on the device; float64
+    throughout, readable, not fast, n x n): the maximum-similarity spanning tree of the complete graph over the valid rows - the
+    dendrogram that answers :func:`threshold_clusters` at every threshold at once.  ``rows`` (n, 512) float32; validity and
+    ``metric`` as in :func:`nearest_neighbours`.  The value of the pair {i, j} is taken once, for i < j; -0 counts as +0 and a pair
+    whose value is NaN is no edge (the result is then a forest).  An edge is better when its value is larger, ties go to the smaller
+    lo = min(i, j), then to the smaller hi = max(i, j); Kruskal walks the pairs in that order and takes an edge iff it joins two
+    different components.  Returns (a, b, sim, valid): the tree's edges in that order, best first - ``a`` int64 (lo), ``b`` int64
+    (hi), ``sim`` float32 (the float64 value, rounded) - and ``valid`` uint8 (n,)."""
+    if metric not in NEIGHBOUR_METRICS:
+        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    r32 = neighbour_rows(rows, "rows")
+    n = len(r32)
+    ok = np.isfinite(r32).all(axis=1)
+    r = np.where(ok[:, None], r32, 0).astype(np.float64)
+    if metric == "cosine":
+        norm = np.sqrt((r * r).sum(axis=1))
+        ok &= norm > 0
+        r = r / np.where(ok, norm, 1.0)[:, None]
+    # one pair at a time and the same sum either way round, as in greedy_representatives: a tie is a tie; read for i < j only
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = np.stack([(r * r[i]).sum(axis=1) for i in range(n)]) if n else np.zeros((0, 0))
+    lo, hi = np.triu_indices(n, 1)
+    keep = ok[lo] & ok[hi] & ~np.isnan(s[lo, hi])
+    lo, hi = lo[keep], hi[keep]
+    v = s[lo, hi] + 0.0                                  # -0 + 0 = +0
+    order = np.lexsort((hi, lo, -v))                     # value descending, then lo, then hi ascending
+    root = np.arange(n)
+
+    def find(x):
+        while root[x] != x:
+            root[x] = root[root[x]]
+            x = root[x]
+        return x
+
+    a, b, sim = [], [], []
+    want = max(int(ok.sum()) - 1, 0)
+    for e in order:
+        if len(a) == want:                               # the tree spans the valid rows: nothing later joins anything
+            break
+        x, y = find(lo[e]), find(hi[e])
+        if x != y:
+            root[max(x, y)] = min(x, y)
+            a.append(lo[e])
+            b.append(hi[e])
+            sim.append(v[e])
+    return np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64), np.asarray(sim, dtype=np.float32), ok.astype(np.uint8)
+
+
+def _linkage_arrays(a, b, sim):
+    a, b = np.asarray(a, dtype=np.int64).ravel(), np.asarray(b, dtype=np.int64).ravel()
+    sim = np.asarray(sim, dtype=np.float32).ravel()
+    if not len(a) == len(b) == len(sim):
+        raise ValueError(f"a, b and sim have {len(a)}, {len(b)} and {len(sim)} entries: one of each per edge is required")
+    return a, b, sim
+
+
+def linkage_cut(a, b, sim, valid, threshold) -> np.ndarray:
+    """The clusters of a :func:`single_linkage_tree` at ``threshold``: the rows joined by its edges with sim >= the float32 the
+    threshold rounds to (a tie is an edge).  Returns int64 ``label`` (n,): the smallest index of the row's cluster, -1 for an
+    invalid row - ``threshold_clusters(rows, threshold)[0]`` where the tree is that of the same values."""
+    a, b, sim = _linkage_arrays(a, b, sim)
+    valid = np.asarray(valid).astype(bool).ravel()
+    thr = cluster_threshold(threshold)
+    root = np.arange(len(valid))
+
+    def find(x):
+        while root[x] != x:
+            root[x] = root[root[x]]
+            x = root[x]
+        return x
+
+    for e in np.flatnonzero(sim >= thr):
+        x, y = find(a[e]), find(b[e])
+        root[max(x, y)] = min(x, y)                      # towards the smaller index: a root is its cluster's smallest row
+    label = np.array([find(i) for i in range(len(valid))], dtype=np.int64).reshape(len(valid))
+    label[~valid] = -1
+    return label
+
+
+def linkage_cluster_counts(sim, n_valid, thresholds) -> np.ndarray:
+    """Clusters (singletons included) that a cut of the tree leaves at each of ``thresholds``: n_valid - #(sim >= t), int64."""
+    sim = np.asarray(sim, dtype=np.float32).ravel()
+    return np.array([int(n_valid) - int((sim >= cluster_threshold(t)).sum()) for t in np.atleast_1d(thresholds)], dtype=np.int64)
+
+
+def linkage_matrix(a, b, sim, n) -> np.ndarray:
+    """The tree as a linkage matrix in the convention of SciPy's ``scipy.cluster.hierarchy.linkage`` (float64, (n - 1, 4)): per
+    merge, best first, the ids of the two clusters merged (the smaller first), the distance 1 - sim and the new cluster's size; a
+    row is cluster i, the cluster of step k is n + k.  For cosine similarities, all rows valid and a spanning tree: anything else -
+    another number of edges than n - 1, an edge inside one cluster, an index outside [0, n) - is a ValueError."""
+    a, b, sim = _linkage_arrays(a, b, sim)
+    n = int(n)
+    if n < 1 or len(a) != n - 1:
+        raise ValueError(f"{len(a)} edges among {n} rows: a linkage matrix needs a spanning tree of n - 1 edges over n >= 1 valid rows")
+    if len(a) and (min(a.min(), b.min()) < 0 or max(a.max(), b.max()) >= n):
+        raise ValueError(f"an edge names a row outside [0, {n})")
+    if np.isnan(sim).any():
+        raise ValueError("an edge's similarity is not a number")
+    root = np.arange(n)
+    cluster, size = np.arange(n), np.ones(n, dtype=np.int64)         # at a root: its cluster's id and size
+
+    def find(x):
+        while root[x] != x:
+            root[x] = root[root[x]]
+            x = root[x]
+        return x
+
+    z = np.zeros((n - 1, 4), dtype=np.float64)
+    for k in range(n - 1):
+        x, y = find(a[k]), find(b[k])
+        if x == y:
+            raise ValueError(f"edge {k} ({a[k]}, {b[k]}) joins two rows of one cluster: not a tree")
+        z[k] = (min(cluster[x], cluster[y]), max(cluster[x], cluster[y]), 1.0 - float(sim[k]), size[x] + size[y])
+        root[y] = x
+        cluster[x], size[x] = n + k, size[x] + size[y]
+    return z
+
+
+def linkage_table(a, b, sim, n_valid, names=None):
+    """One record per merge of a :func:`single_linkage_tree`, best first: ``rank`` (from 1), ``a``, ``b`` (the names where ``names``
+    is given), ``sim`` and ``clusters_left``, the clusters among the valid rows once the merge is made: n_valid - rank."""
+    a, b, sim = _linkage_arrays(a, b, sim)
+    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    return [{"rank": k + 1, "a": name(a[k]), "b": name(b[k]), "sim": float(sim[k]), "clusters_left": int(n_valid) - k - 1}
+            for k in range(len(a))]
+
+
 def prefix_of(input_path: Path) -> str:
     """nn_classification.py:106-108: stem, minus one more extension if the file is compressed."""
     prefix = Path(input_path).stem

@@ -654,6 +654,44 @@ int gnn_representatives_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, floa
  * last gnn_representatives* call; *n_out = the rounds recorded, at most `capacity` of them are written. */
 int gnn_debug_representative_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
 
+/* ---- single-linkage tree among encoder embeddings: Boruvka on the device ------------------------------------
+ * "Which rows belong together AT EVERY THRESHOLD": the single-linkage dendrogram = the maximum-similarity spanning tree of the complete
+ * graph over the valid rows.  Cutting it at t - the union of its edges with sim >= t - gives exactly gnn_cluster's label at t, and the
+ * clusters at t number n_valid - #(edges >= t).  Rows, validity and metric are those of gnn_cluster; no forward pass runs and no other
+ * entry point's result changes.
+ *   value     the weight of the pair {i, j}, i < j, is the f32 that gnn_neighbours returns for query i and base row j (the same
+ *             fragments, k-steps, order and scale as gnn_cluster); (j, i) is never computed.  -0 counts as +0.  A pair whose value is
+ *             not a number is no edge: the result is then a forest.
+ *   order     an edge is better when its value is larger; ties go to the smaller lo = min(i, j), then to the smaller hi = max(i, j).
+ *   tree      Kruskal over the valid pairs in that order: an edge is taken iff it joins two different components.  The order is
+ *             strict, so the tree is unique.
+ *   outputs   the tree's edges in that order, best first: a (int64, lo), b (int64, hi), sim (f32), each of capacity max(n - 1, 0),
+ *             entries past *n_edges_host are -1 / -1 / NaN; *n_edges_host = n_valid - 1 unless NaN pairs split the forest (0 where no
+ *             row is valid); valid (uint8 [n]): 1 for a valid row; *rounds_host: the passes of the device that added an edge.
+ *   rounds    Boruvka: in a round every component picks its best outgoing edge in the order above - one pass over the upper triangle
+ *             that keeps a 64-bit maximum per row, two launches that reduce them per component - and the picked edges join.  The
+ *             components that are not final at least halve per round: at most ceil(log2 n_valid) rounds add an edge, one more finds
+ *             none (it is not run where the tree already spans all n rows).  A 33rd round returns GNN_ERR_STATE with a message
+ *             naming the round: n < 2^31 halves at most 31 times.  The host sorts the <= n - 1 records at the end.
+ *   ranges    0 <= n < 2^31, a metric in [0, 1]; GNN_ERR_ARG with the value and the range in the message - checked before the ctx is
+ *             looked at, nothing is written.  n == 0 is GNN_OK with zero edges and zero rounds.
+ *   exact     every key is an integer maximum or minimum of values that depend on the pair alone, and the records are sorted:
+ *             bit-identical, rounds included, for every split of the base (gnn_debug_set_neighbour_split sets the range for this
+ *             search too).
+ * What it is not: not approximate; not average or complete linkage (single linkage chains, see gnn_cluster); no width other than
+ * GNN_EMBED_DIM; not multi-GPU.
+ * Device memory, persistent in the ctx and grow-only: the 2 KB of fragments + 1 B per row of the neighbour search (shared with it;
+ * gnn_linkage: + the row's 2 KB of f32) and 40 B per row of parent, component, the two keys, hi and the edge records.  Nothing is n x n.
+ * gnn_linkage: host pointers, synchronous.  gnn_linkage_dev: the rows on the device, every output on the host; it enqueues on the ctx
+ * stream, SYNCHRONISES IT ONCE PER ROUND - the host reads 8 bytes, the number of edges - and returns with the results written. */
+int gnn_linkage(gnn_ctx* ctx, const float* rows_host, int64_t n, int metric, int64_t* a_host, int64_t* b_host, float* sim_host,
+                uint8_t* valid_host, int64_t* n_edges_host, int64_t* rounds_host);
+int gnn_linkage_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, int metric, int64_t* a_host, int64_t* b_host, float* sim_host,
+                    uint8_t* valid_host, int64_t* n_edges_host, int64_t* rounds_host);
+/* measurement only: with gnn_profile_enable on, the HIP-event milliseconds of every round (its six launches; the last one may have
+ * added no edge) of the ctx's last gnn_linkage* call; *n_out = the rounds recorded, at most `capacity` of them are written. */
+int gnn_debug_linkage_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
+
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
  * in-memory text buffer (already decompressed, newlines normalised to '\n').
@@ -738,7 +776,8 @@ int gnn_synth_windows_dev(gnn_ctx* ctx, uint64_t seed, int64_t first, int64_t n_
 #define GNN_K_REGIONS 6      /* region calls: every kernel of gnn_region_states_dev / gnn_call_regions; interval embeddings: the fold and
                               * finish kernels of gnn_embed_intervals / gnn_interval_fold_dev / gnn_interval_finish_dev */
 #define GNN_K_NEIGHBOURS 7   /* nearest neighbours: the prepare, tile and merge kernels of gnn_neighbours / gnn_neighbours_dev; clusters:
-                              * every kernel of gnn_cluster / gnn_cluster_dev; representatives: every kernel of gnn_representatives* */
+                              * every kernel of gnn_cluster / gnn_cluster_dev; representatives: every kernel of gnn_representatives*;
+                              * single-linkage tree: every kernel of gnn_linkage / gnn_linkage_dev */
 #define GNN_K_COUNT 8
 int gnn_profile_enable(gnn_ctx* ctx, int on);
 int gnn_profile_reset(gnn_ctx* ctx);
