@@ -662,7 +662,9 @@ int gnn_debug_representative_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capa
  *   value     the weight of the pair {i, j}, i < j, is the f32 that gnn_neighbours returns for query i and base row j (the same
  *             fragments, k-steps, order and scale as gnn_cluster); (j, i) is never computed.  -0 counts as +0.  A pair whose value is
  *             not a number is no edge: the result is then a forest.
+ *             Under GNN_KNN_DOT a finite row with an element beyond the f16 range is a valid, isolated row of that forest.
  *   order     an edge is better when its value is larger; ties go to the smaller lo = min(i, j), then to the smaller hi = max(i, j).
+ *             The order holds for negative values as for positive ones: a negative edge ranks below every zero and positive one.
  *   tree      Kruskal over the valid pairs in that order: an edge is taken iff it joins two different components.  The order is
  *             strict, so the tree is unique.
  *   outputs   the tree's edges in that order, best first: a (int64, lo), b (int64, hi), sim (f32), each of capacity max(n - 1, 0),

@@ -1,8 +1,33 @@
 """For the single-linkage tests: a brute-force Kruskal over a given value matrix and a naive agglomeration, neither sharing code with
-sequence.single_linkage_tree; the device's own pair values for any n; and the fixtures of the cluster tests that the linkage tests reuse."""
+sequence.single_linkage_tree; the device's own pair values for any n; what the device tests compare a result by (bits, same,
+check_shape); and the fixtures of the cluster tests that the linkage tests reuse."""
+import math
+
 import numpy as np
 
 from tests.neighbours_data import rows
+
+
+def bits(x):
+    return np.asarray(x, np.float32).view(np.uint32)
+
+
+def same(got, want):
+    """two LinkageResults, or a result and an (a, b, sim) of the same f32: indices, bits, flags and rounds"""
+    if isinstance(want, tuple):
+        return np.array_equal(got.a, want[0]) and np.array_equal(got.b, want[1]) and np.array_equal(bits(got.sim), bits(want[2]))
+    return (np.array_equal(got.a, want.a) and np.array_equal(got.b, want.b) and np.array_equal(bits(got.sim), bits(want.sim))
+            and np.array_equal(got.valid, want.valid) and got.rounds == want.rounds)
+
+
+def check_shape(res, n):
+    assert res.a.dtype == res.b.dtype == np.int64 and res.sim.dtype == np.float32 and res.valid.dtype == np.uint8
+    assert res.n == n and res.valid.shape == (n,) and res.n_valid == int(res.valid.sum())
+    assert res.a.shape == res.b.shape == res.sim.shape == (res.n_edges,)
+    if res.n_valid >= 2:
+        assert 1 <= res.rounds <= math.ceil(math.log2(res.n_valid)), (res.rounds, res.n_valid)
+    else:
+        assert res.rounds == 0 and res.n_edges == 0
 
 
 def kruskal(values, valid=None):

@@ -4,40 +4,17 @@
 weights against fp64, independence of how the base is split over workgroups, many joins at once, the bound on the rounds, the edges of
 the interface, and embed_contigs -> linkage end to end.  Second-scale shapes, those of tests/test_clusters_gpu.py: 333 rows are six
 64-row tiles and two 256-column steps, off every boundary."""
-import math
-
 import numpy as np
 import pytest
 
 from genomad_amd import sequence, synthetic
 from genomad_amd._lib import GnnError
 from tests.clusters_data import THRESHOLDS, planted
-from tests.linkage_data import device_values, integer_rows, integer_rows_with_two_invalid, interface_rows, kruskal, many_copies
+from tests.linkage_data import (bits, check_shape, device_values, integer_rows, integer_rows_with_two_invalid, interface_rows, kruskal,
+                                many_copies, same)
 from tests.neighbours_data import rows
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(x):
-    return np.asarray(x, np.float32).view(np.uint32)
-
-
-def same(got, want):
-    """two LinkageResults, or a result and an (a, b, sim) of the same f32: indices, bits, flags and rounds"""
-    if isinstance(want, tuple):
-        return np.array_equal(got.a, want[0]) and np.array_equal(got.b, want[1]) and np.array_equal(bits(got.sim), bits(want[2]))
-    return (np.array_equal(got.a, want.a) and np.array_equal(got.b, want.b) and np.array_equal(bits(got.sim), bits(want.sim))
-            and np.array_equal(got.valid, want.valid) and got.rounds == want.rounds)
-
-
-def check_shape(res, n):
-    assert res.a.dtype == res.b.dtype == np.int64 and res.sim.dtype == np.float32 and res.valid.dtype == np.uint8
-    assert res.n == n and res.valid.shape == (n,) and res.n_valid == int(res.valid.sum())
-    assert res.a.shape == res.b.shape == res.sim.shape == (res.n_edges,)
-    if res.n_valid >= 2:
-        assert 1 <= res.rounds <= math.ceil(math.log2(res.n_valid)), (res.rounds, res.n_valid)
-    else:
-        assert res.rounds == 0 and res.n_edges == 0
 
 
 @pytest.fixture(scope="module")
