@@ -1,9 +1,9 @@
 // Clusters among encoder embeddings (include/genomad_nn.h, "clusters"): the connected components of the graph
 // with an edge {i, j} iff both rows are valid and sim(i, j) >= threshold - single linkage at the threshold, exact, five kernels.
-//   prepare    nn_prepare of gnn_nn_frag.h, as it is: the neighbour search's fragments and flags, in its buffers.
+//   prepare    nn_prepare (gnn_neighbours.hip), as it is: the neighbour search's fragments and flags, in its buffers.
 //   init       parent[i] = i, degree = size = key = 0.
-//   tile       nn_tile_kernel's skeleton - 64 rows' fragments in LDS, the base streamed in steps of 256 columns, the same three
-//              products per k-step in the same order, the same scale - over the UPPER TRIANGLE only.  The value of the pair {i, j},
+//   tile       the tile parts of gnn_nn_frag.h - 64 rows' fragments in LDS, the base streamed in steps of 256 columns, NN_PRODUCTS'
+//              three products per k-step in their order, the same scale - over the UPPER TRIANGLE only.  The value of the pair {i, j},
 //              i < j, is the f32 that gnn_neighbours returns for query i and base row j; (j, i) is never computed: hi.lo then lo.hi is
 //              not symmetric in the last bit.  Behind every step, for every value with row < col, both rows valid and s >= threshold
 //              (false for a NaN): the edge is counted at both ends and the two rows are joined.  No lists, no barrier per step.
@@ -50,54 +50,34 @@ __global__ __launch_bounds__(256) void cl_tile_kernel(ClusterArgs a) {
     __shared__ int ldeg[QT];               // edges of this workgroup's columns at the tile's rows: flushed once
     __shared__ uint8_t lok[QT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t r0 = (int64_t)blockIdx.x * QT;
-    const int64_t b0 = (int64_t)blockIdx.y * a.split_rows, b1 = min(a.n, b0 + a.split_rows);
-    if (b1 <= r0 + 1) return;              // no column of the range lies right of the tile's first row (the whole workgroup leaves)
-    {
-        const uint4* src = a.frag + (int64_t)blockIdx.x * 2 * BLK_U4;
-        for (int i = tid; i < 2 * BLK_U4; i += 256) qs[i] = src[i];
-        if (tid < QT) {
-            ldeg[tid] = 0;
-            lok[tid] = r0 + tid < a.n && a.valid[r0 + tid];
-        }
+    TileRange t;
+    if (!nn_tile_range(t, a.split_rows, a.n, true)) return;
+    const int64_t r0 = t.r0;
+    nn_copy_tile(qs, a.frag, tid);
+    if (tid < QT) {
+        ldeg[tid] = 0;
+        lok[tid] = r0 + tid < a.n && a.valid[r0 + tid];
     }
     __syncthreads();
-    const int64_t last_blk = (b1 - 1) / 32;
-    // the first step begins at the 32-column block that holds the tile's first row (r0 and b0 are multiples of 32); a pair's value
-    // depends on its two rows only, so where a step begins changes nothing.  Ends: c0 grows by STEP towards b1.
-    for (int64_t c0 = max(b0, r0); c0 < b1; c0 += STEP) {
+    const int64_t last_blk = t.last_blk();
+    // Ends: c0 grows by STEP towards b1.
+    for (int64_t c0 = t.c0; c0 < t.b1; c0 += STEP) {
         const uint4* bp[2];
         int cg[2];                         // the lane's column, -1: no edge can end there
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
-            const int64_t blk = c0 / 32 + wave * 2 + nb;
-            bp[nb] = a.frag + min(blk, last_blk) * BLK_U4 + lane;
-            const int64_t col = blk * 32 + (lane & 31);
-            cg[nb] = col < b1 && a.valid[col] ? (int)col : -1;
+            const int64_t col = nn_step_column(a.frag, c0, wave, lane, nb, last_blk, bp[nb]);
+            cg[nb] = col < t.b1 && a.valid[col] ? (int)col : -1;
         }
         f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        BFrag f0, f1;
-        nn_load_b(f0, bp, 0);
-#pragma unroll 1
-        for (int ks = 0; ks < NKS; ks += 2) {              // k-step ks + 1 is fetched under the MFMAs of ks
-            nn_load_b(f1, bp, ks + 1);
-            nn_mfma(qs, ks, lane, f0, acc);
-            nn_load_b(f0, bp, min(ks + 2, NKS - 1));
-            nn_mfma(qs, ks + 1, lane, f1, acc);
-        }
-        // ---- edges: C/D layout column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5); bit (mb * 2 + nb) * 16 + reg
+        NN_PRODUCTS(qs, bp, lane, acc);
+        // ---- edges: bit (mb * 2 + nb) * 16 + reg
         unsigned long long edge = 0;
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int row = nn_acc_row(mb, r, lane >> 5);
                 const int rg = (int)r0 + row;
                 const bool rok = lok[row];
 #pragma unroll
@@ -117,7 +97,7 @@ __global__ __launch_bounds__(256) void cl_tile_kernel(ClusterArgs a) {
                 const unsigned long long e0 = __ballot((edge >> (mb * 32 + r)) & 1), e1 = __ballot((edge >> (mb * 32 + 16 + r)) & 1);
                 const int half = lane >> 5;
                 const int c = __popc((unsigned)(e0 >> (32 * half))) + __popc((unsigned)(e1 >> (32 * half)));
-                if ((lane & 31) == 0 && c) atomicAdd(&ldeg[mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half], c);
+                if ((lane & 31) == 0 && c) atomicAdd(&ldeg[nn_acc_row(mb, r, half)], c);
             }
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
@@ -131,7 +111,7 @@ __global__ __launch_bounds__(256) void cl_tile_kernel(ClusterArgs a) {
             const int b = __ffsll((long long)edge) - 1;
             edge &= edge - 1;
             const int r = b & 15, nb = (b >> 4) & 1, mb = b >> 5;
-            const int rg = (int)r0 + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int rg = (int)r0 + nn_acc_row(mb, r, lane >> 5);
             const int t = cl_join(a.parent, rg, nb ? top[1] : top[0]);
             if (nb) top[1] = t; else top[0] = t;
         }
@@ -140,7 +120,7 @@ __global__ __launch_bounds__(256) void cl_tile_kernel(ClusterArgs a) {
     if (tid < QT && ldeg[tid]) atomicAdd(a.degree + r0 + tid, ldeg[tid]);       // ldeg > 0 only at a valid row < n
 }
 
-// A launch of its own behind the tile kernel: plain loads see every link.  Ends: a step of the climb goes to p < r, and r >= 0.
+// A launch of its own behind the tile kernel: nn_root's plain loads see every link.
 __global__ __launch_bounds__(256) void cl_flatten_kernel(int64_t n, const uint8_t* __restrict__ valid, const int32_t* __restrict__ parent,
                                                          const int32_t* __restrict__ degree, int32_t* __restrict__ size,
                                                          unsigned long long* __restrict__ key, int64_t* __restrict__ label) {
@@ -150,16 +130,11 @@ __global__ __launch_bounds__(256) void cl_flatten_kernel(int64_t n, const uint8_
         label[i] = -1;
         return;
     }
-    int r = (int)i;
-    for (;;) {
-        const int p = parent[r];
-        if (p == r) break;
-        r = p;
-    }
+    const int r = nn_root(parent, (int)i);
     label[i] = r;
     atomicAdd(size + r, 1);
     // the largest degree wins, among equals the smallest row
-    atomicMax(key + r, ((unsigned long long)(unsigned)degree[i] << 32) | (0xffffffffull - (unsigned long long)i));
+    atomicMax(key + r, nn_key((unsigned)degree[i], (unsigned)i));
 }
 
 __global__ __launch_bounds__(256) void cl_summarise_kernel(int64_t n, const uint8_t* __restrict__ valid, const int32_t* __restrict__ degree,
@@ -177,7 +152,7 @@ __global__ __launch_bounds__(256) void cl_summarise_kernel(int64_t n, const uint
     const int64_t r = label[i];
     degree_out[i] = degree[i];
     size_out[i] = size[r];
-    rep_out[i] = (int64_t)(0xffffffffull - (key[r] & 0xffffffffull));
+    rep_out[i] = (int64_t)nn_key_index(key[r]);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
@@ -193,10 +168,7 @@ int check_cluster_args(const char* fn, const void* rows, int64_t n, float thresh
         set_error(f + ": threshold " + std::to_string(threshold) + " is outside (-inf, inf): a finite f32 is required");
         return GNN_ERR_ARG;
     }
-    if (metric != GNN_KNN_COSINE && metric != GNN_KNN_DOT) {
-        set_error(f + ": metric " + std::to_string(metric) + " is outside [0, 1] (GNN_KNN_COSINE, GNN_KNN_DOT)");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_metric(f, metric)) return rc;
     if (n > 0 && (!rows || !label || !degree || !size || !rep)) {
         set_error("bad argument to " + f + ": the rows and the four outputs are required");
         return GNN_ERR_ARG;
@@ -214,14 +186,10 @@ int cl_run(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int 
     if (!rc) rc = nn_reserve(ctx, c.degree, (size_t)n);
     if (!rc) rc = nn_reserve(ctx, c.size, (size_t)n);
     if (!rc) rc = nn_reserve(ctx, c.key, (size_t)n);
-    if (rc) return rc;
     const int64_t tiles = (n + QT - 1) / QT;
-    const int64_t split_rows = nn_split_rows(ctx, tiles, n);
-    const int64_t splits = (n + split_rows - 1) / split_rows;
-    if (splits > 65535) {
-        set_error("gnn_cluster: " + std::to_string(n) + " rows in ranges of " + std::to_string(split_rows) + " are more than 65535 ranges");
-        return GNN_ERR_ARG;
-    }
+    int64_t split_rows, splits;
+    if (!rc) rc = nn_tile_grid(ctx, "gnn_cluster", "rows", tiles, n, &split_rows, &splits);
+    if (rc) return rc;
     ProfScope prof(ctx, GNN_K_NEIGHBOURS);
     const dim3 per_row((unsigned)((n + 255) / 256));
     hipLaunchKernelGGL(cl_init_kernel, per_row, dim3(256), 0, ctx->stream, n, c.parent.get(), c.degree.get(), c.size.get(), c.key.get());
@@ -231,7 +199,7 @@ int cl_run(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int 
     a.valid = w.bvalid.get();
     a.n = n;
     a.split_rows = split_rows;
-    a.scale = metric == GNN_KNN_COSINE ? 1.f / 65536.f : 1.f;
+    a.scale = nn_metric_scale(metric);
     a.threshold = threshold;
     a.parent = c.parent.get();
     a.degree = c.degree.get();
@@ -266,10 +234,9 @@ extern "C" int gnn_cluster(gnn_ctx* ctx, const float* rows_host, int64_t n, floa
     if (n == 0) return GNN_OK;
     NeighbourWorkspace& w = ctx->nn;
     ClusterWorkspace& c = ctx->cl;
-    int rc = nn_reserve(ctx, w.d_base, (size_t)n * D);
-    if (!rc) rc = nn_reserve(ctx, c.d_out, (size_t)4 * n);
+    int rc = nn_reserve(ctx, c.d_out, (size_t)4 * n);         // both buffers stand before the copy is enqueued
+    if (!rc) rc = nn_upload_rows(ctx, rows_host, n);
     if (rc) return rc;
-    GNN_HIP(hipMemcpyAsync(w.d_base, rows_host, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     int64_t* out = c.d_out;
     if ((rc = cl_run(ctx, w.d_base, n, threshold, metric, out, out + n, out + 2 * n, out + 3 * n))) return rc;
     int64_t* const host[4] = {label_host, degree_host, size_host, rep_host};

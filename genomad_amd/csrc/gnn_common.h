@@ -187,6 +187,25 @@ struct NeighbourWorkspace {
     DevBuf<float> d_sim;
 };
 
+// ---- the host-side prologue that the searches over encoder embeddings share (gnn_neighbours.hip, which also holds the prepare
+// kernel; gnn_clusters.hip, gnn_representatives.hip, gnn_linkage.hip).  `fn` is the name an error message carries.
+int nn_check_metric(const std::string& fn, int metric);      // GNN_OK, or GNN_ERR_ARG for a metric outside gnn_knn_metric
+float nn_metric_scale(int metric);                           // what a tile kernel multiplies its products by: 2^-16 for cosine, 1 for dot
+// rows_dev[n][GNN_EMBED_DIM] -> fragments and flags of round_up(n, 64) rows
+int nn_prepare(gnn_ctx* ctx, const float* rows_dev, int64_t n, int metric, DevBuf<uint4>& frag, DevBuf<uint8_t>& valid);
+// The tile grid of `tiles` row tiles over nb `noun` ("rows", "base rows"): base rows per workgroup - the debug value, or what gives
+// every CU two workgroups; a multiple of 32 - and the number of such ranges, or GNN_ERR_ARG for more than 65535 of them.
+int nn_tile_grid(const gnn_ctx* ctx, const std::string& fn, const char* noun, int64_t tiles, int64_t nb, int64_t* split_rows, int64_t* splits);
+int nn_upload_rows(gnn_ctx* ctx, const float* rows_host, int64_t n);      // n rows into ctx->nn.d_base, enqueued on the ctx's stream
+// The HIP-event time of one round of a search that synchronises once per round.  a, b: the events of the round's ProfScope (NULL:
+// profiling is off); file() appends the elapsed ms, after the round's synchronise.
+struct RoundTimer {
+    hipEvent_t a = nullptr, b = nullptr;
+    void file(std::vector<float>& round_ms) const;
+};
+// the body of gnn_debug_representative_round_ms and gnn_debug_linkage_round_ms, behind their check_ctx
+int nn_round_ms_out(const char* fn, const std::vector<float>& round_ms, double* ms_out, int64_t capacity, int64_t* n_out);
+
 // ---- clusters (gnn_clusters.hip): persistent, grow-only.  The fragments and flags are NeighbourWorkspace's bfrag / bvalid (and d_base
 // for the host entry point); here 20 B per row and, for gnn_cluster alone, its 32 B of results.  Nothing is n x n.
 struct ClusterWorkspace {

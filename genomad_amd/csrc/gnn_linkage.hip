@@ -3,10 +3,10 @@
 // order (value descending, lo ascending, hi ascending) - what Kruskal takes.  Boruvka rounds; a round is six launches:
 //   reset      best = cbest = 0, chi = INT_MAX, parent = comp (the trees of the last round, compressed to depth one; comp[i] is -1
 //              for an invalid row, which stays a tree of its own that nothing joins).
-//   tile       cl_tile_kernel's skeleton - 64 rows' fragments in LDS, the base streamed in steps of 256 columns, the same three
-//              products per k-step in the same order, the same scale - over the UPPER TRIANGLE only.  Every value with row < col, both
-//              rows valid, comp[row] != comp[col] and not NaN is a candidate AT BOTH ENDS: best[x] = max of
-//              (image(s) << 32) | (2^32 - 1 - partner) over the candidates at x, 0: none.  A lane keeps a running best per accumulator
+//   tile       the tile parts of gnn_nn_frag.h - 64 rows' fragments in LDS, the base streamed in steps of 256 columns, NN_PRODUCTS'
+//              three products per k-step in their order, the same scale - over the UPPER TRIANGLE only.  Every value with row < col,
+//              both rows valid, comp[row] != comp[col] and not NaN is a candidate AT BOTH ENDS: best[x] = max of nn_key(nn_image(s),
+//              partner) = (image << 32) | (2^32 - 1 - partner) over the candidates at x, 0: none.  A lane keeps a running best per accumulator
 //              register over the workgroup's steps (the row side: one LDS max per row and wave at the end, one global max per row and
 //              workgroup) and takes one max per column and step (the column side).  A wave whose rows and columns share one component
 //              skips its k-loop.
@@ -22,7 +22,6 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstring>
 #include <numeric>
 #include <vector>
 
@@ -33,27 +32,9 @@ namespace {
 
 constexpr int64_t N_MAX = (int64_t)1 << 31;      // rows are int32 in parent[] and 32 bits of a key
 constexpr int ROUNDS_MAX = 32;                   // components at least halve per round: n < 2^31 needs at most 31
-constexpr unsigned long long LOW32 = 0xffffffffull;
-
-// the order-preserving map of an f32 that is not NaN to a u32 > 0; -0 counts as +0
-__device__ __forceinline__ unsigned lk_image(float s) {
-    unsigned u = __float_as_uint(s);
-    u = u == 0x80000000u ? 0u : u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-inline float lk_value(unsigned image) {
-    const unsigned u = (image & 0x80000000u) ? (image ^ 0x80000000u) : ~image;
-    float s;
-    memcpy(&s, &u, sizeof s);
-    return s;
-}
 
 __device__ __forceinline__ unsigned long long lk_peek(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned long long lk_shfl_xor(unsigned long long v, int mask) {
-    const unsigned lo = __shfl_xor((unsigned)v, mask), hi = __shfl_xor((unsigned)(v >> 32), mask);
-    return ((unsigned long long)hi << 32) | lo;
 }
 
 __global__ __launch_bounds__(256) void lk_init_kernel(int64_t n, const uint8_t* __restrict__ valid, int32_t* __restrict__ comp) {
@@ -81,10 +62,10 @@ struct LinkageArgs {
     unsigned long long* best;  // [n]
 };
 
-// The candidates of one step: C/D layout column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  The registers are walked
-// by ascending row and a lane's columns ascend with nb and with the steps, and `!(s <= best so far)` is false for an equal value (-0
-// equals +0) and true while the best is still NaN (none): the smallest partner among equals is kept.  An invalid column has scale =
-// NaN, so its values fail s == s like a NaN pair.  DIAG: the step overlaps the tile's own rows, and only then is row < col a test.
+// The candidates of one step.  The registers are walked by ascending row (nn_acc_row) and a lane's columns ascend with nb and with the
+// steps, and `!(s <= best so far)` is false for an equal value (-0 equals +0) and true while the best is still NaN (none): the
+// smallest partner among equals is kept.  An invalid column has scale = NaN, so its values fail s == s like a NaN pair.  DIAG: the
+// step overlaps the tile's own rows, and only then is row < col a test.
 template <bool DIAG>
 __device__ __forceinline__ void lk_candidates(const f32x16 (&acc)[2][2], const int* lcomp, int r0, int lane, const float (&scale)[2],
                                               const int (&col)[2], const int (&cc)[2], float (&bval)[2][16], int (&bcol)[2][16],
@@ -93,7 +74,7 @@ __device__ __forceinline__ void lk_candidates(const f32x16 (&acc)[2][2], const i
     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int row = nn_acc_row(mb, r, lane >> 5);
             const int rg = r0 + row;
             const int rc = lcomp[row];
 #pragma unroll
@@ -119,16 +100,13 @@ __global__ __launch_bounds__(256) void lk_tile_kernel(LinkageArgs a) {
     __shared__ unsigned long long lbest[QT];   // the rows' best partners among this workgroup's columns: flushed once
     __shared__ int lcomp[QT];                  // the row's component, -1: the row is invalid or beyond n
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t r0 = (int64_t)blockIdx.x * QT;
-    const int64_t b0 = (int64_t)blockIdx.y * a.split_rows, b1 = min(a.n, b0 + a.split_rows);
-    if (b1 <= r0 + 1) return;              // no column of the range lies right of the tile's first row (the whole workgroup leaves)
-    {
-        const uint4* src = a.frag + (int64_t)blockIdx.x * 2 * BLK_U4;
-        for (int i = tid; i < 2 * BLK_U4; i += 256) qs[i] = src[i];
-        if (tid < QT) {
-            lbest[tid] = 0;
-            lcomp[tid] = r0 + tid < a.n ? a.comp[r0 + tid] : -1;
-        }
+    TileRange t;
+    if (!nn_tile_range(t, a.split_rows, a.n, true)) return;
+    const int64_t r0 = t.r0, b1 = t.b1;
+    nn_copy_tile(qs, a.frag, tid);
+    if (tid < QT) {
+        lbest[tid] = 0;
+        lcomp[tid] = r0 + tid < a.n ? a.comp[r0 + tid] : -1;
     }
     __syncthreads();
     // the component all valid rows of the tile share; -1: they do not.  The same in every wave: a tile without a valid row leaves whole
@@ -149,7 +127,7 @@ __global__ __launch_bounds__(256) void lk_tile_kernel(LinkageArgs a) {
             bval[mb][r] = NAN;
             bcol[mb][r] = -1;
         }
-    const int64_t last_blk = (b1 - 1) / 32;
+    const int64_t last_blk = t.last_blk();
     // what a step needs of its columns, fetched one step ahead - with one wave per SIMD nothing else hides a load in front of the
     // fragment loads: the column's component (-1: no column, or an invalid one) and what best[] holds for it now.  The latter may be
     // older than another workgroup's maximum by the time it is used: then a maximum is merely not skipped.
@@ -158,23 +136,21 @@ __global__ __launch_bounds__(256) void lk_tile_kernel(LinkageArgs a) {
     auto fetch = [&](int64_t c0) {
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
-            const int64_t col = (c0 / 32 + wave * 2 + nb) * 32 + (lane & 31);
+            const int64_t col = nn_blk_col(nn_step_blk(c0, wave, nb), lane);
             ncc[nb] = col < b1 ? a.comp[col] : -1;
             npk[nb] = col < b1 ? lk_peek(a.best + col) : ~0ull;
         }
     };
-    fetch(max(b0, r0));
-    // as in cl_tile_kernel.  Ends: c0 grows by STEP towards b1.
-    for (int64_t c0 = max(b0, r0); c0 < b1; c0 += STEP) {
+    fetch(t.c0);
+    // Ends: c0 grows by STEP towards b1.
+    for (int64_t c0 = t.c0; c0 < b1; c0 += STEP) {
         const uint4* bp[2];
         int col[2], cc[2];                 // the lane's column and its component, -1: no edge can end there
         unsigned long long pk[2];
         float scale[2];
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
-            const int64_t blk = c0 / 32 + wave * 2 + nb;
-            bp[nb] = a.frag + min(blk, last_blk) * BLK_U4 + lane;
-            col[nb] = (int)(blk * 32 + (lane & 31));       // read only where cc >= 0: there it is < b1 < 2^31
+            col[nb] = (int)nn_step_column(a.frag, c0, wave, lane, nb, last_blk, bp[nb]);    // read only where cc >= 0: there it is < b1 < 2^31
             cc[nb] = ncc[nb];
             pk[nb] = npk[nb];
             scale[nb] = cc[nb] >= 0 ? a.scale : NAN;
@@ -184,21 +160,7 @@ __global__ __launch_bounds__(256) void lk_tile_kernel(LinkageArgs a) {
         // Wave-uniform, and no barrier follows in the loop
         if (__all((cc[0] < 0 || cc[0] == tc) && (cc[1] < 0 || cc[1] == tc))) continue;
         f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        BFrag f0, f1;
-        nn_load_b(f0, bp, 0);
-#pragma unroll 1
-        for (int ks = 0; ks < NKS; ks += 2) {              // k-step ks + 1 is fetched under the MFMAs of ks
-            nn_load_b(f1, bp, ks + 1);
-            nn_mfma(qs, ks, lane, f0, acc);
-            nn_load_b(f0, bp, min(ks + 2, NKS - 1));
-            nn_mfma(qs, ks + 1, lane, f1, acc);
-        }
+        NN_PRODUCTS(qs, bp, lane, acc);
         float cval[2] = {NAN, NAN};        // per column of the lane: the best value in this step's rows, and its row
         int crow[2] = {-1, -1};
         if (c0 < r0 + QT)                  // wave-uniform
@@ -209,8 +171,8 @@ __global__ __launch_bounds__(256) void lk_tile_kernel(LinkageArgs a) {
         // only where it can raise what the load of a step ago saw
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
-            unsigned long long key = crow[nb] >= 0 ? ((unsigned long long)lk_image(cval[nb]) << 32) | (LOW32 - (unsigned)crow[nb]) : 0ull;
-            const unsigned long long other = lk_shfl_xor(key, 32);
+            unsigned long long key = crow[nb] >= 0 ? nn_key(nn_image(cval[nb]), (unsigned)crow[nb]) : 0ull;
+            const unsigned long long other = __shfl_xor(key, 32);
             key = other > key ? other : key;
             if (lane < 32 && key > pk[nb]) atomicMax(a.best + col[nb], key);     // key > 0 only where cc >= 0: col < b1
         }
@@ -220,13 +182,13 @@ __global__ __launch_bounds__(256) void lk_tile_kernel(LinkageArgs a) {
     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            unsigned long long key = bcol[mb][r] >= 0 ? ((unsigned long long)lk_image(bval[mb][r]) << 32) | (LOW32 - (unsigned)bcol[mb][r]) : 0ull;
+            unsigned long long key = bcol[mb][r] >= 0 ? nn_key(nn_image(bval[mb][r]), (unsigned)bcol[mb][r]) : 0ull;
 #pragma unroll
             for (int s = 16; s > 0; s >>= 1) {
-                const unsigned long long other = lk_shfl_xor(key, s);
+                const unsigned long long other = __shfl_xor(key, s);
                 key = other > key ? other : key;
             }
-            if ((lane & 31) == 0 && key) atomicMax(&lbest[mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)], key);
+            if ((lane & 31) == 0 && key) atomicMax(&lbest[nn_acc_row(mb, r, lane >> 5)], key);
         }
     __syncthreads();
     if (tid < QT && lbest[tid]) atomicMax(a.best + r0 + tid, lbest[tid]);       // lbest > 0 only at a valid row < n
@@ -237,18 +199,18 @@ __global__ __launch_bounds__(256) void lk_pick_lo_kernel(int64_t n, const int32_
                                                          unsigned long long* __restrict__ cbest) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || best[i] == 0) return;
-    const unsigned partner = (unsigned)(LOW32 - (best[i] & LOW32));
+    const unsigned partner = nn_key_index(best[i]);
     const unsigned lo = min((unsigned)i, partner);
-    atomicMax(cbest + comp[i], (best[i] & ~LOW32) | (LOW32 - lo));
+    atomicMax(cbest + comp[i], nn_key((unsigned)(best[i] >> 32), lo));
 }
 
 __global__ __launch_bounds__(256) void lk_pick_hi_kernel(int64_t n, const int32_t* __restrict__ comp, const unsigned long long* __restrict__ best,
                                                          const unsigned long long* __restrict__ cbest, int32_t* __restrict__ chi) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || best[i] == 0) return;
-    const unsigned partner = (unsigned)(LOW32 - (best[i] & LOW32));
+    const unsigned partner = nn_key_index(best[i]);
     const unsigned lo = min((unsigned)i, partner), hi = max((unsigned)i, partner);
-    if (((best[i] & ~LOW32) | (LOW32 - lo)) == cbest[comp[i]]) atomicMin(chi + comp[i], (int32_t)hi);
+    if (nn_key((unsigned)(best[i] >> 32), lo) == cbest[comp[i]]) atomicMin(chi + comp[i], (int32_t)hi);
 }
 
 // One thread per root with a chosen edge.  comp, cbest and chi are the round's and constant here; only parent[] changes.
@@ -258,7 +220,7 @@ __global__ __launch_bounds__(256) void lk_link_kernel(int64_t n, int64_t capacit
                                                       unsigned* __restrict__ es, unsigned long long* __restrict__ count) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || comp[i] != (int32_t)i || cbest[i] == 0) return;
-    const int lo = (int)(LOW32 - (cbest[i] & LOW32)), hi = chi[i];
+    const int lo = (int)nn_key_index(cbest[i]), hi = chi[i];
     if ((int64_t)hi >= n) return;          // never: the row that set cbest[i] matches it and has set chi[i]
     const int other = comp[lo] == (int32_t)i ? comp[hi] : comp[lo];
     // a mutual pick is recorded once, by the smaller root; any other pair of components chose two different edges
@@ -274,17 +236,11 @@ __global__ __launch_bounds__(256) void lk_link_kernel(int64_t n, int64_t capacit
     (void)cl_join(parent, (int)i, other);
 }
 
-// A launch of its own behind the links: plain loads see every link.  Ends: a step of the climb goes to p < r, and r >= 0.
+// A launch of its own behind the links: nn_root's plain loads see every link.
 __global__ __launch_bounds__(256) void lk_flatten_kernel(int64_t n, const int32_t* __restrict__ parent, int32_t* comp) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || comp[i] < 0) return;     // an invalid row stays -1
-    int r = (int)i;
-    for (;;) {
-        const int p = parent[r];
-        if (p == r) break;
-        r = p;
-    }
-    comp[i] = r;
+    comp[i] = nn_root(parent, (int)i);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
@@ -296,10 +252,7 @@ int check_linkage_args(const char* fn, const void* rows, int64_t n, int metric, 
         set_error(f + ": " + std::to_string(n) + " rows is outside [0, 2^31)");
         return GNN_ERR_ARG;
     }
-    if (metric != GNN_KNN_COSINE && metric != GNN_KNN_DOT) {
-        set_error(f + ": metric " + std::to_string(metric) + " is outside [0, 1] (GNN_KNN_COSINE, GNN_KNN_DOT)");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_metric(f, metric)) return rc;
     if (!n_edges || !rounds || (n > 0 && (!rows || !valid)) || (n > 1 && (!a || !b || !sim))) {
         set_error("bad argument to " + f + ": the rows, the four arrays, n_edges and rounds are required");
         return GNN_ERR_ARG;
@@ -325,21 +278,17 @@ int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int m
     if (!rc) rc = nn_reserve(ctx, k.es, (size_t)n);
     if (!rc) rc = nn_reserve(ctx, k.count, 1);
     if (!rc) rc = k.h_count.reserve(1);
-    if (rc) return rc;
     const int64_t tiles = (n + QT - 1) / QT;
-    const int64_t split_rows = nn_split_rows(ctx, tiles, n);
-    const int64_t splits = (n + split_rows - 1) / split_rows;
-    if (splits > 65535) {
-        set_error(std::string(fn) + ": " + std::to_string(n) + " rows in ranges of " + std::to_string(split_rows) + " are more than 65535 ranges");
-        return GNN_ERR_ARG;
-    }
+    int64_t split_rows, splits;
+    if (!rc) rc = nn_tile_grid(ctx, fn, "rows", tiles, n, &split_rows, &splits);
+    if (rc) return rc;
     const dim3 per_row((unsigned)((n + 255) / 256)), tile_grid((unsigned)tiles, (unsigned)splits);
     LinkageArgs a;
     a.frag = w.bfrag.get();
     a.comp = k.comp.get();
     a.n = n;
     a.split_rows = split_rows;
-    a.scale = metric == GNN_KNN_COSINE ? 1.f / 65536.f : 1.f;
+    a.scale = nn_metric_scale(metric);
     a.best = k.best.get();
     k.round_ms.clear();
     {
@@ -359,11 +308,10 @@ int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int m
                       std::to_string(edges) + " edges so far): at most " + std::to_string(ROUNDS_MAX) + " rounds can be");
             return GNN_ERR_STATE;
         }
-        hipEvent_t e0 = nullptr, e1 = nullptr;
+        RoundTimer timer;
         {
             ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-            e0 = prof.a;
-            e1 = prof.b;
+            timer = {prof.a, prof.b};
             hipLaunchKernelGGL(lk_reset_kernel, per_row, dim3(256), 0, ctx->stream, n, k.comp.get(), k.parent.get(), k.best.get(), k.cbest.get(),
                                k.chi.get());
             GNN_HIP(hipGetLastError());
@@ -382,8 +330,7 @@ int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int m
         GNN_HIP(hipMemcpyAsync(k.h_count.get(), k.count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         GNN_HIP(hipStreamSynchronize(ctx->stream));
         const unsigned long long now = k.h_count.get()[0];
-        float ms = 0.f;                    // profiling only: the round's two events have completed with the synchronise above
-        if (e0 && e1 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) k.round_ms.push_back(ms);
+        timer.file(k.round_ms);
         if (now > (unsigned long long)capacity) {
             set_error(std::string(fn) + ": round " + std::to_string(pass + 1) + " recorded " + std::to_string(now) + " edges among " +
                       std::to_string(n) + " rows: a forest has at most n - 1");
@@ -415,7 +362,7 @@ int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int m
         const bool edge = i < (int64_t)m;
         a_host[i] = edge ? ea[order[i]] : -1;
         b_host[i] = edge ? eb[order[i]] : -1;
-        sim_host[i] = edge ? lk_value(es[order[i]]) : NAN;
+        sim_host[i] = edge ? nn_unimage(es[order[i]]) : NAN;
     }
     *n_edges_host = (int64_t)m;
     *rounds_host = rounds;
@@ -446,20 +393,11 @@ extern "C" int gnn_linkage(gnn_ctx* ctx, const float* rows_host, int64_t n, int 
     *n_edges_host = 0;
     *rounds_host = 0;
     if (n == 0) return GNN_OK;
-    NeighbourWorkspace& w = ctx->nn;
-    if (int rc = nn_reserve(ctx, w.d_base, (size_t)n * D)) return rc;
-    GNN_HIP(hipMemcpyAsync(w.d_base, rows_host, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    return lk_run(ctx, fn, w.d_base, n, metric, a_host, b_host, sim_host, valid_host, n_edges_host, rounds_host);
+    if (int rc = nn_upload_rows(ctx, rows_host, n)) return rc;
+    return lk_run(ctx, fn, ctx->nn.d_base, n, metric, a_host, b_host, sim_host, valid_host, n_edges_host, rounds_host);
 }
 
 extern "C" int gnn_debug_linkage_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
     if (int rc = check_ctx(ctx)) return rc;
-    if (capacity < 0 || (capacity > 0 && !ms_out) || !n_out) {
-        set_error("bad argument to gnn_debug_linkage_round_ms: a capacity >= 0, its array and n_out are required");
-        return GNN_ERR_ARG;
-    }
-    const std::vector<float>& ms = ctx->lk.round_ms;
-    *n_out = (int64_t)ms.size();
-    for (int64_t i = 0; i < std::min<int64_t>(capacity, (int64_t)ms.size()); ++i) ms_out[i] = ms[i];
-    return GNN_OK;
+    return nn_round_ms_out("gnn_debug_linkage_round_ms", ctx->lk.round_ms, ms_out, capacity, n_out);
 }

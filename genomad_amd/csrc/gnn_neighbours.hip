@@ -16,6 +16,70 @@ namespace {
 constexpr int KMAX = 64;                         // one list entry per lane of a wave
 constexpr int64_t QSLAB = 16384;                 // query rows per launch: bounds the partial lists (8 k B per query and range)
 constexpr int64_t NB_MAX = (int64_t)1 << 31;     // base indices are int32 in the partial lists
+constexpr int64_t SPLIT_MAX = 65280;             // base rows per workgroup at the most: a neighbour list entry holds its row as a 16-bit offset
+
+// ---- prepare: grid = padded rows / 32, 256 threads; wave w of a block takes its rows 8 w .. 8 w + 7, lane l the elements
+// 8 l .. 8 l + 7 = the 16-byte fragment chunk (k-step l >> 1, half l & 1).  Rows at or beyond n, and invalid rows, become zero
+// fragments with flag 0.  Cosine: the row is first scaled by the power of two that brings its largest element into [0.5, 1) - exact,
+// and the norm then neither overflows nor vanishes - the squares are summed per lane in element order and over the lanes by a fixed
+// butterfly; y = x / norm * 2^8 (the low limbs of a unit row, about 3e-5, would be f16 subnormals; the tile kernel scales the f32
+// result back by 2^-16, exactly).
+__global__ __launch_bounds__(256) void nn_prepare_kernel(const float* __restrict__ rows, int64_t n, int cosine, uint4* __restrict__ frag,
+                                                         uint8_t* __restrict__ valid) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t blk = blockIdx.x;
+    for (int i = 0; i < 8; ++i) {
+        const int rb = wave * 8 + i;
+        const int64_t row = blk * 32 + rb;
+        float x[8];
+        bool finite = true;
+        float amax = 0.f;
+        if (row < n) {
+            const float4* src = reinterpret_cast<const float4*>(rows + row * D) + lane * 2;
+            const float4 a = src[0], b = src[1];
+            x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                finite = finite && fabsf(x[e]) <= 3.4028234663852886e38f;      // false for Inf and for NaN
+                amax = fmaxf(amax, fabsf(x[e]));
+            }
+        } else {
+            finite = false;
+        }
+        bool ok = __all(finite);
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) amax = fmaxf(amax, __shfl_xor(amax, s));
+        if (cosine) {
+            ok = ok && amax > 0.f;
+            if (ok) {
+                int ex;
+                (void)frexpf(amax, &ex);
+                float ss = 0.f;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    x[e] = ldexpf(x[e], -ex);
+                    ss += x[e] * x[e];
+                }
+#pragma unroll
+                for (int s = 32; s > 0; s >>= 1) ss += __shfl_xor(ss, s);
+                const float norm = sqrtf(ss);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) x[e] = x[e] / norm * 256.f;
+            }
+        }
+        f16x8 hi, lo;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float v = ok ? x[e] : 0.f;
+            hi[e] = (_Float16)v;
+            lo[e] = (_Float16)(v - (float)hi[e]);
+        }
+        uint4* dst = frag + (blk * NKS + (lane >> 1)) * 2 * 64 + (lane & 1) * 32 + rb;
+        dst[0] = __builtin_bit_cast(uint4, hi);
+        dst[64] = __builtin_bit_cast(uint4, lo);
+        if (lane == 0) valid[row] = ok ? 1 : 0;
+    }
+}
 
 struct TileArgs {
     const uint4* qfrag;        // the slab's query fragments: 2 * gridDim.x blocks
@@ -69,56 +133,37 @@ __global__ __launch_bounds__(256) void nn_tile_kernel(TileArgs a) {
     __shared__ int lany[2][4];             // per step parity and wave: does the wave hold a candidate
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int k = a.k;
-    const int64_t b0 = (int64_t)blockIdx.y * a.split_rows, b1 = min(a.nb, b0 + a.split_rows);
-    {
-        const uint4* src = a.qfrag + (int64_t)blockIdx.x * 2 * BLK_U4;
-        for (int i = tid; i < 2 * BLK_U4; i += 256) qs[i] = src[i];
-        if (tid < QT) {
-            const int q = blockIdx.x * QT + tid;
-            lcnt[tid] = 0;
-            lok[tid] = q < a.nq && a.qvalid[q];
-            const int64_t own = a.self_off < 0 ? -1 : a.self_off + q - b0;
-            lself[tid] = own >= 0 && own < a.split_rows ? (int)own : -1;
-        }
+    TileRange t;
+    nn_tile_range(t, a.split_rows, a.nb, false);          // never empty: the host launches no empty range
+    nn_copy_tile(qs, a.qfrag, tid);
+    if (tid < QT) {
+        const int q = blockIdx.x * QT + tid;
+        lcnt[tid] = 0;
+        lok[tid] = q < a.nq && a.qvalid[q];
+        const int64_t own = a.self_off < 0 ? -1 : a.self_off + q - t.b0;
+        lself[tid] = own >= 0 && own < a.split_rows ? (int)own : -1;
     }
     __syncthreads();
-    const int64_t last_blk = (b1 - 1) / 32;               // b1 > b0: the host launches no empty range
+    const int64_t last_blk = t.last_blk();
     int par = 0;
-    for (int64_t c0 = b0; c0 < b1; c0 += STEP, par ^= 1) {
-        // ---- this wave's two column blocks; one beyond the range reads the range's last block and is masked below
+    for (int64_t c0 = t.c0; c0 < t.b1; c0 += STEP, par ^= 1) {
         const uint4* bp[2];
         int coff[2];                       // the lane's column as an offset into the range, -1: no candidate
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
-            const int64_t blk = c0 / 32 + wave * 2 + nb;
-            bp[nb] = a.bfrag + min(blk, last_blk) * BLK_U4 + lane;
-            const int64_t col = blk * 32 + (lane & 31);
-            coff[nb] = col < b1 && a.bvalid[col] ? (int)(col - b0) : -1;
+            const int64_t col = nn_step_column(a.bfrag, c0, wave, lane, nb, last_blk, bp[nb]);
+            coff[nb] = col < t.b1 && a.bvalid[col] ? (int)(col - t.b0) : -1;
         }
         f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        BFrag f0, f1;
-        nn_load_b(f0, bp, 0);
-#pragma unroll 1
-        for (int ks = 0; ks < NKS; ks += 2) {              // k-step ks + 1 is fetched under the MFMAs of ks
-            nn_load_b(f1, bp, ks + 1);
-            nn_mfma(qs, ks, lane, f0, acc);
-            nn_load_b(f0, bp, min(ks + 2, NKS - 1));
-            nn_mfma(qs, ks + 1, lane, f1, acc);
-        }
-        // ---- candidates: C/D layout column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  A value that does not reach
-        // the row's k-th best is dropped here; the others are re-examined when they are filed
+        NN_PRODUCTS(qs, bp, lane, acc);
+        // ---- candidates.  A value that does not reach the row's k-th best is dropped here; the others are re-examined when they are
+        // filed
         unsigned long long pick = 0;
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int row = nn_acc_row(mb, r, lane >> 5);
                 const int cnt = lcnt[row];
                 const float kth = lsim[row][k - 1];
                 const int own = lself[row];
@@ -148,7 +193,7 @@ __global__ __launch_bounds__(256) void nn_tile_kernel(TileArgs a) {
                                 while (bal) {
                                     const int src = __ffsll((long long)bal) - 1;
                                     bal &= bal - 1;
-                                    const int row = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * (src >> 5);
+                                    const int row = nn_acc_row(mb, r, src >> 5);
                                     const float s = __shfl(acc[mb][nb][r], src);
                                     const unsigned off = (unsigned)__shfl(coff[nb], src);
                                     nn_insert(lsim[row], loff[row], &lcnt[row], k, lane, s, off);
@@ -167,7 +212,7 @@ __global__ __launch_bounds__(256) void nn_tile_kernel(TileArgs a) {
         const bool have = j < lcnt[row];
         const int64_t o = ((int64_t)q * a.splits + blockIdx.y) * k + j;
         a.psim[o] = have ? lsim[row][j] : NAN;
-        a.pidx[o] = have ? (int32_t)(b0 + loff[row][j]) : -1;
+        a.pidx[o] = have ? (int32_t)(t.b0 + loff[row][j]) : -1;
     }
 }
 
@@ -222,10 +267,7 @@ int check_nn_args(const char* fn, const void* query, int64_t nq, int64_t nb, boo
         set_error(f + ": k " + std::to_string(k) + " is outside [1, " + std::to_string(KMAX) + "]");
         return GNN_ERR_ARG;
     }
-    if (metric != GNN_KNN_COSINE && metric != GNN_KNN_DOT) {
-        set_error(f + ": metric " + std::to_string(metric) + " is outside [0, 1] (GNN_KNN_COSINE, GNN_KNN_DOT)");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_metric(f, metric)) return rc;
     if (nq < 0) {
         set_error(f + ": n_query " + std::to_string(nq) + " is outside [0, 2^63)");
         return GNN_ERR_ARG;
@@ -247,14 +289,11 @@ int nn_search_slab(gnn_ctx* ctx, const uint4* qfrag, const uint8_t* qvalid, int6
                    int64_t* idx_dev, float* sim_dev) {
     NeighbourWorkspace& w = ctx->nn;
     const int64_t tiles = (m + QT - 1) / QT;
-    const int64_t split_rows = nn_split_rows(ctx, tiles, nb);
-    const int64_t splits = (nb + split_rows - 1) / split_rows;
-    if (splits > 65535) {
-        set_error("gnn_neighbours: " + std::to_string(nb) + " base rows in ranges of " + std::to_string(split_rows) + " are more than 65535 ranges");
-        return GNN_ERR_ARG;
-    }
+    int64_t split_rows, splits;
+    int rc = nn_tile_grid(ctx, "gnn_neighbours", "base rows", tiles, nb, &split_rows, &splits);
+    if (rc) return rc;
     const size_t part = (size_t)m * splits * k;
-    int rc = nn_reserve(ctx, w.psim, part);
+    rc = nn_reserve(ctx, w.psim, part);
     if (!rc) rc = nn_reserve(ctx, w.pidx, part);
     if (rc) return rc;
     ProfScope prof(ctx, GNN_K_NEIGHBOURS);
@@ -269,7 +308,7 @@ int nn_search_slab(gnn_ctx* ctx, const uint4* qfrag, const uint8_t* qvalid, int6
         a.split_rows = split_rows;
         a.splits = (int)splits;
         a.k = k;
-        a.scale = metric == GNN_KNN_COSINE ? 1.f / 65536.f : 1.f;
+        a.scale = nn_metric_scale(metric);
         a.self_off = self_off;
         a.psim = w.psim.get();
         a.pidx = w.pidx.get();
@@ -324,6 +363,65 @@ int nn_search(gnn_ctx* ctx, const float* query_dev, const float* query_host, int
 }
 
 }  // namespace
+
+// ---- the prologue of every search over encoder embeddings (declared in gnn_common.h) ------------------------------------------------
+
+int nn_check_metric(const std::string& fn, int metric) {
+    if (metric == GNN_KNN_COSINE || metric == GNN_KNN_DOT) return GNN_OK;
+    set_error(fn + ": metric " + std::to_string(metric) + " is outside [0, 1] (GNN_KNN_COSINE, GNN_KNN_DOT)");
+    return GNN_ERR_ARG;
+}
+
+float nn_metric_scale(int metric) { return metric == GNN_KNN_COSINE ? 1.f / 65536.f : 1.f; }
+
+int nn_prepare(gnn_ctx* ctx, const float* rows_dev, int64_t n, int metric, DevBuf<uint4>& frag, DevBuf<uint8_t>& valid) {
+    const int64_t padded = round_up(n, QT);
+    int rc = nn_reserve(ctx, frag, (size_t)(padded / 32 * BLK_U4));
+    if (!rc) rc = nn_reserve(ctx, valid, (size_t)padded);
+    if (rc) return rc;
+    if (padded == 0) return GNN_OK;
+    ProfScope prof(ctx, GNN_K_NEIGHBOURS);
+    hipLaunchKernelGGL(nn_prepare_kernel, dim3((unsigned)(padded / 32)), dim3(256), 0, ctx->stream, rows_dev, n, metric == GNN_KNN_COSINE,
+                       frag.get(), valid.get());
+    GNN_HIP(hipGetLastError());
+    return GNN_OK;
+}
+
+int nn_tile_grid(const gnn_ctx* ctx, const std::string& fn, const char* noun, int64_t tiles, int64_t nb, int64_t* split_rows, int64_t* splits) {
+    int64_t rows = ctx->nn.split;
+    if (rows <= 0) {
+        const int64_t want = std::max<int64_t>(1, (2 * std::max(ctx->cu_count, 1) + tiles - 1) / tiles);
+        rows = std::max<int64_t>(STEP, (nb + want - 1) / want);
+    }
+    *split_rows = std::min(round_up(rows, 32), SPLIT_MAX);
+    *splits = (nb + *split_rows - 1) / *split_rows;
+    if (*splits <= 65535) return GNN_OK;
+    set_error(fn + ": " + std::to_string(nb) + " " + noun + " in ranges of " + std::to_string(*split_rows) + " are more than 65535 ranges");
+    return GNN_ERR_ARG;
+}
+
+int nn_upload_rows(gnn_ctx* ctx, const float* rows_host, int64_t n) {
+    DevBuf<float>& d_base = ctx->nn.d_base;
+    if (int rc = nn_reserve(ctx, d_base, (size_t)std::max<int64_t>(n, 1) * D)) return rc;
+    if (n > 0) GNN_HIP(hipMemcpyAsync(d_base, rows_host, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    return GNN_OK;
+}
+
+void RoundTimer::file(std::vector<float>& round_ms) const {
+    float ms = 0.f;                        // profiling only: the round's two events have completed with the synchronise before this
+    if (a && b && hipEventElapsedTime(&ms, a, b) == hipSuccess) round_ms.push_back(ms);
+}
+
+int nn_round_ms_out(const char* fn, const std::vector<float>& round_ms, double* ms_out, int64_t capacity, int64_t* n_out) {
+    if (capacity < 0 || (capacity > 0 && !ms_out) || !n_out) {
+        set_error(std::string("bad argument to ") + fn + ": a capacity >= 0, its array and n_out are required");
+        return GNN_ERR_ARG;
+    }
+    *n_out = (int64_t)round_ms.size();
+    for (int64_t i = 0; i < std::min<int64_t>(capacity, (int64_t)round_ms.size()); ++i) ms_out[i] = round_ms[i];
+    return GNN_OK;
+}
+
 }  // namespace gnn
 
 using namespace gnn;
@@ -358,11 +456,7 @@ extern "C" int gnn_neighbours(gnn_ctx* ctx, const float* query_host, int64_t n_q
     if (int rc = check_ctx(ctx)) return rc;
     if (n_query == 0) return GNN_OK;
     const int64_t nb = self ? n_query : n_base;
-    NeighbourWorkspace& w = ctx->nn;
     // the base goes up once; the queries follow slab by slab
-    if (int rc = nn_reserve(ctx, w.d_base, (size_t)std::max<int64_t>(nb, 1) * D)) return rc;
-    if (nb > 0)
-        GNN_HIP(hipMemcpyAsync(w.d_base, self ? query_host : base_host_or_null, (size_t)nb * D * sizeof(float), hipMemcpyHostToDevice,
-                               ctx->stream));
-    return nn_search(ctx, nullptr, self ? nullptr : query_host, n_query, w.d_base, nb, self, k, metric, idx_host, sim_host, true);
+    if (int rc = nn_upload_rows(ctx, self ? query_host : base_host_or_null, nb)) return rc;
+    return nn_search(ctx, nullptr, self ? nullptr : query_host, n_query, ctx->nn.d_base, nb, self, k, metric, idx_host, sim_host, true);
 }

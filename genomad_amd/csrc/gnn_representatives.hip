@@ -10,19 +10,19 @@
 // FRESH only when every smaller-rank neighbour is decided and none of them is a representative - one would have been FRESH in some
 // earlier round while the row was UNDECIDED, and made it a MEMBER in the round after -, and it turns MEMBER only behind a
 // representative of smaller rank.  WORST CASE: a path walked end to end needs as many rounds as it has rows; `rounds` is returned.
-//   prepare    nn_prepare of gnn_nn_frag.h, as it is: the neighbour search's fragments and flags, in its buffers.
+//   prepare    nn_prepare (gnn_neighbours.hip), as it is: the neighbour search's fragments and flags, in its buffers.
 //   init       state = UNDECIDED or INVALID, flag = key = size = 0, the live maps, the count of undecided rows.
-//   round      cl_tile_kernel's skeleton (gnn_clusters.hip) - 64 rows' fragments in LDS, the base streamed in steps of 256 columns, the
-//              same three products per k-step in the same order, the same scale, the UPPER TRIANGLE only: the value of the pair i < j
+//   round      the tile parts of gnn_nn_frag.h - 64 rows' fragments in LDS, the base streamed in steps of 256 columns, NN_PRODUCTS'
+//              three products per k-step in their order, the same scale, the UPPER TRIANGLE only: the value of the pair i < j
 //              is the f32 gnn_neighbours returns for query i and base row j.  state[] is read-only during the launch.  For i < j with
 //              s >= threshold, column j UNDECIDED and row i FRESH or UNDECIDED: HIT or WAIT is ORed into flag[j].  A workgroup whose
 //              row tile holds no FRESH or UNDECIDED row leaves before it loads fragments; a wave whose two column blocks hold no
 //              UNDECIDED column skips the step's k-loop: later rounds touch few rows.
 //   decide     one thread per row: the rule above on (state, flag); FRESH of the previous round turns REP; the flag is cleared; the
 //              undecided count and the live maps are brought up to date.
-//   assign     only if a row is MEMBER; the round skeleton with rows = representatives, columns = members: a 64-bit atomicMax at
-//              key[j] of (order-preserving image of s) << 32 | (2^32 - 1 - i).  A pass of its own: a representative of smaller rank
-//              may be decided in a later round than the one that made j a member.
+//   assign     only if a row is MEMBER; the round kernel's other instance with rows = representatives, columns = members: a 64-bit
+//              atomicMax at key[j] of nn_key(nn_image(s), i).  A pass of its own: a representative of smaller rank may be decided in a
+//              later round than the one that made j a member.
 //   finish     rep and the exact f32 sim from the key; integer adds of the sizes at the representative.
 //   summarise  every row takes its representative's size; an invalid row is -1 / NaN / 0.
 // Flags are ORs, keys maxima, sizes integer adds: nothing depends on the order the workgroups run in or on the split of the base.  No
@@ -73,13 +73,6 @@ struct TileArgs {
     unsigned long long* key;   // assign kernel
 };
 
-// s (not a NaN) -> a u32 that orders as s does; -0 counts as +0
-__device__ __forceinline__ unsigned rp_image(float s) {
-    const unsigned u = __float_as_uint(s + 0.f);
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float rp_unimage(unsigned v) { return __uint_as_float(v ^ ((v >> 31) ? 0x80000000u : 0xffffffffu)); }
-
 // grid = (row tiles, base ranges), 256 threads.  LDS: the tile's fragments 128 KB and what its rows contribute.
 // ASSIGN false: the round kernel (rows FRESH -> HIT, UNDECIDED -> WAIT; columns UNDECIDED; OR into flag).
 // ASSIGN true:  the assign kernel (rows FRESH or REP; columns MEMBER; max into key).
@@ -88,9 +81,9 @@ __global__ __launch_bounds__(256) void rp_tile_kernel(TileArgs a) {
     __shared__ uint4 qs[2 * BLK_U4];
     __shared__ uint8_t lsrc[QT];           // what an edge from the tile's row says: 0 = nothing
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t r0 = (int64_t)blockIdx.x * QT;
-    const int64_t b0 = (int64_t)blockIdx.y * a.split_rows, b1 = min(a.n, b0 + a.split_rows);
-    if (b1 <= r0 + 1) return;              // no column of the range lies right of the tile's first row (the whole workgroup leaves)
+    TileRange t;
+    if (!nn_tile_range(t, a.split_rows, a.n, true)) return;
+    const int64_t r0 = t.r0, b1 = t.b1;
     uint8_t src = 0;
     if (tid < QT) {
         const uint8_t st = a.state[r0 + tid];              // state[] covers the padded rows
@@ -101,22 +94,19 @@ __global__ __launch_bounds__(256) void rp_tile_kernel(TileArgs a) {
     } else {
         if (!a.row_live[blockIdx.x]) return;               // neither FRESH nor UNDECIDED (one byte: the whole workgroup leaves)
     }
-    {
-        const uint4* frag = a.frag + (int64_t)blockIdx.x * 2 * BLK_U4;
-        for (int i = tid; i < 2 * BLK_U4; i += 256) qs[i] = frag[i];
-        if (tid < QT) lsrc[tid] = src;
-    }
+    nn_copy_tile(qs, a.frag, tid);
+    if (tid < QT) lsrc[tid] = src;
     __syncthreads();
-    const int64_t last_blk = (b1 - 1) / 32;
+    const int64_t last_blk = t.last_blk();
     // Whether a step runs: bit nb of the lane's answer says that its column block nb matters.  Round: the block's live byte (the
     // same for the whole wave).  Assign: the lane's own column is a MEMBER.
     auto probe = [&](int64_t c0) -> int {
         int w = 0;
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
-            const int64_t blk = c0 / 32 + wave * 2 + nb;
+            const int64_t blk = nn_step_blk(c0, wave, nb);
             if (ASSIGN) {
-                const int64_t col = blk * 32 + (lane & 31);
+                const int64_t col = nn_blk_col(blk, lane);
                 w |= (int)(col < b1 && a.state[col] == ST_MEMBER) << nb;
             } else {
                 w |= (int)(blk <= last_blk && a.col_live[blk] != 0) << nb;
@@ -124,9 +114,8 @@ __global__ __launch_bounds__(256) void rp_tile_kernel(TileArgs a) {
         }
         return w;
     };
-    // the first step begins at the 32-column block that holds the tile's first row (r0 and b0 are multiples of 32); a pair's value
-    // depends on its two rows only, so where a step begins changes nothing.  Ends: c0 grows by STEP towards b1.
-    int64_t c0 = max(b0, r0);
+    // Ends: c0 grows by STEP towards b1.
+    int64_t c0 = t.c0;
     int next = probe(c0);
     for (; c0 < b1; c0 += STEP) {
         const int want = next;
@@ -136,37 +125,21 @@ __global__ __launch_bounds__(256) void rp_tile_kernel(TileArgs a) {
         int cg[2];                         // the lane's column, -1: nothing can end there
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
-            const int64_t blk = c0 / 32 + wave * 2 + nb;
-            bp[nb] = a.frag + min(blk, last_blk) * BLK_U4 + lane;
-            const int64_t col = blk * 32 + (lane & 31);
+            const int64_t col = nn_step_column(a.frag, c0, wave, lane, nb, last_blk, bp[nb]);
             const bool open = ASSIGN ? (want >> nb) & 1 : col < b1 && a.state[col] == ST_UNDECIDED;       // round: read behind the MFMAs
             cg[nb] = open ? (int)col : -1;
         }
         f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        BFrag f0, f1;
-        nn_load_b(f0, bp, 0);
-#pragma unroll 1
-        for (int ks = 0; ks < NKS; ks += 2) {              // k-step ks + 1 is fetched under the MFMAs of ks
-            nn_load_b(f1, bp, ks + 1);
-            nn_mfma(qs, ks, lane, f0, acc);
-            nn_load_b(f0, bp, min(ks + 2, NKS - 1));
-            nn_mfma(qs, ks + 1, lane, f1, acc);
-        }
-        // ---- C/D layout: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  A column is one lane's through all its
-        // registers, and the other half-wave's: reduced in the lane, then with one __shfl_xor; one atomic per column and step
+        NN_PRODUCTS(qs, bp, lane, acc);
+        // ---- a column is one lane's through all its registers, and the other half-wave's: reduced in the lane, then with one
+        // __shfl_xor; one atomic per column and step
         unsigned f[2] = {0, 0};            // round: the flag bits of the lane's two columns
         unsigned long long k[2] = {0, 0};  // assign: their largest keys
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int row = nn_acc_row(mb, r, lane >> 5);
                 const int rg = (int)r0 + row;
                 const unsigned s8 = lsrc[row];
 #pragma unroll
@@ -174,7 +147,7 @@ __global__ __launch_bounds__(256) void rp_tile_kernel(TileArgs a) {
                     const float s = acc[mb][nb][r] * a.scale;
                     const bool e = s8 && rg < cg[nb] && s >= a.threshold;           // cg = -1 fails rg < cg; a NaN fails >=
                     if (ASSIGN) {
-                        const unsigned long long key = ((unsigned long long)rp_image(s) << 32) | (0xffffffffull - (unsigned)rg);
+                        const unsigned long long key = nn_key(nn_image(s), (unsigned)rg);
                         k[nb] = e && key > k[nb] ? key : k[nb];
                     } else {
                         f[nb] |= e ? s8 : 0u;
@@ -233,10 +206,10 @@ __global__ __launch_bounds__(256) void rp_finish_kernel(int64_t n, const uint8_t
         r = i;
     } else if (st == ST_MEMBER) {
         const unsigned long long k = key[i];
-        const int64_t from = (int64_t)(0xffffffffull - (k & 0xffffffffull));
+        const int64_t from = (int64_t)nn_key_index(k);
         if (k && from < i) {               // every member has a key (the FRESH row that made it one is a representative): a bound, not a case
             r = from;
-            s = rp_unimage((unsigned)(k >> 32));
+            s = nn_unimage((unsigned)(k >> 32));
         }
     }
     rep[i] = r;
@@ -265,10 +238,7 @@ int check_rep_args(const char* fn, const void* rows, int64_t n, float threshold,
         set_error(f + ": threshold " + std::to_string(threshold) + " is outside (-inf, inf): a finite f32 is required");
         return GNN_ERR_ARG;
     }
-    if (metric != GNN_KNN_COSINE && metric != GNN_KNN_DOT) {
-        set_error(f + ": metric " + std::to_string(metric) + " is outside [0, 1] (GNN_KNN_COSINE, GNN_KNN_DOT)");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_metric(f, metric)) return rc;
     if (n > 0 && (!rows || !rep || !sim || !size || !rounds)) {
         set_error("bad argument to " + f + ": the rows, the three outputs and rounds are required");
         return GNN_ERR_ARG;
@@ -301,14 +271,10 @@ int rp_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, float
     if (!rc) rc = nn_reserve(ctx, p.col_live, (size_t)(padded / 32));
     if (!rc) rc = nn_reserve(ctx, p.count, 2);
     if (!rc) rc = p.h_count.reserve(1);
-    if (rc) return rc;
     const int64_t tiles = padded / QT;
-    const int64_t split_rows = nn_split_rows(ctx, tiles, n);
-    const int64_t splits = (n + split_rows - 1) / split_rows;
-    if (splits > 65535) {
-        set_error(std::string(fn) + ": " + std::to_string(n) + " rows in ranges of " + std::to_string(split_rows) + " are more than 65535 ranges");
-        return GNN_ERR_ARG;
-    }
+    int64_t split_rows, splits;
+    if (!rc) rc = nn_tile_grid(ctx, fn, "rows", tiles, n, &split_rows, &splits);
+    if (rc) return rc;
     const dim3 per_row((unsigned)((n + 255) / 256)), per_padded((unsigned)((padded + 255) / 256)), tile_grid((unsigned)tiles, (unsigned)splits);
     TileArgs a;
     a.frag = w.bfrag.get();
@@ -317,7 +283,7 @@ int rp_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, float
     a.col_live = p.col_live.get();
     a.n = n;
     a.split_rows = split_rows;
-    a.scale = metric == GNN_KNN_COSINE ? 1.f / 65536.f : 1.f;
+    a.scale = nn_metric_scale(metric);
     a.threshold = threshold;
     a.flag = p.flag.get();
     a.key = p.key.get();
@@ -341,11 +307,10 @@ int rp_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, float
                       std::to_string(n) + " rows");
             return GNN_ERR_STATE;
         }
-        hipEvent_t e0 = nullptr, e1 = nullptr;
+        RoundTimer timer;
         {
             ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-            e0 = prof.a;
-            e1 = prof.b;
+            timer = {prof.a, prof.b};
             hipLaunchKernelGGL(rp_tile_kernel<false>, tile_grid, dim3(256), 0, ctx->stream, a);
             GNN_HIP(hipGetLastError());
             hipLaunchKernelGGL(rp_decide_kernel, per_padded, dim3(256), 0, ctx->stream, padded, p.state.get(), p.flag.get(), p.row_live.get(),
@@ -355,8 +320,7 @@ int rp_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, float
         unsigned long long now = 0;
         if ((rc = rp_read_count(ctx, 0, &now))) return rc;
         ++rounds;
-        float ms = 0.f;                    // profiling only: the round's two events have completed with the synchronise above
-        if (e0 && e1 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) p.round_ms.push_back(ms);
+        timer.file(p.round_ms);            // behind the synchronise of rp_read_count
         if (now >= undecided) {
             set_error(std::string(fn) + ": round " + std::to_string(rounds) + " left " + std::to_string(now) + " of " + std::to_string(undecided) +
                       " undecided rows undecided: the count must fall in every round");
@@ -406,10 +370,9 @@ extern "C" int gnn_representatives(gnn_ctx* ctx, const float* rows_host, int64_t
     }
     NeighbourWorkspace& w = ctx->nn;
     RepresentativeWorkspace& p = ctx->rp;
-    int rc = nn_reserve(ctx, w.d_base, (size_t)n * D);
-    if (!rc) rc = nn_reserve(ctx, p.d_out, (size_t)(2 * n + (n + 1) / 2));
+    int rc = nn_reserve(ctx, p.d_out, (size_t)(2 * n + (n + 1) / 2));      // both buffers stand before the copy is enqueued
+    if (!rc) rc = nn_upload_rows(ctx, rows_host, n);
     if (rc) return rc;
-    GNN_HIP(hipMemcpyAsync(w.d_base, rows_host, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     int64_t* const out = p.d_out;
     float* const sim = reinterpret_cast<float*>(out + 2 * n);
     if ((rc = rp_run(ctx, fn, w.d_base, n, threshold, metric, out, sim, out + n, rounds_host))) return rc;
@@ -422,12 +385,5 @@ extern "C" int gnn_representatives(gnn_ctx* ctx, const float* rows_host, int64_t
 
 extern "C" int gnn_debug_representative_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
     if (int rc = check_ctx(ctx)) return rc;
-    if (capacity < 0 || (capacity > 0 && !ms_out) || !n_out) {
-        set_error("bad argument to gnn_debug_representative_round_ms: a capacity >= 0, its array and n_out are required");
-        return GNN_ERR_ARG;
-    }
-    const std::vector<float>& ms = ctx->rp.round_ms;
-    *n_out = (int64_t)ms.size();
-    for (int64_t i = 0; i < std::min<int64_t>(capacity, (int64_t)ms.size()); ++i) ms_out[i] = ms[i];
-    return GNN_OK;
+    return nn_round_ms_out("gnn_debug_representative_round_ms", ctx->rp.round_ms, ms_out, capacity, n_out);
 }
