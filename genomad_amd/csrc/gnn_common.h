@@ -245,6 +245,26 @@ struct LinkageWorkspace {
     std::vector<float> round_ms;                 // profiling on: HIP-event time of every round of the last call
 };
 
+// ---- similarity graph (gnn_graph.hip): persistent, grow-only.  The fragments and flags are NeighbourWorkspace's bfrag / bvalid (and
+// d_base for the host entry points); here 12 B per (row, base range) of counters and offsets and, for gnn_graph_count / gnn_graph_fill
+// alone, 8 B per row and 8 B per edge of results.  Nothing is n x n.
+struct GraphWorkspace {
+    DevBuf<int32_t> cnt;                         // [n * splits]: the edges of row i among the columns of range p, at i * splits + p
+    DevBuf<int64_t> off;                         // [n * splits + 1]: their exclusive prefix sums, then the total
+    // what the last count call ran with: the fill runs the same grid, and answers GNN_ERR_STATE for another (n, threshold, metric)
+    bool counted = false;
+    int64_t n = 0;
+    uint32_t threshold_bits = 0;
+    int metric = 0;
+    int64_t split_rows = 0, splits = 0;
+    int64_t total = 0;                           // edges
+    bool host_rows = false;                      // NeighbourWorkspace's d_base still holds the rows gnn_graph_count uploaded
+    DevBuf<int64_t> d_indptr;                    // gnn_graph_count: [n + 1]
+    DevBuf<int32_t> d_col;                       // gnn_graph_fill: [total]
+    DevBuf<float> d_sim;
+    std::vector<float> pass_ms;                  // profiling on: HIP-event time of the last count call's [count pass, scan]
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -433,6 +453,7 @@ struct gnn_ctx {
     gnn::ClusterWorkspace cl;                     // gnn_clusters.hip
     gnn::RepresentativeWorkspace rp;              // gnn_representatives.hip
     gnn::LinkageWorkspace lk;                     // gnn_linkage.hip
+    gnn::GraphWorkspace gr;                       // gnn_graph.hip
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;

@@ -1,0 +1,397 @@
+// Similarity graph among encoder embeddings (include/genomad_nn.h, "similarity graph"): every pair i < j of valid
+// rows with sim(i, j) >= threshold and its f32 similarity, as a CSR over the upper triangle - rows in order, a row's columns
+// ascending.  The edge set is the one gnn_cluster acts on; here it is kept.  Exact, two passes of one tile kernel and a scan:
+//   prepare    nn_prepare (gnn_neighbours.hip), as it is: the neighbour search's fragments and flags, in its buffers.
+//   count      gr_tile_kernel<false>: gnn_clusters.hip's tile kernel up to and including its `edge` mask - the tile parts of
+//              gnn_nn_frag.h, NN_PRODUCTS' three products per k-step in their order, the same scale, the UPPER TRIANGLE only: the
+//              value of the pair i < j is the f32 that gnn_neighbours returns for query i and base row j.  An edge belongs to its
+//              smaller row: each of the tile's rows counts its edges among the workgroup's columns (ballots, one LDS add per row
+//              and step) and stores the count at cnt[row * splits + part] - one owner workgroup per counter, a plain store.  A
+//              workgroup that leaves early stores nothing: the array is cleared first.
+//   scan       exclusive int64 prefix sums over the n * splits counters in the order (row, part), the total behind them; integer
+//              sums, so the shape of the scan changes nothing.  indptr[i] = off[i * splits].  The host reads the 8-byte total.
+//   fill       gr_tile_kernel<true>: the same products in the same steps.  A workgroup whose 64 (row, part) segments are all empty
+//              leaves before it loads fragments.  Otherwise lpos[row] starts at the segment's offset; in a step with an edge every
+//              wave files its rows' counts, and an edge's place is lpos[row] + the counts of the lower waves + its own wave's
+//              column block 0 if it sits in block 1 + the edges at lower lanes of its half of the ballot: ascending in (wave,
+//              column block, lane & 31), which is ascending in the column.  Steps ascend and the parts follow each other in the scan:
+//              a row's columns come out sorted.  Every store is guarded by the segment's end: rows that change between count and
+//              fill give garbage, never an overrun.
+// No atomics in global memory, no position that depends on the order workgroups or waves run in: bit-identical for every split of the
+// base.  No loop here waits for another workgroup: every loop's termination argument stands next to it.
+#include <cmath>
+#include <cstring>
+
+#include "gnn_nn_frag.h"
+
+namespace gnn {
+namespace {
+
+constexpr int64_t N_MAX = (int64_t)1 << 31;      // columns are int32
+constexpr int SCAN_THREADS = 1024;               // the one block that scans the counters
+
+struct GraphArgs {
+    const uint4* frag;         // round_up(n, 64) / 32 blocks: rows and columns alike
+    const uint8_t* valid;      // [round_up(n, 64)]
+    int64_t n;
+    int64_t split_rows;        // base rows per workgroup: a multiple of 32
+    int64_t splits;            // = gridDim.y
+    float scale;               // 2^-16 for cosine, 1 for dot
+    float threshold;
+    int32_t* cnt;              // count: [n * splits], cleared before the launch
+    const int64_t* off;        // fill: [n * splits + 1]
+    int32_t* col;              // fill: [off[n * splits]]
+    float* sim;
+};
+
+// grid = (row tiles, base ranges), 256 threads.  LDS: the tile's fragments 128 KB, its rows' flags and counts or positions.
+// FILL false: the count pass.  FILL true: the fill pass - there every thread reaches the same barriers: the step loop's bounds and
+// the vote behind the products are the same in the whole workgroup.
+template <bool FILL>
+__global__ __launch_bounds__(256) void gr_tile_kernel(GraphArgs a) {
+    __shared__ uint4 qs[2 * BLK_U4];
+    __shared__ uint8_t lok[QT];
+    __shared__ int lcnt[QT];               // count: edges of this workgroup's columns at the tile's rows, stored once
+    __shared__ int64_t lpos[QT], lend[QT]; // fill: where the row's next edge goes, and the end of its (row, part) segment
+    __shared__ int wcnt[4][QT];            // fill: the step's edges per wave and row
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
+    TileRange t;
+    if (!nn_tile_range(t, a.split_rows, a.n, true)) return;
+    const int64_t r0 = t.r0;
+    if (FILL) {
+        int64_t p = 0, e = 0;
+        if (tid < QT && r0 + tid < a.n) {
+            const int64_t i = (r0 + tid) * a.splits + blockIdx.y;
+            p = a.off[i];
+            e = a.off[i + 1];
+        }
+        if (!__syncthreads_or(e > p)) return;                  // no edge in the 64 segments (uniform: the whole workgroup leaves)
+        if (tid < QT) {
+            lpos[tid] = p;
+            lend[tid] = e;
+        }
+    }
+    nn_copy_tile(qs, a.frag, tid);
+    if (tid < QT) {
+        lcnt[tid] = 0;
+        lok[tid] = r0 + tid < a.n && a.valid[r0 + tid];
+    }
+    __syncthreads();
+    const int64_t last_blk = t.last_blk();
+    // Ends: c0 grows by STEP towards b1.
+    for (int64_t c0 = t.c0; c0 < t.b1; c0 += STEP) {
+        const uint4* bp[2];
+        int cg[2];                         // the lane's column, -1: no edge can end there
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            const int64_t col = nn_step_column(a.frag, c0, wave, lane, nb, last_blk, bp[nb]);
+            cg[nb] = col < t.b1 && a.valid[col] ? (int)col : -1;
+        }
+        f32x16 acc[2][2];
+        NN_PRODUCTS(qs, bp, lane, acc);
+        // ---- edges: bit (mb * 2 + nb) * 16 + reg
+        unsigned long long edge = 0;
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = nn_acc_row(mb, r, half);
+                const int rg = (int)r0 + row;
+                const bool rok = lok[row];
+#pragma unroll
+                for (int nb = 0; nb < 2; ++nb) {
+                    const float s = acc[mb][nb][r] * a.scale;
+                    const bool e = rok && rg < cg[nb] && s >= a.threshold;          // cg = -1 fails rg < cg; a NaN fails >=
+                    edge |= (unsigned long long)e << ((mb * 2 + nb) * 16 + r);
+                }
+            }
+        if (!FILL) {
+            if (__ballot(edge != 0) == 0) continue;            // wave-uniform, and no barrier follows in the loop
+            // A row's edges of this step lie in one register of 32 lanes per column block: a ballot counts them, one lane per half
+            // adds them in LDS.
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const unsigned long long e0 = __ballot((edge >> (mb * 32 + r)) & 1), e1 = __ballot((edge >> (mb * 32 + 16 + r)) & 1);
+                    const int c = __popc((unsigned)(e0 >> (32 * half))) + __popc((unsigned)(e1 >> (32 * half)));
+                    if ((lane & 31) == 0 && c) atomicAdd(&lcnt[nn_acc_row(mb, r, half)], c);
+                }
+        } else {
+            if (!__syncthreads_or(edge != 0)) continue;        // workgroup-uniform: an edge-free step costs this one vote
+            // ---- the wave's edges per row: row (mb, r, half) is one lane's to file, and every wave files all 64 of its rows
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const unsigned long long e0 = __ballot((edge >> (mb * 32 + r)) & 1), e1 = __ballot((edge >> (mb * 32 + 16 + r)) & 1);
+                    const int c = __popc((unsigned)(e0 >> (32 * half))) + __popc((unsigned)(e1 >> (32 * half)));
+                    if ((lane & 31) == 0) wcnt[wave][nn_acc_row(mb, r, half)] = c;
+                }
+            __syncthreads();
+            // ---- places: ascending in (wave, column block, lane & 31)
+            const unsigned below = (1u << (lane & 31)) - 1u;
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const unsigned h0 = (unsigned)(__ballot((edge >> (mb * 32 + r)) & 1) >> (32 * half));
+                    const unsigned h1 = (unsigned)(__ballot((edge >> (mb * 32 + 16 + r)) & 1) >> (32 * half));
+                    if (((edge >> (mb * 32 + r)) | (edge >> (mb * 32 + 16 + r))) & 1) {
+                        const int row = nn_acc_row(mb, r, half);
+                        int64_t base = lpos[row];
+                        for (int w = 0; w < wave; ++w) base += wcnt[w][row];       // Ends: w grows towards wave <= 3
+                        const int64_t end = lend[row];
+#pragma unroll
+                        for (int nb = 0; nb < 2; ++nb)
+                            if ((edge >> ((mb * 2 + nb) * 16 + r)) & 1) {
+                                const int64_t at = base + (nb ? __popc(h0) : 0) + __popc((nb ? h1 : h0) & below);
+                                if (at < end) {            // always, unless the rows changed since the count: never an overrun
+                                    a.col[at] = cg[nb];
+                                    a.sim[at] = acc[mb][nb][r] * a.scale;
+                                }
+                            }
+                    }
+                }
+            __syncthreads();
+            if (tid < QT) lpos[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
+            __syncthreads();
+        }
+    }
+    if (!FILL) {
+        __syncthreads();
+        if (tid < QT && r0 + tid < a.n) a.cnt[(r0 + tid) * a.splits + blockIdx.y] = lcnt[tid];
+    }
+}
+
+// Exclusive prefix sums of the m counters, and their total behind them: ONE block, thread i owns a run of counters (the scheme of
+// gnn_regions.hip's block_offsets_kernel).  Every loop ends: i grows towards e, or towards SCAN_THREADS.
+__global__ __launch_bounds__(SCAN_THREADS) void gr_scan_kernel(const int32_t* __restrict__ cnt, int64_t m, int64_t* __restrict__ off) {
+    __shared__ int64_t run[SCAN_THREADS];
+    const int64_t per = (m + SCAN_THREADS - 1) / SCAN_THREADS;
+    const int64_t a = min(m, (int64_t)threadIdx.x * per), e = min(m, a + per);
+    int64_t s = 0;
+    for (int64_t i = a; i < e; ++i) s += cnt[i];
+    run[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t acc = 0;
+        for (int i = 0; i < SCAN_THREADS; ++i) {
+            const int64_t v = run[i];
+            run[i] = acc;
+            acc += v;
+        }
+        off[m] = acc;
+    }
+    __syncthreads();
+    s = run[threadIdx.x];
+    for (int64_t i = a; i < e; ++i) {
+        off[i] = s;
+        s += cnt[i];
+    }
+}
+
+// indptr[i] = off[i * splits] for i <= n: a row's first part, and the total at n
+__global__ __launch_bounds__(256) void gr_indptr_kernel(int64_t n, int64_t splits, const int64_t* __restrict__ off, int64_t* __restrict__ indptr) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > n) return;
+    indptr[i] = off[i * splits];
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+
+int check_graph_args(const std::string& f, int64_t n, float threshold, int metric) {
+    if (n < 0 || n >= N_MAX) {
+        set_error(f + ": " + std::to_string(n) + " rows is outside [0, 2^31)");
+        return GNN_ERR_ARG;
+    }
+    if (!std::isfinite(threshold)) {
+        set_error(f + ": threshold " + std::to_string(threshold) + " is outside (-inf, inf): a finite f32 is required");
+        return GNN_ERR_ARG;
+    }
+    return nn_check_metric(f, metric);
+}
+
+uint32_t bits_of(float x) {
+    uint32_t u;
+    std::memcpy(&u, &x, sizeof u);
+    return u;
+}
+
+GraphArgs gr_args(gnn_ctx* ctx, int64_t n, float threshold, int metric) {
+    const NeighbourWorkspace& w = ctx->nn;
+    const GraphWorkspace& g = ctx->gr;
+    GraphArgs a;
+    a.frag = w.bfrag.get();
+    a.valid = w.bvalid.get();
+    a.n = n;
+    a.split_rows = g.split_rows;
+    a.splits = g.splits;
+    a.scale = nn_metric_scale(metric);
+    a.threshold = threshold;
+    a.cnt = g.cnt.get();
+    a.off = g.off.get();
+    a.col = nullptr;
+    a.sim = nullptr;
+    return a;
+}
+
+// n >= 0 rows on the device -> indptr[n + 1] on the device and the total on the host; the ctx's stream is synchronised once.  The
+// workspace then remembers what the fill needs.
+int gr_count(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, float threshold, int metric, int64_t* indptr_dev, int64_t* nnz_host) {
+    NeighbourWorkspace& w = ctx->nn;
+    GraphWorkspace& g = ctx->gr;
+    g.counted = false;
+    g.host_rows = false;
+    g.pass_ms.clear();
+    RoundTimer t_count, t_scan;
+    int64_t total = 0;
+    if (n == 0) {
+        g.split_rows = g.splits = 0;
+        GNN_HIP(hipMemsetAsync(indptr_dev, 0, sizeof(int64_t), ctx->stream));
+    } else {
+        int rc = nn_prepare(ctx, rows_dev, n, metric, w.bfrag, w.bvalid);
+        const int64_t tiles = (n + QT - 1) / QT;
+        if (!rc) rc = nn_tile_grid(ctx, fn, "rows", tiles, n, &g.split_rows, &g.splits);
+        const int64_t m = n * g.splits;
+        if (!rc) rc = nn_reserve(ctx, g.cnt, (size_t)m);
+        if (!rc) rc = nn_reserve(ctx, g.off, (size_t)m + 1);
+        if (rc) return rc;
+        {
+            ProfScope prof(ctx, GNN_K_NEIGHBOURS);
+            t_count = {prof.a, prof.b};
+            GNN_HIP(hipMemsetAsync(g.cnt.get(), 0, (size_t)m * sizeof(int32_t), ctx->stream));
+            hipLaunchKernelGGL(gr_tile_kernel<false>, dim3((unsigned)tiles, (unsigned)g.splits), dim3(256), 0, ctx->stream,
+                               gr_args(ctx, n, threshold, metric));
+            GNN_HIP(hipGetLastError());
+        }
+        {
+            ProfScope prof(ctx, GNN_K_NEIGHBOURS);
+            t_scan = {prof.a, prof.b};
+            hipLaunchKernelGGL(gr_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, g.cnt.get(), m, g.off.get());
+            GNN_HIP(hipGetLastError());
+            if (int rc2 = launch_1d(gr_indptr_kernel, n + 1, ctx->stream, n, g.splits, g.off.get(), indptr_dev)) return rc2;
+        }
+        GNN_HIP(hipMemcpyAsync(&total, g.off.get() + m, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    GNN_HIP(hipStreamSynchronize(ctx->stream));
+    t_count.file(g.pass_ms);               // behind the synchronise
+    t_scan.file(g.pass_ms);
+    g.n = n;
+    g.threshold_bits = bits_of(threshold);
+    g.metric = metric;
+    g.total = total;
+    g.counted = true;
+    *nnz_host = total;
+    return GNN_OK;
+}
+
+// GNN_OK when the fill may run (or has nothing to do), with the total in the workspace
+int gr_check_fill(gnn_ctx* ctx, const std::string& f, int64_t n, float threshold, int metric, int64_t capacity, bool host_rows) {
+    const GraphWorkspace& g = ctx->gr;
+    if (!g.counted || g.n != n || g.threshold_bits != bits_of(threshold) || g.metric != metric || (host_rows && !g.host_rows)) {
+        set_error(f + ": no " + (host_rows ? "gnn_graph_count" : "gnn_graph_count*") + " of the same (n, threshold, metric) = (" +
+                  std::to_string(n) + ", " + std::to_string(threshold) + ", " + std::to_string(metric) + ") came before it" +
+                  (host_rows ? ", or another search has replaced the rows it uploaded" : ""));
+        return GNN_ERR_STATE;
+    }
+    if (capacity < g.total) {
+        set_error(f + ": capacity " + std::to_string(capacity) + " is below the " + std::to_string(g.total) + " edges the count found");
+        return GNN_ERR_ARG;
+    }
+    return GNN_OK;
+}
+
+// total > 0 edges of the counted graph -> col and sim on the device, enqueued on the ctx's stream.  nn_prepare runs again: another
+// search may have used the shared fragment buffers since the count, and it is deterministic.
+int gr_fill(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int metric, int32_t* col_dev, float* sim_dev) {
+    NeighbourWorkspace& w = ctx->nn;
+    const GraphWorkspace& g = ctx->gr;
+    if (int rc = nn_prepare(ctx, rows_dev, n, metric, w.bfrag, w.bvalid)) return rc;
+    ProfScope prof(ctx, GNN_K_NEIGHBOURS);
+    GraphArgs a = gr_args(ctx, n, threshold, metric);
+    a.col = col_dev;
+    a.sim = sim_dev;
+    hipLaunchKernelGGL(gr_tile_kernel<true>, dim3((unsigned)((n + QT - 1) / QT), (unsigned)g.splits), dim3(256), 0, ctx->stream, a);
+    GNN_HIP(hipGetLastError());
+    return GNN_OK;
+}
+
+}  // namespace
+}  // namespace gnn
+
+using namespace gnn;
+
+extern "C" int gnn_graph_count_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int metric, int64_t* indptr_dev,
+                                   int64_t* nnz_host) {
+    const char* const fn = "gnn_graph_count_dev";
+    if (int rc = check_graph_args(fn, n, threshold, metric)) return rc;
+    if ((n > 0 && !rows_dev) || !indptr_dev || !nnz_host) {
+        set_error(std::string("bad argument to ") + fn + ": the rows, indptr and nnz are required");
+        return GNN_ERR_ARG;
+    }
+    if (int rc = check_ctx(ctx)) return rc;
+    return gr_count(ctx, fn, rows_dev, n, threshold, metric, indptr_dev, nnz_host);
+}
+
+extern "C" int gnn_graph_fill_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int metric, int32_t* col_dev, float* sim_dev,
+                                  int64_t capacity) {
+    const char* const fn = "gnn_graph_fill_dev";
+    if (int rc = check_graph_args(fn, n, threshold, metric)) return rc;
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = gr_check_fill(ctx, fn, n, threshold, metric, capacity, false)) return rc;
+    if (ctx->gr.total == 0) return GNN_OK;
+    if (!rows_dev || !col_dev || !sim_dev) {
+        set_error(std::string("bad argument to ") + fn + ": the rows, col and sim are required");
+        return GNN_ERR_ARG;
+    }
+    return gr_fill(ctx, rows_dev, n, threshold, metric, col_dev, sim_dev);
+}
+
+extern "C" int gnn_graph_count(gnn_ctx* ctx, const float* rows_host, int64_t n, float threshold, int metric, int64_t* indptr_host,
+                               int64_t* nnz_host) {
+    const char* const fn = "gnn_graph_count";
+    if (int rc = check_graph_args(fn, n, threshold, metric)) return rc;
+    if ((n > 0 && !rows_host) || !indptr_host || !nnz_host) {
+        set_error(std::string("bad argument to ") + fn + ": the rows, indptr and nnz are required");
+        return GNN_ERR_ARG;
+    }
+    if (int rc = check_ctx(ctx)) return rc;
+    GraphWorkspace& g = ctx->gr;
+    g.counted = false;
+    int rc = nn_reserve(ctx, g.d_indptr, (size_t)n + 1);         // both buffers stand before the copy is enqueued
+    if (!rc) rc = nn_upload_rows(ctx, rows_host, n);
+    if (!rc) rc = gr_count(ctx, fn, ctx->nn.d_base, n, threshold, metric, g.d_indptr, nnz_host);
+    if (rc) return rc;
+    GNN_HIP(hipMemcpyAsync(indptr_host, g.d_indptr.get(), (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    GNN_HIP(hipStreamSynchronize(ctx->stream));
+    g.host_rows = true;
+    return GNN_OK;
+}
+
+extern "C" int gnn_debug_graph_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
+    if (int rc = check_ctx(ctx)) return rc;
+    return nn_round_ms_out("gnn_debug_graph_pass_ms", ctx->gr.pass_ms, ms_out, capacity, n_out);
+}
+
+extern "C" int gnn_graph_fill(gnn_ctx* ctx, int64_t n, float threshold, int metric, int32_t* col_host, float* sim_host, int64_t capacity) {
+    const char* const fn = "gnn_graph_fill";
+    if (int rc = check_graph_args(fn, n, threshold, metric)) return rc;
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = gr_check_fill(ctx, fn, n, threshold, metric, capacity, true)) return rc;
+    GraphWorkspace& g = ctx->gr;
+    const int64_t total = g.total;
+    if (total == 0) return GNN_OK;
+    if (!col_host || !sim_host) {
+        set_error(std::string("bad argument to ") + fn + ": col and sim are required");
+        return GNN_ERR_ARG;
+    }
+    int rc = nn_reserve(ctx, g.d_col, (size_t)total);
+    if (!rc) rc = nn_reserve(ctx, g.d_sim, (size_t)total);
+    if (!rc) rc = gr_fill(ctx, ctx->nn.d_base, n, threshold, metric, g.d_col, g.d_sim);
+    if (rc) return rc;
+    GNN_HIP(hipMemcpyAsync(col_host, g.d_col.get(), (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    GNN_HIP(hipMemcpyAsync(sim_host, g.d_sim.get(), (size_t)total * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    GNN_HIP(hipStreamSynchronize(ctx->stream));
+    return GNN_OK;
+}

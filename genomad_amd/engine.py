@@ -259,6 +259,50 @@ class LinkageResult:
         return cls(a=a, b=b, sim=sim, valid=valid, n=len(valid), n_valid=int(np.count_nonzero(valid)), rounds=int(rounds), metric=str(metric))
 
 
+class GraphResult:
+    """What :meth:`NNEngine.graph` returns (the definition is ``sequence.threshold_graph``): the similarity graph's upper triangle in
+    CSR form - ``indptr`` (int64 (n + 1,)), ``col`` (int32: row i owns ``col[indptr[i]:indptr[i + 1]]``, its partners j > i in
+    ascending order) and ``sim`` (float32, the device's own values) -, ``valid`` (bool (n,): the rows that took part; it cannot be
+    read off the graph), ``n``, ``n_edges``, the ``threshold`` as the float32 it was compared as, and ``metric``."""
+    FIELDS = ("indptr", "col", "sim", "valid", "n", "n_edges", "threshold", "metric")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw.get(k))
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    def edges(self):
+        """COO: (a int64, b int64, sim) with a < b, in the CSR's order"""
+        a, b = _sequence.graph_edges(self.indptr, self.col)
+        return a, b, self.sim
+
+    def degree(self) -> np.ndarray:
+        """int64 (n,), both ends counted: what :meth:`NNEngine.cluster` returns as ``degree``"""
+        return _sequence.graph_degree(self.indptr, self.col)
+
+    def symmetric(self):
+        """the full CSR (indptr int64, col int32, sim): every edge at both its rows, a row's partners ascending"""
+        return _sequence.graph_symmetric(self.indptr, self.col, self.sim)
+
+    def components(self) -> np.ndarray:
+        """int64 (n,): what :meth:`NNEngine.cluster` returns as ``label`` - the smallest index of the row's component, -1 for an
+        invalid row - by a union-find on the host"""
+        return _sequence.graph_components(self.indptr, self.col, self.valid)
+
+    def table(self, names=None):
+        """``sequence.graph_table``: one record per edge - a, b, sim"""
+        return _sequence.graph_table(self.indptr, self.col, self.sim, names)
+
+    @classmethod
+    def build(cls, arrays, valid, threshold, metric):
+        """from the (indptr, col, sim) of ``sequence.threshold_graph`` or the library, and the rows' validity"""
+        indptr, col, sim = arrays
+        return cls(indptr=indptr, col=col, sim=sim, valid=np.asarray(valid, dtype=bool), n=len(indptr) - 1, n_edges=len(col),
+                   threshold=float(_sequence.cluster_threshold(threshold)), metric=str(metric))
+
+
 class NNEngine:
     def __init__(self, device: int = 0, weights: dict = None, chunk: int = None):
         self.lib = _lib.load()
@@ -777,6 +821,57 @@ class NNEngine:
         each), enqueued on the engine's stream."""
         check(self.lib.gnn_cluster_dev(self.ctx, rows_ptr, int(n), float(threshold), self._knn_metric(metric), label_ptr, degree_ptr,
                                        size_ptr, rep_ptr))
+
+    # -- similarity graph ----------------------------------------------------------------
+    def graph(self, rows, threshold, metric="cosine", max_edges=1 << 28) -> GraphResult:
+        """The similarity graph among encoder embeddings (``gnn_graph_count`` + ``gnn_graph_fill``; the definition is
+        ``sequence.threshold_graph``): every pair i < j of valid rows of ``rows`` (n, 512) whose similarity under ``metric`` is >=
+        ``threshold``, with that similarity - the edges :meth:`cluster` joins, kept; exact, two passes over the upper triangle on
+        the matrix pipe.  The similarity of the pair i < j is the float32 :meth:`neighbours` returns for query i and base row j.
+        The count runs first: more than ``max_edges`` edges raise ``ValueError`` before anything is allocated for them (a
+        threshold of -1 on 262 144 rows is 3.4e10 edges).  :meth:`set_neighbour_split` sets the range of this search too; no
+        result depends on it."""
+        r = _sequence.neighbour_rows(rows, "rows")
+        if isinstance(metric, str) and metric not in _lib.KNN_METRICS:
+            raise ValueError(f"metric {metric!r}: expected one of {tuple(_lib.KNN_METRICS)}")
+        code = self._knn_metric(metric)
+        n = len(r)
+        indptr = np.empty(n + 1, dtype=np.int64)
+        total = C.c_int64(0)
+        check(self.lib.gnn_graph_count(self.ctx, r.ctypes.data, n, float(threshold), code, indptr.ctypes.data, C.addressof(total)))
+        m = int(total.value)
+        if m > int(max_edges):
+            raise ValueError(f"the graph has {m} edges at the threshold {float(np.float32(threshold)):g}, more than max_edges = "
+                             f"{int(max_edges)}: raise the threshold or max_edges")
+        col, sim = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float32)
+        check(self.lib.gnn_graph_fill(self.ctx, n, float(threshold), code, col.ctypes.data, sim.ctypes.data, m))
+        name = metric if isinstance(metric, str) else {v: k for k, v in _lib.KNN_METRICS.items()}[code]
+        return GraphResult.build((indptr, col, sim), _sequence.valid_rows(r, name), np.float32(threshold), name)
+
+    def graph_count_dev(self, rows_ptr: int, n: int, threshold, indptr_ptr: int, metric="cosine") -> int:
+        """``gnn_graph_count_dev``: device pointers in (rows n x 512 f32) and out (indptr n + 1 int64); the engine's stream is
+        synchronised once.  Returns the number of edges: what ``col`` and ``sim`` of :meth:`graph_fill_dev` must hold."""
+        total = C.c_int64(0)
+        check(self.lib.gnn_graph_count_dev(self.ctx, rows_ptr, int(n), float(threshold), self._knn_metric(metric), indptr_ptr,
+                                           C.addressof(total)))
+        return int(total.value)
+
+    def graph_fill_dev(self, rows_ptr: int, n: int, threshold, col_ptr, sim_ptr, capacity: int, metric="cosine"):
+        """Asynchronous (``gnn_graph_fill_dev``): the edges of the engine's last :meth:`graph_count_dev`, which must have had the
+        same rows, n, threshold and metric - col (int32) and sim (f32) of ``capacity`` elements each on the device, enqueued on
+        the engine's stream."""
+        check(self.lib.gnn_graph_fill_dev(self.ctx, rows_ptr, int(n), float(threshold), self._knn_metric(metric), col_ptr, sim_ptr,
+                                          int(capacity)))
+
+    def graph_pass_ms(self):
+        """measurement only (``gnn_debug_graph_pass_ms``): with profiling enabled, the HIP-event milliseconds of the last count call's
+        [count pass, scan]"""
+        n = C.c_int64(0)
+        check(self.lib.gnn_debug_graph_pass_ms(self.ctx, None, 0, C.addressof(n)))
+        ms = np.zeros(n.value, np.float64)
+        if n.value:
+            check(self.lib.gnn_debug_graph_pass_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
+        return ms
 
     # -- representatives -----------------------------------------------------------------
     def representatives(self, rows, threshold, weight=None, metric="cosine") -> RepresentativeResult:

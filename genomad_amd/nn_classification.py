@@ -103,6 +103,11 @@ class Outputs:
         self.nn_linkage_tsv_output = d / f"{p}_nn_linkage.tsv"
         self.provirus_nn_linkage_output = d / f"{p}_provirus_nn_linkage.npz"
         self.provirus_nn_linkage_tsv_output = d / f"{p}_provirus_nn_linkage.tsv"
+        # written only when GENOMAD_AMD_GRAPH is set (the similarity graph among the per-contig embeddings; no counterpart in the reference)
+        self.nn_graph_output = d / f"{p}_nn_graph.npz"
+        self.nn_graph_tsv_output = d / f"{p}_nn_graph.tsv"
+        self.provirus_nn_graph_output = d / f"{p}_provirus_nn_graph.npz"
+        self.provirus_nn_graph_tsv_output = d / f"{p}_provirus_nn_graph.tsv"
         f = o / f"{p}_find_proviruses"
         self.find_proviruses_execution_info = f / f"{p}_find_proviruses.json"
         self.find_proviruses_output = f / f"{p}_provirus.tsv"
@@ -698,6 +703,43 @@ def write_linkage(npz_path, tsv_path, names_key, names, res, strand="forward"):
     write_linkage_tsv(tsv_path, names, res)
 
 
+def graph_requested():
+    """GENOMAD_AMD_GRAPH=<float in [-1, 1]>: main() also writes the similarity graph of the contigs - every pair whose per-contig encoder
+    embeddings of GENOMAD_AMD_EMBEDDINGS=1 have at least that cosine similarity, the edges GENOMAD_AMD_CLUSTERS joins at the same value
+    (<prefix>_nn_graph.npz and .tsv); unset or empty: nothing changes (None).  Any other value is an error.  Returns the threshold as
+    it is compared: the float32 it rounds to."""
+    v = os.environ.get("GENOMAD_AMD_GRAPH", "").strip()
+    if not v:
+        return None
+    try:
+        t = float(v)
+    except ValueError:
+        t = float("nan")
+    if not -1.0 <= t <= 1.0:                             # a NaN fails both comparisons
+        raise ValueError(f"GENOMAD_AMD_GRAPH={v!r}: expected a float in [-1, 1] (the cosine similarity at which two contigs share an edge)")
+    return float(np.float32(t))
+
+
+GRAPH_TSV_HEADER = "contig_a\tcontig_b\tsimilarity\n"
+
+
+def write_graph_tsv(path, names, res):
+    """One line per edge of a GraphResult, in its order (rows ascending, a row's partners ascending): the names of the two contigs and
+    their similarity - the label-label-weight ("abc") format graph tools read, behind one header line."""
+    with open(path, "w") as fout:
+        fout.write(GRAPH_TSV_HEADER)
+        for e in res.table(names):
+            fout.write(f"{e['a']}\t{e['b']}\t{e['sim']:.6f}\n")
+
+
+def write_graph(npz_path, tsv_path, names_key, names, res, strand="forward"):
+    """Both graph files of a stage: the arrays of a GraphResult with the contig names, and its edge list."""
+    np.savez_compressed(npz_path, **{names_key: names, "threshold": np.float64(res.threshold), "metric": np.array(res.metric),
+                                     "indptr": res.indptr, "col": res.col, "sim": res.sim,
+                                     **({"strand": np.array(strand)} if strand != "forward" else {})})
+    write_graph_tsv(tsv_path, names, res)
+
+
 REGION_TSV_HEADER = ("seq_name\tstart\tend\tclass\tn_bins\tevidence_bins\t"
                      + "\t".join("mean_" + c[:-len("_score")] for c in TSV_HEADER.split()[1:]) + "\tmargin\n")
 
@@ -892,6 +934,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     clusters_threshold = clusters_requested()
     representatives_threshold = representatives_requested()
     linkage = linkage_requested()
+    graph_threshold = graph_requested()
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -941,6 +984,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     if linkage and not embeddings:
         console.error("GENOMAD_AMD_LINKAGE needs GENOMAD_AMD_EMBEDDINGS=1: the tree is built among the per-contig encoder "
                       "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_LINKAGE.")
+        sys.exit(1)
+    if graph_threshold is not None and not embeddings:
+        console.error("GENOMAD_AMD_GRAPH needs GENOMAD_AMD_EMBEDDINGS=1: the graph's edges are found among the per-contig encoder "
+                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_GRAPH.")
         sys.exit(1)
 
     if strand != "forward" and not device_front_end:
@@ -1130,6 +1177,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         ``linkage_paths`` (npz, tsv; GENOMAD_AMD_LINKAGE=1, which needs the embeddings): rank 0 builds the single-linkage tree
         (NNEngine.linkage, cosine) of the same gathered embeddings and writes both files.  They are there iff they were asked for,
         in the strand mode asked for; otherwise the stage runs again.
+        ``graph_files[what]`` (npz, tsv; GENOMAD_AMD_GRAPH, which needs the embeddings): rank 0 lists the edges (NNEngine.graph, cosine)
+        of the same gathered embeddings and writes both files.  They follow the clusters files' rule.
         ``region_emb_path`` (GENOMAD_AMD_REGION_EMBEDDINGS=1, which needs the regions): right after a piece's scan, while its
         sequence is in memory, the piece's own track is segmented (regions are per contig and exact integers: they are the ones
         rank 0 calls on the gathered track, which rank 0 checks) and NNEngine.embed_intervals folds the scan windows' encoder
@@ -1140,6 +1189,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         clusters_path, clusters_tsv_path = clusters_paths
         representatives_path, representatives_tsv_path = representatives_paths
         linkage_path, linkage_tsv_path = linkage_paths
+        graph_path, graph_tsv_path = graph_files[what]
         regions_path, regions_tsv_path = regions_paths
         regions_request = None if region_penalty is None else (scan_stride, region_penalty)
         (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and _strand_of_file(strand_path) == strand
@@ -1158,6 +1208,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                  and (representatives_threshold is None or _npz_strand(representatives_path) == strand)
                                  and linkage == linkage_path.exists() == linkage_tsv_path.exists()
                                  and (not linkage or _npz_strand(linkage_path) == strand)
+                                 and _clusters_of_file(graph_path) == graph_threshold
+                                 and (graph_threshold is None) == (not graph_tsv_path.exists())
+                                 and (graph_threshold is None or _npz_strand(graph_path) == strand)
                                  and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
                                  and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
                                                             and _npz_strand(scan_path) == strand)))   # :284-292
@@ -1386,6 +1439,20 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     for p in (linkage_path, linkage_tsv_path):
                         if p.exists():
                             p.unlink()
+                if graph_threshold is not None:
+                    try:
+                        res = eng.graph(embeddings_all, graph_threshold, NEIGHBOUR_METRIC)
+                    except ValueError as e:         # more edges than NNEngine.graph's cap: nothing was allocated for them
+                        console.error(f"GENOMAD_AMD_GRAPH={graph_threshold:g}: {e}. Raise GENOMAD_AMD_GRAPH or unset it.")
+                        sys.exit(1)
+                    write_graph(graph_path, graph_tsv_path, names_key, names, res, strand)
+                    console.log(f"Similarity graph of the {what}s ({NEIGHBOUR_METRIC} similarity of the encoder embeddings >= "
+                                f"{graph_threshold:g}: {res.n_edges} edges among {int(res.valid.sum())} {what}s) written to "
+                                f"{graph_path.name} and {graph_tsv_path.name}.")
+                else:                               # likewise, both files
+                    for p in (graph_path, graph_tsv_path):
+                        if p.exists():
+                            p.unlink()
         if cleanup and rank0 and enc_dir.is_dir():
             console.log(f"Deleting encoded {what} data.")
             shutil.rmtree(enc_dir)
@@ -1394,6 +1461,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
 
     run = stage_device if device_front_end else stage
     region_emb_default = {"sequence": outputs.nn_region_embeddings_output, "provirus": outputs.provirus_nn_region_embeddings_output}
+    graph_files = {"sequence": (outputs.nn_graph_output, outputs.nn_graph_tsv_output),
+                   "provirus": (outputs.provirus_nn_graph_output, outputs.provirus_nn_graph_tsv_output)}
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
     scan_kw = (lambda path: {"scan_path": path}) if scan_stride is not None else (lambda path: {})
     region_emb_kw = (lambda path: {"region_emb_path": path}) if region_embeddings else (lambda path: {})

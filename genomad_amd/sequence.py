@@ -812,6 +812,101 @@ def threshold_clusters(rows, threshold, metric="cosine"):
     return label, degree, size, rep
 
 
+def threshold_graph(rows, threshold, metric="cosine"):
+    """The similarity graph among encoder embeddings, spelled out (the definition ``gnn_graph_count`` / ``gnn_graph_fill`` compute on
+    the device; float64 throughout, readable, not fast, n x n): the edges :func:`threshold_clusters` joins, kept.  ``rows`` (n, 512)
+    float32; validity, ``metric`` and the threshold as there, and the same adjacency - an edge {i, j} iff both rows are valid and
+    sim(i, j) or sim(j, i) >= the float32 ``threshold`` rounds to.  Returns the upper triangle in CSR form: ``indptr`` (int64, n + 1),
+    ``col`` (int32: row i owns ``col[indptr[i]:indptr[i + 1]]``, its partners j > i in ascending order; an invalid row owns nothing)
+    and ``sim`` (float64: r[i] . r[j])."""
+    if metric not in NEIGHBOUR_METRICS:
+        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    r32 = neighbour_rows(rows, "rows")
+    thr = float(cluster_threshold(threshold))
+    n = len(r32)
+    ok = np.isfinite(r32).all(axis=1)
+    r = np.where(ok[:, None], r32, 0).astype(np.float64)
+    if metric == "cosine":
+        norm = np.sqrt((r * r).sum(axis=1))
+        ok &= norm > 0
+        r = r / np.where(ok, norm, 1.0)[:, None]
+    s = r @ r.T
+    adj = (s >= thr) & ok[:, None] & ok[None, :]
+    adj |= adj.T                        # as threshold_clusters: an edge either way is an edge
+    upper = np.triu(adj, 1)
+    a, b = np.nonzero(upper)            # row-major: rows in order, a row's columns ascending
+    indptr = np.concatenate([[0], np.cumsum(upper.sum(axis=1))]).astype(np.int64)
+    return indptr, b.astype(np.int32), s[a, b].astype(np.float64)
+
+
+def valid_rows(rows, metric="cosine") -> np.ndarray:
+    """bool (n,): the rows a search over encoder embeddings takes part with - every element finite and, under ``cosine``, a norm
+    > 0 (:func:`nearest_neighbours`)"""
+    if metric not in NEIGHBOUR_METRICS:
+        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    r32 = neighbour_rows(rows, "rows")
+    ok = np.isfinite(r32).all(axis=1)
+    if metric == "cosine":
+        r = np.where(ok[:, None], r32, 0).astype(np.float64)
+        ok &= np.sqrt((r * r).sum(axis=1)) > 0
+    return ok
+
+
+def graph_edges(indptr, col):
+    """(a, b) int64 of an upper-triangle CSR: edge e joins rows a[e] < b[e], in the CSR's order"""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    a = np.repeat(np.arange(len(indptr) - 1, dtype=np.int64), np.diff(indptr))
+    return a, np.asarray(col, dtype=np.int64)
+
+
+def graph_degree(indptr, col) -> np.ndarray:
+    """int64 (n,): the edges at every row, both ends counted - the ``degree`` of :func:`threshold_clusters`"""
+    a, b = graph_edges(indptr, col)
+    n = len(indptr) - 1
+    return (np.bincount(a, minlength=n) + np.bincount(b, minlength=n)).astype(np.int64)
+
+
+def graph_symmetric(indptr, col, sim):
+    """The full CSR of an upper-triangle one: (indptr int64, col int32, sim) with every edge at both its rows, a row's partners
+    ascending."""
+    a, b = graph_edges(indptr, col)
+    n = len(indptr) - 1
+    sim = np.asarray(sim)
+    src, dst = np.concatenate([a, b]), np.concatenate([b, a])
+    order = np.lexsort((dst, src))
+    full = np.concatenate([[0], np.cumsum(np.bincount(src, minlength=n))]).astype(np.int64)
+    return full, dst[order].astype(np.int32), np.concatenate([sim, sim])[order]
+
+
+def graph_components(indptr, col, valid) -> np.ndarray:
+    """int64 (n,): the smallest index of every row's connected component, -1 where ``valid`` is false - the ``label`` of
+    :func:`threshold_clusters`.  A union-find whose links point to the smaller index, edge by edge."""
+    a, b = graph_edges(indptr, col)
+    n = len(indptr) - 1
+    parent = list(range(n))
+
+    def root(x):
+        while parent[x] != x:           # ends: a link points to a smaller index
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    for u, v in zip(a.tolist(), b.tolist()):
+        u, v = root(u), root(v)
+        if u != v:
+            parent[max(u, v)] = min(u, v)
+    label = np.fromiter((root(i) for i in range(n)), dtype=np.int64, count=n)
+    return np.where(np.asarray(valid, dtype=bool), label, -1)
+
+
+def graph_table(indptr, col, sim, names=None):
+    """One record per edge of an upper-triangle CSR, in its order: ``a`` < ``b`` (indices; the names where ``names`` is given) and
+    ``sim``."""
+    a, b = graph_edges(indptr, col)
+    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    return [{"a": name(i), "b": name(j), "sim": float(s)} for i, j, s in zip(a, b, np.asarray(sim))]
+
+
 def cluster_table(result, names=None):
     """One record per cluster of a :func:`threshold_clusters` result (the four arrays, a dict of them, or anything with them as
     attributes), ordered by label: ``label``, ``size``, ``rep``, ``members`` (their indices in ascending order; the names where

@@ -694,6 +694,47 @@ int gnn_linkage_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, int metric, 
  * added no edge) of the ctx's last gnn_linkage* call; *n_out = the rounds recorded, at most `capacity` of them are written. */
 int gnn_debug_linkage_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
 
+/* ---- similarity graph among encoder embeddings: every pair above a threshold --------------------------------
+ * "Which pairs are the edges": the thresholded similarity graph that gnn_cluster acts on and throws away, kept - every pair i < j of
+ * valid rows with sim(i, j) >= threshold and its similarity, as a CSR over the upper triangle.  Rows, validity, metric and threshold
+ * are those of gnn_cluster; no forward pass runs and no other entry point's result changes.
+ *   value     the similarity of the pair i < j is the f32 that gnn_neighbours returns for query i and base row j (the same fragments,
+ *             k-steps, order and scale as gnn_cluster); (j, i) is never computed.  The threshold is compared as the f32 given; a tie
+ *             is an edge; a similarity that is not a number is none.
+ *   outputs   indptr (int64 [n + 1]): row i owns col[indptr[i] .. indptr[i + 1]), its partners j > i in ascending order, and
+ *             sim[...], their similarities; an invalid row owns nothing and is nobody's partner.  col is int32 (n < 2^31), sim f32.
+ *             The degree of gnn_cluster counts an edge at both ends: here it stands once, at its smaller row.
+ *   passes    count: one pass over the upper triangle that counts every row's edges per base range, a prefix sum, indptr and the
+ *             total (*nnz_host; the stream is synchronised once to hand it back).  fill: a second pass that computes the same
+ *             products and writes every edge to its place; base ranges without an edge at a tile's rows are skipped.  The caller
+ *             sizes col and sim between the two.  The fill belongs to the ctx's LAST count: GNN_ERR_STATE unless that count had
+ *             the same (n, threshold, metric).  The rows must be the same; if they changed, the result is garbage, but no store
+ *             leaves a row's segment.
+ *   ranges    0 <= n < 2^31, a finite threshold, a metric in [0, 1]; GNN_ERR_ARG with the value and the range in the message - checked
+ *             before the ctx is looked at.  n == 0: indptr = [0], *nnz_host = 0.  capacity < the total: GNN_ERR_ARG with both numbers.
+ *             A total of 0: the fill launches nothing and col and sim may be NULL.
+ *   exact     a counter has one owner workgroup, the offsets are integer prefix sums, an edge's place follows from its row, base
+ *             range, step, wave, column block and lane: no atomics in global memory, bit-identical for every split of the base
+ *             (gnn_debug_set_neighbour_split sets the range for this search too).
+ * What it is not: not approximate; not bipartite (query rows against other base rows); no width other than GNN_EMBED_DIM; not
+ * multi-GPU.  The edge list is as large as the threshold makes it - n (n - 1) / 2 at -1: look at *nnz_host before allocating.
+ * Device memory, persistent in the ctx and grow-only: the 2 KB of fragments + 1 B per row of the neighbour search (shared with it;
+ * gnn_graph_count: + the row's 2 KB of f32), 12 B per (row, base range) of counters and offsets (gnn_graph_count: + 8 B per row;
+ * gnn_graph_fill: + 8 B per edge).  Nothing is n x n.
+ * gnn_graph_count / gnn_graph_fill: host pointers, synchronous; the fill uses the rows its count uploaded and answers GNN_ERR_STATE
+ * when another host-pointer search has replaced them.  gnn_graph_count_dev: device pointers, *nnz_host on the host.
+ * gnn_graph_fill_dev: device pointers, asynchronous on the ctx stream like gnn_classify_dev. */
+int gnn_graph_count(gnn_ctx* ctx, const float* rows_host, int64_t n, float threshold, int metric, int64_t* indptr_host, int64_t* nnz_host);
+int gnn_graph_fill(gnn_ctx* ctx, int64_t n, float threshold, int metric, int32_t* col_host, float* sim_host, int64_t capacity);
+int gnn_graph_count_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int metric, int64_t* indptr_dev,
+                        int64_t* nnz_host);
+int gnn_graph_fill_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int metric, int32_t* col_dev, float* sim_dev,
+                       int64_t capacity);
+/* measurement only: with gnn_profile_enable on, the HIP-event milliseconds of the ctx's last gnn_graph_count* call: [0] the clear and
+ * the count pass, [1] the scan and indptr; *n_out = the figures recorded (2, or 0 for n == 0 or without profiling), at most `capacity`
+ * of them are written.  The prepare kernel and the fill are timed from outside, by gnn_profile_get around the calls. */
+int gnn_debug_graph_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
+
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
  * in-memory text buffer (already decompressed, newlines normalised to '\n').
