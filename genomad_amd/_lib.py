@@ -140,6 +140,11 @@ SIGNATURES = {
     "gnn_graph_count_dev": (_int, [_vp, _vp, _i64, C.c_float, _int, _vp, _vp]),
     "gnn_graph_fill_dev": (_int, [_vp, _vp, _i64, C.c_float, _int, _vp, _vp, _i64]),
     "gnn_debug_graph_pass_ms": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_match_count": (_int, [_vp, _vp, _i64, _vp, _i64, C.c_float, _int, _vp, _vp]),
+    "gnn_match_fill": (_int, [_vp, _i64, _i64, C.c_float, _int, _vp, _vp, _i64]),
+    "gnn_match_count_dev": (_int, [_vp, _vp, _i64, _vp, _i64, C.c_float, _int, _vp, _vp]),
+    "gnn_match_fill_dev": (_int, [_vp, _vp, _i64, _vp, _i64, C.c_float, _int, _vp, _vp, _i64]),
+    "gnn_debug_match_pass_ms": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_embed": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_embed_dev": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_debug_forward": (_int, [_vp, _vp, _i64, _int, _vp, C.POINTER(Taps)]),

@@ -175,7 +175,8 @@ struct IntervalWorkspace {
 
 // ---- nearest neighbours (gnn_neighbours.hip): persistent, grow-only.  Per base row 2 KB of f16 fragments + 1 B flag (and, for the
 // host entry point, its 2 KB of f32); per query row of ONE slab of 16384 the same, 8 k B per base range of partial lists and 12 k B
-// of results.  Nothing grows with the number of queries.
+// of results.  Nothing of the neighbour search grows with the number of queries; the match (gnn_graph.hip) prepares all its query rows
+// at once into qfrag / qvalid.
 struct NeighbourWorkspace {
     int64_t split = 0;                           // base rows per workgroup (gnn_debug_set_neighbour_split); 0: the library's choice
     DevBuf<uint4> bfrag, qfrag;                  // [32-row block][k-step 32][hi | lo][lane 64] x 16 B
@@ -248,17 +249,22 @@ struct LinkageWorkspace {
 // ---- similarity graph (gnn_graph.hip): persistent, grow-only.  The fragments and flags are NeighbourWorkspace's bfrag / bvalid (and
 // d_base for the host entry points); here 12 B per (row, base range) of counters and offsets and, for gnn_graph_count / gnn_graph_fill
 // alone, 8 B per row and 8 B per edge of results.  Nothing is n x n.
+// The match (gnn_match_*: the same passes over the rectangle query x base) shares all of it - a fill belongs to the ctx's last count of
+// either kind - and prepares ALL its query rows at once into NeighbourWorkspace's qfrag / qvalid: 2 KB + 1 B per query row, 12 B per
+// (query row, base range) of counters and offsets and, for gnn_match_count / gnn_match_fill alone, the query's 2 KB of f32 per row.
 struct GraphWorkspace {
     DevBuf<int32_t> cnt;                         // [n * splits]: the edges of row i among the columns of range p, at i * splits + p
     DevBuf<int64_t> off;                         // [n * splits + 1]: their exclusive prefix sums, then the total
     // what the last count call ran with: the fill runs the same grid, and answers GNN_ERR_STATE for another (n, threshold, metric)
     bool counted = false;
-    int64_t n = 0;
+    bool rect = false;                           // it was a gnn_match_count*: n query rows against nb base rows
+    int64_t n = 0, nb = 0;                       // the graph: nb = n
     uint32_t threshold_bits = 0;
     int metric = 0;
     int64_t split_rows = 0, splits = 0;
     int64_t total = 0;                           // edges
-    bool host_rows = false;                      // NeighbourWorkspace's d_base still holds the rows gnn_graph_count uploaded
+    bool host_rows = false;                      // NeighbourWorkspace's d_base still holds the rows gnn_graph_count / gnn_match_count uploaded
+    DevBuf<float> d_query;                       // gnn_match_count: the query's rows - the match's own, no other search writes here
     DevBuf<int64_t> d_indptr;                    // gnn_graph_count: [n + 1]
     DevBuf<int32_t> d_col;                       // gnn_graph_fill: [total]
     DevBuf<float> d_sim;

@@ -19,6 +19,14 @@
 //              fill give garbage, never an overrun.
 // No atomics in global memory, no position that depends on the order workgroups or waves run in: bit-identical for every split of the
 // base.  No loop here waits for another workgroup: every loop's termination argument stands next to it.
+//
+// The match (include/genomad_nn.h, "matches against a reference") is the same kernel over the RECTANGLE query x
+// base (gr_tile_kernel<., true>): the tile's fragments and flags are the query's (NeighbourWorkspace's qfrag / qvalid), the columns the
+// base's, the ranges those of nn_tile_range(..., upper = false), the edge rule `rok && cg >= 0 && s >= threshold` - no pair is left
+// out, the value of (i, j) is the f32 gnn_neighbours returns for query i and base row j - and the counters sit at cnt[row * splits +
+// part] for row < n_query.  Products, scale, ballots, placement, segment guard, early exit, scan and indptr are the lines above.
+// Memory: all query rows are prepared at once, with no slabs - 2 KB of fragments + 1 B per query row - and 12 B per (query row, base
+// range) of counters and offsets; the workspace is the graph's, so a fill belongs to the ctx's last count of either kind.
 #include <cmath>
 #include <cstring>
 
@@ -31,9 +39,9 @@ constexpr int64_t N_MAX = (int64_t)1 << 31;      // columns are int32
 constexpr int SCAN_THREADS = 1024;               // the one block that scans the counters
 
 struct GraphArgs {
-    const uint4* frag;         // round_up(n, 64) / 32 blocks: rows and columns alike
+    const uint4* frag;         // round_up(n, 64) / 32 blocks: rows and columns alike; rectangle: the query's, the tile's rows only
     const uint8_t* valid;      // [round_up(n, 64)]
-    int64_t n;
+    int64_t n;                 // rows; rectangle: n_query
     int64_t split_rows;        // base rows per workgroup: a multiple of 32
     int64_t splits;            // = gridDim.y
     float scale;               // 2^-16 for cosine, 1 for dot
@@ -42,12 +50,18 @@ struct GraphArgs {
     const int64_t* off;        // fill: [n * splits + 1]
     int32_t* col;              // fill: [off[n * splits]]
     float* sim;
+    // the rectangle alone, behind everything the upper triangle reads: the columns' fragments, flags and number
+    const uint4* bfrag;        // round_up(nb, 64) / 32 blocks
+    const uint8_t* bvalid;     // [round_up(nb, 64)]
+    int64_t nb;                // n_base
 };
 
 // grid = (row tiles, base ranges), 256 threads.  LDS: the tile's fragments 128 KB, its rows' flags and counts or positions.
 // FILL false: the count pass.  FILL true: the fill pass - there every thread reaches the same barriers: the step loop's bounds and
 // the vote behind the products are the same in the whole workgroup.
-template <bool FILL>
+// RECT false: the upper triangle among one set of rows (the graph).  RECT true: the rectangle (the match) - the tile's rows are the
+// query's, the columns the base's, every pair of valid rows is a candidate; the ranges run over the base, none is empty.
+template <bool FILL, bool RECT>
 __global__ __launch_bounds__(256) void gr_tile_kernel(GraphArgs a) {
     __shared__ uint4 qs[2 * BLK_U4];
     __shared__ uint8_t lok[QT];
@@ -56,7 +70,9 @@ __global__ __launch_bounds__(256) void gr_tile_kernel(GraphArgs a) {
     __shared__ int wcnt[4][QT];            // fill: the step's edges per wave and row
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
     TileRange t;
-    if (!nn_tile_range(t, a.split_rows, a.n, true)) return;
+    const uint4* const cfrag = RECT ? a.bfrag : a.frag;        // where the columns come from
+    const uint8_t* const cvalid = RECT ? a.bvalid : a.valid;
+    if (!nn_tile_range(t, a.split_rows, RECT ? a.nb : a.n, !RECT)) return;
     const int64_t r0 = t.r0;
     if (FILL) {
         int64_t p = 0, e = 0;
@@ -84,8 +100,8 @@ __global__ __launch_bounds__(256) void gr_tile_kernel(GraphArgs a) {
         int cg[2];                         // the lane's column, -1: no edge can end there
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
-            const int64_t col = nn_step_column(a.frag, c0, wave, lane, nb, last_blk, bp[nb]);
-            cg[nb] = col < t.b1 && a.valid[col] ? (int)col : -1;
+            const int64_t col = nn_step_column(cfrag, c0, wave, lane, nb, last_blk, bp[nb]);
+            cg[nb] = col < t.b1 && cvalid[col] ? (int)col : -1;
         }
         f32x16 acc[2][2];
         NN_PRODUCTS(qs, bp, lane, acc);
@@ -101,7 +117,8 @@ __global__ __launch_bounds__(256) void gr_tile_kernel(GraphArgs a) {
 #pragma unroll
                 for (int nb = 0; nb < 2; ++nb) {
                     const float s = acc[mb][nb][r] * a.scale;
-                    const bool e = rok && rg < cg[nb] && s >= a.threshold;          // cg = -1 fails rg < cg; a NaN fails >=
+                    // cg = -1 fails rg < cg; a NaN fails >=.  The rectangle has no row < col: (i, i) and both orientations count
+                    const bool e = rok && (RECT ? cg[nb] >= 0 : rg < cg[nb]) && s >= a.threshold;
                     edge |= (unsigned long long)e << ((mb * 2 + nb) * 16 + r);
                 }
             }
@@ -200,16 +217,32 @@ __global__ __launch_bounds__(256) void gr_indptr_kernel(int64_t n, int64_t split
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 
-int check_graph_args(const std::string& f, int64_t n, float threshold, int metric) {
-    if (n < 0 || n >= N_MAX) {
-        set_error(f + ": " + std::to_string(n) + " rows is outside [0, 2^31)");
-        return GNN_ERR_ARG;
-    }
+int check_threshold_metric(const std::string& f, float threshold, int metric) {
     if (!std::isfinite(threshold)) {
         set_error(f + ": threshold " + std::to_string(threshold) + " is outside (-inf, inf): a finite f32 is required");
         return GNN_ERR_ARG;
     }
     return nn_check_metric(f, metric);
+}
+
+int check_graph_args(const std::string& f, int64_t n, float threshold, int metric) {
+    if (n < 0 || n >= N_MAX) {
+        set_error(f + ": " + std::to_string(n) + " rows is outside [0, 2^31)");
+        return GNN_ERR_ARG;
+    }
+    return check_threshold_metric(f, threshold, metric);
+}
+
+int check_match_args(const std::string& f, int64_t nq, int64_t nb, float threshold, int metric) {
+    if (nq < 0 || nq >= N_MAX) {
+        set_error(f + ": n_query " + std::to_string(nq) + " is outside [0, 2^31)");
+        return GNN_ERR_ARG;
+    }
+    if (nb < 0 || nb >= N_MAX) {
+        set_error(f + ": n_base " + std::to_string(nb) + " is outside [0, 2^31)");
+        return GNN_ERR_ARG;
+    }
+    return check_threshold_metric(f, threshold, metric);
 }
 
 uint32_t bits_of(float x) {
@@ -218,13 +251,14 @@ uint32_t bits_of(float x) {
     return u;
 }
 
-GraphArgs gr_args(gnn_ctx* ctx, int64_t n, float threshold, int metric) {
+// what both passes of the counted search run with; g.rect: the rectangle (n = n_query rows against g.nb base rows)
+GraphArgs gr_args(gnn_ctx* ctx, float threshold, int metric) {
     const NeighbourWorkspace& w = ctx->nn;
     const GraphWorkspace& g = ctx->gr;
     GraphArgs a;
-    a.frag = w.bfrag.get();
-    a.valid = w.bvalid.get();
-    a.n = n;
+    a.frag = g.rect ? w.qfrag.get() : w.bfrag.get();
+    a.valid = g.rect ? w.qvalid.get() : w.bvalid.get();
+    a.n = g.n;
     a.split_rows = g.split_rows;
     a.splits = g.splits;
     a.scale = nn_metric_scale(metric);
@@ -233,26 +267,43 @@ GraphArgs gr_args(gnn_ctx* ctx, int64_t n, float threshold, int metric) {
     a.off = g.off.get();
     a.col = nullptr;
     a.sim = nullptr;
+    a.bfrag = w.bfrag.get();
+    a.bvalid = w.bvalid.get();
+    a.nb = g.nb;
     return a;
 }
 
-// n >= 0 rows on the device -> indptr[n + 1] on the device and the total on the host; the ctx's stream is synchronised once.  The
-// workspace then remembers what the fill needs.
-int gr_count(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, float threshold, int metric, int64_t* indptr_dev, int64_t* nnz_host) {
+// The fragments and flags of the counted search, for either pass.  The graph: its rows in the base's buffers.  The match: the base
+// there, and ALL query rows at once in the query's buffers (no slabs: 2 KB + 1 B per query row).
+int gr_prepare(gnn_ctx* ctx, const float* rows_dev, const float* base_dev, int metric) {
     NeighbourWorkspace& w = ctx->nn;
+    const GraphWorkspace& g = ctx->gr;
+    if (!g.rect) return nn_prepare(ctx, rows_dev, g.n, metric, w.bfrag, w.bvalid);
+    if (int rc = nn_prepare(ctx, base_dev, g.nb, metric, w.bfrag, w.bvalid)) return rc;
+    return nn_prepare(ctx, rows_dev, g.n, metric, w.qfrag, w.qvalid);
+}
+
+// n >= 0 rows on the device -> indptr[n + 1] on the device and the total on the host; the ctx's stream is synchronised once.  The
+// workspace then remembers what the fill needs.  rect: the n rows are queries against the nb rows of base_dev (the match); otherwise
+// the upper triangle among the n rows (the graph; base_dev and nb are not looked at).
+int gr_count(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, const float* base_dev, int64_t nb, bool rect, float threshold,
+             int metric, int64_t* indptr_dev, int64_t* nnz_host) {
     GraphWorkspace& g = ctx->gr;
     g.counted = false;
     g.host_rows = false;
     g.pass_ms.clear();
+    g.rect = rect;
+    g.n = n;
+    g.nb = rect ? nb : n;
     RoundTimer t_count, t_scan;
     int64_t total = 0;
-    if (n == 0) {
+    if (n == 0 || g.nb == 0) {             // an empty side launches nothing
         g.split_rows = g.splits = 0;
-        GNN_HIP(hipMemsetAsync(indptr_dev, 0, sizeof(int64_t), ctx->stream));
+        GNN_HIP(hipMemsetAsync(indptr_dev, 0, (size_t)(n + 1) * sizeof(int64_t), ctx->stream));
     } else {
-        int rc = nn_prepare(ctx, rows_dev, n, metric, w.bfrag, w.bvalid);
+        int rc = gr_prepare(ctx, rows_dev, base_dev, metric);
         const int64_t tiles = (n + QT - 1) / QT;
-        if (!rc) rc = nn_tile_grid(ctx, fn, "rows", tiles, n, &g.split_rows, &g.splits);
+        if (!rc) rc = nn_tile_grid(ctx, fn, rect ? "base rows" : "rows", tiles, g.nb, &g.split_rows, &g.splits);
         const int64_t m = n * g.splits;
         if (!rc) rc = nn_reserve(ctx, g.cnt, (size_t)m);
         if (!rc) rc = nn_reserve(ctx, g.off, (size_t)m + 1);
@@ -261,8 +312,8 @@ int gr_count(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, flo
             ProfScope prof(ctx, GNN_K_NEIGHBOURS);
             t_count = {prof.a, prof.b};
             GNN_HIP(hipMemsetAsync(g.cnt.get(), 0, (size_t)m * sizeof(int32_t), ctx->stream));
-            hipLaunchKernelGGL(gr_tile_kernel<false>, dim3((unsigned)tiles, (unsigned)g.splits), dim3(256), 0, ctx->stream,
-                               gr_args(ctx, n, threshold, metric));
+            void (*const kernel)(GraphArgs) = rect ? gr_tile_kernel<false, true> : gr_tile_kernel<false, false>;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)tiles, (unsigned)g.splits), dim3(256), 0, ctx->stream, gr_args(ctx, threshold, metric));
             GNN_HIP(hipGetLastError());
         }
         {
@@ -277,7 +328,6 @@ int gr_count(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, flo
     GNN_HIP(hipStreamSynchronize(ctx->stream));
     t_count.file(g.pass_ms);               // behind the synchronise
     t_scan.file(g.pass_ms);
-    g.n = n;
     g.threshold_bits = bits_of(threshold);
     g.metric = metric;
     g.total = total;
@@ -286,13 +336,18 @@ int gr_count(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, flo
     return GNN_OK;
 }
 
-// GNN_OK when the fill may run (or has nothing to do), with the total in the workspace
-int gr_check_fill(gnn_ctx* ctx, const std::string& f, int64_t n, float threshold, int metric, int64_t capacity, bool host_rows) {
+// GNN_OK when the fill may run (or has nothing to do), with the total in the workspace.  A fill belongs to the ctx's last count, of
+// its own kind: rect - a gnn_match_count* of the same (n, nb, ...); otherwise a gnn_graph_count* of the same (n, ...).
+int gr_check_fill(gnn_ctx* ctx, const std::string& f, int64_t n, int64_t nb, bool rect, float threshold, int metric, int64_t capacity,
+                  bool host_rows) {
     const GraphWorkspace& g = ctx->gr;
-    if (!g.counted || g.n != n || g.threshold_bits != bits_of(threshold) || g.metric != metric || (host_rows && !g.host_rows)) {
-        set_error(f + ": no " + (host_rows ? "gnn_graph_count" : "gnn_graph_count*") + " of the same (n, threshold, metric) = (" +
-                  std::to_string(n) + ", " + std::to_string(threshold) + ", " + std::to_string(metric) + ") came before it" +
-                  (host_rows ? ", or another search has replaced the rows it uploaded" : ""));
+    if (!g.counted || g.rect != rect || g.n != n || (rect && g.nb != nb) || g.threshold_bits != bits_of(threshold) || g.metric != metric ||
+        (host_rows && !g.host_rows)) {
+        const std::string count = std::string(rect ? "gnn_match_count" : "gnn_graph_count") + (host_rows ? "" : "*");
+        const std::string what = rect ? "(n_query, n_base, threshold, metric) = (" + std::to_string(n) + ", " + std::to_string(nb) + ", "
+                                      : "(n, threshold, metric) = (" + std::to_string(n) + ", ";
+        set_error(f + ": no " + count + " of the same " + what + std::to_string(threshold) + ", " + std::to_string(metric) +
+                  ") came before it" + (host_rows ? ", or another search has replaced the rows it uploaded" : ""));
         return GNN_ERR_STATE;
     }
     if (capacity < g.total) {
@@ -302,18 +357,37 @@ int gr_check_fill(gnn_ctx* ctx, const std::string& f, int64_t n, float threshold
     return GNN_OK;
 }
 
-// total > 0 edges of the counted graph -> col and sim on the device, enqueued on the ctx's stream.  nn_prepare runs again: another
+// total > 0 edges of the counted search -> col and sim on the device, enqueued on the ctx's stream.  The prepare runs again: another
 // search may have used the shared fragment buffers since the count, and it is deterministic.
-int gr_fill(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int metric, int32_t* col_dev, float* sim_dev) {
-    NeighbourWorkspace& w = ctx->nn;
+int gr_fill(gnn_ctx* ctx, const float* rows_dev, const float* base_dev, float threshold, int metric, int32_t* col_dev, float* sim_dev) {
     const GraphWorkspace& g = ctx->gr;
-    if (int rc = nn_prepare(ctx, rows_dev, n, metric, w.bfrag, w.bvalid)) return rc;
+    if (int rc = gr_prepare(ctx, rows_dev, base_dev, metric)) return rc;
     ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-    GraphArgs a = gr_args(ctx, n, threshold, metric);
+    GraphArgs a = gr_args(ctx, threshold, metric);
     a.col = col_dev;
     a.sim = sim_dev;
-    hipLaunchKernelGGL(gr_tile_kernel<true>, dim3((unsigned)((n + QT - 1) / QT), (unsigned)g.splits), dim3(256), 0, ctx->stream, a);
+    void (*const kernel)(GraphArgs) = g.rect ? gr_tile_kernel<true, true> : gr_tile_kernel<true, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((g.n + QT - 1) / QT), (unsigned)g.splits), dim3(256), 0, ctx->stream, a);
     GNN_HIP(hipGetLastError());
+    return GNN_OK;
+}
+
+// the host fill of either kind, behind its checks: the edges land in the ctx's buffers, are copied out and waited for
+int gr_fill_host(gnn_ctx* ctx, const char* fn, float threshold, int metric, int32_t* col_host, float* sim_host) {
+    GraphWorkspace& g = ctx->gr;
+    const int64_t total = g.total;
+    if (total == 0) return GNN_OK;
+    if (!col_host || !sim_host) {
+        set_error(std::string("bad argument to ") + fn + ": col and sim are required");
+        return GNN_ERR_ARG;
+    }
+    int rc = nn_reserve(ctx, g.d_col, (size_t)total);
+    if (!rc) rc = nn_reserve(ctx, g.d_sim, (size_t)total);
+    if (!rc) rc = gr_fill(ctx, g.rect ? g.d_query.get() : ctx->nn.d_base.get(), ctx->nn.d_base, threshold, metric, g.d_col, g.d_sim);
+    if (rc) return rc;
+    GNN_HIP(hipMemcpyAsync(col_host, g.d_col.get(), (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    GNN_HIP(hipMemcpyAsync(sim_host, g.d_sim.get(), (size_t)total * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    GNN_HIP(hipStreamSynchronize(ctx->stream));
     return GNN_OK;
 }
 
@@ -331,7 +405,7 @@ extern "C" int gnn_graph_count_dev(gnn_ctx* ctx, const float* rows_dev, int64_t 
         return GNN_ERR_ARG;
     }
     if (int rc = check_ctx(ctx)) return rc;
-    return gr_count(ctx, fn, rows_dev, n, threshold, metric, indptr_dev, nnz_host);
+    return gr_count(ctx, fn, rows_dev, n, nullptr, 0, false, threshold, metric, indptr_dev, nnz_host);
 }
 
 extern "C" int gnn_graph_fill_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int metric, int32_t* col_dev, float* sim_dev,
@@ -339,13 +413,13 @@ extern "C" int gnn_graph_fill_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n
     const char* const fn = "gnn_graph_fill_dev";
     if (int rc = check_graph_args(fn, n, threshold, metric)) return rc;
     if (int rc = check_ctx(ctx)) return rc;
-    if (int rc = gr_check_fill(ctx, fn, n, threshold, metric, capacity, false)) return rc;
+    if (int rc = gr_check_fill(ctx, fn, n, 0, false, threshold, metric, capacity, false)) return rc;
     if (ctx->gr.total == 0) return GNN_OK;
     if (!rows_dev || !col_dev || !sim_dev) {
         set_error(std::string("bad argument to ") + fn + ": the rows, col and sim are required");
         return GNN_ERR_ARG;
     }
-    return gr_fill(ctx, rows_dev, n, threshold, metric, col_dev, sim_dev);
+    return gr_fill(ctx, rows_dev, nullptr, threshold, metric, col_dev, sim_dev);
 }
 
 extern "C" int gnn_graph_count(gnn_ctx* ctx, const float* rows_host, int64_t n, float threshold, int metric, int64_t* indptr_host,
@@ -361,7 +435,7 @@ extern "C" int gnn_graph_count(gnn_ctx* ctx, const float* rows_host, int64_t n, 
     g.counted = false;
     int rc = nn_reserve(ctx, g.d_indptr, (size_t)n + 1);         // both buffers stand before the copy is enqueued
     if (!rc) rc = nn_upload_rows(ctx, rows_host, n);
-    if (!rc) rc = gr_count(ctx, fn, ctx->nn.d_base, n, threshold, metric, g.d_indptr, nnz_host);
+    if (!rc) rc = gr_count(ctx, fn, ctx->nn.d_base, n, nullptr, 0, false, threshold, metric, g.d_indptr, nnz_host);
     if (rc) return rc;
     GNN_HIP(hipMemcpyAsync(indptr_host, g.d_indptr.get(), (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     GNN_HIP(hipStreamSynchronize(ctx->stream));
@@ -378,20 +452,74 @@ extern "C" int gnn_graph_fill(gnn_ctx* ctx, int64_t n, float threshold, int metr
     const char* const fn = "gnn_graph_fill";
     if (int rc = check_graph_args(fn, n, threshold, metric)) return rc;
     if (int rc = check_ctx(ctx)) return rc;
-    if (int rc = gr_check_fill(ctx, fn, n, threshold, metric, capacity, true)) return rc;
-    GraphWorkspace& g = ctx->gr;
-    const int64_t total = g.total;
-    if (total == 0) return GNN_OK;
-    if (!col_host || !sim_host) {
-        set_error(std::string("bad argument to ") + fn + ": col and sim are required");
+    if (int rc = gr_check_fill(ctx, fn, n, 0, false, threshold, metric, capacity, true)) return rc;
+    return gr_fill_host(ctx, fn, threshold, metric, col_host, sim_host);
+}
+
+// ---- the match: the same passes over the rectangle query x base ----------------------------------------------------------------------
+
+extern "C" int gnn_match_count_dev(gnn_ctx* ctx, const float* query_dev, int64_t n_query, const float* base_dev, int64_t n_base,
+                                   float threshold, int metric, int64_t* indptr_dev, int64_t* nnz_host) {
+    const char* const fn = "gnn_match_count_dev";
+    if (int rc = check_match_args(fn, n_query, n_base, threshold, metric)) return rc;
+    if ((n_query > 0 && !query_dev) || (n_base > 0 && !base_dev) || !indptr_dev || !nnz_host) {
+        set_error(std::string("bad argument to ") + fn + ": the query, the base, indptr and nnz are required");
         return GNN_ERR_ARG;
     }
-    int rc = nn_reserve(ctx, g.d_col, (size_t)total);
-    if (!rc) rc = nn_reserve(ctx, g.d_sim, (size_t)total);
-    if (!rc) rc = gr_fill(ctx, ctx->nn.d_base, n, threshold, metric, g.d_col, g.d_sim);
+    if (int rc = check_ctx(ctx)) return rc;
+    return gr_count(ctx, fn, query_dev, n_query, base_dev, n_base, true, threshold, metric, indptr_dev, nnz_host);
+}
+
+extern "C" int gnn_match_fill_dev(gnn_ctx* ctx, const float* query_dev, int64_t n_query, const float* base_dev, int64_t n_base,
+                                  float threshold, int metric, int32_t* col_dev, float* sim_dev, int64_t capacity) {
+    const char* const fn = "gnn_match_fill_dev";
+    if (int rc = check_match_args(fn, n_query, n_base, threshold, metric)) return rc;
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = gr_check_fill(ctx, fn, n_query, n_base, true, threshold, metric, capacity, false)) return rc;
+    if (ctx->gr.total == 0) return GNN_OK;
+    if (!query_dev || !base_dev || !col_dev || !sim_dev) {
+        set_error(std::string("bad argument to ") + fn + ": the query, the base, col and sim are required");
+        return GNN_ERR_ARG;
+    }
+    return gr_fill(ctx, query_dev, base_dev, threshold, metric, col_dev, sim_dev);
+}
+
+extern "C" int gnn_match_count(gnn_ctx* ctx, const float* query_host, int64_t n_query, const float* base_host, int64_t n_base,
+                               float threshold, int metric, int64_t* indptr_host, int64_t* nnz_host) {
+    const char* const fn = "gnn_match_count";
+    if (int rc = check_match_args(fn, n_query, n_base, threshold, metric)) return rc;
+    if ((n_query > 0 && !query_host) || (n_base > 0 && !base_host) || !indptr_host || !nnz_host) {
+        set_error(std::string("bad argument to ") + fn + ": the query, the base, indptr and nnz are required");
+        return GNN_ERR_ARG;
+    }
+    if (int rc = check_ctx(ctx)) return rc;
+    GraphWorkspace& g = ctx->gr;
+    g.counted = false;
+    // every buffer stands before a copy is enqueued.  The query rows go into a buffer of the match's own: no other search writes it
+    int rc = nn_reserve(ctx, g.d_indptr, (size_t)n_query + 1);
+    if (!rc) rc = nn_reserve(ctx, g.d_query, (size_t)std::max<int64_t>(n_query, 1) * D);
+    if (!rc) rc = nn_upload_rows(ctx, base_host, n_base);
     if (rc) return rc;
-    GNN_HIP(hipMemcpyAsync(col_host, g.d_col.get(), (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(sim_host, g.d_sim.get(), (size_t)total * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (n_query > 0)
+        GNN_HIP(hipMemcpyAsync(g.d_query.get(), query_host, (size_t)n_query * D * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    rc = gr_count(ctx, fn, g.d_query, n_query, ctx->nn.d_base, n_base, true, threshold, metric, g.d_indptr, nnz_host);
+    if (rc) return rc;
+    GNN_HIP(hipMemcpyAsync(indptr_host, g.d_indptr.get(), (size_t)(n_query + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     GNN_HIP(hipStreamSynchronize(ctx->stream));
+    g.host_rows = true;
     return GNN_OK;
+}
+
+extern "C" int gnn_match_fill(gnn_ctx* ctx, int64_t n_query, int64_t n_base, float threshold, int metric, int32_t* col_host, float* sim_host,
+                              int64_t capacity) {
+    const char* const fn = "gnn_match_fill";
+    if (int rc = check_match_args(fn, n_query, n_base, threshold, metric)) return rc;
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = gr_check_fill(ctx, fn, n_query, n_base, true, threshold, metric, capacity, true)) return rc;
+    return gr_fill_host(ctx, fn, threshold, metric, col_host, sim_host);
+}
+
+extern "C" int gnn_debug_match_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
+    if (int rc = check_ctx(ctx)) return rc;
+    return nn_round_ms_out("gnn_debug_match_pass_ms", ctx->gr.pass_ms, ms_out, capacity, n_out);
 }

@@ -402,7 +402,7 @@ int nn_tile_grid(const gnn_ctx* ctx, const std::string& fn, const char* noun, in
 
 int nn_upload_rows(gnn_ctx* ctx, const float* rows_host, int64_t n) {
     DevBuf<float>& d_base = ctx->nn.d_base;
-    ctx->gr.host_rows = false;             // gnn_graph_fill reads the rows its count uploaded: these replace them
+    ctx->gr.host_rows = false;             // gnn_graph_fill / gnn_match_fill read the rows their count uploaded here: these replace them
     if (int rc = nn_reserve(ctx, d_base, (size_t)std::max<int64_t>(n, 1) * D)) return rc;
     if (n > 0) GNN_HIP(hipMemcpyAsync(d_base, rows_host, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     return GNN_OK;

@@ -302,6 +302,77 @@ class GraphResult:
         return cls(indptr=indptr, col=col, sim=sim, valid=np.asarray(valid, dtype=bool), n=len(indptr) - 1, n_edges=len(col),
                    threshold=float(_sequence.cluster_threshold(threshold)), metric=str(metric))
 
+    def extend(self, cross: "MatchResult", new: "GraphResult") -> "GraphResult":
+        """The graph of the concatenated rows [this graph's rows; ``new``'s rows] (``sequence.graph_extend``), where ``cross`` =
+        ``match(query=these rows, base=new's rows)`` at the same threshold and metric: a pair's value depends on its two rows only,
+        so the result equals ``graph(concatenation)`` bit for bit and the old x old products are not computed again.  Its
+        :meth:`components` is the assignment of the new rows to the old clusters.  ``ValueError`` when sizes, threshold bits or
+        metric disagree."""
+        if cross.n_query != self.n or cross.n_base != new.n:
+            raise ValueError(f"the cross matches are {cross.n_query} x {cross.n_base}, the graphs have {self.n} and {new.n} rows: "
+                             "match(query=the old rows, base=the new rows) is required")
+        bits = [np.float32(x.threshold).view(np.uint32) for x in (self, cross, new)]
+        if bits[0] != bits[1] or bits[0] != bits[2]:
+            raise ValueError(f"the thresholds {self.threshold!r}, {cross.threshold!r} and {new.threshold!r} differ")
+        if not self.metric == cross.metric == new.metric:
+            raise ValueError(f"the metrics {self.metric!r}, {cross.metric!r} and {new.metric!r} differ")
+        arrays = _sequence.graph_extend(*((x.indptr, x.col, x.sim) for x in (self, cross, new)))
+        return GraphResult.build(arrays, np.concatenate([self.valid, new.valid]), self.threshold, self.metric)
+
+
+class MatchResult:
+    """What :meth:`NNEngine.match` returns (the definition is ``sequence.threshold_matches``): the bipartite similarity graph query x
+    base in CSR form by query row - ``indptr`` (int64 (n_query + 1,)), ``col`` (int32: query i owns ``col[indptr[i]:indptr[i + 1]]``,
+    its base partners in ascending order) and ``sim`` (float32, the device's own values: what :meth:`NNEngine.neighbours` returns for
+    query i and base row j) -, ``query_valid`` and ``base_valid`` (bool: the rows that took part), ``n_query``, ``n_base``,
+    ``n_edges``, the ``threshold`` as the float32 it was compared as, and ``metric``."""
+    FIELDS = ("indptr", "col", "sim", "query_valid", "base_valid", "n_query", "n_base", "n_edges", "threshold", "metric")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw.get(k))
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    def edges(self):
+        """COO: (query int64, base int64, sim), in the CSR's order"""
+        a, b = _sequence.graph_edges(self.indptr, self.col)
+        return a, b, self.sim
+
+    def hits(self) -> np.ndarray:
+        """int64 (n_query,): the partners of every query"""
+        return np.diff(self.indptr).astype(np.int64)
+
+    def base_hits(self) -> np.ndarray:
+        """int64 (n_base,): the queries that matched every base row"""
+        return np.bincount(np.asarray(self.col, dtype=np.int64), minlength=self.n_base).astype(np.int64)
+
+    def best(self):
+        """``sequence.match_best``: (idx int64 (n_query,), sim (n_query,)) - per query the partner with the largest ``sim``, ties to
+        the smaller index, -1 / NaN where there is none.  It is ``neighbours(query, base, 1)`` wherever that similarity is >= the
+        threshold."""
+        return _sequence.match_best(self.indptr, self.col, self.sim)
+
+    def transpose(self):
+        """``sequence.match_transpose``: the CSR by base row (indptr int64 (n_base + 1,), col int32: the queries, ascending; sim) -
+        on the host; a pair's value keeps its orientation (query i, base row j)"""
+        return _sequence.match_transpose(self.indptr, self.col, self.sim, self.n_base)
+
+    def table(self, query_names=None, base_names=None):
+        """``sequence.match_table``: one record per match - query, base, sim"""
+        return _sequence.match_table(self.indptr, self.col, self.sim, query_names, base_names)
+
+    @classmethod
+    def build(cls, arrays, query_valid, base_valid, threshold, metric):
+        """from the (indptr, col, sim) of ``sequence.threshold_matches`` or the library, and the validity of both sides"""
+        indptr, col, sim = arrays
+        query_valid, base_valid = np.asarray(query_valid, dtype=bool), np.asarray(base_valid, dtype=bool)
+        if len(query_valid) != len(indptr) - 1:
+            raise ValueError(f"query_valid has {len(query_valid)} flags, indptr {len(indptr) - 1} rows")
+        return cls(indptr=indptr, col=col, sim=sim, query_valid=query_valid, base_valid=base_valid, n_query=len(indptr) - 1,
+                   n_base=len(base_valid), n_edges=len(col), threshold=float(_sequence.cluster_threshold(threshold)), metric=str(metric))
+
 
 class NNEngine:
     def __init__(self, device: int = 0, weights: dict = None, chunk: int = None):
@@ -871,6 +942,63 @@ class NNEngine:
         ms = np.zeros(n.value, np.float64)
         if n.value:
             check(self.lib.gnn_debug_graph_pass_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
+        return ms
+
+    # -- matches against a reference -----------------------------------------------------
+    def match(self, query, base, threshold, metric="cosine", max_edges=1 << 28) -> MatchResult:
+        """Matches against a reference (``gnn_match_count`` + ``gnn_match_fill``; the definition is ``sequence.threshold_matches``):
+        every pair of a valid row i of ``query`` (nq, 512) and a valid row j of ``base`` (nb, 512) whose similarity under ``metric``
+        is >= ``threshold``, with that similarity - ALL the reference rows a query is within the threshold of, where
+        :meth:`neighbours` stops at 64; exact, the passes of :meth:`graph` over the rectangle.  The similarity of the pair (i, j) is
+        the float32 :meth:`neighbours` returns for query i and base row j; no pair is excluded.  The count runs first: more than
+        ``max_edges`` matches raise ``ValueError`` before anything is allocated for them.  With :meth:`GraphResult.extend` it adds
+        rows to a graph without computing old x old again.  :meth:`set_neighbour_split` sets the range of this search too; no
+        result depends on it."""
+        q = _sequence.neighbour_rows(query)
+        b = _sequence.neighbour_rows(base, "base")
+        if isinstance(metric, str) and metric not in _lib.KNN_METRICS:
+            raise ValueError(f"metric {metric!r}: expected one of {tuple(_lib.KNN_METRICS)}")
+        code = self._knn_metric(metric)
+        nq, nb = len(q), len(b)
+        indptr = np.empty(nq + 1, dtype=np.int64)
+        total = C.c_int64(0)
+        check(self.lib.gnn_match_count(self.ctx, q.ctypes.data, nq, b.ctypes.data, nb, float(threshold), code, indptr.ctypes.data,
+                                       C.addressof(total)))
+        m = int(total.value)
+        if m > int(max_edges):
+            raise ValueError(f"there are {m} matches at the threshold {float(np.float32(threshold)):g}, more than max_edges = "
+                             f"{int(max_edges)}: raise the threshold or max_edges")
+        col, sim = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float32)
+        check(self.lib.gnn_match_fill(self.ctx, nq, nb, float(threshold), code, col.ctypes.data, sim.ctypes.data, m))
+        name = metric if isinstance(metric, str) else {v: k for k, v in _lib.KNN_METRICS.items()}[code]
+        return MatchResult.build((indptr, col, sim), _sequence.valid_rows(q, name), _sequence.valid_rows(b, name), np.float32(threshold),
+                                 name)
+
+    def match_count_dev(self, query_ptr: int, n_query: int, base_ptr: int, n_base: int, threshold, indptr_ptr: int, metric="cosine") -> int:
+        """``gnn_match_count_dev``: device pointers in (query n_query x 512 f32, base n_base x 512 f32) and out (indptr n_query + 1
+        int64); the engine's stream is synchronised once.  Returns the number of matches: what ``col`` and ``sim`` of
+        :meth:`match_fill_dev` must hold."""
+        total = C.c_int64(0)
+        check(self.lib.gnn_match_count_dev(self.ctx, query_ptr, int(n_query), base_ptr, int(n_base), float(threshold),
+                                           self._knn_metric(metric), indptr_ptr, C.addressof(total)))
+        return int(total.value)
+
+    def match_fill_dev(self, query_ptr: int, n_query: int, base_ptr: int, n_base: int, threshold, col_ptr, sim_ptr, capacity: int,
+                       metric="cosine"):
+        """Asynchronous (``gnn_match_fill_dev``): the matches of the engine's last :meth:`match_count_dev`, which must have had the
+        same rows, sizes, threshold and metric - col (int32) and sim (f32) of ``capacity`` elements each on the device, enqueued on
+        the engine's stream."""
+        check(self.lib.gnn_match_fill_dev(self.ctx, query_ptr, int(n_query), base_ptr, int(n_base), float(threshold),
+                                          self._knn_metric(metric), col_ptr, sim_ptr, int(capacity)))
+
+    def match_pass_ms(self):
+        """measurement only (``gnn_debug_match_pass_ms``): with profiling enabled, the HIP-event milliseconds of the last count call's
+        [count pass, scan]"""
+        n = C.c_int64(0)
+        check(self.lib.gnn_debug_match_pass_ms(self.ctx, None, 0, C.addressof(n)))
+        ms = np.zeros(n.value, np.float64)
+        if n.value:
+            check(self.lib.gnn_debug_match_pass_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
         return ms
 
     # -- representatives -----------------------------------------------------------------

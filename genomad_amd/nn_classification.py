@@ -108,6 +108,12 @@ class Outputs:
         self.nn_graph_tsv_output = d / f"{p}_nn_graph.tsv"
         self.provirus_nn_graph_output = d / f"{p}_provirus_nn_graph.npz"
         self.provirus_nn_graph_tsv_output = d / f"{p}_provirus_nn_graph.tsv"
+        # written only when GENOMAD_AMD_MATCH and GENOMAD_AMD_MATCH_BASE are set (the matches of the per-contig embeddings against a
+        # reference's; no counterpart in the reference)
+        self.nn_matches_output = d / f"{p}_nn_matches.npz"
+        self.nn_matches_tsv_output = d / f"{p}_nn_matches.tsv"
+        self.provirus_nn_matches_output = d / f"{p}_provirus_nn_matches.npz"
+        self.provirus_nn_matches_tsv_output = d / f"{p}_provirus_nn_matches.tsv"
         f = o / f"{p}_find_proviruses"
         self.find_proviruses_execution_info = f / f"{p}_find_proviruses.json"
         self.find_proviruses_output = f / f"{p}_provirus.tsv"
@@ -740,6 +746,86 @@ def write_graph(npz_path, tsv_path, names_key, names, res, strand="forward"):
     write_graph_tsv(tsv_path, names, res)
 
 
+def match_requested():
+    """GENOMAD_AMD_MATCH=<float in [-1, 1]>: main() also writes, for every contig, ALL the rows of the reference named by
+    GENOMAD_AMD_MATCH_BASE whose encoder embedding has at least that cosine similarity to the contig's per-contig embedding of
+    GENOMAD_AMD_EMBEDDINGS=1 (<prefix>_nn_matches.npz and .tsv); unset or empty: nothing changes (None).  Any other value is an error.
+    Returns the threshold as it is compared: the float32 it rounds to."""
+    v = os.environ.get("GENOMAD_AMD_MATCH", "").strip()
+    if not v:
+        return None
+    try:
+        t = float(v)
+    except ValueError:
+        t = float("nan")
+    if not -1.0 <= t <= 1.0:                             # a NaN fails both comparisons
+        raise ValueError(f"GENOMAD_AMD_MATCH={v!r}: expected a float in [-1, 1] (the cosine similarity at which a contig matches a "
+                         "reference row)")
+    return float(np.float32(t))
+
+
+def match_base_requested():
+    """GENOMAD_AMD_MATCH_BASE=<path>: the reference GENOMAD_AMD_MATCH matches against - an .npz as GENOMAD_AMD_EMBEDDINGS=1 writes it
+    (:func:`load_match_base`); unset or empty: None."""
+    v = os.environ.get("GENOMAD_AMD_MATCH_BASE", "").strip()
+    return Path(v) if v else None
+
+
+def load_match_base(path, strand="forward"):
+    """(names, embeddings float32 (n, 512)) of a reference file: ``embeddings`` of shape (n, 512), ONE other 1-D array of n entries -
+    the names, under whatever key (contig_names, provirus_names) - and an optional ``strand``, which must be the run's mode (a file
+    without it is forward).  ``ValueError`` with the reason for anything else."""
+    what = f"GENOMAD_AMD_MATCH_BASE={str(path)!r}"
+    if not Path(path).is_file():
+        raise ValueError(f"{what}: no such file")
+    try:
+        z = np.load(path)
+        files = list(z.files)
+        emb = z["embeddings"] if "embeddings" in files else None
+        others = {k: z[k] for k in files if k not in ("embeddings", "strand")}
+        base_strand = str(z["strand"]) if "strand" in files else "forward"
+    except Exception as e:  # noqa: BLE001  (not an .npz, or one that cannot be read)
+        raise ValueError(f"{what}: not a readable .npz ({e})") from None
+    if emb is None or emb.ndim != 2 or emb.shape[1] != sequence.NEIGHBOUR_DIM or emb.dtype.kind != "f":
+        raise ValueError(f"{what}: it must hold 'embeddings' of shape (n, {sequence.NEIGHBOUR_DIM}) as GENOMAD_AMD_EMBEDDINGS=1 writes them"
+                         + ("" if emb is None else f", not {emb.dtype} {emb.shape}"))
+    names = [k for k, v in others.items() if v.ndim == 1 and len(v) == len(emb) and v.dtype.kind in "US"]
+    if len(names) != 1:
+        raise ValueError(f"{what}: it must hold one 1-D array of the {len(emb)} names beside 'embeddings' (found: {sorted(others)})")
+    if base_strand != strand:
+        raise ValueError(f"{what}: its embeddings were computed under GENOMAD_AMD_STRAND={base_strand}, this run's are under {strand}: "
+                         "embeddings of different strand modes are not comparable")
+    return others[names[0]], np.ascontiguousarray(emb, dtype=np.float32)
+
+
+MATCH_TSV_HEADER = "seq_name\treference\tsimilarity\n"
+
+
+def write_matches_tsv(path, names, base_names, res):
+    """One line per match of a MatchResult, in its order (contigs ascending, a contig's reference rows ascending): the contig's name,
+    the reference row's name and their similarity, behind one header line."""
+    with open(path, "w") as fout:
+        fout.write(MATCH_TSV_HEADER)
+        for e in res.table(names, base_names):
+            fout.write(f"{e['query']}\t{e['base']}\t{e['sim']:.6f}\n")
+
+
+def write_matches(npz_path, tsv_path, names_key, names, base_names, res, strand="forward"):
+    """Both match files of a stage: the arrays of a MatchResult with the names of both sides, and its list of matches."""
+    np.savez_compressed(npz_path, **{names_key: names, "base_names": base_names, "threshold": np.float64(res.threshold),
+                                     "metric": np.array(res.metric), "indptr": res.indptr, "col": res.col, "sim": res.sim,
+                                     **({"strand": np.array(strand)} if strand != "forward" else {})})
+    write_matches_tsv(tsv_path, names, base_names, res)
+
+
+def _match_base_of_file(path):
+    """The reference names a stage's match file was computed against; no file, or an unreadable one = None."""
+    try:
+        return np.load(path)["base_names"]
+    except Exception:  # noqa: BLE001
+        return None
+
+
 REGION_TSV_HEADER = ("seq_name\tstart\tend\tclass\tn_bins\tevidence_bins\t"
                      + "\t".join("mean_" + c[:-len("_score")] for c in TSV_HEADER.split()[1:]) + "\tmargin\n")
 
@@ -935,6 +1021,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     representatives_threshold = representatives_requested()
     linkage = linkage_requested()
     graph_threshold = graph_requested()
+    match_threshold = match_requested()
+    match_base_path = match_base_requested()
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -989,6 +1077,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         console.error("GENOMAD_AMD_GRAPH needs GENOMAD_AMD_EMBEDDINGS=1: the graph's edges are found among the per-contig encoder "
                       "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_GRAPH.")
         sys.exit(1)
+    if (match_threshold is None) != (match_base_path is None) or (match_threshold is not None and not embeddings):
+        console.error("GENOMAD_AMD_MATCH and GENOMAD_AMD_MATCH_BASE need each other and GENOMAD_AMD_EMBEDDINGS=1: the per-contig encoder "
+                      "embeddings are matched against the reference's at that threshold. Set all three or unset both.")
+        sys.exit(1)
 
     if strand != "forward" and not device_front_end:
         console.error("GENOMAD_AMD_STRAND needs the device front end: the host front end (GENOMAD_AMD_FRONT_END=host) does "
@@ -1016,6 +1108,15 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         console.error(f"GENOMAD_AMD_ATTRIBUTION_BIN is forward-strand only: it cannot be combined with GENOMAD_AMD_STRAND={strand}. "
                       "Unset GENOMAD_AMD_STRAND or GENOMAD_AMD_ATTRIBUTION_BIN.")
         sys.exit(1)
+
+    match_base = None                # (names, embeddings) of the reference, read before any classification starts
+    if match_threshold is not None:
+        try:
+            match_base = load_match_base(match_base_path, strand)
+        except ValueError as e:
+            console.error(f"{e}. Name a file that GENOMAD_AMD_EMBEDDINGS=1 wrote under the same GENOMAD_AMD_STRAND, or unset "
+                          "GENOMAD_AMD_MATCH and GENOMAD_AMD_MATCH_BASE.")
+            sys.exit(1)
 
     def everywhere(*flags):
         """Decisions read from files that rank 0 is about to rewrite are taken on rank 0 and made known to
@@ -1179,6 +1280,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         in the strand mode asked for; otherwise the stage runs again.
         ``graph_files[what]`` (npz, tsv; GENOMAD_AMD_GRAPH, which needs the embeddings): rank 0 lists the edges (NNEngine.graph, cosine)
         of the same gathered embeddings and writes both files.  They follow the clusters files' rule.
+        ``match_files[what]`` (npz, tsv; GENOMAD_AMD_MATCH with GENOMAD_AMD_MATCH_BASE, which need the embeddings): rank 0 matches the
+        same gathered embeddings (query) against the reference's (base; NNEngine.match, cosine) and writes both files.  They follow
+        the clusters files' rule, and the reference's names must be those the file was computed against.
         ``region_emb_path`` (GENOMAD_AMD_REGION_EMBEDDINGS=1, which needs the regions): right after a piece's scan, while its
         sequence is in memory, the piece's own track is segmented (regions are per contig and exact integers: they are the ones
         rank 0 calls on the gathered track, which rank 0 checks) and NNEngine.embed_intervals folds the scan windows' encoder
@@ -1190,6 +1294,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         representatives_path, representatives_tsv_path = representatives_paths
         linkage_path, linkage_tsv_path = linkage_paths
         graph_path, graph_tsv_path = graph_files[what]
+        match_path, match_tsv_path = match_files[what]
         regions_path, regions_tsv_path = regions_paths
         regions_request = None if region_penalty is None else (scan_stride, region_penalty)
         (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and _strand_of_file(strand_path) == strand
@@ -1211,6 +1316,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                  and _clusters_of_file(graph_path) == graph_threshold
                                  and (graph_threshold is None) == (not graph_tsv_path.exists())
                                  and (graph_threshold is None or _npz_strand(graph_path) == strand)
+                                 and _clusters_of_file(match_path) == match_threshold
+                                 and (match_threshold is None) == (not match_tsv_path.exists())
+                                 and (match_threshold is None or (_npz_strand(match_path) == strand
+                                                                  and np.array_equal(_match_base_of_file(match_path), match_base[0])))
                                  and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
                                  and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
                                                             and _npz_strand(scan_path) == strand)))   # :284-292
@@ -1453,6 +1562,21 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     for p in (graph_path, graph_tsv_path):
                         if p.exists():
                             p.unlink()
+                if match_threshold is not None:
+                    base_names, base_rows = match_base
+                    try:
+                        res = eng.match(embeddings_all, base_rows, match_threshold, NEIGHBOUR_METRIC)
+                    except ValueError as e:         # more matches than NNEngine.match's cap: nothing was allocated for them
+                        console.error(f"GENOMAD_AMD_MATCH={match_threshold:g}: {e}. Raise GENOMAD_AMD_MATCH or unset it.")
+                        sys.exit(1)
+                    write_matches(match_path, match_tsv_path, names_key, names, base_names, res, strand)
+                    console.log(f"Matches of the {what}s against {match_base_path.name} ({NEIGHBOUR_METRIC} similarity of the encoder "
+                                f"embeddings >= {match_threshold:g}: {res.n_edges} matches of {int((res.hits() > 0).sum())} {what}s among "
+                                f"{res.n_base} reference rows) written to {match_path.name} and {match_tsv_path.name}.")
+                else:                               # likewise, both files
+                    for p in (match_path, match_tsv_path):
+                        if p.exists():
+                            p.unlink()
         if cleanup and rank0 and enc_dir.is_dir():
             console.log(f"Deleting encoded {what} data.")
             shutil.rmtree(enc_dir)
@@ -1463,6 +1587,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     region_emb_default = {"sequence": outputs.nn_region_embeddings_output, "provirus": outputs.provirus_nn_region_embeddings_output}
     graph_files = {"sequence": (outputs.nn_graph_output, outputs.nn_graph_tsv_output),
                    "provirus": (outputs.provirus_nn_graph_output, outputs.provirus_nn_graph_tsv_output)}
+    match_files = {"sequence": (outputs.nn_matches_output, outputs.nn_matches_tsv_output),
+                   "provirus": (outputs.provirus_nn_matches_output, outputs.provirus_nn_matches_tsv_output)}
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
     scan_kw = (lambda path: {"scan_path": path}) if scan_stride is not None else (lambda path: {})
     region_emb_kw = (lambda path: {"region_emb_path": path}) if region_embeddings else (lambda path: {})

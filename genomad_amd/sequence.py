@@ -907,6 +907,98 @@ def graph_table(indptr, col, sim, names=None):
     return [{"a": name(i), "b": name(j), "sim": float(s)} for i, j, s in zip(a, b, np.asarray(sim))]
 
 
+def threshold_matches(query, base, threshold, metric="cosine"):
+    """Matches against a reference, spelled out (the definition ``gnn_match_count`` / ``gnn_match_fill`` compute on the device; float64
+    throughout, readable, not fast, nq x nb): the bipartite similarity graph between two sets of encoder embeddings.  ``query``
+    (nq, 512) and ``base`` (nb, 512) are float32 rows; validity, ``metric`` and the threshold are those of :func:`threshold_graph`.
+    The pair (i, j) is a match iff query row i and base row j are valid and sim(i, j) = q[i] . b[j] >= the float32 ``threshold``
+    rounds to.  No pair is excluded: where query and base are the same rows, (i, i) and both orientations are there.  Returns the CSR
+    by query row: ``indptr`` (int64, nq + 1), ``col`` (int32: query i owns ``col[indptr[i]:indptr[i + 1]]``, its base partners in
+    ascending order; an invalid query owns nothing, an invalid base row is nobody's partner) and ``sim`` (float64)."""
+    if metric not in NEIGHBOUR_METRICS:
+        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    q32, b32 = neighbour_rows(query), neighbour_rows(base, "base")
+    thr = float(cluster_threshold(threshold))
+
+    def unit(r32):
+        ok = np.isfinite(r32).all(axis=1)
+        r = np.where(ok[:, None], r32, 0).astype(np.float64)
+        if metric == "cosine":
+            norm = np.sqrt((r * r).sum(axis=1))
+            ok &= norm > 0
+            r = r / np.where(ok, norm, 1.0)[:, None]
+        return r, ok
+
+    (q, q_ok), (b, b_ok) = unit(q32), unit(b32)
+    s = q @ b.T
+    hit = (s >= thr) & q_ok[:, None] & b_ok[None, :]
+    i, j = np.nonzero(hit)              # row-major: queries in order, a query's partners ascending
+    indptr = np.concatenate([[0], np.cumsum(hit.sum(axis=1))]).astype(np.int64)
+    return indptr, j.astype(np.int32), s[i, j].astype(np.float64)
+
+
+def match_best(indptr, col, sim):
+    """(idx int64 (nq,), sim (nq,)) of a match CSR: every query's partner with the largest ``sim``, ties to the smaller index; -1 / NaN
+    where it has none - ``nearest_neighbours(query, base, 1)`` wherever that similarity reaches the threshold."""
+    a, b = graph_edges(indptr, col)
+    sim = np.asarray(sim)
+    nq = len(indptr) - 1
+    order = np.lexsort((b, -sim, a))    # by query, then similarity descending, then base index ascending: segments stay in place
+    idx = np.full(nq, -1, dtype=np.int64)
+    best = np.full(nq, np.nan, dtype=sim.dtype if sim.dtype.kind == "f" else np.float64)
+    has = np.flatnonzero(np.diff(np.asarray(indptr, dtype=np.int64)) > 0)
+    first = order[np.asarray(indptr, dtype=np.int64)[has]]
+    idx[has] = b[first]
+    best[has] = sim[first]
+    return idx, best
+
+
+def match_transpose(indptr, col, sim, n_base):
+    """The CSR by base row of a match CSR: (indptr int64 (n_base + 1,), col int32 - the queries that matched the base row, ascending -,
+    sim: the same values, the pair's orientation unchanged)."""
+    a, b = graph_edges(indptr, col)
+    n_base = int(n_base)
+    if len(b) and int(b.max()) >= n_base:
+        raise ValueError(f"a partner is base row {int(b.max())}, beyond the {n_base} base rows")
+    order = np.lexsort((a, b))
+    t_ptr = np.concatenate([[0], np.cumsum(np.bincount(b, minlength=n_base))]).astype(np.int64)
+    return t_ptr, a[order].astype(np.int32), np.asarray(sim)[order]
+
+
+def match_table(indptr, col, sim, query_names=None, base_names=None):
+    """One record per match of a match CSR, in its order: ``query`` and ``base`` (indices; the names where given) and ``sim``."""
+    a, b = graph_edges(indptr, col)
+    qn = (lambda i: int(i)) if query_names is None else (lambda i: str(query_names[int(i)]))
+    bn = (lambda i: int(i)) if base_names is None else (lambda i: str(base_names[int(i)]))
+    return [{"query": qn(i), "base": bn(j), "sim": float(s)} for i, j, s in zip(a, b, np.asarray(sim))]
+
+
+def graph_extend(old, cross, new):
+    """The upper-triangle CSR of the concatenated rows [old rows; new rows] from three pieces, each an (indptr, col, sim): ``old`` =
+    the graph of the old rows, ``cross`` = the matches of query = the old rows against base = the new rows, ``new`` = the graph of the
+    new rows.  Row i < n_old gets its old partners followed by ``cross``'s columns + n_old; row n_old + i gets ``new``'s columns +
+    n_old.  A pair's value depends on its two rows only and the pair i < j is (query i, base row j) in all three pieces: this IS the
+    graph of the concatenation - for the device's pieces bit for bit -, and the old x old products are not computed again."""
+    (o_ptr, o_col, o_sim), (c_ptr, c_col, c_sim), (n_ptr, n_col, n_sim) = (
+        (np.asarray(p, dtype=np.int64), np.asarray(c, dtype=np.int64), np.asarray(s)) for p, c, s in (old, cross, new))
+    n_old, n_new = len(o_ptr) - 1, len(n_ptr) - 1
+    if len(c_ptr) - 1 != n_old:
+        raise ValueError(f"the cross matches have {len(c_ptr) - 1} query rows, the old graph {n_old} rows: query = the old rows is required")
+    if len(c_col) and int(c_col.max()) >= n_new:
+        raise ValueError(f"the cross matches name base row {int(c_col.max())}, the new graph has {n_new} rows: base = the new rows is required")
+    o_deg, c_deg = np.diff(o_ptr), np.diff(c_ptr)
+    indptr = np.concatenate([[0], np.cumsum(np.concatenate([o_deg + c_deg, np.diff(n_ptr)]))]).astype(np.int64)
+    col = np.empty(indptr[-1], dtype=np.int32)
+    sim = np.empty(indptr[-1], dtype=np.result_type(o_sim, c_sim, n_sim))
+    at_old =np.repeat(indptr[:n_old] - o_ptr[:-1], o_deg) + np.arange(len(o_col))                # the row's segment, from its start
+    at_cross = np.repeat(indptr[:n_old] + o_deg - c_ptr[:-1], c_deg) + np.arange(len(c_col))      # behind the row's old partners
+    at_new = indptr[n_old] + np.arange(len(n_col))
+    col[at_old], sim[at_old] = o_col, o_sim
+    col[at_cross], sim[at_cross] = c_col + n_old, c_sim
+    col[at_new], sim[at_new] = n_col + n_old, n_sim
+    return indptr, col, sim
+
+
 def cluster_table(result, names=None):
     """One record per cluster of a :func:`threshold_clusters` result (the four arrays, a dict of them, or anything with them as
     attributes), ordered by label: ``label``, ``size``, ``rep``, ``members`` (their indices in ascending order; the names where

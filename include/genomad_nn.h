@@ -716,8 +716,8 @@ int gnn_debug_linkage_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, i
  *   exact     a counter has one owner workgroup, the offsets are integer prefix sums, an edge's place follows from its row, base
  *             range, step, wave, column block and lane: no atomics in global memory, bit-identical for every split of the base
  *             (gnn_debug_set_neighbour_split sets the range for this search too).
- * What it is not: not approximate; not bipartite (query rows against other base rows); no width other than GNN_EMBED_DIM; not
- * multi-GPU.  The edge list is as large as the threshold makes it - n (n - 1) / 2 at -1: look at *nnz_host before allocating.
+ * What it is not: not approximate; no width other than GNN_EMBED_DIM; not multi-GPU.  Query rows against OTHER base rows - the
+ * bipartite graph - is gnn_match_count / gnn_match_fill below.  The edge list is as large as the threshold makes it - n (n - 1) / 2 at -1: look at *nnz_host before allocating.
  * Device memory, persistent in the ctx and grow-only: the 2 KB of fragments + 1 B per row of the neighbour search (shared with it;
  * gnn_graph_count: + the row's 2 KB of f32), 12 B per (row, base range) of counters and offsets (gnn_graph_count: + 8 B per row;
  * gnn_graph_fill: + 8 B per edge).  Nothing is n x n.
@@ -734,6 +734,50 @@ int gnn_graph_fill_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, float thr
  * the count pass, [1] the scan and indptr; *n_out = the figures recorded (2, or 0 for n == 0 or without profiling), at most `capacity`
  * of them are written.  The prepare kernel and the fill are timed from outside, by gnn_profile_get around the calls. */
 int gnn_debug_graph_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
+
+/* ---- matches against a reference: the bipartite similarity graph query x base ------------------------------
+ * "Which reference rows is every new row within the threshold of, all of them": every pair (i, j) of a valid query row i and a valid
+ * base row j with sim(i, j) >= threshold and its similarity, as a CSR by query row.  The passes, the kernel, the workspace and the
+ * contract are those of gnn_graph_* - the rectangle instead of the upper triangle -; validity, metric and threshold are those of
+ * gnn_cluster; no forward pass runs and no other entry point's result changes.
+ *   value     the similarity of the pair (i, j) is the f32 that gnn_neighbours returns for query i and base row j.  No pair is
+ *             excluded: where query and base are the same rows, (i, i) and both orientations (i, j), (j, i) are present.  The threshold
+ *             is compared as the f32 given; a tie is an edge; a similarity that is not a number is none.
+ *   outputs   indptr (int64 [n_query + 1]): query row i owns col[indptr[i] .. indptr[i + 1]), its base partners in ascending order,
+ *             and sim[...], their similarities; an invalid query owns nothing, an invalid base row is nobody's partner.  col is int32
+ *             (n_base < 2^31), sim f32.
+ *   passes    count, scan and fill as for the graph, over ceil(n_query / 64) tiles x the ranges of the base; the caller sizes col and
+ *             sim between the two calls.
+ *   state     the count / scan workspace is the graph's: a fill belongs to the ctx's LAST count of either kind.  gnn_match_fill* after
+ *             a gnn_graph_count*, gnn_graph_fill* after a gnn_match_count*, and gnn_match_fill* for another (n_query, n_base,
+ *             threshold, metric) answer GNN_ERR_STATE.  The rows must be the same; if they changed, the result is garbage, but no
+ *             store leaves a row's segment.
+ *   ranges    0 <= n_query, n_base < 2^31, a finite threshold, a metric in [0, 1]; GNN_ERR_ARG with the value and the range in the
+ *             message - checked before the ctx is looked at.  n_query == 0 or n_base == 0: nothing is launched, indptr is n_query + 1
+ *             zeros, *nnz_host = 0.  capacity < the total: GNN_ERR_ARG with both numbers.  A total of 0: the fill launches nothing and
+ *             col and sim may be NULL.
+ *   exact     as the graph: no atomics in global memory, bit-identical for every split of the base.
+ * What it is not: not approximate; not a top-k (gnn_neighbours); no width other than GNN_EMBED_DIM; not multi-GPU.  The edge list is as
+ * large as the threshold makes it - n_query * n_base at -1: look at *nnz_host before allocating.
+ * Device memory, persistent in the ctx and grow-only: per base row the 2 KB of fragments + 1 B of the neighbour search (shared with it);
+ * ALL query rows are prepared at once, with no slabs: 2 KB of fragments + 1 B per query row (the neighbour search's query buffers), and
+ * 12 B per (query row, base range) of counters and offsets (shared with the graph).  gnn_match_count: + 2 KB of f32 per base row and per
+ * query row and 8 B per query row; gnn_match_fill: + 8 B per edge.  Nothing is n_query x n_base.
+ * gnn_match_count / gnn_match_fill: host pointers, synchronous; the base's rows go where every host-pointer search puts its base, the
+ * query's into a buffer of the match's own; the fill prepares both again and answers GNN_ERR_STATE when another host-pointer search
+ * has replaced the base's rows.  gnn_match_count_dev: device pointers, *nnz_host on the host.  gnn_match_fill_dev: device pointers,
+ * asynchronous on the ctx stream like gnn_classify_dev. */
+int gnn_match_count(gnn_ctx* ctx, const float* query_host, int64_t n_query, const float* base_host, int64_t n_base, float threshold,
+                    int metric, int64_t* indptr_host, int64_t* nnz_host);
+int gnn_match_fill(gnn_ctx* ctx, int64_t n_query, int64_t n_base, float threshold, int metric, int32_t* col_host, float* sim_host,
+                   int64_t capacity);
+int gnn_match_count_dev(gnn_ctx* ctx, const float* query_dev, int64_t n_query, const float* base_dev, int64_t n_base, float threshold,
+                        int metric, int64_t* indptr_dev, int64_t* nnz_host);
+int gnn_match_fill_dev(gnn_ctx* ctx, const float* query_dev, int64_t n_query, const float* base_dev, int64_t n_base, float threshold,
+                       int metric, int32_t* col_dev, float* sim_dev, int64_t capacity);
+/* measurement only: [count pass, scan] of the ctx's last gnn_match_count* call, as gnn_debug_graph_pass_ms (the figures are the
+ * workspace's: those of the last count of either kind). */
+int gnn_debug_match_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
 
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
