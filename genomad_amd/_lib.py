@@ -129,6 +129,8 @@ SIGNATURES = {
     "gnn_debug_set_neighbour_split": (_int, [_vp, _i64]),
     "gnn_cluster": (_int, [_vp, _vp, _i64, C.c_float, _int, _vp, _vp, _vp, _vp]),
     "gnn_cluster_dev": (_int, [_vp, _vp, _i64, C.c_float, _int, _vp, _vp, _vp, _vp]),
+    "gnn_density": (_int, [_vp, _vp, _i64, C.c_float, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_density_dev": (_int, [_vp, _vp, _i64, C.c_float, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_representatives": (_int, [_vp, _vp, _i64, C.c_float, _int, _vp, _vp, _vp, _vp]),
     "gnn_representatives_dev": (_int, [_vp, _vp, _i64, C.c_float, _int, _vp, _vp, _vp, _vp]),
     "gnn_debug_representative_round_ms": (_int, [_vp, _vp, _i64, _vp]),

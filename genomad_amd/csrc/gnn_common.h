@@ -216,6 +216,18 @@ struct ClusterWorkspace {
     DevBuf<int64_t> d_out;                       // gnn_cluster: [label | degree | size | rep]
 };
 
+// ---- density clusters (gnn_density.hip): persistent, grow-only.  The fragments and flags are NeighbourWorkspace's bfrag / bvalid (and
+// d_base for the host entry point); here 21 B per row, one byte per (row tile, base range) and, for gnn_density alone, its 37 B of
+// results.  Nothing is n x n.
+struct DensityWorkspace {
+    DevBuf<int32_t> parent;                      // union-find over the core rows: a link points to a smaller index, a root to itself
+    DevBuf<int32_t> degree, size;                // edges at the row; rows that carry the label, at the label's row
+    DevBuf<unsigned long long> key;              // at a row that is not core: max of (image of the similarity << 32) | (2^32 - 1 - core row)
+    DevBuf<uint8_t> core;                        // [round_up(n, 64)]: degree + 1 >= min_points at a valid row
+    DevBuf<uint8_t> flag;                        // [tiles * splits]: the count pass saw an edge in the workgroup's pairs
+    DevBuf<int64_t> d_out;                       // gnn_density: [label | degree | size | anchor | sim (f32) | kind (u8)]
+};
+
 // ---- representatives (gnn_representatives.hip): persistent, grow-only.  The fragments and flags are NeighbourWorkspace's bfrag /
 // bvalid (and d_base for the host entry point); here 21 B per row (padded to 64), one live byte per 64 and per 32 rows, two counters
 // and, for gnn_representatives alone, its 20 B of results.  Nothing is n x n.
@@ -457,6 +469,7 @@ struct gnn_ctx {
     gnn::DevBuf<uint8_t> align_buf;
     gnn::NeighbourWorkspace nn;                   // gnn_neighbours.hip
     gnn::ClusterWorkspace cl;                     // gnn_clusters.hip
+    gnn::DensityWorkspace dn;                     // gnn_density.hip
     gnn::RepresentativeWorkspace rp;              // gnn_representatives.hip
     gnn::LinkageWorkspace lk;                     // gnn_linkage.hip
     gnn::GraphWorkspace gr;                       // gnn_graph.hip

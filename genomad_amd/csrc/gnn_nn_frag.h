@@ -1,5 +1,5 @@
-// What the device code of the searches over encoder embeddings shares (gnn_neighbours.hip, gnn_clusters.hip, gnn_representatives.hip,
-// gnn_linkage.hip).  All of them run the same k-steps in the same order on the same fragments: a pair's f32 value is the same in each,
+// What the device code of the searches over encoder embeddings shares (gnn_neighbours.hip, gnn_clusters.hip, gnn_density.hip,
+// gnn_representatives.hip, gnn_linkage.hip, gnn_graph.hip).  All of them run the same k-steps in the same order on the same fragments: a pair's f32 value is the same in each,
 // because the steps below exist once.
 //   the fragment layout and its constants
 //   the parts of a tile kernel, in the order a kernel calls them: nn_copy_tile (the tile's fragments into LDS), nn_tile_range (the
@@ -145,7 +145,8 @@ __host__ __device__ __forceinline__ unsigned long long nn_key(unsigned hi, unsig
 }
 __host__ __device__ __forceinline__ unsigned nn_key_index(unsigned long long key) { return (unsigned)(LOW32 - (key & LOW32)); }
 
-// ---- the union-find of the clusters and of the single-linkage tree (gnn_clusters.hip, gnn_linkage.hip): parent[] is int32 in global
+// ---- the union-find of the clusters, the density clusters and the single-linkage tree (gnn_clusters.hip, gnn_density.hip,
+// gnn_linkage.hip): parent[] is int32 in global
 // memory, a link always points to the SMALLER index, a root to itself.
 // a load that the compiler neither caches nor hoists; what it returns may still be older than another workgroup's compare-and-swap
 __device__ __forceinline__ int cl_peek(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

@@ -174,6 +174,51 @@ class ClusterResult:
         return cls(label=label, degree=degree, size=size, rep=rep, threshold=float(S.cluster_threshold(threshold)), metric=str(metric))
 
 
+class DensityResult:
+    """What :meth:`NNEngine.density` returns (the definition is ``sequence.density_clusters``): ``label``, ``degree``, ``size``,
+    ``anchor`` (int64 (n,)), ``sim`` (float32 from the device; a border row's similarity to its anchor, NaN otherwise), ``kind``
+    (uint8: 0 invalid, 1 noise, 2 border, 3 core), the ``threshold`` as the float32 it was compared as, ``min_points`` and
+    ``metric``."""
+    FIELDS = ("label", "degree", "size", "anchor", "sim", "kind", "threshold", "min_points", "metric")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw.get(k))
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    @property
+    def n_clusters(self) -> int:
+        """clusters: the core rows that are their own label"""
+        return int((self.label == np.arange(len(self.label))).sum())
+
+    @property
+    def n_core(self) -> int:
+        return int((self.kind == 3).sum())
+
+    @property
+    def n_border(self) -> int:
+        return int((self.kind == 2).sum())
+
+    @property
+    def n_noise(self) -> int:
+        return int((self.kind == 1).sum())
+
+    def table(self, names=None):
+        """``sequence.density_table``: one record per cluster, ordered by label"""
+        from . import sequence as S
+        return S.density_table(self, names)
+
+    @classmethod
+    def build(cls, arrays, threshold, min_points, metric):
+        """from the six arrays of ``sequence.density_clusters`` or the library"""
+        from . import sequence as S
+        label, degree, size, anchor, sim, kind = arrays
+        return cls(label=label, degree=degree, size=size, anchor=anchor, sim=sim, kind=kind,
+                   threshold=float(S.cluster_threshold(threshold)), min_points=int(min_points), metric=str(metric))
+
+
 class RepresentativeResult:
     """What :meth:`NNEngine.representatives` returns (the definition is ``sequence.greedy_representatives``), in the caller's index
     space: ``rep`` (int64; a representative names itself, -1 for an invalid row), ``sim`` (float32; a member's similarity to its
@@ -892,6 +937,32 @@ class NNEngine:
         each), enqueued on the engine's stream."""
         check(self.lib.gnn_cluster_dev(self.ctx, rows_ptr, int(n), float(threshold), self._knn_metric(metric), label_ptr, degree_ptr,
                                        size_ptr, rep_ptr))
+
+    # -- density clusters ----------------------------------------------------------------
+    def density(self, rows, threshold, min_points=5, metric="cosine") -> DensityResult:
+        """Density clusters among encoder embeddings (``gnn_density``; the definition is ``sequence.density_clusters``): DBSCAN at
+        one (``threshold``, ``min_points``) on the graph :meth:`cluster` acts on.  A valid row of ``rows`` (n, 512) with ``degree``
+        + 1 >= ``min_points`` is core; clusters are the components of the core rows; a row that is not core hangs on to its most
+        similar core neighbour as a border row (ties to the smaller index) and joins nothing; the rest is noise (label -1).  A row
+        between two dense families no longer merges them.  Exact, two passes over the upper triangle on the matrix pipe; the
+        similarity of the pair i < j is the float32 :meth:`neighbours` returns for query i and base row j.  Unlike textbook DBSCAN
+        the result depends on no visiting order.  :meth:`set_neighbour_split` sets the range of this search too; no result depends
+        on it."""
+        r = _sequence.neighbour_rows(rows, "rows")
+        if isinstance(metric, str) and metric not in _lib.KNN_METRICS:
+            raise ValueError(f"metric {metric!r}: expected one of {tuple(_lib.KNN_METRICS)}")
+        n = len(r)
+        out = [np.empty(n, dtype=np.int64) for _ in range(4)] + [np.empty(n, dtype=np.float32), np.empty(n, dtype=np.uint8)]
+        check(self.lib.gnn_density(self.ctx, r.ctypes.data, n, float(threshold), int(min_points), self._knn_metric(metric),
+                                   *(a.ctypes.data for a in out)))
+        return DensityResult.build(out, np.float32(threshold), min_points, metric)
+
+    def density_dev(self, rows_ptr: int, n: int, threshold, min_points, label_ptr: int, degree_ptr: int, size_ptr: int, anchor_ptr: int,
+                    sim_ptr: int, kind_ptr: int, metric="cosine"):
+        """Asynchronous (``gnn_density_dev``): device pointers in (rows n x 512 f32) and out (label, degree, size, anchor: n int64
+        each; sim: n f32; kind: n uint8), enqueued on the engine's stream."""
+        check(self.lib.gnn_density_dev(self.ctx, rows_ptr, int(n), float(threshold), int(min_points), self._knn_metric(metric), label_ptr,
+                                       degree_ptr, size_ptr, anchor_ptr, sim_ptr, kind_ptr))
 
     # -- similarity graph ----------------------------------------------------------------
     def graph(self, rows, threshold, metric="cosine", max_edges=1 << 28) -> GraphResult:

@@ -93,6 +93,11 @@ class Outputs:
         self.nn_clusters_tsv_output = d / f"{p}_nn_clusters.tsv"
         self.provirus_nn_clusters_output = d / f"{p}_provirus_nn_clusters.npz"
         self.provirus_nn_clusters_tsv_output = d / f"{p}_provirus_nn_clusters.tsv"
+        # written only when GENOMAD_AMD_DENSITY is set (density clusters among the per-contig embeddings; no counterpart in the reference)
+        self.nn_density_output = d / f"{p}_nn_density.npz"
+        self.nn_density_tsv_output = d / f"{p}_nn_density.tsv"
+        self.provirus_nn_density_output = d / f"{p}_provirus_nn_density.npz"
+        self.provirus_nn_density_tsv_output = d / f"{p}_provirus_nn_density.tsv"
         # written only when GENOMAD_AMD_REPRESENTATIVES is set (greedy clusters among the per-contig embeddings; no counterpart in the reference)
         self.nn_representatives_output = d / f"{p}_nn_representatives.npz"
         self.nn_representatives_tsv_output = d / f"{p}_nn_representatives.tsv"
@@ -642,6 +647,76 @@ def write_clusters_tsv(path, names, res):
                 fout.write(f"{name}\t{names[res.label[i]]}\t{res.size[i]}\t{names[res.rep[i]]}\t{res.degree[i]}\n")
 
 
+DENSITY_MIN_POINTS_DEFAULT = 5
+
+
+def density_requested():
+    """GENOMAD_AMD_DENSITY=<float in [-1, 1]>: main() also writes the density clusters (DBSCAN) of the contigs at that cosine similarity
+    of the per-contig encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1 (<prefix>_nn_density.npz and .tsv); unset or empty: nothing
+    changes (None).  GENOMAD_AMD_DENSITY_MIN_POINTS=<integer >= 1> (default 5) is how many contigs, itself included, a contig needs
+    within the threshold to be a core contig; it is an error without GENOMAD_AMD_DENSITY.  Any other value of either is an error.
+    Returns (the threshold as it is compared: the float32 it rounds to, min_points), or None."""
+    v = os.environ.get("GENOMAD_AMD_DENSITY", "").strip()
+    m = os.environ.get("GENOMAD_AMD_DENSITY_MIN_POINTS", "").strip()
+    if not v:
+        if m:
+            raise ValueError(f"GENOMAD_AMD_DENSITY_MIN_POINTS={m!r} needs GENOMAD_AMD_DENSITY: set the threshold of the density clusters "
+                             "or unset GENOMAD_AMD_DENSITY_MIN_POINTS")
+        return None
+    try:
+        t = float(v)
+    except ValueError:
+        t = float("nan")
+    if not -1.0 <= t <= 1.0:                             # a NaN fails both comparisons
+        raise ValueError(f"GENOMAD_AMD_DENSITY={v!r}: expected a float in [-1, 1] (the cosine similarity within which contigs count "
+                         "towards each other's density)")
+    try:
+        k = int(m) if m else DENSITY_MIN_POINTS_DEFAULT
+    except ValueError:
+        k = 0
+    if not 1 <= k < sequence.DENSITY_MIN_POINTS_END:
+        raise ValueError(f"GENOMAD_AMD_DENSITY_MIN_POINTS={m!r}: expected an integer >= 1 (below 2^31): the contigs, itself included, "
+                         "that a core contig has within the threshold")
+    return float(np.float32(t)), k
+
+
+def _density_of_file(path):
+    """The (threshold, min_points) a stage's density file was computed with; no file = None (no density clusters were asked for)."""
+    if not Path(path).exists():
+        return None
+    try:
+        z = np.load(path)
+        return float(z["threshold"]), int(z["min_points"])
+    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
+        return float("nan"), -1
+
+
+DENSITY_TSV_HEADER = "seq_name\tcluster\tcluster_size\tkind\tanchor\tsimilarity\tdegree\n"
+
+
+def write_density_tsv(path, names, res):
+    """One line per contig of a DensityResult: the name of its cluster's label contig, the cluster's size, core | border | noise |
+    invalid, the name of its anchor (a core contig's is its own), a border contig's similarity to its anchor and the contig's own
+    degree; NA wherever there is none."""
+    with open(path, "w") as fout:
+        fout.write(DENSITY_TSV_HEADER)
+        for i, name in enumerate(names):
+            kind = sequence.DENSITY_KINDS[int(res.kind[i])]
+            cluster = names[res.label[i]] if res.label[i] >= 0 else "NA"
+            anchor = names[res.anchor[i]] if res.anchor[i] >= 0 else "NA"
+            sim = f"{res.sim[i]:.6f}" if kind == "border" else "NA"
+            fout.write(f"{name}\t{cluster}\t{res.size[i]}\t{kind}\t{anchor}\t{sim}\t{res.degree[i]}\n")
+
+
+def write_density(npz_path, tsv_path, names_key, names, res, strand="forward"):
+    """Both density files of a stage: the arrays of a DensityResult with the contig names, and one line per contig."""
+    np.savez_compressed(npz_path, **{names_key: names, "threshold": np.float64(res.threshold), "min_points": np.int64(res.min_points),
+                                     "metric": np.array(res.metric), "label": res.label, "degree": res.degree, "size": res.size,
+                                     "anchor": res.anchor, "sim": res.sim, "kind": res.kind,
+                                     **({"strand": np.array(strand)} if strand != "forward" else {})})
+    write_density_tsv(tsv_path, names, res)
+
+
 def representatives_requested():
     """GENOMAD_AMD_REPRESENTATIVES=<float in [-1, 1]>: main() also writes the greedy clusters of the contigs at that cosine similarity of
     the per-contig encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1 - contigs walked by their number of kept windows, the larger first,
@@ -1018,6 +1093,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     region_embeddings = region_embeddings_requested()
     neighbours_k = neighbours_requested()
     clusters_threshold = clusters_requested()
+    density_request = density_requested()
     representatives_threshold = representatives_requested()
     linkage = linkage_requested()
     graph_threshold = graph_requested()
@@ -1064,6 +1140,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     if clusters_threshold is not None and not embeddings:
         console.error("GENOMAD_AMD_CLUSTERS needs GENOMAD_AMD_EMBEDDINGS=1: clusters are formed among the per-contig encoder "
                       "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_CLUSTERS.")
+        sys.exit(1)
+    if density_request is not None and not embeddings:
+        console.error("GENOMAD_AMD_DENSITY needs GENOMAD_AMD_EMBEDDINGS=1: density clusters are formed among the per-contig encoder "
+                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_DENSITY.")
         sys.exit(1)
     if representatives_threshold is not None and not embeddings:
         console.error("GENOMAD_AMD_REPRESENTATIVES needs GENOMAD_AMD_EMBEDDINGS=1: representatives are chosen among the per-contig encoder "
@@ -1280,6 +1360,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         in the strand mode asked for; otherwise the stage runs again.
         ``graph_files[what]`` (npz, tsv; GENOMAD_AMD_GRAPH, which needs the embeddings): rank 0 lists the edges (NNEngine.graph, cosine)
         of the same gathered embeddings and writes both files.  They follow the clusters files' rule.
+        ``density_files[what]`` (npz, tsv; GENOMAD_AMD_DENSITY with the optional GENOMAD_AMD_DENSITY_MIN_POINTS, which need the
+        embeddings): rank 0 forms the density clusters (NNEngine.density, cosine) of the same gathered embeddings and writes both
+        files.  They follow the clusters files' rule, with (threshold, min_points) in place of the threshold.
         ``match_files[what]`` (npz, tsv; GENOMAD_AMD_MATCH with GENOMAD_AMD_MATCH_BASE, which need the embeddings): rank 0 matches the
         same gathered embeddings (query) against the reference's (base; NNEngine.match, cosine) and writes both files.  They follow
         the clusters files' rule, and the reference's names must be those the file was computed against.
@@ -1294,6 +1377,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         representatives_path, representatives_tsv_path = representatives_paths
         linkage_path, linkage_tsv_path = linkage_paths
         graph_path, graph_tsv_path = graph_files[what]
+        density_path, density_tsv_path = density_files[what]
         match_path, match_tsv_path = match_files[what]
         regions_path, regions_tsv_path = regions_paths
         regions_request = None if region_penalty is None else (scan_stride, region_penalty)
@@ -1316,6 +1400,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                  and _clusters_of_file(graph_path) == graph_threshold
                                  and (graph_threshold is None) == (not graph_tsv_path.exists())
                                  and (graph_threshold is None or _npz_strand(graph_path) == strand)
+                                 and _density_of_file(density_path) == density_request
+                                 and (density_request is None) == (not density_tsv_path.exists())
+                                 and (density_request is None or _npz_strand(density_path) == strand)
                                  and _clusters_of_file(match_path) == match_threshold
                                  and (match_threshold is None) == (not match_tsv_path.exists())
                                  and (match_threshold is None or (_npz_strand(match_path) == strand
@@ -1562,6 +1649,17 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     for p in (graph_path, graph_tsv_path):
                         if p.exists():
                             p.unlink()
+                if density_request is not None:
+                    res = eng.density(embeddings_all, density_request[0], density_request[1], NEIGHBOUR_METRIC)
+                    write_density(density_path, density_tsv_path, names_key, names, res, strand)
+                    console.log(f"Density clusters of the {what}s ({NEIGHBOUR_METRIC} similarity of the encoder embeddings >= "
+                                f"{density_request[0]:g}, at least {density_request[1]} {what}s for a core: {res.n_clusters} clusters, "
+                                f"{res.n_core} core, {res.n_border} border, {res.n_noise} noise) written to {density_path.name} and "
+                                f"{density_tsv_path.name}.")
+                else:                               # likewise, both files
+                    for p in (density_path, density_tsv_path):
+                        if p.exists():
+                            p.unlink()
                 if match_threshold is not None:
                     base_names, base_rows = match_base
                     try:
@@ -1587,6 +1685,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     region_emb_default = {"sequence": outputs.nn_region_embeddings_output, "provirus": outputs.provirus_nn_region_embeddings_output}
     graph_files = {"sequence": (outputs.nn_graph_output, outputs.nn_graph_tsv_output),
                    "provirus": (outputs.provirus_nn_graph_output, outputs.provirus_nn_graph_tsv_output)}
+    density_files = {"sequence": (outputs.nn_density_output, outputs.nn_density_tsv_output),
+                     "provirus": (outputs.provirus_nn_density_output, outputs.provirus_nn_density_tsv_output)}
     match_files = {"sequence": (outputs.nn_matches_output, outputs.nn_matches_tsv_output),
                    "provirus": (outputs.provirus_nn_matches_output, outputs.provirus_nn_matches_tsv_output)}
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})

@@ -1024,6 +1024,106 @@ def cluster_table(result, names=None):
     return out
 
 
+DENSITY_FIELDS = ("label", "degree", "size", "anchor", "sim", "kind")
+DENSITY_KINDS = ("invalid", "noise", "border", "core")          # the values of ``kind``: 0, 1, 2, 3
+DENSITY_MIN_POINTS_END = 1 << 31
+
+
+def density_min_points(min_points) -> int:
+    """``min_points`` as an int: an integer in [1, 2^31) (a bool or a float with a fraction is a ValueError)"""
+    ok = not isinstance(min_points, (bool, np.bool_))
+    try:
+        m = int(min_points) if ok else 0
+        ok = ok and m == min_points
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok or not 1 <= m < DENSITY_MIN_POINTS_END:
+        raise ValueError(f"min_points {min_points!r}: an integer in [1, 2^31) is required")
+    return m
+
+
+def density_clusters(rows, threshold, min_points=5, metric="cosine"):
+    """Density clusters among encoder embeddings, spelled out (the definition ``gnn_density`` computes on the device; float64
+    throughout, readable, not fast, n x n): DBSCAN at one (``threshold``, ``min_points``).  Rows, validity, ``metric``, the threshold
+    and the adjacency are those of :func:`threshold_clusters`: an edge {i, j}, i != j, iff both rows are valid and sim(i, j) or
+    sim(j, i) >= the float32 ``threshold`` rounds to.  ``degree`` is that function's.  A valid row is *core* iff degree + 1 >=
+    ``min_points`` (the row counts itself, as scikit-learn's ``min_samples`` does).  Clusters are the connected components of the
+    core rows under core-core edges, a cluster's ``label`` its smallest core index.  A valid row that is not core and has a core
+    neighbour is a *border* row: ``anchor`` = the core neighbour with the largest similarity, ties to the smaller index; ``label`` =
+    the anchor's; ``sim`` = that similarity.  A border row joins nothing.  Any other valid row is *noise*: ``label`` = ``anchor`` =
+    -1.  A core row has ``anchor`` = itself and ``sim`` = NaN.  ``size`` = the rows, core and border, that carry the row's label; 0
+    for noise.  ``kind``: 0 invalid, 1 noise, 2 border, 3 core.  An invalid row: -1, 0, 0, -1, NaN, 0.  The border rule looks at all
+    core neighbours: unlike textbook DBSCAN, the result does not depend on a visiting order.  Returns ``label``, ``degree``, ``size``,
+    ``anchor`` (int64), ``sim`` (float64) and ``kind`` (uint8), each of n."""
+    if metric not in NEIGHBOUR_METRICS:
+        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    r32 = neighbour_rows(rows, "rows")
+    thr = float(cluster_threshold(threshold))
+    need = density_min_points(min_points)
+    n = len(r32)
+    ok = np.isfinite(r32).all(axis=1)
+    r = np.where(ok[:, None], r32, 0).astype(np.float64)
+    if metric == "cosine":
+        norm = np.sqrt((r * r).sum(axis=1))
+        ok &= norm > 0
+        r = r / np.where(ok, norm, 1.0)[:, None]
+    s = r @ r.T
+    adj = (s >= thr) & ok[:, None] & ok[None, :]
+    adj |= adj.T                        # as threshold_clusters: an edge either way is an edge
+    adj[np.arange(n), np.arange(n)] = False
+    s = np.maximum(s, s.T)              # the similarity of an edge: the larger of its two float64 sums
+    degree = adj.sum(axis=1).astype(np.int64)
+    core = ok & (degree + 1 >= need)
+    label = np.full(n, -1, dtype=np.int64)
+    size = np.zeros(n, dtype=np.int64)
+    anchor = np.full(n, -1, dtype=np.int64)
+    sim = np.full(n, np.nan, dtype=np.float64)
+    kind = np.where(core, 3, np.where(ok, 1, 0)).astype(np.uint8)
+    core_adj = adj & core[:, None] & core[None, :]
+    for i in np.flatnonzero(core):      # ascending: the first unlabelled core row of a component is its smallest
+        if label[i] >= 0:
+            continue
+        stack = [i]
+        label[i] = i
+        while stack:
+            for j in np.flatnonzero(core_adj[stack.pop()] & (label < 0)):
+                label[j] = i
+                stack.append(j)
+    anchor[core] = np.flatnonzero(core)
+    for i in np.flatnonzero(ok & ~core):
+        near = np.flatnonzero(adj[i] & core)
+        if len(near):
+            a = near[np.argmax(s[i, near])]       # argmax: the first = the smallest index among equals
+            anchor[i], label[i], sim[i], kind[i] = a, label[a], s[i, a], 2
+    labelled = label >= 0
+    size[labelled] = np.bincount(label[labelled], minlength=n)[label[labelled]]
+    return label, degree, size, anchor, sim, kind
+
+
+def density_table(result, names=None):
+    """One record per cluster of a :func:`density_clusters` result (the six arrays, a dict of them, or anything with them as
+    attributes), ordered by label: ``label``, ``size``, ``cores``, ``borders`` (how many of either) and ``members`` (core and border
+    rows, their indices in ascending order; the names where ``names`` is given, as is then ``label``).  Noise and invalid rows are
+    in no record."""
+    if isinstance(result, dict):
+        arrays = [result[k] for k in DENSITY_FIELDS]
+    elif isinstance(result, (tuple, list)):
+        arrays = list(result)
+    else:
+        arrays = [getattr(result, k) for k in DENSITY_FIELDS]
+    label, kind = np.asarray(arrays[0], dtype=np.int64), np.asarray(arrays[5], dtype=np.uint8)
+    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    order = np.argsort(label, kind="stable")
+    order = order[label[order] >= 0]
+    out = []
+    bounds = np.flatnonzero(np.diff(label[order], prepend=-1)) if len(order) else []
+    for a, b in zip(bounds, list(bounds[1:]) + [len(order)]):
+        members = order[a:b]
+        out.append({"label": name(label[members[0]]), "size": len(members), "cores": int((kind[members] == 3).sum()),
+                    "borders": int((kind[members] == 2).sum()), "members": [name(i) for i in members]})
+    return out
+
+
 REPRESENTATIVE_FIELDS = ("rep", "sim", "size", "rank")
 
 

@@ -618,6 +618,41 @@ int gnn_cluster(gnn_ctx* ctx, const float* rows_host, int64_t n, float threshold
 int gnn_cluster_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int metric, int64_t* label_dev, int64_t* degree_dev,
                     int64_t* size_dev, int64_t* rep_dev);
 
+/* ---- density clusters among encoder embeddings: DBSCAN on the device ----------------------------------------
+ * "Which rows form dense groups, which hang on to one, and which are alone": DBSCAN at one (threshold, min_points) pair on the graph
+ * of gnn_cluster above - an edge {i, j}, i != j, iff both rows are valid and sim(i, j) >= threshold.  Rows, validity, metric, the value
+ * of a pair (the f32 gnn_neighbours returns for query i < base row j; (j, i) is never computed) and the threshold (compared as the f32
+ * given, a tie is an edge) are those of gnn_cluster; no forward pass runs and no other entry point's result changes.
+ *   core      a valid row with degree + 1 >= min_points: the row counts itself, as scikit-learn's min_samples does.
+ *   clusters  the connected components of the core rows under core-core edges; a cluster's label is its smallest core row.
+ *   border    a valid row that is not core and has a core neighbour: anchor = the core neighbour with the largest similarity, ties to
+ *             the smaller index; label = the anchor's; sim = that similarity (the f32's bits, -0 reported as +0).  A border row joins
+ *             nothing: a border-border edge has no effect, and a row between two dense families no longer merges them.
+ *   noise     a valid row that is not core and has no core neighbour: label = anchor = -1.
+ *   outputs   label, degree, size, anchor: int64 arrays of n; sim: f32; kind: uint8, 0 invalid, 1 noise, 2 border, 3 core.  degree IS
+ *             gnn_cluster's.  size = the rows, core and border, that carry the row's label; 0 for noise.  A core row has anchor =
+ *             itself and sim = NaN.  An invalid row: -1, 0, 0, -1, NaN, 0.
+ *   ranges    0 <= n < 2^31, a finite threshold, 1 <= min_points < 2^31, a metric in [0, 1], in this order; GNN_ERR_ARG with the value
+ *             and the range in the message - checked before the ctx is looked at, nothing is written.  n == 0 is GNN_OK, needs a ctx
+ *             and no pointers, and writes nothing.
+ *   exact     degrees and sizes are integer sums, the anchor a 64-bit integer maximum over ALL core neighbours, the label the root of a
+ *             union-find whose links point to the smaller index: nothing depends on the order workgroups run in or on how the base
+ *             is split over them (gnn_debug_set_neighbour_split sets the range for this search too).  Unlike textbook DBSCAN, where
+ *             a border row goes to the cluster that reaches it first, there is no visiting order for the result to depend on.
+ * min_points = 1: label is gnn_cluster's label.  min_points = 2: the core rows are the rows with an edge and carry gnn_cluster's labels,
+ * the noise rows are its clusters of one, and there is no border row.
+ * What it is not: not HDBSCAN - one (threshold, min_points), no hierarchy over thresholds; not approximate; no width other than
+ * GNN_EMBED_DIM; not multi-GPU.
+ * Two passes over the upper triangle (degrees first: who is core is known only when every edge is counted), no rounds.  Device memory,
+ * persistent in the ctx and grow-only: the 2 KB of fragments + 1 B per row of the neighbour search (shared with it; gnn_density: + the
+ * row's 2 KB of f32), 21 B per row of parent, degree, size, key and core flag, one byte per (64-row tile, base range) (gnn_density: +
+ * 37 B of results).  Nothing is n x n and no edge list is stored.
+ * gnn_density: host pointers, synchronous.  gnn_density_dev: device pointers, asynchronous on the ctx stream like gnn_classify_dev. */
+int gnn_density(gnn_ctx* ctx, const float* rows_host, int64_t n, float threshold, int64_t min_points, int metric, int64_t* label_host,
+                int64_t* degree_host, int64_t* size_host, int64_t* anchor_host, float* sim_host, uint8_t* kind_host);
+int gnn_density_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int64_t min_points, int metric, int64_t* label_dev,
+                    int64_t* degree_dev, int64_t* size_dev, int64_t* anchor_dev, float* sim_dev, uint8_t* kind_dev);
+
 /* ---- representatives among encoder embeddings: greedy clusters on the device --------------------------------
  * "Which rows stand for the others": greedy incremental clustering, as dereplication tools do it.  THE ROWS ARRIVE IN PRIORITY ORDER
  * (index = rank; NNEngine.representatives sorts by weight and maps the answer back).  Walked in that order, a valid row is a
@@ -864,7 +899,8 @@ int gnn_synth_windows_dev(gnn_ctx* ctx, uint64_t seed, int64_t first, int64_t n_
                               * finish kernels of gnn_embed_intervals / gnn_interval_fold_dev / gnn_interval_finish_dev */
 #define GNN_K_NEIGHBOURS 7   /* nearest neighbours: the prepare, tile and merge kernels of gnn_neighbours / gnn_neighbours_dev; clusters:
                               * every kernel of gnn_cluster / gnn_cluster_dev; representatives: every kernel of gnn_representatives*;
-                              * single-linkage tree: every kernel of gnn_linkage / gnn_linkage_dev */
+                              * single-linkage tree: every kernel of gnn_linkage / gnn_linkage_dev; density clusters: every kernel of
+                              * gnn_density / gnn_density_dev */
 #define GNN_K_COUNT 8
 int gnn_profile_enable(gnn_ctx* ctx, int on);
 int gnn_profile_reset(gnn_ctx* ctx);
