@@ -147,6 +147,12 @@ SIGNATURES = {
     "gnn_match_count_dev": (_int, [_vp, _vp, _i64, _vp, _i64, C.c_float, _int, _vp, _vp]),
     "gnn_match_fill_dev": (_int, [_vp, _vp, _i64, _vp, _i64, C.c_float, _int, _vp, _vp, _i64]),
     "gnn_debug_match_pass_ms": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_kmeans": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_kmeans_dev": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_centroids": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp]),
+    "gnn_centroids_dev": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp]),
+    "gnn_debug_set_kmeans_lds": (_int, [_vp, _int]),
+    "gnn_debug_kmeans_pass_ms": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_embed": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_embed_dev": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_debug_forward": (_int, [_vp, _vp, _i64, _int, _vp, C.POINTER(Taps)]),

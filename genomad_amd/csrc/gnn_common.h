@@ -283,6 +283,27 @@ struct GraphWorkspace {
     std::vector<float> pass_ms;                  // profiling on: HIP-event time of the last count call's [count pass, scan]
 };
 
+// ---- spherical k-means (gnn_kmeans.hip): persistent, grow-only.  The rows' fragments and flags are NeighbourWorkspace's bfrag / bvalid
+// (and d_base for the host entry points); here 8 B per row (9 B with the farthest-first init), 2 KB + 1 B of fragments and 4 KB + 8 B
+// of sums per centroid, one 128 KB one-column base, five counters and, for gnn_kmeans / gnn_centroids alone, their results and the
+// init's 2 KB per centroid.  Nothing is n x k.
+struct KMeansWorkspace {
+    int lds_k = 128;                             // up to this many groups the update adds in LDS first (gnn_debug_set_kmeans_lds); no result depends on it
+    DevBuf<uint4> cfrag;                         // the centroids' fragments (first: the init's), as NeighbourWorkspace's
+    DevBuf<uint8_t> cvalid;
+    DevBuf<unsigned long long> key;              // at a row: max of (image of the similarity << 32) | (2^32 - 1 - centroid), 0: none
+    DevBuf<unsigned long long> S;                // [k][512] int64 sums of the members' 32-bit fixed-point unit rows
+    DevBuf<unsigned long long> cnt;              // [k] members
+    DevBuf<uint4> one;                           // farthest-first: the fragments of the last pick as a base of one row (63 zero rows)
+    DevBuf<uint8_t> one_valid, picked;           // its flags [64]; per row: it is a pick
+    DevBuf<unsigned long long> count;            // [changed labels, valid rows, invalid init rows, bad labels, the farthest row's key]
+    PinnedBuf<unsigned long long> h_count;       // where the host reads them: once at the start and once per assignment
+    DevBuf<float> d_init;                        // gnn_kmeans: the init's rows
+    DevBuf<int64_t> d_out;                       // gnn_kmeans: [centroids (f32) | label | size | init_rows | sim (f32)]; gnn_centroids: [centroids | label | size]
+    std::vector<float> pass_ms;                  // profiling on: HIP-event time of the last call's [init, then per assignment: assign,
+                                                 // and behind every assignment but the last: update, finish, prepare]
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -473,6 +494,7 @@ struct gnn_ctx {
     gnn::RepresentativeWorkspace rp;              // gnn_representatives.hip
     gnn::LinkageWorkspace lk;                     // gnn_linkage.hip
     gnn::GraphWorkspace gr;                       // gnn_graph.hip
+    gnn::KMeansWorkspace km;                      // gnn_kmeans.hip
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;

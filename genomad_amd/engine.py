@@ -219,6 +219,42 @@ class DensityResult:
                    threshold=float(S.cluster_threshold(threshold)), min_points=int(min_points), metric=str(metric))
 
 
+class KMeansResult:
+    """What :meth:`NNEngine.kmeans` returns (the definition is ``sequence.spherical_kmeans``): ``label`` (int64 (n,); -1 for an
+    invalid row), ``sim`` (float32 (n,): the similarity to the row's own centroid, NaN for an invalid row), ``centroids`` (float32
+    (k, 512), unit rows), ``size`` (int64 (k,)), ``iterations``, ``converged`` and ``init_rows`` (int64 (k,): the rows the
+    farthest-first traversal picked, -1 for a given init)."""
+    FIELDS = ("label", "sim", "centroids", "size", "iterations", "converged", "init_rows")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw.get(k))
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    @property
+    def k(self) -> int:
+        return len(self.size)
+
+    @property
+    def objective(self) -> float:
+        """the sum of ``sim`` over the valid rows, in float64"""
+        return float(np.asarray(self.sim, dtype=np.float64)[np.asarray(self.label) >= 0].sum())
+
+    def table(self, names=None):
+        """``sequence.kmeans_table``: one record per cluster, by cluster index"""
+        from . import sequence as S
+        return S.kmeans_table(self, names)
+
+    @classmethod
+    def build(cls, arrays):
+        """from the seven values of ``sequence.spherical_kmeans`` or the library"""
+        label, sim, centroids, size, iterations, converged, init_rows = arrays
+        return cls(label=label, sim=sim, centroids=centroids, size=size, iterations=int(iterations), converged=bool(converged),
+                   init_rows=init_rows)
+
+
 class RepresentativeResult:
     """What :meth:`NNEngine.representatives` returns (the definition is ``sequence.greedy_representatives``), in the caller's index
     space: ``rep`` (int64; a representative names itself, -1 for an invalid row), ``sim`` (float32; a member's similarity to its
@@ -1070,6 +1106,83 @@ class NNEngine:
         ms = np.zeros(n.value, np.float64)
         if n.value:
             check(self.lib.gnn_debug_match_pass_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
+        return ms
+
+    # -- spherical k-means ---------------------------------------------------------------
+    def kmeans(self, rows, k, init=None, max_iter=_sequence.KMEANS_MAX_ITER_DEFAULT) -> KMeansResult:
+        """Spherical k-means among encoder embeddings (``gnn_kmeans``; the definition is ``sequence.spherical_kmeans``): the valid
+        rows of ``rows`` (n, 512) in exactly ``k`` (1..65535, at most the valid rows) groups under cosine similarity, and one unit
+        centroid per group - a new row that stands for it, ordinary input for :meth:`match` and :meth:`neighbours`.  A row's label
+        is its most similar centroid (ties to the smaller index), a centroid the unit vector of the sum of its members' unit rows;
+        assignments and updates alternate on the device until no label changes or ``max_iter`` (0..1000) updates were made, and
+        the labels returned are always the assignment to the centroids returned.  ``init``: (k, 512) valid rows, or None for the
+        farthest-first traversal (no random numbers: the same rows give the same result).  ``label`` / ``sim`` are what
+        :meth:`neighbours` returns for (rows, centroids, k=1), bit for bit; the centroids are sums of exact integers, so a
+        permutation of the rows changes no bit of them.  Not Euclidean k-means, not the dot metric, not k-means++, not
+        mini-batch.  :meth:`set_neighbour_split` sets the range of this search too; no result depends on it."""
+        r = _sequence.neighbour_rows(rows, "rows")
+        k, max_iter = _sequence.kmeans_k(k), _sequence.kmeans_max_iter(max_iter)
+        b = None
+        if init is not None:
+            b = _sequence.neighbour_rows(init, "init")
+            if len(b) != k:
+                raise ValueError(f"init has {len(b)} rows: k = {k} are required")
+            bad = int((~_sequence.valid_rows(b)).sum())
+            if bad:
+                raise ValueError(f"{bad} of the {k} init rows are not valid (finite, norm > 0)")
+        n = len(r)
+        label, sim = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.float32)
+        cent, size, picks = np.empty((k, _lib.EMBED_DIM), dtype=np.float32), np.empty(k, dtype=np.int64), np.empty(k, dtype=np.int64)
+        iterations, converged = C.c_int64(0), C.c_int(0)
+        check(self.lib.gnn_kmeans(self.ctx, r.ctypes.data, n, k, None if b is None else b.ctypes.data, max_iter, label.ctypes.data,
+                                  sim.ctypes.data, cent.ctypes.data, size.ctypes.data, picks.ctypes.data, C.addressof(iterations),
+                                  C.addressof(converged)))
+        return KMeansResult.build((label, sim, cent, size, iterations.value, converged.value, picks))
+
+    def kmeans_dev(self, rows_ptr: int, n: int, k: int, label_ptr: int, sim_ptr: int, centroids_ptr: int, size_ptr: int, init_rows_ptr: int,
+                   init_ptr=None, max_iter=_sequence.KMEANS_MAX_ITER_DEFAULT):
+        """``gnn_kmeans_dev``: device pointers in (rows n x 512 f32; init k x 512 f32 or None) and out (label n int64, sim n f32,
+        centroids k x 512 f32, size k int64, init_rows k int64), enqueued on the engine's stream - which is synchronised once at
+        the start and once per assignment; the arrays are ready when the stream is.  Returns (iterations, converged)."""
+        iterations, converged = C.c_int64(0), C.c_int(0)
+        check(self.lib.gnn_kmeans_dev(self.ctx, rows_ptr, int(n), int(k), init_ptr, int(max_iter), label_ptr, sim_ptr, centroids_ptr,
+                                      size_ptr, init_rows_ptr, C.addressof(iterations), C.addressof(converged)))
+        return int(iterations.value), bool(converged.value)
+
+    def centroids(self, rows, label, k):
+        """One unit row per group (``gnn_centroids``; the definition is ``sequence.group_centroids``): the k-means update alone, for
+        any int64 ``label`` in [-1, k) over ``rows`` (n, 512) - the clusters of :meth:`cluster`, :meth:`density` or
+        :meth:`representatives` after a relabel to 0 .. k - 1.  Label -1 and invalid rows are skipped; a group without members or
+        with a zero sum is a zero row.  Returns (centroids float32 (k, 512), size int64 (k,)); a permutation of the rows changes no
+        bit of either."""
+        r = _sequence.neighbour_rows(rows, "rows")
+        k = _sequence.kmeans_k(k)
+        lab = np.ascontiguousarray(label, dtype=np.int64)
+        if lab.shape != (len(r),):
+            raise ValueError(f"label has the shape {lab.shape}: one label per row ({len(r)}) is required")
+        cent, size = np.full((k, _lib.EMBED_DIM), np.nan, dtype=np.float32), np.full(k, -1, dtype=np.int64)
+        check(self.lib.gnn_centroids(self.ctx, r.ctypes.data, len(r), lab.ctypes.data, k, cent.ctypes.data, size.ctypes.data))
+        return cent, size
+
+    def centroids_dev(self, rows_ptr: int, n: int, label_ptr: int, k: int, centroids_ptr: int, size_ptr: int):
+        """``gnn_centroids_dev``: device pointers in (rows n x 512 f32, label n int64) and out (centroids k x 512 f32, size k
+        int64); the engine's stream is synchronised once (the labels' verdict), the rest is enqueued on it."""
+        check(self.lib.gnn_centroids_dev(self.ctx, rows_ptr, int(n), label_ptr, int(k), centroids_ptr, size_ptr))
+
+    def set_kmeans_lds(self, max_k: int):
+        """test aid (``gnn_debug_set_kmeans_lds``): up to ``max_k`` (0..128, the default) groups the k-means update adds in LDS before it adds to
+        memory; no result depends on it."""
+        check(self.lib.gnn_debug_set_kmeans_lds(self.ctx, int(max_k)))
+
+    def kmeans_pass_ms(self):
+        """measurement only (``gnn_debug_kmeans_pass_ms``): with profiling enabled, the HIP-event milliseconds of the last
+        :meth:`kmeans` / :meth:`kmeans_dev` call - [init, then per assignment: assign, and behind every assignment but the last:
+        update, finish, prepare]"""
+        n = C.c_int64(0)
+        check(self.lib.gnn_debug_kmeans_pass_ms(self.ctx, None, 0, C.addressof(n)))
+        ms = np.zeros(n.value, np.float64)
+        if n.value:
+            check(self.lib.gnn_debug_kmeans_pass_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
         return ms
 
     # -- representatives -----------------------------------------------------------------

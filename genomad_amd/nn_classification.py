@@ -34,7 +34,7 @@ from pathlib import Path
 import numpy as np
 
 from . import sequence
-from ._lib import DEFAULT_PRECISION
+from ._lib import DEFAULT_PRECISION, GnnError
 
 # arithmetic of the fused front end (GENOMAD_AMD_PRECISION overrides): "f16x3tc" = split-f16 limbs with conv2 / conv3 by Toom-Cook
 # minimal filtering, f32-class accuracy - the default, because the TSV prints four decimals and the 1e-4 tolerance has to hold
@@ -98,6 +98,11 @@ class Outputs:
         self.nn_density_tsv_output = d / f"{p}_nn_density.tsv"
         self.provirus_nn_density_output = d / f"{p}_provirus_nn_density.npz"
         self.provirus_nn_density_tsv_output = d / f"{p}_provirus_nn_density.tsv"
+        # written only when GENOMAD_AMD_KMEANS is set (spherical k-means among the per-contig embeddings; no counterpart in the reference)
+        self.nn_kmeans_output = d / f"{p}_nn_kmeans.npz"
+        self.nn_kmeans_tsv_output = d / f"{p}_nn_kmeans.tsv"
+        self.provirus_nn_kmeans_output = d / f"{p}_provirus_nn_kmeans.npz"
+        self.provirus_nn_kmeans_tsv_output = d / f"{p}_provirus_nn_kmeans.tsv"
         # written only when GENOMAD_AMD_REPRESENTATIVES is set (greedy clusters among the per-contig embeddings; no counterpart in the reference)
         self.nn_representatives_output = d / f"{p}_nn_representatives.npz"
         self.nn_representatives_tsv_output = d / f"{p}_nn_representatives.tsv"
@@ -717,6 +722,71 @@ def write_density(npz_path, tsv_path, names_key, names, res, strand="forward"):
     write_density_tsv(tsv_path, names, res)
 
 
+def kmeans_requested():
+    """GENOMAD_AMD_KMEANS=<integer in [1, 65535]>: main() also writes the spherical k-means of the contigs - exactly that many groups
+    under the cosine similarity of the per-contig encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1, and one centroid per group
+    (<prefix>_nn_kmeans.npz and .tsv); unset or empty: nothing changes (None).  GENOMAD_AMD_KMEANS_MAX_ITER=<integer in [0, 1000]>
+    (default 50) bounds the updates; it is an error without GENOMAD_AMD_KMEANS.  Any other value of either is an error.  Returns
+    (k, max_iter), or None."""
+    v = os.environ.get("GENOMAD_AMD_KMEANS", "").strip()
+    m = os.environ.get("GENOMAD_AMD_KMEANS_MAX_ITER", "").strip()
+    if not v:
+        if m:
+            raise ValueError(f"GENOMAD_AMD_KMEANS_MAX_ITER={m!r} needs GENOMAD_AMD_KMEANS: set the number of groups or unset "
+                             "GENOMAD_AMD_KMEANS_MAX_ITER")
+        return None
+    try:
+        k = int(v)
+    except ValueError:
+        k = 0
+    if not 1 <= k <= sequence.KMEANS_K_MAX:
+        raise ValueError(f"GENOMAD_AMD_KMEANS={v!r}: expected an integer in [1, {sequence.KMEANS_K_MAX}] (the number of groups)")
+    try:
+        it = int(m) if m else sequence.KMEANS_MAX_ITER_DEFAULT
+    except ValueError:
+        it = -1
+    if not 0 <= it <= sequence.KMEANS_MAX_ITER_MAX:
+        raise ValueError(f"GENOMAD_AMD_KMEANS_MAX_ITER={m!r}: expected an integer in [0, {sequence.KMEANS_MAX_ITER_MAX}] (the centroid "
+                         "updates at the most)")
+    return k, it
+
+
+def _kmeans_of_file(path):
+    """The (k, max_iter) a stage's k-means file was computed with; no file = None (no k-means was asked for)."""
+    if not Path(path).exists():
+        return None
+    try:
+        z = np.load(path)
+        return int(z["k"]), int(z["max_iter"])
+    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
+        return -1, -1
+
+
+KMEANS_TSV_HEADER = "seq_name\tcluster\tcluster_size\tsimilarity\n"
+
+
+def write_kmeans_tsv(path, names, res):
+    """One line per contig of a KMeansResult: the index of its cluster, the cluster's size and the contig's similarity to the
+    cluster's centroid; a contig without a valid embedding has NA, 0, NA."""
+    with open(path, "w") as fout:
+        fout.write(KMEANS_TSV_HEADER)
+        for i, name in enumerate(names):
+            if res.label[i] < 0:
+                fout.write(f"{name}\tNA\t0\tNA\n")
+            else:
+                fout.write(f"{name}\t{res.label[i]}\t{res.size[res.label[i]]}\t{res.sim[i]:.6f}\n")
+
+
+def write_kmeans(npz_path, tsv_path, names_key, names, res, max_iter, strand="forward"):
+    """Both k-means files of a stage: the arrays of a KMeansResult with the contig names, and one line per contig."""
+    np.savez_compressed(npz_path, **{names_key: names, "k": np.int64(res.k), "max_iter": np.int64(max_iter), "metric": np.array("cosine"),
+                                     "label": res.label, "sim": res.sim, "centroids": res.centroids, "size": res.size,
+                                     "iterations": np.int64(res.iterations), "converged": np.bool_(res.converged),
+                                     "init_rows": res.init_rows, "objective": np.float64(res.objective),
+                                     **({"strand": np.array(strand)} if strand != "forward" else {})})
+    write_kmeans_tsv(tsv_path, names, res)
+
+
 def representatives_requested():
     """GENOMAD_AMD_REPRESENTATIVES=<float in [-1, 1]>: main() also writes the greedy clusters of the contigs at that cosine similarity of
     the per-contig encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1 - contigs walked by their number of kept windows, the larger first,
@@ -1094,6 +1164,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     neighbours_k = neighbours_requested()
     clusters_threshold = clusters_requested()
     density_request = density_requested()
+    kmeans_request = kmeans_requested()
     representatives_threshold = representatives_requested()
     linkage = linkage_requested()
     graph_threshold = graph_requested()
@@ -1144,6 +1215,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     if density_request is not None and not embeddings:
         console.error("GENOMAD_AMD_DENSITY needs GENOMAD_AMD_EMBEDDINGS=1: density clusters are formed among the per-contig encoder "
                       "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_DENSITY.")
+        sys.exit(1)
+    if kmeans_request is not None and not embeddings:
+        console.error("GENOMAD_AMD_KMEANS needs GENOMAD_AMD_EMBEDDINGS=1: the groups are formed among the per-contig encoder "
+                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_KMEANS.")
         sys.exit(1)
     if representatives_threshold is not None and not embeddings:
         console.error("GENOMAD_AMD_REPRESENTATIVES needs GENOMAD_AMD_EMBEDDINGS=1: representatives are chosen among the per-contig encoder "
@@ -1363,6 +1438,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         ``density_files[what]`` (npz, tsv; GENOMAD_AMD_DENSITY with the optional GENOMAD_AMD_DENSITY_MIN_POINTS, which need the
         embeddings): rank 0 forms the density clusters (NNEngine.density, cosine) of the same gathered embeddings and writes both
         files.  They follow the clusters files' rule, with (threshold, min_points) in place of the threshold.
+        ``kmeans_files[what]`` (npz, tsv; GENOMAD_AMD_KMEANS with the optional GENOMAD_AMD_KMEANS_MAX_ITER, which need the embeddings):
+        rank 0 runs the spherical k-means (NNEngine.kmeans, farthest-first init) of the same gathered embeddings and writes both
+        files.  They follow the clusters files' rule, with (k, max_iter) in place of the threshold.
         ``match_files[what]`` (npz, tsv; GENOMAD_AMD_MATCH with GENOMAD_AMD_MATCH_BASE, which need the embeddings): rank 0 matches the
         same gathered embeddings (query) against the reference's (base; NNEngine.match, cosine) and writes both files.  They follow
         the clusters files' rule, and the reference's names must be those the file was computed against.
@@ -1378,6 +1456,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         linkage_path, linkage_tsv_path = linkage_paths
         graph_path, graph_tsv_path = graph_files[what]
         density_path, density_tsv_path = density_files[what]
+        kmeans_path, kmeans_tsv_path = kmeans_files[what]
         match_path, match_tsv_path = match_files[what]
         regions_path, regions_tsv_path = regions_paths
         regions_request = None if region_penalty is None else (scan_stride, region_penalty)
@@ -1403,6 +1482,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                  and _density_of_file(density_path) == density_request
                                  and (density_request is None) == (not density_tsv_path.exists())
                                  and (density_request is None or _npz_strand(density_path) == strand)
+                                 and _kmeans_of_file(kmeans_path) == kmeans_request
+                                 and (kmeans_request is None) == (not kmeans_tsv_path.exists())
+                                 and (kmeans_request is None or _npz_strand(kmeans_path) == strand)
                                  and _clusters_of_file(match_path) == match_threshold
                                  and (match_threshold is None) == (not match_tsv_path.exists())
                                  and (match_threshold is None or (_npz_strand(match_path) == strand
@@ -1660,6 +1742,20 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     for p in (density_path, density_tsv_path):
                         if p.exists():
                             p.unlink()
+                if kmeans_request is not None:
+                    try:
+                        res = eng.kmeans(embeddings_all, kmeans_request[0], None, kmeans_request[1])
+                    except (ValueError, GnnError) as e:         # more groups than contigs with a valid embedding
+                        console.error(f"GENOMAD_AMD_KMEANS={kmeans_request[0]}: {e}. Lower GENOMAD_AMD_KMEANS or unset it.")
+                        sys.exit(1)
+                    write_kmeans(kmeans_path, kmeans_tsv_path, names_key, names, res, kmeans_request[1], strand)
+                    console.log(f"Spherical k-means of the {what}s ({NEIGHBOUR_METRIC} similarity of the encoder embeddings: "
+                                f"{kmeans_request[0]} groups, {res.iterations} updates, {'converged' if res.converged else 'not converged'}, "
+                                f"objective {res.objective:.3f}) written to {kmeans_path.name} and {kmeans_tsv_path.name}.")
+                else:                               # likewise, both files
+                    for p in (kmeans_path, kmeans_tsv_path):
+                        if p.exists():
+                            p.unlink()
                 if match_threshold is not None:
                     base_names, base_rows = match_base
                     try:
@@ -1687,6 +1783,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                    "provirus": (outputs.provirus_nn_graph_output, outputs.provirus_nn_graph_tsv_output)}
     density_files = {"sequence": (outputs.nn_density_output, outputs.nn_density_tsv_output),
                      "provirus": (outputs.provirus_nn_density_output, outputs.provirus_nn_density_tsv_output)}
+    kmeans_files = {"sequence": (outputs.nn_kmeans_output, outputs.nn_kmeans_tsv_output),
+                    "provirus": (outputs.provirus_nn_kmeans_output, outputs.provirus_nn_kmeans_tsv_output)}
     match_files = {"sequence": (outputs.nn_matches_output, outputs.nn_matches_tsv_output),
                    "provirus": (outputs.provirus_nn_matches_output, outputs.provirus_nn_matches_tsv_output)}
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})

@@ -1373,6 +1373,173 @@ def linkage_table(a, b, sim, n_valid, names=None):
             for k in range(len(a))]
 
 
+KMEANS_FIELDS = ("label", "sim", "centroids", "size", "iterations", "converged", "init_rows")
+KMEANS_K_MAX = 65535
+KMEANS_MAX_ITER_MAX = 1000
+KMEANS_MAX_ITER_DEFAULT = 50
+
+
+def _whole(value, what, lo, hi) -> int:
+    """``value`` as an int in [lo, hi] (a bool or a float with a fraction is a ValueError)"""
+    ok = not isinstance(value, (bool, np.bool_))
+    try:
+        v = int(value) if ok else 0
+        ok = ok and v == value
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok or not lo <= v <= hi:
+        raise ValueError(f"{what} {value!r}: an integer in [{lo}, {hi}] is required")
+    return v
+
+
+def kmeans_k(k) -> int:
+    return _whole(k, "k", 1, KMEANS_K_MAX)
+
+
+def kmeans_max_iter(max_iter) -> int:
+    return _whole(max_iter, "max_iter", 0, KMEANS_MAX_ITER_MAX)
+
+
+def _unit_rows(r32):
+    """(the rows as float64 unit vectors - zero where the row is not valid -, the valid rows) as :func:`nearest_neighbours` has them"""
+    ok = np.isfinite(r32).all(axis=1)
+    r = np.where(ok[:, None], r32, 0).astype(np.float64)
+    norm = np.sqrt((r * r).sum(axis=1))
+    ok &= norm > 0
+    return r / np.where(ok, norm, 1.0)[:, None], ok
+
+
+def farthest_first(unit, ok, k) -> np.ndarray:
+    """The farthest-first traversal of :func:`spherical_kmeans` over float64 unit rows: int64 (k,) row indices.  The first centre is
+    the valid row of smallest index, every next one the valid row, not yet picked, whose largest similarity to the centres so far
+    is smallest - ties to the smaller row index."""
+    cand = np.flatnonzero(ok)
+    picks = [int(cand[0])]
+    best = unit[cand] @ unit[picks[0]]                  # per candidate: its largest similarity to a centre so far
+    free = np.ones(len(cand), dtype=bool)
+    free[0] = False
+    while len(picks) < k:
+        j = int(np.flatnonzero(free)[np.argmin(best[free])])       # argmin: the first = the smallest index among equals
+        picks.append(int(cand[j]))
+        free[j] = False
+        best = np.maximum(best, unit[cand] @ unit[cand[j]])
+    return np.asarray(picks, dtype=np.int64)
+
+
+def spherical_kmeans(rows, k, init=None, max_iter=KMEANS_MAX_ITER_DEFAULT, trace=None):
+    """Spherical k-means among encoder embeddings, spelled out (the definition ``gnn_kmeans`` computes on the device; float64
+    throughout, readable, not fast).  ``rows`` (n, 512) float32, cosine only; the valid rows are exactly those of
+    :func:`nearest_neighbours` under cosine, and an invalid row has label -1, sim NaN and contributes to nothing.  1 <= ``k`` <=
+    min(valid rows, 65535); 0 <= ``max_iter`` <= 1000.
+
+    *Assignment*: a row's label is the centroid with the largest cosine, ties to the smaller centroid index.  *Update*: centroid c
+    becomes the unit vector of the sum of its members' unit rows; a centroid without members, or whose sum is exactly zero, keeps
+    its previous value.  *Loop*: label = assign(centroids); stop if no label changed against the previous assignment (``converged``)
+    or ``iterations`` == ``max_iter``; otherwise centroids = update(label), ``iterations`` += 1, again.  The labels returned are
+    therefore always the assignment to the centroids returned; ``max_iter`` = 0 is a pure assignment to ``init``.
+
+    ``init``: a (k, 512) array whose rows are all valid (their unit rows are the first centroids), or None - the farthest-first
+    traversal of :func:`farthest_first`; no random number is drawn.  ``trace``: a list that receives, per assignment, a dict of its
+    ``label``, its ``objective`` and its ``gap`` (the smallest distance between a valid row's best and second-best similarity; inf
+    for k = 1).
+
+    Returns ``label`` (int64 (n,)), ``sim`` (float32 (n,): the similarity to the row's own centroid), ``centroids`` (float32
+    (k, 512), unit rows), ``size`` (int64 (k,): the members, 0 for a centroid nobody chose), ``iterations`` (int), ``converged``
+    (bool) and ``init_rows`` (int64 (k,): the rows the traversal picked, -1 for a given ``init``)."""
+    r32 = neighbour_rows(rows, "rows")
+    k, max_iter = kmeans_k(k), kmeans_max_iter(max_iter)
+    unit, ok = _unit_rows(r32)
+    n, valid = len(r32), np.flatnonzero(ok)
+    if k > len(valid):
+        raise ValueError(f"k {k} is more than the {len(valid)} valid rows of {n}")
+    if init is None:
+        init_rows = farthest_first(unit, ok, k)
+        centroids = unit[init_rows].copy()
+    else:
+        i32 = neighbour_rows(init, "init")
+        centroids, i_ok = _unit_rows(i32)
+        if len(i32) != k:
+            raise ValueError(f"init has {len(i32)} rows: k = {k} are required")
+        if not i_ok.all():
+            raise ValueError(f"{int((~i_ok).sum())} of the {k} init rows are not valid (finite, norm > 0)")
+        init_rows = np.full(k, -1, dtype=np.int64)
+    label = np.full(n, -1, dtype=np.int64)
+    sim = np.full(n, np.nan, dtype=np.float64)
+    previous, iterations, converged = None, 0, False
+    while True:
+        s = unit[valid] @ centroids.T
+        best = np.argmax(s, axis=1)                     # argmax: the first = the smaller centroid among equals
+        label[valid], sim[valid] = best, s[np.arange(len(valid)), best]
+        if trace is not None:
+            top = np.sort(s, axis=1)[:, -2:]
+            trace.append({"label": label.copy(), "objective": float(sim[valid].sum()),
+                          "gap": float((top[:, 1] - top[:, 0]).min()) if k > 1 else float("inf")})
+        if previous is not None and np.array_equal(label, previous):
+            converged = True
+            break
+        if iterations == max_iter:
+            break
+        previous = label.copy()
+        for c in range(k):
+            total = unit[valid[best == c]].sum(axis=0)
+            norm = np.sqrt((total * total).sum())
+            if (best == c).any() and norm > 0:
+                centroids[c] = total / norm
+        iterations += 1
+    size = np.bincount(label[valid], minlength=k).astype(np.int64)
+    return label, sim.astype(np.float32), centroids.astype(np.float32), size, iterations, converged, init_rows
+
+
+def group_centroids(rows, label, k):
+    """One unit row per group of ``label``, spelled out (the definition ``gnn_centroids`` computes on the device; float64): the
+    update of :func:`spherical_kmeans` alone, for any int64 labels in [-1, k).  ``rows`` (n, 512) float32; label -1 and invalid
+    rows are skipped; centroid c is the unit vector of the sum of its members' unit rows, a zero row for a group without members
+    or with a zero sum.  Returns ``centroids`` (float32 (k, 512)) and ``size`` (int64 (k,): the valid members)."""
+    r32 = neighbour_rows(rows, "rows")
+    k = kmeans_k(k)
+    label = np.asarray(label)
+    if label.shape != (len(r32),) or label.dtype.kind not in "iu":
+        raise ValueError(f"label has the shape {label.shape} and the type {label.dtype}: one integer per row is required")
+    label = label.astype(np.int64)
+    if len(label) and (label.min() < -1 or label.max() >= k):
+        raise ValueError(f"a label is outside [-1, {k})")
+    unit, ok = _unit_rows(r32)
+    centroids = np.zeros((k, NEIGHBOUR_DIM), dtype=np.float64)
+    size = np.zeros(k, dtype=np.int64)
+    for c in range(k):
+        members = np.flatnonzero(ok & (label == c))
+        total = unit[members].sum(axis=0)
+        norm = np.sqrt((total * total).sum())
+        size[c] = len(members)
+        if len(members) and norm > 0:
+            centroids[c] = total / norm
+    return centroids.astype(np.float32), size
+
+
+def kmeans_table(result, names=None):
+    """One record per cluster of a :func:`spherical_kmeans` result (its tuple, a dict of its fields, or anything with them as
+    attributes), by cluster index: ``cluster``, ``size``, ``mean_sim`` (the members' mean similarity to the centroid) and
+    ``nearest`` (the member most similar to it, ties to the smaller index; its name where ``names`` is given); ``mean_sim`` and
+    ``nearest`` are None for a cluster without members."""
+    if isinstance(result, dict):
+        label, sim, size = (result[f] for f in ("label", "sim", "size"))
+    elif isinstance(result, (tuple, list)):
+        label, sim, size = result[0], result[1], result[3]
+    else:
+        label, sim, size = (getattr(result, f) for f in ("label", "sim", "size"))
+    label, sim = np.asarray(label, dtype=np.int64), np.asarray(sim, dtype=np.float64)
+    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    out = []
+    for c in range(len(size)):
+        members = np.flatnonzero(label == c)
+        if len(members):
+            out.append({"cluster": c, "size": int(size[c]), "mean_sim": float(sim[members].mean()),
+                        "nearest": name(members[np.argmax(sim[members])])})
+        else:
+            out.append({"cluster": c, "size": int(size[c]), "mean_sim": None, "nearest": None})
+    return out
+
+
 def prefix_of(input_path: Path) -> str:
     """nn_classification.py:106-108: stem, minus one more extension if the file is compressed."""
     prefix = Path(input_path).stem

@@ -814,6 +814,58 @@ int gnn_match_fill_dev(gnn_ctx* ctx, const float* query_dev, int64_t n_query, co
  * workspace's: those of the last count of either kind). */
 int gnn_debug_match_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
 
+/* ---- spherical k-means among encoder embeddings: centroids on the device ------------------------------------
+ * "Exactly k groups, and one new row that stands for each": a partition of the valid rows into k groups under cosine similarity and
+ * one unit centroid per group (the definition is sequence.spherical_kmeans).  Validity is gnn_neighbours' under cosine; an invalid row
+ * has label -1, sim NaN and contributes to nothing; no forward pass runs and no other entry point's result changes.
+ *   assign    a row's label is the centroid with the largest similarity, ties to the smaller centroid index.  The similarity of (row i,
+ *             centroid c) is the f32 that gnn_neighbours returns for query i and base row c of the centroid table.
+ *   update    centroid c becomes the unit vector of the sum of its members' unit rows; a centroid without members, or whose sum is
+ *             exactly zero, keeps its row bit for bit.  The sums are int64 sums of 32-bit fixed-point images of the rows' unit vectors
+ *             (exact, a pure function of each row): no order of execution changes a bit of a centroid - a permutation of the rows
+ *             gives the same table.  The norm is summed in float64 in a fixed order and the quotient rounded to f32 once.
+ *   loop      label = assign(centroids); stop when no label changed against the previous assignment (*converged_host = 1) or after
+ *             max_iter updates; otherwise centroids = update(label), *iterations_host += 1, again.  The labels returned are ALWAYS the
+ *             assignment to the centroids returned; max_iter = 0 is a pure assignment to the init's unit rows.
+ *   init      init (k x 512 f32, every row valid): its unit rows.  NULL: farthest-first traversal - the first centre is the valid row
+ *             of smallest index, every next one the valid unpicked row whose largest similarity to the centres so far is smallest,
+ *             ties to the smaller row index; the similarities are gnn_neighbours' for (row, that centre alone as the base).  No random
+ *             number is drawn anywhere.  init_rows (int64 [k]): the rows picked, -1 for a given init.
+ *   outputs   label int64 [n], sim f32 [n] (to the row's own centroid), centroids f32 [k][512] (unit rows), size int64 [k] (the
+ *             members under the labels returned; 0 for a centroid nobody chose).
+ *   ranges    0 <= n <= 2^30 (the int64 sums of more rows could overflow: |image| < 2^33), 1 <= k <= 65535, 0 <= max_iter <= 1000;
+ *             GNN_ERR_ARG with the value and the range - checked before the ctx is looked at.  k more than the valid rows, or an init
+ *             row that is not valid: GNN_ERR_ARG after one synchronise, nothing written.
+ *   exact     integer add / max / min atomics only: bit-identical for every split of the centroids (gnn_debug_set_neighbour_split), for
+ *             both paths of the update (gnn_debug_set_kmeans_lds) and for the host and _dev entry points.
+ * gnn_centroids: the update alone, for ANY int64 labels in [-1, k) - one unit row per cluster of gnn_cluster / gnn_density /
+ * gnn_representatives after a host-side relabel to 0 .. k - 1.  Label -1 and invalid rows are skipped; a group without members or with a
+ * zero sum is a zero row, size = the valid members.  A label outside [-1, k): GNN_ERR_ARG, found on the device and reported after one
+ * synchronise, nothing written.
+ * What it is not: not Euclidean k-means and not the dot metric (rows are compared and summed as unit vectors); not k-means++ (no random
+ * numbers); not mini-batch (every update sums every row); no width other than GNN_EMBED_DIM; not multi-GPU.
+ * Device memory, persistent in the ctx and grow-only: per row the 2 KB of fragments + 1 B of the neighbour search (shared with it) and
+ * 8 B (9 B under the farthest-first init); per centroid 2 KB + 1 B of fragments and 4 KB + 8 B of sums; 128 KB for the init.  Nothing is
+ * n x k.  gnn_kmeans / gnn_centroids: host pointers, synchronous.  gnn_kmeans_dev: device pointers, iterations and converged on the host;
+ * the ctx stream is synchronised once at the start and once per assignment (8 bytes each).  gnn_centroids_dev: device pointers, one
+ * synchronise, then asynchronous on the ctx stream like gnn_classify_dev. */
+int gnn_kmeans(gnn_ctx* ctx, const float* rows_host, int64_t n, int k, const float* init_host_or_null, int max_iter, int64_t* label_host,
+               float* sim_host, float* centroids_host, int64_t* size_host, int64_t* init_rows_host, int64_t* iterations_host,
+               int* converged_host);
+int gnn_kmeans_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, int k, const float* init_dev_or_null, int max_iter, int64_t* label_dev,
+                   float* sim_dev, float* centroids_dev, int64_t* size_dev, int64_t* init_rows_dev, int64_t* iterations_host,
+                   int* converged_host);
+int gnn_centroids(gnn_ctx* ctx, const float* rows_host, int64_t n, const int64_t* label_host, int k, float* centroids_host,
+                  int64_t* size_host);
+int gnn_centroids_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, const int64_t* label_dev, int k, float* centroids_dev,
+                      int64_t* size_dev);
+/* test aid: up to max_k groups (0 .. 128, default 128) a workgroup of the update adds in LDS, 16 at a time, before it adds to memory;
+ * 0: every add goes straight to memory.  No result depends on it. */
+int gnn_debug_set_kmeans_lds(gnn_ctx* ctx, int max_k);
+/* measurement only: with profiling enabled, the HIP-event milliseconds of the ctx's last gnn_kmeans* call - [init, then per assignment:
+ * assign, and behind every assignment but the last: update, finish, prepare] - as gnn_debug_graph_pass_ms. */
+int gnn_debug_kmeans_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
+
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
  * in-memory text buffer (already decompressed, newlines normalised to '\n').
