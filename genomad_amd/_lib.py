@@ -153,6 +153,12 @@ SIGNATURES = {
     "gnn_centroids_dev": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp]),
     "gnn_debug_set_kmeans_lds": (_int, [_vp, _int]),
     "gnn_debug_kmeans_pass_ms": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_pca_moments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "gnn_pca_moments_dev": (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "gnn_pca_project": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp]),
+    "gnn_pca_project_dev": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp]),
+    "gnn_debug_set_pca_split": (_int, [_vp, _i64]),
+    "gnn_debug_pca_pass_ms": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_embed": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_embed_dev": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "gnn_debug_forward": (_int, [_vp, _vp, _i64, _int, _vp, C.POINTER(Taps)]),

@@ -304,6 +304,20 @@ struct KMeansWorkspace {
                                                  // and behind every assignment but the last: update, finish, prepare]
 };
 
+// ---- principal components (gnn_pca.hip): persistent, grow-only.  The rows' fragments and flags are NeighbourWorkspace's bfrag / bvalid
+// (and d_base for the host entry points); here the components' 128 KB of fragments and, for the host entry points alone, their
+// arguments and results.  Nothing here grows with n but gnn_pca_project's own output.
+struct PCAWorkspace {
+    int64_t split = 0;                           // rows per workgroup of the Gram pass (gnn_debug_set_pca_split): a multiple of 256; 0: the library's choice; no result depends on it
+    DevBuf<uint4> cfrag;                         // the components' fragments, as NeighbourWorkspace's
+    DevBuf<uint8_t> cvalid;
+    DevBuf<int64_t> d_mom;                       // gnn_pca_moments: [G 512 x 512 | S 512 | n_valid]
+    DevBuf<float> d_comp;                        // gnn_pca_project: [components 64 x 512 | off 64]
+    DevBuf<float> d_out;                         // gnn_pca_project: [n][ncomp]
+    std::vector<RoundTimer> pending;             // profiling on: the last call's passes, filed by gnn_debug_pca_pass_ms behind a synchronise
+    std::vector<float> pass_ms;                  // moments: [prepare, sums, gram, mirror]; project: [prepare rows, prepare components, project]
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -495,6 +509,7 @@ struct gnn_ctx {
     gnn::LinkageWorkspace lk;                     // gnn_linkage.hip
     gnn::GraphWorkspace gr;                       // gnn_graph.hip
     gnn::KMeansWorkspace km;                      // gnn_kmeans.hip
+    gnn::PCAWorkspace pca;                        // gnn_pca.hip
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;

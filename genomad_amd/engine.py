@@ -255,6 +255,37 @@ class KMeansResult:
                    init_rows=init_rows)
 
 
+class PCAResult:
+    """What :meth:`NNEngine.pca` returns: ``mean`` (float64 (512,): the mean of the valid rows' unit vectors; zeros for
+    ``center=False``), ``components`` (float32 (c, 512), unit rows, by eigenvalue descending, the entry of largest magnitude
+    positive), ``explained_variance`` / ``explained_variance_ratio`` (float64 (c,)), ``total_variance``, ``n_valid``, ``valid``
+    (bool (n,)) and ``projection`` (float32 (n, c): the rows' scores, NaN for an invalid row)."""
+    FIELDS = ("mean", "components", "explained_variance", "explained_variance_ratio", "total_variance", "n_valid", "valid", "projection")
+
+    def __init__(self, engine=None, **kw):
+        self._engine = engine
+        for k in self.FIELDS:
+            setattr(self, k, kw.get(k))
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    @property
+    def n_components(self) -> int:
+        return len(self.components)
+
+    def transform(self, rows) -> np.ndarray:
+        """new rows onto the same axes (float32 (m, c)): :meth:`NNEngine.project` with this result's components and mean"""
+        if self._engine is None:
+            raise ValueError("this PCAResult has no engine: call NNEngine.project(rows, result.components, result.mean)")
+        return self._engine.project(rows, self.components, self.mean)
+
+    def table(self, names=None):
+        """``sequence.pca_table``: one record per row"""
+        from . import sequence as S
+        return S.pca_table(self.projection, self.valid, names)
+
+
 class RepresentativeResult:
     """What :meth:`NNEngine.representatives` returns (the definition is ``sequence.greedy_representatives``), in the caller's index
     space: ``rep`` (int64; a representative names itself, -1 for an invalid row), ``sim`` (float32; a member's similarity to its
@@ -1183,6 +1214,82 @@ class NNEngine:
         ms = np.zeros(n.value, np.float64)
         if n.value:
             check(self.lib.gnn_debug_kmeans_pass_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
+        return ms
+
+    # -- principal components ------------------------------------------------------------
+    def pca_moments(self, rows):
+        """The second moments of the unit rows (``gnn_pca_moments``; the definition is ``sequence.pca_moments``): ``G`` (float64
+        (512, 512): the sum of u uT over the valid rows' unit vectors), ``S`` (float64 (512,): the sum of u) and ``n_valid``.  The
+        device sums int64 fixed-point values in units of 2^-32 - S exactly, G from f32 product chains over granules of 256 rows
+        turned into integers once - so no bit depends on how the rows are split over workgroups (:meth:`set_pca_split`).
+        :meth:`pca_moments_fixed` returns the integers themselves."""
+        G, S, n_valid = self.pca_moments_fixed(rows)
+        return G.astype(np.float64) / 2.0 ** 32, S.astype(np.float64) / 2.0 ** 32, n_valid
+
+    def pca_moments_fixed(self, rows):
+        """:meth:`pca_moments` as the library returns it: int64 ``G`` (512, 512) and ``S`` (512,) in units of 2^-32, and ``n_valid``"""
+        r = _sequence.neighbour_rows(rows, "rows")
+        if not 1 <= len(r) <= _sequence.PCA_ROWS_MAX:
+            raise ValueError(f"{len(r)} rows: 1 to 2^30 are required")
+        G, S = np.empty((_lib.EMBED_DIM, _lib.EMBED_DIM), dtype=np.int64), np.empty(_lib.EMBED_DIM, dtype=np.int64)
+        n_valid = C.c_int64(0)
+        check(self.lib.gnn_pca_moments(self.ctx, r.ctypes.data, len(r), G.ctypes.data, S.ctypes.data, C.addressof(n_valid)))
+        return G, S, int(n_valid.value)
+
+    def pca_moments_dev(self, rows_ptr: int, n: int, G_ptr: int, S_ptr: int, n_valid_ptr: int):
+        """``gnn_pca_moments_dev``: device pointers in (rows n x 512 f32) and out (G 512 x 512 int64, S 512 int64, n_valid 1 int64,
+        all in units of 2^-32 but the last), enqueued on the engine's stream."""
+        check(self.lib.gnn_pca_moments_dev(self.ctx, rows_ptr, int(n), G_ptr, S_ptr, n_valid_ptr))
+
+    def project(self, rows, components, mean=None) -> np.ndarray:
+        """Scores of ``rows`` (n, 512) on ``components`` (c, 512; 1 <= c <= 64 valid rows: directions, renormalised)
+        (``gnn_pca_project``; the definition is ``sequence.pca_project``): float32 (n, c), the f32 cosine that :meth:`neighbours`
+        returns for (row, component) minus ``mean`` . component - computed in float64 on the host and rounded to f32 once, then one
+        f32 subtraction per value on the device -; NaN for an invalid row.  ``mean`` None: the cosines themselves."""
+        r = _sequence.neighbour_rows(rows, "rows")
+        if not 1 <= len(r) <= _sequence.PCA_ROWS_MAX:
+            raise ValueError(f"{len(r)} rows: 1 to 2^30 are required")
+        c32, _ = _sequence.pca_directions(components)
+        off = None if mean is None else np.ascontiguousarray(_sequence.pca_offsets(c32, mean), dtype=np.float32)
+        out = np.empty((len(r), len(c32)), dtype=np.float32)
+        check(self.lib.gnn_pca_project(self.ctx, r.ctypes.data, len(r), c32.ctypes.data, len(c32), None if off is None else off.ctypes.data,
+                                       out.ctypes.data))
+        return out
+
+    def project_dev(self, rows_ptr: int, n: int, components_ptr: int, ncomp: int, out_ptr: int, off_ptr=None):
+        """``gnn_pca_project_dev``: device pointers in (rows n x 512 f32, components ncomp x 512 f32, off ncomp f32 or None) and
+        out (n x ncomp f32), enqueued on the engine's stream."""
+        check(self.lib.gnn_pca_project_dev(self.ctx, rows_ptr, int(n), components_ptr, int(ncomp), off_ptr, out_ptr))
+
+    def pca(self, rows, n_components=2, center=True) -> PCAResult:
+        """Principal components among encoder embeddings: the directions of largest variance of the valid rows' UNIT vectors - the
+        geometry every search here works in - and the rows' scores on them.  :meth:`pca_moments` on the device, the 512 x 512
+        eigenproblem on the host (``sequence.pca_from_moments``, float64: the matrix is 2 MB whatever n is), :meth:`project` on the
+        device.  1 <= ``n_components`` <= 64; fewer than two valid rows is a ValueError.  ``center=False``: the second moments about
+        the origin.  Not PCA of the raw (un-normalised) rows, not kernel PCA, not t-SNE / UMAP."""
+        r = _sequence.neighbour_rows(rows, "rows")
+        c = _sequence.pca_components(n_components)
+        G, S, n_valid = self.pca_moments(r)
+        m = _sequence.pca_from_moments(G, S, n_valid, c, center)
+        comp = np.ascontiguousarray(m["components"], dtype=np.float32)
+        proj = self.project(r, comp, m["mean"] if center else None)
+        return PCAResult(engine=self, mean=m["mean"], components=comp, explained_variance=m["explained_variance"],
+                         explained_variance_ratio=m["explained_variance_ratio"], total_variance=m["total_variance"], n_valid=n_valid,
+                         valid=~np.isnan(proj[:, 0]), projection=proj)
+
+    def set_pca_split(self, rows: int):
+        """test aid (``gnn_debug_set_pca_split``): the rows a workgroup of the Gram pass takes, a multiple of 256; 0 = the
+        library's choice; no result depends on it."""
+        check(self.lib.gnn_debug_set_pca_split(self.ctx, int(rows)))
+
+    def pca_pass_ms(self):
+        """measurement only (``gnn_debug_pca_pass_ms``): with profiling enabled, the HIP-event milliseconds of the last moments
+        call - [prepare, sums, gram, mirror] - or projection - [prepare rows, prepare components, project]"""
+        n = C.c_int64(0)
+        check(self.lib.gnn_debug_pca_pass_ms(self.ctx, None, 0, C.addressof(n)))
+        ms = np.zeros(n.value, np.float64)
+        if n.value:
+            check(self.lib.gnn_debug_pca_pass_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
         return ms
 
     # -- representatives -----------------------------------------------------------------

@@ -103,6 +103,11 @@ class Outputs:
         self.nn_kmeans_tsv_output = d / f"{p}_nn_kmeans.tsv"
         self.provirus_nn_kmeans_output = d / f"{p}_provirus_nn_kmeans.npz"
         self.provirus_nn_kmeans_tsv_output = d / f"{p}_provirus_nn_kmeans.tsv"
+        # written only when GENOMAD_AMD_PCA is set (principal components among the per-contig embeddings; no counterpart in the reference)
+        self.nn_pca_output = d / f"{p}_nn_pca.npz"
+        self.nn_pca_tsv_output = d / f"{p}_nn_pca.tsv"
+        self.provirus_nn_pca_output = d / f"{p}_provirus_nn_pca.npz"
+        self.provirus_nn_pca_tsv_output = d / f"{p}_provirus_nn_pca.tsv"
         # written only when GENOMAD_AMD_REPRESENTATIVES is set (greedy clusters among the per-contig embeddings; no counterpart in the reference)
         self.nn_representatives_output = d / f"{p}_nn_representatives.npz"
         self.nn_representatives_tsv_output = d / f"{p}_nn_representatives.tsv"
@@ -787,6 +792,55 @@ def write_kmeans(npz_path, tsv_path, names_key, names, res, max_iter, strand="fo
     write_kmeans_tsv(tsv_path, names, res)
 
 
+def pca_requested():
+    """GENOMAD_AMD_PCA=<integer in [1, 64]>: main() also writes that many principal components of the contigs' per-contig encoder
+    embeddings of GENOMAD_AMD_EMBEDDINGS=1 - of their unit vectors, the geometry every search works in - and every contig's scores
+    on them (<prefix>_nn_pca.npz and .tsv); unset or empty: nothing changes (None).  Any other value is an error.  Returns the
+    number of components, or None."""
+    v = os.environ.get("GENOMAD_AMD_PCA", "").strip()
+    if not v:
+        return None
+    try:
+        c = int(v)
+    except ValueError:
+        c = 0
+    if not 1 <= c <= sequence.PCA_COMPONENTS_MAX:
+        raise ValueError(f"GENOMAD_AMD_PCA={v!r}: expected an integer in [1, {sequence.PCA_COMPONENTS_MAX}] (the number of components)")
+    return c
+
+
+def _pca_of_file(path):
+    """The number of components a stage's PCA file was computed with; no file = None (no PCA was asked for)."""
+    if not Path(path).exists():
+        return None
+    try:
+        return int(np.load(path)["n_components"])
+    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
+        return -1
+
+
+def write_pca_tsv(path, names, res):
+    """One line per contig of a PCAResult: its scores on the components; NA for a contig without a valid embedding."""
+    c = res.n_components
+    with open(path, "w") as fout:
+        fout.write("seq_name\t" + "\t".join(f"pc{j + 1}" for j in range(c)) + "\n")
+        for i, name in enumerate(names):
+            if res.valid[i]:
+                fout.write(f"{name}\t" + "\t".join(f"{x:.6f}" for x in res.projection[i]) + "\n")
+            else:
+                fout.write(f"{name}\t" + "\t".join(["NA"] * c) + "\n")
+
+
+def write_pca(npz_path, tsv_path, names_key, names, res, strand="forward"):
+    """Both PCA files of a stage: the arrays of a PCAResult with the contig names, and one line per contig."""
+    np.savez_compressed(npz_path, **{names_key: names, "n_components": np.int64(res.n_components), "metric": np.array("cosine"),
+                                     "mean": res.mean, "components": res.components, "explained_variance": res.explained_variance,
+                                     "explained_variance_ratio": res.explained_variance_ratio,
+                                     "total_variance": np.float64(res.total_variance), "n_valid": np.int64(res.n_valid),
+                                     "projection": res.projection, **({"strand": np.array(strand)} if strand != "forward" else {})})
+    write_pca_tsv(tsv_path, names, res)
+
+
 def representatives_requested():
     """GENOMAD_AMD_REPRESENTATIVES=<float in [-1, 1]>: main() also writes the greedy clusters of the contigs at that cosine similarity of
     the per-contig encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1 - contigs walked by their number of kept windows, the larger first,
@@ -1165,6 +1219,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     clusters_threshold = clusters_requested()
     density_request = density_requested()
     kmeans_request = kmeans_requested()
+    pca_request = pca_requested()
     representatives_threshold = representatives_requested()
     linkage = linkage_requested()
     graph_threshold = graph_requested()
@@ -1219,6 +1274,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     if kmeans_request is not None and not embeddings:
         console.error("GENOMAD_AMD_KMEANS needs GENOMAD_AMD_EMBEDDINGS=1: the groups are formed among the per-contig encoder "
                       "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_KMEANS.")
+        sys.exit(1)
+    if pca_request is not None and not embeddings:
+        console.error("GENOMAD_AMD_PCA needs GENOMAD_AMD_EMBEDDINGS=1: the components are those of the per-contig encoder "
+                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_PCA.")
         sys.exit(1)
     if representatives_threshold is not None and not embeddings:
         console.error("GENOMAD_AMD_REPRESENTATIVES needs GENOMAD_AMD_EMBEDDINGS=1: representatives are chosen among the per-contig encoder "
@@ -1441,6 +1500,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         ``kmeans_files[what]`` (npz, tsv; GENOMAD_AMD_KMEANS with the optional GENOMAD_AMD_KMEANS_MAX_ITER, which need the embeddings):
         rank 0 runs the spherical k-means (NNEngine.kmeans, farthest-first init) of the same gathered embeddings and writes both
         files.  They follow the clusters files' rule, with (k, max_iter) in place of the threshold.
+        ``pca_files[what]`` (npz, tsv; GENOMAD_AMD_PCA, which needs the embeddings): rank 0 computes the principal components
+        (NNEngine.pca) of the same gathered embeddings and writes both files.  They follow the clusters files' rule, with the number
+        of components in place of the threshold.
         ``match_files[what]`` (npz, tsv; GENOMAD_AMD_MATCH with GENOMAD_AMD_MATCH_BASE, which need the embeddings): rank 0 matches the
         same gathered embeddings (query) against the reference's (base; NNEngine.match, cosine) and writes both files.  They follow
         the clusters files' rule, and the reference's names must be those the file was computed against.
@@ -1457,6 +1519,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         graph_path, graph_tsv_path = graph_files[what]
         density_path, density_tsv_path = density_files[what]
         kmeans_path, kmeans_tsv_path = kmeans_files[what]
+        pca_path, pca_tsv_path = pca_files[what]
         match_path, match_tsv_path = match_files[what]
         regions_path, regions_tsv_path = regions_paths
         regions_request = None if region_penalty is None else (scan_stride, region_penalty)
@@ -1485,6 +1548,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                  and _kmeans_of_file(kmeans_path) == kmeans_request
                                  and (kmeans_request is None) == (not kmeans_tsv_path.exists())
                                  and (kmeans_request is None or _npz_strand(kmeans_path) == strand)
+                                 and _pca_of_file(pca_path) == pca_request
+                                 and (pca_request is None) == (not pca_tsv_path.exists())
+                                 and (pca_request is None or _npz_strand(pca_path) == strand)
                                  and _clusters_of_file(match_path) == match_threshold
                                  and (match_threshold is None) == (not match_tsv_path.exists())
                                  and (match_threshold is None or (_npz_strand(match_path) == strand
@@ -1756,6 +1822,20 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     for p in (kmeans_path, kmeans_tsv_path):
                         if p.exists():
                             p.unlink()
+                if pca_request is not None:
+                    try:
+                        res = eng.pca(embeddings_all, pca_request)
+                    except (ValueError, GnnError) as e:         # fewer than two contigs with a valid embedding
+                        console.error(f"GENOMAD_AMD_PCA={pca_request}: {e}. Unset GENOMAD_AMD_PCA.")
+                        sys.exit(1)
+                    write_pca(pca_path, pca_tsv_path, names_key, names, res, strand)
+                    console.log(f"Principal components of the {what}s (unit encoder embeddings: {pca_request} components of "
+                                f"{res.n_valid} {what}s, {float(np.nansum(res.explained_variance_ratio)):.3f} of the variance) written to "
+                                f"{pca_path.name} and {pca_tsv_path.name}.")
+                else:                               # likewise, both files
+                    for p in (pca_path, pca_tsv_path):
+                        if p.exists():
+                            p.unlink()
                 if match_threshold is not None:
                     base_names, base_rows = match_base
                     try:
@@ -1785,6 +1865,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                      "provirus": (outputs.provirus_nn_density_output, outputs.provirus_nn_density_tsv_output)}
     kmeans_files = {"sequence": (outputs.nn_kmeans_output, outputs.nn_kmeans_tsv_output),
                     "provirus": (outputs.provirus_nn_kmeans_output, outputs.provirus_nn_kmeans_tsv_output)}
+    pca_files = {"sequence": (outputs.nn_pca_output, outputs.nn_pca_tsv_output),
+                 "provirus": (outputs.provirus_nn_pca_output, outputs.provirus_nn_pca_tsv_output)}
     match_files = {"sequence": (outputs.nn_matches_output, outputs.nn_matches_tsv_output),
                    "provirus": (outputs.provirus_nn_matches_output, outputs.provirus_nn_matches_tsv_output)}
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})

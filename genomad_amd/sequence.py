@@ -1540,6 +1540,95 @@ def kmeans_table(result, names=None):
     return out
 
 
+PCA_COMPONENTS_MAX = 64
+PCA_ROWS_MAX = 1 << 30
+
+
+def pca_components(n_components) -> int:
+    return _whole(n_components, "n_components", 1, PCA_COMPONENTS_MAX)
+
+
+def pca_moments(rows):
+    """The second moments of the unit rows, spelled out (the definition ``gnn_pca_moments`` computes on the device in fixed point;
+    float64 here).  ``rows`` (n, 512) float32; the valid rows are exactly those of :func:`nearest_neighbours` under cosine and an
+    invalid row contributes nothing.  Returns ``G`` (float64 (512, 512): the sum of u uT over the valid rows' unit vectors u),
+    ``S`` (float64 (512,): the sum of u) and ``n_valid`` (int)."""
+    unit, ok = _unit_rows(neighbour_rows(rows, "rows"))
+    return unit.T @ unit, unit.sum(axis=0), int(ok.sum())
+
+
+def pca_from_moments(G, S, n_valid, n_components, center=True):
+    """Principal components from the moments of :func:`pca_moments` - the product code of the 512 x 512 step, which the engine calls
+    too (there is no device eigen-solver: the matrix is 2 MB whatever n is).  Float64 throughout.  C = G / n_valid - mu muT with
+    mu = S / n_valid, or G / n_valid when ``center`` is false (mu is then zero); ``numpy.linalg.eigh``; components ordered by
+    eigenvalue descending, each one's sign fixed so that its entry of largest magnitude is positive (ties to the smallest index).
+    ``n_valid`` < 2 is a ValueError.
+
+    Returns a dict: ``mean`` (float64 (512,)), ``components`` (float64 (c, 512), unit rows), ``explained_variance`` (float64 (c,):
+    the eigenvalues, clipped at 0), ``explained_variance_ratio`` (over trace(C); NaN when that is 0) and ``total_variance``
+    (trace(C))."""
+    c = pca_components(n_components)
+    G, S = np.asarray(G, dtype=np.float64), np.asarray(S, dtype=np.float64)
+    if G.shape != (NEIGHBOUR_DIM, NEIGHBOUR_DIM) or S.shape != (NEIGHBOUR_DIM,):
+        raise ValueError(f"G {G.shape} and S {S.shape}: ({NEIGHBOUR_DIM}, {NEIGHBOUR_DIM}) and ({NEIGHBOUR_DIM},) are required")
+    n_valid = int(n_valid)
+    if n_valid < 2:
+        raise ValueError(f"{n_valid} valid rows: principal components need two at the least")
+    mean = S / n_valid if center else np.zeros(NEIGHBOUR_DIM)
+    C = G / n_valid - np.outer(mean, mean)
+    C = (C + C.T) / 2
+    w, v = np.linalg.eigh(C)
+    order = np.argsort(-w, kind="stable")[:c]
+    comp = v[:, order].T.copy()
+    lead = np.argmax(np.abs(comp), axis=1)                 # argmax: the first = the smallest index among equals
+    comp[comp[np.arange(c), lead] < 0] *= -1
+    total = float(np.trace(C))
+    var = np.clip(w[order], 0, None)
+    return {"mean": mean, "components": comp, "explained_variance": var,
+            "explained_variance_ratio": var / total if total > 0 else np.full(c, np.nan), "total_variance": total}
+
+
+def pca_directions(components):
+    """``components`` (c, 512) float32, 1 <= c <= 64, every row valid -> (the float32 rows, their float64 renormalisation)"""
+    c32 = neighbour_rows(components, "components")
+    if not 1 <= len(c32) <= PCA_COMPONENTS_MAX:
+        raise ValueError(f"{len(c32)} components: 1 to {PCA_COMPONENTS_MAX} are required")
+    unit, ok = _unit_rows(c32)
+    if not ok.all():
+        raise ValueError(f"{int((~ok).sum())} of the {len(c32)} components are not valid (finite, norm > 0)")
+    return c32, unit
+
+
+def pca_offsets(components, mean):
+    """What :func:`pca_project` subtracts per component: mean . v in float64, v the float64 renormalisation of the float32
+    component; ``mean`` None: zeros"""
+    _, unit = pca_directions(components)
+    if mean is None:
+        return np.zeros(len(unit))
+    mean = np.asarray(mean, dtype=np.float64)
+    if mean.shape != (NEIGHBOUR_DIM,):
+        raise ValueError(f"mean has the shape {mean.shape}: ({NEIGHBOUR_DIM},) is required")
+    return unit @ mean
+
+
+def pca_project(rows, components, mean=None):
+    """Principal-component scores, spelled out (the definition ``gnn_pca_project`` computes on the device; float64): u_i . v_c -
+    mean . v_c for the unit vector u_i of row i and the unit vector v_c of component c; NaN for an invalid row.  Returns float64
+    (n, c)."""
+    unit, ok = _unit_rows(neighbour_rows(rows, "rows"))
+    _, v = pca_directions(components)
+    out = unit @ v.T - pca_offsets(components, mean)[None, :]
+    out[~ok] = np.nan
+    return out
+
+
+def pca_table(projection, valid, names=None):
+    """One record per row of a projection: ``row`` (its index, or its name where ``names`` is given) and ``pc`` (the list of its
+    scores; None for a row without a valid embedding)"""
+    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    return [{"row": name(i), "pc": [float(x) for x in projection[i]] if valid[i] else None} for i in range(len(projection))]
+
+
 def prefix_of(input_path: Path) -> str:
     """nn_classification.py:106-108: stem, minus one more extension if the file is compressed."""
     prefix = Path(input_path).stem

@@ -866,6 +866,47 @@ int gnn_debug_set_kmeans_lds(gnn_ctx* ctx, int max_k);
  * assign, and behind every assignment but the last: update, finish, prepare] - as gnn_debug_graph_pass_ms. */
 int gnn_debug_kmeans_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
 
+/* ---- principal components among encoder embeddings: Gram sums on the device ---------------------------------
+ * "Look at the rows": the second moments of the UNIT rows - the geometry every search here works in - and the projection of rows onto
+ * directions.  Validity is gnn_neighbours' under cosine; an invalid row contributes nothing to a moment and projects to NaN; no forward
+ * pass runs and no other entry point's result changes.  The 512 x 512 eigenproblem between the two calls is the host's
+ * (sequence.pca_from_moments): the matrix is 2 MB whatever n is, there is no device eigen-solver.
+ *   moments   q_i = the 32-bit fixed-point image of row i's unit vector that gnn_kmeans sums: (hi + lo) * 2^24 of its own fragments,
+ *             x_i = q_i * 2^-24 = unit * 2^8, exact in f32.
+ *             S[d] = sum_i q_i[d], int64, exact: units of 2^-32 of sum_i u_i[d].
+ *             G[a][b], int64, units of 2^-32 of sum_i u_i[a] u_i[b]: the rows are taken in granules of 256 rows aligned to the
+ *             absolute row index; within a granule the products x_i[a] * x_i[b] are accumulated in f32 in ascending row order from 0
+ *             (a k-ordered fmaf chain: v_mfma_f32_32x32x2_f32), the granule's f32 sum p becomes llrint((double)p * 2^16) once, and
+ *             the granules' integers are added as integers.  No bit of G, S or n_valid depends on the row split
+ *             (gnn_debug_set_pca_split) or on the order of execution; G is symmetric bit for bit.  Rows whose unit entries are powers
+ *             of two times small integers (all products and partial sums exact in f32) give G = Q^T Q >> 32 exactly.
+ *             n_valid: the valid rows.
+ *   project   out[i][c] = s(i, c) - off[c], one f32 subtraction (off NULL: s itself), where s(i, c) IS the f32 that gnn_neighbours
+ *             returns for query i and base row c of `components` under cosine - the components go through the prologue like any base:
+ *             they are directions and are renormalised.  NaN at an invalid row or component.  out is [n][ncomp], nothing else is
+ *             written.
+ *   ranges    1 <= n <= 2^30 (the int64 sums of more rows could overflow), 1 <= ncomp <= 64; GNN_ERR_ARG with the value and the range
+ *             - checked before the ctx is looked at.
+ * What it is not: not PCA of the raw (un-normalised) rows, not kernel PCA, not t-SNE / UMAP, no width other than GNN_EMBED_DIM, not
+ * more than 64 components, not multi-GPU, not incremental.
+ * Device memory, persistent in the ctx and grow-only: per row the 2 KB of fragments + 1 B of the neighbour search (shared with it);
+ * 128 KB for the components; the host forms' 2 MB of moments and n x ncomp f32 of output.  gnn_pca_moments / gnn_pca_project: host
+ * pointers, synchronous.  The _dev forms: device pointers (G int64 [512 * 512], S int64 [512], n_valid int64 [1]; components f32
+ * [ncomp][512], off f32 [ncomp] or NULL, out f32 [n][ncomp]), asynchronous on the ctx stream like gnn_classify_dev. */
+int gnn_pca_moments(gnn_ctx* ctx, const float* rows_host, int64_t n, int64_t* G_host, int64_t* S_host, int64_t* n_valid_host);
+int gnn_pca_moments_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, int64_t* G_dev, int64_t* S_dev, int64_t* n_valid_dev);
+int gnn_pca_project(gnn_ctx* ctx, const float* rows_host, int64_t n, const float* components_host, int ncomp, const float* off_host_or_null,
+                    float* out_host);
+int gnn_pca_project_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, const float* components_dev, int ncomp, const float* off_dev_or_null,
+                        float* out_dev);
+/* test aid: the rows a workgroup of the Gram pass takes - a multiple of 256, anything else is GNN_ERR_ARG; 0: the library's choice
+ * (every CU about two workgroups).  No result depends on it. */
+int gnn_debug_set_pca_split(gnn_ctx* ctx, int64_t rows_per_workgroup);
+/* measurement only: with profiling enabled, the HIP-event milliseconds of the ctx's last gnn_pca_* call - moments: [prepare, sums,
+ * gram, mirror]; project: [prepare rows, prepare components, project] - as gnn_debug_kmeans_pass_ms.  Synchronises the ctx stream;
+ * ask before the ctx's next call of any kind. */
+int gnn_debug_pca_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
+
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
  * in-memory text buffer (already decompressed, newlines normalised to '\n').
