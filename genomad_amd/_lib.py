@@ -153,6 +153,10 @@ SIGNATURES = {
     "gnn_centroids_dev": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp]),
     "gnn_debug_set_kmeans_lds": (_int, [_vp, _int]),
     "gnn_debug_kmeans_pass_ms": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_vote": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _int, C.c_float, _vp, _vp, _vp, _vp]),
+    "gnn_vote_dev": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _int, C.c_float, _vp, _vp, _vp, _vp]),
+    "gnn_debug_set_vote_lds": (_int, [_vp, _int]),
+    "gnn_debug_vote_pass_ms": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_pca_moments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "gnn_pca_moments_dev": (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "gnn_pca_project": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp]),

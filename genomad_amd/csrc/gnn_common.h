@@ -318,6 +318,22 @@ struct PCAWorkspace {
     std::vector<float> pass_ms;                  // moments: [prepare, sums, gram, mirror]; project: [prepare rows, prepare components, project]
 };
 
+// ---- label transfer (gnn_votes.hip): persistent, grow-only.  The base's fragments and flags are NeighbourWorkspace's bfrag / bvalid (and
+// d_base for the host entry point), one slab's query fragments its qfrag / qvalid (and d_query); here 4 B per padded base column, 8 B
+// of keys per (query row of a slab, class), one flag and, for gnn_vote alone, the labels and one slab's 28 B of results per cell.
+// Nothing is n_query x n_base.
+struct VoteWorkspace {
+    int lds_c = 16;                              // up to this many classes a workgroup votes in LDS first (gnn_debug_set_vote_lds); no result depends on it
+    DevBuf<int32_t> blabel;                      // [round_up(n_base, 64)]: the column's class; -1: unlabelled, invalid or padded
+    DevBuf<unsigned long long> key;              // [query rows of the slab][classes]: max of (image of the similarity << 32) | (2^32 - 1 - base row), 0: none
+    DevBuf<unsigned long long> flag;             // a label outside [-1, n_classes)
+    PinnedBuf<unsigned long long> h_flag;        // where the host reads it, once per call
+    DevBuf<int64_t> d_label;                     // gnn_vote: the labels
+    DevBuf<int64_t> d_out;                       // gnn_vote: one slab's [count | weight | nearest | nearest_sim (f32)]
+    std::vector<RoundTimer> pending;             // profiling on: the last call's passes, filed by gnn_debug_vote_pass_ms behind a synchronise
+    std::vector<float> pass_ms;                  // [labels, then per slab of queries: votes, finish]
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -510,6 +526,7 @@ struct gnn_ctx {
     gnn::GraphWorkspace gr;                       // gnn_graph.hip
     gnn::KMeansWorkspace km;                      // gnn_kmeans.hip
     gnn::PCAWorkspace pca;                        // gnn_pca.hip
+    gnn::VoteWorkspace vt;                        // gnn_votes.hip
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;

@@ -486,6 +486,53 @@ class MatchResult:
                    n_base=len(base_valid), n_edges=len(col), threshold=float(_sequence.cluster_threshold(threshold)), metric=str(metric))
 
 
+class VoteResult:
+    """What :meth:`NNEngine.vote` returns (the definition is ``sequence.class_votes``): per query row and class of a labelled base,
+    over the voters - the valid base rows of the class whose cosine similarity reaches the threshold - ``count`` (int64: how many),
+    ``weight`` (int64: their similarities summed in units of 2^-32), ``nearest`` (int64) and ``nearest_sim`` (float32, the device's
+    own value): the most similar voter, ties to the smaller index, -1 / NaN where the class has none -, each (n_query, n_classes);
+    ``query_valid`` (bool: the rows that took part; the others have 0 / 0 / -1 / NaN), ``n_classes`` and the ``threshold`` as the
+    float32 it was compared as."""
+    FIELDS = ("count", "weight", "nearest", "nearest_sim", "query_valid", "n_classes", "threshold")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw.get(k))
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    def similarity_sum(self) -> np.ndarray:
+        """float64 (n_query, n_classes): ``weight`` / 2^32 - the voters' similarities summed"""
+        return self.weight.astype(np.float64) / _sequence.VOTE_UNIT
+
+    def mean_similarity(self) -> np.ndarray:
+        """float64 (n_query, n_classes): the voters' mean similarity, NaN where the class has none"""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(self.count > 0, self.similarity_sum() / self.count, np.nan)
+
+    def predict(self, rule="weight", min_votes=1):
+        """``sequence.vote_predict``: (label int64, confidence float64, margin float64) per query - the class with the largest
+        ``weight`` / ``count`` / ``nearest_sim``, ties to the smaller class, -1 where fewer than ``min_votes`` voters are within the
+        threshold.  A share of votes, no calibrated probability."""
+        return _sequence.vote_predict(self.count, self.weight, rule, self.nearest_sim, min_votes)
+
+    def table(self, names=None, class_names=None, base_names=None, rule="weight", min_votes=1):
+        """``sequence.vote_table``: one record per query - label, confidence, votes of the winner, votes in all, the nearest voter
+        of the winning class and its similarity"""
+        return _sequence.vote_table(self.count, self.weight, self.nearest, self.nearest_sim, names, class_names, base_names, rule, min_votes)
+
+    @classmethod
+    def build(cls, arrays, query_valid, n_classes, threshold):
+        """from the (count, weight, nearest, nearest_sim) of ``sequence.class_votes`` or the library, and the queries' validity"""
+        count, weight, nearest, nearest_sim = arrays
+        query_valid = np.asarray(query_valid, dtype=bool)
+        if count.shape != (len(query_valid), int(n_classes)):
+            raise ValueError(f"count has the shape {count.shape}, expected {(len(query_valid), int(n_classes))}")
+        return cls(count=count, weight=weight, nearest=nearest, nearest_sim=nearest_sim, query_valid=query_valid, n_classes=int(n_classes),
+                   threshold=float(_sequence.cluster_threshold(threshold)))
+
+
 class NNEngine:
     def __init__(self, device: int = 0, weights: dict = None, chunk: int = None):
         self.lib = _lib.load()
@@ -1137,6 +1184,54 @@ class NNEngine:
         ms = np.zeros(n.value, np.float64)
         if n.value:
             check(self.lib.gnn_debug_match_pass_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
+        return ms
+
+    # -- label transfer ------------------------------------------------------------------
+    def vote(self, query, base, label, n_classes, threshold) -> VoteResult:
+        """Label transfer among encoder embeddings (``gnn_vote``; the definition is ``sequence.class_votes``): for every valid row i
+        of ``query`` (nq, 512) and every class c, the voters - the valid rows j of ``base`` (nb, 512) with ``label[j]`` == c whose
+        cosine similarity to i is >= ``threshold`` - counted, their similarities summed as integers in units of 2^-32, and the most
+        similar one named: n_query x n_classes numbers where :meth:`match` would write every edge.  ``label``: int64 per base row
+        in [0, ``n_classes``), or -1 for an unlabelled row, which is ignored; 1 <= ``n_classes`` <= 1024.  ``base=None``: the rows
+        vote among themselves, ``label`` runs over them and the pair (i, i) is left out - leave-one-out over a labelled set.  The
+        similarity of the pair (i, j) is the float32 :meth:`neighbours` and :meth:`match` return for it, and the sums are integer
+        sums: no bit of the result depends on the order of execution, and a permutation of the base with its labels changes no
+        bit of ``count``, ``weight`` or ``nearest_sim``.  Not a top-k vote, not the dot metric, not approximate, no calibrated
+        probability.  :meth:`set_neighbour_split` sets the range of this search too; no result depends on it."""
+        q = _sequence.neighbour_rows(query)
+        b = None if base is None else _sequence.neighbour_rows(base, "base")
+        nc = _sequence.vote_classes(n_classes)
+        thr = _sequence.cluster_threshold(threshold)
+        lab = _sequence.vote_labels(label, len(q) if b is None else len(b), nc)
+        shape = (len(q), nc)
+        count, weight, nearest = (np.empty(shape, dtype=np.int64) for _ in range(3))
+        nearest_sim = np.empty(shape, dtype=np.float32)
+        check(self.lib.gnn_vote(self.ctx, q.ctypes.data, len(q), None if b is None else b.ctypes.data, 0 if b is None else len(b),
+                                lab.ctypes.data, nc, float(thr), count.ctypes.data, weight.ctypes.data, nearest.ctypes.data,
+                                nearest_sim.ctypes.data))
+        return VoteResult.build((count, weight, nearest, nearest_sim), _sequence.valid_rows(q), nc, thr)
+
+    def vote_dev(self, query_ptr: int, n_query: int, base_ptr, n_base: int, label_ptr: int, n_classes: int, threshold, count_ptr: int,
+                 weight_ptr: int, nearest_ptr: int, nearest_sim_ptr: int):
+        """``gnn_vote_dev``: device pointers in (query n_query x 512 f32; base n_base x 512 f32, or None for the self form; label
+        int64 per base row) and out (count, weight, nearest: n_query x n_classes int64 each; nearest_sim: the same in f32); the
+        engine's stream is synchronised once (the labels' verdict), the rest is enqueued on it."""
+        check(self.lib.gnn_vote_dev(self.ctx, query_ptr, int(n_query), base_ptr, int(n_base), label_ptr, int(n_classes), float(threshold),
+                                    count_ptr, weight_ptr, nearest_ptr, nearest_sim_ptr))
+
+    def set_vote_lds(self, max_classes: int):
+        """test aid (``gnn_debug_set_vote_lds``): up to ``max_classes`` (0..16, the default) classes a workgroup of :meth:`vote` adds
+        in LDS before it adds to memory; no result depends on it."""
+        check(self.lib.gnn_debug_set_vote_lds(self.ctx, int(max_classes)))
+
+    def vote_pass_ms(self):
+        """measurement only (``gnn_debug_vote_pass_ms``): with profiling enabled, the HIP-event milliseconds of the last
+        :meth:`vote` / :meth:`vote_dev` call - [labels, then per slab of 262 144 queries: votes, finish]"""
+        n = C.c_int64(0)
+        check(self.lib.gnn_debug_vote_pass_ms(self.ctx, None, 0, C.addressof(n)))
+        ms = np.zeros(n.value, np.float64)
+        if n.value:
+            check(self.lib.gnn_debug_vote_pass_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
         return ms
 
     # -- spherical k-means ---------------------------------------------------------------

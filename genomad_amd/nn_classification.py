@@ -129,6 +129,12 @@ class Outputs:
         self.nn_matches_tsv_output = d / f"{p}_nn_matches.tsv"
         self.provirus_nn_matches_output = d / f"{p}_provirus_nn_matches.npz"
         self.provirus_nn_matches_tsv_output = d / f"{p}_provirus_nn_matches.tsv"
+        # written only when GENOMAD_AMD_VOTE and GENOMAD_AMD_VOTE_BASE are set (the per-class votes of a labelled reference's embeddings
+        # on the per-contig embeddings; no counterpart in the reference)
+        self.nn_votes_output = d / f"{p}_nn_votes.npz"
+        self.nn_votes_tsv_output = d / f"{p}_nn_votes.tsv"
+        self.provirus_nn_votes_output = d / f"{p}_provirus_nn_votes.npz"
+        self.provirus_nn_votes_tsv_output = d / f"{p}_provirus_nn_votes.tsv"
         f = o / f"{p}_find_proviruses"
         self.find_proviruses_execution_info = f / f"{p}_find_proviruses.json"
         self.find_proviruses_output = f / f"{p}_provirus.tsv"
@@ -1025,6 +1031,144 @@ def _match_base_of_file(path):
         return None
 
 
+def vote_requested():
+    """GENOMAD_AMD_VOTE=<float in [-1, 1]>: main() also writes, for every contig and every class of the labelled reference named by
+    GENOMAD_AMD_VOTE_BASE, how many of the class's rows have at least that cosine similarity to the contig's per-contig embedding of
+    GENOMAD_AMD_EMBEDDINGS=1, their similarity sum and the most similar one, and the label they vote for (<prefix>_nn_votes.npz and
+    .tsv); unset or empty: nothing changes (None).  Any other value is an error.  Returns the threshold as it is compared: the
+    float32 it rounds to."""
+    v = os.environ.get("GENOMAD_AMD_VOTE", "").strip()
+    if not v:
+        return None
+    try:
+        t = float(v)
+    except ValueError:
+        t = float("nan")
+    if not -1.0 <= t <= 1.0:                             # a NaN fails both comparisons
+        raise ValueError(f"GENOMAD_AMD_VOTE={v!r}: expected a float in [-1, 1] (the cosine similarity at which a labelled reference row "
+                         "votes on a contig)")
+    return float(np.float32(t))
+
+
+def vote_base_requested():
+    """GENOMAD_AMD_VOTE_BASE=<path>: the labelled reference GENOMAD_AMD_VOTE takes its voters from (:func:`load_vote_base`); unset or
+    empty: None."""
+    v = os.environ.get("GENOMAD_AMD_VOTE_BASE", "").strip()
+    return Path(v) if v else None
+
+
+def vote_min_votes_requested() -> int:
+    """GENOMAD_AMD_VOTE_MIN_VOTES=<integer >= 1>: the voters a contig needs within the threshold to get a label; unset or empty: 1.
+    Any other value is an error."""
+    v = os.environ.get("GENOMAD_AMD_VOTE_MIN_VOTES", "").strip()
+    if not v:
+        return 1
+    try:
+        m = int(v)
+    except ValueError:
+        m = 0
+    if m < 1:
+        raise ValueError(f"GENOMAD_AMD_VOTE_MIN_VOTES={v!r}: expected an integer >= 1 (the voters a contig needs to get a label)")
+    return m
+
+
+def load_vote_base(path, strand="forward"):
+    """(names, embeddings float32 (n, 512), classes, label int64 (n,)) of a labelled reference file: an embeddings file as
+    GENOMAD_AMD_EMBEDDINGS=1 writes it - ``embeddings`` of shape (n, 512), ONE 1-D array of the n names under whatever key, an
+    optional ``strand``, which must be the run's mode - plus ``labels``, a 1-D array of n strings: "" means unlabelled (label -1), the
+    classes are the sorted distinct non-empty strings (at most 1024) and a row's label is its class's place among them.
+    ``ValueError`` with the reason for anything else."""
+    what = f"GENOMAD_AMD_VOTE_BASE={str(path)!r}"
+    if not Path(path).is_file():
+        raise ValueError(f"{what}: no such file")
+    try:
+        z = np.load(path)
+        files = list(z.files)
+        emb = z["embeddings"] if "embeddings" in files else None
+        labels = z["labels"] if "labels" in files else None
+        others = {k: z[k] for k in files if k not in ("embeddings", "strand", "labels")}
+        base_strand = str(z["strand"]) if "strand" in files else "forward"
+    except Exception as e:  # noqa: BLE001  (not an .npz, or one that cannot be read)
+        raise ValueError(f"{what}: not a readable .npz ({e})") from None
+    if emb is None or emb.ndim != 2 or emb.shape[1] != sequence.NEIGHBOUR_DIM or emb.dtype.kind != "f":
+        raise ValueError(f"{what}: it must hold 'embeddings' of shape (n, {sequence.NEIGHBOUR_DIM}) as GENOMAD_AMD_EMBEDDINGS=1 writes them"
+                         + ("" if emb is None else f", not {emb.dtype} {emb.shape}"))
+    if labels is None or labels.ndim != 1 or len(labels) != len(emb) or labels.dtype.kind not in "US":
+        raise ValueError(f"{what}: it must hold 'labels', a 1-D array of the {len(emb)} class names (\"\" for an unlabelled row)"
+                         + ("" if labels is None else f", not {labels.dtype} {labels.shape}"))
+    names = [k for k, v in others.items() if v.ndim == 1 and len(v) == len(emb) and v.dtype.kind in "US"]
+    if len(names) != 1:
+        raise ValueError(f"{what}: it must hold one 1-D array of the {len(emb)} names beside 'embeddings' and 'labels' (found: {sorted(others)})")
+    if base_strand != strand:
+        raise ValueError(f"{what}: its embeddings were computed under GENOMAD_AMD_STRAND={base_strand}, this run's are under {strand}: "
+                         "embeddings of different strand modes are not comparable")
+    labels = labels.astype(str)
+    classes = np.array(sorted(set(labels.tolist()) - {""}), dtype=str)
+    if not len(classes):
+        raise ValueError(f"{what}: no row has a label: every entry of 'labels' is \"\"")
+    if len(classes) > sequence.VOTE_CLASSES_MAX:
+        raise ValueError(f"{what}: 'labels' names {len(classes)} classes, more than {sequence.VOTE_CLASSES_MAX}")
+    label = np.where(labels == "", -1, np.searchsorted(classes, labels)).astype(np.int64)
+    return others[names[0]], np.ascontiguousarray(emb, dtype=np.float32), classes, label
+
+
+VOTE_TSV_HEADER = "seq_name\tlabel\tconfidence\tvotes\ttotal_votes\tnearest\tsimilarity\n"
+VOTE_RULE = "weight"                    # the rule of the labels main() writes
+
+
+def write_votes_tsv(path, names, classes, base_names, res, min_votes=1):
+    """One line per contig of a VoteResult: its name, the class its voters' similarity sum is largest for, that class's share of the
+    sum, its voters, the voters of all classes, the most similar voter of the winning class and its similarity, behind one header
+    line; NA where the contig has no label (and for a share that is not defined)."""
+    with open(path, "w") as fout:
+        fout.write(VOTE_TSV_HEADER)
+        for e in res.table(names, classes, base_names, VOTE_RULE, min_votes):
+            if e["label"] is None:
+                fout.write(f"{e['query']}\tNA\tNA\t0\t{e['total_votes']}\tNA\tNA\n")
+            else:
+                conf = "NA" if e["confidence"] is None else f"{e['confidence']:.6f}"
+                fout.write(f"{e['query']}\t{e['label']}\t{conf}\t{e['votes']}\t{e['total_votes']}\t{e['nearest']}\t{e['similarity']:.6f}\n")
+
+
+def write_votes(npz_path, tsv_path, names_key, names, classes, base_names, base_label, res, min_votes=1, strand="forward"):
+    """Both vote files of a stage: the arrays of a VoteResult with the names of the contigs, the classes and the reference rows (and
+    the rows' labels), the labels of rule ``weight``, and one line per contig."""
+    label, confidence, margin = res.predict(VOTE_RULE, min_votes)
+    np.savez_compressed(npz_path, **{names_key: names, "base_names": base_names, "base_label": np.asarray(base_label, dtype=np.int64),
+                                     "classes": classes, "threshold": np.float64(res.threshold),
+                                     "min_votes": np.int64(min_votes), "count": res.count, "weight": res.weight, "nearest": res.nearest,
+                                     "nearest_sim": res.nearest_sim, "label": label, "confidence": confidence, "margin": margin,
+                                     **({"strand": np.array(strand)} if strand != "forward" else {})})
+    write_votes_tsv(tsv_path, names, classes, base_names, res, min_votes)
+
+
+def _vote_of_file(path):
+    """(threshold, min_votes) a stage's vote file was computed with; no file = None (no votes were asked for)."""
+    if not Path(path).exists():
+        return None
+    try:
+        z = np.load(path)
+        return float(z["threshold"]), int(z["min_votes"])
+    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
+        return float("nan"), 0
+
+
+def _vote_base_of_file(path):
+    """(the reference names, the classes, the rows' labels) a stage's vote file was computed against; no file, or an unreadable one =
+    None."""
+    try:
+        z = np.load(path)
+        return z["base_names"], z["classes"], z["base_label"]
+    except Exception:  # noqa: BLE001
+        return None
+
+
+def _same_vote_base(of_file, vote_base) -> bool:
+    """``vote_base``: what :func:`load_vote_base` returned"""
+    return (of_file is not None and np.array_equal(of_file[0], vote_base[0]) and np.array_equal(of_file[1], vote_base[2])
+            and np.array_equal(of_file[2], vote_base[3]))
+
+
 REGION_TSV_HEADER = ("seq_name\tstart\tend\tclass\tn_bins\tevidence_bins\t"
                      + "\t".join("mean_" + c[:-len("_score")] for c in TSV_HEADER.split()[1:]) + "\tmargin\n")
 
@@ -1225,6 +1369,9 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     graph_threshold = graph_requested()
     match_threshold = match_requested()
     match_base_path = match_base_requested()
+    vote_threshold = vote_requested()
+    vote_base_path = vote_base_requested()
+    vote_min_votes = vote_min_votes_requested()
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -1295,6 +1442,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         console.error("GENOMAD_AMD_MATCH and GENOMAD_AMD_MATCH_BASE need each other and GENOMAD_AMD_EMBEDDINGS=1: the per-contig encoder "
                       "embeddings are matched against the reference's at that threshold. Set all three or unset both.")
         sys.exit(1)
+    if (vote_threshold is None) != (vote_base_path is None) or (vote_threshold is not None and not embeddings):
+        console.error("GENOMAD_AMD_VOTE and GENOMAD_AMD_VOTE_BASE need each other and GENOMAD_AMD_EMBEDDINGS=1: the labelled reference's "
+                      "embeddings vote on the per-contig encoder embeddings at that threshold. Set all three or unset both.")
+        sys.exit(1)
 
     if strand != "forward" and not device_front_end:
         console.error("GENOMAD_AMD_STRAND needs the device front end: the host front end (GENOMAD_AMD_FRONT_END=host) does "
@@ -1331,6 +1482,15 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
             console.error(f"{e}. Name a file that GENOMAD_AMD_EMBEDDINGS=1 wrote under the same GENOMAD_AMD_STRAND, or unset "
                           "GENOMAD_AMD_MATCH and GENOMAD_AMD_MATCH_BASE.")
             sys.exit(1)
+    vote_base = None                 # (names, embeddings, classes, label) of the labelled reference, read before any classification starts
+    if vote_threshold is not None:
+        try:
+            vote_base = load_vote_base(vote_base_path, strand)
+        except ValueError as e:
+            console.error(f"{e}. Name a file that GENOMAD_AMD_EMBEDDINGS=1 wrote under the same GENOMAD_AMD_STRAND, with 'labels' added, "
+                          "or unset GENOMAD_AMD_VOTE and GENOMAD_AMD_VOTE_BASE.")
+            sys.exit(1)
+    vote_request = None if vote_threshold is None else (vote_threshold, vote_min_votes)
 
     def everywhere(*flags):
         """Decisions read from files that rank 0 is about to rewrite are taken on rank 0 and made known to
@@ -1506,6 +1666,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         ``match_files[what]`` (npz, tsv; GENOMAD_AMD_MATCH with GENOMAD_AMD_MATCH_BASE, which need the embeddings): rank 0 matches the
         same gathered embeddings (query) against the reference's (base; NNEngine.match, cosine) and writes both files.  They follow
         the clusters files' rule, and the reference's names must be those the file was computed against.
+        ``vote_files[what]`` (npz, tsv; GENOMAD_AMD_VOTE with GENOMAD_AMD_VOTE_BASE and the optional GENOMAD_AMD_VOTE_MIN_VOTES, which
+        need the embeddings): rank 0 lets the labelled reference's rows (base) vote on the same gathered embeddings (query;
+        NNEngine.vote, cosine) and writes both files.  They follow the match files' rule, with (threshold, min_votes) in place of
+        the threshold and the reference's names, classes and labels in place of its names.
         ``region_emb_path`` (GENOMAD_AMD_REGION_EMBEDDINGS=1, which needs the regions): right after a piece's scan, while its
         sequence is in memory, the piece's own track is segmented (regions are per contig and exact integers: they are the ones
         rank 0 calls on the gathered track, which rank 0 checks) and NNEngine.embed_intervals folds the scan windows' encoder
@@ -1521,6 +1685,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         kmeans_path, kmeans_tsv_path = kmeans_files[what]
         pca_path, pca_tsv_path = pca_files[what]
         match_path, match_tsv_path = match_files[what]
+        vote_path, vote_tsv_path = vote_files[what]
         regions_path, regions_tsv_path = regions_paths
         regions_request = None if region_penalty is None else (scan_stride, region_penalty)
         (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and _strand_of_file(strand_path) == strand
@@ -1555,6 +1720,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                  and (match_threshold is None) == (not match_tsv_path.exists())
                                  and (match_threshold is None or (_npz_strand(match_path) == strand
                                                                   and np.array_equal(_match_base_of_file(match_path), match_base[0])))
+                                 and _vote_of_file(vote_path) == vote_request
+                                 and (vote_request is None) == (not vote_tsv_path.exists())
+                                 and (vote_request is None or (_npz_strand(vote_path) == strand
+                                                               and _same_vote_base(_vote_base_of_file(vote_path), vote_base)))
                                  and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
                                  and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
                                                             and _npz_strand(scan_path) == strand)))   # :284-292
@@ -1851,6 +2020,17 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     for p in (match_path, match_tsv_path):
                         if p.exists():
                             p.unlink()
+                if vote_request is not None:
+                    base_names, base_rows, classes, base_label = vote_base
+                    res = eng.vote(embeddings_all, base_rows, base_label, len(classes), vote_threshold)
+                    write_votes(vote_path, vote_tsv_path, names_key, names, classes, base_names, base_label, res, vote_min_votes, strand)
+                    console.log(f"Votes of {vote_base_path.name} on the {what}s ({NEIGHBOUR_METRIC} similarity of the encoder embeddings >= "
+                                f"{vote_threshold:g}, {len(classes)} classes: {int((res.predict(VOTE_RULE, vote_min_votes)[0] >= 0).sum())} "
+                                f"of {len(names)} {what}s got a label) written to {vote_path.name} and {vote_tsv_path.name}.")
+                else:                               # likewise, both files
+                    for p in (vote_path, vote_tsv_path):
+                        if p.exists():
+                            p.unlink()
         if cleanup and rank0 and enc_dir.is_dir():
             console.log(f"Deleting encoded {what} data.")
             shutil.rmtree(enc_dir)
@@ -1869,6 +2049,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                  "provirus": (outputs.provirus_nn_pca_output, outputs.provirus_nn_pca_tsv_output)}
     match_files = {"sequence": (outputs.nn_matches_output, outputs.nn_matches_tsv_output),
                    "provirus": (outputs.provirus_nn_matches_output, outputs.provirus_nn_matches_tsv_output)}
+    vote_files = {"sequence": (outputs.nn_votes_output, outputs.nn_votes_tsv_output),
+                  "provirus": (outputs.provirus_nn_votes_output, outputs.provirus_nn_votes_tsv_output)}
     emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
     scan_kw = (lambda path: {"scan_path": path}) if scan_stride is not None else (lambda path: {})
     region_emb_kw = (lambda path: {"region_emb_path": path}) if region_embeddings else (lambda path: {})

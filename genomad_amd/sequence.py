@@ -973,6 +973,150 @@ def match_table(indptr, col, sim, query_names=None, base_names=None):
     return [{"query": qn(i), "base": bn(j), "sim": float(s)} for i, j, s in zip(a, b, np.asarray(sim))]
 
 
+VOTE_FIELDS = ("count", "weight", "nearest", "nearest_sim")
+VOTE_CLASSES_MAX = 1024
+VOTE_BASE_MAX = 1 << 30                   # kmeans' N_MAX: |rint(s * 2^32)| <= 2^32 + 2^10, so the int64 sums of 2^30 voters cannot overflow
+VOTE_UNIT = float(1 << 32)                # ``weight`` counts similarity in units of 2^-32
+VOTE_RULES = ("weight", "count", "nearest")
+
+
+def vote_classes(n_classes) -> int:
+    return _whole(n_classes, "n_classes", 1, VOTE_CLASSES_MAX)
+
+
+def vote_labels(label, n_rows, n_classes) -> np.ndarray:
+    """``label`` as the int64 (n_rows,) the device takes: one integer in [-1, n_classes) per base row"""
+    label = np.asarray(label)
+    if label.shape != (n_rows,) or label.dtype.kind not in "iu":
+        raise ValueError(f"label has the shape {label.shape} and the type {label.dtype}: one integer per base row ({n_rows}) is required")
+    label = np.ascontiguousarray(label, dtype=np.int64)
+    if len(label) and (label.min() < -1 or label.max() >= n_classes):
+        raise ValueError(f"a label is outside [-1, {n_classes})")
+    return label
+
+
+def class_votes(query, base, label, n_classes, threshold, sims=None):
+    """Label transfer among encoder embeddings, spelled out (the definition ``gnn_vote`` computes on the device; float64 where it
+    matters, readable, not fast, nq x nb).  Cosine only.  ``query`` (nq, 512) and ``base`` (nb, 512) are float32 rows whose validity
+    is that of :func:`nearest_neighbours` under cosine; ``label`` is one int64 per base row: a value in [0, ``n_classes``) makes a
+    valid row a voter, -1 means unlabelled (the row is ignored), anything else is a ValueError.  ``threshold`` is a finite float,
+    compared as the float32 it rounds to with >= (:func:`cluster_threshold`).  ``base=None`` is the self form: the rows vote among
+    themselves, ``label`` runs over them and the pair (i, i) is left out - leave-one-out.
+
+    Per valid query i and class c, over the voters j of class c with s_ij >= threshold: ``count[i][c]`` (int64) - how many;
+    ``weight[i][c]`` (int64) - the sum of rint(float64(s_ij) * 2^32), the similarity sum in units of 2^-32 (the product by a power
+    of two is exact, rint rounds half to even as the device's llrint does, and |s| <= 1 + 2^-22 keeps 2^30 voters from overflowing);
+    ``nearest[i][c]`` (int64) and ``nearest_sim[i][c]`` (float32) - the most similar such voter, ties to the smaller index, -1 / NaN
+    where the class has none.  An invalid query has 0 / 0 / -1 / NaN in every class.
+
+    ``sims``: a (nq, nb) array to take s_ij from instead of the float64 cosines - the device's own float32 values give the
+    device's integers bit for bit.  Returns (count, weight, nearest, nearest_sim), each (nq, n_classes)."""
+    n_classes = vote_classes(n_classes)
+    thr = float(cluster_threshold(threshold))
+    q32 = neighbour_rows(query)
+    self_form = base is None
+    b32 = q32 if self_form else neighbour_rows(base, "base")
+    if len(b32) > VOTE_BASE_MAX:
+        raise ValueError(f"{len(b32)} base rows is outside [0, 2^30]")
+    label = vote_labels(label, len(b32), n_classes)
+    q, q_ok = _unit_rows(q32)
+    b, b_ok = (q, q_ok) if self_form else _unit_rows(b32)
+    s = q @ b.T if sims is None else np.asarray(sims, dtype=np.float64)
+    if s.shape != (len(q32), len(b32)):
+        raise ValueError(f"sims has the shape {s.shape}: ({len(q32)}, {len(b32)}) is required")
+    with np.errstate(invalid="ignore"):
+        vote = (s >= thr) & q_ok[:, None] & (b_ok & (label >= 0))[None, :]
+    if self_form:
+        vote[np.arange(len(q32)), np.arange(len(q32))] = False
+    units = np.rint(np.where(vote, s, 0.0) * VOTE_UNIT).astype(np.int64)
+    shape = (len(q32), n_classes)
+    count, weight = np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.int64)
+    nearest, nearest_sim = np.full(shape, -1, dtype=np.int64), np.full(shape, np.nan, dtype=np.float32)
+    for c in range(n_classes):
+        cols = np.flatnonzero(label == c)
+        if not len(cols):
+            continue
+        v = vote[:, cols]
+        count[:, c] = v.sum(axis=1)
+        weight[:, c] = units[:, cols].sum(axis=1)
+        masked = np.where(v, s[:, cols], -np.inf)
+        best = np.argmax(masked, axis=1)                # argmax: the first = the smaller index among equals
+        has = v.any(axis=1)
+        nearest[has, c] = cols[best[has]]
+        nearest_sim[has, c] = masked[has, best[has]]
+    return count, weight, nearest, nearest_sim
+
+
+def vote_predict(count, weight, rule="weight", nearest_sim=None, min_votes=1):
+    """One label per query from the arrays of :func:`class_votes` (numpy only).  ``rule``: the statistic whose argmax over the classes
+    is the label - ``weight`` (the similarity sum), ``count`` (the voters) or ``nearest`` (the similarity of the most similar voter;
+    needs ``nearest_sim``, a class without voters never wins) - ties to the smaller class.  Returns (``label`` int64: -1 where fewer
+    than ``min_votes`` (>= 1) voters are within the threshold, all classes together; ``confidence`` float64: the winner's share of
+    the statistic's total over the classes, from the integers - NaN under ``nearest``, where the total is not positive, and where
+    there is no label; ``margin`` float64: winner minus runner-up, in similarity units for ``weight`` / ``nearest``, in votes for
+    ``count``; the winner's own statistic where it is the only class with a voter; NaN where there is no label).  A share of votes
+    is no calibrated probability."""
+    if rule not in VOTE_RULES:
+        raise ValueError(f"rule {rule!r}: expected one of {VOTE_RULES}")
+    min_votes = _whole(min_votes, "min_votes", 1, 1 << 62)
+    count, weight = np.asarray(count, dtype=np.int64), np.asarray(weight, dtype=np.int64)
+    if count.ndim != 2 or weight.shape != count.shape:
+        raise ValueError(f"count {count.shape} and weight {weight.shape}: two (n_query, n_classes) arrays are required")
+    nq, nc = count.shape
+    voted = count > 0
+    if rule == "nearest":
+        if nearest_sim is None or np.shape(nearest_sim) != count.shape:
+            raise ValueError("rule 'nearest' needs nearest_sim of count's shape")
+        stat = np.where(voted, np.asarray(nearest_sim, dtype=np.float64), -np.inf)
+        unit = 1.0
+    else:
+        stat = np.where(voted, (weight if rule == "weight" else count).astype(np.float64), -np.inf)
+        unit = VOTE_UNIT if rule == "weight" else 1.0
+    label = np.full(nq, -1, dtype=np.int64)
+    confidence, margin = np.full(nq, np.nan), np.full(nq, np.nan)
+    if nc == 0:
+        return label, confidence, margin
+    # the integers decide the winner under weight / count: a float64 image of an int64 may round
+    key = stat if rule == "nearest" else np.where(voted, weight if rule == "weight" else count, np.iinfo(np.int64).min)
+    best = np.argmax(key, axis=1)                       # argmax: the first = the smaller class among equals
+    ok = count.sum(axis=1) >= min_votes
+    label[ok] = best[ok]
+    rows = np.flatnonzero(ok)
+    top = stat[rows, best[rows]]
+    rest = stat[rows].copy()
+    rest[np.arange(len(rows)), best[rows]] = -np.inf
+    second = rest.max(axis=1) if nc > 1 else np.full(len(rows), -np.inf)
+    margin[rows] = np.where(np.isfinite(second), top - second, top) / unit
+    if rule != "nearest":
+        ints = weight if rule == "weight" else count
+        total = ints[rows].sum(axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            share = ints[rows, best[rows]].astype(np.float64) / total.astype(np.float64)
+        confidence[rows] = np.where(total > 0, share, np.nan)
+    return label, confidence, margin
+
+
+def vote_table(count, weight, nearest, nearest_sim, names=None, class_names=None, base_names=None, rule="weight", min_votes=1):
+    """One record per query of a :func:`class_votes` result: ``query`` (its index; its name where ``names`` is given), ``label`` (the
+    class of :func:`vote_predict` under ``rule``; its name where ``class_names`` is given; None where there is none),
+    ``confidence``, ``votes`` (the winner's voters), ``total_votes`` (all classes'), ``nearest`` (the winner's most similar voter;
+    its name where ``base_names`` is given) and ``similarity`` (to that voter); None where there is no label."""
+    label, confidence, _ = vote_predict(count, weight, rule, nearest_sim, min_votes)
+    count = np.asarray(count, dtype=np.int64)
+    qn = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    cn = (lambda c: int(c)) if class_names is None else (lambda c: str(class_names[int(c)]))
+    bn = (lambda j: int(j)) if base_names is None else (lambda j: str(base_names[int(j)]))
+    out = []
+    for i, c in enumerate(label.tolist()):
+        rec = {"query": qn(i), "label": None, "confidence": None, "votes": 0, "total_votes": int(count[i].sum()), "nearest": None,
+               "similarity": None}
+        if c >= 0:
+            rec.update(label=cn(c), confidence=None if np.isnan(confidence[i]) else float(confidence[i]), votes=int(count[i, c]),
+                       nearest=bn(nearest[i][c]), similarity=float(nearest_sim[i][c]))
+        out.append(rec)
+    return out
+
+
 def graph_extend(old, cross, new):
     """The upper-triangle CSR of the concatenated rows [old rows; new rows] from three pieces, each an (indptr, col, sim): ``old`` =
     the graph of the old rows, ``cross`` = the matches of query = the old rows against base = the new rows, ``new`` = the graph of the

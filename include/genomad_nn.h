@@ -907,6 +907,50 @@ int gnn_debug_set_pca_split(gnn_ctx* ctx, int64_t rows_per_workgroup);
  * ask before the ctx's next call of any kind. */
 int gnn_debug_pca_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
 
+/* ---- label transfer among encoder embeddings: per-class neighbourhood votes on the device -------------------
+ * "Which class do this row's neighbours say it is": for every valid query row i and every class c of a labelled base, the voters - the
+ * valid base rows j with label[j] == c and sim(i, j) >= threshold - counted, their similarities summed and the most similar one named
+ * (the definition is sequence.class_votes).  Cosine only; validity is gnn_neighbours' under cosine; no forward pass runs and no other
+ * entry point's result changes.
+ *   value     the similarity of the pair (i, j) is the f32 that gnn_neighbours and gnn_match_* return for query i and base row j.  The
+ *             threshold is compared as the f32 given; a tie is a vote; a similarity that is not a number is none.
+ *   labels    label int64 [n_base]: a value in [0, n_classes) makes a valid row a voter, -1 means unlabelled - the row is ignored.  Any
+ *             other value: GNN_ERR_ARG, found on the device and reported after one synchronise, before any output is touched.
+ *   self      base NULL: the rows vote among themselves - n_base is ignored, label has n_query entries and the pair (i, i) is left
+ *             out: leave-one-out over a labelled set, or a per-row agreement score for the labels of gnn_cluster / gnn_density /
+ *             gnn_kmeans.
+ *   outputs   four arrays [n_query][n_classes].  count int64: the voters.  weight int64: the sum of llrint((double)s * 2^32) over them -
+ *             the similarity sum in units of 2^-32.  nearest int64 / nearest_sim f32: the most similar voter, ties to the smaller
+ *             base index; -1 / NaN where the class has no voter.  An invalid query row has 0 / 0 / -1 / NaN in every class.
+ *   exact     the product by 2^32 is exact in float64 and llrint rounds half to even, as numpy's rint does: the sums are the int64
+ *             sums of the definition taken on the device's own f32 similarities, bit for bit.  Integer add / max atomics only:
+ *             bit-identical for every split of the base (gnn_debug_set_neighbour_split), for both paths (gnn_debug_set_vote_lds) and
+ *             for the host and _dev entry points; a permutation of the base rows with their labels changes no bit of count, weight
+ *             or nearest_sim.
+ *   ranges    0 <= n_query < 2^31, 0 <= n_base <= 2^30 (|llrint(s * 2^32)| <= 2^32 + 2^10: the int64 sums of more voters could
+ *             overflow), 1 <= n_classes <= 1024, a finite threshold; GNN_ERR_ARG with the value and the range - checked before the ctx
+ *             is looked at.  n_base == 0: every class is empty.
+ * What it is not: not a top-k vote (every row within the threshold votes, however many); not the dot metric; not approximate; no width
+ * other than GNN_EMBED_DIM; not multi-GPU; no calibrated probability - a share of votes is a share of votes.
+ * Device memory, persistent in the ctx and grow-only: per base row the 2 KB of fragments + 1 B of the neighbour search (shared with it)
+ * and 4 B of its class; the queries go in slabs of 262 144 rows: 2 KB + 1 B per row of a slab (the neighbour search's query buffers)
+ * and 8 B per (row of a slab, class) of keys.  gnn_vote: + 2 KB of f32 per base row and per query row of a slab, 8 B per base row and
+ * 28 B per (row of a slab, class).  Nothing is n_query x n_base.
+ * gnn_vote: host pointers, synchronous.  gnn_vote_dev: device pointers; the ctx stream is synchronised once (the labels' verdict), the
+ * rest is enqueued on it like gnn_classify_dev. */
+int gnn_vote(gnn_ctx* ctx, const float* query_host, int64_t n_query, const float* base_host_or_null, int64_t n_base,
+             const int64_t* label_host, int n_classes, float threshold, int64_t* count_host, int64_t* weight_host, int64_t* nearest_host,
+             float* nearest_sim_host);
+int gnn_vote_dev(gnn_ctx* ctx, const float* query_dev, int64_t n_query, const float* base_dev_or_null, int64_t n_base,
+                 const int64_t* label_dev, int n_classes, float threshold, int64_t* count_dev, int64_t* weight_dev, int64_t* nearest_dev,
+                 float* nearest_sim_dev);
+/* test aid: up to max_classes classes (0 .. 16, default 16) a workgroup votes in LDS before it adds to memory; 0: every vote goes
+ * straight to memory.  No result depends on it. */
+int gnn_debug_set_vote_lds(gnn_ctx* ctx, int max_classes);
+/* measurement only: with profiling enabled, the HIP-event milliseconds of the ctx's last gnn_vote* call - [labels, then per slab of
+ * queries: votes, finish] - as gnn_debug_pca_pass_ms: synchronises the ctx stream; ask before the ctx's next call of any kind. */
+int gnn_debug_vote_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
+
 /* ---- host-side FASTA record packer (no GPU needed) ------------------------------------------------ */
 /* replaces the line loop of sequence.read_fasta(path, strip_n) (genomad/sequence.py:96-121) on an
  * in-memory text buffer (already decompressed, newlines normalised to '\n').
