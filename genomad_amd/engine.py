@@ -38,19 +38,24 @@ class DeviceBuffer:
             self.ptr = None
 
 
-class ScanResult:
+class _Result:
+    """The base of what the engine's calls return: one attribute per name of ``FIELDS`` (None for one that is not given)."""
+    FIELDS = ()
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw.get(k))
+
+    def asdict(self) -> dict:
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+
+class ScanResult(_Result):
     """What :meth:`NNEngine.scan_contigs` returns.  Windows (CSR over contigs by ``win_offsets``): ``starts`` (contig-relative),
     ``lens``, ``kept`` (bool: the N rule's mask), ``scores`` (n_windows, 3).  Bins (CSR by ``bin_offsets``, ``stride`` bases each):
     ``track`` (n_bins, 3; NaN where ``cover`` == 0), ``cover`` (kept windows averaged into the bin).  ``contig_scores``
     (n_contigs, 3): the mean of each contig's kept windows."""
     FIELDS = ("stride", "win_offsets", "starts", "lens", "kept", "scores", "bin_offsets", "track", "cover", "contig_scores")
-
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw[k])
-
-    def asdict(self) -> dict:
-        return {k: getattr(self, k) for k in self.FIELDS}
 
 
 class StrandScanResult(ScanResult):
@@ -60,7 +65,7 @@ class StrandScanResult(ScanResult):
     FIELDS = ScanResult.FIELDS + ("strand", "scores_fwd", "scores_rev")
 
 
-class OcclusionResult:
+class OcclusionResult(_Result):
     """What :meth:`NNEngine.occlude_contigs` returns.  Windows (CSR over contigs by ``win_offsets``): ``starts`` (contig-relative),
     ``lens``, ``kept`` (bool: the N rule's mask), ``scores`` (n_windows, 3: the windows' ordinary scores).  Pairs (CSR over windows
     by ``blk_offsets``, ``block`` bases each - ``sequence.occlusion_blocks``): ``delta`` (n_pairs, 3) = scores[window] - the score
@@ -68,15 +73,8 @@ class OcclusionResult:
     mean of each contig's kept windows."""
     FIELDS = ("block", "win_offsets", "starts", "lens", "kept", "scores", "blk_offsets", "delta", "contig_scores")
 
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw[k])
 
-    def asdict(self) -> dict:
-        return {k: getattr(self, k) for k in self.FIELDS}
-
-
-class AttributionResult:
+class AttributionResult(_Result):
     """What :meth:`NNEngine.attribute_contigs` returns.  Windows (CSR over contigs by ``win_offsets``): ``starts`` (contig-relative),
     ``lens``, ``kept`` (bool: the N rule's mask), ``window_scores`` (n_windows, 3).  Maps: ``contrib`` (n_windows, 2, nb, 3) - head A,
     B; bins of ``bin`` pooled positions (a position = 8 tokens; nb = ceil(749 / bin)); class - each bin's signed share of the
@@ -84,15 +82,8 @@ class AttributionResult:
     ``contig_scores`` (n_contigs, 3): the mean of each contig's kept windows."""
     FIELDS = ("bin", "win_offsets", "starts", "lens", "kept", "window_scores", "contrib", "bias", "logits", "contig_scores")
 
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw[k])
 
-    def asdict(self) -> dict:
-        return {k: getattr(self, k) for k in self.FIELDS}
-
-
-class RegionResult:
+class RegionResult(_Result):
     """What :meth:`NNEngine.call_regions` returns (the definition is ``sequence.call_regions``).  ``penalty``; bins (CSR over contigs
     by ``bin_offsets``): ``state`` (n_bins,) uint8, the path's class per bin.  Regions, ordered by contig, then position:
     ``region_contig``, ``region_lo``, ``region_hi`` (int64; contig-relative bins, half-open), ``region_state`` (uint8),
@@ -100,13 +91,6 @@ class RegionResult:
     table of ``sequence.region_table``: ``stride``, ``start``, ``end`` (bases), ``mean`` (n_regions, 3), ``margin``; None otherwise."""
     FIELDS = ("penalty", "bin_offsets", "state", "region_contig", "region_lo", "region_hi", "region_state", "region_evidence",
               "region_qsum", "stride", "start", "end", "mean", "margin")
-
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw.get(k))
-
-    def asdict(self) -> dict:
-        return {k: getattr(self, k) for k in self.FIELDS}
 
     @property
     def regions(self) -> dict:
@@ -122,7 +106,7 @@ class RegionResult:
                    stride=None if stride is None else int(stride), **table)
 
 
-class IntervalResult:
+class IntervalResult(_Result):
     """What :meth:`NNEngine.embed_intervals` returns (the definition is ``sequence.interval_embeddings``).  ``stride`` and ``strand``
     of the pass; per interval ``contig``, ``start``, ``end`` (int64; 0-based half-open bases within the contig), its member windows
     [``w_lo``, ``w_hi``) in the window order of a scan at ``stride``, ``count`` (int32: the kept members), ``embedding``
@@ -132,25 +116,11 @@ class IntervalResult:
     (n_intervals, 3): the mean of the members' window scores."""
     FIELDS = ("stride", "strand", "contig", "start", "end", "w_lo", "w_hi", "count", "embedding", "coherence", "scores")
 
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw[k])
 
-    def asdict(self) -> dict:
-        return {k: getattr(self, k) for k in self.FIELDS}
-
-
-class ClusterResult:
+class ClusterResult(_Result):
     """What :meth:`NNEngine.cluster` returns (the definition is ``sequence.threshold_clusters``): ``label``, ``degree``, ``size``,
     ``rep`` (int64 (n,); -1 / 0 / 0 / -1 for an invalid row), the ``threshold`` as the float32 it was compared as, and ``metric``."""
     FIELDS = ("label", "degree", "size", "rep", "threshold", "metric")
-
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw.get(k))
-
-    def asdict(self) -> dict:
-        return {k: getattr(self, k) for k in self.FIELDS}
 
     @property
     def n_clusters(self) -> int:
@@ -174,19 +144,12 @@ class ClusterResult:
         return cls(label=label, degree=degree, size=size, rep=rep, threshold=float(S.cluster_threshold(threshold)), metric=str(metric))
 
 
-class DensityResult:
+class DensityResult(_Result):
     """What :meth:`NNEngine.density` returns (the definition is ``sequence.density_clusters``): ``label``, ``degree``, ``size``,
     ``anchor`` (int64 (n,)), ``sim`` (float32 from the device; a border row's similarity to its anchor, NaN otherwise), ``kind``
     (uint8: 0 invalid, 1 noise, 2 border, 3 core), the ``threshold`` as the float32 it was compared as, ``min_points`` and
     ``metric``."""
     FIELDS = ("label", "degree", "size", "anchor", "sim", "kind", "threshold", "min_points", "metric")
-
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw.get(k))
-
-    def asdict(self) -> dict:
-        return {k: getattr(self, k) for k in self.FIELDS}
 
     @property
     def n_clusters(self) -> int:
@@ -219,19 +182,12 @@ class DensityResult:
                    threshold=float(S.cluster_threshold(threshold)), min_points=int(min_points), metric=str(metric))
 
 
-class KMeansResult:
+class KMeansResult(_Result):
     """What :meth:`NNEngine.kmeans` returns (the definition is ``sequence.spherical_kmeans``): ``label`` (int64 (n,); -1 for an
     invalid row), ``sim`` (float32 (n,): the similarity to the row's own centroid, NaN for an invalid row), ``centroids`` (float32
     (k, 512), unit rows), ``size`` (int64 (k,)), ``iterations``, ``converged`` and ``init_rows`` (int64 (k,): the rows the
     farthest-first traversal picked, -1 for a given init)."""
     FIELDS = ("label", "sim", "centroids", "size", "iterations", "converged", "init_rows")
-
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw.get(k))
-
-    def asdict(self) -> dict:
-        return {k: getattr(self, k) for k in self.FIELDS}
 
     @property
     def k(self) -> int:
@@ -255,7 +211,7 @@ class KMeansResult:
                    init_rows=init_rows)
 
 
-class PCAResult:
+class PCAResult(_Result):
     """What :meth:`NNEngine.pca` returns: ``mean`` (float64 (512,): the mean of the valid rows' unit vectors; zeros for
     ``center=False``), ``components`` (float32 (c, 512), unit rows, by eigenvalue descending, the entry of largest magnitude
     positive), ``explained_variance`` / ``explained_variance_ratio`` (float64 (c,)), ``total_variance``, ``n_valid``, ``valid``
@@ -263,12 +219,8 @@ class PCAResult:
     FIELDS = ("mean", "components", "explained_variance", "explained_variance_ratio", "total_variance", "n_valid", "valid", "projection")
 
     def __init__(self, engine=None, **kw):
+        super().__init__(**kw)
         self._engine = engine
-        for k in self.FIELDS:
-            setattr(self, k, kw.get(k))
-
-    def asdict(self) -> dict:
-        return {k: getattr(self, k) for k in self.FIELDS}
 
     @property
     def n_components(self) -> int:
@@ -286,20 +238,13 @@ class PCAResult:
         return S.pca_table(self.projection, self.valid, names)
 
 
-class RepresentativeResult:
+class RepresentativeResult(_Result):
     """What :meth:`NNEngine.representatives` returns (the definition is ``sequence.greedy_representatives``), in the caller's index
     space: ``rep`` (int64; a representative names itself, -1 for an invalid row), ``sim`` (float32; a member's similarity to its
     representative, NaN otherwise), ``size`` (int64; 0 for an invalid row), ``rank`` (int64; the row's place in the priority order),
     ``rounds`` (the synchronous rounds the device ran: a property of the graph and the order), the ``threshold`` as the float32 it
     was compared as, and ``metric``."""
     FIELDS = ("rep", "sim", "size", "rank", "rounds", "threshold", "metric")
-
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw.get(k))
-
-    def asdict(self) -> dict:
-        return {k: getattr(self, k) for k in self.FIELDS}
 
     @property
     def is_rep(self) -> np.ndarray:
@@ -323,18 +268,11 @@ class RepresentativeResult:
                    metric=str(metric))
 
 
-class LinkageResult:
+class LinkageResult(_Result):
     """What :meth:`NNEngine.linkage` returns (the definition is ``sequence.single_linkage_tree``): the single-linkage tree's edges,
     best first - ``a`` (int64, the smaller row), ``b`` (int64, the larger), ``sim`` (float32), trimmed to ``n_edges`` -, ``valid``
     (uint8 (n,)), ``n``, ``n_valid``, ``rounds`` (the Boruvka rounds of the device that added an edge) and ``metric``."""
     FIELDS = ("a", "b", "sim", "valid", "n", "n_valid", "rounds", "metric")
-
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw.get(k))
-
-    def asdict(self) -> dict:
-        return {k: getattr(self, k) for k in self.FIELDS}
 
     @property
     def n_edges(self) -> int:
@@ -371,19 +309,12 @@ class LinkageResult:
         return cls(a=a, b=b, sim=sim, valid=valid, n=len(valid), n_valid=int(np.count_nonzero(valid)), rounds=int(rounds), metric=str(metric))
 
 
-class GraphResult:
+class GraphResult(_Result):
     """What :meth:`NNEngine.graph` returns (the definition is ``sequence.threshold_graph``): the similarity graph's upper triangle in
     CSR form - ``indptr`` (int64 (n + 1,)), ``col`` (int32: row i owns ``col[indptr[i]:indptr[i + 1]]``, its partners j > i in
     ascending order) and ``sim`` (float32, the device's own values) -, ``valid`` (bool (n,): the rows that took part; it cannot be
     read off the graph), ``n``, ``n_edges``, the ``threshold`` as the float32 it was compared as, and ``metric``."""
     FIELDS = ("indptr", "col", "sim", "valid", "n", "n_edges", "threshold", "metric")
-
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw.get(k))
-
-    def asdict(self) -> dict:
-        return {k: getattr(self, k) for k in self.FIELDS}
 
     def edges(self):
         """COO: (a int64, b int64, sim) with a < b, in the CSR's order"""
@@ -432,20 +363,13 @@ class GraphResult:
         return GraphResult.build(arrays, np.concatenate([self.valid, new.valid]), self.threshold, self.metric)
 
 
-class MatchResult:
+class MatchResult(_Result):
     """What :meth:`NNEngine.match` returns (the definition is ``sequence.threshold_matches``): the bipartite similarity graph query x
     base in CSR form by query row - ``indptr`` (int64 (n_query + 1,)), ``col`` (int32: query i owns ``col[indptr[i]:indptr[i + 1]]``,
     its base partners in ascending order) and ``sim`` (float32, the device's own values: what :meth:`NNEngine.neighbours` returns for
     query i and base row j) -, ``query_valid`` and ``base_valid`` (bool: the rows that took part), ``n_query``, ``n_base``,
     ``n_edges``, the ``threshold`` as the float32 it was compared as, and ``metric``."""
     FIELDS = ("indptr", "col", "sim", "query_valid", "base_valid", "n_query", "n_base", "n_edges", "threshold", "metric")
-
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw.get(k))
-
-    def asdict(self) -> dict:
-        return {k: getattr(self, k) for k in self.FIELDS}
 
     def edges(self):
         """COO: (query int64, base int64, sim), in the CSR's order"""
@@ -486,7 +410,7 @@ class MatchResult:
                    n_base=len(base_valid), n_edges=len(col), threshold=float(_sequence.cluster_threshold(threshold)), metric=str(metric))
 
 
-class VoteResult:
+class VoteResult(_Result):
     """What :meth:`NNEngine.vote` returns (the definition is ``sequence.class_votes``): per query row and class of a labelled base,
     over the voters - the valid base rows of the class whose cosine similarity reaches the threshold - ``count`` (int64: how many),
     ``weight`` (int64: their similarities summed in units of 2^-32), ``nearest`` (int64) and ``nearest_sim`` (float32, the device's
@@ -494,13 +418,6 @@ class VoteResult:
     ``query_valid`` (bool: the rows that took part; the others have 0 / 0 / -1 / NaN), ``n_classes`` and the ``threshold`` as the
     float32 it was compared as."""
     FIELDS = ("count", "weight", "nearest", "nearest_sim", "query_valid", "n_classes", "threshold")
-
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw.get(k))
-
-    def asdict(self) -> dict:
-        return {k: getattr(self, k) for k in self.FIELDS}
 
     def similarity_sum(self) -> np.ndarray:
         """float64 (n_query, n_classes): ``weight`` / 2^32 - the voters' similarities summed"""
@@ -1009,6 +926,26 @@ class NNEngine:
     def _knn_metric(metric) -> int:
         return _lib.KNN_METRICS[metric] if isinstance(metric, str) else int(metric)
 
+    @staticmethod
+    def _check_metric(metric):
+        """an unknown metric name is a ``ValueError`` before anything is allocated or launched"""
+        if isinstance(metric, str) and metric not in _lib.KNN_METRICS:
+            raise ValueError(f"metric {metric!r}: expected one of {tuple(_lib.KNN_METRICS)}")
+
+    @staticmethod
+    def _metric_name(metric) -> str:
+        """the name of a metric given by name or by the library's code"""
+        return metric if isinstance(metric, str) else {v: k for k, v in _lib.KNN_METRICS.items()}[int(metric)]
+
+    def _debug_ms(self, fn) -> np.ndarray:
+        """the float64 milliseconds a ``gnn_debug_*_ms`` entry point keeps: ask for their number, allocate, ask again"""
+        n = C.c_int64(0)
+        check(fn(self.ctx, None, 0, C.addressof(n)))
+        ms = np.zeros(n.value, np.float64)
+        if n.value:
+            check(fn(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
+        return ms
+
     def neighbours(self, query, base=None, k=10, metric="cosine"):
         """Nearest neighbours among encoder embeddings (``gnn_neighbours``; the definition is ``sequence.nearest_neighbours``): for
         every row of ``query`` (nq, 512) its ``k`` (1..64) most similar rows of ``base`` (nb, 512) under ``metric`` ("cosine" or
@@ -1038,8 +975,7 @@ class NNEngine:
         (a representative with few edges for its cluster's size) from a clique.  :meth:`set_neighbour_split` sets the range of
         this search too; no result depends on it."""
         r = _sequence.neighbour_rows(rows, "rows")
-        if isinstance(metric, str) and metric not in _lib.KNN_METRICS:
-            raise ValueError(f"metric {metric!r}: expected one of {tuple(_lib.KNN_METRICS)}")
+        self._check_metric(metric)
         out = [np.empty(len(r), dtype=np.int64) for _ in range(4)]
         check(self.lib.gnn_cluster(self.ctx, r.ctypes.data, len(r), float(threshold), self._knn_metric(metric),
                                    *(a.ctypes.data for a in out)))
@@ -1063,8 +999,7 @@ class NNEngine:
         the result depends on no visiting order.  :meth:`set_neighbour_split` sets the range of this search too; no result depends
         on it."""
         r = _sequence.neighbour_rows(rows, "rows")
-        if isinstance(metric, str) and metric not in _lib.KNN_METRICS:
-            raise ValueError(f"metric {metric!r}: expected one of {tuple(_lib.KNN_METRICS)}")
+        self._check_metric(metric)
         n = len(r)
         out = [np.empty(n, dtype=np.int64) for _ in range(4)] + [np.empty(n, dtype=np.float32), np.empty(n, dtype=np.uint8)]
         check(self.lib.gnn_density(self.ctx, r.ctypes.data, n, float(threshold), int(min_points), self._knn_metric(metric),
@@ -1088,8 +1023,7 @@ class NNEngine:
         threshold of -1 on 262 144 rows is 3.4e10 edges).  :meth:`set_neighbour_split` sets the range of this search too; no
         result depends on it."""
         r = _sequence.neighbour_rows(rows, "rows")
-        if isinstance(metric, str) and metric not in _lib.KNN_METRICS:
-            raise ValueError(f"metric {metric!r}: expected one of {tuple(_lib.KNN_METRICS)}")
+        self._check_metric(metric)
         code = self._knn_metric(metric)
         n = len(r)
         indptr = np.empty(n + 1, dtype=np.int64)
@@ -1101,7 +1035,7 @@ class NNEngine:
                              f"{int(max_edges)}: raise the threshold or max_edges")
         col, sim = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float32)
         check(self.lib.gnn_graph_fill(self.ctx, n, float(threshold), code, col.ctypes.data, sim.ctypes.data, m))
-        name = metric if isinstance(metric, str) else {v: k for k, v in _lib.KNN_METRICS.items()}[code]
+        name = self._metric_name(metric)
         return GraphResult.build((indptr, col, sim), _sequence.valid_rows(r, name), np.float32(threshold), name)
 
     def graph_count_dev(self, rows_ptr: int, n: int, threshold, indptr_ptr: int, metric="cosine") -> int:
@@ -1122,12 +1056,7 @@ class NNEngine:
     def graph_pass_ms(self):
         """measurement only (``gnn_debug_graph_pass_ms``): with profiling enabled, the HIP-event milliseconds of the last count call's
         [count pass, scan]"""
-        n = C.c_int64(0)
-        check(self.lib.gnn_debug_graph_pass_ms(self.ctx, None, 0, C.addressof(n)))
-        ms = np.zeros(n.value, np.float64)
-        if n.value:
-            check(self.lib.gnn_debug_graph_pass_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
-        return ms
+        return self._debug_ms(self.lib.gnn_debug_graph_pass_ms)
 
     # -- matches against a reference -----------------------------------------------------
     def match(self, query, base, threshold, metric="cosine", max_edges=1 << 28) -> MatchResult:
@@ -1141,8 +1070,7 @@ class NNEngine:
         result depends on it."""
         q = _sequence.neighbour_rows(query)
         b = _sequence.neighbour_rows(base, "base")
-        if isinstance(metric, str) and metric not in _lib.KNN_METRICS:
-            raise ValueError(f"metric {metric!r}: expected one of {tuple(_lib.KNN_METRICS)}")
+        self._check_metric(metric)
         code = self._knn_metric(metric)
         nq, nb = len(q), len(b)
         indptr = np.empty(nq + 1, dtype=np.int64)
@@ -1155,7 +1083,7 @@ class NNEngine:
                              f"{int(max_edges)}: raise the threshold or max_edges")
         col, sim = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float32)
         check(self.lib.gnn_match_fill(self.ctx, nq, nb, float(threshold), code, col.ctypes.data, sim.ctypes.data, m))
-        name = metric if isinstance(metric, str) else {v: k for k, v in _lib.KNN_METRICS.items()}[code]
+        name = self._metric_name(metric)
         return MatchResult.build((indptr, col, sim), _sequence.valid_rows(q, name), _sequence.valid_rows(b, name), np.float32(threshold),
                                  name)
 
@@ -1179,12 +1107,7 @@ class NNEngine:
     def match_pass_ms(self):
         """measurement only (``gnn_debug_match_pass_ms``): with profiling enabled, the HIP-event milliseconds of the last count call's
         [count pass, scan]"""
-        n = C.c_int64(0)
-        check(self.lib.gnn_debug_match_pass_ms(self.ctx, None, 0, C.addressof(n)))
-        ms = np.zeros(n.value, np.float64)
-        if n.value:
-            check(self.lib.gnn_debug_match_pass_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
-        return ms
+        return self._debug_ms(self.lib.gnn_debug_match_pass_ms)
 
     # -- label transfer ------------------------------------------------------------------
     def vote(self, query, base, label, n_classes, threshold) -> VoteResult:
@@ -1227,12 +1150,7 @@ class NNEngine:
     def vote_pass_ms(self):
         """measurement only (``gnn_debug_vote_pass_ms``): with profiling enabled, the HIP-event milliseconds of the last
         :meth:`vote` / :meth:`vote_dev` call - [labels, then per slab of 262 144 queries: votes, finish]"""
-        n = C.c_int64(0)
-        check(self.lib.gnn_debug_vote_pass_ms(self.ctx, None, 0, C.addressof(n)))
-        ms = np.zeros(n.value, np.float64)
-        if n.value:
-            check(self.lib.gnn_debug_vote_pass_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
-        return ms
+        return self._debug_ms(self.lib.gnn_debug_vote_pass_ms)
 
     # -- spherical k-means ---------------------------------------------------------------
     def kmeans(self, rows, k, init=None, max_iter=_sequence.KMEANS_MAX_ITER_DEFAULT) -> KMeansResult:
@@ -1304,12 +1222,7 @@ class NNEngine:
         """measurement only (``gnn_debug_kmeans_pass_ms``): with profiling enabled, the HIP-event milliseconds of the last
         :meth:`kmeans` / :meth:`kmeans_dev` call - [init, then per assignment: assign, and behind every assignment but the last:
         update, finish, prepare]"""
-        n = C.c_int64(0)
-        check(self.lib.gnn_debug_kmeans_pass_ms(self.ctx, None, 0, C.addressof(n)))
-        ms = np.zeros(n.value, np.float64)
-        if n.value:
-            check(self.lib.gnn_debug_kmeans_pass_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
-        return ms
+        return self._debug_ms(self.lib.gnn_debug_kmeans_pass_ms)
 
     # -- principal components ------------------------------------------------------------
     def pca_moments(self, rows):
@@ -1380,12 +1293,7 @@ class NNEngine:
     def pca_pass_ms(self):
         """measurement only (``gnn_debug_pca_pass_ms``): with profiling enabled, the HIP-event milliseconds of the last moments
         call - [prepare, sums, gram, mirror] - or projection - [prepare rows, prepare components, project]"""
-        n = C.c_int64(0)
-        check(self.lib.gnn_debug_pca_pass_ms(self.ctx, None, 0, C.addressof(n)))
-        ms = np.zeros(n.value, np.float64)
-        if n.value:
-            check(self.lib.gnn_debug_pca_pass_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
-        return ms
+        return self._debug_ms(self.lib.gnn_debug_pca_pass_ms)
 
     # -- representatives -----------------------------------------------------------------
     def representatives(self, rows, threshold, weight=None, metric="cosine") -> RepresentativeResult:
@@ -1399,8 +1307,7 @@ class NNEngine:
         rounds (``rounds``; a path walked end to end takes as many as it has rows), one stream synchronise each.
         :meth:`set_neighbour_split` sets the range of this search too; no result depends on it."""
         r = _sequence.neighbour_rows(rows, "rows")
-        if isinstance(metric, str) and metric not in _lib.KNN_METRICS:
-            raise ValueError(f"metric {metric!r}: expected one of {tuple(_lib.KNN_METRICS)}")
+        self._check_metric(metric)
         n = len(r)
         order = _sequence.priority_order(weight, n)
         rank = np.empty(n, dtype=np.int64)
@@ -1427,17 +1334,11 @@ class NNEngine:
     def representative_round_ms(self):
         """measurement only (``gnn_debug_representative_round_ms``): with profiling enabled, the HIP-event milliseconds of every
         round of the last ``representatives`` / ``representatives_dev`` call"""
-        n = C.c_int64(0)
-        check(self.lib.gnn_debug_representative_round_ms(self.ctx, None, 0, C.addressof(n)))
-        ms = np.zeros(n.value, np.float64)
-        if n.value:
-            check(self.lib.gnn_debug_representative_round_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
-        return ms
+        return self._debug_ms(self.lib.gnn_debug_representative_round_ms)
 
     # -- single-linkage tree -------------------------------------------------------------
     def _linkage(self, fn, rows_ptr, n, metric) -> LinkageResult:
-        if isinstance(metric, str) and metric not in _lib.KNN_METRICS:
-            raise ValueError(f"metric {metric!r}: expected one of {tuple(_lib.KNN_METRICS)}")
+        self._check_metric(metric)
         cap = max(int(n) - 1, 0)
         a, b, sim = np.empty(cap, np.int64), np.empty(cap, np.int64), np.empty(cap, np.float32)
         valid = np.zeros(max(int(n), 0), np.uint8)
@@ -1445,7 +1346,7 @@ class NNEngine:
         check(fn(self.ctx, rows_ptr, int(n), self._knn_metric(metric), a.ctypes.data, b.ctypes.data, sim.ctypes.data, valid.ctypes.data,
                  C.addressof(n_edges), C.addressof(rounds)))
         m = n_edges.value
-        name = metric if isinstance(metric, str) else {v: k for k, v in _lib.KNN_METRICS.items()}[int(metric)]
+        name = self._metric_name(metric)
         return LinkageResult.build((a[:m].copy(), b[:m].copy(), sim[:m].copy(), valid), name, rounds.value)
 
     def linkage(self, rows, metric="cosine") -> LinkageResult:
@@ -1466,12 +1367,7 @@ class NNEngine:
     def linkage_round_ms(self):
         """measurement only (``gnn_debug_linkage_round_ms``): with profiling enabled, the HIP-event milliseconds of every round of the
         last ``linkage`` / ``linkage_dev`` call, a last round that added no edge included"""
-        n = C.c_int64(0)
-        check(self.lib.gnn_debug_linkage_round_ms(self.ctx, None, 0, C.addressof(n)))
-        ms = np.zeros(n.value, np.float64)
-        if n.value:
-            check(self.lib.gnn_debug_linkage_round_ms(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
-        return ms
+        return self._debug_ms(self.lib.gnn_debug_linkage_round_ms)
 
     # -- occlusion maps ------------------------------------------------------------------
     def occlusion_plan(self, offsets: np.ndarray, block: int, single_window: bool = False):

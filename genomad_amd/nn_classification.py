@@ -28,8 +28,10 @@ import shutil
 import sys
 import threading
 import time
+from collections import namedtuple
 from datetime import datetime, timezone
 from pathlib import Path
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -85,62 +87,33 @@ class Outputs:
         # written only when GENOMAD_AMD_REGION_EMBEDDINGS=1 (encoder embeddings per called region; no counterpart in the reference)
         self.nn_region_embeddings_output = d / f"{p}_nn_region_embeddings.npz"
         self.provirus_nn_region_embeddings_output = d / f"{p}_provirus_nn_region_embeddings.npz"
-        # written only when GENOMAD_AMD_NEIGHBOURS is set (nearest neighbours among the per-contig embeddings; no counterpart in the reference)
-        self.nn_neighbours_output = d / f"{p}_nn_neighbours.npz"
-        self.provirus_nn_neighbours_output = d / f"{p}_provirus_nn_neighbours.npz"
-        # written only when GENOMAD_AMD_CLUSTERS is set (threshold clusters among the per-contig embeddings; no counterpart in the reference)
-        self.nn_clusters_output = d / f"{p}_nn_clusters.npz"
-        self.nn_clusters_tsv_output = d / f"{p}_nn_clusters.tsv"
-        self.provirus_nn_clusters_output = d / f"{p}_provirus_nn_clusters.npz"
-        self.provirus_nn_clusters_tsv_output = d / f"{p}_provirus_nn_clusters.tsv"
-        # written only when GENOMAD_AMD_DENSITY is set (density clusters among the per-contig embeddings; no counterpart in the reference)
-        self.nn_density_output = d / f"{p}_nn_density.npz"
-        self.nn_density_tsv_output = d / f"{p}_nn_density.tsv"
-        self.provirus_nn_density_output = d / f"{p}_provirus_nn_density.npz"
-        self.provirus_nn_density_tsv_output = d / f"{p}_provirus_nn_density.tsv"
-        # written only when GENOMAD_AMD_KMEANS is set (spherical k-means among the per-contig embeddings; no counterpart in the reference)
-        self.nn_kmeans_output = d / f"{p}_nn_kmeans.npz"
-        self.nn_kmeans_tsv_output = d / f"{p}_nn_kmeans.tsv"
-        self.provirus_nn_kmeans_output = d / f"{p}_provirus_nn_kmeans.npz"
-        self.provirus_nn_kmeans_tsv_output = d / f"{p}_provirus_nn_kmeans.tsv"
-        # written only when GENOMAD_AMD_PCA is set (principal components among the per-contig embeddings; no counterpart in the reference)
-        self.nn_pca_output = d / f"{p}_nn_pca.npz"
-        self.nn_pca_tsv_output = d / f"{p}_nn_pca.tsv"
-        self.provirus_nn_pca_output = d / f"{p}_provirus_nn_pca.npz"
-        self.provirus_nn_pca_tsv_output = d / f"{p}_provirus_nn_pca.tsv"
-        # written only when GENOMAD_AMD_REPRESENTATIVES is set (greedy clusters among the per-contig embeddings; no counterpart in the reference)
-        self.nn_representatives_output = d / f"{p}_nn_representatives.npz"
-        self.nn_representatives_tsv_output = d / f"{p}_nn_representatives.tsv"
-        self.provirus_nn_representatives_output = d / f"{p}_provirus_nn_representatives.npz"
-        self.provirus_nn_representatives_tsv_output = d / f"{p}_provirus_nn_representatives.tsv"
-        # written only when GENOMAD_AMD_LINKAGE=1 (the single-linkage tree among the per-contig embeddings; no counterpart in the reference)
-        self.nn_linkage_output = d / f"{p}_nn_linkage.npz"
-        self.nn_linkage_tsv_output = d / f"{p}_nn_linkage.tsv"
-        self.provirus_nn_linkage_output = d / f"{p}_provirus_nn_linkage.npz"
-        self.provirus_nn_linkage_tsv_output = d / f"{p}_provirus_nn_linkage.tsv"
-        # written only when GENOMAD_AMD_GRAPH is set (the similarity graph among the per-contig embeddings; no counterpart in the reference)
-        self.nn_graph_output = d / f"{p}_nn_graph.npz"
-        self.nn_graph_tsv_output = d / f"{p}_nn_graph.tsv"
-        self.provirus_nn_graph_output = d / f"{p}_provirus_nn_graph.npz"
-        self.provirus_nn_graph_tsv_output = d / f"{p}_provirus_nn_graph.tsv"
-        # written only when GENOMAD_AMD_MATCH and GENOMAD_AMD_MATCH_BASE are set (the matches of the per-contig embeddings against a
-        # reference's; no counterpart in the reference)
-        self.nn_matches_output = d / f"{p}_nn_matches.npz"
-        self.nn_matches_tsv_output = d / f"{p}_nn_matches.tsv"
-        self.provirus_nn_matches_output = d / f"{p}_provirus_nn_matches.npz"
-        self.provirus_nn_matches_tsv_output = d / f"{p}_provirus_nn_matches.tsv"
-        # written only when GENOMAD_AMD_VOTE and GENOMAD_AMD_VOTE_BASE are set (the per-class votes of a labelled reference's embeddings
-        # on the per-contig embeddings; no counterpart in the reference)
-        self.nn_votes_output = d / f"{p}_nn_votes.npz"
-        self.nn_votes_tsv_output = d / f"{p}_nn_votes.tsv"
-        self.provirus_nn_votes_output = d / f"{p}_provirus_nn_votes.npz"
-        self.provirus_nn_votes_tsv_output = d / f"{p}_provirus_nn_votes.tsv"
+        # written only when the analysis is requested (the ten analyses of the per-contig embeddings, ANALYSES below: <stem>.npz and,
+        # for all but the neighbours, <stem>.tsv; no counterpart in the reference)
+        for stage in self._STAGE.values():
+            for a in ANALYSES:
+                setattr(self, f"{stage}nn_{a.name}_output", d / f"{p}_{stage}nn_{a.name}.npz")
+                if a.tsv:
+                    setattr(self, f"{stage}nn_{a.name}_tsv_output", d / f"{p}_{stage}nn_{a.name}.tsv")
         f = o / f"{p}_find_proviruses"
         self.find_proviruses_execution_info = f / f"{p}_find_proviruses.json"
         self.find_proviruses_output = f / f"{p}_provirus.tsv"
         self.find_proviruses_nucleotide_output = f / f"{p}_provirus.fna"
         self.find_proviruses_proteins_output = f / f"{p}_provirus_proteins.faa"
         self.find_proviruses_genes_output = f / f"{p}_provirus_genes.tsv"
+
+    _STAGE = {"sequence": "", "provirus": "provirus_"}          # main()'s name of a stage -> what its files' names carry
+
+    def files(self, what, name):
+        """(npz, tsv or None) of a stage's output ``name`` - "strand", "regions", ..., or one of the ANALYSES"""
+        stem = f"{self._STAGE[what]}nn_{name}"
+        return getattr(self, f"{stem}_output"), getattr(self, f"{stem}_tsv_output", None)
+
+    def classification_files(self, what):
+        """(directory of the encoded windows, window ids, scores npz, scores tsv) of a stage"""
+        if what == "sequence":
+            return self.encoded_sequences_dir, self.seq_window_id_output, self.nn_classification_npz_output, self.nn_classification_output
+        return (self.encoded_proviruses_dir, self.provirus_window_id_output, self.provirus_nn_classification_npz_output,
+                self.provirus_nn_classification_output)
 
 
 class Console:
@@ -418,6 +391,65 @@ def embed_contigs_safely(eng, seq, offsets, single_window, precision, console=No
     return pr, emb, wid
 
 
+def _env_similarity(name, meaning):
+    """The switch ``name`` as a cosine similarity: a float in [-1, 1], returned as it is compared - the float32 it rounds to; unset or
+    empty: None.  Any other value is a ``ValueError`` that ends with ``meaning``."""
+    v = os.environ.get(name, "").strip()
+    if not v:
+        return None
+    try:
+        t = float(v)
+    except ValueError:
+        t = float("nan")
+    if not -1.0 <= t <= 1.0:                             # a NaN fails both comparisons
+        raise ValueError(f"{name}={v!r}: expected a float in [-1, 1] {meaning}")
+    return float(np.float32(t))
+
+
+def _env_int(name, lo, hi, meaning, default=None):
+    """The switch ``name`` as an integer in [lo, hi] (``hi`` None: no upper bound); unset or empty: ``default``.  Any other value is a
+    ``ValueError`` that ends with ``meaning``."""
+    v = os.environ.get(name, "").strip()
+    if not v:
+        return default
+    try:
+        k = int(v)
+    except ValueError:
+        k = lo - 1
+    if k < lo or (hi is not None and k > hi):
+        bounds = f"in [{lo}, {hi}]" if hi is not None and hi < (1 << 31) - 1 else f">= {lo}"      # the int32 limit is not spelt out
+        raise ValueError(f"{name}={v!r}: expected an integer {bounds} {meaning}")
+    return k
+
+
+def _env_refines(name, other, advice):
+    """``name`` only refines the request of ``other``: set without it, it is a ``ValueError``"""
+    m = os.environ.get(name, "").strip()
+    if m:
+        raise ValueError(f"{name}={m!r} needs {other}: {advice} {name}")
+
+
+def _strand_entry(strand) -> dict:
+    """the ``strand`` entry of an output file, which only reverse / both write (:func:`_npz_strand`)"""
+    return {"strand": np.array(strand)} if strand != "forward" else {}
+
+
+_UNREADABLE = object()        # what _request_of_file says of a file it cannot read: equal to no request, so the stage runs again
+
+
+def _request_of_file(path, keys):
+    """The request an output file of a stage was computed with, as it spells it: the value of its entry ``keys`` = ((name, cast),),
+    or the tuple of several; no file = None (nothing was asked for); a file that cannot be read = ``_UNREADABLE``."""
+    if not Path(path).exists():
+        return None
+    try:
+        z = np.load(path)
+        got = tuple(cast(z[k]) for k, cast in keys)
+    except Exception:  # noqa: BLE001
+        return _UNREADABLE
+    return got[0] if len(got) == 1 else got
+
+
 def embeddings_requested() -> bool:
     """GENOMAD_AMD_EMBEDDINGS=1: main() also writes the per-contig encoder embeddings (<prefix>_nn_embeddings.npz); unset or 0:
     nothing changes.  Any other value is an error."""
@@ -440,16 +472,7 @@ def scan_contigs_safely(eng, seq, offsets, stride, single_window, precision, con
 def scan_stride_requested():
     """GENOMAD_AMD_SCAN_STRIDE=<int in [1, 6000]>: main() also writes the score tracks along the contigs (<prefix>_nn_scan.npz),
     windows every that many bases; unset or empty: nothing changes (None).  Any other value is an error."""
-    v = os.environ.get("GENOMAD_AMD_SCAN_STRIDE", "").strip()
-    if not v:
-        return None
-    try:
-        stride = int(v)
-    except ValueError:
-        stride = 0
-    if not 1 <= stride <= sequence.WINDOW:
-        raise ValueError(f"GENOMAD_AMD_SCAN_STRIDE={v!r}: expected an integer in [1, {sequence.WINDOW}] (bases between window starts)")
-    return stride
+    return _env_int("GENOMAD_AMD_SCAN_STRIDE", 1, sequence.WINDOW, "(bases between window starts)")
 
 
 def _scan_file_has_stride(path, stride) -> bool:
@@ -473,26 +496,7 @@ def occlusion_block_requested():
     """GENOMAD_AMD_OCCLUSION_BLOCK=<int in [1, 6000]>: main() also writes the occlusion maps of the contigs (<prefix>_nn_occlusion.npz):
     every window scored again with each block of that many bases set to N; unset or empty: nothing changes (None).  Any other value
     is an error."""
-    v = os.environ.get("GENOMAD_AMD_OCCLUSION_BLOCK", "").strip()
-    if not v:
-        return None
-    try:
-        block = int(v)
-    except ValueError:
-        block = 0
-    if not 1 <= block <= sequence.WINDOW:
-        raise ValueError(f"GENOMAD_AMD_OCCLUSION_BLOCK={v!r}: expected an integer in [1, {sequence.WINDOW}] (bases per occluded block)")
-    return block
-
-
-def _occlusion_block_of_file(path):
-    """The block size a stage's occlusion file was computed with; no file = None (no occlusion was asked for)."""
-    if not Path(path).exists():
-        return None
-    try:
-        return int(np.load(path)["block"])
-    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
-        return -1
+    return _env_int("GENOMAD_AMD_OCCLUSION_BLOCK", 1, sequence.WINDOW, "(bases per occluded block)")
 
 
 def attribute_contigs_safely(eng, seq, offsets, bin, single_window, precision, console=None):
@@ -512,26 +516,7 @@ def attribution_bin_requested():
     """GENOMAD_AMD_ATTRIBUTION_BIN=<int in [1, 749]>: main() also writes the attention contribution maps of the windows
     (<prefix>_nn_attribution.npz): each bin of that many pooled positions' share of every window's logits, computed in the pass that
     scores the window; unset or empty: nothing changes (None).  Any other value is an error."""
-    v = os.environ.get("GENOMAD_AMD_ATTRIBUTION_BIN", "").strip()
-    if not v:
-        return None
-    try:
-        bin_ = int(v)
-    except ValueError:
-        bin_ = 0
-    if not 1 <= bin_ <= ATTRIBUTION_POSITIONS:
-        raise ValueError(f"GENOMAD_AMD_ATTRIBUTION_BIN={v!r}: expected an integer in [1, {ATTRIBUTION_POSITIONS}] (pooled positions per bin of the map)")
-    return bin_
-
-
-def _attribution_bin_of_file(path):
-    """The bin a stage's attribution file was computed with; no file = None (no attribution was asked for)."""
-    if not Path(path).exists():
-        return None
-    try:
-        return int(np.load(path)["bin"])
-    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
-        return -1
+    return _env_int("GENOMAD_AMD_ATTRIBUTION_BIN", 1, ATTRIBUTION_POSITIONS, "(pooled positions per bin of the map)")
 
 
 def region_penalty_requested():
@@ -549,17 +534,6 @@ def region_penalty_requested():
         raise ValueError(f"GENOMAD_AMD_REGION_PENALTY={v!r}: expected a number in [0, {sequence.REGION_PENALTY_MAX:g}] (the cost of a switch "
                          "between classes, in score x bins)")
     return penalty
-
-
-def _regions_of_file(path):
-    """(stride, penalty) a stage's region file was computed with; no file = None (no regions were asked for)."""
-    if not Path(path).exists():
-        return None
-    try:
-        z = np.load(path)
-        return int(z["stride"]), float(z["penalty"])
-    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
-        return -1, -1.0
 
 
 def embed_intervals_safely(eng, seq, offsets, stride, contig, start, end, strand, single_window, precision, console=None):
@@ -582,17 +556,6 @@ def region_embeddings_requested() -> bool:
     return v == "1"
 
 
-def _region_embeddings_of_file(path):
-    """(stride, penalty, strand) a stage's region embeddings were computed with; no file = None (none were asked for)."""
-    if not Path(path).exists():
-        return None
-    try:
-        z = np.load(path)
-        return int(z["stride"]), float(z["penalty"]), str(z["strand"])
-    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
-        return -1, -1.0, ""
-
-
 NEIGHBOUR_METRIC = "cosine"          # what main() searches with
 
 
@@ -600,52 +563,21 @@ def neighbours_requested():
     """GENOMAD_AMD_NEIGHBOURS=<int in [1, 64]>: main() also writes every contig's that many nearest neighbours among the per-contig
     encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1 (<prefix>_nn_neighbours.npz: cosine similarity, the contig itself excluded);
     unset or empty: nothing changes (None).  Any other value is an error."""
-    v = os.environ.get("GENOMAD_AMD_NEIGHBOURS", "").strip()
-    if not v:
-        return None
-    try:
-        k = int(v)
-    except ValueError:
-        k = 0
-    if not 1 <= k <= sequence.NEIGHBOUR_K_MAX:
-        raise ValueError(f"GENOMAD_AMD_NEIGHBOURS={v!r}: expected an integer in [1, {sequence.NEIGHBOUR_K_MAX}] (neighbours per contig)")
-    return k
+    return _env_int("GENOMAD_AMD_NEIGHBOURS", 1, sequence.NEIGHBOUR_K_MAX, "(neighbours per contig)")
 
 
-def _neighbours_of_file(path):
-    """The k a stage's neighbour file was computed with; no file = None (no neighbours were asked for)."""
-    if not Path(path).exists():
-        return None
-    try:
-        return int(np.load(path)["k"])
-    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
-        return -1
+def write_neighbours(npz_path, names_key, names, res, k, strand="forward"):
+    """The neighbour file of a stage: the (idx, sim) of NNEngine.neighbours with the contig names."""
+    idx, sim = res
+    np.savez_compressed(npz_path, **{names_key: names, "k": np.int64(k), "metric": np.array(NEIGHBOUR_METRIC), "idx": idx, "sim": sim,
+                                     **_strand_entry(strand)})
 
 
 def clusters_requested():
     """GENOMAD_AMD_CLUSTERS=<float in [-1, 1]>: main() also writes the single-linkage clusters of the contigs at that cosine similarity
     of the per-contig encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1 (<prefix>_nn_clusters.npz and .tsv); unset or empty: nothing
     changes (None).  Any other value is an error.  Returns the threshold as it is compared: the float32 it rounds to."""
-    v = os.environ.get("GENOMAD_AMD_CLUSTERS", "").strip()
-    if not v:
-        return None
-    try:
-        t = float(v)
-    except ValueError:
-        t = float("nan")
-    if not -1.0 <= t <= 1.0:                             # a NaN fails both comparisons
-        raise ValueError(f"GENOMAD_AMD_CLUSTERS={v!r}: expected a float in [-1, 1] (the cosine similarity at which two contigs are joined)")
-    return float(np.float32(t))
-
-
-def _clusters_of_file(path):
-    """The threshold a stage's cluster file was computed with; no file = None (no clusters were asked for)."""
-    if not Path(path).exists():
-        return None
-    try:
-        return float(np.load(path)["threshold"])
-    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
-        return float("nan")
+    return _env_similarity("GENOMAD_AMD_CLUSTERS", "(the cosine similarity at which two contigs are joined)")
 
 
 CLUSTER_TSV_HEADER = "seq_name\tcluster\tcluster_size\trepresentative\tdegree\n"
@@ -663,6 +595,13 @@ def write_clusters_tsv(path, names, res):
                 fout.write(f"{name}\t{names[res.label[i]]}\t{res.size[i]}\t{names[res.rep[i]]}\t{res.degree[i]}\n")
 
 
+def write_clusters(npz_path, tsv_path, names_key, names, res, threshold, strand="forward"):
+    """Both cluster files of a stage: the arrays of a ClusterResult with the contig names, and one line per contig."""
+    np.savez_compressed(npz_path, **{names_key: names, "threshold": np.float64(threshold), "metric": np.array(NEIGHBOUR_METRIC),
+                                     "label": res.label, "degree": res.degree, "size": res.size, "rep": res.rep, **_strand_entry(strand)})
+    write_clusters_tsv(tsv_path, names, res)
+
+
 DENSITY_MIN_POINTS_DEFAULT = 5
 
 
@@ -672,39 +611,12 @@ def density_requested():
     changes (None).  GENOMAD_AMD_DENSITY_MIN_POINTS=<integer >= 1> (default 5) is how many contigs, itself included, a contig needs
     within the threshold to be a core contig; it is an error without GENOMAD_AMD_DENSITY.  Any other value of either is an error.
     Returns (the threshold as it is compared: the float32 it rounds to, min_points), or None."""
-    v = os.environ.get("GENOMAD_AMD_DENSITY", "").strip()
-    m = os.environ.get("GENOMAD_AMD_DENSITY_MIN_POINTS", "").strip()
-    if not v:
-        if m:
-            raise ValueError(f"GENOMAD_AMD_DENSITY_MIN_POINTS={m!r} needs GENOMAD_AMD_DENSITY: set the threshold of the density clusters "
-                             "or unset GENOMAD_AMD_DENSITY_MIN_POINTS")
+    t = _env_similarity("GENOMAD_AMD_DENSITY", "(the cosine similarity within which contigs count towards each other's density)")
+    if t is None:
+        _env_refines("GENOMAD_AMD_DENSITY_MIN_POINTS", "GENOMAD_AMD_DENSITY", "set the threshold of the density clusters or unset")
         return None
-    try:
-        t = float(v)
-    except ValueError:
-        t = float("nan")
-    if not -1.0 <= t <= 1.0:                             # a NaN fails both comparisons
-        raise ValueError(f"GENOMAD_AMD_DENSITY={v!r}: expected a float in [-1, 1] (the cosine similarity within which contigs count "
-                         "towards each other's density)")
-    try:
-        k = int(m) if m else DENSITY_MIN_POINTS_DEFAULT
-    except ValueError:
-        k = 0
-    if not 1 <= k < sequence.DENSITY_MIN_POINTS_END:
-        raise ValueError(f"GENOMAD_AMD_DENSITY_MIN_POINTS={m!r}: expected an integer >= 1 (below 2^31): the contigs, itself included, "
-                         "that a core contig has within the threshold")
-    return float(np.float32(t)), k
-
-
-def _density_of_file(path):
-    """The (threshold, min_points) a stage's density file was computed with; no file = None (no density clusters were asked for)."""
-    if not Path(path).exists():
-        return None
-    try:
-        z = np.load(path)
-        return float(z["threshold"]), int(z["min_points"])
-    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
-        return float("nan"), -1
+    return t, _env_int("GENOMAD_AMD_DENSITY_MIN_POINTS", 1, sequence.DENSITY_MIN_POINTS_END - 1,
+                       "(below 2^31): the contigs, itself included, that a core contig has within the threshold", DENSITY_MIN_POINTS_DEFAULT)
 
 
 DENSITY_TSV_HEADER = "seq_name\tcluster\tcluster_size\tkind\tanchor\tsimilarity\tdegree\n"
@@ -728,8 +640,7 @@ def write_density(npz_path, tsv_path, names_key, names, res, strand="forward"):
     """Both density files of a stage: the arrays of a DensityResult with the contig names, and one line per contig."""
     np.savez_compressed(npz_path, **{names_key: names, "threshold": np.float64(res.threshold), "min_points": np.int64(res.min_points),
                                      "metric": np.array(res.metric), "label": res.label, "degree": res.degree, "size": res.size,
-                                     "anchor": res.anchor, "sim": res.sim, "kind": res.kind,
-                                     **({"strand": np.array(strand)} if strand != "forward" else {})})
+                                     "anchor": res.anchor, "sim": res.sim, "kind": res.kind, **_strand_entry(strand)})
     write_density_tsv(tsv_path, names, res)
 
 
@@ -739,38 +650,12 @@ def kmeans_requested():
     (<prefix>_nn_kmeans.npz and .tsv); unset or empty: nothing changes (None).  GENOMAD_AMD_KMEANS_MAX_ITER=<integer in [0, 1000]>
     (default 50) bounds the updates; it is an error without GENOMAD_AMD_KMEANS.  Any other value of either is an error.  Returns
     (k, max_iter), or None."""
-    v = os.environ.get("GENOMAD_AMD_KMEANS", "").strip()
-    m = os.environ.get("GENOMAD_AMD_KMEANS_MAX_ITER", "").strip()
-    if not v:
-        if m:
-            raise ValueError(f"GENOMAD_AMD_KMEANS_MAX_ITER={m!r} needs GENOMAD_AMD_KMEANS: set the number of groups or unset "
-                             "GENOMAD_AMD_KMEANS_MAX_ITER")
+    k = _env_int("GENOMAD_AMD_KMEANS", 1, sequence.KMEANS_K_MAX, "(the number of groups)")
+    if k is None:
+        _env_refines("GENOMAD_AMD_KMEANS_MAX_ITER", "GENOMAD_AMD_KMEANS", "set the number of groups or unset")
         return None
-    try:
-        k = int(v)
-    except ValueError:
-        k = 0
-    if not 1 <= k <= sequence.KMEANS_K_MAX:
-        raise ValueError(f"GENOMAD_AMD_KMEANS={v!r}: expected an integer in [1, {sequence.KMEANS_K_MAX}] (the number of groups)")
-    try:
-        it = int(m) if m else sequence.KMEANS_MAX_ITER_DEFAULT
-    except ValueError:
-        it = -1
-    if not 0 <= it <= sequence.KMEANS_MAX_ITER_MAX:
-        raise ValueError(f"GENOMAD_AMD_KMEANS_MAX_ITER={m!r}: expected an integer in [0, {sequence.KMEANS_MAX_ITER_MAX}] (the centroid "
-                         "updates at the most)")
-    return k, it
-
-
-def _kmeans_of_file(path):
-    """The (k, max_iter) a stage's k-means file was computed with; no file = None (no k-means was asked for)."""
-    if not Path(path).exists():
-        return None
-    try:
-        z = np.load(path)
-        return int(z["k"]), int(z["max_iter"])
-    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
-        return -1, -1
+    return k, _env_int("GENOMAD_AMD_KMEANS_MAX_ITER", 0, sequence.KMEANS_MAX_ITER_MAX, "(the centroid updates at the most)",
+                       sequence.KMEANS_MAX_ITER_DEFAULT)
 
 
 KMEANS_TSV_HEADER = "seq_name\tcluster\tcluster_size\tsimilarity\n"
@@ -793,8 +678,7 @@ def write_kmeans(npz_path, tsv_path, names_key, names, res, max_iter, strand="fo
     np.savez_compressed(npz_path, **{names_key: names, "k": np.int64(res.k), "max_iter": np.int64(max_iter), "metric": np.array("cosine"),
                                      "label": res.label, "sim": res.sim, "centroids": res.centroids, "size": res.size,
                                      "iterations": np.int64(res.iterations), "converged": np.bool_(res.converged),
-                                     "init_rows": res.init_rows, "objective": np.float64(res.objective),
-                                     **({"strand": np.array(strand)} if strand != "forward" else {})})
+                                     "init_rows": res.init_rows, "objective": np.float64(res.objective), **_strand_entry(strand)})
     write_kmeans_tsv(tsv_path, names, res)
 
 
@@ -803,26 +687,7 @@ def pca_requested():
     embeddings of GENOMAD_AMD_EMBEDDINGS=1 - of their unit vectors, the geometry every search works in - and every contig's scores
     on them (<prefix>_nn_pca.npz and .tsv); unset or empty: nothing changes (None).  Any other value is an error.  Returns the
     number of components, or None."""
-    v = os.environ.get("GENOMAD_AMD_PCA", "").strip()
-    if not v:
-        return None
-    try:
-        c = int(v)
-    except ValueError:
-        c = 0
-    if not 1 <= c <= sequence.PCA_COMPONENTS_MAX:
-        raise ValueError(f"GENOMAD_AMD_PCA={v!r}: expected an integer in [1, {sequence.PCA_COMPONENTS_MAX}] (the number of components)")
-    return c
-
-
-def _pca_of_file(path):
-    """The number of components a stage's PCA file was computed with; no file = None (no PCA was asked for)."""
-    if not Path(path).exists():
-        return None
-    try:
-        return int(np.load(path)["n_components"])
-    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
-        return -1
+    return _env_int("GENOMAD_AMD_PCA", 1, sequence.PCA_COMPONENTS_MAX, "(the number of components)")
 
 
 def write_pca_tsv(path, names, res):
@@ -843,7 +708,7 @@ def write_pca(npz_path, tsv_path, names_key, names, res, strand="forward"):
                                      "mean": res.mean, "components": res.components, "explained_variance": res.explained_variance,
                                      "explained_variance_ratio": res.explained_variance_ratio,
                                      "total_variance": np.float64(res.total_variance), "n_valid": np.int64(res.n_valid),
-                                     "projection": res.projection, **({"strand": np.array(strand)} if strand != "forward" else {})})
+                                     "projection": res.projection, **_strand_entry(strand)})
     write_pca_tsv(tsv_path, names, res)
 
 
@@ -852,17 +717,7 @@ def representatives_requested():
     the per-contig encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1 - contigs walked by their number of kept windows, the larger first,
     every contig within the threshold of its representative (<prefix>_nn_representatives.npz and .tsv); unset or empty: nothing changes
     (None).  Any other value is an error.  Returns the threshold as it is compared: the float32 it rounds to."""
-    v = os.environ.get("GENOMAD_AMD_REPRESENTATIVES", "").strip()
-    if not v:
-        return None
-    try:
-        t = float(v)
-    except ValueError:
-        t = float("nan")
-    if not -1.0 <= t <= 1.0:                             # a NaN fails both comparisons
-        raise ValueError(f"GENOMAD_AMD_REPRESENTATIVES={v!r}: expected a float in [-1, 1] (the cosine similarity at which a contig joins "
-                         "a representative)")
-    return float(np.float32(t))
+    return _env_similarity("GENOMAD_AMD_REPRESENTATIVES", "(the cosine similarity at which a contig joins a representative)")
 
 
 REPRESENTATIVE_TSV_HEADER = "seq_name\trepresentative\tsimilarity\tcluster_size\tis_representative\n"
@@ -880,6 +735,15 @@ def write_representatives_tsv(path, names, res):
                 fout.write(f"{name}\t{name}\tNA\t{res.size[i]}\tTrue\n")
             else:
                 fout.write(f"{name}\t{names[res.rep[i]]}\t{res.sim[i]:.6f}\t{res.size[i]}\tFalse\n")
+
+
+def write_representatives(npz_path, tsv_path, names_key, names, res, threshold, weight, strand="forward"):
+    """Both representative files of a stage: the arrays of a RepresentativeResult with the contig names and the ``weight`` the contigs
+    were walked by, and one line per contig."""
+    np.savez_compressed(npz_path, **{names_key: names, "threshold": np.float64(threshold), "metric": np.array(NEIGHBOUR_METRIC),
+                                     "weight": weight, "rep": res.rep, "sim": res.sim, "size": res.size, "rank": res.rank,
+                                     "rounds": np.int64(res.rounds), **_strand_entry(strand)})
+    write_representatives_tsv(tsv_path, names, res)
 
 
 def linkage_requested() -> bool:
@@ -909,8 +773,7 @@ def write_linkage_tsv(path, names, res):
 def write_linkage(npz_path, tsv_path, names_key, names, res, strand="forward"):
     """Both linkage files of a stage: the arrays of a LinkageResult with the contig names, and the table of its merges."""
     np.savez_compressed(npz_path, **{names_key: names, "metric": np.array(res.metric), "a": res.a, "b": res.b, "sim": res.sim,
-                                     "valid": res.valid, "rounds": np.int64(res.rounds),
-                                     **({"strand": np.array(strand)} if strand != "forward" else {})})
+                                     "valid": res.valid, "rounds": np.int64(res.rounds), **_strand_entry(strand)})
     write_linkage_tsv(tsv_path, names, res)
 
 
@@ -919,16 +782,7 @@ def graph_requested():
     embeddings of GENOMAD_AMD_EMBEDDINGS=1 have at least that cosine similarity, the edges GENOMAD_AMD_CLUSTERS joins at the same value
     (<prefix>_nn_graph.npz and .tsv); unset or empty: nothing changes (None).  Any other value is an error.  Returns the threshold as
     it is compared: the float32 it rounds to."""
-    v = os.environ.get("GENOMAD_AMD_GRAPH", "").strip()
-    if not v:
-        return None
-    try:
-        t = float(v)
-    except ValueError:
-        t = float("nan")
-    if not -1.0 <= t <= 1.0:                             # a NaN fails both comparisons
-        raise ValueError(f"GENOMAD_AMD_GRAPH={v!r}: expected a float in [-1, 1] (the cosine similarity at which two contigs share an edge)")
-    return float(np.float32(t))
+    return _env_similarity("GENOMAD_AMD_GRAPH", "(the cosine similarity at which two contigs share an edge)")
 
 
 GRAPH_TSV_HEADER = "contig_a\tcontig_b\tsimilarity\n"
@@ -946,8 +800,7 @@ def write_graph_tsv(path, names, res):
 def write_graph(npz_path, tsv_path, names_key, names, res, strand="forward"):
     """Both graph files of a stage: the arrays of a GraphResult with the contig names, and its edge list."""
     np.savez_compressed(npz_path, **{names_key: names, "threshold": np.float64(res.threshold), "metric": np.array(res.metric),
-                                     "indptr": res.indptr, "col": res.col, "sim": res.sim,
-                                     **({"strand": np.array(strand)} if strand != "forward" else {})})
+                                     "indptr": res.indptr, "col": res.col, "sim": res.sim, **_strand_entry(strand)})
     write_graph_tsv(tsv_path, names, res)
 
 
@@ -956,17 +809,7 @@ def match_requested():
     GENOMAD_AMD_MATCH_BASE whose encoder embedding has at least that cosine similarity to the contig's per-contig embedding of
     GENOMAD_AMD_EMBEDDINGS=1 (<prefix>_nn_matches.npz and .tsv); unset or empty: nothing changes (None).  Any other value is an error.
     Returns the threshold as it is compared: the float32 it rounds to."""
-    v = os.environ.get("GENOMAD_AMD_MATCH", "").strip()
-    if not v:
-        return None
-    try:
-        t = float(v)
-    except ValueError:
-        t = float("nan")
-    if not -1.0 <= t <= 1.0:                             # a NaN fails both comparisons
-        raise ValueError(f"GENOMAD_AMD_MATCH={v!r}: expected a float in [-1, 1] (the cosine similarity at which a contig matches a "
-                         "reference row)")
-    return float(np.float32(t))
+    return _env_similarity("GENOMAD_AMD_MATCH", "(the cosine similarity at which a contig matches a reference row)")
 
 
 def match_base_requested():
@@ -1019,16 +862,8 @@ def write_matches(npz_path, tsv_path, names_key, names, base_names, res, strand=
     """Both match files of a stage: the arrays of a MatchResult with the names of both sides, and its list of matches."""
     np.savez_compressed(npz_path, **{names_key: names, "base_names": base_names, "threshold": np.float64(res.threshold),
                                      "metric": np.array(res.metric), "indptr": res.indptr, "col": res.col, "sim": res.sim,
-                                     **({"strand": np.array(strand)} if strand != "forward" else {})})
+                                     **_strand_entry(strand)})
     write_matches_tsv(tsv_path, names, base_names, res)
-
-
-def _match_base_of_file(path):
-    """The reference names a stage's match file was computed against; no file, or an unreadable one = None."""
-    try:
-        return np.load(path)["base_names"]
-    except Exception:  # noqa: BLE001
-        return None
 
 
 def vote_requested():
@@ -1037,17 +872,7 @@ def vote_requested():
     GENOMAD_AMD_EMBEDDINGS=1, their similarity sum and the most similar one, and the label they vote for (<prefix>_nn_votes.npz and
     .tsv); unset or empty: nothing changes (None).  Any other value is an error.  Returns the threshold as it is compared: the
     float32 it rounds to."""
-    v = os.environ.get("GENOMAD_AMD_VOTE", "").strip()
-    if not v:
-        return None
-    try:
-        t = float(v)
-    except ValueError:
-        t = float("nan")
-    if not -1.0 <= t <= 1.0:                             # a NaN fails both comparisons
-        raise ValueError(f"GENOMAD_AMD_VOTE={v!r}: expected a float in [-1, 1] (the cosine similarity at which a labelled reference row "
-                         "votes on a contig)")
-    return float(np.float32(t))
+    return _env_similarity("GENOMAD_AMD_VOTE", "(the cosine similarity at which a labelled reference row votes on a contig)")
 
 
 def vote_base_requested():
@@ -1060,16 +885,7 @@ def vote_base_requested():
 def vote_min_votes_requested() -> int:
     """GENOMAD_AMD_VOTE_MIN_VOTES=<integer >= 1>: the voters a contig needs within the threshold to get a label; unset or empty: 1.
     Any other value is an error."""
-    v = os.environ.get("GENOMAD_AMD_VOTE_MIN_VOTES", "").strip()
-    if not v:
-        return 1
-    try:
-        m = int(v)
-    except ValueError:
-        m = 0
-    if m < 1:
-        raise ValueError(f"GENOMAD_AMD_VOTE_MIN_VOTES={v!r}: expected an integer >= 1 (the voters a contig needs to get a label)")
-    return m
+    return _env_int("GENOMAD_AMD_VOTE_MIN_VOTES", 1, None, "(the voters a contig needs to get a label)", 1)
 
 
 def load_vote_base(path, strand="forward"):
@@ -1138,35 +954,8 @@ def write_votes(npz_path, tsv_path, names_key, names, classes, base_names, base_
                                      "classes": classes, "threshold": np.float64(res.threshold),
                                      "min_votes": np.int64(min_votes), "count": res.count, "weight": res.weight, "nearest": res.nearest,
                                      "nearest_sim": res.nearest_sim, "label": label, "confidence": confidence, "margin": margin,
-                                     **({"strand": np.array(strand)} if strand != "forward" else {})})
+                                     **_strand_entry(strand)})
     write_votes_tsv(tsv_path, names, classes, base_names, res, min_votes)
-
-
-def _vote_of_file(path):
-    """(threshold, min_votes) a stage's vote file was computed with; no file = None (no votes were asked for)."""
-    if not Path(path).exists():
-        return None
-    try:
-        z = np.load(path)
-        return float(z["threshold"]), int(z["min_votes"])
-    except Exception:  # noqa: BLE001  (unreadable: no request matches, the stage runs again)
-        return float("nan"), 0
-
-
-def _vote_base_of_file(path):
-    """(the reference names, the classes, the rows' labels) a stage's vote file was computed against; no file, or an unreadable one =
-    None."""
-    try:
-        z = np.load(path)
-        return z["base_names"], z["classes"], z["base_label"]
-    except Exception:  # noqa: BLE001
-        return None
-
-
-def _same_vote_base(of_file, vote_base) -> bool:
-    """``vote_base``: what :func:`load_vote_base` returned"""
-    return (of_file is not None and np.array_equal(of_file[0], vote_base[0]) and np.array_equal(of_file[1], vote_base[2])
-            and np.array_equal(of_file[2], vote_base[3]))
 
 
 REGION_TSV_HEADER = ("seq_name\tstart\tend\tclass\tn_bins\tevidence_bins\t"
@@ -1343,6 +1132,123 @@ def _encode(fasta_path, enc_dir: Path, window_id_path: Path, single_window: bool
     return names, ids, windows
 
 
+# ---- the analyses of the gathered per-contig embeddings ------------------------------------------------------------------------------
+# Ten analyses follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
+#   name      the stem of its files, <prefix>_nn_<name>.npz and - where ``tsv`` - .tsv
+#   switch    the environment variable that requests it; ``request()`` reads it (and its companions): the request, or None
+#   needs     the middle clause of the message that refuses the switch without GENOMAD_AMD_EMBEDDINGS=1
+#   keys      the npz entries that spell the request, with their casts (:func:`_request_of_file`)
+#   title     the head of its log line, before " (<summary>) written to ..."; {what} is "sequence" or "provirus", {base} the reference file
+#   run(eng, embeddings, request, ctx) -> the result; ``ctx`` holds what only some need: what, names, ids (the gathered window ids),
+#             request, base (what the reference's loader returned) and base_path
+#   write(npz, tsv, names_key, names, res, strand, ctx) and summary(res, request, what, ctx): its files and its log line's middle
+#   errors    the exceptions of ``run`` that end the run with status 1 and one line, "<switch>=<request>: <error>. <advice>"
+#   base      for an analysis against a reference (AnalysisBase): ``request()`` its path, ``load(path, strand)``, the ``hint`` of the
+#             message about a file that cannot be loaded, and ``same(npz, base)``: the file was computed against this very reference
+Analysis = namedtuple("Analysis", "name switch request needs keys title run write summary tsv errors advice base",
+                      defaults=(True, (), "", None))
+AnalysisBase = namedtuple("AnalysisBase", "request load hint same")
+_SIMILARITY = f"{NEIGHBOUR_METRIC} similarity of the encoder embeddings"
+
+
+def _kept_windows(ctx):
+    """the representatives' weight: every contig's number of kept windows, counted in the gathered window ids (no further collective)"""
+    return np.bincount(np.asarray(ctx.ids, dtype=np.int64), minlength=len(ctx.names)).astype(np.int64)
+
+
+def _vote_request():
+    t, m = vote_requested(), vote_min_votes_requested()          # a bad GENOMAD_AMD_VOTE_MIN_VOTES is an error with or without the threshold
+    return None if t is None else (t, m)
+
+
+def _same_vote_base(z, base) -> bool:
+    """the reference's names, classes and labels are those the vote file was computed against"""
+    return all(np.array_equal(z[k], base[i]) for k, i in (("base_names", 0), ("classes", 2), ("base_label", 3)))
+
+
+ANALYSES = (        # in the order they run, which is the order of the log lines and of what is on disk when one of them ends the run
+    Analysis("neighbours", "GENOMAD_AMD_NEIGHBOURS", neighbours_requested,
+             "neighbours are searched among the per-contig encoder embeddings", (("k", int),), "Nearest neighbours of the {what}s",
+             lambda eng, emb, k, ctx: eng.neighbours(emb, None, k, NEIGHBOUR_METRIC),          # the self-search: a contig is not its own neighbour
+             lambda npz, tsv, key, names, res, strand, ctx: write_neighbours(npz, key, names, res, ctx.request, strand),
+             lambda res, k, what, ctx: f"{k} per {what}, {_SIMILARITY}", tsv=False),
+    Analysis("clusters", "GENOMAD_AMD_CLUSTERS", clusters_requested,
+             "clusters are formed among the per-contig encoder embeddings", (("threshold", float),), "Clusters of the {what}s",
+             lambda eng, emb, t, ctx: eng.cluster(emb, t, NEIGHBOUR_METRIC),
+             lambda npz, tsv, key, names, res, strand, ctx: write_clusters(npz, tsv, key, names, res, ctx.request, strand),
+             lambda res, t, what, ctx: f"{_SIMILARITY} >= {t:g}, single linkage: {res.n_clusters} clusters, {res.n_edges} edges"),
+    Analysis("representatives", "GENOMAD_AMD_REPRESENTATIVES", representatives_requested,
+             "representatives are chosen among the per-contig encoder embeddings", (("threshold", float),), "Representatives of the {what}s",
+             lambda eng, emb, t, ctx: eng.representatives(emb, t, _kept_windows(ctx), NEIGHBOUR_METRIC),      # ties in FASTA order
+             lambda npz, tsv, key, names, res, strand, ctx: write_representatives(npz, tsv, key, names, res, ctx.request, _kept_windows(ctx),
+                                                                                  strand),
+             lambda res, t, what, ctx: f"{_SIMILARITY} >= {t:g}, greedy by kept windows: {res.n_clusters} clusters in {res.rounds} rounds"),
+    Analysis("linkage", "GENOMAD_AMD_LINKAGE", lambda: () if linkage_requested() else None,      # its request is its files' existence
+             "the tree is built among the per-contig encoder embeddings", (), "Single-linkage tree of the {what}s",
+             lambda eng, emb, _, ctx: eng.linkage(emb, NEIGHBOUR_METRIC),
+             lambda npz, tsv, key, names, res, strand, ctx: write_linkage(npz, tsv, key, names, res, strand),
+             lambda res, _, what, ctx: f"{_SIMILARITY}: {res.n_edges} merges among {res.n_valid} {what}s in {res.rounds} rounds"),
+    Analysis("graph", "GENOMAD_AMD_GRAPH", graph_requested,
+             "the graph's edges are found among the per-contig encoder embeddings", (("threshold", float),), "Similarity graph of the {what}s",
+             lambda eng, emb, t, ctx: eng.graph(emb, t, NEIGHBOUR_METRIC),
+             lambda npz, tsv, key, names, res, strand, ctx: write_graph(npz, tsv, key, names, res, strand),
+             lambda res, t, what, ctx: f"{_SIMILARITY} >= {t:g}: {res.n_edges} edges among {int(res.valid.sum())} {what}s",
+             errors=ValueError, advice="Raise GENOMAD_AMD_GRAPH or unset it."),      # more edges than NNEngine.graph's cap: none was allocated
+    Analysis("density", "GENOMAD_AMD_DENSITY", density_requested,
+             "density clusters are formed among the per-contig encoder embeddings", (("threshold", float), ("min_points", int)),
+             "Density clusters of the {what}s",
+             lambda eng, emb, r, ctx: eng.density(emb, r[0], r[1], NEIGHBOUR_METRIC),
+             lambda npz, tsv, key, names, res, strand, ctx: write_density(npz, tsv, key, names, res, strand),
+             lambda res, r, what, ctx: (f"{_SIMILARITY} >= {r[0]:g}, at least {r[1]} {what}s for a core: {res.n_clusters} clusters, "
+                                        f"{res.n_core} core, {res.n_border} border, {res.n_noise} noise")),
+    Analysis("kmeans", "GENOMAD_AMD_KMEANS", kmeans_requested,
+             "the groups are formed among the per-contig encoder embeddings", (("k", int), ("max_iter", int)), "Spherical k-means of the {what}s",
+             lambda eng, emb, r, ctx: eng.kmeans(emb, r[0], None, r[1]),                       # farthest-first init
+             lambda npz, tsv, key, names, res, strand, ctx: write_kmeans(npz, tsv, key, names, res, ctx.request[1], strand),
+             lambda res, r, what, ctx: (f"{_SIMILARITY}: {r[0]} groups, {res.iterations} updates, "
+                                        f"{'converged' if res.converged else 'not converged'}, objective {res.objective:.3f}"),
+             errors=(ValueError, GnnError), advice="Lower GENOMAD_AMD_KMEANS or unset it."),   # more groups than contigs with a valid embedding
+    Analysis("pca", "GENOMAD_AMD_PCA", pca_requested,
+             "the components are those of the per-contig encoder embeddings", (("n_components", int),), "Principal components of the {what}s",
+             lambda eng, emb, c, ctx: eng.pca(emb, c),
+             lambda npz, tsv, key, names, res, strand, ctx: write_pca(npz, tsv, key, names, res, strand),
+             lambda res, c, what, ctx: (f"unit encoder embeddings: {c} components of {res.n_valid} {what}s, "
+                                        f"{float(np.nansum(res.explained_variance_ratio)):.3f} of the variance"),
+             errors=(ValueError, GnnError), advice="Unset GENOMAD_AMD_PCA."),                  # fewer than two contigs with a valid embedding
+    Analysis("matches", "GENOMAD_AMD_MATCH", match_requested,
+             "the per-contig encoder embeddings are matched against the reference's at that threshold", (("threshold", float),),
+             "Matches of the {what}s against {base}",
+             lambda eng, emb, t, ctx: eng.match(emb, ctx.base[1], t, NEIGHBOUR_METRIC),        # query: the contigs; base: the reference
+             lambda npz, tsv, key, names, res, strand, ctx: write_matches(npz, tsv, key, names, ctx.base[0], res, strand),
+             lambda res, t, what, ctx: (f"{_SIMILARITY} >= {t:g}: {res.n_edges} matches of {int((res.hits() > 0).sum())} {what}s among "
+                                        f"{res.n_base} reference rows"),
+             errors=ValueError, advice="Raise GENOMAD_AMD_MATCH or unset it.",                 # more matches than NNEngine.match's cap
+             base=AnalysisBase(match_base_requested, load_match_base, "", lambda z, base: np.array_equal(z["base_names"], base[0]))),
+    Analysis("votes", "GENOMAD_AMD_VOTE", _vote_request,
+             "the labelled reference's embeddings vote on the per-contig encoder embeddings at that threshold",
+             (("threshold", float), ("min_votes", int)), "Votes of {base} on the {what}s",
+             lambda eng, emb, r, ctx: eng.vote(emb, ctx.base[1], ctx.base[3], len(ctx.base[2]), r[0]),
+             lambda npz, tsv, key, names, res, strand, ctx: write_votes(npz, tsv, key, names, ctx.base[2], ctx.base[0], ctx.base[3], res,
+                                                                        ctx.request[1], strand),
+             lambda res, r, what, ctx: (f"{_SIMILARITY} >= {r[0]:g}, {len(ctx.base[2])} classes: "
+                                        f"{int((res.predict(VOTE_RULE, r[1])[0] >= 0).sum())} of {len(ctx.names)} {what}s got a label"),
+             base=AnalysisBase(vote_base_requested, load_vote_base, ", with 'labels' added", _same_vote_base)),
+)
+
+
+def _resumes(a, npz, tsv, request, strand, base) -> bool:
+    """Analysis ``a``'s files of a stage are what a run with ``request`` would write: the npz spells the request (no file: none), the tsv
+    is there iff there is a request, and a requested file was computed under this strand mode and against this reference."""
+    if _request_of_file(npz, a.keys) != request or (tsv is not None and tsv.exists() != (request is not None)):
+        return False
+    if request is None:
+        return True
+    try:
+        return _npz_strand(npz) == strand and (a.base is None or bool(a.base.same(np.load(npz), base)))
+    except Exception:  # noqa: BLE001  (the entries of the reference are not there: the stage runs again)
+        return False
+
+
 def main(input_path, output_path, single_window, batch_size, restart, threads, verbose, cleanup,
          _backend=None, _comm=None):
     """``_backend`` (tests only) replaces the GPU engine with an object offering score() and
@@ -1359,19 +1265,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     attribution_bin = attribution_bin_requested()
     region_penalty = region_penalty_requested()
     region_embeddings = region_embeddings_requested()
-    neighbours_k = neighbours_requested()
-    clusters_threshold = clusters_requested()
-    density_request = density_requested()
-    kmeans_request = kmeans_requested()
-    pca_request = pca_requested()
-    representatives_threshold = representatives_requested()
-    linkage = linkage_requested()
-    graph_threshold = graph_requested()
-    match_threshold = match_requested()
-    match_base_path = match_base_requested()
-    vote_threshold = vote_requested()
-    vote_base_path = vote_base_requested()
-    vote_min_votes = vote_min_votes_requested()
+    requests = {a.name: a.request() for a in ANALYSES}
+    base_paths = {a.name: a.base.request() for a in ANALYSES if a.base is not None}
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -1406,46 +1301,14 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         console.error("GENOMAD_AMD_REGION_EMBEDDINGS=1 needs GENOMAD_AMD_REGION_PENALTY: the embeddings are those of the regions called "
                       "along the score tracks. Set GENOMAD_AMD_REGION_PENALTY or unset GENOMAD_AMD_REGION_EMBEDDINGS.")
         sys.exit(1)
-    if neighbours_k is not None and not embeddings:
-        console.error("GENOMAD_AMD_NEIGHBOURS needs GENOMAD_AMD_EMBEDDINGS=1: neighbours are searched among the per-contig encoder "
-                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_NEIGHBOURS.")
-        sys.exit(1)
-    if clusters_threshold is not None and not embeddings:
-        console.error("GENOMAD_AMD_CLUSTERS needs GENOMAD_AMD_EMBEDDINGS=1: clusters are formed among the per-contig encoder "
-                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_CLUSTERS.")
-        sys.exit(1)
-    if density_request is not None and not embeddings:
-        console.error("GENOMAD_AMD_DENSITY needs GENOMAD_AMD_EMBEDDINGS=1: density clusters are formed among the per-contig encoder "
-                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_DENSITY.")
-        sys.exit(1)
-    if kmeans_request is not None and not embeddings:
-        console.error("GENOMAD_AMD_KMEANS needs GENOMAD_AMD_EMBEDDINGS=1: the groups are formed among the per-contig encoder "
-                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_KMEANS.")
-        sys.exit(1)
-    if pca_request is not None and not embeddings:
-        console.error("GENOMAD_AMD_PCA needs GENOMAD_AMD_EMBEDDINGS=1: the components are those of the per-contig encoder "
-                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_PCA.")
-        sys.exit(1)
-    if representatives_threshold is not None and not embeddings:
-        console.error("GENOMAD_AMD_REPRESENTATIVES needs GENOMAD_AMD_EMBEDDINGS=1: representatives are chosen among the per-contig encoder "
-                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_REPRESENTATIVES.")
-        sys.exit(1)
-    if linkage and not embeddings:
-        console.error("GENOMAD_AMD_LINKAGE needs GENOMAD_AMD_EMBEDDINGS=1: the tree is built among the per-contig encoder "
-                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_LINKAGE.")
-        sys.exit(1)
-    if graph_threshold is not None and not embeddings:
-        console.error("GENOMAD_AMD_GRAPH needs GENOMAD_AMD_EMBEDDINGS=1: the graph's edges are found among the per-contig encoder "
-                      "embeddings. Set GENOMAD_AMD_EMBEDDINGS=1 or unset GENOMAD_AMD_GRAPH.")
-        sys.exit(1)
-    if (match_threshold is None) != (match_base_path is None) or (match_threshold is not None and not embeddings):
-        console.error("GENOMAD_AMD_MATCH and GENOMAD_AMD_MATCH_BASE need each other and GENOMAD_AMD_EMBEDDINGS=1: the per-contig encoder "
-                      "embeddings are matched against the reference's at that threshold. Set all three or unset both.")
-        sys.exit(1)
-    if (vote_threshold is None) != (vote_base_path is None) or (vote_threshold is not None and not embeddings):
-        console.error("GENOMAD_AMD_VOTE and GENOMAD_AMD_VOTE_BASE need each other and GENOMAD_AMD_EMBEDDINGS=1: the labelled reference's "
-                      "embeddings vote on the per-contig encoder embeddings at that threshold. Set all three or unset both.")
-        sys.exit(1)
+    for a in ANALYSES:
+        requested = requests[a.name] is not None
+        if a.base is None and requested and not embeddings:
+            console.error(f"{a.switch} needs GENOMAD_AMD_EMBEDDINGS=1: {a.needs}. Set GENOMAD_AMD_EMBEDDINGS=1 or unset {a.switch}.")
+            sys.exit(1)
+        if a.base is not None and (requested != (base_paths[a.name] is not None) or (requested and not embeddings)):
+            console.error(f"{a.switch} and {a.switch}_BASE need each other and GENOMAD_AMD_EMBEDDINGS=1: {a.needs}. Set all three or unset both.")
+            sys.exit(1)
 
     if strand != "forward" and not device_front_end:
         console.error("GENOMAD_AMD_STRAND needs the device front end: the host front end (GENOMAD_AMD_FRONT_END=host) does "
@@ -1474,23 +1337,15 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                       "Unset GENOMAD_AMD_STRAND or GENOMAD_AMD_ATTRIBUTION_BIN.")
         sys.exit(1)
 
-    match_base = None                # (names, embeddings) of the reference, read before any classification starts
-    if match_threshold is not None:
-        try:
-            match_base = load_match_base(match_base_path, strand)
-        except ValueError as e:
-            console.error(f"{e}. Name a file that GENOMAD_AMD_EMBEDDINGS=1 wrote under the same GENOMAD_AMD_STRAND, or unset "
-                          "GENOMAD_AMD_MATCH and GENOMAD_AMD_MATCH_BASE.")
-            sys.exit(1)
-    vote_base = None                 # (names, embeddings, classes, label) of the labelled reference, read before any classification starts
-    if vote_threshold is not None:
-        try:
-            vote_base = load_vote_base(vote_base_path, strand)
-        except ValueError as e:
-            console.error(f"{e}. Name a file that GENOMAD_AMD_EMBEDDINGS=1 wrote under the same GENOMAD_AMD_STRAND, with 'labels' added, "
-                          "or unset GENOMAD_AMD_VOTE and GENOMAD_AMD_VOTE_BASE.")
-            sys.exit(1)
-    vote_request = None if vote_threshold is None else (vote_threshold, vote_min_votes)
+    bases = {}                       # what every requested reference's loader returned, read before any classification starts
+    for a in ANALYSES:
+        if a.base is not None and requests[a.name] is not None:
+            try:
+                bases[a.name] = a.base.load(base_paths[a.name], strand)
+            except ValueError as e:
+                console.error(f"{e}. Name a file that GENOMAD_AMD_EMBEDDINGS=1 wrote under the same GENOMAD_AMD_STRAND{a.base.hint}, or unset "
+                              f"{a.switch} and {a.switch}_BASE.")
+                sys.exit(1)
 
     def everywhere(*flags):
         """Decisions read from files that rank 0 is about to rewrite are taken on rank 0 and made known to
@@ -1613,15 +1468,15 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         if rank0:
             write_tsv(tsv_path, names, predictions)                                  # :340-352 (always rewritten)
 
-    def stage_device(fasta, enc_dir, wid_path, npz_path, tsv_path, names_key, ids_key, what, strand_path, occ_path, attr_path, regions_paths,
-                     nn_path, clusters_paths, representatives_paths, linkage_paths, emb_path=None, scan_path=None, region_emb_path=None):
+    def stage_device(fasta, what, names_key, ids_key):
         """Product path: the contig front end (NNEngine.classify_contigs) does windowing, the N rule,
         tokenising, classification and the per-contig mean on the GPU, so encoding and classification
         are one step; ``<prefix>_seq_window_id.npz`` is still written.  With several ranks the CONTIGS are
         sharded: every rank reads and packs only its own record-aligned byte range of the file (for
         compressed inputs: every world-th record-aligned chunk of the decompressed stream), classifies it
         on its GPU, and rank 0 collects the per-contig scores with one gather and writes the files —
-        results are bit-identical for any number of ranks.  ``emb_path`` (GENOMAD_AMD_EMBEDDINGS=1): the per-contig encoder
+        results are bit-identical for any number of ranks.  Every path is that of stage ``what`` in ``outputs``.
+        ``emb_path`` (GENOMAD_AMD_EMBEDDINGS=1): the per-contig encoder
         embeddings are computed in the same pass and written there; a run that finds the scores but not that file classifies again.
         ``scan_path`` (GENOMAD_AMD_SCAN_STRIDE): every piece is also scanned at that stride (NNEngine.scan_contigs) and the score
         tracks are written there; a run that finds the scores but no scan file of that stride runs the stage again.
@@ -1636,94 +1491,35 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         ``attr_path`` (GENOMAD_AMD_ATTRIBUTION_BIN): after its normal classification every piece also goes through
         NNEngine.attribute_contigs with bins of that many pooled positions, and the maps are written there.  The file follows the
         occlusion file's rule, with the bin in place of the block.
-        ``regions_paths`` (npz, tsv; GENOMAD_AMD_REGION_PENALTY): rank 0 calls regions (NNEngine.call_regions) on the gathered track -
-        regions are per contig, so the result does not depend on the number of ranks - and writes both files.  They follow the
+        ``regions_path``, ``regions_tsv_path`` (GENOMAD_AMD_REGION_PENALTY): rank 0 calls regions (NNEngine.call_regions) on the gathered
+        track - regions are per contig, so the result does not depend on the number of ranks - and writes both files.  They follow the
         occlusion file's rule, with (stride, penalty) in place of the block.
-        ``nn_path`` (GENOMAD_AMD_NEIGHBOURS, which needs the embeddings): rank 0 runs the self-search (NNEngine.neighbours) on the
-        gathered per-contig embeddings - of the strand mode the stage ran under - and writes every contig's k nearest there.  The
-        file follows the occlusion file's rule, with k in place of the block.
-        ``clusters_paths`` (npz, tsv; GENOMAD_AMD_CLUSTERS, which needs the embeddings): rank 0 clusters the same gathered embeddings
-        (NNEngine.cluster, cosine) where it runs the neighbour search, and writes both files.  They follow the neighbour file's
-        rule, with the threshold in place of k.
-        ``representatives_paths`` (npz, tsv; GENOMAD_AMD_REPRESENTATIVES, which needs the embeddings): rank 0 runs the greedy clustering
-        (NNEngine.representatives, cosine) on the same gathered embeddings, the contig's number of kept windows (the count of its
-        entries in the gathered window ids: no further collective) as its weight, ties in FASTA order.  The files follow the
-        clusters files' rule.
-        ``linkage_paths`` (npz, tsv; GENOMAD_AMD_LINKAGE=1, which needs the embeddings): rank 0 builds the single-linkage tree
-        (NNEngine.linkage, cosine) of the same gathered embeddings and writes both files.  They are there iff they were asked for,
-        in the strand mode asked for; otherwise the stage runs again.
-        ``graph_files[what]`` (npz, tsv; GENOMAD_AMD_GRAPH, which needs the embeddings): rank 0 lists the edges (NNEngine.graph, cosine)
-        of the same gathered embeddings and writes both files.  They follow the clusters files' rule.
-        ``density_files[what]`` (npz, tsv; GENOMAD_AMD_DENSITY with the optional GENOMAD_AMD_DENSITY_MIN_POINTS, which need the
-        embeddings): rank 0 forms the density clusters (NNEngine.density, cosine) of the same gathered embeddings and writes both
-        files.  They follow the clusters files' rule, with (threshold, min_points) in place of the threshold.
-        ``kmeans_files[what]`` (npz, tsv; GENOMAD_AMD_KMEANS with the optional GENOMAD_AMD_KMEANS_MAX_ITER, which need the embeddings):
-        rank 0 runs the spherical k-means (NNEngine.kmeans, farthest-first init) of the same gathered embeddings and writes both
-        files.  They follow the clusters files' rule, with (k, max_iter) in place of the threshold.
-        ``pca_files[what]`` (npz, tsv; GENOMAD_AMD_PCA, which needs the embeddings): rank 0 computes the principal components
-        (NNEngine.pca) of the same gathered embeddings and writes both files.  They follow the clusters files' rule, with the number
-        of components in place of the threshold.
-        ``match_files[what]`` (npz, tsv; GENOMAD_AMD_MATCH with GENOMAD_AMD_MATCH_BASE, which need the embeddings): rank 0 matches the
-        same gathered embeddings (query) against the reference's (base; NNEngine.match, cosine) and writes both files.  They follow
-        the clusters files' rule, and the reference's names must be those the file was computed against.
-        ``vote_files[what]`` (npz, tsv; GENOMAD_AMD_VOTE with GENOMAD_AMD_VOTE_BASE and the optional GENOMAD_AMD_VOTE_MIN_VOTES, which
-        need the embeddings): rank 0 lets the labelled reference's rows (base) vote on the same gathered embeddings (query;
-        NNEngine.vote, cosine) and writes both files.  They follow the match files' rule, with (threshold, min_votes) in place of
-        the threshold and the reference's names, classes and labels in place of its names.
         ``region_emb_path`` (GENOMAD_AMD_REGION_EMBEDDINGS=1, which needs the regions): right after a piece's scan, while its
         sequence is in memory, the piece's own track is segmented (regions are per contig and exact integers: they are the ones
         rank 0 calls on the gathered track, which rank 0 checks) and NNEngine.embed_intervals folds the scan windows' encoder
         embeddings into the regions, in the run's arithmetic and strand mode.  The file follows the occlusion file's rule, with
-        (stride, penalty, strand) in place of the block."""
+        (stride, penalty, strand) in place of the block.
+        The ANALYSES (each needs the embeddings): rank 0 runs every requested one, in the table's order, on the gathered per-contig
+        embeddings - of the strand mode the stage ran under - and writes its npz and its tsv.  The files follow the occlusion file's
+        rule (:func:`_resumes`): the npz spells the request it was computed with (absent: none), the tsv is there iff the npz is, a
+        file of reverse / both carries the mode, and one computed against a reference holds the reference's identity; a run that asks
+        for anything else runs the stage again, and one that asks for none removes both files."""
+        enc_dir, wid_path, npz_path, tsv_path = outputs.classification_files(what)
+        emb_path = outputs.files(what, "embeddings")[0] if embeddings else None
+        scan_path = outputs.files(what, "scan")[0] if scan_stride is not None else None
+        strand_path, occ_path, attr_path = (outputs.files(what, name)[0] for name in ("strand", "occlusion", "attribution"))
+        regions_path, regions_tsv_path = outputs.files(what, "regions")
+        region_emb_file = outputs.files(what, "region_embeddings")[0]
+        region_emb_path = region_emb_file if region_embeddings else None
         region_emb_request = None if region_emb_path is None else (scan_stride, region_penalty, strand)
-        region_emb_file = region_emb_path if region_emb_path is not None else region_emb_default[what]
-        clusters_path, clusters_tsv_path = clusters_paths
-        representatives_path, representatives_tsv_path = representatives_paths
-        linkage_path, linkage_tsv_path = linkage_paths
-        graph_path, graph_tsv_path = graph_files[what]
-        density_path, density_tsv_path = density_files[what]
-        kmeans_path, kmeans_tsv_path = kmeans_files[what]
-        pca_path, pca_tsv_path = pca_files[what]
-        match_path, match_tsv_path = match_files[what]
-        vote_path, vote_tsv_path = vote_files[what]
-        regions_path, regions_tsv_path = regions_paths
         regions_request = None if region_penalty is None else (scan_stride, region_penalty)
         (have_npz,) = everywhere(rank0 and skip and npz_path.exists() and _strand_of_file(strand_path) == strand
-                                 and _occlusion_block_of_file(occ_path) == occlusion_block
-                                 and _attribution_bin_of_file(attr_path) == attribution_bin
-                                 and _regions_of_file(regions_path) == regions_request
+                                 and _request_of_file(occ_path, (("block", int),)) == occlusion_block
+                                 and _request_of_file(attr_path, (("bin", int),)) == attribution_bin
+                                 and _request_of_file(regions_path, (("stride", int), ("penalty", float))) == regions_request
                                  and (regions_request is None) == (not regions_tsv_path.exists())
-                                 and _region_embeddings_of_file(region_emb_file) == region_emb_request
-                                 and _neighbours_of_file(nn_path) == neighbours_k
-                                 and (neighbours_k is None or _npz_strand(nn_path) == strand)
-                                 and _clusters_of_file(clusters_path) == clusters_threshold
-                                 and (clusters_threshold is None) == (not clusters_tsv_path.exists())
-                                 and (clusters_threshold is None or _npz_strand(clusters_path) == strand)
-                                 and _clusters_of_file(representatives_path) == representatives_threshold
-                                 and (representatives_threshold is None) == (not representatives_tsv_path.exists())
-                                 and (representatives_threshold is None or _npz_strand(representatives_path) == strand)
-                                 and linkage == linkage_path.exists() == linkage_tsv_path.exists()
-                                 and (not linkage or _npz_strand(linkage_path) == strand)
-                                 and _clusters_of_file(graph_path) == graph_threshold
-                                 and (graph_threshold is None) == (not graph_tsv_path.exists())
-                                 and (graph_threshold is None or _npz_strand(graph_path) == strand)
-                                 and _density_of_file(density_path) == density_request
-                                 and (density_request is None) == (not density_tsv_path.exists())
-                                 and (density_request is None or _npz_strand(density_path) == strand)
-                                 and _kmeans_of_file(kmeans_path) == kmeans_request
-                                 and (kmeans_request is None) == (not kmeans_tsv_path.exists())
-                                 and (kmeans_request is None or _npz_strand(kmeans_path) == strand)
-                                 and _pca_of_file(pca_path) == pca_request
-                                 and (pca_request is None) == (not pca_tsv_path.exists())
-                                 and (pca_request is None or _npz_strand(pca_path) == strand)
-                                 and _clusters_of_file(match_path) == match_threshold
-                                 and (match_threshold is None) == (not match_tsv_path.exists())
-                                 and (match_threshold is None or (_npz_strand(match_path) == strand
-                                                                  and np.array_equal(_match_base_of_file(match_path), match_base[0])))
-                                 and _vote_of_file(vote_path) == vote_request
-                                 and (vote_request is None) == (not vote_tsv_path.exists())
-                                 and (vote_request is None or (_npz_strand(vote_path) == strand
-                                                               and _same_vote_base(_vote_base_of_file(vote_path), vote_base)))
+                                 and _request_of_file(region_emb_file, (("stride", int), ("penalty", float), ("strand", str))) == region_emb_request
+                                 and all(_resumes(a, *outputs.files(what, a.name), requests[a.name], strand, bases.get(a.name)) for a in ANALYSES)
                                  and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
                                  and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
                                                             and _npz_strand(scan_path) == strand)))   # :284-292
@@ -1844,8 +1640,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                 console.log(f"{what.capitalize()}s classified ({len(ids)} windows).")
                 np.savez_compressed(npz_path, **{names_key: names, "predictions": predictions})
                 if emb_path is not None:
-                    np.savez_compressed(emb_path, **{names_key: names, "embeddings": embeddings_all,
-                                                     **({"strand": np.array(strand)} if strand != "forward" else {})})
+                    np.savez_compressed(emb_path, **{names_key: names, "embeddings": embeddings_all, **_strand_entry(strand)})
                     console.log(f"Encoder embeddings of the {what}s written to {emb_path.name}.")
                 if scan_path is not None:
                     sc = scans_all
@@ -1903,186 +1698,41 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     console.log(f"Encoder embeddings of the {len(mine[0])} regions of the {what}s written to {region_emb_path.name}.")
                 elif region_emb_file.exists():      # likewise
                     region_emb_file.unlink()
-                if neighbours_k is not None:
-                    nn_idx, nn_sim = eng.neighbours(embeddings_all, None, neighbours_k, NEIGHBOUR_METRIC)
-                    np.savez_compressed(nn_path, **{names_key: names, "k": np.int64(neighbours_k), "metric": np.array(NEIGHBOUR_METRIC),
-                                                    "idx": nn_idx, "sim": nn_sim,
-                                                    **({"strand": np.array(strand)} if strand != "forward" else {})})
-                    console.log(f"Nearest neighbours of the {what}s ({neighbours_k} per {what}, {NEIGHBOUR_METRIC} similarity of the encoder "
-                                f"embeddings) written to {nn_path.name}.")
-                elif nn_path.exists():              # likewise
-                    nn_path.unlink()
-                if clusters_threshold is not None:
-                    res = eng.cluster(embeddings_all, clusters_threshold, NEIGHBOUR_METRIC)
-                    np.savez_compressed(clusters_path, **{names_key: names, "threshold": np.float64(clusters_threshold),
-                                                          "metric": np.array(NEIGHBOUR_METRIC), "label": res.label, "degree": res.degree,
-                                                          "size": res.size, "rep": res.rep,
-                                                          **({"strand": np.array(strand)} if strand != "forward" else {})})
-                    write_clusters_tsv(clusters_tsv_path, names, res)
-                    console.log(f"Clusters of the {what}s ({NEIGHBOUR_METRIC} similarity of the encoder embeddings >= {clusters_threshold:g}, "
-                                f"single linkage: {res.n_clusters} clusters, {res.n_edges} edges) written to {clusters_path.name} and "
-                                f"{clusters_tsv_path.name}.")
-                else:                               # likewise, both files
-                    for p in (clusters_path, clusters_tsv_path):
-                        if p.exists():
-                            p.unlink()
-                if representatives_threshold is not None:
-                    weight = np.bincount(np.asarray(ids, dtype=np.int64), minlength=len(names)).astype(np.int64)     # kept windows
-                    res = eng.representatives(embeddings_all, representatives_threshold, weight, NEIGHBOUR_METRIC)
-                    np.savez_compressed(representatives_path, **{names_key: names, "threshold": np.float64(representatives_threshold),
-                                                                 "metric": np.array(NEIGHBOUR_METRIC), "weight": weight, "rep": res.rep,
-                                                                 "sim": res.sim, "size": res.size, "rank": res.rank,
-                                                                 "rounds": np.int64(res.rounds),
-                                                                 **({"strand": np.array(strand)} if strand != "forward" else {})})
-                    write_representatives_tsv(representatives_tsv_path, names, res)
-                    console.log(f"Representatives of the {what}s ({NEIGHBOUR_METRIC} similarity of the encoder embeddings >= "
-                                f"{representatives_threshold:g}, greedy by kept windows: {res.n_clusters} clusters in {res.rounds} rounds) "
-                                f"written to {representatives_path.name} and {representatives_tsv_path.name}.")
-                else:                               # likewise, both files
-                    for p in (representatives_path, representatives_tsv_path):
-                        if p.exists():
-                            p.unlink()
-                if linkage:
-                    res = eng.linkage(embeddings_all, NEIGHBOUR_METRIC)
-                    write_linkage(linkage_path, linkage_tsv_path, names_key, names, res, strand)
-                    console.log(f"Single-linkage tree of the {what}s ({NEIGHBOUR_METRIC} similarity of the encoder embeddings: {res.n_edges} "
-                                f"merges among {res.n_valid} {what}s in {res.rounds} rounds) written to {linkage_path.name} and "
-                                f"{linkage_tsv_path.name}.")
-                else:                               # likewise, both files
-                    for p in (linkage_path, linkage_tsv_path):
-                        if p.exists():
-                            p.unlink()
-                if graph_threshold is not None:
+                for a in ANALYSES:
+                    npz, tsv = outputs.files(what, a.name)
+                    request = requests[a.name]
+                    if request is None:             # likewise, both files
+                        for p in (npz, tsv):
+                            if p is not None and p.exists():
+                                p.unlink()
+                        continue
+                    ctx = SimpleNamespace(what=what, names=names, ids=ids, request=request, base=bases.get(a.name),
+                                          base_path=base_paths.get(a.name))
                     try:
-                        res = eng.graph(embeddings_all, graph_threshold, NEIGHBOUR_METRIC)
-                    except ValueError as e:         # more edges than NNEngine.graph's cap: nothing was allocated for them
-                        console.error(f"GENOMAD_AMD_GRAPH={graph_threshold:g}: {e}. Raise GENOMAD_AMD_GRAPH or unset it.")
+                        res = a.run(eng, embeddings_all, request, ctx)
+                    except a.errors as e:           # nothing of this analysis was written; the earlier ones' files are
+                        console.error(f"{a.switch}={request[0] if isinstance(request, tuple) else request:g}: {e}. {a.advice}")
                         sys.exit(1)
-                    write_graph(graph_path, graph_tsv_path, names_key, names, res, strand)
-                    console.log(f"Similarity graph of the {what}s ({NEIGHBOUR_METRIC} similarity of the encoder embeddings >= "
-                                f"{graph_threshold:g}: {res.n_edges} edges among {int(res.valid.sum())} {what}s) written to "
-                                f"{graph_path.name} and {graph_tsv_path.name}.")
-                else:                               # likewise, both files
-                    for p in (graph_path, graph_tsv_path):
-                        if p.exists():
-                            p.unlink()
-                if density_request is not None:
-                    res = eng.density(embeddings_all, density_request[0], density_request[1], NEIGHBOUR_METRIC)
-                    write_density(density_path, density_tsv_path, names_key, names, res, strand)
-                    console.log(f"Density clusters of the {what}s ({NEIGHBOUR_METRIC} similarity of the encoder embeddings >= "
-                                f"{density_request[0]:g}, at least {density_request[1]} {what}s for a core: {res.n_clusters} clusters, "
-                                f"{res.n_core} core, {res.n_border} border, {res.n_noise} noise) written to {density_path.name} and "
-                                f"{density_tsv_path.name}.")
-                else:                               # likewise, both files
-                    for p in (density_path, density_tsv_path):
-                        if p.exists():
-                            p.unlink()
-                if kmeans_request is not None:
-                    try:
-                        res = eng.kmeans(embeddings_all, kmeans_request[0], None, kmeans_request[1])
-                    except (ValueError, GnnError) as e:         # more groups than contigs with a valid embedding
-                        console.error(f"GENOMAD_AMD_KMEANS={kmeans_request[0]}: {e}. Lower GENOMAD_AMD_KMEANS or unset it.")
-                        sys.exit(1)
-                    write_kmeans(kmeans_path, kmeans_tsv_path, names_key, names, res, kmeans_request[1], strand)
-                    console.log(f"Spherical k-means of the {what}s ({NEIGHBOUR_METRIC} similarity of the encoder embeddings: "
-                                f"{kmeans_request[0]} groups, {res.iterations} updates, {'converged' if res.converged else 'not converged'}, "
-                                f"objective {res.objective:.3f}) written to {kmeans_path.name} and {kmeans_tsv_path.name}.")
-                else:                               # likewise, both files
-                    for p in (kmeans_path, kmeans_tsv_path):
-                        if p.exists():
-                            p.unlink()
-                if pca_request is not None:
-                    try:
-                        res = eng.pca(embeddings_all, pca_request)
-                    except (ValueError, GnnError) as e:         # fewer than two contigs with a valid embedding
-                        console.error(f"GENOMAD_AMD_PCA={pca_request}: {e}. Unset GENOMAD_AMD_PCA.")
-                        sys.exit(1)
-                    write_pca(pca_path, pca_tsv_path, names_key, names, res, strand)
-                    console.log(f"Principal components of the {what}s (unit encoder embeddings: {pca_request} components of "
-                                f"{res.n_valid} {what}s, {float(np.nansum(res.explained_variance_ratio)):.3f} of the variance) written to "
-                                f"{pca_path.name} and {pca_tsv_path.name}.")
-                else:                               # likewise, both files
-                    for p in (pca_path, pca_tsv_path):
-                        if p.exists():
-                            p.unlink()
-                if match_threshold is not None:
-                    base_names, base_rows = match_base
-                    try:
-                        res = eng.match(embeddings_all, base_rows, match_threshold, NEIGHBOUR_METRIC)
-                    except ValueError as e:         # more matches than NNEngine.match's cap: nothing was allocated for them
-                        console.error(f"GENOMAD_AMD_MATCH={match_threshold:g}: {e}. Raise GENOMAD_AMD_MATCH or unset it.")
-                        sys.exit(1)
-                    write_matches(match_path, match_tsv_path, names_key, names, base_names, res, strand)
-                    console.log(f"Matches of the {what}s against {match_base_path.name} ({NEIGHBOUR_METRIC} similarity of the encoder "
-                                f"embeddings >= {match_threshold:g}: {res.n_edges} matches of {int((res.hits() > 0).sum())} {what}s among "
-                                f"{res.n_base} reference rows) written to {match_path.name} and {match_tsv_path.name}.")
-                else:                               # likewise, both files
-                    for p in (match_path, match_tsv_path):
-                        if p.exists():
-                            p.unlink()
-                if vote_request is not None:
-                    base_names, base_rows, classes, base_label = vote_base
-                    res = eng.vote(embeddings_all, base_rows, base_label, len(classes), vote_threshold)
-                    write_votes(vote_path, vote_tsv_path, names_key, names, classes, base_names, base_label, res, vote_min_votes, strand)
-                    console.log(f"Votes of {vote_base_path.name} on the {what}s ({NEIGHBOUR_METRIC} similarity of the encoder embeddings >= "
-                                f"{vote_threshold:g}, {len(classes)} classes: {int((res.predict(VOTE_RULE, vote_min_votes)[0] >= 0).sum())} "
-                                f"of {len(names)} {what}s got a label) written to {vote_path.name} and {vote_tsv_path.name}.")
-                else:                               # likewise, both files
-                    for p in (vote_path, vote_tsv_path):
-                        if p.exists():
-                            p.unlink()
+                    a.write(npz, tsv, names_key, names, res, strand, ctx)
+                    title = a.title.format(what=what, base=ctx.base_path.name if ctx.base_path is not None else None)
+                    console.log(f"{title} ({a.summary(res, request, what, ctx)}) written to {npz.name}"
+                                + (f" and {tsv.name}." if tsv is not None else "."))
         if cleanup and rank0 and enc_dir.is_dir():
             console.log(f"Deleting encoded {what} data.")
             shutil.rmtree(enc_dir)
         if rank0:
             write_tsv(tsv_path, names, predictions)
 
-    run = stage_device if device_front_end else stage
-    region_emb_default = {"sequence": outputs.nn_region_embeddings_output, "provirus": outputs.provirus_nn_region_embeddings_output}
-    graph_files = {"sequence": (outputs.nn_graph_output, outputs.nn_graph_tsv_output),
-                   "provirus": (outputs.provirus_nn_graph_output, outputs.provirus_nn_graph_tsv_output)}
-    density_files = {"sequence": (outputs.nn_density_output, outputs.nn_density_tsv_output),
-                     "provirus": (outputs.provirus_nn_density_output, outputs.provirus_nn_density_tsv_output)}
-    kmeans_files = {"sequence": (outputs.nn_kmeans_output, outputs.nn_kmeans_tsv_output),
-                    "provirus": (outputs.provirus_nn_kmeans_output, outputs.provirus_nn_kmeans_tsv_output)}
-    pca_files = {"sequence": (outputs.nn_pca_output, outputs.nn_pca_tsv_output),
-                 "provirus": (outputs.provirus_nn_pca_output, outputs.provirus_nn_pca_tsv_output)}
-    match_files = {"sequence": (outputs.nn_matches_output, outputs.nn_matches_tsv_output),
-                   "provirus": (outputs.provirus_nn_matches_output, outputs.provirus_nn_matches_tsv_output)}
-    vote_files = {"sequence": (outputs.nn_votes_output, outputs.nn_votes_tsv_output),
-                  "provirus": (outputs.provirus_nn_votes_output, outputs.provirus_nn_votes_tsv_output)}
-    emb_kw = (lambda path: {"emb_path": path}) if embeddings else (lambda path: {})
-    scan_kw = (lambda path: {"scan_path": path}) if scan_stride is not None else (lambda path: {})
-    region_emb_kw = (lambda path: {"region_emb_path": path}) if region_embeddings else (lambda path: {})
-    strand_kw = ((lambda path, occ, attr, reg, nn, cl, rp, lk: {"strand_path": path, "occ_path": occ, "attr_path": attr, "regions_paths": reg,
-                                                                "nn_path": nn, "clusters_paths": cl, "representatives_paths": rp,
-                                                                "linkage_paths": lk})
-                 if device_front_end else (lambda path, occ, attr, reg, nn, cl, rp, lk: {}))
+    def run(fasta, what, names_key, ids_key):
+        if device_front_end:
+            stage_device(fasta, what, names_key, ids_key)
+        else:
+            stage(fasta, *outputs.classification_files(what), names_key, ids_key, what)
+
     try:
-        run(input_path, outputs.encoded_sequences_dir, outputs.seq_window_id_output,
-            outputs.nn_classification_npz_output, outputs.nn_classification_output,
-            "contig_names", "contig_ids", "sequence", **strand_kw(outputs.nn_strand_output, outputs.nn_occlusion_output, outputs.nn_attribution_output,
-                                                           (outputs.nn_regions_output, outputs.nn_regions_tsv_output),
-                                                           outputs.nn_neighbours_output,
-                                                           (outputs.nn_clusters_output, outputs.nn_clusters_tsv_output),
-                                                           (outputs.nn_representatives_output, outputs.nn_representatives_tsv_output),
-                                                           (outputs.nn_linkage_output, outputs.nn_linkage_tsv_output)),
-            **emb_kw(outputs.nn_embeddings_output),
-            **scan_kw(outputs.nn_scan_output), **region_emb_kw(outputs.nn_region_embeddings_output))
+        run(input_path, "sequence", "contig_names", "contig_ids")
         if classify_proviruses:                                                      # :248-281, :355-425
-            run(outputs.find_proviruses_nucleotide_output, outputs.encoded_proviruses_dir,
-                outputs.provirus_window_id_output, outputs.provirus_nn_classification_npz_output,
-                outputs.provirus_nn_classification_output, "provirus_names", "provirus_ids", "provirus", **strand_kw(outputs.provirus_nn_strand_output, outputs.provirus_nn_occlusion_output, outputs.provirus_nn_attribution_output,
-                                                                           (outputs.provirus_nn_regions_output, outputs.provirus_nn_regions_tsv_output),
-                                                                           outputs.provirus_nn_neighbours_output,
-                                                                           (outputs.provirus_nn_clusters_output,
-                                                                            outputs.provirus_nn_clusters_tsv_output),
-                                                                           (outputs.provirus_nn_representatives_output,
-                                                                            outputs.provirus_nn_representatives_tsv_output),
-                                                                           (outputs.provirus_nn_linkage_output,
-                                                                            outputs.provirus_nn_linkage_tsv_output)),
-                **emb_kw(outputs.provirus_nn_embeddings_output), **scan_kw(outputs.provirus_nn_scan_output),
-                **region_emb_kw(outputs.provirus_nn_region_embeddings_output))
+            run(outputs.find_proviruses_nucleotide_output, "provirus", "provirus_names", "provirus_ids")
     finally:
         if check_pool is not None:
             check_pool.shutdown(wait=True)
