@@ -137,6 +137,9 @@ SIGNATURES = {
     "gnn_linkage": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_linkage_dev": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_debug_linkage_round_ms": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_density_tree": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_density_tree_dev": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_debug_density_tree_round_ms": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_graph_count": (_int, [_vp, _vp, _i64, C.c_float, _int, _vp, _vp]),
     "gnn_graph_fill": (_int, [_vp, _i64, C.c_float, _int, _vp, _vp, _i64]),
     "gnn_graph_count_dev": (_int, [_vp, _vp, _i64, C.c_float, _int, _vp, _vp]),

@@ -256,6 +256,11 @@ struct LinkageWorkspace {
     DevBuf<unsigned long long> count;            // edges recorded so far
     PinnedBuf<unsigned long long> h_count;       // where the host reads it, once per round
     std::vector<float> round_ms;                 // profiling on: HIP-event time of every round of the last call
+    // the density tree (gnn_density_tree*) alone: 4 B per row, and 12 B per row and neighbour of the self-search's lists
+    DevBuf<float> core;                          // the row's core similarity, NaN at an invalid row
+    DevBuf<int64_t> nidx;                        // gnn_neighbours_dev's [n][min_points - 1] lists, of which only sim is read
+    DevBuf<float> nsim;
+    std::vector<float> tree_round_ms;            // round_ms of the last gnn_density_tree* call
 };
 
 // ---- similarity graph (gnn_graph.hip): persistent, grow-only.  The fragments and flags are NeighbourWorkspace's bfrag / bvalid (and

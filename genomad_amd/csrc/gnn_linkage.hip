@@ -19,6 +19,9 @@
 // Every best, cbest and chi is an integer max or min of values that depend on the pair alone, the slots' order is sorted away: nothing
 // depends on the order the workgroups run in or on the split of the base.  No loop here waits for another workgroup: every loop's
 // termination argument stands next to it.
+// The density-aware linkage tree (gnn_density_tree*; "density-aware linkage tree" in the header) is the same rounds
+// over the mutual-reachability values min(v, core[row], core[col]): the tile kernel and its candidates are templates on a bool, the
+// cores come from the self-search of gnn_neighbours.hip (lk_core_kernel), and reset, pick, link, flatten and lk_run are shared.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -60,16 +63,19 @@ struct LinkageArgs {
     int64_t split_rows;        // base rows per workgroup: a multiple of 32
     float scale;               // 2^-16 for cosine, 1 for dot
     unsigned long long* best;  // [n]
+    const float* core;         // [n] the density tree's core similarities, NaN at an invalid row; unread by the plain tree
 };
 
 // The candidates of one step.  The registers are walked by ascending row (nn_acc_row) and a lane's columns ascend with nb and with the
 // steps, and `!(s <= best so far)` is false for an equal value (-0 equals +0) and true while the best is still NaN (none): the
 // smallest partner among equals is kept.  An invalid column has scale = NaN, so its values fail s == s like a NaN pair.  DIAG: the
-// step overlaps the tile's own rows, and only then is row < col a test.
-template <bool DIAG>
-__device__ __forceinline__ void lk_candidates(const f32x16 (&acc)[2][2], const int* lcomp, int r0, int lane, const float (&scale)[2],
-                                              const int (&col)[2], const int (&cc)[2], float (&bval)[2][16], int (&bcol)[2][16],
-                                              float (&cval)[2], int (&crow)[2]) {
+// step overlaps the tile's own rows, and only then is row < col a test.  MR (the density tree): the candidate's value is the pair's
+// mutual-reachability value min(s, core[row], core[col]) - taken behind the s == s test, since fminf drops a NaN operand and would
+// turn a NaN pair into an edge; a valid row's core is a number wherever it has a candidate.
+template <bool DIAG, bool MR>
+__device__ __forceinline__ void lk_candidates(const f32x16 (&acc)[2][2], const int* lcomp, const float* lcore, int r0, int lane,
+                                              const float (&scale)[2], const int (&col)[2], const int (&cc)[2], const float (&ccore)[2],
+                                              float (&bval)[2][16], int (&bcol)[2][16], float (&cval)[2], int (&crow)[2]) {
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
@@ -77,10 +83,13 @@ __device__ __forceinline__ void lk_candidates(const f32x16 (&acc)[2][2], const i
             const int row = nn_acc_row(mb, r, lane >> 5);
             const int rg = r0 + row;
             const int rc = lcomp[row];
+            float rcore = 0.f;
+            if constexpr (MR) rcore = lcore[row];
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
-                const float s = acc[mb][nb][r] * scale[nb];
+                float s = acc[mb][nb][r] * scale[nb];
                 const bool e = rc >= 0 && rc != cc[nb] && s == s && (!DIAG || rg < col[nb]);
+                if constexpr (MR) s = fminf(fminf(s, rcore), ccore[nb]);
                 if (e && !(s <= bval[mb][r])) {
                     bval[mb][r] = s;
                     bcol[mb][r] = col[nb];
@@ -94,11 +103,15 @@ __device__ __forceinline__ void lk_candidates(const f32x16 (&acc)[2][2], const i
 }
 
 // grid = (row tiles, base ranges), 256 threads.  LDS: the tile's fragments 128 KB - one workgroup per CU, a wave has its SIMD's whole
-// register file: 64 VGPRs of running bests beside the 64 of acc -, its rows' components and bests.
+// register file: 64 VGPRs of running bests beside the 64 of acc -, its rows' components and bests.  MR: the density tree's values
+// (lk_candidates), the rows' cores in LDS and a column's fetched with its component; the skip rule and the key > pk shortcut only ever
+// skip a maximum that cannot win, whatever the value is made of.
+template <bool MR>
 __global__ __launch_bounds__(256) void lk_tile_kernel(LinkageArgs a) {
     __shared__ uint4 qs[2 * BLK_U4];
     __shared__ unsigned long long lbest[QT];   // the rows' best partners among this workgroup's columns: flushed once
     __shared__ int lcomp[QT];                  // the row's component, -1: the row is invalid or beyond n
+    __shared__ float lcore[MR ? QT : 1];       // MR: the row's core similarity
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     TileRange t;
     if (!nn_tile_range(t, a.split_rows, a.n, true)) return;
@@ -107,6 +120,7 @@ __global__ __launch_bounds__(256) void lk_tile_kernel(LinkageArgs a) {
     if (tid < QT) {
         lbest[tid] = 0;
         lcomp[tid] = r0 + tid < a.n ? a.comp[r0 + tid] : -1;
+        if constexpr (MR) lcore[tid] = r0 + tid < a.n ? a.core[r0 + tid] : NAN;
     }
     __syncthreads();
     // the component all valid rows of the tile share; -1: they do not.  The same in every wave: a tile without a valid row leaves whole
@@ -133,12 +147,14 @@ __global__ __launch_bounds__(256) void lk_tile_kernel(LinkageArgs a) {
     // older than another workgroup's maximum by the time it is used: then a maximum is merely not skipped.
     int ncc[2];
     unsigned long long npk[2];
+    float ncore[2] = {NAN, NAN};           // MR: the column's core similarity
     auto fetch = [&](int64_t c0) {
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
             const int64_t col = nn_blk_col(nn_step_blk(c0, wave, nb), lane);
             ncc[nb] = col < b1 ? a.comp[col] : -1;
             npk[nb] = col < b1 ? lk_peek(a.best + col) : ~0ull;
+            if constexpr (MR) ncore[nb] = col < b1 ? a.core[col] : NAN;
         }
     };
     fetch(t.c0);
@@ -147,12 +163,13 @@ __global__ __launch_bounds__(256) void lk_tile_kernel(LinkageArgs a) {
         const uint4* bp[2];
         int col[2], cc[2];                 // the lane's column and its component, -1: no edge can end there
         unsigned long long pk[2];
-        float scale[2];
+        float scale[2], ccore[2];
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
             col[nb] = (int)nn_step_column(a.frag, c0, wave, lane, nb, last_blk, bp[nb]);    // read only where cc >= 0: there it is < b1 < 2^31
             cc[nb] = ncc[nb];
             pk[nb] = npk[nb];
+            ccore[nb] = ncore[nb];
             scale[nb] = cc[nb] >= 0 ? a.scale : NAN;
         }
         fetch(c0 + STEP);
@@ -164,9 +181,9 @@ __global__ __launch_bounds__(256) void lk_tile_kernel(LinkageArgs a) {
         float cval[2] = {NAN, NAN};        // per column of the lane: the best value in this step's rows, and its row
         int crow[2] = {-1, -1};
         if (c0 < r0 + QT)                  // wave-uniform
-            lk_candidates<true>(acc, lcomp, (int)r0, lane, scale, col, cc, bval, bcol, cval, crow);
+            lk_candidates<true, MR>(acc, lcomp, lcore, (int)r0, lane, scale, col, cc, ccore, bval, bcol, cval, crow);
         else
-            lk_candidates<false>(acc, lcomp, (int)r0, lane, scale, col, cc, bval, bcol, cval, crow);
+            lk_candidates<false, MR>(acc, lcomp, lcore, (int)r0, lane, scale, col, cc, ccore, bval, bcol, cval, crow);
         // ---- the column side: a column is one lane's in all its registers and the other half's - one max per column and step, and
         // only where it can raise what the load of a step ago saw
 #pragma unroll
@@ -243,6 +260,21 @@ __global__ __launch_bounds__(256) void lk_flatten_kernel(int64_t n, const int32_
     comp[i] = nn_root(parent, (int)i);
 }
 
+// The density tree's core similarities from the self-search's lists (gnn_neighbours_dev, k = min_points - 1): the last entry of the
+// row's list that is a number - the lists are NaN-padded behind their last partner -, NaN for a row without one.  k == 0
+// (min_points 1): +inf at a valid row, which leaves every pair value as it is.
+__global__ __launch_bounds__(256) void lk_core_kernel(int64_t n, int k, const uint8_t* __restrict__ valid, const float* __restrict__ nsim,
+                                                      float* __restrict__ core) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float c = k == 0 && valid[i] ? INFINITY : NAN;
+    for (int j = 0; j < k; ++j) {          // Ends: j counts to k <= 64
+        const float s = nsim[i * k + j];
+        if (s == s) c = s;
+    }
+    core[i] = c;
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 
 int check_linkage_args(const char* fn, const void* rows, int64_t n, int metric, const void* a, const void* b, const void* sim, const void* valid,
@@ -261,13 +293,26 @@ int check_linkage_args(const char* fn, const void* rows, int64_t n, int metric, 
 }
 
 // n > 0 rows on the device -> the sorted tree, the flags and the two counts on the host.  The ctx's stream is synchronised once per
-// round (the host reads the number of edges) and once for the records.
-int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int metric, int64_t* a_host, int64_t* b_host, float* sim_host,
-           uint8_t* valid_host, int64_t* n_edges_host, int64_t* rounds_host) {
+// round (the host reads the number of edges) and once for the records.  min_points > 0: the density tree - the pair values are the
+// mutual-reachability values under the core similarities, which go to core_host [n] as well; min_points >= 2 runs the self-search
+// first, whose prepare leaves the same fragments and flags as nn_prepare would.
+int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int metric, int min_points, int64_t* a_host, int64_t* b_host,
+           float* sim_host, float* core_host, uint8_t* valid_host, int64_t* n_edges_host, int64_t* rounds_host) {
     NeighbourWorkspace& w = ctx->nn;
     LinkageWorkspace& k = ctx->lk;
     const int64_t capacity = n - 1;
-    int rc = nn_prepare(ctx, rows_dev, n, metric, w.bfrag, w.bvalid);
+    const bool mr = min_points > 0;
+    const int nk = mr ? min_points - 1 : 0;
+    std::vector<float>& round_ms = mr ? k.tree_round_ms : k.round_ms;
+    int rc = GNN_OK;
+    if (nk > 0) {
+        rc = nn_reserve(ctx, k.nidx, (size_t)n * nk);
+        if (!rc) rc = nn_reserve(ctx, k.nsim, (size_t)n * nk);
+        if (!rc) rc = gnn_neighbours_dev(ctx, rows_dev, n, nullptr, n, nk, metric, k.nidx.get(), k.nsim.get());
+    } else {
+        rc = nn_prepare(ctx, rows_dev, n, metric, w.bfrag, w.bvalid);
+    }
+    if (!rc && mr) rc = nn_reserve(ctx, k.core, (size_t)n);
     if (!rc) rc = nn_reserve(ctx, k.parent, (size_t)n);
     if (!rc) rc = nn_reserve(ctx, k.comp, (size_t)n);
     if (!rc) rc = nn_reserve(ctx, k.chi, (size_t)n);
@@ -290,12 +335,17 @@ int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int m
     a.split_rows = split_rows;
     a.scale = nn_metric_scale(metric);
     a.best = k.best.get();
-    k.round_ms.clear();
+    a.core = mr ? k.core.get() : nullptr;
+    round_ms.clear();
     {
         ProfScope prof(ctx, GNN_K_NEIGHBOURS);
         GNN_HIP(hipMemsetAsync(k.count.get(), 0, sizeof(unsigned long long), ctx->stream));
         hipLaunchKernelGGL(lk_init_kernel, per_row, dim3(256), 0, ctx->stream, n, w.bvalid.get(), k.comp.get());
         GNN_HIP(hipGetLastError());
+        if (mr) {
+            hipLaunchKernelGGL(lk_core_kernel, per_row, dim3(256), 0, ctx->stream, n, nk, w.bvalid.get(), k.nsim.get(), k.core.get());
+            GNN_HIP(hipGetLastError());
+        }
     }
     // One Boruvka round per pass.  Every component with an outgoing edge is joined to another one, so the components that are not
     // yet final at least halve: at most 31 rounds add an edge for n < 2^31, and one more adds none.  Ends: the loop is bounded by
@@ -315,7 +365,10 @@ int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int m
             hipLaunchKernelGGL(lk_reset_kernel, per_row, dim3(256), 0, ctx->stream, n, k.comp.get(), k.parent.get(), k.best.get(), k.cbest.get(),
                                k.chi.get());
             GNN_HIP(hipGetLastError());
-            hipLaunchKernelGGL(lk_tile_kernel, tile_grid, dim3(256), 0, ctx->stream, a);
+            if (mr)
+                hipLaunchKernelGGL(lk_tile_kernel<true>, tile_grid, dim3(256), 0, ctx->stream, a);
+            else
+                hipLaunchKernelGGL(lk_tile_kernel<false>, tile_grid, dim3(256), 0, ctx->stream, a);
             GNN_HIP(hipGetLastError());
             hipLaunchKernelGGL(lk_pick_lo_kernel, per_row, dim3(256), 0, ctx->stream, n, k.comp.get(), k.best.get(), k.cbest.get());
             GNN_HIP(hipGetLastError());
@@ -330,7 +383,7 @@ int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int m
         GNN_HIP(hipMemcpyAsync(k.h_count.get(), k.count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         GNN_HIP(hipStreamSynchronize(ctx->stream));
         const unsigned long long now = k.h_count.get()[0];
-        timer.file(k.round_ms);
+        timer.file(round_ms);
         if (now > (unsigned long long)capacity) {
             set_error(std::string(fn) + ": round " + std::to_string(pass + 1) + " recorded " + std::to_string(now) + " edges among " +
                       std::to_string(n) + " rows: a forest has at most n - 1");
@@ -350,6 +403,7 @@ int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int m
         GNN_HIP(hipMemcpyAsync(es.data(), k.es.get(), m * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     }
     GNN_HIP(hipMemcpyAsync(valid_host, w.bvalid.get(), (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (mr) GNN_HIP(hipMemcpyAsync(core_host, k.core.get(), (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     GNN_HIP(hipStreamSynchronize(ctx->stream));
     std::vector<int64_t> order(m);
     std::iota(order.begin(), order.end(), (int64_t)0);
@@ -382,7 +436,7 @@ extern "C" int gnn_linkage_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, i
     *n_edges_host = 0;
     *rounds_host = 0;
     if (n == 0) return GNN_OK;
-    return lk_run(ctx, fn, rows_dev, n, metric, a_host, b_host, sim_host, valid_host, n_edges_host, rounds_host);
+    return lk_run(ctx, fn, rows_dev, n, metric, 0, a_host, b_host, sim_host, nullptr, valid_host, n_edges_host, rounds_host);
 }
 
 extern "C" int gnn_linkage(gnn_ctx* ctx, const float* rows_host, int64_t n, int metric, int64_t* a_host, int64_t* b_host, float* sim_host,
@@ -394,10 +448,66 @@ extern "C" int gnn_linkage(gnn_ctx* ctx, const float* rows_host, int64_t n, int 
     *rounds_host = 0;
     if (n == 0) return GNN_OK;
     if (int rc = nn_upload_rows(ctx, rows_host, n)) return rc;
-    return lk_run(ctx, fn, ctx->nn.d_base, n, metric, a_host, b_host, sim_host, valid_host, n_edges_host, rounds_host);
+    return lk_run(ctx, fn, ctx->nn.d_base, n, metric, 0, a_host, b_host, sim_host, nullptr, valid_host, n_edges_host, rounds_host);
 }
 
 extern "C" int gnn_debug_linkage_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
     if (int rc = check_ctx(ctx)) return rc;
     return nn_round_ms_out("gnn_debug_linkage_round_ms", ctx->lk.round_ms, ms_out, capacity, n_out);
+}
+
+// ---- the density tree: the same rounds over the mutual-reachability values (include/genomad_nn.h, "density-aware linkage tree") ----
+
+namespace gnn {
+namespace {
+
+constexpr int MIN_POINTS_MAX = 65;               // the row itself and the neighbour search's 64
+
+int check_density_tree_args(const char* fn, const void* rows, int64_t n, int min_points, int metric, const void* a, const void* b, const void* sim,
+                            const void* core, const void* valid, const void* n_edges, const void* rounds) {
+    if (min_points < 1 || min_points > MIN_POINTS_MAX) {
+        set_error(std::string(fn) + ": min_points " + std::to_string(min_points) + " is outside [1, " + std::to_string(MIN_POINTS_MAX) + "]");
+        return GNN_ERR_ARG;
+    }
+    if (int rc = check_linkage_args(fn, rows, n, metric, a, b, sim, valid, n_edges, rounds)) return rc;
+    if (n > 0 && !core) {
+        set_error(std::string("bad argument to ") + fn + ": core is required");
+        return GNN_ERR_ARG;
+    }
+    return GNN_OK;
+}
+
+}  // namespace
+}  // namespace gnn
+
+extern "C" int gnn_density_tree_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, int min_points, int metric, int64_t* a_host, int64_t* b_host,
+                                    float* sim_host, float* core_host, uint8_t* valid_host, int64_t* n_edges_host, int64_t* rounds_host) {
+    const char* const fn = "gnn_density_tree_dev";
+    if (int rc = check_density_tree_args(fn, rows_dev, n, min_points, metric, a_host, b_host, sim_host, core_host, valid_host, n_edges_host,
+                                         rounds_host))
+        return rc;
+    if (int rc = check_ctx(ctx)) return rc;
+    *n_edges_host = 0;
+    *rounds_host = 0;
+    if (n == 0) return GNN_OK;
+    return lk_run(ctx, fn, rows_dev, n, metric, min_points, a_host, b_host, sim_host, core_host, valid_host, n_edges_host, rounds_host);
+}
+
+extern "C" int gnn_density_tree(gnn_ctx* ctx, const float* rows_host, int64_t n, int min_points, int metric, int64_t* a_host, int64_t* b_host,
+                                float* sim_host, float* core_host, uint8_t* valid_host, int64_t* n_edges_host, int64_t* rounds_host) {
+    const char* const fn = "gnn_density_tree";
+    if (int rc = check_density_tree_args(fn, rows_host, n, min_points, metric, a_host, b_host, sim_host, core_host, valid_host, n_edges_host,
+                                         rounds_host))
+        return rc;
+    if (int rc = check_ctx(ctx)) return rc;
+    *n_edges_host = 0;
+    *rounds_host = 0;
+    if (n == 0) return GNN_OK;
+    if (int rc = nn_upload_rows(ctx, rows_host, n)) return rc;
+    return lk_run(ctx, fn, ctx->nn.d_base, n, metric, min_points, a_host, b_host, sim_host, core_host, valid_host, n_edges_host, rounds_host);
+}
+
+extern "C" int gnn_debug_density_tree_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
+    if (int rc = check_ctx(ctx)) return rc;
+    return nn_round_ms_out("gnn_debug_density_tree_round_ms", ctx->lk.tree_round_ms, ms_out, capacity, n_out);
 }

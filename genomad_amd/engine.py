@@ -309,6 +309,59 @@ class LinkageResult(_Result):
         return cls(a=a, b=b, sim=sim, valid=valid, n=len(valid), n_valid=int(np.count_nonzero(valid)), rounds=int(rounds), metric=str(metric))
 
 
+class DensityTreeResult(_Result):
+    """What :meth:`NNEngine.density_tree` returns (the definition is ``sequence.mutual_reachability_tree``): the tree's edges, best
+    first - ``a`` (int64, the smaller row), ``b`` (int64, the larger), ``sim`` (float32, the mutual-reachability value), trimmed to
+    ``n_edges`` -, ``core`` (float32 (n,): the row's core similarity, NaN for an invalid row), ``valid`` (uint8 (n,)), ``n``,
+    ``n_valid``, ``rounds``, ``min_points`` and ``metric``."""
+    FIELDS = ("a", "b", "sim", "core", "valid", "n", "n_valid", "rounds", "min_points", "metric")
+
+    @property
+    def n_edges(self) -> int:
+        return len(self.a)
+
+    def cut(self, threshold) -> np.ndarray:
+        """``sequence.density_tree_cut``: the ``label`` of :meth:`NNEngine.density` at (``threshold``, ``min_points``) at its core
+        rows, -1 at every other row"""
+        from . import sequence as S
+        return S.density_tree_cut(self.a, self.b, self.sim, self.core, self.valid, threshold)
+
+    def cluster_counts(self, thresholds) -> np.ndarray:
+        """``sequence.density_tree_cluster_counts``: the clusters of core rows a cut leaves at each threshold"""
+        from . import sequence as S
+        return S.density_tree_cluster_counts(self.sim, self.core, self.valid, thresholds)
+
+    def hdbscan(self, min_cluster_size=5, allow_single_cluster=False) -> dict:
+        """``sequence.hdbscan_clusters`` of this tree: ``label``, ``lambda_out`` and the cluster table.  Cosine only (1 - sim is a
+        distance); a forest - which only ``dot`` can give - is a ValueError there."""
+        from . import sequence as S
+        if self.metric != "cosine":
+            raise ValueError(f"metric {self.metric!r}: 1 - sim is a distance under cosine only")
+        return S.hdbscan_clusters(self.a, self.b, self.sim, self.valid, min_cluster_size, allow_single_cluster)
+
+    def matrix(self) -> np.ndarray:
+        """``sequence.linkage_matrix`` of the mutual-reachability values: SciPy's convention, distance = 1 - sim; cosine, all rows
+        valid and a spanning tree only"""
+        from . import sequence as S
+        if self.metric != "cosine":
+            raise ValueError(f"metric {self.metric!r}: 1 - sim is a distance under cosine only")
+        if self.n_valid != self.n:
+            raise ValueError(f"{self.n - self.n_valid} of {self.n} rows are invalid: a linkage matrix needs every row")
+        return S.linkage_matrix(self.a, self.b, self.sim, self.n)
+
+    def table(self, names=None):
+        """``sequence.linkage_table``: one record per merge - rank, a, b, sim, clusters left"""
+        from . import sequence as S
+        return S.linkage_table(self.a, self.b, self.sim, self.n_valid, names)
+
+    @classmethod
+    def build(cls, arrays, min_points, metric, rounds=0):
+        """from the (a, b, sim, core, valid) of ``sequence.mutual_reachability_tree`` or the library, already trimmed"""
+        a, b, sim, core, valid = arrays
+        return cls(a=a, b=b, sim=sim, core=core, valid=valid, n=len(valid), n_valid=int(np.count_nonzero(valid)), rounds=int(rounds),
+                   min_points=int(min_points), metric=str(metric))
+
+
 class GraphResult(_Result):
     """What :meth:`NNEngine.graph` returns (the definition is ``sequence.threshold_graph``): the similarity graph's upper triangle in
     CSR form - ``indptr`` (int64 (n + 1,)), ``col`` (int32: row i owns ``col[indptr[i]:indptr[i + 1]]``, its partners j > i in
@@ -1368,6 +1421,42 @@ class NNEngine:
         """measurement only (``gnn_debug_linkage_round_ms``): with profiling enabled, the HIP-event milliseconds of every round of the
         last ``linkage`` / ``linkage_dev`` call, a last round that added no edge included"""
         return self._debug_ms(self.lib.gnn_debug_linkage_round_ms)
+
+    # -- density-aware linkage tree ------------------------------------------------------
+    def _density_tree(self, fn, rows_ptr, n, min_points, metric) -> DensityTreeResult:
+        self._check_metric(metric)
+        m = _sequence.density_tree_min_points(min_points)
+        cap = max(int(n) - 1, 0)
+        a, b, sim = np.empty(cap, np.int64), np.empty(cap, np.int64), np.empty(cap, np.float32)
+        core = np.full(max(int(n), 0), np.nan, np.float32)
+        valid = np.zeros(max(int(n), 0), np.uint8)
+        n_edges, rounds = C.c_int64(0), C.c_int64(0)
+        check(fn(self.ctx, rows_ptr, int(n), m, self._knn_metric(metric), a.ctypes.data, b.ctypes.data, sim.ctypes.data, core.ctypes.data,
+                 valid.ctypes.data, C.addressof(n_edges), C.addressof(rounds)))
+        e = n_edges.value
+        return DensityTreeResult.build((a[:e].copy(), b[:e].copy(), sim[:e].copy(), core, valid), m, self._metric_name(metric), rounds.value)
+
+    def density_tree(self, rows, min_points=5, metric="cosine") -> DensityTreeResult:
+        """The density-aware linkage tree among encoder embeddings (``gnn_density_tree``; the definition is
+        ``sequence.mutual_reachability_tree``): :meth:`linkage` over the mutual-reachability values min(v(i, j), core_i, core_j),
+        where core_i is row i's similarity to its (``min_points`` - 1)-th nearest neighbour - the last finite entry of row i of
+        ``neighbours(rows, None, min_points - 1).sim``, bit for bit.  A bridge row between two families no longer merges them
+        early, and a straggler joins late: ``result.cut(t)`` is the core rows' ``label`` of :meth:`density` at (t, min_points) for
+        every t without another pass, and ``result.hdbscan(min_cluster_size)`` picks the clusters without a threshold.  Exact;
+        1 <= ``min_points`` <= 65; ``min_points`` 1 is :meth:`linkage`, bit for bit.  :meth:`set_neighbour_split` sets the range of
+        this search too; no result depends on it."""
+        r = _sequence.neighbour_rows(rows, "rows")
+        return self._density_tree(self.lib.gnn_density_tree, r.ctypes.data, len(r), min_points, metric)
+
+    def density_tree_dev(self, rows_ptr: int, n: int, min_points=5, metric="cosine") -> DensityTreeResult:
+        """``gnn_density_tree_dev``: the rows (n x 512 f32) on the device, the result on the host; the engine's stream is synchronised
+        once per round and the call returns with the result."""
+        return self._density_tree(self.lib.gnn_density_tree_dev, rows_ptr, n, min_points, metric)
+
+    def density_tree_round_ms(self):
+        """measurement only (``gnn_debug_density_tree_round_ms``): with profiling enabled, the HIP-event milliseconds of every round
+        of the last ``density_tree`` / ``density_tree_dev`` call, a last round that added no edge included"""
+        return self._debug_ms(self.lib.gnn_debug_density_tree_round_ms)
 
     # -- occlusion maps ------------------------------------------------------------------
     def occlusion_plan(self, offsets: np.ndarray, block: int, single_window: bool = False):

@@ -87,7 +87,7 @@ class Outputs:
         # written only when GENOMAD_AMD_REGION_EMBEDDINGS=1 (encoder embeddings per called region; no counterpart in the reference)
         self.nn_region_embeddings_output = d / f"{p}_nn_region_embeddings.npz"
         self.provirus_nn_region_embeddings_output = d / f"{p}_provirus_nn_region_embeddings.npz"
-        # written only when the analysis is requested (the ten analyses of the per-contig embeddings, ANALYSES below: <stem>.npz and,
+        # written only when the analysis is requested (the eleven analyses of the per-contig embeddings, ANALYSES below: <stem>.npz and,
         # for all but the neighbours, <stem>.tsv; no counterpart in the reference)
         for stage in self._STAGE.values():
             for a in ANALYSES:
@@ -644,6 +644,59 @@ def write_density(npz_path, tsv_path, names_key, names, res, strand="forward"):
     write_density_tsv(tsv_path, names, res)
 
 
+def hdbscan_requested():
+    """GENOMAD_AMD_HDBSCAN=<integer >= 2>: main() also writes the HDBSCAN clusters of the contigs - the density-aware linkage tree
+    under the cosine similarity of the per-contig encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1, condensed with that minimum
+    cluster size and cut by excess of mass (<prefix>_nn_hdbscan.npz and .tsv); unset or empty: nothing changes (None).
+    GENOMAD_AMD_HDBSCAN_MIN_POINTS=<integer in [1, 65]> (default: the minimum cluster size, 65 at the most) is how many contigs,
+    itself included, a contig's core similarity looks at; it is an error without GENOMAD_AMD_HDBSCAN.  Any other value of either
+    is an error.  Returns (min_cluster_size, min_points), or None."""
+    size = _env_int("GENOMAD_AMD_HDBSCAN", 2, (1 << 31) - 1, "(below 2^31): the contigs a cluster has at the least")
+    if size is None:
+        _env_refines("GENOMAD_AMD_HDBSCAN_MIN_POINTS", "GENOMAD_AMD_HDBSCAN", "set the minimum cluster size or unset")
+        return None
+    return size, _env_int("GENOMAD_AMD_HDBSCAN_MIN_POINTS", 1, sequence.DENSITY_TREE_MIN_POINTS_MAX,
+                          "(the contigs, itself included, that a contig's core similarity looks at)",
+                          min(size, sequence.DENSITY_TREE_MIN_POINTS_MAX))
+
+
+HDBSCAN_TSV_HEADER = "seq_name\tcluster\tcluster_size\tcore_similarity\tlambda_out\n"
+
+
+def write_hdbscan_tsv(path, names, tree, found):
+    """One line per contig: the name of its cluster's label contig and the cluster's size (NA, 0 for noise), its core similarity and
+    the lambda at which it left the deepest cluster it was in; a contig without a valid embedding has NA, 0, NA, NA."""
+    label = found["label"]
+    size = np.bincount(label[label >= 0], minlength=len(names))
+    with open(path, "w") as fout:
+        fout.write(HDBSCAN_TSV_HEADER)
+        for i, name in enumerate(names):
+            if not tree.valid[i]:
+                fout.write(f"{name}\tNA\t0\tNA\tNA\n")
+                continue
+            cluster = names[label[i]] if label[i] >= 0 else "NA"
+            core = f"{tree.core[i]:.6f}" if np.isfinite(tree.core[i]) else "NA"
+            fout.write(f"{name}\t{cluster}\t{size[label[i]] if label[i] >= 0 else 0}\t{core}\t{found['lambda_out'][i]:.6g}\n")
+
+
+def write_hdbscan(npz_path, tsv_path, names_key, names, res, min_cluster_size, strand="forward"):
+    """Both HDBSCAN files of a stage: the DensityTreeResult's tree and core similarities, the labels and the cluster table of
+    ``sequence.hdbscan_clusters`` with the contig names, and one line per contig."""
+    tree, found = res
+    np.savez_compressed(npz_path, **{names_key: names, "min_cluster_size": np.int64(min_cluster_size), "min_points": np.int64(tree.min_points),
+                                     "metric": np.array(tree.metric), "a": tree.a, "b": tree.b, "sim": tree.sim, "core": tree.core,
+                                     "valid": tree.valid, "rounds": np.int64(tree.rounds), "label": found["label"],
+                                     "lambda_out": found["lambda_out"],
+                                     **{"cluster_" + k: found[k] for k in ("parent", "birth", "stability", "size", "selected")},
+                                     "cluster": found["cluster"], **_strand_entry(strand)})
+    write_hdbscan_tsv(tsv_path, names, tree, found)
+
+
+def _run_hdbscan(eng, emb, request):
+    tree = eng.density_tree(emb, request[1], NEIGHBOUR_METRIC)
+    return tree, tree.hdbscan(request[0])
+
+
 def kmeans_requested():
     """GENOMAD_AMD_KMEANS=<integer in [1, 65535]>: main() also writes the spherical k-means of the contigs - exactly that many groups
     under the cosine similarity of the per-contig encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1, and one centroid per group
@@ -1133,7 +1186,7 @@ def _encode(fasta_path, enc_dir: Path, window_id_path: Path, single_window: bool
 
 
 # ---- the analyses of the gathered per-contig embeddings ------------------------------------------------------------------------------
-# Ten analyses follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
+# Eleven analyses follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
 #   name      the stem of its files, <prefix>_nn_<name>.npz and - where ``tsv`` - .tsv
 #   switch    the environment variable that requests it; ``request()`` reads it (and its companions): the request, or None
 #   needs     the middle clause of the message that refuses the switch without GENOMAD_AMD_EMBEDDINGS=1
@@ -1201,6 +1254,14 @@ ANALYSES = (        # in the order they run, which is the order of the log lines
              lambda npz, tsv, key, names, res, strand, ctx: write_density(npz, tsv, key, names, res, strand),
              lambda res, r, what, ctx: (f"{_SIMILARITY} >= {r[0]:g}, at least {r[1]} {what}s for a core: {res.n_clusters} clusters, "
                                         f"{res.n_core} core, {res.n_border} border, {res.n_noise} noise")),
+    Analysis("hdbscan", "GENOMAD_AMD_HDBSCAN", hdbscan_requested,
+             "the density-aware tree is built among the per-contig encoder embeddings", (("min_cluster_size", int), ("min_points", int)),
+             "HDBSCAN clusters of the {what}s",
+             lambda eng, emb, r, ctx: _run_hdbscan(eng, emb, r),
+             lambda npz, tsv, key, names, res, strand, ctx: write_hdbscan(npz, tsv, key, names, res, ctx.request[0], strand),
+             lambda res, r, what, ctx: (f"{_SIMILARITY}, at least {r[0]} {what}s per cluster, core similarity over {r[1]}: "
+                                        f"{int(res[1]['selected'].sum())} clusters, {int((res[1]['label'] < 0).sum() - (res[0].n - res[0].n_valid))} "
+                                        f"noise, tree in {res[0].rounds} rounds")),
     Analysis("kmeans", "GENOMAD_AMD_KMEANS", kmeans_requested,
              "the groups are formed among the per-contig encoder embeddings", (("k", int), ("max_iter", int)), "Spherical k-means of the {what}s",
              lambda eng, emb, r, ctx: eng.kmeans(emb, r[0], None, r[1]),                       # farthest-first init

@@ -1517,6 +1517,269 @@ def linkage_table(a, b, sim, n_valid, names=None):
             for k in range(len(a))]
 
 
+DENSITY_TREE_MIN_POINTS_MAX = NEIGHBOUR_K_MAX + 1     # the row itself and the neighbour search's 64
+HDBSCAN_FIELDS = ("label", "lambda_out", "cluster", "parent", "birth", "stability", "size", "selected")
+HDBSCAN_D_MIN = 2.0 ** -24                # the floor of the distance 1 - sim: duplicates (sim = 1) get a finite lambda
+
+
+def density_tree_min_points(min_points) -> int:
+    """``min_points`` of the density tree as an int: an integer in [1, 65]"""
+    return _whole(min_points, "min_points", 1, DENSITY_TREE_MIN_POINTS_MAX)
+
+
+def _pair_values(rows, metric):
+    """(s float64 (n, n), ok bool (n,)): the pair values as :func:`single_linkage_tree` forms them - one pair at a time, the same sum
+    either way round, so s is symmetric to the bit - and the rows' validity"""
+    if metric not in NEIGHBOUR_METRICS:
+        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    r32 = neighbour_rows(rows, "rows")
+    n = len(r32)
+    ok = np.isfinite(r32).all(axis=1)
+    r = np.where(ok[:, None], r32, 0).astype(np.float64)
+    if metric == "cosine":
+        norm = np.sqrt((r * r).sum(axis=1))
+        ok &= norm > 0
+        r = r / np.where(ok, norm, 1.0)[:, None]
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = np.stack([(r * r[i]).sum(axis=1) for i in range(n)]) if n else np.zeros((0, 0))
+    return s + 0.0, ok                                   # -0 + 0 = +0
+
+
+def core_similarity(rows, min_points=5, metric="cosine"):
+    """The core similarities of the density tree, spelled out (float64): for a valid row i its similarity to its
+    (``min_points`` - 1)-th most similar partner among the valid rows j != i whose pair value is a number - the row counts itself,
+    as in :func:`density_clusters`.  Fewer partners than that: the least similar partner there is.  ``min_points`` 1: +inf.  An
+    invalid row, or a row without such a partner: NaN.  Returns (core float64 (n,), valid uint8 (n,)).  The device takes core from
+    ``gnn_neighbours``' lists, whose (i -> j) value may differ in the last bit from the pair value of i < j: this definition has one
+    value per pair."""
+    m = density_tree_min_points(min_points)
+    s, ok = _pair_values(rows, metric)
+    core = np.full(len(ok), np.nan, dtype=np.float64)
+    for i in np.flatnonzero(ok):
+        if m == 1:
+            core[i] = np.inf
+            continue
+        v = s[i][ok & (np.arange(len(ok)) != i)]
+        v = np.sort(v[~np.isnan(v)])[::-1]
+        if len(v):
+            core[i] = v[min(m - 1, len(v)) - 1]
+    return core, ok.astype(np.uint8)
+
+
+def mutual_reachability_tree(rows, min_points=5, metric="cosine"):
+    """The density-aware linkage tree among encoder embeddings, spelled out (the definition ``gnn_density_tree`` computes on the
+    device; float64 throughout, readable, not fast, n x n): :func:`single_linkage_tree` over the mutual-reachability values w(i, j)
+    = min(v(i, j), core_i, core_j), core from :func:`core_similarity`.  The same pairs are edges (both rows valid, v a number), the
+    same strict order decides - w descending, lo ascending, hi ascending; mutual reachability makes many pairs tie exactly - and
+    Kruskal takes an edge iff it joins two components.  Returns (a int64, b int64, sim float32, core float32 (n,), valid uint8 (n,)):
+    the edges best first, sim = w rounded."""
+    core, _ = core_similarity(rows, min_points, metric)
+    s, ok = _pair_values(rows, metric)
+    n = len(ok)
+    lo, hi = np.triu_indices(n, 1)
+    keep = ok[lo] & ok[hi] & ~np.isnan(s[lo, hi])
+    lo, hi = lo[keep], hi[keep]
+    w = np.minimum(np.minimum(s[lo, hi], core[lo]), core[hi])
+    order = np.lexsort((hi, lo, -w))
+    root = np.arange(n)
+
+    def find(x):
+        while root[x] != x:
+            root[x] = root[root[x]]
+            x = root[x]
+        return x
+
+    a, b, sim = [], [], []
+    want = max(int(ok.sum()) - 1, 0)
+    for e in order:
+        if len(a) == want:
+            break
+        x, y = find(lo[e]), find(hi[e])
+        if x != y:
+            root[max(x, y)] = min(x, y)
+            a.append(lo[e])
+            b.append(hi[e])
+            sim.append(w[e])
+    return (np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64), np.asarray(sim, dtype=np.float32), core.astype(np.float32),
+            ok.astype(np.uint8))
+
+
+def density_tree_cut(a, b, sim, core, valid, threshold) -> np.ndarray:
+    """The clusters of a :func:`mutual_reachability_tree` at ``threshold``: the labels of the core-only form of DBSCAN at
+    (threshold, min_points).  A valid row whose core >= the float32 the threshold rounds to gets the smallest index of its
+    component under the tree's edges with sim >= it (an edge's sim is at most either end's core: such a component holds core rows
+    only); every other row gets -1.  Where at least ``min_points`` rows are valid this is ``density_clusters(...)``'s label at the
+    rows of kind 3 (with fewer, core is the least similar partner and the row would never be core there)."""
+    core = np.asarray(core, dtype=np.float32).ravel()
+    label = linkage_cut(a, b, sim, valid, threshold)
+    if len(core) != len(label):
+        raise ValueError(f"core has {len(core)} entries for {len(label)} rows")
+    with np.errstate(invalid="ignore"):
+        label[~(core >= cluster_threshold(threshold))] = -1
+    return label
+
+
+def density_tree_cluster_counts(sim, core, valid, thresholds) -> np.ndarray:
+    """Clusters of core rows that :func:`density_tree_cut` leaves at each of ``thresholds``: #(core >= t) - #(sim >= t), int64."""
+    sim = np.asarray(sim, dtype=np.float32).ravel()
+    core = np.asarray(core, dtype=np.float32).ravel()[np.asarray(valid).astype(bool).ravel()]
+    with np.errstate(invalid="ignore"):
+        return np.array([int((core >= cluster_threshold(t)).sum()) - int((sim >= cluster_threshold(t)).sum())
+                         for t in np.atleast_1d(thresholds)], dtype=np.int64)
+
+
+def hdbscan_clusters(a, b, sim, valid, min_cluster_size=5, allow_single_cluster=False):
+    """HDBSCAN's flat clusters from a :func:`mutual_reachability_tree` over cosine similarities, defined BY LEVELS, not by binary
+    merges: mutual reachability makes many edges tie exactly, and nothing here depends on the order of tied edges or on which
+    spanning tree was found.  The tree must span the valid rows (n_valid - 1 edges; a forest is a ValueError).
+      distance   d = max(1 - float64(sim), 2^-24), lambda = 1 / d.
+      levels     the distinct values of ``sim``, from small lambda to large.  At a level a current cluster falls apart into the
+                 components of its members under the edges with larger sim.  Two or more components of >= ``min_cluster_size`` rows:
+                 each is a new cluster born at that lambda, and the smaller components fall out as points at that lambda.  Exactly
+                 one: the cluster continues in it, the rest falls out.  None: the cluster ends, all its points leave at that lambda.
+      stability  S(C) = sum over the points ever in C of (lambda_p - lambda_birth(C)); lambda_p is the lambda at which p left C, by
+                 falling out or by the split.  The root, all valid rows, is born at lambda = 0.
+      selection  excess of mass, bottom-up: a cluster is selected when S(C) >= the summed stability selected beneath it (a tie
+                 keeps the parent), which unselects everything beneath.  The root is never selected unless ``allow_single_cluster``.
+      label      the smallest member index of the selected cluster from whose subtree the row left; otherwise -1.
+    Returns a dict: ``label`` (int64 (n,)), ``lambda_out`` (float64 (n,): the lambda at which the row left the deepest cluster it
+    was in; NaN for an invalid row) and per cluster, in the order of creation (the root first, a parent before its children),
+    ``cluster`` (its smallest member), ``parent`` (the index of its parent cluster, -1), ``birth``, ``stability``, ``size`` and
+    ``selected``.  ``min_cluster_size`` >= 2."""
+    a, b, sim = _linkage_arrays(a, b, sim)
+    valid = np.asarray(valid).astype(bool).ravel()
+    n = len(valid)
+    mcs = _whole(min_cluster_size, "min_cluster_size", 2, 1 << 31)
+    rows_in = np.flatnonzero(valid)
+    if len(a) != max(len(rows_in) - 1, 0):
+        raise ValueError(f"{len(a)} edges among {len(rows_in)} valid rows: hdbscan needs a spanning tree, not a forest")
+    if np.isnan(sim).any():
+        raise ValueError("an edge's similarity is not a number")
+    if len(a) and (min(a.min(), b.min()) < 0 or max(a.max(), b.max()) >= n or not (valid[a].all() and valid[b].all())):
+        raise ValueError("an edge names a row that is not valid")
+    lam_of = lambda s: 1.0 / max(1.0 - float(s), HDBSCAN_D_MIN)
+    # The dendrogram by levels, bottom-up: node x < n is row x; walking the distinct values of sim downwards, every component that the
+    # level's edges form becomes a node whose children are the components they joined.  kids / level / count / least per node.
+    kids, level, count, least = [None] * n, [None] * n, [1] * n, list(range(n))
+    root = np.arange(n)
+    node_at = list(range(n))                             # at a union-find root: the dendrogram node of its component
+
+    def find(x):
+        while root[x] != x:
+            root[x] = root[root[x]]
+            x = root[x]
+        return x
+
+    order = np.argsort(-sim.astype(np.float64), kind="stable")
+    e = 0
+    while e < len(order):
+        f = e
+        while f < len(order) and sim[order[f]] == sim[order[e]]:
+            f += 1
+        touched = {}                                     # new union-find root -> the nodes joined under it at this level
+        for k in order[e:f]:
+            x, y = find(a[k]), find(b[k])
+            if x == y:
+                raise ValueError(f"edge {k} ({a[k]}, {b[k]}) joins two rows of one component: not a tree")
+            lo, hi = min(x, y), max(x, y)
+            root[hi] = lo
+            touched[lo] = touched.pop(lo, [node_at[lo]]) + touched.pop(hi, [node_at[hi]])
+        for r, nodes in touched.items():
+            kids.append(nodes)
+            level.append(float(sim[order[e]]))
+            count.append(sum(count[x] for x in nodes))
+            least.append(min(least[x] for x in nodes))
+            node_at[r] = len(kids) - 1
+        e = f
+    label = np.full(n, -1, dtype=np.int64)
+    lambda_out = np.full(n, np.nan, dtype=np.float64)
+    out = {"label": label, "lambda_out": lambda_out}
+    c_least, c_parent, c_birth, c_stab, c_size = [], [], [], [], []
+    deepest = np.full(n, -1, dtype=np.int64)             # the row's deepest cluster
+
+    def leaves(x):
+        stack, got = [x], []
+        while stack:
+            y = stack.pop()
+            if kids[y] is None:
+                got.append(y)
+            else:
+                stack.extend(kids[y])
+        return got
+
+    def new_cluster(x, parent, birth):
+        for lst, v in ((c_least, least[x]), (c_parent, parent), (c_birth, birth), (c_stab, 0.0), (c_size, count[x])):
+            lst.append(v)
+        return len(c_least) - 1
+
+    if len(rows_in):
+        top = node_at[find(rows_in[0])]
+        new_cluster(top, -1, 0.0)
+        work = [(0, top)]                                # (cluster, the dendrogram node it lives in now)
+        while work:
+            c, x = work.pop()
+            while True:
+                if kids[x] is None:                      # a single row that is all of the root: it never leaves
+                    deepest[x], lambda_out[x] = c, 0.0
+                    break
+                lam = lam_of(level[x])
+                big = [y for y in kids[x] if count[y] >= mcs]
+                stays = big[0] if len(big) == 1 else -1  # the component the cluster continues in
+                for y in kids[x]:
+                    if y == stays:
+                        continue
+                    c_stab[c] += count[y] * (lam - c_birth[c])
+                    if len(big) >= 2 and count[y] >= mcs:
+                        work.append((new_cluster(y, c, lam), y))
+                    else:
+                        for p in leaves(y):
+                            deepest[p], lambda_out[p] = c, lam
+                if stays < 0:
+                    break
+                x = stays
+    nc = len(c_least)
+    selected = np.zeros(nc, dtype=bool)
+    beneath = np.zeros(nc, dtype=np.float64)             # the stability selected in the cluster's subtree
+    child_sum = np.zeros(nc, dtype=np.float64)
+    has_child = np.zeros(nc, dtype=bool)
+    for c in range(nc - 1, -1, -1):                      # a child was created after its parent
+        if (c > 0 or allow_single_cluster) and (not has_child[c] or c_stab[c] >= child_sum[c]):
+            selected[c], beneath[c] = True, c_stab[c]
+        else:
+            beneath[c] = child_sum[c]
+        if c_parent[c] >= 0:
+            child_sum[c_parent[c]] += beneath[c]
+            has_child[c_parent[c]] = True
+    owner = np.full(nc, -1, dtype=np.int64)              # the topmost selected cluster at or above c
+    for c in range(nc):
+        up = owner[c_parent[c]] if c_parent[c] >= 0 else -1
+        owner[c] = up if up >= 0 else (c if selected[c] else -1)
+    for c in range(nc):
+        selected[c] = owner[c] == c
+    for p in rows_in:
+        if deepest[p] >= 0 and owner[deepest[p]] >= 0:
+            label[p] = c_least[owner[deepest[p]]]
+    out.update(cluster=np.asarray(c_least, dtype=np.int64), parent=np.asarray(c_parent, dtype=np.int64),
+               birth=np.asarray(c_birth, dtype=np.float64), stability=np.asarray(c_stab, dtype=np.float64),
+               size=np.asarray(c_size, dtype=np.int64), selected=selected)
+    return out
+
+
+def hdbscan_table(result, names=None):
+    """One record per selected cluster of a :func:`hdbscan_clusters` result, ordered by label: ``label``, ``size`` (the rows that
+    carry the label), ``birth``, ``stability`` and ``members`` (indices ascending; the names where ``names`` is given, as is then
+    ``label``)."""
+    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    label = np.asarray(result["label"])
+    sel = np.flatnonzero(result["selected"])
+    recs = []
+    for c in sel[np.argsort(np.asarray(result["cluster"])[sel], kind="stable")]:
+        rows_of = np.flatnonzero(label == result["cluster"][c])
+        recs.append({"label": name(result["cluster"][c]), "size": len(rows_of), "birth": float(result["birth"][c]),
+                     "stability": float(result["stability"][c]), "members": [name(i) for i in rows_of]})
+    return recs
+
+
 KMEANS_FIELDS = ("label", "sim", "centroids", "size", "iterations", "converged", "init_rows")
 KMEANS_K_MAX = 65535
 KMEANS_MAX_ITER_MAX = 1000

@@ -641,7 +641,7 @@ int gnn_cluster_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, float thresh
  *             a border row goes to the cluster that reaches it first, there is no visiting order for the result to depend on.
  * min_points = 1: label is gnn_cluster's label.  min_points = 2: the core rows are the rows with an edge and carry gnn_cluster's labels,
  * the noise rows are its clusters of one, and there is no border row.
- * What it is not: not HDBSCAN - one (threshold, min_points), no hierarchy over thresholds; not approximate; no width other than
+ * What it is not: not HDBSCAN - one (threshold, min_points), no hierarchy over thresholds (gnn_density_tree is that); not approximate; no width other than
  * GNN_EMBED_DIM; not multi-GPU.
  * Two passes over the upper triangle (degrees first: who is core is known only when every edge is counted), no rounds.  Device memory,
  * persistent in the ctx and grow-only: the 2 KB of fragments + 1 B per row of the neighbour search (shared with it; gnn_density: + the
@@ -728,6 +728,42 @@ int gnn_linkage_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, int metric, 
 /* measurement only: with gnn_profile_enable on, the HIP-event milliseconds of every round (its six launches; the last one may have
  * added no edge) of the ctx's last gnn_linkage* call; *n_out = the rounds recorded, at most `capacity` of them are written. */
 int gnn_debug_linkage_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
+
+/* ---- density-aware linkage tree among encoder embeddings: mutual-reachability Boruvka ------------------------
+ * "Which rows belong together at every threshold, bridges and stragglers aside": the tree that answers the core-only form of
+ * gnn_density at every threshold at once, as gnn_linkage answers gnn_cluster - the input of HDBSCAN.  Rows, validity and metric are
+ * those of gnn_linkage; no forward pass runs and no other entry point's result changes.
+ *   core      core[i] of a valid row i: its similarity to its (min_points - 1)-th most similar partner - the row itself counts
+ *             towards min_points, as in gnn_density and scikit-learn's min_samples.  It is the last entry that is a number of row i
+ *             of the sim that the self-search gnn_neighbours(rows, NULL, k = min_points - 1, metric) returns, bit for bit: fewer
+ *             valid partners than that give the least similar partner there is, min_points == 1 gives +inf, an invalid row or a row
+ *             without a partner whose value is a number gives NaN.  gnn_neighbours forms (i -> j) and (j -> i) with the two cross
+ *             products in opposite order, so core[i] may differ in the last bit from the k-th largest of the pair values below: that
+ *             is accepted, core is what gnn_neighbours says.
+ *   value     w(i, j) = fminf(fminf(v, core[i]), core[j]) for i < j, both rows valid and v a number; v is gnn_linkage's value of the
+ *             pair.  A pair whose v is not a number is no edge.  With min_points == 1, w == v: a, b, sim, valid and rounds are
+ *             gnn_linkage's, bit for bit.
+ *   order, tree, rounds, exact: gnn_linkage's, over w.  Mutual reachability makes many pairs tie exactly; the strict order (value
+ *             descending, lo ascending, hi ascending) decides every one of them, so the tree is unique and bit-identical for every
+ *             split of the base.
+ *   outputs   a, b, sim, valid, *n_edges_host, *rounds_host as gnn_linkage's (sim = w), and core (f32 [n]).
+ *   ranges    gnn_linkage's, and 1 <= min_points <= 65 (the neighbour search stops at k = 64): GNN_ERR_ARG with the value and the
+ *             range in the message before anything is launched or written.
+ * Cutting the tree at t - the rows with core >= t, joined by the edges with sim >= t - gives the core rows of gnn_density at
+ * (t, min_points) and their labels wherever no pair value lies within rounding of t (core comes from the (i -> j) orientation,
+ * gnn_density counts the i < j one).  genomad_amd.sequence.hdbscan_clusters condenses the tree by levels of sim and selects clusters by
+ * excess of mass on the host.
+ * What it is: exact.  What it is not: not approximate; no width other than GNN_EMBED_DIM; not multi-GPU; not scikit-learn's handling
+ * of tied merges (the condensed tree here is defined by levels, so it does not depend on which spanning tree was found); no
+ * min_points above 65.
+ * Device memory, persistent in the ctx and grow-only: gnn_linkage's, 4 B per row of core and 12 B per row and neighbour of the
+ * self-search's lists.  Host and _dev forms and the synchronisation per round are gnn_linkage's. */
+int gnn_density_tree(gnn_ctx* ctx, const float* rows_host, int64_t n, int min_points, int metric, int64_t* a_host, int64_t* b_host,
+                     float* sim_host, float* core_host, uint8_t* valid_host, int64_t* n_edges_host, int64_t* rounds_host);
+int gnn_density_tree_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, int min_points, int metric, int64_t* a_host, int64_t* b_host,
+                         float* sim_host, float* core_host, uint8_t* valid_host, int64_t* n_edges_host, int64_t* rounds_host);
+/* measurement only: gnn_debug_linkage_round_ms for the ctx's last gnn_density_tree* call (the self-search is not part of a round) */
+int gnn_debug_density_tree_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
 
 /* ---- similarity graph among encoder embeddings: every pair above a threshold --------------------------------
  * "Which pairs are the edges": the thresholded similarity graph that gnn_cluster acts on and throws away, kept - every pair i < j of
