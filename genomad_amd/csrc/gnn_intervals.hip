@@ -6,7 +6,8 @@
 //     a contig's last window is shorter than 6000, by less than 2 * its advance), so the members of an interval are one range
 //     [w_lo, w_hi) of the global window order; the ranges of sorted, disjoint intervals are disjoint and ordered.
 //   - Per interval, over its KEPT members e_0, e_1, ... in window order: S = ((0 + e_0) + e_1) + ..., the same for the window scores,
-//     and U = ((0 + u_0) + u_1) + ... with u_i = e_i * rsqrt(sum_j e_i[j]^2) (a zero row when that sum is 0 or not finite).
+//     and U = ((0 + u_0) + u_1) + ... with u_i = e_i * rsqrt(sum_j e_i[j]^2) (a zero row when e_i has a non-finite element or is
+//     all zeros - the rows gnn_neighbours calls invalid under cosine; every other row has a unit row, whatever its scale).
 //     embedding = S / count, coherence = |U| / count; under GNN_STRAND_BOTH (S_f + S_r) / (2 count) and |U_f + U_r| / (2 count).
 //
 // Scheme.  A pass walks the window table in slabs, as every contig call does.  interval_fold_kernel runs one workgroup per interval
@@ -18,6 +19,7 @@
 // while the loads of the next batch are in flight.
 #include <cfloat>
 #include <cstring>
+#include <type_traits>
 
 #include "gnn_common.h"
 
@@ -25,12 +27,50 @@ namespace gnn {
 
 constexpr int IV_BATCH = 8;                      // rows in flight per step of a workgroup: 8 x 16 B per lane
 
+// The plain f32 squared norm of a row serves as it is when it lies in [IV_PLAIN_MIN, FLT_MAX].  Finite: no element is inf or NaN
+// and no partial sum has overflowed (the terms are non-negative, so every partial sum is at most the total).  At least 2^-116: a
+// product below FLT_MIN = 2^-126 is rounded to a multiple of 2^-149, off by at most 2^-150; 512 of them cost at most
+// 512 * 2^-150 = 2^-141 absolute (sums of such values are exact), which is 2^-25 of 2^-116 - half a rounding error, a quarter of
+// an ulp, beside the 11 roundings of the sum itself.  Every other row - a non-finite element, all zeros, squares that overflow
+// or vanish - goes the slow way of unit_scale below.
+constexpr float IV_PLAIN_MIN = 0x1p-116f;
+
+// f over the FOLD_THREADS values x of a workgroup, in every lane: a butterfly inside each wave, one exchange through `slot`, wave 0's
+// part first.  Every lane of the workgroup calls it (two barriers: the readers of the call before are done, the parts are written).
+template <class F>
+__device__ __forceinline__ float over_workgroup(float x, float* slot, int wave, int lane, F f) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) x = f(x, __shfl_xor(x, off));
+    __syncthreads();
+    if (lane == 0) slot[wave] = x;
+    __syncthreads();
+    return f(slot[0], slot[1]);
+}
+
+// The slow way to a unit row, the rule of nn_prepare_kernel (gnn_neighbours.hip): a row is valid iff every element is finite and
+// one is not zero.  v <- v * 2^-ex, which brings the largest |element| into [0.5, 1) - exact but for elements that fall below
+// 2^-149 of it, and those weigh nothing in a unit row - so the squared norm lies in [0.25, 512): it neither overflows nor vanishes.
+// Returns whether the row is valid and, if so, 1 / |v| of the scaled row in r.  Every lane of the workgroup calls it.
+__device__ __forceinline__ bool unit_scale(float4& v, float& r, float* slot, int wave, int lane) {
+    const float a = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));      // fmaxf drops a NaN: ask each element
+    const bool finite = fabsf(v.x) <= FLT_MAX && fabsf(v.y) <= FLT_MAX && fabsf(v.z) <= FLT_MAX && fabsf(v.w) <= FLT_MAX;
+    const float amax = over_workgroup(finite ? a : INFINITY, slot, wave, lane, [](float p, float q) { return fmaxf(p, q); });
+    if (!(amax > 0.f && amax <= FLT_MAX)) return false;      // uniform: amax is the same in every lane
+    int ex;
+    (void)frexpf(amax, &ex);
+    v.x = ldexpf(v.x, -ex), v.y = ldexpf(v.y, -ex), v.z = ldexpf(v.z, -ex), v.w = ldexpf(v.w, -ex);
+    const float ss = ((v.x * v.x + v.y * v.y) + v.z * v.z) + v.w * v.w;
+    r = rsqrtf(over_workgroup(ss, slot, wave, lane, [](float p, float q) { return p + q; }));
+    return true;
+}
+
 // The kept windows of slab rows [lo, hi) of interval iv0 + blockIdx.x -> its running sums.  Every pointer but the sums is relative
 // to the slab's first window: rows[m][HID], scores[m][3] (SCORES), and the N rule's inputs window_n[m] / counts[m] (RULE) or
 // kept[m].  FOLD_THREADS lanes x float4 = one row per load instruction.  The squared norm of a row: each lane sums its 4
 // squares, a butterfly over the 64 lanes of each wave (__shfl_xor, offsets 1 .. 32), one exchange through LDS between the two
-// waves, wave 0's part first - the same order every time, in every lane.
-// No branch inside a step: a row beyond the range is read as the range's last row and, like a masked one, enters as zeros (a sum
+// waves, wave 0's part first - the same order every time, in every lane.  A kept row whose sum is not in [IV_PLAIN_MIN, FLT_MAX]
+// is scaled by a power of two first (unit_scale) - a decision about the row alone, so no result depends on the slab.
+// No other branch inside a step: a row beyond the range is read as the range's last row and, like a masked one, enters as zeros (a sum
 // is never -0, so adding +0 leaves its bits alone) - the loads of a batch are independent and all in flight together.
 template <bool RULE, bool SCORES>
 __global__ __launch_bounds__(FOLD_THREADS) void interval_fold_kernel(const float* __restrict__ rows, const float* __restrict__ scores,
@@ -40,6 +80,7 @@ __global__ __launch_bounds__(FOLD_THREADS) void interval_fold_kernel(const float
                                                                      int64_t iv0, float* __restrict__ sum, float* __restrict__ unit,
                                                                      float* __restrict__ score_sum, int32_t* __restrict__ count) {
     __shared__ float part[2][2][IV_BATCH];       // [parity of the step][wave][row of the batch]
+    __shared__ float wide[2];                    // unit_scale's exchange, one value per wave
     const int64_t iv = iv0 + blockIdx.x;
     const int64_t lo = (w_lo[iv] > a ? w_lo[iv] : a) - a, hi = (w_hi[iv] < a + m ? w_hi[iv] : a + m) - a;
     if (lo >= hi) return;                        // an empty range between two touched ones: the whole workgroup leaves
@@ -83,20 +124,37 @@ __global__ __launch_bounds__(FOLD_THREADS) void interval_fold_kernel(const float
 #pragma unroll
             for (int j = 0; j < IV_BATCH; ++j) part[par][wave][j] = ss[j];
         __syncthreads();                         // one barrier per step: the next step writes the other parity
+        float n2[IV_BATCH];
+        bool odd = false;                        // a kept row of this batch needs the slow way (a NaN sum fails the comparison too)
 #pragma unroll
         for (int j = 0; j < IV_BATCH; ++j) {
-            const bool keep = cur.keep[j];
-            const float4 v = cur.v[j];
-            const float n2 = part[par][0][j] + part[par][1][j];
-            const bool ok = keep && n2 > 0.f && n2 <= FLT_MAX;       // the guard is the sum itself: 0, inf and NaN all fail
-            const float r = rsqrtf(n2);
-            s.x += keep ? v.x : 0.f, s.y += keep ? v.y : 0.f, s.z += keep ? v.z : 0.f, s.w += keep ? v.w : 0.f;
-            // scaled, then added: two roundings, no fused multiply-add
-            u.x += ok ? __fmul_rn(v.x, r) : 0.f, u.y += ok ? __fmul_rn(v.y, r) : 0.f;
-            u.z += ok ? __fmul_rn(v.z, r) : 0.f, u.w += ok ? __fmul_rn(v.w, r) : 0.f;
-            sc += keep ? cur.score[j] : 0.f;
-            k += keep;
+            n2[j] = part[par][0][j] + part[par][1][j];
+            odd |= cur.keep[j] && !(n2[j] >= IV_PLAIN_MIN && n2[j] <= FLT_MAX);
         }
+        // the batch, row after row; with_slow: the rows that need the slow way take it
+        auto add = [&](auto with_slow) {
+#pragma unroll
+            for (int j = 0; j < IV_BATCH; ++j) {
+                const bool keep = cur.keep[j];
+                const float4 v = cur.v[j];
+                float4 w = v;                                        // the row its unit row is made of
+                float r = rsqrtf(n2[j]);
+                bool ok = keep;
+                if constexpr (decltype(with_slow)::value)
+                    if (__builtin_amdgcn_readfirstlane(keep && !(n2[j] >= IV_PLAIN_MIN && n2[j] <= FLT_MAX)))
+                        ok = unit_scale(w, r, wide, wave, lane);
+                s.x += keep ? v.x : 0.f, s.y += keep ? v.y : 0.f, s.z += keep ? v.z : 0.f, s.w += keep ? v.w : 0.f;
+                // scaled, then added: two roundings, no fused multiply-add
+                u.x += ok ? __fmul_rn(w.x, r) : 0.f, u.y += ok ? __fmul_rn(w.y, r) : 0.f;
+                u.z += ok ? __fmul_rn(w.z, r) : 0.f, u.w += ok ? __fmul_rn(w.w, r) : 0.f;
+                sc += keep ? cur.score[j] : 0.f;
+                k += keep;
+            }
+        };
+        // keep and n2 are the same in every lane, and the compiler is told so: the whole workgroup takes a branch or none of it does,
+        // and no barrier is split.  One branch per step on the way every ordinary batch goes.
+        if (__builtin_amdgcn_readfirstlane(odd)) add(std::true_type{});
+        else add(std::false_type{});
     }
     *srow = s;
     *urow = u;

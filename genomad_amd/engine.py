@@ -919,13 +919,19 @@ class NNEngine:
         return self.embed_intervals(seq, offsets, regions.stride, regions.region_contig, regions.start, regions.end, strand, single_window,
                                     precision)
 
-    def fold_intervals(self, rows, kept, w_lo, w_hi, scores=None, rows_per_call=None):
+    def fold_intervals(self, rows, kept, w_lo, w_hi, scores=None, rows_per_call=None, rows_rev=None):
         """The building blocks (``gnn_interval_fold_dev`` + ``gnn_interval_finish_dev``) on rows of the caller's choosing: ``rows``
         (n, 512) float32, ``kept`` (n,) the mask, [w_lo[i], w_hi[i]) the member rows of interval i, ``scores`` (n, 3) or None.  The
-        rows are fed in slices of ``rows_per_call`` (None: all at once); no result depends on it.  Returns a dict of ``count``,
-        ``embedding``, ``coherence`` (float32) and ``scores`` as ``sequence.interval_embeddings``."""
+        rows are fed in slices of ``rows_per_call`` (None: all at once); no result depends on it.  ``rows_rev`` (n, 512) selects strand
+        mode ``both`` as ``gnn_embed_intervals`` runs it: the reverse rows are folded slice by slice into sums of their own (no scores,
+        a count that is ignored) and the finish adds the two; ``scores`` are then the combined window scores.  Returns a dict of
+        ``count``, ``embedding``, ``coherence`` (float32) and ``scores`` as ``sequence.interval_embeddings``."""
         rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, _lib.EMBED_DIM)
         n = len(rows)
+        if rows_rev is not None:
+            rows_rev = np.ascontiguousarray(rows_rev, dtype=np.float32).reshape(-1, _lib.EMBED_DIM)
+            if len(rows_rev) != n:
+                raise ValueError(f"rows_rev has {len(rows_rev)} rows, rows has {n}")
         kept = np.ascontiguousarray(np.asarray(kept).astype(bool), dtype=np.uint8)
         w_lo, w_hi = (np.ascontiguousarray(a, dtype=np.int64).reshape(-1) for a in (w_lo, w_hi))
         if len(kept) != n or len(w_lo) != len(w_hi):
@@ -942,22 +948,33 @@ class NNEngine:
         step = n if rows_per_call is None else max(1, int(rows_per_call))
         sizes = {"rows": rows.nbytes, "scores": n * 12, "sum": ni * 2048, "unit": ni * 2048, "score_sum": ni * 12, "count": ni * 4,
                  "coherence": ni * 4}
+        zeroed = ["sum", "unit", "score_sum", "count"]
+        if rows_rev is not None:         # the second strand: its own rows and sums, and the count the entry point insists on
+            sizes.update({"rows_rev": rows_rev.nbytes, "sum_rev": ni * 2048, "unit_rev": ni * 2048, "count_rev": ni * 4})
+            zeroed += ["sum_rev", "unit_rev", "count_rev"]
         bufs = {}
         try:
             for k, v in sizes.items():
                 bufs[k] = self.alloc(v)
             bufs["rows"].upload(rows)
+            if rows_rev is not None:
+                bufs["rows_rev"].upload(rows_rev)
             if scores is not None:
                 bufs["scores"].upload(scores)
-            for k in ("sum", "unit", "score_sum", "count"):
+            for k in zeroed:
                 bufs[k].upload(np.zeros(sizes[k], np.uint8))
             sc = bufs["scores"].ptr if scores is not None else None
             ssum = bufs["score_sum"].ptr if scores is not None else None
+            sum_rev, unit_rev = (bufs["sum_rev"].ptr, bufs["unit_rev"].ptr) if rows_rev is not None else (None, None)
             for a in range(0, n, step):
                 check(self.lib.gnn_interval_fold_dev(self.ctx, bufs["rows"].ptr, sc, a, min(step, n - a), kept.ctypes.data, w_lo.ctypes.data,
                                                      w_hi.ctypes.data, ni, bufs["sum"].ptr, bufs["unit"].ptr, ssum, bufs["count"].ptr))
-            check(self.lib.gnn_interval_finish_dev(self.ctx, bufs["sum"].ptr, bufs["unit"].ptr, None, None, ssum, bufs["count"].ptr, ni,
-                                                   bufs["sum"].ptr, bufs["coherence"].ptr, ssum))
+                if rows_rev is not None:
+                    check(self.lib.gnn_interval_fold_dev(self.ctx, bufs["rows_rev"].ptr, None, a, min(step, n - a), kept.ctypes.data,
+                                                         w_lo.ctypes.data, w_hi.ctypes.data, ni, sum_rev, unit_rev, None,
+                                                         bufs["count_rev"].ptr))
+            check(self.lib.gnn_interval_finish_dev(self.ctx, bufs["sum"].ptr, bufs["unit"].ptr, sum_rev, unit_rev, ssum, bufs["count"].ptr,
+                                                   ni, bufs["sum"].ptr, bufs["coherence"].ptr, ssum))
             self.sync()
             out["embedding"] = bufs["sum"].download((ni, _lib.EMBED_DIM), np.float32)
             out["count"] = bufs["count"].download((ni,), np.int32)

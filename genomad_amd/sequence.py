@@ -657,7 +657,8 @@ def interval_embeddings(rows, scores, kept, w_lo, w_hi, rows_rev=None):
     - ``embedding``: ((0 + e_0) + e_1) + ... in float32, divided once by float32(count); a zero row when count == 0;
     - ``scores``: the same sequential float32 sum and single divide over the members' scores (zeros when ``scores`` is None);
     - ``coherence`` float64 in [0, 1], the mean resultant length of the unit rows: u_i = e_i / sqrt(sum_j e_i[j]^2), a zero row
-      when that sum is 0 or not finite; coherence = |u_0 + u_1 + ...| / count, 0 when count == 0 - evaluated in float64.
+      when e_i has a non-finite element or is all zeros (in float64 the sum of squares of a finite float32 row neither overflows
+      nor vanishes: every other row has a unit row, whatever its scale); coherence = |u_0 + u_1 + ...| / count, 0 when count == 0 - evaluated in float64.
 
     ``rows_rev`` (the reverse windows' rows) selects strand mode ``both``: two independent sums, embedding = (S_f + S_r) /
     float32(2 count) and coherence = |U_f + U_r| / (2 count); ``scores`` are then the combined window scores

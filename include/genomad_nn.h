@@ -508,10 +508,13 @@ int gnn_debug_set_region_tile(gnn_ctx* ctx, int bins);
  *                          gnn_classify_contigs_embed; a zero row when count == 0.
  *               scores     [3] f32: the same sequential sum and single divide over the members' window scores of the strand mode.
  *               coherence  f32 in [0, 1], the mean resultant length of the members' unit rows: u_i = e_i / sqrt(sum_j e_i[j]^2), or a
- *                          zero row when that sum is 0 or not finite; U = ((0 + u_0) + u_1) + ...; coherence = |U| / count, 0 when
- *                          count == 0.  1: the members point one way; low: the mean averages unlike rows.  The device computes it in
- *                          f32 (a fixed reduction order per row, rsqrt); it agrees with a float64 evaluation of the definition to 1e-5
- *                          for intervals of up to 64 kept members, and grows by about 3e-8 per further member.
+ *                          zero row when e_i has a non-finite element or is all zeros - the rows gnn_neighbours calls invalid under
+ *                          cosine; every other row has a unit row whatever its scale, from all-subnormal to FLT_MAX, and coherence
+ *                          does not change when a row is multiplied by a power of two; U = ((0 + u_0) + u_1) + ...;
+ *                          coherence = |U| / count, 0 when count == 0.  1: the members point one way; low: the mean averages
+ *                          unlike rows.  The device computes it in f32 (a fixed reduction order per row, rsqrt); with n kept
+ *                          members it agrees with a float64 evaluation of the definition to (17 + (n + 1) / 2) * 2^-24, and to
+ *                          (18 + (n + 1) / 2) * 2^-24 under GNN_STRAND_BOTH: 3.0e-6 at n = 64, 6.1e-5 at n = 2000.
  *   strand      gnn_strand, as gnn_classify_contigs_strand.  REVERSE folds the reverse windows' rows and scores.  BOTH keeps two
  *               independent sums per interval: embedding = (S_f + S_r) / (2 count), coherence = |U_f + U_r| / (2 count), scores fold
  *               the combined window scores (f + r) * 0.5f.  Windows, membership, kept and count are the forward ones in every mode.
