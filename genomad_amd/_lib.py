@@ -150,6 +150,13 @@ SIGNATURES = {
     "gnn_match_count_dev": (_int, [_vp, _vp, _i64, _vp, _i64, C.c_float, _int, _vp, _vp]),
     "gnn_match_fill_dev": (_int, [_vp, _vp, _i64, _vp, _i64, C.c_float, _int, _vp, _vp, _i64]),
     "gnn_debug_match_pass_ms": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_mcl": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_mcl_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_mcl_matrix": (_int, [_vp, _i64, _int, _vp, _vp, _vp]),
+    "gnn_debug_mcl_lds": (_int, [_vp, _int]),
+    "gnn_debug_mcl_groups": (_int, [_vp, _int]),
+    "gnn_debug_mcl_ms": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_debug_mcl_overflow": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_kmeans": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_kmeans_dev": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_centroids": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp]),

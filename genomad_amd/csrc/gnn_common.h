@@ -339,6 +339,39 @@ struct VoteWorkspace {
     std::vector<float> pass_ms;                  // [labels, then per slab of queries: votes, finish]
 };
 
+// ---- Markov clusters (gnn_mcl.hip): persistent, grow-only.  Two matrices of 8 B per (row, select) and 4 B per row, the symmetric graph
+// (16 B per edge, 21 B per row), one uint64[n] accumulator and one int32[n] list per workgroup of the overflow pass (at most 2^27 cells
+// in all), 12 B per row of lists and union-find, two counters per iteration and, for gnn_mcl alone, the graph and its 29 B of results per row.
+struct MclWorkspace {
+    int lds_slots = 4096;                        // slots of the LDS table (gnn_debug_mcl_lds): 0 .. 4096; no result depends on it
+    int groups = 0;                              // workgroups of a pass (gnn_debug_mcl_groups); 0: two per CU; no result depends on it
+    DevBuf<int32_t> len[2], idx[2];              // the matrix, double buffered: [n], [n][select] rows ascending
+    DevBuf<uint32_t> val[2];                     // [n][select]: flow in units of 2^-30
+    DevBuf<uint8_t> ok;                          // [n]: the row takes part
+    DevBuf<int32_t> deg;                         // the symmetric graph: edges at the row, both ends counted
+    DevBuf<int64_t> soff;                        // [n + 1]: their exclusive prefix sums
+    DevBuf<unsigned long long> cursor;           // [n]: where the row's next entry goes
+    DevBuf<int32_t> sidx;                        // [soff[n]]: the partner
+    DevBuf<uint32_t> sq;                         // and the edge's integer weight
+    DevBuf<unsigned long long> count;            // [pass][changed columns, overflow columns], pass 0 the initial matrix; behind them the graph's flag
+    PinnedBuf<unsigned long long> h_count;       // where the host reads one of them, once per iteration
+    DevBuf<int32_t> ovf_list;                    // [n]: the columns of a pass whose rows did not fit the LDS table
+    DevBuf<unsigned long long> dense;            // [overflow workgroups][n]: all zero between columns
+    DevBuf<int32_t> touched;                     // [overflow workgroups][n]: the rows of the column at work
+    DevBuf<int32_t> parent, size;                // union-find over the final matrix; rows of the tree, at its root
+    bool have = false;                           // the ctx's last gnn_mcl* succeeded: gnn_mcl_matrix may read buffer `cur`
+    int64_t n = 0;
+    int select = 0, cur = 0;
+    DevBuf<int64_t> d_indptr;                    // gnn_mcl: the graph
+    DevBuf<int32_t> d_col;
+    DevBuf<float> d_sim;
+    DevBuf<uint8_t> d_valid;
+    DevBuf<int64_t> d_out;                       // gnn_mcl: [label | size | attractor | flow (u32) | is_attractor (u8)]
+    std::vector<RoundTimer> pending;             // profiling on: passes whose synchronise is still to come
+    std::vector<float> pass_ms;                  // profiling on: HIP-event time of the last call's [validate + symmetrise, initial matrix, then every iteration]
+    std::vector<int64_t> overflow;               // the last call's overflow columns: [initial matrix, then every iteration]
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -532,6 +565,7 @@ struct gnn_ctx {
     gnn::KMeansWorkspace km;                      // gnn_kmeans.hip
     gnn::PCAWorkspace pca;                        // gnn_pca.hip
     gnn::VoteWorkspace vt;                        // gnn_votes.hip
+    gnn::MclWorkspace mcl;                        // gnn_mcl.hip
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;

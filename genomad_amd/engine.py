@@ -391,6 +391,11 @@ class GraphResult(_Result):
         """``sequence.graph_table``: one record per edge - a, b, sim"""
         return _sequence.graph_table(self.indptr, self.col, self.sim, names)
 
+    def mcl(self, engine, **kw) -> "MCLResult":
+        """:meth:`NNEngine.mcl` of this graph and its rows' validity: Markov clusters, with ``inflation``, ``select``, ``precision``
+        and ``max_iter`` as there"""
+        return engine.mcl(self.indptr, self.col, self.sim, self.valid, **kw)
+
     @classmethod
     def build(cls, arrays, valid, threshold, metric):
         """from the (indptr, col, sim) of ``sequence.threshold_graph`` or the library, and the rows' validity"""
@@ -463,6 +468,35 @@ class MatchResult(_Result):
                    n_base=len(base_valid), n_edges=len(col), threshold=float(_sequence.cluster_threshold(threshold)), metric=str(metric))
 
 
+class MCLResult(_Result):
+    """What :meth:`NNEngine.mcl` returns (the definition is ``sequence.markov_clusters``), per row: ``label`` (int64: the smallest
+    index of the row's cluster; -1 for an invalid row), ``size`` (int64: rows of its cluster), ``attractor`` (int64: the row most of
+    its flow ends at; -1), ``flow`` (uint32: that share, in units of 2^-30) and ``is_attractor`` (bool: the row keeps flow to itself);
+    ``iterations``, ``converged``, ``changed`` (int64: the columns every iteration changed), ``n`` and the ``inflation``, ``select``,
+    ``precision`` it ran with.  :meth:`NNEngine.mcl_dev` leaves the per-row arrays on the device: they are None here."""
+    FIELDS = _sequence.MCL_FIELDS + ("iterations", "converged", "changed", "n", "inflation", "select", "precision")
+
+    def __init__(self, engine=None, serial=0, **kw):
+        super().__init__(**kw)
+        self._engine, self._serial, self._matrix = engine, serial, None
+
+    @property
+    def n_clusters(self) -> int:
+        return int(np.count_nonzero(self.label == np.arange(self.n)))
+
+    def matrix(self):
+        """The final matrix (``gnn_mcl_matrix``) as ``sequence.markov_clusters`` returns it: (length int64 (n,), idx int32, val
+        uint32) - column j owns the next ``length[j]`` entries, rows ascending.  It is read from the engine on the first call, which
+        must come before the engine's next Markov clustering (``GnnError`` otherwise)."""
+        if self._matrix is None:
+            self._matrix = self._engine._mcl_matrix(self.n, self.select, self._serial)
+        return self._matrix
+
+    def table(self, names=None):
+        """``sequence.mcl_table``: one record per cluster - label, size, members, attractors"""
+        return _sequence.mcl_table(self.label, self.size, self.is_attractor, names)
+
+
 class VoteResult(_Result):
     """What :meth:`NNEngine.vote` returns (the definition is ``sequence.class_votes``): per query row and class of a labelled base,
     over the voters - the valid base rows of the class whose cosine similarity reaches the threshold - ``count`` (int64: how many),
@@ -511,6 +545,7 @@ class NNEngine:
         self.ctx = ctx
         self.device = int(device)
         self._weights_keepalive = None
+        self._mcl_serial = 0                         # Markov clusterings so far: an MCLResult's matrix belongs to the last one
         if chunk:
             check(self.lib.gnn_set_chunk(self.ctx, int(chunk)))
         if weights is not None:
@@ -1221,6 +1256,94 @@ class NNEngine:
         """measurement only (``gnn_debug_vote_pass_ms``): with profiling enabled, the HIP-event milliseconds of the last
         :meth:`vote` / :meth:`vote_dev` call - [labels, then per slab of 262 144 queries: votes, finish]"""
         return self._debug_ms(self.lib.gnn_debug_vote_pass_ms)
+
+    # -- Markov clusters -----------------------------------------------------------------
+    @staticmethod
+    def _mcl_knobs(inflation, select, precision, max_iter):
+        """the four knobs as the library takes them; a ``ValueError`` for one out of range, before anything is allocated"""
+        return (_sequence.mcl_inflation(inflation), _sequence._whole(select, "select", 1, _sequence.MCL_SELECT_MAX),
+                _sequence._whole(precision, "precision", 1, _sequence.MCL_PRECISION_MAX),
+                _sequence._whole(max_iter, "max_iter", 0, _sequence.MCL_MAX_ITER_MAX))
+
+    def _mcl_call(self, fn, graph, n, nnz, knobs, outs, inflation):
+        changed = np.zeros(knobs[3], dtype=np.int64)
+        iterations, converged = C.c_int64(0), C.c_int(0)
+        self._mcl_serial += 1
+        check(fn(self.ctx, *graph, int(n), int(nnz), *knobs, *outs, changed.ctypes.data, C.addressof(iterations), C.addressof(converged)))
+        return dict(iterations=int(iterations.value), converged=bool(converged.value), changed=changed[:iterations.value], n=int(n),
+                    inflation=float(inflation), select=knobs[1], precision=knobs[2], engine=self, serial=self._mcl_serial)
+
+    def mcl(self, indptr, col, sim, valid=None, inflation=2.0, select=256, precision=10000, max_iter=100) -> MCLResult:
+        """Markov clusters of a similarity graph (``gnn_mcl``; the definition is ``sequence.markov_clusters``): van Dongen's MCL of
+        the upper-triangle CSR (``indptr``, ``col``, ``sim``) :meth:`graph` returns - flow-based families that survive a few bridge
+        edges, with one knob, the ``inflation`` (a multiple of 0.25 in [1.25, 8]; larger: smaller clusters).  In integers throughout:
+        every output equals the definition bit for bit.  ``valid``: bool per row (None: all); ``select`` (1..1024): the entries a
+        column keeps at the most; ``precision`` (1..2^20): an entry below 1 / precision of its column is cut; ``max_iter`` (0..10000).
+        ``ValueError`` for a knob out of range, ``GnnError`` for a graph that is no such CSR."""
+        knobs = self._mcl_knobs(inflation, select, precision, max_iter)
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        with np.errstate(over="ignore"):
+            sim = np.ascontiguousarray(sim, dtype=np.float32)
+        n = len(indptr) - 1
+        if indptr.ndim != 1 or n < 0 or col.ndim != 1 or sim.shape != col.shape:
+            raise ValueError("indptr (n + 1,), col (nnz,) and sim (nnz,) are required")
+        ok = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+        if ok is not None and ok.shape != (n,):
+            raise ValueError(f"valid must have one entry per row ({n})")
+        out = [np.empty(n, dtype=np.int64) for _ in range(3)] + [np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint8)]
+        kw = self._mcl_call(self.lib.gnn_mcl, (indptr.ctypes.data, col.ctypes.data, sim.ctypes.data, None if ok is None else ok.ctypes.data),
+                            n, len(col), knobs, [a.ctypes.data for a in out], inflation)
+        out[4] = out[4].astype(bool)
+        return MCLResult(**dict(zip(_sequence.MCL_FIELDS, out)), **kw)
+
+    def mcl_dev(self, indptr_ptr: int, col_ptr, sim_ptr, n: int, nnz: int, label_ptr: int, size_ptr: int, attractor_ptr: int, flow_ptr: int,
+                is_attractor_ptr: int, valid_ptr=None, inflation=2.0, select=256, precision=10000, max_iter=100) -> MCLResult:
+        """``gnn_mcl_dev``: device pointers in - indptr (n + 1 int64), col (nnz int32) and sim (nnz f32) exactly as
+        :meth:`graph_count_dev` and :meth:`graph_fill_dev` wrote them, valid (n uint8, or None) - and out (label, size, attractor: n
+        int64 each; flow: n uint32; is_attractor: n uint8); the engine's stream is synchronised once per iteration.  Returns an
+        :class:`MCLResult` without the per-row arrays."""
+        knobs = self._mcl_knobs(inflation, select, precision, max_iter)
+        return MCLResult(**self._mcl_call(self.lib.gnn_mcl_dev, (indptr_ptr, col_ptr, sim_ptr, valid_ptr), n, nnz, knobs,
+                                          [label_ptr, size_ptr, attractor_ptr, flow_ptr, is_attractor_ptr], inflation))
+
+    def _mcl_matrix(self, n, select, serial):
+        if serial != self._mcl_serial:
+            raise GnnError("the engine has run another Markov clustering since: its matrix is gone")
+        length = np.zeros(n, dtype=np.int32)
+        idx, val = np.zeros((n, select), dtype=np.int32), np.zeros((n, select), dtype=np.uint32)
+        check(self.lib.gnn_mcl_matrix(self.ctx, int(n), int(select), length.ctypes.data, idx.ctypes.data, val.ctypes.data))
+        keep = np.arange(select)[None, :] < length[:, None]
+        return length.astype(np.int64), idx[keep], val[keep]
+
+    def set_mcl_lds(self, slots: int) -> int:
+        """test aid (``gnn_debug_mcl_lds``): the slots (0..4096, the default) of the LDS table :meth:`mcl` sums a column's products in
+        - a column that needs more takes the overflow path, with 0 every column; -1 changes nothing.  Returns the value before the
+        call.  No result depends on it."""
+        before = self.lib.gnn_debug_mcl_lds(self.ctx, int(slots))
+        if before < 0:
+            check(before)
+        return int(before)
+
+    def set_mcl_groups(self, groups: int):
+        """test aid (``gnn_debug_mcl_groups``): the workgroups of a pass of :meth:`mcl` (0: the library's choice); no result depends
+        on it."""
+        check(self.lib.gnn_debug_mcl_groups(self.ctx, int(groups)))
+
+    def mcl_pass_ms(self):
+        """measurement only (``gnn_debug_mcl_ms``): with profiling enabled, the HIP-event milliseconds of the last :meth:`mcl` /
+        :meth:`mcl_dev` call - [validate and symmetrise, the initial matrix, then every iteration]"""
+        return self._debug_ms(self.lib.gnn_debug_mcl_ms)
+
+    def mcl_overflow(self) -> np.ndarray:
+        """measurement only (``gnn_debug_mcl_overflow``): the columns that took the overflow path in the last :meth:`mcl` /
+        :meth:`mcl_dev` call - int64 [the initial matrix, then every iteration]"""
+        n = C.c_int64(0)
+        check(self.lib.gnn_debug_mcl_overflow(self.ctx, None, 0, C.addressof(n)))
+        out = np.zeros(n.value, np.int64)
+        if n.value:
+            check(self.lib.gnn_debug_mcl_overflow(self.ctx, out.ctypes.data, n.value, C.addressof(n)))
+        return out
 
     # -- spherical k-means ---------------------------------------------------------------
     def kmeans(self, rows, k, init=None, max_iter=_sequence.KMEANS_MAX_ITER_DEFAULT) -> KMeansResult:

@@ -87,7 +87,7 @@ class Outputs:
         # written only when GENOMAD_AMD_REGION_EMBEDDINGS=1 (encoder embeddings per called region; no counterpart in the reference)
         self.nn_region_embeddings_output = d / f"{p}_nn_region_embeddings.npz"
         self.provirus_nn_region_embeddings_output = d / f"{p}_provirus_nn_region_embeddings.npz"
-        # written only when the analysis is requested (the eleven analyses of the per-contig embeddings, ANALYSES below: <stem>.npz and,
+        # written only when the analysis is requested (the twelve analyses of the per-contig embeddings, ANALYSES below: <stem>.npz and,
         # for all but the neighbours, <stem>.tsv; no counterpart in the reference)
         for stage in self._STAGE.values():
             for a in ANALYSES:
@@ -857,6 +857,62 @@ def write_graph(npz_path, tsv_path, names_key, names, res, strand="forward"):
     write_graph_tsv(tsv_path, names, res)
 
 
+MCL_SELECT_DEFAULT = 256
+
+
+def mcl_requested():
+    """GENOMAD_AMD_MCL=<a multiple of 0.25 in [1.25, 8]>: main() also writes the Markov clusters (MCL) of the contigs - the families the
+    flow through the similarity graph of GENOMAD_AMD_GRAPH settles in at that inflation (<prefix>_nn_mcl.npz and .tsv); unset or empty:
+    nothing changes (None).  It clusters the graph of GENOMAD_AMD_GRAPH=<threshold>, which must be set with it (main() refuses the one
+    without the other).  GENOMAD_AMD_MCL_SELECT=<integer in [1, 1024]> (default 256) is how many entries a column of the flow matrix
+    keeps at the most; it is an error without GENOMAD_AMD_MCL.  Any other value of either is an error.  Returns (inflation, the graph's
+    threshold as it is compared or None, select), or None."""
+    v = os.environ.get("GENOMAD_AMD_MCL", "").strip()
+    if not v:
+        _env_refines("GENOMAD_AMD_MCL_SELECT", "GENOMAD_AMD_MCL", "set the inflation of the Markov clusters or unset")
+        return None
+    try:
+        inflation = float(v)
+        sequence.mcl_inflation(inflation)
+    except ValueError:
+        raise ValueError(f"GENOMAD_AMD_MCL={v!r}: expected a multiple of 0.25 in [1.25, 8] (the inflation: the larger, the smaller the "
+                         "clusters)") from None
+    return inflation, graph_requested(), _env_int("GENOMAD_AMD_MCL_SELECT", 1, sequence.MCL_SELECT_MAX,
+                                                  "(the entries a column of the flow matrix keeps at the most)", MCL_SELECT_DEFAULT)
+
+
+def _run_mcl(eng, emb, request):
+    """the graph at the request's threshold, computed again, and its Markov clusters"""
+    inflation, threshold, select = request
+    g = eng.graph(emb, threshold, NEIGHBOUR_METRIC)
+    return eng.mcl(g.indptr, g.col, g.sim, g.valid, inflation=inflation, select=select), g.n_edges
+
+
+MCL_TSV_HEADER = "seq_name\tcluster\tcluster_size\tattractor\tflow\n"
+
+
+def write_mcl_tsv(path, names, res):
+    """One line per contig of an MCLResult: the name of its cluster's label contig, the cluster's size, the name of its attractor
+    (the contig most of its flow ends at) and that share of its flow; a contig without a valid embedding has NA, 0, NA, NA."""
+    with open(path, "w") as fout:
+        fout.write(MCL_TSV_HEADER)
+        for i, name in enumerate(names):
+            if res.label[i] < 0:
+                fout.write(f"{name}\tNA\t0\tNA\tNA\n")
+            else:
+                fout.write(f"{name}\t{names[res.label[i]]}\t{res.size[i]}\t{names[res.attractor[i]]}\t{int(res.flow[i]) / sequence.MCL_ONE:.6f}\n")
+
+
+def write_mcl(npz_path, tsv_path, names_key, names, res, request, strand="forward"):
+    """Both Markov-cluster files of a stage: the arrays of an MCLResult with the contig names and the request, and one line per contig."""
+    np.savez_compressed(npz_path, **{names_key: names, "inflation": np.float64(request[0]), "threshold": np.float64(request[1]),
+                                     "select": np.int64(request[2]), "precision": np.int64(res.precision), "metric": np.array(NEIGHBOUR_METRIC),
+                                     "label": res.label, "size": res.size, "attractor": res.attractor, "flow": res.flow,
+                                     "is_attractor": res.is_attractor, "iterations": np.int64(res.iterations),
+                                     "converged": np.bool_(res.converged), "changed": res.changed, **_strand_entry(strand)})
+    write_mcl_tsv(tsv_path, names, res)
+
+
 def match_requested():
     """GENOMAD_AMD_MATCH=<float in [-1, 1]>: main() also writes, for every contig, ALL the rows of the reference named by
     GENOMAD_AMD_MATCH_BASE whose encoder embedding has at least that cosine similarity to the contig's per-contig embedding of
@@ -1186,7 +1242,7 @@ def _encode(fasta_path, enc_dir: Path, window_id_path: Path, single_window: bool
 
 
 # ---- the analyses of the gathered per-contig embeddings ------------------------------------------------------------------------------
-# Eleven analyses follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
+# Twelve analyses follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
 #   name      the stem of its files, <prefix>_nn_<name>.npz and - where ``tsv`` - .tsv
 #   switch    the environment variable that requests it; ``request()`` reads it (and its companions): the request, or None
 #   needs     the middle clause of the message that refuses the switch without GENOMAD_AMD_EMBEDDINGS=1
@@ -1198,8 +1254,9 @@ def _encode(fasta_path, enc_dir: Path, window_id_path: Path, single_window: bool
 #   errors    the exceptions of ``run`` that end the run with status 1 and one line, "<switch>=<request>: <error>. <advice>"
 #   base      for an analysis against a reference (AnalysisBase): ``request()`` its path, ``load(path, strand)``, the ``hint`` of the
 #             message about a file that cannot be loaded, and ``same(npz, base)``: the file was computed against this very reference
-Analysis = namedtuple("Analysis", "name switch request needs keys title run write summary tsv errors advice base",
-                      defaults=(True, (), "", None))
+#   after     the name of the analysis whose switch it needs as well (its request then holds that one's too), or None
+Analysis = namedtuple("Analysis", "name switch request needs keys title run write summary tsv errors advice base after",
+                      defaults=(True, (), "", None, None))
 AnalysisBase = namedtuple("AnalysisBase", "request load hint same")
 _SIMILARITY = f"{NEIGHBOUR_METRIC} similarity of the encoder embeddings"
 
@@ -1247,6 +1304,15 @@ ANALYSES = (        # in the order they run, which is the order of the log lines
              lambda npz, tsv, key, names, res, strand, ctx: write_graph(npz, tsv, key, names, res, strand),
              lambda res, t, what, ctx: f"{_SIMILARITY} >= {t:g}: {res.n_edges} edges among {int(res.valid.sum())} {what}s",
              errors=ValueError, advice="Raise GENOMAD_AMD_GRAPH or unset it."),      # more edges than NNEngine.graph's cap: none was allocated
+    Analysis("mcl", "GENOMAD_AMD_MCL", mcl_requested,
+             "the flow runs on the similarity graph of the per-contig encoder embeddings", (("inflation", float), ("threshold", float), ("select", int)),
+             "Markov clusters of the {what}s",
+             lambda eng, emb, r, ctx: _run_mcl(eng, emb, r),
+             lambda npz, tsv, key, names, res, strand, ctx: write_mcl(npz, tsv, key, names, res[0], ctx.request, strand),
+             lambda res, r, what, ctx: (f"{_SIMILARITY} >= {r[1]:g}, {res[1]} edges, inflation {r[0]:g}, at most {r[2]} entries per column: "
+                                        f"{res[0].n_clusters} clusters in {res[0].iterations} iterations, "
+                                        f"{'converged' if res[0].converged else 'not converged'}"),
+             errors=(ValueError, GnnError), advice="Raise GENOMAD_AMD_GRAPH or unset GENOMAD_AMD_MCL.", after="graph"),      # the graph's cap on its edges
     Analysis("density", "GENOMAD_AMD_DENSITY", density_requested,
              "density clusters are formed among the per-contig encoder embeddings", (("threshold", float), ("min_points", int)),
              "Density clusters of the {what}s",
@@ -1366,6 +1432,10 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         requested = requests[a.name] is not None
         if a.base is None and requested and not embeddings:
             console.error(f"{a.switch} needs GENOMAD_AMD_EMBEDDINGS=1: {a.needs}. Set GENOMAD_AMD_EMBEDDINGS=1 or unset {a.switch}.")
+            sys.exit(1)
+        if requested and a.after is not None and requests[a.after] is None:
+            other = next(b.switch for b in ANALYSES if b.name == a.after)
+            console.error(f"{a.switch} needs {other}: {a.needs}. Set {other} or unset {a.switch}.")
             sys.exit(1)
         if a.base is not None and (requested != (base_paths[a.name] is not None) or (requested and not embeddings)):
             console.error(f"{a.switch} and {a.switch}_BASE need each other and GENOMAD_AMD_EMBEDDINGS=1: {a.needs}. Set all three or unset both.")

@@ -2037,6 +2037,266 @@ def pca_table(projection, valid, names=None):
     return [{"row": name(i), "pc": [float(x) for x in projection[i]] if valid[i] else None} for i in range(len(projection))]
 
 
+MCL_ONE = 1 << 30                  # a column's flow sums to (a little under) this
+MCL_W = 1 << 24                    # a similarity of 1 as an integer weight
+MCL_SIM_END = 64.0                 # similarities are below this: weights stay below 2^30
+MCL_SELECT_MAX = 1024
+MCL_PRECISION_MAX = 1 << 20
+MCL_MAX_ITER_MAX = 10000
+MCL_N_MAX = 1 << 24
+MCL_FIELDS = ("label", "size", "attractor", "flow", "is_attractor")
+
+
+def mcl_inflation(inflation) -> int:
+    """4 * ``inflation`` as the integer in [5, 32] the integer power is built from; anything else is a ``ValueError``: the power is
+    made of floor operations alone (products, square roots, fourth roots), so the inflation is a multiple of 0.25 in [1.25, 8]."""
+    try:
+        a = float(inflation) * 4.0
+        ok = not isinstance(inflation, (bool, np.bool_)) and a == int(a) and 5 <= a <= 32
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"inflation {inflation!r}: a multiple of 0.25 in [1.25, 8] is required")
+    return int(a)
+
+
+def _mcl_isqrt(x):
+    """floor(sqrt(x)) of uint64 x <= 2^60: the float64 estimate is off by one at the most, integer comparisons correct it"""
+    r = np.sqrt(x.astype(np.float64)).astype(np.uint64)
+    r = np.where(r * r > x, r - np.uint64(1), r)
+    return np.where((r + np.uint64(1)) * (r + np.uint64(1)) <= x, r + np.uint64(1), r)
+
+
+def _mcl_pow(u, a):
+    """u^(a / 4) in 2^-30 fixed point, u <= 2^30 (uint64): a // 4 products by u, one by its square root where a % 4 >= 2, one by its
+    fourth root where a is odd; every product is floored"""
+    one, sh = np.uint64(MCL_ONE), np.uint64(30)
+    h = _mcl_isqrt(u * one)
+    g = _mcl_isqrt(h * one)
+    r = np.full(u.shape, MCL_ONE, dtype=np.uint64)
+    for _ in range(a // 4):
+        r = (r * u) >> sh
+    if a % 4 >= 2:
+        r = (r * h) >> sh
+    if a % 2:
+        r = (r * g) >> sh
+    return r
+
+
+def _mcl_segments(cj):
+    """(first position of every run of the sorted ``cj``, the run every position belongs to)"""
+    first = np.flatnonzero(np.concatenate([[True], cj[1:] != cj[:-1]]))
+    return first, np.cumsum(np.concatenate([[0], cj[1:] != cj[:-1]]))
+
+
+def _mcl_prune(cj, ci, y, select, precision):
+    """``prune`` of every column at once: entries (column cj, row ci, y > 0) sorted by (cj, ci) -> (cj, ci, p) in the same order"""
+    if not len(cj):
+        return cj, ci, y
+    first, seg = _mcl_segments(cj)
+    keep = y * np.uint64(precision) >= np.add.reduceat(y, first)[seg]
+    cj, ci, y = cj[keep], ci[keep], y[keep]
+    order = np.lexsort((ci, ~y, cj))                      # column, then y descending, then row ascending
+    cj, ci, y = cj[order], ci[order], y[order]
+    first, seg = _mcl_segments(cj)
+    keep = np.arange(len(cj)) - first[seg] < select
+    cj, ci, y = cj[keep], ci[keep], y[keep]
+    order = np.lexsort((ci, cj))
+    cj, ci, y = cj[order], ci[order], y[order]
+    first, seg = _mcl_segments(cj)
+    p = y * np.uint64(MCL_ONE) // np.add.reduceat(y, first)[seg]
+    keep = p > 0
+    return cj[keep], ci[keep], p[keep]
+
+
+MCL_DENSE_ROWS = 2048              # up to this many rows the definition multiplies dense matrices; no result depends on it
+
+
+def _mcl_products(n, cj, ci, p):
+    """(key, e) of the matrix (cj, ci, p), sorted by (cj, ci): e_ij = sum_k p_ik * p_kj at key = j * n + i, keys ascending, zeros left
+    out.  Every sum is exact.  A small matrix is multiplied densely, in float64 on 15-bit halves of p <= 2^30: a product is below
+    2^31 and a sum of n <= 2048 of them below 2^53.  A large one entry by entry - (k, j) meets the entries (i, k) of column k -, the
+    products added in uint64 behind a sort."""
+    if n <= MCL_DENSE_ROWS:
+        hi, lo = np.zeros((n, n)), np.zeros((n, n))
+        hi[ci, cj], lo[ci, cj] = p >> np.uint64(15), p & np.uint64(0x7fff)
+        e = (((hi @ hi).astype(np.uint64) << np.uint64(30)) + ((hi @ lo + lo @ hi).astype(np.uint64) << np.uint64(15))
+             + (lo @ lo).astype(np.uint64)).T.ravel()              # [j][i]
+        key = np.flatnonzero(e)
+        return key, e[key]
+    length = np.bincount(cj, minlength=n)
+    ptr = np.concatenate([[0], np.cumsum(length)])
+    cnt = length[ci]
+    src = np.repeat(np.arange(len(ci)), cnt)
+    pos = ptr[ci[src]] + np.arange(len(src)) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    key = cj[src] * np.int64(n) + ci[pos]
+    prod = p[pos] * p[src]
+    order = np.argsort(key, kind="stable")
+    key, prod = key[order], prod[order]
+    first = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]]))
+    return key[first], np.add.reduceat(prod, first)
+
+
+def _mcl_expand(n, cj, ci, p, a, select, precision):
+    """One iteration on the matrix (cj, ci, p), sorted by (cj, ci): expansion, inflation, prune."""
+    if not len(cj):
+        return cj, ci, p
+    key, e = _mcl_products(n, cj, ci, p)
+    t = e >> np.uint64(30)
+    key, t = key[t > 0], t[t > 0]
+    if not len(key):
+        return key, key, t
+    cj, ci = key // n, key % n
+    first, seg = _mcl_segments(cj)
+    y = _mcl_pow(t * np.uint64(MCL_ONE) // np.maximum.reduceat(t, first)[seg], a)
+    return _mcl_prune(cj[y > 0], ci[y > 0], y[y > 0], select, precision)
+
+
+def _mcl_changed(n, old, new) -> int:
+    """the columns of the matrix ``new`` that differ from ``old``'s"""
+    lo, ln = np.bincount(old[0], minlength=n), np.bincount(new[0], minlength=n)
+    same = lo == ln
+    a, b = same[old[0]], same[new[0]]
+    diff = (old[1][a] != new[1][b]) | (old[2][a] != new[2][b])
+    return int(np.count_nonzero(~same)) + len(np.unique(new[0][b][diff]))
+
+
+def mcl_weights(indptr, col, sim, valid=None):
+    """The integer graph Markov clustering starts from: (n, a, b, q, valid) - the edges a < b that exist, with their weights q =
+    rint(float32(sim) * 2^24) > 0, and the rows' validity.  ``ValueError`` for a CSR that is none (indptr not rising from 0 to
+    len(col)), a column outside (row, n), a similarity that is not finite or >= 64, more than 2^24 rows, a ``valid`` of another length."""
+    indptr = np.asarray(indptr)
+    col = np.asarray(col)
+    if indptr.ndim != 1 or len(indptr) < 1 or indptr.dtype.kind not in "iu" or col.ndim != 1 or col.dtype.kind not in "iu":
+        raise ValueError("indptr (n + 1,) and col (nnz,) must be integer arrays")
+    indptr, col = indptr.astype(np.int64), col.astype(np.int64)
+    n = len(indptr) - 1
+    if n > MCL_N_MAX:
+        raise ValueError(f"{n} rows: at most 2^24 are supported")
+    s32 = np.asarray(sim)
+    if s32.ndim != 1 or s32.dtype.kind != "f" or len(s32) != len(col):
+        raise ValueError("sim must be a float array with one value per entry of col")
+    with np.errstate(over="ignore"):
+        s32 = s32.astype(np.float32)
+    if indptr[0] != 0 or indptr[-1] != len(col) or (np.diff(indptr) < 0).any():
+        raise ValueError("indptr does not rise from 0 to len(col)")
+    a = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+    if ((col <= a) | (col >= n)).any():
+        raise ValueError("col: a row's entries must lie in (row, n) - the upper triangle")
+    if not (np.isfinite(s32) & (s32 < MCL_SIM_END)).all():
+        raise ValueError("sim: every value must be finite and below 64")
+    ok = np.ones(n, dtype=bool) if valid is None else np.asarray(valid)
+    if ok.shape != (n,) or ok.dtype.kind != "b":
+        raise ValueError(f"valid must be a bool array of {n}")
+    q = np.rint(s32.astype(np.float64) * MCL_W).astype(np.int64)
+    keep = (q > 0) & ok[a] & ok[col]
+    return n, a[keep], col[keep], q[keep].astype(np.uint64), ok
+
+
+def mcl_initial(n, a, b, q, valid, select, precision):
+    """The initial matrix (cj, ci, p): node j's column is ``prune`` of its edges' weights - parallel edges count once, with the largest
+    of their weights - and its loop, the largest of them (2^24 for a node without an edge); an invalid node's column is empty."""
+    key = np.concatenate([a * np.int64(n) + b, b * np.int64(n) + a])
+    w = np.concatenate([q, q])
+    order = np.argsort(key, kind="stable")
+    key, w = key[order], w[order]
+    if len(key):
+        first = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]]))
+        key, w = key[first], np.maximum.reduceat(w, first)
+    loop = np.full(n, MCL_W, dtype=np.uint64)
+    if len(key):
+        first, _ = _mcl_segments(key // n)
+        loop[(key // n)[first]] = np.maximum.reduceat(w, first)
+    nodes = np.flatnonzero(valid).astype(np.int64)
+    key = np.concatenate([key, nodes * np.int64(n) + nodes])
+    w = np.concatenate([w, loop[nodes]])
+    order = np.argsort(key, kind="stable")
+    key, w = key[order], w[order]
+    return _mcl_prune(key // n, key % n, w, select, precision)
+
+
+def mcl_interpret(n, cj, ci, p, valid):
+    """(label, size, attractor, flow, is_attractor) of the matrix (cj, ci, p), sorted by (cj, ci)"""
+    label = np.arange(n, dtype=np.int64)
+    while True:                                           # ends: labels only fall, and stop at the component's smallest index
+        low = np.minimum(label[ci], label[cj])
+        nxt = label.copy()
+        np.minimum.at(nxt, ci, low)
+        np.minimum.at(nxt, cj, low)
+        nxt = nxt[nxt]
+        if np.array_equal(nxt, label):
+            break
+        label = nxt
+    label = np.where(valid, label, -1)
+    size = np.where(valid, np.bincount(label[valid], minlength=n)[np.maximum(label, 0)], 0).astype(np.int64)
+    attractor = np.full(n, -1, dtype=np.int64)
+    flow = np.zeros(n, dtype=np.uint32)
+    is_attractor = np.zeros(n, dtype=bool)
+    if len(cj):
+        order = np.lexsort((ci, ~p, cj))                  # a column's largest entry first, among equals the smallest row
+        first, _ = _mcl_segments(cj)
+        top = order[first]
+        attractor[cj[top]] = ci[top]
+        flow[cj[top]] = p[top].astype(np.uint32)
+        is_attractor[cj[ci == cj]] = True
+    return label, size, attractor, flow, is_attractor
+
+
+def markov_clusters(indptr, col, sim, valid=None, inflation=2.0, select=256, precision=10000, max_iter=100):
+    """Markov clustering (van Dongen's MCL) of a similarity graph, in integers throughout (the definition ``gnn_mcl`` computes on the
+    device).  The graph is an upper-triangle CSR as :func:`threshold_graph` returns it: row i owns
+    ``col[indptr[i]:indptr[i + 1]]``, its partners j > i in any order, with ``sim`` (cast to float32 first); ``valid`` is a bool per
+    row (None: all).  ONE = 2^30, W = 2^24; every quantity is a non-negative integer below 2^63.
+
+    Weights: q = rint(float32(sim) * W); an edge with q <= 0 or an invalid end does not exist; an edge sits at both its ends; parallel
+    edges count once, with the largest q; node j's loop is the largest q at j, W without an edge.
+    prune(entries (i, y > 0)): S = sum y; keep y * precision >= S; of more than ``select`` keep the first ``select`` under (y
+    descending, i ascending); S' = sum of the kept; p_i = y_i * ONE // S'; drop p = 0; ascending by i.
+    Initial column of a valid node: prune(its edges' q and its loop); an invalid node's column is empty.
+    One iteration, per column j from the previous matrix: e_i = sum_k p_ik * p_kj (exact); t_i = e_i >> 30, zeros dropped; u_i =
+    t_i * ONE // max t; y_i = pow(u_i), zeros dropped; prune.  pow for inflation = a / 4 (:func:`mcl_inflation`): mul(x, y) = x * y
+    >> 30, h = isqrt(u * ONE), g = isqrt(h * ONE); from ONE, a // 4 times mul by u, then by h if a % 4 >= 2, then by g if a is odd.
+    It stops behind the first iteration that changes no column (``converged``) or behind ``max_iter`` iterations.
+
+    Returns a dict: ``label`` (int64: the smallest index of the node's connected component in the graph {i, j : p_ij > 0} of the final
+    matrix; -1 for an invalid row), ``size`` (int64: nodes of its cluster), ``attractor`` (int64: the i with the largest p_ij in column
+    j, ties to the smaller i; -1 for an invalid row), ``flow`` (uint32: that p), ``is_attractor`` (bool: p_jj > 0), ``iterations``,
+    ``converged``, ``changed`` (int64: the columns every iteration changed) and the final matrix as ``length`` (int64 (n,)), ``idx``
+    (int32) and ``val`` (uint32): column j owns the next ``length[j]`` entries, rows ascending."""
+    a4 = mcl_inflation(inflation)
+    select = _whole(select, "select", 1, MCL_SELECT_MAX)
+    precision = _whole(precision, "precision", 1, MCL_PRECISION_MAX)
+    max_iter = _whole(max_iter, "max_iter", 0, MCL_MAX_ITER_MAX)
+    n, a, b, q, ok = mcl_weights(indptr, col, sim, valid)
+    m = mcl_initial(n, a, b, q, ok, select, precision)
+    changed, converged = [], False
+    while len(changed) < max_iter and not converged:
+        nxt = _mcl_expand(n, *m, a4, select, precision)
+        changed.append(_mcl_changed(n, m, nxt))
+        converged = changed[-1] == 0
+        m = nxt
+    out = dict(zip(MCL_FIELDS, mcl_interpret(n, *m, ok)))
+    out.update(iterations=len(changed), converged=converged, changed=np.asarray(changed, dtype=np.int64),
+               length=np.bincount(m[0], minlength=n).astype(np.int64), idx=m[1].astype(np.int32), val=m[2].astype(np.uint32))
+    return out
+
+
+def mcl_table(label, size, is_attractor, names=None):
+    """One record per cluster, ordered by label: ``label``, ``size``, ``members`` and ``attractors`` (the members with flow to
+    themselves), as indices in ascending order or - where ``names`` is given - as names"""
+    label = np.asarray(label, dtype=np.int64)
+    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    order = np.argsort(label, kind="stable")
+    order = order[label[order] >= 0]
+    bounds = np.flatnonzero(np.diff(label[order], prepend=-1)) if len(order) else []
+    out = []
+    for a, b in zip(bounds, list(bounds[1:]) + [len(order)]):
+        members = order[a:b]
+        out.append({"label": name(label[members[0]]), "size": int(size[members[0]]), "members": [name(i) for i in members],
+                    "attractors": [name(i) for i in members if is_attractor[i]]})
+    return out
+
+
 def prefix_of(input_path: Path) -> str:
     """nn_classification.py:106-108: stem, minus one more extension if the file is compressed."""
     prefix = Path(input_path).stem

@@ -809,6 +809,63 @@ int gnn_graph_fill_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, float thr
  * of them are written.  The prepare kernel and the fill are timed from outside, by gnn_profile_get around the calls. */
 int gnn_debug_graph_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
 
+/* ---- Markov clusters of a similarity graph: integer MCL on the device ---------------------------------------
+ * "Which families does the flow through the graph settle in": van Dongen's Markov clustering of the graph gnn_graph_* writes, with one
+ * knob, the inflation - and in integers throughout, so that every output equals the definition (sequence.markov_clusters) bit for bit,
+ * for any number of workgroups, any table size and any order they run in.  No forward pass runs and no other entry point's result changes.
+ *   graph     an upper-triangle CSR: indptr (int64 [n + 1]) rises from 0 to nnz, row i owns col[indptr[i] .. indptr[i + 1]), its
+ *             partners in (i, n) in ANY order, and sim[...] (f32, finite, < 64); valid (uint8 [n], or NULL: every row).  Exactly what
+ *             gnn_graph_fill_dev wrote is such a graph.  Anything else: GNN_ERR_ARG behind one O(nnz) kernel, before anything else runs,
+ *             the outputs untouched.
+ *   weights   ONE = 2^30, W = 2^24.  q = rint(sim * W); an edge with q <= 0 or an invalid end does not exist; an edge sits at both its
+ *             ends; parallel edges count once, with the largest q; node j's loop is the largest q at j, W without an edge.
+ *   prune     of entries (i, y > 0): S = sum y; keep y * precision >= S; of more than `select` the first `select` under (y descending,
+ *             i ascending); S' = sum of the kept; p_i = y_i * ONE / S' (floor); p = 0 dropped; ascending by i.
+ *   matrix    initial column of a valid node: prune(its edges' q and its loop) - pruned like any other; an invalid node's is empty.  An
+ *             iteration, per column j: e_i = sum_k p_ik p_kj (exact); t_i = e_i >> 30; u_i = t_i * ONE / max t; y_i = u_i ^ (a / 4)
+ *             for inflation_quarters = a in [5, 32] - from ONE, a / 4 floored products by u, one by h = isqrt(u * ONE) if a % 4 >= 2, one
+ *             by isqrt(h * ONE) if a is odd -; zeros dropped; prune.  It stops behind the first iteration that changes no column
+ *             (*converged_host = 1) or behind max_iter iterations; *iterations_host counts them, changed_host[it] (capacity max_iter)
+ *             the columns iteration it changed.  max_iter = 0: the initial matrix is interpreted.
+ *   outputs   label (int64: the smallest index of the node's connected component in the graph {i, j : p_ij > 0} of the final matrix;
+ *             -1 for an invalid row - gnn_cluster's rule), size (int64: nodes of its cluster; 0), attractor (int64: the i with the
+ *             largest p_ij in column j, ties to the smaller i; -1), flow (uint32: that p; 0), is_attractor (uint8: p_jj > 0).
+ *   ranges    0 <= n <= 2^24, nnz >= 0, inflation_quarters in [5, 32], select in [1, 1024], precision in [1, 2^20], max_iter in
+ *             [0, 10000]; GNN_ERR_ARG with the value and the range in the message - checked before the ctx is looked at.  n == 0:
+ *             nothing is launched; one iteration that changes nothing.
+ *   exact     the sums are 64-bit integer adds into a table keyed by row (in LDS; a column whose rows do not fit is finished with
+ *             an accumulator in global memory), the selection a radix select on integer keys, the square roots corrected by integer
+ *             comparisons: no float is added or compared, nothing depends on an order.
+ * What it is not: not mcl's floating-point arithmetic nor its recovery / scheme options; no overlapping clusters (a node between two
+ * attractor systems joins them, as the component rule says); select <= 1024; not multi-GPU.
+ * Device memory, persistent in the ctx and grow-only: 16 B per (row, select) of matrices, 16 B per edge and about 40 B per row of graph,
+ * lists and union-find, and at most 1.5 GB of overflow accumulators (gnn_mcl: + the graph and 29 B per row of results).
+ * gnn_mcl: host pointers, synchronous.  gnn_mcl_dev: device pointers in and out; changed, iterations and converged on the host; the
+ * ctx stream is synchronised once for the verdict on the graph and once per iteration (8 bytes). */
+int gnn_mcl(gnn_ctx* ctx, const int64_t* indptr_host, const int32_t* col_host, const float* sim_host, const uint8_t* valid_host_or_null,
+            int64_t n, int64_t nnz, int inflation_quarters, int select, int precision, int max_iter, int64_t* label_host,
+            int64_t* size_host, int64_t* attractor_host, uint32_t* flow_host, uint8_t* is_attractor_host, int64_t* changed_host,
+            int64_t* iterations_host, int* converged_host);
+int gnn_mcl_dev(gnn_ctx* ctx, const int64_t* indptr_dev, const int32_t* col_dev, const float* sim_dev, const uint8_t* valid_dev_or_null,
+                int64_t n, int64_t nnz, int inflation_quarters, int select, int precision, int max_iter, int64_t* label_dev,
+                int64_t* size_dev, int64_t* attractor_dev, uint32_t* flow_dev, uint8_t* is_attractor_dev, int64_t* changed_host,
+                int64_t* iterations_host, int* converged_host);
+/* The final matrix of the ctx's last gnn_mcl* call, which must have had this (n, select) and succeeded - GNN_ERR_STATE otherwise: length
+ * (int32 [n]), idx (int32 [n][select]) and val (uint32 [n][select]) on the host; column j owns the first length[j] cells of its row, rows
+ * ascending; the cells behind them are not written.  Synchronous. */
+int gnn_mcl_matrix(gnn_ctx* ctx, int64_t n, int select, int32_t* length_host, int32_t* idx_host, uint32_t* val_host);
+/* test aids; no result depends on them.  gnn_debug_mcl_lds: the slots of the LDS table, 0 .. 4096 (0: every column takes the overflow
+ * path; -1: leave it as it is); returns the value before the call (>= 0), or GNN_ERR_ARG.  gnn_debug_mcl_groups: the workgroups of a
+ * pass, 1 .. 65535 (0: the library's choice, two per CU). */
+int gnn_debug_mcl_lds(gnn_ctx* ctx, int slots);
+int gnn_debug_mcl_groups(gnn_ctx* ctx, int groups);
+/* measurement only.  gnn_debug_mcl_ms: with gnn_profile_enable on, the HIP-event milliseconds of the ctx's last gnn_mcl* call: [0]
+ * validate and symmetrise, [1] the initial matrix, then one figure per iteration; *n_out = the figures recorded, at most `capacity` are
+ * written.  gnn_debug_mcl_overflow: the columns each pass of that call pushed on the overflow list: [0] the initial matrix, then one
+ * count per iteration. */
+int gnn_debug_mcl_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
+int gnn_debug_mcl_overflow(gnn_ctx* ctx, int64_t* count_out, int64_t capacity, int64_t* n_out);
+
 /* ---- matches against a reference: the bipartite similarity graph query x base ------------------------------
  * "Which reference rows is every new row within the threshold of, all of them": every pair (i, j) of a valid query row i and a valid
  * base row j with sim(i, j) >= threshold and its similarity, as a CSR by query row.  The passes, the kernel, the workspace and the
