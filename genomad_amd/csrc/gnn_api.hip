@@ -1170,6 +1170,7 @@ int gnn_profile_enable(gnn_ctx* ctx, int on) {
 
 static int drain_profile(gnn_ctx* ctx) {
     GNN_HIP(hipStreamSynchronize(ctx->stream));
+    for (gnn::PassLog* log : ctx->pass_logs) log->settle();      // while the events they hold are still theirs
     for (auto& s : ctx->prof) {
         for (auto& pr : s.pending) {
             float ms = 0.f;

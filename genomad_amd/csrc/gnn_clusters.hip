@@ -21,7 +21,6 @@
 namespace gnn {
 namespace {
 
-constexpr int64_t N_MAX = (int64_t)1 << 31;      // rows are int32 in parent[]
 
 __global__ __launch_bounds__(256) void cl_init_kernel(int64_t n, int32_t* __restrict__ parent, int32_t* __restrict__ degree,
                                                       int32_t* __restrict__ size, unsigned long long* __restrict__ key) {
@@ -160,20 +159,10 @@ __global__ __launch_bounds__(256) void cl_summarise_kernel(int64_t n, const uint
 int check_cluster_args(const char* fn, const void* rows, int64_t n, float threshold, int metric, const void* label, const void* degree,
                        const void* size, const void* rep) {
     const std::string f(fn);
-    if (n < 0 || n >= N_MAX) {
-        set_error(f + ": " + std::to_string(n) + " rows is outside [0, 2^31)");
-        return GNN_ERR_ARG;
-    }
-    if (!std::isfinite(threshold)) {
-        set_error(f + ": threshold " + std::to_string(threshold) + " is outside (-inf, inf): a finite f32 is required");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_rows(f, n, "rows")) return rc;
+    if (int rc = nn_check_threshold(f, threshold)) return rc;
     if (int rc = nn_check_metric(f, metric)) return rc;
-    if (n > 0 && (!rows || !label || !degree || !size || !rep)) {
-        set_error("bad argument to " + f + ": the rows and the four outputs are required");
-        return GNN_ERR_ARG;
-    }
-    return GNN_OK;
+    return nn_check_required(f, n == 0 || (rows && label && degree && size && rep), "the rows and the four outputs");
 }
 
 // n > 0 rows on the device -> the four arrays on the device, enqueued on the ctx's stream
@@ -191,9 +180,7 @@ int cl_run(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int 
     if (!rc) rc = nn_tile_grid(ctx, "gnn_cluster", "rows", tiles, n, &split_rows, &splits);
     if (rc) return rc;
     ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-    const dim3 per_row((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(cl_init_kernel, per_row, dim3(256), 0, ctx->stream, n, c.parent.get(), c.degree.get(), c.size.get(), c.key.get());
-    GNN_HIP(hipGetLastError());
+    if ((rc = launch_1d(cl_init_kernel, n, ctx->stream, n, c.parent, c.degree, c.size, c.key))) return rc;
     ClusterArgs a;
     a.frag = w.bfrag.get();
     a.valid = w.bvalid.get();
@@ -203,15 +190,9 @@ int cl_run(gnn_ctx* ctx, const float* rows_dev, int64_t n, float threshold, int 
     a.threshold = threshold;
     a.parent = c.parent.get();
     a.degree = c.degree.get();
-    hipLaunchKernelGGL(cl_tile_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, ctx->stream, a);
-    GNN_HIP(hipGetLastError());
-    hipLaunchKernelGGL(cl_flatten_kernel, per_row, dim3(256), 0, ctx->stream, n, w.bvalid.get(), c.parent.get(), c.degree.get(), c.size.get(),
-                       c.key.get(), label);
-    GNN_HIP(hipGetLastError());
-    hipLaunchKernelGGL(cl_summarise_kernel, per_row, dim3(256), 0, ctx->stream, n, w.bvalid.get(), c.degree.get(), c.size.get(), c.key.get(),
-                       label, degree, size, rep);
-    GNN_HIP(hipGetLastError());
-    return GNN_OK;
+    if ((rc = launch_tiles(cl_tile_kernel, tiles, splits, ctx->stream, a))) return rc;
+    if ((rc = launch_1d(cl_flatten_kernel, n, ctx->stream, n, w.bvalid, c.parent, c.degree, c.size, c.key, label))) return rc;
+    return launch_1d(cl_summarise_kernel, n, ctx->stream, n, w.bvalid, c.degree, c.size, c.key, label, degree, size, rep);
 }
 
 }  // namespace
@@ -234,14 +215,12 @@ extern "C" int gnn_cluster(gnn_ctx* ctx, const float* rows_host, int64_t n, floa
     if (n == 0) return GNN_OK;
     NeighbourWorkspace& w = ctx->nn;
     ClusterWorkspace& c = ctx->cl;
-    int rc = nn_reserve(ctx, c.d_out, (size_t)4 * n);         // both buffers stand before the copy is enqueued
+    Landing land(c.d_out);
+    const int label = land.add(label_host, n), degree = land.add(degree_host, n), size = land.add(size_host, n), rep = land.add(rep_host, n);
+    int rc = land.reserve(ctx);                               // both buffers stand before the copy is enqueued
     if (!rc) rc = nn_upload_rows(ctx, rows_host, n);
-    if (rc) return rc;
-    int64_t* out = c.d_out;
-    if ((rc = cl_run(ctx, w.d_base, n, threshold, metric, out, out + n, out + 2 * n, out + 3 * n))) return rc;
-    int64_t* const host[4] = {label_host, degree_host, size_host, rep_host};
-    for (int i = 0; i < 4; ++i)
-        GNN_HIP(hipMemcpyAsync(host[i], out + (int64_t)i * n, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
-    return GNN_OK;
+    if (!rc)
+        rc = cl_run(ctx, w.d_base, n, threshold, metric, land.dev<int64_t>(label), land.dev<int64_t>(degree), land.dev<int64_t>(size),
+                    land.dev<int64_t>(rep));
+    return rc ? rc : land.copy_out(ctx);
 }

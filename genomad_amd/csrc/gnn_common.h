@@ -184,28 +184,26 @@ struct NeighbourWorkspace {
     DevBuf<float> psim;                          // partial lists [query of the slab][range][k]
     DevBuf<int32_t> pidx;
     DevBuf<float> d_base, d_query;               // gnn_neighbours: the base's rows and one slab's query rows
-    DevBuf<int64_t> d_idx;                       // gnn_neighbours: one slab's results
-    DevBuf<float> d_sim;
+    DevBuf<int64_t> d_out;                       // gnn_neighbours: one slab's [idx | sim (f32)], a Landing
 };
 
-// ---- the host-side prologue that the searches over encoder embeddings share (gnn_neighbours.hip, which also holds the prepare
-// kernel; gnn_clusters.hip, gnn_representatives.hip, gnn_linkage.hip).  `fn` is the name an error message carries.
-int nn_check_metric(const std::string& fn, int metric);      // GNN_OK, or GNN_ERR_ARG for a metric outside gnn_knn_metric
-float nn_metric_scale(int metric);                           // what a tile kernel multiplies its products by: 2^-16 for cosine, 1 for dot
-// rows_dev[n][GNN_EMBED_DIM] -> fragments and flags of round_up(n, 64) rows
-int nn_prepare(gnn_ctx* ctx, const float* rows_dev, int64_t n, int metric, DevBuf<uint4>& frag, DevBuf<uint8_t>& valid);
-// The tile grid of `tiles` row tiles over nb `noun` ("rows", "base rows"): base rows per workgroup - the debug value, or what gives
-// every CU two workgroups; a multiple of 32 - and the number of such ranges, or GNN_ERR_ARG for more than 65535 of them.
-int nn_tile_grid(const gnn_ctx* ctx, const std::string& fn, const char* noun, int64_t tiles, int64_t nb, int64_t* split_rows, int64_t* splits);
-int nn_upload_rows(gnn_ctx* ctx, const float* rows_host, int64_t n);      // n rows into ctx->nn.d_base, enqueued on the ctx's stream
-// The HIP-event time of one round of a search that synchronises once per round.  a, b: the events of the round's ProfScope (NULL:
-// profiling is off); file() appends the elapsed ms, after the round's synchronise.
-struct RoundTimer {
+// HIP-event timing of what is enqueued on ctx->stream while the scope lives, filed under kernel id `id` (gnn_profile_get); defined
+// behind gnn_ctx
+struct ProfScope {
+    gnn_ctx* ctx;
+    int id;
     hipEvent_t a = nullptr, b = nullptr;
-    void file(std::vector<float>& round_ms) const;
+    ProfScope(gnn_ctx* c, int kid);
+    ~ProfScope();
 };
-// the body of gnn_debug_representative_round_ms and gnn_debug_linkage_round_ms, behind their check_ctx
-int nn_round_ms_out(const char* fn, const std::vector<float>& round_ms, double* ms_out, int64_t capacity, int64_t* n_out);
+
+}  // namespace gnn
+
+// ---- the host side that the analyses over encoder embeddings share: the prologue (gnn_neighbours.hip, which also holds the prepare
+// kernel and the scan), PassLog, HostCounters, Landing
+#include "gnn_nn_host.h"
+
+namespace gnn {
 
 // ---- clusters (gnn_clusters.hip): persistent, grow-only.  The fragments and flags are NeighbourWorkspace's bfrag / bvalid (and d_base
 // for the host entry point); here 20 B per row and, for gnn_cluster alone, its 32 B of results.  Nothing is n x n.
@@ -213,7 +211,7 @@ struct ClusterWorkspace {
     DevBuf<int32_t> parent;                      // union-find: a link points to a smaller index, a root to itself
     DevBuf<int32_t> degree, size;                // edges at the row; rows of the tree, at its root
     DevBuf<unsigned long long> key;              // at the root: max of (degree << 32) | (2^32 - 1 - row) over the tree
-    DevBuf<int64_t> d_out;                       // gnn_cluster: [label | degree | size | rep]
+    DevBuf<int64_t> d_out;                       // gnn_cluster: [label | degree | size | rep], a Landing
 };
 
 // ---- density clusters (gnn_density.hip): persistent, grow-only.  The fragments and flags are NeighbourWorkspace's bfrag / bvalid (and
@@ -225,7 +223,7 @@ struct DensityWorkspace {
     DevBuf<unsigned long long> key;              // at a row that is not core: max of (image of the similarity << 32) | (2^32 - 1 - core row)
     DevBuf<uint8_t> core;                        // [round_up(n, 64)]: degree + 1 >= min_points at a valid row
     DevBuf<uint8_t> flag;                        // [tiles * splits]: the count pass saw an edge in the workgroup's pairs
-    DevBuf<int64_t> d_out;                       // gnn_density: [label | degree | size | anchor | sim (f32) | kind (u8)]
+    DevBuf<int64_t> d_out;                       // gnn_density: [label | degree | size | anchor | sim (f32) | kind (u8)], a Landing
 };
 
 // ---- representatives (gnn_representatives.hip): persistent, grow-only.  The fragments and flags are NeighbourWorkspace's bfrag /
@@ -237,10 +235,9 @@ struct RepresentativeWorkspace {
     DevBuf<unsigned long long> key;              // at a member: max of (image of the similarity << 32) | (2^32 - 1 - representative)
     DevBuf<unsigned long long> size;             // at a representative: the rows of its cluster
     DevBuf<uint8_t> row_live, col_live;          // per 64 rows: a FRESH or UNDECIDED row; per 32 rows: an UNDECIDED row
-    DevBuf<unsigned long long> count;            // [undecided rows, members]
-    PinnedBuf<unsigned long long> h_count;       // where the host reads one of them, once per round
-    DevBuf<int64_t> d_out;                       // gnn_representatives: [rep | size | sim (f32)]
-    std::vector<float> round_ms;                 // profiling on: HIP-event time of every round of the last call
+    HostCounters count;                          // [undecided rows, members]: the host reads one of them, once per round
+    DevBuf<int64_t> d_out;                       // gnn_representatives: [rep | size | sim (f32)], a Landing
+    PassLog rounds;                              // profiling on: HIP-event time of every round of the last call
 };
 
 // ---- single-linkage tree (gnn_linkage.hip): persistent, grow-only.  The fragments and flags are NeighbourWorkspace's bfrag / bvalid
@@ -253,14 +250,13 @@ struct LinkageWorkspace {
     DevBuf<int32_t> chi;                         // at a root: min of hi among the rows that match cbest
     DevBuf<int32_t> ea, eb;                      // the edges recorded so far, in no order: lo, hi
     DevBuf<unsigned> es;                         // and the image of their similarity
-    DevBuf<unsigned long long> count;            // edges recorded so far
-    PinnedBuf<unsigned long long> h_count;       // where the host reads it, once per round
-    std::vector<float> round_ms;                 // profiling on: HIP-event time of every round of the last call
+    HostCounters count;                          // edges recorded so far: the host reads it, once per round
+    PassLog rounds;                              // profiling on: HIP-event time of every round of the last call
     // the density tree (gnn_density_tree*) alone: 4 B per row, and 12 B per row and neighbour of the self-search's lists
     DevBuf<float> core;                          // the row's core similarity, NaN at an invalid row
     DevBuf<int64_t> nidx;                        // gnn_neighbours_dev's [n][min_points - 1] lists, of which only sim is read
     DevBuf<float> nsim;
-    std::vector<float> tree_round_ms;            // round_ms of the last gnn_density_tree* call
+    PassLog tree_rounds;                         // the rounds of the last gnn_density_tree* call
 };
 
 // ---- similarity graph (gnn_graph.hip): persistent, grow-only.  The fragments and flags are NeighbourWorkspace's bfrag / bvalid (and
@@ -282,10 +278,8 @@ struct GraphWorkspace {
     int64_t total = 0;                           // edges
     bool host_rows = false;                      // NeighbourWorkspace's d_base still holds the rows gnn_graph_count / gnn_match_count uploaded
     DevBuf<float> d_query;                       // gnn_match_count: the query's rows - the match's own, no other search writes here
-    DevBuf<int64_t> d_indptr;                    // gnn_graph_count: [n + 1]
-    DevBuf<int32_t> d_col;                       // gnn_graph_fill: [total]
-    DevBuf<float> d_sim;
-    std::vector<float> pass_ms;                  // profiling on: HIP-event time of the last count call's [count pass, scan]
+    DevBuf<int64_t> d_out;                       // a Landing: gnn_graph_count's indptr [n + 1]; gnn_graph_fill's [col (i32) | sim (f32)]
+    PassLog passes;                              // profiling on: HIP-event time of the last count call's [count pass, scan]
 };
 
 // ---- spherical k-means (gnn_kmeans.hip): persistent, grow-only.  The rows' fragments and flags are NeighbourWorkspace's bfrag / bvalid
@@ -301,11 +295,11 @@ struct KMeansWorkspace {
     DevBuf<unsigned long long> cnt;              // [k] members
     DevBuf<uint4> one;                           // farthest-first: the fragments of the last pick as a base of one row (63 zero rows)
     DevBuf<uint8_t> one_valid, picked;           // its flags [64]; per row: it is a pick
-    DevBuf<unsigned long long> count;            // [changed labels, valid rows, invalid init rows, bad labels, the farthest row's key]
-    PinnedBuf<unsigned long long> h_count;       // where the host reads them: once at the start and once per assignment
+    HostCounters count;                          // [changed labels, valid rows, invalid init rows, bad labels, the farthest row's key]:
+                                                 // the host reads them once at the start and once per assignment
     DevBuf<float> d_init;                        // gnn_kmeans: the init's rows
-    DevBuf<int64_t> d_out;                       // gnn_kmeans: [centroids (f32) | label | size | init_rows | sim (f32)]; gnn_centroids: [centroids | label | size]
-    std::vector<float> pass_ms;                  // profiling on: HIP-event time of the last call's [init, then per assignment: assign,
+    DevBuf<int64_t> d_out;                       // a Landing.  gnn_kmeans: [label | sim (f32) | size | init_rows | centroids (f32)]; gnn_centroids: [label | size | centroids]
+    PassLog passes;                              // profiling on: HIP-event time of the last call's [init, then per assignment: assign,
                                                  // and behind every assignment but the last: update, finish, prepare]
 };
 
@@ -316,11 +310,10 @@ struct PCAWorkspace {
     int64_t split = 0;                           // rows per workgroup of the Gram pass (gnn_debug_set_pca_split): a multiple of 256; 0: the library's choice; no result depends on it
     DevBuf<uint4> cfrag;                         // the components' fragments, as NeighbourWorkspace's
     DevBuf<uint8_t> cvalid;
-    DevBuf<int64_t> d_mom;                       // gnn_pca_moments: [G 512 x 512 | S 512 | n_valid]
     DevBuf<float> d_comp;                        // gnn_pca_project: [components 64 x 512 | off 64]
-    DevBuf<float> d_out;                         // gnn_pca_project: [n][ncomp]
-    std::vector<RoundTimer> pending;             // profiling on: the last call's passes, filed by gnn_debug_pca_pass_ms behind a synchronise
-    std::vector<float> pass_ms;                  // moments: [prepare, sums, gram, mirror]; project: [prepare rows, prepare components, project]
+    DevBuf<int64_t> d_out;                       // a Landing.  gnn_pca_moments: [G 512 x 512 | S 512 | n_valid]; gnn_pca_project: [n][ncomp] (f32)
+    PassLog passes;                              // profiling on: the last call's passes, which the _dev entry points leave pending (they do not
+                                                 // synchronise).  moments: [prepare, sums, gram, mirror]; project: [prepare rows, prepare components, project]
 };
 
 // ---- label transfer (gnn_votes.hip): persistent, grow-only.  The base's fragments and flags are NeighbourWorkspace's bfrag / bvalid (and
@@ -331,12 +324,11 @@ struct VoteWorkspace {
     int lds_c = 16;                              // up to this many classes a workgroup votes in LDS first (gnn_debug_set_vote_lds); no result depends on it
     DevBuf<int32_t> blabel;                      // [round_up(n_base, 64)]: the column's class; -1: unlabelled, invalid or padded
     DevBuf<unsigned long long> key;              // [query rows of the slab][classes]: max of (image of the similarity << 32) | (2^32 - 1 - base row), 0: none
-    DevBuf<unsigned long long> flag;             // a label outside [-1, n_classes)
-    PinnedBuf<unsigned long long> h_flag;        // where the host reads it, once per call
+    HostCounters flag;                           // a label outside [-1, n_classes): the host reads it, once per call
     DevBuf<int64_t> d_label;                     // gnn_vote: the labels
-    DevBuf<int64_t> d_out;                       // gnn_vote: one slab's [count | weight | nearest | nearest_sim (f32)]
-    std::vector<RoundTimer> pending;             // profiling on: the last call's passes, filed by gnn_debug_vote_pass_ms behind a synchronise
-    std::vector<float> pass_ms;                  // [labels, then per slab of queries: votes, finish]
+    DevBuf<int64_t> d_out;                       // gnn_vote: one slab's [count | weight | nearest | nearest_sim (f32)], a Landing
+    PassLog passes;                              // profiling on: the last call's [labels, then per slab of queries: votes, finish]; gnn_vote_dev
+                                                 // leaves its last slab's pending
 };
 
 // ---- Markov clusters (gnn_mcl.hip): persistent, grow-only.  Two matrices of 8 B per (row, select) and 4 B per row, the symmetric graph
@@ -353,8 +345,8 @@ struct MclWorkspace {
     DevBuf<unsigned long long> cursor;           // [n]: where the row's next entry goes
     DevBuf<int32_t> sidx;                        // [soff[n]]: the partner
     DevBuf<uint32_t> sq;                         // and the edge's integer weight
-    DevBuf<unsigned long long> count;            // [pass][changed columns, overflow columns], pass 0 the initial matrix; behind them the graph's flag
-    PinnedBuf<unsigned long long> h_count;       // where the host reads one of them, once per iteration
+    HostCounters count;                          // [pass][changed columns, overflow columns], pass 0 the initial matrix; behind them the graph's
+                                                 // flag.  The host reads one of them, once per iteration
     DevBuf<int32_t> ovf_list;                    // [n]: the columns of a pass whose rows did not fit the LDS table
     DevBuf<unsigned long long> dense;            // [overflow workgroups][n]: all zero between columns
     DevBuf<int32_t> touched;                     // [overflow workgroups][n]: the rows of the column at work
@@ -366,9 +358,8 @@ struct MclWorkspace {
     DevBuf<int32_t> d_col;
     DevBuf<float> d_sim;
     DevBuf<uint8_t> d_valid;
-    DevBuf<int64_t> d_out;                       // gnn_mcl: [label | size | attractor | flow (u32) | is_attractor (u8)]
-    std::vector<RoundTimer> pending;             // profiling on: passes whose synchronise is still to come
-    std::vector<float> pass_ms;                  // profiling on: HIP-event time of the last call's [validate + symmetrise, initial matrix, then every iteration]
+    DevBuf<int64_t> d_out;                       // gnn_mcl: [label | size | attractor | flow (u32) | is_attractor (u8)], a Landing
+    PassLog passes;                              // profiling on: HIP-event time of the last call's [validate + symmetrise, initial matrix, then every iteration]
     std::vector<int64_t> overflow;               // the last call's overflow columns: [initial matrix, then every iteration]
 };
 
@@ -493,6 +484,14 @@ static int launch_1d(void (*kernel)(P...), int64_t cells, hipStream_t stream, A&
     return GNN_OK;
 }
 
+// The tile grids of the analyses over encoder embeddings: (row tiles, base ranges) workgroups of 256 threads.
+template <typename... P, typename... A>
+static int launch_tiles(void (*kernel)(P...), int64_t tiles, int64_t splits, hipStream_t stream, A&&... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, stream, static_cast<P>(args)...);
+    GNN_HIP(hipGetLastError());
+    return GNN_OK;
+}
+
 // What an attribution call adds to a pass of classify_chunks (gnn_attrib.hip): device buffers, row i = window i of the pass.
 // contrib[n][2][attrib_bins(bin)][3]; bias[n][3] and logits[n][3] may be NULL.
 struct AttribOut {
@@ -566,6 +565,8 @@ struct gnn_ctx {
     gnn::PCAWorkspace pca;                        // gnn_pca.hip
     gnn::VoteWorkspace vt;                        // gnn_votes.hip
     gnn::MclWorkspace mcl;                        // gnn_mcl.hip
+    // every PassLog above: drain_profile settles them before an event they hold returns to event_pool
+    gnn::PassLog* const pass_logs[8] = {&rp.rounds, &lk.rounds, &lk.tree_rounds, &gr.passes, &km.passes, &pca.passes, &vt.passes, &mcl.passes};
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;
@@ -574,33 +575,27 @@ struct gnn_ctx {
 
 namespace gnn {
 
-// HIP-event timing of what is enqueued on ctx->stream while the scope lives, filed under kernel id `id` (gnn_profile_get)
-struct ProfScope {
-    gnn_ctx* ctx;
-    int id;
-    hipEvent_t a = nullptr, b = nullptr;
-    ProfScope(gnn_ctx* c, int kid) : ctx(c), id(kid) {
-        if (!ctx->profile) return;
-        auto take = [&]() {
-            hipEvent_t e = nullptr;
-            if (!ctx->event_pool.empty()) {
-                e = ctx->event_pool.back();
-                ctx->event_pool.pop_back();
-            } else if (hipEventCreate(&e) != hipSuccess) {
-                e = nullptr;
-            }
-            return e;
-        };
-        a = take();
-        b = take();
-        if (a) (void)hipEventRecord(a, ctx->stream);
-    }
-    ~ProfScope() {
-        if (!ctx->profile || !a || !b) return;
-        (void)hipEventRecord(b, ctx->stream);
-        ctx->prof[id].pending.emplace_back(a, b);
-    }
-};
+inline ProfScope::ProfScope(gnn_ctx* c, int kid) : ctx(c), id(kid) {
+    if (!ctx->profile) return;
+    auto take = [&]() {
+        hipEvent_t e = nullptr;
+        if (!ctx->event_pool.empty()) {
+            e = ctx->event_pool.back();
+            ctx->event_pool.pop_back();
+        } else if (hipEventCreate(&e) != hipSuccess) {
+            e = nullptr;
+        }
+        return e;
+    };
+    a = take();
+    b = take();
+    if (a) (void)hipEventRecord(a, ctx->stream);
+}
+inline ProfScope::~ProfScope() {
+    if (!ctx->profile || !a || !b) return;
+    (void)hipEventRecord(b, ctx->stream);
+    ctx->prof[id].pending.emplace_back(a, b);
+}
 
 // The one way a weight pack reaches the device: an allocation ctx->owned keeps until gnn_destroy, filled from the host.
 template <typename Tp>

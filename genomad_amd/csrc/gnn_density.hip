@@ -284,24 +284,14 @@ __global__ __launch_bounds__(256) void dn_summarise_kernel(int64_t n, const uint
 int check_density_args(const char* fn, const void* rows, int64_t n, float threshold, int64_t min_points, int metric, const void* label,
                        const void* degree, const void* size, const void* anchor, const void* sim, const void* kind) {
     const std::string f(fn);
-    if (n < 0 || n >= N_MAX) {
-        set_error(f + ": " + std::to_string(n) + " rows is outside [0, 2^31)");
-        return GNN_ERR_ARG;
-    }
-    if (!std::isfinite(threshold)) {
-        set_error(f + ": threshold " + std::to_string(threshold) + " is outside (-inf, inf): a finite f32 is required");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_rows(f, n, "rows")) return rc;
+    if (int rc = nn_check_threshold(f, threshold)) return rc;
     if (min_points < 1 || min_points >= N_MAX) {
         set_error(f + ": min_points " + std::to_string(min_points) + " is outside [1, 2^31)");
         return GNN_ERR_ARG;
     }
     if (int rc = nn_check_metric(f, metric)) return rc;
-    if (n > 0 && (!rows || !label || !degree || !size || !anchor || !sim || !kind)) {
-        set_error("bad argument to " + f + ": the rows and the six outputs are required");
-        return GNN_ERR_ARG;
-    }
-    return GNN_OK;
+    return nn_check_required(f, n == 0 || (rows && label && degree && size && anchor && sim && kind), "the rows and the six outputs");
 }
 
 // n > 0 rows on the device -> the six arrays on the device, enqueued on the ctx's stream
@@ -322,10 +312,7 @@ int dn_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, float
     if (!rc) rc = nn_reserve(ctx, d.flag, (size_t)flags);
     if (rc) return rc;
     ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-    const dim3 per_row((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(dn_init_kernel, dim3((unsigned)(((n > flags ? n : flags) + 255) / 256)), dim3(256), 0, ctx->stream, n, flags,
-                       d.parent.get(), d.degree.get(), d.size.get(), d.key.get(), d.flag.get());
-    GNN_HIP(hipGetLastError());
+    if ((rc = launch_1d(dn_init_kernel, std::max(n, flags), ctx->stream, n, flags, d.parent, d.degree, d.size, d.key, d.flag))) return rc;
     DensityArgs a;
     a.frag = w.bfrag.get();
     a.valid = w.bvalid.get();
@@ -339,21 +326,11 @@ int dn_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, float
     a.degree = d.degree.get();
     a.key = d.key.get();
     a.flag = d.flag.get();
-    const dim3 grid((unsigned)tiles, (unsigned)splits);
-    hipLaunchKernelGGL(dn_count_kernel, grid, dim3(256), 0, ctx->stream, a);
-    GNN_HIP(hipGetLastError());
-    hipLaunchKernelGGL(dn_mark_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, ctx->stream, n, padded, min_points,
-                       w.bvalid.get(), d.degree.get(), d.core.get());
-    GNN_HIP(hipGetLastError());
-    hipLaunchKernelGGL(dn_link_kernel, grid, dim3(256), 0, ctx->stream, a);
-    GNN_HIP(hipGetLastError());
-    hipLaunchKernelGGL(dn_flatten_kernel, per_row, dim3(256), 0, ctx->stream, n, w.bvalid.get(), d.core.get(), d.parent.get(), d.key.get(),
-                       d.size.get(), label, anchor, sim, kind);
-    GNN_HIP(hipGetLastError());
-    hipLaunchKernelGGL(dn_summarise_kernel, per_row, dim3(256), 0, ctx->stream, n, w.bvalid.get(), d.degree.get(), d.size.get(), label, degree,
-                       size);
-    GNN_HIP(hipGetLastError());
-    return GNN_OK;
+    if ((rc = launch_tiles(dn_count_kernel, tiles, splits, ctx->stream, a))) return rc;
+    if ((rc = launch_1d(dn_mark_kernel, padded, ctx->stream, n, padded, min_points, w.bvalid, d.degree, d.core))) return rc;
+    if ((rc = launch_tiles(dn_link_kernel, tiles, splits, ctx->stream, a))) return rc;
+    if ((rc = launch_1d(dn_flatten_kernel, n, ctx->stream, n, w.bvalid, d.core, d.parent, d.key, d.size, label, anchor, sim, kind))) return rc;
+    return launch_1d(dn_summarise_kernel, n, ctx->stream, n, w.bvalid, d.degree, d.size, label, degree, size);
 }
 
 }  // namespace
@@ -383,21 +360,13 @@ extern "C" int gnn_density(gnn_ctx* ctx, const float* rows_host, int64_t n, floa
     if (n == 0) return GNN_OK;
     NeighbourWorkspace& w = ctx->nn;
     DensityWorkspace& d = ctx->dn;
-    // [label | degree | size | anchor] int64, then sim (f32) and kind (u8) in the int64 words behind them
-    const int64_t sim_words = (n + 1) / 2, kind_words = (n + 7) / 8;
-    int rc = nn_reserve(ctx, d.d_out, (size_t)(4 * n + sim_words + kind_words));         // both buffers stand before the copy is enqueued
+    Landing land(d.d_out);
+    const int label = land.add(label_host, n), degree = land.add(degree_host, n), size = land.add(size_host, n), anchor = land.add(anchor_host, n),
+              sim = land.add(sim_host, n), kind = land.add(kind_host, n);
+    int rc = land.reserve(ctx);                               // both buffers stand before the copy is enqueued
     if (!rc) rc = nn_upload_rows(ctx, rows_host, n);
-    if (rc) return rc;
-    int64_t* out = d.d_out;
-    float* sim = reinterpret_cast<float*>(out + 4 * n);
-    uint8_t* kind = reinterpret_cast<uint8_t*>(out + 4 * n + sim_words);
-    if ((rc = dn_run(ctx, "gnn_density", w.d_base, n, threshold, min_points, metric, out, out + n, out + 2 * n, out + 3 * n, sim, kind)))
-        return rc;
-    int64_t* const host[4] = {label_host, degree_host, size_host, anchor_host};
-    for (int i = 0; i < 4; ++i)
-        GNN_HIP(hipMemcpyAsync(host[i], out + (int64_t)i * n, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(sim_host, sim, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(kind_host, kind, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
-    return GNN_OK;
+    if (!rc)
+        rc = dn_run(ctx, "gnn_density", w.d_base, n, threshold, min_points, metric, land.dev<int64_t>(label), land.dev<int64_t>(degree),
+                    land.dev<int64_t>(size), land.dev<int64_t>(anchor), land.dev<float>(sim), land.dev<uint8_t>(kind));
+    return rc ? rc : land.copy_out(ctx);
 }

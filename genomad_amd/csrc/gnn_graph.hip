@@ -35,8 +35,6 @@
 namespace gnn {
 namespace {
 
-constexpr int64_t N_MAX = (int64_t)1 << 31;      // columns are int32
-constexpr int SCAN_THREADS = 1024;               // the one block that scans the counters
 
 struct GraphArgs {
     const uint4* frag;         // round_up(n, 64) / 32 blocks: rows and columns alike; rectangle: the query's, the tile's rows only
@@ -181,33 +179,6 @@ __global__ __launch_bounds__(256) void gr_tile_kernel(GraphArgs a) {
     }
 }
 
-// Exclusive prefix sums of the m counters, and their total behind them: ONE block, thread i owns a run of counters (the scheme of
-// gnn_regions.hip's block_offsets_kernel).  Every loop ends: i grows towards e, or towards SCAN_THREADS.
-__global__ __launch_bounds__(SCAN_THREADS) void gr_scan_kernel(const int32_t* __restrict__ cnt, int64_t m, int64_t* __restrict__ off) {
-    __shared__ int64_t run[SCAN_THREADS];
-    const int64_t per = (m + SCAN_THREADS - 1) / SCAN_THREADS;
-    const int64_t a = min(m, (int64_t)threadIdx.x * per), e = min(m, a + per);
-    int64_t s = 0;
-    for (int64_t i = a; i < e; ++i) s += cnt[i];
-    run[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t acc = 0;
-        for (int i = 0; i < SCAN_THREADS; ++i) {
-            const int64_t v = run[i];
-            run[i] = acc;
-            acc += v;
-        }
-        off[m] = acc;
-    }
-    __syncthreads();
-    s = run[threadIdx.x];
-    for (int64_t i = a; i < e; ++i) {
-        off[i] = s;
-        s += cnt[i];
-    }
-}
-
 // indptr[i] = off[i * splits] for i <= n: a row's first part, and the total at n
 __global__ __launch_bounds__(256) void gr_indptr_kernel(int64_t n, int64_t splits, const int64_t* __restrict__ off, int64_t* __restrict__ indptr) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -217,32 +188,17 @@ __global__ __launch_bounds__(256) void gr_indptr_kernel(int64_t n, int64_t split
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 
-int check_threshold_metric(const std::string& f, float threshold, int metric) {
-    if (!std::isfinite(threshold)) {
-        set_error(f + ": threshold " + std::to_string(threshold) + " is outside (-inf, inf): a finite f32 is required");
-        return GNN_ERR_ARG;
-    }
+int check_graph_args(const std::string& f, int64_t n, float threshold, int metric) {
+    if (int rc = nn_check_rows(f, n, "rows")) return rc;
+    if (int rc = nn_check_threshold(f, threshold)) return rc;
     return nn_check_metric(f, metric);
 }
 
-int check_graph_args(const std::string& f, int64_t n, float threshold, int metric) {
-    if (n < 0 || n >= N_MAX) {
-        set_error(f + ": " + std::to_string(n) + " rows is outside [0, 2^31)");
-        return GNN_ERR_ARG;
-    }
-    return check_threshold_metric(f, threshold, metric);
-}
-
 int check_match_args(const std::string& f, int64_t nq, int64_t nb, float threshold, int metric) {
-    if (nq < 0 || nq >= N_MAX) {
-        set_error(f + ": n_query " + std::to_string(nq) + " is outside [0, 2^31)");
-        return GNN_ERR_ARG;
-    }
-    if (nb < 0 || nb >= N_MAX) {
-        set_error(f + ": n_base " + std::to_string(nb) + " is outside [0, 2^31)");
-        return GNN_ERR_ARG;
-    }
-    return check_threshold_metric(f, threshold, metric);
+    if (int rc = nn_check_rows(f, nq, "n_query")) return rc;
+    if (int rc = nn_check_rows(f, nb, "n_base")) return rc;
+    if (int rc = nn_check_threshold(f, threshold)) return rc;
+    return nn_check_metric(f, metric);
 }
 
 uint32_t bits_of(float x) {
@@ -291,11 +247,10 @@ int gr_count(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, con
     GraphWorkspace& g = ctx->gr;
     g.counted = false;
     g.host_rows = false;
-    g.pass_ms.clear();
+    g.passes.begin();
     g.rect = rect;
     g.n = n;
     g.nb = rect ? nb : n;
-    RoundTimer t_count, t_scan;
     int64_t total = 0;
     if (n == 0 || g.nb == 0) {             // an empty side launches nothing
         g.split_rows = g.splits = 0;
@@ -309,25 +264,21 @@ int gr_count(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, con
         if (!rc) rc = nn_reserve(ctx, g.off, (size_t)m + 1);
         if (rc) return rc;
         {
-            ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-            t_count = {prof.a, prof.b};
+            PassLog::Scope pass(ctx, g.passes);
             GNN_HIP(hipMemsetAsync(g.cnt.get(), 0, (size_t)m * sizeof(int32_t), ctx->stream));
-            void (*const kernel)(GraphArgs) = rect ? gr_tile_kernel<false, true> : gr_tile_kernel<false, false>;
-            hipLaunchKernelGGL(kernel, dim3((unsigned)tiles, (unsigned)g.splits), dim3(256), 0, ctx->stream, gr_args(ctx, threshold, metric));
-            GNN_HIP(hipGetLastError());
+            if ((rc = launch_tiles(rect ? gr_tile_kernel<false, true> : gr_tile_kernel<false, false>, tiles, g.splits, ctx->stream,
+                                   gr_args(ctx, threshold, metric))))
+                return rc;
         }
         {
-            ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-            t_scan = {prof.a, prof.b};
-            hipLaunchKernelGGL(gr_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, g.cnt.get(), m, g.off.get());
-            GNN_HIP(hipGetLastError());
-            if (int rc2 = launch_1d(gr_indptr_kernel, n + 1, ctx->stream, n, g.splits, g.off.get(), indptr_dev)) return rc2;
+            PassLog::Scope pass(ctx, g.passes);
+            if ((rc = nn_scan(ctx->stream, g.cnt, m, g.off, nullptr))) return rc;
+            if ((rc = launch_1d(gr_indptr_kernel, n + 1, ctx->stream, n, g.splits, g.off, indptr_dev))) return rc;
         }
         GNN_HIP(hipMemcpyAsync(&total, g.off.get() + m, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     }
     GNN_HIP(hipStreamSynchronize(ctx->stream));
-    t_count.file(g.pass_ms);               // behind the synchronise
-    t_scan.file(g.pass_ms);
+    g.passes.settle();
     g.threshold_bits = bits_of(threshold);
     g.metric = metric;
     g.total = total;
@@ -366,10 +317,7 @@ int gr_fill(gnn_ctx* ctx, const float* rows_dev, const float* base_dev, float th
     GraphArgs a = gr_args(ctx, threshold, metric);
     a.col = col_dev;
     a.sim = sim_dev;
-    void (*const kernel)(GraphArgs) = g.rect ? gr_tile_kernel<true, true> : gr_tile_kernel<true, false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((g.n + QT - 1) / QT), (unsigned)g.splits), dim3(256), 0, ctx->stream, a);
-    GNN_HIP(hipGetLastError());
-    return GNN_OK;
+    return launch_tiles(g.rect ? gr_tile_kernel<true, true> : gr_tile_kernel<true, false>, (g.n + QT - 1) / QT, g.splits, ctx->stream, a);
 }
 
 // the host fill of either kind, behind its checks: the edges land in the ctx's buffers, are copied out and waited for
@@ -377,18 +325,14 @@ int gr_fill_host(gnn_ctx* ctx, const char* fn, float threshold, int metric, int3
     GraphWorkspace& g = ctx->gr;
     const int64_t total = g.total;
     if (total == 0) return GNN_OK;
-    if (!col_host || !sim_host) {
-        set_error(std::string("bad argument to ") + fn + ": col and sim are required");
-        return GNN_ERR_ARG;
-    }
-    int rc = nn_reserve(ctx, g.d_col, (size_t)total);
-    if (!rc) rc = nn_reserve(ctx, g.d_sim, (size_t)total);
-    if (!rc) rc = gr_fill(ctx, g.rect ? g.d_query.get() : ctx->nn.d_base.get(), ctx->nn.d_base, threshold, metric, g.d_col, g.d_sim);
-    if (rc) return rc;
-    GNN_HIP(hipMemcpyAsync(col_host, g.d_col.get(), (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(sim_host, g.d_sim.get(), (size_t)total * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
-    return GNN_OK;
+    if (int rc = nn_check_required(fn, col_host && sim_host, "col and sim")) return rc;
+    Landing land(g.d_out);
+    const int col = land.add(col_host, total), sim = land.add(sim_host, total);
+    int rc = land.reserve(ctx);
+    if (!rc)
+        rc = gr_fill(ctx, g.rect ? g.d_query.get() : ctx->nn.d_base.get(), ctx->nn.d_base, threshold, metric, land.dev<int32_t>(col),
+                     land.dev<float>(sim));
+    return rc ? rc : land.copy_out(ctx);
 }
 
 }  // namespace
@@ -400,10 +344,7 @@ extern "C" int gnn_graph_count_dev(gnn_ctx* ctx, const float* rows_dev, int64_t 
                                    int64_t* nnz_host) {
     const char* const fn = "gnn_graph_count_dev";
     if (int rc = check_graph_args(fn, n, threshold, metric)) return rc;
-    if ((n > 0 && !rows_dev) || !indptr_dev || !nnz_host) {
-        set_error(std::string("bad argument to ") + fn + ": the rows, indptr and nnz are required");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_required(fn, (n == 0 || rows_dev) && indptr_dev && nnz_host, "the rows, indptr and nnz")) return rc;
     if (int rc = check_ctx(ctx)) return rc;
     return gr_count(ctx, fn, rows_dev, n, nullptr, 0, false, threshold, metric, indptr_dev, nnz_host);
 }
@@ -415,10 +356,7 @@ extern "C" int gnn_graph_fill_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n
     if (int rc = check_ctx(ctx)) return rc;
     if (int rc = gr_check_fill(ctx, fn, n, 0, false, threshold, metric, capacity, false)) return rc;
     if (ctx->gr.total == 0) return GNN_OK;
-    if (!rows_dev || !col_dev || !sim_dev) {
-        set_error(std::string("bad argument to ") + fn + ": the rows, col and sim are required");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_required(fn, rows_dev && col_dev && sim_dev, "the rows, col and sim")) return rc;
     return gr_fill(ctx, rows_dev, nullptr, threshold, metric, col_dev, sim_dev);
 }
 
@@ -426,26 +364,24 @@ extern "C" int gnn_graph_count(gnn_ctx* ctx, const float* rows_host, int64_t n, 
                                int64_t* nnz_host) {
     const char* const fn = "gnn_graph_count";
     if (int rc = check_graph_args(fn, n, threshold, metric)) return rc;
-    if ((n > 0 && !rows_host) || !indptr_host || !nnz_host) {
-        set_error(std::string("bad argument to ") + fn + ": the rows, indptr and nnz are required");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_required(fn, (n == 0 || rows_host) && indptr_host && nnz_host, "the rows, indptr and nnz")) return rc;
     if (int rc = check_ctx(ctx)) return rc;
     GraphWorkspace& g = ctx->gr;
     g.counted = false;
-    int rc = nn_reserve(ctx, g.d_indptr, (size_t)n + 1);         // both buffers stand before the copy is enqueued
+    Landing land(g.d_out);
+    land.add(indptr_host, n + 1);
+    int rc = land.reserve(ctx);                               // both buffers stand before the copy is enqueued
     if (!rc) rc = nn_upload_rows(ctx, rows_host, n);
-    if (!rc) rc = gr_count(ctx, fn, ctx->nn.d_base, n, nullptr, 0, false, threshold, metric, g.d_indptr, nnz_host);
+    if (!rc) rc = gr_count(ctx, fn, ctx->nn.d_base, n, nullptr, 0, false, threshold, metric, land.dev<int64_t>(0), nnz_host);
+    if (!rc) rc = land.copy_out(ctx);
     if (rc) return rc;
-    GNN_HIP(hipMemcpyAsync(indptr_host, g.d_indptr.get(), (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
     g.host_rows = true;
     return GNN_OK;
 }
 
 extern "C" int gnn_debug_graph_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
     if (int rc = check_ctx(ctx)) return rc;
-    return nn_round_ms_out("gnn_debug_graph_pass_ms", ctx->gr.pass_ms, ms_out, capacity, n_out);
+    return ctx->gr.passes.out(ctx, "gnn_debug_graph_pass_ms", ms_out, capacity, n_out);
 }
 
 extern "C" int gnn_graph_fill(gnn_ctx* ctx, int64_t n, float threshold, int metric, int32_t* col_host, float* sim_host, int64_t capacity) {
@@ -462,10 +398,9 @@ extern "C" int gnn_match_count_dev(gnn_ctx* ctx, const float* query_dev, int64_t
                                    float threshold, int metric, int64_t* indptr_dev, int64_t* nnz_host) {
     const char* const fn = "gnn_match_count_dev";
     if (int rc = check_match_args(fn, n_query, n_base, threshold, metric)) return rc;
-    if ((n_query > 0 && !query_dev) || (n_base > 0 && !base_dev) || !indptr_dev || !nnz_host) {
-        set_error(std::string("bad argument to ") + fn + ": the query, the base, indptr and nnz are required");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_required(fn, (n_query == 0 || query_dev) && (n_base == 0 || base_dev) && indptr_dev && nnz_host,
+                                   "the query, the base, indptr and nnz"))
+        return rc;
     if (int rc = check_ctx(ctx)) return rc;
     return gr_count(ctx, fn, query_dev, n_query, base_dev, n_base, true, threshold, metric, indptr_dev, nnz_host);
 }
@@ -477,10 +412,7 @@ extern "C" int gnn_match_fill_dev(gnn_ctx* ctx, const float* query_dev, int64_t 
     if (int rc = check_ctx(ctx)) return rc;
     if (int rc = gr_check_fill(ctx, fn, n_query, n_base, true, threshold, metric, capacity, false)) return rc;
     if (ctx->gr.total == 0) return GNN_OK;
-    if (!query_dev || !base_dev || !col_dev || !sim_dev) {
-        set_error(std::string("bad argument to ") + fn + ": the query, the base, col and sim are required");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_required(fn, query_dev && base_dev && col_dev && sim_dev, "the query, the base, col and sim")) return rc;
     return gr_fill(ctx, query_dev, base_dev, threshold, metric, col_dev, sim_dev);
 }
 
@@ -488,24 +420,24 @@ extern "C" int gnn_match_count(gnn_ctx* ctx, const float* query_host, int64_t n_
                                float threshold, int metric, int64_t* indptr_host, int64_t* nnz_host) {
     const char* const fn = "gnn_match_count";
     if (int rc = check_match_args(fn, n_query, n_base, threshold, metric)) return rc;
-    if ((n_query > 0 && !query_host) || (n_base > 0 && !base_host) || !indptr_host || !nnz_host) {
-        set_error(std::string("bad argument to ") + fn + ": the query, the base, indptr and nnz are required");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_required(fn, (n_query == 0 || query_host) && (n_base == 0 || base_host) && indptr_host && nnz_host,
+                                   "the query, the base, indptr and nnz"))
+        return rc;
     if (int rc = check_ctx(ctx)) return rc;
     GraphWorkspace& g = ctx->gr;
     g.counted = false;
     // every buffer stands before a copy is enqueued.  The query rows go into a buffer of the match's own: no other search writes it
-    int rc = nn_reserve(ctx, g.d_indptr, (size_t)n_query + 1);
+    Landing land(g.d_out);
+    land.add(indptr_host, n_query + 1);
+    int rc = land.reserve(ctx);
     if (!rc) rc = nn_reserve(ctx, g.d_query, (size_t)std::max<int64_t>(n_query, 1) * D);
     if (!rc) rc = nn_upload_rows(ctx, base_host, n_base);
     if (rc) return rc;
     if (n_query > 0)
         GNN_HIP(hipMemcpyAsync(g.d_query.get(), query_host, (size_t)n_query * D * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    rc = gr_count(ctx, fn, g.d_query, n_query, ctx->nn.d_base, n_base, true, threshold, metric, g.d_indptr, nnz_host);
+    rc = gr_count(ctx, fn, g.d_query, n_query, ctx->nn.d_base, n_base, true, threshold, metric, land.dev<int64_t>(0), nnz_host);
+    if (!rc) rc = land.copy_out(ctx);
     if (rc) return rc;
-    GNN_HIP(hipMemcpyAsync(indptr_host, g.d_indptr.get(), (size_t)(n_query + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
     g.host_rows = true;
     return GNN_OK;
 }
@@ -521,5 +453,5 @@ extern "C" int gnn_match_fill(gnn_ctx* ctx, int64_t n_query, int64_t n_base, flo
 
 extern "C" int gnn_debug_match_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
     if (int rc = check_ctx(ctx)) return rc;
-    return nn_round_ms_out("gnn_debug_match_pass_ms", ctx->gr.pass_ms, ms_out, capacity, n_out);
+    return ctx->gr.passes.out(ctx, "gnn_debug_match_pass_ms", ms_out, capacity, n_out);
 }

@@ -305,32 +305,15 @@ int check_kmeans_args(const char* fn, const void* rows, int64_t n, int k, int ma
         set_error(f + ": max_iter " + std::to_string(max_iter) + " is outside [0, " + std::to_string(MAX_ITER_MAX) + "]");
         return GNN_ERR_ARG;
     }
-    if (!cent || !size || !init_rows || !iterations || !converged || (n > 0 && (!rows || !label || !sim))) {
-        set_error("bad argument to " + f + ": the rows, the five outputs, iterations and converged are required");
-        return GNN_ERR_ARG;
-    }
-    return GNN_OK;
+    return nn_check_required(f, cent && size && init_rows && iterations && converged && (n == 0 || (rows && label && sim)),
+                             "the rows, the five outputs, iterations and converged");
 }
 
 int check_centroid_args(const char* fn, const void* rows, int64_t n, const void* label, int k, const void* cent, const void* size) {
     const std::string f(fn);
     if (int rc = check_rows(f, n)) return rc;
     if (int rc = check_k(f, k)) return rc;
-    if (!cent || !size || (n > 0 && (!rows || !label))) {
-        set_error("bad argument to " + f + ": the rows, the labels and both outputs are required");
-        return GNN_ERR_ARG;
-    }
-    return GNN_OK;
-}
-
-// `words` counters to the host, behind everything enqueued: a synchronise
-int km_read(gnn_ctx* ctx, int first, int words, unsigned long long* out) {
-    KMeansWorkspace& m = ctx->km;
-    GNN_HIP(hipMemcpyAsync(m.h_count.get(), m.count.get() + first, (size_t)words * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                           ctx->stream));
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < words; ++i) out[i] = m.h_count.get()[i];
-    return GNN_OK;
+    return nn_check_required(f, cent && size && (n == 0 || (rows && label)), "the rows, the labels and both outputs");
 }
 
 enum { C_CHANGED = 0, C_VALID = 1, C_BAD_INIT = 2, C_BAD_LABEL = 3, C_BEST = 4, C_WORDS = 5 };
@@ -340,18 +323,17 @@ int km_reserve(gnn_ctx* ctx, int64_t n, int64_t k) {
     int rc = nn_reserve(ctx, m.key, (size_t)std::max<int64_t>(n, 1));
     if (!rc) rc = nn_reserve(ctx, m.S, (size_t)k * D);
     if (!rc) rc = nn_reserve(ctx, m.cnt, (size_t)k);
-    if (!rc) rc = nn_reserve(ctx, m.count, (size_t)C_WORDS);
-    if (!rc) rc = m.h_count.reserve(C_WORDS);
+    if (!rc) rc = m.count.reserve(ctx, C_WORDS);
     return rc;
 }
 
-// The sums of `items` rows by group -> k rows of `cent`, enqueued.  The sums and counts are cleared here.
+// The sums of `items` rows by group -> k rows of `cent`, enqueued.  The sums and counts are cleared here.  log: where the two passes
+// (update, finish) are timed, or NULL.
 int km_update(gnn_ctx* ctx, const uint4* frag, const uint8_t* valid, int64_t items, const int64_t* pick, const int64_t* label, int64_t k,
-              int zero_empty, float* cent, RoundTimer* t_update, RoundTimer* t_finish) {
+              int zero_empty, float* cent, PassLog* log) {
     KMeansWorkspace& m = ctx->km;
     {
-        ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-        if (t_update) *t_update = {prof.a, prof.b};
+        PassLog::Scope pass(ctx, log);
         GNN_HIP(hipMemsetAsync(m.S.get(), 0, (size_t)k * D * sizeof(unsigned long long), ctx->stream));
         GNN_HIP(hipMemsetAsync(m.cnt.get(), 0, (size_t)k * sizeof(unsigned long long), ctx->stream));
         if (items > 0) {
@@ -377,8 +359,7 @@ int km_update(gnn_ctx* ctx, const uint4* frag, const uint8_t* valid, int64_t ite
             GNN_HIP(hipGetLastError());
         }
     }
-    ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-    if (t_finish) *t_finish = {prof.a, prof.b};
+    PassLog::Scope pass(ctx, log);
     hipLaunchKernelGGL(km_finish_kernel, dim3((unsigned)k), dim3(64), 0, ctx->stream, m.S.get(), m.cnt.get(), zero_empty, cent);
     GNN_HIP(hipGetLastError());
     return GNN_OK;
@@ -400,9 +381,7 @@ int km_assign(gnn_ctx* ctx, const char* fn, int64_t n, const uint4* cfrag, const
     a.split_rows = split_rows;
     a.scale = nn_metric_scale(GNN_KNN_COSINE);
     a.key = ctx->km.key.get();
-    hipLaunchKernelGGL(km_assign_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, ctx->stream, a);
-    GNN_HIP(hipGetLastError());
-    return GNN_OK;
+    return launch_tiles(km_assign_kernel, tiles, splits, ctx->stream, a);
 }
 
 // n >= 0 rows on the device -> the five arrays on the device, iterations and converged on the host.  The ctx's stream is synchronised
@@ -412,19 +391,19 @@ int km_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int k
     const std::string f(fn);
     NeighbourWorkspace& w = ctx->nn;
     KMeansWorkspace& m = ctx->km;
-    m.pass_ms.clear();
+    m.passes.begin();
     int rc = nn_prepare(ctx, rows_dev, n, GNN_KNN_COSINE, w.bfrag, w.bvalid);
     if (!rc) rc = km_reserve(ctx, n, k);
     if (!rc && init_dev) rc = nn_prepare(ctx, init_dev, k, GNN_KNN_COSINE, m.cfrag, m.cvalid);
+    if (!rc) rc = m.count.zero(ctx, 0, C_WORDS);
     if (rc) return rc;
-    GNN_HIP(hipMemsetAsync(m.count.get(), 0, C_WORDS * sizeof(unsigned long long), ctx->stream));
     const int64_t cells = std::max<int64_t>(n, init_dev ? k : 0);
     if (cells > 0)
         if ((rc = launch_1d(km_census_kernel, cells, ctx->stream, n, w.bvalid.get(), (int64_t)(init_dev ? k : 0), m.cvalid.get(),
-                            m.count.get() + C_VALID)))
+                            m.count.dev() + C_VALID)))
             return rc;
     unsigned long long census[2] = {0, 0};
-    if ((rc = km_read(ctx, C_VALID, 2, census))) return rc;
+    if ((rc = m.count.read(ctx, C_VALID, 2, census))) return rc;
     if ((unsigned long long)k > census[0]) {
         set_error(f + ": k " + std::to_string(k) + " is more than the " + std::to_string(census[0]) + " valid rows of " + std::to_string(n));
         return GNN_ERR_ARG;
@@ -433,71 +412,59 @@ int km_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int k
         set_error(f + ": " + std::to_string(census[1]) + " of the " + std::to_string(k) + " init rows are not valid (finite, norm > 0)");
         return GNN_ERR_ARG;
     }
-    std::vector<RoundTimer> timers;            // in the order they are filed, each behind a later synchronise
-    RoundTimer t_init, t_update, t_finish, t_prepare;
+    // every pass is settled behind a later synchronise: the next assignment's read
     if (init_dev) {
         // the init's rows, each a group of its own: the centroids are their unit rows by the update's own arithmetic
-        ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-        t_init = {prof.a, prof.b};
+        PassLog::Scope init(ctx, m.passes);
         if ((rc = launch_1d(km_fill_kernel, k, ctx->stream, (int64_t)k, (int64_t)-1, init_rows))) return rc;
-        if ((rc = km_update(ctx, m.cfrag.get(), m.cvalid.get(), k, nullptr, nullptr, k, 0, cent, nullptr, nullptr))) return rc;
+        if ((rc = km_update(ctx, m.cfrag.get(), m.cvalid.get(), k, nullptr, nullptr, k, 0, cent, nullptr))) return rc;
     } else {
         if ((rc = nn_reserve(ctx, m.one, (size_t)(2 * BLK_U4)))) return rc;
         if ((rc = nn_reserve(ctx, m.one_valid, (size_t)QT))) return rc;
         if ((rc = nn_reserve(ctx, m.picked, (size_t)n))) return rc;
-        ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-        t_init = {prof.a, prof.b};
+        PassLog::Scope init(ctx, m.passes);
         GNN_HIP(hipMemsetAsync(m.one.get(), 0, (size_t)(2 * BLK_U4) * sizeof(uint4), ctx->stream));
         GNN_HIP(hipMemsetAsync(m.one_valid.get(), 0, (size_t)QT, ctx->stream));
         GNN_HIP(hipMemsetAsync(m.one_valid.get(), 1, 1, ctx->stream));
         GNN_HIP(hipMemsetAsync(m.picked.get(), 0, (size_t)n, ctx->stream));
         GNN_HIP(hipMemsetAsync(m.key.get(), 0, (size_t)n * sizeof(unsigned long long), ctx->stream));
-        GNN_HIP(hipMemsetAsync(m.count.get() + C_BEST, 0xff, sizeof(unsigned long long), ctx->stream));
+        GNN_HIP(hipMemsetAsync(m.count.dev() + C_BEST, 0xff, sizeof(unsigned long long), ctx->stream));
         // Ends: k picks.  No pick waits for the host: the chosen row's fragments move on the device.
         for (int64_t j = 0; j < k; ++j) {
-            if ((rc = launch_1d(km_far_kernel, n, ctx->stream, n, w.bvalid.get(), m.picked.get(), m.key.get(), m.count.get() + C_BEST))) return rc;
-            hipLaunchKernelGGL(km_pick_kernel, dim3(1), dim3(64), 0, ctx->stream, w.bfrag.get(), m.count.get() + C_BEST, j, init_rows,
+            if ((rc = launch_1d(km_far_kernel, n, ctx->stream, n, w.bvalid.get(), m.picked.get(), m.key.get(), m.count.dev() + C_BEST))) return rc;
+            hipLaunchKernelGGL(km_pick_kernel, dim3(1), dim3(64), 0, ctx->stream, w.bfrag.get(), m.count.dev() + C_BEST, j, init_rows,
                                m.picked.get(), m.one.get());
             GNN_HIP(hipGetLastError());
             if (j + 1 < k && (rc = km_assign(ctx, fn, n, m.one.get(), m.one_valid.get(), 1, (unsigned)j))) return rc;
         }
-        if ((rc = km_update(ctx, w.bfrag.get(), w.bvalid.get(), k, init_rows, nullptr, k, 0, cent, nullptr, nullptr))) return rc;
+        if ((rc = km_update(ctx, w.bfrag.get(), w.bvalid.get(), k, init_rows, nullptr, k, 0, cent, nullptr))) return rc;
     }
     if ((rc = nn_prepare(ctx, cent, k, GNN_KNN_COSINE, m.cfrag, m.cvalid))) return rc;
     GNN_HIP(hipMemsetAsync(m.key.get(), 0, (size_t)n * sizeof(unsigned long long), ctx->stream));
     if ((rc = launch_1d(km_fill_kernel, n, ctx->stream, n, (int64_t)-2, label))) return rc;       // no row has the label -2: the first assignment changes all
-    timers.push_back(t_init);
     // One assignment per pass.  Ends: `iterations` grows by one per pass and the loop leaves at max_iter <= 1000 at the latest.
     int64_t iterations = 0;
     bool converged = false;
     for (;;) {
-        RoundTimer t_assign;
         {
-            ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-            t_assign = {prof.a, prof.b};
-            GNN_HIP(hipMemsetAsync(m.count.get() + C_CHANGED, 0, sizeof(unsigned long long), ctx->stream));
+            PassLog::Scope assign(ctx, m.passes);
+            if ((rc = m.count.zero(ctx, C_CHANGED, 1))) return rc;
             if ((rc = km_assign(ctx, fn, n, m.cfrag.get(), m.cvalid.get(), k, 0))) return rc;
-            if ((rc = launch_1d(km_label_kernel, n, ctx->stream, n, m.key.get(), label, sim, m.count.get() + C_CHANGED))) return rc;
+            if ((rc = launch_1d(km_label_kernel, n, ctx->stream, n, m.key.get(), label, sim, m.count.dev() + C_CHANGED))) return rc;
         }
-        timers.push_back(t_assign);
         unsigned long long changed = 0;
-        if ((rc = km_read(ctx, C_CHANGED, 1, &changed))) return rc;
-        for (const RoundTimer& t : timers) t.file(m.pass_ms);      // behind the synchronise of km_read
-        timers.clear();
+        if ((rc = m.count.read(ctx, C_CHANGED, 1, &changed))) return rc;
+        m.passes.settle();
         if (changed == 0) {
             converged = true;
             break;
         }
         if (iterations == max_iter) break;
-        if ((rc = km_update(ctx, w.bfrag.get(), w.bvalid.get(), n, nullptr, label, k, 0, cent, &t_update, &t_finish))) return rc;
+        if ((rc = km_update(ctx, w.bfrag.get(), w.bvalid.get(), n, nullptr, label, k, 0, cent, &m.passes))) return rc;
         {
-            ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-            t_prepare = {prof.a, prof.b};
+            PassLog::Scope prepare(ctx, m.passes);
             if ((rc = nn_prepare(ctx, cent, k, GNN_KNN_COSINE, m.cfrag, m.cvalid))) return rc;
         }
-        timers.push_back(t_update);
-        timers.push_back(t_finish);
-        timers.push_back(t_prepare);
         ++iterations;
     }
     ProfScope prof(ctx, GNN_K_NEIGHBOURS);
@@ -516,15 +483,15 @@ int km_centroids(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n,
     int rc = nn_prepare(ctx, rows_dev, n, GNN_KNN_COSINE, w.bfrag, w.bvalid);
     if (!rc) rc = km_reserve(ctx, n, k);
     if (rc) return rc;
-    GNN_HIP(hipMemsetAsync(m.count.get(), 0, C_WORDS * sizeof(unsigned long long), ctx->stream));
-    if (n > 0 && (rc = launch_1d(km_check_kernel, n, ctx->stream, n, (int64_t)k, label, m.count.get() + C_BAD_LABEL))) return rc;
+    if ((rc = m.count.zero(ctx, 0, C_WORDS))) return rc;
+    if (n > 0 && (rc = launch_1d(km_check_kernel, n, ctx->stream, n, (int64_t)k, label, m.count.dev() + C_BAD_LABEL))) return rc;
     unsigned long long bad = 0;
-    if ((rc = km_read(ctx, C_BAD_LABEL, 1, &bad))) return rc;
+    if ((rc = m.count.read(ctx, C_BAD_LABEL, 1, &bad))) return rc;
     if (bad) {
         set_error(std::string(fn) + ": a label is outside [-1, " + std::to_string(k) + ")");
         return GNN_ERR_ARG;
     }
-    if ((rc = km_update(ctx, w.bfrag.get(), w.bvalid.get(), n, nullptr, label, k, 1, cent, nullptr, nullptr))) return rc;
+    if ((rc = km_update(ctx, w.bfrag.get(), w.bvalid.get(), n, nullptr, label, k, 1, cent, nullptr))) return rc;
     GNN_HIP(hipMemcpyAsync(size, m.cnt.get(), (size_t)k * sizeof(int64_t), hipMemcpyDeviceToDevice, ctx->stream));
     return GNN_OK;
 }
@@ -556,32 +523,18 @@ extern "C" int gnn_kmeans(gnn_ctx* ctx, const float* rows_host, int64_t n, int k
     if (int rc = check_ctx(ctx)) return rc;
     NeighbourWorkspace& w = ctx->nn;
     KMeansWorkspace& m = ctx->km;
-    // the centroids (k x 512 f32, first: the kernels move them as 16-byte vectors) in int64 words, then [label n | size k | init_rows k]
-    // int64 and sim (n f32)
-    const int64_t sim_words = (n + 1) / 2, cent_words = (int64_t)k * D / 2;
-    int rc = nn_reserve(ctx, m.d_out, (size_t)(n + 2 * (int64_t)k + sim_words + cent_words));      // every buffer stands before a copy is enqueued
+    Landing land(m.d_out);
+    const int label = land.add(label_host, n), sim = land.add(sim_host, n), size = land.add(size_host, k), init_rows = land.add(init_rows_host, k),
+              cent = land.add(centroids_host, (int64_t)k * D);
+    int rc = land.reserve(ctx);                               // every buffer stands before a copy is enqueued
     if (!rc && init_host_or_null) rc = nn_reserve(ctx, m.d_init, (size_t)k * D);
     if (!rc) rc = nn_upload_rows(ctx, rows_host, n);
     if (rc) return rc;
     if (init_host_or_null)
         GNN_HIP(hipMemcpyAsync(m.d_init.get(), init_host_or_null, (size_t)k * D * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    float* const cent = reinterpret_cast<float*>(m.d_out.get());
-    int64_t* const out = m.d_out.get() + cent_words;
-    int64_t* const size = out + n;
-    int64_t* const init_rows = size + k;
-    float* const sim = reinterpret_cast<float*>(init_rows + k);
-    if ((rc = km_run(ctx, fn, w.d_base, n, k, init_host_or_null ? m.d_init.get() : nullptr, max_iter, out, sim, cent, size, init_rows,
-                     iterations_host, converged_host)))
-        return rc;
-    if (n > 0) {
-        GNN_HIP(hipMemcpyAsync(label_host, out, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-        GNN_HIP(hipMemcpyAsync(sim_host, sim, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    GNN_HIP(hipMemcpyAsync(size_host, size, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(init_rows_host, init_rows, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(centroids_host, cent, (size_t)k * D * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
-    return GNN_OK;
+    rc = km_run(ctx, fn, w.d_base, n, k, init_host_or_null ? m.d_init.get() : nullptr, max_iter, land.dev<int64_t>(label), land.dev<float>(sim),
+                land.dev<float>(cent), land.dev<int64_t>(size), land.dev<int64_t>(init_rows), iterations_host, converged_host);
+    return rc ? rc : land.copy_out(ctx);
 }
 
 extern "C" int gnn_centroids_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, const int64_t* label_dev, int k, float* centroids_dev,
@@ -599,19 +552,15 @@ extern "C" int gnn_centroids(gnn_ctx* ctx, const float* rows_host, int64_t n, co
     if (int rc = check_ctx(ctx)) return rc;
     NeighbourWorkspace& w = ctx->nn;
     KMeansWorkspace& m = ctx->km;
-    // the centroids (k x 512 f32, first: moved as 16-byte vectors), then [label n | size k] int64
-    const int64_t cent_words = (int64_t)k * D / 2;
-    int rc = nn_reserve(ctx, m.d_out, (size_t)(cent_words + n + k));       // both buffers stand before the copy is enqueued
+    Landing land(m.d_out);
+    const int label = land.add<int64_t>(nullptr, n), size = land.add(size_host, k), cent = land.add(centroids_host, (int64_t)k * D);
+    int rc = land.reserve(ctx);                               // both buffers stand before the copy is enqueued
     if (!rc) rc = nn_upload_rows(ctx, rows_host, n);
     if (rc) return rc;
-    float* const cent = reinterpret_cast<float*>(m.d_out.get());
-    int64_t* const out = m.d_out.get() + cent_words;
-    if (n > 0) GNN_HIP(hipMemcpyAsync(out, label_host, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = km_centroids(ctx, fn, w.d_base, n, out, k, cent, out + n))) return rc;
-    GNN_HIP(hipMemcpyAsync(size_host, out + n, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(centroids_host, cent, (size_t)k * D * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
-    return GNN_OK;
+    int64_t* const label_dev = land.dev<int64_t>(label);      // the slice is the call's own: the labels go up, nothing comes back
+    if (n > 0) GNN_HIP(hipMemcpyAsync(label_dev, label_host, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    rc = km_centroids(ctx, fn, w.d_base, n, label_dev, k, land.dev<float>(cent), land.dev<int64_t>(size));
+    return rc ? rc : land.copy_out(ctx);
 }
 
 extern "C" int gnn_debug_set_kmeans_lds(gnn_ctx* ctx, int max_k) {
@@ -627,5 +576,5 @@ extern "C" int gnn_debug_set_kmeans_lds(gnn_ctx* ctx, int max_k) {
 
 extern "C" int gnn_debug_kmeans_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
     if (int rc = check_ctx(ctx)) return rc;
-    return nn_round_ms_out("gnn_debug_kmeans_pass_ms", ctx->km.pass_ms, ms_out, capacity, n_out);
+    return ctx->km.passes.out(ctx, "gnn_debug_kmeans_pass_ms", ms_out, capacity, n_out);
 }

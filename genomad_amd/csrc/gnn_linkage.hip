@@ -33,7 +33,6 @@
 namespace gnn {
 namespace {
 
-constexpr int64_t N_MAX = (int64_t)1 << 31;      // rows are int32 in parent[] and 32 bits of a key
 constexpr int ROUNDS_MAX = 32;                   // components at least halve per round: n < 2^31 needs at most 31
 
 __device__ __forceinline__ unsigned long long lk_peek(const unsigned long long* p) {
@@ -280,16 +279,10 @@ __global__ __launch_bounds__(256) void lk_core_kernel(int64_t n, int k, const ui
 int check_linkage_args(const char* fn, const void* rows, int64_t n, int metric, const void* a, const void* b, const void* sim, const void* valid,
                        const void* n_edges, const void* rounds) {
     const std::string f(fn);
-    if (n < 0 || n >= N_MAX) {
-        set_error(f + ": " + std::to_string(n) + " rows is outside [0, 2^31)");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_rows(f, n, "rows")) return rc;
     if (int rc = nn_check_metric(f, metric)) return rc;
-    if (!n_edges || !rounds || (n > 0 && (!rows || !valid)) || (n > 1 && (!a || !b || !sim))) {
-        set_error("bad argument to " + f + ": the rows, the four arrays, n_edges and rounds are required");
-        return GNN_ERR_ARG;
-    }
-    return GNN_OK;
+    return nn_check_required(f, n_edges && rounds && (n == 0 || (rows && valid)) && (n <= 1 || (a && b && sim)),
+                             "the rows, the four arrays, n_edges and rounds");
 }
 
 // n > 0 rows on the device -> the sorted tree, the flags and the two counts on the host.  The ctx's stream is synchronised once per
@@ -303,7 +296,7 @@ int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int m
     const int64_t capacity = n - 1;
     const bool mr = min_points > 0;
     const int nk = mr ? min_points - 1 : 0;
-    std::vector<float>& round_ms = mr ? k.tree_round_ms : k.round_ms;
+    PassLog& log = mr ? k.tree_rounds : k.rounds;
     int rc = GNN_OK;
     if (nk > 0) {
         rc = nn_reserve(ctx, k.nidx, (size_t)n * nk);
@@ -321,13 +314,11 @@ int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int m
     if (!rc) rc = nn_reserve(ctx, k.ea, (size_t)n);
     if (!rc) rc = nn_reserve(ctx, k.eb, (size_t)n);
     if (!rc) rc = nn_reserve(ctx, k.es, (size_t)n);
-    if (!rc) rc = nn_reserve(ctx, k.count, 1);
-    if (!rc) rc = k.h_count.reserve(1);
+    if (!rc) rc = k.count.reserve(ctx, 1);
     const int64_t tiles = (n + QT - 1) / QT;
     int64_t split_rows, splits;
     if (!rc) rc = nn_tile_grid(ctx, fn, "rows", tiles, n, &split_rows, &splits);
     if (rc) return rc;
-    const dim3 per_row((unsigned)((n + 255) / 256)), tile_grid((unsigned)tiles, (unsigned)splits);
     LinkageArgs a;
     a.frag = w.bfrag.get();
     a.comp = k.comp.get();
@@ -336,16 +327,12 @@ int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int m
     a.scale = nn_metric_scale(metric);
     a.best = k.best.get();
     a.core = mr ? k.core.get() : nullptr;
-    round_ms.clear();
+    log.begin();
     {
         ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-        GNN_HIP(hipMemsetAsync(k.count.get(), 0, sizeof(unsigned long long), ctx->stream));
-        hipLaunchKernelGGL(lk_init_kernel, per_row, dim3(256), 0, ctx->stream, n, w.bvalid.get(), k.comp.get());
-        GNN_HIP(hipGetLastError());
-        if (mr) {
-            hipLaunchKernelGGL(lk_core_kernel, per_row, dim3(256), 0, ctx->stream, n, nk, w.bvalid.get(), k.nsim.get(), k.core.get());
-            GNN_HIP(hipGetLastError());
-        }
+        if ((rc = k.count.zero(ctx, 0, 1))) return rc;
+        if ((rc = launch_1d(lk_init_kernel, n, ctx->stream, n, w.bvalid, k.comp))) return rc;
+        if (mr && (rc = launch_1d(lk_core_kernel, n, ctx->stream, n, nk, w.bvalid, k.nsim, k.core))) return rc;
     }
     // One Boruvka round per pass.  Every component with an outgoing edge is joined to another one, so the components that are not
     // yet final at least halve: at most 31 rounds add an edge for n < 2^31, and one more adds none.  Ends: the loop is bounded by
@@ -358,32 +345,19 @@ int lk_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int m
                       std::to_string(edges) + " edges so far): at most " + std::to_string(ROUNDS_MAX) + " rounds can be");
             return GNN_ERR_STATE;
         }
-        RoundTimer timer;
         {
-            ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-            timer = {prof.a, prof.b};
-            hipLaunchKernelGGL(lk_reset_kernel, per_row, dim3(256), 0, ctx->stream, n, k.comp.get(), k.parent.get(), k.best.get(), k.cbest.get(),
-                               k.chi.get());
-            GNN_HIP(hipGetLastError());
-            if (mr)
-                hipLaunchKernelGGL(lk_tile_kernel<true>, tile_grid, dim3(256), 0, ctx->stream, a);
-            else
-                hipLaunchKernelGGL(lk_tile_kernel<false>, tile_grid, dim3(256), 0, ctx->stream, a);
-            GNN_HIP(hipGetLastError());
-            hipLaunchKernelGGL(lk_pick_lo_kernel, per_row, dim3(256), 0, ctx->stream, n, k.comp.get(), k.best.get(), k.cbest.get());
-            GNN_HIP(hipGetLastError());
-            hipLaunchKernelGGL(lk_pick_hi_kernel, per_row, dim3(256), 0, ctx->stream, n, k.comp.get(), k.best.get(), k.cbest.get(), k.chi.get());
-            GNN_HIP(hipGetLastError());
-            hipLaunchKernelGGL(lk_link_kernel, per_row, dim3(256), 0, ctx->stream, n, capacity, k.comp.get(), k.cbest.get(), k.chi.get(),
-                               k.parent.get(), k.ea.get(), k.eb.get(), k.es.get(), k.count.get());
-            GNN_HIP(hipGetLastError());
-            hipLaunchKernelGGL(lk_flatten_kernel, per_row, dim3(256), 0, ctx->stream, n, k.parent.get(), k.comp.get());
-            GNN_HIP(hipGetLastError());
+            PassLog::Scope round(ctx, log);
+            if ((rc = launch_1d(lk_reset_kernel, n, ctx->stream, n, k.comp, k.parent, k.best, k.cbest, k.chi))) return rc;
+            if ((rc = launch_tiles(mr ? lk_tile_kernel<true> : lk_tile_kernel<false>, tiles, splits, ctx->stream, a))) return rc;
+            if ((rc = launch_1d(lk_pick_lo_kernel, n, ctx->stream, n, k.comp, k.best, k.cbest))) return rc;
+            if ((rc = launch_1d(lk_pick_hi_kernel, n, ctx->stream, n, k.comp, k.best, k.cbest, k.chi))) return rc;
+            if ((rc = launch_1d(lk_link_kernel, n, ctx->stream, n, capacity, k.comp, k.cbest, k.chi, k.parent, k.ea, k.eb, k.es, k.count.dev())))
+                return rc;
+            if ((rc = launch_1d(lk_flatten_kernel, n, ctx->stream, n, k.parent, k.comp))) return rc;
         }
-        GNN_HIP(hipMemcpyAsync(k.h_count.get(), k.count.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        GNN_HIP(hipStreamSynchronize(ctx->stream));
-        const unsigned long long now = k.h_count.get()[0];
-        timer.file(round_ms);
+        unsigned long long now = 0;
+        if ((rc = k.count.read(ctx, 0, 1, &now))) return rc;
+        log.settle();
         if (now > (unsigned long long)capacity) {
             set_error(std::string(fn) + ": round " + std::to_string(pass + 1) + " recorded " + std::to_string(now) + " edges among " +
                       std::to_string(n) + " rows: a forest has at most n - 1");
@@ -453,7 +427,7 @@ extern "C" int gnn_linkage(gnn_ctx* ctx, const float* rows_host, int64_t n, int 
 
 extern "C" int gnn_debug_linkage_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
     if (int rc = check_ctx(ctx)) return rc;
-    return nn_round_ms_out("gnn_debug_linkage_round_ms", ctx->lk.round_ms, ms_out, capacity, n_out);
+    return ctx->lk.rounds.out(ctx, "gnn_debug_linkage_round_ms", ms_out, capacity, n_out);
 }
 
 // ---- the density tree: the same rounds over the mutual-reachability values (include/genomad_nn.h, "density-aware linkage tree") ----
@@ -471,7 +445,7 @@ int check_density_tree_args(const char* fn, const void* rows, int64_t n, int min
     }
     if (int rc = check_linkage_args(fn, rows, n, metric, a, b, sim, valid, n_edges, rounds)) return rc;
     if (n > 0 && !core) {
-        set_error(std::string("bad argument to ") + fn + ": core is required");
+        set_error(std::string("bad argument to ") + fn + ": core is required");      // "is", not nn_check_required's "are"
         return GNN_ERR_ARG;
     }
     return GNN_OK;
@@ -509,5 +483,5 @@ extern "C" int gnn_density_tree(gnn_ctx* ctx, const float* rows_host, int64_t n,
 
 extern "C" int gnn_debug_density_tree_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
     if (int rc = check_ctx(ctx)) return rc;
-    return nn_round_ms_out("gnn_debug_density_tree_round_ms", ctx->lk.tree_round_ms, ms_out, capacity, n_out);
+    return ctx->lk.tree_rounds.out(ctx, "gnn_debug_density_tree_round_ms", ms_out, capacity, n_out);
 }

@@ -38,7 +38,6 @@ constexpr int MAX_ITER_MAX = 10000;
 constexpr int LDS_SLOTS = 4096;                  // the table: 16 KB of keys + 32 KB of sums - two workgroups per CU
 constexpr ull ONE = 1ull << 30;
 constexpr double W = 16777216.0;                 // 2^24
-constexpr int SCAN_THREADS = 1024;
 constexpr int THREADS = 256;
 
 struct MclArgs {
@@ -480,35 +479,6 @@ __global__ __launch_bounds__(256) void mc_edges_kernel(int64_t n, const int64_t*
     }
 }
 
-// Exclusive int64 prefix sums of the n degrees, the total behind them, and the cursors: ONE block, thread t owns a run (the scheme of
-// gnn_graph.hip's scan).  Every loop ends: i grows towards e, or towards SCAN_THREADS.
-__global__ __launch_bounds__(SCAN_THREADS) void mc_scan_kernel(const int32_t* __restrict__ deg, int64_t n, int64_t* __restrict__ soff,
-                                                               ull* __restrict__ cursor) {
-    __shared__ int64_t run[SCAN_THREADS];
-    const int64_t per = (n + SCAN_THREADS - 1) / SCAN_THREADS;
-    const int64_t a = min(n, (int64_t)threadIdx.x * per), e = min(n, a + per);
-    int64_t s = 0;
-    for (int64_t i = a; i < e; ++i) s += deg[i];
-    run[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t acc = 0;
-        for (int i = 0; i < SCAN_THREADS; ++i) {
-            const int64_t v = run[i];
-            run[i] = acc;
-            acc += v;
-        }
-        soff[n] = acc;
-    }
-    __syncthreads();
-    s = run[threadIdx.x];
-    for (int64_t i = a; i < e; ++i) {
-        soff[i] = s;
-        cursor[i] = (ull)s;
-        s += deg[i];
-    }
-}
-
 // ---- interpret -----------------------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void mc_parent_kernel(int64_t n, int32_t* __restrict__ parent, int32_t* __restrict__ size) {
@@ -606,26 +576,24 @@ int mcl_run(gnn_ctx* ctx, const char* fn, const MclIn& in, int64_t* label, int64
             uint8_t* is_attractor, int64_t* changed_host, int64_t* iterations_host, int* converged_host) {
     MclWorkspace& m = ctx->mcl;
     m.have = false;
-    m.pass_ms.clear();
+    m.passes.begin();
     m.overflow.clear();
     const int64_t n = in.n;
     const int groups = mcl_groups(ctx);
     const int dense_groups = (int)std::max<int64_t>(1, std::min<int64_t>(groups, ((int64_t)1 << 27) / n));
     const size_t cells = (size_t)n * in.select;
     int rc = nn_reserve(ctx, m.ok, (size_t)n);
-    if (!rc) rc = nn_reserve(ctx, m.count, (size_t)2 * (in.max_iter + 1) + 1);
-    if (!rc) rc = m.h_count.reserve(1);
+    const size_t flag = (size_t)2 * (in.max_iter + 1);       // the graph's flag stands behind the passes' counters
+    if (!rc) rc = m.count.reserve(ctx, flag + 1);
+    if (!rc) rc = m.count.zero(ctx, 0, flag + 1);
     if (rc) return rc;
-    ull* const flag = m.count.get() + 2 * (in.max_iter + 1);
-    GNN_HIP(hipMemsetAsync(m.count.get(), 0, ((size_t)2 * (in.max_iter + 1) + 1) * sizeof(ull), ctx->stream));
-    RoundTimer t_setup;
     {
-        ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-        t_setup = {prof.a, prof.b};
-        if (int rc2 = launch_1d(mc_validate_kernel, n, ctx->stream, n, in.nnz, in.indptr, in.col, in.sim, in.valid, m.ok.get(), flag)) return rc2;
-        GNN_HIP(hipMemcpyAsync(m.h_count.get(), flag, sizeof(ull), hipMemcpyDeviceToHost, ctx->stream));
-        GNN_HIP(hipStreamSynchronize(ctx->stream));
-        if (*m.h_count.get()) {
+        PassLog::Scope setup(ctx, m.passes);                  // open across the read below: nothing is settled there
+        if ((rc = launch_1d(mc_validate_kernel, n, ctx->stream, n, in.nnz, in.indptr, in.col, in.sim, in.valid, m.ok.get(), m.count.dev() + flag)))
+            return rc;
+        ull bad = 0;
+        if ((rc = m.count.read(ctx, flag, 1, &bad))) return rc;
+        if (bad) {
             set_error(std::string(fn) + ": the graph is no upper-triangle CSR of " + std::to_string(n) + " rows and " + std::to_string(in.nnz) +
                       " entries with similarities below 64: indptr must rise from 0 to nnz, a row's col lie in (row, n), sim be finite");
             return GNN_ERR_ARG;
@@ -651,8 +619,7 @@ int mcl_run(gnn_ctx* ctx, const char* fn, const MclIn& in, int64_t* label, int64
         if ((rc = launch_1d(mc_edges_kernel<false>, n, ctx->stream, n, in.indptr, in.col, in.sim, m.ok.get(), m.deg.get(), m.soff.get(),
                             m.cursor.get(), m.sidx.get(), m.sq.get())))
             return rc;
-        hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, m.deg.get(), n, m.soff.get(), m.cursor.get());
-        GNN_HIP(hipGetLastError());
+        if ((rc = nn_scan(ctx->stream, m.deg, n, m.soff, m.cursor))) return rc;
         if ((rc = launch_1d(mc_edges_kernel<true>, n, ctx->stream, n, in.indptr, in.col, in.sim, m.ok.get(), m.deg.get(), m.soff.get(),
                             m.cursor.get(), m.sidx.get(), m.sq.get())))
             return rc;
@@ -678,8 +645,8 @@ int mcl_run(gnn_ctx* ctx, const char* fn, const MclIn& in, int64_t* label, int64
         a.nlen = m.len[it & 1].get();
         a.nidx = m.idx[it & 1].get();
         a.nval = m.val[it & 1].get();
-        a.changed = m.count.get() + 2 * it;
-        a.ovf_count = m.count.get() + 2 * it + 1;
+        a.changed = m.count.dev() + 2 * it;
+        a.ovf_count = m.count.dev() + 2 * it + 1;
         hipLaunchKernelGGL(it ? mc_lds_kernel<false> : mc_lds_kernel<true>, dim3((unsigned)std::min<int64_t>(groups, n)), dim3(THREADS), 0,
                            ctx->stream, a);
         GNN_HIP(hipGetLastError());
@@ -688,28 +655,22 @@ int mcl_run(gnn_ctx* ctx, const char* fn, const MclIn& in, int64_t* label, int64
         return GNN_OK;
     };
     {
-        ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-        RoundTimer t_init = {prof.a, prof.b};
+        PassLog::Scope init(ctx, m.passes);
         if ((rc = pass(0))) return rc;
-        m.pending = {t_setup, t_init};
     }
     int it = 0;
     bool converged = false;
     while (it < in.max_iter && !converged) {                  // Ends: it grows towards max_iter
         ++it;
-        RoundTimer t;
         {
-            ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-            t = {prof.a, prof.b};
+            PassLog::Scope iteration(ctx, m.passes);
             if ((rc = pass(it))) return rc;
         }
-        GNN_HIP(hipMemcpyAsync(m.h_count.get(), m.count.get() + 2 * it, sizeof(ull), hipMemcpyDeviceToHost, ctx->stream));
-        GNN_HIP(hipStreamSynchronize(ctx->stream));
-        for (const RoundTimer& p : m.pending) p.file(m.pass_ms);
-        m.pending.clear();
-        t.file(m.pass_ms);
-        changed_host[it - 1] = (int64_t)*m.h_count.get();
-        converged = changed_host[it - 1] == 0;
+        ull changed = 0;
+        if ((rc = m.count.read(ctx, (size_t)2 * it, 1, &changed))) return rc;
+        m.passes.settle();
+        changed_host[it - 1] = (int64_t)changed;
+        converged = changed == 0;
     }
     const int cur = it & 1;
     {
@@ -724,10 +685,8 @@ int mcl_run(gnn_ctx* ctx, const char* fn, const MclIn& in, int64_t* label, int64
     // the columns every pass pushed on the overflow list, the initial matrix first: read once, behind everything
     m.overflow.assign((size_t)it + 1, 0);
     std::vector<ull> counts((size_t)2 * (it + 1));
-    GNN_HIP(hipMemcpyAsync(counts.data(), m.count.get(), counts.size() * sizeof(ull), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
-    for (const RoundTimer& p : m.pending) p.file(m.pass_ms);
-    m.pending.clear();
+    if ((rc = m.count.read(ctx, 0, counts.size(), counts.data()))) return rc;
+    m.passes.settle();
     for (int k = 0; k <= it; ++k) m.overflow[k] = (int64_t)counts[2 * k + 1];
     *iterations_host = it;
     *converged_host = converged;
@@ -743,19 +702,17 @@ int mcl_check(const char* fn, const MclIn& in, const void* label, const void* si
               const void* changed, const void* iterations, const void* converged) {
     const std::string f(fn);
     if (int rc = check_mcl_args(f, in.n, in.nnz, in.a4, in.select, in.precision, in.max_iter)) return rc;
-    if (!in.indptr || (in.nnz > 0 && (!in.col || !in.sim)) || !iterations || !converged || (in.max_iter > 0 && !changed) ||
-        (in.n > 0 && (!label || !size || !attractor || !flow || !is_attractor))) {
-        set_error("bad argument to " + f + ": indptr, col, sim, the five outputs, changed, iterations and converged are required");
-        return GNN_ERR_ARG;
-    }
-    return GNN_OK;
+    return nn_check_required(f,
+                             in.indptr && (in.nnz == 0 || (in.col && in.sim)) && iterations && converged && (in.max_iter == 0 || changed) &&
+                                 (in.n == 0 || (label && size && attractor && flow && is_attractor)),
+                             "indptr, col, sim, the five outputs, changed, iterations and converged");
 }
 
 // n == 0: the definition's answer - one iteration that changes nothing
 void mcl_empty(gnn_ctx* ctx, int max_iter, int64_t* changed_host, int64_t* iterations_host, int* converged_host) {
     ctx->mcl.have = true;
     ctx->mcl.n = 0;
-    ctx->mcl.pass_ms.clear();
+    ctx->mcl.passes.begin();
     ctx->mcl.overflow.clear();
     if (max_iter > 0) changed_host[0] = 0;
     *iterations_host = max_iter > 0;
@@ -804,7 +761,10 @@ extern "C" int gnn_mcl(gnn_ctx* ctx, const int64_t* indptr_host, const int32_t* 
     if (!rc) rc = nn_reserve(ctx, m.d_col, (size_t)std::max<int64_t>(nnz, 1));
     if (!rc) rc = nn_reserve(ctx, m.d_sim, (size_t)std::max<int64_t>(nnz, 1));
     if (!rc) rc = nn_reserve(ctx, m.d_valid, (size_t)n);
-    if (!rc) rc = nn_reserve(ctx, m.d_out, (size_t)4 * n + 1);
+    Landing land(m.d_out);
+    const int label = land.add(label_host, n), size = land.add(size_host, n), attractor = land.add(attractor_host, n),
+              flow = land.add(flow_host, n), is_attractor = land.add(is_attractor_host, n);
+    if (!rc) rc = land.reserve(ctx);
     if (rc) return rc;
     GNN_HIP(hipMemcpyAsync(m.d_indptr.get(), indptr_host, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     if (nnz > 0) {
@@ -816,17 +776,9 @@ extern "C" int gnn_mcl(gnn_ctx* ctx, const int64_t* indptr_host, const int32_t* 
     in.col = m.d_col.get();
     in.sim = m.d_sim.get();
     in.valid = valid_host_or_null ? m.d_valid.get() : nullptr;
-    int64_t* const out = m.d_out.get();
-    uint32_t* const flow_dev = reinterpret_cast<uint32_t*>(out + 3 * n);
-    uint8_t* const att_dev = reinterpret_cast<uint8_t*>(flow_dev + n);
-    if ((rc = mcl_run(ctx, fn, in, out, out + n, out + 2 * n, flow_dev, att_dev, changed_host, iterations_host, converged_host))) return rc;
-    GNN_HIP(hipMemcpyAsync(label_host, out, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(size_host, out + n, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(attractor_host, out + 2 * n, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(flow_host, flow_dev, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(is_attractor_host, att_dev, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
-    return GNN_OK;
+    rc = mcl_run(ctx, fn, in, land.dev<int64_t>(label), land.dev<int64_t>(size), land.dev<int64_t>(attractor), land.dev<uint32_t>(flow),
+                 land.dev<uint8_t>(is_attractor), changed_host, iterations_host, converged_host);
+    return rc ? rc : land.copy_out(ctx);
 }
 
 extern "C" int gnn_mcl_matrix(gnn_ctx* ctx, int64_t n, int select, int32_t* length_host, int32_t* idx_host, uint32_t* val_host) {
@@ -839,10 +791,7 @@ extern "C" int gnn_mcl_matrix(gnn_ctx* ctx, int64_t n, int select, int32_t* leng
         return GNN_ERR_STATE;
     }
     if (n == 0) return GNN_OK;
-    if (!length_host || !idx_host || !val_host) {
-        set_error(std::string("bad argument to ") + fn + ": length, idx and val are required");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_required(fn, length_host && idx_host && val_host, "length, idx and val")) return rc;
     const size_t cells = (size_t)n * select;
     GNN_HIP(hipMemcpyAsync(length_host, m.len[m.cur].get(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     GNN_HIP(hipMemcpyAsync(idx_host, m.idx[m.cur].get(), cells * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -874,7 +823,7 @@ extern "C" int gnn_debug_mcl_groups(gnn_ctx* ctx, int groups) {
 
 extern "C" int gnn_debug_mcl_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
     if (int rc = check_ctx(ctx)) return rc;
-    return nn_round_ms_out("gnn_debug_mcl_ms", ctx->mcl.pass_ms, ms_out, capacity, n_out);
+    return ctx->mcl.passes.out(ctx, "gnn_debug_mcl_ms", ms_out, capacity, n_out);
 }
 
 extern "C" int gnn_debug_mcl_overflow(gnn_ctx* ctx, int64_t* count_out, int64_t capacity, int64_t* n_out) {

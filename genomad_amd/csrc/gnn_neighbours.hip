@@ -15,7 +15,6 @@ namespace {
 
 constexpr int KMAX = 64;                         // one list entry per lane of a wave
 constexpr int64_t QSLAB = 16384;                 // query rows per launch: bounds the partial lists (8 k B per query and range)
-constexpr int64_t NB_MAX = (int64_t)1 << 31;     // base indices are int32 in the partial lists
 constexpr int64_t SPLIT_MAX = 65280;             // base rows per workgroup at the most: a neighbour list entry holds its row as a 16-bit offset
 
 // ---- prepare: grid = padded rows / 32, 256 threads; wave w of a block takes its rows 8 w .. 8 w + 7, lane l the elements
@@ -272,16 +271,8 @@ int check_nn_args(const char* fn, const void* query, int64_t nq, int64_t nb, boo
         set_error(f + ": n_query " + std::to_string(nq) + " is outside [0, 2^63)");
         return GNN_ERR_ARG;
     }
-    const int64_t rows = self ? nq : nb;
-    if (rows < 0 || rows >= NB_MAX) {
-        set_error(f + ": " + std::to_string(rows) + " base rows is outside [0, 2^31)");
-        return GNN_ERR_ARG;
-    }
-    if (nq > 0 && (!query || !idx || !sim)) {
-        set_error("bad argument to " + f + ": the query and both outputs are required");
-        return GNN_ERR_ARG;
-    }
-    return GNN_OK;
+    if (int rc = nn_check_rows(f, self ? nq : nb, "base rows")) return rc;
+    return nn_check_required(f, nq == 0 || (query && idx && sim), "the query and both outputs");
 }
 
 // m <= QSLAB prepared query rows against the prepared base: tile, then merge into idx_dev[m][k], sim_dev[m][k]
@@ -312,8 +303,7 @@ int nn_search_slab(gnn_ctx* ctx, const uint4* qfrag, const uint8_t* qvalid, int6
         a.self_off = self_off;
         a.psim = w.psim.get();
         a.pidx = w.pidx.get();
-        hipLaunchKernelGGL(nn_tile_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, ctx->stream, a);
-        GNN_HIP(hipGetLastError());
+        if ((rc = launch_tiles(nn_tile_kernel, tiles, splits, ctx->stream, a))) return rc;
     }
     hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)m), dim3(64), 0, ctx->stream, w.psim.get(), w.pidx.get(), (int)splits, k, idx_dev,
                        sim_dev);
@@ -346,18 +336,16 @@ int nn_search(gnn_ctx* ctx, const float* query_dev, const float* query_host, int
         }
         int64_t* idx_dev = idx + q0 * k;
         float* sim_dev = sim + q0 * k;
+        Landing land(w.d_out);
         if (to_host) {
-            if ((rc = nn_reserve(ctx, w.d_idx, (size_t)m * k))) return rc;
-            if ((rc = nn_reserve(ctx, w.d_sim, (size_t)m * k))) return rc;
-            idx_dev = w.d_idx;
-            sim_dev = w.d_sim;
+            land.add(idx_dev, m * k);
+            land.add(sim_dev, m * k);
+            if ((rc = land.reserve(ctx))) return rc;
+            idx_dev = land.dev<int64_t>(0);
+            sim_dev = land.dev<float>(1);
         }
         if ((rc = nn_search_slab(ctx, qfrag, qvalid, m, nb, k, metric, self ? q0 : -1, idx_dev, sim_dev))) return rc;
-        if (to_host) {
-            GNN_HIP(hipMemcpyAsync(idx + q0 * k, w.d_idx, (size_t)m * k * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-            GNN_HIP(hipMemcpyAsync(sim + q0 * k, w.d_sim, (size_t)m * k * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-            GNN_HIP(hipStreamSynchronize(ctx->stream));      // the landing buffers and d_query serve the next slab
-        }
+        if (to_host && (rc = land.copy_out(ctx))) return rc;      // synchronised: the landing buffer and d_query serve the next slab
     }
     return GNN_OK;
 }
@@ -408,18 +396,94 @@ int nn_upload_rows(gnn_ctx* ctx, const float* rows_host, int64_t n) {
     return GNN_OK;
 }
 
-void RoundTimer::file(std::vector<float>& round_ms) const {
-    float ms = 0.f;                        // profiling only: the round's two events have completed with the synchronise before this
-    if (a && b && hipEventElapsedTime(&ms, a, b) == hipSuccess) round_ms.push_back(ms);
+// ---- the scan (nn_scan): ONE block, thread t owns a run of counters, thread 0 scans the 1024 run sums between two barriers.  Every
+// loop ends: i grows towards e, or towards SCAN_THREADS.
+constexpr int SCAN_THREADS = 1024;
+__global__ __launch_bounds__(SCAN_THREADS) void nn_scan_kernel(const int32_t* __restrict__ cnt, int64_t m, int64_t* __restrict__ off,
+                                                               unsigned long long* __restrict__ cursor) {
+    __shared__ int64_t run[SCAN_THREADS];
+    const int64_t per = (m + SCAN_THREADS - 1) / SCAN_THREADS;
+    const int64_t a = min(m, (int64_t)threadIdx.x * per), e = min(m, a + per);
+    int64_t s = 0;
+    for (int64_t i = a; i < e; ++i) s += cnt[i];
+    run[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t acc = 0;
+        for (int i = 0; i < SCAN_THREADS; ++i) {
+            const int64_t v = run[i];
+            run[i] = acc;
+            acc += v;
+        }
+        off[m] = acc;
+    }
+    __syncthreads();
+    s = run[threadIdx.x];
+    for (int64_t i = a; i < e; ++i) {
+        off[i] = s;
+        if (cursor) cursor[i] = (unsigned long long)s;
+        s += cnt[i];
+    }
 }
 
-int nn_round_ms_out(const char* fn, const std::vector<float>& round_ms, double* ms_out, int64_t capacity, int64_t* n_out) {
+int nn_scan(hipStream_t stream, const int32_t* cnt, int64_t m, int64_t* off, unsigned long long* cursor) {
+    hipLaunchKernelGGL(nn_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, cnt, m, off, cursor);
+    GNN_HIP(hipGetLastError());
+    return GNN_OK;
+}
+
+// ---- PassLog, HostCounters, Landing (gnn_nn_host.h) ----------------------------------------------------------------------------------
+
+void PassLog::settle() {
+    for (const auto& pr : pending_) {
+        float ms = 0.f;                    // profiling only: the pair's events have completed with the synchronise before this
+        if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) ms_.push_back(ms);
+    }
+    pending_.clear();
+}
+
+int PassLog::out(gnn_ctx* ctx, const char* fn, double* ms_out, int64_t capacity, int64_t* n_out) {
+    if (!pending_.empty()) {
+        GNN_HIP(hipStreamSynchronize(ctx->stream));
+        settle();
+    }
     if (capacity < 0 || (capacity > 0 && !ms_out) || !n_out) {
         set_error(std::string("bad argument to ") + fn + ": a capacity >= 0, its array and n_out are required");
         return GNN_ERR_ARG;
     }
-    *n_out = (int64_t)round_ms.size();
-    for (int64_t i = 0; i < std::min<int64_t>(capacity, (int64_t)round_ms.size()); ++i) ms_out[i] = round_ms[i];
+    *n_out = (int64_t)ms_.size();
+    for (int64_t i = 0; i < std::min<int64_t>(capacity, (int64_t)ms_.size()); ++i) ms_out[i] = ms_[i];
+    return GNN_OK;
+}
+
+int HostCounters::reserve(gnn_ctx* ctx, size_t words) { return nn_reserve(ctx, dev_, words); }
+
+int HostCounters::zero(gnn_ctx* ctx, size_t first, size_t words) {
+    GNN_HIP(hipMemsetAsync(dev_.get() + first, 0, words * sizeof(unsigned long long), ctx->stream));
+    return GNN_OK;
+}
+
+int HostCounters::read(gnn_ctx* ctx, size_t first, size_t words, unsigned long long* out) {
+    if (int rc = host_.reserve(words)) return rc;             // no copy into it is in flight: every read ends with a synchronise
+    GNN_HIP(hipMemcpyAsync(host_.get(), dev_.get() + first, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    GNN_HIP(hipStreamSynchronize(ctx->stream));
+    std::copy(host_.get(), host_.get() + words, out);
+    return GNN_OK;
+}
+
+int Landing::reserve(gnn_ctx* ctx) {
+    if (!ok()) {
+        set_error("a Landing holds at most " + std::to_string(LANDING_SLICES) + " slices");
+        return GNN_ERR_STATE;
+    }
+    return nn_reserve(ctx, buf_, std::max<size_t>(total_ / sizeof(int64_t), 1));
+}
+
+int Landing::copy_out(gnn_ctx* ctx) const {
+    for (int i = 0; i < n_; ++i)
+        if (s_[i].host && s_[i].bytes)
+            GNN_HIP(hipMemcpyAsync(s_[i].host, reinterpret_cast<char*>(buf_.get()) + s_[i].at, s_[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+    GNN_HIP(hipStreamSynchronize(ctx->stream));
     return GNN_OK;
 }
 

@@ -11,7 +11,7 @@
 //   the union-find: cl_peek, cl_join, nn_root
 //   nn_reserve, the one host-side piece that is a template
 // The prepare kernel and the host-side prologue (nn_prepare, nn_tile_grid, nn_upload_rows, ...) are compiled once, in
-// gnn_neighbours.hip, and declared in gnn_common.h.
+// gnn_neighbours.hip, and declared in gnn_nn_host.h with the rest of what the host code shares.
 #pragma once
 #include <cmath>
 

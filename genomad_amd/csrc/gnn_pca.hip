@@ -246,11 +246,7 @@ int check_rows(const std::string& f, int64_t n) {
 int check_moments_args(const char* fn, const void* rows, int64_t n, const void* G, const void* S, const void* n_valid) {
     const std::string f(fn);
     if (int rc = check_rows(f, n)) return rc;
-    if (!rows || !G || !S || !n_valid) {
-        set_error("bad argument to " + f + ": the rows and the three outputs are required");
-        return GNN_ERR_ARG;
-    }
-    return GNN_OK;
+    return nn_check_required(f, rows && G && S && n_valid, "the rows and the three outputs");
 }
 
 int check_project_args(const char* fn, const void* rows, int64_t n, const void* comp, int ncomp, const void* out) {
@@ -260,25 +256,14 @@ int check_project_args(const char* fn, const void* rows, int64_t n, const void* 
         set_error(f + ": " + std::to_string(ncomp) + " components is outside [1, " + std::to_string(NCOMP_MAX) + "]");
         return GNN_ERR_ARG;
     }
-    if (!rows || !comp || !out) {
-        set_error("bad argument to " + f + ": the rows, the components and the output are required");
-        return GNN_ERR_ARG;
-    }
-    return GNN_OK;
+    return nn_check_required(f, rows && comp && out, "the rows, the components and the output");
 }
-
-// a pass's events, filed by gnn_debug_pca_pass_ms behind a synchronise of its own: the _dev entry points have none
-struct PassScope {
-    ProfScope prof;
-    PassScope(gnn_ctx* ctx) : prof(ctx, GNN_K_NEIGHBOURS) { ctx->pca.pending.push_back({prof.a, prof.b}); }
-};
 
 // n >= 1 rows on the device -> G, S and n_valid on the device, enqueued
 int pca_moments(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, int64_t* G, int64_t* S, int64_t* n_valid) {
     NeighbourWorkspace& w = ctx->nn;
     PCAWorkspace& p = ctx->pca;
-    p.pending.clear();
-    p.pass_ms.clear();
+    p.passes.begin();
     const int64_t granules = (n + GRANULE - 1) / GRANULE;
     int64_t per = p.split / GRANULE;       // granules per workgroup
     if (per <= 0) {
@@ -291,14 +276,14 @@ int pca_moments(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, 
         return GNN_ERR_ARG;
     }
     {
-        PassScope pass(ctx);
+        PassLog::Scope pass(ctx, p.passes);
         if (int rc = nn_prepare(ctx, rows_dev, n, GNN_KNN_COSINE, w.bfrag, w.bvalid)) return rc;
     }
     const int64_t padded = round_up(n, QT);
     unsigned long long* const Gu = reinterpret_cast<unsigned long long*>(G);
     unsigned long long* const Su = reinterpret_cast<unsigned long long*>(S);
     {
-        PassScope pass(ctx);
+        PassLog::Scope pass(ctx, p.passes);
         GNN_HIP(hipMemsetAsync(S, 0, (size_t)D * sizeof(int64_t), ctx->stream));
         const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((padded + 63) / 64, 2 * std::max(ctx->cu_count, 1)));
         const int64_t per_block = (padded + blocks - 1) / blocks;
@@ -307,7 +292,7 @@ int pca_moments(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, 
         GNN_HIP(hipGetLastError());
     }
     {
-        PassScope pass(ctx);
+        PassLog::Scope pass(ctx, p.passes);
         GNN_HIP(hipMemsetAsync(G, 0, (size_t)D * D * sizeof(int64_t), ctx->stream));
         GramArgs a;
         a.frag = w.bfrag.get();
@@ -317,7 +302,7 @@ int pca_moments(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, 
         hipLaunchKernelGGL(pca_gram_kernel, dim3(NPAIR, (unsigned)ranges), dim3(256), 0, ctx->stream, a);
         GNN_HIP(hipGetLastError());
     }
-    PassScope pass(ctx);
+    PassLog::Scope pass(ctx, p.passes);
     GNN_HIP(hipMemsetAsync(n_valid, 0, sizeof(int64_t), ctx->stream));
     return launch_1d(pca_mirror_kernel, std::max<int64_t>(n, (int64_t)(NPAIR - NFB) * FB * FB), ctx->stream, Gu, n, w.bvalid.get(),
                      reinterpret_cast<unsigned long long*>(n_valid));
@@ -327,17 +312,16 @@ int pca_moments(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, 
 int pca_project(gnn_ctx* ctx, const float* rows_dev, int64_t n, const float* comp_dev, int ncomp, const float* off_dev, float* out) {
     NeighbourWorkspace& w = ctx->nn;
     PCAWorkspace& p = ctx->pca;
-    p.pending.clear();
-    p.pass_ms.clear();
+    p.passes.begin();
     {
-        PassScope pass(ctx);
+        PassLog::Scope pass(ctx, p.passes);
         if (int rc = nn_prepare(ctx, rows_dev, n, GNN_KNN_COSINE, w.bfrag, w.bvalid)) return rc;
     }
     {
-        PassScope pass(ctx);
+        PassLog::Scope pass(ctx, p.passes);
         if (int rc = nn_prepare(ctx, comp_dev, ncomp, GNN_KNN_COSINE, p.cfrag, p.cvalid)) return rc;
     }
-    PassScope pass(ctx);
+    PassLog::Scope pass(ctx, p.passes);
     ProjectArgs a;
     a.frag = w.bfrag.get();
     a.valid = w.bvalid.get();
@@ -348,9 +332,7 @@ int pca_project(gnn_ctx* ctx, const float* rows_dev, int64_t n, const float* com
     a.scale = nn_metric_scale(GNN_KNN_COSINE);
     a.off = off_dev;
     a.out = out;
-    hipLaunchKernelGGL(pca_project_kernel, dim3((unsigned)((n + QT - 1) / QT)), dim3(256), 0, ctx->stream, a);
-    GNN_HIP(hipGetLastError());
-    return GNN_OK;
+    return launch_tiles(pca_project_kernel, (n + QT - 1) / QT, 1, ctx->stream, a);
 }
 
 }  // namespace
@@ -370,17 +352,14 @@ extern "C" int gnn_pca_moments(gnn_ctx* ctx, const float* rows_host, int64_t n, 
     if (int rc = check_moments_args(fn, rows_host, n, G_host, S_host, n_valid_host)) return rc;
     if (int rc = check_ctx(ctx)) return rc;
     PCAWorkspace& p = ctx->pca;
-    // [G | S | n_valid]; both buffers stand before a copy is enqueued
-    int rc = nn_reserve(ctx, p.d_mom, (size_t)(D * D + D + 1));
+    Landing land(p.d_out);
+    const int G = land.add(G_host, D * D), S = land.add(S_host, D), n_valid = land.add(n_valid_host, 1);
+    int rc = land.reserve(ctx);                               // both buffers stand before a copy is enqueued
     if (!rc) rc = nn_upload_rows(ctx, rows_host, n);
-    if (rc) return rc;
-    int64_t* const G = p.d_mom.get();
-    if ((rc = pca_moments(ctx, fn, ctx->nn.d_base, n, G, G + D * D, G + D * D + D))) return rc;
-    GNN_HIP(hipMemcpyAsync(G_host, G, (size_t)D * D * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(S_host, G + D * D, (size_t)D * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(n_valid_host, G + D * D + D, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
-    return GNN_OK;
+    if (!rc) rc = pca_moments(ctx, fn, ctx->nn.d_base, n, land.dev<int64_t>(G), land.dev<int64_t>(S), land.dev<int64_t>(n_valid));
+    if (!rc) rc = land.copy_out(ctx);
+    if (!rc) p.passes.settle();
+    return rc;
 }
 
 extern "C" int gnn_pca_project_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, const float* components_dev, int ncomp,
@@ -396,17 +375,19 @@ extern "C" int gnn_pca_project(gnn_ctx* ctx, const float* rows_host, int64_t n, 
     if (int rc = check_ctx(ctx)) return rc;
     PCAWorkspace& p = ctx->pca;
     // [components ncomp x 512 | off ncomp]; every buffer stands before a copy is enqueued
+    Landing land(p.d_out);
+    land.add(out_host, n * ncomp);
     int rc = nn_reserve(ctx, p.d_comp, (size_t)(NCOMP_MAX * D + NCOMP_MAX));
-    if (!rc) rc = nn_reserve(ctx, p.d_out, (size_t)n * ncomp);
+    if (!rc) rc = land.reserve(ctx);
     if (!rc) rc = nn_upload_rows(ctx, rows_host, n);
     if (rc) return rc;
     float* const off = p.d_comp.get() + NCOMP_MAX * D;
     GNN_HIP(hipMemcpyAsync(p.d_comp.get(), components_host, (size_t)ncomp * D * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     if (off_host_or_null) GNN_HIP(hipMemcpyAsync(off, off_host_or_null, (size_t)ncomp * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = pca_project(ctx, ctx->nn.d_base, n, p.d_comp.get(), ncomp, off_host_or_null ? off : nullptr, p.d_out.get()))) return rc;
-    GNN_HIP(hipMemcpyAsync(out_host, p.d_out.get(), (size_t)n * ncomp * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
-    return GNN_OK;
+    rc = pca_project(ctx, ctx->nn.d_base, n, p.d_comp.get(), ncomp, off_host_or_null ? off : nullptr, land.dev<float>(0));
+    if (!rc) rc = land.copy_out(ctx);
+    if (!rc) p.passes.settle();
+    return rc;
 }
 
 extern "C" int gnn_debug_set_pca_split(gnn_ctx* ctx, int64_t rows_per_workgroup) {
@@ -422,11 +403,5 @@ extern "C" int gnn_debug_set_pca_split(gnn_ctx* ctx, int64_t rows_per_workgroup)
 
 extern "C" int gnn_debug_pca_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
     if (int rc = check_ctx(ctx)) return rc;
-    PCAWorkspace& p = ctx->pca;
-    if (!p.pending.empty()) {
-        GNN_HIP(hipStreamSynchronize(ctx->stream));
-        for (const RoundTimer& t : p.pending) t.file(p.pass_ms);
-        p.pending.clear();
-    }
-    return nn_round_ms_out("gnn_debug_pca_pass_ms", p.pass_ms, ms_out, capacity, n_out);
+    return ctx->pca.passes.out(ctx, "gnn_debug_pca_pass_ms", ms_out, capacity, n_out);
 }

@@ -67,7 +67,6 @@ constexpr float Q_ONE = 1048576.f;               // 2^20
 constexpr double PENALTY_MAX = 4096.0;
 constexpr int TILE_MAX = 4096;
 constexpr int RB = 256;                          // bins per block of the region kernels
-constexpr int SCAN_THREADS = 1024;               // the one block that scans the block counts
 
 typedef long long i64;
 __host__ __device__ inline i64 imin(i64 a, i64 b) { return a < b ? a : b; }
@@ -225,32 +224,7 @@ __global__ __launch_bounds__(RB) void region_flag_kernel(const uint8_t* __restri
     if (threadIdx.x == 0) blk_count[blockIdx.x] = n;
 }
 
-// ---- 6b: exclusive prefix sums of the block counts, and their total behind them: ONE block; thread i owns a run of counts
-__global__ __launch_bounds__(SCAN_THREADS) void block_offsets_kernel(const int32_t* __restrict__ blk_count, int64_t n_blocks,
-                                                                     int64_t* __restrict__ blk_off) {
-    __shared__ int64_t run[SCAN_THREADS];
-    const int64_t per = (n_blocks + SCAN_THREADS - 1) / SCAN_THREADS;
-    const int64_t a = imin(n_blocks, threadIdx.x * per), e = imin(n_blocks, a + per);
-    int64_t s = 0;
-    for (int64_t i = a; i < e; ++i) s += blk_count[i];
-    run[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t acc = 0;
-        for (int i = 0; i < SCAN_THREADS; ++i) {
-            const int64_t v = run[i];
-            run[i] = acc;
-            acc += v;
-        }
-        blk_off[n_blocks] = acc;
-    }
-    __syncthreads();
-    s = run[threadIdx.x];
-    for (int64_t i = a; i < e; ++i) {
-        blk_off[i] = s;
-        s += blk_count[i];
-    }
-}
+// ---- 6b: exclusive prefix sums of the block counts, and their total behind them: nn_scan (gnn_nn_host.h)
 
 // ---- 6c: region r of bin b = (flags before b, itself included) - 1.  The thread of a region's first bin writes contig, lo, state;
 // the first thread of every run of one region inside the block sums the run's q and evidence and adds them to the region.
@@ -445,8 +419,7 @@ extern "C" int gnn_call_regions(gnn_ctx* ctx, const float* track_host, const int
         ProfScope prof(ctx, GNN_K_REGIONS);
         hipLaunchKernelGGL(region_flag_kernel, dim3((unsigned)n_blocks), dim3(RB), 0, stream, w.d_state.get(), d_bin, n_contigs, n_bins,
                            w.d_flag.get(), w.d_blk_count.get());
-        hipLaunchKernelGGL(block_offsets_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, w.d_blk_count.get(), n_blocks, w.d_blk_off.get());
-        GNN_HIP(hipGetLastError());
+        if ((rc = nn_scan(stream, w.d_blk_count, n_blocks, w.d_blk_off, nullptr))) return rc;
     }
     int64_t n_regions = 0;
     GNN_HIP(hipMemcpyAsync(&n_regions, w.d_blk_off + n_blocks, sizeof(int64_t), hipMemcpyDeviceToHost, stream));

@@ -34,7 +34,6 @@
 namespace gnn {
 namespace {
 
-constexpr int64_t N_MAX = (int64_t)1 << 31;      // a key holds its row in 32 bits, columns are int32 in the tile kernel
 
 enum : uint8_t { ST_INVALID = 0, ST_UNDECIDED = 1, ST_FRESH = 2, ST_REP = 3, ST_MEMBER = 4 };
 enum : unsigned { FL_HIT = 1, FL_WAIT = 2 };
@@ -230,29 +229,10 @@ __global__ __launch_bounds__(256) void rp_summarise_kernel(int64_t n, const int6
 int check_rep_args(const char* fn, const void* rows, int64_t n, float threshold, int metric, const void* rep, const void* sim, const void* size,
                    const void* rounds) {
     const std::string f(fn);
-    if (n < 0 || n >= N_MAX) {
-        set_error(f + ": " + std::to_string(n) + " rows is outside [0, 2^31)");
-        return GNN_ERR_ARG;
-    }
-    if (!std::isfinite(threshold)) {
-        set_error(f + ": threshold " + std::to_string(threshold) + " is outside (-inf, inf): a finite f32 is required");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_rows(f, n, "rows")) return rc;
+    if (int rc = nn_check_threshold(f, threshold)) return rc;
     if (int rc = nn_check_metric(f, metric)) return rc;
-    if (n > 0 && (!rows || !rep || !sim || !size || !rounds)) {
-        set_error("bad argument to " + f + ": the rows, the three outputs and rounds are required");
-        return GNN_ERR_ARG;
-    }
-    return GNN_OK;
-}
-
-// 8 bytes of the counters to the host, behind everything enqueued: the one synchronise of a round
-int rp_read_count(gnn_ctx* ctx, int which, unsigned long long* out) {
-    RepresentativeWorkspace& p = ctx->rp;
-    GNN_HIP(hipMemcpyAsync(p.h_count.get(), p.count.get() + which, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
-    *out = p.h_count.get()[0];
-    return GNN_OK;
+    return nn_check_required(f, n == 0 || (rows && rep && sim && size && rounds), "the rows, the three outputs and rounds");
 }
 
 // n > 0 rows on the device, in priority order -> the three arrays on the device and the number of rounds.  Enqueued on the ctx's
@@ -269,13 +249,11 @@ int rp_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, float
     if (!rc) rc = nn_reserve(ctx, p.size, (size_t)padded);
     if (!rc) rc = nn_reserve(ctx, p.row_live, (size_t)(padded / 64));
     if (!rc) rc = nn_reserve(ctx, p.col_live, (size_t)(padded / 32));
-    if (!rc) rc = nn_reserve(ctx, p.count, 2);
-    if (!rc) rc = p.h_count.reserve(1);
+    if (!rc) rc = p.count.reserve(ctx, 2);
     const int64_t tiles = padded / QT;
     int64_t split_rows, splits;
     if (!rc) rc = nn_tile_grid(ctx, fn, "rows", tiles, n, &split_rows, &splits);
     if (rc) return rc;
-    const dim3 per_row((unsigned)((n + 255) / 256)), per_padded((unsigned)((padded + 255) / 256)), tile_grid((unsigned)tiles, (unsigned)splits);
     TileArgs a;
     a.frag = w.bfrag.get();
     a.state = p.state.get();
@@ -287,16 +265,16 @@ int rp_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, float
     a.threshold = threshold;
     a.flag = p.flag.get();
     a.key = p.key.get();
-    p.round_ms.clear();
+    p.rounds.begin();
     unsigned long long undecided = 0, members = 0;
     {
         ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-        GNN_HIP(hipMemsetAsync(p.count.get(), 0, 2 * sizeof(unsigned long long), ctx->stream));
-        hipLaunchKernelGGL(rp_init_kernel, per_padded, dim3(256), 0, ctx->stream, n, padded, w.bvalid.get(), p.state.get(), p.flag.get(),
-                           p.key.get(), p.size.get(), p.row_live.get(), p.col_live.get(), p.count.get());
-        GNN_HIP(hipGetLastError());
+        if ((rc = p.count.zero(ctx, 0, 2))) return rc;
+        if ((rc = launch_1d(rp_init_kernel, padded, ctx->stream, n, padded, w.bvalid, p.state, p.flag, p.key, p.size, p.row_live, p.col_live,
+                            p.count.dev())))
+            return rc;
     }
-    if ((rc = rp_read_count(ctx, 0, &undecided))) return rc;
+    if ((rc = p.count.read(ctx, 0, 1, &undecided))) return rc;       // the one synchronise of a round
     // One round per pass.  Ends: the undecided row of smallest rank is decided in every round - nothing undecided precedes it, so it
     // is flagged HIT (a member) or not at all (a representative) -, the count strictly falls and at most n rounds find a row to
     // decide.  The loop is bounded by n + 1 whatever the device answers, and a round that does not lower the count is an error.
@@ -307,20 +285,15 @@ int rp_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, float
                       std::to_string(n) + " rows");
             return GNN_ERR_STATE;
         }
-        RoundTimer timer;
         {
-            ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-            timer = {prof.a, prof.b};
-            hipLaunchKernelGGL(rp_tile_kernel<false>, tile_grid, dim3(256), 0, ctx->stream, a);
-            GNN_HIP(hipGetLastError());
-            hipLaunchKernelGGL(rp_decide_kernel, per_padded, dim3(256), 0, ctx->stream, padded, p.state.get(), p.flag.get(), p.row_live.get(),
-                               p.col_live.get(), p.count.get());
-            GNN_HIP(hipGetLastError());
+            PassLog::Scope pass(ctx, p.rounds);
+            if ((rc = launch_tiles(rp_tile_kernel<false>, tiles, splits, ctx->stream, a))) return rc;
+            if ((rc = launch_1d(rp_decide_kernel, padded, ctx->stream, padded, p.state, p.flag, p.row_live, p.col_live, p.count.dev()))) return rc;
         }
         unsigned long long now = 0;
-        if ((rc = rp_read_count(ctx, 0, &now))) return rc;
+        if ((rc = p.count.read(ctx, 0, 1, &now))) return rc;
         ++rounds;
-        timer.file(p.round_ms);            // behind the synchronise of rp_read_count
+        p.rounds.settle();
         if (now >= undecided) {
             set_error(std::string(fn) + ": round " + std::to_string(rounds) + " left " + std::to_string(now) + " of " + std::to_string(undecided) +
                       " undecided rows undecided: the count must fall in every round");
@@ -328,16 +301,11 @@ int rp_run(gnn_ctx* ctx, const char* fn, const float* rows_dev, int64_t n, float
         }
         undecided = now;
     }
-    if ((rc = rp_read_count(ctx, 1, &members))) return rc;
+    if ((rc = p.count.read(ctx, 1, 1, &members))) return rc;
     ProfScope prof(ctx, GNN_K_NEIGHBOURS);
-    if (members > 0) {
-        hipLaunchKernelGGL(rp_tile_kernel<true>, tile_grid, dim3(256), 0, ctx->stream, a);
-        GNN_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(rp_finish_kernel, per_row, dim3(256), 0, ctx->stream, n, p.state.get(), p.key.get(), p.size.get(), rep, sim);
-    GNN_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rp_summarise_kernel, per_row, dim3(256), 0, ctx->stream, n, rep, p.size.get(), size);
-    GNN_HIP(hipGetLastError());
+    if (members > 0 && (rc = launch_tiles(rp_tile_kernel<true>, tiles, splits, ctx->stream, a))) return rc;
+    if ((rc = launch_1d(rp_finish_kernel, n, ctx->stream, n, p.state, p.key, p.size, rep, sim))) return rc;
+    if ((rc = launch_1d(rp_summarise_kernel, n, ctx->stream, n, rep, p.size, size))) return rc;
     *rounds_out = rounds;
     return GNN_OK;
 }
@@ -370,20 +338,15 @@ extern "C" int gnn_representatives(gnn_ctx* ctx, const float* rows_host, int64_t
     }
     NeighbourWorkspace& w = ctx->nn;
     RepresentativeWorkspace& p = ctx->rp;
-    int rc = nn_reserve(ctx, p.d_out, (size_t)(2 * n + (n + 1) / 2));      // both buffers stand before the copy is enqueued
+    Landing land(p.d_out);
+    const int rep = land.add(rep_host, n), sim = land.add(sim_host, n), size = land.add(size_host, n);
+    int rc = land.reserve(ctx);                               // both buffers stand before the copy is enqueued
     if (!rc) rc = nn_upload_rows(ctx, rows_host, n);
-    if (rc) return rc;
-    int64_t* const out = p.d_out;
-    float* const sim = reinterpret_cast<float*>(out + 2 * n);
-    if ((rc = rp_run(ctx, fn, w.d_base, n, threshold, metric, out, sim, out + n, rounds_host))) return rc;
-    GNN_HIP(hipMemcpyAsync(rep_host, out, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(size_host, out + n, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipMemcpyAsync(sim_host, sim, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    GNN_HIP(hipStreamSynchronize(ctx->stream));
-    return GNN_OK;
+    if (!rc) rc = rp_run(ctx, fn, w.d_base, n, threshold, metric, land.dev<int64_t>(rep), land.dev<float>(sim), land.dev<int64_t>(size), rounds_host);
+    return rc ? rc : land.copy_out(ctx);
 }
 
 extern "C" int gnn_debug_representative_round_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
     if (int rc = check_ctx(ctx)) return rc;
-    return nn_round_ms_out("gnn_debug_representative_round_ms", ctx->rp.round_ms, ms_out, capacity, n_out);
+    return ctx->rp.rounds.out(ctx, "gnn_debug_representative_round_ms", ms_out, capacity, n_out);
 }

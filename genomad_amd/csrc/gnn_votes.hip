@@ -26,7 +26,6 @@ namespace gnn {
 namespace {
 
 constexpr int64_t N_MAX = (int64_t)1 << 30;      // |rint(s * 2^32)| <= 2^32 + 2^10 per voter: the int64 sums of 2^30 base rows stay below 2^63
-constexpr int64_t NQ_MAX = (int64_t)1 << 31;
 constexpr int C_MAX = 1024;
 constexpr int LDS_C = 16;                        // classes whose cells a workgroup holds in LDS: 64 x 16 x (4 + 8 + 8) B = 20 KB
 constexpr int64_t QSLAB = 262144;                // query rows per launch: bounds the query fragments (512 MB) and the keys (8 B per class and row)
@@ -184,10 +183,7 @@ int check_vote_args(const char* fn, const void* query, int64_t nq, const void* b
                     float threshold, const void* count, const void* weight, const void* nearest, const void* nearest_sim) {
     const std::string f(fn);
     const bool self = !base;
-    if (nq < 0 || nq >= NQ_MAX) {
-        set_error(f + ": n_query " + std::to_string(nq) + " is outside [0, 2^31)");
-        return GNN_ERR_ARG;
-    }
+    if (int rc = nn_check_rows(f, nq, "n_query")) return rc;
     const int64_t rows = self ? nq : nb;
     if (rows < 0 || rows > N_MAX) {
         set_error(f + ": " + std::to_string(rows) + " base rows is outside [0, 2^30]: the int64 sums of more rows could overflow");
@@ -197,22 +193,10 @@ int check_vote_args(const char* fn, const void* query, int64_t nq, const void* b
         set_error(f + ": n_classes " + std::to_string(n_classes) + " is outside [1, " + std::to_string(C_MAX) + "]");
         return GNN_ERR_ARG;
     }
-    if (!std::isfinite(threshold)) {
-        set_error(f + ": threshold " + std::to_string(threshold) + " is outside (-inf, inf): a finite f32 is required");
-        return GNN_ERR_ARG;
-    }
-    if ((rows > 0 && !label) || (nq > 0 && (!query || !count || !weight || !nearest || !nearest_sim))) {
-        set_error("bad argument to " + f + ": the query, the labels and the four outputs are required");
-        return GNN_ERR_ARG;
-    }
-    return GNN_OK;
+    if (int rc = nn_check_threshold(f, threshold)) return rc;
+    return nn_check_required(f, (rows == 0 || label) && (nq == 0 || (query && count && weight && nearest && nearest_sim)),
+                             "the query, the labels and the four outputs");
 }
-
-// a pass's events, filed by gnn_debug_vote_pass_ms behind a synchronise of its own
-struct PassScope {
-    ProfScope prof;
-    PassScope(gnn_ctx* ctx) : prof(ctx, GNN_K_NEIGHBOURS) { ctx->vt.pending.push_back({prof.a, prof.b}); }
-};
 
 // The votes over a base on the device, the queries in slabs of QSLAB rows.  self: the query fragments are the base's own.  Otherwise
 // the query rows are on the device (query_dev) or go up slab by slab (query_host).  to_host: the four outputs are host pointers; every
@@ -223,25 +207,24 @@ int vt_run(gnn_ctx* ctx, const char* fn, const float* query_dev, const float* qu
            float* nearest_sim, bool to_host) {
     NeighbourWorkspace& w = ctx->nn;
     VoteWorkspace& v = ctx->vt;
-    v.pending.clear();
-    v.pass_ms.clear();
+    v.passes.begin();
     const int64_t padded = round_up(nb, QT);
     int rc = nn_prepare(ctx, base_dev, nb, GNN_KNN_COSINE, w.bfrag, w.bvalid);
     if (!rc) rc = nn_reserve(ctx, v.blabel, (size_t)std::max<int64_t>(padded, 1));
-    if (!rc) rc = nn_reserve(ctx, v.flag, (size_t)1);
-    if (!rc) rc = v.h_flag.reserve(1);
+    if (!rc) rc = v.flag.reserve(ctx, 1);
     if (rc) return rc;
     if (nb > 0) {
         {
-            PassScope pass(ctx);
-            GNN_HIP(hipMemsetAsync(v.flag.get(), 0, sizeof(unsigned long long), ctx->stream));
+            PassLog::Scope pass(ctx, v.passes);
+            if ((rc = v.flag.zero(ctx, 0, 1))) return rc;
             if ((rc = launch_1d(vt_label_kernel, padded, ctx->stream, nb, padded, n_classes, label_dev, w.bvalid.get(), v.blabel.get(),
-                                v.flag.get())))
+                                v.flag.dev())))
                 return rc;
         }
-        GNN_HIP(hipMemcpyAsync(v.h_flag.get(), v.flag.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        GNN_HIP(hipStreamSynchronize(ctx->stream));
-        if (*v.h_flag.get()) {
+        unsigned long long bad = 0;
+        if ((rc = v.flag.read(ctx, 0, 1, &bad))) return rc;
+        v.passes.settle();
+        if (bad) {
             set_error(std::string(fn) + ": a label is outside [-1, " + std::to_string(n_classes) + ")");
             return GNN_ERR_ARG;
         }
@@ -268,19 +251,21 @@ int vt_run(gnn_ctx* ctx, const char* fn, const float* query_dev, const float* qu
         unsigned long long* wgt_dev = reinterpret_cast<unsigned long long*>(weight + q0 * n_classes);
         int64_t* near_dev = nearest + q0 * n_classes;
         float* nsim_dev = nearest_sim + q0 * n_classes;
+        Landing land(v.d_out);
         if (to_host) {
-            // [count | weight | nearest] int64, then nearest_sim (f32)
-            if ((rc = nn_reserve(ctx, v.d_out, (size_t)(3 * cells + (cells + 1) / 2)))) return rc;
-            cnt_dev = reinterpret_cast<unsigned long long*>(v.d_out.get());
-            wgt_dev = cnt_dev + cells;
-            near_dev = v.d_out.get() + 2 * cells;
-            nsim_dev = reinterpret_cast<float*>(v.d_out.get() + 3 * cells);
+            const int c = land.add(count + q0 * n_classes, cells), g = land.add(weight + q0 * n_classes, cells), nr = land.add(near_dev, cells),
+                      ns = land.add(nsim_dev, cells);
+            if ((rc = land.reserve(ctx))) return rc;
+            cnt_dev = land.dev<unsigned long long>(c);
+            wgt_dev = land.dev<unsigned long long>(g);
+            near_dev = land.dev<int64_t>(nr);
+            nsim_dev = land.dev<float>(ns);
         }
         const int64_t tiles = (m + QT - 1) / QT;
         int64_t split_rows, splits;
         if ((rc = nn_tile_grid(ctx, fn, "base rows", tiles, nb, &split_rows, &splits))) return rc;
         {
-            PassScope pass(ctx);
+            PassLog::Scope pass(ctx, v.passes);
             GNN_HIP(hipMemsetAsync(cnt_dev, 0, (size_t)cells * sizeof(unsigned long long), ctx->stream));
             GNN_HIP(hipMemsetAsync(wgt_dev, 0, (size_t)cells * sizeof(unsigned long long), ctx->stream));
             GNN_HIP(hipMemsetAsync(v.key.get(), 0, (size_t)cells * sizeof(unsigned long long), ctx->stream));
@@ -302,21 +287,16 @@ int vt_run(gnn_ctx* ctx, const char* fn, const float* query_dev, const float* qu
                 a.key = v.key.get();
                 void (*const kernel)(VoteArgs) = n_classes <= v.lds_c ? (self ? vt_tile_kernel<true, true> : vt_tile_kernel<true, false>)
                                                                        : (self ? vt_tile_kernel<false, true> : vt_tile_kernel<false, false>);
-                hipLaunchKernelGGL(kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, ctx->stream, a);
-                GNN_HIP(hipGetLastError());
+                if ((rc = launch_tiles(kernel, tiles, splits, ctx->stream, a))) return rc;
             }
         }
         {
-            PassScope pass(ctx);
+            PassLog::Scope pass(ctx, v.passes);
             if ((rc = launch_1d(vt_finish_kernel, cells, ctx->stream, cells, v.key.get(), near_dev, nsim_dev))) return rc;
         }
         if (to_host) {
-            const int64_t o = q0 * n_classes;
-            GNN_HIP(hipMemcpyAsync(count + o, cnt_dev, (size_t)cells * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-            GNN_HIP(hipMemcpyAsync(weight + o, wgt_dev, (size_t)cells * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-            GNN_HIP(hipMemcpyAsync(nearest + o, near_dev, (size_t)cells * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-            GNN_HIP(hipMemcpyAsync(nearest_sim + o, nsim_dev, (size_t)cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-            GNN_HIP(hipStreamSynchronize(ctx->stream));      // the landing buffer and d_query serve the next slab
+            if ((rc = land.copy_out(ctx))) return rc;         // synchronised: the landing buffer and d_query serve the next slab
+            v.passes.settle();
         }
     }
     return GNN_OK;
@@ -373,11 +353,5 @@ extern "C" int gnn_debug_set_vote_lds(gnn_ctx* ctx, int max_classes) {
 
 extern "C" int gnn_debug_vote_pass_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out) {
     if (int rc = check_ctx(ctx)) return rc;
-    VoteWorkspace& v = ctx->vt;
-    if (!v.pending.empty()) {
-        GNN_HIP(hipStreamSynchronize(ctx->stream));
-        for (const RoundTimer& t : v.pending) t.file(v.pass_ms);
-        v.pending.clear();
-    }
-    return nn_round_ms_out("gnn_debug_vote_pass_ms", v.pass_ms, ms_out, capacity, n_out);
+    return ctx->vt.passes.out(ctx, "gnn_debug_vote_pass_ms", ms_out, capacity, n_out);
 }

@@ -1042,14 +1042,28 @@ class NNEngine:
         """the name of a metric given by name or by the library's code"""
         return metric if isinstance(metric, str) else {v: k for k, v in _lib.KNN_METRICS.items()}[int(metric)]
 
-    def _debug_ms(self, fn) -> np.ndarray:
-        """the float64 milliseconds a ``gnn_debug_*_ms`` entry point keeps: ask for their number, allocate, ask again"""
+    def _debug_ms(self, fn, dtype=np.float64) -> np.ndarray:
+        """the float64 milliseconds a ``gnn_debug_*_ms`` entry point keeps (or the ``dtype`` values of another entry point of that
+        shape): ask for their number, allocate, ask again"""
         n = C.c_int64(0)
         check(fn(self.ctx, None, 0, C.addressof(n)))
-        ms = np.zeros(n.value, np.float64)
+        ms = np.zeros(n.value, dtype)
         if n.value:
             check(fn(self.ctx, ms.ctypes.data, n.value, C.addressof(n)))
         return ms
+
+    def _count_then_fill(self, count, fill, n_indptr, max_edges, too_many):
+        """what :meth:`graph` and :meth:`match` share: ``count(indptr_ptr, total_ptr)``, the verdict on ``max_edges`` (``too_many``
+        words the ``ValueError``), then ``fill(col_ptr, sim_ptr, m)`` into arrays of the counted size.  Returns (indptr, col, sim)."""
+        indptr = np.empty(n_indptr, dtype=np.int64)
+        total = C.c_int64(0)
+        check(count(indptr.ctypes.data, C.addressof(total)))
+        m = int(total.value)
+        if m > int(max_edges):
+            raise ValueError(f"{too_many(m)}, more than max_edges = {int(max_edges)}: raise the threshold or max_edges")
+        col, sim = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float32)
+        check(fill(col.ctypes.data, sim.ctypes.data, m))
+        return indptr, col, sim
 
     def neighbours(self, query, base=None, k=10, metric="cosine"):
         """Nearest neighbours among encoder embeddings (``gnn_neighbours``; the definition is ``sequence.nearest_neighbours``): for
@@ -1130,18 +1144,13 @@ class NNEngine:
         r = _sequence.neighbour_rows(rows, "rows")
         self._check_metric(metric)
         code = self._knn_metric(metric)
-        n = len(r)
-        indptr = np.empty(n + 1, dtype=np.int64)
-        total = C.c_int64(0)
-        check(self.lib.gnn_graph_count(self.ctx, r.ctypes.data, n, float(threshold), code, indptr.ctypes.data, C.addressof(total)))
-        m = int(total.value)
-        if m > int(max_edges):
-            raise ValueError(f"the graph has {m} edges at the threshold {float(np.float32(threshold)):g}, more than max_edges = "
-                             f"{int(max_edges)}: raise the threshold or max_edges")
-        col, sim = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float32)
-        check(self.lib.gnn_graph_fill(self.ctx, n, float(threshold), code, col.ctypes.data, sim.ctypes.data, m))
+        n, t = len(r), float(threshold)
+        csr = self._count_then_fill(
+            lambda indptr, total: self.lib.gnn_graph_count(self.ctx, r.ctypes.data, n, t, code, indptr, total),
+            lambda col, sim, m: self.lib.gnn_graph_fill(self.ctx, n, t, code, col, sim, m), n + 1, max_edges,
+            lambda m: f"the graph has {m} edges at the threshold {float(np.float32(threshold)):g}")
         name = self._metric_name(metric)
-        return GraphResult.build((indptr, col, sim), _sequence.valid_rows(r, name), np.float32(threshold), name)
+        return GraphResult.build(csr, _sequence.valid_rows(r, name), np.float32(threshold), name)
 
     def graph_count_dev(self, rows_ptr: int, n: int, threshold, indptr_ptr: int, metric="cosine") -> int:
         """``gnn_graph_count_dev``: device pointers in (rows n x 512 f32) and out (indptr n + 1 int64); the engine's stream is
@@ -1177,20 +1186,13 @@ class NNEngine:
         b = _sequence.neighbour_rows(base, "base")
         self._check_metric(metric)
         code = self._knn_metric(metric)
-        nq, nb = len(q), len(b)
-        indptr = np.empty(nq + 1, dtype=np.int64)
-        total = C.c_int64(0)
-        check(self.lib.gnn_match_count(self.ctx, q.ctypes.data, nq, b.ctypes.data, nb, float(threshold), code, indptr.ctypes.data,
-                                       C.addressof(total)))
-        m = int(total.value)
-        if m > int(max_edges):
-            raise ValueError(f"there are {m} matches at the threshold {float(np.float32(threshold)):g}, more than max_edges = "
-                             f"{int(max_edges)}: raise the threshold or max_edges")
-        col, sim = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float32)
-        check(self.lib.gnn_match_fill(self.ctx, nq, nb, float(threshold), code, col.ctypes.data, sim.ctypes.data, m))
+        nq, nb, t = len(q), len(b), float(threshold)
+        csr = self._count_then_fill(
+            lambda indptr, total: self.lib.gnn_match_count(self.ctx, q.ctypes.data, nq, b.ctypes.data, nb, t, code, indptr, total),
+            lambda col, sim, m: self.lib.gnn_match_fill(self.ctx, nq, nb, t, code, col, sim, m), nq + 1, max_edges,
+            lambda m: f"there are {m} matches at the threshold {float(np.float32(threshold)):g}")
         name = self._metric_name(metric)
-        return MatchResult.build((indptr, col, sim), _sequence.valid_rows(q, name), _sequence.valid_rows(b, name), np.float32(threshold),
-                                 name)
+        return MatchResult.build(csr, _sequence.valid_rows(q, name), _sequence.valid_rows(b, name), np.float32(threshold), name)
 
     def match_count_dev(self, query_ptr: int, n_query: int, base_ptr: int, n_base: int, threshold, indptr_ptr: int, metric="cosine") -> int:
         """``gnn_match_count_dev``: device pointers in (query n_query x 512 f32, base n_base x 512 f32) and out (indptr n_query + 1
@@ -1338,12 +1340,7 @@ class NNEngine:
     def mcl_overflow(self) -> np.ndarray:
         """measurement only (``gnn_debug_mcl_overflow``): the columns that took the overflow path in the last :meth:`mcl` /
         :meth:`mcl_dev` call - int64 [the initial matrix, then every iteration]"""
-        n = C.c_int64(0)
-        check(self.lib.gnn_debug_mcl_overflow(self.ctx, None, 0, C.addressof(n)))
-        out = np.zeros(n.value, np.int64)
-        if n.value:
-            check(self.lib.gnn_debug_mcl_overflow(self.ctx, out.ctypes.data, n.value, C.addressof(n)))
-        return out
+        return self._debug_ms(self.lib.gnn_debug_mcl_overflow, np.int64)
 
     # -- spherical k-means ---------------------------------------------------------------
     def kmeans(self, rows, k, init=None, max_iter=_sequence.KMEANS_MAX_ITER_DEFAULT) -> KMeansResult:

@@ -3,7 +3,7 @@ the limits tests/test_graph_gpu.py stays away from.  The rows come from the gene
 tests/neighbours_data.py and tests/clusters_data.py; what is made here is only what the graph needs on top of them:
 
   integer_base, PREFIXES,     342 signed integer rows (every dot exact) and the prefixes and debug splits that sit on the 32-column
-  SCAN_CASES, counters        block, the 64-row tile, the 256-column step and the 1024 threads of gr_scan_kernel
+  SCAN_CASES, counters        block, the 64-row tile, the 256-column step and the 1024 threads of nn_scan_kernel
   two_range_base              lim.capped_base with pairs planted across column 65280 = SPLIT_MAX: the second range of
                               gr_tile_kernel, `t.b1 > t.r0 + 1`, `max(b0, r0)`, cnt[row * splits + 1], a segment that continues
                               from part 0 into part 1
@@ -25,7 +25,7 @@ SPLITS = (32, 100, 333, 4096, 0)          # tests/test_graph_gpu.py
 SIGN_THRESHOLDS = (-0.05, 0.0, 0.05)
 PREFIXES = (2, 31, 32, 33, 63, 64, 65, 255, 256, 257)
 PREFIX_SPLITS = (0, 32, 64, 96)
-SCAN_THREADS = 1024       # gnn_graph.hip
+SCAN_THREADS = 1024       # gnn_neighbours.hip
 SCAN_CASES = ((341, 128, 1023), (256, 64, 1024), (342, 128, 1026))       # (rows, debug split, n * splits)
 N_INTEGER = 342
 

@@ -7,7 +7,7 @@ used as they are -; what is made here is only what the rectangle needs on top of
   check_csr, dense,         a CSR by query row over (nq, nb): no `a < b`, (i, i) and both orientations are there
   exact_csr, check_exact
   integer_sides             the 342 signed integer rows split into 133 query and 209 base rows, with the negated row and its ties
-  SCAN_CASES                n_query * splits at 1023, 1024 and 1026 against 342 base rows: the 1024 threads of gr_scan_kernel
+  SCAN_CASES                n_query * splits at 1023, 1024 and 1026 against 342 base rows: the 1024 threads of nn_scan_kernel
   slab_queries              16454 query rows: more than one QSLAB = 16384 of the neighbour search, whose buffers the match fills with
                             ALL query rows at once
   two_range_sides           75 query rows against the 65350 rows of lim.capped_base: cnt[row * splits + 1], a segment that continues

@@ -10,7 +10,7 @@ sequence.call_regions: exact emissions over fractions, and a Viterbi pass that c
                 so `a tie stays`, `the lowest s'` and `the lowest s with maximal d` decide states, also on the first bin of a tile
   planted_ties  four contigs whose outcome hangs on one tie each, the run that ties laid across a tile seam; the regions are written
                 out by hand
-  long_track    262 845 bins: 1 027 blocks of 256 (block_offsets_kernel with more than one count per thread), 1 024 tiles in one
+  long_track    262 845 bins: 1 027 blocks of 256 (nn_scan_kernel with more than one count per thread), 1 024 tiles in one
                 contig (carry_kernel, carry_back_kernel), and at the largest penalty one region whose qsum passes 2^32"""
 import functools
 from fractions import Fraction

@@ -6,7 +6,7 @@ conditions: tests/graph_limits_data.py, tests/test_graph_limits_host.py).  Which
                      that gnn_neighbours returns; the values of NN_PRODUCTS (gnn_nn_frag.h) bit for bit those of nn_tile_kernel on
                      six tiles, two steps and, under the split of 32, eleven parts.
   B  sizes, scan     nn_tile_range / nn_step_column (gnn_nn_frag.h) with n on and beside the 32-column block, the 64-row tile and the
-                     256-column step: `t.b1 > t.r0 + 1`, `min(blk, last_blk)`, `col < t.b1`; gr_scan_kernel with n * splits at 1023,
+                     256-column step: `t.b1 > t.r0 + 1`, `min(blk, last_blk)`, `col < t.b1`; nn_scan_kernel with n * splits at 1023,
                      1024 and 1026: `per = (m + SCAN_THREADS - 1) / SCAN_THREADS`, `min(m, threadIdx.x * per)`, the runs of two.
   C  row scales      nn_prepare_kernel (gnn_neighbours.hip) as the graph reaches it: `frexpf(amax, &ex)` / `ldexpf(x[e], -ex)` from
                      all-subnormal rows to FLT_MAX, one-hot rows, heavy tails; under dot `a NaN fails >=` in gr_tile_kernel for rows

@@ -5,7 +5,7 @@ conditions: tests/match_limits_data.py, tests/test_match_limits_host.py).  Which
                      negative, a zero and a tied threshold; `a.sim[at] = acc[mb][nb][r] * a.scale` on negative values and on an
                      exact zero, which must be +0; the values bit for bit those of nn_tile_kernel on three query tiles and two steps.
   B  borders, scan   nn_tile_range(..., upper = false) / nn_step_column with n_query and n_base on and beside the 32-column block, the
-                     64-row tile and the 256-column step, with rows that differ; gr_scan_kernel with n_query * splits at 1023, 1024
+                     64-row tile and the 256-column step, with rows that differ; nn_scan_kernel with n_query * splits at 1023, 1024
                      and 1026.
   C  slabs           gr_prepare: ALL query rows into qfrag / qvalid at once, 16454 of them, where nn_search works in slabs of 16384;
                      the neighbour search and a small match on the same engine afterwards.

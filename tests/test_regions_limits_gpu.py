@@ -8,7 +8,7 @@ np.array_equal with dtype and shape, against sequence.call_regions.  What each g
   ties           dp_state's `a tie stays` and `the lowest s'`, carry_kernel's `lowest s with maximal d`, at every penalty and tile,
                  tile 4096 (TILE_MAX) included; planted ties across a tile seam, against regions written by hand; the host's rint of
                  penalty * 2^20 on penalties between two steps
-  size           1 027 blocks (block_offsets_kernel with two counts per thread), 1 024 tiles at the default tile and 262 139 at tile 1
+  size           1 027 blocks (nn_scan_kernel with two counts per thread), 1 024 tiles at the default tile and 262 139 at tile 1
                  in one contig (carry_kernel, carry_back_kernel), a region across seven blocks, and one region of 262 139 bins whose
                  qsum needs the high word of region_emit_kernel's 64-bit atomics
   building block bin_offsets[0] > 0 with bins before and behind that belong to no contig; two calls with no sync between, the second
