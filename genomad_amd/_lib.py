@@ -157,6 +157,11 @@ SIGNATURES = {
     "gnn_debug_mcl_groups": (_int, [_vp, _int]),
     "gnn_debug_mcl_ms": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_debug_mcl_overflow": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_spread": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_spread_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_debug_spread_groups": (_int, [_vp, _int]),
+    "gnn_debug_spread_skip": (_int, [_vp, _int]),
+    "gnn_debug_spread_ms": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_kmeans": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_kmeans_dev": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_centroids": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp]),

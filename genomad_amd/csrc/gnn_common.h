@@ -363,6 +363,32 @@ struct MclWorkspace {
     std::vector<int64_t> overflow;               // the last call's overflow columns: [initial matrix, then every iteration]
 };
 
+// ---- label spreading (gnn_spread.hip): persistent, grow-only.  The symmetric graph with its transition weights (8 B per entry, 20 B per
+// row), two score matrices of 4 B per (row, class), 18 B per row of seeds, marks, lists and `first`, one counter per iteration and, for
+// gnn_spread alone, the graph, the labels and its 24 B of results per row.
+struct SpreadWorkspace {
+    int groups = 0;                              // workgroups of an iteration (gnn_debug_spread_groups); 0: the library's choice; no result depends on it
+    bool skip = true;                            // the dirty-row rule (gnn_debug_spread_skip); no result depends on it
+    DevBuf<uint8_t> ok;                          // [n]: the row takes part
+    DevBuf<int32_t> deg;                         // the symmetric graph: entries at the row, both ends counted
+    DevBuf<int64_t> soff;                        // [n + 1]: their exclusive prefix sums
+    DevBuf<unsigned long long> cursor;           // [n]: where the row's next entry goes
+    DevBuf<int32_t> sidx;                        // [soff[n]]: the partner j
+    DevBuf<uint32_t> sp;                         // and the entry's weight q, then its transition mass p_ij
+    DevBuf<int32_t> seed;                        // [n]: the class of a seed, -1 for every other row
+    DevBuf<uint32_t> F[2];                       // [n][n_classes]: the scores, double buffered
+    DevBuf<uint8_t> mark[2];                     // [n]: the row or a neighbour of it changed in the iteration that wrote the array
+    DevBuf<int32_t> rows, long_rows;             // the rows an iteration computes: one wave each, one workgroup each
+    HostCounters count;                          // [iteration] changed rows; behind them [short rows, long rows, the verdict on graph and labels]
+    DevBuf<int64_t> d_indptr;                    // gnn_spread: the graph, its rows' validity and the labels
+    DevBuf<int32_t> d_col;
+    DevBuf<float> d_sim;
+    DevBuf<uint8_t> d_valid;
+    DevBuf<int64_t> d_label;
+    DevBuf<int64_t> d_out;                       // gnn_spread: [best (i32) | best_score (u32) | second_score (u32) | total (u64) | first (i32)], a Landing
+    PassLog passes;                              // profiling on: HIP-event time of the last call's [validate + symmetrise, then every iteration]
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -565,8 +591,10 @@ struct gnn_ctx {
     gnn::PCAWorkspace pca;                        // gnn_pca.hip
     gnn::VoteWorkspace vt;                        // gnn_votes.hip
     gnn::MclWorkspace mcl;                        // gnn_mcl.hip
+    gnn::SpreadWorkspace sprd;                    // gnn_spread.hip
     // every PassLog above: drain_profile settles them before an event they hold returns to event_pool
-    gnn::PassLog* const pass_logs[8] = {&rp.rounds, &lk.rounds, &lk.tree_rounds, &gr.passes, &km.passes, &pca.passes, &vt.passes, &mcl.passes};
+    gnn::PassLog* const pass_logs[9] = {&rp.rounds, &lk.rounds, &lk.tree_rounds, &gr.passes,  &km.passes, &pca.passes,
+                                        &vt.passes, &mcl.passes, &sprd.passes};
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;

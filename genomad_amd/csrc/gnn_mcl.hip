@@ -2,11 +2,8 @@
 // throughout - the definition is sequence.markov_clusters, and every output here equals it bit for bit.  ONE = 2^30 is a column's flow,
 // W = 2^24 a similarity of 1.  The matrix has a fixed width of `select` entries per column (idx int32, val uint32, rows ascending) and a
 // length per column, and is double buffered.
-//   validate     one thread per row: indptr rises within [0, nnz], every col lies in (row, n), every sim is finite and < 64.  The host
-//                reads one flag; GNN_ERR_ARG before anything else runs, the outputs untouched.  It also writes the rows' validity.
-//   symmetrise   the edges that exist (q = rint(sim * W) > 0, both ends valid) are counted at both ends (integer adds), the counts
-//                scanned by one block, the edges filed through per-row cursors.  A row's entries stand in arrival order: nothing
-//                downstream depends on it - the table is keyed by row index, and prune has a strict order.
+//   validate, symmetrise   gnn_csr_sym.h, shared with gnn_spread.hip.  A row's entries stand in arrival order: nothing downstream
+//                depends on it - the table is keyed by row index, and prune has a strict order.
 //   initial      mc_lds_kernel<true>: column j = prune(its edges' weights - of parallel edges the largest - and its loop).
 //   iteration    mc_lds_kernel<false>, one launch per iteration: workgroups loop over columns.  The products p_ik * p_kj of column j
 //                are added into an LDS table keyed by i: open addressing, the slot claimed by a compare-and-swap, the value a 64-bit
@@ -25,6 +22,7 @@
 #include <cmath>
 
 #include "gnn_nn_frag.h"
+#include "gnn_csr_sym.h"
 
 namespace gnn {
 namespace {
@@ -37,7 +35,7 @@ constexpr int PRECISION_MAX = 1 << 20;
 constexpr int MAX_ITER_MAX = 10000;
 constexpr int LDS_SLOTS = 4096;                  // the table: 16 KB of keys + 32 KB of sums - two workgroups per CU
 constexpr ull ONE = 1ull << 30;
-constexpr double W = 16777216.0;                 // 2^24
+constexpr double W = CSR_W;                      // 2^24
 constexpr int THREADS = 256;
 
 struct MclArgs {
@@ -427,58 +425,6 @@ __global__ __launch_bounds__(THREADS) void mc_dense_kernel(MclArgs a) {
     }
 }
 
-// ---- validate, symmetrise ------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ int64_t mc_weight(float sim) { return (int64_t)rint((double)sim * W); }      // exact product, ties to even
-
-// one thread per row; flag: a CSR that is none.  ok[i] = the row takes part
-__global__ __launch_bounds__(256) void mc_validate_kernel(int64_t n, int64_t nnz, const int64_t* __restrict__ indptr, const int32_t* __restrict__ col,
-                                                          const float* __restrict__ sim, const uint8_t* __restrict__ valid,
-                                                          uint8_t* __restrict__ ok, ull* __restrict__ flag) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    ok[i] = valid ? valid[i] != 0 : 1;
-    const int64_t b = indptr[i], e = indptr[i + 1];
-    bool bad = b < 0 || e < b || e > nnz || (i == 0 && b != 0) || (i == n - 1 && e != nnz);
-    if (!bad)
-        for (int64_t x = b; x < e; ++x) {                     // Ends: x grows towards e <= nnz
-            const int32_t c = col[x];
-            const float s = sim[x];
-            bad |= c <= i || c >= n || !(fabsf(s) < INFINITY) || !(s < 64.0f);
-        }
-    if (bad) atomicOr(flag, 1ull);
-}
-
-// one thread per row: its existing edges are counted at both ends (FILL false) or filed there (FILL true) through the cursors, every
-// store below the end of its row's segment
-template <bool FILL>
-__global__ __launch_bounds__(256) void mc_edges_kernel(int64_t n, const int64_t* __restrict__ indptr, const int32_t* __restrict__ col,
-                                                       const float* __restrict__ sim, const uint8_t* __restrict__ ok, int32_t* __restrict__ deg,
-                                                       const int64_t* __restrict__ soff, ull* __restrict__ cursor, int32_t* __restrict__ sidx,
-                                                       uint32_t* __restrict__ sq) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n || !ok[i]) return;
-    for (int64_t x = indptr[i]; x < indptr[i + 1]; ++x) {     // Ends: x grows towards the row's end
-        const int64_t c = col[x];
-        const int64_t q = mc_weight(sim[x]);
-        if (q <= 0 || !ok[c]) continue;
-        if (!FILL) {
-            atomicAdd(deg + i, 1);
-            atomicAdd(deg + c, 1);
-        } else {
-            const int64_t at = (int64_t)atomicAdd(cursor + i, 1ull), bt = (int64_t)atomicAdd(cursor + c, 1ull);
-            if (at < soff[i + 1]) {
-                sidx[at] = (int32_t)c;
-                sq[at] = (uint32_t)q;
-            }
-            if (bt < soff[c + 1]) {
-                sidx[bt] = (int32_t)i;
-                sq[bt] = (uint32_t)q;
-            }
-        }
-    }
-}
-
 // ---- interpret -----------------------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void mc_parent_kernel(int64_t n, int32_t* __restrict__ parent, int32_t* __restrict__ size) {
@@ -614,14 +560,9 @@ int mcl_run(gnn_ctx* ctx, const char* fn, const MclIn& in, int64_t* label, int64
         if (!rc) rc = nn_reserve(ctx, m.parent, (size_t)n);
         if (!rc) rc = nn_reserve(ctx, m.size, (size_t)n);
         if (rc) return rc;
-        GNN_HIP(hipMemsetAsync(m.deg.get(), 0, (size_t)n * sizeof(int32_t), ctx->stream));
         GNN_HIP(hipMemsetAsync(m.dense.get(), 0, (size_t)dense_groups * n * sizeof(ull), ctx->stream));
-        if ((rc = launch_1d(mc_edges_kernel<false>, n, ctx->stream, n, in.indptr, in.col, in.sim, m.ok.get(), m.deg.get(), m.soff.get(),
-                            m.cursor.get(), m.sidx.get(), m.sq.get())))
-            return rc;
-        if ((rc = nn_scan(ctx->stream, m.deg, n, m.soff, m.cursor))) return rc;
-        if ((rc = launch_1d(mc_edges_kernel<true>, n, ctx->stream, n, in.indptr, in.col, in.sim, m.ok.get(), m.deg.get(), m.soff.get(),
-                            m.cursor.get(), m.sidx.get(), m.sq.get())))
+        if ((rc = csr_symmetrise(ctx->stream, n, in.indptr, in.col, in.sim, m.ok.get(), m.deg.get(), m.soff.get(), m.cursor.get(), m.sidx.get(),
+                                 m.sq.get())))
             return rc;
     }
     MclArgs a;

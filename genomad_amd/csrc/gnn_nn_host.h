@@ -1,5 +1,5 @@
 // What the host code of the analyses over encoder embeddings shares (gnn_neighbours.hip, gnn_clusters.hip, gnn_density.hip,
-// gnn_representatives.hip, gnn_linkage.hip, gnn_graph.hip, gnn_kmeans.hip, gnn_pca.hip, gnn_votes.hip, gnn_mcl.hip).  Host only, and
+// gnn_representatives.hip, gnn_linkage.hip, gnn_graph.hip, gnn_kmeans.hip, gnn_pca.hip, gnn_votes.hip, gnn_mcl.hip, gnn_spread.hip).  Host only, and
 // included by gnn_common.h, in front of the workspaces that hold these types.
 //   the prologue: nn_check_metric / nn_check_rows / nn_check_threshold / nn_check_required (an argument check's text exists once),
 //   nn_metric_scale, nn_prepare, nn_tile_grid, nn_upload_rows, nn_scan (the one block-wide exclusive scan)
@@ -45,7 +45,7 @@ int nn_prepare(gnn_ctx* ctx, const float* rows_dev, int64_t n, int metric, DevBu
 int nn_tile_grid(const gnn_ctx* ctx, const std::string& fn, const char* noun, int64_t tiles, int64_t nb, int64_t* split_rows, int64_t* splits);
 int nn_upload_rows(gnn_ctx* ctx, const float* rows_host, int64_t n);      // n rows into ctx->nn.d_base, enqueued on the ctx's stream
 // Exclusive int64 prefix sums of the m counters into off[0 .. m), their total into off[m] and, unless cursor is NULL, the sums into
-// cursor[0 .. m) as well: one block on `stream` (the region calls, the similarity graph, the Markov clusters).
+// cursor[0 .. m) as well: one block on `stream` (the region calls, the similarity graph, the Markov clusters, label spreading).
 int nn_scan(hipStream_t stream, const int32_t* cnt, int64_t m, int64_t* off, unsigned long long* cursor);
 
 // ---- PassLog: the HIP-event times of the passes of an analysis's last call, while profiling is on.  begin() at the start of a call;

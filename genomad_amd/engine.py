@@ -396,6 +396,11 @@ class GraphResult(_Result):
         and ``max_iter`` as there"""
         return engine.mcl(self.indptr, self.col, self.sim, self.valid, **kw)
 
+    def spread(self, engine, label, n_classes, **kw) -> "SpreadResult":
+        """:meth:`NNEngine.spread` of this graph and its rows' validity: the labels of the seed rows spread along its edges, with
+        ``alpha``, ``clamp``, ``max_iter`` and ``scores`` as there"""
+        return engine.spread(self.indptr, self.col, self.sim, label, n_classes, valid=self.valid, **kw)
+
     @classmethod
     def build(cls, arrays, valid, threshold, metric):
         """from the (indptr, col, sim) of ``sequence.threshold_graph`` or the library, and the rows' validity"""
@@ -495,6 +500,25 @@ class MCLResult(_Result):
     def table(self, names=None):
         """``sequence.mcl_table``: one record per cluster - label, size, members, attractors"""
         return _sequence.mcl_table(self.label, self.size, self.is_attractor, names)
+
+
+class SpreadResult(_Result):
+    """What :meth:`NNEngine.spread` returns (the definition is ``sequence.label_spread``), per row: ``score`` (uint32 (n, n_classes),
+    units of 2^-30; None where it was not asked for), ``best`` (int32: the class of the largest score, ties to the smaller class; -1
+    where every score is 0), ``best_score``, ``second_score`` (uint32), ``total`` (uint64) and ``first`` (int32: the first iteration
+    behind which the row's total was not 0; -1); ``seed`` (bool: the valid rows that carried a label); ``iterations``, ``converged``,
+    ``changed`` (int64: the rows every iteration changed), ``n``, ``n_classes`` and the ``alpha`` and ``clamp`` it ran with.
+    :meth:`NNEngine.spread_dev` leaves the per-row arrays on the device: they are None here."""
+    FIELDS = _sequence.SPREAD_FIELDS + ("seed", "iterations", "converged", "changed", "n", "n_classes", "alpha", "clamp")
+
+    def predict(self, min_score=0.0):
+        """``sequence.spread_predict``: (label int64, confidence = best_score / total, margin = (best_score - second_score) / total)
+        per row; -1 / NaN where no class reached the row or its best score is below ``min_score``.  No calibrated probability."""
+        return _sequence.spread_predict(self.best, self.best_score, self.second_score, self.total, min_score)
+
+    def table(self, names=None, class_names=None, min_score=0.0):
+        """``sequence.spread_table``: one record per row - label, confidence, score, total_score, first"""
+        return _sequence.spread_table(self.best, self.best_score, self.second_score, self.total, self.first, names, class_names, min_score)
 
 
 class VoteResult(_Result):
@@ -1341,6 +1365,78 @@ class NNEngine:
         """measurement only (``gnn_debug_mcl_overflow``): the columns that took the overflow path in the last :meth:`mcl` /
         :meth:`mcl_dev` call - int64 [the initial matrix, then every iteration]"""
         return self._debug_ms(self.lib.gnn_debug_mcl_overflow, np.int64)
+
+    # -- label spreading -----------------------------------------------------------------
+    def _spread_call(self, fn, graph, n, nnz, knobs, outs, alpha):
+        nc, a, clamp, max_iter = knobs
+        changed = np.zeros(max_iter, dtype=np.int64)
+        iterations, converged = C.c_int64(0), C.c_int(0)
+        check(fn(self.ctx, *graph, int(n), int(nnz), nc, a, int(clamp), max_iter, *outs, changed.ctypes.data, C.addressof(iterations),
+                 C.addressof(converged)))
+        return dict(iterations=int(iterations.value), converged=bool(converged.value), changed=changed[:iterations.value], n=int(n),
+                    n_classes=nc, alpha=float(alpha), clamp=bool(clamp))
+
+    @staticmethod
+    def _spread_knobs(n_classes, alpha, clamp, max_iter):
+        """the knobs as the library takes them; a ``ValueError`` for one out of range, before anything is allocated"""
+        return (_sequence.vote_classes(n_classes), _sequence.spread_alpha(alpha), bool(clamp),
+                _sequence._whole(max_iter, "max_iter", 1, _sequence.SPREAD_MAX_ITER_MAX))
+
+    def spread(self, indptr, col, sim, label, n_classes, valid=None, alpha=0.5, clamp=True, max_iter=200, scores=True) -> SpreadResult:
+        """Label spreading over a similarity graph (``gnn_spread``; the definition is ``sequence.label_spread``): the labels of the
+        seed rows - ``label`` int64 per row in [-1, ``n_classes``), -1: unlabelled - spread along the edges of the upper-triangle CSR
+        (``indptr``, ``col``, ``sim``) :meth:`graph` returns until nothing changes: a row gets a class through any number of
+        unlabelled rows, where :meth:`vote` crosses one edge.  ``alpha``: a multiple of 1/64 in (0, 1), the share a row takes from
+        its neighbours; ``clamp``: a seed keeps its label's full score; ``max_iter`` (1..10000); ``scores=False``: the n x n_classes
+        matrix is not copied back (``score`` is None).  In integers throughout: every output equals the definition bit for bit.
+        Random-walk rows, not the symmetric normalisation; no calibrated probability.  ``ValueError`` for a knob out of range,
+        ``GnnError`` for a graph that is no such CSR."""
+        knobs = self._spread_knobs(n_classes, alpha, clamp, max_iter)
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        with np.errstate(over="ignore"):
+            sim = np.ascontiguousarray(sim, dtype=np.float32)
+        n = len(indptr) - 1
+        if indptr.ndim != 1 or n < 0 or col.ndim != 1 or sim.shape != col.shape:
+            raise ValueError("indptr (n + 1,), col (nnz,) and sim (nnz,) are required")
+        ok = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+        if ok is not None and ok.shape != (n,):
+            raise ValueError(f"valid must have one entry per row ({n})")
+        lab = _sequence.vote_labels(label, n, knobs[0])
+        score = np.empty((n, knobs[0]), dtype=np.uint32) if scores else None
+        out = [np.empty(n, dtype=np.int32), np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint64),
+               np.empty(n, dtype=np.int32)]
+        kw = self._spread_call(self.lib.gnn_spread, (indptr.ctypes.data, col.ctypes.data, sim.ctypes.data, None if ok is None else ok.ctypes.data,
+                                                     lab.ctypes.data), n, len(col), knobs,
+                               [None if score is None else score.ctypes.data] + [a.ctypes.data for a in out], alpha)
+        seed = (lab >= 0) & (np.ones(n, dtype=bool) if ok is None else ok.astype(bool))
+        return SpreadResult(score=score, **dict(zip(_sequence.SPREAD_FIELDS[1:], out)), seed=seed, **kw)
+
+    def spread_dev(self, indptr_ptr: int, col_ptr, sim_ptr, label_ptr: int, n: int, nnz: int, n_classes: int, best_ptr: int, best_score_ptr: int,
+                   second_score_ptr: int, total_ptr: int, first_ptr: int, score_ptr=None, valid_ptr=None, alpha=0.5, clamp=True,
+                   max_iter=200) -> SpreadResult:
+        """``gnn_spread_dev``: device pointers in - indptr (n + 1 int64), col (nnz int32) and sim (nnz f32) exactly as
+        :meth:`graph_count_dev` and :meth:`graph_fill_dev` wrote them, label (n int64), valid (n uint8, or None) - and out (best,
+        first: n int32; best_score, second_score: n uint32; total: n uint64; score: n x n_classes uint32, or None); the engine's
+        stream is synchronised once per iteration.  Returns a :class:`SpreadResult` without the per-row arrays."""
+        knobs = self._spread_knobs(n_classes, alpha, clamp, max_iter)
+        return SpreadResult(**self._spread_call(self.lib.gnn_spread_dev, (indptr_ptr, col_ptr, sim_ptr, valid_ptr, label_ptr), n, nnz, knobs,
+                                                [score_ptr, best_ptr, best_score_ptr, second_score_ptr, total_ptr, first_ptr], alpha))
+
+    def set_spread_groups(self, groups: int):
+        """test aid (``gnn_debug_spread_groups``): the workgroups of an iteration of :meth:`spread` (0: the library's choice); no
+        result depends on it."""
+        check(self.lib.gnn_debug_spread_groups(self.ctx, int(groups)))
+
+    def set_spread_skip(self, on: bool):
+        """test aid (``gnn_debug_spread_skip``): the dirty-row rule of :meth:`spread` - a row none of whose neighbours changed is not
+        computed again - on (the default) or off; no result depends on it."""
+        check(self.lib.gnn_debug_spread_skip(self.ctx, int(bool(on))))
+
+    def spread_pass_ms(self):
+        """measurement only (``gnn_debug_spread_ms``): with profiling enabled, the HIP-event milliseconds of the last :meth:`spread`
+        / :meth:`spread_dev` call - [validate and symmetrise, then every iteration]"""
+        return self._debug_ms(self.lib.gnn_debug_spread_ms)
 
     # -- spherical k-means ---------------------------------------------------------------
     def kmeans(self, rows, k, init=None, max_iter=_sequence.KMEANS_MAX_ITER_DEFAULT) -> KMeansResult:

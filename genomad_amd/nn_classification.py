@@ -21,6 +21,7 @@ ranks, the per-contig scores are collected with one RCCL gather (genomad_amd/rcc
 writes the files.
 """
 import concurrent.futures
+import functools
 import hashlib
 import json
 import os
@@ -87,7 +88,7 @@ class Outputs:
         # written only when GENOMAD_AMD_REGION_EMBEDDINGS=1 (encoder embeddings per called region; no counterpart in the reference)
         self.nn_region_embeddings_output = d / f"{p}_nn_region_embeddings.npz"
         self.provirus_nn_region_embeddings_output = d / f"{p}_provirus_nn_region_embeddings.npz"
-        # written only when the analysis is requested (the twelve analyses of the per-contig embeddings, ANALYSES below: <stem>.npz and,
+        # written only when the analysis is requested (the thirteen analyses of the per-contig embeddings, ANALYSES below: <stem>.npz and,
         # for all but the neighbours, <stem>.tsv; no counterpart in the reference)
         for stage in self._STAGE.values():
             for a in ANALYSES:
@@ -997,13 +998,14 @@ def vote_min_votes_requested() -> int:
     return _env_int("GENOMAD_AMD_VOTE_MIN_VOTES", 1, None, "(the voters a contig needs to get a label)", 1)
 
 
-def load_vote_base(path, strand="forward"):
-    """(names, embeddings float32 (n, 512), classes, label int64 (n,)) of a labelled reference file: an embeddings file as
+def load_vote_base(path, strand="forward", switch="GENOMAD_AMD_VOTE_BASE"):
+    """(names, embeddings float32 (n, 512), classes, label int64 (n,)) of a labelled reference file (``switch``: the variable that
+    named it, for the messages): an embeddings file as
     GENOMAD_AMD_EMBEDDINGS=1 writes it - ``embeddings`` of shape (n, 512), ONE 1-D array of the n names under whatever key, an
     optional ``strand``, which must be the run's mode - plus ``labels``, a 1-D array of n strings: "" means unlabelled (label -1), the
     classes are the sorted distinct non-empty strings (at most 1024) and a row's label is its class's place among them.
     ``ValueError`` with the reason for anything else."""
-    what = f"GENOMAD_AMD_VOTE_BASE={str(path)!r}"
+    what = f"{switch}={str(path)!r}"
     if not Path(path).is_file():
         raise ValueError(f"{what}: no such file")
     try:
@@ -1065,6 +1067,85 @@ def write_votes(npz_path, tsv_path, names_key, names, classes, base_names, base_
                                      "nearest_sim": res.nearest_sim, "label": label, "confidence": confidence, "margin": margin,
                                      **_strand_entry(strand)})
     write_votes_tsv(tsv_path, names, classes, base_names, res, min_votes)
+
+
+SPREAD_MAX_ITER_DEFAULT = 200
+SPREAD_SCORE_CLASSES = 64               # the score matrix is written for up to this many classes
+
+
+def spread_requested():
+    """GENOMAD_AMD_SPREAD=<alpha, a multiple of 1/64 in (0, 1)>: main() also spreads the labels of the reference named by
+    GENOMAD_AMD_SPREAD_BASE (a labelled embeddings file, the format of GENOMAD_AMD_VOTE_BASE) along the similarity graph of the
+    reference's rows and the contigs' per-contig embeddings at the threshold of GENOMAD_AMD_GRAPH, which must be set with it - a contig
+    gets a label through any number of unlabelled contigs, where GENOMAD_AMD_VOTE crosses one edge (<prefix>_nn_spread.npz and .tsv);
+    unset or empty: nothing changes (None).  GENOMAD_AMD_SPREAD_MAX_ITER=<integer in [1, 10000]> (default 200) bounds the iterations;
+    it is an error without GENOMAD_AMD_SPREAD.  Any other value of either is an error.  Returns (alpha, the graph's threshold as it is
+    compared or None, max_iter), or None."""
+    v = os.environ.get("GENOMAD_AMD_SPREAD", "").strip()
+    if not v:
+        _env_refines("GENOMAD_AMD_SPREAD_MAX_ITER", "GENOMAD_AMD_SPREAD", "set the alpha of the label spreading or unset")
+        return None
+    try:
+        alpha = float(v)
+        sequence.spread_alpha(alpha)
+    except ValueError:
+        raise ValueError(f"GENOMAD_AMD_SPREAD={v!r}: expected a multiple of 1/64 in (0, 1) (alpha: the share of its score a contig takes "
+                         "from its neighbours)") from None
+    return alpha, graph_requested(), _env_int("GENOMAD_AMD_SPREAD_MAX_ITER", 1, sequence.SPREAD_MAX_ITER_MAX,
+                                              "(the iterations the label spreading runs at the most)", SPREAD_MAX_ITER_DEFAULT)
+
+
+def spread_base_requested():
+    """GENOMAD_AMD_SPREAD_BASE=<path>: the labelled reference GENOMAD_AMD_SPREAD takes its seeds from (:func:`load_vote_base`); unset
+    or empty: None."""
+    v = os.environ.get("GENOMAD_AMD_SPREAD_BASE", "").strip()
+    return Path(v) if v else None
+
+
+def _run_spread(eng, emb, request, base):
+    """the graph over [the reference's rows; the contigs' rows] at the request's threshold, and the reference's labels spread along it
+    as clamped seeds: (the SpreadResult of all rows, the graph's edges, the reference's rows)"""
+    alpha, threshold, max_iter = request
+    _, base_emb, classes, base_label = base
+    g = eng.graph(np.concatenate([base_emb, np.asarray(emb, dtype=np.float32)]), threshold, NEIGHBOUR_METRIC)
+    label = np.concatenate([np.asarray(base_label, dtype=np.int64), np.full(len(emb), -1, dtype=np.int64)])
+    res = eng.spread(g.indptr, g.col, g.sim, label, len(classes), valid=g.valid, alpha=alpha, clamp=True, max_iter=max_iter,
+                     scores=len(classes) <= SPREAD_SCORE_CLASSES)
+    return res, g.n_edges, len(base_emb)
+
+
+SPREAD_TSV_HEADER = "seq_name\tlabel\tconfidence\tscore\ttotal_score\tfirst\n"
+
+
+def write_spread_tsv(path, names, classes, arrays):
+    """One line per contig of the contigs' part of a SpreadResult: its name, the class with the largest score, that score's share of
+    the contig's total, the score, the total and the first iteration that brought the contig any score, behind one header line; NA
+    where the contig has no label."""
+    with open(path, "w") as fout:
+        fout.write(SPREAD_TSV_HEADER)
+        for e in sequence.spread_table(*(arrays[k] for k in sequence.SPREAD_FIELDS[1:]), names, classes):
+            if e["label"] is None:
+                fout.write(f"{e['row']}\tNA\tNA\tNA\t{e['total_score']:.6f}\tNA\n")
+            else:
+                fout.write(f"{e['row']}\t{e['label']}\t{e['confidence']:.6f}\t{e['score']:.6f}\t{e['total_score']:.6f}\t{e['first']}\n")
+
+
+def write_spread(npz_path, tsv_path, names_key, names, base, res, request, strand="forward"):
+    """Both label-spreading files of a stage: the contigs' part of the arrays of a SpreadResult (the reference's rows come first in
+    it) with the names of the contigs, the classes and the reference rows (and the rows' labels), the request, the labels, and one
+    line per contig."""
+    res, n_edges, nb = res
+    base_names, _, classes, base_label = base
+    arrays = {k: getattr(res, k)[nb:] for k in sequence.SPREAD_FIELDS[1:]}
+    label, confidence, margin = sequence.spread_predict(*(arrays[k] for k in sequence.SPREAD_FIELDS[1:5]))
+    score = {"score": res.score[nb:]} if res.score is not None else {}
+    np.savez_compressed(npz_path, **{names_key: names, "base_names": base_names, "base_label": np.asarray(base_label, dtype=np.int64),
+                                     "classes": classes, "alpha": np.float64(request[0]), "threshold": np.float64(request[1]),
+                                     "max_iter": np.int64(request[2]), "metric": np.array(NEIGHBOUR_METRIC), **arrays, **score,
+                                     "label": label, "confidence": confidence, "margin": margin, "iterations": np.int64(res.iterations),
+                                     "converged": np.bool_(res.converged), "changed": res.changed, "n_edges": np.int64(n_edges),
+                                     **_strand_entry(strand)})
+    write_spread_tsv(tsv_path, names, classes, arrays)
 
 
 REGION_TSV_HEADER = ("seq_name\tstart\tend\tclass\tn_bins\tevidence_bins\t"
@@ -1242,7 +1323,7 @@ def _encode(fasta_path, enc_dir: Path, window_id_path: Path, single_window: bool
 
 
 # ---- the analyses of the gathered per-contig embeddings ------------------------------------------------------------------------------
-# Twelve analyses follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
+# Thirteen analyses follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
 #   name      the stem of its files, <prefix>_nn_<name>.npz and - where ``tsv`` - .tsv
 #   switch    the environment variable that requests it; ``request()`` reads it (and its companions): the request, or None
 #   needs     the middle clause of the message that refuses the switch without GENOMAD_AMD_EMBEDDINGS=1
@@ -1360,6 +1441,18 @@ ANALYSES = (        # in the order they run, which is the order of the log lines
              lambda res, r, what, ctx: (f"{_SIMILARITY} >= {r[0]:g}, {len(ctx.base[2])} classes: "
                                         f"{int((res.predict(VOTE_RULE, r[1])[0] >= 0).sum())} of {len(ctx.names)} {what}s got a label"),
              base=AnalysisBase(vote_base_requested, load_vote_base, ", with 'labels' added", _same_vote_base)),
+    Analysis("spread", "GENOMAD_AMD_SPREAD", spread_requested,
+             "the labelled reference's labels spread along the similarity graph of its embeddings and the per-contig encoder embeddings",
+             (("alpha", float), ("threshold", float), ("max_iter", int)), "Labels of {base} spread to the {what}s",
+             lambda eng, emb, r, ctx: _run_spread(eng, emb, r, ctx.base),
+             lambda npz, tsv, key, names, res, strand, ctx: write_spread(npz, tsv, key, names, ctx.base, res, ctx.request, strand),
+             lambda res, r, what, ctx: (f"{_SIMILARITY} >= {r[1]:g}, {res[1]} edges among {res[2]} reference rows and {len(ctx.names)} {what}s, "
+                                        f"alpha {r[0]:g}, {len(ctx.base[2])} classes: {int((res[0].best[res[2]:] >= 0).sum())} of "
+                                        f"{len(ctx.names)} {what}s got a label in {res[0].iterations} iterations, "
+                                        f"{'converged' if res[0].converged else 'not converged'}"),
+             errors=(ValueError, GnnError), advice="Raise GENOMAD_AMD_GRAPH or unset GENOMAD_AMD_SPREAD.",      # the graph's cap on its edges
+             base=AnalysisBase(spread_base_requested, functools.partial(load_vote_base, switch="GENOMAD_AMD_SPREAD_BASE"),
+                               ", with 'labels' added", _same_vote_base), after="graph"),
 )
 
 

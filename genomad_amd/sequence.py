@@ -2297,6 +2297,144 @@ def mcl_table(label, size, is_attractor, names=None):
     return out
 
 
+SPREAD_ONE = 1 << 30              # a score of 1
+SPREAD_P = 1 << 31                # a row's transition mass
+SPREAD_MAX_ITER_MAX = 10000
+SPREAD_FIELDS = ("score", "best", "best_score", "second_score", "total", "first")
+
+
+def spread_alpha(alpha) -> int:
+    """64 * ``alpha`` as the integer in [1, 63] the iteration multiplies by; anything else is a ``ValueError``: the damping is a
+    shift by 6 bits, so alpha is a multiple of 1/64 in (0, 1)."""
+    try:
+        a = float(alpha) * 64.0
+        ok = not isinstance(alpha, (bool, np.bool_)) and a == int(a) and 1 <= a <= 63
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"alpha {alpha!r}: a multiple of 1/64 in (0, 1) is required")
+    return int(a)
+
+
+def spread_transitions(indptr, col, sim, valid=None):
+    """The integer random-walk rows label spreading runs on: (n, i, j, p, valid) - every existing entry of :func:`mcl_weights` at both
+    its ends (row i, partner j), sorted by i, with p_ij = (q_ij << 31) // d_i for d_i = the sum of q over the entries at row i;
+    parallel entries stay apart (their p add up in every sum)."""
+    n, a, b, q, ok = mcl_weights(indptr, col, sim, valid)
+    i, j, q = np.concatenate([a, b]), np.concatenate([b, a]), np.concatenate([q, q])
+    order = np.argsort(i, kind="stable")
+    i, j, q = i[order], j[order], q[order]
+    d = np.zeros(n, dtype=np.uint64)
+    np.add.at(d, i, q)
+    return n, i, j, (q << np.uint64(31)) // d[i] if len(i) else q, ok
+
+
+def spread_step(n, i, j, p, F, base, fixed, a):
+    """One synchronous iteration: F (uint64 (n, c)) -> the next F.  ``base`` = (64 - a) * ONE * y, ``fixed`` = the rows that keep
+    ``fixed_value`` = their row of ONE * y (clamped seeds) or 0 (invalid rows) - given as (mask, values)."""
+    g = np.zeros_like(F)
+    if len(i):
+        first = np.flatnonzero(np.concatenate([[True], i[1:] != i[:-1]]))
+        g[i[first]] = np.add.reduceat(p[:, None] * F[j], first, axis=0)      # every sum is below 2^61
+    nxt = (np.uint64(a) * (g >> np.uint64(31)) + base) >> np.uint64(6)
+    nxt[fixed[0]] = fixed[1][fixed[0]]
+    return nxt
+
+
+def label_spread(indptr, col, sim, label, n_classes, valid=None, alpha=0.5, clamp=True, max_iter=200, trace=None):
+    """Label spreading over a similarity graph, in integers throughout (the definition ``gnn_spread`` computes on the device; DESIGN.md
+    section 5t): the labels of seed rows spread along the edges until nothing changes - multi-hop label transfer, where
+    :func:`class_votes` crosses one edge.  The graph is the upper-triangle CSR of :func:`threshold_graph`, with ``valid`` (bool per
+    row, None: all), read as :func:`markov_clusters` reads it; ``label`` is one int64 per row in [-1, ``n_classes``), -1 = unlabelled;
+    1 <= ``n_classes`` <= 1024; ``alpha`` = a / 64 (:func:`spread_alpha`); ``max_iter`` in [1, 10000].  ONE = 2^30 is a score of 1.
+
+    Weights: q = rint(float32(sim) * 2^24); an entry with q <= 0 or an invalid end does not exist; an entry sits at both its ends;
+    parallel entries are added.  d_i = the sum of q at row i, p_ij = (q_ij << 31) // d_i: a row's p sum to 2^31 at the most, and with
+    scores <= 2^30 a row's sum stays below 2^61 at any degree.
+    Seeds: the valid rows with label >= 0; y_i[c] = 1 where label_i == c, else 0.
+    Iteration (synchronous, F^0 = 0): g_i[c] = (sum_j p_ij * F_j[c]) >> 31; F'_i[c] = ONE * y_i[c] for a seed under ``clamp``, otherwise
+    (a * g_i[c] + (64 - a) * ONE * y_i[c]) >> 6; an invalid row stays 0.  It stops behind the first iteration that changes no row
+    (``converged``) or behind ``max_iter`` iterations.
+
+    Why it ends: the map F -> F' is monotone - every term is a floor of a sum of products with non-negative constants, so F <= G
+    entry by entry gives F' <= G' - and F^1 >= F^0 = 0, hence F^(t+1) >= F^t for every t by induction; every score is an integer in
+    [0, ONE] (g <= ONE because the p of a row sum to <= 2^31, and a * ONE + (64 - a) * ONE = 64 * ONE).  A sequence of integer matrices
+    that never falls and is bounded stops changing.  Nothing bounds the number of iterations short of n * n_classes * 2^30, so
+    ``iterations`` and ``converged`` are outputs.  ``trace``: a list that receives every F^t (uint64 copies), t = 1, 2, ...
+
+    Returns a dict: ``score`` (uint32 (n, n_classes), units of 2^-30), ``best`` (int32: the class of the largest score, ties to the
+    smaller class; -1 where every score is 0, so for an invalid row), ``best_score`` and ``second_score`` (uint32: the largest score
+    among the other classes; 0 with one class), ``total`` (uint64: the sum over the classes), ``first`` (int32: the first iteration,
+    counted from 1, behind which the row's total was not 0; -1: never.  A score is floored, so mass that has become smaller than
+    2^-30 on its way is 0: ``first`` can be larger than the row's hop distance from a seed, and a row far enough away stays -1),
+    ``seed`` (bool: the row is a seed), ``iterations``, ``converged`` and ``changed`` (int64: the rows every iteration changed)."""
+    a = spread_alpha(alpha)
+    nc = vote_classes(n_classes)
+    max_iter = _whole(max_iter, "max_iter", 1, SPREAD_MAX_ITER_MAX)
+    n, i, j, p, ok = spread_transitions(indptr, col, sim, valid)
+    label = vote_labels(label, n, nc)
+    seed = ok & (label >= 0)
+    y = np.zeros((n, nc), dtype=np.uint64)
+    y[np.flatnonzero(seed), label[seed]] = 1
+    base = np.uint64((64 - a) * SPREAD_ONE) * y
+    hold = seed if clamp else np.zeros(n, dtype=bool)
+    fixed = (hold | ~ok, np.uint64(SPREAD_ONE) * y)           # an invalid row is no seed: its row of y is 0
+    F = np.zeros((n, nc), dtype=np.uint64)
+    first = np.full(n, -1, dtype=np.int32)
+    changed, converged = [], False
+    while len(changed) < max_iter and not converged:
+        nxt = spread_step(n, i, j, p, F, base, fixed, a)
+        changed.append(int(np.count_nonzero((nxt != F).any(axis=1))))
+        converged = changed[-1] == 0
+        F = nxt
+        first[(first < 0) & (F.sum(axis=1) > 0)] = len(changed)
+        if trace is not None:
+            trace.append(F.copy())
+    out = spread_summary(F)
+    out.update(seed=seed, iterations=len(changed), converged=converged, changed=np.asarray(changed, dtype=np.int64), first=first)
+    return out
+
+
+def spread_summary(score):
+    """``score``, ``best``, ``best_score``, ``second_score`` and ``total`` of a score matrix, as :func:`label_spread` returns them"""
+    F = np.asarray(score).astype(np.uint64)
+    n, nc = F.shape
+    top = np.argmax(F, axis=1) if n else np.zeros(0, dtype=np.int64)          # argmax: the first = the smallest class among equals
+    best_score = F[np.arange(n), top]
+    rest = F.copy()
+    rest[np.arange(n), top] = 0
+    return {"score": F.astype(np.uint32), "best": np.where(best_score > 0, top, -1).astype(np.int32), "best_score": best_score.astype(np.uint32),
+            "second_score": (rest.max(axis=1) if nc > 1 else np.zeros(n, dtype=np.uint64)).astype(np.uint32), "total": F.sum(axis=1)}
+
+
+def spread_predict(best, best_score, second_score, total, min_score=0.0):
+    """One label per row from the arrays of :func:`label_spread`: (``label`` int64: ``best``, -1 where there is none or where
+    ``best_score`` / 2^30 is below ``min_score``; ``confidence`` float64: ``best_score`` / ``total``; ``margin`` float64:
+    (``best_score`` - ``second_score``) / ``total``; NaN where there is no label).  A share of the seed mass that reached the row, no
+    calibrated probability."""
+    min_score = float(min_score)
+    if not 0.0 <= min_score <= 1.0:
+        raise ValueError(f"min_score {min_score!r}: a float in [0, 1] is required")
+    best = np.asarray(best, dtype=np.int64)
+    bs, ss, tot = (np.asarray(x).astype(np.float64) for x in (best_score, second_score, total))
+    has = (best >= 0) & (bs / SPREAD_ONE >= min_score)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        confidence = np.where(has, bs / tot, np.nan)
+        margin = np.where(has, (bs - ss) / tot, np.nan)
+    return np.where(has, best, -1), confidence, margin
+
+
+def spread_table(best, best_score, second_score, total, first, names=None, class_names=None, min_score=0.0):
+    """One record per row: ``row`` (its index, or its name), ``label`` (the class, or its name; None without one), ``confidence``,
+    ``score`` (``best_score`` / 2^30), ``total_score`` (``total`` / 2^30) and ``first``"""
+    label, confidence, _ = spread_predict(best, best_score, second_score, total, min_score)
+    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    cname = (lambda c: int(c)) if class_names is None else (lambda c: str(class_names[int(c)]))
+    return [{"row": name(i), "label": cname(label[i]) if label[i] >= 0 else None, "confidence": float(confidence[i]) if label[i] >= 0 else None,
+             "score": int(best_score[i]) / SPREAD_ONE, "total_score": int(total[i]) / SPREAD_ONE, "first": int(first[i])}
+            for i in range(len(label))]
+
+
 def prefix_of(input_path: Path) -> str:
     """nn_classification.py:106-108: stem, minus one more extension if the file is compressed."""
     prefix = Path(input_path).stem

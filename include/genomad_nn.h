@@ -866,6 +866,55 @@ int gnn_debug_mcl_groups(gnn_ctx* ctx, int groups);
 int gnn_debug_mcl_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
 int gnn_debug_mcl_overflow(gnn_ctx* ctx, int64_t* count_out, int64_t capacity, int64_t* n_out);
 
+/* ---- label spreading over a similarity graph: multi-hop label transfer on the device ----------------------------
+ * "Which class reaches every row through the graph, over any number of edges": the labels of seed rows spread along the edges of the
+ * graph gnn_graph_* writes until nothing changes - where gnn_vote crosses one edge - in integers throughout, so that every output equals
+ * the definition (sequence.label_spread) bit for bit, for any number of workgroups and any order they run in.  No forward pass runs and
+ * no other entry point's result changes.
+ *   graph     gnn_mcl's: an upper-triangle CSR with sim (f32, finite, < 64) and valid (uint8 [n], or NULL); exactly what
+ *             gnn_graph_fill_dev wrote is such a graph.  label (int64 [n]) in [-1, n_classes), -1: unlabelled.  Anything else:
+ *             GNN_ERR_ARG behind two O(nnz + n) kernels, before anything else runs, the outputs untouched.
+ *   weights   ONE = 2^30 is a score of 1, W = 2^24.  q = rint(sim * W); an entry with q <= 0 or an invalid end does not exist; an entry
+ *             sits at both its ends; parallel entries are added.  d_i = the sum of q at row i; p_ij = (q_ij << 31) / d_i (floor).
+ *   seeds     a valid row with label >= 0; y_i[c] = 1 where label_i == c, else 0.
+ *   iteration synchronous, F^0 = 0: g_i[c] = (sum_j p_ij * F_j[c]) >> 31; F'_i[c] = ONE * y_i[c] for a seed under `clamp`, otherwise
+ *             (a * g_i[c] + (64 - a) * ONE * y_i[c]) >> 6 for alpha = a / 64, alpha_64ths = a in [1, 63]; an invalid row stays 0.  It
+ *             stops behind the first iteration that changes no row (*converged_host = 1) or behind max_iter iterations;
+ *             *iterations_host counts them, changed_host[it] (capacity max_iter) the rows iteration it changed.  The map is monotone
+ *             and F^1 >= F^0: F never falls and is bounded, so it ends - after how many iterations, nothing here says.
+ *   outputs   score (uint32 [n][n_classes], units of 2^-30; NULL: the matrix is not wanted and not copied), best (int32: the class of
+ *             the largest score, ties to the smaller class; -1 where every score is 0), best_score, second_score (uint32: the largest
+ *             score among the other classes), total (uint64: the sum over the classes), first (int32: the first iteration, counted from
+ *             1, behind which the row's total was not 0; -1: never.  The floors can make it larger than the row's distance from a seed).
+ *   ranges    0 <= n <= 2^24, nnz >= 0, n_classes in [1, 1024], alpha_64ths in [1, 63], max_iter in [1, 10000]; GNN_ERR_ARG with the
+ *             value and the range in the message - checked before the ctx is looked at.  n == 0: nothing is launched; one iteration
+ *             that changes nothing.
+ *   exact     a row's sum is below 2^61 at any degree (the p of a row sum to 2^31 at the most, a score is at most 2^30): 64-bit integer
+ *             multiply-adds, reduced by shuffles and through LDS; integer add atomics on counters only.  A row neither whose own nor
+ *             whose neighbours' scores changed in the previous iteration is not computed again (gnn_debug_spread_skip): no bit depends
+ *             on that.
+ * What it is not: not Zhou's symmetric normalisation D^-1/2 W D^-1/2 (rows are random-walk rows, D^-1 W); not float; no calibrated
+ * probability (a score is a share of seed mass that reached the row); n_classes <= 1024; not multi-GPU.
+ * Device memory, persistent in the ctx and grow-only: 8 B per symmetric entry (two per edge), 2 * n * n_classes * 4 B of scores, about
+ * 30 B per row (gnn_spread: + the graph, the labels and 24 B per row of results).  A failed allocation: GNN_ERR_NOMEM, outputs untouched.
+ * gnn_spread: host pointers, synchronous.  gnn_spread_dev: device pointers in and out; changed, iterations and converged on the host;
+ * the ctx stream is synchronised once for the verdict on graph and labels and once per iteration (8 bytes). */
+int gnn_spread(gnn_ctx* ctx, const int64_t* indptr_host, const int32_t* col_host, const float* sim_host, const uint8_t* valid_host_or_null,
+               const int64_t* label_host, int64_t n, int64_t nnz, int n_classes, int alpha_64ths, int clamp, int max_iter,
+               uint32_t* score_host_or_null, int32_t* best_host, uint32_t* best_score_host, uint32_t* second_score_host, uint64_t* total_host,
+               int32_t* first_host, int64_t* changed_host, int64_t* iterations_host, int* converged_host);
+int gnn_spread_dev(gnn_ctx* ctx, const int64_t* indptr_dev, const int32_t* col_dev, const float* sim_dev, const uint8_t* valid_dev_or_null,
+                   const int64_t* label_dev, int64_t n, int64_t nnz, int n_classes, int alpha_64ths, int clamp, int max_iter,
+                   uint32_t* score_dev_or_null, int32_t* best_dev, uint32_t* best_score_dev, uint32_t* second_score_dev, uint64_t* total_dev,
+                   int32_t* first_dev, int64_t* changed_host, int64_t* iterations_host, int* converged_host);
+/* test aids; no result depends on them.  gnn_debug_spread_groups: the workgroups of an iteration, 1 .. 65535 (0: the library's choice,
+ * eight per CU).  gnn_debug_spread_skip: the dirty-row rule on (the default) or off. */
+int gnn_debug_spread_groups(gnn_ctx* ctx, int groups);
+int gnn_debug_spread_skip(gnn_ctx* ctx, int on);
+/* measurement only: with gnn_profile_enable on, the HIP-event milliseconds of the ctx's last gnn_spread* call: [0] validate and
+ * symmetrise, then one figure per iteration; *n_out = the figures recorded, at most `capacity` are written. */
+int gnn_debug_spread_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
+
 /* ---- matches against a reference: the bipartite similarity graph query x base ------------------------------
  * "Which reference rows is every new row within the threshold of, all of them": every pair (i, j) of a valid query row i and a valid
  * base row j with sim(i, j) >= threshold and its similarity, as a CSR by query row.  The passes, the kernel, the workspace and the
