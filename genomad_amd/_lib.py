@@ -162,6 +162,14 @@ SIGNATURES = {
     "gnn_debug_spread_groups": (_int, [_vp, _int]),
     "gnn_debug_spread_skip": (_int, [_vp, _int]),
     "gnn_debug_spread_ms": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_avglink": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_avglink_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_debug_avglink_slots": (_int, [_vp, _int]),
+    "gnn_debug_avglink_wave_rows": (_int, [_vp, _int]),
+    "gnn_debug_avglink_groups": (_int, [_vp, _int]),
+    "gnn_debug_avglink_order": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_debug_avglink_ms": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_debug_avglink_classes": (_int, [_vp, _vp]),
     "gnn_kmeans": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_kmeans_dev": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_centroids": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp]),

@@ -389,6 +389,35 @@ struct SpreadWorkspace {
     PassLog passes;                              // profiling on: HIP-event time of the last call's [validate + symmetrise, then every iteration]
 };
 
+// ---- average linkage (gnn_avglink.hip): persistent, grow-only.  The symmetric graph and two entry buffers (12 B per entry each, two
+// entries per edge), about 70 B per row of state, lists and records, at most 2^24 cells of dense accumulators (192 MB) and, for
+// gnn_avglink alone, the graph and its 24 B of results per row.
+struct AvglinkWorkspace {
+    int slots = 4096;                            // slots of the LDS table (gnn_debug_avglink_slots): 0 .. 4096; no result depends on it
+    int wave_rows = 256;                         // the longest upper bound one wave takes (gnn_debug_avglink_wave_rows); no result depends on it
+    int groups = 0;                              // workgroups of a contraction (gnn_debug_avglink_groups); 0: the library's choice; no result depends on it
+    DevBuf<uint8_t> ok;                          // [n]: the row takes part
+    DevBuf<int32_t> len;                         // [n]: entries of the live cluster's segment (first the symmetric graph's degrees)
+    DevBuf<int64_t> off[2];                      // [n + 1]: where a segment starts in entry buffer b
+    DevBuf<unsigned long long> cursor;           // [n]: symmetrise's
+    DevBuf<int32_t> idx[2];                      // the entries, ping-pong: the neighbour cluster
+    DevBuf<unsigned long long> sum[2];           // and S, the sum of q between the two clusters
+    DevBuf<uint32_t> sq;                         // symmetrise's weights, widened into sum[0]
+    DevBuf<int32_t> map, size, best, partner, ub;      // [n] each: see gnn_avglink.hip
+    DevBuf<unsigned long long> bestS;            // [n]
+    DevBuf<int32_t> rows;                        // [3][n]: the rows of a round by class - wave, workgroup, dense
+    DevBuf<unsigned long long> dense;            // [dense workgroups][n]: all zero between rows
+    DevBuf<int32_t> touched;                     // [dense workgroups][n]
+    HostCounters count;                          // [2][merged, wave rows, workgroup rows, dense rows], then the call's class totals [3], then the verdict
+    DevBuf<int64_t> d_indptr;                    // gnn_avglink: the graph
+    DevBuf<int32_t> d_col;
+    DevBuf<float> d_sim;
+    DevBuf<uint8_t> d_valid;
+    DevBuf<int64_t> d_out;                       // gnn_avglink: [parent (i32) | weight (u64) | size_a (i32) | size_b (i32) | round (i32)], a Landing
+    PassLog passes;                              // profiling on: HIP-event time of the last call's [validate + symmetrise, then every round]
+    int64_t class_rows[3] = {0, 0, 0};           // the last call's rows by class, all rounds (gnn_debug_avglink_classes)
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -592,9 +621,10 @@ struct gnn_ctx {
     gnn::VoteWorkspace vt;                        // gnn_votes.hip
     gnn::MclWorkspace mcl;                        // gnn_mcl.hip
     gnn::SpreadWorkspace sprd;                    // gnn_spread.hip
+    gnn::AvglinkWorkspace avl;                    // gnn_avglink.hip
     // every PassLog above: drain_profile settles them before an event they hold returns to event_pool
-    gnn::PassLog* const pass_logs[9] = {&rp.rounds, &lk.rounds, &lk.tree_rounds, &gr.passes,  &km.passes, &pca.passes,
-                                        &vt.passes, &mcl.passes, &sprd.passes};
+    gnn::PassLog* const pass_logs[10] = {&rp.rounds, &lk.rounds, &lk.tree_rounds, &gr.passes,  &km.passes, &pca.passes,
+                                         &vt.passes, &mcl.passes, &sprd.passes, &avl.passes};
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;

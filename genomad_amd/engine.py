@@ -401,6 +401,11 @@ class GraphResult(_Result):
         ``alpha``, ``clamp``, ``max_iter`` and ``scores`` as there"""
         return engine.spread(self.indptr, self.col, self.sim, label, n_classes, valid=self.valid, **kw)
 
+    def average_linkage(self, engine, **kw) -> "AverageLinkageResult":
+        """:meth:`NNEngine.average_linkage` of this graph and its rows' validity: the UPGMA tree, with ``stop`` and ``max_rounds``
+        as there"""
+        return engine.average_linkage(self.indptr, self.col, self.sim, valid=self.valid, **kw)
+
     @classmethod
     def build(cls, arrays, valid, threshold, metric):
         """from the (indptr, col, sim) of ``sequence.threshold_graph`` or the library, and the rows' validity"""
@@ -519,6 +524,36 @@ class SpreadResult(_Result):
     def table(self, names=None, class_names=None, min_score=0.0):
         """``sequence.spread_table``: one record per row - label, confidence, score, total_score, first"""
         return _sequence.spread_table(self.best, self.best_score, self.second_score, self.total, self.first, names, class_names, min_score)
+
+
+class AverageLinkageResult(_Result):
+    """What :meth:`NNEngine.average_linkage` returns (the definition is ``sequence.average_linkage``), per merge, best first -
+    the average descending as an exact rational, then the round, then ``a``; children before parents: ``a`` < ``b`` (int64: the
+    absorbing and the absorbed cluster, each named by its smallest member), ``weight`` (uint64: S, the sum of the integer weights
+    between them), ``size_a``, ``size_b``, ``round`` (int64) and ``sim`` (float64: S / (size_a * size_b) / 2^24); ``valid`` (bool
+    per row), ``rounds``, ``merged_per_round`` (int64), ``complete`` (the rounds ended because one merged nothing), ``n`` and the
+    ``stop`` it ran with.  :meth:`NNEngine.average_linkage_dev` leaves the per-node records on the device: the per-merge arrays and
+    ``valid`` are None here."""
+    FIELDS = _sequence.AVGLINK_FIELDS + ("sim", "valid", "rounds", "merged_per_round", "complete", "n", "stop")
+
+    def _arrays(self):
+        return {k: getattr(self, k) for k in _sequence.AVGLINK_FIELDS + ("sim", "valid")}
+
+    def cut(self, t) -> np.ndarray:
+        """``sequence.average_linkage_cut``: int64 label per row at the similarity ``t`` - the smallest member, -1 for an invalid row"""
+        return _sequence.average_linkage_cut(self._arrays(), t)
+
+    def cluster_counts(self, thresholds) -> np.ndarray:
+        """``sequence.average_linkage_cluster_counts``: the clusters a cut leaves at each threshold"""
+        return _sequence.average_linkage_cluster_counts(self._arrays(), thresholds)
+
+    def matrix(self) -> np.ndarray:
+        """``sequence.average_linkage_matrix``: SciPy's convention, distance = 1 - sim; all rows valid and a whole tree only"""
+        return _sequence.average_linkage_matrix(self._arrays())
+
+    def table(self, names=None):
+        """``sequence.average_linkage_table``: one record per merge - rank, a, b, sim, size, round, clusters left"""
+        return _sequence.average_linkage_table(self._arrays(), names)
 
 
 class VoteResult(_Result):
@@ -1437,6 +1472,104 @@ class NNEngine:
         """measurement only (``gnn_debug_spread_ms``): with profiling enabled, the HIP-event milliseconds of the last :meth:`spread`
         / :meth:`spread_dev` call - [validate and symmetrise, then every iteration]"""
         return self._debug_ms(self.lib.gnn_debug_spread_ms)
+
+    # -- average linkage -----------------------------------------------------------------
+    @staticmethod
+    def _avglink_knobs(stop, max_rounds):
+        """the knobs as the library takes them; a ``ValueError`` for one out of range, before anything is allocated"""
+        return (_sequence.average_linkage_stop(stop), _sequence._whole(max_rounds, "max_rounds", 1, _sequence.AVGLINK_MAX_ROUNDS_MAX))
+
+    def _avglink_call(self, fn, graph, n, nnz, knobs, outs):
+        stop_q, max_rounds = knobs
+        merged = np.zeros(min(max_rounds, int(n) + 1), dtype=np.int64)      # a round that is not the last merges a pair
+        rounds, complete = C.c_int64(0), C.c_int(0)
+        check(fn(self.ctx, *graph, int(n), int(nnz), stop_q, max_rounds, *outs, merged.ctypes.data, C.addressof(rounds), C.addressof(complete)))
+        return dict(rounds=int(rounds.value), complete=bool(complete.value), merged_per_round=merged[:rounds.value], n=int(n),
+                    stop=stop_q / _sequence.MCL_W)
+
+    def average_linkage(self, indptr, col, sim, valid=None, stop=_sequence.AVGLINK_STOP_DEFAULT,
+                        max_rounds=_sequence.AVGLINK_MAX_ROUNDS_MAX) -> AverageLinkageResult:
+        """Average linkage over a similarity graph (``gnn_avglink``; the definition is ``sequence.average_linkage``): the UPGMA tree
+        of the upper-triangle CSR (``indptr``, ``col``, ``sim``) :meth:`graph` returns, by rounds of reciprocal best pairs - two
+        groups merge by their *mean* similarity, so one bridge pair chains nothing, there is no knob to guess, and the tree answers
+        every cut level at once (:meth:`AverageLinkageResult.cut`).  A pair of rows without an entry counts as similarity 0.
+        ``stop``: a similarity in (0, 64), the smallest average that still merges; ``max_rounds`` (1..2^20).  In integers throughout:
+        every output equals the definition bit for bit.  ``ValueError`` for a knob out of range, ``GnnError`` for a graph that is
+        no such CSR."""
+        knobs = self._avglink_knobs(stop, max_rounds)
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        with np.errstate(over="ignore"):
+            sim = np.ascontiguousarray(sim, dtype=np.float32)
+        n = len(indptr) - 1
+        if indptr.ndim != 1 or n < 0 or col.ndim != 1 or sim.shape != col.shape:
+            raise ValueError("indptr (n + 1,), col (nnz,) and sim (nnz,) are required")
+        ok = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+        if ok is not None and ok.shape != (n,):
+            raise ValueError(f"valid must have one entry per row ({n})")
+        parent, weight = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.uint64)
+        size_a, size_b, rnd = (np.empty(n, dtype=np.int32) for _ in range(3))
+        kw = self._avglink_call(self.lib.gnn_avglink, (indptr.ctypes.data, col.ctypes.data, sim.ctypes.data, None if ok is None else ok.ctypes.data),
+                                n, len(col), knobs, [a.ctypes.data for a in (parent, weight, size_a, size_b, rnd)])
+        b = np.flatnonzero(parent >= 0)                   # the host's part: the per-node records as the ordered merge list
+        merges = _sequence.average_linkage_order(parent[b], b, weight[b], size_a[b], size_b[b], rnd[b])
+        return AverageLinkageResult(**merges, valid=np.ones(n, dtype=bool) if ok is None else ok.astype(bool), **kw)
+
+    def average_linkage_dev(self, indptr_ptr: int, col_ptr, sim_ptr, n: int, nnz: int, parent_ptr: int, weight_ptr: int, size_a_ptr: int,
+                            size_b_ptr: int, round_ptr: int, valid_ptr=None, stop=_sequence.AVGLINK_STOP_DEFAULT,
+                            max_rounds=_sequence.AVGLINK_MAX_ROUNDS_MAX) -> AverageLinkageResult:
+        """``gnn_avglink_dev``: device pointers in - indptr (n + 1 int64), col (nnz int32) and sim (nnz f32) exactly as
+        :meth:`graph_count_dev` and :meth:`graph_fill_dev` wrote them, valid (n uint8, or None) - and out, per node, written where
+        the node was absorbed (parent: n int32, -1 for a node never absorbed; weight: n uint64; size_a, size_b, round: n int32); the
+        engine's stream is synchronised once per round.  Returns an :class:`AverageLinkageResult` without the per-merge arrays."""
+        knobs = self._avglink_knobs(stop, max_rounds)
+        return AverageLinkageResult(**self._avglink_call(self.lib.gnn_avglink_dev, (indptr_ptr, col_ptr, sim_ptr, valid_ptr), n, nnz, knobs,
+                                                         [parent_ptr, weight_ptr, size_a_ptr, size_b_ptr, round_ptr]))
+
+    def _avglink_knob(self, fn, value) -> int:
+        before = fn(self.ctx, int(value))
+        if before < 0:
+            check(before)
+        return int(before)
+
+    def set_average_linkage_slots(self, slots: int) -> int:
+        """test aid (``gnn_debug_avglink_slots``): the slots (0..4096, the default) of the LDS table :meth:`average_linkage` sums a
+        row's entries in - a row with more entries takes the accumulator in global memory, with 0 every row; -1 changes nothing.
+        Returns the value before the call.  No result depends on it."""
+        return self._avglink_knob(self.lib.gnn_debug_avglink_slots, slots)
+
+    def set_average_linkage_wave_rows(self, entries: int) -> int:
+        """test aid (``gnn_debug_avglink_wave_rows``): the longest upper bound (0..4096; the default is 256) of a row that one wave
+        of :meth:`average_linkage` takes with its quarter of the table; 0: none; -1 changes nothing.  Returns the value before the
+        call.  No result depends on it."""
+        return self._avglink_knob(self.lib.gnn_debug_avglink_wave_rows, entries)
+
+    def set_average_linkage_groups(self, groups: int):
+        """test aid (``gnn_debug_avglink_groups``): the workgroups of a contraction of :meth:`average_linkage` (0: the library's
+        choice); no result depends on it."""
+        check(self.lib.gnn_debug_avglink_groups(self.ctx, int(groups)))
+
+    def average_linkage_order(self, quads) -> np.ndarray:
+        """test aid (``gnn_debug_avglink_order``): the device's order function over ``quads`` (m, 4) uint64 = (s1, d1, s2, d2):
+        int32 (m,) of -1 / 0 / 1 as s1 / d1 is below, equal to or above s2 / d2"""
+        quads = np.ascontiguousarray(quads, dtype=np.uint64)
+        if quads.ndim != 2 or quads.shape[1] != 4:
+            raise ValueError("quads (m, 4) uint64 is required")
+        out = np.empty(len(quads), dtype=np.int32)
+        check(self.lib.gnn_debug_avglink_order(self.ctx, quads.ctypes.data, len(quads), out.ctypes.data))
+        return out
+
+    def average_linkage_pass_ms(self):
+        """measurement only (``gnn_debug_avglink_ms``): with profiling enabled, the HIP-event milliseconds of the last
+        :meth:`average_linkage` / :meth:`average_linkage_dev` call - [validate and symmetrise, then every round]"""
+        return self._debug_ms(self.lib.gnn_debug_avglink_ms)
+
+    def average_linkage_classes(self) -> np.ndarray:
+        """measurement only (``gnn_debug_avglink_classes``): the rows the contractions of the last call took by class, all rounds
+        together - int64 [one wave, one workgroup, the accumulator in global memory]"""
+        out = np.zeros(3, dtype=np.int64)
+        check(self.lib.gnn_debug_avglink_classes(self.ctx, out.ctypes.data))
+        return out
 
     # -- spherical k-means ---------------------------------------------------------------
     def kmeans(self, rows, k, init=None, max_iter=_sequence.KMEANS_MAX_ITER_DEFAULT) -> KMeansResult:

@@ -914,6 +914,53 @@ def write_mcl(npz_path, tsv_path, names_key, names, res, request, strand="forwar
     write_mcl_tsv(tsv_path, names, res)
 
 
+def average_linkage_requested():
+    """GENOMAD_AMD_AVERAGE_LINKAGE=<cut similarity in (0, 1]>: main() also writes the average-linkage (UPGMA) clusters of the contigs -
+    groups merge by the *mean* similarity between them over the similarity graph of GENOMAD_AMD_GRAPH, a pair without an edge counting
+    as 0, down to that mean (<prefix>_nn_average_linkage.npz and .tsv); unset or empty: nothing changes (None).  It needs
+    GENOMAD_AMD_GRAPH=<threshold>, which must be set with it (main() refuses the one without the other).  Any other value is an error.
+    Returns (the cut as it is compared: a multiple of 2^-24, the graph's threshold as it is compared or None), or None."""
+    v = os.environ.get("GENOMAD_AMD_AVERAGE_LINKAGE", "").strip()
+    if not v:
+        return None
+    try:
+        cut = float(v)
+        if not 0.0 < cut <= 1.0:                         # a NaN fails both comparisons
+            raise ValueError
+        cut = sequence.average_linkage_stop(cut) / sequence.MCL_W
+    except ValueError:
+        raise ValueError(f"GENOMAD_AMD_AVERAGE_LINKAGE={v!r}: expected a float in (0, 1] (the mean cosine similarity between two groups "
+                         "down to which they merge)") from None
+    return cut, graph_requested()
+
+
+def _run_average_linkage(eng, emb, request):
+    """the graph at the request's threshold, computed again, and its average-linkage tree down to the cut"""
+    cut, threshold = request
+    g = eng.graph(emb, threshold, NEIGHBOUR_METRIC)
+    return eng.average_linkage(g.indptr, g.col, g.sim, g.valid, stop=cut), g.n_edges
+
+
+AVERAGE_LINKAGE_TSV_HEADER = "seq_name\tcluster\tcluster_size\n"
+
+
+def write_average_linkage(npz_path, tsv_path, names_key, names, res, request, strand="forward"):
+    """Both average-linkage files of a stage: the merges of an AverageLinkageResult with the contig names, the request and the labels
+    at the cut, and one line per contig - the name of its cluster's label contig and the cluster's size; a contig without a valid
+    embedding has NA and 0."""
+    label = res.cut(request[0])
+    size = np.where(label >= 0, np.bincount(label[label >= 0], minlength=len(label))[np.maximum(label, 0)], 0).astype(np.int64)
+    np.savez_compressed(npz_path, **{names_key: names, "cut": np.float64(request[0]), "threshold": np.float64(request[1]),
+                                     "metric": np.array(NEIGHBOUR_METRIC), "a": res.a, "b": res.b, "weight": res.weight, "size_a": res.size_a,
+                                     "size_b": res.size_b, "round": res.round, "sim": res.sim, "valid": res.valid, "label": label, "size": size,
+                                     "rounds": np.int64(res.rounds), "merged_per_round": res.merged_per_round,
+                                     "complete": np.bool_(res.complete), **_strand_entry(strand)})
+    with open(tsv_path, "w") as fout:
+        fout.write(AVERAGE_LINKAGE_TSV_HEADER)
+        for i, name in enumerate(names):
+            fout.write(f"{name}\tNA\t0\n" if label[i] < 0 else f"{name}\t{names[label[i]]}\t{size[i]}\n")
+
+
 def match_requested():
     """GENOMAD_AMD_MATCH=<float in [-1, 1]>: main() also writes, for every contig, ALL the rows of the reference named by
     GENOMAD_AMD_MATCH_BASE whose encoder embedding has at least that cosine similarity to the contig's per-contig embedding of
@@ -1323,7 +1370,7 @@ def _encode(fasta_path, enc_dir: Path, window_id_path: Path, single_window: bool
 
 
 # ---- the analyses of the gathered per-contig embeddings ------------------------------------------------------------------------------
-# Thirteen analyses follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
+# Fourteen analyses follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
 #   name      the stem of its files, <prefix>_nn_<name>.npz and - where ``tsv`` - .tsv
 #   switch    the environment variable that requests it; ``request()`` reads it (and its companions): the request, or None
 #   needs     the middle clause of the message that refuses the switch without GENOMAD_AMD_EMBEDDINGS=1
@@ -1394,6 +1441,15 @@ ANALYSES = (        # in the order they run, which is the order of the log lines
                                         f"{res[0].n_clusters} clusters in {res[0].iterations} iterations, "
                                         f"{'converged' if res[0].converged else 'not converged'}"),
              errors=(ValueError, GnnError), advice="Raise GENOMAD_AMD_GRAPH or unset GENOMAD_AMD_MCL.", after="graph"),      # the graph's cap on its edges
+    Analysis("average_linkage", "GENOMAD_AMD_AVERAGE_LINKAGE", average_linkage_requested,
+             "the groups merge by their mean similarity over the similarity graph of the per-contig encoder embeddings",
+             (("cut", float), ("threshold", float)), "Average-linkage clusters of the {what}s",
+             lambda eng, emb, r, ctx: _run_average_linkage(eng, emb, r),
+             lambda npz, tsv, key, names, res, strand, ctx: write_average_linkage(npz, tsv, key, names, res[0], ctx.request, strand),
+             lambda res, r, what, ctx: (f"{_SIMILARITY} >= {r[1]:g}, {res[1]} edges, mean similarity >= {r[0]:g}, a pair without an edge "
+                                        f"counting as 0: {int(res[0].valid.sum()) - len(res[0].a)} clusters, {len(res[0].a)} merges in "
+                                        f"{res[0].rounds} rounds"),
+             errors=(ValueError, GnnError), advice="Raise GENOMAD_AMD_GRAPH or unset GENOMAD_AMD_AVERAGE_LINKAGE.", after="graph"),
     Analysis("density", "GENOMAD_AMD_DENSITY", density_requested,
              "density clusters are formed among the per-contig encoder embeddings", (("threshold", float), ("min_points", int)),
              "Density clusters of the {what}s",

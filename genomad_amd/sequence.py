@@ -2435,6 +2435,177 @@ def spread_table(best, best_score, second_score, total, first, names=None, class
             for i in range(len(label))]
 
 
+AVGLINK_STOP_DEFAULT = 2.0 ** -24  # stop_q = 1: every merge with a positive average
+AVGLINK_MAX_ROUNDS_MAX = 1 << 20
+AVGLINK_FIELDS = ("a", "b", "weight", "size_a", "size_b", "round")
+
+
+def average_linkage_stop(stop) -> int:
+    """``stop_q`` = rint(``stop`` * 2^24), the smallest average (in units of 2^-24) at which a pair still merges, for a float in
+    (0, 64) that rounds to 1 at the least; anything else is a ``ValueError``."""
+    try:
+        s = float(stop)
+        ok = not isinstance(stop, (bool, np.bool_)) and 0.0 < s < MCL_SIM_END
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    q = int(np.rint(s * MCL_W)) if ok else 0
+    if not 1 <= q < (1 << 30):
+        raise ValueError(f"stop {stop!r}: a similarity in (0, 64) that is at least 2^-25 is required")
+    return q
+
+
+def _avglink_better(s1, d1, id1, s2, d2, id2) -> bool:
+    """(s1 / d1, id1) comes before (s2 / d2, id2): the larger ratio, among equals the smaller id - in Python integers"""
+    l, r = s1 * d2, s2 * d1
+    return l > r or (l == r and id1 < id2)
+
+
+def average_linkage_order(a, b, weight, size_a, size_b, round):
+    """The merges of an average-linkage tree in its output order - the average ``weight / (size_a * size_b)`` descending as an exact
+    rational, then ``round`` ascending, then ``a`` ascending - as the arrays of :data:`AVGLINK_FIELDS` (``a``, ``b``, ``size_a``,
+    ``size_b``, ``round`` int64, ``weight`` uint64) and ``sim`` (float64: ``weight / (size_a * size_b) / 2^24``, rounded once)."""
+    import functools
+    m = [tuple(int(v) for v in t) for t in zip(a, b, weight, size_a, size_b, round)]
+
+    def cmp(x, y):
+        l, r = x[2] * y[3] * y[4], y[2] * x[3] * x[4]
+        if l != r:
+            return -1 if l > r else 1
+        return -1 if (x[5], x[0]) < (y[5], y[0]) else (1 if (x[5], x[0]) > (y[5], y[0]) else 0)
+
+    m.sort(key=functools.cmp_to_key(cmp))
+    cols = list(zip(*m)) if m else [()] * 6
+    out = {k: np.asarray(cols[i], dtype=np.uint64 if k == "weight" else np.int64) for i, k in enumerate(AVGLINK_FIELDS)}
+    from fractions import Fraction
+    out["sim"] = np.asarray([float(Fraction(w, sa * sb * MCL_W)) for _, _, w, sa, sb, _ in m], dtype=np.float64)
+    return out
+
+
+def average_linkage(indptr, col, sim, valid=None, stop=AVGLINK_STOP_DEFAULT, max_rounds=AVGLINK_MAX_ROUNDS_MAX):
+    """Average linkage (UPGMA) over a similarity graph by rounds of reciprocal best pairs, in integers throughout (the definition
+    ``gnn_avglink`` computes on the device).  The graph is the upper-triangle CSR of :func:`threshold_graph`,
+    with ``valid`` (bool per row, None: all), read as :func:`markov_clusters` reads it.
+
+    Weights: q = rint(float32(sim) * 2^24); an entry with q <= 0 or an invalid end does not exist; parallel entries are added.
+    Clusters: a cluster's id is its smallest member; S(A, B) = the sum of q over the entries between A and B; the average is
+    S / (|A| * |B|) - a pair of rows without an entry counts as similarity 0, so on a graph cut at a threshold the average is a lower
+    bound of the true mean, and on a complete graph it is the true mean.
+    A round: every live cluster A with a neighbour names best[A], the neighbour B with the largest S(A, B) / |B| (ties to the smaller
+    id; S1 * |B2| against S2 * |B1| as exact integers), if S(A, B) >= stop_q * |A| * |B| (:func:`average_linkage_stop`); every pair
+    with best[A] = B, best[B] = A and A < B merges - B is absorbed into A -; the rows are contracted: columns relabelled, self entries
+    dropped, duplicates summed.  It stops behind the first round that merges nothing (``complete``) or behind ``max_rounds`` rounds.
+    A round in which a cluster names a best merges a pair (the largest pair under average, smaller id, larger id names itself).
+
+    Returns a dict: per merge, ordered by :func:`average_linkage_order` (children before parents), ``a`` < ``b`` (int64: the absorbing
+    and the absorbed cluster), ``weight`` (uint64: S), ``size_a``, ``size_b``, ``round`` (int64, from 0) and ``sim`` (float64);
+    ``valid``, ``rounds``, ``merged_per_round`` (int64), ``complete`` and ``stop`` (stop_q / 2^24)."""
+    stop_q = average_linkage_stop(stop)
+    max_rounds = _whole(max_rounds, "max_rounds", 1, AVGLINK_MAX_ROUNDS_MAX)
+    n, ea, eb, eq, ok = mcl_weights(indptr, col, sim, valid)
+    rows = {}
+    for x, y, w in zip(ea.tolist(), eb.tolist(), eq.tolist()):
+        rx, ry = rows.setdefault(x, {}), rows.setdefault(y, {})
+        rx[y] = rx.get(y, 0) + w
+        ry[x] = ry.get(x, 0) + w
+    size = {i: 1 for i in rows}
+    merges, merged, complete = [], [], False
+    while len(merged) < max_rounds and not complete:
+        best = {}
+        for A, row in rows.items():
+            top = None
+            for B, S in row.items():
+                if top is None or _avglink_better(S, size[B], B, top[1], size[top[0]], top[0]):
+                    top = (B, S)
+            if top is not None and top[1] >= stop_q * size[A] * size[top[0]]:
+                best[A] = top
+        pairs = [(A, B, S) for A, (B, S) in best.items() if A < B and B in best and best[B][0] == A]
+        merged.append(len(pairs))
+        complete = not pairs
+        if complete:
+            break
+        into = {}
+        for A, B, S in pairs:
+            merges.append((A, B, S, size[A], size[B], len(merged) - 1))
+            into[B] = A
+        for A, B, _ in pairs:
+            size[A] += size.pop(B)
+        contracted = {}
+        for A, row in rows.items():
+            R = into.get(A, A)
+            new = contracted.setdefault(R, {})
+            for c, S in row.items():
+                m = into.get(c, c)
+                if m != R:
+                    new[m] = new.get(m, 0) + S
+        rows = contracted
+    out = average_linkage_order(*zip(*merges)) if merges else average_linkage_order(*[()] * 6)
+    out.update(valid=ok, rounds=len(merged), merged_per_round=np.asarray(merged, dtype=np.int64), complete=complete, stop=stop_q / MCL_W)
+    return out
+
+
+def average_linkage_cut(result, t) -> np.ndarray:
+    """The clusters of an average-linkage tree (the dict of :func:`average_linkage`, or anything with its keys) at the similarity
+    ``t``: the merges with ``weight >= t_q * size_a * size_b`` applied, in Python integers (t_q = :func:`average_linkage_stop`).
+    Returns int64 ``label`` (n,): the smallest member of the row's cluster, -1 for an invalid row.  ``t`` below the tree's ``stop``
+    cuts where the tree stopped."""
+    t_q = average_linkage_stop(t)
+    valid = np.asarray(result["valid"]).astype(bool).ravel()
+    root = list(range(len(valid)))
+
+    def find(x):
+        while root[x] != x:
+            root[x] = root[root[x]]
+            x = root[x]
+        return x
+
+    for a, b, w, sa, sb in zip(*(np.asarray(result[k]).tolist() for k in AVGLINK_FIELDS[:5])):
+        if w >= t_q * sa * sb:
+            x, y = find(a), find(b)
+            root[max(x, y)] = min(x, y)                      # towards the smaller index: a root is its cluster's smallest row
+    label = np.array([find(i) for i in range(len(valid))], dtype=np.int64).reshape(len(valid))
+    label[~valid] = -1
+    return label
+
+
+def average_linkage_cluster_counts(result, thresholds) -> np.ndarray:
+    """Clusters (singletons included) among the valid rows that :func:`average_linkage_cut` leaves at each of ``thresholds``: the
+    valid rows minus the merges at or above it, int64."""
+    n_valid = int(np.count_nonzero(np.asarray(result["valid"])))
+    m = list(zip(*(np.asarray(result[k]).tolist() for k in ("weight", "size_a", "size_b"))))
+    return np.array([n_valid - sum(1 for w, sa, sb in m if w >= average_linkage_stop(t) * sa * sb) for t in np.atleast_1d(thresholds)],
+                    dtype=np.int64)
+
+
+def average_linkage_matrix(result) -> np.ndarray:
+    """The tree as a linkage matrix in the convention of SciPy's ``scipy.cluster.hierarchy.linkage`` (float64, (n - 1, 4)), as
+    :func:`linkage_matrix` builds it: per merge, in the tree's order, the ids of the two clusters merged (the smaller first), the
+    distance 1 - sim and the new cluster's size; a row is cluster i, the cluster of step k is n + k.  For all rows valid and a whole
+    tree of n - 1 merges (a complete graph, or a connected one with ``stop`` at its lowest): anything else is a ValueError."""
+    valid = np.asarray(result["valid"]).astype(bool).ravel()
+    n = len(valid)
+    a, b, sim = np.asarray(result["a"]).tolist(), np.asarray(result["b"]).tolist(), np.asarray(result["sim"], dtype=np.float64)
+    if n < 1 or not valid.all() or len(a) != n - 1:
+        raise ValueError(f"{len(a)} merges among {n} rows, {int(valid.sum())} of them valid: a linkage matrix needs n - 1 merges over n >= 1 "
+                         "valid rows")
+    cluster, size = list(range(n)), [1] * n              # at a cluster's id: its SciPy id and its size
+    z = np.zeros((n - 1, 4), dtype=np.float64)
+    for k in range(n - 1):
+        x, y = a[k], b[k]
+        z[k] = (min(cluster[x], cluster[y]), max(cluster[x], cluster[y]), 1.0 - sim[k], size[x] + size[y])
+        cluster[x], size[x] = n + k, size[x] + size[y]
+    return z
+
+
+def average_linkage_table(result, names=None):
+    """One record per merge of an average-linkage tree, best first: ``rank`` (from 1), ``a``, ``b`` (the names where ``names`` is
+    given), ``sim``, ``size`` (of the merged cluster), ``round`` and ``clusters_left`` among the valid rows once the merge is made."""
+    n_valid = int(np.count_nonzero(np.asarray(result["valid"])))
+    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    cols = [np.asarray(result[k]).tolist() for k in ("a", "b", "sim", "size_a", "size_b", "round")]
+    return [{"rank": k + 1, "a": name(a), "b": name(b), "sim": float(s), "size": int(sa + sb), "round": int(r), "clusters_left": n_valid - k - 1}
+            for k, (a, b, s, sa, sb, r) in enumerate(zip(*cols))]
+
+
 def prefix_of(input_path: Path) -> str:
     """nn_classification.py:106-108: stem, minus one more extension if the file is compressed."""
     prefix = Path(input_path).stem

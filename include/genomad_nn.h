@@ -915,6 +915,60 @@ int gnn_debug_spread_skip(gnn_ctx* ctx, int on);
  * symmetrise, then one figure per iteration; *n_out = the figures recorded, at most `capacity` are written. */
 int gnn_debug_spread_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
 
+/* ---- average linkage over a similarity graph: UPGMA rounds on the device ------------------------------------
+ * "Which groups have the largest mean similarity to each other, at every cut level at once": the average-linkage (UPGMA) tree of the
+ * graph gnn_graph_* writes, by rounds of reciprocal best pairs - where gnn_cluster and gnn_linkage chain through one bridge pair - in
+ * integers throughout, so that every output equals the definition (sequence.average_linkage) bit for bit, for any number of
+ * workgroups, any table size, any row class and any order they run in.  No forward pass runs and no other entry point's result changes.
+ *   graph     gnn_mcl's: an upper-triangle CSR with sim (f32, finite, < 64) and valid (uint8 [n], or NULL); exactly what
+ *             gnn_graph_fill_dev wrote is such a graph.  Anything else: GNN_ERR_ARG behind one O(nnz) kernel, before anything else
+ *             runs, the outputs untouched.
+ *   weights   W = 2^24.  q = rint(sim * W); an entry with q <= 0 or an invalid end does not exist; parallel entries are added.
+ *   clusters  a cluster's id is its smallest member.  S(A, B) = the sum of q over the entries between A and B; the average is
+ *             S / (|A| * |B|): a pair of rows without an entry counts as similarity 0.
+ *   round     every live cluster A with a neighbour names best[A] = the neighbour B with the largest S(A, B) / |B|, ties to the smaller
+ *             id - S1 * |B2| against S2 * |B1| as exact 128-bit integers - if S(A, B) >= stop_q * |A| * |B|; every pair with best[A] =
+ *             B, best[B] = A, A < B merges: B is absorbed into A.  The rows are contracted: columns relabelled, self entries dropped,
+ *             duplicates summed.  It stops behind the first round that merges nothing (*complete_host = 1) or behind max_rounds rounds;
+ *             *rounds_host counts them, merged_per_round_host[r] (capacity min(max_rounds, n + 1)) the pairs round r merged.  A round
+ *             in which a cluster names a best merges a pair: at most n rounds.
+ *   outputs   per node, written where the node was absorbed: parent (int32: the cluster that absorbed it; -1: never absorbed), weight
+ *             (uint64: S of the merge), size_a, size_b (int32: the sizes of the absorbing and the absorbed cluster before the merge),
+ *             round (int32, from 0).  A node never absorbed: -1, 0, 0, 0, 0.
+ *   ranges    0 <= n <= 2^24, nnz >= 0, stop_q in [1, 2^30), max_rounds in [1, 2^20]; GNN_ERR_ARG with the value and the range in the
+ *             message - checked before the ctx is looked at.  n == 0: nothing is launched; one round that merges nothing.
+ *   exact     S < 2^63 and |A| * |B| < 2^48: every sum is a 64-bit integer add - into a table in LDS keyed by the relabelled column,
+ *             or, for a row with more entries than the table has slots, into an accumulator in global memory - and every comparison
+ *             a comparison of two 128-bit products.  No float is added or compared, nothing depends on an order.
+ * What it is not: not the mean over existing entries only (a missing pair is a 0, so on a graph cut at a threshold the average is a
+ * lower bound of the true mean); not complete linkage or Ward; not approximate; a round rewrites every live row; not multi-GPU.
+ * Device memory, persistent in the ctx and grow-only: 32 B per symmetric entry (two per edge), about 70 B per row, at most 192 MB of
+ * accumulators (gnn_avglink: + the graph and 24 B per row of results).  A failed allocation: GNN_ERR_NOMEM, outputs untouched.
+ * gnn_avglink: host pointers, synchronous.  gnn_avglink_dev: device pointers in and out; merged_per_round, rounds and complete on the
+ * host; the ctx stream is synchronised once for the verdict on the graph and once per round (8 bytes). */
+int gnn_avglink(gnn_ctx* ctx, const int64_t* indptr_host, const int32_t* col_host, const float* sim_host, const uint8_t* valid_host_or_null,
+                int64_t n, int64_t nnz, int64_t stop_q, int max_rounds, int32_t* parent_host, uint64_t* weight_host, int32_t* size_a_host,
+                int32_t* size_b_host, int32_t* round_host, int64_t* merged_per_round_host, int64_t* rounds_host, int* complete_host);
+int gnn_avglink_dev(gnn_ctx* ctx, const int64_t* indptr_dev, const int32_t* col_dev, const float* sim_dev, const uint8_t* valid_dev_or_null,
+                    int64_t n, int64_t nnz, int64_t stop_q, int max_rounds, int32_t* parent_dev, uint64_t* weight_dev, int32_t* size_a_dev,
+                    int32_t* size_b_dev, int32_t* round_dev, int64_t* merged_per_round_host, int64_t* rounds_host, int* complete_host);
+/* test aids; no result depends on them.  gnn_debug_avglink_slots: the slots of the LDS table, 0 .. 4096 (0: every row takes the
+ * accumulator in global memory; -1: leave it as it is); returns the value before the call (>= 0), or GNN_ERR_ARG.
+ * gnn_debug_avglink_wave_rows: the longest upper bound of a row that a single wave takes, 0 .. 4096 (0: none; -1: leave it); returns
+ * the value before the call.  gnn_debug_avglink_groups: the workgroups of a contraction, 1 .. 65535 (0: the library's choice, eight per
+ * CU).  gnn_debug_avglink_order: the order function of the best scan and the stop test, run on the device over n quadruples (s1, d1,
+ * s2, d2) of uint64 on the host: out_host[i] (int32) = -1, 0 or 1 as s1 / d1 is below, equal to or above s2 / d2. */
+int gnn_debug_avglink_slots(gnn_ctx* ctx, int slots);
+int gnn_debug_avglink_wave_rows(gnn_ctx* ctx, int entries);
+int gnn_debug_avglink_groups(gnn_ctx* ctx, int groups);
+int gnn_debug_avglink_order(gnn_ctx* ctx, const uint64_t* quads_host, int64_t n, int32_t* out_host);
+/* measurement only.  gnn_debug_avglink_ms: with gnn_profile_enable on, the HIP-event milliseconds of the ctx's last gnn_avglink* call:
+ * [0] validate and symmetrise, then one figure per round; *n_out = the figures recorded, at most `capacity` are written.
+ * gnn_debug_avglink_classes: the rows the contractions of that call took by class, all rounds together: [one wave, one workgroup, the
+ * accumulator in global memory]. */
+int gnn_debug_avglink_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
+int gnn_debug_avglink_classes(gnn_ctx* ctx, int64_t* rows_out);
+
 /* ---- matches against a reference: the bipartite similarity graph query x base ------------------------------
  * "Which reference rows is every new row within the threshold of, all of them": every pair (i, j) of a valid query row i and a valid
  * base row j with sim(i, j) >= threshold and its similarity, as a CSR by query row.  The passes, the kernel, the workspace and the
