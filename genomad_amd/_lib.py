@@ -170,6 +170,16 @@ SIGNATURES = {
     "gnn_debug_avglink_order": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_debug_avglink_ms": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_debug_avglink_classes": (_int, [_vp, _vp]),
+    "gnn_communities": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_communities_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_label_components": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "gnn_label_components_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "gnn_debug_communities_slots": (_int, [_vp, _int]),
+    "gnn_debug_communities_wave_rows": (_int, [_vp, _int]),
+    "gnn_debug_communities_groups": (_int, [_vp, _int]),
+    "gnn_debug_communities_gain": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_debug_communities_ms": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_debug_communities_classes": (_int, [_vp, _vp]),
     "gnn_kmeans": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_kmeans_dev": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_centroids": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp]),

@@ -418,6 +418,43 @@ struct AvglinkWorkspace {
     int64_t class_rows[3] = {0, 0, 0};           // the last call's rows by class, all rounds (gnn_debug_avglink_classes)
 };
 
+// ---- modularity communities (gnn_communities.hip): persistent, grow-only.  The symmetric graph and two entry buffers (12 B per entry
+// each, two entries per edge, + 4 B of symmetrise's weights), about 190 B per row of state, lists and maps, at most 2^24 cells of dense
+// accumulators (192 MB) and, for gnn_communities / gnn_label_components alone, the graph and the results.
+struct CommunitiesWorkspace {
+    int slots = 4096;                            // slots of the LDS table (gnn_debug_communities_slots): 0 .. 4096; no result depends on it
+    int wave_rows = 256;                         // the longest row one wave takes (gnn_debug_communities_wave_rows); no result depends on it
+    int groups = 0;                              // workgroups of a launch (gnn_debug_communities_groups); 0: the library's choice; no result depends on it
+    DevBuf<uint8_t> ok;                          // [n]: the row takes part
+    DevBuf<int32_t> len[2];                      // [n]: entries of a node's segment in entry buffer b
+    DevBuf<int64_t> off[2];                      // [n + 1]: where it starts
+    DevBuf<unsigned long long> cursor;           // [n]: symmetrise's
+    DevBuf<int32_t> idx[2];                      // the entries, ping-pong over the levels: the neighbour node
+    DevBuf<unsigned long long> sum[2];           // and the summed weight
+    DevBuf<uint32_t> sq;                         // symmetrise's weights, widened into sum[0]
+    DevBuf<int32_t> comm[2];                     // [n]: the assignment and the sweep's proposal
+    DevBuf<unsigned long long> tot[2];           // [n]: their communities' totals
+    DevBuf<unsigned long long> k;                // [n]: a node's weight
+    DevBuf<int32_t> want_c;                      // [n]: the community a node wants, -1: none
+    DevBuf<unsigned long long> want_d;           // [n][2]: its gain D, low and high word
+    DevBuf<int32_t> parent, comp, flag, ub, mcount, mlist;      // [n] each: the level's end, see gnn_communities.hip
+    DevBuf<int64_t> numoff, mstart;              // [n + 1]: a component's number, where its member list starts
+    DevBuf<unsigned long long> mcursor;          // [n]
+    DevBuf<int32_t> map;                         // [n]: row -> its node, -1: an invalid row
+    DevBuf<int32_t> noderow[2];                  // [n]: node -> its smallest row
+    DevBuf<int32_t> rows;                        // [3][n]: the nodes of a launch by class - wave, workgroup, dense
+    DevBuf<unsigned long long> dense;            // [dense workgroups][n]: all zero between rows
+    DevBuf<int32_t> touched;                     // [dense workgroups][n]
+    HostCounters count;                          // see gnn_communities.hip, "the counters"
+    DevBuf<int64_t> d_indptr;                    // gnn_communities, gnn_label_components: the graph
+    DevBuf<int32_t> d_col;
+    DevBuf<float> d_sim;
+    DevBuf<uint8_t> d_valid;
+    DevBuf<int64_t> d_out;                       // gnn_communities: [label | size | level_label], gnn_label_components: [label | out]; a Landing
+    PassLog passes;                              // profiling on: the last call's [setup, then per level every sweep and, behind an accepted one, the level's end]
+    int64_t class_rows[6] = {0, 0, 0, 0, 0, 0};  // the last call's rows by class: the want launches', the contractions' (gnn_debug_communities_classes)
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -622,9 +659,10 @@ struct gnn_ctx {
     gnn::MclWorkspace mcl;                        // gnn_mcl.hip
     gnn::SpreadWorkspace sprd;                    // gnn_spread.hip
     gnn::AvglinkWorkspace avl;                    // gnn_avglink.hip
+    gnn::CommunitiesWorkspace cmt;                // gnn_communities.hip
     // every PassLog above: drain_profile settles them before an event they hold returns to event_pool
-    gnn::PassLog* const pass_logs[10] = {&rp.rounds, &lk.rounds, &lk.tree_rounds, &gr.passes,  &km.passes, &pca.passes,
-                                         &vt.passes, &mcl.passes, &sprd.passes, &avl.passes};
+    gnn::PassLog* const pass_logs[11] = {&rp.rounds, &lk.rounds, &lk.tree_rounds, &gr.passes,  &km.passes, &pca.passes,
+                                         &vt.passes, &mcl.passes, &sprd.passes, &avl.passes, &cmt.passes};
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;

@@ -406,6 +406,15 @@ class GraphResult(_Result):
         as there"""
         return engine.average_linkage(self.indptr, self.col, self.sim, valid=self.valid, **kw)
 
+    def communities(self, engine, **kw) -> "CommunityResult":
+        """:meth:`NNEngine.communities` of this graph and its rows' validity: modularity communities, with ``resolution``,
+        ``max_levels`` and ``max_sweeps`` as there"""
+        return engine.communities(self.indptr, self.col, self.sim, valid=self.valid, **kw)
+
+    def label_components(self, engine, label) -> np.ndarray:
+        """:meth:`NNEngine.label_components` of this graph and its rows' validity: the connected parts of every label's rows"""
+        return engine.label_components(self.indptr, self.col, self.sim, label, valid=self.valid)
+
     @classmethod
     def build(cls, arrays, valid, threshold, metric):
         """from the (indptr, col, sim) of ``sequence.threshold_graph`` or the library, and the rows' validity"""
@@ -554,6 +563,36 @@ class AverageLinkageResult(_Result):
     def table(self, names=None):
         """``sequence.average_linkage_table``: one record per merge - rank, a, b, sim, size, round, clusters left"""
         return _sequence.average_linkage_table(self._arrays(), names)
+
+
+class CommunityResult(_Result):
+    """What :meth:`NNEngine.communities` returns (the definition is ``sequence.modularity_communities``), per row: ``label`` (int64:
+    the smallest row of its community; -1 for an invalid row) and ``size`` (int64); ``level_label`` (int64 (levels, n)): the labelling
+    behind each level, every level's communities nested in the next one's; per level (int64) ``nodes``, ``communities``, ``sweeps``,
+    ``accepted``, ``moved``, ``rejected``, ``split`` and ``qnum`` (a list of Python ints; ``qnum_words`` uint64 (levels, 2): the
+    device's low and high word, two's complement); ``levels``, ``complete``, ``m2``, ``resolution``, ``modularity`` (float64: the last
+    qnum / (64 * m2^2); 0.0 without a level), ``valid`` and ``n``.  :meth:`NNEngine.communities_dev` leaves ``label``, ``size`` and
+    ``level_label`` on the device: they and ``valid`` are None here."""
+    FIELDS = (("label", "size", "level_label") + _sequence.COMM_LEVEL_FIELDS +
+              ("qnum", "qnum_words", "levels", "complete", "m2", "resolution", "modularity", "valid", "n"))
+
+    @property
+    def n_communities(self) -> int:
+        return int(np.count_nonzero(self.label == np.arange(self.n)))
+
+    def at_level(self, level) -> np.ndarray:
+        """int64 label per row behind level ``level`` (negative: from the last): the finest partition is level 0"""
+        return self.level_label[level]
+
+    def table(self, names=None):
+        """``sequence.communities_table``: one record per community - label, size, members"""
+        return _sequence.communities_table({"label": self.label, "size": self.size}, names)
+
+    @classmethod
+    def build(cls, result):
+        """from the dict of ``sequence.modularity_communities``"""
+        words = np.array([[q & (2 ** 64 - 1), (q >> 64) & (2 ** 64 - 1)] for q in result["qnum"]], dtype=np.uint64).reshape(-1, 2)
+        return cls(**{k: result[k] for k in cls.FIELDS if k in result}, qnum_words=words, n=len(result["label"]))
 
 
 class VoteResult(_Result):
@@ -1569,6 +1608,132 @@ class NNEngine:
         together - int64 [one wave, one workgroup, the accumulator in global memory]"""
         out = np.zeros(3, dtype=np.int64)
         check(self.lib.gnn_debug_avglink_classes(self.ctx, out.ctypes.data))
+        return out
+
+    # -- modularity communities ------------------------------------------------------------
+    @staticmethod
+    def _communities_knobs(resolution, max_levels, max_sweeps):
+        """the knobs as the library takes them; a ``ValueError`` for one out of range, before anything is allocated"""
+        return (_sequence.communities_resolution(resolution), _sequence._whole(max_levels, "max_levels", 1, _sequence.COMM_LEVELS_MAX),
+                _sequence._whole(max_sweeps, "max_sweeps", 1, _sequence.COMM_SWEEPS_MAX))
+
+    @staticmethod
+    def _csr_arrays(indptr, col, sim, valid):
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        with np.errstate(over="ignore"):
+            sim = np.ascontiguousarray(sim, dtype=np.float32)
+        n = len(indptr) - 1
+        if indptr.ndim != 1 or n < 0 or col.ndim != 1 or sim.shape != col.shape:
+            raise ValueError("indptr (n + 1,), col (nnz,) and sim (nnz,) are required")
+        ok = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+        if ok is not None and ok.shape != (n,):
+            raise ValueError(f"valid must have one entry per row ({n})")
+        return indptr, col, sim, ok, n
+
+    def _communities_call(self, fn, graph, n, nnz, knobs, outs):
+        r, max_levels, max_sweeps = knobs
+        stats = np.zeros((max_levels, len(_sequence.COMM_LEVEL_FIELDS)), dtype=np.int64)
+        words = np.zeros((max_levels, 2), dtype=np.uint64)
+        levels, complete, m2 = C.c_int64(0), C.c_int(0), C.c_uint64(0)
+        check(fn(self.ctx, *graph, int(n), int(nnz), r, max_levels, max_sweeps, *outs, stats.ctypes.data, words.ctypes.data,
+                 C.addressof(levels), C.addressof(complete), C.addressof(m2)))
+        lv, m2 = int(levels.value), int(m2.value)
+        qnum = [((int(hi) << 64) | int(lo)) - ((1 << 128) if int(hi) >> 63 else 0) for lo, hi in words[:lv]]
+        from fractions import Fraction
+        out = {f: stats[:lv, k].copy() for k, f in enumerate(_sequence.COMM_LEVEL_FIELDS)}
+        out.update(qnum=qnum, qnum_words=words[:lv].copy(), levels=lv, complete=bool(complete.value), m2=m2, resolution=r / _sequence.COMM_R_ONE,
+                   modularity=float(Fraction(qnum[-1], 64 * m2 * m2)) if qnum else 0.0, n=int(n))
+        return out
+
+    def communities(self, indptr, col, sim, valid=None, resolution=1.0, max_levels=_sequence.COMM_LEVELS_MAX,
+                    max_sweeps=_sequence.COMM_SWEEPS_MAX) -> CommunityResult:
+        """Modularity communities of a similarity graph (``gnn_communities``; the definition is
+        ``sequence.modularity_communities``): Louvain's levels over the upper-triangle CSR (``indptr``, ``col``, ``sim``)
+        :meth:`graph` returns - a partition that scores itself (``modularity``), with one knob that has a natural default
+        (``resolution`` 1, a multiple of 1/64 in [1/64, 4]) and a coarse-to-fine hierarchy (``level_label``).  ``max_levels`` (1..32),
+        ``max_sweeps`` per level (1..2^20).  In integers throughout: every output equals the definition bit for bit.  Every community
+        is connected (the split at a level's end), which is not Leiden's refinement: well-connectedness is not guaranteed.
+        ``ValueError`` for a knob out of range, ``GnnError`` for a graph that is no such CSR or whose doubled weight reaches 2^58."""
+        knobs = self._communities_knobs(resolution, max_levels, max_sweeps)
+        indptr, col, sim, ok, n = self._csr_arrays(indptr, col, sim, valid)
+        label, size = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+        level_label = np.empty((knobs[1], n), dtype=np.int64)
+        kw = self._communities_call(self.lib.gnn_communities,
+                                    (indptr.ctypes.data, col.ctypes.data, sim.ctypes.data, None if ok is None else ok.ctypes.data), n, len(col),
+                                    knobs, [a.ctypes.data for a in (label, size, level_label)])
+        return CommunityResult(label=label, size=size, level_label=level_label[:kw["levels"]].copy(),
+                               valid=np.ones(n, dtype=bool) if ok is None else ok.astype(bool), **kw)
+
+    def communities_dev(self, indptr_ptr: int, col_ptr, sim_ptr, n: int, nnz: int, label_ptr: int, size_ptr: int, level_label_ptr: int,
+                        valid_ptr=None, resolution=1.0, max_levels=_sequence.COMM_LEVELS_MAX,
+                        max_sweeps=_sequence.COMM_SWEEPS_MAX) -> CommunityResult:
+        """``gnn_communities_dev``: device pointers in - indptr (n + 1 int64), col (nnz int32) and sim (nnz f32) exactly as
+        :meth:`graph_count_dev` and :meth:`graph_fill_dev` wrote them, valid (n uint8, or None) - and out: label and size (n int64
+        each) and level_label (``max_levels`` x n int64, of which the first ``levels`` rows are written); the engine's stream is
+        synchronised once per sweep.  Returns a :class:`CommunityResult` without the per-row arrays."""
+        knobs = self._communities_knobs(resolution, max_levels, max_sweeps)
+        return CommunityResult(**self._communities_call(self.lib.gnn_communities_dev, (indptr_ptr, col_ptr, sim_ptr, valid_ptr), n, nnz, knobs,
+                                                        [label_ptr, size_ptr, level_label_ptr]))
+
+    def label_components(self, indptr, col, sim, label, valid=None) -> np.ndarray:
+        """``gnn_label_components`` (the definition is ``sequence.label_components``): for any labelling of the rows (int64, -1:
+        none) the connected components of every label's induced subgraph over the graph's existing entries - int64 per row, the
+        smallest row of its component; -1 for label -1 and for an invalid row."""
+        indptr, col, sim, ok, n = self._csr_arrays(indptr, col, sim, valid)
+        label = np.asarray(label)
+        if label.shape != (n,) or label.dtype.kind not in "iu" or (label < -1).any():
+            raise ValueError(f"label must be an integer array of {n} with values >= -1")
+        label = np.ascontiguousarray(label, dtype=np.int64)
+        out = np.empty(n, dtype=np.int64)
+        check(self.lib.gnn_label_components(self.ctx, indptr.ctypes.data, col.ctypes.data, sim.ctypes.data, None if ok is None else ok.ctypes.data,
+                                            n, len(col), label.ctypes.data, out.ctypes.data))
+        return out
+
+    def label_components_dev(self, indptr_ptr: int, col_ptr, sim_ptr, n: int, nnz: int, label_ptr: int, out_ptr: int, valid_ptr=None):
+        """``gnn_label_components_dev``: device pointers in (the graph as :meth:`graph_fill_dev` wrote it, label: n int64) and out
+        (n int64); enqueued on the engine's stream behind one synchronise for the verdict on the graph."""
+        check(self.lib.gnn_label_components_dev(self.ctx, indptr_ptr, col_ptr, sim_ptr, valid_ptr, int(n), int(nnz), label_ptr, out_ptr))
+
+    def set_communities_slots(self, slots: int) -> int:
+        """test aid (``gnn_debug_communities_slots``): the slots (0..4096, the default) of the LDS table :meth:`communities` sums a
+        row's entries in - a longer row takes the accumulator in global memory, with 0 every row; -1 changes nothing.  Returns the
+        value before the call.  No result depends on it."""
+        return self._avglink_knob(self.lib.gnn_debug_communities_slots, slots)
+
+    def set_communities_wave_rows(self, entries: int) -> int:
+        """test aid (``gnn_debug_communities_wave_rows``): the longest row (0..4096; the default is 256) that one wave of
+        :meth:`communities` takes with its quarter of the table; 0: none; -1 changes nothing.  Returns the value before the call.
+        No result depends on it."""
+        return self._avglink_knob(self.lib.gnn_debug_communities_wave_rows, entries)
+
+    def set_communities_groups(self, groups: int):
+        """test aid (``gnn_debug_communities_groups``): the workgroups of a launch of :meth:`communities` (0: the library's
+        choice); no result depends on it."""
+        check(self.lib.gnn_debug_communities_groups(self.ctx, int(groups)))
+
+    def communities_gain(self, operands) -> np.ndarray:
+        """test aid (``gnn_debug_communities_gain``): the device's gain and score arithmetic over ``operands`` (m, 12) uint64 =
+        (64 * M2, r, k, w_ic, w_ia, tot_c, tot_a, in, sq low, sq high, previous Qnum low, high): uint64 (m, 5) = (D low, D high,
+        Qnum low, Qnum high, Qnum > previous), 128-bit values in two's complement"""
+        operands = np.ascontiguousarray(operands, dtype=np.uint64)
+        if operands.ndim != 2 or operands.shape[1] != 12:
+            raise ValueError("operands (m, 12) uint64 is required")
+        out = np.empty((len(operands), 5), dtype=np.uint64)
+        check(self.lib.gnn_debug_communities_gain(self.ctx, operands.ctypes.data, len(operands), out.ctypes.data))
+        return out
+
+    def communities_pass_ms(self):
+        """measurement only (``gnn_debug_communities_ms``): with profiling enabled, the HIP-event milliseconds of the last
+        :meth:`communities` / :meth:`communities_dev` call - [setup, then per level every sweep and, behind a level with an accepted
+        sweep, its end (split, contraction and the next level's start)]"""
+        return self._debug_ms(self.lib.gnn_debug_communities_ms)
+
+    def communities_classes(self) -> np.ndarray:
+        """measurement only (``gnn_debug_communities_classes``): the rows the last call took by class, all launches together - int64
+        [one wave, one workgroup, the accumulator in global memory] of the want launches, then of the contractions"""
+        out = np.zeros(6, dtype=np.int64)
+        check(self.lib.gnn_debug_communities_classes(self.ctx, out.ctypes.data))
         return out
 
     # -- spherical k-means ---------------------------------------------------------------

@@ -88,10 +88,10 @@ class Outputs:
         # written only when GENOMAD_AMD_REGION_EMBEDDINGS=1 (encoder embeddings per called region; no counterpart in the reference)
         self.nn_region_embeddings_output = d / f"{p}_nn_region_embeddings.npz"
         self.provirus_nn_region_embeddings_output = d / f"{p}_provirus_nn_region_embeddings.npz"
-        # written only when the analysis is requested (the thirteen analyses of the per-contig embeddings, ANALYSES below: <stem>.npz and,
+        # written only when the analysis is requested (the analyses of the per-contig embeddings, ANALYSES below: <stem>.npz and,
         # for all but the neighbours, <stem>.tsv; no counterpart in the reference)
         for stage in self._STAGE.values():
-            for a in ANALYSES:
+            for a in ALL_ANALYSES:
                 setattr(self, f"{stage}nn_{a.name}_output", d / f"{p}_{stage}nn_{a.name}.npz")
                 if a.tsv:
                     setattr(self, f"{stage}nn_{a.name}_tsv_output", d / f"{p}_{stage}nn_{a.name}.tsv")
@@ -961,6 +961,53 @@ def write_average_linkage(npz_path, tsv_path, names_key, names, res, request, st
             fout.write(f"{name}\tNA\t0\n" if label[i] < 0 else f"{name}\t{names[label[i]]}\t{size[i]}\n")
 
 
+def communities_requested():
+    """GENOMAD_AMD_COMMUNITIES=<resolution, a multiple of 1/64 in [1/64, 4]>: main() also writes the modularity communities (Louvain's
+    levels) of the contigs over the similarity graph of GENOMAD_AMD_GRAPH - a partition that scores itself, 1 being the natural
+    resolution (<prefix>_nn_communities.npz and .tsv); unset or empty: nothing changes (None).  It needs GENOMAD_AMD_GRAPH=<threshold>,
+    which must be set with it (main() refuses the one without the other).  GENOMAD_AMD_COMMUNITIES_MAX_LEVELS=<integer in [1, 32]>
+    (default 32) caps the levels; it is an error without GENOMAD_AMD_COMMUNITIES.  Any other value of either is an error.  Returns
+    (resolution, the graph's threshold as it is compared or None, max_levels), or None."""
+    v = os.environ.get("GENOMAD_AMD_COMMUNITIES", "").strip()
+    if not v:
+        _env_refines("GENOMAD_AMD_COMMUNITIES_MAX_LEVELS", "GENOMAD_AMD_COMMUNITIES", "set the resolution of the communities or unset")
+        return None
+    try:
+        resolution = float(v)
+        sequence.communities_resolution(resolution)
+    except ValueError:
+        raise ValueError(f"GENOMAD_AMD_COMMUNITIES={v!r}: expected a multiple of 1/64 in [1/64, 4] (the resolution: the larger, the smaller "
+                         "the communities; 1 is modularity itself)") from None
+    return resolution, graph_requested(), _env_int("GENOMAD_AMD_COMMUNITIES_MAX_LEVELS", 1, sequence.COMM_LEVELS_MAX,
+                                                   "(the levels of the hierarchy at the most)", sequence.COMM_LEVELS_MAX)
+
+
+def _run_communities(eng, emb, request):
+    """the graph at the request's threshold, computed again, and its modularity communities"""
+    resolution, threshold, max_levels = request
+    g = eng.graph(emb, threshold, NEIGHBOUR_METRIC)
+    return eng.communities(g.indptr, g.col, g.sim, g.valid, resolution=resolution, max_levels=max_levels), g.n_edges
+
+
+COMMUNITIES_TSV_HEADER = "seq_name\tcommunity\tcommunity_size\n"
+
+
+def write_communities(npz_path, tsv_path, names_key, names, res, request, strand="forward"):
+    """Both community files of a stage: every array of a CommunityResult with the contig names and the request (Qnum as the device's
+    two words per level), and one line per contig - the name of its community's label contig and the community's size; a contig
+    without a valid embedding has NA and 0."""
+    np.savez_compressed(npz_path, **{names_key: names, "resolution": np.float64(request[0]), "threshold": np.float64(request[1]),
+                                     "max_levels": np.int64(request[2]), "metric": np.array(NEIGHBOUR_METRIC), "label": res.label,
+                                     "size": res.size, "level_label": res.level_label, "valid": res.valid,
+                                     **{k: getattr(res, k) for k in sequence.COMM_LEVEL_FIELDS}, "qnum_words": res.qnum_words,
+                                     "levels": np.int64(res.levels), "complete": np.bool_(res.complete), "m2": np.uint64(res.m2),
+                                     "modularity": np.float64(res.modularity), **_strand_entry(strand)})
+    with open(tsv_path, "w") as fout:
+        fout.write(COMMUNITIES_TSV_HEADER)
+        for i, name in enumerate(names):
+            fout.write(f"{name}\tNA\t0\n" if res.label[i] < 0 else f"{name}\t{names[res.label[i]]}\t{res.size[i]}\n")
+
+
 def match_requested():
     """GENOMAD_AMD_MATCH=<float in [-1, 1]>: main() also writes, for every contig, ALL the rows of the reference named by
     GENOMAD_AMD_MATCH_BASE whose encoder embedding has at least that cosine similarity to the contig's per-contig embedding of
@@ -1370,7 +1417,7 @@ def _encode(fasta_path, enc_dir: Path, window_id_path: Path, single_window: bool
 
 
 # ---- the analyses of the gathered per-contig embeddings ------------------------------------------------------------------------------
-# Fourteen analyses follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
+# Fifteen analyses (ALL_ANALYSES) follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
 #   name      the stem of its files, <prefix>_nn_<name>.npz and - where ``tsv`` - .tsv
 #   switch    the environment variable that requests it; ``request()`` reads it (and its companions): the request, or None
 #   needs     the middle clause of the message that refuses the switch without GENOMAD_AMD_EMBEDDINGS=1
@@ -1511,6 +1558,21 @@ ANALYSES = (        # in the order they run, which is the order of the log lines
                                ", with 'labels' added", _same_vote_base), after="graph"),
 )
 
+# The fifteenth analysis.  It stands in a table of its own behind ANALYSES, so that table stays what the earlier analyses' tests
+# count; main() walks ALL_ANALYSES, and everything said of a record above holds for these.
+MORE_ANALYSES = (
+    Analysis("communities", "GENOMAD_AMD_COMMUNITIES", communities_requested,
+             "modularity is optimised over the similarity graph of the per-contig encoder embeddings",
+             (("resolution", float), ("threshold", float), ("max_levels", int)), "Modularity communities of the {what}s",
+             lambda eng, emb, r, ctx: _run_communities(eng, emb, r),
+             lambda npz, tsv, key, names, res, strand, ctx: write_communities(npz, tsv, key, names, res[0], ctx.request, strand),
+             lambda res, r, what, ctx: (f"{_SIMILARITY} >= {r[1]:g}, {res[1]} edges, resolution {r[0]:g}: {res[0].n_communities} communities, "
+                                        f"modularity {res[0].modularity:.4f}, {res[0].levels} levels, "
+                                        f"{'complete' if res[0].complete else 'not complete'}"),
+             errors=(ValueError, GnnError), advice="Raise GENOMAD_AMD_GRAPH or unset GENOMAD_AMD_COMMUNITIES.", after="graph"),
+)
+ALL_ANALYSES = ANALYSES + MORE_ANALYSES
+
 
 def _resumes(a, npz, tsv, request, strand, base) -> bool:
     """Analysis ``a``'s files of a stage are what a run with ``request`` would write: the npz spells the request (no file: none), the tsv
@@ -1541,8 +1603,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     attribution_bin = attribution_bin_requested()
     region_penalty = region_penalty_requested()
     region_embeddings = region_embeddings_requested()
-    requests = {a.name: a.request() for a in ANALYSES}
-    base_paths = {a.name: a.base.request() for a in ANALYSES if a.base is not None}
+    requests = {a.name: a.request() for a in ALL_ANALYSES}
+    base_paths = {a.name: a.base.request() for a in ALL_ANALYSES if a.base is not None}
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -1577,13 +1639,13 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         console.error("GENOMAD_AMD_REGION_EMBEDDINGS=1 needs GENOMAD_AMD_REGION_PENALTY: the embeddings are those of the regions called "
                       "along the score tracks. Set GENOMAD_AMD_REGION_PENALTY or unset GENOMAD_AMD_REGION_EMBEDDINGS.")
         sys.exit(1)
-    for a in ANALYSES:
+    for a in ALL_ANALYSES:
         requested = requests[a.name] is not None
         if a.base is None and requested and not embeddings:
             console.error(f"{a.switch} needs GENOMAD_AMD_EMBEDDINGS=1: {a.needs}. Set GENOMAD_AMD_EMBEDDINGS=1 or unset {a.switch}.")
             sys.exit(1)
         if requested and a.after is not None and requests[a.after] is None:
-            other = next(b.switch for b in ANALYSES if b.name == a.after)
+            other = next(b.switch for b in ALL_ANALYSES if b.name == a.after)
             console.error(f"{a.switch} needs {other}: {a.needs}. Set {other} or unset {a.switch}.")
             sys.exit(1)
         if a.base is not None and (requested != (base_paths[a.name] is not None) or (requested and not embeddings)):
@@ -1618,7 +1680,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         sys.exit(1)
 
     bases = {}                       # what every requested reference's loader returned, read before any classification starts
-    for a in ANALYSES:
+    for a in ALL_ANALYSES:
         if a.base is not None and requests[a.name] is not None:
             try:
                 bases[a.name] = a.base.load(base_paths[a.name], strand)
@@ -1799,7 +1861,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                  and _request_of_file(regions_path, (("stride", int), ("penalty", float))) == regions_request
                                  and (regions_request is None) == (not regions_tsv_path.exists())
                                  and _request_of_file(region_emb_file, (("stride", int), ("penalty", float), ("strand", str))) == region_emb_request
-                                 and all(_resumes(a, *outputs.files(what, a.name), requests[a.name], strand, bases.get(a.name)) for a in ANALYSES)
+                                 and all(_resumes(a, *outputs.files(what, a.name), requests[a.name], strand, bases.get(a.name)) for a in ALL_ANALYSES)
                                  and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
                                  and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
                                                             and _npz_strand(scan_path) == strand)))   # :284-292
@@ -1978,7 +2040,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     console.log(f"Encoder embeddings of the {len(mine[0])} regions of the {what}s written to {region_emb_path.name}.")
                 elif region_emb_file.exists():      # likewise
                     region_emb_file.unlink()
-                for a in ANALYSES:
+                for a in ALL_ANALYSES:
                     npz, tsv = outputs.files(what, a.name)
                     request = requests[a.name]
                     if request is None:             # likewise, both files

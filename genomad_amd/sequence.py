@@ -10,6 +10,7 @@ one (n_windows, 6000) uint8 array with numpy slicing.  Tokenising and everything
 on the GPU (libgenomad_nn_hip.so).
 """
 import bz2
+from fractions import Fraction
 import gzip
 import lzma
 import sys
@@ -2604,6 +2605,220 @@ def average_linkage_table(result, names=None):
     cols = [np.asarray(result[k]).tolist() for k in ("a", "b", "sim", "size_a", "size_b", "round")]
     return [{"rank": k + 1, "a": name(a), "b": name(b), "sim": float(s), "size": int(sa + sb), "round": int(r), "clusters_left": n_valid - k - 1}
             for k, (a, b, s, sa, sb, r) in enumerate(zip(*cols))]
+
+
+COMM_R_ONE = 64                    # a resolution of 1
+COMM_R_MAX = 256                   # resolution 4
+COMM_LEVELS_MAX = 32
+COMM_SWEEPS_MAX = 1 << 20
+COMM_M2_END = 1 << 58              # the graph's doubled weight stays below this: every quantity then fits 128 bits with its sign
+COMM_LEVEL_FIELDS = ("nodes", "communities", "sweeps", "accepted", "moved", "rejected", "split")
+
+
+def communities_resolution(resolution) -> int:
+    """64 * ``resolution`` as the integer r in [1, 256] the gains are built from; anything else is a ``ValueError``: the resolution
+    is a multiple of 1/64 in [1/64, 4]."""
+    try:
+        a = float(resolution) * COMM_R_ONE
+        ok = not isinstance(resolution, (bool, np.bool_)) and a == int(a) and 1 <= a <= COMM_R_MAX
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"resolution {resolution!r}: a multiple of 1/64 in [1/64, 4] is required")
+    return int(a)
+
+
+def communities_hash(i, s) -> int:
+    """h of node ``i`` in sweep ``s``: the middle part of a mover's priority (D, h, -i)"""
+    return ((i + 1) * 2654435761 + s * 40503) & 0xffffffff
+
+
+def communities_qnum(rows, comm, m2, r) -> int:
+    """Qnum = 64 * M2 * sum_c in_c - r * sum_c tot_c^2 of the assignment ``comm`` (node -> community) over the rows ``rows`` (node ->
+    {neighbour: weight}, self entries included): the modularity is Qnum / (64 * M2^2)"""
+    inner, tot = 0, {}
+    for i, row in rows.items():
+        tot[comm[i]] = tot.get(comm[i], 0) + sum(row.values())
+        inner += sum(w for j, w in row.items() if comm[j] == comm[i])
+    return 64 * m2 * inner - r * sum(t * t for t in tot.values())
+
+
+def _comm_sweep(rows, k, comm, m2, r, s):
+    """One synchronous sweep ``s`` over the assignment ``comm``: (want {node: (D, target)}, the new assignment, the movers)"""
+    tot = {}
+    for i, c in comm.items():
+        tot[c] = tot.get(c, 0) + k[i]
+    want = {}
+    for i, row in rows.items():
+        a, w = comm[i], {}
+        for j, x in row.items():
+            if j != i:
+                w[comm[j]] = w.get(comm[j], 0) + x
+        wa, top = w.get(a, 0), None
+        for c, wc in w.items():
+            if c == a:
+                continue
+            d = 64 * m2 * (wc - wa) - r * k[i] * (tot[c] + k[i] - tot[a])
+            if d > 0 and (top is None or d > top[0] or (d == top[0] and c < top[1])):
+                top = (d, c)
+        if top is not None:
+            want[i] = top
+    prio = {i: (d, communities_hash(i, s), -i) for i, (d, _) in want.items()}
+    new, moved = dict(comm), 0
+    for i, (_, c) in want.items():
+        if all(prio[j] < prio[i] for j in rows[i] if j != i and j in want and comm[j] in (comm[i], c)):
+            new[i] = c
+            moved += 1
+    return want, new, moved
+
+
+def _comm_roots(nodes, pairs):
+    """node -> the smallest node of its connected component under ``pairs``"""
+    root = {i: i for i in nodes}
+
+    def find(x):
+        while root[x] != x:
+            root[x] = root[root[x]]
+            x = root[x]
+        return x
+
+    for x, y in pairs:
+        x, y = find(x), find(y)
+        root[max(x, y)] = min(x, y)                       # towards the smaller: a root is its component's smallest node
+    return {i: find(i) for i in nodes}
+
+
+def modularity_communities(indptr, col, sim, valid=None, resolution=1.0, max_levels=COMM_LEVELS_MAX, max_sweeps=COMM_SWEEPS_MAX,
+                           trace=None):
+    """Modularity communities (Louvain's levels, a synchronous move rule) of a similarity graph, in integers throughout (the
+    definition ``gnn_communities`` computes on the device).  The graph is the upper-triangle CSR of
+    :func:`threshold_graph`, with ``valid`` (bool per row, None: all), read as :func:`markov_clusters` reads it.
+
+    Graph: q = rint(float32(sim) * 2^24); an entry with q <= 0 or an invalid end does not exist; the graph is symmetric, parallel
+    entries are added.  A level works on *nodes*: at level 0 the valid rows, under their row indices; later the components of the
+    level before, numbered from 0 in the order of their smallest member.  A node's row may hold a self entry A_ii (none at level 0;
+    later the node's inner weight, both directions counted).  k_i = sum_j A_ij, M2 = sum_i k_i (the same at every level, < 2^58),
+    r = 64 * ``resolution`` (:func:`communities_resolution`).
+    A level starts with comm[i] = i; a community is named by its founding node; tot_c = the sum of k over c's members.  Sweep s = 0,
+    1, ... is synchronous.  *Want*: for node i of community a and every community c != a that holds a neighbour j != i, with w_ic =
+    the sum of A_ij over j in c, j != i: D(i, c) = 64 * M2 * (w_ic - w_ia) - r * k_i * (tot_c + k_i - tot_a), which is 32 * M2^2 times
+    the modularity change of the move alone; i wants the c of the largest D > 0, ties to the smaller c.  *Pick*: a wanting node has
+    the priority (D, h, -i), h = :func:`communities_hash`; i moves iff every neighbour j != i that wants to move and sits in comm[i]
+    or in i's target has a strictly smaller priority.  *Score*: Qnum (:func:`communities_qnum`) of the new assignment; strictly
+    larger than before: the sweep is accepted; otherwise it is discarded and ends the level (``rejected``).  A sweep that moves
+    nobody - nobody wanted: the largest priority always moves - ends the level too, and so do ``max_sweeps`` sweeps.
+    End of a level with an accepted sweep: every community is split into the connected components of its induced subgraph, the
+    components are numbered by their smallest member and the graph is contracted - a node per component, entries summed, the inner
+    weight as the self entry.  A level without an accepted sweep is the last; ``max_levels`` caps them.  M2 = 0: no level.
+
+    ``trace``: a list that receives, per sweep that moved somebody, a dict ``level``, ``sweep``, ``comm`` (before), ``want`` (node
+    -> (D, target)), ``new``, ``qnum`` (of ``new``), ``accepted`` and ``node_of`` (row -> its node at this level).
+
+    Returns a dict: per row ``label`` (int64: the smallest row of its final community; -1 for an invalid row) and ``size``;
+    ``level_label`` (int64 (levels, n)): the labelling behind each level; per level (int64) ``nodes``, ``communities``, ``sweeps``
+    (the level's last one included, whatever ended it), ``accepted``, ``moved`` (in accepted sweeps), ``rejected`` (0 or 1), ``split``
+    (components minus communities) and ``qnum`` (a list of Python ints: Qnum of the level's labelling); ``levels``, ``complete`` (the
+    last level had no accepted sweep and ``max_sweeps`` ended none), ``m2``, ``resolution`` (r / 64), ``modularity`` (float64 of the
+    last qnum / (64 * m2^2); 0.0 without a level) and ``valid``."""
+    r = communities_resolution(resolution)
+    max_levels = _whole(max_levels, "max_levels", 1, COMM_LEVELS_MAX)
+    max_sweeps = _whole(max_sweeps, "max_sweeps", 1, COMM_SWEEPS_MAX)
+    n, ea, eb, eq, ok = mcl_weights(indptr, col, sim, valid)
+    rows = {int(i): {} for i in np.flatnonzero(ok)}
+    for x, y, w in zip(ea.tolist(), eb.tolist(), eq.tolist()):
+        rows[x][y] = rows[x].get(y, 0) + w
+        rows[y][x] = rows[y].get(x, 0) + w
+    m2 = sum(sum(row.values()) for row in rows.values())
+    if m2 >= COMM_M2_END:
+        raise ValueError(f"the graph's doubled weight {m2} is not below 2^58")
+    node_of = {i: i for i in rows}                            # row -> its node
+    first_row = {i: i for i in rows}                          # node -> its smallest row
+    stats = {f: [] for f in COMM_LEVEL_FIELDS}
+    qnums, level_label = [], []
+    complete, capped = m2 == 0, False
+    while m2 > 0 and len(qnums) < max_levels and not complete:
+        k = {i: sum(row.values()) for i, row in rows.items()}
+        comm = {i: i for i in rows}
+        qn = communities_qnum(rows, comm, m2, r)
+        sweeps = accepted = moved = rejected = 0
+        while sweeps < max_sweeps:
+            want, new, mv = _comm_sweep(rows, k, comm, m2, r, sweeps)
+            sweeps += 1
+            if mv == 0:
+                break
+            qnew = communities_qnum(rows, new, m2, r)
+            if trace is not None:
+                trace.append({"level": len(qnums), "sweep": sweeps - 1, "comm": dict(comm), "want": want, "new": dict(new), "qnum": qnew,
+                              "accepted": qnew > qn, "node_of": dict(node_of)})
+            if qnew <= qn:
+                rejected = 1
+                break
+            comm, qn, accepted, moved = new, qnew, accepted + 1, moved + mv
+        else:
+            capped = True                                     # max_sweeps sweeps, the last one accepted
+        comp = comm
+        if accepted:
+            comp = _comm_roots(rows, ((i, j) for i, row in rows.items() for j in row if comm[i] == comm[j]))
+            number = {c: v for v, c in enumerate(sorted(set(comp.values())))}
+            contracted = {v: {} for v in number.values()}
+            for i, row in rows.items():
+                new_row = contracted[number[comp[i]]]
+                for j, w in row.items():
+                    new_row[number[comp[j]]] = new_row.get(number[comp[j]], 0) + w
+            first_row = {number[c]: first_row[c] for c in number}      # a component's smallest node holds its smallest row
+            node_of = {row: number[comp[i]] for row, i in node_of.items()}
+            n_comp = len(number)
+        else:
+            contracted, n_comp = rows, len(rows)
+            complete = not capped
+        for f, v in zip(COMM_LEVEL_FIELDS, (len(rows), len(set(comm.values())), sweeps, accepted, moved, rejected,
+                                            n_comp - len(set(comm.values())))):
+            stats[f].append(v)
+        rows = contracted
+        qnums.append(communities_qnum(rows, {i: i for i in rows}, m2, r) if accepted else qn)
+        lab = np.full(n, -1, dtype=np.int64)
+        for row, i in node_of.items():
+            lab[row] = first_row[i]
+        level_label.append(lab)
+        if not accepted:
+            break
+    label = level_label[-1] if level_label else np.where(ok, np.arange(n, dtype=np.int64), -1)
+    size = np.where(ok, np.bincount(label[ok], minlength=n)[np.maximum(label, 0)], 0).astype(np.int64)
+    out = {"label": label.copy(), "size": size, "level_label": np.asarray(level_label, dtype=np.int64).reshape(len(level_label), n),
+           "qnum": qnums, "levels": len(qnums), "complete": bool(complete), "m2": m2, "resolution": r / COMM_R_ONE,
+           "modularity": float(Fraction(qnums[-1], 64 * m2 * m2)) if qnums else 0.0, "valid": ok}
+    out.update({f: np.asarray(v, dtype=np.int64) for f, v in stats.items()})
+    return out
+
+
+def label_components(indptr, col, sim, label, valid=None) -> np.ndarray:
+    """The connected components of every label's induced subgraph over the existing entries of a similarity graph (read as
+    :func:`modularity_communities` reads it; the definition ``gnn_label_components`` computes on the device): int64 per row - the
+    smallest row of its component among the rows of its own ``label`` (int64 per row, -1: none); -1 for label -1 and for an invalid
+    row."""
+    n, ea, eb, _, ok = mcl_weights(indptr, col, sim, valid)
+    label = np.asarray(label)
+    if label.shape != (n,) or label.dtype.kind not in "iu" or (label < -1).any():
+        raise ValueError(f"label must be an integer array of {n} with values >= -1")
+    label = label.astype(np.int64)
+    same = (label[ea] == label[eb]) & (label[ea] >= 0)
+    root = _comm_roots(range(n), zip(ea[same].tolist(), eb[same].tolist()))
+    out = np.array([root[i] for i in range(n)], dtype=np.int64).reshape(n)
+    out[~ok | (label < 0)] = -1
+    return out
+
+
+def communities_table(result, names=None):
+    """One record per community of a result of :func:`modularity_communities` (or anything with its ``label`` and ``size``), ordered
+    by label: ``label``, ``size`` and ``members``, as indices in ascending order or - where ``names`` is given - as names"""
+    label = np.asarray(result["label"], dtype=np.int64)
+    size = np.asarray(result["size"])
+    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    order = np.argsort(label, kind="stable")
+    order = order[label[order] >= 0]
+    bounds = np.flatnonzero(np.diff(label[order], prepend=-1)) if len(order) else []
+    return [{"label": name(label[order[a]]), "size": int(size[order[a]]), "members": [name(i) for i in order[a:b]]}
+            for a, b in zip(bounds, list(bounds[1:]) + [len(order)])]
 
 
 def prefix_of(input_path: Path) -> str:

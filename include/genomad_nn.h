@@ -969,6 +969,86 @@ int gnn_debug_avglink_order(gnn_ctx* ctx, const uint64_t* quads_host, int64_t n,
 int gnn_debug_avglink_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
 int gnn_debug_avglink_classes(gnn_ctx* ctx, int64_t* rows_out);
 
+/* ---- modularity communities of a similarity graph: Louvain's levels on the device ---------------------------
+ * "Which groups does the graph fall into by itself, and how good is that partition": modularity optimisation over the graph
+ * gnn_graph_* writes - one knob with a natural default (resolution 1), a partition that scores itself, a coarse-to-fine hierarchy -
+ * in integers throughout, so that every output equals the definition (sequence.modularity_communities) bit for bit, for any number
+ * of workgroups, any table size, any row class and any order they run in.  No forward pass runs and no other entry point's result
+ * changes.
+ *   graph     gnn_mcl's: an upper-triangle CSR with sim (f32, finite, < 64) and valid (uint8 [n], or NULL); exactly what
+ *             gnn_graph_fill_dev wrote is such a graph.  Anything else: GNN_ERR_ARG behind one O(nnz) kernel, before anything else
+ *             runs, the outputs untouched.
+ *   weights   W = 2^24.  q = rint(sim * W); an entry with q <= 0 or an invalid end does not exist; parallel entries are added.
+ *             k_i = the sum of node i's row (its self entry included), M2 = the sum of all k: the same at every level, < 2^58 or
+ *             GNN_ERR_ARG (outputs untouched).  r = 64 * resolution, an integer in [1, 256].
+ *   level     nodes: at level 0 the valid rows under their row indices, later the components of the level before, numbered by their
+ *             smallest member.  comm[i] = i at its start; a community is named by its founding node; tot_c = the sum of k over c.
+ *   sweep s   synchronous.  Want: node i of community a takes, over the communities c != a of its neighbours j != i, D(i, c) = 64 M2
+ *             (w_ic - w_ia) - r k_i (tot_c + k_i - tot_a) (w_ic: the sum of A_ij over j in c, j != i), a signed 128-bit integer, and
+ *             wants the c of the largest D > 0, ties to the smaller c.  Pick: its priority is (D, h, -i), h = ((i + 1) * 2654435761 +
+ *             s * 40503) mod 2^32; i moves iff every neighbour j != i that wants to move and sits in comm[i] or in i's target has a
+ *             strictly smaller priority.  Score: Qnum = 64 M2 (the weight inside communities, both directions, self entries
+ *             included) - r (the sum of tot_c^2); strictly larger than the assignment's: accepted; otherwise discarded, and the
+ *             level ends (rejected).  A sweep that moves nobody ends the level, and so do max_sweeps sweeps.
+ *   level end behind an accepted sweep: every community is split into the connected components of its induced subgraph, the components
+ *             are numbered by their smallest member, the graph is contracted (entries summed, the inner weight as the self entry).
+ *             A level without an accepted sweep is the last; max_levels caps them.  M2 == 0: no level, every valid row alone.
+ *   outputs   label (int64 [n]: the smallest row of the row's final community; -1 for an invalid row), size (int64 [n]), level_label
+ *             (int64 [max_levels][n], rows [0, *levels_host) written: the labelling behind each level, each nested in the next);
+ *             level_stats_host (int64 [max_levels][7]: nodes, communities, sweeps, accepted, moved, rejected, split = components -
+ *             communities), level_qnum_host (uint64 [max_levels][2]: Qnum of the level's labelling, low and high word, two's
+ *             complement), *levels_host, *complete_host (the last level had no accepted sweep and max_sweeps ended none), *m2_host.
+ *             The modularity of level l is Qnum / (64 * M2^2).
+ *   ranges    0 <= n <= 2^24, 0 <= nnz < 2^30, r in [1, 256], max_levels in [1, 32], max_sweeps in [1, 2^20]; GNN_ERR_ARG with the
+ *             value and the range in the message - checked before the ctx is looked at.  n == 0: nothing is launched; no level.
+ *   exact     every weight, k, tot and inner sum is a 64-bit integer add - into a table in LDS keyed by the neighbour's community,
+ *             or, for a row longer than the table, into an accumulator in global memory; D, the squares and Qnum are 128-bit
+ *             integers (|D| < 2^126, |Qnum| < 2^125 under the ranges above).  No float is added or compared, nothing depends on an
+ *             order.
+ * What it is not: not Leiden's refinement (connectedness is guaranteed by the split, well-connectedness is not); not the sequential
+ * Louvain sweep (moves are synchronous and a sweep that does not raise the modularity ends its level); not float; not overlapping;
+ * not multi-GPU; resolution <= 4; n <= 2^24.
+ * Device memory, persistent in the ctx and grow-only: 28 B per symmetric entry (two per edge), about 190 B per row, at most 192 MB of
+ * accumulators (gnn_communities: + the graph and 8 B * (2 + max_levels) per row of results).  A failed allocation: GNN_ERR_NOMEM,
+ * outputs untouched.
+ * gnn_communities: host pointers, synchronous.  gnn_communities_dev: device pointers in and out (label, size, level_label), the rest
+ * on the host; the ctx stream is synchronised once for the verdict on the graph, once per level's start and end, and once per sweep
+ * (56 bytes: the movers, the sums, the verdict, Qnum). */
+int gnn_communities(gnn_ctx* ctx, const int64_t* indptr_host, const int32_t* col_host, const float* sim_host, const uint8_t* valid_host_or_null,
+                    int64_t n, int64_t nnz, int r, int max_levels, int max_sweeps, int64_t* label_host, int64_t* size_host,
+                    int64_t* level_label_host, int64_t* level_stats_host, uint64_t* level_qnum_host, int64_t* levels_host, int* complete_host,
+                    uint64_t* m2_host);
+int gnn_communities_dev(gnn_ctx* ctx, const int64_t* indptr_dev, const int32_t* col_dev, const float* sim_dev, const uint8_t* valid_dev_or_null,
+                        int64_t n, int64_t nnz, int r, int max_levels, int max_sweeps, int64_t* label_dev, int64_t* size_dev,
+                        int64_t* level_label_dev, int64_t* level_stats_host, uint64_t* level_qnum_host, int64_t* levels_host,
+                        int* complete_host, uint64_t* m2_host);
+/* The connected components of every label's induced subgraph over the graph's existing entries (sequence.label_components): label
+ * (int64 [n], negative: none) -> out (int64 [n]): the smallest row of the row's component among the rows of its own label; -1 for a
+ * row without a label and for an invalid row.  The graph, its verdict and the ranges of n and nnz are gnn_communities'; one
+ * synchronise for the verdict.  Device memory: 5 B per row. */
+int gnn_label_components(gnn_ctx* ctx, const int64_t* indptr_host, const int32_t* col_host, const float* sim_host,
+                         const uint8_t* valid_host_or_null, int64_t n, int64_t nnz, const int64_t* label_host, int64_t* out_host);
+int gnn_label_components_dev(gnn_ctx* ctx, const int64_t* indptr_dev, const int32_t* col_dev, const float* sim_dev,
+                             const uint8_t* valid_dev_or_null, int64_t n, int64_t nnz, const int64_t* label_dev, int64_t* out_dev);
+/* test aids; no result depends on them.  gnn_debug_communities_slots: the slots of the LDS table, 0 .. 4096 (0: every row takes the
+ * accumulator in global memory; -1: leave it as it is); returns the value before the call (>= 0), or GNN_ERR_ARG.
+ * gnn_debug_communities_wave_rows: the longest row that a single wave takes, 0 .. 4096 (0: none; -1: leave it); returns the value
+ * before the call.  gnn_debug_communities_groups: the workgroups of a launch, 1 .. 65535 (0: the library's choice, eight per CU).
+ * gnn_debug_communities_gain: the gain and the score, run on the device over n rows of 12 uint64 on the host - 64 * M2, r, k, w_ic,
+ * w_ia, tot_c, tot_a, in, the squares' low and high word, the previous Qnum's low and high word -: out_host[i] (5 uint64) = D low,
+ * D high, Qnum low, Qnum high (two's complement), Qnum > previous. */
+int gnn_debug_communities_slots(gnn_ctx* ctx, int slots);
+int gnn_debug_communities_wave_rows(gnn_ctx* ctx, int entries);
+int gnn_debug_communities_groups(gnn_ctx* ctx, int groups);
+int gnn_debug_communities_gain(gnn_ctx* ctx, const uint64_t* operands_host, int64_t n, uint64_t* out_host);
+/* measurement only.  gnn_debug_communities_ms: with gnn_profile_enable on, the HIP-event milliseconds of the ctx's last
+ * gnn_communities* call: [0] validate, symmetrise and level 0's start, then per level one figure per sweep and - behind a level with
+ * an accepted sweep - one for its end (split, contraction, the next level's start); *n_out = the figures recorded, at most `capacity`
+ * are written.  gnn_debug_communities_classes: the rows that call took by class, all launches together: [one wave, one workgroup, the
+ * accumulator in global memory] of the want launches, then of the contractions (6 values). */
+int gnn_debug_communities_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
+int gnn_debug_communities_classes(gnn_ctx* ctx, int64_t* rows_out);
+
 /* ---- matches against a reference: the bipartite similarity graph query x base ------------------------------
  * "Which reference rows is every new row within the threshold of, all of them": every pair (i, j) of a valid query row i and a valid
  * base row j with sim(i, j) >= threshold and its similarity, as a CSR by query row.  The passes, the kernel, the workspace and the
