@@ -41,6 +41,8 @@ STRANDS = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_
 K_FUSED, K_BACKEND, K_ENCODER, K_F32_FRONT, K_ATTR_HEAD, K_ATTR_CONTRIB, K_REGIONS, K_NEIGHBOURS = 0, 1, 2, 3, 4, 5, 6, 7
 KNN_COSINE, KNN_DOT = 0, 1                                  # gnn_knn_metric
 KNN_METRICS = {"cosine": KNN_COSINE, "dot": KNN_DOT}
+KNN_GRAPH_MODES = {"union": 0, "mutual": 1}                    # gnn_knn_graph_mode
+KNN_GRAPH_WEIGHTS = {"similarity": 0, "jaccard": 1}            # gnn_knn_graph_weight
 KNN_K_MAX = 64
 
 _f32p = C.POINTER(C.c_float)
@@ -180,6 +182,14 @@ SIGNATURES = {
     "gnn_debug_communities_gain": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_debug_communities_ms": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_debug_communities_classes": (_int, [_vp, _vp]),
+    "gnn_knn_graph_count": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp]),
+    "gnn_knn_graph_fill": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _i64]),
+    "gnn_knn_graph_count_dev": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp]),
+    "gnn_knn_graph_fill_dev": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _i64]),
+    "gnn_debug_knn_graph_wave_rows": (_int, [_vp, _int]),
+    "gnn_debug_knn_graph_group_rows": (_int, [_vp, _int]),
+    "gnn_debug_knn_graph_classes": (_int, [_vp, _vp]),
+    "gnn_debug_knn_graph_ms": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_kmeans": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_kmeans_dev": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_centroids": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp]),

@@ -455,6 +455,36 @@ struct CommunitiesWorkspace {
     int64_t class_rows[6] = {0, 0, 0, 0, 0, 0};  // the last call's rows by class: the want launches', the contractions' (gnn_debug_communities_classes)
 };
 
+// ---- k-nearest-neighbour graph (gnn_knn_graph.hip): persistent, grow-only.  Per row 20 k B of lists (the search's int64 / f32 and the
+// ordered int32 / f32) and 36 B of length, counter, offset, cursor and class lists; per edge 16 B (the packed entries and the radix
+// class's second buffer) and, for gnn_knn_graph_count / gnn_knn_graph_fill alone, 8 B per row and 9 B per edge of results.  Nothing is
+// n x n.  The search's own buffers are NeighbourWorkspace's.
+struct KnnGraphWorkspace {
+    int wave_rows = 64;                          // the longest row one wave orders (gnn_debug_knn_graph_wave_rows): 1 .. 64; no result depends on it
+    int group_rows = 2048;                       // the longest row a workgroup orders in LDS (gnn_debug_knn_graph_group_rows): 1 .. 4096; no result depends on it
+    DevBuf<int64_t> nidx;                        // [n][k]: the self-search's lists, as gnn_neighbours_dev writes them
+    DevBuf<float> nsim;
+    DevBuf<int32_t> lidx;                        // [n][k]: a row's neighbours ascending, the first len[i] of them
+    DevBuf<float> lsim;                          // and their similarities
+    DevBuf<int32_t> len;                         // [n]
+    DevBuf<int32_t> cnt;                         // [n]: the edges row i owns
+    DevBuf<int64_t> off;                         // [n + 1]: their exclusive prefix sums, then the total
+    DevBuf<unsigned long long> cursor;           // [n]: where the row's next edge goes
+    DevBuf<int32_t> rows;                        // [2][n]: the rows a workgroup orders in LDS, then those it orders by radix
+    DevBuf<unsigned long long> pairs[2];         // [total]: an edge as partner << 32 | similarity bits; [1]: the radix class's other buffer
+    HostCounters count;                          // [0], [1]: the rows of the two workgroup classes
+    // what the last count call ran with: the fill answers GNN_ERR_STATE for another (n, k, mode, weight, metric)
+    bool counted = false;
+    bool host_rows = false;                      // it was a gnn_knn_graph_count
+    int64_t n = 0;
+    int k = 0, mode = 0, weight = 0, metric = 0;
+    int64_t total = 0;                           // edges
+    int64_t class_rows[2] = {0, 0};              // the rows of the LDS class and of the radix class
+    int wave_limit = 0, group_limit = 0;         // the class limits the count ran with: the fill's
+    DevBuf<int64_t> d_out;                       // a Landing: gnn_knn_graph_count's indptr [n + 1]; gnn_knn_graph_fill's [col (i32) | sim (f32) | mutual (u8)]
+    PassLog passes;                              // profiling on: the last count's [search, lists, count, scan + classes], behind them every fill's [fill, order, finish]
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -660,9 +690,10 @@ struct gnn_ctx {
     gnn::SpreadWorkspace sprd;                    // gnn_spread.hip
     gnn::AvglinkWorkspace avl;                    // gnn_avglink.hip
     gnn::CommunitiesWorkspace cmt;                // gnn_communities.hip
+    gnn::KnnGraphWorkspace kg;                    // gnn_knn_graph.hip
     // every PassLog above: drain_profile settles them before an event they hold returns to event_pool
-    gnn::PassLog* const pass_logs[11] = {&rp.rounds, &lk.rounds, &lk.tree_rounds, &gr.passes,  &km.passes, &pca.passes,
-                                         &vt.passes, &mcl.passes, &sprd.passes, &avl.passes, &cmt.passes};
+    gnn::PassLog* const pass_logs[12] = {&rp.rounds, &lk.rounds, &lk.tree_rounds, &gr.passes,  &km.passes, &pca.passes,
+                                         &vt.passes, &mcl.passes, &sprd.passes, &avl.passes, &cmt.passes, &kg.passes};
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;

@@ -440,6 +440,26 @@ class GraphResult(_Result):
         return GraphResult.build(arrays, np.concatenate([self.valid, new.valid]), self.threshold, self.metric)
 
 
+class KNNGraphResult(GraphResult):
+    """What :meth:`NNEngine.knn_graph` returns (the definition is ``sequence.knn_graph``): a :class:`GraphResult` - the same CSR over
+    the upper triangle, so everything said there holds, the four consumers included - whose edges join rows that list each other
+    among their ``k`` nearest neighbours: ``mode`` ("union": either lists the other; "mutual": both), ``weight`` ("similarity": ``sim``
+    is the similarity the lists carry; "jaccard": the overlap of the two neighbourhoods) and ``mutual`` (uint8 per edge: both ends
+    list each other).  ``threshold`` is NaN: there is none."""
+    FIELDS = GraphResult.FIELDS + ("k", "mode", "weight", "mutual")
+
+    def table(self, names=None):
+        """``sequence.knn_graph_table``: one record per edge - a, b, weight, mutual"""
+        return _sequence.knn_graph_table(self.indptr, self.col, self.sim, self.mutual, names)
+
+    @classmethod
+    def build(cls, arrays, valid, k, mode, weight, metric):
+        """from the (indptr, col, sim, mutual) of ``sequence.knn_graph`` or the library, and the rows' validity"""
+        indptr, col, sim, mutual = arrays
+        return cls(indptr=indptr, col=col, sim=sim, valid=np.asarray(valid, dtype=bool), n=len(indptr) - 1, n_edges=len(col),
+                   threshold=float("nan"), metric=str(metric), k=int(k), mode=str(mode), weight=str(weight), mutual=mutual)
+
+
 class MatchResult(_Result):
     """What :meth:`NNEngine.match` returns (the definition is ``sequence.threshold_matches``): the bipartite similarity graph query x
     base in CSR form by query row - ``indptr`` (int64 (n_query + 1,)), ``col`` (int32: query i owns ``col[indptr[i]:indptr[i + 1]]``,
@@ -1269,6 +1289,83 @@ class NNEngine:
         """measurement only (``gnn_debug_graph_pass_ms``): with profiling enabled, the HIP-event milliseconds of the last count call's
         [count pass, scan]"""
         return self._debug_ms(self.lib.gnn_debug_graph_pass_ms)
+
+    # -- k-nearest-neighbour graph --------------------------------------------------------
+    @staticmethod
+    def _knn_graph_codes(k, mode, weight):
+        """(k, mode code, weight code): an unknown name is a ``ValueError`` before anything is allocated or launched; a k outside
+        [1, 64] is one too, with the value and the range"""
+        return (_sequence.neighbour_k(k), _lib.KNN_GRAPH_MODES[_sequence.knn_graph_mode(mode)],
+                _lib.KNN_GRAPH_WEIGHTS[_sequence.knn_graph_weight(weight)])
+
+    def knn_graph(self, rows, k=15, mode="union", weight="similarity", metric="cosine") -> KNNGraphResult:
+        """The k-nearest-neighbour graph among encoder embeddings (``gnn_knn_graph_count`` + ``gnn_knn_graph_fill``; the definition is
+        ``sequence.knn_graph``): the lists of :meth:`neighbours`' self-search at ``k`` (1..64), joined on the device into the CSR
+        :meth:`graph` returns - a pair i < j of valid rows is an edge when either lists the other (``mode`` "union") or both do
+        ("mutual").  At most n k edges whatever the data, and a density that adapts per row: what a single threshold cannot give.
+        ``weight`` "similarity": where j is among i's neighbours, the float32 :meth:`graph` gives the pair, bit for bit; otherwise
+        the float32 row j's list holds for i - the other orientation, which may differ from the graph's value in the last bit.
+        Negative similarities are kept; the consumers drop weights <= 0.  "jaccard": the overlap of the two neighbourhoods, each
+        with its own row, |A & B| / |A | B| in (0, 1] - shared nearest neighbours.  The result's :meth:`~GraphResult.mcl`,
+        :meth:`~GraphResult.spread`, :meth:`~GraphResult.average_linkage` and :meth:`~GraphResult.communities` run the consumers
+        on it.  :meth:`set_neighbour_split` sets the range of this search too; no result depends on it."""
+        r = _sequence.neighbour_rows(rows, "rows")
+        self._check_metric(metric)
+        k, m, w = self._knn_graph_codes(k, mode, weight)
+        code = self._knn_metric(metric)
+        n = len(r)
+        flags = []
+
+        def fill(col, sim, total):
+            flags.append(np.empty(total, dtype=np.uint8))
+            return self.lib.gnn_knn_graph_fill(self.ctx, n, k, m, w, code, col, sim, flags[0].ctypes.data, total)
+
+        csr = self._count_then_fill(
+            lambda indptr, total: self.lib.gnn_knn_graph_count(self.ctx, r.ctypes.data, n, k, m, w, code, indptr, total),
+            fill, n + 1, n * k, lambda total: f"the graph has {total} edges")          # the cap cannot be met: at most n k edges
+        name = self._metric_name(metric)
+        return KNNGraphResult.build(csr + (flags[0],), _sequence.valid_rows(r, name), k, mode, weight, name)
+
+    def knn_graph_count_dev(self, rows_ptr: int, n: int, indptr_ptr: int, k=15, mode="union", weight="similarity", metric="cosine") -> int:
+        """``gnn_knn_graph_count_dev``: device pointers in (rows n x 512 f32) and out (indptr n + 1 int64); the engine's stream is
+        synchronised.  Returns the number of edges: what ``col``, ``sim`` and ``mutual`` of :meth:`knn_graph_fill_dev` must hold."""
+        k, m, w = self._knn_graph_codes(k, mode, weight)
+        total = C.c_int64(0)
+        check(self.lib.gnn_knn_graph_count_dev(self.ctx, rows_ptr, int(n), k, m, w, self._knn_metric(metric), indptr_ptr, C.addressof(total)))
+        return int(total.value)
+
+    def knn_graph_fill_dev(self, n: int, col_ptr, sim_ptr, mutual_ptr, capacity: int, k=15, mode="union", weight="similarity",
+                           metric="cosine"):
+        """Asynchronous (``gnn_knn_graph_fill_dev``): the edges of the engine's last :meth:`knn_graph_count_dev`, which must have had
+        the same n, k, mode, weight and metric - col (int32), sim (f32) and mutual (uint8, or None) of ``capacity`` elements each on
+        the device, enqueued on the engine's stream.  It reads the lists the count left in the engine, not the rows."""
+        k, m, w = self._knn_graph_codes(k, mode, weight)
+        check(self.lib.gnn_knn_graph_fill_dev(self.ctx, int(n), k, m, w, self._knn_metric(metric), col_ptr, sim_ptr, mutual_ptr, int(capacity)))
+
+    def _knn_graph_knob(self, fn, value) -> int:
+        check(fn(self.ctx, int(value)))
+        return int(value)
+
+    def set_knn_graph_wave_rows(self, entries: int) -> int:
+        """test aid (``gnn_debug_knn_graph_wave_rows``): the longest row one wave orders, 1..64 (the default 64); no result depends on
+        it."""
+        return self._knn_graph_knob(self.lib.gnn_debug_knn_graph_wave_rows, entries)
+
+    def set_knn_graph_group_rows(self, entries: int) -> int:
+        """test aid (``gnn_debug_knn_graph_group_rows``): the longest row a workgroup orders in LDS, 1..4096 (the default 2048); no
+        result depends on it."""
+        return self._knn_graph_knob(self.lib.gnn_debug_knn_graph_group_rows, entries)
+
+    def knn_graph_classes(self) -> np.ndarray:
+        """measurement only (``gnn_debug_knn_graph_classes``): the rows the last count gave the [LDS, radix] class"""
+        out = np.zeros(2, dtype=np.int64)
+        check(self.lib.gnn_debug_knn_graph_classes(self.ctx, out.ctypes.data))
+        return out
+
+    def knn_graph_pass_ms(self):
+        """measurement only (``gnn_debug_knn_graph_ms``): with profiling enabled, the HIP-event milliseconds of the last count call's
+        [search, lists, count, scan] and, behind them, of every fill's [fill, order, finish] since"""
+        return self._debug_ms(self.lib.gnn_debug_knn_graph_ms)
 
     # -- matches against a reference -----------------------------------------------------
     def match(self, query, base, threshold, metric="cosine", max_edges=1 << 28) -> MatchResult:

@@ -91,7 +91,7 @@ class Outputs:
         # written only when the analysis is requested (the analyses of the per-contig embeddings, ANALYSES below: <stem>.npz and,
         # for all but the neighbours, <stem>.tsv; no counterpart in the reference)
         for stage in self._STAGE.values():
-            for a in ALL_ANALYSES:
+            for a in EVERY_ANALYSIS:
                 setattr(self, f"{stage}nn_{a.name}_output", d / f"{p}_{stage}nn_{a.name}.npz")
                 if a.tsv:
                     setattr(self, f"{stage}nn_{a.name}_tsv_output", d / f"{p}_{stage}nn_{a.name}.tsv")
@@ -858,6 +858,49 @@ def write_graph(npz_path, tsv_path, names_key, names, res, strand="forward"):
     write_graph_tsv(tsv_path, names, res)
 
 
+def _env_name(name, choices, default, meaning):
+    """The switch ``name`` as one of the names ``choices``; unset or empty: ``default``.  Any other value is a ``ValueError`` that ends
+    with ``meaning``."""
+    v = os.environ.get(name, "").strip()
+    if not v:
+        return default
+    if v not in choices:
+        raise ValueError(f"{name}={v!r}: expected one of {', '.join(choices)} {meaning}")
+    return v
+
+
+def knn_graph_requested():
+    """GENOMAD_AMD_KNN_GRAPH=<int in [1, 64]>: main() also writes the k-nearest-neighbour graph of the contigs - every pair of which one
+    lists the other among its that many nearest neighbours by the per-contig encoder embeddings of GENOMAD_AMD_EMBEDDINGS=1
+    (<prefix>_nn_knn_graph.npz and .tsv); unset or empty: nothing changes (None).  GENOMAD_AMD_KNN_GRAPH_MODE=union|mutual (default
+    union: either lists the other; mutual: both do) and GENOMAD_AMD_KNN_GRAPH_WEIGHT=similarity|jaccard (default similarity; jaccard:
+    the overlap of the two neighbourhoods) refine it; each is an error without GENOMAD_AMD_KNN_GRAPH.  Any other value of the three is
+    an error.  Returns (k, mode, weight), or None."""
+    k = _env_int("GENOMAD_AMD_KNN_GRAPH", 1, sequence.NEIGHBOUR_K_MAX, "(neighbours per contig)")
+    if k is None:
+        for companion in ("GENOMAD_AMD_KNN_GRAPH_MODE", "GENOMAD_AMD_KNN_GRAPH_WEIGHT"):
+            _env_refines(companion, "GENOMAD_AMD_KNN_GRAPH", "set the neighbours per contig or unset")
+        return None
+    return (k, _env_name("GENOMAD_AMD_KNN_GRAPH_MODE", sequence.KNN_GRAPH_MODES, "union", "(which pairs are edges)"),
+            _env_name("GENOMAD_AMD_KNN_GRAPH_WEIGHT", sequence.KNN_GRAPH_WEIGHTS, "similarity", "(what an edge weighs)"))
+
+
+KNN_GRAPH_TSV_HEADER = "contig_a\tcontig_b\tweight\n"
+
+
+def write_knn_graph(npz_path, tsv_path, names_key, names, res, strand="forward"):
+    """Both files of a stage's k-nearest-neighbour graph: the arrays of a KNNGraphResult with the contig names, and its edge list - one
+    line per edge in the CSR's order, the names of the two contigs and the weight, the label-label-weight ("abc") format graph tools
+    read, behind one header line."""
+    np.savez_compressed(npz_path, **{names_key: names, "k": np.int64(res.k), "mode": np.array(res.mode), "weight": np.array(res.weight),
+                                     "metric": np.array(res.metric), "indptr": res.indptr, "col": res.col, "sim": res.sim,
+                                     "mutual": res.mutual, "valid": res.valid, **_strand_entry(strand)})
+    with open(tsv_path, "w") as fout:
+        fout.write(KNN_GRAPH_TSV_HEADER)
+        for e in res.table(names):
+            fout.write(f"{e['a']}\t{e['b']}\t{e['weight']:.6f}\n")
+
+
 MCL_SELECT_DEFAULT = 256
 
 
@@ -1417,7 +1460,7 @@ def _encode(fasta_path, enc_dir: Path, window_id_path: Path, single_window: bool
 
 
 # ---- the analyses of the gathered per-contig embeddings ------------------------------------------------------------------------------
-# Fifteen analyses (ALL_ANALYSES) follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
+# Sixteen analyses (EVERY_ANALYSIS) follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
 #   name      the stem of its files, <prefix>_nn_<name>.npz and - where ``tsv`` - .tsv
 #   switch    the environment variable that requests it; ``request()`` reads it (and its companions): the request, or None
 #   needs     the middle clause of the message that refuses the switch without GENOMAD_AMD_EMBEDDINGS=1
@@ -1559,7 +1602,7 @@ ANALYSES = (        # in the order they run, which is the order of the log lines
 )
 
 # The fifteenth analysis.  It stands in a table of its own behind ANALYSES, so that table stays what the earlier analyses' tests
-# count; main() walks ALL_ANALYSES, and everything said of a record above holds for these.
+# count; main() walks EVERY_ANALYSIS (below), and everything said of a record above holds for these.
 MORE_ANALYSES = (
     Analysis("communities", "GENOMAD_AMD_COMMUNITIES", communities_requested,
              "modularity is optimised over the similarity graph of the per-contig encoder embeddings",
@@ -1572,6 +1615,19 @@ MORE_ANALYSES = (
              errors=(ValueError, GnnError), advice="Raise GENOMAD_AMD_GRAPH or unset GENOMAD_AMD_COMMUNITIES.", after="graph"),
 )
 ALL_ANALYSES = ANALYSES + MORE_ANALYSES
+
+# The sixteenth analysis, in a third table for the same reason: ALL_ANALYSES stays what the communities' tests count.  main() and the
+# file table of Outputs walk EVERY_ANALYSIS, and everything said of a record above holds for this one.
+KNN_ANALYSES = (
+    Analysis("knn_graph", "GENOMAD_AMD_KNN_GRAPH", knn_graph_requested,
+             "the neighbour lists are those of the per-contig encoder embeddings", (("k", int), ("mode", str), ("weight", str)),
+             "k-nearest-neighbour graph of the {what}s",
+             lambda eng, emb, r, ctx: eng.knn_graph(emb, r[0], r[1], r[2], NEIGHBOUR_METRIC),
+             lambda npz, tsv, key, names, res, strand, ctx: write_knn_graph(npz, tsv, key, names, res, strand),
+             lambda res, r, what, ctx: (f"{r[0]} neighbours per {what}, {_SIMILARITY}, {r[1]}, weighted by {r[2]}: {res.n_edges} edges among "
+                                        f"{int(res.valid.sum())} {what}s, {int(np.asarray(res.mutual).sum())} of them mutual")),
+)
+EVERY_ANALYSIS = ALL_ANALYSES + KNN_ANALYSES
 
 
 def _resumes(a, npz, tsv, request, strand, base) -> bool:
@@ -1603,8 +1659,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     attribution_bin = attribution_bin_requested()
     region_penalty = region_penalty_requested()
     region_embeddings = region_embeddings_requested()
-    requests = {a.name: a.request() for a in ALL_ANALYSES}
-    base_paths = {a.name: a.base.request() for a in ALL_ANALYSES if a.base is not None}
+    requests = {a.name: a.request() for a in EVERY_ANALYSIS}
+    base_paths = {a.name: a.base.request() for a in EVERY_ANALYSIS if a.base is not None}
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -1639,13 +1695,13 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         console.error("GENOMAD_AMD_REGION_EMBEDDINGS=1 needs GENOMAD_AMD_REGION_PENALTY: the embeddings are those of the regions called "
                       "along the score tracks. Set GENOMAD_AMD_REGION_PENALTY or unset GENOMAD_AMD_REGION_EMBEDDINGS.")
         sys.exit(1)
-    for a in ALL_ANALYSES:
+    for a in EVERY_ANALYSIS:
         requested = requests[a.name] is not None
         if a.base is None and requested and not embeddings:
             console.error(f"{a.switch} needs GENOMAD_AMD_EMBEDDINGS=1: {a.needs}. Set GENOMAD_AMD_EMBEDDINGS=1 or unset {a.switch}.")
             sys.exit(1)
         if requested and a.after is not None and requests[a.after] is None:
-            other = next(b.switch for b in ALL_ANALYSES if b.name == a.after)
+            other = next(b.switch for b in EVERY_ANALYSIS if b.name == a.after)
             console.error(f"{a.switch} needs {other}: {a.needs}. Set {other} or unset {a.switch}.")
             sys.exit(1)
         if a.base is not None and (requested != (base_paths[a.name] is not None) or (requested and not embeddings)):
@@ -1680,7 +1736,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         sys.exit(1)
 
     bases = {}                       # what every requested reference's loader returned, read before any classification starts
-    for a in ALL_ANALYSES:
+    for a in EVERY_ANALYSIS:
         if a.base is not None and requests[a.name] is not None:
             try:
                 bases[a.name] = a.base.load(base_paths[a.name], strand)
@@ -1861,7 +1917,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                  and _request_of_file(regions_path, (("stride", int), ("penalty", float))) == regions_request
                                  and (regions_request is None) == (not regions_tsv_path.exists())
                                  and _request_of_file(region_emb_file, (("stride", int), ("penalty", float), ("strand", str))) == region_emb_request
-                                 and all(_resumes(a, *outputs.files(what, a.name), requests[a.name], strand, bases.get(a.name)) for a in ALL_ANALYSES)
+                                 and all(_resumes(a, *outputs.files(what, a.name), requests[a.name], strand, bases.get(a.name)) for a in EVERY_ANALYSIS)
                                  and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
                                  and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
                                                             and _npz_strand(scan_path) == strand)))   # :284-292
@@ -2040,7 +2096,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     console.log(f"Encoder embeddings of the {len(mine[0])} regions of the {what}s written to {region_emb_path.name}.")
                 elif region_emb_file.exists():      # likewise
                     region_emb_file.unlink()
-                for a in ALL_ANALYSES:
+                for a in EVERY_ANALYSIS:
                     npz, tsv = outputs.files(what, a.name)
                     request = requests[a.name]
                     if request is None:             # likewise, both files

@@ -2821,6 +2821,71 @@ def communities_table(result, names=None):
             for a, b in zip(bounds, list(bounds[1:]) + [len(order)])]
 
 
+KNN_GRAPH_MODES = ("union", "mutual")                  # gnn_knn_graph_mode: GNN_KNN_GRAPH_UNION = 0, _MUTUAL = 1
+KNN_GRAPH_WEIGHTS = ("similarity", "jaccard")          # gnn_knn_graph_weight: GNN_KNN_GRAPH_SIMILARITY = 0, _JACCARD = 1
+KNN_GRAPH_FIELDS = ("indptr", "col", "sim", "mutual", "valid")
+
+
+def knn_graph_mode(mode) -> str:
+    if mode not in KNN_GRAPH_MODES:
+        raise ValueError(f"mode {mode!r} is outside {KNN_GRAPH_MODES}")
+    return mode
+
+
+def knn_graph_weight(weight) -> str:
+    if weight not in KNN_GRAPH_WEIGHTS:
+        raise ValueError(f"weight {weight!r} is outside {KNN_GRAPH_WEIGHTS}")
+    return weight
+
+
+def knn_graph(rows, k, mode="union", weight="similarity", metric="cosine", neighbours=None):
+    """The k-nearest-neighbour graph among encoder embeddings, spelled out (the definition ``gnn_knn_graph_count`` /
+    ``gnn_knn_graph_fill`` compute on the device; readable, not fast).  ``rows`` (n, 512) float32; validity, ``metric`` and ``k``
+    (1..64) as in :func:`nearest_neighbours`, whose self-search gives the lists - or ``neighbours`` = (idx, sim), lists computed
+    elsewhere (the device's own).  N(i) is row i's entries other than -1, N+(i) = N(i) + {i}; an invalid row has an empty list and is
+    in nobody's.  The edges are the unordered pairs i < j of valid rows with j in N(i) or i in N(j) (``union``), or both (``mutual``);
+    a pair stands once, at its smaller row.  ``weight`` "similarity": where j is in N(i), the float32 that stands in row i's list for
+    j - what :func:`threshold_graph` computes for the pair; otherwise the float32 in row j's list for i, the other orientation, which
+    on the device may differ from the graph's value in the last bit.  Negative similarities are kept: the consumers (:func:`mcl_weights`,
+    :func:`spread_transitions`, :func:`average_linkage`, :func:`modularity_communities`) drop weights <= 0.  "jaccard": s = |N+(i) &
+    N+(j)|, u = |N+(i)| + |N+(j)| - s, and the weight is float32(s) / float32(u), one correctly rounded division - every edge has
+    s >= 1, so it lies in (0, 1].  Returns a dict: ``indptr`` (int64, n + 1), ``col`` (int32: row i owns ``col[indptr[i]:indptr[i + 1]]``,
+    its partners j > i strictly ascending), ``sim`` (float32), ``mutual`` (uint8: 1 when both ends list each other - everywhere under
+    ``mutual``) and ``valid`` (bool, n).  There are at most n_valid * k edges."""
+    k = neighbour_k(k)
+    knn_graph_mode(mode)
+    knn_graph_weight(weight)
+    r32 = neighbour_rows(rows, "rows")
+    valid = valid_rows(r32, metric)
+    n = len(r32)
+    idx, sim = nearest_neighbours(r32, None, k, metric) if neighbours is None else neighbours
+    idx, sim = np.asarray(idx, dtype=np.int64), np.asarray(sim, dtype=np.float32)
+    src, slot = np.nonzero(idx >= 0)                     # the arcs src -> dst
+    dst, s = idx[src, slot], sim[src, slot]
+    back = np.isin(dst * n + src, src * n + dst)         # the arc dst -> src is there too
+    own = src < dst                                      # the arc of the pair's smaller row: its value is the pair's
+    keep = own & back if mode == "mutual" else own | ~back
+    a, b = np.minimum(src, dst)[keep], np.maximum(src, dst)[keep]
+    order = np.lexsort((b, a))
+    a, b, s, both = a[order], b[order], s[keep][order], back[keep][order]
+    if weight == "jaccard":
+        plus = [set(idx[i][idx[i] >= 0].tolist()) | {i} for i in range(n)]
+        shared = np.array([len(plus[i] & plus[j]) for i, j in zip(a.tolist(), b.tolist())], dtype=np.int64).reshape(len(a))
+        size = np.array([len(p) for p in plus], dtype=np.int64).reshape(n)
+        s = shared.astype(np.float32) / (size[a] + size[b] - shared).astype(np.float32)
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(a, minlength=n))]).astype(np.int64)
+    return {"indptr": indptr, "col": b.astype(np.int32), "sim": s.astype(np.float32), "mutual": both.astype(np.uint8), "valid": valid}
+
+
+def knn_graph_table(indptr, col, sim, mutual, names=None):
+    """One record per edge of a k-nearest-neighbour graph, in its order: ``a`` < ``b`` (indices; the names where ``names`` is given),
+    ``weight`` and ``mutual`` (both ends list each other)."""
+    a, b = graph_edges(indptr, col)
+    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    return [{"a": name(i), "b": name(j), "weight": float(s), "mutual": bool(m)}
+            for i, j, s, m in zip(a, b, np.asarray(sim), np.asarray(mutual))]
+
+
 def prefix_of(input_path: Path) -> str:
     """nn_classification.py:106-108: stem, minus one more extension if the file is compressed."""
     prefix = Path(input_path).stem

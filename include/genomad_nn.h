@@ -1049,6 +1049,60 @@ int gnn_debug_communities_gain(gnn_ctx* ctx, const uint64_t* operands_host, int6
 int gnn_debug_communities_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
 int gnn_debug_communities_classes(gnn_ctx* ctx, int64_t* rows_out);
 
+/* ---- k-nearest-neighbour graph of encoder embeddings: union / mutual, similarity / Jaccard ------------------
+ * "Which rows list each other": the neighbour lists of gnn_neighbours' self-search, joined into the upper-triangle CSR of gnn_graph_* -
+ * at most n k edges whatever the data, a density that adapts per row, and the graph every consumer below gnn_graph (gnn_mcl, gnn_spread,
+ * gnn_avglink, gnn_communities) takes.  Rows, validity, metric and k are those of gnn_neighbours; no forward pass runs and no other
+ * entry point's result changes.  N(i): the entries of row i's list other than -1; N+(i) = N(i) + {i}.
+ *   edges     unordered pairs i < j of valid rows.  GNN_KNN_GRAPH_UNION: j in N(i) or i in N(j).  GNN_KNN_GRAPH_MUTUAL: both.  A pair
+ *             stands once, at its smaller row; an invalid row owns nothing and is nobody's partner.  At most n_valid * k edges.
+ *   mutual    uint8 per edge: 1 when both ends list each other (everywhere, under GNN_KNN_GRAPH_MUTUAL).  May be NULL.
+ *   weight    GNN_KNN_GRAPH_SIMILARITY: where j is in N(i), the f32 that stands in row i's list for j - bit for bit gnn_graph's value
+ *             of the pair; otherwise the f32 in row j's list for i, the other orientation, which may differ from gnn_graph's value in
+ *             the last bit.  Negative similarities are kept: the consumers drop weights <= 0.  GNN_KNN_GRAPH_JACCARD: s = |N+(i) and
+ *             N+(j)|, u = |N+(i)| + |N+(j)| - s, weight = (f32)s / (f32)u, one correctly rounded division; s >= 1, so it is in (0, 1].
+ *   outputs   indptr (int64 [n + 1]), col (int32: a row's partners j > i strictly ascending), sim (f32), mutual (uint8).
+ *   passes    count: the self-search into lists the ctx owns, every list put in ascending order, one walk over the lists that counts
+ *             every row's edges (membership: a binary search), a prefix sum, indptr and the total (*nnz_host; the stream is
+ *             synchronised to hand it back).  fill: the same walk files every edge in its owner's segment, every segment is put in
+ *             order, and the weights and flags are written.  The caller sizes col, sim and mutual between the two.  The fill reads
+ *             the lists its count left in the ctx, not the rows: it belongs to the ctx's LAST count, GNN_ERR_STATE unless that count
+ *             had the same (n, k, mode, weight, metric).  No store leaves a row's segment or the total.
+ *   ranges    0 <= n < 2^31, k in [1, 64], mode, weight and metric in [0, 1]; GNN_ERR_ARG with the value and the range in the message -
+ *             checked before the ctx is looked at.  n == 0: indptr = [0], *nnz_host = 0.  capacity < the total: GNN_ERR_ARG with both
+ *             numbers.  A total of 0: the fill launches nothing and col, sim and mutual may be NULL.
+ *   exact     the edge set, an edge's owner and its weight follow from (i, j) and the lists alone, and a segment is ordered by a
+ *             total order on distinct keys: integer atomics place the edges, yet no output bit depends on the order they arrive in,
+ *             on the grid, on gnn_debug_set_neighbour_split or on the class limits below.
+ * What it is not: not approximate; no k above 64; not multi-GPU; the consumers are not run from here.
+ * Device memory, persistent in the ctx and grow-only: what gnn_neighbours_dev holds, 20 k B per row of lists, 36 B per row of lengths,
+ * counters, offsets, cursors and class lists, 16 B per edge (gnn_knn_graph_count: + 8 B per row and the rows' 2 KB of f32;
+ * gnn_knn_graph_fill: + 9 B per edge).  Nothing is n x n.
+ * gnn_knn_graph_count / gnn_knn_graph_fill: host pointers, synchronous; the fill answers GNN_ERR_STATE unless a gnn_knn_graph_count
+ * came before it.  gnn_knn_graph_count_dev: device pointers, *nnz_host on the host.  gnn_knn_graph_fill_dev: device pointers,
+ * asynchronous on the ctx stream like gnn_classify_dev. */
+typedef enum gnn_knn_graph_mode { GNN_KNN_GRAPH_UNION = 0, GNN_KNN_GRAPH_MUTUAL = 1 } gnn_knn_graph_mode;
+typedef enum gnn_knn_graph_weight { GNN_KNN_GRAPH_SIMILARITY = 0, GNN_KNN_GRAPH_JACCARD = 1 } gnn_knn_graph_weight;
+int gnn_knn_graph_count(gnn_ctx* ctx, const float* rows_host, int64_t n, int k, int mode, int weight, int metric, int64_t* indptr_host,
+                        int64_t* nnz_host);
+int gnn_knn_graph_fill(gnn_ctx* ctx, int64_t n, int k, int mode, int weight, int metric, int32_t* col_host, float* sim_host,
+                       uint8_t* mutual_host_or_null, int64_t capacity);
+int gnn_knn_graph_count_dev(gnn_ctx* ctx, const float* rows_dev, int64_t n, int k, int mode, int weight, int metric, int64_t* indptr_dev,
+                            int64_t* nnz_host);
+int gnn_knn_graph_fill_dev(gnn_ctx* ctx, int64_t n, int k, int mode, int weight, int metric, int32_t* col_dev, float* sim_dev,
+                           uint8_t* mutual_dev_or_null, int64_t capacity);
+/* test aids; no result depends on them, and a count fixes them for its fill.  A segment of up to gnn_debug_knn_graph_wave_rows entries
+ * (1 .. 64, the default 64) is ordered by one wave in registers, one of up to gnn_debug_knn_graph_group_rows (1 .. 4096, the default
+ * 2048) by a workgroup in LDS, a longer one by a workgroup's stable radix passes through a second buffer in global memory.
+ * gnn_debug_knn_graph_classes: the rows the last count gave the [LDS, radix] class (2 values). */
+int gnn_debug_knn_graph_wave_rows(gnn_ctx* ctx, int entries);
+int gnn_debug_knn_graph_group_rows(gnn_ctx* ctx, int entries);
+int gnn_debug_knn_graph_classes(gnn_ctx* ctx, int64_t* rows_out);
+/* measurement only: with gnn_profile_enable on, the HIP-event milliseconds of the ctx's last gnn_knn_graph_count* call - [0] the
+ * self-search, [1] the ordered lists, [2] the count, [3] the scan, indptr and the classes - and behind them those of every fill since:
+ * [fill, order, finish]; *n_out = the figures recorded (0 for n == 0 or without profiling), at most `capacity` are written. */
+int gnn_debug_knn_graph_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
+
 /* ---- matches against a reference: the bipartite similarity graph query x base ------------------------------
  * "Which reference rows is every new row within the threshold of, all of them": every pair (i, j) of a valid query row i and a valid
  * base row j with sim(i, j) >= threshold and its similarity, as a CSR by query row.  The passes, the kernel, the workspace and the
