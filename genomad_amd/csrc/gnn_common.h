@@ -331,6 +331,25 @@ struct VoteWorkspace {
                                                  // leaves its last slab's pending
 };
 
+// ---- what the consumers of the similarity graph's CSR share (gnn_csr_sym.h, gnn_row_table.h) ----
+// the graph of a host-pointer entry point on the device
+struct GraphStaging {
+    DevBuf<int64_t> d_indptr;                    // [n + 1]
+    DevBuf<int32_t> d_col;                       // [nnz]
+    DevBuf<float> d_sim;
+    DevBuf<uint8_t> d_valid;                     // [n]
+};
+
+// the keyed-sum row table (gnn_row_table.h): its debug knobs and what its three row classes need
+struct RowTable {
+    int slots = 4096;                            // slots of the LDS table: 0 .. 4096; no result depends on it
+    int wave_rows = 256;                         // the longest upper bound one wave takes; no result depends on it
+    int groups = 0;                              // workgroups of a launch; 0: the library's choice; no result depends on it
+    DevBuf<int32_t> rows;                        // [3][n]: the rows of a launch by class - wave, workgroup, dense
+    DevBuf<unsigned long long> dense;            // [dense workgroups][n]: all zero between rows
+    DevBuf<int32_t> touched;                     // [dense workgroups][n]
+};
+
 // ---- Markov clusters (gnn_mcl.hip): persistent, grow-only.  Two matrices of 8 B per (row, select) and 4 B per row, the symmetric graph
 // (16 B per edge, 21 B per row), one uint64[n] accumulator and one int32[n] list per workgroup of the overflow pass (at most 2^27 cells
 // in all), 12 B per row of lists and union-find, two counters per iteration and, for gnn_mcl alone, the graph and its 29 B of results per row.
@@ -354,10 +373,7 @@ struct MclWorkspace {
     bool have = false;                           // the ctx's last gnn_mcl* succeeded: gnn_mcl_matrix may read buffer `cur`
     int64_t n = 0;
     int select = 0, cur = 0;
-    DevBuf<int64_t> d_indptr;                    // gnn_mcl: the graph
-    DevBuf<int32_t> d_col;
-    DevBuf<float> d_sim;
-    DevBuf<uint8_t> d_valid;
+    GraphStaging graph;                          // gnn_mcl: the graph
     DevBuf<int64_t> d_out;                       // gnn_mcl: [label | size | attractor | flow (u32) | is_attractor (u8)], a Landing
     PassLog passes;                              // profiling on: HIP-event time of the last call's [validate + symmetrise, initial matrix, then every iteration]
     std::vector<int64_t> overflow;               // the last call's overflow columns: [initial matrix, then every iteration]
@@ -380,10 +396,7 @@ struct SpreadWorkspace {
     DevBuf<uint8_t> mark[2];                     // [n]: the row or a neighbour of it changed in the iteration that wrote the array
     DevBuf<int32_t> rows, long_rows;             // the rows an iteration computes: one wave each, one workgroup each
     HostCounters count;                          // [iteration] changed rows; behind them [short rows, long rows, the verdict on graph and labels]
-    DevBuf<int64_t> d_indptr;                    // gnn_spread: the graph, its rows' validity and the labels
-    DevBuf<int32_t> d_col;
-    DevBuf<float> d_sim;
-    DevBuf<uint8_t> d_valid;
+    GraphStaging graph;                          // gnn_spread: the graph, its rows' validity and the labels
     DevBuf<int64_t> d_label;
     DevBuf<int64_t> d_out;                       // gnn_spread: [best (i32) | best_score (u32) | second_score (u32) | total (u64) | first (i32)], a Landing
     PassLog passes;                              // profiling on: HIP-event time of the last call's [validate + symmetrise, then every iteration]
@@ -393,9 +406,7 @@ struct SpreadWorkspace {
 // entries per edge), about 70 B per row of state, lists and records, at most 2^24 cells of dense accumulators (192 MB) and, for
 // gnn_avglink alone, the graph and its 24 B of results per row.
 struct AvglinkWorkspace {
-    int slots = 4096;                            // slots of the LDS table (gnn_debug_avglink_slots): 0 .. 4096; no result depends on it
-    int wave_rows = 256;                         // the longest upper bound one wave takes (gnn_debug_avglink_wave_rows); no result depends on it
-    int groups = 0;                              // workgroups of a contraction (gnn_debug_avglink_groups); 0: the library's choice; no result depends on it
+    RowTable table;                              // the row table's knobs (gnn_debug_avglink_slots, _wave_rows, _groups), lists and accumulators
     DevBuf<uint8_t> ok;                          // [n]: the row takes part
     DevBuf<int32_t> len;                         // [n]: entries of the live cluster's segment (first the symmetric graph's degrees)
     DevBuf<int64_t> off[2];                      // [n + 1]: where a segment starts in entry buffer b
@@ -405,14 +416,8 @@ struct AvglinkWorkspace {
     DevBuf<uint32_t> sq;                         // symmetrise's weights, widened into sum[0]
     DevBuf<int32_t> map, size, best, partner, ub;      // [n] each: see gnn_avglink.hip
     DevBuf<unsigned long long> bestS;            // [n]
-    DevBuf<int32_t> rows;                        // [3][n]: the rows of a round by class - wave, workgroup, dense
-    DevBuf<unsigned long long> dense;            // [dense workgroups][n]: all zero between rows
-    DevBuf<int32_t> touched;                     // [dense workgroups][n]
     HostCounters count;                          // [2][merged, wave rows, workgroup rows, dense rows], then the call's class totals [3], then the verdict
-    DevBuf<int64_t> d_indptr;                    // gnn_avglink: the graph
-    DevBuf<int32_t> d_col;
-    DevBuf<float> d_sim;
-    DevBuf<uint8_t> d_valid;
+    GraphStaging graph;                          // gnn_avglink: the graph
     DevBuf<int64_t> d_out;                       // gnn_avglink: [parent (i32) | weight (u64) | size_a (i32) | size_b (i32) | round (i32)], a Landing
     PassLog passes;                              // profiling on: HIP-event time of the last call's [validate + symmetrise, then every round]
     int64_t class_rows[3] = {0, 0, 0};           // the last call's rows by class, all rounds (gnn_debug_avglink_classes)
@@ -422,9 +427,7 @@ struct AvglinkWorkspace {
 // each, two entries per edge, + 4 B of symmetrise's weights), about 190 B per row of state, lists and maps, at most 2^24 cells of dense
 // accumulators (192 MB) and, for gnn_communities / gnn_label_components alone, the graph and the results.
 struct CommunitiesWorkspace {
-    int slots = 4096;                            // slots of the LDS table (gnn_debug_communities_slots): 0 .. 4096; no result depends on it
-    int wave_rows = 256;                         // the longest row one wave takes (gnn_debug_communities_wave_rows); no result depends on it
-    int groups = 0;                              // workgroups of a launch (gnn_debug_communities_groups); 0: the library's choice; no result depends on it
+    RowTable table;                              // the row table's knobs (gnn_debug_communities_slots, _wave_rows, _groups), lists and accumulators
     DevBuf<uint8_t> ok;                          // [n]: the row takes part
     DevBuf<int32_t> len[2];                      // [n]: entries of a node's segment in entry buffer b
     DevBuf<int64_t> off[2];                      // [n + 1]: where it starts
@@ -442,14 +445,8 @@ struct CommunitiesWorkspace {
     DevBuf<unsigned long long> mcursor;          // [n]
     DevBuf<int32_t> map;                         // [n]: row -> its node, -1: an invalid row
     DevBuf<int32_t> noderow[2];                  // [n]: node -> its smallest row
-    DevBuf<int32_t> rows;                        // [3][n]: the nodes of a launch by class - wave, workgroup, dense
-    DevBuf<unsigned long long> dense;            // [dense workgroups][n]: all zero between rows
-    DevBuf<int32_t> touched;                     // [dense workgroups][n]
     HostCounters count;                          // see gnn_communities.hip, "the counters"
-    DevBuf<int64_t> d_indptr;                    // gnn_communities, gnn_label_components: the graph
-    DevBuf<int32_t> d_col;
-    DevBuf<float> d_sim;
-    DevBuf<uint8_t> d_valid;
+    GraphStaging graph;                          // gnn_communities, gnn_label_components: the graph
     DevBuf<int64_t> d_out;                       // gnn_communities: [label | size | level_label], gnn_label_components: [label | out]; a Landing
     PassLog passes;                              // profiling on: the last call's [setup, then per level every sweep and, behind an accepted one, the level's end]
     int64_t class_rows[6] = {0, 0, 0, 0, 0, 0};  // the last call's rows by class: the want launches', the contractions' (gnn_debug_communities_classes)

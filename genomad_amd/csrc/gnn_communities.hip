@@ -1,21 +1,19 @@
 // Modularity communities of a similarity graph (include/genomad_nn.h, "modularity communities"): Louvain's
 // levels with a synchronous move rule, in integers throughout - the definition is sequence.modularity_communities, and every output
 // here equals it bit for bit.  W = 2^24 is a similarity of 1; M2 < 2^58 is the graph's doubled weight; r = 64 * resolution.
-//   validate, symmetrise   gnn_csr_sym.h, shared with gnn_mcl.hip, gnn_spread.hip and gnn_avglink.hip.  The host reads one word;
-//                GNN_ERR_ARG before anything else runs, the outputs untouched.
+//   validate, symmetrise   gnn_csr_sym.h, shared with the other consumers of the graph.  The host reads one word; GNN_ERR_ARG before
+//                anything else runs, the outputs untouched.
 //   graph        per level m nodes; node i owns the segment (off[i], len[i]) of one of two entry buffers (idx int32, sum uint64), self
 //                entry included, parallel entries allowed (level 0 has them apart; every consumer below adds them).
 //   level start  comm[i] = i, tot[i] = k[i] = the row's sum (one wave per node), the nodes filed by their rows' lengths on three
 //                lists, Qnum of the identity by the score and verdict launches.  Level 0 also sums M2, which the host checks.
-//   want         per filed node i of community a: the entries j != i keyed by comm[j] and summed into a table (LDS: an atomicCAS on the
-//                key, a 64-bit add on the sum), those of a itself summed aside as w_ia.  The table's walk takes D(i, c) = 64 M2 (w_ic -
+//   want         per filed node i of community a: the entries j != i keyed by comm[j] and summed into the row table of gnn_row_table.h
+//                (policy CmTable<true>), those of a itself summed aside as w_ia.  The table's walk takes D(i, c) = 64 M2 (w_ic -
 //                w_ia) - r k_i (tot_c + k_i - tot_a) in signed 128 bits and keeps the largest D > 0, among equals the smaller c, into
 //                want_c[i] and the two words of want_d[i].
-//   row classes  by the row's length (the contraction: by the upper bound of the new row), so a table never overflows: up to
-//                min(wave_rows, slots / 4) one wave with its quarter of the table in LDS; up to `slots` the workgroup with the whole
-//                table; beyond, the workgroup with a uint64[n] accumulator in global memory and a list of the keys touched
-//                (gnn_avglink.hip's scheme).  Every sum is an integer add and every choice goes through a total order: no output
-//                depends on the class, the table's size, the entries' order or the grid.
+//   row classes  gnn_row_table.h's, by the row's length (the contraction: by the upper bound of the new row).  Every sum is an integer
+//                add and every choice goes through a total order: no output depends on the class, the table's size, the entries' order
+//                or the grid.
 //   pick         one wave per node: a wanting node i moves unless an entry j != i wants to move, sits in comm[i] or in i's target and
 //                has a priority (D, h, -j) that is not smaller than i's.  It writes new_comm[i], adds k[i] to its community's new total
 //                and counts the movers.
@@ -26,32 +24,27 @@
 //   level end    the entries with equal comm join their ends (cl_join), a launch of its own flattens (nn_root); the roots are numbered
 //                by a scan (nn_scan: the order of the smallest member), the members counted, scanned and scattered (the order inside a
 //                list matters to nothing), the upper bounds len summed per component and scanned into the new segments' starts.  The
-//                contraction gathers all rows of a component's members, keyed by the column's component number, self entries kept, by
-//                the same three classes into the other entry buffer.  The map row -> node and node -> smallest row follow, and
-//                level_label is written.
+//                contraction (policy CmTable<false>) gathers all rows of a component's members, keyed by the column's component
+//                number, self entries kept, by the same three classes into the other entry buffer.  The map row -> node and node ->
+//                smallest row follow, and level_label is written.
 // Only integer atomics (LDS: keys and sums; global: the accumulators, the lists' counters, totals and sums).  No float is added or
 // compared, no inline assembly, no loop that waits for another workgroup: every loop's termination argument stands next to it.
 // Every store is guarded by its bound.
 #include "gnn_nn_frag.h"
 #include "gnn_csr_sym.h"
+#include "gnn_row_table.h"
 
 namespace gnn {
 namespace {
 
-typedef unsigned long long ull;
 typedef unsigned __int128 u128;
 typedef __int128 i128;
 
-constexpr int64_t N_MAX = (int64_t)1 << 24;      // the graph's limit (gnn_mcl)
 constexpr int64_t NNZ_END = (int64_t)1 << 30;    // entries of the upper triangle: a row's upper bound and its sum stay in their words
 constexpr ull M2_END = 1ull << 58;
 constexpr int R_MAX = 256;
 constexpr int LEVELS_MAX = 32;
 constexpr int SWEEPS_MAX = 1 << 20;
-constexpr int SLOTS_MAX = 4096;
-constexpr int THREADS = 256;
-constexpr int64_t DENSE_CELLS = (int64_t)1 << 24;       // the accumulators' cells, all workgroups together
-constexpr int EMPTY = -1;
 // the counters
 enum : size_t {
     C_FLAG = 0,                // a CSR that is none
@@ -81,11 +74,6 @@ __device__ __forceinline__ void cm_add128(ull* w, u128 x) {
     if (hi + carry) atomicAdd(w + 1, hi + carry);            // hi < 2^63 here: no wrap of its own
 }
 
-__device__ __forceinline__ ull cm_wave_sum(ull v) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);      // Ends: o halves towards 0
-    return v;
-}
-
 // The gain of node i (weight k) moving from a (total ta, w_ia = wa) into c (total tc, w_ic = wc): exact, below 2^126 in magnitude
 __device__ __forceinline__ i128 cm_gain(ull m2x64, int r, ull k, ull wc, ull wa, ull tc, ull ta) {
     return (i128)(u128)m2x64 * ((i128)(u128)wc - (i128)(u128)wa) -
@@ -95,26 +83,26 @@ __device__ __forceinline__ i128 cm_gain(ull m2x64, int r, ull k, ull wc, ull wa,
 struct Best {
     ull lo, hi;                // D > 0
     int c;                     // c < 0: none
+    static __device__ __forceinline__ Best none() { return {0ull, 0ull, -1}; }
+    // the larger D, among equals the smaller c
+    __device__ __forceinline__ void take(ull olo, ull ohi, int oc) {
+        if (oc < 0) return;
+        if (c >= 0) {
+            if (ohi < hi || (ohi == hi && (olo < lo || (olo == lo && oc >= c)))) return;
+        }
+        lo = olo;
+        hi = ohi;
+        c = oc;
+    }
+    __device__ __forceinline__ void take(const Best& o) { take(o.lo, o.hi, o.c); }
+    __device__ __forceinline__ void wave_reduce() {
+        for (int o = 32; o; o >>= 1) {                        // Ends: o halves towards 0
+            const ull olo = __shfl_xor(lo, o), ohi = __shfl_xor(hi, o);
+            const int oc = __shfl_xor(c, o);
+            take(olo, ohi, oc);
+        }
+    }
 };
-
-// the larger D, among equals the smaller c
-__device__ __forceinline__ void cm_take(Best& b, ull lo, ull hi, int c) {
-    if (c < 0) return;
-    if (b.c >= 0) {
-        if (hi < b.hi || (hi == b.hi && (lo < b.lo || (lo == b.lo && c >= b.c)))) return;
-    }
-    b.lo = lo;
-    b.hi = hi;
-    b.c = c;
-}
-
-__device__ __forceinline__ void cm_wave_reduce(Best& b) {
-    for (int o = 32; o; o >>= 1) {                            // Ends: o halves towards 0
-        const ull lo = __shfl_xor(b.lo, o), hi = __shfl_xor(b.hi, o);
-        const int c = __shfl_xor(b.c, o);
-        cm_take(b, lo, hi, c);
-    }
-}
 
 // the priority (D, h, -i) of mover j is smaller than that of mover i
 __device__ __forceinline__ bool cm_lower(ull jlo, ull jhi, unsigned jh, int j, ull ilo, ull ihi, unsigned ih, int i) {
@@ -126,25 +114,12 @@ __device__ __forceinline__ bool cm_lower(ull jlo, ull jhi, unsigned jh, int j, u
 
 __device__ __forceinline__ unsigned cm_hash(int i, int s) { return ((unsigned)i + 1u) * 2654435761u + (unsigned)s * 40503u; }
 
-// LDS traffic of one wave's lanes becomes visible to its other lanes: nothing moves across, and the wave's DS operations are done
-__device__ __forceinline__ void cm_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-struct CmArgs {
-    int64_t m, stride, cap;    // nodes; the allocation's rows (the accumulators' stride); elements of an entry buffer
-    int slots, wave_limit, dense_groups;
+struct CmArgs : RtArgs {         // m: the level's nodes; stride: the graph's rows
+    int64_t cap;               // elements of an entry buffer
     const int64_t* off;        // the source graph
     const int32_t* len;
     const int32_t* idx;
     const ull* sum;
-    const int32_t* rows;       // [3][stride]: the launch's nodes by class
-    const ull* nrows;          // [3]
-    ull* totals;               // [3]
-    ull* dense;                // [dense_groups][stride], all zero between rows
-    int32_t* touched;          // [dense_groups][stride]
     // want
     const int32_t* comm;
     const ull* tot;
@@ -177,248 +152,75 @@ __device__ __forceinline__ void cm_row(const CmArgs& a, int src, int me, int coo
     }
 }
 
-// What node R's table receives: f(key, weight), key < m.  WANT: R's entries j != R under comm[j], those of R's own community added to
-// `side` instead.  Otherwise: the entries of all members of component R under their columns' component numbers, self entries kept.
-template <bool WANT, typename F>
-__device__ __forceinline__ void cm_gather(const CmArgs& a, int R, int me, int coop, ull& side, F&& f) {
-    if (WANT) {
-        const int own = a.comm[R];
-        cm_row(a, R, me, coop, [&](int c, ull s) {
-            if (c == R) return;
-            const int key = a.comm[c];
-            if (key == own)
-                side += s;
-            else if ((unsigned)key < (ull)a.m)                // always
-                f(key, s);
-        });
-    } else {
-        const int64_t p0 = a.mstart[R], p1 = a.mstart[R + 1];
-        if (p0 < 0 || p1 > a.m) return;                       // never: the lists hold the level's nodes
-        for (int64_t p = p0; p < p1; ++p) {                   // Ends: p grows towards p1
-            const int src = a.mlist[p];
-            if ((unsigned)src >= (ull)a.m) continue;          // never
-            cm_row(a, src, me, coop, [&](int c, ull s) {
-                const int root = a.comp[c];
-                if ((unsigned)root >= (ull)a.m) return;       // never
-                const int64_t key = a.numoff[root];
-                if (key >= 0 && key < a.m) f((int)key, s);    // always
+// The two launches as policies of the row table (gnn_row_table.h).  WANT: node R's best move.  Otherwise: the contraction of component R.
+template <bool WANT>
+struct CmTable {
+    typedef CmArgs Args;
+    typedef gnn::Best Best;
+    static constexpr bool SIDE = WANT, PLACED = !WANT;
+
+    // What R's table receives: f(key, weight), key < m.  WANT: R's entries j != R under comm[j], those of R's own community added to
+    // `side` instead.  Otherwise: the entries of all members of component R under their columns' component numbers, self entries kept.
+    template <typename F>
+    static __device__ __forceinline__ void gather(const CmArgs& a, int R, int me, int coop, ull& side, F&& f) {
+        if (WANT) {
+            const int own = a.comm[R];
+            cm_row(a, R, me, coop, [&](int c, ull s) {
+                if (c == R) return;
+                const int key = a.comm[c];
+                if (key == own)
+                    side += s;
+                else if ((unsigned)key < (ull)a.m)            // always
+                    f(key, s);
             });
+        } else {
+            const int64_t p0 = a.mstart[R], p1 = a.mstart[R + 1];
+            if (p0 < 0 || p1 > a.m) return;                   // never: the lists hold the level's nodes
+            for (int64_t p = p0; p < p1; ++p) {               // Ends: p grows towards p1
+                const int src = a.mlist[p];
+                if ((unsigned)src >= (ull)a.m) continue;      // never
+                cm_row(a, src, me, coop, [&](int c, ull s) {
+                    const int root = a.comp[c];
+                    if ((unsigned)root >= (ull)a.m) return;   // never
+                    const int64_t key = a.numoff[root];
+                    if (key >= 0 && key < a.m) f((int)key, s);      // always
+                });
+            }
         }
     }
-}
 
-template <bool WANT>
-__device__ __forceinline__ int cm_bound(const CmArgs& a, int R) {
-    return WANT ? a.len[R] : a.ub[R];
-}
+    static __device__ __forceinline__ int bound(const CmArgs& a, int R, int64_t&) { return WANT ? a.len[R] : a.ub[R]; }
 
-// one entry of the finished table, by the thread that walks it: WANT takes its gain, otherwise it becomes entry `pos` of the new row
-template <bool WANT>
-__device__ __forceinline__ void cm_visit(const CmArgs& a, int R, int u, int key, ull S, int pos, ull wa, Best& b) {
-    if (WANT) {
-        const i128 d = cm_gain(a.m2x64, a.r, a.k[R], S, wa, a.tot[key], a.tot[a.comm[R]]);
-        if (d > 0) cm_take(b, (ull)(u128)d, (ull)((u128)d >> 64), key);
-    } else {
-        const int64_t nb = a.noff[R];
-        if (pos < u && nb >= 0 && nb + u <= a.cap) {          // always: the distinct keys are at most the entries
-            a.nidx[nb + pos] = key;
-            a.nsum[nb + pos] = S;
+    // WANT takes the key's gain (wa: w_ia), otherwise the key becomes entry `pos` of the new row
+    static __device__ __forceinline__ void visit(const CmArgs& a, int R, int u, int64_t, int key, ull S, int pos, ull wa, Best& b) {
+        if (WANT) {
+            const i128 d = cm_gain(a.m2x64, a.r, a.k[R], S, wa, a.tot[key], a.tot[a.comm[R]]);
+            if (d > 0) b.take((ull)(u128)d, (ull)((u128)d >> 64), key);
+        } else {
+            const int64_t nb = a.noff[R];
+            if (pos < u && nb >= 0 && nb + u <= a.cap) {      // always: the distinct keys are at most the entries
+                a.nidx[nb + pos] = key;
+                a.nsum[nb + pos] = S;
+            }
         }
     }
-}
 
-// the row's results, by one thread
-template <bool WANT>
-__device__ __forceinline__ void cm_finish(const CmArgs& a, int R, const Best& b, int count) {
-    if (WANT) {
-        a.want_c[R] = b.c;
-        a.want_d[2 * (int64_t)R] = b.c >= 0 ? b.lo : 0ull;
-        a.want_d[2 * (int64_t)R + 1] = b.c >= 0 ? b.hi : 0ull;
-    } else {
-        a.nlen[R] = count;
-    }
-}
-
-// (key, s) into a table of T slots that holds fewer than T other keys: linear probing from a multiplicative hash
-__device__ __forceinline__ void cm_insert(int32_t* keys, ull* sums, int T, int key, ull s) {
-    unsigned h = (unsigned)(((ull)((unsigned)key * 2654435761u) * (ull)T) >> 32);      // < T
-    for (int p = 0; p < T; ++p) {                             // Ends: p grows towards T; a free slot or the key's own is met before
-        const int prev = atomicCAS(&keys[h], EMPTY, key);
-        if (prev == EMPTY || prev == key) {
-            atomicAdd(&sums[h], s);
-            return;
+    // the row's results
+    static __device__ __forceinline__ void finish(const CmArgs& a, int R, const Best& b, int count) {
+        if (WANT) {
+            a.want_c[R] = b.c;
+            a.want_d[2 * (int64_t)R] = b.c >= 0 ? b.lo : 0ull;
+            a.want_d[2 * (int64_t)R + 1] = b.c >= 0 ? b.hi : 0ull;
+        } else {
+            a.nlen[R] = count;
         }
-        h = h + 1 == (unsigned)T ? 0u : h + 1;
     }
-}
-
-// the table size a row of upper bound u takes of `most` >= u slots: results do not depend on it, the walk's length does
-__device__ __forceinline__ int cm_table(int u, int most, int least) { return min(most, max(least, 2 * u)); }
-
-// R by one wave, its table the T slots at keys / sums
-template <bool WANT>
-__device__ __forceinline__ void cm_row_wave(const CmArgs& a, int R, int32_t* keys, ull* sums, int slice) {
-    const int lane = threadIdx.x & 63;
-    const int u = cm_bound<WANT>(a, R);
-    if (u < 1 || u > slice) return;                           // never: the row was filed by its bound
-    const int T = cm_table(u, slice, 64);
-    ull side = 0;
-    cm_gather<WANT>(a, R, lane, 64, side, [&](int key, ull s) { cm_insert(keys, sums, T, key, s); });
-    side = cm_wave_sum(side);
-    cm_wave_sync();
-    Best b = {0ull, 0ull, -1};
-    int count = 0;
-    for (int s0 = 0; s0 < T; s0 += 64) {                      // Ends: s0 grows towards T; uniform in the wave
-        const int s = s0 + lane;
-        const int key = s < T ? keys[s] : EMPTY;
-        const ull full = __ballot(key != EMPTY);
-        if (key != EMPTY) {
-            const ull S = sums[s];
-            keys[s] = EMPTY;
-            sums[s] = 0;
-            cm_visit<WANT>(a, R, u, key, S, count + __popcll(full & ((1ull << lane) - 1ull)), side, b);
-        }
-        count += __popcll(full);
-    }
-    cm_wave_sync();                                           // the slots are clear for the wave's next row
-    cm_wave_reduce(b);
-    if (lane == 0) cm_finish<WANT>(a, R, b, min(count, u));
-}
-
-struct BlockShared {
-    Best red[THREADS / 64];
-    ull side;
-    int cnt;
 };
 
-// the workgroup's best of its threads', in thread 0
-__device__ __forceinline__ void cm_block_reduce(Best& b, Best* red) {
-    cm_wave_reduce(b);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < THREADS / 64; ++w) cm_take(b, red[w].lo, red[w].hi, red[w].c);      // Ends: w grows towards 4
-}
-
-// R by the whole workgroup (every thread calls it), its table the first T of the `slots`
+// grid = the groups, RT_THREADS threads: rt_rows
 template <bool WANT>
-__device__ __forceinline__ void cm_row_block(const CmArgs& a, int R, int32_t* keys, ull* sums, BlockShared* sh) {
-    const int tid = threadIdx.x;
-    const int u = cm_bound<WANT>(a, R);
-    if (u < 1 || u > a.slots) return;                         // never; uniform
-    const int T = cm_table(u, a.slots, THREADS);
-    ull side = 0;
-    cm_gather<WANT>(a, R, tid, THREADS, side, [&](int key, ull s) { cm_insert(keys, sums, T, key, s); });
-    if (side) atomicAdd(&sh->side, side);
-    __syncthreads();
-    const ull wa = sh->side;
-    Best b = {0ull, 0ull, -1};
-    for (int s = tid; s < T; s += THREADS) {                  // Ends: s grows towards T
-        const int key = keys[s];
-        if (key == EMPTY) continue;
-        const ull S = sums[s];
-        keys[s] = EMPTY;
-        sums[s] = 0;
-        cm_visit<WANT>(a, R, u, key, S, WANT ? 0 : atomicAdd(&sh->cnt, 1), wa, b);
-    }
-    cm_block_reduce(b, sh->red);                              // its barrier: every add to cnt and every read of side is done
-    if (tid == 0) {
-        cm_finish<WANT>(a, R, b, min(sh->cnt, u));
-        sh->cnt = 0;
-        sh->side = 0;
-    }
-    __syncthreads();
-}
-
-// R by the whole workgroup with its accumulator in global memory: a key's first add finds 0 there (every weight is > 0)
-template <bool WANT>
-__device__ __forceinline__ void cm_row_dense(const CmArgs& a, int R, BlockShared* sh) {
-    const int tid = threadIdx.x;
-    ull* const dense = a.dense + (int64_t)blockIdx.x * a.stride;
-    int32_t* const touched = a.touched + (int64_t)blockIdx.x * a.stride;
-    const int u = cm_bound<WANT>(a, R);
-    if (u < 1) return;                                        // never; uniform
-    ull side = 0;
-    cm_gather<WANT>(a, R, tid, THREADS, side, [&](int key, ull s) {
-        const ull old = atomicAdd(dense + key, s);            // key < m <= stride: cm_gather
-        if (old == 0) {
-            const int at = atomicAdd(&sh->cnt, 1);
-            if (at < a.m) touched[at] = key;                  // always: at most m keys
-        }
-    });
-    if (side) atomicAdd(&sh->side, side);
-    __syncthreads();
-    const ull wa = sh->side;
-    const int P = (int)min<int64_t>(min(sh->cnt, u), a.m);
-    Best b = {0ull, 0ull, -1};
-    for (int p = tid; p < P; p += THREADS) {                  // Ends: p grows towards P
-        const int key = touched[p];
-        if ((unsigned)key >= (ull)a.m) continue;              // never
-        // written by atomics of this workgroup: the load goes where they went
-        const ull S = __hip_atomic_load(dense + key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(dense + key, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        cm_visit<WANT>(a, R, u, key, S, p, wa, b);
-    }
-    cm_block_reduce(b, sh->red);
-    if (tid == 0) {
-        cm_finish<WANT>(a, R, b, P);
-        sh->cnt = 0;
-        sh->side = 0;
-    }
-    __syncthreads();
-}
-
-// grid = the groups, 256 threads: the first dense_groups workgroups take the dense rows g, g + dense_groups, ..., then every workgroup
-// the workgroup rows g, g + groups, ..., then its waves the wave rows w, w + 4 * groups, ...
-template <bool WANT>
-__global__ __launch_bounds__(THREADS) void cm_table_kernel(CmArgs a) {
-    __shared__ int32_t keys[SLOTS_MAX];
-    __shared__ ull sums[SLOTS_MAX];
-    __shared__ BlockShared sh;
-    const int tid = threadIdx.x, wave = tid >> 6;
-    for (int s = tid; s < SLOTS_MAX; s += THREADS) {          // Ends: s grows towards SLOTS_MAX
-        keys[s] = EMPTY;
-        sums[s] = 0;
-    }
-    if (tid == 0) {
-        sh.cnt = 0;
-        sh.side = 0;
-    }
-    __syncthreads();
-    const int64_t nwave = (int64_t)min(a.nrows[0], (ull)a.m), nblock = (int64_t)min(a.nrows[1], (ull)a.m),
-                  ndense = (int64_t)min(a.nrows[2], (ull)a.m);
-    if (blockIdx.x == 0 && tid < 3) a.totals[tid] += a.nrows[tid];
-    if ((int)blockIdx.x < a.dense_groups)
-        for (int64_t w = blockIdx.x; w < ndense; w += a.dense_groups) {      // Ends: w grows towards ndense
-            const int R = a.rows[2 * a.stride + w];
-            if ((unsigned)R < (ull)a.m) cm_row_dense<WANT>(a, R, &sh);       // always; uniform: w is the workgroup's
-        }
-    for (int64_t w = blockIdx.x; w < nblock; w += gridDim.x) {               // Ends: w grows towards nblock
-        const int R = a.rows[a.stride + w];
-        if ((unsigned)R < (ull)a.m) cm_row_block<WANT>(a, R, keys, sums, &sh);      // always; uniform
-    }
-    const int slice = a.slots / 4;                            // a wave's quarter of the table
-    for (int64_t w = (int64_t)blockIdx.x * 4 + wave; w < nwave; w += (int64_t)gridDim.x * 4) {      // Ends: w grows towards nwave
-        const int R = a.rows[w];
-        if ((unsigned)R < (ull)a.m) cm_row_wave<WANT>(a, R, keys + wave * slice, sums + wave * slice, slice);      // always; no barrier here
-    }
-}
-
-// The class of node i of bound u (-1: no entries) filed on its list, by every thread of the wave
-__device__ __forceinline__ void cm_file(int64_t stride, int i, int u, int slots, int wave_limit, int32_t* rows, ull* nrows) {
-    const int lane = threadIdx.x & 63;
-    const ull below = (1ull << lane) - 1ull;
-    const int cls = u < 1 ? -1 : (u <= wave_limit ? 0 : (u <= slots ? 1 : 2));
-    for (int k = 0; k < 3; ++k) {                             // Ends: three classes
-        const ull mask = __ballot(cls == k);
-        if (!mask) continue;                                  // uniform
-        const int leader = __ffsll((long long)mask) - 1;
-        ull base = 0;
-        if (lane == leader) base = atomicAdd(nrows + k, (ull)__popcll(mask));
-        base = __shfl(base, leader);
-        const ull at = base + (ull)__popcll(mask & below);
-        if (cls == k && at < (ull)stride) rows[(int64_t)k * stride + (int64_t)at] = i;      // always: a node is filed once
-    }
+__global__ __launch_bounds__(RT_THREADS) void cm_table_kernel(CmArgs a) {
+    rt_rows<CmTable<WANT>>(a);
 }
 
 // one thread per row: the state before level 0
@@ -428,13 +230,6 @@ __global__ __launch_bounds__(256) void cm_rows_init_kernel(int64_t n, const uint
     if (i >= n) return;
     map[i] = ok[i] ? (int32_t)i : -1;
     noderow[i] = (int32_t)i;
-}
-
-// the symmetric graph's weights as the sums of buffer 0
-__global__ __launch_bounds__(256) void cm_widen_kernel(int64_t cells, const int64_t* __restrict__ soff, int64_t n, const uint32_t* __restrict__ sq,
-                                                       ull* __restrict__ sum) {
-    const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (x < cells && x < soff[n]) sum[x] = sq[x];
 }
 
 // one thread per node: a level's first assignment, and the nodes filed by their rows' lengths
@@ -451,7 +246,7 @@ __global__ __launch_bounds__(256) void cm_level_init_kernel(int64_t m, int64_t s
         want_d[2 * i + 1] = 0;
         parent[i] = (int32_t)i;
     }
-    cm_file(stride, (int)i, u, slots, wave_limit, rows, nrows);
+    rt_file(stride, (int)i, u, slots, wave_limit, rows, nrows);
 }
 
 // one wave per node: k[i] = tot[i] = the row's sum; m2 (not NULL at level 0) receives their sum in two words
@@ -466,7 +261,7 @@ __global__ __launch_bounds__(256) void cm_degree_kernel(int64_t m, int64_t cap, 
         ull s = 0;
         if (b >= 0 && l >= 0 && b + l <= cap)                 // always
             for (int x = lane; x < l; x += 64) s += sum[b + x];      // Ends: x grows towards l
-        s = cm_wave_sum(s);
+        s = rt_wave_sum(s);
         if (lane == 0) {
             k[i] = s;
             tot[i] = s;
@@ -533,7 +328,7 @@ __global__ __launch_bounds__(256) void cm_score_kernel(int64_t m, int64_t cap, c
             }
         if (lane == 0) squares += (u128)tot[i] * tot[i];      // the community founded by i; an empty one adds 0
     }
-    inner = cm_wave_sum(inner);                               // below M2 < 2^58
+    inner = rt_wave_sum(inner);                               // below M2 < 2^58
     if (lane == 0) {
         if (inner) atomicAdd(in, inner);
         if (squares) cm_add128(sq, squares);                  // below M2^2 < 2^116
@@ -624,7 +419,7 @@ __global__ __launch_bounds__(256) void cm_contract_file_kernel(int64_t m, int64_
         nlen[v] = 0;
     }
     if (v == 0) *components = (ull)numoff[m];
-    cm_file(stride, (int)v, u, slots, wave_limit, rows, nrows);
+    rt_file(stride, (int)v, u, slots, wave_limit, rows, nrows);
 }
 
 // one thread per row and per node (m <= n): the maps follow the contraction
@@ -715,12 +510,7 @@ __global__ __launch_bounds__(256) void lc_out_kernel(int64_t n, const uint8_t* _
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 
-struct CommIn {
-    const int64_t* indptr;     // device
-    const int32_t* col;
-    const float* sim;
-    const uint8_t* valid;      // device, or NULL: every row
-    int64_t n, nnz;
+struct CommIn : CsrGraph {      // the graph on the device
     int r, max_levels, max_sweeps;
 };
 
@@ -738,15 +528,8 @@ struct CommHost {
     uint64_t* m2;
 };
 
-int graph_check(const std::string& f, int64_t n, int64_t nnz) {
-    const auto bad = [&](const char* what, int64_t v, const char* range) {
-        set_error(f + ": " + what + " " + std::to_string(v) + " is outside " + range);
-        return GNN_ERR_ARG;
-    };
-    if (n < 0 || n > N_MAX) return bad("n", n, "[0, 2^24]");
-    if (nnz < 0 || nnz >= NNZ_END) return bad("nnz", nnz, "[0, 2^30)");
-    return GNN_OK;
-}
+// the graph's limits here: a row's upper bound and its sum stay in their words
+int cm_graph_check(const std::string& f, int64_t n, int64_t nnz) { return graph_check(f, n, nnz, NNZ_END, "[0, 2^30)"); }
 
 int communities_check(const char* fn, const CommIn& in, const CommOut& out, const CommHost& h) {
     const std::string f(fn);
@@ -754,7 +537,7 @@ int communities_check(const char* fn, const CommIn& in, const CommOut& out, cons
         set_error(f + ": " + what + " " + std::to_string(v) + " is outside " + range);
         return GNN_ERR_ARG;
     };
-    if (int rc = graph_check(f, in.n, in.nnz)) return rc;
+    if (int rc = cm_graph_check(f, in.n, in.nnz)) return rc;
     if (in.r < 1 || in.r > R_MAX) return bad("r", in.r, "[1, 256]: the resolution is a multiple of 1/64 in [1/64, 4]");
     if (in.max_levels < 1 || in.max_levels > LEVELS_MAX) return bad("max_levels", in.max_levels, "[1, 32]");
     if (in.max_sweeps < 1 || in.max_sweeps > SWEEPS_MAX) return bad("max_sweeps", in.max_sweeps, "[1, 2^20]");
@@ -765,21 +548,12 @@ int communities_check(const char* fn, const CommIn& in, const CommOut& out, cons
 }
 
 // validate: the verdict on the graph and the rows' validity in w.ok; one synchronise
-int graph_validate(gnn_ctx* ctx, const char* fn, CommunitiesWorkspace& w, const int64_t* indptr, const int32_t* col, const float* sim,
-                   const uint8_t* valid, int64_t n, int64_t nnz) {
-    int rc = nn_reserve(ctx, w.ok, (size_t)n);
+int cm_validate(gnn_ctx* ctx, const char* fn, CommunitiesWorkspace& w, const CsrGraph& g) {
+    int rc = nn_reserve(ctx, w.ok, (size_t)g.n);
     if (!rc) rc = w.count.reserve(ctx, C_WORDS);
     if (!rc) rc = w.count.zero(ctx, 0, C_WORDS);
     if (rc) return rc;
-    if ((rc = launch_1d(mc_validate_kernel, n, ctx->stream, n, nnz, indptr, col, sim, valid, w.ok.get(), w.count.dev() + C_FLAG))) return rc;
-    ull bad = 0;
-    if ((rc = w.count.read(ctx, C_FLAG, 1, &bad))) return rc;
-    if (bad) {
-        set_error(std::string(fn) + ": the graph is no upper-triangle CSR of " + std::to_string(n) + " rows and " + std::to_string(nnz) +
-                  " entries with similarities below 64: indptr must rise from 0 to nnz, a row's col lie in (row, n), sim be finite");
-        return GNN_ERR_ARG;
-    }
-    return GNN_OK;
+    return graph_validate(ctx, fn, g, w.ok.get(), w.count, C_FLAG);
 }
 
 // n > 0 rows: the graph on the device -> label, size and level_label on the device, the rest on the host.  The ctx's stream is
@@ -789,9 +563,8 @@ int communities_run(gnn_ctx* ctx, const char* fn, const CommIn& in, const CommOu
     w.passes.begin();
     const int64_t n = in.n;
     const size_t entries = (size_t)std::max<int64_t>(2 * in.nnz, 1);
-    const int slots = w.slots, wave_limit = std::min(w.wave_rows, slots / 4);
-    const int groups = w.groups > 0 ? w.groups : (int)std::min<int64_t>((n + 3) / 4, 8 * (int64_t)std::max(ctx->cu_count, 1));
-    const int dense_groups = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(groups, 64), DENSE_CELLS / n));
+    const int slots = w.table.slots;
+    RtPlan plan;
     int rc = GNN_OK;
     ull m2 = 0;
     ull qnum[2] = {0, 0};
@@ -805,10 +578,10 @@ int communities_run(gnn_ctx* ctx, const char* fn, const CommIn& in, const CommOu
     const auto level_start = [&](bool first) -> int {
         if ((rc = w.count.zero(ctx, C_MOVED, C_COMPONENTS - C_MOVED))) return rc;
         if ((rc = w.count.zero(ctx, C_WANT_ROWS, 3))) return rc;
-        if ((rc = launch_1d(cm_level_init_kernel, m, ctx->stream, m, n, slots, wave_limit, w.len[cur].get(), w.comm[0].get(), w.want_c.get(),
-                            w.want_d.get(), w.parent.get(), w.rows.get(), w.count.dev() + C_WANT_ROWS)))
+        if ((rc = launch_1d(cm_level_init_kernel, m, ctx->stream, m, n, slots, plan.wave_limit, w.len[cur].get(), w.comm[0].get(),
+                            w.want_c.get(), w.want_d.get(), w.parent.get(), w.table.rows.get(), w.count.dev() + C_WANT_ROWS)))
             return rc;
-        const unsigned wgrid = (unsigned)std::min<int64_t>((m + 3) / 4, groups);
+        const unsigned wgrid = (unsigned)std::min<int64_t>((m + 3) / 4, plan.groups);
         hipLaunchKernelGGL(cm_degree_kernel, dim3(wgrid), dim3(256), 0, ctx->stream, m, (int64_t)entries, w.off[cur].get(), w.len[cur].get(),
                            w.sum[cur].get(), w.k.get(), w.tot[0].get(), first ? w.count.dev() + C_M2 : nullptr);
         GNN_HIP(hipGetLastError());
@@ -832,7 +605,7 @@ int communities_run(gnn_ctx* ctx, const char* fn, const CommIn& in, const CommOu
 
     {
         PassLog::Scope setup(ctx, w.passes);                  // open across the reads below: nothing is settled there
-        if ((rc = graph_validate(ctx, fn, w, in.indptr, in.col, in.sim, in.valid, n, in.nnz))) return rc;
+        if ((rc = cm_validate(ctx, fn, w, in))) return rc;
         rc = nn_reserve(ctx, w.cursor, (size_t)n);
         if (!rc) rc = nn_reserve(ctx, w.sq, entries);
         for (int b = 0; b < 2 && !rc; ++b) {
@@ -851,15 +624,12 @@ int communities_run(gnn_ctx* ctx, const char* fn, const CommIn& in, const CommOu
         if (!rc) rc = nn_reserve(ctx, w.mcursor, (size_t)n);
         if (!rc) rc = nn_reserve(ctx, w.numoff, (size_t)n + 1);
         if (!rc) rc = nn_reserve(ctx, w.mstart, (size_t)n + 1);
-        if (!rc) rc = nn_reserve(ctx, w.rows, (size_t)3 * n);
-        if (!rc) rc = nn_reserve(ctx, w.dense, (size_t)dense_groups * n);
-        if (!rc) rc = nn_reserve(ctx, w.touched, (size_t)dense_groups * n);
+        if (!rc) rc = rt_plan(ctx, n, w.table, plan);
         if (rc) return rc;
-        GNN_HIP(hipMemsetAsync(w.dense.get(), 0, (size_t)dense_groups * n * sizeof(ull), ctx->stream));
         if ((rc = csr_symmetrise(ctx->stream, n, in.indptr, in.col, in.sim, w.ok.get(), w.len[0].get(), w.off[0].get(), w.cursor.get(),
                                  w.idx[0].get(), w.sq.get())))
             return rc;
-        if ((rc = launch_1d(cm_widen_kernel, (int64_t)entries, ctx->stream, (int64_t)entries, w.off[0].get(), n, w.sq.get(), w.sum[0].get()))) return rc;
+        if ((rc = launch_1d(rt_widen_kernel, (int64_t)entries, ctx->stream, (int64_t)entries, w.off[0].get(), n, w.sq.get(), w.sum[0].get()))) return rc;
         if ((rc = launch_1d(cm_rows_init_kernel, n, ctx->stream, n, w.ok.get(), w.map.get(), w.noderow[0].get()))) return rc;
         live = w.ok.get();
         if ((rc = level_start(true))) return rc;
@@ -868,11 +638,11 @@ int communities_run(gnn_ctx* ctx, const char* fn, const CommIn& in, const CommOu
     a.stride = n;
     a.cap = (int64_t)entries;
     a.slots = slots;
-    a.wave_limit = wave_limit;
-    a.dense_groups = dense_groups;
-    a.rows = w.rows.get();
-    a.dense = w.dense.get();
-    a.touched = w.touched.get();
+    a.wave_limit = plan.wave_limit;
+    a.dense_groups = plan.dense_groups;
+    a.rows = w.table.rows.get();
+    a.dense = w.table.dense.get();
+    a.touched = w.table.touched.get();
     a.k = w.k.get();
     a.m2x64 = m2 * 64;
     a.r = in.r;
@@ -894,7 +664,7 @@ int communities_run(gnn_ctx* ctx, const char* fn, const CommIn& in, const CommOu
             for (uint8_t v : ok) n_live += v != 0;
         }
         const int64_t nodes = levels == 0 ? n_live : m;
-        const unsigned wgrid = (unsigned)std::min<int64_t>((m + 3) / 4, groups);
+        const unsigned wgrid = (unsigned)std::min<int64_t>((m + 3) / 4, plan.groups);
         a.m = m;
         a.off = w.off[cur].get();
         a.len = w.len[cur].get();
@@ -913,7 +683,7 @@ int communities_run(gnn_ctx* ctx, const char* fn, const CommIn& in, const CommOu
                 GNN_HIP(hipMemsetAsync(w.tot[c ^ 1].get(), 0, (size_t)m * sizeof(ull), ctx->stream));
                 a.comm = w.comm[c].get();
                 a.tot = w.tot[c].get();
-                hipLaunchKernelGGL(cm_table_kernel<true>, dim3((unsigned)groups), dim3(THREADS), 0, ctx->stream, a);
+                hipLaunchKernelGGL(cm_table_kernel<true>, dim3((unsigned)plan.groups), dim3(RT_THREADS), 0, ctx->stream, a);
                 GNN_HIP(hipGetLastError());
                 hipLaunchKernelGGL(cm_pick_kernel, dim3(wgrid), dim3(256), 0, ctx->stream, m, a.cap, (int)sweeps, a.off, a.len, a.idx, a.comm,
                                    w.want_c.get(), w.want_d.get(), w.k.get(), w.comm[c ^ 1].get(), w.tot[c ^ 1].get(), w.count.dev() + C_MOVED);
@@ -961,8 +731,8 @@ int communities_run(gnn_ctx* ctx, const char* fn, const CommIn& in, const CommOu
             if ((rc = launch_1d(cm_scatter_kernel, m, ctx->stream, m, live, w.comp.get(), w.numoff.get(), w.mstart.get(), w.mcursor.get(),
                                 w.mlist.get())))
                 return rc;
-            if ((rc = launch_1d(cm_contract_file_kernel, m, ctx->stream, m, n, slots, wave_limit, w.ub.get(), w.numoff.get(), w.len[nxt].get(),
-                                w.rows.get(), w.count.dev() + C_CONTRACT_ROWS, w.count.dev() + C_COMPONENTS)))
+            if ((rc = launch_1d(cm_contract_file_kernel, m, ctx->stream, m, n, slots, plan.wave_limit, w.ub.get(), w.numoff.get(),
+                                w.len[nxt].get(), w.table.rows.get(), w.count.dev() + C_CONTRACT_ROWS, w.count.dev() + C_COMPONENTS)))
                 return rc;
             a.nrows = w.count.dev() + C_CONTRACT_ROWS;
             a.totals = w.count.dev() + C_TOTALS + 3;
@@ -970,7 +740,7 @@ int communities_run(gnn_ctx* ctx, const char* fn, const CommIn& in, const CommOu
             a.nlen = w.len[nxt].get();
             a.nidx = w.idx[nxt].get();
             a.nsum = w.sum[nxt].get();
-            hipLaunchKernelGGL(cm_table_kernel<false>, dim3((unsigned)groups), dim3(THREADS), 0, ctx->stream, a);
+            hipLaunchKernelGGL(cm_table_kernel<false>, dim3((unsigned)plan.groups), dim3(RT_THREADS), 0, ctx->stream, a);
             GNN_HIP(hipGetLastError());
             if ((rc = launch_1d(cm_relabel_kernel, n, ctx->stream, n, m, w.comp.get(), w.flag.get(), w.numoff.get(), w.map.get(), w.noderow[nr].get(),
                                 w.noderow[nr ^ 1].get())))
@@ -1030,54 +800,22 @@ void communities_empty(gnn_ctx* ctx, const CommHost& h) {
     *h.m2 = 0;
 }
 
-// the graph of a host-pointer entry point into the workspace; every buffer stands before a copy is enqueued
-int graph_upload(gnn_ctx* ctx, CommunitiesWorkspace& w, const int64_t* indptr, const int32_t* col, const float* sim, const uint8_t* valid, int64_t n,
-                 int64_t nnz) {
-    GNN_HIP(hipMemcpyAsync(w.d_indptr.get(), indptr, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (nnz > 0) {
-        GNN_HIP(hipMemcpyAsync(w.d_col.get(), col, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        GNN_HIP(hipMemcpyAsync(w.d_sim.get(), sim, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (valid) GNN_HIP(hipMemcpyAsync(w.d_valid.get(), valid, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    return GNN_OK;
-}
-
-int graph_reserve(gnn_ctx* ctx, CommunitiesWorkspace& w, int64_t n, int64_t nnz) {
-    int rc = nn_reserve(ctx, w.d_indptr, (size_t)n + 1);
-    if (!rc) rc = nn_reserve(ctx, w.d_col, (size_t)std::max<int64_t>(nnz, 1));
-    if (!rc) rc = nn_reserve(ctx, w.d_sim, (size_t)std::max<int64_t>(nnz, 1));
-    if (!rc) rc = nn_reserve(ctx, w.d_valid, (size_t)n);
-    return rc;
-}
-
 // n > 0: label -> out on the device
-int components_run(gnn_ctx* ctx, const char* fn, const int64_t* indptr, const int32_t* col, const float* sim, const uint8_t* valid, int64_t n, int64_t nnz,
-                   const int64_t* label, int64_t* out) {
+int components_run(gnn_ctx* ctx, const char* fn, const CsrGraph& g, const int64_t* label, int64_t* out) {
     CommunitiesWorkspace& w = ctx->cmt;
+    const int64_t n = g.n;
     int rc = nn_reserve(ctx, w.parent, (size_t)n);
     if (rc) return rc;
-    if ((rc = graph_validate(ctx, fn, w, indptr, col, sim, valid, n, nnz))) return rc;
+    if ((rc = cm_validate(ctx, fn, w, g))) return rc;
     if ((rc = launch_1d(lc_init_kernel, n, ctx->stream, n, w.parent.get()))) return rc;
-    if ((rc = launch_1d(lc_join_kernel, n, ctx->stream, n, indptr, col, sim, w.ok.get(), label, w.parent.get()))) return rc;
+    if ((rc = launch_1d(lc_join_kernel, n, ctx->stream, n, g.indptr, g.col, g.sim, w.ok.get(), label, w.parent.get()))) return rc;
     return launch_1d(lc_out_kernel, n, ctx->stream, n, w.ok.get(), label, w.parent.get(), out);
 }
 
 int components_check(const char* fn, const int64_t* indptr, const int32_t* col, const float* sim, int64_t n, int64_t nnz, const int64_t* label,
                      const int64_t* out) {
-    if (int rc = graph_check(fn, n, nnz)) return rc;
+    if (int rc = cm_graph_check(fn, n, nnz)) return rc;
     return nn_check_required(fn, indptr && (nnz == 0 || (col && sim)) && (n == 0 || (label && out)), "indptr, col, sim, label and out");
-}
-
-// the body of the two debug knobs that return the value before the call
-int communities_knob(gnn_ctx* ctx, const char* fn, int* knob, int value) {
-    if (int rc = check_ctx(ctx)) return rc;
-    if (value < -1 || value > SLOTS_MAX) {
-        set_error(std::string(fn) + ": " + std::to_string(value) + " is outside [-1, " + std::to_string(SLOTS_MAX) + "]");
-        return GNN_ERR_ARG;
-    }
-    const int before = *knob;
-    if (value >= 0) *knob = value;
-    return before;
 }
 
 }  // namespace
@@ -1090,7 +828,7 @@ extern "C" int gnn_communities_dev(gnn_ctx* ctx, const int64_t* indptr_dev, cons
                                    int64_t* level_label_dev, int64_t* level_stats_host, uint64_t* level_qnum_host, int64_t* levels_host,
                                    int* complete_host, uint64_t* m2_host) {
     const char* const fn = "gnn_communities_dev";
-    const CommIn in = {indptr_dev, col_dev, sim_dev, valid_dev_or_null, n, nnz, r, max_levels, max_sweeps};
+    const CommIn in = {{indptr_dev, col_dev, sim_dev, valid_dev_or_null, n, nnz}, r, max_levels, max_sweeps};
     const CommOut out = {label_dev, size_dev, level_label_dev};
     const CommHost h = {level_stats_host, level_qnum_host, levels_host, complete_host, m2_host};
     if (int rc = communities_check(fn, in, out, h)) return rc;
@@ -1107,7 +845,7 @@ extern "C" int gnn_communities(gnn_ctx* ctx, const int64_t* indptr_host, const i
                                int64_t* level_label_host, int64_t* level_stats_host, uint64_t* level_qnum_host, int64_t* levels_host,
                                int* complete_host, uint64_t* m2_host) {
     const char* const fn = "gnn_communities";
-    CommIn in = {indptr_host, col_host, sim_host, valid_host_or_null, n, nnz, r, max_levels, max_sweeps};
+    CommIn in = {{indptr_host, col_host, sim_host, valid_host_or_null, n, nnz}, r, max_levels, max_sweeps};
     const CommOut host = {label_host, size_host, level_label_host};
     const CommHost h = {level_stats_host, level_qnum_host, levels_host, complete_host, m2_host};
     if (int rc = communities_check(fn, in, host, h)) return rc;
@@ -1118,17 +856,13 @@ extern "C" int gnn_communities(gnn_ctx* ctx, const int64_t* indptr_host, const i
     }
     CommunitiesWorkspace& w = ctx->cmt;
     // the results stand in a scratch of their own and reach the caller behind a run that succeeded: d_out = [label | size | level_label]
-    int rc = graph_reserve(ctx, w, n, nnz);
+    int rc = graph_reserve(ctx, w.graph, n, nnz);
     Landing land(w.d_out);
     const int label = land.add((int64_t*)nullptr, n), size = land.add((int64_t*)nullptr, n),
               level_label = land.add((int64_t*)nullptr, (int64_t)max_levels * n);
     if (!rc) rc = land.reserve(ctx);
     if (rc) return rc;
-    if ((rc = graph_upload(ctx, w, indptr_host, col_host, sim_host, valid_host_or_null, n, nnz))) return rc;
-    in.indptr = w.d_indptr.get();
-    in.col = w.d_col.get();
-    in.sim = w.d_sim.get();
-    in.valid = valid_host_or_null ? w.d_valid.get() : nullptr;
+    if ((rc = graph_upload(ctx, w.graph, in))) return rc;
     const CommOut dev = {land.dev<int64_t>(label), land.dev<int64_t>(size), land.dev<int64_t>(level_label)};
     if ((rc = communities_run(ctx, fn, in, dev, h))) return rc;
     GNN_HIP(hipMemcpyAsync(label_host, dev.label, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -1145,7 +879,7 @@ extern "C" int gnn_label_components_dev(gnn_ctx* ctx, const int64_t* indptr_dev,
     if (int rc = components_check(fn, indptr_dev, col_dev, sim_dev, n, nnz, label_dev, out_dev)) return rc;
     if (int rc = check_ctx(ctx)) return rc;
     if (n == 0) return GNN_OK;
-    return components_run(ctx, fn, indptr_dev, col_dev, sim_dev, valid_dev_or_null, n, nnz, label_dev, out_dev);
+    return components_run(ctx, fn, {indptr_dev, col_dev, sim_dev, valid_dev_or_null, n, nnz}, label_dev, out_dev);
 }
 
 extern "C" int gnn_label_components(gnn_ctx* ctx, const int64_t* indptr_host, const int32_t* col_host, const float* sim_host,
@@ -1155,40 +889,33 @@ extern "C" int gnn_label_components(gnn_ctx* ctx, const int64_t* indptr_host, co
     if (int rc = check_ctx(ctx)) return rc;
     if (n == 0) return GNN_OK;
     CommunitiesWorkspace& w = ctx->cmt;
-    int rc = graph_reserve(ctx, w, n, nnz);
+    int rc = graph_reserve(ctx, w.graph, n, nnz);
     Landing land(w.d_out);
     const int label = land.add((int64_t*)nullptr, n), out = land.add(out_host, n);
     if (!rc) rc = land.reserve(ctx);
     if (rc) return rc;
-    if ((rc = graph_upload(ctx, w, indptr_host, col_host, sim_host, valid_host_or_null, n, nnz))) return rc;
+    CsrGraph g = {indptr_host, col_host, sim_host, valid_host_or_null, n, nnz};
+    if ((rc = graph_upload(ctx, w.graph, g))) return rc;
     GNN_HIP(hipMemcpyAsync(land.dev<int64_t>(label), label_host, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = components_run(ctx, fn, w.d_indptr.get(), w.d_col.get(), w.d_sim.get(), valid_host_or_null ? w.d_valid.get() : nullptr, n, nnz,
-                             land.dev<int64_t>(label), land.dev<int64_t>(out))))
-        return rc;
+    if ((rc = components_run(ctx, fn, g, land.dev<int64_t>(label), land.dev<int64_t>(out)))) return rc;
     return land.copy_out(ctx);
 }
 
 extern "C" int gnn_debug_communities_slots(gnn_ctx* ctx, int slots) {
-    return ctx ? communities_knob(ctx, "gnn_debug_communities_slots", &ctx->cmt.slots, slots) : check_ctx(ctx);
+    return rt_knob(ctx, "gnn_debug_communities_slots", ctx ? &ctx->cmt.table.slots : nullptr, slots);
 }
 
 extern "C" int gnn_debug_communities_wave_rows(gnn_ctx* ctx, int entries) {
-    return ctx ? communities_knob(ctx, "gnn_debug_communities_wave_rows", &ctx->cmt.wave_rows, entries) : check_ctx(ctx);
+    return rt_knob(ctx, "gnn_debug_communities_wave_rows", ctx ? &ctx->cmt.table.wave_rows : nullptr, entries);
 }
 
 extern "C" int gnn_debug_communities_groups(gnn_ctx* ctx, int groups) {
-    if (int rc = check_ctx(ctx)) return rc;
-    if (groups < 0 || groups > 65535) {
-        set_error("gnn_debug_communities_groups: " + std::to_string(groups) + " workgroups is outside [0, 65535]");
-        return GNN_ERR_ARG;
-    }
-    ctx->cmt.groups = groups;
-    return GNN_OK;
+    return rt_set_groups(ctx, "gnn_debug_communities_groups", ctx ? &ctx->cmt.table.groups : nullptr, groups);
 }
 
 extern "C" int gnn_debug_communities_gain(gnn_ctx* ctx, const uint64_t* operands_host, int64_t n, uint64_t* out_host) {
     const char* const fn = "gnn_debug_communities_gain";
-    if (n < 0 || n > N_MAX) {
+    if (n < 0 || n > CSR_N_MAX) {
         set_error(std::string(fn) + ": n " + std::to_string(n) + " is outside [0, 2^24]");
         return GNN_ERR_ARG;
     }

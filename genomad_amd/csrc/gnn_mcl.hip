@@ -2,8 +2,8 @@
 // throughout - the definition is sequence.markov_clusters, and every output here equals it bit for bit.  ONE = 2^30 is a column's flow,
 // W = 2^24 a similarity of 1.  The matrix has a fixed width of `select` entries per column (idx int32, val uint32, rows ascending) and a
 // length per column, and is double buffered.
-//   validate, symmetrise   gnn_csr_sym.h, shared with gnn_spread.hip.  A row's entries stand in arrival order: nothing downstream
-//                depends on it - the table is keyed by row index, and prune has a strict order.
+//   validate, symmetrise   gnn_csr_sym.h, shared with the other consumers of the graph.  A row's entries stand in arrival order:
+//                nothing downstream depends on it - the table is keyed by row index, and prune has a strict order.
 //   initial      mc_lds_kernel<true>: column j = prune(its edges' weights - of parallel edges the largest - and its loop).
 //   iteration    mc_lds_kernel<false>, one launch per iteration: workgroups loop over columns.  The products p_ik * p_kj of column j
 //                are added into an LDS table keyed by i: open addressing, the slot claimed by a compare-and-swap, the value a 64-bit
@@ -29,7 +29,6 @@ namespace {
 
 typedef unsigned long long ull;
 
-constexpr int64_t N_MAX = (int64_t)1 << 24;      // a row index has 24 bits in the selection's key
 constexpr int SELECT_MAX = 1024;                 // the sort buffer
 constexpr int PRECISION_MAX = 1 << 20;
 constexpr int MAX_ITER_MAX = 10000;
@@ -489,12 +488,7 @@ __global__ __launch_bounds__(256) void mc_summarise_kernel(int64_t n, int select
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 
-struct MclIn {
-    const int64_t* indptr;     // device
-    const int32_t* col;
-    const float* sim;
-    const uint8_t* valid;      // device, or NULL: every row
-    int64_t n, nnz;
+struct MclIn : CsrGraph {       // the graph on the device
     int a4, select, precision, max_iter;
 };
 
@@ -503,8 +497,7 @@ int check_mcl_args(const std::string& f, int64_t n, int64_t nnz, int a4, int sel
         set_error(f + ": " + what + " " + std::to_string(v) + " is outside " + range);
         return GNN_ERR_ARG;
     };
-    if (n < 0 || n > N_MAX) return bad("n", n, "[0, 2^24]");
-    if (nnz < 0) return bad("nnz", nnz, "[0, 2^63)");
+    if (int rc = graph_check(f, n, nnz)) return rc;
     if (a4 < 5 || a4 > 32) return bad("inflation_quarters", a4, "[5, 32]: the inflation is a multiple of 0.25 in [1.25, 8]");
     if (select < 1 || select > SELECT_MAX) return bad("select", select, "[1, 1024]");
     if (precision < 1 || precision > PRECISION_MAX) return bad("precision", precision, "[1, 2^20]");
@@ -535,15 +528,7 @@ int mcl_run(gnn_ctx* ctx, const char* fn, const MclIn& in, int64_t* label, int64
     if (rc) return rc;
     {
         PassLog::Scope setup(ctx, m.passes);                  // open across the read below: nothing is settled there
-        if ((rc = launch_1d(mc_validate_kernel, n, ctx->stream, n, in.nnz, in.indptr, in.col, in.sim, in.valid, m.ok.get(), m.count.dev() + flag)))
-            return rc;
-        ull bad = 0;
-        if ((rc = m.count.read(ctx, flag, 1, &bad))) return rc;
-        if (bad) {
-            set_error(std::string(fn) + ": the graph is no upper-triangle CSR of " + std::to_string(n) + " rows and " + std::to_string(in.nnz) +
-                      " entries with similarities below 64: indptr must rise from 0 to nnz, a row's col lie in (row, n), sim be finite");
-            return GNN_ERR_ARG;
-        }
+        if ((rc = graph_validate(ctx, fn, in, m.ok.get(), m.count, flag))) return rc;
         for (int b = 0; b < 2 && !rc; ++b) {
             rc = nn_reserve(ctx, m.len[b], (size_t)n);
             if (!rc) rc = nn_reserve(ctx, m.idx[b], cells);
@@ -670,7 +655,7 @@ extern "C" int gnn_mcl_dev(gnn_ctx* ctx, const int64_t* indptr_dev, const int32_
                            int64_t* size_dev, int64_t* attractor_dev, uint32_t* flow_dev, uint8_t* is_attractor_dev, int64_t* changed_host,
                            int64_t* iterations_host, int* converged_host) {
     const char* const fn = "gnn_mcl_dev";
-    const MclIn in = {indptr_dev, col_dev, sim_dev, valid_dev_or_null, n, nnz, inflation_quarters, select, precision, max_iter};
+    const MclIn in = {{indptr_dev, col_dev, sim_dev, valid_dev_or_null, n, nnz}, inflation_quarters, select, precision, max_iter};
     if (int rc = mcl_check(fn, in, label_dev, size_dev, attractor_dev, flow_dev, is_attractor_dev, changed_host, iterations_host, converged_host))
         return rc;
     if (int rc = check_ctx(ctx)) return rc;
@@ -686,7 +671,7 @@ extern "C" int gnn_mcl(gnn_ctx* ctx, const int64_t* indptr_host, const int32_t* 
                        int64_t* size_host, int64_t* attractor_host, uint32_t* flow_host, uint8_t* is_attractor_host, int64_t* changed_host,
                        int64_t* iterations_host, int* converged_host) {
     const char* const fn = "gnn_mcl";
-    MclIn in = {indptr_host, col_host, sim_host, valid_host_or_null, n, nnz, inflation_quarters, select, precision, max_iter};
+    MclIn in = {{indptr_host, col_host, sim_host, valid_host_or_null, n, nnz}, inflation_quarters, select, precision, max_iter};
     if (int rc = mcl_check(fn, in, label_host, size_host, attractor_host, flow_host, is_attractor_host, changed_host, iterations_host,
                            converged_host))
         return rc;
@@ -698,25 +683,13 @@ extern "C" int gnn_mcl(gnn_ctx* ctx, const int64_t* indptr_host, const int32_t* 
     MclWorkspace& m = ctx->mcl;
     m.have = false;
     // every buffer stands before a copy is enqueued.  d_out: [label | size | attractor | flow (u32) | is_attractor (u8)]
-    int rc = nn_reserve(ctx, m.d_indptr, (size_t)n + 1);
-    if (!rc) rc = nn_reserve(ctx, m.d_col, (size_t)std::max<int64_t>(nnz, 1));
-    if (!rc) rc = nn_reserve(ctx, m.d_sim, (size_t)std::max<int64_t>(nnz, 1));
-    if (!rc) rc = nn_reserve(ctx, m.d_valid, (size_t)n);
+    int rc = graph_reserve(ctx, m.graph, n, nnz);
     Landing land(m.d_out);
     const int label = land.add(label_host, n), size = land.add(size_host, n), attractor = land.add(attractor_host, n),
               flow = land.add(flow_host, n), is_attractor = land.add(is_attractor_host, n);
     if (!rc) rc = land.reserve(ctx);
     if (rc) return rc;
-    GNN_HIP(hipMemcpyAsync(m.d_indptr.get(), indptr_host, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (nnz > 0) {
-        GNN_HIP(hipMemcpyAsync(m.d_col.get(), col_host, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        GNN_HIP(hipMemcpyAsync(m.d_sim.get(), sim_host, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (valid_host_or_null) GNN_HIP(hipMemcpyAsync(m.d_valid.get(), valid_host_or_null, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    in.indptr = m.d_indptr.get();
-    in.col = m.d_col.get();
-    in.sim = m.d_sim.get();
-    in.valid = valid_host_or_null ? m.d_valid.get() : nullptr;
+    if ((rc = graph_upload(ctx, m.graph, in))) return rc;
     rc = mcl_run(ctx, fn, in, land.dev<int64_t>(label), land.dev<int64_t>(size), land.dev<int64_t>(attractor), land.dev<uint32_t>(flow),
                  land.dev<uint8_t>(is_attractor), changed_host, iterations_host, converged_host);
     return rc ? rc : land.copy_out(ctx);

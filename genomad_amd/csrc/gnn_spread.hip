@@ -1,8 +1,8 @@
 // Label spreading over a similarity graph (include/genomad_nn.h, "label spreading"): the labels of seed rows
 // spread along the graph's edges until nothing changes, in integers throughout - the definition is sequence.label_spread, and every
 // output here equals it bit for bit.  ONE = 2^30 is a score of 1, 2^31 a row's transition mass, W = 2^24 a similarity of 1.
-//   validate, symmetrise   gnn_csr_sym.h, shared with gnn_mcl.hip; a second flag bit is a label outside [-1, n_classes).  The host reads
-//                one word; GNN_ERR_ARG before anything else runs, the outputs untouched.
+//   validate, symmetrise   gnn_csr_sym.h, shared with the other consumers of the graph; a second flag bit is a label outside
+//                [-1, n_classes).  The host reads one word; GNN_ERR_ARG before anything else runs, the outputs untouched.
 //   convert      one wave per row: d = the sum of the row's q (integer adds, a shuffle reduction), then p = (q << 31) / d in place of
 //                q - the one 64-bit division per entry.  The rows an iteration has to compute - valid, with entries, no clamped seed -
 //                are pushed on one of two lists: a row of up to LONG_ROW entries is a wave's work, a longer one a workgroup's.  A row
@@ -30,7 +30,6 @@ namespace {
 
 typedef unsigned long long ull;
 
-constexpr int64_t N_MAX = (int64_t)1 << 24;      // the graph's limit (gnn_mcl)
 constexpr int CLASSES_MAX = 1024;                // gnn_vote's
 constexpr int MAX_ITER_MAX = 10000;
 constexpr int LONG_ROW = 1024;                   // a row of more entries is a workgroup's work
@@ -232,13 +231,8 @@ __global__ __launch_bounds__(THREADS) void sp_summarise_kernel(int64_t n, int C,
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 
-struct SpreadIn {
-    const int64_t* indptr;     // device
-    const int32_t* col;
-    const float* sim;
-    const uint8_t* valid;      // device, or NULL: every row
+struct SpreadIn : CsrGraph {    // the graph on the device
     const int64_t* label;      // device
-    int64_t n, nnz;
     int C, a, clamp, max_iter;
 };
 
@@ -257,8 +251,7 @@ int spread_check(const char* fn, const SpreadIn& in, const SpreadOut& out, const
         set_error(f + ": " + what + " " + std::to_string(v) + " is outside " + range);
         return GNN_ERR_ARG;
     };
-    if (in.n < 0 || in.n > N_MAX) return bad("n", in.n, "[0, 2^24]");
-    if (in.nnz < 0) return bad("nnz", in.nnz, "[0, 2^63)");
+    if (int rc = graph_check(f, in.n, in.nnz)) return rc;
     if (in.C < 1 || in.C > CLASSES_MAX) return bad("n_classes", in.C, "[1, 1024]");
     if (in.a < 1 || in.a > 63) return bad("alpha_64ths", in.a, "[1, 63]: alpha is a multiple of 1/64 in (0, 1)");
     if (in.max_iter < 1 || in.max_iter > MAX_ITER_MAX) return bad("max_iter", in.max_iter, "[1, 10000]");
@@ -290,16 +283,10 @@ int spread_run(gnn_ctx* ctx, const char* fn, const SpreadIn& in, const SpreadOut
     if (rc) return rc;
     {
         PassLog::Scope setup(ctx, w.passes);                  // open across the read below: nothing is settled there
-        if ((rc = launch_1d(mc_validate_kernel, n, ctx->stream, n, in.nnz, in.indptr, in.col, in.sim, in.valid, w.ok.get(), w.count.dev() + tail + 2)))
-            return rc;
+        if ((rc = graph_validate_launch(ctx, in, w.ok.get(), w.count, tail + 2))) return rc;
         if ((rc = launch_1d(sp_seed_kernel, n, ctx->stream, n, in.C, in.label, w.ok.get(), w.seed.get(), w.count.dev() + tail + 2))) return rc;
         ull bad = 0;
-        if ((rc = w.count.read(ctx, tail + 2, 1, &bad))) return rc;
-        if (bad & 1) {
-            set_error(std::string(fn) + ": the graph is no upper-triangle CSR of " + std::to_string(n) + " rows and " + std::to_string(in.nnz) +
-                      " entries with similarities below 64: indptr must rise from 0 to nnz, a row's col lie in (row, n), sim be finite");
-            return GNN_ERR_ARG;
-        }
+        if ((rc = graph_verdict(ctx, fn, in, w.count, tail + 2, &bad))) return rc;
         if (bad) {
             set_error(std::string(fn) + ": a label is outside [-1, " + std::to_string(in.C) + ")");
             return GNN_ERR_ARG;
@@ -399,7 +386,7 @@ extern "C" int gnn_spread_dev(gnn_ctx* ctx, const int64_t* indptr_dev, const int
                               uint32_t* score_dev_or_null, int32_t* best_dev, uint32_t* best_score_dev, uint32_t* second_score_dev,
                               uint64_t* total_dev, int32_t* first_dev, int64_t* changed_host, int64_t* iterations_host, int* converged_host) {
     const char* const fn = "gnn_spread_dev";
-    const SpreadIn in = {indptr_dev, col_dev, sim_dev, valid_dev_or_null, label_dev, n, nnz, n_classes, alpha_64ths, clamp != 0, max_iter};
+    const SpreadIn in = {{indptr_dev, col_dev, sim_dev, valid_dev_or_null, n, nnz}, label_dev, n_classes, alpha_64ths, clamp != 0, max_iter};
     const SpreadOut out = {score_dev_or_null, best_dev, best_score_dev, second_score_dev, reinterpret_cast<ull*>(total_dev), first_dev};
     if (int rc = spread_check(fn, in, out, changed_host, iterations_host, converged_host)) return rc;
     if (int rc = check_ctx(ctx)) return rc;
@@ -419,7 +406,7 @@ extern "C" int gnn_spread(gnn_ctx* ctx, const int64_t* indptr_host, const int32_
                           uint32_t* score_host_or_null, int32_t* best_host, uint32_t* best_score_host, uint32_t* second_score_host,
                           uint64_t* total_host, int32_t* first_host, int64_t* changed_host, int64_t* iterations_host, int* converged_host) {
     const char* const fn = "gnn_spread";
-    SpreadIn in = {indptr_host, col_host, sim_host, valid_host_or_null, label_host, n, nnz, n_classes, alpha_64ths, clamp != 0, max_iter};
+    SpreadIn in = {{indptr_host, col_host, sim_host, valid_host_or_null, n, nnz}, label_host, n_classes, alpha_64ths, clamp != 0, max_iter};
     const SpreadOut host = {score_host_or_null, best_host, best_score_host, second_score_host, reinterpret_cast<ull*>(total_host), first_host};
     if (int rc = spread_check(fn, in, host, changed_host, iterations_host, converged_host)) return rc;
     if (int rc = check_ctx(ctx)) return rc;
@@ -429,27 +416,15 @@ extern "C" int gnn_spread(gnn_ctx* ctx, const int64_t* indptr_host, const int32_
     }
     SpreadWorkspace& w = ctx->sprd;
     // every buffer stands before a copy is enqueued.  d_out: [best (i32) | best_score (u32) | second_score (u32) | total (u64) | first (i32)]
-    int rc = nn_reserve(ctx, w.d_indptr, (size_t)n + 1);
-    if (!rc) rc = nn_reserve(ctx, w.d_col, (size_t)std::max<int64_t>(nnz, 1));
-    if (!rc) rc = nn_reserve(ctx, w.d_sim, (size_t)std::max<int64_t>(nnz, 1));
-    if (!rc) rc = nn_reserve(ctx, w.d_valid, (size_t)n);
+    int rc = graph_reserve(ctx, w.graph, n, nnz);
     if (!rc) rc = nn_reserve(ctx, w.d_label, (size_t)n);
     Landing land(w.d_out);
     const int best = land.add(best_host, n), best_score = land.add(best_score_host, n), second_score = land.add(second_score_host, n),
               total = land.add(host.total, n), first = land.add(first_host, n);
     if (!rc) rc = land.reserve(ctx);
     if (rc) return rc;
-    GNN_HIP(hipMemcpyAsync(w.d_indptr.get(), indptr_host, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (nnz > 0) {
-        GNN_HIP(hipMemcpyAsync(w.d_col.get(), col_host, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        GNN_HIP(hipMemcpyAsync(w.d_sim.get(), sim_host, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (valid_host_or_null) GNN_HIP(hipMemcpyAsync(w.d_valid.get(), valid_host_or_null, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = graph_upload(ctx, w.graph, in))) return rc;
     GNN_HIP(hipMemcpyAsync(w.d_label.get(), label_host, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    in.indptr = w.d_indptr.get();
-    in.col = w.d_col.get();
-    in.sim = w.d_sim.get();
-    in.valid = valid_host_or_null ? w.d_valid.get() : nullptr;
     in.label = w.d_label.get();
     const SpreadOut dev = {nullptr, land.dev<int32_t>(best), land.dev<uint32_t>(best_score), land.dev<uint32_t>(second_score), land.dev<ull>(total),
                            land.dev<int32_t>(first)};

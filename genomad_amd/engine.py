@@ -1342,19 +1342,15 @@ class NNEngine:
         k, m, w = self._knn_graph_codes(k, mode, weight)
         check(self.lib.gnn_knn_graph_fill_dev(self.ctx, int(n), k, m, w, self._knn_metric(metric), col_ptr, sim_ptr, mutual_ptr, int(capacity)))
 
-    def _knn_graph_knob(self, fn, value) -> int:
-        check(fn(self.ctx, int(value)))
-        return int(value)
-
     def set_knn_graph_wave_rows(self, entries: int) -> int:
         """test aid (``gnn_debug_knn_graph_wave_rows``): the longest row one wave orders, 1..64 (the default 64); no result depends on
         it."""
-        return self._knn_graph_knob(self.lib.gnn_debug_knn_graph_wave_rows, entries)
+        return self._knob(self.lib.gnn_debug_knn_graph_wave_rows, entries, answers_before=False)
 
     def set_knn_graph_group_rows(self, entries: int) -> int:
         """test aid (``gnn_debug_knn_graph_group_rows``): the longest row a workgroup orders in LDS, 1..4096 (the default 2048); no
         result depends on it."""
-        return self._knn_graph_knob(self.lib.gnn_debug_knn_graph_group_rows, entries)
+        return self._knob(self.lib.gnn_debug_knn_graph_group_rows, entries, answers_before=False)
 
     def knn_graph_classes(self) -> np.ndarray:
         """measurement only (``gnn_debug_knn_graph_classes``): the rows the last count gave the [LDS, radix] class"""
@@ -1454,9 +1450,33 @@ class NNEngine:
         :meth:`vote` / :meth:`vote_dev` call - [labels, then per slab of 262 144 queries: votes, finish]"""
         return self._debug_ms(self.lib.gnn_debug_vote_pass_ms)
 
+    # -- the similarity graph's consumers ---------------------------------------------------
+    @staticmethod
+    def _csr_arrays(indptr, col, sim, valid):
+        """the graph as the library takes it: (indptr, col, sim, valid as uint8 or None, n); a ``ValueError`` for arrays that are no CSR"""
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        with np.errstate(over="ignore"):
+            sim = np.ascontiguousarray(sim, dtype=np.float32)
+        n = len(indptr) - 1
+        if indptr.ndim != 1 or n < 0 or col.ndim != 1 or sim.shape != col.shape:
+            raise ValueError("indptr (n + 1,), col (nnz,) and sim (nnz,) are required")
+        ok = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+        if ok is not None and ok.shape != (n,):
+            raise ValueError(f"valid must have one entry per row ({n})")
+        return indptr, col, sim, ok, n
+
+    def _knob(self, fn, value, answers_before=True) -> int:
+        """a debug knob's setter: ``GnnError`` for a value out of range.  Returns what the library answers, the value before the call,
+        or - where it answers ``GNN_OK`` - the value set."""
+        rc = fn(self.ctx, int(value))
+        if rc < 0:
+            check(rc)
+        return int(rc) if answers_before else int(value)
+
     # -- Markov clusters -----------------------------------------------------------------
     @staticmethod
-    def _mcl_knobs(inflation, select, precision, max_iter):
+    def _mcl_params(inflation, select, precision, max_iter):
         """the four knobs as the library takes them; a ``ValueError`` for one out of range, before anything is allocated"""
         return (_sequence.mcl_inflation(inflation), _sequence._whole(select, "select", 1, _sequence.MCL_SELECT_MAX),
                 _sequence._whole(precision, "precision", 1, _sequence.MCL_PRECISION_MAX),
@@ -1477,17 +1497,8 @@ class NNEngine:
         every output equals the definition bit for bit.  ``valid``: bool per row (None: all); ``select`` (1..1024): the entries a
         column keeps at the most; ``precision`` (1..2^20): an entry below 1 / precision of its column is cut; ``max_iter`` (0..10000).
         ``ValueError`` for a knob out of range, ``GnnError`` for a graph that is no such CSR."""
-        knobs = self._mcl_knobs(inflation, select, precision, max_iter)
-        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
-        col = np.ascontiguousarray(col, dtype=np.int32)
-        with np.errstate(over="ignore"):
-            sim = np.ascontiguousarray(sim, dtype=np.float32)
-        n = len(indptr) - 1
-        if indptr.ndim != 1 or n < 0 or col.ndim != 1 or sim.shape != col.shape:
-            raise ValueError("indptr (n + 1,), col (nnz,) and sim (nnz,) are required")
-        ok = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
-        if ok is not None and ok.shape != (n,):
-            raise ValueError(f"valid must have one entry per row ({n})")
+        knobs = self._mcl_params(inflation, select, precision, max_iter)
+        indptr, col, sim, ok, n = self._csr_arrays(indptr, col, sim, valid)
         out = [np.empty(n, dtype=np.int64) for _ in range(3)] + [np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint8)]
         kw = self._mcl_call(self.lib.gnn_mcl, (indptr.ctypes.data, col.ctypes.data, sim.ctypes.data, None if ok is None else ok.ctypes.data),
                             n, len(col), knobs, [a.ctypes.data for a in out], inflation)
@@ -1500,7 +1511,7 @@ class NNEngine:
         :meth:`graph_count_dev` and :meth:`graph_fill_dev` wrote them, valid (n uint8, or None) - and out (label, size, attractor: n
         int64 each; flow: n uint32; is_attractor: n uint8); the engine's stream is synchronised once per iteration.  Returns an
         :class:`MCLResult` without the per-row arrays."""
-        knobs = self._mcl_knobs(inflation, select, precision, max_iter)
+        knobs = self._mcl_params(inflation, select, precision, max_iter)
         return MCLResult(**self._mcl_call(self.lib.gnn_mcl_dev, (indptr_ptr, col_ptr, sim_ptr, valid_ptr), n, nnz, knobs,
                                           [label_ptr, size_ptr, attractor_ptr, flow_ptr, is_attractor_ptr], inflation))
 
@@ -1548,7 +1559,7 @@ class NNEngine:
                     n_classes=nc, alpha=float(alpha), clamp=bool(clamp))
 
     @staticmethod
-    def _spread_knobs(n_classes, alpha, clamp, max_iter):
+    def _spread_params(n_classes, alpha, clamp, max_iter):
         """the knobs as the library takes them; a ``ValueError`` for one out of range, before anything is allocated"""
         return (_sequence.vote_classes(n_classes), _sequence.spread_alpha(alpha), bool(clamp),
                 _sequence._whole(max_iter, "max_iter", 1, _sequence.SPREAD_MAX_ITER_MAX))
@@ -1562,17 +1573,8 @@ class NNEngine:
         matrix is not copied back (``score`` is None).  In integers throughout: every output equals the definition bit for bit.
         Random-walk rows, not the symmetric normalisation; no calibrated probability.  ``ValueError`` for a knob out of range,
         ``GnnError`` for a graph that is no such CSR."""
-        knobs = self._spread_knobs(n_classes, alpha, clamp, max_iter)
-        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
-        col = np.ascontiguousarray(col, dtype=np.int32)
-        with np.errstate(over="ignore"):
-            sim = np.ascontiguousarray(sim, dtype=np.float32)
-        n = len(indptr) - 1
-        if indptr.ndim != 1 or n < 0 or col.ndim != 1 or sim.shape != col.shape:
-            raise ValueError("indptr (n + 1,), col (nnz,) and sim (nnz,) are required")
-        ok = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
-        if ok is not None and ok.shape != (n,):
-            raise ValueError(f"valid must have one entry per row ({n})")
+        knobs = self._spread_params(n_classes, alpha, clamp, max_iter)
+        indptr, col, sim, ok, n = self._csr_arrays(indptr, col, sim, valid)
         lab = _sequence.vote_labels(label, n, knobs[0])
         score = np.empty((n, knobs[0]), dtype=np.uint32) if scores else None
         out = [np.empty(n, dtype=np.int32), np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint64),
@@ -1590,7 +1592,7 @@ class NNEngine:
         :meth:`graph_count_dev` and :meth:`graph_fill_dev` wrote them, label (n int64), valid (n uint8, or None) - and out (best,
         first: n int32; best_score, second_score: n uint32; total: n uint64; score: n x n_classes uint32, or None); the engine's
         stream is synchronised once per iteration.  Returns a :class:`SpreadResult` without the per-row arrays."""
-        knobs = self._spread_knobs(n_classes, alpha, clamp, max_iter)
+        knobs = self._spread_params(n_classes, alpha, clamp, max_iter)
         return SpreadResult(**self._spread_call(self.lib.gnn_spread_dev, (indptr_ptr, col_ptr, sim_ptr, valid_ptr, label_ptr), n, nnz, knobs,
                                                 [score_ptr, best_ptr, best_score_ptr, second_score_ptr, total_ptr, first_ptr], alpha))
 
@@ -1611,7 +1613,7 @@ class NNEngine:
 
     # -- average linkage -----------------------------------------------------------------
     @staticmethod
-    def _avglink_knobs(stop, max_rounds):
+    def _avglink_params(stop, max_rounds):
         """the knobs as the library takes them; a ``ValueError`` for one out of range, before anything is allocated"""
         return (_sequence.average_linkage_stop(stop), _sequence._whole(max_rounds, "max_rounds", 1, _sequence.AVGLINK_MAX_ROUNDS_MAX))
 
@@ -1632,17 +1634,8 @@ class NNEngine:
         ``stop``: a similarity in (0, 64), the smallest average that still merges; ``max_rounds`` (1..2^20).  In integers throughout:
         every output equals the definition bit for bit.  ``ValueError`` for a knob out of range, ``GnnError`` for a graph that is
         no such CSR."""
-        knobs = self._avglink_knobs(stop, max_rounds)
-        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
-        col = np.ascontiguousarray(col, dtype=np.int32)
-        with np.errstate(over="ignore"):
-            sim = np.ascontiguousarray(sim, dtype=np.float32)
-        n = len(indptr) - 1
-        if indptr.ndim != 1 or n < 0 or col.ndim != 1 or sim.shape != col.shape:
-            raise ValueError("indptr (n + 1,), col (nnz,) and sim (nnz,) are required")
-        ok = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
-        if ok is not None and ok.shape != (n,):
-            raise ValueError(f"valid must have one entry per row ({n})")
+        knobs = self._avglink_params(stop, max_rounds)
+        indptr, col, sim, ok, n = self._csr_arrays(indptr, col, sim, valid)
         parent, weight = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.uint64)
         size_a, size_b, rnd = (np.empty(n, dtype=np.int32) for _ in range(3))
         kw = self._avglink_call(self.lib.gnn_avglink, (indptr.ctypes.data, col.ctypes.data, sim.ctypes.data, None if ok is None else ok.ctypes.data),
@@ -1658,27 +1651,21 @@ class NNEngine:
         :meth:`graph_count_dev` and :meth:`graph_fill_dev` wrote them, valid (n uint8, or None) - and out, per node, written where
         the node was absorbed (parent: n int32, -1 for a node never absorbed; weight: n uint64; size_a, size_b, round: n int32); the
         engine's stream is synchronised once per round.  Returns an :class:`AverageLinkageResult` without the per-merge arrays."""
-        knobs = self._avglink_knobs(stop, max_rounds)
+        knobs = self._avglink_params(stop, max_rounds)
         return AverageLinkageResult(**self._avglink_call(self.lib.gnn_avglink_dev, (indptr_ptr, col_ptr, sim_ptr, valid_ptr), n, nnz, knobs,
                                                          [parent_ptr, weight_ptr, size_a_ptr, size_b_ptr, round_ptr]))
-
-    def _avglink_knob(self, fn, value) -> int:
-        before = fn(self.ctx, int(value))
-        if before < 0:
-            check(before)
-        return int(before)
 
     def set_average_linkage_slots(self, slots: int) -> int:
         """test aid (``gnn_debug_avglink_slots``): the slots (0..4096, the default) of the LDS table :meth:`average_linkage` sums a
         row's entries in - a row with more entries takes the accumulator in global memory, with 0 every row; -1 changes nothing.
         Returns the value before the call.  No result depends on it."""
-        return self._avglink_knob(self.lib.gnn_debug_avglink_slots, slots)
+        return self._knob(self.lib.gnn_debug_avglink_slots, slots)
 
     def set_average_linkage_wave_rows(self, entries: int) -> int:
         """test aid (``gnn_debug_avglink_wave_rows``): the longest upper bound (0..4096; the default is 256) of a row that one wave
         of :meth:`average_linkage` takes with its quarter of the table; 0: none; -1 changes nothing.  Returns the value before the
         call.  No result depends on it."""
-        return self._avglink_knob(self.lib.gnn_debug_avglink_wave_rows, entries)
+        return self._knob(self.lib.gnn_debug_avglink_wave_rows, entries)
 
     def set_average_linkage_groups(self, groups: int):
         """test aid (``gnn_debug_avglink_groups``): the workgroups of a contraction of :meth:`average_linkage` (0: the library's
@@ -1709,24 +1696,10 @@ class NNEngine:
 
     # -- modularity communities ------------------------------------------------------------
     @staticmethod
-    def _communities_knobs(resolution, max_levels, max_sweeps):
+    def _communities_params(resolution, max_levels, max_sweeps):
         """the knobs as the library takes them; a ``ValueError`` for one out of range, before anything is allocated"""
         return (_sequence.communities_resolution(resolution), _sequence._whole(max_levels, "max_levels", 1, _sequence.COMM_LEVELS_MAX),
                 _sequence._whole(max_sweeps, "max_sweeps", 1, _sequence.COMM_SWEEPS_MAX))
-
-    @staticmethod
-    def _csr_arrays(indptr, col, sim, valid):
-        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
-        col = np.ascontiguousarray(col, dtype=np.int32)
-        with np.errstate(over="ignore"):
-            sim = np.ascontiguousarray(sim, dtype=np.float32)
-        n = len(indptr) - 1
-        if indptr.ndim != 1 or n < 0 or col.ndim != 1 or sim.shape != col.shape:
-            raise ValueError("indptr (n + 1,), col (nnz,) and sim (nnz,) are required")
-        ok = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
-        if ok is not None and ok.shape != (n,):
-            raise ValueError(f"valid must have one entry per row ({n})")
-        return indptr, col, sim, ok, n
 
     def _communities_call(self, fn, graph, n, nnz, knobs, outs):
         r, max_levels, max_sweeps = knobs
@@ -1752,7 +1725,7 @@ class NNEngine:
         ``max_sweeps`` per level (1..2^20).  In integers throughout: every output equals the definition bit for bit.  Every community
         is connected (the split at a level's end), which is not Leiden's refinement: well-connectedness is not guaranteed.
         ``ValueError`` for a knob out of range, ``GnnError`` for a graph that is no such CSR or whose doubled weight reaches 2^58."""
-        knobs = self._communities_knobs(resolution, max_levels, max_sweeps)
+        knobs = self._communities_params(resolution, max_levels, max_sweeps)
         indptr, col, sim, ok, n = self._csr_arrays(indptr, col, sim, valid)
         label, size = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
         level_label = np.empty((knobs[1], n), dtype=np.int64)
@@ -1769,7 +1742,7 @@ class NNEngine:
         :meth:`graph_count_dev` and :meth:`graph_fill_dev` wrote them, valid (n uint8, or None) - and out: label and size (n int64
         each) and level_label (``max_levels`` x n int64, of which the first ``levels`` rows are written); the engine's stream is
         synchronised once per sweep.  Returns a :class:`CommunityResult` without the per-row arrays."""
-        knobs = self._communities_knobs(resolution, max_levels, max_sweeps)
+        knobs = self._communities_params(resolution, max_levels, max_sweeps)
         return CommunityResult(**self._communities_call(self.lib.gnn_communities_dev, (indptr_ptr, col_ptr, sim_ptr, valid_ptr), n, nnz, knobs,
                                                         [label_ptr, size_ptr, level_label_ptr]))
 
@@ -1796,13 +1769,13 @@ class NNEngine:
         """test aid (``gnn_debug_communities_slots``): the slots (0..4096, the default) of the LDS table :meth:`communities` sums a
         row's entries in - a longer row takes the accumulator in global memory, with 0 every row; -1 changes nothing.  Returns the
         value before the call.  No result depends on it."""
-        return self._avglink_knob(self.lib.gnn_debug_communities_slots, slots)
+        return self._knob(self.lib.gnn_debug_communities_slots, slots)
 
     def set_communities_wave_rows(self, entries: int) -> int:
         """test aid (``gnn_debug_communities_wave_rows``): the longest row (0..4096; the default is 256) that one wave of
         :meth:`communities` takes with its quarter of the table; 0: none; -1 changes nothing.  Returns the value before the call.
         No result depends on it."""
-        return self._avglink_knob(self.lib.gnn_debug_communities_wave_rows, entries)
+        return self._knob(self.lib.gnn_debug_communities_wave_rows, entries)
 
     def set_communities_groups(self, groups: int):
         """test aid (``gnn_debug_communities_groups``): the workgroups of a launch of :meth:`communities` (0: the library's

@@ -1,7 +1,7 @@
 """Average linkage on the MI355X: every array of NNEngine.average_linkage, rounds, merged_per_round and complete equal
 sequence.average_linkage bit for bit - on every fixture of tests/avglink_data.py, for every size of the LDS table (the library's, none,
 8, 64 slots), with and without rows taken by single waves, and for every number of workgroups; the 4 200-leaf star takes the
-accumulator in global memory at the library's own table size; the host and the device entry points agree; graph_count_dev ->
+accumulator in global memory at the library's own table size; rows exactly on a class border are filed by the class rule; the host and the device entry points agree; graph_count_dev ->
 graph_fill_dev -> average_linkage_dev never leaves the device; the order function is exact where 64 bits are not; bad arguments leave
 the outputs untouched."""
 import ctypes as C
@@ -9,9 +9,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from genomad_amd import _lib
+from genomad_amd import _lib, sequence
 from genomad_amd._lib import GnnError
 from tests import avglink_data as D
+from tests import row_table_data as B
 from tests.clusters_data import planted
 
 pytestmark = pytest.mark.gpu
@@ -89,6 +90,20 @@ def test_the_star_takes_the_accumulator_at_the_librarys_own_table_size(knobs):
         assert_equal(engine.average_linkage(*D.STAR, max_rounds=4), want, ("star", groups))
         classes = engine.average_linkage_classes()
         assert classes[2] == 4 and classes[0] == 4 * D.STAR_LEAVES - 6, classes      # the hub every round; the leaves not yet absorbed
+
+
+def test_a_row_on_a_class_border_is_filed_by_the_rule(knobs):
+    engine = knobs
+    assert defaults_of(engine) == (4096, 256)
+    for degrees, slots, wave_limit, classes in B.BORDERS:
+        csr, degree = B.stars(degrees)
+        assert len(degree) == sum(classes) and B.histogram(degree, slots, wave_limit) == classes
+        want = sequence.average_linkage(*csr, max_rounds=1)
+        engine.set_average_linkage_slots(4096 if slots < 0 else slots)
+        for groups in GROUPS:
+            engine.set_average_linkage_groups(groups)
+            assert_equal(engine.average_linkage(*csr, max_rounds=1), want, (degrees, groups))
+            assert engine.average_linkage_classes().tolist() == classes, (degrees, groups)
 
 
 def dev_call(engine, csr, valid, **kw):

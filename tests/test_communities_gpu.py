@@ -1,7 +1,7 @@
 """Modularity communities on the MI355X: every array of NNEngine.communities - label, size, level_label, the per-level counters and
 both words of qnum - equals sequence.modularity_communities bit for bit: on the three weight kinds at r = 16, 64, 160 and 256, the
 searched inputs with a rejected sweep and with a split community, invalid and empty rows, parallel entries, the big-hub star, one
-level and one sweep; for every size of the LDS table, with and without rows taken by single waves, and for every number of
+level and one sweep, rows exactly on a class border; for every size of the LDS table, with and without rows taken by single waves, and for every number of
 workgroups; the host and the device entry points agree; graph_count_dev -> graph_fill_dev -> communities_dev never leaves the
 device; gnn_label_components equals its definition; the gain and score arithmetic is exact in 128 bits at the stated bounds; bad
 arguments leave the outputs untouched."""
@@ -13,6 +13,7 @@ import pytest
 from genomad_amd import _lib, sequence
 from genomad_amd._lib import GnnError
 from tests import communities_data as D
+from tests import row_table_data as B
 from tests.clusters_data import planted
 
 pytestmark = pytest.mark.gpu
@@ -84,6 +85,20 @@ def test_every_table_size_wave_rule_and_grid_equals_the_definition(knobs, name):
 def test_the_searched_inputs_reach_the_rare_paths():
     assert D.reference("rejected", D.REJECTED["resolution"])["rejected"].any()
     assert D.reference("split", D.SPLIT["resolution"])["split"].any()
+
+
+def test_a_row_on_a_class_border_is_filed_by_the_rule(knobs):
+    engine = knobs
+    assert (engine.set_communities_slots(-1), engine.set_communities_wave_rows(-1)) == (4096, 256)
+    for degrees, slots, wave_limit, classes in B.BORDERS:
+        csr, degree = B.stars(degrees)
+        assert len(degree) == sum(classes) and B.histogram(degree, slots, wave_limit) == classes
+        want = sequence.modularity_communities(*csr, max_levels=1, max_sweeps=1)
+        engine.set_communities_slots(4096 if slots < 0 else slots)
+        for groups in GROUPS:
+            engine.set_communities_groups(groups)
+            assert_equal(engine.communities(*csr, max_levels=1, max_sweeps=1), want, (degrees, groups))
+            assert engine.communities_classes()[:3].tolist() == classes, (degrees, groups)
 
 
 def test_the_star_takes_the_accumulator_at_the_librarys_own_table_size(knobs):
