@@ -100,8 +100,7 @@ class RegionResult(_Result):
     @classmethod
     def build(cls, penalty, bin_offsets, state, regions, offsets=None, stride=None):
         """from the output of ``sequence.call_regions`` or the library; the table where ``offsets`` and ``stride`` are given"""
-        from . import sequence as S
-        table = S.region_table(regions, offsets, stride) if offsets is not None and stride is not None else {}
+        table = _sequence.region_table(regions, offsets, stride) if offsets is not None and stride is not None else {}
         return cls(penalty=float(penalty), bin_offsets=bin_offsets, state=state, **{"region_" + k: v for k, v in regions.items()},
                    stride=None if stride is None else int(stride), **table)
 
@@ -133,15 +132,13 @@ class ClusterResult(_Result):
 
     def table(self, names=None):
         """``sequence.cluster_table``: one record per cluster, ordered by label"""
-        from . import sequence as S
-        return S.cluster_table(self, names)
+        return _sequence.cluster_table(self, names)
 
     @classmethod
     def build(cls, arrays, threshold, metric):
         """from the four arrays of ``sequence.threshold_clusters`` or the library"""
-        from . import sequence as S
         label, degree, size, rep = arrays
-        return cls(label=label, degree=degree, size=size, rep=rep, threshold=float(S.cluster_threshold(threshold)), metric=str(metric))
+        return cls(label=label, degree=degree, size=size, rep=rep, threshold=float(_sequence.cluster_threshold(threshold)), metric=str(metric))
 
 
 class DensityResult(_Result):
@@ -170,16 +167,14 @@ class DensityResult(_Result):
 
     def table(self, names=None):
         """``sequence.density_table``: one record per cluster, ordered by label"""
-        from . import sequence as S
-        return S.density_table(self, names)
+        return _sequence.density_table(self, names)
 
     @classmethod
     def build(cls, arrays, threshold, min_points, metric):
         """from the six arrays of ``sequence.density_clusters`` or the library"""
-        from . import sequence as S
         label, degree, size, anchor, sim, kind = arrays
         return cls(label=label, degree=degree, size=size, anchor=anchor, sim=sim, kind=kind,
-                   threshold=float(S.cluster_threshold(threshold)), min_points=int(min_points), metric=str(metric))
+                   threshold=float(_sequence.cluster_threshold(threshold)), min_points=int(min_points), metric=str(metric))
 
 
 class KMeansResult(_Result):
@@ -200,8 +195,7 @@ class KMeansResult(_Result):
 
     def table(self, names=None):
         """``sequence.kmeans_table``: one record per cluster, by cluster index"""
-        from . import sequence as S
-        return S.kmeans_table(self, names)
+        return _sequence.kmeans_table(self, names)
 
     @classmethod
     def build(cls, arrays):
@@ -234,8 +228,7 @@ class PCAResult(_Result):
 
     def table(self, names=None):
         """``sequence.pca_table``: one record per row"""
-        from . import sequence as S
-        return S.pca_table(self.projection, self.valid, names)
+        return _sequence.pca_table(self.projection, self.valid, names)
 
 
 class RepresentativeResult(_Result):
@@ -256,15 +249,13 @@ class RepresentativeResult(_Result):
 
     def table(self, names=None):
         """``sequence.representative_table``: one record per cluster, ordered by the representative's rank"""
-        from . import sequence as S
-        return S.representative_table(self, names)
+        return _sequence.representative_table(self, names)
 
     @classmethod
     def build(cls, arrays, threshold, metric):
         """from the (rep, sim, size, rank, rounds) of ``sequence.greedy_representatives`` or the library"""
-        from . import sequence as S
         rep, sim, size, rank, rounds = arrays
-        return cls(rep=rep, sim=sim, size=size, rank=rank, rounds=int(rounds), threshold=float(S.cluster_threshold(threshold)),
+        return cls(rep=rep, sim=sim, size=size, rank=rank, rounds=int(rounds), threshold=float(_sequence.cluster_threshold(threshold)),
                    metric=str(metric))
 
 
@@ -280,27 +271,23 @@ class LinkageResult(_Result):
 
     def cut(self, threshold) -> np.ndarray:
         """``sequence.linkage_cut``: the ``label`` of :meth:`NNEngine.cluster` at ``threshold``"""
-        from . import sequence as S
-        return S.linkage_cut(self.a, self.b, self.sim, self.valid, threshold)
+        return _sequence.linkage_cut(self.a, self.b, self.sim, self.valid, threshold)
 
     def cluster_counts(self, thresholds) -> np.ndarray:
         """``sequence.linkage_cluster_counts``: the clusters a cut leaves at each threshold"""
-        from . import sequence as S
-        return S.linkage_cluster_counts(self.sim, self.n_valid, thresholds)
+        return _sequence.linkage_cluster_counts(self.sim, self.n_valid, thresholds)
 
     def matrix(self) -> np.ndarray:
         """``sequence.linkage_matrix``: SciPy's convention, distance = 1 - sim; cosine, all rows valid and a spanning tree only"""
-        from . import sequence as S
         if self.metric != "cosine":
             raise ValueError(f"metric {self.metric!r}: 1 - sim is a distance under cosine only")
         if self.n_valid != self.n:
             raise ValueError(f"{self.n - self.n_valid} of {self.n} rows are invalid: a linkage matrix needs every row")
-        return S.linkage_matrix(self.a, self.b, self.sim, self.n)
+        return _sequence.linkage_matrix(self.a, self.b, self.sim, self.n)
 
     def table(self, names=None):
         """``sequence.linkage_table``: one record per merge - rank, a, b, sim, clusters left"""
-        from . import sequence as S
-        return S.linkage_table(self.a, self.b, self.sim, self.n_valid, names)
+        return _sequence.linkage_table(self.a, self.b, self.sim, self.n_valid, names)
 
     @classmethod
     def build(cls, arrays, metric, rounds=0):
@@ -323,36 +310,31 @@ class DensityTreeResult(_Result):
     def cut(self, threshold) -> np.ndarray:
         """``sequence.density_tree_cut``: the ``label`` of :meth:`NNEngine.density` at (``threshold``, ``min_points``) at its core
         rows, -1 at every other row"""
-        from . import sequence as S
-        return S.density_tree_cut(self.a, self.b, self.sim, self.core, self.valid, threshold)
+        return _sequence.density_tree_cut(self.a, self.b, self.sim, self.core, self.valid, threshold)
 
     def cluster_counts(self, thresholds) -> np.ndarray:
         """``sequence.density_tree_cluster_counts``: the clusters of core rows a cut leaves at each threshold"""
-        from . import sequence as S
-        return S.density_tree_cluster_counts(self.sim, self.core, self.valid, thresholds)
+        return _sequence.density_tree_cluster_counts(self.sim, self.core, self.valid, thresholds)
 
     def hdbscan(self, min_cluster_size=5, allow_single_cluster=False) -> dict:
         """``sequence.hdbscan_clusters`` of this tree: ``label``, ``lambda_out`` and the cluster table.  Cosine only (1 - sim is a
         distance); a forest - which only ``dot`` can give - is a ValueError there."""
-        from . import sequence as S
         if self.metric != "cosine":
             raise ValueError(f"metric {self.metric!r}: 1 - sim is a distance under cosine only")
-        return S.hdbscan_clusters(self.a, self.b, self.sim, self.valid, min_cluster_size, allow_single_cluster)
+        return _sequence.hdbscan_clusters(self.a, self.b, self.sim, self.valid, min_cluster_size, allow_single_cluster)
 
     def matrix(self) -> np.ndarray:
         """``sequence.linkage_matrix`` of the mutual-reachability values: SciPy's convention, distance = 1 - sim; cosine, all rows
         valid and a spanning tree only"""
-        from . import sequence as S
         if self.metric != "cosine":
             raise ValueError(f"metric {self.metric!r}: 1 - sim is a distance under cosine only")
         if self.n_valid != self.n:
             raise ValueError(f"{self.n - self.n_valid} of {self.n} rows are invalid: a linkage matrix needs every row")
-        return S.linkage_matrix(self.a, self.b, self.sim, self.n)
+        return _sequence.linkage_matrix(self.a, self.b, self.sim, self.n)
 
     def table(self, names=None):
         """``sequence.linkage_table``: one record per merge - rank, a, b, sim, clusters left"""
-        from . import sequence as S
-        return S.linkage_table(self.a, self.b, self.sim, self.n_valid, names)
+        return _sequence.linkage_table(self.a, self.b, self.sim, self.n_valid, names)
 
     @classmethod
     def build(cls, arrays, min_points, metric, rounds=0):
@@ -2195,10 +2177,9 @@ class NNEngine:
                                precision=_lib.DEFAULT_PRECISION):
         """The same result assembled on the host from the span-level entry points (gnn_span_byte_count,
         gnn_classify_spans, gnn_segment_mean) — kept as an independently coded cross-check for the tests."""
-        from . import sequence as S
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n_contigs = len(offsets) - 1
-        starts, lens, ids, window_n = S.candidate_spans(offsets, single_window)
+        starts, lens, ids, window_n = _sequence.candidate_spans(offsets, single_window)
         if not len(starts):
             return np.zeros((n_contigs, _lib.CLASSES), np.float32), ids
         later = np.flatnonzero(window_n > 0)              # window 0 is never skipped (:70)
@@ -2208,7 +2189,7 @@ class NNEngine:
             counts = np.empty(len(later), dtype=np.int32)
             check(self.lib.gnn_span_byte_count(self.ctx, seq_ptr, st.ctypes.data, ln.ctypes.data, len(later),
                                                ord("N"), counts.ctypes.data))
-            keep[later[counts > S.MAX_N]] = False
+            keep[later[counts > _sequence.MAX_N]] = False
         starts, lens, ids = (np.ascontiguousarray(a[keep]) for a in (starts, lens, ids))
         scores = np.empty((len(starts), _lib.CLASSES), dtype=np.float32)
         check(self.lib.gnn_classify_spans(self.ctx, seq_ptr, starts.ctypes.data, lens.ctypes.data, len(starts),

@@ -720,6 +720,30 @@ def neighbour_k(k) -> int:
     return k
 
 
+def neighbour_metric(metric) -> str:
+    if metric not in NEIGHBOUR_METRICS:
+        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    return metric
+
+
+def _row_rule(r32, metric):
+    """(r float64 (n, 512), ok bool (n,)): the row rule of every definition below, stated in :func:`nearest_neighbours`.  A row is
+    valid iff every element is finite and, under ``cosine``, its norm is > 0; ``r`` holds zeros where the row is not valid, unit
+    vectors under ``cosine`` and the rows themselves under ``dot``."""
+    ok = np.isfinite(r32).all(axis=1)
+    r = np.where(ok[:, None], r32, 0).astype(np.float64)
+    if metric == "cosine":
+        norm = np.sqrt((r * r).sum(axis=1))
+        ok &= norm > 0
+        r = r / np.where(ok, norm, 1.0)[:, None]
+    return r, ok
+
+
+def _namer(names):
+    """i -> the int i where ``names`` is None, otherwise the str ``names[i]``: how every ``*_table`` names a row or a class"""
+    return (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+
+
 def nearest_neighbours(query, base=None, k=10, metric="cosine"):
     """Nearest neighbours among encoder embeddings, spelled out (the definition ``gnn_neighbours`` computes on the device; float64
     throughout, readable, not fast).  ``query`` (nq, 512) and ``base`` (nb, 512) are float32 rows; ``base=None`` is the self-search:
@@ -729,23 +753,12 @@ def nearest_neighbours(query, base=None, k=10, metric="cosine"):
     each row ordered by (similarity descending, base index ascending) and padded with idx = -1, sim = NaN where fewer than k
     candidates exist.  1 <= k <= 64."""
     k = neighbour_k(k)
-    if metric not in NEIGHBOUR_METRICS:
-        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    neighbour_metric(metric)
     q32 = neighbour_rows(query)
     self_search = base is None
     b32 = q32 if self_search else neighbour_rows(base, "base")
-
-    def unit(r32):
-        ok = np.isfinite(r32).all(axis=1)
-        r = np.where(ok[:, None], r32, 0).astype(np.float64)
-        if metric == "cosine":
-            norm = np.sqrt((r * r).sum(axis=1))
-            ok &= norm > 0
-            r = r / np.where(ok, norm, 1.0)[:, None]
-        return r, ok
-
-    q, q_ok = unit(q32)
-    b, b_ok = (q, q_ok) if self_search else unit(b32)
+    q, q_ok = _row_rule(q32, metric)
+    b, b_ok = (q, q_ok) if self_search else _row_rule(b32, metric)
     idx = np.full((len(q), k), -1, dtype=np.int64)
     sim = np.full((len(q), k), np.nan, dtype=np.float32)
     cand = np.flatnonzero(b_ok)
@@ -780,17 +793,11 @@ def threshold_clusters(rows, threshold, metric="cosine"):
     components (single linkage at the threshold), a valid row without an edge a cluster of one.  Returns four int64 arrays of n:
     ``label`` (the smallest index of the row's cluster), ``degree`` (edges at the row), ``size`` (rows of its cluster) and ``rep``
     (the member of its cluster with the largest degree, ties to the smallest index); an invalid row has -1, 0, 0, -1."""
-    if metric not in NEIGHBOUR_METRICS:
-        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    neighbour_metric(metric)
     r32 = neighbour_rows(rows, "rows")
     thr = float(cluster_threshold(threshold))
     n = len(r32)
-    ok = np.isfinite(r32).all(axis=1)
-    r = np.where(ok[:, None], r32, 0).astype(np.float64)
-    if metric == "cosine":
-        norm = np.sqrt((r * r).sum(axis=1))
-        ok &= norm > 0
-        r = r / np.where(ok, norm, 1.0)[:, None]
+    r, ok = _row_rule(r32, metric)
     adj = (r @ r.T >= thr) & ok[:, None] & ok[None, :]
     adj |= adj.T                        # x.y and y.x may differ in the last bit of a float64 sum: an edge either way is an edge
     adj[np.arange(n), np.arange(n)] = False
@@ -821,17 +828,10 @@ def threshold_graph(rows, threshold, metric="cosine"):
     sim(i, j) or sim(j, i) >= the float32 ``threshold`` rounds to.  Returns the upper triangle in CSR form: ``indptr`` (int64, n + 1),
     ``col`` (int32: row i owns ``col[indptr[i]:indptr[i + 1]]``, its partners j > i in ascending order; an invalid row owns nothing)
     and ``sim`` (float64: r[i] . r[j])."""
-    if metric not in NEIGHBOUR_METRICS:
-        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    neighbour_metric(metric)
     r32 = neighbour_rows(rows, "rows")
     thr = float(cluster_threshold(threshold))
-    n = len(r32)
-    ok = np.isfinite(r32).all(axis=1)
-    r = np.where(ok[:, None], r32, 0).astype(np.float64)
-    if metric == "cosine":
-        norm = np.sqrt((r * r).sum(axis=1))
-        ok &= norm > 0
-        r = r / np.where(ok, norm, 1.0)[:, None]
+    r, ok = _row_rule(r32, metric)
     s = r @ r.T
     adj = (s >= thr) & ok[:, None] & ok[None, :]
     adj |= adj.T                        # as threshold_clusters: an edge either way is an edge
@@ -844,14 +844,8 @@ def threshold_graph(rows, threshold, metric="cosine"):
 def valid_rows(rows, metric="cosine") -> np.ndarray:
     """bool (n,): the rows a search over encoder embeddings takes part with - every element finite and, under ``cosine``, a norm
     > 0 (:func:`nearest_neighbours`)"""
-    if metric not in NEIGHBOUR_METRICS:
-        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
-    r32 = neighbour_rows(rows, "rows")
-    ok = np.isfinite(r32).all(axis=1)
-    if metric == "cosine":
-        r = np.where(ok[:, None], r32, 0).astype(np.float64)
-        ok &= np.sqrt((r * r).sum(axis=1)) > 0
-    return ok
+    neighbour_metric(metric)
+    return _row_rule(neighbour_rows(rows, "rows"), metric)[1]
 
 
 def graph_edges(indptr, col):
@@ -880,32 +874,44 @@ def graph_symmetric(indptr, col, sim):
     return full, dst[order].astype(np.int32), np.concatenate([sim, sim])[order]
 
 
+def _find(root, x):
+    """The root of x in the union-find ``root`` - a list over the rows 0 .. n - 1 (a dict where the nodes are other keys), every
+    entry its own root at the start -, with path halving"""
+    while root[x] != x:                 # ends: a link points to a smaller index
+        root[x] = root[root[x]]
+        x = root[x]
+    return x
+
+
+def _join(root, x, y) -> bool:
+    """Joins the components of x and y, the larger root linked to the smaller - a root is its component's smallest member -, and
+    says whether they were two."""
+    x, y = _find(root, x), _find(root, y)
+    root[max(x, y)] = min(x, y)
+    return x != y
+
+
+def _root_labels(root, valid) -> np.ndarray:
+    """int64 (n,): the smallest member of every row's component in the union-find ``root``, -1 where ``valid`` is false"""
+    label = np.fromiter((_find(root, i) for i in range(len(root))), dtype=np.int64, count=len(root))
+    return np.where(np.asarray(valid, dtype=bool), label, -1)
+
+
 def graph_components(indptr, col, valid) -> np.ndarray:
     """int64 (n,): the smallest index of every row's connected component, -1 where ``valid`` is false - the ``label`` of
     :func:`threshold_clusters`.  A union-find whose links point to the smaller index, edge by edge."""
     a, b = graph_edges(indptr, col)
-    n = len(indptr) - 1
-    parent = list(range(n))
-
-    def root(x):
-        while parent[x] != x:           # ends: a link points to a smaller index
-            parent[x] = parent[parent[x]]
-            x = parent[x]
-        return x
-
+    root = list(range(len(indptr) - 1))
     for u, v in zip(a.tolist(), b.tolist()):
-        u, v = root(u), root(v)
-        if u != v:
-            parent[max(u, v)] = min(u, v)
-    label = np.fromiter((root(i) for i in range(n)), dtype=np.int64, count=n)
-    return np.where(np.asarray(valid, dtype=bool), label, -1)
+        _join(root, u, v)
+    return _root_labels(root, valid)
 
 
 def graph_table(indptr, col, sim, names=None):
     """One record per edge of an upper-triangle CSR, in its order: ``a`` < ``b`` (indices; the names where ``names`` is given) and
     ``sim``."""
     a, b = graph_edges(indptr, col)
-    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    name = _namer(names)
     return [{"a": name(i), "b": name(j), "sim": float(s)} for i, j, s in zip(a, b, np.asarray(sim))]
 
 
@@ -917,21 +923,10 @@ def threshold_matches(query, base, threshold, metric="cosine"):
     rounds to.  No pair is excluded: where query and base are the same rows, (i, i) and both orientations are there.  Returns the CSR
     by query row: ``indptr`` (int64, nq + 1), ``col`` (int32: query i owns ``col[indptr[i]:indptr[i + 1]]``, its base partners in
     ascending order; an invalid query owns nothing, an invalid base row is nobody's partner) and ``sim`` (float64)."""
-    if metric not in NEIGHBOUR_METRICS:
-        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    neighbour_metric(metric)
     q32, b32 = neighbour_rows(query), neighbour_rows(base, "base")
     thr = float(cluster_threshold(threshold))
-
-    def unit(r32):
-        ok = np.isfinite(r32).all(axis=1)
-        r = np.where(ok[:, None], r32, 0).astype(np.float64)
-        if metric == "cosine":
-            norm = np.sqrt((r * r).sum(axis=1))
-            ok &= norm > 0
-            r = r / np.where(ok, norm, 1.0)[:, None]
-        return r, ok
-
-    (q, q_ok), (b, b_ok) = unit(q32), unit(b32)
+    (q, q_ok), (b, b_ok) = _row_rule(q32, metric), _row_rule(b32, metric)
     s = q @ b.T
     hit = (s >= thr) & q_ok[:, None] & b_ok[None, :]
     i, j = np.nonzero(hit)              # row-major: queries in order, a query's partners ascending
@@ -970,8 +965,7 @@ def match_transpose(indptr, col, sim, n_base):
 def match_table(indptr, col, sim, query_names=None, base_names=None):
     """One record per match of a match CSR, in its order: ``query`` and ``base`` (indices; the names where given) and ``sim``."""
     a, b = graph_edges(indptr, col)
-    qn = (lambda i: int(i)) if query_names is None else (lambda i: str(query_names[int(i)]))
-    bn = (lambda i: int(i)) if base_names is None else (lambda i: str(base_names[int(i)]))
+    qn, bn = _namer(query_names), _namer(base_names)
     return [{"query": qn(i), "base": bn(j), "sim": float(s)} for i, j, s in zip(a, b, np.asarray(sim))]
 
 
@@ -1021,8 +1015,8 @@ def class_votes(query, base, label, n_classes, threshold, sims=None):
     if len(b32) > VOTE_BASE_MAX:
         raise ValueError(f"{len(b32)} base rows is outside [0, 2^30]")
     label = vote_labels(label, len(b32), n_classes)
-    q, q_ok = _unit_rows(q32)
-    b, b_ok = (q, q_ok) if self_form else _unit_rows(b32)
+    q, q_ok = _row_rule(q32, "cosine")
+    b, b_ok = (q, q_ok) if self_form else _row_rule(b32, "cosine")
     s = q @ b.T if sims is None else np.asarray(sims, dtype=np.float64)
     if s.shape != (len(q32), len(b32)):
         raise ValueError(f"sims has the shape {s.shape}: ({len(q32)}, {len(b32)}) is required")
@@ -1105,9 +1099,7 @@ def vote_table(count, weight, nearest, nearest_sim, names=None, class_names=None
     its name where ``base_names`` is given) and ``similarity`` (to that voter); None where there is no label."""
     label, confidence, _ = vote_predict(count, weight, rule, nearest_sim, min_votes)
     count = np.asarray(count, dtype=np.int64)
-    qn = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
-    cn = (lambda c: int(c)) if class_names is None else (lambda c: str(class_names[int(c)]))
-    bn = (lambda j: int(j)) if base_names is None else (lambda j: str(base_names[int(j)]))
+    qn, cn, bn = _namer(names), _namer(class_names), _namer(base_names)
     out = []
     for i, c in enumerate(label.tolist()):
         rec = {"query": qn(i), "label": None, "confidence": None, "votes": 0, "total_votes": int(count[i].sum()), "nearest": None,
@@ -1157,7 +1149,7 @@ def cluster_table(result, names=None):
     else:
         label, degree, size, rep = (getattr(result, k) for k in CLUSTER_FIELDS)
     label, degree, size, rep = (np.asarray(a, dtype=np.int64) for a in (label, degree, size, rep))
-    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    name = _namer(names)
     order = np.argsort(label, kind="stable")
     order = order[label[order] >= 0]
     out = []
@@ -1201,18 +1193,12 @@ def density_clusters(rows, threshold, min_points=5, metric="cosine"):
     for noise.  ``kind``: 0 invalid, 1 noise, 2 border, 3 core.  An invalid row: -1, 0, 0, -1, NaN, 0.  The border rule looks at all
     core neighbours: unlike textbook DBSCAN, the result does not depend on a visiting order.  Returns ``label``, ``degree``, ``size``,
     ``anchor`` (int64), ``sim`` (float64) and ``kind`` (uint8), each of n."""
-    if metric not in NEIGHBOUR_METRICS:
-        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    neighbour_metric(metric)
     r32 = neighbour_rows(rows, "rows")
     thr = float(cluster_threshold(threshold))
     need = density_min_points(min_points)
     n = len(r32)
-    ok = np.isfinite(r32).all(axis=1)
-    r = np.where(ok[:, None], r32, 0).astype(np.float64)
-    if metric == "cosine":
-        norm = np.sqrt((r * r).sum(axis=1))
-        ok &= norm > 0
-        r = r / np.where(ok, norm, 1.0)[:, None]
+    r, ok = _row_rule(r32, metric)
     s = r @ r.T
     adj = (s >= thr) & ok[:, None] & ok[None, :]
     adj |= adj.T                        # as threshold_clusters: an edge either way is an edge
@@ -1258,7 +1244,7 @@ def density_table(result, names=None):
     else:
         arrays = [getattr(result, k) for k in DENSITY_FIELDS]
     label, kind = np.asarray(arrays[0], dtype=np.int64), np.asarray(arrays[5], dtype=np.uint8)
-    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    name = _namer(names)
     order = np.argsort(label, kind="stable")
     order = order[label[order] >= 0]
     out = []
@@ -1323,24 +1309,18 @@ def greedy_representatives(rows, threshold, weight=None, metric="cosine"):
     representative in the caller's index space, a representative names itself, an invalid row has -1; ``sim`` float32 - a member's
     similarity to ``rep``, NaN for representatives and invalid rows; ``size`` int64 - the rows of its cluster, 0 for an invalid
     row; ``rank`` int64 - the row's place in the order; ``rounds`` - what :func:`representative_rounds` counts on this graph."""
-    if metric not in NEIGHBOUR_METRICS:
-        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
+    neighbour_metric(metric)
     r32 = neighbour_rows(rows, "rows")
     thr = float(cluster_threshold(threshold))
     n = len(r32)
     order = priority_order(weight, n)
     rank = np.empty(n, dtype=np.int64)
     rank[order] = np.arange(n)
-    r32 = r32[order]                                     # from here on index = rank
-    ok = np.isfinite(r32).all(axis=1)
-    r = np.where(ok[:, None], r32, 0).astype(np.float64)
-    if metric == "cosine":
-        norm = np.sqrt((r * r).sum(axis=1))
-        ok &= norm > 0
-        r = r / np.where(ok, norm, 1.0)[:, None]
+    r, ok = _row_rule(r32[order], metric)                # from here on index = rank
     # one pair at a time and the same sum either way round: identical rows get identical values, so a tie is a tie (a matrix
-    # product may round two equal pairs differently); read for i < j only
-    s = np.stack([(r * r[i]).sum(axis=1) for i in range(n)]) if n else np.zeros((0, 0))
+    # product may round two equal pairs differently); read for i < j only.  The sums as they are, not _pair_values' s + 0.0:
+    # ``sim`` returns them, and the float32 of a sum of -0 is -0
+    s = _pair_sums(r)
     edge = np.triu(s >= thr, 1) & ok[:, None] & ok[None, :]
     rep_p = np.full(n, -1, dtype=np.int64)
     sim_p = np.full(n, np.nan, dtype=np.float32)
@@ -1375,7 +1355,7 @@ def representative_table(result, names=None):
         rep, sim, size, rank = (getattr(result, k) for k in REPRESENTATIVE_FIELDS)
     rep, size, rank = (np.asarray(a, dtype=np.int64) for a in (rep, size, rank))
     sim = np.asarray(sim, dtype=np.float32)
-    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    name = _namer(names)
     by_rank = np.argsort(rank, kind="stable")
     members = {}
     for i in by_rank:
@@ -1400,44 +1380,28 @@ def single_linkage_tree(rows, metric="cosine"):
     lo = min(i, j), then to the smaller hi = max(i, j); Kruskal walks the pairs in that order and takes an edge iff it joins two
     different components.  Returns (a, b, sim, valid): the tree's edges in that order, best first - ``a`` int64 (lo), ``b`` int64
     (hi), ``sim`` float32 (the float64 value, rounded) - and ``valid`` uint8 (n,)."""
-    if metric not in NEIGHBOUR_METRICS:
-        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
-    r32 = neighbour_rows(rows, "rows")
-    n = len(r32)
-    ok = np.isfinite(r32).all(axis=1)
-    r = np.where(ok[:, None], r32, 0).astype(np.float64)
-    if metric == "cosine":
-        norm = np.sqrt((r * r).sum(axis=1))
-        ok &= norm > 0
-        r = r / np.where(ok, norm, 1.0)[:, None]
-    # one pair at a time and the same sum either way round, as in greedy_representatives: a tie is a tie; read for i < j only
-    with np.errstate(invalid="ignore", over="ignore"):
-        s = np.stack([(r * r[i]).sum(axis=1) for i in range(n)]) if n else np.zeros((0, 0))
-    lo, hi = np.triu_indices(n, 1)
+    s, ok = _pair_values(rows, metric)                   # a tie is a tie, -0 is +0; read for i < j only
+    lo, hi = np.triu_indices(len(ok), 1)
     keep = ok[lo] & ok[hi] & ~np.isnan(s[lo, hi])
     lo, hi = lo[keep], hi[keep]
-    v = s[lo, hi] + 0.0                                  # -0 + 0 = +0
+    v = s[lo, hi]
     order = np.lexsort((hi, lo, -v))                     # value descending, then lo, then hi ascending
-    root = np.arange(n)
+    return _kruskal(lo, hi, v, order, ok) + (ok.astype(np.uint8),)
 
-    def find(x):
-        while root[x] != x:
-            root[x] = root[root[x]]
-            x = root[x]
-        return x
 
-    a, b, sim = [], [], []
+def _kruskal(lo, hi, value, order, ok):
+    """(a int64, b int64, sim float32): the pairs (lo[e], hi[e]) that Kruskal takes when it walks them in ``order`` - a pair iff
+    it joins two components - with their ``value``, rounded, until the tree spans the rows of ``ok``"""
+    root, a, b, sim = list(range(len(ok))), [], [], []
     want = max(int(ok.sum()) - 1, 0)
-    for e in order:
+    for e in order.tolist():
         if len(a) == want:                               # the tree spans the valid rows: nothing later joins anything
             break
-        x, y = find(lo[e]), find(hi[e])
-        if x != y:
-            root[max(x, y)] = min(x, y)
+        if _join(root, int(lo[e]), int(hi[e])):
             a.append(lo[e])
             b.append(hi[e])
-            sim.append(v[e])
-    return np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64), np.asarray(sim, dtype=np.float32), ok.astype(np.uint8)
+            sim.append(value[e])
+    return np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64), np.asarray(sim, dtype=np.float32)
 
 
 def _linkage_arrays(a, b, sim):
@@ -1454,21 +1418,11 @@ def linkage_cut(a, b, sim, valid, threshold) -> np.ndarray:
     invalid row - ``threshold_clusters(rows, threshold)[0]`` where the tree is that of the same values."""
     a, b, sim = _linkage_arrays(a, b, sim)
     valid = np.asarray(valid).astype(bool).ravel()
-    thr = cluster_threshold(threshold)
-    root = np.arange(len(valid))
-
-    def find(x):
-        while root[x] != x:
-            root[x] = root[root[x]]
-            x = root[x]
-        return x
-
-    for e in np.flatnonzero(sim >= thr):
-        x, y = find(a[e]), find(b[e])
-        root[max(x, y)] = min(x, y)                      # towards the smaller index: a root is its cluster's smallest row
-    label = np.array([find(i) for i in range(len(valid))], dtype=np.int64).reshape(len(valid))
-    label[~valid] = -1
-    return label
+    keep = sim >= cluster_threshold(threshold)
+    root = list(range(len(valid)))
+    for x, y in zip(a[keep].tolist(), b[keep].tolist()):
+        _join(root, x, y)
+    return _root_labels(root, valid)
 
 
 def linkage_cluster_counts(sim, n_valid, thresholds) -> np.ndarray:
@@ -1490,22 +1444,27 @@ def linkage_matrix(a, b, sim, n) -> np.ndarray:
         raise ValueError(f"an edge names a row outside [0, {n})")
     if np.isnan(sim).any():
         raise ValueError("an edge's similarity is not a number")
-    root = np.arange(n)
-    cluster, size = np.arange(n), np.ones(n, dtype=np.int64)         # at a root: its cluster's id and size
+    root = list(range(n))
 
-    def find(x):
-        while root[x] != x:
-            root[x] = root[root[x]]
-            x = root[x]
-        return x
+    def merges():
+        for k, (i, j, s) in enumerate(zip(a.tolist(), b.tolist(), sim.tolist())):
+            x, y = _find(root, i), _find(root, j)
+            if x == y:
+                raise ValueError(f"edge {k} ({i}, {j}) joins two rows of one cluster: not a tree")
+            root[y] = x                                  # the edge's own orientation: x stays its cluster's slot
+            yield x, y, s
 
+    return _scipy_matrix(n, merges())
+
+
+def _scipy_matrix(n, merges) -> np.ndarray:
+    """The (n - 1, 4) float64 linkage matrix of SciPy's convention from n - 1 ``merges`` (x, y, sim) in their order: x and y are
+    the rows that stand for the two clusters merged, x goes on to stand for the merged one.  Per merge the two clusters' ids (the
+    smaller first), the distance 1 - sim and the new size; row i is cluster i, the cluster of merge k is n + k."""
+    cluster, size = list(range(n)), [1] * n              # at a row that stands for a cluster: its SciPy id and its size
     z = np.zeros((n - 1, 4), dtype=np.float64)
-    for k in range(n - 1):
-        x, y = find(a[k]), find(b[k])
-        if x == y:
-            raise ValueError(f"edge {k} ({a[k]}, {b[k]}) joins two rows of one cluster: not a tree")
-        z[k] = (min(cluster[x], cluster[y]), max(cluster[x], cluster[y]), 1.0 - float(sim[k]), size[x] + size[y])
-        root[y] = x
+    for k, (x, y, sim) in enumerate(merges):
+        z[k] = (min(cluster[x], cluster[y]), max(cluster[x], cluster[y]), 1.0 - sim, size[x] + size[y])
         cluster[x], size[x] = n + k, size[x] + size[y]
     return z
 
@@ -1514,7 +1473,7 @@ def linkage_table(a, b, sim, n_valid, names=None):
     """One record per merge of a :func:`single_linkage_tree`, best first: ``rank`` (from 1), ``a``, ``b`` (the names where ``names``
     is given), ``sim`` and ``clusters_left``, the clusters among the valid rows once the merge is made: n_valid - rank."""
     a, b, sim = _linkage_arrays(a, b, sim)
-    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    name = _namer(names)
     return [{"rank": k + 1, "a": name(a[k]), "b": name(b[k]), "sim": float(sim[k]), "clusters_left": int(n_valid) - k - 1}
             for k in range(len(a))]
 
@@ -1532,19 +1491,15 @@ def density_tree_min_points(min_points) -> int:
 def _pair_values(rows, metric):
     """(s float64 (n, n), ok bool (n,)): the pair values as :func:`single_linkage_tree` forms them - one pair at a time, the same sum
     either way round, so s is symmetric to the bit - and the rows' validity"""
-    if metric not in NEIGHBOUR_METRICS:
-        raise ValueError(f"metric {metric!r}: expected one of {NEIGHBOUR_METRICS}")
-    r32 = neighbour_rows(rows, "rows")
-    n = len(r32)
-    ok = np.isfinite(r32).all(axis=1)
-    r = np.where(ok[:, None], r32, 0).astype(np.float64)
-    if metric == "cosine":
-        norm = np.sqrt((r * r).sum(axis=1))
-        ok &= norm > 0
-        r = r / np.where(ok, norm, 1.0)[:, None]
+    neighbour_metric(metric)
+    r, ok = _row_rule(neighbour_rows(rows, "rows"), metric)
+    return _pair_sums(r) + 0.0, ok                       # -0 + 0 = +0
+
+
+def _pair_sums(r):
+    """float64 (n, n): r[i] . r[j] as one sum per pair, the same either way round - the one place these sums are formed"""
     with np.errstate(invalid="ignore", over="ignore"):
-        s = np.stack([(r * r[i]).sum(axis=1) for i in range(n)]) if n else np.zeros((0, 0))
-    return s + 0.0, ok                                   # -0 + 0 = +0
+        return np.stack([(r * r[i]).sum(axis=1) for i in range(len(r))]) if len(r) else np.zeros((0, 0))
 
 
 def core_similarity(rows, min_points=5, metric="cosine"):
@@ -1577,33 +1532,12 @@ def mutual_reachability_tree(rows, min_points=5, metric="cosine"):
     the edges best first, sim = w rounded."""
     core, _ = core_similarity(rows, min_points, metric)
     s, ok = _pair_values(rows, metric)
-    n = len(ok)
-    lo, hi = np.triu_indices(n, 1)
+    lo, hi = np.triu_indices(len(ok), 1)
     keep = ok[lo] & ok[hi] & ~np.isnan(s[lo, hi])
     lo, hi = lo[keep], hi[keep]
     w = np.minimum(np.minimum(s[lo, hi], core[lo]), core[hi])
     order = np.lexsort((hi, lo, -w))
-    root = np.arange(n)
-
-    def find(x):
-        while root[x] != x:
-            root[x] = root[root[x]]
-            x = root[x]
-        return x
-
-    a, b, sim = [], [], []
-    want = max(int(ok.sum()) - 1, 0)
-    for e in order:
-        if len(a) == want:
-            break
-        x, y = find(lo[e]), find(hi[e])
-        if x != y:
-            root[max(x, y)] = min(x, y)
-            a.append(lo[e])
-            b.append(hi[e])
-            sim.append(w[e])
-    return (np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64), np.asarray(sim, dtype=np.float32), core.astype(np.float32),
-            ok.astype(np.uint8))
+    return _kruskal(lo, hi, w, order, ok) + (core.astype(np.float32), ok.astype(np.uint8))
 
 
 def density_tree_cut(a, b, sim, core, valid, threshold) -> np.ndarray:
@@ -1663,15 +1597,8 @@ def hdbscan_clusters(a, b, sim, valid, min_cluster_size=5, allow_single_cluster=
     # The dendrogram by levels, bottom-up: node x < n is row x; walking the distinct values of sim downwards, every component that the
     # level's edges form becomes a node whose children are the components they joined.  kids / level / count / least per node.
     kids, level, count, least = [None] * n, [None] * n, [1] * n, list(range(n))
-    root = np.arange(n)
+    root = list(range(n))
     node_at = list(range(n))                             # at a union-find root: the dendrogram node of its component
-
-    def find(x):
-        while root[x] != x:
-            root[x] = root[root[x]]
-            x = root[x]
-        return x
-
     order = np.argsort(-sim.astype(np.float64), kind="stable")
     e = 0
     while e < len(order):
@@ -1679,11 +1606,11 @@ def hdbscan_clusters(a, b, sim, valid, min_cluster_size=5, allow_single_cluster=
         while f < len(order) and sim[order[f]] == sim[order[e]]:
             f += 1
         touched = {}                                     # new union-find root -> the nodes joined under it at this level
-        for k in order[e:f]:
-            x, y = find(a[k]), find(b[k])
+        for k in order[e:f].tolist():
+            x, y = _find(root, int(a[k])), _find(root, int(b[k]))
             if x == y:
                 raise ValueError(f"edge {k} ({a[k]}, {b[k]}) joins two rows of one component: not a tree")
-            lo, hi = min(x, y), max(x, y)
+            lo, hi = min(x, y), max(x, y)                # the two roots are needed below: the link is made here, as _join makes it
             root[hi] = lo
             touched[lo] = touched.pop(lo, [node_at[lo]]) + touched.pop(hi, [node_at[hi]])
         for r, nodes in touched.items():
@@ -1715,7 +1642,7 @@ def hdbscan_clusters(a, b, sim, valid, min_cluster_size=5, allow_single_cluster=
         return len(c_least) - 1
 
     if len(rows_in):
-        top = node_at[find(rows_in[0])]
+        top = node_at[_find(root, int(rows_in[0]))]
         new_cluster(top, -1, 0.0)
         work = [(0, top)]                                # (cluster, the dendrogram node it lives in now)
         while work:
@@ -1771,7 +1698,7 @@ def hdbscan_table(result, names=None):
     """One record per selected cluster of a :func:`hdbscan_clusters` result, ordered by label: ``label``, ``size`` (the rows that
     carry the label), ``birth``, ``stability`` and ``members`` (indices ascending; the names where ``names`` is given, as is then
     ``label``)."""
-    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    name = _namer(names)
     label = np.asarray(result["label"])
     sel = np.flatnonzero(result["selected"])
     recs = []
@@ -1807,15 +1734,6 @@ def kmeans_k(k) -> int:
 
 def kmeans_max_iter(max_iter) -> int:
     return _whole(max_iter, "max_iter", 0, KMEANS_MAX_ITER_MAX)
-
-
-def _unit_rows(r32):
-    """(the rows as float64 unit vectors - zero where the row is not valid -, the valid rows) as :func:`nearest_neighbours` has them"""
-    ok = np.isfinite(r32).all(axis=1)
-    r = np.where(ok[:, None], r32, 0).astype(np.float64)
-    norm = np.sqrt((r * r).sum(axis=1))
-    ok &= norm > 0
-    return r / np.where(ok, norm, 1.0)[:, None], ok
 
 
 def farthest_first(unit, ok, k) -> np.ndarray:
@@ -1857,7 +1775,7 @@ def spherical_kmeans(rows, k, init=None, max_iter=KMEANS_MAX_ITER_DEFAULT, trace
     (bool) and ``init_rows`` (int64 (k,): the rows the traversal picked, -1 for a given ``init``)."""
     r32 = neighbour_rows(rows, "rows")
     k, max_iter = kmeans_k(k), kmeans_max_iter(max_iter)
-    unit, ok = _unit_rows(r32)
+    unit, ok = _row_rule(r32, "cosine")
     n, valid = len(r32), np.flatnonzero(ok)
     if k > len(valid):
         raise ValueError(f"k {k} is more than the {len(valid)} valid rows of {n}")
@@ -1866,7 +1784,7 @@ def spherical_kmeans(rows, k, init=None, max_iter=KMEANS_MAX_ITER_DEFAULT, trace
         centroids = unit[init_rows].copy()
     else:
         i32 = neighbour_rows(init, "init")
-        centroids, i_ok = _unit_rows(i32)
+        centroids, i_ok = _row_rule(i32, "cosine")
         if len(i32) != k:
             raise ValueError(f"init has {len(i32)} rows: k = {k} are required")
         if not i_ok.all():
@@ -1912,7 +1830,7 @@ def group_centroids(rows, label, k):
     label = label.astype(np.int64)
     if len(label) and (label.min() < -1 or label.max() >= k):
         raise ValueError(f"a label is outside [-1, {k})")
-    unit, ok = _unit_rows(r32)
+    unit, ok = _row_rule(r32, "cosine")
     centroids = np.zeros((k, NEIGHBOUR_DIM), dtype=np.float64)
     size = np.zeros(k, dtype=np.int64)
     for c in range(k):
@@ -1937,7 +1855,7 @@ def kmeans_table(result, names=None):
     else:
         label, sim, size = (getattr(result, f) for f in ("label", "sim", "size"))
     label, sim = np.asarray(label, dtype=np.int64), np.asarray(sim, dtype=np.float64)
-    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    name = _namer(names)
     out = []
     for c in range(len(size)):
         members = np.flatnonzero(label == c)
@@ -1962,7 +1880,7 @@ def pca_moments(rows):
     float64 here).  ``rows`` (n, 512) float32; the valid rows are exactly those of :func:`nearest_neighbours` under cosine and an
     invalid row contributes nothing.  Returns ``G`` (float64 (512, 512): the sum of u uT over the valid rows' unit vectors u),
     ``S`` (float64 (512,): the sum of u) and ``n_valid`` (int)."""
-    unit, ok = _unit_rows(neighbour_rows(rows, "rows"))
+    unit, ok = _row_rule(neighbour_rows(rows, "rows"), "cosine")
     return unit.T @ unit, unit.sum(axis=0), int(ok.sum())
 
 
@@ -2002,7 +1920,7 @@ def pca_directions(components):
     c32 = neighbour_rows(components, "components")
     if not 1 <= len(c32) <= PCA_COMPONENTS_MAX:
         raise ValueError(f"{len(c32)} components: 1 to {PCA_COMPONENTS_MAX} are required")
-    unit, ok = _unit_rows(c32)
+    unit, ok = _row_rule(c32, "cosine")
     if not ok.all():
         raise ValueError(f"{int((~ok).sum())} of the {len(c32)} components are not valid (finite, norm > 0)")
     return c32, unit
@@ -2024,7 +1942,7 @@ def pca_project(rows, components, mean=None):
     """Principal-component scores, spelled out (the definition ``gnn_pca_project`` computes on the device; float64): u_i . v_c -
     mean . v_c for the unit vector u_i of row i and the unit vector v_c of component c; NaN for an invalid row.  Returns float64
     (n, c)."""
-    unit, ok = _unit_rows(neighbour_rows(rows, "rows"))
+    unit, ok = _row_rule(neighbour_rows(rows, "rows"), "cosine")
     _, v = pca_directions(components)
     out = unit @ v.T - pca_offsets(components, mean)[None, :]
     out[~ok] = np.nan
@@ -2034,7 +1952,7 @@ def pca_project(rows, components, mean=None):
 def pca_table(projection, valid, names=None):
     """One record per row of a projection: ``row`` (its index, or its name where ``names`` is given) and ``pc`` (the list of its
     scores; None for a row without a valid embedding)"""
-    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    name = _namer(names)
     return [{"row": name(i), "pc": [float(x) for x in projection[i]] if valid[i] else None} for i in range(len(projection))]
 
 
@@ -2286,7 +2204,7 @@ def mcl_table(label, size, is_attractor, names=None):
     """One record per cluster, ordered by label: ``label``, ``size``, ``members`` and ``attractors`` (the members with flow to
     themselves), as indices in ascending order or - where ``names`` is given - as names"""
     label = np.asarray(label, dtype=np.int64)
-    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    name = _namer(names)
     order = np.argsort(label, kind="stable")
     order = order[label[order] >= 0]
     bounds = np.flatnonzero(np.diff(label[order], prepend=-1)) if len(order) else []
@@ -2429,8 +2347,8 @@ def spread_table(best, best_score, second_score, total, first, names=None, class
     """One record per row: ``row`` (its index, or its name), ``label`` (the class, or its name; None without one), ``confidence``,
     ``score`` (``best_score`` / 2^30), ``total_score`` (``total`` / 2^30) and ``first``"""
     label, confidence, _ = spread_predict(best, best_score, second_score, total, min_score)
-    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
-    cname = (lambda c: int(c)) if class_names is None else (lambda c: str(class_names[int(c)]))
+    name = _namer(names)
+    cname = _namer(class_names)
     return [{"row": name(i), "label": cname(label[i]) if label[i] >= 0 else None, "confidence": float(confidence[i]) if label[i] >= 0 else None,
              "score": int(best_score[i]) / SPREAD_ONE, "total_score": int(total[i]) / SPREAD_ONE, "first": int(first[i])}
             for i in range(len(label))]
@@ -2552,20 +2470,10 @@ def average_linkage_cut(result, t) -> np.ndarray:
     t_q = average_linkage_stop(t)
     valid = np.asarray(result["valid"]).astype(bool).ravel()
     root = list(range(len(valid)))
-
-    def find(x):
-        while root[x] != x:
-            root[x] = root[root[x]]
-            x = root[x]
-        return x
-
     for a, b, w, sa, sb in zip(*(np.asarray(result[k]).tolist() for k in AVGLINK_FIELDS[:5])):
         if w >= t_q * sa * sb:
-            x, y = find(a), find(b)
-            root[max(x, y)] = min(x, y)                      # towards the smaller index: a root is its cluster's smallest row
-    label = np.array([find(i) for i in range(len(valid))], dtype=np.int64).reshape(len(valid))
-    label[~valid] = -1
-    return label
+            _join(root, a, b)
+    return _root_labels(root, valid)
 
 
 def average_linkage_cluster_counts(result, thresholds) -> np.ndarray:
@@ -2588,20 +2496,14 @@ def average_linkage_matrix(result) -> np.ndarray:
     if n < 1 or not valid.all() or len(a) != n - 1:
         raise ValueError(f"{len(a)} merges among {n} rows, {int(valid.sum())} of them valid: a linkage matrix needs n - 1 merges over n >= 1 "
                          "valid rows")
-    cluster, size = list(range(n)), [1] * n              # at a cluster's id: its SciPy id and its size
-    z = np.zeros((n - 1, 4), dtype=np.float64)
-    for k in range(n - 1):
-        x, y = a[k], b[k]
-        z[k] = (min(cluster[x], cluster[y]), max(cluster[x], cluster[y]), 1.0 - sim[k], size[x] + size[y])
-        cluster[x], size[x] = n + k, size[x] + size[y]
-    return z
+    return _scipy_matrix(n, zip(a, b, sim.tolist()))     # a absorbs b: a cluster's id, its smallest member, stands for it
 
 
 def average_linkage_table(result, names=None):
     """One record per merge of an average-linkage tree, best first: ``rank`` (from 1), ``a``, ``b`` (the names where ``names`` is
     given), ``sim``, ``size`` (of the merged cluster), ``round`` and ``clusters_left`` among the valid rows once the merge is made."""
     n_valid = int(np.count_nonzero(np.asarray(result["valid"])))
-    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    name = _namer(names)
     cols = [np.asarray(result[k]).tolist() for k in ("a", "b", "sim", "size_a", "size_b", "round")]
     return [{"rank": k + 1, "a": name(a), "b": name(b), "sim": float(s), "size": int(sa + sb), "round": int(r), "clusters_left": n_valid - k - 1}
             for k, (a, b, s, sa, sb, r) in enumerate(zip(*cols))]
@@ -2674,18 +2576,10 @@ def _comm_sweep(rows, k, comm, m2, r, s):
 
 def _comm_roots(nodes, pairs):
     """node -> the smallest node of its connected component under ``pairs``"""
-    root = {i: i for i in nodes}
-
-    def find(x):
-        while root[x] != x:
-            root[x] = root[root[x]]
-            x = root[x]
-        return x
-
+    root = {i: i for i in nodes}                          # a dict: a level's nodes are the keys of its rows
     for x, y in pairs:
-        x, y = find(x), find(y)
-        root[max(x, y)] = min(x, y)                       # towards the smaller: a root is its component's smallest node
-    return {i: find(i) for i in nodes}
+        _join(root, x, y)
+    return {i: _find(root, i) for i in nodes}
 
 
 def modularity_communities(indptr, col, sim, valid=None, resolution=1.0, max_levels=COMM_LEVELS_MAX, max_sweeps=COMM_SWEEPS_MAX,
@@ -2802,10 +2696,10 @@ def label_components(indptr, col, sim, label, valid=None) -> np.ndarray:
         raise ValueError(f"label must be an integer array of {n} with values >= -1")
     label = label.astype(np.int64)
     same = (label[ea] == label[eb]) & (label[ea] >= 0)
-    root = _comm_roots(range(n), zip(ea[same].tolist(), eb[same].tolist()))
-    out = np.array([root[i] for i in range(n)], dtype=np.int64).reshape(n)
-    out[~ok | (label < 0)] = -1
-    return out
+    root = list(range(n))
+    for x, y in zip(ea[same].tolist(), eb[same].tolist()):
+        _join(root, x, y)
+    return _root_labels(root, ok & (label >= 0))
 
 
 def communities_table(result, names=None):
@@ -2813,7 +2707,7 @@ def communities_table(result, names=None):
     by label: ``label``, ``size`` and ``members``, as indices in ascending order or - where ``names`` is given - as names"""
     label = np.asarray(result["label"], dtype=np.int64)
     size = np.asarray(result["size"])
-    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    name = _namer(names)
     order = np.argsort(label, kind="stable")
     order = order[label[order] >= 0]
     bounds = np.flatnonzero(np.diff(label[order], prepend=-1)) if len(order) else []
@@ -2881,7 +2775,7 @@ def knn_graph_table(indptr, col, sim, mutual, names=None):
     """One record per edge of a k-nearest-neighbour graph, in its order: ``a`` < ``b`` (indices; the names where ``names`` is given),
     ``weight`` and ``mutual`` (both ends list each other)."""
     a, b = graph_edges(indptr, col)
-    name = (lambda i: int(i)) if names is None else (lambda i: str(names[int(i)]))
+    name = _namer(names)
     return [{"a": name(i), "b": name(j), "weight": float(s), "mutual": bool(m)}
             for i, j, s, m in zip(a, b, np.asarray(sim), np.asarray(mutual))]
 
