@@ -157,6 +157,7 @@ SIGNATURES = {
     "gnn_mcl_matrix": (_int, [_vp, _i64, _int, _vp, _vp, _vp]),
     "gnn_debug_mcl_lds": (_int, [_vp, _int]),
     "gnn_debug_mcl_groups": (_int, [_vp, _int]),
+    "gnn_debug_mcl_pow": (_int, [_vp, _vp, _i64, _int, _vp]),
     "gnn_debug_mcl_ms": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_debug_mcl_overflow": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_spread": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -105,6 +105,12 @@ __device__ __forceinline__ ull mc_pow(ull u, int a4) {
     return r;
 }
 
+// gnn_debug_mcl_pow: the passes' own power, one value per thread
+__global__ __launch_bounds__(256) void mc_pow_kernel(int64_t n, int a4, const ull* __restrict__ u, ull* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = mc_pow(u[i], a4);
+}
+
 // The LDS table as mc_finish reads it: position p is a slot, idx < 0 an empty one.
 struct LdsTab {
     int* key;
@@ -732,6 +738,30 @@ extern "C" int gnn_debug_mcl_groups(gnn_ctx* ctx, int groups) {
         return GNN_ERR_ARG;
     }
     ctx->mcl.groups = groups;
+    return GNN_OK;
+}
+
+extern "C" int gnn_debug_mcl_pow(gnn_ctx* ctx, const uint64_t* u_host, int64_t n, int inflation_quarters, uint64_t* out_host) {
+    const std::string fn = "gnn_debug_mcl_pow";
+    const auto bad = [&](const char* what, int64_t v, const char* range) {
+        set_error(fn + ": " + what + " " + std::to_string(v) + " is outside " + range);
+        return GNN_ERR_ARG;
+    };
+    if (inflation_quarters < 5 || inflation_quarters > 32) return bad("inflation_quarters", inflation_quarters, "[5, 32]");
+    if (n < 0 || n > CSR_N_MAX) return bad("n", n, "[0, 2^24]");
+    if (int rc = nn_check_required(fn, n == 0 || (u_host && out_host), "u and out")) return rc;
+    for (int64_t i = 0; i < n; ++i)                           // Ends: i grows towards n
+        if (u_host[i] > ONE) return bad("u", (int64_t)std::min<uint64_t>(u_host[i], INT64_MAX), "[0, 2^30]");
+    if (int rc = check_ctx(ctx)) return rc;
+    if (n == 0) return GNN_OK;
+    DevBuf<ull> u, out;
+    int rc = u.reserve((size_t)n);
+    if (!rc) rc = out.reserve((size_t)n);
+    if (rc) return rc;
+    GNN_HIP(hipMemcpyAsync(u.get(), u_host, (size_t)n * sizeof(ull), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = launch_1d(mc_pow_kernel, n, ctx->stream, n, inflation_quarters, u.get(), out.get()))) return rc;
+    GNN_HIP(hipMemcpyAsync(out_host, out.get(), (size_t)n * sizeof(ull), hipMemcpyDeviceToHost, ctx->stream));
+    GNN_HIP(hipStreamSynchronize(ctx->stream));               // before the buffers go
     return GNN_OK;
 }
 

@@ -1520,6 +1520,17 @@ class NNEngine:
         on it."""
         check(self.lib.gnn_debug_mcl_groups(self.ctx, int(groups)))
 
+    def mcl_pow(self, u, inflation) -> np.ndarray:
+        """test aid (``gnn_debug_mcl_pow``): the device's integer power over ``u`` (m,) uint64 <= 2^30: uint64 (m,) of u ^ inflation
+        in 2^-30 fixed point, by the function the passes of :meth:`mcl` call"""
+        a4 = _sequence.mcl_inflation(inflation)
+        u = np.ascontiguousarray(u, dtype=np.uint64)
+        if u.ndim != 1:
+            raise ValueError("u (m,) uint64 is required")
+        out = np.empty(len(u), dtype=np.uint64)
+        check(self.lib.gnn_debug_mcl_pow(self.ctx, u.ctypes.data, len(u), a4, out.ctypes.data))
+        return out
+
     def mcl_pass_ms(self):
         """measurement only (``gnn_debug_mcl_ms``): with profiling enabled, the HIP-event milliseconds of the last :meth:`mcl` /
         :meth:`mcl_dev` call - [validate and symmetrise, the initial matrix, then every iteration]"""

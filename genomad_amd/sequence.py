@@ -2015,6 +2015,8 @@ def _mcl_prune(cj, ci, y, select, precision):
     first, seg = _mcl_segments(cj)
     keep = y * np.uint64(precision) >= np.add.reduceat(y, first)[seg]
     cj, ci, y = cj[keep], ci[keep], y[keep]
+    if not len(cj):                                       # the cutoff kept nothing (precision below a column's equal entries)
+        return cj, ci, y
     order = np.lexsort((ci, ~y, cj))                      # column, then y descending, then row ascending
     cj, ci, y = cj[order], ci[order], y[order]
     first, seg = _mcl_segments(cj)

@@ -856,9 +856,13 @@ int gnn_mcl_dev(gnn_ctx* ctx, const int64_t* indptr_dev, const int32_t* col_dev,
 int gnn_mcl_matrix(gnn_ctx* ctx, int64_t n, int select, int32_t* length_host, int32_t* idx_host, uint32_t* val_host);
 /* test aids; no result depends on them.  gnn_debug_mcl_lds: the slots of the LDS table, 0 .. 4096 (0: every column takes the overflow
  * path; -1: leave it as it is); returns the value before the call (>= 0), or GNN_ERR_ARG.  gnn_debug_mcl_groups: the workgroups of a
- * pass, 1 .. 65535 (0: the library's choice, two per CU). */
+ * pass, 1 .. 65535 (0: the library's choice, two per CU).  gnn_debug_mcl_pow: the integer power of the iteration, run on the device by
+ * the function the passes call: out[i] = u[i] ^ (inflation_quarters / 4) in 2^-30 fixed point for n values u <= 2^30 (uint64, on the
+ * host); GNN_ERR_ARG - before the ctx is looked at - for inflation_quarters outside [5, 32], n outside [0, 2^24], a u above 2^30 or a
+ * missing pointer with n > 0.  Synchronous. */
 int gnn_debug_mcl_lds(gnn_ctx* ctx, int slots);
 int gnn_debug_mcl_groups(gnn_ctx* ctx, int groups);
+int gnn_debug_mcl_pow(gnn_ctx* ctx, const uint64_t* u_host, int64_t n, int inflation_quarters, uint64_t* out_host);
 /* measurement only.  gnn_debug_mcl_ms: with gnn_profile_enable on, the HIP-event milliseconds of the ctx's last gnn_mcl* call: [0]
  * validate and symmetrise, [1] the initial matrix, then one figure per iteration; *n_out = the figures recorded, at most `capacity` are
  * written.  gnn_debug_mcl_overflow: the columns each pass of that call pushed on the overflow list: [0] the initial matrix, then one

@@ -8,6 +8,7 @@ import numpy as np
 from genomad_amd import sequence
 from tests.clusters_data import planted
 from tests.mcl_data import RANDOM, csr_of_edges
+from tests.mcl_limits_data import heavy, ranged
 from tests.spread_data import PARALLEL, RANDOM_VALID, n_of, star
 
 W = 1 << 24
@@ -72,11 +73,12 @@ def cases():
         "sparse0": (sparse(0), None), "sparse1": (sparse(1), None), "tied0": (tied(0), None), "tied1": (tied(1), None),
         "complete": (complete(), None), "planted": (pg, pv), "path": (rising_path(), None), "parallel": (PARALLEL, None),
         "masked": (RANDOM, RANDOM_MASKED_VALID), "empty": (EMPTY, np.array([True, False, True, True, True])), "none": (NONE, None),
-        "one": (ONE, None),
+        "one": (ONE, None), "heavy": (heavy(), None), "ranged": (ranged(), None),
     }
 
 
-NAMES = ("sparse0", "sparse1", "tied0", "tied1", "complete", "planted", "path", "parallel", "masked", "empty", "none", "one")
+NAMES = ("sparse0", "sparse1", "tied0", "tied1", "complete", "planted", "path", "parallel", "masked", "empty", "none", "one", "heavy",
+         "ranged")
 
 
 @functools.lru_cache(maxsize=None)

@@ -9,6 +9,7 @@ import numpy as np
 from genomad_amd import sequence
 from tests.clusters_data import planted          # noqa: F401 - the tests take it from here too
 from tests.mcl_data import RANDOM, csr_of_edges
+from tests.mcl_limits_data import heavy, ranged
 from tests.spread_data import PARALLEL, RANDOM_VALID, n_of, star
 
 W = 1 << 24
@@ -108,13 +109,14 @@ def cases():
         "split": (random_graph(SPLIT["seed"], SPLIT["n"], SPLIT["p"], "unit"), None),
         "planted": (pg, pv), "path": (path(), None), "ring": (ring_of_cliques(), None), "grid": (grid(), None), "parallel": (PARALLEL, None),
         "masked": (RANDOM, RANDOM_VALID), "empty": (EMPTY, np.array([True, False, True, True, True])), "none": (NONE, None),
-        "one": (ONE, None),
+        "one": (ONE, None), "heavy": (heavy(), None), "ranged": (ranged(), None),
     })
     return out
 
 
 RANDOM_NAMES = tuple(f"{kind}{seed}" for kind in KINDS for seed in (0, 1))
-NAMES = RANDOM_NAMES + ("rejected", "split", "planted", "path", "ring", "grid", "parallel", "masked", "empty", "none", "one")
+NAMES = RANDOM_NAMES + ("rejected", "split", "planted", "path", "ring", "grid", "parallel", "masked", "empty", "none", "one",
+                        "heavy", "ranged")
 
 
 @functools.lru_cache(maxsize=None)

@@ -60,6 +60,7 @@ RANDOM_VALID = np.arange(n_of(RANDOM)) % 9 != 4       # every ninth row takes no
 
 def cases(n_classes):
     """name -> (csr, valid or None, label) for ``n_classes`` classes: every fixture but the large star"""
+    from tests.mcl_limits_data import heavy, ranged      # that module takes star() and PARALLEL from this one
     c = n_classes
     return {
         "planted": (PLANTED, None, planted_labels(c)),
@@ -71,4 +72,6 @@ def cases(n_classes):
         "parallel": (PARALLEL, None, np.minimum(PARALLEL_LABELS, c - 1)),
         "star_at": (STAR_AT, None, star_labels(LONG_ROW, c)),
         "star_over": (STAR_OVER, None, star_labels(LONG_ROW + 1, c)),
+        "heavy": (heavy(), None, planted_labels(c)),
+        "ranged": (ranged(), None, planted_labels(c)),
     }
