@@ -191,6 +191,12 @@ SIGNATURES = {
     "gnn_debug_knn_graph_group_rows": (_int, [_vp, _int]),
     "gnn_debug_knn_graph_classes": (_int, [_vp, _vp]),
     "gnn_debug_knn_graph_ms": (_int, [_vp, _vp, _i64, _vp]),
+    "gnn_tsne": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _int, _int, C.c_double, C.c_float, _vp, _vp, _vp]),
+    "gnn_tsne_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _int, _int, C.c_double, C.c_float, _vp, _vp, _vp]),
+    "gnn_tsne_forces": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_tsne_forces_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gnn_debug_tsne_split": (_int, [_vp, _int]),
+    "gnn_debug_tsne_ms": (_int, [_vp, _vp, _i64, _vp]),
     "gnn_kmeans": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_kmeans_dev": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gnn_centroids": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp]),

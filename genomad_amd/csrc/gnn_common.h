@@ -482,6 +482,29 @@ struct KnnGraphWorkspace {
     PassLog passes;                              // profiling on: the last count's [search, lists, count, scan + classes], behind them every fill's [fill, order, finish]
 };
 
+// ---- t-SNE layout (gnn_tsne.hip): persistent, grow-only.  The symmetric graph (12 B per entry, 25 B per row), 24 B per row of Y, gains
+// and updates, 40 B per row of integer sums, 8 B per iterate of Z and, for the host entry points alone, the graph and their arguments
+// and results.  Nothing is n x n.
+struct TsneWorkspace {
+    int split = 0;                               // workgroups over the columns of the repel pass (gnn_debug_tsne_split); 0: two workgroups per CU; no result depends on it
+    DevBuf<uint8_t> ok;                          // [n]: the row takes part
+    DevBuf<int32_t> deg;                         // the symmetric graph: edges at the row, both ends counted
+    DevBuf<int64_t> soff;                        // [n + 1]: their exclusive prefix sums
+    DevBuf<unsigned long long> cursor;           // [n]: where the row's next entry goes
+    DevBuf<int32_t> sidx;                        // [soff[n]]: the partner
+    DevBuf<uint32_t> sq;                         // the entry's integer weight
+    DevBuf<float> sp;                            // and its affinity p = q / M2
+    DevBuf<int32_t> long_list;                   // [n]: the rows whose entries a workgroup attracts
+    DevBuf<float> y, gain, upd;                  // [n][2] each
+    DevBuf<long long> zi, rx, ry;                // [n]: the repel pass's sums, zero between passes
+    DevBuf<long long> ax, ay;                    // [n]: the attract pass's sums
+    DevBuf<unsigned long long> ztrace;           // [n_iter + 1]: Z of every iterate, accumulated where it stands
+    HostCounters count;                          // [the graph's and the init's flag, M2, rows of the long list]: the host reads the flag, once
+    GraphStaging graph;                          // gnn_tsne, gnn_tsne_forces: the graph
+    DevBuf<int64_t> d_out;                       // a Landing.  gnn_tsne: [layout (f32) | z_trace | valid (u8) | init (f32)]; gnn_tsne_forces: [zi | rx | ry | ax | ay | m2 | Y (f32)]
+    PassLog passes;                              // profiling on: the last gnn_tsne* call's [setup, the loop, the final Z and the results]
+};
+
 struct ContigWorkspace {
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> piece_done;
@@ -688,9 +711,10 @@ struct gnn_ctx {
     gnn::AvglinkWorkspace avl;                    // gnn_avglink.hip
     gnn::CommunitiesWorkspace cmt;                // gnn_communities.hip
     gnn::KnnGraphWorkspace kg;                    // gnn_knn_graph.hip
+    gnn::TsneWorkspace ts;                        // gnn_tsne.hip
     // every PassLog above: drain_profile settles them before an event they hold returns to event_pool
-    gnn::PassLog* const pass_logs[12] = {&rp.rounds, &lk.rounds, &lk.tree_rounds, &gr.passes,  &km.passes, &pca.passes,
-                                         &vt.passes, &mcl.passes, &sprd.passes, &avl.passes, &cmt.passes, &kg.passes};
+    gnn::PassLog* const pass_logs[13] = {&rp.rounds, &lk.rounds, &lk.tree_rounds, &gr.passes,  &km.passes,  &pca.passes, &vt.passes,
+                                         &mcl.passes, &sprd.passes, &avl.passes, &cmt.passes, &kg.passes, &ts.passes};
     // RCCL communicator of this ctx (gnn_comm.hip); ncclComm_t kept opaque here
     void* comm = nullptr;
     int comm_ranks = 1, comm_rank = 0;

@@ -397,6 +397,11 @@ class GraphResult(_Result):
         """:meth:`NNEngine.label_components` of this graph and its rows' validity: the connected parts of every label's rows"""
         return engine.label_components(self.indptr, self.col, self.sim, label, valid=self.valid)
 
+    def tsne(self, engine, init=None, **kw) -> "TSNEResult":
+        """:meth:`NNEngine.tsne` of this graph and its rows' validity: the exact t-SNE layout, with ``n_iter``, ``exaggeration_iter``,
+        ``exaggeration`` and ``learning_rate`` as there; ``init`` None: ``sequence.tsne_init``"""
+        return engine.tsne(self.indptr, self.col, self.sim, _sequence.tsne_init(self.n) if init is None else init, valid=self.valid, **kw)
+
     @classmethod
     def build(cls, arrays, valid, threshold, metric):
         """from the (indptr, col, sim) of ``sequence.threshold_graph`` or the library, and the rows' validity"""
@@ -595,6 +600,20 @@ class CommunityResult(_Result):
         """from the dict of ``sequence.modularity_communities``"""
         words = np.array([[q & (2 ** 64 - 1), (q >> 64) & (2 ** 64 - 1)] for q in result["qnum"]], dtype=np.uint64).reshape(-1, 2)
         return cls(**{k: result[k] for k in cls.FIELDS if k in result}, qnum_words=words, n=len(result["label"]))
+
+
+class TSNEResult(_Result):
+    """What :meth:`NNEngine.tsne` returns (the definition is ``sequence.tsne_layout``): ``layout`` (float32 (n, 2), NaN at an invalid
+    row), ``z_trace`` (uint64 (n_iter + 1,): the integer Z - the sum of 1 / (1 + d^2) over all ordered pairs in units of 2^-20 - of
+    every iterate, the final one included), ``kl_divergence`` (float64: ``sequence.tsne_kl`` of the final layout), ``iterations``,
+    ``valid`` (bool (n,)), ``n`` and the knobs it ran with: ``exaggeration_iter``, ``exaggeration``, ``learning_rate``.  From
+    :meth:`NNEngine.tsne_dev` the per-row arrays stay on the device and ``layout``, ``z_trace``, ``kl_divergence`` and ``valid`` are
+    None."""
+    FIELDS = ("layout", "z_trace", "kl_divergence", "iterations", "valid", "n", "exaggeration_iter", "exaggeration", "learning_rate")
+
+    def table(self, names=None):
+        """``sequence.tsne_table``: one record per row - name, x, y"""
+        return _sequence.tsne_table(self.layout, self.valid, names)
 
 
 class VoteResult(_Result):
@@ -1540,6 +1559,87 @@ class NNEngine:
         """measurement only (``gnn_debug_mcl_overflow``): the columns that took the overflow path in the last :meth:`mcl` /
         :meth:`mcl_dev` call - int64 [the initial matrix, then every iteration]"""
         return self._debug_ms(self.lib.gnn_debug_mcl_overflow, np.int64)
+
+    # -- t-SNE layout --------------------------------------------------------------------
+    @staticmethod
+    def _tsne_init(init, n):
+        with np.errstate(over="ignore"):
+            y = np.ascontiguousarray(init, dtype=np.float32)
+        if y.shape != (n, 2):
+            raise ValueError(f"the layout must be ({n}, 2)")
+        return y
+
+    def tsne(self, indptr, col, sim, init, valid=None, n_iter=750, exaggeration_iter=250, exaggeration=12.0, learning_rate=None) -> TSNEResult:
+        """The exact t-SNE layout of a similarity graph (``gnn_tsne``; the definition is ``sequence.tsne_layout``): a 2-D picture of
+        the upper-triangle CSR (``indptr``, ``col``, ``sim``) :meth:`graph` / :meth:`knn_graph` return, from ``init`` (float32 (n, 2),
+        finite at every valid row).  The affinities are the graph's own weights, the repulsion the exact all-pairs pass; every output
+        equals the definition bit for bit, whatever the grid.  ``valid``: bool per row (None: all); ``n_iter`` (0..100000) iterations,
+        the first ``exaggeration_iter`` with the attraction times ``exaggeration`` (1..1024) and momentum 0.5, the others with
+        momentum 0.8; ``learning_rate`` None: max(n_valid / exaggeration / 4, 50).  ``ValueError`` for a knob out of range,
+        ``GnnError`` for a graph that is no such CSR, more than 2^21 rows or an init that is not finite.  Not Barnes-Hut, not
+        perplexity-calibrated, not UMAP; n^2 pairs per iteration."""
+        indptr, col, sim, ok, n = self._csr_arrays(indptr, col, sim, valid)
+        y = self._tsne_init(init, n)
+        n_valid = n if ok is None else int(np.count_nonzero(ok))
+        n_iter, ex_iter, e, lr = _sequence.tsne_params(n_iter, exaggeration_iter, exaggeration, learning_rate, n_valid)
+        layout, z_trace, valid_out = np.empty((n, 2), dtype=np.float32), np.empty(n_iter + 1, dtype=np.uint64), np.empty(n, dtype=np.uint8)
+        check(self.lib.gnn_tsne(self.ctx, indptr.ctypes.data, col.ctypes.data, sim.ctypes.data, None if ok is None else ok.ctypes.data, n, len(col),
+                                y.ctypes.data, n_iter, ex_iter, e, float(lr), layout.ctypes.data, z_trace.ctypes.data, valid_out.ctypes.data))
+        valid_out = valid_out.astype(bool)
+        kl = _sequence.tsne_kl(indptr, col, sim, layout, z_trace[-1], valid_out)
+        return TSNEResult(layout=layout, z_trace=z_trace, kl_divergence=kl, iterations=n_iter, valid=valid_out, n=n, exaggeration_iter=ex_iter,
+                          exaggeration=e, learning_rate=float(lr))
+
+    def tsne_dev(self, indptr_ptr: int, col_ptr, sim_ptr, n: int, nnz: int, init_ptr: int, layout_ptr: int, z_trace_ptr: int, valid_out_ptr: int,
+                 valid_ptr=None, n_valid=None, n_iter=750, exaggeration_iter=250, exaggeration=12.0, learning_rate=None) -> TSNEResult:
+        """``gnn_tsne_dev``: device pointers in - indptr (n + 1 int64), col (nnz int32) and sim (nnz f32) exactly as the graph's fill
+        wrote them, valid (n uint8, or None), init (n x 2 f32) - and out (layout: n x 2 f32; z_trace: n_iter + 1 uint64; valid_out: n
+        uint8); the engine's stream is synchronised once, before the loop is enqueued.  ``n_valid`` (None: n) is what the default
+        ``learning_rate`` counts.  Returns a :class:`TSNEResult` without the arrays."""
+        n_iter, ex_iter, e, lr = _sequence.tsne_params(n_iter, exaggeration_iter, exaggeration, learning_rate, int(n if n_valid is None else n_valid))
+        check(self.lib.gnn_tsne_dev(self.ctx, indptr_ptr, col_ptr, sim_ptr, valid_ptr, int(n), int(nnz), init_ptr, n_iter, ex_iter, e, float(lr),
+                                    layout_ptr, z_trace_ptr, valid_out_ptr))
+        return TSNEResult(layout=None, z_trace=None, kl_divergence=None, iterations=n_iter, valid=None, n=int(n), exaggeration_iter=ex_iter,
+                          exaggeration=e, learning_rate=float(lr))
+
+    def tsne_forces(self, indptr, col, sim, y, valid=None) -> dict:
+        """One evaluation of the layout's forces at ``y`` (float32 (n, 2)) (``gnn_tsne_forces``; the definition is
+        ``sequence.tsne_forces`` over ``sequence.tsne_affinities``): a dict of int64 (n,) ``zi``, ``rx``, ``ry`` (the repulsion's
+        sums in units of 2^-20 and 2^-32), ``ax``, ``ay`` (the attraction's, 2^-32) and ``m2`` (the integer sum of the weights) -
+        what every iteration of :meth:`tsne` computes, by the same kernels."""
+        indptr, col, sim, ok, n = self._csr_arrays(indptr, col, sim, valid)
+        y = self._tsne_init(y, n)
+        out = {k: np.zeros(n, dtype=np.int64) for k in ("zi", "rx", "ry", "ax", "ay")}
+        m2 = C.c_int64(0)
+        check(self.lib.gnn_tsne_forces(self.ctx, indptr.ctypes.data, col.ctypes.data, sim.ctypes.data, None if ok is None else ok.ctypes.data, n,
+                                       len(col), y.ctypes.data, *(a.ctypes.data for a in out.values()), C.addressof(m2)))
+        out["m2"] = int(m2.value)
+        return out
+
+    def tsne_rows(self, rows, k=15, mode="union", weight="similarity", **kw) -> TSNEResult:
+        """The chain in one call: :meth:`knn_graph` of ``rows`` (n, 512) with ``k``, ``mode`` and ``weight``, :meth:`pca` onto two
+        components scaled so that the first has standard deviation 1e-4 over the valid rows as the init (0 at an invalid row), then
+        :meth:`tsne` with ``**kw``."""
+        g = self.knn_graph(rows, k, mode, weight)
+        return g.tsne(self, init=self.tsne_pca_init(rows), **kw)
+
+    def tsne_pca_init(self, rows) -> np.ndarray:
+        """float32 (n, 2): the rows' scores on their first two principal components (:meth:`pca`), scaled in float64 so that the first
+        has standard deviation 1e-4 over the valid rows; 0 at an invalid row, and everywhere when that deviation is 0"""
+        res = self.pca(rows, 2)
+        proj = np.where(res.valid[:, None], res.projection, 0).astype(np.float64)
+        sd = float(proj[res.valid, 0].std()) if res.valid.any() else 0.0
+        return (proj * (1e-4 / sd) if sd > 0 else np.zeros_like(proj)).astype(np.float32)
+
+    def set_tsne_split(self, splits: int):
+        """test aid (``gnn_debug_tsne_split``): the workgroups the repel pass of :meth:`tsne` splits the columns over, at granule
+        boundaries (0: the library's choice); no result depends on it."""
+        check(self.lib.gnn_debug_tsne_split(self.ctx, int(splits)))
+
+    def tsne_pass_ms(self):
+        """measurement only (``gnn_debug_tsne_ms``): with profiling enabled, the HIP-event milliseconds of the last :meth:`tsne` /
+        :meth:`tsne_dev` call - [validate, symmetrise and affinities; the whole loop; the final Z and the results]"""
+        return self._debug_ms(self.lib.gnn_debug_tsne_ms)
 
     # -- label spreading -----------------------------------------------------------------
     def _spread_call(self, fn, graph, n, nnz, knobs, outs, alpha):

@@ -91,7 +91,7 @@ class Outputs:
         # written only when the analysis is requested (the analyses of the per-contig embeddings, ANALYSES below: <stem>.npz and,
         # for all but the neighbours, <stem>.tsv; no counterpart in the reference)
         for stage in self._STAGE.values():
-            for a in EVERY_ANALYSIS:
+            for a in ANALYSES_RUN:
                 setattr(self, f"{stage}nn_{a.name}_output", d / f"{p}_{stage}nn_{a.name}.npz")
                 if a.tsv:
                     setattr(self, f"{stage}nn_{a.name}_tsv_output", d / f"{p}_{stage}nn_{a.name}.tsv")
@@ -901,6 +901,35 @@ def write_knn_graph(npz_path, tsv_path, names_key, names, res, strand="forward")
             fout.write(f"{e['a']}\t{e['b']}\t{e['weight']:.6f}\n")
 
 
+def tsne_requested():
+    """GENOMAD_AMD_TSNE=<integer in [1, 100000]>: main() also writes the exact t-SNE layout of the contigs - that many iterations (the
+    first 250 exaggerated) over the k-nearest-neighbour graph of GENOMAD_AMD_KNN_GRAPH, from the first two principal components of
+    the per-contig encoder embeddings (<prefix>_nn_tsne.npz and .tsv); unset or empty: nothing changes (None).  It lays out the graph
+    of GENOMAD_AMD_KNN_GRAPH=<k>, which must be set with it (main() refuses the one without the other).  Any other value is an error.
+    Returns (n_iter, k, mode, weight) - the last three the graph's request, None without one -, or None."""
+    n_iter = _env_int("GENOMAD_AMD_TSNE", 1, sequence.TSNE_ITER_MAX, "(the iterations of the layout)")
+    if n_iter is None:
+        return None
+    return (n_iter,) + (knn_graph_requested() or (None, None, None))
+
+
+TSNE_TSV_HEADER = "seq_name\tx\ty\n"
+
+
+def write_tsne(npz_path, tsv_path, names_key, names, res, request, strand="forward"):
+    """Both layout files of a stage: the arrays of a TSNEResult with the contig names and the request, and one line per contig - its
+    name and its two coordinates, NA for a contig without a valid embedding."""
+    np.savez_compressed(npz_path, **{names_key: names, "n_iter": np.int64(request[0]), "k": np.int64(request[1]), "mode": np.array(request[2]),
+                                     "weight": np.array(request[3]), "metric": np.array(NEIGHBOUR_METRIC), "init": np.array("pca"),
+                                     "exaggeration_iter": np.int64(res.exaggeration_iter), "exaggeration": np.float64(res.exaggeration),
+                                     "learning_rate": np.float64(res.learning_rate), "layout": res.layout, "z_trace": res.z_trace,
+                                     "kl_divergence": np.float64(res.kl_divergence), "valid": res.valid, **_strand_entry(strand)})
+    with open(tsv_path, "w") as fout:
+        fout.write(TSNE_TSV_HEADER)
+        for name, xy, ok in zip(names, res.layout, res.valid):
+            fout.write(f"{name}\t{xy[0]:.6f}\t{xy[1]:.6f}\n" if ok else f"{name}\tNA\tNA\n")
+
+
 MCL_SELECT_DEFAULT = 256
 
 
@@ -1460,7 +1489,7 @@ def _encode(fasta_path, enc_dir: Path, window_id_path: Path, single_window: bool
 
 
 # ---- the analyses of the gathered per-contig embeddings ------------------------------------------------------------------------------
-# Sixteen analyses (EVERY_ANALYSIS) follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
+# Seventeen analyses (ANALYSES_RUN) follow one rule in main() (the docstring of its stage_device); a record of ANALYSES holds what differs between them:
 #   name      the stem of its files, <prefix>_nn_<name>.npz and - where ``tsv`` - .tsv
 #   switch    the environment variable that requests it; ``request()`` reads it (and its companions): the request, or None
 #   needs     the middle clause of the message that refuses the switch without GENOMAD_AMD_EMBEDDINGS=1
@@ -1602,7 +1631,7 @@ ANALYSES = (        # in the order they run, which is the order of the log lines
 )
 
 # The fifteenth analysis.  It stands in a table of its own behind ANALYSES, so that table stays what the earlier analyses' tests
-# count; main() walks EVERY_ANALYSIS (below), and everything said of a record above holds for these.
+# count; main() walks ANALYSES_RUN (below), and everything said of a record above holds for these.
 MORE_ANALYSES = (
     Analysis("communities", "GENOMAD_AMD_COMMUNITIES", communities_requested,
              "modularity is optimised over the similarity graph of the per-contig encoder embeddings",
@@ -1617,7 +1646,7 @@ MORE_ANALYSES = (
 ALL_ANALYSES = ANALYSES + MORE_ANALYSES
 
 # The sixteenth analysis, in a third table for the same reason: ALL_ANALYSES stays what the communities' tests count.  main() and the
-# file table of Outputs walk EVERY_ANALYSIS, and everything said of a record above holds for this one.
+# file table of Outputs walk ANALYSES_RUN (below), and everything said of a record above holds for this one.
 KNN_ANALYSES = (
     Analysis("knn_graph", "GENOMAD_AMD_KNN_GRAPH", knn_graph_requested,
              "the neighbour lists are those of the per-contig encoder embeddings", (("k", int), ("mode", str), ("weight", str)),
@@ -1628,6 +1657,22 @@ KNN_ANALYSES = (
                                         f"{int(res.valid.sum())} {what}s, {int(np.asarray(res.mutual).sum())} of them mutual")),
 )
 EVERY_ANALYSIS = ALL_ANALYSES + KNN_ANALYSES
+
+# The seventeenth analysis and the first consumer of the k-nearest-neighbour graph, in a fourth table for the same reason:
+# EVERY_ANALYSIS stays what the graph's tests count.  main() and the file table of Outputs walk ANALYSES_RUN, and everything said of a
+# record above holds for this one.
+TSNE_ANALYSES = (
+    Analysis("tsne", "GENOMAD_AMD_TSNE", tsne_requested,
+             "the layout is that of the k-nearest-neighbour graph of the per-contig encoder embeddings",
+             (("n_iter", int), ("k", int), ("mode", str), ("weight", str)), "t-SNE layout of the {what}s",
+             lambda eng, emb, r, ctx: eng.tsne_rows(emb, r[1], r[2], r[3], n_iter=r[0]),      # the graph computed again, the init by PCA
+             lambda npz, tsv, key, names, res, strand, ctx: write_tsne(npz, tsv, key, names, res, ctx.request, strand),
+             lambda res, r, what, ctx: (f"{r[0]} iterations over the {r[1]}-nearest-neighbour graph, {r[2]}, weighted by {r[3]}, from the first "
+                                        f"two principal components: {int(np.asarray(res.valid).sum())} {what}s placed, "
+                                        f"Kullback-Leibler divergence {res.kl_divergence:.4f}"),
+             errors=(ValueError, GnnError), advice="Unset GENOMAD_AMD_TSNE.", after="knn_graph"),      # fewer than two valid embeddings; more than 2^21 contigs
+)
+ANALYSES_RUN = EVERY_ANALYSIS + TSNE_ANALYSES
 
 
 def _resumes(a, npz, tsv, request, strand, base) -> bool:
@@ -1659,8 +1704,8 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
     attribution_bin = attribution_bin_requested()
     region_penalty = region_penalty_requested()
     region_embeddings = region_embeddings_requested()
-    requests = {a.name: a.request() for a in EVERY_ANALYSIS}
-    base_paths = {a.name: a.base.request() for a in EVERY_ANALYSIS if a.base is not None}
+    requests = {a.name: a.request() for a in ANALYSES_RUN}
+    base_paths = {a.name: a.base.request() for a in ANALYSES_RUN if a.base is not None}
     input_path, output_path = Path(input_path), Path(output_path)
     if _comm is not None:
         comm = _comm
@@ -1695,13 +1740,13 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         console.error("GENOMAD_AMD_REGION_EMBEDDINGS=1 needs GENOMAD_AMD_REGION_PENALTY: the embeddings are those of the regions called "
                       "along the score tracks. Set GENOMAD_AMD_REGION_PENALTY or unset GENOMAD_AMD_REGION_EMBEDDINGS.")
         sys.exit(1)
-    for a in EVERY_ANALYSIS:
+    for a in ANALYSES_RUN:
         requested = requests[a.name] is not None
         if a.base is None and requested and not embeddings:
             console.error(f"{a.switch} needs GENOMAD_AMD_EMBEDDINGS=1: {a.needs}. Set GENOMAD_AMD_EMBEDDINGS=1 or unset {a.switch}.")
             sys.exit(1)
         if requested and a.after is not None and requests[a.after] is None:
-            other = next(b.switch for b in EVERY_ANALYSIS if b.name == a.after)
+            other = next(b.switch for b in ANALYSES_RUN if b.name == a.after)
             console.error(f"{a.switch} needs {other}: {a.needs}. Set {other} or unset {a.switch}.")
             sys.exit(1)
         if a.base is not None and (requested != (base_paths[a.name] is not None) or (requested and not embeddings)):
@@ -1736,7 +1781,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
         sys.exit(1)
 
     bases = {}                       # what every requested reference's loader returned, read before any classification starts
-    for a in EVERY_ANALYSIS:
+    for a in ANALYSES_RUN:
         if a.base is not None and requests[a.name] is not None:
             try:
                 bases[a.name] = a.base.load(base_paths[a.name], strand)
@@ -1917,7 +1962,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                                  and _request_of_file(regions_path, (("stride", int), ("penalty", float))) == regions_request
                                  and (regions_request is None) == (not regions_tsv_path.exists())
                                  and _request_of_file(region_emb_file, (("stride", int), ("penalty", float), ("strand", str))) == region_emb_request
-                                 and all(_resumes(a, *outputs.files(what, a.name), requests[a.name], strand, bases.get(a.name)) for a in EVERY_ANALYSIS)
+                                 and all(_resumes(a, *outputs.files(what, a.name), requests[a.name], strand, bases.get(a.name)) for a in ANALYSES_RUN)
                                  and (emb_path is None or (emb_path.exists() and _npz_strand(emb_path) == strand))
                                  and (scan_path is None or (_scan_file_has_stride(scan_path, scan_stride)
                                                             and _npz_strand(scan_path) == strand)))   # :284-292
@@ -2096,7 +2141,7 @@ def main(input_path, output_path, single_window, batch_size, restart, threads, v
                     console.log(f"Encoder embeddings of the {len(mine[0])} regions of the {what}s written to {region_emb_path.name}.")
                 elif region_emb_file.exists():      # likewise
                     region_emb_file.unlink()
-                for a in EVERY_ANALYSIS:
+                for a in ANALYSES_RUN:
                     npz, tsv = outputs.files(what, a.name)
                     request = requests[a.name]
                     if request is None:             # likewise, both files

@@ -2782,6 +2782,173 @@ def knn_graph_table(indptr, col, sim, mutual, names=None):
             for i, j, s, m in zip(a, b, np.asarray(sim), np.asarray(mutual))]
 
 
+TSNE_N_MAX = 1 << 21               # Z < 2^63: DESIGN.md section 5x
+TSNE_ITER_MAX = 100000
+TSNE_GRANULE = 256                 # columns of one float32 chain, aligned to the column index
+TSNE_Z_UNIT = float(1 << 20)       # a granule's sum of q in units of 2^-20
+TSNE_F_UNIT = float(1 << 32)       # forces in units of 2^-32
+TSNE_EXAGGERATION_MAX = 1024.0
+TSNE_LEARNING_RATE_MAX = float(1 << 20)
+TSNE_FIELDS = ("layout", "z_trace", "iterations", "valid")
+_TSNE_BLOCK_CELLS = 1 << 22        # cells of the definition's row blocks; no result depends on it
+
+
+def tsne_init(n, offset=0) -> np.ndarray:
+    """The layout t-SNE starts from when none is given: float32 (n, 2), coordinate k = 2 i + c the (k + offset)-th output of splitmix64
+    from seed 0 - z = (k + offset + 1) * 0x9E3779B97F4A7C15, z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) *
+    0x94D049BB133111EB, z ^= z >> 31, all mod 2^64 - whose top 24 bits u map to float32((u / 2^23 - 1) * 1e-4), in [-1e-4, 1e-4).  No
+    random state: the same n gives the same bits everywhere."""
+    n = _whole(n, "n", 0, TSNE_N_MAX)
+    z = (np.arange(2 * n, dtype=np.uint64) + np.uint64(_whole(offset, "offset", 0, 1 << 62) + 1)) * np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    z = z ^ (z >> np.uint64(31))
+    u = (z >> np.uint64(40)).astype(np.float64)
+    return ((u / float(1 << 23) - 1.0) * 1e-4).astype(np.float32).reshape(n, 2)
+
+
+def tsne_params(n_iter=750, exaggeration_iter=250, exaggeration=12.0, learning_rate=None, n_valid=0):
+    """(n_iter, exaggeration_iter, exaggeration as a float, learning_rate as a float32) as the library takes them; a ``ValueError`` for
+    one out of range.  ``learning_rate`` None: max(n_valid / exaggeration / 4, 50), scikit-learn's "auto"."""
+    n_iter = _whole(n_iter, "n_iter", 0, TSNE_ITER_MAX)
+    exaggeration_iter = _whole(exaggeration_iter, "exaggeration_iter", 0, TSNE_ITER_MAX)
+    try:
+        e = float(exaggeration)
+        lr = np.float32(max(n_valid / e / 4.0, 50.0) if learning_rate is None else learning_rate)
+    except (TypeError, ValueError, ZeroDivisionError):
+        raise ValueError(f"exaggeration {exaggeration!r} and learning_rate {learning_rate!r}: floats are required") from None
+    if not 1.0 <= e <= TSNE_EXAGGERATION_MAX:
+        raise ValueError(f"exaggeration {exaggeration!r} is outside [1, 1024]")
+    if not 0.0 < lr <= TSNE_LEARNING_RATE_MAX:
+        raise ValueError(f"learning_rate {learning_rate!r} is outside (0, 2^20]")
+    return n_iter, exaggeration_iter, e, lr
+
+
+def tsne_affinities(indptr, col, sim, valid=None):
+    """The affinities t-SNE attracts by, from the upper-triangle CSR :func:`threshold_graph` / :func:`knn_graph` return: (n, i, j, p, q,
+    m2, valid).  The weights are :func:`mcl_weights`': q = rint(float64(float32(sim)) * 2^24), an entry with q <= 0 or an invalid end
+    does not exist.  Every entry stands in both orientations (i, j) and (j, i), parallel entries stay separate entries; ``m2`` is the
+    integer sum of q over all of them and p = float32(float64(q) / float64(m2)).  ``ValueError`` as there, and for more than 2^21 rows."""
+    n, a, b, q, ok = mcl_weights(indptr, col, sim, valid)
+    if n > TSNE_N_MAX:
+        raise ValueError(f"{n} rows: at most 2^21 are supported")
+    i, j, q = np.concatenate([a, b]), np.concatenate([b, a]), np.concatenate([q, q]).astype(np.int64)
+    m2 = int(q.sum())
+    p = (q.astype(np.float64) / np.float64(m2)).astype(np.float32) if m2 else np.zeros(0, dtype=np.float32)
+    return n, i, j, p, q, m2, ok
+
+
+def _tsne_q(dx, dy, m):
+    """m / (1 + (dx dx + dy dy)) in float32, one rounding per operation"""
+    return m / (np.float32(1.0) + (dx * dx + dy * dy))
+
+
+def _tsne_image(chain, unit):
+    return np.rint(chain.astype(np.float64) * unit).astype(np.int64)
+
+
+def tsne_forces(y, i, j, p, valid, attract=True):
+    """One evaluation of t-SNE's forces at the layout ``y`` (float32 (n, 2), finite at every valid row) for the entries (i, j, p) of
+    :func:`tsne_affinities`: int64 (zi, rx, ry, ax, ay), each (n,) and 0 at an invalid row.  Every float32 operation is a single IEEE
+    operation.  Repulsion, row r against column c: dx = x_r - x_c, dy = y_r - y_c, q = 1 / (1 + (dx dx + dy dy)), and q = 0 where
+    c == r, c is invalid or c is padding behind n; for every granule of 256 columns, aligned to the column index, three float32 chains
+    in ascending column order - cz += q, cx += (q q) dx, cy += (q q) dy - and at its end zi += rint(float64(cz) * 2^20), rx +=
+    rint(float64(cx) * 2^32), ry likewise.  Attraction, per entry: ax_i += rint(float64((p q) dx) * 2^32), ay likewise - integer adds,
+    in any order."""
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    ok = np.asarray(valid, dtype=bool)
+    n = len(ok)
+    if y.shape != (n, 2):
+        raise ValueError(f"the layout must be ({n}, 2)")
+    granules = -(-n // TSNE_GRANULE)
+    pad = granules * TSNE_GRANULE
+    cx_, cy_, m = (np.zeros(pad, dtype=np.float32) for _ in range(3))
+    cx_[:n], cy_[:n], m[:n] = np.where(ok, y[:, 0], 0), np.where(ok, y[:, 1], 0), ok
+    zi, rx, ry, ax, ay = (np.zeros(n, dtype=np.int64) for _ in range(5))
+    rows = np.flatnonzero(ok)
+    block = max(1, _TSNE_BLOCK_CELLS // max(pad, 1))
+    for s in range(0, len(rows), block):
+        r = rows[s:s + block]
+        dx, dy = y[r, 0][:, None] - cx_[None, :], y[r, 1][:, None] - cy_[None, :]
+        q = _tsne_q(dx, dy, m[None, :])
+        q[np.arange(len(r)), r] = 0
+        q2 = q * q
+        for out, term, unit in ((zi, q, TSNE_Z_UNIT), (rx, q2 * dx, TSNE_F_UNIT), (ry, q2 * dy, TSNE_F_UNIT)):
+            # np.add.accumulate adds one element at a time, in the array's own type: the chain
+            chain = np.add.accumulate(term.reshape(len(r), granules, TSNE_GRANULE), axis=2, dtype=np.float32)[:, :, -1]
+            out[r] = _tsne_image(chain, unit).sum(axis=1)
+    if attract and len(i):
+        dx, dy = y[i, 0] - y[j, 0], y[i, 1] - y[j, 1]
+        pq = np.asarray(p, dtype=np.float32) * _tsne_q(dx, dy, np.float32(1.0))
+        np.add.at(ax, i, _tsne_image(pq * dx, TSNE_F_UNIT))
+        np.add.at(ay, i, _tsne_image(pq * dy, TSNE_F_UNIT))
+    return zi, rx, ry, ax, ay
+
+
+def tsne_layout(indptr, col, sim, init, valid=None, n_iter=750, exaggeration_iter=250, exaggeration=12.0, learning_rate=None):
+    """The exact t-SNE layout of a similarity graph, spelled out (the definition ``gnn_tsne`` computes on the device, bit for bit;
+    DESIGN.md section 5x).  The graph is an upper-triangle CSR as :func:`threshold_graph` / :func:`knn_graph` return it, ``valid`` a
+    bool per row (None: all), ``init`` the float32 (n, 2) layout it starts from (finite at every valid row: ``ValueError`` otherwise).
+    The affinities are :func:`tsne_affinities`' - the graph's own weights, not perplexity-calibrated ones.
+
+    Iteration ``it`` = 0 .. n_iter - 1, with Y in float32: the forces of :func:`tsne_forces`; Z = sum zi, an integer; in float64,
+    rounded to float32 once, g = 4 (e A / 2^32 - (R / 2^32) / (Z / 2^20)) with e = ``exaggeration`` while it < ``exaggeration_iter``
+    and 1 from there on, the second term 0 where Z == 0.  Then elementwise in float32: gain += 0.2 where g and the previous update have
+    strictly opposite signs (g > 0 and upd < 0, or g < 0 and upd > 0), otherwise gain *= 0.8, and gain is at least 0.01 (it starts at
+    1, upd at 0); upd = mom upd - lr (gain g) with mom = 0.5 while it < ``exaggeration_iter`` and 0.8 from there on; Y += upd.  There is
+    no recentring and no early end.  ``learning_rate`` None: max(n_valid / exaggeration / 4, 50).
+
+    Returns a dict: ``layout`` (float32 (n, 2), NaN at an invalid row), ``z_trace`` (uint64 (n_iter + 1,): the Z of every iterate, the
+    final one included), ``iterations`` and ``valid``."""
+    n, i, j, p, _, _, ok = tsne_affinities(indptr, col, sim, valid)
+    n_iter, exaggeration_iter, e_early, lr = tsne_params(n_iter, exaggeration_iter, exaggeration, learning_rate, int(ok.sum()))
+    with np.errstate(over="ignore"):
+        y = np.array(init, dtype=np.float32)
+    if y.shape != (n, 2):
+        raise ValueError(f"init must be ({n}, 2)")
+    if not np.isfinite(y[ok]).all():
+        raise ValueError("init: every valid row must be finite")
+    y[~ok] = np.nan
+    gain, upd = np.ones((n, 2), dtype=np.float32), np.zeros((n, 2), dtype=np.float32)
+    z_trace = np.zeros(n_iter + 1, dtype=np.uint64)
+    for it in range(n_iter + 1):
+        zi, rx, ry, ax, ay = tsne_forces(y, i, j, p, ok, attract=it < n_iter)
+        z = int(zi.sum())
+        z_trace[it] = z
+        if it == n_iter:
+            break
+        early = it < exaggeration_iter
+        att = (e_early if early else 1.0) * (np.stack([ax, ay], axis=1).astype(np.float64) / TSNE_F_UNIT)
+        rep = (np.stack([rx, ry], axis=1).astype(np.float64) / TSNE_F_UNIT) / (float(z) / TSNE_Z_UNIT) if z else 0.0
+        g = (4.0 * (att - rep)).astype(np.float32)
+        opposite = ((g > 0) & (upd < 0)) | ((g < 0) & (upd > 0))
+        gain = np.maximum(np.where(opposite, gain + np.float32(0.2), gain * np.float32(0.8)), np.float32(0.01))
+        upd = np.float32(0.5 if early else 0.8) * upd - lr * (gain * g)
+        y = y + upd
+    return {"layout": y, "z_trace": z_trace, "iterations": n_iter, "valid": ok}
+
+
+def tsne_kl(indptr, col, sim, layout, z, valid=None) -> float:
+    """The Kullback-Leibler divergence of a layout from the graph's affinities, in float64 and O(entries): sum over the entries of
+    p (log p - log q) + log(z / 2^20), with q = 1 / (1 + |y_i - y_j|^2) as :func:`tsne_forces` computes it in float32 and ``z`` the
+    layout's integer Z (``z_trace[-1]``).  A graph without an entry has 0."""
+    _, i, j, p, _, m2, ok = tsne_affinities(indptr, col, sim, valid)
+    if not m2 or int(z) <= 0:
+        return 0.0
+    y = np.ascontiguousarray(layout, dtype=np.float32)
+    q = _tsne_q(y[i, 0] - y[j, 0], y[i, 1] - y[j, 1], np.float32(1.0)).astype(np.float64)
+    p = p.astype(np.float64)
+    keep = p > 0
+    return float((p[keep] * (np.log(p[keep]) - np.log(q[keep]))).sum() + np.log(float(int(z)) / TSNE_Z_UNIT))
+
+
+def tsne_table(layout, valid, names=None):
+    """One record per row: ``name`` (the index without ``names``), ``x`` and ``y`` (None at an invalid row)"""
+    name = _namer(names)
+    return [{"name": name(i), "x": float(xy[0]) if ok else None, "y": float(xy[1]) if ok else None}
+            for i, (xy, ok) in enumerate(zip(np.asarray(layout), np.asarray(valid, dtype=bool)))]
+
+
 def prefix_of(input_path: Path) -> str:
     """nn_classification.py:106-108: stem, minus one more extension if the file is compressed."""
     prefix = Path(input_path).stem

@@ -1107,6 +1107,56 @@ int gnn_debug_knn_graph_classes(gnn_ctx* ctx, int64_t* rows_out);
  * [fill, order, finish]; *n_out = the figures recorded (0 for n == 0 or without profiling), at most `capacity` are written. */
 int gnn_debug_knn_graph_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
 
+/* ---- t-SNE layout of a similarity graph: exact, on the device ----------------------------------------------
+ * "Where does every row lie in a 2-D picture of the graph": t-SNE's gradient descent with the graph's own weights as the affinities and
+ * the exact all-pairs repulsion, from a given init.  The definition is sequence.tsne_layout; every output equals it bit for bit.
+ *   graph     gnn_mcl's: an upper-triangle CSR with sim (f32, finite, < 64) and valid (uint8 [n], or NULL); exactly what
+ *             gnn_graph_fill / gnn_knn_graph_fill write.  q = rint((f64)sim * 2^24); an entry with q <= 0 or an invalid end does not
+ *             exist; an edge stands at both its ends and parallel entries stay separate.  M2 = the integer sum over all of them,
+ *             p = (f32)((f64)q / (f64)M2).
+ *   iterate   Y (f32 [n][2]) starts as `init`.  Per iteration, every f32 operation one IEEE operation, nothing fused: for row i and
+ *             column j, dx = x_i - x_j, dy = y_i - y_j, qij = 1 / (1 + (dx dx + dy dy)) (0 where j = i, j is invalid or beyond n); per
+ *             granule of 256 columns (aligned to the column index) three f32 chains in ascending column order - cz += qij,
+ *             cx += (qij qij) dx, cy likewise - whose ends become integers: Zi += rint((f64)cz * 2^20), RX += rint((f64)cx * 2^32), RY
+ *             likewise; Z = the sum of Zi.  Per entry (i, j): AX_i += rint((f64)((p qij) dx) * 2^32), AY likewise.  In f64, rounded
+ *             to f32 once: g = 4 (e A / 2^32 - (R / 2^32) / (Z / 2^20)), e = `exaggeration` before iteration `exaggeration_iter` and 1
+ *             from it on, the second term 0 where Z = 0.  In f32: gain += 0.2 where g and the previous update have strictly opposite
+ *             signs, else gain *= 0.8, at least 0.01 (it starts at 1); upd = mom upd - lr (gain g), mom = 0.5 with e and 0.8 behind;
+ *             Y += upd.  No recentring, no early end.
+ *   outputs   layout (f32 [n][2]; NaN at an invalid row), z_trace (uint64 [n_iter + 1]: Z of every iterate, the final one included),
+ *             valid_out (uint8 [n]).
+ *   ranges    0 <= n <= 2^21 (Z < 2^63), n_iter and exaggeration_iter in [0, 100000], exaggeration in [1, 1024], learning_rate in
+ *             (0, 2^20]: GNN_ERR_ARG with the value and the range - checked before the ctx is looked at.  A graph that is no such CSR
+ *             and an init that is not finite at a valid row: GNN_ERR_ARG behind the one synchronise, before an output is written.
+ *             n == 0: z_trace is n_iter + 1 zeros.
+ *   exact     a granule's chains are the same whoever runs them and whatever the grid; everything behind them is a sum of integers:
+ *             no output bit depends on gnn_debug_tsne_split, the grid or the order the graph's entries arrive in.
+ * gnn_tsne_forces*: one evaluation at `y` (finite at every valid row) - zi, rx, ry, ax, ay (int64 [n]; 0 at an invalid row) and *m2.
+ * What it is not: not Barnes-Hut nor FFT-interpolated; no perplexity-calibrated affinities; not UMAP; no transform of new rows; not
+ * multi-GPU.  Cost: n^2 pairs per iteration.
+ * Device memory, persistent in the ctx and grow-only: 12 B per entry at both ends, 89 B per row, 8 B per iterate (the host entry
+ * points: + the graph, the init and the results).  Nothing is n x n.
+ * gnn_tsne / gnn_tsne_forces: host pointers, synchronous.  gnn_tsne_dev / gnn_tsne_forces_dev: device pointers; the stream is
+ * synchronised once, for the verdict on the graph and the init, and the whole loop is enqueued behind it without another read. */
+int gnn_tsne(gnn_ctx* ctx, const int64_t* indptr_host, const int32_t* col_host, const float* sim_host, const uint8_t* valid_host_or_null,
+             int64_t n, int64_t nnz, const float* init_host, int n_iter, int exaggeration_iter, double exaggeration, float learning_rate,
+             float* layout_host, uint64_t* z_trace_host, uint8_t* valid_out_host);
+int gnn_tsne_dev(gnn_ctx* ctx, const int64_t* indptr_dev, const int32_t* col_dev, const float* sim_dev, const uint8_t* valid_dev_or_null,
+                 int64_t n, int64_t nnz, const float* init_dev, int n_iter, int exaggeration_iter, double exaggeration, float learning_rate,
+                 float* layout_dev, uint64_t* z_trace_dev, uint8_t* valid_out_dev);
+int gnn_tsne_forces(gnn_ctx* ctx, const int64_t* indptr_host, const int32_t* col_host, const float* sim_host,
+                    const uint8_t* valid_host_or_null, int64_t n, int64_t nnz, const float* y_host, int64_t* zi_host, int64_t* rx_host,
+                    int64_t* ry_host, int64_t* ax_host, int64_t* ay_host, int64_t* m2_host);
+int gnn_tsne_forces_dev(gnn_ctx* ctx, const int64_t* indptr_dev, const int32_t* col_dev, const float* sim_dev,
+                        const uint8_t* valid_dev_or_null, int64_t n, int64_t nnz, const float* y_dev, int64_t* zi_dev, int64_t* rx_dev,
+                        int64_t* ry_dev, int64_t* ax_dev, int64_t* ay_dev, int64_t* m2_dev);
+/* test aid; no result depends on it: the workgroups the repel pass splits the columns over, at granule boundaries (1 .. 65535; 0: the
+ * library's choice). */
+int gnn_debug_tsne_split(gnn_ctx* ctx, int splits);
+/* measurement only: with gnn_profile_enable on, the HIP-event milliseconds of the ctx's last gnn_tsne* call - [0] validate, symmetrise
+ * and affinities, [1] the whole loop, [2] the final Z and the results; *n_out = the figures recorded, at most `capacity` are written. */
+int gnn_debug_tsne_ms(gnn_ctx* ctx, double* ms_out, int64_t capacity, int64_t* n_out);
+
 /* ---- matches against a reference: the bipartite similarity graph query x base ------------------------------
  * "Which reference rows is every new row within the threshold of, all of them": every pair (i, j) of a valid query row i and a valid
  * base row j with sim(i, j) >= threshold and its similarity, as a CSR by query row.  The passes, the kernel, the workspace and the
